@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the hot path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+K timed steps follow W warm-up steps; `ms_per_step` in the result line is the wall time of the K steps / K.  With --dump-outputs, rank 0
+writes what the last timed step returned -- o, dq, dk, dv on a fixed sample of (batch, head) slices, float32 -- as DIR/<name>.npy.
+The inputs are seeded, so the same arguments give the same inputs on every run.
 
 A "step" is one forward + backward of flash_cosine_sim_attention on one batch of synthetic
 input at the configuration the metric is quoted on (BASELINE.json configs[2] / SURVEY "C3"):
@@ -48,6 +52,29 @@ def lib_sha256():
     import hashlib
     from flash_cosine_sim_attention_amd import _lib
     return hashlib.sha256(open(_lib.LIB_PATH, "rb").read()).hexdigest()
+
+
+DUMP_SLICES = 8                   # --dump-outputs: 8 of the 32 (batch, head) slices, 4 arrays x 8 x 4096 x 64 float32 = 32 MB
+DUMP_SEED = 0
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_sample(outputs, n_slices=DUMP_SLICES, seed=DUMP_SEED):
+    """{name: (B, H, ...) tensor} -> ({name: float32 array (n_slices, ...)}, flat indices b * H + h): the same (batch, head) slices of
+    every output, chosen by a fixed seed so that two runs or two builds dump the same elements."""
+    B, H = next(iter(outputs.values())).shape[:2]
+    picked = torch.randperm(B * H, generator=torch.Generator().manual_seed(seed))[:n_slices].sort().values
+    arrays = {name: t.detach().reshape(B * H, *t.shape[2:])[picked.to(t.device)].float().cpu().numpy() for name, t in outputs.items()}
+    return arrays, picked.tolist()
+
+
+def write_dump(dirname, arrays):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, "dump of %d bytes exceeds the %d byte limit" % (total, DUMP_LIMIT_BYTES)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def aggregate_over_ranks(elapsed_s, flops_local, dist=None, device="cpu"):
@@ -261,7 +288,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-events", action="store_true", help="skip the instrumented pass for the roofline object")
     ap.add_argument("--no-extra-configs", action="store_true", help="skip the C2 / C4 / C5 / ... entries and the reference-protocol leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned (o, dq, dk, dv; a fixed sample of "
+                                                          "(batch, head) slices, float32) as DIR/<name>.npy, to compare two builds")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -312,12 +343,22 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        o_last = step()
     barrier()
     elapsed = time.perf_counter() - t0
     elapsed, flops_per_step_all_ranks = aggregate_over_ranks(elapsed, flops(w), dist, "cuda")
     ms_per_step = elapsed / args.steps * 1e3
     value = flops_per_step_all_ranks / (ms_per_step * 1e-3) / 1e12
+
+    # ---- what the last timed step returned to its caller, before any later pass overwrites the gradients ----------------------
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        arrays, picked = dump_sample({"o": o_last, "dq": q.grad, "dk": k.grad, "dv": v.grad})
+        write_dump(args.dump_outputs, arrays)
+        dumped = {"dir": args.dump_outputs, "arrays": {n: list(a.shape) for n, a in arrays.items()}, "dtype": "float32",
+                  "slices_bh": [[i // w["H"], i % w["H"]] for i in picked],
+                  "what": "o and q/k/v gradients of the last timed step, the same %d (batch, head) slices of each (seed %d)"
+                          % (DUMP_SLICES, DUMP_SEED)}
 
     # ---- roofline: dominant kernel, timed with HIP events on the launch stream (library hook) ----------
     roofline = None
@@ -497,6 +538,7 @@ def main():
             "configs": configs,
             "reference_protocol": ref_proto,
             "small_n_f16_causal_fwdbwd": small,
+            "dump_outputs": dumped,
         }
         print(json.dumps(out))
     if dist is not None:

@@ -11,6 +11,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # FCSA_LIB selects an alternative build of the same ABI (kernel-tuning A/B runs, tools/ab_bench.py)
@@ -88,7 +89,8 @@ _lib = None
 
 def build(verbose: bool = False) -> str:
     """Compile libfcsa_hip.so for gfx950 with hipcc (works without a GPU)."""
-    cmd = ["make", "-C", CSRC, "-j", str(min(8, os.cpu_count() or 1))]
+    # PYTHON: the binding compiles against the torch of THIS interpreter, not whatever `python3` is first on PATH (as setup.py does)
+    cmd = ["make", "-C", CSRC, "-j", str(min(8, os.cpu_count() or 1)), "PYTHON=" + sys.executable]
     res = subprocess.run(cmd, capture_output=True, text=True)
     if verbose or res.returncode != 0:
         print(res.stdout)
