@@ -82,7 +82,7 @@ KernelStat = _STRUCTS["fcsa_kernel_stat"]
 
 
 EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fcsa_forward_workspace_bytes", "fcsa_forward_needs_qn",
-           "fcsa_l2norm", "fcsa_debug", "fcsa_debug_forward_form", "fcsa_last_error", "fcsa_profile_enable", "fcsa_profile_collect")
+           "fcsa_l2norm", "fcsa_debug", "fcsa_debug_forward_form", "fcsa_debug_kv_group_form", "fcsa_last_error", "fcsa_profile_enable", "fcsa_profile_collect")
 
 _lib = None
 
@@ -128,6 +128,8 @@ def load():
     lib.fcsa_debug.restype = C.c_int
     lib.fcsa_debug_forward_form.argtypes = [C.c_int32]
     lib.fcsa_debug_forward_form.restype = C.c_int
+    lib.fcsa_debug_kv_group_form.argtypes = [C.c_int32]
+    lib.fcsa_debug_kv_group_form.restype = C.c_int
     lib.fcsa_profile_enable.argtypes = [C.c_int32]
     lib.fcsa_profile_enable.restype = C.c_int
     lib.fcsa_profile_collect.argtypes = [C.POINTER(KernelStat), C.c_int32]
@@ -152,6 +154,13 @@ def forward_form(form: int) -> int:
     forward, < 0 = query.  Returns the previous setting.  (Applies to the library THIS module loaded -- the one the compiled binding
     links, unless FCSA_LIB / fcsa_torch_use_library routed the ops elsewhere.)"""
     return int(load().fcsa_debug_forward_form(int(form)))
+
+
+def kv_group_form(form: int) -> int:
+    """Debug knob of the C ABI (include/fcsa.h, fcsa_debug_kv_group_form): which dK/dV form grouped-query problems take.  1 = automatic,
+    0 = never the group-sweep kernel (per-query-head slabs + finalize), 2 = the sweep wherever it is compiled, < 0 = query.  Returns the
+    previous setting (same library caveat as forward_form)."""
+    return int(load().fcsa_debug_kv_group_form(int(form)))
 
 
 def source_sha256() -> str:

@@ -34,6 +34,18 @@ def normalise_groups(t: torch.Tensor, groups: int = 1) -> torch.Tensor:
     return (g / length.clamp_min(floor)).reshape(t.shape).to(t.dtype)
 
 
+def expand_kv_heads(t: torch.Tensor, heads: int) -> torch.Tensor:
+    """K or V of shape [B, Hk, M, D] for `heads` query heads.  Hk == heads and Hk == 1 (single-headed: broadcast) are returned as
+    they are; grouped-query K/V (1 < Hk < heads, heads % Hk == 0) is repeated so that query head h reads K/V head h // (heads // Hk),
+    the repeat_interleave convention of torch's scaled_dot_product_attention(enable_gqa=True)."""
+    hk = t.shape[1]
+    if hk == heads or hk == 1:
+        return t
+    if hk < 1 or heads % hk:
+        raise ValueError(f"k/v heads must divide q heads ({heads}): grouped-query attention needs H % Hk == 0, got Hk = {hk}")
+    return t.repeat_interleave(heads // hk, dim=1)
+
+
 def attention_forward_cpu(q, k, v, mask=None, attn_bias=None, scale=8.0, groups=1, causal=False, l2norm_qk=True,
                           attn_bias_batch_dim=False, row_block=256, key_block=1024):
     """Forward-only blockwise cosine-sim attention on host tensors.  Same argument meaning as the GPU operator."""
@@ -54,9 +66,10 @@ def attention_forward_cpu(q, k, v, mask=None, attn_bias=None, scale=8.0, groups=
         raise ValueError(f"q must have 3 or 4 dimensions, got {q.dim()}")
     if l2norm_qk:
         q, k = normalise_groups(q, groups), normalise_groups(k, groups)
-    k4 = k.unsqueeze(1) if k.dim() == 3 else k           # [B, 1 or H, M, D]: single-headed K/V broadcast over heads
-    v4 = v.unsqueeze(1) if v.dim() == 3 else v
     B, H, N, D = q.shape
+    # [B, 1 or H, M, D]: single-headed K/V broadcast over heads, grouped-query K/V repeated over each group
+    k4 = expand_kv_heads(k.unsqueeze(1) if k.dim() == 3 else k, H)
+    v4 = expand_kv_heads(v.unsqueeze(1) if v.dim() == 3 else v, H)
     M = k4.shape[2]
     qf, kt, vf = q.float(), k4.float().transpose(-1, -2), v4.float()
     bias = None

@@ -361,8 +361,9 @@ __global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const Bw
     int m0_, nt_;
     geometry(pass_, m0_, nt_);
     if constexpr (DMA) {
-      stk = dk_.open(p.k.p + (int64_t)b_ * p.k.sb + (int64_t)h_ * p.k.sh + (int64_t)k_lo * p.k.sn, p.k.sn, Mk);
-      stv = dv_.open(p.v.p + (int64_t)b_ * p.v.sb + (int64_t)h_ * p.v.sh + (int64_t)k_lo * p.v.sn, p.v.sn, Mk);
+      const int hk_ = h_ / p.kv_group;      // K/V head of the query head
+      stk = dk_.open(p.k.p + (int64_t)b_ * p.k.sb + (int64_t)hk_ * p.k.sh + (int64_t)k_lo * p.k.sn, p.k.sn, Mk);
+      stv = dv_.open(p.v.p + (int64_t)b_ * p.v.sb + (int64_t)hk_ * p.v.sh + (int64_t)k_lo * p.v.sn, p.v.sn, Mk);
       split0 = SPLIT0 && cold && nt_ > 1;
       if (nt_ > 0) {
         if (SPLIT0 && split0) {
@@ -410,8 +411,9 @@ __global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const Bw
   geometry(pass, m0, nt);
   const int mw = m0 + rwave * 32;
   const int i = mw + (lane & 31);
-  const char* kbase = p.k.p + (int64_t)b * p.k.sb + (int64_t)h * p.k.sh + (int64_t)k_lo * p.k.sn;
-  const char* vbase = p.v.p + (int64_t)b * p.v.sb + (int64_t)h * p.v.sh + (int64_t)k_lo * p.v.sn;
+  const int hk = h / p.kv_group;      // K/V head of the query head
+  const char* kbase = p.k.p + (int64_t)b * p.k.sb + (int64_t)hk * p.k.sh + (int64_t)k_lo * p.k.sn;
+  const char* vbase = p.v.p + (int64_t)b * p.v.sb + (int64_t)hk * p.v.sh + (int64_t)k_lo * p.v.sn;
   // (the first stage is requested ahead of the row chunks and the delta reduction -- or, with SEP, before the previous epilogue)
   if (!have_pre) request_ahead(b, h, pass, true);
 
@@ -811,8 +813,9 @@ __global__ void __launch_bounds__(256, (D * Traits<T>::ES <= 128 ? 2 : 1)) bwd_d
   };
   auto request = [&](int red_) {
     const int b = p.bias_batch ? owner : red_, h = p.bias_batch ? red_ : owner;
-    sk.load(p.k.p + (int64_t)b * p.k.sb + (int64_t)h * p.k.sh + (int64_t)j0 * p.k.sn, p.k.sn, p.M - j0);
-    sv.load(p.v.p + (int64_t)b * p.v.sb + (int64_t)h * p.v.sh + (int64_t)j0 * p.v.sn, p.v.sn, p.M - j0);
+    const int hk = h / p.kv_group;      // K/V head of the query head
+    sk.load(p.k.p + (int64_t)b * p.k.sb + (int64_t)hk * p.k.sh + (int64_t)j0 * p.k.sn, p.k.sn, p.M - j0);
+    sv.load(p.v.p + (int64_t)b * p.v.sb + (int64_t)hk * p.v.sh + (int64_t)j0 * p.v.sn, p.v.sn, p.M - j0);
     if constexpr (ROWS_AHEAD) load_rows(red_, nq, ndo);
     if (i < p.N) {
       const int64_t ridx = ((int64_t)b * p.H + h) * p.N + i;
@@ -1140,9 +1143,14 @@ FCSA_DEV void dkv_tile_pipe(const char* qt, const char* dot, const float* lcs, c
 // QSPLIT (8 waves; the pipelined ring tile, or the generic two-buffer tile where a bias rides along): the workgroup owns 128 keys and its wave halves split the QUERIES of every staged tile -- waves 0-3 take its
 // first BMQ / 2 rows, waves 4-7 the others, for the same four 32-key slices -- and add their dK / dV partials through the LDS at the end of
 // the pass: the mirror image of the key-split forward / dQ forms, for grids of at most one 128-key workgroup per CU.
-template <typename T, int D, int NW, int BMQ, bool BIAS, bool LEAN, bool KM, bool RING = false, bool QSPLIT = false>      // KM: not causal, masked tiles in the rank-1 form (see fwd_kernel)
+// SWEEP (grouped-query attention, kv_group > 1; 16-bit, no bias, no split, LDS-DMA staging): the workgroup owns the keys of one (batch, K/V
+// head) and, in every pass, walks the kv_group query heads of its group one after the other, each through the same query-tile loop.  dK^ / dV
+// stay in registers across the heads and the epilogue writes the group's sum once (no slabs, no finalize).  The Q / dO stream runs on
+// across the head seam: the tile requested ahead of the last tile of head g is the first tile of head g + 1, so the pipeline does not drain.
+template <typename T, int D, int NW, int BMQ, bool BIAS, bool LEAN, bool KM, bool RING = false, bool QSPLIT = false, bool SWEEP = false>      // KM: not causal, masked tiles in the rank-1 form (see fwd_kernel)
 __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes || LEAN) ? 2 : 1)) bwd_dkv_kernel(const BwdParams p) {
   static_assert(!QSPLIT || (NW == 8 && !LEAN && (RING || BIAS) && BMQ % 64 == 0), "query-split form: 8 waves; pipelined ring tile, or the generic tile with a bias");
+  static_assert(!SWEEP || (!BIAS && !QSPLIT && Traits<T>::ES == 2), "group sweep: 16-bit, bias-free, key tiles of whole workgroups");
   const int causal = KM ? 0 : p.causal;      // (same type and value as p.causal: the causal instantiations compile to what they were)
   typedef TileGeom<D, Traits<T>::ES> G;
   typedef Traits<T> TR;
@@ -1170,11 +1178,18 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
   // causal: the LOW key tiles are the heavy ones (they see every later query); pair (pt, KT-1-pt) per workgroup
   const int KT = (p.M + BNK - 1) / BNK;
   const int PT = causal ? (KT + 1) / 2 : KT;
-  int bh, pt;
-  block_to_work(blockIdx.x, p.B * p.H, PT, bh, pt);
-  const int b = bh / p.H, h = bh % p.H;
+  int bh, pt, b, h, hk;
+  if constexpr (SWEEP) {      // grid: (batch, K/V head) x key tiles; h = the group's first query head
+    const int HK = p.H / p.kv_group;
+    block_to_work(blockIdx.x, p.B * HK, PT, bh, pt);
+    b = bh / HK; hk = bh % HK; h = hk * p.kv_group;
+  } else {
+    block_to_work(blockIdx.x, p.B * p.H, PT, bh, pt);
+    b = bh / p.H; h = bh % p.H; hk = h / p.kv_group;
+  }
   const int npass = (causal && (KT - 1 - pt) != pt) ? 2 : 1;
   const int diff = p.M - p.N;
+  const int64_t rk_bh = (int64_t)b * (p.H / p.kv_group) + hk;      // (batch, K/V head) row block of rk
   Trace ts;
   ts.reset();
 #ifdef FCSA_TRACE_WG
@@ -1205,6 +1220,14 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
   const char* dobase = p.d_out.p + (int64_t)b * p.d_out.sb + (int64_t)h * p.d_out.sh;
   const float* invl_row = p.inv_l + ((int64_t)b * p.H + h) * p.N;
   const float* delta_row = p.delta + ((int64_t)b * p.H + h) * p.N;
+  // SWEEP: the query head the Q / dO stream is loading (head h + lh of the group, tile lt): the bases above follow it
+  int lh = 0, lt = 0;
+  auto rebase = [&](int hh) {
+    qbase = p.q.p + (int64_t)b * p.q.sb + (int64_t)hh * p.q.sh;
+    dobase = p.d_out.p + (int64_t)b * p.d_out.sb + (int64_t)hh * p.d_out.sh;
+    invl_row = p.inv_l + ((int64_t)b * p.H + hh) * p.N;
+    delta_row = p.delta + ((int64_t)b * p.H + hh) * p.N;
+  };
   // Q / dO tiles: LDS-DMA in the pipelined form (no staging registers, no ds_write passes), else through registers
   constexpr bool DMA = (PIPE || LEAN) && (BMQ * G::ROWB) % 1024 == 0;
   typedef DkvLds<T, D, NW, BMQ, BIAS, LEAN, NBUF> LDS;
@@ -1248,6 +1271,22 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
       stdo = ddo_.open(dobase + (int64_t)t * BMQ * p.d_out.sn, p.d_out.sn, p.N - t * BMQ);
     }
   };
+  // SWEEP: move the load cursor to the next (head, tile) of the pass -- the next tile of the same head, else the first tile t0_ of the next
+  // head (streams re-opened at its base) -- and say whether there is one.  Scalar work once per tile, a re-base once per head.
+  auto cursor_next = [&](int t0_) -> bool {
+    if (lt + 1 < QT) {
+      ++lt;
+      advance(lt);
+      return true;
+    }
+    if (lh + 1 >= p.kv_group) return false;
+    ++lh;
+    lt = t0_;
+    rebase(h + lh);
+    stq = dq_.open(qbase + (int64_t)lt * BMQ * p.q.sn, p.q.sn, p.N - lt * BMQ);
+    stdo = ddo_.open(dobase + (int64_t)lt * BMQ * p.d_out.sn, p.d_out.sn, p.N - lt * BMQ);
+    return true;
+  };
   // loads of tile t through registers (non-DMA form); `buf` = the LDS buffer it is going to
   auto load_tile = [&](int t, char* buf) {
     const int i0 = t * BMQ;
@@ -1279,6 +1318,11 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
   auto request_ahead = [&](int pass_) {
     int n0_, t0_;
     geometry(pass_, n0_, t0_);
+    if constexpr (SWEEP) {      // the pass starts at the group's first head
+      lh = 0;
+      lt = t0_;
+      rebase(h);
+    }
     if constexpr (DMA) {
       stq = dq_.open(qbase + (int64_t)t0_ * BMQ * p.q.sn, p.q.sn, p.N - t0_ * BMQ);
       stdo = ddo_.open(dobase + (int64_t)t0_ * BMQ * p.d_out.sn, p.d_out.sn, p.N - t0_ * BMQ);
@@ -1288,15 +1332,23 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
         load_rows(t0_ * BMQ);
       }
       if constexpr (RING) {      // second tile of the pass -> buffer 1 (its per-query terms travel in the second register set)
-        if (t0_ + 1 < QT) {
+        bool second = false;
+        int t2 = t0_ + 1;
+        if constexpr (SWEEP) {
+          second = t0_ < QT && cursor_next(t0_);      // (the next head's first tile where the first head has one tile)
+          t2 = lt;
+        } else if (t0_ + 1 < QT) {
+          second = true;
           advance(t0_ + 1);
+        }
+        if (second) {
           dq_.issue(stq, lds0 + BUF_B, wave);
           ddo_.issue(stdo, lds0 + BUF_B + TILE_B, wave);
           if (tid < BMQ) {
-            const int i = min((t0_ + 1) * BMQ + tid, p.N - 1);
+            const int i = min(t2 * BMQ + tid, p.N - 1);
             lc_r2 = invl_row[i];
             dl_r2 = delta_row[i];
-            row_ok2 = (t0_ + 1) * BMQ + tid < p.N;
+            row_ok2 = t2 * BMQ + tid < p.N;
           }
         }
       }
@@ -1304,12 +1356,12 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
     if constexpr (LEAN) {      // the V rows of this workgroup's keys -> LDS (rows past M are zero-filled by the descriptor's range check)
       DmaStager<T, D, BNK, NW> dvown_;      // (set up here, once per pass, from an opaque lane id: nothing of it lives across the tile loops)
       dvown_.init(p.v.sn, wave, opaque(lane));
-      dvown_.issue(p.v.p + (int64_t)b * p.v.sb + (int64_t)h * p.v.sh + (int64_t)n0_ * p.v.sn, p.v.sn, p.M - n0_, smem + LDS::VOWN, wave);
+      dvown_.issue(p.v.p + (int64_t)b * p.v.sb + (int64_t)hk * p.v.sh + (int64_t)n0_ * p.v.sn, p.v.sn, p.M - n0_, smem + LDS::VOWN, wave);
     }
     const int ln = opaque(lane), hi_ = ln >> 5;
     const int nw_ = n0_ + rwave * 32, j_ = nw_ + (ln & 31);
-    const char* krow = p.k.p + (int64_t)b * p.k.sb + (int64_t)h * p.k.sh + (int64_t)j_ * p.k.sn;
-    const char* vrow = p.v.p + (int64_t)b * p.v.sb + (int64_t)h * p.v.sh + (int64_t)j_ * p.v.sn;
+    const char* krow = p.k.p + (int64_t)b * p.k.sb + (int64_t)hk * p.k.sh + (int64_t)j_ * p.k.sn;
+    const char* vrow = p.v.p + (int64_t)b * p.v.sb + (int64_t)hk * p.v.sh + (int64_t)j_ * p.v.sn;
 #pragma unroll
     for (int kk = 0; kk < G::KS; ++kk) {
       const u32x4 z = {0u, 0u, 0u, 0u};
@@ -1324,7 +1376,7 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
     typedef RowEpilogue<T, D> EP;
     if constexpr (SEP) {      // (without SEP the epilogue loads them itself: fewer registers live across the tile loops)
       if (p.rk != nullptr && p.M - nw_ > 0)
-        EP::load_inv(rinv_n, p.rk + (((int64_t)b * p.H + h) * p.M + nw_) * p.G, p.G, p.lgm, ln, p.M - nw_);
+        EP::load_inv(rinv_n, p.rk + (rk_bh * p.M + nw_) * p.G, p.G, p.lgm, ln, p.M - nw_);
     }
   };
 
@@ -1395,7 +1447,7 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
 
   if (t0 < QT) store_tile(smem);
   if constexpr (RING) {      // per-query terms of the pass's second tile (its DMA was covered by the wait above)
-    if (t0 + 1 < QT && tid < BMQ) {
+    if ((SWEEP ? t0 < QT && (t0 + 1 < QT || p.kv_group > 1) : t0 + 1 < QT) && tid < BMQ) {
       char* buf1 = smem + BUF_B;
       reinterpret_cast<float*>(buf1 + 2 * TILE_B)[tid] = row_ok2 ? (p.invl_log2 ? lc_r2 : __builtin_amdgcn_logf(lc_r2)) - p.c2 : -INFINITY;
       reinterpret_cast<float*>(buf1 + 2 * TILE_B + BMQ * 4)[tid] = row_ok2 ? -dl_r2 : 0.f;
@@ -1416,6 +1468,8 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
     t_m = t0;
     if (causal) t_m = min(QT, max(t0, (nw + 31 - diff - hq + BMQ - 1) / BMQ));      // (QSPLIT: of this wave's rows of the tile)
   }
+  // SWEEP: this wave skips the first tile of every head (see `skip` below): the last tile of a head must not prefetch into it
+  const bool head_skip0 = SWEEP && causal && t_m > t0 && t0 * BMQ + hq + BMS - 1 + diff < nw;
 
 #ifdef FCSA_TRACE_BAR
   unsigned long long bar_t = 0, loop_t = 0;
@@ -1424,6 +1478,8 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
   DkvPipe<T, D, BMS> pipe;      // RING: lives across the tiles of a pass
   int pipe_tile = -1;           // RING: the tile whose first block's fragments are in flight
   int ring = 0;                 // RING: staging buffer of the current tile (t - t0 mod 3, kept without a division)
+  int tpar = 0;                 // SWEEP, two buffers: staging buffer of the current tile (the tile count of a head may be odd)
+  int gi = 0;                   // SWEEP: the query head (of the group) the tiles being computed belong to
   auto run = [&](auto masked_tag, int t_begin, int t_end) {
     constexpr int MODE = decltype(masked_tag)::value;      // dkv_tile: 0 all valid, 1 causal select, 2 key mask by rank-1 MFMA
     constexpr bool MASKED = MODE != 0;
@@ -1431,22 +1487,28 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
       const int i0 = t * BMQ;
       // two buffers: the next tile lands in the other one during this tile.  RING: tile t + 1 is complete already (requested at the
       // top of tile t - 1, or in the pass prologue); tile t + 2 is requested here into the buffer tile t - 1 has left
-      const int par = RING ? ring : (t - t0) & 1;
+      const int par = RING ? ring : SWEEP ? tpar : (t - t0) & 1;
       const int par_nxt = RING ? (ring == 2 ? 0 : ring + 1) : (par ^ 1);          // buffer of tile t + 1
       const int par_ld = RING ? (ring == 0 ? 2 : ring - 1) : (par ^ 1);           // buffer this tile's requests fill
       const int t_ld = RING ? t + 2 : t + 1;                                      // ... with this tile
       const char* cur = smem + par * BUF_B;
       char* nxt = smem + par_ld * BUF_B;
-      const bool more = t_ld < QT;
+      bool more = t_ld < QT;
       FCSA_STAMP(ts, 0);
       const float* lcs = reinterpret_cast<const float*>(cur + 2 * TILE_B);
       const float* dls = lcs + BMQ;
-      if constexpr (DMA) {
+      if constexpr (SWEEP) {
+        // the load cursor runs on into the next head of the group (cursor_next), one tile per computed tile
+        more = cursor_next(t0);
+        if (more) load_rows(lt * BMQ);
+      } else if constexpr (DMA) {
         // the next tile arrives by LDS-DMA, all pieces requested at the top of this tile
         if (more) {
           advance(t_ld);
           load_rows(t_ld * BMQ);
         }
+      }
+      if constexpr (DMA) {
         const uint32_t lds_nxt = lds0 + par_ld * BUF_B;
         FCSA_STAMP(ts, 1);
         if (more) {
@@ -1463,14 +1525,14 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
       if constexpr (PIPE) {
         if constexpr (RING) {
           if (!skip) {
-            const bool has_next = t + 1 < QT;      // (else: the request reads this tile's buffer again and is never used)
+            const bool has_next = t + 1 < QT || (SWEEP && gi + 1 < p.kv_group && !head_skip0);      // (else: the request reads this tile's buffer again and is never used)
             if constexpr (QSPLIT)
               dkv_tile_pipe<T, D, BMS, tile_mode<MODE>(), true, true>(cur + hoff, cur + TILE_B + hoff, lcs + hq, dls + hq, fa, kf, vf, dk, dv, kmask, ncm, j, i0 + hq, diff, ts,
                                                           pipe, pipe_tile != t, has_next ? smem + par_nxt * BUF_B : cur, wave >= 4, hoff, hq);
             else
             dkv_tile_pipe<T, D, BMQ, tile_mode<MODE>(), true>(cur, cur + TILE_B, lcs, dls, fa, kf, vf, dk, dv, kmask, ncm, j, i0, diff, ts, pipe, pipe_tile != t,
                                                   has_next ? smem + par_nxt * BUF_B : cur, NW == 8 && wave >= 4);
-            pipe_tile = has_next ? t + 1 : -1;
+            pipe_tile = has_next ? (t + 1 < QT ? t + 1 : t0) : -1;      // (SWEEP: the next head starts at t0)
           }
           ring = par_nxt;
         } else {
@@ -1492,6 +1554,7 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
       }
       FCSA_STAMP(ts, 8);
       if (more) store_tile(nxt);
+      if constexpr (SWEEP) tpar ^= 1;
       FCSA_STAMP(ts, 9);
       FCSA_BAR_BEGIN(bar_t);
       __syncthreads();
@@ -1501,9 +1564,12 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
     }
   };
   FCSA_PASS_MARK(1);
-  run(std::integral_constant<int, KM ? 2 : 1>{}, t0, t_m);
-  FCSA_PASS_MARK(2);
-  run(std::integral_constant<int, 0>{}, t_m, QT);
+  tpar = 0;
+  for (gi = 0; gi < (SWEEP ? p.kv_group : 1); ++gi) {      // (SWEEP: the heads of the group, in order; dk / dv accumulate across them)
+    run(std::integral_constant<int, KM ? 2 : 1>{}, t0, t_m);
+    FCSA_PASS_MARK(2);
+    run(std::integral_constant<int, 0>{}, t_m, QT);
+  }
   FCSA_PASS_MARK(3);
 #ifdef FCSA_TRACE_BAR
   FCSA_BAR_END(loop_t, bar_loop);
@@ -1551,7 +1617,7 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
     if constexpr (!SEP) {
 #pragma unroll
       for (int e = 0; e < EP::NP; ++e) rinv[e] = 1.f;
-      if (fused && rows_valid > 0) EP::load_inv(rinv, p.rk + (((int64_t)b * p.H + h) * p.M + nw) * p.G, p.G, p.lgm, le, rows_valid);
+      if (fused && rows_valid > 0) EP::load_inv(rinv, p.rk + (rk_bh * p.M + nw) * p.G, p.G, p.lgm, le, rows_valid);
     }
     if (rows_valid > 0) EP::put(scr, dk, kmul, le, (LDS::X && fused) ? kf : nullptr, xs, LDS::XPITCH);
     have_pre = false;
@@ -1563,9 +1629,10 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
     }
     if (rows_valid > 0) {
       const int64_t split_off = p.dkv_splits > 1 ? (int64_t)blockIdx.y * p.dkv_split_stride : 0;
-      char* dk0 = p.dk.p + (int64_t)b * p.dk.sb + (int64_t)h * p.dk.sh + (int64_t)nw * p.dk.sn + split_off;
-      char* dv0 = p.dv.p + (int64_t)b * p.dv.sb + (int64_t)h * p.dv.sh + (int64_t)nw * p.dv.sn + split_off;
-      const char* x0 = fused ? p.k.p + (int64_t)b * p.k.sb + (int64_t)h * p.k.sh + (int64_t)nw * p.k.sn : nullptr;
+      const int ho = SWEEP ? hk : h;      // output head: the K/V head (the group's sum), or the query head's slab
+      char* dk0 = p.dk.p + (int64_t)b * p.dk.sb + (int64_t)ho * p.dk.sh + (int64_t)nw * p.dk.sn + split_off;
+      char* dv0 = p.dv.p + (int64_t)b * p.dv.sb + (int64_t)ho * p.dv.sh + (int64_t)nw * p.dv.sn + split_off;
+      const char* x0 = fused ? p.k.p + (int64_t)b * p.k.sb + (int64_t)hk * p.k.sh + (int64_t)nw * p.k.sn : nullptr;
       EP::template finish<LDS::X>(scr, xs, LDS::XPITCH, le, dk0, p.dk.sn, rows_valid, fused ? false : p.dk_f32 != 0, x0, p.k.sn, 1.f, rinv, p.lgm,
                                   p.norm_eps);
       EP::put(scr, dv, 1.f, le, nullptr, xs, LDS::XPITCH);
@@ -1733,7 +1800,7 @@ static hipError_t launch_dq_b(const BwdParams& p, hipStream_t s) {
   return launch_dq_nw<T, D, BIAS, 4, NARROW>(p, s);
 }
 
-template <typename T, int D, bool BIAS, int NW, bool LEAN = false, bool QSPLIT = false>
+template <typename T, int D, bool BIAS, int NW, bool LEAN = false, bool QSPLIT = false, bool SWEEP = false>
 static hipError_t launch_dkv_nw(const BwdParams& p, hipStream_t s) {
   constexpr int BNK = 32 * (QSPLIT ? NW / 2 : NW);
   // staged query tile: 32 rows for wide feature rows (16-bit D >= 96, f32 D >= 64: VGPR budget of the staging registers),
@@ -1754,14 +1821,14 @@ static hipError_t launch_dkv_nw(const BwdParams& p, hipStream_t s) {
   static_assert(!QSPLIT || RING || BIAS, "query-split form: ring tile, or the generic tile with a bias");
   size_t lds = DkvLds<T, D, NW, BMQ, BIAS, LEAN, RING ? 3 : 2>::TOTAL + (BIAS ? (size_t)NW * BiasBlock<T>::BYTES : 0);
   if (QSPLIT && lds < (size_t)(NW / 2) * 64 * 16 * TileGeom<D, Traits<T>::ES>::DB * 8) lds = (size_t)(NW / 2) * 64 * 16 * TileGeom<D, Traits<T>::ES>::DB * 8;
-  const dim3 grid((unsigned)(p.B * p.H * PT), (unsigned)(p.dkv_splits > 1 ? p.dkv_splits : 1));
+  const dim3 grid((unsigned)(p.B * (SWEEP ? p.H / p.kv_group : p.H) * PT), (unsigned)(p.dkv_splits > 1 ? p.dkv_splits : 1));
   if (p.causal) {        // (two instantiations, see launch_fwd_nw)
-    auto kern = bwd_dkv_kernel<T, D, NW, BMQ, BIAS, LEAN, false, RING, QSPLIT>;
+    auto kern = bwd_dkv_kernel<T, D, NW, BMQ, BIAS, LEAN, false, RING, QSPLIT, SWEEP>;
     static std::atomic<uint64_t> lds_ok{0};
     if (hipError_t e = ensure_dynamic_lds(kern, lds, lds_ok); e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, s, p);
   } else {
-    auto kern = bwd_dkv_kernel<T, D, NW, BMQ, BIAS, LEAN, true, RING, QSPLIT>;
+    auto kern = bwd_dkv_kernel<T, D, NW, BMQ, BIAS, LEAN, true, RING, QSPLIT, SWEEP>;
     static std::atomic<uint64_t> lds_ok{0};
     if (hipError_t e = ensure_dynamic_lds(kern, lds, lds_ok); e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, s, p);
@@ -1769,8 +1836,32 @@ static hipError_t launch_dkv_nw(const BwdParams& p, hipStream_t s) {
   return hipGetLastError();
 }
 
+// Group-sweep dK/dV (grouped-query attention): compiled for the 8-wave forms of 16-bit D = 64 (pipelined ring tile) and D = 128 (lean tile),
+// the forms the dispatch below picks for key grids that cover the chip.  The C ABI takes it (BwdParams::kv_sweep) where the sweep grid --
+// batch x K/V heads x 256-key tiles -- gets the 8-wave form by the same rule (tile_waves), else it keeps per-query-head slabs + finalize.
+template <typename T, int D, bool BIAS> constexpr bool dkv_has_sweep() { return Traits<T>::ES == 2 && !BIAS && (D == 64 || D == 128); }
+
+static std::atomic<int> g_kv_group_mode{1};
+int kv_group_mode(int set) {
+  if (set < 0) return g_kv_group_mode.load(std::memory_order_relaxed);
+  return g_kv_group_mode.exchange(set > 2 ? 2 : set, std::memory_order_relaxed);
+}
+
+bool backward_dkv_sweep(int dtype, int D, int64_t batch_kv_heads, int N, int M, int causal, int mode) {
+  (void)N;
+  if ((dtype != 1 && dtype != 2) || (D != 64 && D != 128) || mode <= 0) return false;
+  return mode >= 2 || tile_waves(batch_kv_heads, M, causal != 0, true, 1) == 8;
+}
+
 template <typename T, int D, bool BIAS>
 static hipError_t launch_dkv_b(const BwdParams& p, hipStream_t s) {
+  if (p.kv_sweep) {
+    if constexpr (dkv_has_sweep<T, D, BIAS>()) {
+      if constexpr (D * Traits<T>::ES <= kDkv2WBytes) return launch_dkv_nw<T, D, BIAS, 8, false, false, true>(p, s);
+      else return launch_dkv_nw<T, D, BIAS, 8, true, false, true>(p, s);
+    }
+    return hipErrorInvalidValue;      // (the C ABI only sets kv_sweep where backward_dkv_sweep said so)
+  }
   if (p.dkv_splits > 1) return launch_dkv_nw<T, D, BIAS, 4>(p, s);       // split-query path: 128-key tiles x query ranges
 #ifdef FCSA_VAR_SPLIT_ENV      // sweep builds only: FCSA_DKV_FORM = 1 key tiles of 8 waves, 2 query-split 8 waves, 3 four waves
   if constexpr (D * Traits<T>::ES <= kDkv2WBytes && bwd_ksplit<T, D, BIAS>() && (D == 64 || D == 32 || D == 16)) {

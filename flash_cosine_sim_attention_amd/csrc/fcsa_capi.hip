@@ -47,8 +47,8 @@ int check_problem(const fcsa_problem& p) {
     return fail(FCSA_ERR_UNSUPPORTED, "dim_head %d not in {16, 32, 64, 96, 128}", p.dim_head);
   if (p.batch < 0 || p.heads < 0 || p.q_len < 0 || p.k_len < 0)
     return fail(FCSA_ERR_INVALID_ARG, "negative size (B=%d H=%d N=%d M=%d)", p.batch, p.heads, p.q_len, p.k_len);
-  if (p.kv_heads != p.heads && p.kv_heads != 1)
-    return fail(FCSA_ERR_INVALID_ARG, "kv_heads must be heads (%d) or 1, got %d", p.heads, p.kv_heads);
+  if (p.kv_heads < 1 ? p.heads != 0 || p.kv_heads != 0 : p.heads % p.kv_heads != 0)
+    return fail(FCSA_ERR_INVALID_ARG, "kv_heads must divide heads (%d), got %d", p.heads, p.kv_heads);
   if (p.l2norm_qk) {
     if (p.groups < 1 || p.dim_head % p.groups != 0)
       return fail(FCSA_ERR_INVALID_ARG, "groups (%d) must divide dim_head (%d)", p.groups, p.dim_head);
@@ -151,6 +151,7 @@ float rowsum_eps(const fcsa_problem& p, bool has_bias) {
 struct BwdLayout {
   size_t delta, dq_slab, dk_slab, dv_slab, total;
   bool need_dq_slab, need_dk_slab, need_dv_slab, fuse_norm;
+  bool kv_sweep;          // grouped-query K/V (1 < kv_heads < heads): a bias-free launch runs the group-sweep dK/dV kernel (no dk / dv slabs)
   int dq_splits;          // > 1: split-key dQ kernel, dq_slab holds dq_splits partial slabs
   int dkv_splits;         // > 1: split-query dK/dV kernel, dk_slab / dv_slab hold dkv_splits partial slabs each
 };
@@ -269,20 +270,33 @@ int log2_blocks_per_group(const fcsa_problem& p) {     // log2(group size / 8), 
 }
 bool fusable_groups(const fcsa_problem& p) { return log2_blocks_per_group(p) >= 0; }
 
+// Grouped-query K/V (1 < kv_heads < heads) with the group-sweep dK/dV kernel: one workgroup per (batch, K/V head, key tile) sums the dK / dV of
+// its group's query heads in registers.  Where it is compiled (16-bit, D = 64 / 128), for epilogues that finish the job (no l2norm groups that
+// need the finalize kernel), and where its grid gets the 8-wave form (fcsa_debug_kv_group_form: 0 never, 2 wherever compiled).  A launch with
+// an attn_bias takes the slab route instead: the workspace keeps room for its slabs.
+bool kv_sweep(const fcsa_problem& p) {
+  if (p.kv_heads <= 1 || p.kv_heads == p.heads) return false;
+  if (p.l2norm_qk != 0 && !fusable_groups(p)) return false;
+  return fcsa::backward_dkv_sweep(p.dtype, p.dim_head, (int64_t)p.batch * p.kv_heads, p.q_len, p.k_len, p.causal, fcsa::kv_group_mode(-1));
+}
+
 BwdLayout bwd_layout(const fcsa_problem& p) {
   BwdLayout L;
-  const bool single = p.kv_heads == 1 && p.heads > 1;
+  // K/V heads fewer than query heads (single-headed or grouped): the dK/dV kernel writes per-query-head f32 slabs that the finalize kernel
+  // sums over each K/V head's group -- except for the group sweep (kv_sweep), whose bias-free launches write dk / dv directly
+  const bool grouped = p.kv_heads != p.heads && p.heads > 1;
+  L.kv_sweep = kv_sweep(p);
   const size_t qn = (size_t)p.batch * p.heads * p.q_len;
   const size_t kn = (size_t)p.batch * p.heads * p.k_len;      // slabs are per q-head
   // the l2norm backward is fused into the dQ / dKV epilogues when every group is 8 * 2^k features wide;
-  // otherwise (odd group sizes) and for the head reduction of single-headed K/V the kernels write f32
+  // otherwise (odd group sizes) and for the head reduction of single-headed / grouped K/V the kernels write f32
   // slabs that the finalize kernel reduces / differentiates.
   L.fuse_norm = p.l2norm_qk != 0 && fusable_groups(p);
   L.dq_splits = backward_dq_splits(p);
   L.need_dq_slab = (p.l2norm_qk != 0 && !L.fuse_norm) || L.dq_splits > 1;
-  L.dkv_splits = backward_dkv_splits(p);
-  L.need_dk_slab = single || (p.l2norm_qk != 0 && !L.fuse_norm) || L.dkv_splits > 1;
-  L.need_dv_slab = single || L.dkv_splits > 1;
+  L.dkv_splits = L.kv_sweep ? 1 : backward_dkv_splits(p);      // (sweep problems: a bias launch takes the slab route, which never splits)
+  L.need_dk_slab = grouped || (p.l2norm_qk != 0 && !L.fuse_norm) || L.dkv_splits > 1;
+  L.need_dv_slab = grouped || L.dkv_splits > 1;
   size_t off = 0;
   L.delta = off;   off = align_up(off + qn * 4, 256);
   L.dq_slab = off; off = align_up(off + (L.need_dq_slab ? qn * p.dim_head * 4 * (size_t)L.dq_splits : 0), 256);
@@ -362,13 +376,15 @@ int fcsa_debug(char* buf, size_t buf_bytes) {
     snprintf(buf, buf_bytes,
              "libfcsa_hip abi=%d arch=gfx950 dtypes=f32,f16,bf16 dim_head=16,32,64,96,128 "
              "kernels=l2norm,l2norm_pair,fwd(32 rows/wave; lean two-wave form at D=96/128),fwd2(64 rows/wave),fwd3(D=128: 64 rows/wave, 1 wave/SIMD),fwd_ksplit(128 rows, wave halves split the keys),fwd_split+combine,"
-             "fwd_dyn(per-row shift),bwd_dq(+split-key; key-split form on 8 waves),bwd_dkv(+lean; query-split form on 8 waves),bwd_dbias,finalize",
+             "fwd_dyn(per-row shift),bwd_dq(+split-key; key-split form on 8 waves),bwd_dkv(+lean; query-split form on 8 waves; grouped-query K/V head sweep),bwd_dbias,finalize kv_heads=divisors of heads",
              FCSA_ABI_VERSION);
   }
   return FCSA_ABI_VERSION;
 }
 
 int fcsa_debug_forward_form(int32_t form) { return fcsa::forward_wide128_mode(form); }
+
+int fcsa_debug_kv_group_form(int32_t form) { return fcsa::kv_group_mode(form); }
 
 int fcsa_l2norm(int32_t dtype, int32_t batch, int32_t heads, int32_t len, int32_t dim_head, int32_t groups,
                 const fcsa_tensor* x, void* xn, float* inv_norm, void* stream) {
@@ -467,9 +483,10 @@ int fcsa_forward(const fcsa_forward_args* a) {
   if (int rc = check_tensor("v", a->v, es, true)) return rc;
   if (int rc = check_tensor("o", a->o, es, true)) return rc;
   hipStream_t s = static_cast<hipStream_t>(a->stream);
-  const bool single = p.kv_heads == 1 && p.heads > 1;
+  const bool single = p.kv_heads == 1 && p.heads > 1;      // one K/V head: stride-0 head views; grouped K/V: kv_group query heads per K/V head
 
   fcsa::FwdParams fp;
+  fp.kv_group = single ? 1 : p.heads / p.kv_heads;
   bool fuse_q = false;
   fp.q = view(a->q, es);
   fp.k = view(a->k, es, single);
@@ -574,10 +591,14 @@ int fcsa_backward(const fcsa_backward_args* a) {
   if ((reinterpret_cast<uintptr_t>(a->workspace) & 255) != 0) return fail(FCSA_ERR_WORKSPACE, "workspace not 256-byte aligned");
 
   hipStream_t s = static_cast<hipStream_t>(a->stream);
-  const bool single = p.kv_heads == 1 && p.heads > 1;
+  const bool single = p.kv_heads == 1 && p.heads > 1;      // stride-0 K/V head views
+  const bool grouped = p.kv_heads != p.heads;             // single-headed or grouped-query K/V: dk / dv are sums over query heads
+  const bool sweep = L.kv_sweep && a->attn_bias == nullptr;      // grouped, in-kernel head sum; else per-query-head slabs + finalize
   char* ws = static_cast<char*>(a->workspace);
 
   fcsa::BwdParams bp;
+  bp.kv_group = single ? 1 : p.heads / p.kv_heads;
+  bp.kv_sweep = sweep ? 1 : 0;
   if (p.l2norm_qk) {
     bp.q = contiguous_view(a->norm.qn, p.heads, p.q_len, p.dim_head, es);
     bp.k = contiguous_view(a->norm.kn, p.kv_heads, p.k_len, p.dim_head, es, single);
@@ -598,9 +619,9 @@ int fcsa_backward(const fcsa_backward_args* a) {
   bp.dq_split_stride = (int64_t)p.q_len * p.dim_head * 4;
   // split-query dK/dV: same condition on dk / dv (flat (batch, head) index for the finalize kernel); the bias form keeps the unsplit kernel
   const bool dkv_flat = a->dk.stride0 == (int64_t)p.heads * a->dk.stride1 && a->dv.stride0 == (int64_t)p.heads * a->dv.stride1;
-  const int dkv_splits = (L.dkv_splits > 1 && (dkv_flat || single) && a->attn_bias == nullptr) ? L.dkv_splits : 1;
-  const bool dk_slab = dkv_splits > 1 || single || (p.l2norm_qk != 0 && !L.fuse_norm);
-  const bool dv_slab = dkv_splits > 1 || single;
+  const int dkv_splits = (L.dkv_splits > 1 && (dkv_flat || grouped) && a->attn_bias == nullptr && !sweep) ? L.dkv_splits : 1;
+  const bool dk_slab = !sweep && (dkv_splits > 1 || grouped || (p.l2norm_qk != 0 && !L.fuse_norm));
+  const bool dv_slab = !sweep && (dkv_splits > 1 || grouped);
   bp.dkv_splits = dkv_splits;
   bp.dkv_split_stride = (int64_t)p.k_len * p.dim_head * 4;
   bp.dq_f32 = dq_slab;
@@ -640,7 +661,7 @@ int fcsa_backward(const fcsa_backward_args* a) {
   bp.q_scaled = p.l2norm_qk ? 1 : 0;
   bp.G = p.groups; bp.lgm = L.fuse_norm ? log2_blocks_per_group(p) : 0; bp.norm_eps = 1e-12f;
   bp.rq = (L.fuse_norm && dq_splits <= 1) ? a->norm.rq : nullptr;    // fused: dq kernel writes the final dq
-  bp.rk = (L.fuse_norm && !single && dkv_splits <= 1) ? a->norm.rk : nullptr;          // fused: dkv kernel writes the final dk
+  bp.rk = (L.fuse_norm && (!grouped || sweep) && dkv_splits <= 1) ? a->norm.rk : nullptr;          // fused: dkv kernel writes the final dk
 
   // 1. dQ (also publishes delta), 2. dK/dV, 3. head reduction + l2norm backward where needed
   if (int rc = timed("bwd_dq", "backward dq", s, [&] { return fcsa::launch_backward_dq(p.dtype, p.dim_head, bp, s); })) return rc;
@@ -686,8 +707,8 @@ int fcsa_backward(const fcsa_backward_args* a) {
   }
   if (dkv_splits > 1) {         // the splits are the "heads" of a flat (batch * head) batch, summed down to one
     for (fcsa::NormBwdParams* n : {&nk, &nv}) {
-      if (single) {               // slabs [batch][heads x splits][M][D] summed down to the one K/V head
-        n->HS = p.heads * dkv_splits; n->HO = 1;
+      if (grouped) {              // slabs [batch][heads x splits][M][D]: each K/V head sums its group's heads x splits
+        n->HS = p.heads * dkv_splits; n->HO = p.kv_heads;
         continue;
       }
       n->B = p.batch * p.heads; n->HS = dkv_splits; n->HO = 1;

@@ -547,8 +547,9 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ?
   if (causal) last_key = min(last_key, m0 + BM - 1 + diff);
   const int nt = last_key < 0 ? 0 : last_key / BN + 1;
 
-  const char* kbase = p.k.p + (int64_t)b * p.k.sb + (int64_t)h * p.k.sh + (int64_t)k_lo * p.k.sn;
-  const char* vbase = p.v.p + (int64_t)b * p.v.sb + (int64_t)h * p.v.sh + (int64_t)k_lo * p.v.sn;
+  const int hk = h / p.kv_group;                  // K/V head of this query head (grouped-query attention)
+  const char* kbase = p.k.p + (int64_t)b * p.k.sb + (int64_t)hk * p.k.sh + (int64_t)k_lo * p.k.sn;
+  const char* vbase = p.v.p + (int64_t)b * p.v.sb + (int64_t)hk * p.v.sh + (int64_t)k_lo * p.v.sn;
   // DMA form (16-bit types): tile t+1 goes global -> LDS by LDS-DMA (DmaStager: no staging registers, no ds_write passes), issued
   // at the top of tile t into the buffer whose last reads finished before the barrier of tile t-1, and waited for right before
   // the barrier of tile t.  The FIRST tile is issued here, ahead of the Q fragments and their fused l2norm, so that its
@@ -1083,8 +1084,9 @@ __global__ void __launch_bounds__(NW * 64, 1) fwd2_kernel(const FwdParams p) {
   const int npass = (p.causal && (MT - 1 - pt) != pt) ? 2 : 1;
   const int diff = p.M - p.N;
   const uint32_t ncm = p.causal ? 0u : 0xffffffffu;
-  const char* kbase = p.k.p + (int64_t)b * p.k.sb + (int64_t)h * p.k.sh;
-  const char* vbase = p.v.p + (int64_t)b * p.v.sb + (int64_t)h * p.v.sh;
+  const int hk = h / p.kv_group;                               // K/V head of this query head (grouped-query attention)
+  const char* kbase = p.k.p + (int64_t)b * p.k.sb + (int64_t)hk * p.k.sh;
+  const char* vbase = p.v.p + (int64_t)b * p.v.sb + (int64_t)hk * p.v.sh;
   const uint8_t* mrow = p.mask ? p.mask + (int64_t)b * p.M : nullptr;
   Stager<T, D, BN, NT> sk, sv;
   sk.init(p.k.sn, tid);

@@ -358,8 +358,9 @@ __global__ void __launch_bounds__(256, 1) fwd3_kernel(const FwdParams p) {
   const int b = bh / p.H, h = bh % p.H;
   const int npass = (p.causal && (MT - 1 - pt) != pt) ? 2 : 1;
   const int diff = p.M - p.N;
-  const char* kbase = p.k.p + (int64_t)b * p.k.sb + (int64_t)h * p.k.sh;
-  const char* vbase = p.v.p + (int64_t)b * p.v.sb + (int64_t)h * p.v.sh;
+  const int hk = h / p.kv_group;                               // K/V head of this query head (grouped-query attention)
+  const char* kbase = p.k.p + (int64_t)b * p.k.sb + (int64_t)hk * p.k.sh;
+  const char* vbase = p.v.p + (int64_t)b * p.v.sb + (int64_t)hk * p.v.sh;
   DS dk_, dv_;
   dk_.init(p.k.sn, wave, lane);
   dv_.init(p.v.sn, wave, lane);

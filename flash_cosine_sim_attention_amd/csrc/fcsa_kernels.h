@@ -18,6 +18,7 @@ struct FwdParams {
   const uint8_t* mask;      // [B,M] or nullptr
   const char* bias;         // [Hb,N,M] contiguous, element type = dtype, or nullptr
   int B, H, N, M;
+  int kv_group;             // query heads per K/V head: query head h reads K/V head h / kv_group (1: Hk == H, or a stride-0 head view)
   int causal, bias_batch;
   float c1;                 // scale * log2(e)
   float c2;                 // shift * log2(e)      (P~ = exp2(c1 * qk - c2))
@@ -39,7 +40,7 @@ struct FwdParams {
 struct BwdParams {
   View q, k, v, o, d_out;   // q,k normalised
   View dq;                  // [B,H,N,D]  dtype, or f32 slab when dq_f32
-  View dk, dv;              // [B,H,M,D]  (per q-head!) dtype or f32 slabs
+  View dk, dv;              // [B,H,M,D]  (per q-head!) dtype or f32 slabs; kv_sweep: the final [B,Hk,M,D] outputs
   int dq_f32, dk_f32, dv_f32;   // element type of the gradient outputs above: 1 = float32
   const float* inv_l;       // [B,H,N]: 1 / rowsum, or log2 of it (invl_log2: the forward ran its per-row-shift form)
   int invl_log2;
@@ -52,13 +53,16 @@ struct BwdParams {
   int dkv_splits;           // > 1: the dK/dV kernel splits the QUERY range over gridDim.y workgroups, partial f32 slabs
   int64_t dkv_split_stride; //      byte distance between the dk (and dv) slabs of consecutive splits
   int B, H, N, M;
+  int kv_group;             // query heads per K/V head (see FwdParams)
+  int kv_sweep;             // 1: the dK/dV kernel runs its group-sweep form -- one workgroup per (batch, K/V head, key tile) walks the kv_group
+                            //    query heads of its group and writes the summed dK / dV once (16-bit, no bias, no split; kv_group > 1)
   int causal, bias_batch;
   float c1, c2, bias_c;
   float scale;
   int q_scaled;             // see FwdParams
   // fused l2norm backward in the epilogues (group size multiple of 8 with a power-of-two number of 8-blocks):
   const float* rq;          // [B,H,N,G] inverse norms of q, or nullptr: dq kernel writes plain dQ^ (dtype or f32 slab)
-  const float* rk;          // [B,H,M,G] inverse norms of k, or nullptr (never set for single-headed K/V)
+  const float* rk;          // [B,Hk,M,G] inverse norms of k, or nullptr (set for Hk == H and for the group sweep only)
   int G, lgm;               // groups; log2(group size / 8)
   float norm_eps;           // 1e-12
 };
@@ -75,7 +79,7 @@ struct NormParams {         // grouped l2norm forward:  x -> xn, inv_norm
 struct NormBwdParams {      // dx = reduce_heads(slab) then (optionally) l2norm backward
   const char* slab;         // [B,HS,L,D] contiguous; element type f32 (slab_f32) or dtype
   int slab_f32;
-  int HS;                   // heads in the slab (summed down to HO when HS != HO)
+  int HS;                   // heads in the slab: output head ho sums the contiguous slab heads [ho * HS / HO, (ho + 1) * HS / HO)
   const char* xn;           // contiguous [B,HO,L,D] normalised input (dtype) or nullptr (no norm)
   const float* inv_norm;    // [B,HO,L,G]
   View dx;                  // [B,HO,L,D] out (dtype)
@@ -131,6 +135,10 @@ hipError_t launch_forward_wide128(int dtype, const FwdParams& p, hipStream_t s);
 hipError_t launch_backward_dq(int dtype, int D, const BwdParams& p, hipStream_t s);
 hipError_t launch_backward_dbias(int dtype, int D, const BwdParams& p, hipStream_t s);   // d_bias from recomputed dS tiles (after dq: needs delta)
 hipError_t launch_backward_dkv(int dtype, int D, const BwdParams& p, hipStream_t s);
+// the group-sweep dK/dV form (BwdParams::kv_sweep): whether it is compiled for (dtype, D), and whether the dispatch takes it for a grid of
+// batch_kv_heads * key tiles (mode: 0 never, 1 where the sweep grid covers the chip, 2 wherever it is compiled)
+bool backward_dkv_sweep(int dtype, int D, int64_t batch_kv_heads, int N, int M, int causal, int mode);
+int kv_group_mode(int set);             // debug knob behind fcsa_debug_kv_group_form: set < 0 queries; returns the previous value
 hipError_t launch_l2norm(int dtype, const NormParams& p, hipStream_t s);
 hipError_t launch_l2norm_pair(int dtype, const NormParams& a, const NormParams& b, hipStream_t s);   // q and k in one grid
 hipError_t launch_l2norm_bwd(int dtype, const NormBwdParams& p, hipStream_t s);

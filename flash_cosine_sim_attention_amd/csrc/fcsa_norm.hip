@@ -175,12 +175,14 @@ FCSA_DEV void l2norm_bwd_rows(const NormBwdParams& p, int block) {
   int b = 0, h = 0, l = 0;
   if (m.active) {
     split_row(m.row, nrows, p.L, p.HO, b, h, l);
-    const int nsum = (p.HS == p.HO) ? 1 : p.HS;
+    // output head h sums the contiguous slab heads [h * nsum, (h + 1) * nsum): HS == HO is a copy (+ l2norm backward), HO == 1 the sum of
+    // every slab head, anything between a grouped-query K/V head (its H / Hk query heads, times the split-query slabs of each)
+    const int nsum = p.HS / p.HO;
     if (p.slab_f32) {
       // f32 slabs: the loads of FOUR slabs (8 x 16 bytes per lane) are issued before the first add -- the head loop is the whole kernel
       // (single-headed K/V at C5: 8 slabs of 33.5 MB each way), and one slab per iteration left a single dependent load pair in flight
       const int64_t hstride = (int64_t)p.L * p.D * 4;
-      const char* s0 = p.slab + ((((int64_t)b * p.HS + (p.HS == p.HO ? h : 0)) * p.L + l) * p.D + m.c * 8) * 4;
+      const char* s0 = p.slab + ((((int64_t)b * p.HS + (int64_t)h * nsum) * p.L + l) * p.D + m.c * 8) * 4;
       int hs = 0;
       for (; hs + 4 <= nsum; hs += 4) {
         f32x4 a[4], c[4];
@@ -203,7 +205,7 @@ FCSA_DEV void l2norm_bwd_rows(const NormBwdParams& p, int block) {
       }
     } else {
       for (int hs = 0; hs < nsum; ++hs) {
-        const int64_t srow = ((int64_t)b * p.HS + (p.HS == p.HO ? h : hs)) * p.L + l;
+        const int64_t srow = ((int64_t)b * p.HS + (int64_t)h * nsum + hs) * p.L + l;
         float t[8];
         load8<T>(p.slab + (srow * p.D + m.c * 8) * Traits<T>::ES, t);
 #pragma unroll
@@ -265,13 +267,13 @@ __global__ void __launch_bounds__(256) l2norm_bwd_generic_kernel(const NormBwdPa
   const int l = (int)(row - bh * p.L);
   const int b = (int)(bh / p.HO), h = (int)(bh - (int64_t)b * p.HO);
   const int dg = p.D / p.G;
-  const int nsum = (p.HS == p.HO) ? 1 : p.HS;
+  const int nsum = p.HS / p.HO;      // output head h sums slab heads [h * nsum, (h + 1) * nsum) (see l2norm_bwd_rows)
   const E* xn = p.xn ? reinterpret_cast<const E*>(p.xn) + row * p.D + gi * dg : nullptr;
   E* dx = reinterpret_cast<E*>(p.dx.p + (int64_t)b * p.dx.sb + (int64_t)h * p.dx.sh + (int64_t)l * p.dx.sn) + gi * dg;
   auto grad = [&](int e) {
     float s = 0.f;
     for (int hs = 0; hs < nsum; ++hs) {
-      const int64_t srow = ((int64_t)b * p.HS + (p.HS == p.HO ? h : hs)) * p.L + l;
+      const int64_t srow = ((int64_t)b * p.HS + (int64_t)h * nsum + hs) * p.L + l;
       const int64_t o = srow * p.D + gi * dg + e;
       s += p.slab_f32 ? reinterpret_cast<const float*>(p.slab)[o] : (float)reinterpret_cast<const E*>(p.slab)[o];
     }

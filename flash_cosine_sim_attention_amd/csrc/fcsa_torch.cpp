@@ -122,7 +122,9 @@ Canon canonicalise(const Tensor& q, const Tensor& k, const Tensor& v, const opti
   TORCH_CHECK_VALUE(c.D == 16 || c.D == 32 || c.D == 64 || c.D == 96 || c.D == 128,
                     "only dimensions (16, 32, 64, 96, 128) allowed for now, got ", c.D);                            // cu:1674
   TORCH_CHECK_VALUE(c.k.size(0) == c.B, "batch mismatch between q (", c.B, ") and k/v (", c.k.size(0), ")");
-  TORCH_CHECK_VALUE(c.Hk == c.H || c.Hk == 1, "k/v heads must equal q heads (", c.H, ") or be 1 (single-headed key/values), got ", c.Hk);
+  // grouped-query attention: query head h reads K/V head h / (H / Hk); single-headed (Hk == 1) and Hk == H are the two ends
+  TORCH_CHECK_VALUE(c.Hk == c.H || (c.Hk >= 1 && c.H % c.Hk == 0),
+                    "k/v heads must divide q heads (", c.H, "): grouped-query attention needs H % Hk == 0, got Hk = ", c.Hk);
   if (mask.has_value()) {
     TORCH_CHECK_VALUE(mask->scalar_type() == at::kBool && mask->dim() == 2 && mask->size(0) == c.B && mask->size(1) == c.M,
                       "mask must be a bool tensor of shape (", c.B, ", ", c.M, "), got ", mask->scalar_type(), " ", mask->sizes());

@@ -72,8 +72,9 @@ def plain_cosine_sim_attention(q, k, v, mask=None, attn_bias=None, scale=8, grou
             raise AssertionError("if batch and heads are merged for queries, keys and values must also similarly have only 3 dimensions")
         attn_bias_batch_dim, q = True, q.unsqueeze(1)
     q, k = l2norm_tensors(q, k, groups=groups) if l2norm_qk else (q, k)
-    keys = k.unsqueeze(1) if k.dim() == 3 else k       # single-headed K/V broadcast over the heads
-    values = v.unsqueeze(1) if v.dim() == 3 else v
+    # single-headed K/V broadcast over the heads; grouped-query K/V (Hk dividing H) repeated over each group
+    keys = _cpu.expand_kv_heads(k.unsqueeze(1) if k.dim() == 3 else k, q.shape[1])
+    values = _cpu.expand_kv_heads(v.unsqueeze(1) if v.dim() == 3 else v, q.shape[1])
     logits = torch.matmul(q, keys.transpose(-1, -2)) * scale
     if attn_bias is not None:
         logits = logits + attn_bias.unsqueeze(1 if attn_bias_batch_dim else 0)
@@ -132,6 +133,8 @@ def flash_cosine_sim_attention(q, k, v, mask=None, attn_bias=None, scale=8, grou
     """Fused cosine-similarity attention; signature of flash_cosine_sim_attention.py:308-319.
 
     GPU tensors: hand-written gfx950 kernels, forward and backward (gradients w.r.t. the raw q, k, v, attn_bias).
+    k, v: [B, Hk, M, D] with Hk dividing H (Hk == H; grouped-query attention, query head h attending to K/V head h // (H // Hk);
+    or 3-D single-headed K/V); dk, dv have the shape of k, v (sums over each group's query heads).
     CPU tensors: forward-only blockwise path (`cpu.attention_forward_cpu`), like the reference (py:322-323).
     Any finite scale runs (see the module docstring for the exponent-shift regimes)."""
     if q.device.type == "cpu":

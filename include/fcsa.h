@@ -16,8 +16,10 @@
  *
  * Layout conventions
  *   q, o, d_out, dq        : [B, H, N, D]          (reference accessor order, cu:30-35)
- *   k, v, dk, dv           : [B, Hk, M, D], Hk == H, or Hk == 1 for single-headed key/values
- *                            (reference: 3-D k/v unsqueezed at cu:1656-1660, is_single_head_kv cu:1679)
+ *   k, v, dk, dv           : [B, Hk, M, D], Hk a divisor of H: Hk == H, Hk == 1 for single-headed key/values
+ *                            (reference: 3-D k/v unsqueezed at cu:1656-1660, is_single_head_kv cu:1679), or grouped-query
+ *                            attention in between: query head h attends to K/V head h / (H / Hk) (the repeat_interleave
+ *                            convention), and dk / dv are the sums over the H / Hk query heads of each group
  *   mask                   : [B, M] bytes, non-zero = keep   (cu:1208-1211; torch.bool storage)
  *   attn_bias              : [Hb, N, M], Hb == H (per head) or Hb == B when bias_batch_dim (cu:1168, cu:1214)
  *   inv_l                  : [B, H, N] float32 = 1 / max(rowsum, eps): the row sums are taken with a library-chosen
@@ -73,7 +75,7 @@ typedef struct fcsa_problem {
   int32_t dtype;            /* fcsa_dtype of q,k,v,o,grads,bias */
   int32_t batch;            /* B */
   int32_t heads;            /* H */
-  int32_t kv_heads;         /* H or 1 */
+  int32_t kv_heads;         /* Hk: a divisor of H (H, 1, or grouped-query K/V in between) */
   int32_t q_len;            /* N */
   int32_t k_len;            /* M */
   int32_t dim_head;         /* D in {16,32,64,96,128} (cu:84) */
@@ -155,7 +157,10 @@ typedef struct fcsa_backward_args {
                                     cu:1574-1576, then a cast pass, cu:1912).  No zero-fill, no cast needed. */
   void*           workspace;     /* >= fcsa_backward_workspace_bytes(&p) bytes, 256-byte aligned: delta [B,H,N] f32, plus f32
                                     slabs where an epilogue cannot finish the job -- partial dq of the split-key dQ kernel, partial
-                                    dk / dv of the split-query dK/dV kernel and of single-headed K/V, l2norm groups that are not
+                                    dk / dv of the split-query dK/dV kernel and per-query-head dk / dv of K/V with fewer heads than
+                                    the query (single-headed, or grouped where the group-sweep kernel does not run: it sums a
+                                    group's heads in registers, but the size is reserved for the slab route that a launch with an
+                                    attn_bias takes), l2norm groups that are not
                                     8 * 2^k features wide (one group over the whole head counts as fused at any D: D = 96).  The split forms also need dq (dk, dv) with stride0 == heads * stride1;
                                     other layouts run the unsplit kernels. */
   size_t          workspace_bytes;
@@ -217,6 +222,14 @@ int fcsa_profile_collect(fcsa_kernel_stat* stats, int32_t capacity);
  * un-rounded vs the rounded P~: DESIGN.md section 5), so results are form-dependent at that level; callers that need
  * form-independent bits pin the form with this call. */
 int fcsa_debug_forward_form(int32_t form);
+
+/* Debug knob: which dK/dV form grouped-query problems (1 < kv_heads < heads) take.  form = 1: automatic (the default) -- the group-sweep
+ * kernel, one workgroup per (batch, K/V head, key tile) summing its group's query heads in registers, for bias-free 16-bit D = 64 / 128
+ * problems whose sweep grid covers the chip; per-query-head f32 slabs + the finalize kernel otherwise.  form = 0: never the sweep;
+ * form = 2: the sweep wherever it is compiled, small grids included; form < 0: query only.  Returns the previous setting.  Not read from
+ * the environment.  fcsa_backward_workspace_bytes follows the setting in force when it is called.  The two forms sum the heads in a
+ * different order, so their dk / dv agree to float32 rounding, not bit for bit; each is deterministic. */
+int fcsa_debug_kv_group_form(int32_t form);
 
 /* Message for the last non-OK status returned on this thread ("" if none). */
 const char* fcsa_last_error(void);
