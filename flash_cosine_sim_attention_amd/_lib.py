@@ -164,16 +164,16 @@ def kv_group_form(form: int) -> int:
 
 
 def source_sha256() -> str:
-    """sha256 over the kernel sources and the build recipe (csrc/*.hip, *.cuh, *.h, Makefile, include/fcsa.h; names and bytes, sorted):
-    what measurement files in profiles/ are keyed on.  The library BINARY is not reproducible bit for bit (two clean builds of one
+    """sha256 over the kernel sources and the build recipe (csrc/*.hip, *.cuh, *.h, csrc/dev/*, Makefile, include/fcsa.h; names and bytes,
+    sorted): what measurement files in profiles/ are keyed on.  The library BINARY is not reproducible bit for bit (two clean builds of one
     tree differ in a few bytes), so a hash of the .so would orphan every committed measurement at the first rebuild."""
     import hashlib
     h = hashlib.sha256()
-    files = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".cuh", ".h", ".cpp")) or f == "Makefile"]
-    files.append(HEADER)
-    for f in files:
-        h.update(os.path.basename(f).encode() + b"\0")
-        h.update(open(f, "rb").read())
+    names = [f for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".cuh", ".h", ".cpp")) or f == "Makefile"]
+    names += ["dev/" + f for f in sorted(os.listdir(os.path.join(CSRC, "dev")))]
+    for name, path in [(n, os.path.join(CSRC, n)) for n in names] + [(os.path.basename(HEADER), HEADER)]:
+        h.update(name.encode() + b"\0")
+        h.update(open(path, "rb").read())
     return h.hexdigest()
 
 

@@ -33,19 +33,10 @@
 
 #include "fcsa_common.cuh"
 #include "fcsa_kernels.h"
-#ifdef FCSA_VAR_SPLIT_ENV
-#include "dev/fcsa_sweep_env.h"
-#endif
 
 namespace fcsa {
 // Tuning constants (each settled by a same-box A/B on MI355X; the rejected alternatives are listed in DESIGN.md §8):
-constexpr int kDq2WBytes = 128;      // row bytes D*ES up to which the dQ kernel runs its 8-wave form (two waves / SIMD, one workgroup per CU)
-// Two waves per SIMD (<= 256 registers) for the dQ kernel (template parameter TWO): always for rows up to 128 bytes, and -- round 3 --
-// for 16-bit rows up to 256 bytes (D = 96, 128) in the 4-wave form WHEN the grid puts two 128-row workgroups on every CU, whose waves
-// then hide each other's LDS latency (launch_dq_b).  Those widths ran one wave per SIMD before (435 registers at D = 128), at ~40 %
-// of what the same kernel reaches at D = 64; smaller grids still do (a lone wave is better off with the pipelined tile).
-template <typename T, int D> constexpr bool dq_can_two_waves() { return D * Traits<T>::ES <= (Traits<T>::ES == 2 ? 256 : 128); }
-constexpr int kDkv2WBytes = 128;     // same for the dKV kernel
+// (kDq2WBytes, kDkv2WBytes, dq_can_two_waves: fcsa_dispatch.h)
 constexpr int kDqSub8 = 4;           // 64-key tiles per LDS stage of the 8-wave dQ kernel (16 bit): one barrier per 256 keys
 constexpr bool kDqSplitFirstStage = true;      // cold first stage of a dQ pass requested in two parts (bwd_dq_kernel, SPLIT0)
 constexpr int kDkvBmq8 = 128;        // staged query rows of the 8-wave dKV kernel
@@ -243,7 +234,7 @@ template <typename T, int D, int NW, bool BIAS, int SUB, bool TWO, bool KM, bool
 __global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const BwdParams p) {
   static_assert(!KSPLIT || (NW == 8 && TWO && SUB == 2 && Traits<T>::ES == 2), "key-split form: 8 waves, two-wave tile, 16 bit, 2 tiles per stage");
   // (same type and value as p.causal: the causal instantiations compile to what they were.  The key-split form's !KM twin is only ever
-  //  launched causal -- launch_dq_b -- and says so: at 256-byte rows the kernel sits at its 256 registers)
+  //  launched causal -- choose_dq -- and says so: at 256-byte rows the kernel sits at its 256 registers)
   const int causal = KM ? 0 : KSPLIT ? 1 : p.causal;
   typedef TileGeom<D, Traits<T>::ES> G;
   typedef Traits<T> TR;
@@ -907,11 +898,7 @@ static hipError_t launch_dbias_t(const BwdParams& p, hipStream_t s) {
   const int MT = (p.N + 127) / 128, KT = (p.M + 63) / 64;
   const int64_t owners = p.bias_batch ? p.B : p.H;
   const size_t lds = 2 * 64 * TileGeom<D, Traits<T>::ES>::ROWB + 4 * 32 * (64 * 4 + 16);
-  auto kern = bwd_dbias_kernel<T, D>;
-  static std::atomic<uint64_t> lds_ok{0};
-  if (hipError_t e = ensure_dynamic_lds(kern, lds, lds_ok); e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(owners * MT), (unsigned)KT), dim3(256), lds, s, p);
-  return hipGetLastError();
+  return launch_with_lds<bwd_dbias_kernel<T, D>>(dim3((unsigned)(owners * MT), (unsigned)KT), dim3(256), lds, s, p);
 }
 
 // =============================================================================================
@@ -1698,40 +1685,6 @@ extern "C" int fcsa_trace_read_dkv(unsigned long long* out) {
 namespace fcsa {
 #endif
 
-// key-split forms of the backward kernels (bwd_dq_kernel<.., KSPLIT>): 16-bit, no bias, the head dims the forward has it for
-template <typename T, int D, bool BIAS> constexpr bool bwd_ksplit() {
-  return Traits<T>::ES == 2 && !BIAS && (D == 16 || D == 32 || D == 64 || D == 96 || D == 128);
-}
-
-// ---------------------------------------------------------------------------------------------
-// 8 waves per workgroup when the grid still gives every CU a workgroup (see row_tile_waves in fcsa_fwd.hip), else 4
-// tail: the last-round rule (below): 1 = dK/dV (and the forward, fcsa_fwd.hip row_tile_waves), 2 = dQ
-static int tile_waves(int64_t batch_heads, int len, bool causal, bool bits16 = false, int tail = 0) {
-  const int MT = (len + 255) / 256, cus = cu_count();
-  const int64_t w256 = batch_heads * (causal ? (MT + 1) / 2 : MT);
-  // More 256-position workgroups than CUs, 16-bit (round 6, profiles/r06_form_sweep_big*.txt): the LAST round decides.  A last round that
-  // fills at most ~55 % of the CUs costs the 8-wave form a whole 256-position workgroup time; as 4-wave workgroups the same tail is
-  // 128-position workgroups running alone on their CUs: dK/dV -5 ... -9 % at 264 ... 384, 544 ... 640, 800, 1088 workgroups on 256 CUs
-  // (D = 128 lean form against the pipelined 4-wave form: -8 ... -12 % at 264 ... 352), full or nearly full last rounds keep the 8-wave
-  // form.  dQ: the 4-wave form wins whenever the last round is not full (-3 ... -25 %); with whole rounds the 8-wave form is ahead (C3,
-  // one round: 6 %; (8,8,4096,64) causal, two rounds: 4 %, profiles/r06_ab_forms_tail.txt).
-  if (bits16 && tail != 0 && w256 > cus) {
-    const int64_t rem = w256 % cus;
-    if (tail == 2) return rem != 0 ? 4 : 8;
-    return (rem != 0 && rem * 20 <= (int64_t)cus * 11) ? 4 : 8;
-  }
-  if (w256 >= cus * 7 / 8) return 8;
-  // 16-bit types (round 6, tools/form_sweep.py): once the 128-position tiles outnumber the CUs -- where the split-halves 8-wave forms no
-  // longer apply -- the 256-position 8-wave workgroup wins from 132 workgroups on 256 CUs up, not only from 7/8 of the CUs: rows <= 128
-  // bytes dQ -3 ... -10 %, dK/dV -10 ... -20 % (profiles/r06_form_sweep_d64_b.txt); D = 96 / 128 lean dK/dV -15 ... -20 %
-  // (profiles/r06_form_sweep_d128_b.txt)
-  if (bits16) {
-    const int MT4 = (len + 127) / 128;
-    if (batch_heads * (causal ? (MT4 + 1) / 2 : MT4) > cus) return 8;
-  }
-  return 4;
-}
-
 template <typename T, int D, bool BIAS, int NW, bool TWO, bool KSPLIT = false>
 static hipError_t launch_dq_nw(const BwdParams& p, hipStream_t s) {
   constexpr int RWAVES = KSPLIT ? NW / 2 : NW, BM = 32 * RWAVES;
@@ -1747,57 +1700,31 @@ static hipError_t launch_dq_nw(const BwdParams& p, hipStream_t s) {
   // (two instantiations, see launch_fwd_nw.  The two-wave form of 256-byte rows sits at its 256 registers: its non-causal
   //  instantiation came out with spill reloads inside the tile loops -- +5.6 % time -- so those launches keep the general kernel)
   constexpr bool GENERAL_ONLY = TWO && D * Traits<T>::ES >= 256;      // (its non-causal twin is not even instantiated)
-  if (p.causal || GENERAL_ONLY) {
-    auto kern = bwd_dq_kernel<T, D, NW, BIAS, SUB, TWO, false, KSPLIT>;
-    static std::atomic<uint64_t> lds_ok{0};
-    if (hipError_t e = ensure_dynamic_lds(kern, lds, lds_ok); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, s, p);
-  } else if constexpr (!GENERAL_ONLY) {
-    auto kern = bwd_dq_kernel<T, D, NW, BIAS, SUB, TWO, true, KSPLIT>;
-    static std::atomic<uint64_t> lds_ok{0};
-    if (hipError_t e = ensure_dynamic_lds(kern, lds, lds_ok); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, s, p);
+  if constexpr (!GENERAL_ONLY) {
+    if (!p.causal) return launch_with_lds<bwd_dq_kernel<T, D, NW, BIAS, SUB, TWO, true, KSPLIT>>(grid, dim3(NW * 64), lds, s, p);
   }
-  return hipGetLastError();
+  return launch_with_lds<bwd_dq_kernel<T, D, NW, BIAS, SUB, TWO, false, KSPLIT>>(grid, dim3(NW * 64), lds, s, p);
 }
 
+// the instantiation of form f (choose_dq, fcsa_dispatch.h)
 template <typename T, int D, bool BIAS>
-static hipError_t launch_dq_b(const BwdParams& p, hipStream_t s) {
-  constexpr bool NARROW = D * Traits<T>::ES <= kDq2WBytes;      // rows <= 128 bytes: two waves per SIMD whatever the grid
-  if (p.dq_splits > 1) return launch_dq_nw<T, D, BIAS, 4, NARROW>(p, s);       // split-key path: 128-row tiles x key ranges (the key-split form measured level there)
-#ifdef FCSA_VAR_SPLIT_ENV      // sweep builds only (tools/form_sweep.py): FCSA_DQ_FORM = 1 row tiles of 8 waves, 2 key-split 8 waves, 3 four waves
-  if constexpr (NARROW && bwd_ksplit<T, D, BIAS>()) {
-    const int f = fcsa_dev::env_int("FCSA_DQ_FORM");
-    if (f == 1) return launch_dq_nw<T, D, BIAS, 8, true>(p, s);
-    if (f == 2) return launch_dq_nw<T, D, BIAS, 8, true, true>(p, s);
-    if (f == 3) return launch_dq_nw<T, D, BIAS, 4, NARROW>(p, s);
-  } else if constexpr (!NARROW && dq_can_two_waves<T, D>() && !BIAS && bwd_ksplit<T, D, BIAS>()) {      // 16-bit D = 96 / 128: 1 = four waves, two-wave tile, 2 = key-split 8 waves (causal), 3 = four waves, one per SIMD
-    const int f = fcsa_dev::env_int("FCSA_DQ_FORM");
-    if (f == 1) return launch_dq_nw<T, D, BIAS, 4, true>(p, s);
-    if (f == 2 && p.causal) return launch_dq_nw<T, D, BIAS, 8, true, true>(p, s);
-    if (f == 3) return launch_dq_nw<T, D, BIAS, 4, NARROW>(p, s);
+static hipError_t launch_dq_form(DqForm f, const BwdParams& p, hipStream_t s) {
+  constexpr int ES = Traits<T>::ES;
+  constexpr bool NARROW = D * ES <= kDq2WBytes;      // rows <= 128 bytes: two waves per SIMD whatever the grid
+  switch (f) {
+    case DqForm::Waves4:
+      return launch_dq_nw<T, D, BIAS, 4, NARROW>(p, s);
+    case DqForm::Waves4Two:
+      if constexpr (NARROW || (dq_can_two_waves(ES, D) && !BIAS)) return launch_dq_nw<T, D, BIAS, 4, true>(p, s);
+      break;
+    case DqForm::Waves8:
+      if constexpr (NARROW) return launch_dq_nw<T, D, BIAS, 8, true>(p, s);
+      break;
+    case DqForm::KSplit8:
+      if constexpr (bwd_ksplit(ES, D, false) && (NARROW || (dq_can_two_waves(ES, D) && !BIAS))) return launch_dq_nw<T, D, BIAS, 8, true, true>(p, s);
+      break;
   }
-#endif
-  if constexpr (NARROW) {
-    if (tile_waves((int64_t)p.B * p.H, p.N, p.causal, Traits<T>::ES == 2, 2) == 8) return launch_dq_nw<T, D, BIAS, 8, true>(p, s);
-    if constexpr (bwd_ksplit<T, D, false>()) {      // at most one 128-row workgroup per CU: its wave halves split the keys
-      const int MT4 = (p.N + 127) / 128;
-      if ((int64_t)p.B * p.H * (p.causal ? (MT4 + 1) / 2 : MT4) <= cu_count()) return launch_dq_nw<T, D, BIAS, 8, true, true>(p, s);
-    }
-  } else if constexpr (dq_can_two_waves<T, D>() && !BIAS) {
-    // two waves per SIMD need two 128-row workgroups on every CU; smaller grids keep the one-wave (pipelined) form
-    // (bias launches keep the one-wave form too: their two-wave instantiation spills 17 registers and was never measured ahead)
-    const int MT4 = (p.N + 127) / 128;
-    // (round 6: from MORE 128-row workgroups than CUs on -- rounds 3 - 5 asked for 7/4 of the CUs; at 264 ... 416 workgroups on 256 CUs the two-wave
-    //  tile is 19 - 28 % faster than the one-wave and key-split forms: profiles/r06_form_sweep_d128_b.txt)
-    if ((int64_t)p.B * p.H * (p.causal ? (MT4 + 1) / 2 : MT4) > cu_count()) return launch_dq_nw<T, D, BIAS, 4, true>(p, s);
-    // fewer: the same tile, 8 waves on 128 rows.  Causal launches only: 256-byte rows have no non-causal instantiation of the two-wave tile
-    // (GENERAL_ONLY in launch_dq_nw), and the general one measured +6 % there against the one-wave pipelined form
-    if constexpr (bwd_ksplit<T, D, BIAS>()) {
-      if (p.causal) return launch_dq_nw<T, D, BIAS, 8, true, true>(p, s);
-    }
-  }
-  return launch_dq_nw<T, D, BIAS, 4, NARROW>(p, s);
+  return hipErrorInvalidValue;
 }
 
 template <typename T, int D, bool BIAS, int NW, bool LEAN = false, bool QSPLIT = false, bool SWEEP = false>
@@ -1822,24 +1749,10 @@ static hipError_t launch_dkv_nw(const BwdParams& p, hipStream_t s) {
   size_t lds = DkvLds<T, D, NW, BMQ, BIAS, LEAN, RING ? 3 : 2>::TOTAL + (BIAS ? (size_t)NW * BiasBlock<T>::BYTES : 0);
   if (QSPLIT && lds < (size_t)(NW / 2) * 64 * 16 * TileGeom<D, Traits<T>::ES>::DB * 8) lds = (size_t)(NW / 2) * 64 * 16 * TileGeom<D, Traits<T>::ES>::DB * 8;
   const dim3 grid((unsigned)(p.B * (SWEEP ? p.H / p.kv_group : p.H) * PT), (unsigned)(p.dkv_splits > 1 ? p.dkv_splits : 1));
-  if (p.causal) {        // (two instantiations, see launch_fwd_nw)
-    auto kern = bwd_dkv_kernel<T, D, NW, BMQ, BIAS, LEAN, false, RING, QSPLIT, SWEEP>;
-    static std::atomic<uint64_t> lds_ok{0};
-    if (hipError_t e = ensure_dynamic_lds(kern, lds, lds_ok); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, s, p);
-  } else {
-    auto kern = bwd_dkv_kernel<T, D, NW, BMQ, BIAS, LEAN, true, RING, QSPLIT, SWEEP>;
-    static std::atomic<uint64_t> lds_ok{0};
-    if (hipError_t e = ensure_dynamic_lds(kern, lds, lds_ok); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, s, p);
-  }
-  return hipGetLastError();
+  // (two instantiations, see launch_fwd_nw)
+  return p.causal ? launch_with_lds<bwd_dkv_kernel<T, D, NW, BMQ, BIAS, LEAN, false, RING, QSPLIT, SWEEP>>(grid, dim3(NW * 64), lds, s, p)
+                  : launch_with_lds<bwd_dkv_kernel<T, D, NW, BMQ, BIAS, LEAN, true, RING, QSPLIT, SWEEP>>(grid, dim3(NW * 64), lds, s, p);
 }
-
-// Group-sweep dK/dV (grouped-query attention): compiled for the 8-wave forms of 16-bit D = 64 (pipelined ring tile) and D = 128 (lean tile),
-// the forms the dispatch below picks for key grids that cover the chip.  The C ABI takes it (BwdParams::kv_sweep) where the sweep grid --
-// batch x K/V heads x 256-key tiles -- gets the 8-wave form by the same rule (tile_waves), else it keeps per-query-head slabs + finalize.
-template <typename T, int D, bool BIAS> constexpr bool dkv_has_sweep() { return Traits<T>::ES == 2 && !BIAS && (D == 64 || D == 128); }
 
 static std::atomic<int> g_kv_group_mode{1};
 int kv_group_mode(int set) {
@@ -1847,96 +1760,57 @@ int kv_group_mode(int set) {
   return g_kv_group_mode.exchange(set > 2 ? 2 : set, std::memory_order_relaxed);
 }
 
-bool backward_dkv_sweep(int dtype, int D, int64_t batch_kv_heads, int N, int M, int causal, int mode) {
-  (void)N;
-  if ((dtype != 1 && dtype != 2) || (D != 64 && D != 128) || mode <= 0) return false;
-  return mode >= 2 || tile_waves(batch_kv_heads, M, causal != 0, true, 1) == 8;
-}
-
+// the instantiation of form f (choose_dkv, fcsa_dispatch.h)
 template <typename T, int D, bool BIAS>
-static hipError_t launch_dkv_b(const BwdParams& p, hipStream_t s) {
-  if (p.kv_sweep) {
-    if constexpr (dkv_has_sweep<T, D, BIAS>()) {
-      if constexpr (D * Traits<T>::ES <= kDkv2WBytes) return launch_dkv_nw<T, D, BIAS, 8, false, false, true>(p, s);
-      else return launch_dkv_nw<T, D, BIAS, 8, true, false, true>(p, s);
-    }
-    return hipErrorInvalidValue;      // (the C ABI only sets kv_sweep where backward_dkv_sweep said so)
+static hipError_t launch_dkv_form(DkvForm f, const BwdParams& p, hipStream_t s) {
+  constexpr int ES = Traits<T>::ES;
+  constexpr bool NARROW = D * ES <= kDkv2WBytes;
+  switch (f) {
+    case DkvForm::Waves4:
+      return launch_dkv_nw<T, D, BIAS, 4>(p, s);
+    case DkvForm::Waves8:
+      if constexpr (NARROW) return launch_dkv_nw<T, D, BIAS, 8>(p, s);
+      break;
+    case DkvForm::Lean8:
+      if constexpr (ES == 2 && !BIAS && !NARROW && D * ES <= 256) return launch_dkv_nw<T, D, BIAS, 8, true>(p, s);
+      break;
+    case DkvForm::QSplit8:
+      if constexpr (NARROW && bwd_ksplit(ES, D, false)) return launch_dkv_nw<T, D, BIAS, 8, false, true>(p, s);
+      break;
+    case DkvForm::Sweep:
+      if constexpr (dkv_has_sweep(ES, D, BIAS)) return launch_dkv_nw<T, D, BIAS, 8, !NARROW, false, true>(p, s);
+      break;
   }
-  if (p.dkv_splits > 1) return launch_dkv_nw<T, D, BIAS, 4>(p, s);       // split-query path: 128-key tiles x query ranges
-#ifdef FCSA_VAR_SPLIT_ENV      // sweep builds only: FCSA_DKV_FORM = 1 key tiles of 8 waves, 2 query-split 8 waves, 3 four waves
-  if constexpr (D * Traits<T>::ES <= kDkv2WBytes && bwd_ksplit<T, D, BIAS>() && (D == 64 || D == 32 || D == 16)) {
-    const int f = fcsa_dev::env_int("FCSA_DKV_FORM");
-    if (f == 1) return launch_dkv_nw<T, D, BIAS, 8>(p, s);
-    if (f == 2) return launch_dkv_nw<T, D, BIAS, 8, false, true>(p, s);
-    if (f == 3) return launch_dkv_nw<T, D, BIAS, 4>(p, s);
-  } else if constexpr (Traits<T>::ES == 2 && !BIAS && D * Traits<T>::ES > kDkv2WBytes && D * Traits<T>::ES <= 256) {      // 16-bit D = 96 / 128: 1 = lean 8 waves, 3 = four waves (pipelined, one per SIMD)
-    const int f = fcsa_dev::env_int("FCSA_DKV_FORM");
-    if (f == 1) return launch_dkv_nw<T, D, BIAS, 8, true>(p, s);
-    if (f == 3) return launch_dkv_nw<T, D, BIAS, 4>(p, s);
-  }
-#endif
-  if constexpr (D * Traits<T>::ES <= kDkv2WBytes) {
-    if (tile_waves((int64_t)p.B * p.H, p.M, p.causal, Traits<T>::ES == 2, 1) == 8) return launch_dkv_nw<T, D, BIAS, 8>(p, s);
-    if constexpr (bwd_ksplit<T, D, false>() && (D == 64 || D == 32 || D == 16)) {      // at most one 128-key workgroup per CU: its wave halves split the queries
-      const int KT4 = (p.M + 127) / 128;
-      // (from 512 queries: below, the four or fewer 128-row tiles of a pass do not pay for the hand-over -- 23.5 vs 24.7 us at N = 333 / 777)
-      if (p.N >= 512 && (int64_t)p.B * p.H * (p.causal ? (KT4 + 1) / 2 : KT4) <= cu_count()) return launch_dkv_nw<T, D, BIAS, 8, false, true>(p, s);
-    }
-  } else if constexpr (Traits<T>::ES == 2 && !BIAS && D * Traits<T>::ES <= 256) {
-    // lean form (two waves per SIMD, V fragments from the LDS) where an 8-wave workgroup per CU still covers the chip; smaller grids
-    // keep the one-wave pipelined form.  (Two 4-wave workgroups per CU would do as well, but a grid with >= 448 of those always has
-    // >= 224 of the 8-wave ones.)
-    if (tile_waves((int64_t)p.B * p.H, p.M, p.causal, true, 1) == 8) return launch_dkv_nw<T, D, BIAS, 8, true>(p, s);
-  }
-  return launch_dkv_nw<T, D, BIAS, 4>(p, s);
+  return hipErrorInvalidValue;
 }
 
-template <typename T, int D> static hipError_t launch_dq_t(const BwdParams& p, hipStream_t s) {
-  return p.bias != nullptr ? launch_dq_b<T, D, true>(p, s) : launch_dq_b<T, D, false>(p, s);
+static BwdProblem bwd_problem(int dtype, int D, const BwdParams& p, int splits) {
+  return {dtype == 0 ? 4 : 2, D, (int64_t)p.B * p.H, p.N, p.M, p.causal != 0, p.bias != nullptr, splits, p.kv_sweep != 0};
 }
-template <typename T, int D> static hipError_t launch_dkv_t(const BwdParams& p, hipStream_t s) {
-  return p.bias != nullptr ? launch_dkv_b<T, D, true>(p, s) : launch_dkv_b<T, D, false>(p, s);
-}
-
-#ifdef FCSA_DEV_ONLY      // development builds: one instantiation (bf16, D = 64) for quick compiles / ISA inspection
-#ifndef FCSA_DEV_D
-#define FCSA_DEV_D 64
-#endif
-#define FCSA_DISPATCH_D(FN, T) if (D == FCSA_DEV_D) return FN<BF16, FCSA_DEV_D>(p, s); return hipErrorInvalidValue;
-#else
-#define FCSA_DISPATCH_D(FN, T)                      \
-  switch (D) {                                      \
-    case 16:  return FN<T, 16>(p, s);               \
-    case 32:  return FN<T, 32>(p, s);               \
-    case 64:  return FN<T, 64>(p, s);               \
-    case 96:  return FN<T, 96>(p, s);               \
-    case 128: return FN<T, 128>(p, s);              \
-    default:  return hipErrorInvalidValue;          \
-  }
-#endif
 
 hipError_t launch_backward_dbias(int dtype, int D, const BwdParams& p, hipStream_t s) {
   if (p.B * p.H == 0 || p.N == 0 || p.M == 0 || p.d_bias == nullptr || p.bias == nullptr) return hipSuccess;
-  if (dtype == 2) { FCSA_DISPATCH_D(launch_dbias_t, BF16) }
-  if (dtype == 1) { FCSA_DISPATCH_D(launch_dbias_t, F16) }
-  if (dtype == 0) { FCSA_DISPATCH_D(launch_dbias_t, F32) }
-  return hipErrorInvalidValue;
+  return dispatch_dtype_d(dtype, D, [&](auto td) { return launch_dbias_t<typename decltype(td)::T, decltype(td)::D>(p, s); });
 }
 
 hipError_t launch_backward_dq(int dtype, int D, const BwdParams& p, hipStream_t s) {
   if (p.B * p.H == 0 || p.N == 0) return hipSuccess;
-  if (dtype == 2) { FCSA_DISPATCH_D(launch_dq_t, BF16) }
-  if (dtype == 1) { FCSA_DISPATCH_D(launch_dq_t, F16) }
-  if (dtype == 0) { FCSA_DISPATCH_D(launch_dq_t, F32) }
-  return hipErrorInvalidValue;
+  const DqForm f = choose_dq(bwd_problem(dtype, D, p, p.dq_splits), cu_count());
+  return dispatch_dtype_d(dtype, D, [&](auto td) {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    return p.bias != nullptr ? launch_dq_form<T, DD, true>(f, p, s) : launch_dq_form<T, DD, false>(f, p, s);
+  });
 }
 
 hipError_t launch_backward_dkv(int dtype, int D, const BwdParams& p, hipStream_t s) {
   if (p.B * p.H == 0 || p.M == 0) return hipSuccess;
-  if (dtype == 2) { FCSA_DISPATCH_D(launch_dkv_t, BF16) }
-  if (dtype == 1) { FCSA_DISPATCH_D(launch_dkv_t, F16) }
-  if (dtype == 0) { FCSA_DISPATCH_D(launch_dkv_t, F32) }
-  return hipErrorInvalidValue;
+  const DkvForm f = choose_dkv(bwd_problem(dtype, D, p, p.dkv_splits), cu_count());
+  return dispatch_dtype_d(dtype, D, [&](auto td) {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    return p.bias != nullptr ? launch_dkv_form<T, DD, true>(f, p, s) : launch_dkv_form<T, DD, false>(f, p, s);
+  });
 }
 
 }  // namespace fcsa

@@ -5,9 +5,6 @@
 // cu:1889) and every launch goes to the caller's stream (cf. the default-stream launches cu:1720).
 #include "../../include/fcsa.h"
 #include "fcsa_kernels.h"
-#ifdef FCSA_VAR_SPLIT_ENV
-#include "dev/fcsa_sweep_env.h"
-#endif
 
 #include <algorithm>
 #include <cstdarg>
@@ -148,115 +145,6 @@ float rowsum_eps(const fcsa_problem& p, bool has_bias) {
   return e;
 }
 
-struct BwdLayout {
-  size_t delta, dq_slab, dk_slab, dv_slab, total;
-  bool need_dq_slab, need_dk_slab, need_dv_slab, fuse_norm;
-  bool kv_sweep;          // grouped-query K/V (1 < kv_heads < heads): a bias-free launch runs the group-sweep dK/dV kernel (no dk / dv slabs)
-  int dq_splits;          // > 1: split-key dQ kernel, dq_slab holds dq_splits partial slabs
-  int dkv_splits;         // > 1: split-query dK/dV kernel, dk_slab / dv_slab hold dkv_splits partial slabs each
-};
-
-// ---- split counts (forward keys / dQ keys / dK-dV queries) -------------------------------------------------------------------------
-// Where a problem's 128-position tiles (causal, since round 6: PAIRS of tiles) cannot fill the chip, several workgroups share one tile's loop range and write f32
-// partials that a second pass (fwd_combine_kernel / finalize) sums.  How many: rounds 2 - 5 took "enough workgroups for two per CU";
-// since round 6 the count is the argmin of a small cost model over s = 1 .. 16 (16-bit types; float32 keeps the old rule).  The model
-// prices, in microseconds on MI355X, what a launch with s splits costs:
-//   * the form the launchers run for that count: form A = the 8-wave one-workgroup-per-CU forms (forward: wave halves split the keys,
-//     fcsa_fwd.hip use_ksplit_fwd -- rows <= 128 bytes while tiles * s <= CUs, wider rows always; backward: whatever runs un-split),
-//     else 4-wave workgroups, one per CU (form B) or -- rows <= 128 bytes and more workgroups than CUs -- two per CU (form C);
-//   * a workgroup's time t0 + c * positions, t0 and c growing with D (the exponentials do not shrink with it: floor);
-//   * rounds of workgroups over the slots, a partly filled last round at alpha + (1 - alpha) * fill;
-//   * the second pass: a launch + s partial slabs read once.
-// Constants: least squares in log space over tools/split_sweep.py tables of 27 shapes x 7 counts per kernel, D = 16 .. 128
-// (profiles/r06_split_sweep_*.txt; tools/split_model_fit.py prints them and the table below).  Mean / worst regret of the model's choice
-// against the measured best: forward 0.9 / 10.9 %, dQ 0.3 / 4.5 %, dK/dV 0.2 / 3.6 %; the rule it replaces: 11.2 / 44 %, 8.9 / 42 %,
-// 11.8 / 52 % (it split 160 .. 224 tiles of a 2048-position problem three or four ways where the un-split 8-wave form is 30 - 50 %
-// faster, and took counts that leave a quarter-full last round).  The ONE definition both the workspace sizes and the launches use.
-struct SplitModel { double tA, cA, tB, cB, tC, cC, a0, b0, k0, k1, alpha; int slabs, extra; };
-static const SplitModel kSplitFwd = {5.57, 8.68, 3.61, 11.8, 5.77, 16.1, 0.0, 0.536, 7.77, 0.177, 0.585, 1, 1};
-static const SplitModel kSplitDq  = {11.3, 9.94, 2.35, 12.5, 1.0, 20.9, 0.369, 0.244, 12.2, 0.455, 0.526, 1, 0};
-static const SplitModel kSplitDkv = {11.5, 12.0, 2.25, 15.5, 1.0, 26.6, 0.11, 0.281, 13.5, 0.34, 0.528, 2, 0};
-// tiles: 128-position tiles the un-split grid has; rows: rows of ONE partial slab; len: positions the split loop runs over
-static double split_cost(const SplitModel& m, int D, int64_t tiles, int64_t rows, int len, int s, int cus, bool form_a) {
-  const bool wide = D * 2 > 128;
-  const double ft = m.a0 + (1.0 - m.a0) * D / 64.0, fc = m.b0 + (1.0 - m.b0) * std::max(0.44, D / 64.0);
-  const int64_t tot = tiles * s;
-  double t0 = m.tA, c = m.cA;
-  int64_t slots = cus;
-  if (!form_a) {
-    if (wide || tot <= cus) { t0 = m.tB; c = m.cB; }
-    else { t0 = m.tC; c = m.cC; slots = 2 * (int64_t)cus; }
-  }
-  const double per = t0 * ft + c * fc * ((double)len / s) / 1024.0;
-  const int64_t full = tot / slots, rem = tot % slots;
-  const double rounds = full == 0 ? 1.0 : (double)full + (rem == 0 ? 0.0 : m.alpha + (1.0 - m.alpha) * (double)rem / (double)slots);
-  const double second = s == 1 ? 0.0 : m.k0 + m.k1 * m.slabs * (double)s * (double)rows * (D + m.extra) * 4.0 / 1e6;
-  return rounds * per + second;
-}
-// fwd: the forward's form rule (see above); else the backward's (un-split = form A, split = 4-wave workgroups)
-static int best_split(const SplitModel& m, bool fwd, int D, int64_t tiles, int64_t rows, int len) {
-  const int cus = fcsa::cu_count();
-  if (tiles <= 0 || tiles >= cus) return 1;
-  int best = 1;
-  double best_cost = split_cost(m, D, tiles, rows, len, 1, cus, true);
-  for (int s = 2; s <= 16 && len / s >= 512; ++s) {
-    const bool form_a = fwd && (D * 2 > 128 || tiles * s <= cus);
-    const double cost = split_cost(m, D, tiles, rows, len, s, cus, form_a);
-    if (cost < best_cost) { best_cost = cost; best = s; }
-  }
-  return best;
-}
-// the rule of rounds 2 - 5, still used for float32: two 4-wave workgroups per CU where those run two waves per SIMD (rows <= 128 bytes)
-int split_target(const fcsa_problem& p) { return (elem_size(p.dtype) * p.dim_head <= 128 ? 2 : 1) * fcsa::cu_count(); }
-static int split_by_target(const fcsa_problem& p, int64_t wgs, int len) {
-  const int target = split_target(p);
-  if (wgs <= 0 || wgs >= target / 2) return 1;
-  int64_t s = (target + wgs - 1) / wgs;
-  if (s > 16) s = 16;
-  if (s > len / 512) s = len / 512;
-  return s >= 2 ? (int)s : 1;
-}
-
-// Split-key dQ: every split keeps >= 512 keys.  C4 (1 x 8 heads x 1024 queries, 8192 keys): 64 row tiles, 8 splits.
-int backward_dq_splits(const fcsa_problem& p) {
-#ifdef FCSA_VAR_SPLIT_ENV      // sweep builds only (tools/split_sweep.py, dev/fcsa_sweep_env.h): the count from the environment, per call
-  if (const int v = fcsa_dev::env_int("FCSA_DQ_SPLITS"); v >= 1 && (!p.causal || (elem_size(p.dtype) == 2 && p.q_len >= 256)))
-    return std::min(std::min(v, 16), std::max(1, p.k_len / 64));
-#endif
-  if (p.causal) {
-    // Causal (round 6), like the forward: the workgroups are PAIRS of 128-row tiles; where the pairs cannot fill the chip each row tile's
-    // key range (up to its diagonal) is split.  16-bit only.
-    if (elem_size(p.dtype) != 2 || p.q_len < 256) return 1;
-    const int mt = (p.q_len + 127) / 128;
-    return best_split(kSplitDq, false, p.dim_head, (int64_t)p.batch * p.heads * ((mt + 1) / 2), (int64_t)p.batch * p.heads * p.q_len, p.k_len);
-  }
-  const int64_t wgs = (int64_t)p.batch * p.heads * ((p.q_len + 127) / 128);
-  if (elem_size(p.dtype) == 2) return best_split(kSplitDq, false, p.dim_head, wgs, (int64_t)p.batch * p.heads * p.q_len, p.k_len);
-  return split_by_target(p, wgs, p.k_len);
-}
-
-// Split-query dK/dV: the mirror image -- few keys, many queries (B * H * ceil(M / 128) key tiles cannot fill the chip),
-// K/V with heads (the single-headed form already reduces over slabs), every split keeps >= 512 queries.  Partial dK^ / dV go to f32
-// slabs [batch * heads][split][M][D] and the finalize kernel sums them (and applies the l2norm backward to dK^).
-int backward_dkv_splits(const fcsa_problem& p) {
-  // (single-headed K/V, round 6: split like any other problem -- its per-head slabs simply become heads x splits slabs for the same finalize launch)
-#ifdef FCSA_VAR_SPLIT_ENV      // sweep builds only
-  if (const int v = fcsa_dev::env_int("FCSA_DKV_SPLITS"); v >= 1 && (!p.causal || (elem_size(p.dtype) == 2 && p.k_len >= 256)))
-    return std::min(std::min(v, 16), std::max(1, p.q_len / 64));
-#endif
-  if (p.causal) {
-    // Causal (round 6): the workgroups are PAIRS of 128-key tiles; where the pairs cannot fill the chip each key tile's query range (from
-    // its diagonal down) is split.  16-bit only.
-    if (elem_size(p.dtype) != 2 || p.k_len < 256) return 1;
-    const int kt = (p.k_len + 127) / 128;
-    return best_split(kSplitDkv, false, p.dim_head, (int64_t)p.batch * p.heads * ((kt + 1) / 2), (int64_t)p.batch * p.heads * p.k_len,
-                      std::min(p.q_len, p.k_len));      // (a key tile sees the queries from its diagonal down: at most k_len of them)
-  }
-  const int64_t wgs = (int64_t)p.batch * p.heads * ((p.k_len + 127) / 128);
-  if (elem_size(p.dtype) == 2) return best_split(kSplitDkv, false, p.dim_head, wgs, (int64_t)p.batch * p.heads * p.k_len, p.q_len);
-  return split_by_target(p, wgs, p.q_len);
-}
-
 int log2_blocks_per_group(const fcsa_problem& p) {     // log2(group size / 8), or -1 if not a power of two of 8-blocks
   const int dg = p.dim_head / (p.groups > 0 ? p.groups : 1);
   if (dg % 8 != 0) return -1;
@@ -270,38 +158,55 @@ int log2_blocks_per_group(const fcsa_problem& p) {     // log2(group size / 8), 
 }
 bool fusable_groups(const fcsa_problem& p) { return log2_blocks_per_group(p) >= 0; }
 
-// Grouped-query K/V (1 < kv_heads < heads) with the group-sweep dK/dV kernel: one workgroup per (batch, K/V head, key tile) sums the dK / dV of
-// its group's query heads in registers.  Where it is compiled (16-bit, D = 64 / 128), for epilogues that finish the job (no l2norm groups that
-// need the finalize kernel), and where its grid gets the 8-wave form (fcsa_debug_kv_group_form: 0 never, 2 wherever compiled).  A launch with
-// an attn_bias takes the slab route instead: the workspace keeps room for its slabs.
-bool kv_sweep(const fcsa_problem& p) {
-  if (p.kv_heads <= 1 || p.kv_heads == p.heads) return false;
-  if (p.l2norm_qk != 0 && !fusable_groups(p)) return false;
-  return fcsa::backward_dkv_sweep(p.dtype, p.dim_head, (int64_t)p.batch * p.kv_heads, p.q_len, p.k_len, p.causal, fcsa::kv_group_mode(-1));
+// What a backward call runs: split counts, which gradients go through f32 slabs + the finalize kernel, fused l2norm, group sweep.
+struct BwdPlan {
+  bool fuse_norm;         // the l2norm backward is fused into the dQ / dK/dV epilogues (every group 8 * 2^k features wide)
+  bool kv_sweep;          // grouped-query K/V: the dK/dV kernel sums each K/V head's group in registers (no dk / dv slabs)
+  int dq_splits;          // > 1: split-key dQ kernel, dq_splits partial slabs
+  int dkv_splits;         // > 1: split-query dK/dV kernel, dkv_splits partial dk / dv slabs each
+  bool dq_slab, dk_slab, dv_slab;
+};
+// What the plan depends on beyond the problem: whether the call has an attn_bias, and whether (batch, head) is one flat index of the dq
+// (dk and dv) outputs -- the finalize kernel sums split slabs per (batch * head) row block.
+struct BwdCall { bool bias, dq_flat, dkv_flat; };
+
+// call == nullptr: the most any call of the problem needs, which the workspace is sized for
+BwdPlan bwd_plan(const fcsa_problem& p, const BwdCall* call) {
+  BwdPlan b;
+  const int cus = fcsa::cu_count();
+  // K/V heads fewer than query heads (single-headed or grouped): the dK/dV kernel writes per-query-head f32 slabs that the finalize kernel
+  // sums over each K/V head's group -- except for the group sweep, which runs where dkv_sweep says so for a bias-free launch with
+  // epilogues that finish the job (no l2norm groups that need the finalize kernel).  A launch with an attn_bias takes the slab route.
+  const bool grouped = p.kv_heads != p.heads;
+  const bool sweep = p.kv_heads > 1 && grouped && (p.l2norm_qk == 0 || fusable_groups(p)) &&
+                     fcsa::dkv_sweep(elem_size(p.dtype), p.dim_head, (int64_t)p.batch * p.kv_heads, p.k_len, p.causal != 0, fcsa::kv_group_mode(-1), cus);
+  b.kv_sweep = sweep && call != nullptr && !call->bias;
+  // the l2norm backward is fused into the dQ / dKV epilogues when every group is 8 * 2^k features wide; otherwise (odd group sizes) the
+  // kernels write f32 slabs that the finalize kernel differentiates
+  b.fuse_norm = p.l2norm_qk != 0 && fusable_groups(p);
+  const bool norm_slab = p.l2norm_qk != 0 && !b.fuse_norm;
+  // split dQ: flat dq, and causal splits only in bias-free kernels; split dK/dV: flat dk / dv (or per-query-head slabs anyway), bias-free,
+  // never with the group sweep
+  b.dq_splits = call != nullptr && !(call->dq_flat && !(p.causal && call->bias)) ? 1 : fcsa::backward_dq_splits(p, cus);
+  b.dkv_splits = sweep || (call != nullptr && !((call->dkv_flat || grouped) && !call->bias)) ? 1 : fcsa::backward_dkv_splits(p, cus);
+  b.dq_slab = b.dq_splits > 1 || norm_slab;
+  b.dk_slab = !b.kv_sweep && (b.dkv_splits > 1 || grouped || norm_slab);
+  b.dv_slab = !b.kv_sweep && (b.dkv_splits > 1 || grouped);
+  return b;
 }
 
+// workspace: delta [B,H,N] f32, then the slabs of the largest plan
+struct BwdLayout { size_t delta, dq_slab, dk_slab, dv_slab, total; };
 BwdLayout bwd_layout(const fcsa_problem& p) {
-  BwdLayout L;
-  // K/V heads fewer than query heads (single-headed or grouped): the dK/dV kernel writes per-query-head f32 slabs that the finalize kernel
-  // sums over each K/V head's group -- except for the group sweep (kv_sweep), whose bias-free launches write dk / dv directly
-  const bool grouped = p.kv_heads != p.heads && p.heads > 1;
-  L.kv_sweep = kv_sweep(p);
+  const BwdPlan b = bwd_plan(p, nullptr);
   const size_t qn = (size_t)p.batch * p.heads * p.q_len;
   const size_t kn = (size_t)p.batch * p.heads * p.k_len;      // slabs are per q-head
-  // the l2norm backward is fused into the dQ / dKV epilogues when every group is 8 * 2^k features wide;
-  // otherwise (odd group sizes) and for the head reduction of single-headed / grouped K/V the kernels write f32
-  // slabs that the finalize kernel reduces / differentiates.
-  L.fuse_norm = p.l2norm_qk != 0 && fusable_groups(p);
-  L.dq_splits = backward_dq_splits(p);
-  L.need_dq_slab = (p.l2norm_qk != 0 && !L.fuse_norm) || L.dq_splits > 1;
-  L.dkv_splits = L.kv_sweep ? 1 : backward_dkv_splits(p);      // (sweep problems: a bias launch takes the slab route, which never splits)
-  L.need_dk_slab = grouped || (p.l2norm_qk != 0 && !L.fuse_norm) || L.dkv_splits > 1;
-  L.need_dv_slab = grouped || L.dkv_splits > 1;
+  BwdLayout L;
   size_t off = 0;
   L.delta = off;   off = align_up(off + qn * 4, 256);
-  L.dq_slab = off; off = align_up(off + (L.need_dq_slab ? qn * p.dim_head * 4 * (size_t)L.dq_splits : 0), 256);
-  L.dk_slab = off; off = align_up(off + (L.need_dk_slab ? kn * p.dim_head * 4 * (size_t)L.dkv_splits : 0), 256);
-  L.dv_slab = off; off = align_up(off + (L.need_dv_slab ? kn * p.dim_head * 4 * (size_t)L.dkv_splits : 0), 256);
+  L.dq_slab = off; off = align_up(off + (b.dq_slab ? qn * p.dim_head * 4 * (size_t)b.dq_splits : 0), 256);
+  L.dk_slab = off; off = align_up(off + (b.dk_slab ? kn * p.dim_head * 4 * (size_t)b.dkv_splits : 0), 256);
+  L.dv_slab = off; off = align_up(off + (b.dv_slab ? kn * p.dim_head * 4 * (size_t)b.dkv_splits : 0), 256);
   L.total = off;
   return L;
 }
@@ -408,40 +313,20 @@ int fcsa_l2norm(int32_t dtype, int32_t batch, int32_t heads, int32_t len, int32_
   return timed("l2norm", "l2norm", s, [&] { return fcsa::launch_l2norm(dtype, np, s); });
 }
 
-// Split-key forward (the count: best_split above): only where the 128-row tiles (causal: pairs of them) cannot fill the chip, the static
-// exponent shift applies (partials with a common shift add up exactly) and every split keeps >= 512 keys.
-static int forward_splits(const fcsa_problem& p) {
-  if (dynamic_shift(p, false)) return 1;      // (never called with a bias: fcsa_forward only splits bias-free problems)
-  if (p.causal) {
-    // Causal (round 6): the workgroups are PAIRS of 128-row tiles (constant work: about k_len + 128 keys each); where the pairs cannot fill
-    // the chip -- one sequence of 4096 with 8 heads is 128 pairs on 256 CUs, and takes as long as two sequences -- each row tile's key range
-    // (up to its diagonal) is split.  16-bit only (the form rule of the model); the count from the same model with the pair as the tile.
-    if (elem_size(p.dtype) != 2 || p.q_len < 256) return 1;
-    const int mt = (p.q_len + 127) / 128;
-    const int64_t pairs = (int64_t)p.batch * p.heads * ((mt + 1) / 2);
-#ifdef FCSA_VAR_SPLIT_ENV      // sweep builds only
-    if (const int v = fcsa_dev::env_int("FCSA_SPLITS"); v >= 1) return std::min(std::min(v, 16), std::max(1, p.k_len / 64));
-#endif
-    return best_split(kSplitFwd, true, p.dim_head, pairs, (int64_t)p.batch * p.heads * p.q_len, p.k_len);
-  }
-  const int64_t wgs = (int64_t)p.batch * p.heads * ((p.q_len + 127) / 128);
-  if (wgs <= 0) return 1;
-#ifdef FCSA_VAR_SPLIT_ENV      // sweep builds only
-  if (const int v = fcsa_dev::env_int("FCSA_SPLITS"); v >= 1) return std::min(std::min(v, 16), std::max(1, p.k_len / 64));
-#endif
-  if (elem_size(p.dtype) == 2) return best_split(kSplitFwd, true, p.dim_head, wgs, (int64_t)p.batch * p.heads * p.q_len, p.k_len);
-  return split_by_target(p, wgs, p.k_len);
-}
-
 static size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 
-size_t fcsa_forward_workspace_bytes(const fcsa_problem* p) {
-  if (p == nullptr || p->batch <= 0 || p->heads <= 0 || p->q_len <= 0 || p->dim_head <= 0) return 0;
-  const int s = forward_splits(*p);
-  if (s <= 1) return 0;
-  const size_t rows = (size_t)s * p->batch * p->heads * p->q_len;
-  return align256(rows * p->dim_head * 4) + align256(rows * 4);
+// split-key forward (fcsa::forward_splits: bias-free launches only): the count, and its workspace -- partial P~V, then partial row sums
+static int forward_splits(const fcsa_problem& p) {
+  if (p.batch <= 0 || p.heads <= 0 || p.q_len <= 0 || p.dim_head <= 0) return 1;
+  return fcsa::forward_splits(p, dynamic_shift(p, false), fcsa::cu_count());
 }
+static size_t forward_ws_bytes(const fcsa_problem& p, int splits) {
+  if (splits <= 1) return 0;
+  const size_t rows = (size_t)splits * p.batch * p.heads * p.q_len;
+  return align256(rows * p.dim_head * 4) + align256(rows * 4);
+}
+
+size_t fcsa_forward_workspace_bytes(const fcsa_problem* p) { return p == nullptr ? 0 : forward_ws_bytes(*p, forward_splits(*p)); }
 
 // Zero-size problems (empty tensors: what torch hands over has NULL data pointers then).  batch, heads or q_len == 0: the forward has no
 // output element; k_len == 0: every query row is a row without a valid key, for which the kernels' semantics are o = 0 (cu:1239) and
@@ -536,8 +421,7 @@ int fcsa_forward(const fcsa_forward_args* a) {
   fp.splits = 1; fp.ws_o = nullptr; fp.ws_l = nullptr;
   if (a->workspace != nullptr && a->attn_bias == nullptr) {
     const int sp = forward_splits(p);
-    const size_t need = fcsa_forward_workspace_bytes(&p);
-    if (sp > 1 && a->workspace_bytes >= need && (reinterpret_cast<uintptr_t>(a->workspace) & 255) == 0) {
+    if (sp > 1 && a->workspace_bytes >= forward_ws_bytes(p, sp) && (reinterpret_cast<uintptr_t>(a->workspace) & 255) == 0) {
       const size_t rows = (size_t)sp * p.batch * p.heads * p.q_len;
       fp.splits = sp;
       fp.ws_o = static_cast<float*>(a->workspace);
@@ -593,12 +477,16 @@ int fcsa_backward(const fcsa_backward_args* a) {
   hipStream_t s = static_cast<hipStream_t>(a->stream);
   const bool single = p.kv_heads == 1 && p.heads > 1;      // stride-0 K/V head views
   const bool grouped = p.kv_heads != p.heads;             // single-headed or grouped-query K/V: dk / dv are sums over query heads
-  const bool sweep = L.kv_sweep && a->attn_bias == nullptr;      // grouped, in-kernel head sum; else per-query-head slabs + finalize
+  const BwdCall call = {a->attn_bias != nullptr, a->dq.stride0 == (int64_t)p.heads * a->dq.stride1,
+                        a->dk.stride0 == (int64_t)p.heads * a->dk.stride1 && a->dv.stride0 == (int64_t)p.heads * a->dv.stride1};
+  const BwdPlan plan = bwd_plan(p, &call);
+  const int dq_splits = plan.dq_splits, dkv_splits = plan.dkv_splits;
+  const bool dq_slab = plan.dq_slab, dk_slab = plan.dk_slab, dv_slab = plan.dv_slab;
   char* ws = static_cast<char*>(a->workspace);
 
   fcsa::BwdParams bp;
   bp.kv_group = single ? 1 : p.heads / p.kv_heads;
-  bp.kv_sweep = sweep ? 1 : 0;
+  bp.kv_sweep = plan.kv_sweep ? 1 : 0;
   if (p.l2norm_qk) {
     bp.q = contiguous_view(a->norm.qn, p.heads, p.q_len, p.dim_head, es);
     bp.k = contiguous_view(a->norm.kn, p.kv_heads, p.k_len, p.dim_head, es, single);
@@ -609,19 +497,9 @@ int fcsa_backward(const fcsa_backward_args* a) {
   bp.v = view(a->v, es, single);
   bp.o = view(a->o, es);
   bp.d_out = view(a->d_out, es);
-  // split-key dQ needs (batch, head) to be one flat index of the dq output (the finalize kernel sums the partial slabs per
-  // (batch * head) row block); otherwise the unsplit kernel runs
-  const bool dq_flat = a->dq.stride0 == (int64_t)p.heads * a->dq.stride1;
   const bool want_dbias = a->attn_bias != nullptr && a->d_bias != nullptr;
-  const int dq_splits = (L.dq_splits > 1 && dq_flat && !(p.causal && a->attn_bias != nullptr)) ? L.dq_splits : 1;      // (causal splits: bias-free kernels only)
-  const bool dq_slab = dq_splits > 1 || (p.l2norm_qk != 0 && !L.fuse_norm);
   bp.dq_splits = dq_splits;
   bp.dq_split_stride = (int64_t)p.q_len * p.dim_head * 4;
-  // split-query dK/dV: same condition on dk / dv (flat (batch, head) index for the finalize kernel); the bias form keeps the unsplit kernel
-  const bool dkv_flat = a->dk.stride0 == (int64_t)p.heads * a->dk.stride1 && a->dv.stride0 == (int64_t)p.heads * a->dv.stride1;
-  const int dkv_splits = (L.dkv_splits > 1 && (dkv_flat || grouped) && a->attn_bias == nullptr && !sweep) ? L.dkv_splits : 1;
-  const bool dk_slab = !sweep && (dkv_splits > 1 || grouped || (p.l2norm_qk != 0 && !L.fuse_norm));
-  const bool dv_slab = !sweep && (dkv_splits > 1 || grouped);
   bp.dkv_splits = dkv_splits;
   bp.dkv_split_stride = (int64_t)p.k_len * p.dim_head * 4;
   bp.dq_f32 = dq_slab;
@@ -659,9 +537,9 @@ int fcsa_backward(const fcsa_backward_args* a) {
   bp.bias_c = kLog2e;
   bp.scale = p.scale;
   bp.q_scaled = p.l2norm_qk ? 1 : 0;
-  bp.G = p.groups; bp.lgm = L.fuse_norm ? log2_blocks_per_group(p) : 0; bp.norm_eps = 1e-12f;
-  bp.rq = (L.fuse_norm && dq_splits <= 1) ? a->norm.rq : nullptr;    // fused: dq kernel writes the final dq
-  bp.rk = (L.fuse_norm && (!grouped || sweep) && dkv_splits <= 1) ? a->norm.rk : nullptr;          // fused: dkv kernel writes the final dk
+  bp.G = p.groups; bp.lgm = plan.fuse_norm ? log2_blocks_per_group(p) : 0; bp.norm_eps = 1e-12f;
+  bp.rq = (plan.fuse_norm && dq_splits <= 1) ? a->norm.rq : nullptr;    // fused: dq kernel writes the final dq
+  bp.rk = (plan.fuse_norm && (!grouped || plan.kv_sweep) && dkv_splits <= 1) ? a->norm.rk : nullptr;          // fused: dkv kernel writes the final dk
 
   // 1. dQ (also publishes delta), 2. dK/dV, 3. head reduction + l2norm backward where needed
   if (int rc = timed("bwd_dq", "backward dq", s, [&] { return fcsa::launch_backward_dq(p.dtype, p.dim_head, bp, s); })) return rc;

@@ -55,6 +55,35 @@ struct BF16 {};
 struct F16 {};
 struct F32 {};
 
+// The launchers' dtype x head-dim dispatch: calls fn(TypeDim<T, D>{}) for dtype (fcsa_dtype) and D.  Development builds (-DFCSA_DEV_ONLY,
+// tools/build_dev.sh) instantiate bf16 at one head dim (FCSA_DEV_D, default 64) only, for quick compiles / ISA inspection.
+template <typename TT, int DD> struct TypeDim { using T = TT; static constexpr int D = DD; };
+template <typename F> static hipError_t dispatch_dtype_d(int dtype, int D, F&& fn) {
+#ifdef FCSA_DEV_ONLY
+#ifndef FCSA_DEV_D
+#define FCSA_DEV_D 64
+#endif
+  if (dtype == 2 && D == FCSA_DEV_D) return fn(TypeDim<BF16, FCSA_DEV_D>{});
+  return hipErrorInvalidValue;
+#else
+  auto by_d = [&](auto t) -> hipError_t {
+    using T = decltype(t);
+    switch (D) {
+      case 16:  return fn(TypeDim<T, 16>{});
+      case 32:  return fn(TypeDim<T, 32>{});
+      case 64:  return fn(TypeDim<T, 64>{});
+      case 96:  return fn(TypeDim<T, 96>{});
+      case 128: return fn(TypeDim<T, 128>{});
+      default:  return hipErrorInvalidValue;
+    }
+  };
+  if (dtype == 2) return by_d(BF16{});
+  if (dtype == 1) return by_d(F16{});
+  if (dtype == 0) return by_d(F32{});
+  return hipErrorInvalidValue;
+#endif
+}
+
 template <typename T> struct Traits;
 
 template <> struct Traits<BF16> {

@@ -1,0 +1,338 @@
+// fcsa_dispatch.h -- which kernel form, and how many split workgroups, every problem gets.  The launchers (fcsa_fwd.hip, fcsa_bwd.hip)
+// and the C ABI (fcsa_capi.hip) ask these functions and carry out the answer; nothing else decides.  Host-only and pure: the CU count and
+// the debug knobs are arguments (callers pass cu_count(), forward_wide128_mode(-1), kv_group_mode(-1)), so a g++ program can include it.
+// Sweep builds (-DFCSA_VAR_SPLIT_ENV, tools/form_sweep.py, split_sweep.py, split_fuzz.py) let environment variables override each choice;
+// the product build reads none (sweep_env below is a constant -1 there).
+#pragma once
+#include <stdint.h>
+#include <algorithm>
+
+#include "../../include/fcsa.h"
+#ifdef FCSA_VAR_SPLIT_ENV
+#include "dev/fcsa_sweep_env.h"
+namespace fcsa {
+inline int sweep_env(const char* name) { return fcsa_dev::env_int(name); }      // -1: not set
+constexpr bool kSweepBuild = true;
+}  // namespace fcsa
+#else
+namespace fcsa {
+constexpr int sweep_env(const char*) { return -1; }
+constexpr bool kSweepBuild = false;
+}  // namespace fcsa
+#endif
+
+namespace fcsa {
+
+constexpr int kDq2WBytes = 128;      // row bytes D*ES up to which the dQ kernel runs its 8-wave form (two waves / SIMD, one workgroup per CU)
+constexpr int kDkv2WBytes = 128;     // same for the dKV kernel
+
+// ---- which forms are compiled (element size es, head dim D, bias) --------------------------------------------------------------------
+// "Lean" form of the 32-rows-per-wave forward for 16-bit rows of 129 .. 256 bytes (D = 96, 128) without bias: nothing is prefetched
+// across blocks -- K row fragments and V transposed fragments are requested per 32-key block, next to their MFMAs -- so the wave
+// fits 256 registers and TWO waves share a SIMD (eight waves per CU), the partner hiding the LDS latency the prefetches hid.
+// The round-2 form prefetched a whole tile's K fragments and ran one wave per SIMD at these widths (397 registers at D = 128);
+// measured on MI355X (C3 at D = 128, profiles/r03_*): see DESIGN.md section 6.
+// It only pays when two waves per SIMD are actually resident -- an 8-wave workgroup per CU, or two 4-wave workgroups -- so it is a
+// kernel template parameter chosen at launch; small grids keep the prefetching one-wave form.
+constexpr bool fwd_lean(int es, int D, bool bias) { return es == 2 && !bias && D * es > 128 && D * es <= 256; }
+// Key-split forward (fwd_kernel<.., KSPLIT>): 128-row workgroups of 8 waves whose halves split the keys; 16-bit, bias launches up to D = 64
+constexpr bool fwd_ksplit(int es, int D, bool bias) { return es == 2 && (!bias || D <= 64); }
+// key-split forms of the backward kernels (bwd_dq_kernel<.., KSPLIT>, bwd_dkv_kernel<.., QSPLIT>): 16-bit, no bias
+constexpr bool bwd_ksplit(int es, int D, bool bias) { return es == 2 && !bias && D <= 128; }
+// Two waves per SIMD (<= 256 registers) for the dQ kernel (template parameter TWO): always for rows up to 128 bytes, and -- round 3 --
+// for 16-bit rows up to 256 bytes (D = 96, 128) in the 4-wave form WHEN the grid puts two 128-row workgroups on every CU, whose waves
+// then hide each other's LDS latency.  Those widths ran one wave per SIMD before (435 registers at D = 128), at ~40 % of what the same
+// kernel reaches at D = 64; smaller grids still do (a lone wave is better off with the pipelined tile).
+constexpr bool dq_can_two_waves(int es, int D) { return D * es <= (es == 2 ? 256 : 128); }
+// Group-sweep dK/dV (grouped-query attention): compiled for the 8-wave forms of 16-bit D = 64 (pipelined ring tile) and D = 128 (lean
+// tile), the forms choose_dkv picks for key grids that cover the chip.
+constexpr bool dkv_has_sweep(int es, int D, bool bias) { return es == 2 && !bias && (D == 64 || D == 128); }
+// fwd2_kernel (64 rows per wave, no bias / key mask / per-row shift): D = 32 in the product; sweep builds also time D = 16 and 64
+constexpr bool fwd2_compiled(int es, int D) { return es == 2 && (D == 32 || (kSweepBuild && D <= 64)); }
+
+// ---- forms -----------------------------------------------------------------------------------------------------------------------------
+enum class FwdForm { Rows8, Lean8, KSplit8, Waves4, Fwd2, Fwd3 };     // 8-wave rows, 8-wave lean, key-split 8 waves, 4 waves, fwd2, fwd3
+enum class DqForm { Waves4, Waves4Two, Waves8, KSplit8 };            // 4 waves, 4 waves two-wave tile, 8 waves, key-split 8 waves
+enum class DkvForm { Waves4, Waves8, Lean8, QSplit8, Sweep };        // 4 waves, 8 waves, 8-wave lean, query-split 8 waves, group sweep
+
+// workgroups of `tile`-position tiles over `len` positions for `batch_heads` (batch x heads): causal launches pair the tiles
+inline int64_t tile_workgroups(int64_t batch_heads, int len, int tile, bool causal) {
+  const int t = (len + tile - 1) / tile;
+  return batch_heads * (causal ? (t + 1) / 2 : t);
+}
+
+// Waves per workgroup of the row-tile (key-tile) kernels: 8 (one 256-position workgroup per CU) when that still gives every CU a
+// workgroup, else 4 (two 128-position workgroups per CU).  Both keep two waves per SIMD; with 8 the K / V (Q / dO) tiles are staged once
+// per CU instead of twice, i.e. half the global loads and LDS stores per wave (C3: forward -6%).
+// tail: the last-round rule below -- 1 for the forward and dK/dV, 2 for dQ, 0 none
+inline int tile_waves(int64_t batch_heads, int len, bool causal, bool bits16, int tail, int cus) {
+  const int64_t w256 = tile_workgroups(batch_heads, len, 256, causal);
+  // More 256-position workgroups than CUs, 16-bit (round 6, profiles/r06_form_sweep_big*.txt): the LAST round decides.  A last round that
+  // fills at most ~55 % of the CUs costs the 8-wave form a whole 256-position workgroup time; as 4-wave workgroups (two per CU) the same
+  // tail is 128-position workgroups running alone on their CUs: forward (rows <= 128 bytes) -4 ... -11 % at 264 ... 384 and 544 ... 640
+  // workgroups on 256 CUs, -6 ... -8 % at 800 and 1088; dK/dV -5 ... -9 % at the same counts (D = 128 lean form against the pipelined
+  // 4-wave form: -8 ... -12 % at 264 ... 352).  Full or nearly full last rounds (C3: exactly 256) keep the 8-wave form.  dQ: the 4-wave
+  // form wins whenever the last round is not full (-3 ... -25 %); with whole rounds the 8-wave form is ahead (C3, one round: 6 %;
+  // (8,8,4096,64) causal, two rounds: 4 %, profiles/r06_ab_forms_tail.txt).
+  if (bits16 && tail != 0 && w256 > cus) {
+    const int64_t rem = w256 % cus;
+    if (tail == 2) return rem != 0 ? 4 : 8;
+    return (rem != 0 && rem * 20 <= (int64_t)cus * 11) ? 4 : 8;
+  }
+  if (w256 >= cus * 7 / 8) return 8;
+  // 16-bit types (round 6, tools/form_sweep.py): once the 128-position tiles outnumber the CUs -- where the key-split 8-wave forms would
+  // need a second round of workgroups -- the 256-position 8-wave workgroup wins from 132 workgroups on 256 CUs up, not only from 7/8 of
+  // the CUs: rows <= 128 bytes forward (against two 4-wave workgroups per CU) -5 ... -9 %, dQ -3 ... -10 %, dK/dV -10 ... -20 %
+  // (profiles/r06_form_sweep_d64_b.txt); D = 96 / 128 lean forward against the key-split form -25 ... -35 %, lean dK/dV -15 ... -20 %
+  // (profiles/r06_form_sweep_d128_b.txt)
+  if (bits16 && tile_workgroups(batch_heads, len, 128, causal) > cus) return 8;
+  return 4;
+}
+
+// The key-split forward where it is compiled: rows wider than 128 bytes always (the 4-wave form runs one wave per SIMD there whatever the
+// grid), narrower rows while its workgroups (128-row tiles x splits) fit one round
+inline bool fwd_ksplit_pays(int es, int D, int64_t workgroups, int cus) { return D * es > 128 || workgroups <= cus; }
+
+// ---- forward -------------------------------------------------------------------------------------------------------------------------
+struct FwdProblem {
+  int es, D;
+  int64_t batch_heads;
+  int N, M;
+  bool causal, bias, mask, dyn;
+  int splits;
+  int64_t q_row_bytes, k_row_bytes, v_row_bytes;      // row strides of q, k, v (the 32-bit offsets of fwd3)
+  int wide128_mode;                                   // fcsa_debug_forward_form: 0 = never fwd3
+};
+
+// fwd3_kernel (fcsa_fwd3.hip): 16-bit D = 128, static exponent shift, no bias, no key mask, no key split, a grid of 256-row (causal: paired)
+// workgroups that covers the chip -- or, from 2048 keys, more than half of it -- K / V slices addressable with 32-bit offsets.
+inline bool fwd3_applies(const FwdProblem& f, int cus) {
+  if (f.D != 128 || f.es != 2 || f.bias || f.mask || f.dyn || f.splits > 1 || f.wide128_mode == 0) return false;
+  if (tile_workgroups(f.batch_heads, f.N, 256, f.causal) < cus * 7 / 8) {
+    // round 6 (tools/form_sweep.py, profiles/r06_form_sweep_d128_b.txt): also where the 128-row tiles outnumber the CUs (132 ... 223 of
+    // these workgroups on 256 CUs) and the pass is long enough for its prologue: 31 - 36 % faster than the key-split lean form there, and
+    // ahead of the 256-row lean form from 2048 keys (level at 1024 keys up to ~176 workgroups, behind beyond)
+    if (tile_workgroups(f.batch_heads, f.N, 128, f.causal) <= cus || f.M < 2048) return false;
+  }
+  if ((int64_t)(f.M + 64 * 6) * f.k_row_bytes >= 0x7fffffffLL || (int64_t)(f.M + 64 * 6) * f.v_row_bytes >= 0x7fffffffLL) return false;
+  return (int64_t)(f.N + 256) * f.q_row_bytes < 0x7fffffffLL;
+}
+
+// fwd2_kernel against the 32-row kernel (measured on MI355X, bf16, B4 H8: tools/fwd_ab.py, tools/form_sweep.py).  It needs enough 256-row
+// workgroups to cover the 256 CUs.  Rounds 2 - 3 measured it ahead where the MFMA share of a tile is large or the sequence is long
+// (D = 32 / 64 non-causal: +3..22%; causal N = 8192: +5%; D = 96 against the ONE-wave narrow kernel of round 2: +25..34%); with causal
+// masking and short sequences its 256-row diagonal granularity costs more than the halved LDS traffic saves (N = 4096: -6%, N = 1024:
+// -20%).  Round 6 (tools/form_sweep.py, profiles/r06_form_sweep_*.txt): since round 4 (row sums on the VALU, LDS-DMA staging) the 32-row
+// kernel at two waves per SIMD beats this one at D = 64 -- non-causal (4,8,4096) 135 vs 156 us, (8,8,2048) 74 vs 88, causal (4,8,8192)
+// 273 vs 324 -- and at D = 16 (causal 8192: 155 vs 165); at D = 32 this kernel still wins on long key ranges (causal (4,8,8192) 183 vs
+// 198, non-causal (2,8,8192) 172 vs 178; level at 2048 - 4096 keys, 7 % behind at 1024).  D = 96: the lean two-wave kernel (round 3).
+inline bool fwd2_applies(const FwdProblem& f) {
+  if (f.es != 2 || f.D != 32 || f.bias || f.dyn || f.splits > 1 || f.mask) return false;
+  if (tile_workgroups(f.batch_heads, f.N, 256, f.causal) < 224) return false;
+  return f.causal ? f.N >= 8192 : f.M >= 4096;
+}
+
+// Sweep builds: FCSA_FWD_FORM = 1 row tiles of 8 waves (16-bit D = 96 / 128: lean), 2 key-split 8 waves, 3 four waves, 4 the 64-rows-per-wave
+// kernel (16-bit D <= 64), 5 the D = 128 64-rows-per-wave kernel whatever the grid; any value > 0 rules out the automatic fwd2 / fwd3.
+// FCSA_KSPLIT = 0 / 1 forces the key-split form off / on where it is compiled.
+inline FwdForm choose_forward(const FwdProblem& f, int cus) {
+  const int env = sweep_env("FCSA_FWD_FORM"), env_ks = sweep_env("FCSA_KSPLIT");
+  const bool plain = !f.bias && !f.mask && !f.dyn && f.splits <= 1;
+  if (env > 0) {
+    if (env == 5 && f.D == 128 && f.es == 2 && plain) return FwdForm::Fwd3;
+    if (env == 4 && fwd2_compiled(f.es, f.D) && plain) return FwdForm::Fwd2;
+  } else {
+    if (fwd3_applies(f, cus)) return FwdForm::Fwd3;
+    if (fwd2_applies(f)) return FwdForm::Fwd2;
+  }
+  const bool narrow = f.D * f.es <= 128, lean = fwd_lean(f.es, f.D, f.bias);
+  const bool ksplit = fwd_ksplit(f.es, f.D, f.bias) &&
+      (env_ks >= 0 ? env_ks != 0 : fwd_ksplit_pays(f.es, f.D, tile_workgroups(f.batch_heads, f.N, 128, f.causal) * std::max(f.splits, 1), cus));
+  if (!f.dyn && f.splits > 1) return ksplit ? FwdForm::KSplit8 : FwdForm::Waves4;      // split-key path: 128-row tiles x key ranges
+  if (!f.dyn && fwd_ksplit(f.es, f.D, f.bias) && (narrow || lean) && env >= 1 && env <= 3)
+    return env == 1 ? (narrow ? FwdForm::Rows8 : FwdForm::Lean8) : env == 2 ? FwdForm::KSplit8 : FwdForm::Waves4;
+  // rows <= 128 bytes: two waves per SIMD whatever the grid (<= 256 registers with all prefetches); the lean form needs its partner wave:
+  // one 8-wave workgroup per CU (a grid with two 4-wave workgroups per CU always has that)
+  if (narrow && tile_waves(f.batch_heads, f.N, f.causal, f.es == 2, 1, cus) == 8) return FwdForm::Rows8;
+  if (!narrow && lean && tile_waves(f.batch_heads, f.N, f.causal, true, 0, cus) == 8) return FwdForm::Lean8;
+  return ksplit ? FwdForm::KSplit8 : FwdForm::Waves4;
+}
+
+// ---- dQ ------------------------------------------------------------------------------------------------------------------------------
+struct BwdProblem {
+  int es, D;
+  int64_t batch_heads;
+  int N, M;
+  bool causal, bias;
+  int splits;           // dq_splits / dkv_splits of the launch
+  bool kv_sweep;        // the dK/dV launch runs the group sweep (dkv_sweep below, decided by the C ABI)
+};
+
+// Sweep builds: FCSA_DQ_FORM = 1 row tiles of 8 waves (16-bit D = 96 / 128: four waves, two-wave tile), 2 key-split 8 waves (D = 96 / 128:
+// causal only), 3 four waves
+inline DqForm choose_dq(const BwdProblem& b, int cus) {
+  if (b.splits > 1) return DqForm::Waves4;       // split-key path: 128-row tiles x key ranges (the key-split form measured level there)
+  const bool narrow = b.D * b.es <= kDq2WBytes, two = dq_can_two_waves(b.es, b.D) && !b.bias;
+  if (const int env = sweep_env("FCSA_DQ_FORM"); bwd_ksplit(b.es, b.D, b.bias) && (narrow || two)) {
+    if (env == 1) return narrow ? DqForm::Waves8 : DqForm::Waves4Two;
+    if (env == 2 && (narrow || b.causal)) return DqForm::KSplit8;
+    if (env == 3) return DqForm::Waves4;
+  }
+  const int64_t wgs128 = tile_workgroups(b.batch_heads, b.N, 128, b.causal);
+  if (narrow) {
+    if (tile_waves(b.batch_heads, b.N, b.causal, b.es == 2, 2, cus) == 8) return DqForm::Waves8;
+    // at most one 128-row workgroup per CU: its wave halves split the keys
+    if (bwd_ksplit(b.es, b.D, false) && wgs128 <= cus) return DqForm::KSplit8;
+  } else if (two) {
+    // two waves per SIMD need two 128-row workgroups on every CU; smaller grids keep the one-wave (pipelined) form
+    // (bias launches keep the one-wave form too: their two-wave instantiation spills 17 registers and was never measured ahead)
+    // (round 6: from MORE 128-row workgroups than CUs on -- rounds 3 - 5 asked for 7/4 of the CUs; at 264 ... 416 workgroups on 256 CUs the
+    //  two-wave tile is 19 - 28 % faster than the one-wave and key-split forms: profiles/r06_form_sweep_d128_b.txt)
+    if (wgs128 > cus) return DqForm::Waves4Two;
+    // fewer: the same tile, 8 waves on 128 rows.  Causal launches only: 256-byte rows have no non-causal instantiation of the two-wave tile
+    // (GENERAL_ONLY in launch_dq_nw), and the general one measured +6 % there against the one-wave pipelined form
+    if (bwd_ksplit(b.es, b.D, b.bias) && b.causal) return DqForm::KSplit8;
+  }
+  return DqForm::Waves4;
+}
+
+// ---- dK / dV -------------------------------------------------------------------------------------------------------------------------
+// Grouped-query K/V: the group sweep takes a problem where it is compiled and its grid -- batch x K/V heads x 256-key tiles -- gets the 8-wave
+// form by the rule above (mode, fcsa_debug_kv_group_form: 0 never, 1 by that rule, 2 wherever compiled)
+inline bool dkv_sweep(int es, int D, int64_t batch_kv_heads, int M, bool causal, int mode, int cus) {
+  if (!dkv_has_sweep(es, D, false) || mode <= 0) return false;
+  return mode >= 2 || tile_waves(batch_kv_heads, M, causal, true, 1, cus) == 8;
+}
+
+// Sweep builds: FCSA_DKV_FORM = 1 key tiles of 8 waves (16-bit D = 96 / 128: lean), 2 query-split 8 waves (D <= 64), 3 four waves
+inline DkvForm choose_dkv(const BwdProblem& b, int cus) {
+  if (b.kv_sweep) return DkvForm::Sweep;
+  if (b.splits > 1) return DkvForm::Waves4;      // split-query path: 128-key tiles x query ranges
+  const bool narrow = b.D * b.es <= kDkv2WBytes, lean = b.es == 2 && !b.bias && !narrow && b.D * b.es <= 256;
+  if (const int env = sweep_env("FCSA_DKV_FORM"); (narrow && bwd_ksplit(b.es, b.D, b.bias)) || lean) {
+    if (env == 1) return narrow ? DkvForm::Waves8 : DkvForm::Lean8;
+    if (env == 2 && narrow) return DkvForm::QSplit8;
+    if (env == 3) return DkvForm::Waves4;
+  }
+  if (narrow) {
+    if (tile_waves(b.batch_heads, b.M, b.causal, b.es == 2, 1, cus) == 8) return DkvForm::Waves8;
+    // at most one 128-key workgroup per CU: its wave halves split the queries (from 512 queries: below, the four or fewer 128-row tiles of
+    // a pass do not pay for the hand-over -- 23.5 vs 24.7 us at N = 333 / 777)
+    if (bwd_ksplit(b.es, b.D, false) && b.N >= 512 && tile_workgroups(b.batch_heads, b.M, 128, b.causal) <= cus) return DkvForm::QSplit8;
+  } else if (lean) {
+    // lean form (two waves per SIMD, V fragments from the LDS) where an 8-wave workgroup per CU still covers the chip; smaller grids keep
+    // the one-wave pipelined form.  (Two 4-wave workgroups per CU would do as well, but a grid with >= 448 of those always has >= 224 of
+    // the 8-wave ones.)
+    if (tile_waves(b.batch_heads, b.M, b.causal, true, 1, cus) == 8) return DkvForm::Lean8;
+  }
+  return DkvForm::Waves4;
+}
+
+// ---- split counts (forward keys / dQ keys / dK-dV queries) -------------------------------------------------------------------------
+// Where a problem's 128-position tiles (causal, since round 6: PAIRS of tiles) cannot fill the chip, several workgroups share one tile's
+// loop range and write f32 partials that a second pass (fwd_combine_kernel / finalize) sums.  How many: rounds 2 - 5 took "enough
+// workgroups for two per CU"; since round 6 the count is the argmin of a small cost model over s = 1 .. 16 (16-bit types; float32 keeps
+// the old rule).  The model prices, in microseconds on MI355X, what a launch with s splits costs:
+//   * the form the launchers run for that count: form A = the 8-wave one-workgroup-per-CU forms (forward: wave halves split the keys,
+//     fwd_ksplit_pays; backward: whatever runs un-split), else 4-wave workgroups, one per CU (form B) or -- rows <= 128 bytes and more
+//     workgroups than CUs -- two per CU (form C);
+//   * a workgroup's time t0 + c * positions, t0 and c growing with D (the exponentials do not shrink with it: floor);
+//   * rounds of workgroups over the slots, a partly filled last round at alpha + (1 - alpha) * fill;
+//   * the second pass: a launch + s partial slabs read once.
+// Constants: least squares in log space over tools/split_sweep.py tables of 27 shapes x 7 counts per kernel, D = 16 .. 128
+// (profiles/r06_split_sweep_*.txt; tools/split_model_fit.py prints them and the table below).  Mean / worst regret of the model's choice
+// against the measured best: forward 0.9 / 10.9 %, dQ 0.3 / 4.5 %, dK/dV 0.2 / 3.6 %; the rule it replaces: 11.2 / 44 %, 8.9 / 42 %,
+// 11.8 / 52 % (it split 160 .. 224 tiles of a 2048-position problem three or four ways where the un-split 8-wave form is 30 - 50 %
+// faster, and took counts that leave a quarter-full last round).  The ONE definition both the workspace sizes and the launches use.
+struct SplitModel { double tA, cA, tB, cB, tC, cC, a0, b0, k0, k1, alpha; int slabs, extra; };
+constexpr SplitModel kSplitFwd = {5.57, 8.68, 3.61, 11.8, 5.77, 16.1, 0.0, 0.536, 7.77, 0.177, 0.585, 1, 1};
+constexpr SplitModel kSplitDq  = {11.3, 9.94, 2.35, 12.5, 1.0, 20.9, 0.369, 0.244, 12.2, 0.455, 0.526, 1, 0};
+constexpr SplitModel kSplitDkv = {11.5, 12.0, 2.25, 15.5, 1.0, 26.6, 0.11, 0.281, 13.5, 0.34, 0.528, 2, 0};
+// tiles: 128-position tiles the un-split grid has; rows: rows of ONE partial slab; len: positions the split loop runs over
+inline double split_cost(const SplitModel& m, int D, int64_t tiles, int64_t rows, int len, int s, int cus, bool form_a) {
+  const bool wide = D * 2 > 128;
+  const double ft = m.a0 + (1.0 - m.a0) * D / 64.0, fc = m.b0 + (1.0 - m.b0) * std::max(0.44, D / 64.0);
+  const int64_t tot = tiles * s;
+  double t0 = m.tA, c = m.cA;
+  int64_t slots = cus;
+  if (!form_a) {
+    if (wide || tot <= cus) { t0 = m.tB; c = m.cB; }
+    else { t0 = m.tC; c = m.cC; slots = 2 * (int64_t)cus; }
+  }
+  const double per = t0 * ft + c * fc * ((double)len / s) / 1024.0;
+  const int64_t full = tot / slots, rem = tot % slots;
+  const double rounds = full == 0 ? 1.0 : (double)full + (rem == 0 ? 0.0 : m.alpha + (1.0 - m.alpha) * (double)rem / (double)slots);
+  const double second = s == 1 ? 0.0 : m.k0 + m.k1 * m.slabs * (double)s * (double)rows * (D + m.extra) * 4.0 / 1e6;
+  return rounds * per + second;
+}
+// 16-bit problems.  fwd: a split forward runs the key-split form where choose_forward takes it, else 4-wave workgroups; the backward's
+// split launches always run 4-wave workgroups (un-split = form A)
+inline int best_split(const SplitModel& m, bool fwd, int D, int64_t tiles, int64_t rows, int len, int cus) {
+  if (tiles <= 0 || tiles >= cus) return 1;
+  int best = 1;
+  double best_cost = split_cost(m, D, tiles, rows, len, 1, cus, true);
+  for (int s = 2; s <= 16 && len / s >= 512; ++s) {
+    const bool form_a = fwd && fwd_ksplit(2, D, false) && fwd_ksplit_pays(2, D, tiles * s, cus);
+    const double cost = split_cost(m, D, tiles, rows, len, s, cus, form_a);
+    if (cost < best_cost) { best_cost = cost; best = s; }
+  }
+  return best;
+}
+// the rule of rounds 2 - 5, still used for float32: two 4-wave workgroups per CU where those run two waves per SIMD (rows <= 128 bytes)
+inline int split_by_target(const fcsa_problem& p, int64_t wgs, int len, int cus) {
+  const int target = ((p.dtype == FCSA_F32 ? 4 : 2) * p.dim_head <= 128 ? 2 : 1) * cus;
+  if (wgs <= 0 || wgs >= target / 2) return 1;
+  int64_t s = (target + wgs - 1) / wgs;
+  if (s > 16) s = 16;
+  if (s > len / 512) s = len / 512;
+  return s >= 2 ? (int)s : 1;
+}
+// sweep builds: FCSA_SPLITS / FCSA_DQ_SPLITS / FCSA_DKV_SPLITS = the count, clamped to 16 and to 64 positions per split
+inline int sweep_splits(const char* name, int len) {
+  const int v = sweep_env(name);
+  return v >= 1 ? std::min(std::min(v, 16), std::max(1, len / 64)) : 0;
+}
+
+// Split-key forward: only where the 128-row tiles (causal: pairs of them) cannot fill the chip, the static exponent shift applies (dyn
+// false: partials with a common shift add up exactly) and every split keeps >= 512 keys.  Causal (round 6): the workgroups are PAIRS of
+// 128-row tiles (constant work: about k_len + 128 keys each); where the pairs cannot fill the chip -- one sequence of 4096 with 8 heads is
+// 128 pairs on 256 CUs, and takes as long as two sequences -- each row tile's key range (up to its diagonal) is split.  16-bit only (the
+// form rule of the model); the count from the same model with the pair as the tile.
+inline int forward_splits(const fcsa_problem& p, bool dyn, int cus) {
+  const bool bits16 = p.dtype != FCSA_F32;
+  const int64_t bh = (int64_t)p.batch * p.heads, wgs = tile_workgroups(bh, p.q_len, 128, p.causal);
+  if (dyn || (p.causal && (!bits16 || p.q_len < 256)) || wgs <= 0) return 1;
+  if (const int v = sweep_splits("FCSA_SPLITS", p.k_len)) return v;
+  if (bits16) return best_split(kSplitFwd, true, p.dim_head, wgs, bh * p.q_len, p.k_len, cus);
+  return split_by_target(p, wgs, p.k_len, cus);
+}
+
+// Split-key dQ: every split keeps >= 512 keys.  C4 (1 x 8 heads x 1024 queries, 8192 keys): 64 row tiles, 8 splits.  Causal (round 6),
+// like the forward: the workgroups are PAIRS of 128-row tiles; where the pairs cannot fill the chip each row tile's key range (up to its
+// diagonal) is split.  16-bit only.
+inline int backward_dq_splits(const fcsa_problem& p, int cus) {
+  const bool bits16 = p.dtype != FCSA_F32;
+  if (!p.causal || (bits16 && p.q_len >= 256))
+    if (const int v = sweep_splits("FCSA_DQ_SPLITS", p.k_len)) return v;
+  if (p.causal && (!bits16 || p.q_len < 256)) return 1;
+  const int64_t bh = (int64_t)p.batch * p.heads, wgs = tile_workgroups(bh, p.q_len, 128, p.causal);
+  if (bits16) return best_split(kSplitDq, false, p.dim_head, wgs, bh * p.q_len, p.k_len, cus);
+  return split_by_target(p, wgs, p.k_len, cus);
+}
+
+// Split-query dK/dV: the mirror image -- few keys, many queries (B * H * ceil(M / 128) key tiles cannot fill the chip), every split keeps
+// >= 512 queries.  Partial dK^ / dV go to f32 slabs [batch * heads][split][M][D] and the finalize kernel sums them (and applies the l2norm
+// backward to dK^).  Single-headed and grouped K/V (round 6) split like any other problem: their per-head slabs simply become heads x
+// splits slabs for the same finalize launch.  Causal (round 6): the workgroups are PAIRS of 128-key tiles; where the pairs cannot fill the
+// chip each key tile's query range (from its diagonal down: at most k_len queries) is split.  16-bit only.
+inline int backward_dkv_splits(const fcsa_problem& p, int cus) {
+  const bool bits16 = p.dtype != FCSA_F32;
+  if (!p.causal || (bits16 && p.k_len >= 256))
+    if (const int v = sweep_splits("FCSA_DKV_SPLITS", p.q_len)) return v;
+  if (p.causal && (!bits16 || p.k_len < 256)) return 1;
+  const int64_t bh = (int64_t)p.batch * p.heads, wgs = tile_workgroups(bh, p.k_len, 128, p.causal);
+  if (bits16) return best_split(kSplitDkv, false, p.dim_head, wgs, bh * p.k_len, p.causal ? std::min(p.q_len, p.k_len) : p.q_len, cus);
+  return split_by_target(p, wgs, p.q_len, cus);
+}
+
+}  // namespace fcsa

@@ -42,9 +42,6 @@
 
 #include "fcsa_common.cuh"
 #include "fcsa_kernels.h"
-#ifdef FCSA_VAR_SPLIT_ENV
-#include "dev/fcsa_sweep_env.h"
-#endif
 
 namespace fcsa {
 // 64-key tiles per LDS stage of fwd_kernel where the stages arrive by LDS-DMA.  One: this kernel's barrier sits in the MIDDLE of a
@@ -72,17 +69,6 @@ __device__ unsigned long long g_trace_bar_fwd[64];
 __device__ unsigned long long g_trace_wg_fwd[2048];      // per workgroup: [2 * id] = start time, [2 * id + 1] = end time (wave 0)
 __device__ unsigned long long g_trace_pass_fwd[2560];     // per workgroup (first 256): [pass][5] pass marks of wave 0
 #endif
-
-// "Lean" form of the 32-rows-per-wave kernel for 16-bit rows of 129 .. 256 bytes (D = 96, 128) without bias: nothing is prefetched
-// across blocks -- K row fragments and V transposed fragments are requested per 32-key block, next to their MFMAs -- so the wave
-// fits 256 registers and TWO waves share a SIMD (eight waves per CU), the partner hiding the LDS latency the prefetches hid.
-// The round-2 form prefetched a whole tile's K fragments and ran one wave per SIMD at these widths (397 registers at D = 128);
-// measured on MI355X (C3 at D = 128, profiles/r03_*): see DESIGN.md section 6.
-// It only pays when two waves per SIMD are actually resident -- an 8-wave workgroup per CU, or two 4-wave workgroups -- so it is a
-// kernel template parameter chosen at launch (launch_fwd_b); small grids keep the prefetching one-wave form.
-template <typename T, int D, bool BIAS> constexpr bool fwd_lean() {
-  return Traits<T>::ES == 2 && !BIAS && D * Traits<T>::ES > 128 && D * Traits<T>::ES <= 256;
-}
 
 // Per-row exponent reference of the DYN kernels, kept ONLINE (one pass over the keys).  `x` holds one block's exponents of this lane's
 // row (log2 units, relative to the row's current reference `mref`, masked positions at -inf).  The block is used as it is while its
@@ -1236,82 +1222,6 @@ __global__ void __launch_bounds__(NW * 64, 1) fwd2_kernel(const FwdParams p) {
 #endif
 }
 
-// Wide or narrow forward kernel (measured on MI355X, bf16, B4 H8: tools/fwd_ab.py, tools/form_sweep.py).  The wide kernel needs enough
-// 256-row workgroups to cover the 256 CUs.  Rounds 2 - 3 measured it ahead where the MFMA share of a tile is large or the sequence is
-// long (D = 32 / 64 non-causal: +3..22%; causal N = 8192: +5%; D = 96 against the ONE-wave narrow kernel of round 2: +25..34%); with
-// causal masking and short sequences its 256-row diagonal granularity costs more than the halved LDS traffic saves (N = 4096: -6%,
-// N = 1024: -20%).  Re-measured in round 6, after the 32-row kernel's round-4 gains: see use_wide_fwd.
-template <int D>
-static bool use_wide_fwd(const FwdParams& p) {
-  const int MT = (p.N + 255) / 256;
-  const int64_t wgs = (int64_t)p.B * p.H * (p.causal ? (MT + 1) / 2 : MT);
-  if (wgs < 224) return false;
-  // Round 6 (tools/form_sweep.py, profiles/r06_form_sweep_*.txt): since round 4 (row sums on the VALU, LDS-DMA staging) the 32-row kernel
-  // at two waves per SIMD beats this one at D = 64 -- non-causal (4,8,4096) 135 vs 156 us, (8,8,2048) 74 vs 88, causal (4,8,8192) 273 vs
-  // 324 -- and at D = 16 (causal 8192: 155 vs 165); at D = 32 this kernel still wins on long key ranges (causal (4,8,8192) 183 vs 198,
-  // non-causal (2,8,8192) 172 vs 178; level at 2048 - 4096 keys, 7 % behind at 1024).  D = 96: the lean two-wave kernel (round 3).
-  if (D != 32) return false;
-  return p.causal ? p.N >= 8192 : p.M >= 4096;
-}
-
-template <typename T, int D>
-static hipError_t launch_fwd2(const FwdParams& p, hipStream_t s) {
-  constexpr int NW = 4, BM = 64 * NW;
-  const int MT = (p.N + BM - 1) / BM;
-  const int PT = p.causal ? (MT + 1) / 2 : MT;
-  const size_t lds = 4 * 64 * TileGeom<D, 2>::ROWB;
-  auto kern = fwd2_kernel<T, D, NW>;
-  static std::atomic<uint64_t> lds_ok{0};
-  if (hipError_t e = ensure_dynamic_lds(kern, lds, lds_ok); e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(p.B * p.H * PT)), dim3(NW * 64), lds, s, p);
-  return hipGetLastError();
-}
-
-// Waves per workgroup of the row-tile kernels: 8 (one 256-row workgroup per CU) when that still gives every CU a
-// workgroup, else 4 (two 128-row workgroups per CU).  Both keep two waves per SIMD; with 8 the K / V tiles are
-// staged once per CU instead of twice, i.e. half the global loads and LDS stores per wave (C3: forward -6%).
-// tail: also apply the last-round rule of rows <= 128 bytes (below)
-static int row_tile_waves(int64_t batch_heads, int rows, bool causal, bool bits16 = false, bool tail = false) {
-  const int MT = (rows + 255) / 256, cus = cu_count();
-  const int64_t w256 = batch_heads * (causal ? (MT + 1) / 2 : MT);
-  // More 256-row workgroups than CUs, 16-bit rows <= 128 bytes (round 6, profiles/r06_form_sweep_big*.txt): the LAST round decides.  A
-  // last round that fills at most ~55 % of the CUs costs the 8-wave form a whole 256-row workgroup time; as 4-wave workgroups (two per
-  // CU) the same tail is 128-row workgroups running alone on their CUs: 264 ... 384 and 544 ... 640 workgroups on 256 CUs -4 ... -11 %,
-  // 800 and 1088 -6 ... -8 %.  Full or nearly full last rounds (C3: exactly 256) keep the 8-wave form (K / V staged once per CU).
-  if (bits16 && tail && w256 > cus) {
-    const int64_t rem = w256 % cus;
-    return (rem != 0 && rem * 20 <= (int64_t)cus * 11) ? 4 : 8;
-  }
-  if (w256 >= cus * 7 / 8) return 8;
-  // 16-bit types (round 6, tools/form_sweep.py): once the 128-row tiles outnumber the CUs -- where the key-split 8-wave form would need a
-  // second round of workgroups -- the 256-row 8-wave workgroup wins from 132 workgroups on 256 CUs up, not only from 7/8 of the CUs:
-  // rows <= 128 bytes against two 4-wave workgroups per CU -5 ... -9 % (profiles/r06_form_sweep_d64_b.txt), D = 96 / 128 (lean form)
-  // against the key-split form -25 ... -35 % (profiles/r06_form_sweep_d128_b.txt)
-  if (bits16) {
-    const int MT4 = (rows + 127) / 128;
-    if (batch_heads * (causal ? (MT4 + 1) / 2 : MT4) > cus) return 8;
-  }
-  return 4;
-}
-
-// Key-split form (fwd_kernel<.., KSPLIT>): 128-row workgroups of 8 waves.  Where the 128-row four-wave workgroups would leave the SIMDs
-// with one wave each: rows wider than 128 bytes always (that form runs one wave per SIMD whatever the grid), narrower rows when the grid
-// has fewer than ~1.5 workgroups per CU.
-template <typename T, int D, bool BIAS> constexpr bool fwd_ksplit() {
-  return Traits<T>::ES == 2 && (BIAS ? (D == 64 || D == 32 || D == 16) : (D == 64 || D == 96 || D == 128 || D == 32 || D == 16)) &&
-         (64 * TileGeom<D, Traits<T>::ES>::ROWB) % 1024 == 0;
-}
-template <typename T, int D>
-static bool use_ksplit_fwd(const FwdParams& p) {
-  const int MT = (p.N + 127) / 128;
-  const int64_t wgs = (int64_t)p.B * p.H * (p.causal ? (MT + 1) / 2 : MT) * (p.splits > 1 ? p.splits : 1);
-#ifdef FCSA_VAR_SPLIT_ENV      // sweep builds only (tools/split_sweep.py, dev/fcsa_sweep_env.h): FCSA_KSPLIT = 0 / 1 forces the form
-  if (const int v = fcsa_dev::env_int("FCSA_KSPLIT"); v >= 0) return v != 0;
-#endif
-  if (D * Traits<T>::ES > 128) return true;
-  return wgs <= cu_count();
-}
-
 // Split-key forward, second step: O = (sum_s partial P~V) / max(sum_s partial l, eps), inv_l alike.  One thread per
 // (row, 8 features); the partials are a few MB and L2-resident.
 template <typename T, int D>
@@ -1366,6 +1276,7 @@ __global__ void __launch_bounds__(256) fwd_combine_kernel(const FwdParams p) {
 template <typename T, int D, bool BIAS, int NW, bool DYN, bool LEAN = false, bool KSPLIT = false>
 static hipError_t launch_fwd_nw(const FwdParams& p, hipStream_t s) {
   constexpr int RWAVES = KSPLIT ? NW / 2 : NW, BM = 32 * RWAVES;
+  static_assert(!KSPLIT || (64 * TileGeom<D, Traits<T>::ES>::ROWB) % 1024 == 0, "key-split form: whole 1 KiB LDS-DMA pieces per tile");
   const int MT = (p.N + BM - 1) / BM;
   const int PT = p.causal ? (MT + 1) / 2 : MT;
   size_t lds = 4 * 64 * (KSPLIT ? 2 : fwd_stage_tiles<T, D, DYN>()) * TileGeom<D, Traits<T>::ES>::ROWB;      // 2 buffers x (K + V tiles of a stage)
@@ -1373,18 +1284,9 @@ static hipError_t launch_fwd_nw(const FwdParams& p, hipStream_t s) {
   if (KSPLIT && lds < (size_t)RWAVES * 64 * 16 * (TileGeom<D, Traits<T>::ES>::DB * 4 + 1)) lds = (size_t)RWAVES * 64 * 16 * (TileGeom<D, Traits<T>::ES>::DB * 4 + 1);
   // two instantiations: causal launches (select per logit on the diagonal tiles) and the others (key masks as a rank-1 MFMA)
   const dim3 grid((unsigned)(p.B * p.H * PT), (unsigned)(p.splits > 1 ? p.splits : 1));
-  if (p.causal) {
-    auto kern = fwd_kernel<T, D, NW, BIAS, DYN, LEAN, false, KSPLIT>;
-    static std::atomic<uint64_t> lds_ok{0};
-    if (hipError_t e = ensure_dynamic_lds(kern, lds, lds_ok); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, s, p);
-  } else {
-    auto kern = fwd_kernel<T, D, NW, BIAS, DYN, LEAN, true, KSPLIT>;
-    static std::atomic<uint64_t> lds_ok{0};
-    if (hipError_t e = ensure_dynamic_lds(kern, lds, lds_ok); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, s, p);
-  }
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  const hipError_t e = p.causal ? launch_with_lds<fwd_kernel<T, D, NW, BIAS, DYN, LEAN, false, KSPLIT>>(grid, dim3(NW * 64), lds, s, p)
+                                : launch_with_lds<fwd_kernel<T, D, NW, BIAS, DYN, LEAN, true, KSPLIT>>(grid, dim3(NW * 64), lds, s, p);
+  if (e != hipSuccess) return e;
   if (p.splits > 1) {
     const int64_t items = (int64_t)p.B * p.H * p.N * (D / 8);
     hipLaunchKernelGGL((fwd_combine_kernel<T, D>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p);
@@ -1392,98 +1294,51 @@ static hipError_t launch_fwd_nw(const FwdParams& p, hipStream_t s) {
   return hipGetLastError();
 }
 
-template <typename T, int D, bool BIAS>
-static hipError_t launch_fwd_b(const FwdParams& p, hipStream_t s) {
-  if (p.dyn) {                  // per-row exponent reference (online): the prefetching form, 8 waves where they fit two per SIMD
-    if constexpr (D * Traits<T>::ES <= 128) {
-      if (row_tile_waves((int64_t)p.B * p.H, p.N, p.causal, Traits<T>::ES == 2, true) == 8) return launch_fwd_nw<T, D, BIAS, 8, true>(p, s);
-    } else if constexpr (fwd_lean<T, D, BIAS>()) {
-      if (row_tile_waves((int64_t)p.B * p.H, p.N, p.causal, true) == 8) return launch_fwd_nw<T, D, BIAS, 8, true, true>(p, s);
-    }
-    if constexpr (fwd_ksplit<T, D, BIAS>()) {
-      if (use_ksplit_fwd<T, D>(p)) return launch_fwd_nw<T, D, BIAS, 8, true, !BIAS, true>(p, s);
-    }
-    return launch_fwd_nw<T, D, BIAS, 4, true>(p, s);
-  }
-  if (p.splits > 1) {                                                   // split-key path: 128-row tiles x key ranges
-    if constexpr (fwd_ksplit<T, D, BIAS>()) {
-      if (use_ksplit_fwd<T, D>(p)) return launch_fwd_nw<T, D, BIAS, 8, false, !BIAS, true>(p, s);
-    }
-    return launch_fwd_nw<T, D, BIAS, 4, false>(p, s);
-  }
-#ifdef FCSA_VAR_SPLIT_ENV      // sweep builds only (tools/form_sweep.py): FCSA_FWD_FORM = 1 row tiles of 8 waves, 2 key-split 8 waves, 3 four waves
-  if constexpr (D * Traits<T>::ES <= 128 && fwd_ksplit<T, D, BIAS>()) {
-    const int f = fcsa_dev::env_int("FCSA_FWD_FORM");
-    if (f == 1) return launch_fwd_nw<T, D, BIAS, 8, false>(p, s);
-    if (f == 2) return launch_fwd_nw<T, D, BIAS, 8, false, !BIAS, true>(p, s);
-    if (f == 3) return launch_fwd_nw<T, D, BIAS, 4, false>(p, s);
-  } else if constexpr (fwd_lean<T, D, BIAS>() && fwd_ksplit<T, D, BIAS>()) {      // 16-bit D = 96 / 128: 1 = lean 256-row tiles, 2 = lean key-split, 3 = four waves (one per SIMD)
-    const int f = fcsa_dev::env_int("FCSA_FWD_FORM");
-    if (f == 1) return launch_fwd_nw<T, D, BIAS, 8, false, true>(p, s);
-    if (f == 2) return launch_fwd_nw<T, D, BIAS, 8, false, !BIAS, true>(p, s);
-    if (f == 3) return launch_fwd_nw<T, D, BIAS, 4, false>(p, s);
-  }
-#endif
-  if constexpr (D * Traits<T>::ES <= 128) {      // two waves per SIMD whatever the grid (<= 256 registers with all prefetches)
-    if (row_tile_waves((int64_t)p.B * p.H, p.N, p.causal, Traits<T>::ES == 2, true) == 8) return launch_fwd_nw<T, D, BIAS, 8, false>(p, s);
-  } else if constexpr (fwd_lean<T, D, BIAS>()) {
-    // the lean form needs its partner wave: one 8-wave workgroup per CU (a grid with two 4-wave workgroups per CU always has that)
-    if (row_tile_waves((int64_t)p.B * p.H, p.N, p.causal, true) == 8) return launch_fwd_nw<T, D, BIAS, 8, false, true>(p, s);
-  }
-  if constexpr (fwd_ksplit<T, D, BIAS>()) {
-    if (use_ksplit_fwd<T, D>(p)) return launch_fwd_nw<T, D, BIAS, 8, false, !BIAS, true>(p, s);
-  }
-  return launch_fwd_nw<T, D, BIAS, 4, false>(p, s);
-}
-
 template <typename T, int D>
-static hipError_t launch_fwd_t(const FwdParams& p, hipStream_t s) {
-#ifdef FCSA_VAR_SPLIT_ENV      // sweep builds only (tools/form_sweep.py): FCSA_FWD_FORM = 4 the 64-rows-per-wave kernel, any other value > 0 never
-  if constexpr (Traits<T>::ES == 2 && D <= 64) {
-    if (const int f = fcsa_dev::env_int("FCSA_FWD_FORM"); f > 0) {
-      if (f == 4 && p.bias == nullptr && !p.dyn && p.splits <= 1 && p.mask == nullptr) return launch_fwd2<T, D>(p, s);
-      return p.bias != nullptr ? launch_fwd_b<T, D, true>(p, s) : launch_fwd_b<T, D, false>(p, s);
-    }
-  }
-#endif
-  if constexpr (Traits<T>::ES == 2 && D == 32) {       // (use_wide_fwd: the only head dim fwd2_kernel still wins at -- nothing else instantiates it)
-    if (p.bias == nullptr && !p.dyn && p.splits <= 1 && p.mask == nullptr && use_wide_fwd<D>(p)) return launch_fwd2<T, D>(p, s);
-  }
-  return p.bias != nullptr ? launch_fwd_b<T, D, true>(p, s) : launch_fwd_b<T, D, false>(p, s);
+static hipError_t launch_fwd2(const FwdParams& p, hipStream_t s) {
+  constexpr int NW = 4, BM = 64 * NW;
+  const int MT = (p.N + BM - 1) / BM;
+  const int PT = p.causal ? (MT + 1) / 2 : MT;
+  return launch_with_lds<fwd2_kernel<T, D, NW>>(dim3((unsigned)(p.B * p.H * PT)), dim3(NW * 64), 4 * 64 * TileGeom<D, 2>::ROWB, s, p);
 }
 
-template <typename T>
-static hipError_t launch_fwd_d(int D, const FwdParams& p, hipStream_t s) {
-#ifdef FCSA_DEV_ONLY      // development builds: one instantiation (bf16, D = 64)
-#ifndef FCSA_DEV_D
-#define FCSA_DEV_D 64
-#endif
-  if constexpr (std::is_same<T, BF16>::value) { if (D == FCSA_DEV_D) return launch_fwd_t<T, FCSA_DEV_D>(p, s); }
-  return hipErrorInvalidValue;
-#else
-  switch (D) {
-    case 16:  return launch_fwd_t<T, 16>(p, s);
-    case 32:  return launch_fwd_t<T, 32>(p, s);
-    case 64:  return launch_fwd_t<T, 64>(p, s);
-    case 96:  return launch_fwd_t<T, 96>(p, s);
-    case 128: return launch_fwd_t<T, 128>(p, s);
-    default:  return hipErrorInvalidValue;
+// the instantiation of form f (choose_forward, fcsa_dispatch.h)
+template <typename T, int D, bool BIAS, bool DYN>
+static hipError_t launch_fwd_form(FwdForm f, const FwdParams& p, hipStream_t s) {
+  constexpr int ES = Traits<T>::ES;
+  switch (f) {
+    case FwdForm::Rows8:
+      if constexpr (D * ES <= 128) return launch_fwd_nw<T, D, BIAS, 8, DYN>(p, s);
+      break;
+    case FwdForm::Lean8:
+      if constexpr (fwd_lean(ES, D, BIAS)) return launch_fwd_nw<T, D, BIAS, 8, DYN, true>(p, s);
+      break;
+    case FwdForm::KSplit8:
+      if constexpr (fwd_ksplit(ES, D, BIAS)) return launch_fwd_nw<T, D, BIAS, 8, DYN, !BIAS, true>(p, s);
+      break;
+    case FwdForm::Waves4:
+      return launch_fwd_nw<T, D, BIAS, 4, DYN>(p, s);
+    case FwdForm::Fwd2:
+      if constexpr (fwd2_compiled(ES, D) && !BIAS && !DYN) return launch_fwd2<T, D>(p, s);
+      break;
+    case FwdForm::Fwd3:
+      break;
   }
-#endif
+  return hipErrorInvalidValue;
 }
 
 hipError_t launch_forward(int dtype, int D, const FwdParams& p, hipStream_t s) {
   if (p.B * p.H == 0 || p.N == 0) return hipSuccess;
-#ifdef FCSA_VAR_SPLIT_ENV      // sweep builds only: FCSA_FWD_FORM = 5 forces the D = 128 64-rows-per-wave kernel whatever the grid, 1 .. 4 never take it
-  if (const int f = fcsa_dev::env_int("FCSA_FWD_FORM"); f > 0) {
-    if (f == 5 && D == 128 && (dtype == 1 || dtype == 2) && p.bias == nullptr && p.mask == nullptr && !p.dyn && p.splits <= 1) return launch_forward_wide128(dtype, p, s);
-  } else
-#endif
-  if (use_forward_wide128(dtype, D, p)) return launch_forward_wide128(dtype, p, s);
-  if (dtype == 2) return launch_fwd_d<BF16>(D, p, s);
-  if (dtype == 1) return launch_fwd_d<F16>(D, p, s);
-  if (dtype == 0) return launch_fwd_d<F32>(D, p, s);
-  return hipErrorInvalidValue;
+  const FwdProblem fp = {dtype == 0 ? 4 : 2, D, (int64_t)p.B * p.H, p.N, p.M, p.causal != 0, p.bias != nullptr, p.mask != nullptr, p.dyn != 0,
+                         p.splits, p.q.sn, p.k.sn, p.v.sn, forward_wide128_mode(-1)};
+  const FwdForm f = choose_forward(fp, cu_count());
+  if (f == FwdForm::Fwd3) return launch_forward_wide128(dtype, p, s);
+  return dispatch_dtype_d(dtype, D, [&](auto td) {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    if (p.bias != nullptr) return p.dyn ? launch_fwd_form<T, DD, true, true>(f, p, s) : launch_fwd_form<T, DD, true, false>(f, p, s);
+    return p.dyn ? launch_fwd_form<T, DD, false, true>(f, p, s) : launch_fwd_form<T, DD, false, false>(f, p, s);
+  });
 }
 
 }  // namespace fcsa

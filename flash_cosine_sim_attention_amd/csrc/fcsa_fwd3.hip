@@ -574,11 +574,7 @@ static hipError_t launch_fwd3_t(const FwdParams& p, hipStream_t s) {
   const int PT = p.causal ? (MT + 1) / 2 : MT;
   size_t lds = (size_t)2 * R * 16384;
   if (lds < (size_t)4 * RowEpilogue<T, 128>::BYTES_NOX) lds = (size_t)4 * RowEpilogue<T, 128>::BYTES_NOX;
-  auto kern = fwd3_kernel<T, R, RSUM>;
-  static std::atomic<uint64_t> lds_ok{0};
-  if (hipError_t e = ensure_dynamic_lds(kern, lds, lds_ok); e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(p.B * p.H * PT)), dim3(256), lds, s, p);
-  return hipGetLastError();
+  return launch_with_lds<fwd3_kernel<T, R, RSUM>>(dim3((unsigned)(p.B * p.H * PT)), dim3(256), lds, s, p);
 }
 
 // Escape hatch (same-process A/B, triage): 0 = never take this form.  The environment is read ONCE, when the library is loaded
@@ -592,26 +588,7 @@ int forward_wide128_mode(int set) {      // set < 0: query only; returns the pre
   return set < 0 ? g_wide128.load(std::memory_order_relaxed) : g_wide128.exchange(set != 0 ? 1 : 0, std::memory_order_relaxed);
 }
 
-// Does this problem take the form above?  16-bit D = 128, static exponent shift, no bias, no key mask, no key split, a grid of 256-row
-// (causal: paired) workgroups that covers the chip -- or, from 2048 keys, more than half of it -- K / V slices addressable with 32-bit offsets.
-bool use_forward_wide128(int dtype, int D, const FwdParams& p) {
-  if (D != 128 || (dtype != 1 && dtype != 2)) return false;
-  if (p.bias != nullptr || p.mask != nullptr || p.dyn || p.splits > 1) return false;
-  if (g_wide128.load(std::memory_order_relaxed) == 0) return false;
-  const int MT = (p.N + 255) / 256;
-  const int64_t wgs = (int64_t)p.B * p.H * (p.causal ? (MT + 1) / 2 : MT);
-  if (wgs < cu_count() * 7 / 8) {
-    // round 6 (tools/form_sweep.py, profiles/r06_form_sweep_d128_b.txt): also where the 128-row tiles outnumber the CUs (132 ... 223 of
-    // these workgroups on 256 CUs) and the pass is long enough for its prologue: 31 - 36 % faster than the key-split lean form there, and
-    // ahead of the 256-row lean form from 2048 keys (level at 1024 keys up to ~176 workgroups, behind beyond)
-    const int MT4 = (p.N + 127) / 128;
-    if ((int64_t)p.B * p.H * (p.causal ? (MT4 + 1) / 2 : MT4) <= cu_count() || p.M < 2048) return false;
-  }
-  if ((int64_t)(p.M + 64 * 6) * p.k.sn >= 0x7fffffffLL || (int64_t)(p.M + 64 * 6) * p.v.sn >= 0x7fffffffLL) return false;
-  if ((int64_t)(p.N + 256) * p.q.sn >= 0x7fffffffLL) return false;
-  return true;
-}
-
+// (which problems take this form: fwd3_applies, fcsa_dispatch.h)
 hipError_t launch_forward_wide128(int dtype, const FwdParams& p, hipStream_t s) {
   return dtype == 2 ? launch_fwd3_t<BF16, kFwd3Ring, kFwd3RoundedSums>(p, s) : launch_fwd3_t<F16, kFwd3Ring, kFwd3RoundedSums>(p, s);
 }

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <atomic>
 
+#include "fcsa_dispatch.h"
+
 namespace fcsa {
 
 // [B, H, L, D] view with BYTE strides; feature dim contiguous.
@@ -101,6 +103,16 @@ static inline hipError_t ensure_dynamic_lds(K kern, size_t lds, std::atomic<uint
   return e;
 }
 
+// Launch one kernel instantiation with `lds` bytes of dynamic LDS, raising its limit first (once per device: the static belongs to the
+// instantiation).  The kernels take their parameter block(s) by value.
+template <auto Kernel, typename... Args>
+static inline hipError_t launch_with_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args&... args) {
+  static std::atomic<uint64_t> done{0};
+  if (hipError_t e = ensure_dynamic_lds(Kernel, lds, done); e != hipSuccess) return e;
+  hipLaunchKernelGGL(Kernel, grid, block, lds, s, args...);
+  return hipGetLastError();
+}
+
 // Compute units of the CURRENT device: what every "does this grid cover the chip" threshold of the launchers and of the C ABI's split
 // rules is a multiple of.  Cached per device id (a process may drive unlike devices, e.g. partitioned CPX modes); a query that fails is
 // answered with 256 and NOT remembered (host-only callers: workspace-size queries in the CPU tests; a process that asks before its
@@ -129,15 +141,11 @@ inline int cu_count() {
 // dtype: 1 = f16, 2 = bf16 (fcsa_dtype); returns hipError_t of the launch
 hipError_t launch_forward(int dtype, int D, const FwdParams& p, hipStream_t s);
 // fcsa_fwd3.hip: the 64-rows-per-wave, one-wave-per-SIMD forward for 16-bit D = 128 (launch_forward dispatches to it)
-bool use_forward_wide128(int dtype, int D, const FwdParams& p);
 int forward_wide128_mode(int set);      // debug knob behind fcsa_debug_forward_form: set < 0 queries; returns the previous value
 hipError_t launch_forward_wide128(int dtype, const FwdParams& p, hipStream_t s);
 hipError_t launch_backward_dq(int dtype, int D, const BwdParams& p, hipStream_t s);
 hipError_t launch_backward_dbias(int dtype, int D, const BwdParams& p, hipStream_t s);   // d_bias from recomputed dS tiles (after dq: needs delta)
 hipError_t launch_backward_dkv(int dtype, int D, const BwdParams& p, hipStream_t s);
-// the group-sweep dK/dV form (BwdParams::kv_sweep): whether it is compiled for (dtype, D), and whether the dispatch takes it for a grid of
-// batch_kv_heads * key tiles (mode: 0 never, 1 where the sweep grid covers the chip, 2 wherever it is compiled)
-bool backward_dkv_sweep(int dtype, int D, int64_t batch_kv_heads, int N, int M, int causal, int mode);
 int kv_group_mode(int set);             // debug knob behind fcsa_debug_kv_group_form: set < 0 queries; returns the previous value
 hipError_t launch_l2norm(int dtype, const NormParams& p, hipStream_t s);
 hipError_t launch_l2norm_pair(int dtype, const NormParams& a, const NormParams& b, hipStream_t s);   // q and k in one grid

@@ -195,12 +195,9 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> forward(const Tensor&
   a.norm.rk = (l2norm_qk && need_backward) ? rk.data_ptr<float>() : nullptr;
   Tensor ws;
   a.workspace = nullptr; a.workspace_bytes = 0;
-  if (c.B * c.H * c.N < (causal ? 65536 : 32768)) {   // only grids that cannot fill the chip ever split the key range (< 256 row tiles of 128; causal: < 256 PAIRS of them)
-    const size_t need = g_abi.forward_ws(&a.p);
-    if (need > 0) {
-      ws = at::empty({(int64_t)need}, opt.dtype(at::kByte));
-      a.workspace = ws.data_ptr(); a.workspace_bytes = need;
-    }
+  if (const size_t need = g_abi.forward_ws(&a.p); need > 0) {      // 0 unless the key range is split (grids that cannot fill the chip)
+    ws = at::empty({(int64_t)need}, opt.dtype(at::kByte));
+    a.workspace = ws.data_ptr(); a.workspace_bytes = need;
   }
   a.stream = stream_of(q);
   lap.mark(1);

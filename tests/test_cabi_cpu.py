@@ -145,7 +145,7 @@ def test_backward_workspace_single_head_non_causal_stays_small(lib):
 
 def test_backward_workspace_split_query_dkv(lib):
     """Split-query dK/dV (few keys, many queries, K/V with heads): dkv_splits f32 slabs for dk and for dv, sized by the
-    rule the launch uses (fcsa_capi.hip backward_dkv_splits -> best_split: the argmin of the cost model over 1 .. 16)."""
+    rule the launch uses (fcsa_dispatch.h backward_dkv_splits -> best_split: the argmin of the cost model over 1 .. 16)."""
     al = lambda x: (x + 255) // 256 * 256
     # 1 x 8 heads x 1024 keys = 64 key tiles -> 4 splits of 2048 queries: 256 workgroups, one round (measured 53.3 us against 53.6 with
     # the 8 splits of rounds 2 - 5, profiles/r06_split_sweep_bwd_d64.txt; its 512 dQ row tiles need no split)
@@ -180,7 +180,7 @@ def _split_counts(lib, **kw):
 
 
 def test_split_counts_follow_the_measured_tables(lib):
-    """The split counts are the argmin of a cost model fitted to tools/split_sweep.py tables (fcsa_capi.hip best_split, round 6).  Pinned
+    """The split counts are the argmin of a cost model fitted to tools/split_sweep.py tables (fcsa_dispatch.h best_split, round 6).  Pinned
     here: its choice on shapes of those tables where the winner is clear (profiles/r06_split_sweep_*.txt; the CPU answer uses 256 CUs,
     the MI355X count), and the invariants every count keeps."""
     f16, bf16 = 1, 2

@@ -1,4 +1,4 @@
-"""Parity of the 64-rows-per-wave, one-wave-per-SIMD forward for 16-bit D = 128 (csrc/fcsa_fwd3.hip, `use_forward_wide128`):
+"""Parity of the 64-rows-per-wave, one-wave-per-SIMD forward for 16-bit D = 128 (csrc/fcsa_fwd3.hip, chosen by `fwd3_applies`):
 no bias, no key mask, static exponent shift, grids whose 256-row (causal: paired) workgroups cover the chip.
 
   * against the float64 oracle on (batch, head) slices -- forward elementwise and all gradients (they consume this kernel's O and inv_l):
@@ -27,7 +27,7 @@ def _npf(t):
 
 
 def _grid_ok(B, H, N, causal, M=0):
-    """the dispatch rule of use_forward_wide128 (csrc/fcsa_fwd3.hip): 256-row (causal: paired) workgroups >= 7/8 of the device's CUs, or
+    """the dispatch rule of fwd3_applies (csrc/fcsa_dispatch.h): 256-row (causal: paired) workgroups >= 7/8 of the device's CUs, or
     -- round 6 -- more 128-row tiles than CUs and >= 2048 keys"""
     MT, MT4 = (N + 255) // 256, (N + 127) // 128
     cus = torch.cuda.get_device_properties(0).multi_processor_count

@@ -4,7 +4,7 @@ launch_forward picks it when the 256-row workgroups cover the chip (>= 224 of th
   * not causal with >= 4096 keys, or
   * causal with N >= 8192
 (rounds 1 - 5 also sent dim_head 64 and non-causal problems of any length there; round 6 re-measured: the 32-row kernel at two waves
-per SIMD is 13 - 16 % faster at dim_head 64 since its round-4 changes -- fcsa_fwd.hip use_wide_fwd.  dim_head 96 went to the lean
+per SIMD is 13 - 16 % faster at dim_head 64 since its round-4 changes -- fcsa_dispatch.h fwd2_applies.  dim_head 96 went to the lean
 two-wave 32-row kernel in round 3.  The other cases below stay as parity cases of whatever kernel the dispatch gives them).
 The shapes below are chosen to land on it through the normal dispatch:
   * many small heads (batch*heads = 224+), checked against the float64 oracle elementwise with the stated tolerances,

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Fits the split-count cost model of fcsa_capi.hip (split_cost) to tools/split_sweep.py tables and reports, per shape, what the fitted
+"""Fits the split-count cost model of fcsa_dispatch.h (split_cost) to tools/split_sweep.py tables and reports, per shape, what the fitted
 model picks against the measured best (the regret) and what the round-5 rule ("enough workgroups for two per CU") picked.
 usage: split_model_fit.py fwd|dq|dkv table.txt [table.txt ...]        (prints the constants in the order split_cost takes them)"""
 import re, sys, math
@@ -57,7 +57,7 @@ def cost(theta, kind, sh, s, form):
     return rounds * per + comb
 
 def product_form(kind, sh, s):
-    """the form the launchers run for this count (fwd: use_ksplit_fwd; backward: 8-wave forms un-split, 4-wave workgroups when split)"""
+    """the form the launchers run for this count (fwd: fwd_ksplit_pays; backward: 8-wave forms un-split, 4-wave workgroups when split)"""
     if kind == "fwd": return "A" if (sh["D"] * 2 > 128 or sh["tiles"] * s <= CUS) else "W"
     return "A" if s == 1 else "W"
 
