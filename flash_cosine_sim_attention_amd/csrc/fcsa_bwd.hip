@@ -43,25 +43,8 @@ constexpr int kDkvBmq8 = 128;        // staged query rows of the 8-wave dKV kern
 constexpr int kDkvBmqWide = 64;      // staged query rows of the dKV kernel for 16-bit D >= 96 (LDS-DMA form)
 constexpr bool kDkvRing = true;
       // three-buffer ring + tile pipeline across the tile barrier (dkv_tile_pipe)
-#ifdef FCSA_TRACE
-__device__ unsigned long long g_trace_dkv[128];
-__device__ unsigned long long g_trace_dq[128];
-#endif
-#ifdef FCSA_TRACE_BAR      // per wave of one workgroup: ticks spent at the tile barrier / in the tile loops (two s_memtime per tile, nothing else)
-__device__ unsigned long long g_trace_bar_dkv[64];
-__device__ unsigned long long g_trace_bar_dq[64];
-#define FCSA_BAR_BEGIN(v) do { asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(v)); } while (0)
-#define FCSA_BAR_END(v, acc) do { unsigned long long e_; asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(e_)); acc += e_ - v; } while (0)
-#else
-#define FCSA_BAR_BEGIN(v) ((void)0)
-#define FCSA_BAR_END(v, acc) ((void)0)
-#endif
-#ifdef FCSA_TRACE_WG
-__device__ unsigned long long g_trace_wg_dkv[2048];      // per workgroup: [2 * id] = start time, [2 * id + 1] = end time (wave 0)
-__device__ unsigned long long g_trace_wg_dq[2048];
-__device__ unsigned long long g_trace_pass_dq[2560];       // per workgroup (first 256): [pass][5] pass marks of wave 0
-__device__ unsigned long long g_trace_pass_dkv[2560];
-#endif
+FCSA_TRACE_SITE(dq)
+FCSA_TRACE_SITE(dkv)
 
 // =============================================================================================
 // dQ kernel
@@ -275,17 +258,8 @@ __global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const Bw
   const uint32_t ncm = causal ? 0u : 0xffffffffu;   // OR-ed into the causal bit mask: all ones when not causal
   Trace ts;
   ts.reset();
-#ifdef FCSA_TRACE_WG
-  const unsigned long long trace_t0 = trace_now();
-#endif
-#ifdef FCSA_TRACE
-  unsigned long long pass_marks[2][5] = {{0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}};
-#define FCSA_PASS_MARK(k) pass_marks[pass][k] = trace_now()
-#elif defined(FCSA_TRACE_WG)
-#define FCSA_PASS_MARK(k) do { if (tid == 0 && blockIdx.y == 0 && blockIdx.x < 256) g_trace_pass_dq[blockIdx.x * 10 + pass * 5 + (k)] = trace_now(); } while (0)
-#else
-#define FCSA_PASS_MARK(k) ((void)0)
-#endif
+  TraceRec<TraceSite_dq> tr;
+  tr.start();
   // K / V stages: LDS-DMA for 16-bit types (no staging registers, no ds_write passes; see DmaStager), else through registers.
   constexpr bool DMA = dq_dma<T, D>(SUB);
   // SEP: the epilogue scratch has its own LDS bytes behind the staging buffers.  Then nothing of one (row tile) iteration has to
@@ -393,11 +367,8 @@ __global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const Bw
       EP::load_inv(rinv_n, p.rq + (((int64_t)b_ * p.H + h_) * p.N + m0_ + rwave * 32) * p.G, p.G, p.lgm, ln, rows_valid_);
   };
 
-#ifdef FCSA_TRACE_BAR
-  unsigned long long bar_wait = 0, bar_loop = 0;
-#endif
   for (int pass = 0; pass < npass; ++pass) {
-  FCSA_PASS_MARK(0);
+  tr.mark(pass, 0);
   int m0, nt;
   geometry(pass, m0, nt);
   const int mw = m0 + rwave * 32;
@@ -491,10 +462,7 @@ __global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const Bw
     t_split = min(t_split, nt);
   }
 
-#ifdef FCSA_TRACE_BAR
-  unsigned long long bar_t = 0, loop_t = 0;
-  FCSA_BAR_BEGIN(loop_t);
-#endif
+  tr.loop_begin();
   DqPipe<T, D> pipe;
   pipe.tile = -1;
   auto run = [&](auto masked_tag, int t_begin, int t_end) {
@@ -580,18 +548,18 @@ __global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const Bw
           }
         }
         FCSA_STAMP(ts, 3);
-        FCSA_BAR_BEGIN(bar_t);
+        FCSA_BAR_BEGIN(tr);
         __syncthreads();
-        FCSA_BAR_END(bar_t, bar_wait);
+        FCSA_BAR_END(tr);
       }
       FCSA_STAMP(ts, 4);
       if constexpr (!MASKED) ts.close(4);
     }
   };
-  FCSA_PASS_MARK(1);
+  tr.mark(pass, 1);
   if constexpr (!KSPLIT) {
     run(std::integral_constant<int, 0>{}, 0, t_split);
-    FCSA_PASS_MARK(2);
+    tr.mark(pass, 2);
     run(std::integral_constant<int, KM ? 2 : 1>{}, t_split, nt);
   } else {
     // stage u = tiles 2u, 2u + 1; this wave's tile is t = 2u + half; one barrier per stage for every wave (see fwd_kernel, KSPLIT)
@@ -625,18 +593,16 @@ __global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const Bw
       if constexpr (MODE == 1) skip = skip || (causal && j0 > mw + 31 + diff);
       if (!skip) dq_tile<T, D, tile_mode<MODE>(), BIAS, TWO>(kcur, vcur, fa, qf, dof, dq, lc, delta, p, word, ncm, i, j0, diff, bias_row, Mk);
       if (more) dma_wait();
-      FCSA_BAR_BEGIN(bar_t);
+      FCSA_BAR_BEGIN(tr);
       __syncthreads();
-      FCSA_BAR_END(bar_t, bar_wait);
+      FCSA_BAR_END(tr);
     };
     for (int u = 0; u < u_split; ++u) stage(std::integral_constant<int, 0>{}, u);
-    FCSA_PASS_MARK(2);
+    tr.mark(pass, 2);
     for (int u = u_split; u < nst; ++u) stage(std::integral_constant<int, KM ? 2 : 1>{}, u);
   }
-  FCSA_PASS_MARK(3);
-#ifdef FCSA_TRACE_BAR
-  FCSA_BAR_END(loop_t, bar_loop);
-#endif
+  tr.mark(pass, 3);
+  tr.loop_end();
   if constexpr (KSPLIT) {
     // the odd-tile half hands its dQ partials to the even-tile half of the same rows (the staging buffers are free: every stage ended
     // with a barrier); done before anything of the epilogue or the next pass touches the LDS
@@ -699,23 +665,9 @@ __global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const Bw
       if (pass + 1 < npass) __syncthreads();      // the scratch overlaps the staging buffers of the next pass
     }
   }
-  FCSA_PASS_MARK(4);
+  tr.mark(pass, 4);
   }   // pass
-#undef FCSA_PASS_MARK
-#ifdef FCSA_TRACE_BAR
-  if (blockIdx.x == gridDim.x / 2 + 3 && blockIdx.y == 0 && lane == 0) { g_trace_bar_dq[2 * wave] = bar_wait; g_trace_bar_dq[2 * wave + 1] = bar_loop; }
-#endif
-#ifdef FCSA_TRACE_WG
-  if (tid == 0 && blockIdx.y == 0 && blockIdx.x < 1024) { g_trace_wg_dq[2 * blockIdx.x] = trace_t0; g_trace_wg_dq[2 * blockIdx.x + 1] = trace_now(); }
-#endif
-#ifdef FCSA_TRACE
-  if (blockIdx.x == gridDim.x / 2 + 3 && (tid & 63) == 0 && (wave & 2) == 0) {      // waves 0, 1, 4, 5
-    unsigned long long* out = g_trace_dq + 32 * ((wave & 1) + 2 * (wave >> 2));
-    ts.dump(out, trace_now() - trace_t0);
-    for (int ps = 0; ps < 2; ++ps)
-      for (int k = 0; k < 4; ++k) out[14 + 4 * ps + k] = pass_marks[ps][k + 1] - pass_marks[ps][k];   // prologue | unmasked tiles | masked tiles | epilogue
-  }
-#endif
+  tr.finish(ts, wave, (wave & 2) == 0, trace_row8(wave));      // pass intervals: prologue | unmasked tiles | masked tiles | epilogue
 }
 
 // =============================================================================================
@@ -1179,17 +1131,8 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
   const int64_t rk_bh = (int64_t)b * (p.H / p.kv_group) + hk;      // (batch, K/V head) row block of rk
   Trace ts;
   ts.reset();
-#ifdef FCSA_TRACE_WG
-  const unsigned long long trace_t0 = trace_now();
-#endif
-#ifdef FCSA_TRACE
-  unsigned long long pass_marks[2][5] = {{0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}};
-#define FCSA_PASS_MARK(k) pass_marks[pass][k] = trace_now()
-#elif defined(FCSA_TRACE_WG)
-#define FCSA_PASS_MARK(k) do { if (tid == 0 && blockIdx.x < 256) g_trace_pass_dkv[blockIdx.x * 10 + pass * 5 + (k)] = trace_now(); } while (0)
-#else
-#define FCSA_PASS_MARK(k) ((void)0)
-#endif
+  TraceRec<TraceSite_dkv, kTraceAll, 5, false> tr;
+  tr.start();
   // (batch, head) is fixed for the workgroup: everything that does not depend on the pass is set up once
   // split-query launches (gridDim.y = p.dkv_splits > 1): this workgroup sees the query tiles [t_lo, QT) of its key tile
   // only and writes its partial dK^ / dV (f32) to slab blockIdx.y; the finalize kernel sums the slabs (and applies the l2norm backward).
@@ -1367,11 +1310,8 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
     }
   };
 
-#ifdef FCSA_TRACE_BAR
-  unsigned long long bar_wait = 0, bar_loop = 0;
-#endif
   for (int pass = 0; pass < npass; ++pass) {
-  FCSA_PASS_MARK(0);
+  tr.mark(pass, 0);
   int n0, t0;
   geometry(pass, n0, t0);
   const int nw = n0 + rwave * 32;                       // first key of this wave
@@ -1458,10 +1398,7 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
   // SWEEP: this wave skips the first tile of every head (see `skip` below): the last tile of a head must not prefetch into it
   const bool head_skip0 = SWEEP && causal && t_m > t0 && t0 * BMQ + hq + BMS - 1 + diff < nw;
 
-#ifdef FCSA_TRACE_BAR
-  unsigned long long bar_t = 0, loop_t = 0;
-  FCSA_BAR_BEGIN(loop_t);
-#endif
+  tr.loop_begin();
   DkvPipe<T, D, BMS> pipe;      // RING: lives across the tiles of a pass
   int pipe_tile = -1;           // RING: the tile whose first block's fragments are in flight
   int ring = 0;                 // RING: staging buffer of the current tile (t - t0 mod 3, kept without a division)
@@ -1543,24 +1480,22 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
       if (more) store_tile(nxt);
       if constexpr (SWEEP) tpar ^= 1;
       FCSA_STAMP(ts, 9);
-      FCSA_BAR_BEGIN(bar_t);
+      FCSA_BAR_BEGIN(tr);
       __syncthreads();
-      FCSA_BAR_END(bar_t, bar_wait);
+      FCSA_BAR_END(tr);
       FCSA_STAMP(ts, 10);
       if constexpr (!MASKED) ts.close(10);
     }
   };
-  FCSA_PASS_MARK(1);
+  tr.mark(pass, 1);
   tpar = 0;
   for (gi = 0; gi < (SWEEP ? p.kv_group : 1); ++gi) {      // (SWEEP: the heads of the group, in order; dk / dv accumulate across them)
     run(std::integral_constant<int, KM ? 2 : 1>{}, t0, t_m);
-    FCSA_PASS_MARK(2);
+    tr.mark(pass, 2);
     run(std::integral_constant<int, 0>{}, t_m, QT);
   }
-  FCSA_PASS_MARK(3);
-#ifdef FCSA_TRACE_BAR
-  FCSA_BAR_END(loop_t, bar_loop);
-#endif
+  tr.mark(pass, 3);
+  tr.loop_end();
 
   if constexpr (QSPLIT) {
     // the second-half waves hand their dK / dV partials to the first-half waves of the same keys (the staging buffers are free: every
@@ -1629,61 +1564,10 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
       if (pass + 1 < npass) __syncthreads();      // the scratch overlaps the staging buffers of the next pass
     }
   }
-  FCSA_PASS_MARK(4);
+  tr.mark(pass, 4);
   }   // pass
-#undef FCSA_PASS_MARK
-#ifdef FCSA_TRACE_BAR
-  if (blockIdx.x == gridDim.x / 2 + 3 && lane == 0) { g_trace_bar_dkv[2 * wave] = bar_wait; g_trace_bar_dkv[2 * wave + 1] = bar_loop; }
-#endif
-#ifdef FCSA_TRACE_WG
-  if (tid == 0 && blockIdx.x < 1024) { g_trace_wg_dkv[2 * blockIdx.x] = trace_t0; g_trace_wg_dkv[2 * blockIdx.x + 1] = trace_now(); }
-#endif
-#ifdef FCSA_TRACE
-  if (blockIdx.x == gridDim.x / 2 + 3 && (tid & 63) == 0 && (wave & 2) == 0) {      // waves 0, 1, 4, 5
-    unsigned long long* out = g_trace_dkv + 32 * ((wave & 1) + 2 * (wave >> 2));
-    ts.dump(out, trace_now() - trace_t0);
-    for (int ps = 0; ps < 2; ++ps)
-      for (int k = 0; k < 4; ++k) out[14 + 4 * ps + k] = pass_marks[ps][k + 1] - pass_marks[ps][k];   // prologue | masked tiles | unmasked tiles | epilogue
-  }
-#endif
+  tr.finish(ts, wave, (wave & 2) == 0, trace_row8(wave));      // pass intervals: prologue | masked tiles | unmasked tiles | epilogue
 }
-
-#ifdef FCSA_TRACE_WG
-}  // namespace fcsa
-extern "C" int fcsa_trace_read_wg_dq(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(fcsa::g_trace_wg_dq), sizeof(unsigned long long) * 2048);
-}
-extern "C" int fcsa_trace_read_pass_dq(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(fcsa::g_trace_pass_dq), sizeof(unsigned long long) * 2560);
-}
-extern "C" int fcsa_trace_read_pass_dkv(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(fcsa::g_trace_pass_dkv), sizeof(unsigned long long) * 2560);
-}
-extern "C" int fcsa_trace_read_wg_dkv(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(fcsa::g_trace_wg_dkv), sizeof(unsigned long long) * 2048);
-}
-namespace fcsa {
-#endif
-#ifdef FCSA_TRACE_BAR
-}  // namespace fcsa
-extern "C" int fcsa_trace_read_bar_dkv(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(fcsa::g_trace_bar_dkv), sizeof(unsigned long long) * 64);
-}
-extern "C" int fcsa_trace_read_bar_dq(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(fcsa::g_trace_bar_dq), sizeof(unsigned long long) * 64);
-}
-namespace fcsa {
-#endif
-#ifdef FCSA_TRACE
-}  // namespace fcsa
-extern "C" int fcsa_trace_read_dq(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(fcsa::g_trace_dq), sizeof(unsigned long long) * 128);
-}
-extern "C" int fcsa_trace_read_dkv(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(fcsa::g_trace_dkv), sizeof(unsigned long long) * 128);
-}
-namespace fcsa {
-#endif
 
 template <typename T, int D, bool BIAS, int NW, bool TWO, bool KSPLIT = false>
 static hipError_t launch_dq_nw(const BwdParams& p, hipStream_t s) {

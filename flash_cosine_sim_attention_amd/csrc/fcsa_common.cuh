@@ -27,6 +27,9 @@
 #include <stdint.h>
 #include "fcsa_kernels.h"
 
+#define FCSA_DEV __device__ __forceinline__
+#include "fcsa_trace.h"      // in-kernel timing instrumentation (development builds)
+
 namespace fcsa {
 
 typedef float    f32x16 __attribute__((ext_vector_type(16)));
@@ -40,8 +43,6 @@ typedef __bf16   bf16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8  __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2  __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x4  __attribute__((ext_vector_type(4)));
-
-#define FCSA_DEV __device__ __forceinline__
 
 // NOTE: always pass vector ELEMENTS through this by-value helper.  `__builtin_bit_cast(float, v[t])`
 // applied directly to an ext_vector element lvalue is miscompiled by hipcc 7.2 (it reads element 0
@@ -773,48 +774,6 @@ template <typename T, int D, int NW, int STAGE, bool AHEAD_OK, int CAP> struct E
   static FCSA_DEV char* scratch(char* smem, int wave) { return smem + (SEP ? STAGE : 0) + wave * PER_WAVE; }
   static FCSA_DEV char* xarea(char* smem, int wave) { return SEP ? smem + STAGE / 2 + wave * 32 * XROW : scratch(smem, wave) + 32 * EP::PITCH; }
 };
-
-// ---- in-kernel phase timing (trace builds only: make EXTRA=-DFCSA_TRACE OUT=../libfcsa_hip_trace.so) ----
-// s_memtime stamps are ISSUED at phase boundaries and only READ after an explicit lgkmcnt(0) at the end of
-// the iteration, so they do not add waits inside the pipeline (SMEM returns out of order: a pending stamp only
-// makes the compiler's lgkmcnt(n) waits marginally more conservative).  Product builds compile all of it away.
-#ifdef FCSA_TRACE
-struct Trace {
-  static constexpr int N = 12;
-  unsigned long long t[N];
-  unsigned long long acc[N];
-  unsigned long long iters;
-  FCSA_DEV void reset() { for (int k = 0; k < N; ++k) { t[k] = 0; acc[k] = 0; } iters = 0; }
-  FCSA_DEV void stamp(int k) {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0" : "=s"(t[k]));
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  // call once per iteration after the closing barrier; `last` = index of the last stamp taken
-  FCSA_DEV void close(int last) {
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(t[0]), "+s"(t[1]), "+s"(t[2]), "+s"(t[3]), "+s"(t[4]), "+s"(t[5]), "+s"(t[6]), "+s"(t[7]),
-                 "+s"(t[8]), "+s"(t[9]), "+s"(t[10]), "+s"(t[11]));
-    for (int k = 0; k < last; ++k) acc[k] += t[k + 1] - t[k];
-    iters += 1;
-  }
-  FCSA_DEV void dump(unsigned long long* out, unsigned long long total) const {
-    for (int k = 0; k < N; ++k) out[k] = acc[k];
-    out[N] = iters;
-    out[N + 1] = total;
-  }
-};
-#define FCSA_STAMP(ts, k) (ts).stamp(k)
-#else
-struct Trace { FCSA_DEV void reset() {} FCSA_DEV void close(int) {} };
-#define FCSA_STAMP(ts, k) ((void)0)
-#endif
-
-#if defined(FCSA_TRACE) && !defined(FCSA_TRACE_WG)
-#define FCSA_TRACE_WG      // the phase-trace build also records every workgroup's start / end time (tools/trace_wg.py)
-#endif
-#ifdef FCSA_TRACE_WG
-FCSA_DEV unsigned long long trace_now() { unsigned long long v; asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(v)); return v; }
-#endif
 
 // Issue slots of the slot-scheduled kernels (fwd2, dkv2): one MFMA + a fixed share of the VALU work + at most a couple
 // of memory instructions per slot, fenced so that hipcc's scheduler keeps exactly this program order.

@@ -54,21 +54,7 @@ constexpr int kFwdSub = 1;
 // 136.9 -> 129.9, bias form 66.8 -> 63.2, online-reference form 93.8 -> 90.4 (profiles/r04_ab_rowsum_valu.txt).  (Round 2 measured
 // the same swap at +1 % -- before LDS-DMA staging, with the MFMA group hints still counting the two row-sum MFMAs.)
 // All 16-bit forms (prefetching, lean, generic / bias) use the VALU sums; f32 keeps its per-lane adds.
-#ifdef FCSA_TRACE
-__device__ unsigned long long g_trace_fwd[128];
-#endif
-#ifdef FCSA_TRACE_BAR      // see fcsa_bwd.hip
-__device__ unsigned long long g_trace_bar_fwd[64];
-#define FCSA_BAR_BEGIN(v) do { asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(v)); } while (0)
-#define FCSA_BAR_END(v, acc) do { unsigned long long e_; asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(e_)); acc += e_ - v; } while (0)
-#else
-#define FCSA_BAR_BEGIN(v) ((void)0)
-#define FCSA_BAR_END(v, acc) ((void)0)
-#endif
-#ifdef FCSA_TRACE_WG
-__device__ unsigned long long g_trace_wg_fwd[2048];      // per workgroup: [2 * id] = start time, [2 * id + 1] = end time (wave 0)
-__device__ unsigned long long g_trace_pass_fwd[2560];     // per workgroup (first 256): [pass][5] pass marks of wave 0
-#endif
+FCSA_TRACE_SITE(fwd)      // fwd_kernel and fwd2_kernel
 
 // Per-row exponent reference of the DYN kernels, kept ONLINE (one pass over the keys).  `x` holds one block's exponents of this lane's
 // row (log2 units, relative to the row's current reference `mref`, masked positions at -inf).  The block is used as it is while its
@@ -499,23 +485,10 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ?
   const uint32_t ncm = causal ? 0u : 0xffffffffu;   // OR-ed into the causal bit mask: all ones when not causal
   Trace ts;
   ts.reset();
-#ifdef FCSA_TRACE_WG
-  const unsigned long long trace_t0 = trace_now();
-#endif
-#ifdef FCSA_TRACE
-  unsigned long long pass_marks[2][5] = {{0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}};
-  unsigned long long first_iter[2][2] = {{0, 0}, {0, 0}};      // duration of the first iteration of the [pass][unmasked, masked] loop
-#define FCSA_PASS_MARK(k) pass_marks[pass][k] = trace_now()
-#elif defined(FCSA_TRACE_WG)
-#define FCSA_PASS_MARK(k) do { if (tid == 0 && blockIdx.y == 0 && blockIdx.x < 256) g_trace_pass_fwd[blockIdx.x * 10 + pass * 5 + (k)] = trace_now(); } while (0)
-#else
-#define FCSA_PASS_MARK(k) ((void)0)
-#endif
-#ifdef FCSA_TRACE_BAR
-  unsigned long long bar_wait = 0, bar_loop = 0;
-#endif
+  TraceRec<TraceSite_fwd> tr;
+  tr.start();
   for (int pass = 0; pass < npass; ++pass) {
-  FCSA_PASS_MARK(0);
+  tr.mark(pass, 0);
   const int mt = causal ? (pass == 0 ? MT - 1 - pt : pt) : pt;      // heavy tile first
   const int m0 = mt * BM;
   const int mw = m0 + rwave * 32;                 // first query row of this wave
@@ -569,7 +542,7 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ?
   u32x4 qf[G::KS];
   request_q_rows<T, D>(p, b, h, i, fa.hi, qf);
   finish_q_frags<T, D, LEAN || (BIAS && DYN)>(p, b, h, i, fa, qf, half == 0);
-  FCSA_PASS_MARK(1);
+  tr.mark(pass, 1);
 
   f32x16 o[G::DB];
 #pragma unroll
@@ -646,7 +619,7 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ?
     }
   }
   __syncthreads();
-  FCSA_PASS_MARK(2);
+  tr.mark(pass, 2);
   // K fragments of a tile are 8 * KS registers; 512-byte rows (f32, D = 128) cannot hold them across the PV products
   constexpr bool PREFETCH_K = !LEAN && D * TR::ES < 512;      // (LEAN: K fragments are read per block inside the tile)
   if (PREFETCH_K && nt > 0) request_k(smem);
@@ -660,18 +633,12 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ?
     t_split = min(t_split, nt);
   }
 
-#ifdef FCSA_TRACE_BAR
-  unsigned long long bar_t = 0, loop_t = 0;
-  FCSA_BAR_BEGIN(loop_t);
-#endif
+  tr.loop_begin();
   auto run = [&](auto masked_tag, int t_begin, int t_end) {
     constexpr int MODE = decltype(masked_tag)::value;      // fwd_tile: 0 all valid, 1 causal select, 2 key mask by rank-1 MFMA
     constexpr bool MASKED = MODE != 0;
     for (int t = t_begin; t < t_end; ++t) {
-#ifdef FCSA_TRACE
-      if (t == t_begin + 1) first_iter[pass][MASKED ? 1 : 0] = trace_now() - first_iter[pass][MASKED ? 1 : 0];
-      if (t == t_begin) first_iter[pass][MASKED ? 1 : 0] = trace_now();
-#endif
+      FCSA_ITER(tr, pass, MASKED ? 1 : 0, t, t_begin);
       const int j0 = t * BN;
       const int u = t / SUB, sub = t % SUB;                    // stage, tile inside the stage
       const char* vcur = smem + (u & 1) * STAGE_B + (SUB + sub) * TILE_B;
@@ -719,9 +686,9 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ?
         FCSA_STAMP(ts, 5);
         if (last_of_stage) {
           if constexpr (DMA) dma_wait();
-          FCSA_BAR_BEGIN(bar_t);
+          FCSA_BAR_BEGIN(tr);
           __syncthreads();
-          FCSA_BAR_END(bar_t, bar_wait);
+          FCSA_BAR_END(tr);
           // (kPrioFwd: the younger half of the workgroup is favoured from the barrier to the end of the tile, the older half -- by age --
           //  from the top of the next tile to the barrier; see fcsa_common.cuh)
           if constexpr (kPrioFwd == 1 && NW == 8) { if (wave >= 4) __builtin_amdgcn_s_setprio(1); }
@@ -786,9 +753,9 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ?
       }
       auto mid = [&]() {
         dma_wait();
-        FCSA_BAR_BEGIN(bar_t);
+        FCSA_BAR_BEGIN(tr);
         __syncthreads();
-        FCSA_BAR_END(bar_t, bar_wait);
+        FCSA_BAR_END(tr);
       };
       bool skip = t >= nt;
       if constexpr (MODE == 1) skip = skip || (causal && j0 > mw + 31 + diff);
@@ -803,10 +770,8 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ?
     for (int u = 0; u < u_split; ++u) stage(std::integral_constant<int, 0>{}, u);
     for (int u = u_split; u < ns; ++u) stage(std::integral_constant<int, KM ? 2 : 1>{}, u);
   }
-  FCSA_PASS_MARK(3);
-#ifdef FCSA_TRACE_BAR
-  FCSA_BAR_END(loop_t, bar_loop);
-#endif
+  tr.mark(pass, 3);
+  tr.loop_end();
   // no trailing barrier: every wave completed its last LDS read before the final mid() barrier, so the next
   // pass may overwrite buffer 0 in its prologue
 
@@ -881,50 +846,14 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ?
                 p.N - mw, false, nullptr, 0, 1.f, nullptr, 1, 0, 1.f);
     if (pass + 1 < npass) __syncthreads();
   }
-  FCSA_PASS_MARK(4);
+  tr.mark(pass, 4);
   }   // pass
-#ifdef FCSA_TRACE_BAR
-  if (blockIdx.x == gridDim.x / 2 + 3 && blockIdx.y == 0 && lane == 0) { g_trace_bar_fwd[2 * wave] = bar_wait; g_trace_bar_fwd[2 * wave + 1] = bar_loop; }
-#endif
-#ifdef FCSA_TRACE_WG
-  if (tid == 0 && blockIdx.y == 0 && blockIdx.x < 1024) { g_trace_wg_fwd[2 * blockIdx.x] = trace_t0; g_trace_wg_fwd[2 * blockIdx.x + 1] = trace_now(); }
-#endif
-#ifdef FCSA_TRACE
-  if (blockIdx.x == gridDim.x / 2 + 3 && (tid & 63) == 0 && (NW == 4 ? wave < 4 : (wave & 2) == 0)) {
-    unsigned long long* out = g_trace_fwd + 32 * (NW == 4 ? wave : (wave & 1) + 2 * (wave >> 2));
-    ts.dump(out, trace_now() - trace_t0);   // 8 waves: 0, 1, 4, 5
-    for (int ps = 0; ps < 2; ++ps)
-      for (int k = 0; k < 4; ++k) out[14 + 4 * ps + k] = pass_marks[ps][k + 1] - pass_marks[ps][k];   // Q frags | first tile | key loop | epilogue
-    out[22] = pass_marks[0][0] - trace_t0;
-    for (int ps = 0; ps < 2; ++ps) { out[23 + 2 * ps] = first_iter[ps][0]; out[24 + 2 * ps] = first_iter[ps][1]; }
-  }
-#endif
+  // phase slots: pass intervals Q frags | first tile | key loop | epilogue; [22] start to pass 0; [23 + 2 * pass + loop] first iterations
+  tr.finish(ts, wave, NW == 4 ? wave < 4 : (wave & 2) == 0, NW == 4 ? wave : trace_row8(wave), [&](unsigned long long* out) {
+    out[22] = tr.marks[0][0] - tr.t0;
+    for (int ps = 0; ps < 2; ++ps) { out[23 + 2 * ps] = tr.first[ps][0]; out[24 + 2 * ps] = tr.first[ps][1]; }
+  });
 }
-
-#ifdef FCSA_TRACE_BAR
-}  // namespace fcsa
-extern "C" int fcsa_trace_read_bar_fwd(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(fcsa::g_trace_bar_fwd), sizeof(unsigned long long) * 64);
-}
-namespace fcsa {
-#endif
-#ifdef FCSA_TRACE_WG
-}  // namespace fcsa
-extern "C" int fcsa_trace_read_pass_fwd(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(fcsa::g_trace_pass_fwd), sizeof(unsigned long long) * 2560);
-}
-extern "C" int fcsa_trace_read_wg_fwd(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(fcsa::g_trace_wg_fwd), sizeof(unsigned long long) * 2048);
-}
-namespace fcsa {
-#endif
-#ifdef FCSA_TRACE
-}  // namespace fcsa
-extern "C" int fcsa_trace_read_fwd(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(fcsa::g_trace_fwd), sizeof(unsigned long long) * 128);
-}
-namespace fcsa {
-#endif
 
 // =============================================================================================
 // Wide forward kernel (16-bit types, no bias): every wave owns 64 query rows = two 32-row blocks that share each
@@ -1079,9 +1008,8 @@ __global__ void __launch_bounds__(NW * 64, 1) fwd2_kernel(const FwdParams p) {
   sv.init(p.v.sn, tid);
   Trace ts;
   ts.reset();
-#ifdef FCSA_TRACE
-  const unsigned long long trace_t0 = trace_now();
-#endif
+  TraceRec<TraceSite_fwd, kTracePhase, 0> tr;
+  tr.start();
 
   for (int pass = 0; pass < npass; ++pass) {
     const int mt = p.causal ? (pass == 0 ? MT - 1 - pt : pt) : pt;      // heavy tile first
@@ -1217,9 +1145,7 @@ __global__ void __launch_bounds__(NW * 64, 1) fwd2_kernel(const FwdParams p) {
       }
     }
   }   // pass
-#ifdef FCSA_TRACE
-  if (blockIdx.x == gridDim.x / 2 + 3 && (tid & 63) == 0 && wave < 4) ts.dump(g_trace_fwd + 32 * wave, trace_now() - trace_t0);
-#endif
+  tr.finish(ts, wave, wave < 4, wave);
 }
 
 // Split-key forward, second step: O = (sum_s partial P~V) / max(sum_s partial l, eps), inv_l alike.  One thread per

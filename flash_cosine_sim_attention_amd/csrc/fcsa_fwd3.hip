@@ -330,9 +330,7 @@ FCSA_DEV void fwd3_finish_q(const FwdParams& p, int b, int h, int i, int hi_, u3
   }
 }
 
-#ifdef FCSA_TRACE
-__device__ unsigned long long g_trace_fwd3[128];
-#endif
+FCSA_TRACE_PHASE_SITE(fwd3)
 
 template <typename T, int R, bool RSUM>
 __global__ void __launch_bounds__(256, 1) fwd3_kernel(const FwdParams p) {
@@ -368,14 +366,8 @@ __global__ void __launch_bounds__(256, 1) fwd3_kernel(const FwdParams p) {
 
   Trace ts;
   ts.reset();
-#ifdef FCSA_TRACE
-  const unsigned long long trace_t0 = trace_now();
-  unsigned long long pm[2][8];
-  for (int a_ = 0; a_ < 2; ++a_) for (int b_ = 0; b_ < 8; ++b_) pm[a_][b_] = 0;
-#define FCSA_PASS_MARK(k) pm[pass][k] = trace_now()
-#else
-#define FCSA_PASS_MARK(k) ((void)0)
-#endif
+  TraceRec<TraceSite_fwd3, kTracePhase, 8> tr;
+  tr.start();
   F3State<T> st;
   {
     // (through an opaque VGPR: as a uniform value hipcc keeps the 16-register tuple in SGPRs and re-materialises it with 8 v_mov_b64 per tile)
@@ -399,7 +391,7 @@ __global__ void __launch_bounds__(256, 1) fwd3_kernel(const FwdParams p) {
     if (p.causal) last_key = min(last_key, m0 + BM - 1 + diff);
     const int nt = last_key < 0 ? 0 : last_key / BN + 1;
 
-    FCSA_PASS_MARK(0);
+    tr.mark(pass, 0);
     // ---- prologue: the query rows, then the ring's first tiles by LDS-DMA (K(0..R-2); V(-1) = zeros in slot R-1; V(0..R-3)) ----
     u32x4 qf[2][8];
     {
@@ -429,7 +421,7 @@ __global__ void __launch_bounds__(256, 1) fwd3_kernel(const FwdParams p) {
       dv_.issue(stv, lds0 + R * TILE_B, wave);
       stv.off += v_step;
     }
-    FCSA_PASS_MARK(1);
+    tr.mark(pass, 1);
     u32x4 krs, vrs;      // the streams' descriptors, provably in SGPRs for the loop's DMA statements
 #pragma unroll
     for (int e = 0; e < 4; ++e) { krs[e] = __builtin_amdgcn_readfirstlane(stk.rs[e]); vrs[e] = __builtin_amdgcn_readfirstlane(stv.rs[e]); }
@@ -448,7 +440,7 @@ __global__ void __launch_bounds__(256, 1) fwd3_kernel(const FwdParams p) {
       }
       fwd3_finish_q<T>(p, b, h, i0 + 32, hio, qf[1]);
     }
-    FCSA_PASS_MARK(2);
+    tr.mark(pass, 2);
 #pragma unroll
     for (int r = 0; r < 2; ++r)
 #pragma unroll
@@ -480,10 +472,10 @@ __global__ void __launch_bounds__(256, 1) fwd3_kernel(const FwdParams p) {
 #pragma unroll
       for (int half = 0; half < 2; ++half)                                                                                   // V slot R - 1
         st.va[2 * db + half] = lds0 + (2 * R - 1) * TILE_B + fa.tr_off[half] + (((4 * db + fa.tr_col) ^ fa.tr_swz[half]) << 4);
-    FCSA_PASS_MARK(3);
+    tr.mark(pass, 3);
     wait_vm<0>();
     wg_barrier();
-    FCSA_PASS_MARK(4);
+    tr.mark(pass, 4);
     static_for<8>([&](auto kc) { lds_read_k<0>(st.kf[decltype(kc)::value], st.ka[decltype(kc)::value]); });      // K(0), key block 0
 
     // thresholds: key j of the tile at j0 is visible to this lane's row i iff  j <= min(i + diff, M - 1); the lane compares the
@@ -518,9 +510,9 @@ __global__ void __launch_bounds__(256, 1) fwd3_kernel(const FwdParams p) {
       }
     };
     run(std::false_type{}, 0, t_split);
-    FCSA_PASS_MARK(5);
+    tr.mark(pass, 5);
     run(std::true_type{}, t_split, nt);
-    FCSA_PASS_MARK(6);
+    tr.mark(pass, 6);
     if (nt > 0) {
       const int jl = (nt - 1) * BN;
       const int thr_last[2] = {thr0[0] - jl, thr0[1] - jl};
@@ -543,26 +535,14 @@ __global__ void __launch_bounds__(256, 1) fwd3_kernel(const FwdParams p) {
         RowEpilogue<T, D>::store(scr, st.o[r], inv, lane, out0, p.o.sn, rows_valid, false, nullptr, 0, 1.f, nullptr, 1, 0, 1.f);
       }
     }
-    FCSA_PASS_MARK(7);
+    tr.mark(pass, 7);
     if (pass + 1 < npass) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       wg_barrier();              // the scratch is free again before the next pass's DMA overwrites it
     }
   }   // pass
-#ifdef FCSA_TRACE
-  if (blockIdx.x == gridDim.x / 2 + 3 && lane == 0) {
-    ts.dump(g_trace_fwd3 + 32 * wave, trace_now() - trace_t0);
-    for (int a_ = 0; a_ < 2; ++a_) for (int b_ = 0; b_ < 8; ++b_) g_trace_fwd3[32 * wave + 14 + 8 * a_ + b_] = pm[a_][b_] ? pm[a_][b_] - trace_t0 : 0;
-  }
-#endif
+  tr.finish(ts, wave, true, wave);
 }
-#ifdef FCSA_TRACE
-}  // namespace fcsa
-extern "C" int fcsa_trace_read_fwd3(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(fcsa::g_trace_fwd3), sizeof(unsigned long long) * 128);
-}
-namespace fcsa {
-#endif
 
 constexpr int kFwd3Ring = 4;             // K and V ring depth (tiles): 128 KiB of the CU's 160; K is requested 3 tiles ahead, V 2
 constexpr bool kFwd3RoundedSums = false; // row sums of the un-rounded P~ (plain adds); true = of the rounded pair (v_dot2c: bit-identical to the
