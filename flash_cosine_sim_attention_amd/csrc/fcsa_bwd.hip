@@ -235,25 +235,20 @@ __global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const Bw
   FragAddr<T, D> fa;
   fa.init(lane);
 
-  // causal: a workgroup takes the PAIR of row tiles (MT-1-pt, pt) -> constant work per workgroup (see fwd_kernel)
-  const int MT = (p.N + BM - 1) / BM;
-  const int PT = causal ? (MT + 1) / 2 : MT;
+  // a pair of row tiles per workgroup under causal masking (tile_pairs, fcsa_dispatch.h)
   // (d_bias is not this kernel's business: bwd_dbias_kernel below recomputes the dS tiles of a bias slice and writes it once)
+  const int MT = tile_count(p.N, BM), PT = tile_pairs(MT, causal);
   int bh, pt;
-  block_to_work(blockIdx.x, p.B * p.H, PT, bh, pt);
+  block_work(blockIdx.x, p.B * p.H, PT, bh, pt);
   const int b = bh / p.H, h = bh % p.H;
-  const int npass = (causal && (MT - 1 - pt) != pt) ? 2 : 1;
+  const int npass = pair_passes(MT, pt, causal);
   // split-key launches (gridDim.y = p.dq_splits > 1): this workgroup sees the keys [k_lo, k_lo + Mk) only and
   // writes its partial dQ^ (f32) to slab blockIdx.y; the finalize kernel sums the slabs (and applies the l2norm backward).
   // Like the forward's split (fcsa_fwd.hip), for grids whose row tiles cannot fill the chip.
   // Causal launches (round 6) split the key range of EACH row tile -- the keys up to its diagonal -- so the window is set per pass
-  // (geometry below): the pair (MT-1-pt, pt) keeps its constant work, 1 / dq_splits of it per workgroup.
+  // (geometry below): the pair keeps its constant work, 1 / dq_splits of it per workgroup.
   int k_lo = 0, Mk = p.M;
-  if (p.dq_splits > 1 && !causal) {
-    const int tps = ((p.M + BN - 1) / BN + p.dq_splits - 1) / p.dq_splits;      // 64-key tiles per split
-    k_lo = (int)blockIdx.y * tps * BN;
-    Mk = max(0, min(p.M, k_lo + tps * BN) - k_lo);
-  }
+  if (p.dq_splits > 1 && !causal) key_split(p.M, (int)blockIdx.y, p.dq_splits, BN, k_lo, Mk);
   int diff = p.M - p.N - k_lo;
   const uint32_t ncm = causal ? 0u : 0xffffffffu;   // OR-ed into the causal bit mask: all ones when not causal
   Trace ts;
@@ -287,20 +282,14 @@ __global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const Bw
   }
   // geometry of iteration (pass_): row tile, this lane's row, number of 64-key tiles
   auto geometry = [&](int pass_, int& m0_, int& nt_) {
-    const int mt_ = causal ? (pass_ == 0 ? MT - 1 - pt : pt) : pt;      // heavy tile first
-    m0_ = mt_ * BM;
+    m0_ = pass_tile(MT, pt, pass_, causal, true) * BM;
     if constexpr (!KM && !KSPLIT && !BIAS && NW == 4) {      // (the form causal split launches take; the others compile to what they were)
-      if (p.dq_splits > 1 && causal) {            // this row tile's visible keys [0, vis), split over gridDim.y workgroups
-        const int vis = max(0, min(p.M, m0_ + BM + p.M - p.N));
-        const int tps = max(1, ((vis + BN - 1) / BN + p.dq_splits - 1) / p.dq_splits);
-        k_lo = min((int)blockIdx.y * tps * BN, p.M);
-        Mk = max(0, min(p.M, k_lo + tps * BN) - k_lo);
+      if (p.dq_splits > 1 && causal) {
+        key_split_causal(p.N, p.M, m0_, BM, (int)blockIdx.y, p.dq_splits, BN, k_lo, Mk);
         diff = p.M - p.N - k_lo;
       }
     }
-    int last_key = Mk - 1;
-    if (causal) last_key = min(last_key, m0_ + BM - 1 + diff);
-    nt_ = last_key < 0 ? 0 : last_key / BN + 1;
+    nt_ = key_tiles(Mk, m0_, BM, diff, causal, BN);
   };
   // requests of an iteration that need nothing but free staging buffers: first K / V stage (DMA form) and the raw row chunks
   u32x4 rq_[G::KS], rdo_[G::KS], ro_[G::KS];
@@ -1114,19 +1103,18 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
   FragAddr<T, D> fa;
   fa.init(lane);
 
-  // causal: the LOW key tiles are the heavy ones (they see every later query); pair (pt, KT-1-pt) per workgroup
-  const int KT = (p.M + BNK - 1) / BNK;
-  const int PT = causal ? (KT + 1) / 2 : KT;
+  // causal: a pair of key tiles per workgroup, the LOW one first: it sees every later query (tile_pairs, fcsa_dispatch.h)
+  const int KT = tile_count(p.M, BNK), PT = tile_pairs(KT, causal);
   int bh, pt, b, h, hk;
   if constexpr (SWEEP) {      // grid: (batch, K/V head) x key tiles; h = the group's first query head
     const int HK = p.H / p.kv_group;
-    block_to_work(blockIdx.x, p.B * HK, PT, bh, pt);
+    block_work(blockIdx.x, p.B * HK, PT, bh, pt);
     b = bh / HK; hk = bh % HK; h = hk * p.kv_group;
   } else {
-    block_to_work(blockIdx.x, p.B * p.H, PT, bh, pt);
+    block_work(blockIdx.x, p.B * p.H, PT, bh, pt);
     b = bh / p.H; h = bh % p.H; hk = h / p.kv_group;
   }
-  const int npass = (causal && (KT - 1 - pt) != pt) ? 2 : 1;
+  const int npass = pair_passes(KT, pt, causal);
   const int diff = p.M - p.N;
   const int64_t rk_bh = (int64_t)b * (p.H / p.kv_group) + hk;      // (batch, K/V head) row block of rk
   Trace ts;
@@ -1138,14 +1126,10 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
   // only and writes its partial dK^ / dV (f32) to slab blockIdx.y; the finalize kernel sums the slabs (and applies the l2norm backward).
   // For key grids that cannot fill the chip: few keys, many queries (the mirror image of the split-key forward / dQ).
   // Causal launches (round 6) split the query range of EACH key tile -- the tiles from its diagonal down -- so the window [t0, QT) is set
-  // per pass (geometry below): the pair (pt, KT-1-pt) keeps its constant work, 1 / dkv_splits of it per workgroup.
-  const int QT_all = (p.N + BMQ - 1) / BMQ;
+  // per pass (geometry below): the pair keeps its constant work, 1 / dkv_splits of it per workgroup.
+  const int QT_all = tile_count(p.N, BMQ);
   int QT = QT_all, t_lo = 0;
-  if (p.dkv_splits > 1 && !causal) {
-    const int tps = (QT + p.dkv_splits - 1) / p.dkv_splits;      // query tiles per split
-    t_lo = (int)blockIdx.y * tps;
-    QT = min(QT, t_lo + tps);
-  }
+  if (p.dkv_splits > 1 && !causal) query_split(QT_all, (int)blockIdx.y, p.dkv_splits, t_lo, QT);
   const char* qbase = p.q.p + (int64_t)b * p.q.sb + (int64_t)h * p.q.sh;
   const char* dobase = p.d_out.p + (int64_t)b * p.d_out.sb + (int64_t)h * p.d_out.sh;
   const float* invl_row = p.inv_l + ((int64_t)b * p.H + h) * p.N;
@@ -1226,15 +1210,10 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
   };
   // geometry of a pass: first key of the workgroup's key tile, first query tile it needs (causal keeps i >= j - diff)
   auto geometry = [&](int pass_, int& n0_, int& t0_) {
-    const int kt_ = causal ? (pass_ == 0 ? pt : KT - 1 - pt) : pt;      // heavy tile first
-    n0_ = kt_ * BNK;
-    t0_ = causal ? max(0, n0_ - diff) / BMQ : t_lo;
+    n0_ = pass_tile(KT, pt, pass_, causal, false) * BNK;
+    t0_ = causal ? diagonal_tile(n0_, diff, BMQ) : t_lo;
     if constexpr (!KM && NW == 4 && !LEAN && !QSPLIT && !BIAS) {      // (the form causal split launches take; the others compile to what they were)
-      if (p.dkv_splits > 1 && causal) {
-        const int tps = max(1, (QT_all - t0_ + p.dkv_splits - 1) / p.dkv_splits);
-        t0_ = min(QT_all, t0_ + (int)blockIdx.y * tps);
-        QT = min(QT_all, t0_ + tps);
-      }
+      if (p.dkv_splits > 1 && causal) query_split_causal(QT_all, t0_, (int)blockIdx.y, p.dkv_splits, t0_, QT);
     }
   };
   // requests of a pass that need nothing but a free staging buffer 0: first Q / dO tile (DMA form) with its per-query terms, this
@@ -1572,15 +1551,13 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
 template <typename T, int D, bool BIAS, int NW, bool TWO, bool KSPLIT = false>
 static hipError_t launch_dq_nw(const BwdParams& p, hipStream_t s) {
   constexpr int RWAVES = KSPLIT ? NW / 2 : NW, BM = 32 * RWAVES;
-  const int MT = (p.N + BM - 1) / BM;
-  const int PT = p.causal ? (MT + 1) / 2 : MT;
   // 128-key stages (one barrier per 128 keys) in the 8-wave form and, with LDS-DMA staging (no staging registers), also for the
   // one-wave-per-SIMD configurations (16-bit D >= 96: one workgroup per CU, the LDS is there)
   // 8-wave form: 256-key stages where they arrive by LDS-DMA (no staging registers), 128-key stages through registers (f32)
   constexpr int SUB = KSPLIT ? 2 : NW == 8 ? (Traits<T>::ES == 2 ? kDqSub8 : 2) : 1;
   size_t lds = DqLds<T, D, RWAVES, SUB, TWO, KSPLIT>::TOTAL;      // 2 buffers x (K stage + V stage), epilogue scratch behind or inside them
   if (KSPLIT && lds < (size_t)RWAVES * 64 * 16 * TileGeom<D, Traits<T>::ES>::DB * 4) lds = (size_t)RWAVES * 64 * 16 * TileGeom<D, Traits<T>::ES>::DB * 4;
-  const dim3 grid((unsigned)((int64_t)p.B * p.H * PT), (unsigned)(p.dq_splits > 1 ? p.dq_splits : 1));
+  const dim3 grid((unsigned)((int64_t)p.B * p.H * tile_pairs(tile_count(p.N, BM), p.causal)), (unsigned)(p.dq_splits > 1 ? p.dq_splits : 1));
   // (two instantiations, see launch_fwd_nw.  The two-wave form of 256-byte rows sits at its 256 registers: its non-causal
   //  instantiation came out with spill reloads inside the tile loops -- +5.6 % time -- so those launches keep the general kernel)
   constexpr bool GENERAL_ONLY = TWO && D * Traits<T>::ES >= 256;      // (its non-causal twin is not even instantiated)
@@ -1623,8 +1600,6 @@ static hipError_t launch_dkv_nw(const BwdParams& p, hipStream_t s) {
   // (64-row tiles at D = 128 measured +8 ... +15 % time: two blocks' fragments do not fit, the reloads sit in the tile loop)
   constexpr int LEAN_BMQ = D * Traits<T>::ES < 256 ? 64 : 32;
   constexpr int BMQ = LEAN ? LEAN_BMQ : (D * Traits<T>::ES >= 192) ? (DMA_FORM ? kDkvBmqWide : 32) : (NW == 8 ? kDkvBmq8 : 64);
-  const int KT = (p.M + BNK - 1) / BNK;
-  const int PT = p.causal ? (KT + 1) / 2 : KT;
   // ring form: the pipelined LDS-DMA tile (16 bit, no bias, not lean) where three buffers fit the workgroup's LDS share
   constexpr bool RING = kDkvRing && DMA_FORM && !LEAN && (BMQ * TileGeom<D, Traits<T>::ES>::ROWB) % 1024 == 0 &&
                         DkvLds<T, D, NW, BMQ, BIAS, LEAN, 3>::TOTAL <= ((NW == 8 || D * Traits<T>::ES > kDkv2WBytes) ? 160 : 80) * 1024;
@@ -1632,7 +1607,8 @@ static hipError_t launch_dkv_nw(const BwdParams& p, hipStream_t s) {
   static_assert(!QSPLIT || RING || BIAS, "query-split form: ring tile, or the generic tile with a bias");
   size_t lds = DkvLds<T, D, NW, BMQ, BIAS, LEAN, RING ? 3 : 2>::TOTAL + (BIAS ? (size_t)NW * BiasBlock<T>::BYTES : 0);
   if (QSPLIT && lds < (size_t)(NW / 2) * 64 * 16 * TileGeom<D, Traits<T>::ES>::DB * 8) lds = (size_t)(NW / 2) * 64 * 16 * TileGeom<D, Traits<T>::ES>::DB * 8;
-  const dim3 grid((unsigned)(p.B * (SWEEP ? p.H / p.kv_group : p.H) * PT), (unsigned)(p.dkv_splits > 1 ? p.dkv_splits : 1));
+  const dim3 grid((unsigned)(p.B * (SWEEP ? p.H / p.kv_group : p.H) * tile_pairs(tile_count(p.M, BNK), p.causal)),
+                  (unsigned)(p.dkv_splits > 1 ? p.dkv_splits : 1));
   // (two instantiations, see launch_fwd_nw)
   return p.causal ? launch_with_lds<bwd_dkv_kernel<T, D, NW, BMQ, BIAS, LEAN, false, RING, QSPLIT, SWEEP>>(grid, dim3(NW * 64), lds, s, p)
                   : launch_with_lds<bwd_dkv_kernel<T, D, NW, BMQ, BIAS, LEAN, true, RING, QSPLIT, SWEEP>>(grid, dim3(NW * 64), lds, s, p);

@@ -804,20 +804,6 @@ FCSA_DEV uint32_t le_mask(int thr) { return thr < 0 ? 0u : (thr >= 31 ? 0xffffff
 // bit mask of positions >= thr
 FCSA_DEV uint32_t ge_mask(int thr) { return thr <= 0 ? 0xffffffffu : (thr > 31 ? 0u : ~((1u << thr) - 1u)); }
 
-// block id -> (batch*head index, tile index).  Blocks are dispatched round-robin over the 8 XCDs
-// (block b -> XCD b % 8, guide §1); keep all tiles of one (batch, head) on one XCD so its K/V (or
-// Q/dO) panel stays in that XCD's private 4 MiB L2.  Pure speed choice: any placement is correct.
-FCSA_DEV void block_to_work(int id, int n_bh, int n_tiles, int& bh, int& tile) {
-  if ((n_bh & 7) == 0) {
-    const int xcd = id & 7, slot = id >> 3;
-    bh = (slot / n_tiles) * 8 + xcd;
-    tile = slot % n_tiles;
-  } else {
-    bh = id / n_tiles;
-    tile = id % n_tiles;
-  }
-}
-
 // ---------------------------------------------------------------------------------------------
 // Query rows of the forward kernels (fcsa_fwd.hip, fcsa_fwd3.hip)
 // ---------------------------------------------------------------------------------------------

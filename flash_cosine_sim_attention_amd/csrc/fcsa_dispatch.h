@@ -1,6 +1,7 @@
-// fcsa_dispatch.h -- which kernel form, and how many split workgroups, every problem gets.  The launchers (fcsa_fwd.hip, fcsa_bwd.hip)
-// and the C ABI (fcsa_capi.hip) ask these functions and carry out the answer; nothing else decides.  Host-only and pure: the CU count and
-// the debug knobs are arguments (callers pass cu_count(), forward_wide128_mode(-1), kv_group_mode(-1)), so a g++ program can include it.
+// fcsa_dispatch.h -- which kernel form, and how many split workgroups, every problem gets, and which tiles each workgroup owns.  The
+// launchers (fcsa_fwd.hip, fcsa_bwd.hip) and the C ABI (fcsa_capi.hip) ask these functions and carry out the answer; nothing else decides.
+// Pure, and free of HIP: the CU count and the debug knobs are arguments (callers pass cu_count(), forward_wide128_mode(-1),
+// kv_group_mode(-1)), so a g++ program can include it.  The kernels call the constexpr functions of the tile-ownership section.
 // Sweep builds (-DFCSA_VAR_SPLIT_ENV, tools/form_sweep.py, split_sweep.py, split_fuzz.py) let environment variables override each choice;
 // the product build reads none (sweep_env below is a constant -1 there).
 #pragma once
@@ -55,10 +56,70 @@ enum class FwdForm { Rows8, Lean8, KSplit8, Waves4, Fwd2, Fwd3 };     // 8-wave 
 enum class DqForm { Waves4, Waves4Two, Waves8, KSplit8 };            // 4 waves, 4 waves two-wave tile, 8 waves, key-split 8 waves
 enum class DkvForm { Waves4, Waves8, Lean8, QSplit8, Sweep };        // 4 waves, 8 waves, 8-wave lean, query-split 8 waves, group sweep
 
-// workgroups of `tile`-position tiles over `len` positions for `batch_heads` (batch x heads): causal launches pair the tiles
+// ---- the work of one workgroup of a row-tile (forward, dQ) or key-tile (dK/dV) launch ------------------------------------------------
+// The launchers' grids, the kernels' decoding of blockIdx and the cost model below all use these.  constexpr: the kernels call them too.
+// Under causal masking a tile's work grows with its distance from the start of the diagonal, and a workgroup runs start to finish on one
+// CU, so causal launches give each workgroup a PAIR of tiles (T-1-pair, pair): constant work per workgroup.  Non-causal: one tile each.
+constexpr int tile_count(int len, int tile) { return (len + tile - 1) / tile; }
+constexpr int tile_pairs(int tiles, int causal) { return causal ? (tiles + 1) / 2 : tiles; }
+constexpr int pair_passes(int tiles, int pair, int causal) { return (causal && (tiles - 1 - pair) != pair) ? 2 : 1; }
+// tile of pass `pass`, the heavy one first: row tiles (rows) the high tile T-1-pair, key tiles the low tile `pair`
+constexpr int pass_tile(int tiles, int pair, int pass, int causal, bool rows) {
+  return causal ? (rows ? (pass == 0 ? tiles - 1 - pair : pair) : (pass == 0 ? pair : tiles - 1 - pair)) : pair;
+}
+
+// block id -> (batch*head index, pair).  Blocks are dispatched round-robin over the 8 XCDs (block b -> XCD b % 8); keep all tiles of one
+// (batch, head) on one XCD so its K/V (or Q/dO) panel stays in that XCD's private 4 MiB L2.  Pure speed choice: any placement is correct.
+constexpr void block_work(int id, int n_bh, int pairs, int& bh, int& pair) {
+  if ((n_bh & 7) == 0) {
+    const int xcd = id & 7, slot = id >> 3;
+    bh = (slot / pairs) * 8 + xcd;
+    pair = slot % pairs;
+  } else {
+    bh = id / pairs;
+    pair = id % pairs;
+  }
+}
+
+// Split launches (gridDim.y = splits > 1): workgroup `split` sees only its window of the keys (forward, dQ: keys [lo, lo + len)) or of the
+// query tiles (dK/dV: tiles [lo, hi), empty when hi <= lo).
+// non-causal forward / dQ: the whole key range, in `bn`-key tiles
+constexpr void key_split(int M, int split, int splits, int bn, int& lo, int& len) {
+  const int tps = ((M + bn - 1) / bn + splits - 1) / splits;      // key tiles per split
+  lo = split * tps * bn;
+  len = std::max(std::min(lo + tps * bn, M) - lo, 0);
+}
+// causal forward / dQ: the keys [0, vis) of the row tile [m0, m0 + bm), up to its diagonal
+constexpr void key_split_causal(int N, int M, int m0, int bm, int split, int splits, int bn, int& lo, int& len) {
+  const int vis = std::max(std::min(m0 + bm + M - N, M), 0);
+  const int tps = std::max(((vis + bn - 1) / bn + splits - 1) / splits, 1);
+  lo = std::min(M, split * tps * bn);
+  len = std::max(std::min(lo + tps * bn, M) - lo, 0);
+}
+// `bn`-key tiles the row tile [m0, m0 + bm) runs over a window of `len` keys; diff = M - N - (the window's first key)
+constexpr int key_tiles(int len, int m0, int bm, int diff, int causal, int bn) {
+  int last_key = len - 1;
+  if (causal) last_key = std::min(m0 + bm - 1 + diff, last_key);
+  return last_key < 0 ? 0 : last_key / bn + 1;
+}
+// dK/dV, non-causal: all `tiles` query tiles
+constexpr void query_split(int tiles, int split, int splits, int& lo, int& hi) {
+  const int tps = (tiles + splits - 1) / splits;      // query tiles per split
+  lo = split * tps;
+  hi = std::min(lo + tps, tiles);
+}
+// dK/dV, causal: the first query tile of size `bmq` the key tile from key n0 sees (diff = M - N) ...
+constexpr int diagonal_tile(int n0, int diff, int bmq) { return std::max(n0 - diff, 0) / bmq; }
+// ... and the query tiles [first, tiles) from there down
+constexpr void query_split_causal(int tiles, int first, int split, int splits, int& lo, int& hi) {
+  const int tps = std::max((tiles - first + splits - 1) / splits, 1);
+  lo = std::min(first + split * tps, tiles);
+  hi = std::min(lo + tps, tiles);
+}
+
+// workgroups of `tile`-position tiles over `len` positions for `batch_heads` (batch x heads)
 inline int64_t tile_workgroups(int64_t batch_heads, int len, int tile, bool causal) {
-  const int t = (len + tile - 1) / tile;
-  return batch_heads * (causal ? (t + 1) / 2 : t);
+  return batch_heads * tile_pairs(tile_count(len, tile), causal);
 }
 
 // Waves per workgroup of the row-tile (key-tile) kernels: 8 (one 256-position workgroup per CU) when that still gives every CU a

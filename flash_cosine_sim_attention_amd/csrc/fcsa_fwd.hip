@@ -462,25 +462,18 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ?
   FragAddr<T, D> fa;
   fa.init(lane);
 
-  // Work of a row tile grows with its index under causal masking (2 .. 2*MT key tiles), and a workgroup runs
-  // start to finish on one CU, so the makespan would be set by the heaviest tile.  Each workgroup therefore
-  // takes a PAIR of row tiles (MT-1-pt, pt): constant work per workgroup.  Non-causal: one tile each.
-  const int MT = (p.N + BM - 1) / BM;
-  const int PT = causal ? (MT + 1) / 2 : MT;
+  // a pair of row tiles per workgroup under causal masking (tile_pairs, fcsa_dispatch.h)
+  const int MT = tile_count(p.N, BM), PT = tile_pairs(MT, causal);
   int bh, pt;
-  block_to_work(blockIdx.x, p.B * p.H, PT, bh, pt);
+  block_work(blockIdx.x, p.B * p.H, PT, bh, pt);
   const int b = bh / p.H, h = bh % p.H;
-  const int npass = (causal && (MT - 1 - pt) != pt) ? 2 : 1;
+  const int npass = pair_passes(MT, pt, causal);
   // split-key launches (gridDim.y = p.splits > 1, never bias / dynamic shift): this workgroup sees the keys [k_lo, k_lo + Mk) only and
   // writes un-normalised partials; everything below works on that sub-problem.  Causal launches (round 6) split the key range of EACH row
-  // tile -- the keys up to its diagonal -- so the ranges are set per pass (below): the pair (MT-1-pt, pt) keeps its constant work, 1 / splits
-  // of it per workgroup
+  // tile -- the keys up to its diagonal -- so the ranges are set per pass (below): the pair keeps its constant work, 1 / splits of it per
+  // workgroup
   int k_lo = 0, Mk = p.M;
-  if (p.splits > 1 && !causal) {
-    const int tps = ((p.M + BN - 1) / BN + p.splits - 1) / p.splits;      // 64-key tiles per split
-    k_lo = (int)blockIdx.y * tps * BN;
-    Mk = max(0, min(p.M, k_lo + tps * BN) - k_lo);
-  }
+  if (p.splits > 1 && !causal) key_split(p.M, (int)blockIdx.y, p.splits, BN, k_lo, Mk);
   int diff = p.M - p.N - k_lo;                    // cu:1097 seq_len_diff (in the sub-problem's key numbering)
   const uint32_t ncm = causal ? 0u : 0xffffffffu;   // OR-ed into the causal bit mask: all ones when not causal
   Trace ts;
@@ -489,22 +482,14 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ?
   tr.start();
   for (int pass = 0; pass < npass; ++pass) {
   tr.mark(pass, 0);
-  const int mt = causal ? (pass == 0 ? MT - 1 - pt : pt) : pt;      // heavy tile first
-  const int m0 = mt * BM;
+  const int m0 = pass_tile(MT, pt, pass, causal, true) * BM;
   const int mw = m0 + rwave * 32;                 // first query row of this wave
   const int i = mw + (lane & 31);                 // this lane's query row
-  if (p.splits > 1 && causal) {                   // this row tile's visible keys [0, vis), split over gridDim.y workgroups
-    const int vis = max(0, min(p.M, m0 + BM + p.M - p.N));
-    const int tps = max(1, ((vis + BN - 1) / BN + p.splits - 1) / p.splits);
-    k_lo = min((int)blockIdx.y * tps * BN, p.M);
-    Mk = max(0, min(p.M, k_lo + tps * BN) - k_lo);
+  if (p.splits > 1 && causal) {
+    key_split_causal(p.N, p.M, m0, BM, (int)blockIdx.y, p.splits, BN, k_lo, Mk);
     diff = p.M - p.N - k_lo;
   }
-
-  // key tiles this workgroup needs
-  int last_key = Mk - 1;
-  if (causal) last_key = min(last_key, m0 + BM - 1 + diff);
-  const int nt = last_key < 0 ? 0 : last_key / BN + 1;
+  const int nt = key_tiles(Mk, m0, BM, diff, causal, BN);      // key tiles this workgroup needs
 
   const int hk = h / p.kv_group;                  // K/V head of this query head (grouped-query attention)
   const char* kbase = p.k.p + (int64_t)b * p.k.sb + (int64_t)hk * p.k.sh + (int64_t)k_lo * p.k.sn;
@@ -991,12 +976,11 @@ __global__ void __launch_bounds__(NW * 64, 1) fwd2_kernel(const FwdParams p) {
   FragAddr<T, D> fa;
   fa.init(lane);
 
-  const int MT = (p.N + BM - 1) / BM;
-  const int PT = p.causal ? (MT + 1) / 2 : MT;                 // causal: pairs of row tiles (MT-1-pt, pt), constant work
+  const int MT = tile_count(p.N, BM), PT = tile_pairs(MT, p.causal);
   int bh, pt;
-  block_to_work(blockIdx.x, p.B * p.H, PT, bh, pt);
+  block_work(blockIdx.x, p.B * p.H, PT, bh, pt);
   const int b = bh / p.H, h = bh % p.H;
-  const int npass = (p.causal && (MT - 1 - pt) != pt) ? 2 : 1;
+  const int npass = pair_passes(MT, pt, p.causal);
   const int diff = p.M - p.N;
   const uint32_t ncm = p.causal ? 0u : 0xffffffffu;
   const int hk = h / p.kv_group;                               // K/V head of this query head (grouped-query attention)
@@ -1012,13 +996,10 @@ __global__ void __launch_bounds__(NW * 64, 1) fwd2_kernel(const FwdParams p) {
   tr.start();
 
   for (int pass = 0; pass < npass; ++pass) {
-    const int mt = p.causal ? (pass == 0 ? MT - 1 - pt : pt) : pt;      // heavy tile first
-    const int m0 = mt * BM;
+    const int m0 = pass_tile(MT, pt, pass, p.causal, true) * BM;
     const int mw = m0 + wave * RW;                  // first query row of this wave
     const int i0 = mw + (lane & 31);                // this lane's row in block 0; block 1 is i0 + 32
-    int last_key = p.M - 1;
-    if (p.causal) last_key = min(last_key, m0 + BM - 1 + diff);
-    const int nt = last_key < 0 ? 0 : last_key / BN + 1;
+    const int nt = key_tiles(p.M, m0, BM, diff, p.causal, BN);
 
     u32x4 qf[2][G::KS];
 #pragma unroll
@@ -1203,13 +1184,11 @@ template <typename T, int D, bool BIAS, int NW, bool DYN, bool LEAN = false, boo
 static hipError_t launch_fwd_nw(const FwdParams& p, hipStream_t s) {
   constexpr int RWAVES = KSPLIT ? NW / 2 : NW, BM = 32 * RWAVES;
   static_assert(!KSPLIT || (64 * TileGeom<D, Traits<T>::ES>::ROWB) % 1024 == 0, "key-split form: whole 1 KiB LDS-DMA pieces per tile");
-  const int MT = (p.N + BM - 1) / BM;
-  const int PT = p.causal ? (MT + 1) / 2 : MT;
   size_t lds = 4 * 64 * (KSPLIT ? 2 : fwd_stage_tiles<T, D, DYN>()) * TileGeom<D, Traits<T>::ES>::ROWB;      // 2 buffers x (K + V tiles of a stage)
   if (lds < (size_t)RWAVES * RowEpilogue<T, D>::BYTES_NOX) lds = (size_t)RWAVES * RowEpilogue<T, D>::BYTES_NOX;   // epilogue scratch reuses the same bytes
   if (KSPLIT && lds < (size_t)RWAVES * 64 * 16 * (TileGeom<D, Traits<T>::ES>::DB * 4 + 1)) lds = (size_t)RWAVES * 64 * 16 * (TileGeom<D, Traits<T>::ES>::DB * 4 + 1);
   // two instantiations: causal launches (select per logit on the diagonal tiles) and the others (key masks as a rank-1 MFMA)
-  const dim3 grid((unsigned)(p.B * p.H * PT), (unsigned)(p.splits > 1 ? p.splits : 1));
+  const dim3 grid((unsigned)(p.B * p.H * tile_pairs(tile_count(p.N, BM), p.causal)), (unsigned)(p.splits > 1 ? p.splits : 1));
   const hipError_t e = p.causal ? launch_with_lds<fwd_kernel<T, D, NW, BIAS, DYN, LEAN, false, KSPLIT>>(grid, dim3(NW * 64), lds, s, p)
                                 : launch_with_lds<fwd_kernel<T, D, NW, BIAS, DYN, LEAN, true, KSPLIT>>(grid, dim3(NW * 64), lds, s, p);
   if (e != hipSuccess) return e;
@@ -1223,9 +1202,7 @@ static hipError_t launch_fwd_nw(const FwdParams& p, hipStream_t s) {
 template <typename T, int D>
 static hipError_t launch_fwd2(const FwdParams& p, hipStream_t s) {
   constexpr int NW = 4, BM = 64 * NW;
-  const int MT = (p.N + BM - 1) / BM;
-  const int PT = p.causal ? (MT + 1) / 2 : MT;
-  return launch_with_lds<fwd2_kernel<T, D, NW>>(dim3((unsigned)(p.B * p.H * PT)), dim3(NW * 64), 4 * 64 * TileGeom<D, 2>::ROWB, s, p);
+  return launch_with_lds<fwd2_kernel<T, D, NW>>(dim3((unsigned)(p.B * p.H * tile_pairs(tile_count(p.N, BM), p.causal))), dim3(NW * 64), 4 * 64 * TileGeom<D, 2>::ROWB, s, p);
 }
 
 // the instantiation of form f (choose_forward, fcsa_dispatch.h)

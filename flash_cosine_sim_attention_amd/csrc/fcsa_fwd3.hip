@@ -349,12 +349,11 @@ __global__ void __launch_bounds__(256, 1) fwd3_kernel(const FwdParams p) {
   fa.init(lane);
   const uint32_t lds0 = DS::lds_addr(smem);
 
-  const int MT = (p.N + BM - 1) / BM;
-  const int PT = p.causal ? (MT + 1) / 2 : MT;                 // causal: pairs of row tiles (MT-1-pt, pt), constant work
+  const int MT = tile_count(p.N, BM), PT = tile_pairs(MT, p.causal);
   int bh, pt;
-  block_to_work(blockIdx.x, p.B * p.H, PT, bh, pt);
+  block_work(blockIdx.x, p.B * p.H, PT, bh, pt);
   const int b = bh / p.H, h = bh % p.H;
-  const int npass = (p.causal && (MT - 1 - pt) != pt) ? 2 : 1;
+  const int npass = pair_passes(MT, pt, p.causal);
   const int diff = p.M - p.N;
   const int hk = h / p.kv_group;                               // K/V head of this query head (grouped-query attention)
   const char* kbase = p.k.p + (int64_t)b * p.k.sb + (int64_t)hk * p.k.sh;
@@ -383,13 +382,10 @@ __global__ void __launch_bounds__(256, 1) fwd3_kernel(const FwdParams p) {
     st.one2 = o2;
   }
   for (int pass = 0; pass < npass; ++pass) {
-    const int mt = p.causal ? (pass == 0 ? MT - 1 - pt : pt) : pt;      // heavy tile first
-    const int m0 = mt * BM;
+    const int m0 = pass_tile(MT, pt, pass, p.causal, true) * BM;
     const int mw = m0 + wave * RW;                  // first query row of this wave
     const int i0 = mw + (lane & 31);                // this lane's row in block 0; block 1 is i0 + 32
-    int last_key = p.M - 1;
-    if (p.causal) last_key = min(last_key, m0 + BM - 1 + diff);
-    const int nt = last_key < 0 ? 0 : last_key / BN + 1;
+    const int nt = key_tiles(p.M, m0, BM, diff, p.causal, BN);
 
     tr.mark(pass, 0);
     // ---- prologue: the query rows, then the ring's first tiles by LDS-DMA (K(0..R-2); V(-1) = zeros in slot R-1; V(0..R-3)) ----
@@ -550,11 +546,9 @@ constexpr bool kFwd3RoundedSums = false; // row sums of the un-rounded P~ (plain
 
 template <typename T, int R, bool RSUM>
 static hipError_t launch_fwd3_t(const FwdParams& p, hipStream_t s) {
-  const int MT = (p.N + 255) / 256;
-  const int PT = p.causal ? (MT + 1) / 2 : MT;
   size_t lds = (size_t)2 * R * 16384;
   if (lds < (size_t)4 * RowEpilogue<T, 128>::BYTES_NOX) lds = (size_t)4 * RowEpilogue<T, 128>::BYTES_NOX;
-  return launch_with_lds<fwd3_kernel<T, R, RSUM>>(dim3((unsigned)(p.B * p.H * PT)), dim3(256), lds, s, p);
+  return launch_with_lds<fwd3_kernel<T, R, RSUM>>(dim3((unsigned)(p.B * p.H * tile_pairs(tile_count(p.N, 256), p.causal))), dim3(256), lds, s, p);
 }
 
 // Escape hatch (same-process A/B, triage): 0 = never take this form.  The environment is read ONCE, when the library is loaded

@@ -115,6 +115,18 @@ def test_dispatch_header_is_host_only(tmp_path):
         assert subprocess.run([str(tmp_path / "t")], timeout=60).returncode == 0
 
 
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_tile_ownership(tmp_path):
+    """the tile-ownership functions of csrc/fcsa_dispatch.h (tests/native/tile_work_check.cpp): the block mapping is a bijection onto
+    (batch*head, pair), the passes visit every tile once, and each tile's split windows are disjoint and cover what the tile sees"""
+    exe = str(tmp_path / "tile_work_check")
+    b = subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "flash_cosine_sim_attention_amd", "csrc"),
+                        os.path.join(ROOT, "tests", "native", "tile_work_check.cpp"), "-o", exe], capture_output=True, text=True, timeout=300)
+    assert b.returncode == 0, b.stderr[-2000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.startswith("ok"), r.stderr[-2000:]
+
+
 @pytest.mark.skipif(shutil.which("g++") is None or not os.path.isdir("/opt/rocm/include"), reason="needs g++ and the HIP headers")
 def test_launches_match_golden(tmp_path):
     assert os.path.exists(LIB), "libfcsa_hip.so is not built"

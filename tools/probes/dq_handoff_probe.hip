@@ -11,7 +11,7 @@
 // and needs its predecessor to be two query tiles ahead of it in program order.
 //
 // What this probe measures (one workgroup per CU, 256 workgroups of 512 threads, chains of `CH` workgroups that share an XCD the way the
-// kernels' block_to_work places a head's tiles: block % 8):
+// kernels' block_work places a head's tiles: block % 8):
 //   mode 0  compute only: `mfma` MFMAs per wave and step (v_mfma_f32_32x32x16_bf16, two accumulators per wave), `steps` steps
 //   mode 1  + every workgroup WRITES its 32 KiB partial per step (16-byte write-through stores, drain, flag) -- nobody waits
 //   mode 2  + the chain: poll the predecessor's flag for step s - LAG (one lane, relaxed agent-scope loads, s_sleep), read its 32 KiB with
