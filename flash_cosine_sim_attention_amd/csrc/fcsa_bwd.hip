@@ -184,26 +184,48 @@ FCSA_DEV void dq_tile_pipe(const char* kt, const char* vt, const char* knext, co
   pp_.tile = next_tile;
 }
 
-// LDS plan of the dQ kernel (EpiLds): the next iteration is requested ahead of the epilogue when the stages arrive by LDS-DMA and
-// the scratch fits behind them.
 // K / V stages of the dQ kernel arrive by LDS-DMA for the 16-bit types and for 512-byte rows (f32, D = 128: the staging registers of
 // the register path -- 64 + 16 per lane -- are what pushed that instantiation into scratch)
 template <typename T, int D> constexpr bool dq_dma(int sub) {
   return (Traits<T>::ES == 2 || D * Traits<T>::ES >= 512) && (64 * sub * TileGeom<D, Traits<T>::ES>::ROWB) % 1024 == 0;
 }
-template <typename T, int D, int NW, int SUB, bool TWO, bool WHOLE_CU = false> struct DqLds      // (NW: waves with an epilogue of their own)
-    : EpiLds<T, D, NW, 4 * 64 * SUB * TileGeom<D, Traits<T>::ES>::ROWB, dq_dma<T, D>(SUB),
-             ((NW == 8 || !TWO || WHOLE_CU) ? 160 : 80) * 1024> {};
+// LDS plan of the dQ kernel (EpiLds): two buffers of [K stage | V stage] (SUB 64-key tiles each); the next iteration is requested
+// ahead of the epilogue when the stages arrive by LDS-DMA and the scratch fits behind them.  KSPLIT: the dQ hand-over (SplitHandover)
+// overlays the buffers after the key loop.
+template <typename T, int D, int NW, int SUB, bool TWO, bool KSPLIT> struct DqLds
+    : EpiLds<T, D, KSPLIT ? NW / 2 : NW, 4 * 64 * SUB * TileGeom<D, Traits<T>::ES>::ROWB, dq_dma<T, D>(SUB), ((NW == 8 || !TWO) ? 160 : 80) * 1024> {
+  typedef TileGeom<D, Traits<T>::ES> G;
+  typedef SplitHandover<G::DB * 4> HO;
+  static constexpr int RWAVES = KSPLIT ? NW / 2 : NW;      // waves that own distinct row slices (and an epilogue of their own)
+  static constexpr int TILE_B = 64 * G::ROWB;              // one 64-key tile of K or V
+  static constexpr int HALF_B = SUB * TILE_B;              // K (or V) part of a stage
+  static constexpr int TOTAL = lds_max(DqLds::EPI_TOTAL, KSPLIT ? HO::bytes(RWAVES) : 0);
+  static_assert(TOTAL <= kLdsBytes, "bwd_dq_kernel LDS");
+};
 
-// LDS plan of the dKV kernel: two staging buffers of (Q tile | dO tile | lc | -delta), epilogue scratch behind them when it fits.
+// staging buffer of the dKV kernel: Q tile | dO tile | lc[BMQ] | -delta[BMQ]
+template <typename T, int D> constexpr int dkv_buf_bytes(int bmq) { return 2 * bmq * TileGeom<D, Traits<T>::ES>::ROWB + 2 * bmq * 4; }
+
+// LDS plan of the dKV kernel: NBUF staging buffers, epilogue scratch behind them when it fits.
+// NBUF: 2, or 3 in the ring form (dkv_ring: the tile after the current one is always complete in the LDS).
 // LEAN (16-bit rows of 129 .. 256 bytes, two waves per SIMD): the V rows of the workgroup's own keys live in the LDS behind the staging
 // buffers instead of in registers (VOWN bytes); the epilogue scratch then shares those bytes (never "SEP").
-// NBUF: staging buffers -- 2, or 3 in the ring form (dkv_ring: the tile after the current one is always complete in the LDS).
-template <typename T, int D, int NW, int BMQ, bool BIAS, bool LEAN = false, int NBUF = 2> struct DkvLds
-    : EpiLds<T, D, NW, NBUF * (2 * BMQ * TileGeom<D, Traits<T>::ES>::ROWB + 2 * BMQ * 4) + (LEAN ? 32 * NW * TileGeom<D, Traits<T>::ES>::ROWB : 0),
-             NBUF == 2 && !LEAN && Traits<T>::ES == 2 && !BIAS && (BMQ * TileGeom<D, Traits<T>::ES>::ROWB) % 1024 == 0,
+// BIAS: each wave's private scratch of the bias transposition (BiasBlock) lies behind everything else.
+// QSPLIT: the dK / dV hand-over (SplitHandover) overlays the rest after the query loop.
+template <typename T, int D, int NW, int BMQ, bool BIAS, bool LEAN, bool RING, bool QSPLIT> struct DkvLds
+    : EpiLds<T, D, NW, (RING ? 3 : 2) * dkv_buf_bytes<T, D>(BMQ) + (LEAN ? 32 * NW * TileGeom<D, Traits<T>::ES>::ROWB : 0),
+             !RING && !LEAN && Traits<T>::ES == 2 && !BIAS && (BMQ * TileGeom<D, Traits<T>::ES>::ROWB) % 1024 == 0,
              ((NW == 8 || (D * Traits<T>::ES > kDkv2WBytes && !LEAN)) ? 160 : 80) * 1024> {
-  static constexpr int VOWN = NBUF * (2 * BMQ * TileGeom<D, Traits<T>::ES>::ROWB + 2 * BMQ * 4);      // byte offset of the own-V tile (LEAN)
+  typedef TileGeom<D, Traits<T>::ES> G;
+  typedef SplitHandover<G::DB * 8> HO;
+  static constexpr int RWAVES = QSPLIT ? NW / 2 : NW;      // waves that own distinct key slices
+  static constexpr int TILE_B = BMQ * G::ROWB;
+  static constexpr int BUF_B = dkv_buf_bytes<T, D>(BMQ);
+  static constexpr int NBUF = RING ? 3 : 2;
+  static constexpr int VOWN = NBUF * BUF_B;                // byte offset of the own-V tile (LEAN)
+  static constexpr int BIAS_AT = DkvLds::EPI_TOTAL;        // bias scratch of wave w: BIAS_AT + w * BiasBlock<T>::BYTES
+  static constexpr int TOTAL = lds_max(BIAS_AT + (BIAS ? NW * BiasBlock<T>::BYTES : 0), QSPLIT ? HO::bytes(RWAVES) : 0);
+  static_assert(TOTAL <= kLdsBytes, "bwd_dkv_kernel LDS");
 };
 
 // SUB = 64-key tiles per LDS stage: 1, or 2 / 4 in the 8-wave form (one workgroup per CU has the LDS for 128- / 256-key stages).
@@ -221,11 +243,10 @@ __global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const Bw
   const int causal = KM ? 0 : KSPLIT ? 1 : p.causal;
   typedef TileGeom<D, Traits<T>::ES> G;
   typedef Traits<T> TR;
-  constexpr int RWAVES = KSPLIT ? NW / 2 : NW;      // waves that own distinct row slices
+  typedef DqLds<T, D, NW, SUB, TWO, KSPLIT> LDS;
+  constexpr int RWAVES = LDS::RWAVES, TILE_B = LDS::TILE_B, HALF_B = LDS::HALF_B;
   constexpr int BN = 64, BM = 32 * RWAVES, NT = NW * 64, BNS = BN * SUB;
-  constexpr int TILE_B = BN * G::ROWB;          // one 64-key tile of K or V
-  constexpr int HALF_B = SUB * TILE_B;          // K (or V) part of a stage
-  extern __shared__ __attribute__((aligned(16))) char smem[];   // [2][K stage | V stage]
+  extern __shared__ __attribute__((aligned(16))) char smem[];   // DqLds
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -261,7 +282,6 @@ __global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const Bw
   // be finished before the next one starts loading: the first K / V stage and this lane's Q^ / dO / O row chunks of the NEXT
   // iteration are requested before the epilogue of the current one and land while it runs (the pass marks of the WG trace showed
   // 11 % of this kernel in prologues and 7 % in epilogues: exposed round trips, every workgroup of the chip in step).
-  typedef DqLds<T, D, RWAVES, SUB, TWO, KSPLIT> LDS;
   constexpr bool SEP = LDS::SEP;
   Stager<T, D, BNS, NT> sk, sv;
   typedef DmaStager<T, D, DMA ? BNS : 1024, NW> DS;
@@ -595,28 +615,8 @@ __global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const Bw
   if constexpr (KSPLIT) {
     // the odd-tile half hands its dQ partials to the even-tile half of the same rows (the staging buffers are free: every stage ended
     // with a barrier); done before anything of the epilogue or the next pass touches the LDS
-    f32x4* ms = reinterpret_cast<f32x4*>(smem) + rwave * (G::DB * 4 * 64) + lane;
-    if (half == 1) {
-#pragma unroll
-      for (int db = 0; db < G::DB; ++db)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const f32x4 v = {dq[db][4 * g], dq[db][4 * g + 1], dq[db][4 * g + 2], dq[db][4 * g + 3]};
-          ms[(db * 4 + g) * 64] = v;
-        }
-    }
-    __syncthreads();
-    if (half == 0) {
-#pragma unroll
-      for (int db = 0; db < G::DB; ++db)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const f32x4 v = ms[(db * 4 + g) * 64];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) dq[db][4 * g + e] += v[e];
-        }
-    }
-    __syncthreads();
+    LDS::HO::run(smem, rwave, half, lane, [&](int n) { return acc_x4(dq, n); },
+                 [&](int n, const f32x4& v) { add_x4(dq, n, v); });
   }
 
   // Epilogue through the LDS (RowEpilogue): every stage ended with a barrier, so no wave still reads the staging buffers.
@@ -668,6 +668,15 @@ __global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const Bw
 // and writes the tile once, transposed through the LDS into whole rows: no atomics, no read-modify-write, slices x row tiles x
 // key tiles workgroups, and the dQ kernel runs its plain form.  Needs delta (published by the dQ kernel, launched first).
 // =============================================================================================
+// LDS plan of bwd_dbias_kernel: K tile | V tile | each of the four waves' [32 rows][OPITCH] output scratch
+template <typename T, int D> struct DbiasLds {
+  static constexpr int TILE_B = 64 * TileGeom<D, Traits<T>::ES>::ROWB;
+  static constexpr int OPITCH = 64 * 4 + 16;                            // output scratch row: 64 f32 + pad
+  static constexpr int OUT_B = 32 * OPITCH;                             // output scratch of a wave, from byte 2 * TILE_B
+  static constexpr int TOTAL = 2 * TILE_B + 4 * OUT_B;
+  static_assert(TOTAL <= kLdsBytes, "bwd_dbias_kernel LDS");
+};
+
 // Registers: two row-fragment sets (current + requested-ahead), two staging sets, 64 bias / sum values -- two waves per SIMD (256
 // registers) only fit rows of <= 128 bytes; wider rows run one wave per SIMD, and 512-byte rows (f32, D = 128) load their row
 // fragments at the top of the iteration instead of one iteration ahead.  (Round 2 asked for 2 waves / SIMD up to 256-byte rows and
@@ -677,9 +686,9 @@ __global__ void __launch_bounds__(256, (D * Traits<T>::ES <= 128 ? 2 : 1)) bwd_d
   typedef TileGeom<D, Traits<T>::ES> G;
   typedef Traits<T> TR;
   constexpr int BN = 64, BM = 128, NT = 256;
-  constexpr int TILE_B = BN * G::ROWB;
-  constexpr int OPITCH = 64 * 4 + 16;                                    // output scratch row: 64 f32 + pad
-  extern __shared__ __attribute__((aligned(16))) char smem[];           // K tile | V tile | 4 x [32][OPITCH] output scratch
+  typedef DbiasLds<T, D> LDS;
+  constexpr int TILE_B = LDS::TILE_B, OPITCH = LDS::OPITCH;
+  extern __shared__ __attribute__((aligned(16))) char smem[];           // DbiasLds
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -801,7 +810,7 @@ __global__ void __launch_bounds__(256, (D * Traits<T>::ES <= 128 ? 2 : 1)) bwd_d
 
   // [32 rows x 64 keys] of this wave -> scratch (C layout: lane (row, hi) holds keys 32 * jb + 8 * rq + 4 * hi + 0..3) -> rows
   __syncthreads();                                                        // (scratch is separate from the tiles, but keep the waves' LDS traffic apart)
-  char* scr = smem + 2 * TILE_B + wave * 32 * OPITCH;
+  char* scr = smem + 2 * TILE_B + wave * LDS::OUT_B;
   {
     const int x = lane & 31;
 #pragma unroll
@@ -838,8 +847,7 @@ template <typename T, int D>
 static hipError_t launch_dbias_t(const BwdParams& p, hipStream_t s) {
   const int MT = (p.N + 127) / 128, KT = (p.M + 63) / 64;
   const int64_t owners = p.bias_batch ? p.B : p.H;
-  const size_t lds = 2 * 64 * TileGeom<D, Traits<T>::ES>::ROWB + 4 * 32 * (64 * 4 + 16);
-  return launch_with_lds<bwd_dbias_kernel<T, D>>(dim3((unsigned)(owners * MT), (unsigned)KT), dim3(256), lds, s, p);
+  return launch_with_lds<bwd_dbias_kernel<T, D>>(dim3((unsigned)(owners * MT), (unsigned)KT), dim3(256), DbiasLds<T, D>::TOTAL, s, p);
 }
 
 // =============================================================================================
@@ -1082,17 +1090,15 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
   const int causal = KM ? 0 : p.causal;      // (same type and value as p.causal: the causal instantiations compile to what they were)
   typedef TileGeom<D, Traits<T>::ES> G;
   typedef Traits<T> TR;
-  constexpr int RWAVES = QSPLIT ? NW / 2 : NW;      // waves that own distinct key slices
+  typedef DkvLds<T, D, NW, BMQ, BIAS, LEAN, RING, QSPLIT> LDS;
+  constexpr int RWAVES = LDS::RWAVES, TILE_B = LDS::TILE_B, BUF_B = LDS::BUF_B;
   constexpr int BMS = QSPLIT ? BMQ / 2 : BMQ;       // rows of a staged tile one wave works on
   constexpr int BNK = 32 * RWAVES, NT = NW * 64;
-  constexpr int TILE_B = BMQ * G::ROWB;
   static_assert(!LEAN || (Traits<T>::ES == 2 && !BIAS), "lean form: 16-bit types without bias");
   constexpr bool PIPE = Traits<T>::ES == 2 && !BIAS && !LEAN;      // software-pipelined tile (dkv_tile_pipe)
-  constexpr int BUF_B = 2 * TILE_B + 2 * BMQ * 4;                // Q tile | dO tile | lc[BMQ] | -delta[BMQ]
-  constexpr int NBUF = RING ? 3 : 2;
   static_assert(BMQ % 32 == 0 && BMQ <= NT, "query tile");
   static_assert(!RING || PIPE, "ring form: pipelined LDS-DMA tile only");
-  extern __shared__ __attribute__((aligned(16))) char smem[];   // [NBUF][BUF_B]
+  extern __shared__ __attribute__((aligned(16))) char smem[];   // DkvLds
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -1144,7 +1150,6 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
   };
   // Q / dO tiles: LDS-DMA in the pipelined form (no staging registers, no ds_write passes), else through registers
   constexpr bool DMA = (PIPE || LEAN) && (BMQ * G::ROWB) % 1024 == 0;
-  typedef DkvLds<T, D, NW, BMQ, BIAS, LEAN, NBUF> LDS;
   constexpr bool SEP = LDS::SEP;      // see bwd_dq_kernel: the next pass is requested from inside the epilogue of the current one
   static_assert(!RING || (DMA && !SEP), "ring form");
   Stager<T, D, BMQ, NT> sq, sdo;
@@ -1298,7 +1303,7 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
   const char* bias_col = nullptr;                 // &bias[slice][0][0] (wave-uniform: the element-load fallback adds row and column itself)
   const char* bias_blk = nullptr;                 // &bias[slice][0][first key of this wave]
   BiasBlock<T> bb;
-  char* bscr = smem + LDS::TOTAL + wave * BiasBlock<T>::BYTES;      // private scratch of the bias transposition (BIAS launches only)
+  char* bscr = smem + LDS::BIAS_AT + wave * BiasBlock<T>::BYTES;      // private scratch of the bias transposition (BIAS launches only)
   bool bvec = false;                              // whole key tile inside M, rows 16-byte aligned: block loads (BiasBlock)
   if constexpr (BIAS) {
     const char* slice = p.bias + (int64_t)(p.bias_batch ? b : h) * p.N * (int64_t)p.M * (int64_t)sizeof(typename TR::elem);
@@ -1479,30 +1484,8 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
   if constexpr (QSPLIT) {
     // the second-half waves hand their dK / dV partials to the first-half waves of the same keys (the staging buffers are free: every
     // tile ended with a barrier); done before anything of the epilogue or the next pass touches the LDS
-    f32x4* ms = reinterpret_cast<f32x4*>(smem) + rwave * (G::DB * 8 * 64) + lane;
-    if (half == 1) {
-#pragma unroll
-      for (int db = 0; db < G::DB; ++db)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const f32x4 a = {dk[db][4 * g], dk[db][4 * g + 1], dk[db][4 * g + 2], dk[db][4 * g + 3]};
-          const f32x4 c = {dv[db][4 * g], dv[db][4 * g + 1], dv[db][4 * g + 2], dv[db][4 * g + 3]};
-          ms[(db * 8 + g) * 64] = a;
-          ms[(db * 8 + 4 + g) * 64] = c;
-        }
-    }
-    __syncthreads();
-    if (half == 0) {
-#pragma unroll
-      for (int db = 0; db < G::DB; ++db)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const f32x4 a = ms[(db * 8 + g) * 64], c = ms[(db * 8 + 4 + g) * 64];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { dk[db][4 * g + e] += a[e]; dv[db][4 * g + e] += c[e]; }
-        }
-    }
-    __syncthreads();
+    LDS::HO::run(smem, rwave, half, lane, [&](int n) { return acc_x4(n & 4 ? dv : dk, n / 8 * 4 + n % 4); },      // [db][dK | dV chunks]
+                 [&](int n, const f32x4& v) { add_x4(n & 4 ? dv : dk, n / 8 * 4 + n % 4, v); });
   }
   // Epilogue through the LDS (RowEpilogue): every tile ended with a barrier, so no wave still reads the staging buffers.
   // With SEP the next pass is requested between its steps and the epilogue reads nothing from global memory (see bwd_dq_kernel).
@@ -1550,21 +1533,19 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
 
 template <typename T, int D, bool BIAS, int NW, bool TWO, bool KSPLIT = false>
 static hipError_t launch_dq_nw(const BwdParams& p, hipStream_t s) {
-  constexpr int RWAVES = KSPLIT ? NW / 2 : NW, BM = 32 * RWAVES;
   // 128-key stages (one barrier per 128 keys) in the 8-wave form and, with LDS-DMA staging (no staging registers), also for the
   // one-wave-per-SIMD configurations (16-bit D >= 96: one workgroup per CU, the LDS is there)
   // 8-wave form: 256-key stages where they arrive by LDS-DMA (no staging registers), 128-key stages through registers (f32)
   constexpr int SUB = KSPLIT ? 2 : NW == 8 ? (Traits<T>::ES == 2 ? kDqSub8 : 2) : 1;
-  size_t lds = DqLds<T, D, RWAVES, SUB, TWO, KSPLIT>::TOTAL;      // 2 buffers x (K stage + V stage), epilogue scratch behind or inside them
-  if (KSPLIT && lds < (size_t)RWAVES * 64 * 16 * TileGeom<D, Traits<T>::ES>::DB * 4) lds = (size_t)RWAVES * 64 * 16 * TileGeom<D, Traits<T>::ES>::DB * 4;
-  const dim3 grid((unsigned)((int64_t)p.B * p.H * tile_pairs(tile_count(p.N, BM), p.causal)), (unsigned)(p.dq_splits > 1 ? p.dq_splits : 1));
+  typedef DqLds<T, D, NW, SUB, TWO, KSPLIT> LDS;
+  const dim3 grid((unsigned)((int64_t)p.B * p.H * tile_pairs(tile_count(p.N, 32 * LDS::RWAVES), p.causal)), (unsigned)(p.dq_splits > 1 ? p.dq_splits : 1));
   // (two instantiations, see launch_fwd_nw.  The two-wave form of 256-byte rows sits at its 256 registers: its non-causal
   //  instantiation came out with spill reloads inside the tile loops -- +5.6 % time -- so those launches keep the general kernel)
   constexpr bool GENERAL_ONLY = TWO && D * Traits<T>::ES >= 256;      // (its non-causal twin is not even instantiated)
   if constexpr (!GENERAL_ONLY) {
-    if (!p.causal) return launch_with_lds<bwd_dq_kernel<T, D, NW, BIAS, SUB, TWO, true, KSPLIT>>(grid, dim3(NW * 64), lds, s, p);
+    if (!p.causal) return launch_with_lds<bwd_dq_kernel<T, D, NW, BIAS, SUB, TWO, true, KSPLIT>>(grid, dim3(NW * 64), LDS::TOTAL, s, p);
   }
-  return launch_with_lds<bwd_dq_kernel<T, D, NW, BIAS, SUB, TWO, false, KSPLIT>>(grid, dim3(NW * 64), lds, s, p);
+  return launch_with_lds<bwd_dq_kernel<T, D, NW, BIAS, SUB, TWO, false, KSPLIT>>(grid, dim3(NW * 64), LDS::TOTAL, s, p);
 }
 
 // the instantiation of form f (choose_dq, fcsa_dispatch.h)
@@ -1590,7 +1571,6 @@ static hipError_t launch_dq_form(DqForm f, const BwdParams& p, hipStream_t s) {
 
 template <typename T, int D, bool BIAS, int NW, bool LEAN = false, bool QSPLIT = false, bool SWEEP = false>
 static hipError_t launch_dkv_nw(const BwdParams& p, hipStream_t s) {
-  constexpr int BNK = 32 * (QSPLIT ? NW / 2 : NW);
   // staged query tile: 32 rows for wide feature rows (16-bit D >= 96, f32 D >= 64: VGPR budget of the staging registers),
   // else 64; 128 in the 8-wave form (one workgroup per CU: the LDS is there, and half the barriers per key tile: -4.5%)
   // (the pipelined LDS-DMA form has no staging registers: wide rows can take deeper tiles too -> fragment prefetch across
@@ -1602,16 +1582,13 @@ static hipError_t launch_dkv_nw(const BwdParams& p, hipStream_t s) {
   constexpr int BMQ = LEAN ? LEAN_BMQ : (D * Traits<T>::ES >= 192) ? (DMA_FORM ? kDkvBmqWide : 32) : (NW == 8 ? kDkvBmq8 : 64);
   // ring form: the pipelined LDS-DMA tile (16 bit, no bias, not lean) where three buffers fit the workgroup's LDS share
   constexpr bool RING = kDkvRing && DMA_FORM && !LEAN && (BMQ * TileGeom<D, Traits<T>::ES>::ROWB) % 1024 == 0 &&
-                        DkvLds<T, D, NW, BMQ, BIAS, LEAN, 3>::TOTAL <= ((NW == 8 || D * Traits<T>::ES > kDkv2WBytes) ? 160 : 80) * 1024;
-  // NBUF x [Q tile | dO tile | lc | -delta], epilogue scratch behind or inside them; bias launches: + the waves' transposition scratch
-  static_assert(!QSPLIT || RING || BIAS, "query-split form: ring tile, or the generic tile with a bias");
-  size_t lds = DkvLds<T, D, NW, BMQ, BIAS, LEAN, RING ? 3 : 2>::TOTAL + (BIAS ? (size_t)NW * BiasBlock<T>::BYTES : 0);
-  if (QSPLIT && lds < (size_t)(NW / 2) * 64 * 16 * TileGeom<D, Traits<T>::ES>::DB * 8) lds = (size_t)(NW / 2) * 64 * 16 * TileGeom<D, Traits<T>::ES>::DB * 8;
-  const dim3 grid((unsigned)(p.B * (SWEEP ? p.H / p.kv_group : p.H) * tile_pairs(tile_count(p.M, BNK), p.causal)),
+                        DkvLds<T, D, NW, BMQ, BIAS, false, true, false>::FITS;
+  typedef DkvLds<T, D, NW, BMQ, BIAS, LEAN, RING, QSPLIT> LDS;
+  const dim3 grid((unsigned)(p.B * (SWEEP ? p.H / p.kv_group : p.H) * tile_pairs(tile_count(p.M, 32 * LDS::RWAVES), p.causal)),
                   (unsigned)(p.dkv_splits > 1 ? p.dkv_splits : 1));
   // (two instantiations, see launch_fwd_nw)
-  return p.causal ? launch_with_lds<bwd_dkv_kernel<T, D, NW, BMQ, BIAS, LEAN, false, RING, QSPLIT, SWEEP>>(grid, dim3(NW * 64), lds, s, p)
-                  : launch_with_lds<bwd_dkv_kernel<T, D, NW, BMQ, BIAS, LEAN, true, RING, QSPLIT, SWEEP>>(grid, dim3(NW * 64), lds, s, p);
+  return p.causal ? launch_with_lds<bwd_dkv_kernel<T, D, NW, BMQ, BIAS, LEAN, false, RING, QSPLIT, SWEEP>>(grid, dim3(NW * 64), LDS::TOTAL, s, p)
+                  : launch_with_lds<bwd_dkv_kernel<T, D, NW, BMQ, BIAS, LEAN, true, RING, QSPLIT, SWEEP>>(grid, dim3(NW * 64), LDS::TOTAL, s, p);
 }
 
 static std::atomic<int> g_kv_group_mode{1};

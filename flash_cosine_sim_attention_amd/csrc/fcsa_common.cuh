@@ -756,6 +756,10 @@ template <typename T, int D> struct RowEpilogue {
   }
 };
 
+// Every kernel's LDS plan holds TOTAL, the dynamic LDS bytes its launcher requests, and asserts TOTAL <= kLdsBytes (LDS per CU).
+constexpr int kLdsBytes = 160 * 1024;
+constexpr int lds_max(int a, int b) { return a > b ? a : b; }
+
 // LDS plan of a kernel that stages tiles in two buffers (STAGE bytes together) and ends every pass with a RowEpilogue.
 // SEP: the f32 epilogue scratch lies BEHIND the staging buffers instead of in them, so the next pass can start loading (LDS-DMA
 // into staging buffer 0, row fragments into registers) before the epilogue of the current one has run, and no barrier separates
@@ -769,11 +773,51 @@ template <typename T, int D, int NW, int STAGE, bool AHEAD_OK, int CAP> struct E
   static constexpr bool SEP = AHEAD_OK && STAGE + NW * EP::BYTES_NOX <= CAP;
   static constexpr bool X = Traits<T>::ES == 2 && (SEP ? NW * 32 * XROW <= STAGE / 2 : NW * EP::BYTES <= CAP);
   static constexpr int PER_WAVE = (X && !SEP) ? EP::BYTES : EP::BYTES_NOX;
-  static constexpr int TOTAL = SEP ? STAGE + NW * PER_WAVE : (STAGE > NW * PER_WAVE ? STAGE : NW * PER_WAVE);
+  static constexpr int EPI_TOTAL = SEP ? STAGE + NW * PER_WAVE : lds_max(STAGE, NW * PER_WAVE);    // staging + epilogue scratch
+  static constexpr bool FITS = EPI_TOTAL <= CAP;
   static constexpr int XPITCH = SEP ? XROW : EP::XPITCH;
   static FCSA_DEV char* scratch(char* smem, int wave) { return smem + (SEP ? STAGE : 0) + wave * PER_WAVE; }
   static FCSA_DEV char* xarea(char* smem, int wave) { return SEP ? smem + STAGE / 2 + wave * 32 * XROW : scratch(smem, wave) + 32 * EP::PITCH; }
 };
+
+// Hand-over of the split forms (fwd KSPLIT, dQ KSPLIT, dK/dV QSPLIT): wave rwave + rwaves (half 1) passes N partial f32x4 per lane,
+// put(0 .. N-1), to wave rwave (half 0), which owns the same rows, through the LDS at smem (free: the key / query loop has ended with a
+// barrier).  Half 0 gets them as take(n, value): first the N % 4 values past the last group of four (the forward's row terms, which
+// say how to combine the rest), then the rest in order.  The barrier at the end frees the area for what follows.  The loops walk groups
+// of four (one f32x16 accumulator each): one flat loop over n changed the register allocation of the split kernels.
+template <int N> struct SplitHandover {
+  static constexpr int bytes(int rwaves) { return rwaves * 64 * 16 * N; }
+  template <typename Put, typename Take> static FCSA_DEV void run(char* smem, int rwave, int half, int lane, Put put, Take take) {
+    constexpr int N4 = N / 4 * 4;
+    f32x4* ms = reinterpret_cast<f32x4*>(smem) + rwave * (N * 64) + lane;      // lane-contiguous 16-byte accesses
+    if (half == 1) {
+#pragma unroll
+      for (int a = 0; a < N4; a += 4)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) ms[(a + g) * 64] = put(a + g);
+#pragma unroll
+      for (int n = N4; n < N; ++n) ms[n * 64] = put(n);
+    }
+    __syncthreads();
+    if (half == 0) {
+#pragma unroll
+      for (int n = N4; n < N; ++n) take(n, ms[n * 64]);
+#pragma unroll
+      for (int a = 0; a < N4; a += 4)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) take(a + g, ms[(a + g) * 64]);
+    }
+    __syncthreads();
+  }
+};
+// accumulators acc[DB] as 4 * DB f32x4: the n-th is acc[n / 4][4 * (n % 4) .. + 3]
+template <int DB> FCSA_DEV f32x4 acc_x4(const f32x16 (&acc)[DB], int n) {
+  return f32x4{acc[n / 4][4 * (n % 4)], acc[n / 4][4 * (n % 4) + 1], acc[n / 4][4 * (n % 4) + 2], acc[n / 4][4 * (n % 4) + 3]};
+}
+template <int DB> FCSA_DEV void add_x4(f32x16 (&acc)[DB], int n, const f32x4& v) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) acc[n / 4][4 * (n % 4) + e] += v[e];
+}
 
 // Issue slots of the slot-scheduled kernels (fwd2, dkv2): one MFMA + a fixed share of the VALU work + at most a couple
 // of memory instructions per slot, fenced so that hipcc's scheduler keeps exactly this program order.

@@ -430,6 +430,20 @@ template <typename T, int D, bool DYN> constexpr int fwd_stage_tiles() {
   return (!DYN && Traits<T>::ES == 2 && (64 * TileGeom<D, Traits<T>::ES>::ROWB) % 1024 == 0) ? kFwdSub : 1;
 }
 
+// LDS plan of fwd_kernel: two stages of [SUB K tiles | SUB V tiles].  After the key loop the same bytes hold the row epilogue's
+// scratch (one per row slice) and, before it, the KSPLIT hand-over: O^T accumulators + one vector (l, reference, valid, -) per lane.
+template <typename T, int D, int NW, bool DYN, bool KSPLIT> struct FwdLds {
+  typedef TileGeom<D, Traits<T>::ES> G;
+  typedef SplitHandover<G::DB * 4 + 1> HO;
+  static constexpr int RWAVES = KSPLIT ? NW / 2 : NW;                      // waves that own distinct row slices
+  static constexpr int SUB = KSPLIT ? 2 : fwd_stage_tiles<T, D, DYN>();    // 64-key tiles per stage
+  static constexpr int TILE_B = 64 * G::ROWB;
+  static constexpr int STAGE_B = 2 * SUB * TILE_B;
+  static constexpr int EPI_B = RowEpilogue<T, D>::BYTES_NOX;              // epilogue scratch of a row slice, from byte 0
+  static constexpr int TOTAL = lds_max(lds_max(2 * STAGE_B, RWAVES * EPI_B), KSPLIT ? HO::bytes(RWAVES) : 0);
+  static_assert(TOTAL <= kLdsBytes, "fwd_kernel LDS");
+};
+
 // DYN: per-row exponent reference for logit ranges no constant shift can hold, kept online (online_recentre); the S accumulators
 // start from -reference instead of the static shift and inv_l is saved as log2(1 / sum_j exp(S_ij)), i.e. for shift 0.
 // KM: the launch is NOT causal (compile-time: a third tile loop in one kernel made hipcc spill 200 registers): tiles that need
@@ -447,12 +461,10 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ?
   const int causal = KM ? 0 : p.causal;      // (same type and value as p.causal: the causal instantiations compile to what they were)
   typedef TileGeom<D, Traits<T>::ES> G;
   typedef Traits<T> TR;
-  constexpr int RWAVES = KSPLIT ? NW / 2 : NW;            // waves that own distinct row slices
+  typedef FwdLds<T, D, NW, DYN, KSPLIT> LDS;
+  constexpr int RWAVES = LDS::RWAVES, SUB = LDS::SUB, TILE_B = LDS::TILE_B, STAGE_B = LDS::STAGE_B;
   constexpr int BN = 64, BM = 32 * RWAVES, NT = NW * 64;
-  constexpr int TILE_B = BN * G::ROWB;
-  constexpr int SUB = KSPLIT ? 2 : fwd_stage_tiles<T, D, DYN>();       // 64-key tiles per stage
-  constexpr int STAGE_B = 2 * SUB * TILE_B;                // K tiles | V tiles of one stage
-  extern __shared__ __attribute__((aligned(16))) char smem[];   // [2][SUB K tiles | SUB V tiles]
+  extern __shared__ __attribute__((aligned(16))) char smem[];   // FwdLds
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -763,46 +775,31 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ?
   // epilogue: normalise and store.  Lane (i, hi) holds O[i][32*db + 8*rq + 4*hi + 0..3].
   float lt = (TR::ES == 2) ? lacc[0] + xhalf_sum(l) : xhalf_sum(l);
   if constexpr (KSPLIT) {
-    // the odd-tile half hands its partials to the even-tile half of the same rows through the LDS (the staging buffers are free:
-    // every wave's last LDS read came before the last stage barrier); 16-byte accesses, lane-contiguous
+    // the odd-tile half hands its partials to the even-tile half of the same rows (SplitHandover; the staging buffers are free: every
+    // wave's last LDS read came before the last stage barrier)
     // DYN: the halves kept their own per-row exponent references (c2row; a half that met no valid key has rmax == -inf and nothing
     // accumulated): the partials are brought to the larger reference before they are added -- the one rescale a running max costs here
-    constexpr int NV = G::DB * 4 + 1;                                  // f32x4 per lane: O^T accumulators + (l, reference, valid, -)
-    f32x4* ms = reinterpret_cast<f32x4*>(smem) + rwave * (NV * 64) + lane;
-    if (half == 1) {
+    float f0 = 1.f, f1 = 1.f;
+    constexpr int NV = G::DB * 4 + 1;      // f32x4 per lane: the O^T accumulators, then (l, reference, valid, -)
+    LDS::HO::run(smem, rwave, half, lane,
+                 [&](int n) { return n < NV - 1 ? acc_x4(o, n) : f32x4{lt, c2row, rmax == -INFINITY ? 0.f : 1.f, 0.f}; },
+                 [&](int n, const f32x4& v) {
+                   if (n == NV - 1) {      // (taken first)
+                     if constexpr (DYN) {
+                       const bool v0 = rmax != -INFINITY, v1 = v[2] != 0.f;
+                       const float m = v0 ? (v1 ? fmaxf(c2row, v[1]) : c2row) : v[1];
+                       f0 = v0 ? fast_exp2(c2row - m) : 0.f;
+                       f1 = v1 ? fast_exp2(v[1] - m) : 0.f;
+                       c2row = m;
+                       if (v1) rmax = 0.f;      // (only its -inf-ness is read below)
+                     }
+                     lt = DYN ? lt * f0 + v[0] * f1 : lt + v[0];
+                   } else {
+                     f32x16& od = o[n / 4];
 #pragma unroll
-      for (int db = 0; db < G::DB; ++db)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const f32x4 v = {o[db][4 * g], o[db][4 * g + 1], o[db][4 * g + 2], o[db][4 * g + 3]};
-          ms[(db * 4 + g) * 64] = v;
-        }
-      const f32x4 lv = {lt, c2row, rmax == -INFINITY ? 0.f : 1.f, 0.f};
-      ms[(NV - 1) * 64] = lv;
-    }
-    __syncthreads();
-    if (half == 0) {
-      const f32x4 lv = ms[(NV - 1) * 64];
-      float f0 = 1.f, f1 = 1.f;
-      if constexpr (DYN) {
-        const bool v0 = rmax != -INFINITY, v1 = lv[2] != 0.f;
-        const float m = v0 ? (v1 ? fmaxf(c2row, lv[1]) : c2row) : lv[1];
-        f0 = v0 ? fast_exp2(c2row - m) : 0.f;
-        f1 = v1 ? fast_exp2(lv[1] - m) : 0.f;
-        c2row = m;
-        if (v1) rmax = 0.f;      // (only its -inf-ness is read below)
-      }
-#pragma unroll
-      for (int db = 0; db < G::DB; ++db)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const f32x4 v = ms[(db * 4 + g) * 64];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[db][4 * g + e] = DYN ? o[db][4 * g + e] * f0 + v[e] * f1 : o[db][4 * g + e] + v[e];
-        }
-      lt = DYN ? lt * f0 + lv[0] * f1 : lt + lv[0];
-    }
-    __syncthreads();                                                    // (the row epilogue's scratch overlays what was just read)
+                     for (int e = 0; e < 4; ++e) od[4 * (n % 4) + e] = DYN ? od[4 * (n % 4) + e] * f0 + v[e] * f1 : od[4 * (n % 4) + e] + v[e];
+                   }
+                 });
     if (half == 1) {
       if (pass + 1 < npass) __syncthreads();
       continue;
@@ -827,7 +824,7 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ?
   {
     typedef RowEpilogue<T, D> EP;
     if (p.N - mw > 0)
-      EP::store(smem + rwave * EP::BYTES_NOX, o, inv, (LEAN || (BIAS && DYN)) ? opaque(lane) : lane, p.o.p + (int64_t)b * p.o.sb + (int64_t)h * p.o.sh + (int64_t)mw * p.o.sn, p.o.sn,
+      EP::store(smem + rwave * LDS::EPI_B, o, inv, (LEAN || (BIAS && DYN)) ? opaque(lane) : lane, p.o.p + (int64_t)b * p.o.sb + (int64_t)h * p.o.sh + (int64_t)mw * p.o.sn, p.o.sn,
                 p.N - mw, false, nullptr, 0, 1.f, nullptr, 1, 0, 1.f);
     if (pass + 1 < npass) __syncthreads();
   }
@@ -961,14 +958,20 @@ FCSA_DEV void fwd2_tile(const char* vt, const char* knext, u32x4 (&kf)[2][TileGe
   }
   FCSA_STAMP(ts, 5);
 }
+// LDS plan of fwd2_kernel: two buffers of [K tile | V tile]
+template <typename T, int D> struct Fwd2Lds {
+  static constexpr int TILE_B = 64 * TileGeom<D, Traits<T>::ES>::ROWB;
+  static constexpr int TOTAL = 2 * 2 * TILE_B;
+  static_assert(TOTAL <= kLdsBytes, "fwd2_kernel LDS");
+};
 template <typename T, int D, int NW>
 __global__ void __launch_bounds__(NW * 64, 1) fwd2_kernel(const FwdParams p) {
   typedef TileGeom<D, 2> G;
   typedef Traits<T> TR;
   static_assert(TR::ES == 2, "16-bit types only");
   constexpr int BN = 64, RW = 64, BM = RW * NW, NT = NW * 64;
-  constexpr int TILE_B = BN * G::ROWB;
-  extern __shared__ __attribute__((aligned(16))) char smem[];   // [2][K tile | V tile]
+  constexpr int TILE_B = Fwd2Lds<T, D>::TILE_B;
+  extern __shared__ __attribute__((aligned(16))) char smem[];   // Fwd2Lds
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -1182,15 +1185,13 @@ __global__ void __launch_bounds__(256) fwd_combine_kernel(const FwdParams p) {
 
 template <typename T, int D, bool BIAS, int NW, bool DYN, bool LEAN = false, bool KSPLIT = false>
 static hipError_t launch_fwd_nw(const FwdParams& p, hipStream_t s) {
-  constexpr int RWAVES = KSPLIT ? NW / 2 : NW, BM = 32 * RWAVES;
-  static_assert(!KSPLIT || (64 * TileGeom<D, Traits<T>::ES>::ROWB) % 1024 == 0, "key-split form: whole 1 KiB LDS-DMA pieces per tile");
-  size_t lds = 4 * 64 * (KSPLIT ? 2 : fwd_stage_tiles<T, D, DYN>()) * TileGeom<D, Traits<T>::ES>::ROWB;      // 2 buffers x (K + V tiles of a stage)
-  if (lds < (size_t)RWAVES * RowEpilogue<T, D>::BYTES_NOX) lds = (size_t)RWAVES * RowEpilogue<T, D>::BYTES_NOX;   // epilogue scratch reuses the same bytes
-  if (KSPLIT && lds < (size_t)RWAVES * 64 * 16 * (TileGeom<D, Traits<T>::ES>::DB * 4 + 1)) lds = (size_t)RWAVES * 64 * 16 * (TileGeom<D, Traits<T>::ES>::DB * 4 + 1);
+  typedef FwdLds<T, D, NW, DYN, KSPLIT> LDS;
+  constexpr int BM = 32 * LDS::RWAVES;
+  static_assert(!KSPLIT || LDS::TILE_B % 1024 == 0, "key-split form: whole 1 KiB LDS-DMA pieces per tile");
   // two instantiations: causal launches (select per logit on the diagonal tiles) and the others (key masks as a rank-1 MFMA)
   const dim3 grid((unsigned)(p.B * p.H * tile_pairs(tile_count(p.N, BM), p.causal)), (unsigned)(p.splits > 1 ? p.splits : 1));
-  const hipError_t e = p.causal ? launch_with_lds<fwd_kernel<T, D, NW, BIAS, DYN, LEAN, false, KSPLIT>>(grid, dim3(NW * 64), lds, s, p)
-                                : launch_with_lds<fwd_kernel<T, D, NW, BIAS, DYN, LEAN, true, KSPLIT>>(grid, dim3(NW * 64), lds, s, p);
+  const hipError_t e = p.causal ? launch_with_lds<fwd_kernel<T, D, NW, BIAS, DYN, LEAN, false, KSPLIT>>(grid, dim3(NW * 64), LDS::TOTAL, s, p)
+                                : launch_with_lds<fwd_kernel<T, D, NW, BIAS, DYN, LEAN, true, KSPLIT>>(grid, dim3(NW * 64), LDS::TOTAL, s, p);
   if (e != hipSuccess) return e;
   if (p.splits > 1) {
     const int64_t items = (int64_t)p.B * p.H * p.N * (D / 8);
@@ -1202,7 +1203,7 @@ static hipError_t launch_fwd_nw(const FwdParams& p, hipStream_t s) {
 template <typename T, int D>
 static hipError_t launch_fwd2(const FwdParams& p, hipStream_t s) {
   constexpr int NW = 4, BM = 64 * NW;
-  return launch_with_lds<fwd2_kernel<T, D, NW>>(dim3((unsigned)(p.B * p.H * tile_pairs(tile_count(p.N, BM), p.causal))), dim3(NW * 64), 4 * 64 * TileGeom<D, 2>::ROWB, s, p);
+  return launch_with_lds<fwd2_kernel<T, D, NW>>(dim3((unsigned)(p.B * p.H * tile_pairs(tile_count(p.N, BM), p.causal))), dim3(NW * 64), Fwd2Lds<T, D>::TOTAL, s, p);
 }
 
 // the instantiation of form f (choose_forward, fcsa_dispatch.h)

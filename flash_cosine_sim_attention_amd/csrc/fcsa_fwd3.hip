@@ -332,15 +332,24 @@ FCSA_DEV void fwd3_finish_q(const FwdParams& p, int b, int h, int i, int hi_, u3
 
 FCSA_TRACE_PHASE_SITE(fwd3)
 
+// LDS plan of fwd3_kernel: rings of R K tiles | R V tiles (16 KiB each); after the key loop the bytes hold the four waves' row
+// epilogue scratch
+template <typename T, int R> struct Fwd3Lds {
+  static constexpr int TILE_B = 64 * TileGeom<128, 2>::ROWB;
+  static constexpr int EPI_B = RowEpilogue<T, 128>::BYTES_NOX;      // epilogue scratch of a wave, from byte 0
+  static constexpr int TOTAL = lds_max(2 * R * TILE_B, 4 * EPI_B);
+  static_assert(TILE_B == 16384 && TOTAL <= kLdsBytes, "fwd3_kernel LDS");
+};
+
 template <typename T, int R, bool RSUM>
 __global__ void __launch_bounds__(256, 1) fwd3_kernel(const FwdParams p) {
   constexpr int D = 128;
-  typedef TileGeom<D, 2> G;
   typedef DmaStager<T, D, 64, 4> DS;
+  typedef Fwd3Lds<T, R> LDS;
   constexpr int BN = 64, RW = 64, NW = 4, BM = RW * NW;
-  constexpr int TILE_B = BN * G::ROWB;             // 16 KiB
-  static_assert(TILE_B == 16384 && DS::PER == 4 && DS::UNIFORM && R >= 3, "fwd3 geometry");
-  extern __shared__ __attribute__((aligned(16))) char smem[];      // [R] K tiles | [R] V tiles; the epilogue scratch reuses the bytes
+  constexpr int TILE_B = LDS::TILE_B;
+  static_assert(DS::PER == 4 && DS::UNIFORM && R >= 3, "fwd3 geometry");
+  extern __shared__ __attribute__((aligned(16))) char smem[];      // Fwd3Lds
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -519,7 +528,7 @@ __global__ void __launch_bounds__(256, 1) fwd3_kernel(const FwdParams p) {
     wg_barrier();                // every wave has left the ring: its bytes become the epilogue scratch
 
     // ---- epilogue: normalise, transpose through the LDS, whole-row stores (RowEpilogue) ----
-    char* scr = smem + wave * RowEpilogue<T, D>::BYTES_NOX;
+    char* scr = smem + wave * LDS::EPI_B;
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
       const int i = i0 + 32 * r;
@@ -546,9 +555,8 @@ constexpr bool kFwd3RoundedSums = false; // row sums of the un-rounded P~ (plain
 
 template <typename T, int R, bool RSUM>
 static hipError_t launch_fwd3_t(const FwdParams& p, hipStream_t s) {
-  size_t lds = (size_t)2 * R * 16384;
-  if (lds < (size_t)4 * RowEpilogue<T, 128>::BYTES_NOX) lds = (size_t)4 * RowEpilogue<T, 128>::BYTES_NOX;
-  return launch_with_lds<fwd3_kernel<T, R, RSUM>>(dim3((unsigned)(p.B * p.H * tile_pairs(tile_count(p.N, 256), p.causal))), dim3(256), lds, s, p);
+  return launch_with_lds<fwd3_kernel<T, R, RSUM>>(dim3((unsigned)(p.B * p.H * tile_pairs(tile_count(p.N, 256), p.causal))), dim3(256),
+                                                  Fwd3Lds<T, R>::TOTAL, s, p);
 }
 
 // Escape hatch (same-process A/B, triage): 0 = never take this form.  The environment is read ONCE, when the library is loaded
