@@ -79,10 +79,12 @@ NormState = _STRUCTS["fcsa_norm_state"]
 ForwardArgs = _STRUCTS["fcsa_forward_args"]
 BackwardArgs = _STRUCTS["fcsa_backward_args"]
 KernelStat = _STRUCTS["fcsa_kernel_stat"]
+Varlen = _STRUCTS["fcsa_varlen"]
 
 
 EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fcsa_forward_workspace_bytes", "fcsa_forward_needs_qn",
-           "fcsa_l2norm", "fcsa_debug", "fcsa_debug_forward_form", "fcsa_debug_kv_group_form", "fcsa_last_error", "fcsa_profile_enable", "fcsa_profile_collect")
+           "fcsa_l2norm", "fcsa_debug", "fcsa_debug_forward_form", "fcsa_debug_kv_group_form", "fcsa_last_error", "fcsa_profile_enable", "fcsa_profile_collect",
+           "fcsa_forward_varlen", "fcsa_backward_varlen", "fcsa_backward_varlen_workspace_bytes")
 
 _lib = None
 
@@ -134,6 +136,12 @@ def load():
     lib.fcsa_profile_enable.restype = C.c_int
     lib.fcsa_profile_collect.argtypes = [C.POINTER(KernelStat), C.c_int32]
     lib.fcsa_profile_collect.restype = C.c_int
+    lib.fcsa_forward_varlen.argtypes = [C.POINTER(ForwardArgs), C.POINTER(Varlen)]
+    lib.fcsa_forward_varlen.restype = C.c_int
+    lib.fcsa_backward_varlen.argtypes = [C.POINTER(BackwardArgs), C.POINTER(Varlen)]
+    lib.fcsa_backward_varlen.restype = C.c_int
+    lib.fcsa_backward_varlen_workspace_bytes.argtypes = [C.POINTER(Problem), C.POINTER(Varlen)]
+    lib.fcsa_backward_varlen_workspace_bytes.restype = C.c_size_t
     lib.fcsa_last_error.argtypes = []
     lib.fcsa_last_error.restype = C.c_char_p
     ver = lib.fcsa_debug(None, 0)

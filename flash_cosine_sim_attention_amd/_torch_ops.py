@@ -59,6 +59,30 @@ def _register_fakes():
     def _(q, k, v, mask, attn_bias, attn_bias_batch_dim, scale, causal, l2norm_qk, groups):
         return q.new_empty(q.shape)
 
+    @torch.library.register_fake("fcsa::varlen_forward")
+    def _(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, scale, causal, l2norm_qk, groups, need_backward):
+        TQ, H, D = q.shape
+        TK, Hk = k.shape[0], k.shape[1]
+        f32 = dict(device=q.device, dtype=torch.float32)
+        none32, none = q.new_empty((0,), dtype=torch.float32), q.new_empty((0,))
+        inv_l = torch.empty((H, TQ), **f32) if need_backward else none32
+        blocks = (D // groups) // 8          # as fcsa::forward: the packed rows are a batch-1 problem
+        fusable = D % groups == 0 and (D // groups) % 8 == 0 and (blocks & (blocks - 1) == 0 or groups == 1)
+        qn = q.new_empty((H, TQ, D)) if (l2norm_qk and (need_backward or q.dtype == torch.float32 or not fusable)) else none
+        kn = q.new_empty((Hk, TK, D)) if l2norm_qk else none
+        rq = torch.empty((H, TQ, groups), **f32) if (l2norm_qk and need_backward) else none32
+        rk = torch.empty((Hk, TK, groups), **f32) if (l2norm_qk and need_backward) else none32
+        return q.new_empty(q.shape), inv_l, qn, kn, rq, rk
+
+    @torch.library.register_fake("fcsa::varlen_backward")
+    def _(d_out, o, inv_l, q, k, v, cu_seqlens_q, cu_seqlens_k, qn, kn, rq, rk, max_seqlen_q, max_seqlen_k, scale, causal, l2norm_qk,
+          groups):
+        return q.new_empty(q.shape), k.new_empty(k.shape), v.new_empty(v.shape)
+
+    @torch.library.register_fake("fcsa::varlen_attention")
+    def _(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, scale, causal, l2norm_qk, groups):
+        return q.new_empty(q.shape)
+
     @torch.library.register_fake("fcsa::backward")
     def _(d_out, o, inv_l, q, k, v, mask, attn_bias, qn, kn, rq, rk, attn_bias_batch_dim, scale, causal, l2norm_qk, groups,
           need_bias_grad):

@@ -114,3 +114,20 @@ def attention_forward_cpu(q, k, v, mask=None, attn_bias=None, scale=8.0, groups=
             t.copy_(t_new)
     out = acc / total.clamp_min(1e-30)                    # rows without a valid key: 0 / tiny = 0
     return out.reshape(out_shape).to(out_dtype)
+
+
+def attention_forward_varlen_cpu(q, k, v, cu_seqlens_q, cu_seqlens_k, scale=8.0, groups=1, causal=False, l2norm_qk=True):
+    """Forward-only path of `flash_cosine_sim_attention_varlen` on host tensors: packed q [total_q, H, D], k / v [total_k, Hk, D] and
+    validated host tables; each sequence runs through `attention_forward_cpu` as a batch-1 problem, so its rows are exactly what the
+    dense CPU path gives for that sequence alone."""
+    out = torch.zeros_like(q)
+    cq, ck = cu_seqlens_q.tolist(), cu_seqlens_k.tolist()
+    for s in range(len(cq) - 1):
+        qs = q[cq[s]:cq[s + 1]].permute(1, 0, 2).unsqueeze(0)         # [1, H, N_s, D]
+        ks = k[ck[s]:ck[s + 1]].permute(1, 0, 2).unsqueeze(0)
+        vs = v[ck[s]:ck[s + 1]].permute(1, 0, 2).unsqueeze(0)
+        if qs.shape[2] == 0:
+            continue
+        o = attention_forward_cpu(qs, ks, vs, scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk)
+        out[cq[s]:cq[s + 1]] = o[0].permute(1, 0, 2)
+    return out

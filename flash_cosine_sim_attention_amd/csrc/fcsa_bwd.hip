@@ -236,7 +236,8 @@ template <typename T, int D, int NW, int BMQ, bool BIAS, bool LEAN, bool RING, b
 // the even 64-key tile of a stage, waves 4-7 the odd one -- and add their dQ partials through the LDS at the end of the pass (see
 // fwd_kernel, KSPLIT): for grids of at most one 128-row workgroup per CU, whose four waves would each have a SIMD to themselves.
 template <typename T, int D, int NW, bool BIAS, int SUB, bool TWO, bool KM, bool KSPLIT = false>
-__global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const BwdParams p) {
+__global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const BwdParams p_) {
+  BwdParams p = p_;      // a varlen launch rebinds it to the workgroup's sequence (varlen_bind); dense launches use it as given
   static_assert(!KSPLIT || (NW == 8 && TWO && SUB == 2 && Traits<T>::ES == 2), "key-split form: 8 waves, two-wave tile, 16 bit, 2 tiles per stage");
   // (same type and value as p.causal: the causal instantiations compile to what they were.  The key-split form's !KM twin is only ever
   //  launched causal -- choose_dq -- and says so: at 256-byte rows the kernel sits at its 256 registers)
@@ -258,9 +259,10 @@ __global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const Bw
 
   // a pair of row tiles per workgroup under causal masking (tile_pairs, fcsa_dispatch.h)
   // (d_bias is not this kernel's business: bwd_dbias_kernel below recomputes the dS tiles of a bias slice and writes it once)
-  const int MT = tile_count(p.N, BM), PT = tile_pairs(MT, causal);
   int bh, pt;
-  block_work(blockIdx.x, p.B * p.H, PT, bh, pt);
+  block_work(blockIdx.x, p.B * p.H, tile_pairs(tile_count(p.N, BM), causal), bh, pt);
+  if (p.seq.cu_q != nullptr && !varlen_bind<D, Traits<T>::ES>(p, bh, pt, BM, causal, false)) return;
+  const int MT = tile_count(p.N, BM);
   const int b = bh / p.H, h = bh % p.H;
   const int npass = pair_passes(MT, pt, causal);
   // split-key launches (gridDim.y = p.dq_splits > 1): this workgroup sees the keys [k_lo, k_lo + Mk) only and
@@ -1084,7 +1086,8 @@ FCSA_DEV void dkv_tile_pipe(const char* qt, const char* dot, const float* lcs, c
 // stay in registers across the heads and the epilogue writes the group's sum once (no slabs, no finalize).  The Q / dO stream runs on
 // across the head seam: the tile requested ahead of the last tile of head g is the first tile of head g + 1, so the pipeline does not drain.
 template <typename T, int D, int NW, int BMQ, bool BIAS, bool LEAN, bool KM, bool RING = false, bool QSPLIT = false, bool SWEEP = false>      // KM: not causal, masked tiles in the rank-1 form (see fwd_kernel)
-__global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes || LEAN) ? 2 : 1)) bwd_dkv_kernel(const BwdParams p) {
+__global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes || LEAN) ? 2 : 1)) bwd_dkv_kernel(const BwdParams p_) {
+  BwdParams p = p_;      // a varlen launch rebinds it to the workgroup's sequence (varlen_bind); dense launches use it as given
   static_assert(!QSPLIT || (NW == 8 && !LEAN && (RING || BIAS) && BMQ % 64 == 0), "query-split form: 8 waves; pipelined ring tile, or the generic tile with a bias");
   static_assert(!SWEEP || (!BIAS && !QSPLIT && Traits<T>::ES == 2), "group sweep: 16-bit, bias-free, key tiles of whole workgroups");
   const int causal = KM ? 0 : p.causal;      // (same type and value as p.causal: the causal instantiations compile to what they were)
@@ -1110,16 +1113,17 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
   fa.init(lane);
 
   // causal: a pair of key tiles per workgroup, the LOW one first: it sees every later query (tile_pairs, fcsa_dispatch.h)
-  const int KT = tile_count(p.M, BNK), PT = tile_pairs(KT, causal);
   int bh, pt, b, h, hk;
   if constexpr (SWEEP) {      // grid: (batch, K/V head) x key tiles; h = the group's first query head
     const int HK = p.H / p.kv_group;
-    block_work(blockIdx.x, p.B * HK, PT, bh, pt);
+    block_work(blockIdx.x, p.B * HK, tile_pairs(tile_count(p.M, BNK), causal), bh, pt);
     b = bh / HK; hk = bh % HK; h = hk * p.kv_group;
-  } else {
-    block_work(blockIdx.x, p.B * p.H, PT, bh, pt);
+  } else {      // (varlen: never the group sweep)
+    block_work(blockIdx.x, p.B * p.H, tile_pairs(tile_count(p.M, BNK), causal), bh, pt);
+    if (p.seq.cu_q != nullptr && !varlen_bind<D, Traits<T>::ES>(p, bh, pt, BNK, causal, true)) return;
     b = bh / p.H; h = bh % p.H; hk = h / p.kv_group;
   }
+  const int KT = tile_count(p.M, BNK);
   const int npass = pair_passes(KT, pt, causal);
   const int diff = p.M - p.N;
   const int64_t rk_bh = (int64_t)b * (p.H / p.kv_group) + hk;      // (batch, K/V head) row block of rk
@@ -1622,7 +1626,8 @@ static hipError_t launch_dkv_form(DkvForm f, const BwdParams& p, hipStream_t s) 
 }
 
 static BwdProblem bwd_problem(int dtype, int D, const BwdParams& p, int splits) {
-  return {dtype == 0 ? 4 : 2, D, (int64_t)p.B * p.H, p.N, p.M, p.causal != 0, p.bias != nullptr, splits, p.kv_sweep != 0};
+  return {dtype == 0 ? 4 : 2, D, (int64_t)p.B * p.H, p.N, p.M, p.causal != 0, p.bias != nullptr, splits, p.kv_sweep != 0,
+          p.seq.cu_q != nullptr};
 }
 
 hipError_t launch_backward_dbias(int dtype, int D, const BwdParams& p, hipStream_t s) {

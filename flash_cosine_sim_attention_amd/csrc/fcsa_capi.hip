@@ -170,15 +170,16 @@ struct BwdPlan {
 // (dk and dv) outputs -- the finalize kernel sums split slabs per (batch * head) row block.
 struct BwdCall { bool bias, dq_flat, dkv_flat; };
 
-// call == nullptr: the most any call of the problem needs, which the workspace is sized for
-BwdPlan bwd_plan(const fcsa_problem& p, const BwdCall* call) {
+// call == nullptr: the most any call of the problem needs, which the workspace is sized for.  varlen: packed sequences (p is then the
+// [1, H, total, D] problem of the packed rows), which take neither a split nor the group sweep
+BwdPlan bwd_plan(const fcsa_problem& p, const BwdCall* call, bool varlen = false) {
   BwdPlan b;
   const int cus = fcsa::cu_count();
   // K/V heads fewer than query heads (single-headed or grouped): the dK/dV kernel writes per-query-head f32 slabs that the finalize kernel
   // sums over each K/V head's group -- except for the group sweep, which runs where dkv_sweep says so for a bias-free launch with
   // epilogues that finish the job (no l2norm groups that need the finalize kernel).  A launch with an attn_bias takes the slab route.
   const bool grouped = p.kv_heads != p.heads;
-  const bool sweep = p.kv_heads > 1 && grouped && (p.l2norm_qk == 0 || fusable_groups(p)) &&
+  const bool sweep = !varlen && p.kv_heads > 1 && grouped && (p.l2norm_qk == 0 || fusable_groups(p)) &&
                      fcsa::dkv_sweep(elem_size(p.dtype), p.dim_head, (int64_t)p.batch * p.kv_heads, p.k_len, p.causal != 0, fcsa::kv_group_mode(-1), cus);
   b.kv_sweep = sweep && call != nullptr && !call->bias;
   // the l2norm backward is fused into the dQ / dKV epilogues when every group is 8 * 2^k features wide; otherwise (odd group sizes) the
@@ -187,8 +188,8 @@ BwdPlan bwd_plan(const fcsa_problem& p, const BwdCall* call) {
   const bool norm_slab = p.l2norm_qk != 0 && !b.fuse_norm;
   // split dQ: flat dq, and causal splits only in bias-free kernels; split dK/dV: flat dk / dv (or per-query-head slabs anyway), bias-free,
   // never with the group sweep
-  b.dq_splits = call != nullptr && !(call->dq_flat && !(p.causal && call->bias)) ? 1 : fcsa::backward_dq_splits(p, cus);
-  b.dkv_splits = sweep || (call != nullptr && !((call->dkv_flat || grouped) && !call->bias)) ? 1 : fcsa::backward_dkv_splits(p, cus);
+  b.dq_splits = varlen || (call != nullptr && !(call->dq_flat && !(p.causal && call->bias))) ? 1 : fcsa::backward_dq_splits(p, cus);
+  b.dkv_splits = varlen || sweep || (call != nullptr && !((call->dkv_flat || grouped) && !call->bias)) ? 1 : fcsa::backward_dkv_splits(p, cus);
   b.dq_slab = b.dq_splits > 1 || norm_slab;
   b.dk_slab = !b.kv_sweep && (b.dkv_splits > 1 || grouped || norm_slab);
   b.dv_slab = !b.kv_sweep && (b.dkv_splits > 1 || grouped);
@@ -197,8 +198,8 @@ BwdPlan bwd_plan(const fcsa_problem& p, const BwdCall* call) {
 
 // workspace: delta [B,H,N] f32, then the slabs of the largest plan
 struct BwdLayout { size_t delta, dq_slab, dk_slab, dv_slab, total; };
-BwdLayout bwd_layout(const fcsa_problem& p) {
-  const BwdPlan b = bwd_plan(p, nullptr);
+BwdLayout bwd_layout(const fcsa_problem& p, bool varlen = false) {
+  const BwdPlan b = bwd_plan(p, nullptr, varlen);
   const size_t qn = (size_t)p.batch * p.heads * p.q_len;
   const size_t kn = (size_t)p.batch * p.heads * p.k_len;      // slabs are per q-head
   BwdLayout L;
@@ -234,6 +235,42 @@ template <typename F> int timed(const char* name, const char* what, hipStream_t 
   { std::lock_guard<std::mutex> g(g_prof_mu); g_prof.push_back(t); }
   return launch_check(e, what);
 }
+
+// Packed variable-length sequences (fcsa_varlen): the table is checked as far as the host can see it (never its device contents), and
+// the call is described by the problem of the packed rows -- batch 1, q_len = total_q, k_len = total_k -- which the row kernels (l2norm,
+// its backward, finalize), the workspace layout and the zero-size rules use unchanged; only the attention launches get the sequence
+// table, with B = sequences and N / M = the longest spans (a.p.q_len / k_len).
+int check_varlen(const fcsa_problem& p, const fcsa_varlen* v, bool mask, bool bias) {
+  if (v == nullptr) return fail(FCSA_ERR_INVALID_ARG, "varlen: null sequence table");
+  if (mask || bias) return fail(FCSA_ERR_INVALID_ARG, "varlen: mask and attn_bias are not supported with packed sequences");
+  if (v->total_q < 0 || v->total_k < 0 || v->total_q > INT32_MAX || v->total_k > INT32_MAX)
+    return fail(FCSA_ERR_INVALID_ARG, "varlen: total_q / total_k (%lld, %lld) outside [0, 2^31)", (long long)v->total_q, (long long)v->total_k);
+  if (p.batch > 0 && (v->cu_seqlens_q == nullptr || v->cu_seqlens_k == nullptr))
+    return fail(FCSA_ERR_INVALID_ARG, "varlen: null cu_seqlens");
+  if ((int64_t)p.heads * (v->total_q > v->total_k ? v->total_q : v->total_k) > INT32_MAX)
+    return fail(FCSA_ERR_UNSUPPORTED, "varlen: heads x packed rows above 2^31");
+  return FCSA_OK;
+}
+fcsa_problem packed_problem(const fcsa_problem& p, const fcsa_varlen& v) {
+  fcsa_problem d = p;
+  d.batch = 1;
+  d.q_len = (int32_t)v.total_q;
+  d.k_len = (int32_t)v.total_k;
+  return d;
+}
+// a varlen call: the table and the caller's problem (batch = sequences, q_len / k_len = the longest spans)
+struct VarlenCall { const fcsa_varlen* t; int batch, max_q, max_k; };
+fcsa::SeqTable seq_table(const VarlenCall* v) {
+  if (v == nullptr) return fcsa::SeqTable{nullptr, nullptr, 0, 0};
+  return fcsa::SeqTable{v->t->cu_seqlens_q, v->t->cu_seqlens_k, (int)v->t->total_q, (int)v->t->total_k};
+}
+fcsa_tensor packed(fcsa_tensor t) {       // stride0 of a packed tensor is meaningless: one "batch" of total rows
+  t.stride0 = 0;
+  return t;
+}
+
+int forward_impl(const fcsa_forward_args* a, const VarlenCall* vl);
+int backward_impl(const fcsa_backward_args* a, const VarlenCall* vl);
 
 }  // namespace
 
@@ -345,7 +382,25 @@ static int zero_rows(const char* name, const fcsa_tensor& t, int es, int B, int 
   return FCSA_OK;
 }
 
-int fcsa_forward(const fcsa_forward_args* a) {
+int fcsa_forward(const fcsa_forward_args* a) { return forward_impl(a, nullptr); }
+
+int fcsa_forward_varlen(const fcsa_forward_args* a, const fcsa_varlen* seqs) {
+  if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
+  if (int rc = check_problem(a->p)) return rc;
+  if (int rc = check_varlen(a->p, seqs, a->mask != nullptr, a->attn_bias != nullptr)) return rc;
+  fcsa_forward_args pa = *a;
+  pa.q = packed(pa.q); pa.k = packed(pa.k); pa.v = packed(pa.v); pa.o = packed(pa.o);
+  pa.p = packed_problem(a->p, *seqs);
+  const VarlenCall vl = {seqs, a->p.batch, a->p.q_len, a->p.k_len};
+  return forward_impl(&pa, &vl);
+}
+
+}  // extern "C"
+
+namespace {
+
+// vl != nullptr: packed sequences; a->p is then the problem of the packed rows (packed_problem)
+int forward_impl(const fcsa_forward_args* a, const VarlenCall* vl) {
   if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
   const fcsa_problem& p = a->p;
   if (int rc = check_problem(p)) return rc;
@@ -406,6 +461,8 @@ int fcsa_forward(const fcsa_forward_args* a) {
   fp.mask = a->mask;
   fp.bias = static_cast<const char*>(a->attn_bias);
   fp.B = p.batch; fp.H = p.heads; fp.N = p.q_len; fp.M = p.k_len;
+  fp.seq = seq_table(vl);
+  if (vl != nullptr) { fp.B = vl->batch; fp.N = vl->max_q; fp.M = vl->max_k; }
   fp.causal = p.causal; fp.bias_batch = p.bias_batch_dim;
   fp.c1 = p.scale * kLog2e;
   const bool has_bias = a->attn_bias != nullptr;
@@ -419,7 +476,7 @@ int fcsa_forward(const fcsa_forward_args* a) {
   fp.G = p.groups; fp.lgm = fuse_q ? log2_blocks_per_group(p) : 0; fp.norm_eps = 1e-12f;
   fp.dyn = dynamic_shift(p, has_bias) ? 1 : 0;      // then inv_l holds log2 of the normaliser
   fp.splits = 1; fp.ws_o = nullptr; fp.ws_l = nullptr;
-  if (a->workspace != nullptr && a->attn_bias == nullptr) {
+  if (a->workspace != nullptr && a->attn_bias == nullptr && vl == nullptr) {
     const int sp = forward_splits(p);
     if (sp > 1 && a->workspace_bytes >= forward_ws_bytes(p, sp) && (reinterpret_cast<uintptr_t>(a->workspace) & 255) == 0) {
       const size_t rows = (size_t)sp * p.batch * p.heads * p.q_len;
@@ -430,6 +487,10 @@ int fcsa_forward(const fcsa_forward_args* a) {
   }
   return timed("fwd", "forward", s, [&] { return fcsa::launch_forward(p.dtype, p.dim_head, fp, s); });
 }
+
+}  // namespace
+
+extern "C" {
 
 int fcsa_forward_needs_qn(const fcsa_problem* p, int32_t need_backward) {
   if (p == nullptr || !p->l2norm_qk) return 0;
@@ -442,7 +503,30 @@ size_t fcsa_backward_workspace_bytes(const fcsa_problem* p) {
   return bwd_layout(*p).total;
 }
 
-int fcsa_backward(const fcsa_backward_args* a) {
+size_t fcsa_backward_varlen_workspace_bytes(const fcsa_problem* p, const fcsa_varlen* seqs) {
+  if (p == nullptr || seqs == nullptr || seqs->total_q < 0 || seqs->total_k < 0) return 0;
+  return bwd_layout(packed_problem(*p, *seqs), true).total;
+}
+
+int fcsa_backward(const fcsa_backward_args* a) { return backward_impl(a, nullptr); }
+
+int fcsa_backward_varlen(const fcsa_backward_args* a, const fcsa_varlen* seqs) {
+  if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
+  if (int rc = check_problem(a->p)) return rc;
+  if (int rc = check_varlen(a->p, seqs, a->mask != nullptr, a->attn_bias != nullptr || a->d_bias != nullptr)) return rc;
+  fcsa_backward_args pa = *a;
+  pa.d_out = packed(pa.d_out); pa.o = packed(pa.o); pa.q = packed(pa.q); pa.k = packed(pa.k); pa.v = packed(pa.v);
+  pa.dq = packed(pa.dq); pa.dk = packed(pa.dk); pa.dv = packed(pa.dv);
+  pa.p = packed_problem(a->p, *seqs);
+  const VarlenCall vl = {seqs, a->p.batch, a->p.q_len, a->p.k_len};
+  return backward_impl(&pa, &vl);
+}
+
+}  // extern "C"
+
+namespace {
+
+int backward_impl(const fcsa_backward_args* a, const VarlenCall* vl) {
   if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
   const fcsa_problem& p = a->p;
   if (int rc = check_problem(p)) return rc;
@@ -469,7 +553,7 @@ int fcsa_backward(const fcsa_backward_args* a) {
   }
   if (a->inv_l == nullptr) return fail(FCSA_ERR_INVALID_ARG, "inv_l: null pointer");
   if (a->attn_bias == nullptr && a->d_bias != nullptr) return fail(FCSA_ERR_INVALID_ARG, "d_bias without attn_bias");
-  const BwdLayout L = bwd_layout(p);
+  const BwdLayout L = bwd_layout(p, vl != nullptr);
   if (a->workspace == nullptr || a->workspace_bytes < L.total)
     return fail(FCSA_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", a->workspace_bytes, L.total);
   if ((reinterpret_cast<uintptr_t>(a->workspace) & 255) != 0) return fail(FCSA_ERR_WORKSPACE, "workspace not 256-byte aligned");
@@ -479,7 +563,7 @@ int fcsa_backward(const fcsa_backward_args* a) {
   const bool grouped = p.kv_heads != p.heads;             // single-headed or grouped-query K/V: dk / dv are sums over query heads
   const BwdCall call = {a->attn_bias != nullptr, a->dq.stride0 == (int64_t)p.heads * a->dq.stride1,
                         a->dk.stride0 == (int64_t)p.heads * a->dk.stride1 && a->dv.stride0 == (int64_t)p.heads * a->dv.stride1};
-  const BwdPlan plan = bwd_plan(p, &call);
+  const BwdPlan plan = bwd_plan(p, &call, vl != nullptr);
   const int dq_splits = plan.dq_splits, dkv_splits = plan.dkv_splits;
   const bool dq_slab = plan.dq_slab, dk_slab = plan.dk_slab, dv_slab = plan.dv_slab;
   char* ws = static_cast<char*>(a->workspace);
@@ -530,6 +614,8 @@ int fcsa_backward(const fcsa_backward_args* a) {
   bp.bias = static_cast<const char*>(a->attn_bias);
   bp.d_bias = a->d_bias;
   bp.B = p.batch; bp.H = p.heads; bp.N = p.q_len; bp.M = p.k_len;
+  bp.seq = seq_table(vl);
+  if (vl != nullptr) { bp.B = vl->batch; bp.N = vl->max_q; bp.M = vl->max_k; }
   bp.causal = p.causal; bp.bias_batch = p.bias_batch_dim;
   bp.c1 = p.scale * kLog2e;
   bp.c2 = exponent_shift(p, a->attn_bias != nullptr) * kLog2e;
@@ -624,4 +710,4 @@ int fcsa_backward(const fcsa_backward_args* a) {
   return FCSA_OK;
 }
 
-}  // extern "C"
+}  // namespace

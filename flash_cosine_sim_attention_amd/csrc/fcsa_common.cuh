@@ -913,6 +913,66 @@ FCSA_DEV void finish_q_frags(const FwdParams& p, int b, int h, int i, const Frag
   }
 }
 
+// ---- packed variable-length sequences (SeqTable, fcsa_kernels.h) ---------------------------------------------------------------------
+// A varlen launch is the dense grid for (B = sequences, N / M = the longest spans).  Right after block_work, the workgroup of
+// (sequence s, head h) = bh reads cu[s], cu[s + 1] of both tables (scalar loads), clamps them (seq_span) and rebinds its parameter block
+// to that span: the views start at the span's first row, the per-row buffers ([1, H, total, ...]) at row (h, first row) -- shifted so that
+// the dense index (b * H + h) * N + i with b = 0 and N = the span length lands there -- and B = 1, N / M = the span lengths, bh = h.  The
+// kernel then runs its dense code on one (1, H, N_s, M_s) problem.  Returns false when the workgroup's pair index lies beyond its own
+// sequence's tile pairs (`tile` positions per tile; `by_keys`: the dK/dV grid of key tiles): it has no work.
+FCSA_DEV void varlen_rebase(View& v, int first) {
+  v.p += (int64_t)first * v.sn;
+  v.sb = 0;
+}
+template <int D, int ES>
+FCSA_DEV bool varlen_bind(FwdParams& p, int& bh, int pair, int tile, int causal) {
+  const int s = bh / p.H, h = bh % p.H;
+  int q0, ns, k0, ms;
+  seq_span(p.seq.cu_q[s], p.seq.cu_q[s + 1], p.seq.total_q, p.N, q0, ns);
+  seq_span(p.seq.cu_k[s], p.seq.cu_k[s + 1], p.seq.total_k, p.M, k0, ms);
+  if (seq_pair_idle(pair, ns, tile, causal)) return false;
+  const int64_t qrow = (int64_t)h * (p.seq.total_q - ns) + q0;
+  varlen_rebase(p.q, q0);
+  varlen_rebase(p.o, q0);
+  varlen_rebase(p.k, k0);
+  varlen_rebase(p.v, k0);
+  if (p.inv_l != nullptr) p.inv_l += qrow;
+  if (p.qn_out != nullptr) p.qn_out += qrow * D * ES;
+  if (p.rq_out != nullptr) p.rq_out += qrow * p.G;
+  p.B = 1;
+  p.N = ns;
+  p.M = ms;
+  bh = h;
+  return true;
+}
+template <int D, int ES>
+FCSA_DEV bool varlen_bind(BwdParams& p, int& bh, int pair, int tile, int causal, bool by_keys) {
+  const int s = bh / p.H, h = bh % p.H, hk = h / p.kv_group;
+  int q0, ns, k0, ms;
+  seq_span(p.seq.cu_q[s], p.seq.cu_q[s + 1], p.seq.total_q, p.N, q0, ns);
+  seq_span(p.seq.cu_k[s], p.seq.cu_k[s + 1], p.seq.total_k, p.M, k0, ms);
+  if (seq_pair_idle(pair, by_keys ? ms : ns, tile, causal)) return false;
+  const int64_t qrow = (int64_t)h * (p.seq.total_q - ns) + q0;
+  const int64_t krow = (int64_t)hk * (p.seq.total_k - ms) + k0;
+  varlen_rebase(p.q, q0);
+  varlen_rebase(p.o, q0);
+  varlen_rebase(p.d_out, q0);
+  varlen_rebase(p.dq, q0);
+  varlen_rebase(p.k, k0);
+  varlen_rebase(p.v, k0);
+  varlen_rebase(p.dk, k0);
+  varlen_rebase(p.dv, k0);
+  p.inv_l += qrow;
+  p.delta += qrow;
+  if (p.rq != nullptr) p.rq += qrow * p.G;
+  if (p.rk != nullptr) p.rk += krow * p.G;
+  p.B = 1;
+  p.N = ns;
+  p.M = ms;
+  bh = h;
+  return true;
+}
+
 template <typename T, int D>
 FCSA_DEV void load_q_frags(const FwdParams& p, int b, int h, int i, const FragAddr<T, D>& fa,
                            u32x4 (&qf)[TileGeom<D, Traits<T>::ES>::KS]) {

@@ -117,6 +117,20 @@ constexpr void query_split_causal(int tiles, int first, int split, int splits, i
   hi = std::min(lo + tps, tiles);
 }
 
+// Variable-length launches (packed sequences, fcsa_forward_varlen / fcsa_backward_varlen): sequence s owns the packed rows
+// [cu[s], cu[s + 1]).  The grid is the dense one for (batch = sequences, len = max_len); each workgroup reads its sequence's two table
+// entries and works on that span.  The span is clamped so that ANY table contents stay inside the `total` packed rows: a malformed table
+// gives wrong rows, never an access outside the tensors.  lo / hi are the raw entries cu[s], cu[s + 1].
+constexpr void seq_span(int64_t lo, int64_t hi, int total, int max_len, int& start, int& len) {
+  const int64_t st = std::min(std::max(lo, (int64_t)0), (int64_t)total);
+  const int64_t en = std::min(std::max(hi, st), (int64_t)total);
+  start = (int)st;
+  len = (int)std::min(en - st, (int64_t)std::max(max_len, 0));
+}
+// A workgroup of a variable-length launch whose pair index lies beyond its own sequence's tile pairs (the grid is sized by the longest
+// sequence) has no work and exits at once
+constexpr bool seq_pair_idle(int pair, int len, int tile, int causal) { return pair >= tile_pairs(tile_count(len, tile), causal); }
+
 // workgroups of `tile`-position tiles over `len` positions for `batch_heads` (batch x heads)
 inline int64_t tile_workgroups(int64_t batch_heads, int len, int tile, bool causal) {
   return batch_heads * tile_pairs(tile_count(len, tile), causal);
@@ -163,6 +177,7 @@ struct FwdProblem {
   int splits;
   int64_t q_row_bytes, k_row_bytes, v_row_bytes;      // row strides of q, k, v (the 32-bit offsets of fwd3)
   int wide128_mode;                                   // fcsa_debug_forward_form: 0 = never fwd3
+  bool varlen = false;                                // packed sequences (seq_span): no Fwd2 / Fwd3, no key split
 };
 
 // fwd3_kernel (fcsa_fwd3.hip): 16-bit D = 128, static exponent shift, no bias, no key mask, no key split, a grid of 256-row (causal: paired)
@@ -198,8 +213,10 @@ inline bool fwd2_applies(const FwdProblem& f) {
 // FCSA_KSPLIT = 0 / 1 forces the key-split form off / on where it is compiled.
 inline FwdForm choose_forward(const FwdProblem& f, int cus) {
   const int env = sweep_env("FCSA_FWD_FORM"), env_ks = sweep_env("FCSA_KSPLIT");
-  const bool plain = !f.bias && !f.mask && !f.dyn && f.splits <= 1;
-  if (env > 0) {
+  const bool plain = !f.bias && !f.mask && !f.dyn && f.splits <= 1 && !f.varlen;
+  if (f.varlen) {
+    // packed sequences: the 32-rows-per-wave forms only, the same rules (the caller never splits them: f.splits == 1)
+  } else if (env > 0) {
     if (env == 5 && f.D == 128 && f.es == 2 && plain) return FwdForm::Fwd3;
     if (env == 4 && fwd2_compiled(f.es, f.D) && plain) return FwdForm::Fwd2;
   } else {
@@ -227,12 +244,13 @@ struct BwdProblem {
   bool causal, bias;
   int splits;           // dq_splits / dkv_splits of the launch
   bool kv_sweep;        // the dK/dV launch runs the group sweep (dkv_sweep below, decided by the C ABI)
+  bool varlen = false;  // packed sequences (seq_span): never a split form or the group sweep
 };
 
 // Sweep builds: FCSA_DQ_FORM = 1 row tiles of 8 waves (16-bit D = 96 / 128: four waves, two-wave tile), 2 key-split 8 waves (D = 96 / 128:
 // causal only), 3 four waves
 inline DqForm choose_dq(const BwdProblem& b, int cus) {
-  if (b.splits > 1) return DqForm::Waves4;       // split-key path: 128-row tiles x key ranges (the key-split form measured level there)
+  if (b.splits > 1 && !b.varlen) return DqForm::Waves4;       // split-key path: 128-row tiles x key ranges (the key-split form measured level there)
   const bool narrow = b.D * b.es <= kDq2WBytes, two = dq_can_two_waves(b.es, b.D) && !b.bias;
   if (const int env = sweep_env("FCSA_DQ_FORM"); bwd_ksplit(b.es, b.D, b.bias) && (narrow || two)) {
     if (env == 1) return narrow ? DqForm::Waves8 : DqForm::Waves4Two;
@@ -267,8 +285,8 @@ inline bool dkv_sweep(int es, int D, int64_t batch_kv_heads, int M, bool causal,
 
 // Sweep builds: FCSA_DKV_FORM = 1 key tiles of 8 waves (16-bit D = 96 / 128: lean), 2 query-split 8 waves (D <= 64), 3 four waves
 inline DkvForm choose_dkv(const BwdProblem& b, int cus) {
-  if (b.kv_sweep) return DkvForm::Sweep;
-  if (b.splits > 1) return DkvForm::Waves4;      // split-query path: 128-key tiles x query ranges
+  if (b.kv_sweep && !b.varlen) return DkvForm::Sweep;
+  if (b.splits > 1 && !b.varlen) return DkvForm::Waves4;      // split-query path: 128-key tiles x query ranges
   const bool narrow = b.D * b.es <= kDkv2WBytes, lean = b.es == 2 && !b.bias && !narrow && b.D * b.es <= 256;
   if (const int env = sweep_env("FCSA_DKV_FORM"); (narrow && bwd_ksplit(b.es, b.D, b.bias)) || lean) {
     if (env == 1) return narrow ? DkvForm::Waves8 : DkvForm::Lean8;

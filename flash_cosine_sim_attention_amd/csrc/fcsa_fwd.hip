@@ -456,7 +456,8 @@ template <typename T, int D, int NW, bool DYN, bool KSPLIT> struct FwdLds {
 // SIMD whatever the grid) are one wave per SIMD; this form keeps the grid and doubles the waves, and the partner wave hides what the
 // lean form does not prefetch.
 template <typename T, int D, int NW, bool BIAS, bool DYN, bool LEAN, bool KM, bool KSPLIT = false>
-__global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ? 2 : 1)) fwd_kernel(const FwdParams p) {
+__global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ? 2 : 1)) fwd_kernel(const FwdParams p_) {
+  FwdParams p = p_;      // a varlen launch rebinds it to the workgroup's sequence (varlen_bind); dense launches use it as given
   static_assert(!KSPLIT || (NW == 8 && (LEAN != BIAS) && Traits<T>::ES == 2), "key-split form: 8 waves, 16 bit; lean tile, or the generic tile with a bias");
   const int causal = KM ? 0 : p.causal;      // (same type and value as p.causal: the causal instantiations compile to what they were)
   typedef TileGeom<D, Traits<T>::ES> G;
@@ -475,9 +476,10 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ?
   fa.init(lane);
 
   // a pair of row tiles per workgroup under causal masking (tile_pairs, fcsa_dispatch.h)
-  const int MT = tile_count(p.N, BM), PT = tile_pairs(MT, causal);
   int bh, pt;
-  block_work(blockIdx.x, p.B * p.H, PT, bh, pt);
+  block_work(blockIdx.x, p.B * p.H, tile_pairs(tile_count(p.N, BM), causal), bh, pt);
+  if (p.seq.cu_q != nullptr && !varlen_bind<D, Traits<T>::ES>(p, bh, pt, BM, causal)) return;
+  const int MT = tile_count(p.N, BM);
   const int b = bh / p.H, h = bh % p.H;
   const int npass = pair_passes(MT, pt, causal);
   // split-key launches (gridDim.y = p.splits > 1, never bias / dynamic shift): this workgroup sees the keys [k_lo, k_lo + Mk) only and
@@ -1234,7 +1236,7 @@ static hipError_t launch_fwd_form(FwdForm f, const FwdParams& p, hipStream_t s) 
 hipError_t launch_forward(int dtype, int D, const FwdParams& p, hipStream_t s) {
   if (p.B * p.H == 0 || p.N == 0) return hipSuccess;
   const FwdProblem fp = {dtype == 0 ? 4 : 2, D, (int64_t)p.B * p.H, p.N, p.M, p.causal != 0, p.bias != nullptr, p.mask != nullptr, p.dyn != 0,
-                         p.splits, p.q.sn, p.k.sn, p.v.sn, forward_wide128_mode(-1)};
+                         p.splits, p.q.sn, p.k.sn, p.v.sn, forward_wide128_mode(-1), p.seq.cu_q != nullptr};
   const FwdForm f = choose_forward(fp, cu_count());
   if (f == FwdForm::Fwd3) return launch_forward_wide128(dtype, p, s);
   return dispatch_dtype_d(dtype, D, [&](auto td) {

@@ -14,6 +14,15 @@ struct View {
   int64_t sb, sh, sn;
 };
 
+// Packed variable-length sequences (fcsa_forward_varlen / fcsa_backward_varlen), or all null for a dense launch.  A varlen launch has
+// B = sequences, N / M = the longest query / key span, views whose sb is ignored and per-row buffers laid out [1, H, total, ...]; each
+// workgroup binds itself to its sequence's span first (varlen_bind, fcsa_common.cuh) and then runs the dense code on it.
+struct SeqTable {
+  const int32_t* cu_q;      // [B + 1] device, or nullptr: dense launch
+  const int32_t* cu_k;      // [B + 1] device
+  int total_q, total_k;     // packed rows of q (o, dq, ...) and of k (v, dk, ...)
+};
+
 struct FwdParams {
   View q, k, v, o;          // q,k: already normalised (or raw when !l2norm)
   float* inv_l;             // [B,H,N] or nullptr; dyn: log2(1 / sum_j exp(S_ij)), else 1 / max(rowsum, l_eps)
@@ -37,6 +46,7 @@ struct FwdParams {
   int splits;               // > 1: the key range is split over gridDim.y workgroups that write un-normalised partials
   float* ws_o;              // [splits][B*H][N][D] f32 partial P~V
   float* ws_l;              // [splits][B*H][N]    f32 partial row sums
+  SeqTable seq;             // packed sequences (seq.cu_q != nullptr): no split, no bias, no key mask
 };
 
 struct BwdParams {
@@ -67,6 +77,7 @@ struct BwdParams {
   const float* rk;          // [B,Hk,M,G] inverse norms of k, or nullptr (set for Hk == H and for the group sweep only)
   int G, lgm;               // groups; log2(group size / 8)
   float norm_eps;           // 1e-12
+  SeqTable seq;             // packed sequences (seq.cu_q != nullptr): no split, no bias, no key mask, no group sweep
 };
 
 struct NormParams {         // grouped l2norm forward:  x -> xn, inv_norm

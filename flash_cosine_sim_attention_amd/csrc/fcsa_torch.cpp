@@ -32,6 +32,10 @@ struct Abi {
   size_t (*backward_ws)(const fcsa_problem*) = &fcsa_backward_workspace_bytes;
   int (*needs_qn)(const fcsa_problem*, int32_t) = &fcsa_forward_needs_qn;
   const char* (*last_error)(void) = &fcsa_last_error;
+  // packed sequences: null when a library swapped in by fcsa_torch_use_library does not export them (the varlen ops then raise)
+  int (*forward_varlen)(const fcsa_forward_args*, const fcsa_varlen*) = &fcsa_forward_varlen;
+  int (*backward_varlen)(const fcsa_backward_args*, const fcsa_varlen*) = &fcsa_backward_varlen;
+  size_t (*backward_varlen_ws)(const fcsa_problem*, const fcsa_varlen*) = &fcsa_backward_varlen_workspace_bytes;
 } g_abi;
 
 using at::Tensor;
@@ -277,6 +281,174 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> backward(const Tensor& d_out, const T
   return std::make_tuple(dq.reshape(q.sizes()), dk.reshape(k.sizes()), dv.reshape(v.sizes()), db);
 }
 
+
+// ---- packed variable-length sequences (fcsa_forward_varlen / fcsa_backward_varlen) ----------------------------------------------------
+// q [total_q, H, D], k / v [total_k, Hk, D], cu_seqlens_* int32 [S + 1] on q's device.  The tables are passed to the library as they are:
+// their contents are never read on the host (the Python wrapper validates host tables before they are moved to the device).
+struct VCanon {
+  Tensor q, k, v, cu_q, cu_k;     // rows ok; tables contiguous
+  int64_t S, H, Hk, TQ, TK, D;
+};
+
+VCanon canonicalise_varlen(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q, const Tensor& cu_k, int64_t max_q,
+                           int64_t max_k) {
+  TORCH_CHECK(q.is_cuda(), "flash_cosine_sim_attention_varlen: q, k, v must be GPU tensors (HIP kernels only, no CPU fallback)");
+  for (const auto& [name, t] : {std::pair<const char*, const Tensor*>{"k", &k}, {"v", &v}, {"cu_seqlens_q", &cu_q}, {"cu_seqlens_k", &cu_k}})
+    TORCH_CHECK_VALUE(t->device() == q.device(), name, " is on ", t->device(), " but q is on ", q.device(), ": all tensors must live on q's GPU");
+  TORCH_CHECK_TYPE(q.scalar_type() == k.scalar_type() && q.scalar_type() == v.scalar_type(), "q, k, v must share a dtype, got ",
+                   q.scalar_type(), ", ", k.scalar_type(), ", ", v.scalar_type());
+  dtype_code(q.scalar_type());
+  TORCH_CHECK_VALUE(q.dim() == 3 && k.dim() == 3 && v.dim() == 3, "varlen: q, k, v must be packed [total, heads, dim_head] tensors");
+  TORCH_CHECK_VALUE(v.sizes() == k.sizes(), "k and v must have the same shape, got ", k.sizes(), " and ", v.sizes());
+  TORCH_CHECK_TYPE(cu_q.scalar_type() == at::kInt && cu_k.scalar_type() == at::kInt, "cu_seqlens_q / cu_seqlens_k must be int32");
+  TORCH_CHECK_VALUE(cu_q.dim() == 1 && cu_k.dim() == 1 && cu_q.numel() >= 1 && cu_q.numel() == cu_k.numel(),
+                    "cu_seqlens_q and cu_seqlens_k must be 1-D of the same length (sequences + 1), got ", cu_q.sizes(), " and ", cu_k.sizes());
+  VCanon c;
+  c.S = cu_q.numel() - 1;
+  c.TQ = q.size(0); c.H = q.size(1); c.D = q.size(2);
+  c.TK = k.size(0); c.Hk = k.size(1);
+  TORCH_CHECK_VALUE(k.size(2) == c.D, "query, key, value dimensions must be the same");
+  TORCH_CHECK_VALUE(c.D == 16 || c.D == 32 || c.D == 64 || c.D == 96 || c.D == 128,
+                    "only dimensions (16, 32, 64, 96, 128) allowed for now, got ", c.D);
+  TORCH_CHECK_VALUE(c.Hk >= 1 && c.H % c.Hk == 0, "k/v heads must divide q heads (", c.H, "), got ", c.Hk);
+  TORCH_CHECK_VALUE(max_q >= 0 && max_k >= 0 && max_q <= INT32_MAX && max_k <= INT32_MAX && c.S <= INT32_MAX,
+                    "max_seqlen_q / max_seqlen_k must lie in [0, 2^31), got ", max_q, ", ", max_k);
+  TORCH_CHECK_VALUE(c.H * std::max(c.TQ, c.TK) <= INT32_MAX, "varlen: heads x packed rows must stay below 2^31");
+  c.q = prep(q); c.k = prep(k); c.v = prep(v);
+  c.cu_q = cu_q.contiguous(); c.cu_k = cu_k.contiguous();
+  return c;
+}
+
+fcsa_problem varlen_problem(const VCanon& c, at::ScalarType dt, int64_t max_q, int64_t max_k, bool causal, bool l2norm_qk, int64_t groups,
+                            double scale) {
+  fcsa_problem p;
+  p.dtype = dtype_code(dt);
+  p.batch = (int32_t)c.S; p.heads = (int32_t)c.H; p.kv_heads = (int32_t)c.Hk;
+  p.q_len = (int32_t)max_q; p.k_len = (int32_t)max_k; p.dim_head = (int32_t)c.D;
+  p.causal = causal; p.bias_batch_dim = 0; p.l2norm_qk = l2norm_qk;
+  p.groups = l2norm_qk ? (int32_t)groups : 1;
+  p.scale = (float)scale;
+  return p;
+}
+
+fcsa_varlen varlen_table(const VCanon& c) {
+  fcsa_varlen t;
+  t.cu_seqlens_q = c.cu_q.data_ptr<int32_t>();
+  t.cu_seqlens_k = c.cu_k.data_ptr<int32_t>();
+  t.total_q = c.TQ; t.total_k = c.TK;
+  return t;
+}
+
+// packed [total, heads, D] -> the ABI's view: stride0 ignored, stride1 = head stride, stride2 = token stride
+fcsa_tensor packed3(const Tensor& t) {
+  fcsa_tensor v;
+  v.ptr = t.data_ptr();
+  v.stride0 = 0;
+  v.stride1 = t.stride(1);
+  v.stride2 = t.stride(0);
+  return v;
+}
+
+void need_varlen_abi() {
+  TORCH_CHECK(g_abi.forward_varlen != nullptr && g_abi.backward_varlen != nullptr && g_abi.backward_varlen_ws != nullptr,
+              "flash_cosine_sim_attention_varlen: the loaded libfcsa_hip.so does not export fcsa_forward_varlen / fcsa_backward_varlen");
+}
+
+// (o, inv_l, qn, kn, rq, rk): o [total_q, H, D]; inv_l [H, total_q]; qn [H, total_q, D], kn [Hk, total_k, D], rq / rk [.., G]; empty where
+// not produced
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> varlen_forward(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q,
+                                                                           const Tensor& cu_k, int64_t max_q, int64_t max_k, double scale,
+                                                                           bool causal, bool l2norm_qk, int64_t groups, bool need_backward) {
+  need_varlen_abi();
+  const VCanon c = canonicalise_varlen(q, k, v, cu_q, cu_k, max_q, max_k);
+  TORCH_CHECK_VALUE(!l2norm_qk || (groups >= 1 && c.D % groups == 0), "groups (", groups, ") must divide the head dimension (", c.D, ")");
+  c10::DeviceGuard guard(q.device());
+  const auto opt = q.options();
+  const auto f32 = opt.dtype(at::kFloat);
+  fcsa_forward_args a;
+  a.p = varlen_problem(c, q.scalar_type(), max_q, max_k, causal, l2norm_qk, groups, scale);
+  const fcsa_varlen t = varlen_table(c);
+  Tensor o = at::empty({c.TQ, c.H, c.D}, opt);
+  Tensor none = at::empty({0}, f32);
+  Tensor inv_l = need_backward ? at::empty({c.H, c.TQ}, f32) : none;
+  Tensor qn = at::empty({0}, opt), kn = qn, rq = none, rk = none;
+  if (l2norm_qk) {
+    fcsa_problem pp = a.p;      // fcsa_forward_needs_qn of the packed rows (batch 1, q_len = total_q)
+    pp.batch = 1; pp.q_len = (int32_t)c.TQ; pp.k_len = (int32_t)c.TK;
+    if (g_abi.needs_qn(&pp, need_backward ? 1 : 0) != 0) qn = at::empty({c.H, c.TQ, c.D}, opt);
+    kn = at::empty({c.Hk, c.TK, c.D}, opt);
+    if (need_backward) {
+      rq = at::empty({c.H, c.TQ, groups}, f32);
+      rk = at::empty({c.Hk, c.TK, groups}, f32);
+    }
+  }
+  a.q = packed3(c.q); a.k = packed3(c.k); a.v = packed3(c.v); a.o = packed3(o);
+  a.inv_l = need_backward ? inv_l.data_ptr<float>() : nullptr;
+  a.mask = nullptr;
+  a.attn_bias = nullptr;
+  a.norm.qn = qn.numel() > 0 ? qn.data_ptr() : nullptr;
+  a.norm.kn = (l2norm_qk && kn.numel() > 0) ? kn.data_ptr() : nullptr;
+  a.norm.rq = (l2norm_qk && need_backward) ? rq.data_ptr<float>() : nullptr;
+  a.norm.rk = (l2norm_qk && need_backward) ? rk.data_ptr<float>() : nullptr;
+  a.workspace = nullptr; a.workspace_bytes = 0;      // packed sequences never split the key range
+  a.stream = stream_of(q);
+  check(g_abi.forward_varlen(&a, &t), "fcsa_forward_varlen");
+  return std::make_tuple(o, inv_l, qn, kn, rq, rk);
+}
+
+// (dq, dk, dv) shaped like q, k, v
+std::tuple<Tensor, Tensor, Tensor> varlen_backward(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k,
+                                                   const Tensor& v, const Tensor& cu_q, const Tensor& cu_k, const Tensor& qn, const Tensor& kn,
+                                                   const Tensor& rq, const Tensor& rk, int64_t max_q, int64_t max_k, double scale, bool causal,
+                                                   bool l2norm_qk, int64_t groups) {
+  need_varlen_abi();
+  const VCanon c = canonicalise_varlen(q, k, v, cu_q, cu_k, max_q, max_k);
+  c10::DeviceGuard guard(q.device());
+  const auto opt = q.options();
+  Tensor o3 = prep(o);
+  Tensor do3 = d_out.scalar_type() != q.scalar_type() ? d_out.to(q.scalar_type()) : d_out;
+  do3 = prep(do3);
+  TORCH_CHECK_VALUE(o3.dim() == 3 && o3.size(0) == c.TQ && o3.size(1) == c.H && o3.size(2) == c.D, "o does not belong to these inputs");
+  TORCH_CHECK_VALUE(do3.sizes() == o3.sizes(), "d_out must have the shape of the output");
+  TORCH_CHECK_TYPE(o3.scalar_type() == q.scalar_type() && o3.device() == q.device(), "o must have the dtype and device of q");
+  TORCH_CHECK_VALUE(do3.device() == q.device(), "d_out is on ", do3.device(), " but q is on ", q.device());
+  auto saved_ok = [&](const char* name, const Tensor& t, at::ScalarType st, int64_t numel) {
+    TORCH_CHECK_VALUE(t.defined() && t.device() == q.device() && t.scalar_type() == st && t.numel() == numel && t.is_contiguous(),
+                      name, " does not belong to these inputs (expected a contiguous ", st, " tensor of ", numel, " elements on ", q.device(), ")");
+  };
+  saved_ok("inv_l", inv_l, at::kFloat, c.H * c.TQ);
+  if (l2norm_qk) {
+    saved_ok("qn", qn, q.scalar_type(), c.H * c.TQ * c.D);
+    saved_ok("kn", kn, q.scalar_type(), c.Hk * c.TK * c.D);
+    saved_ok("rq", rq, at::kFloat, c.H * c.TQ * groups);
+    saved_ok("rk", rk, at::kFloat, c.Hk * c.TK * groups);
+  }
+  Tensor dq = at::empty({c.TQ, c.H, c.D}, opt);
+  Tensor dk = at::empty({c.TK, c.Hk, c.D}, opt);
+  Tensor dv = at::empty({c.TK, c.Hk, c.D}, opt);
+  fcsa_backward_args a;
+  a.p = varlen_problem(c, q.scalar_type(), max_q, max_k, causal, l2norm_qk, groups, scale);
+  const fcsa_varlen t = varlen_table(c);
+  size_t wsb = g_abi.backward_varlen_ws(&a.p, &t);
+  if (wsb < 256) wsb = 256;
+  Tensor ws = at::empty({(int64_t)wsb}, opt.dtype(at::kByte));      // the caching allocator
+  a.d_out = packed3(do3); a.o = packed3(o3);
+  a.inv_l = inv_l.numel() > 0 ? inv_l.data_ptr<float>() : nullptr;
+  a.q = packed3(c.q); a.k = packed3(c.k); a.v = packed3(c.v);
+  a.mask = nullptr;
+  a.attn_bias = nullptr;
+  a.norm.qn = (l2norm_qk && qn.numel() > 0) ? qn.data_ptr() : nullptr;
+  a.norm.kn = (l2norm_qk && kn.numel() > 0) ? kn.data_ptr() : nullptr;
+  a.norm.rq = (l2norm_qk && rq.numel() > 0) ? rq.data_ptr<float>() : nullptr;
+  a.norm.rk = (l2norm_qk && rk.numel() > 0) ? rk.data_ptr<float>() : nullptr;
+  a.dq = packed3(dq); a.dk = packed3(dk); a.dv = packed3(dv);
+  a.d_bias = nullptr;
+  a.workspace = ws.data_ptr(); a.workspace_bytes = wsb;
+  a.stream = stream_of(q);
+  check(g_abi.backward_varlen(&a, &t), "fcsa_backward_varlen");
+  return std::make_tuple(dq, dk, dv);
+}
+
 // ---- autograd in C++ (reference: the Python autograd.Function FlashCosineSimAttention, flash_cosine_sim_attention.py:245-302).
 // A Python Function costs ~60 us of interpreter / engine hand-over per forward+backward; this node costs a few.  forward and
 // backward go through the dispatcher (fcsa::forward / fcsa::backward), so torch.compile traces them with the fake kernels.
@@ -344,6 +516,54 @@ Tensor attention_plain(const Tensor& q, const Tensor& k, const Tensor& v, const 
   return std::get<0>(forward(q, k, v, mask, attn_bias, attn_bias_batch_dim, scale, causal, l2norm_qk, groups, false));
 }
 
+
+// the differentiable varlen op: the same node pattern as AttentionFn, over fcsa::varlen_forward / fcsa::varlen_backward
+struct VarlenAttentionFn : public torch::autograd::Function<VarlenAttentionFn> {
+  static Tensor forward(AutogradContext* ctx, const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q, const Tensor& cu_k,
+                        int64_t max_q, int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("fcsa::varlen_forward", "")
+        .typed<std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, const Tensor&,
+                                                                           const Tensor&, int64_t, int64_t, double, bool, bool, int64_t, bool)>();
+    auto r = op.call(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, true);
+    ctx->save_for_backward({std::get<0>(r), std::get<1>(r), q, k, v, cu_q, cu_k, std::get<2>(r), std::get<3>(r), std::get<4>(r), std::get<5>(r)});
+    ctx->saved_data["max_q"] = max_q;
+    ctx->saved_data["max_k"] = max_k;
+    ctx->saved_data["scale"] = scale;
+    ctx->saved_data["causal"] = causal;
+    ctx->saved_data["l2norm_qk"] = l2norm_qk;
+    ctx->saved_data["groups"] = groups;
+    return std::get<0>(r);
+  }
+
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    const auto s = ctx->get_saved_variables();
+    static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("fcsa::varlen_backward", "")
+        .typed<std::tuple<Tensor, Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
+                                                  const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
+                                                  int64_t, int64_t, double, bool, bool, int64_t)>();
+    auto g = op.call(grads[0], s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8], s[9], s[10], ctx->saved_data["max_q"].toInt(),
+                     ctx->saved_data["max_k"].toInt(), ctx->saved_data["scale"].toDouble(), ctx->saved_data["causal"].toBool(),
+                     ctx->saved_data["l2norm_qk"].toBool(), ctx->saved_data["groups"].toInt());
+    return {std::get<0>(g), std::get<1>(g), std::get<2>(g), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+  }
+};
+
+Tensor varlen_attention_autograd(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q, const Tensor& cu_k, int64_t max_q,
+                                 int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups) {
+  const bool tracked = at::GradMode::is_enabled() && (q.requires_grad() || k.requires_grad() || v.requires_grad());
+  if (!tracked) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    return std::get<0>(varlen_forward(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, false));
+  }
+  return VarlenAttentionFn::apply(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups);
+}
+
+Tensor varlen_attention_plain(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q, const Tensor& cu_k, int64_t max_q,
+                              int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups) {
+  return std::get<0>(varlen_forward(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, false));
+}
+
 }  // namespace
 
 // Measurement hook: read (and reset) the host-time counters above.
@@ -362,6 +582,10 @@ extern "C" int fcsa_torch_use_library(const char* path) {
   a.backward_ws = reinterpret_cast<decltype(a.backward_ws)>(dlsym(h, "fcsa_backward_workspace_bytes"));
   a.needs_qn = reinterpret_cast<decltype(a.needs_qn)>(dlsym(h, "fcsa_forward_needs_qn"));
   a.last_error = reinterpret_cast<decltype(a.last_error)>(dlsym(h, "fcsa_last_error"));
+  // optional: a build without packed-sequence support leaves them null, and only the varlen ops refuse to run
+  a.forward_varlen = reinterpret_cast<decltype(a.forward_varlen)>(dlsym(h, "fcsa_forward_varlen"));
+  a.backward_varlen = reinterpret_cast<decltype(a.backward_varlen)>(dlsym(h, "fcsa_backward_varlen"));
+  a.backward_varlen_ws = reinterpret_cast<decltype(a.backward_varlen_ws)>(dlsym(h, "fcsa_backward_varlen_workspace_bytes"));
   if (!a.forward || !a.backward || !a.forward_ws || !a.backward_ws || !a.needs_qn || !a.last_error) { dlclose(h); return -2; }
   // Only libraries of THIS ABI: the binding allocates for the struct layouts and buffer contracts of include/fcsa.h as compiled in
   // (e.g. ABI 3 writes d_bias once in the bias dtype into an uninitialised buffer; an ABI-2 library would accumulate float32 into
@@ -381,14 +605,26 @@ TORCH_LIBRARY(fcsa, m) {
   // the operator itself: differentiable w.r.t. q, k, v, attn_bias (Autograd kernel below)
   m.def("attention(Tensor q, Tensor k, Tensor v, Tensor? mask, Tensor? attn_bias, bool attn_bias_batch_dim, float scale, bool causal, "
         "bool l2norm_qk, int groups) -> Tensor");
+  // packed variable-length sequences (cu_seqlens): q [total_q, H, D], k / v [total_k, Hk, D]
+  m.def("varlen_forward(Tensor q, Tensor k, Tensor v, Tensor cu_seqlens_q, Tensor cu_seqlens_k, int max_seqlen_q, int max_seqlen_k, "
+        "float scale, bool causal, bool l2norm_qk, int groups, bool need_backward) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("varlen_backward(Tensor d_out, Tensor o, Tensor inv_l, Tensor q, Tensor k, Tensor v, Tensor cu_seqlens_q, Tensor cu_seqlens_k, "
+        "Tensor qn, Tensor kn, Tensor rq, Tensor rk, int max_seqlen_q, int max_seqlen_k, float scale, bool causal, bool l2norm_qk, "
+        "int groups) -> (Tensor, Tensor, Tensor)");
+  m.def("varlen_attention(Tensor q, Tensor k, Tensor v, Tensor cu_seqlens_q, Tensor cu_seqlens_k, int max_seqlen_q, int max_seqlen_k, "
+        "float scale, bool causal, bool l2norm_qk, int groups) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(fcsa, CUDA, m) {       // ROCm builds of PyTorch dispatch HIP tensors under the CUDA key
   m.impl("forward", &forward);
   m.impl("backward", &backward);
   m.impl("attention", &attention_plain);
+  m.impl("varlen_forward", &varlen_forward);
+  m.impl("varlen_backward", &varlen_backward);
+  m.impl("varlen_attention", &varlen_attention_plain);
 }
 
 TORCH_LIBRARY_IMPL(fcsa, Autograd, m) {
   m.impl("attention", &attention_autograd);
+  m.impl("varlen_attention", &varlen_attention_autograd);
 }

@@ -143,3 +143,76 @@ def flash_cosine_sim_attention(q, k, v, mask=None, attn_bias=None, scale=8, grou
     # the differentiable dispatcher op: autograd node, checks, allocation and launches all in C++ (csrc/fcsa_torch.cpp)
     return _torch_ops.load().attention(q, k, v, mask, attn_bias, bool(attn_bias_batch_dim), float(scale), bool(causal),
                                        bool(l2norm_qk), int(groups))
+
+
+# ---------------------------------------------------------------------------------------------
+# packed variable-length sequences (the flash-attn cu_seqlens convention; no reference counterpart)
+# ---------------------------------------------------------------------------------------------
+
+def _check_host_cu(name, cu, total, max_len):
+    """Full validation of a HOST table: cu[0] == 0, non-decreasing, cu[-1] == total, every span <= max_len (when given)."""
+    c = cu.tolist()
+    if c[0] != 0 or c[-1] != total:
+        raise ValueError(f"{name} must start at 0 and end at the packed length {total}, got {c[0]} ... {c[-1]}")
+    lens = [b - a for a, b in zip(c[:-1], c[1:])]
+    if any(n < 0 for n in lens):
+        raise ValueError(f"{name} must be non-decreasing")
+    longest = max(lens, default=0)
+    if max_len is not None and longest > max_len:
+        raise ValueError(f"{name}: a sequence of {longest} rows is longer than max_seqlen = {max_len}")
+    return longest
+
+
+def flash_cosine_sim_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, scale=8, groups=1,
+                                      causal=False, l2norm_qk=True):
+    """Fused cosine-similarity attention over packed variable-length sequences.
+
+    q [total_q, H, D] and k, v [total_k, Hk, D] (Hk dividing H) hold S sequences back to back; sequence s owns the query rows
+    [cu_seqlens_q[s], cu_seqlens_q[s + 1]) and the key rows [cu_seqlens_k[s], cu_seqlens_k[s + 1]) (int32 tables of S + 1 entries).
+    Each sequence's output rows are what `flash_cosine_sim_attention` returns for that sequence alone as a [1, H, N_s, D] problem
+    (causal alignment per sequence, rows without a visible key give 0).  Returns o shaped like q; differentiable w.r.t. q, k, v.
+    There is no mask or attn_bias.
+
+    Tables on the host are validated fully (and copied to q's device); tables already on the device are trusted, as in flash-attn --
+    a malformed device table gives wrong rows, never an access outside the tensors.  max_seqlen_q / max_seqlen_k must be at least
+    the longest span: the launch grid is sized by them.  When None they are computed from the tables, which synchronises the device
+    when the tables live there.  CPU tensors take the forward-only path of `cpu.py`, one dense CPU call per sequence."""
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.dim() != 3:
+            raise ValueError(f"{name} must be a packed [total, heads, dim_head] tensor, got {tuple(t.shape)}")
+    if k.shape != v.shape:
+        raise ValueError(f"k and v must have the same shape, got {tuple(k.shape)} and {tuple(v.shape)}")
+    if q.shape[2] != k.shape[2]:
+        raise ValueError("query, key, value dimensions must be the same")
+    if not (q.dtype == k.dtype == v.dtype) or q.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise TypeError(f"q, k, v must share one of float32, float16, bfloat16, got {q.dtype}, {k.dtype}, {v.dtype}")
+    if k.shape[1] < 1 or q.shape[1] % k.shape[1]:
+        raise ValueError(f"k/v heads must divide q heads ({q.shape[1]}), got {k.shape[1]}")
+    for name, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
+        if not isinstance(cu, torch.Tensor) or cu.dtype != torch.int32 or cu.dim() != 1 or cu.numel() < 1:
+            raise TypeError(f"{name} must be a 1-D int32 tensor of sequences + 1 entries")
+    if cu_seqlens_q.numel() != cu_seqlens_k.numel():
+        raise ValueError("cu_seqlens_q and cu_seqlens_k must have the same length (sequences + 1)")
+    for name, m in (("max_seqlen_q", max_seqlen_q), ("max_seqlen_k", max_seqlen_k)):
+        if m is not None and (int(m) != m or m < 0):
+            raise ValueError(f"{name} must be a non-negative integer, got {m}")
+    if cu_seqlens_q.device.type == "cpu":
+        longest = _check_host_cu("cu_seqlens_q", cu_seqlens_q, q.shape[0], max_seqlen_q)
+        max_seqlen_q = longest if max_seqlen_q is None else max_seqlen_q
+    if cu_seqlens_k.device.type == "cpu":
+        longest = _check_host_cu("cu_seqlens_k", cu_seqlens_k, k.shape[0], max_seqlen_k)
+        max_seqlen_k = longest if max_seqlen_k is None else max_seqlen_k
+    if q.device.type == "cpu":
+        if cu_seqlens_q.device.type != "cpu" or cu_seqlens_k.device.type != "cpu":
+            raise ValueError("CPU tensors take host cu_seqlens tables")
+        return _cpu.attention_forward_varlen_cpu(q, k, v, cu_seqlens_q, cu_seqlens_k, scale=scale, groups=groups, causal=causal,
+                                                 l2norm_qk=l2norm_qk)
+    # device tables are trusted; a max_seqlen left to us costs one device synchronisation per table
+    if max_seqlen_q is None:
+        max_seqlen_q = int((cu_seqlens_q[1:] - cu_seqlens_q[:-1]).max().item()) if cu_seqlens_q.numel() > 1 else 0
+    if max_seqlen_k is None:
+        max_seqlen_k = int((cu_seqlens_k[1:] - cu_seqlens_k[:-1]).max().item()) if cu_seqlens_k.numel() > 1 else 0
+    cu_q = cu_seqlens_q.to(q.device, non_blocking=True)
+    cu_k = cu_seqlens_k.to(q.device, non_blocking=True)
+    return _torch_ops.load().varlen_attention(q, k, v, cu_q, cu_k, int(max_seqlen_q), int(max_seqlen_k), float(scale), bool(causal),
+                                              bool(l2norm_qk), int(groups))

@@ -64,7 +64,7 @@ enum fcsa_dtype {
 /* A [d0, d1, d2, D] tensor view: element strides of the leading dims, last dim contiguous. */
 typedef struct fcsa_tensor {
   void*   ptr;
-  int64_t stride0;   /* batch */
+  int64_t stride0;   /* batch (ignored by the varlen entry points: packed tensors) */
   int64_t stride1;   /* head  (0 allowed: broadcast over heads, e.g. single-head kv) */
   int64_t stride2;   /* sequence position */
 } fcsa_tensor;
@@ -73,11 +73,11 @@ typedef struct fcsa_tensor {
  * forward_kernel / backward_kernel, cu:1072-1088, cu:1339-1360). */
 typedef struct fcsa_problem {
   int32_t dtype;            /* fcsa_dtype of q,k,v,o,grads,bias */
-  int32_t batch;            /* B */
+  int32_t batch;            /* B (varlen: sequences) */
   int32_t heads;            /* H */
   int32_t kv_heads;         /* Hk: a divisor of H (H, 1, or grouped-query K/V in between) */
-  int32_t q_len;            /* N */
-  int32_t k_len;            /* M */
+  int32_t q_len;            /* N (varlen: max_seqlen_q) */
+  int32_t k_len;            /* M (varlen: max_seqlen_k) */
   int32_t dim_head;         /* D in {16,32,64,96,128} (cu:84) */
   int32_t causal;           /* cu:1210: key j valid for query i iff j - (M - N) <= i */
   int32_t bias_batch_dim;   /* attn_bias leading dim is batch (1) or heads (0) (cu:1474) */
@@ -104,7 +104,7 @@ typedef struct fcsa_problem {
                                and strongly negative values underflow to an exact 0 weight, as in the reference. */
 } fcsa_problem;
 
-/* State the fused-l2norm forward saves for backward (all caller-allocated, contiguous):
+/* State the fused-l2norm forward saves for backward (all caller-allocated, contiguous; varlen: B = 1, N = total_q, M = total_k):
  *   qn [B,H,N,D], kn [B,Hk,M,D] in `dtype`  : normalised q, k (what the reference's autograd
  *        would have saved as the outputs of F.normalize)
  *   rq [B,H,N,G], rk [B,Hk,M,G] float32     : 1 / max(||x_group||, 1e-12)
@@ -116,6 +116,7 @@ typedef struct fcsa_norm_state {
   float* rk;
 } fcsa_norm_state;
 
+/* (fcsa_forward_varlen / fcsa_backward_varlen reuse the two structs below for packed sequences: see fcsa_varlen) */
 typedef struct fcsa_forward_args {
   fcsa_problem    p;
   fcsa_tensor     q, k, v;       /* inputs (borrowed, never written) */
@@ -155,7 +156,7 @@ typedef struct fcsa_backward_args {
                                     tiles of a bias slice, sums the broadcast index (batch or heads) in float32 registers
                                     and rounds once (reference: f32 atomicAdd per element into a zeroed f32 tensor,
                                     cu:1574-1576, then a cast pass, cu:1912).  No zero-fill, no cast needed. */
-  void*           workspace;     /* >= fcsa_backward_workspace_bytes(&p) bytes, 256-byte aligned: delta [B,H,N] f32, plus f32
+  void*           workspace;     /* >= fcsa_backward_workspace_bytes(&p) bytes (varlen: fcsa_backward_varlen_workspace_bytes), 256-byte aligned: delta [B,H,N] f32, plus f32
                                     slabs where an epilogue cannot finish the job -- partial dq of the split-key dQ kernel, partial
                                     dk / dv of the split-query dK/dV kernel and per-query-head dk / dv of K/V with fewer heads than
                                     the query (single-headed, or grouped where the group-sweep kernel does not run: it sums a
@@ -180,6 +181,32 @@ int fcsa_backward(const fcsa_backward_args* args);
 
 /* Scratch needed by fcsa_backward for this problem (delta, f32 gradient slabs). */
 size_t fcsa_backward_workspace_bytes(const fcsa_problem* p);
+
+/* Packed variable-length sequences (the flash-attn `cu_seqlens` convention; no reference counterpart).
+ * `batch` sequences are packed along the token axis: sequence s owns the query rows [cu_seqlens_q[s], cu_seqlens_q[s + 1]) and the
+ * key rows [cu_seqlens_k[s], cu_seqlens_k[s + 1]).  Each sequence's rows are what fcsa_forward / fcsa_backward compute for that
+ * sequence alone as a batch-1 problem (causal alignment, rows without a visible key, every scale, groups, l2norm_qk, K/V heads).
+ * The argument structs above are reused with these meanings:
+ *   p.batch = sequences, p.q_len = max_seqlen_q, p.k_len = max_seqlen_k (>= every span; longer spans are cut to it)
+ *   q, o, d_out, dq : packed [total_q, H, D] views: stride0 ignored, stride1 = head stride, stride2 = token stride
+ *                     (a strided slice of a packed qkv tensor works)
+ *   k, v, dk, dv    : packed [total_k, Hk, D] views, likewise
+ *   every buffer the dense ABI indexes [B, H, N, ...] is indexed as B = 1, N = total_q: inv_l [1, H, total_q], norm.qn
+ *   [1, H, total_q, D], norm.rq [1, H, total_q, G], and the workspace's delta / f32 slabs; norm.kn, norm.rk as [1, Hk, total_k, ...].
+ * mask, attn_bias and d_bias must be NULL (FCSA_ERR_INVALID_ARG).  The tables live on the device and are never read by the host:
+ * they are trusted, as in flash-attn; each workgroup clamps its span to [0, total) (a malformed table gives wrong rows, never an
+ * access outside the tensors).  Sequences with an empty key span get o = 0 and dq = 0, sequences with an empty query span dk = dv = 0.
+ * The grid is sized by the longest sequence (batch x heads x the tiles of max_seqlen): a workgroup beyond its own sequence's tiles
+ * exits at once.  No split launch, 64-rows-per-wave forward form or grouped-query head sweep is taken. */
+typedef struct fcsa_varlen {
+  const int32_t* cu_seqlens_q;   /* device, [batch + 1] */
+  const int32_t* cu_seqlens_k;   /* device, [batch + 1] */
+  int64_t total_q, total_k;      /* rows of the packed q / k tensors */
+} fcsa_varlen;
+int    fcsa_forward_varlen(const fcsa_forward_args* args, const fcsa_varlen* seqs);
+int    fcsa_backward_varlen(const fcsa_backward_args* args, const fcsa_varlen* seqs);
+/* Scratch fcsa_backward_varlen needs (delta [1, H, total_q], f32 slabs [1, H, total_q or total_k, D] where needed) */
+size_t fcsa_backward_varlen_workspace_bytes(const fcsa_problem* p, const fcsa_varlen* seqs);
 
 /* Bytes of optional forward scratch that enable the split-key forward for this problem (0: never split). */
 size_t fcsa_forward_workspace_bytes(const fcsa_problem* p);
