@@ -80,11 +80,13 @@ ForwardArgs = _STRUCTS["fcsa_forward_args"]
 BackwardArgs = _STRUCTS["fcsa_backward_args"]
 KernelStat = _STRUCTS["fcsa_kernel_stat"]
 Varlen = _STRUCTS["fcsa_varlen"]
+KvCache = _STRUCTS["fcsa_kvcache"]
 
 
 EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fcsa_forward_workspace_bytes", "fcsa_forward_needs_qn",
            "fcsa_l2norm", "fcsa_debug", "fcsa_debug_forward_form", "fcsa_debug_kv_group_form", "fcsa_last_error", "fcsa_profile_enable", "fcsa_profile_collect",
-           "fcsa_forward_varlen", "fcsa_backward_varlen", "fcsa_backward_varlen_workspace_bytes")
+           "fcsa_forward_varlen", "fcsa_backward_varlen", "fcsa_backward_varlen_workspace_bytes", "fcsa_forward_kvcache",
+           "fcsa_forward_kvcache_workspace_bytes")
 
 _lib = None
 
@@ -142,6 +144,10 @@ def load():
     lib.fcsa_backward_varlen.restype = C.c_int
     lib.fcsa_backward_varlen_workspace_bytes.argtypes = [C.POINTER(Problem), C.POINTER(Varlen)]
     lib.fcsa_backward_varlen_workspace_bytes.restype = C.c_size_t
+    lib.fcsa_forward_kvcache.argtypes = [C.POINTER(ForwardArgs), C.POINTER(KvCache)]
+    lib.fcsa_forward_kvcache.restype = C.c_int
+    lib.fcsa_forward_kvcache_workspace_bytes.argtypes = [C.POINTER(Problem), C.POINTER(KvCache)]
+    lib.fcsa_forward_kvcache_workspace_bytes.restype = C.c_size_t
     lib.fcsa_last_error.argtypes = []
     lib.fcsa_last_error.restype = C.c_char_p
     ver = lib.fcsa_debug(None, 0)

@@ -83,6 +83,10 @@ def _register_fakes():
     def _(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, scale, causal, l2norm_qk, groups):
         return q.new_empty(q.shape)
 
+    @torch.library.register_fake("fcsa::kvcache_forward")
+    def _(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups):
+        return q.new_empty(q.shape)      # (the caches are mutated in place: declared by the schema's (a!) / (b!))
+
     @torch.library.register_fake("fcsa::backward")
     def _(d_out, o, inv_l, q, k, v, mask, attn_bias, qn, kn, rq, rk, attn_bias_batch_dim, scale, causal, l2norm_qk, groups,
           need_bias_grad):

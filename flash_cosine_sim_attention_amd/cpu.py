@@ -131,3 +131,51 @@ def attention_forward_varlen_cpu(q, k, v, cu_seqlens_q, cu_seqlens_k, scale=8.0,
         o = attention_forward_cpu(qs, ks, vs, scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk)
         out[cq[s]:cq[s + 1]] = o[0].permute(1, 0, 2)
     return out
+
+
+def cache_gather(cache, b, length, block_table=None):
+    """Positions [0, length) of sequence b of a key or value cache: [1, Hk, length, D].  Contiguous caches are [B, Hk, capacity, D]; paged
+    ones [num_blocks, Hk, page_size, D] with block_table[b, i] holding positions [i * page_size, (i + 1) * page_size)."""
+    if block_table is None:
+        return cache[b:b + 1, :, :length]
+    page = cache.shape[2]
+    blocks = [int(x) for x in block_table[b, :(length + page - 1) // page].tolist()]
+    if not blocks:
+        return cache[:1, :, :0]
+    return torch.cat([cache[i] for i in blocks], dim=1)[None, :, :length]
+
+
+def append_kvcache_cpu(k_cache, v_cache, k_new, v_new, seqlens, block_table=None):
+    """Writes k_new[b], v_new[b] ([B, Hk, N_new, D]) into the caches at positions [seqlens[b], seqlens[b] + N_new), in place; slots at or
+    beyond the capacity are dropped (the GPU kernel's rule)."""
+    page = k_cache.shape[2]
+    capacity = page * block_table.shape[1] if block_table is not None else k_cache.shape[2]
+    for b, start in enumerate(seqlens):
+        for t in range(k_new.shape[2]):
+            pos = start + t
+            if pos >= capacity:
+                break
+            if block_table is None:
+                k_cache[b, :, pos] = k_new[b, :, t]
+                v_cache[b, :, pos] = v_new[b, :, t]
+            else:
+                blk = int(block_table[b, pos // page])
+                k_cache[blk, :, pos % page] = k_new[b, :, t]
+                v_cache[blk, :, pos % page] = v_new[b, :, t]
+
+
+def attention_forward_kvcache_cpu(q, k_cache, v_cache, k_new, v_new, seqlens, block_table=None, scale=8.0, groups=1, causal=False,
+                                  l2norm_qk=True):
+    """Forward-only path of `flash_cosine_sim_attention_with_kvcache` on host tensors: the append as an indexed copy, then the dense CPU
+    forward of every sequence over its first L_b = seqlens[b] + N_new cached positions (o = 0 where L_b == 0).  seqlens: host ints."""
+    if k_new is not None:
+        append_kvcache_cpu(k_cache, v_cache, k_new, v_new, seqlens, block_table)
+    n_new = 0 if k_new is None else k_new.shape[2]
+    out = torch.zeros_like(q)
+    for b, start in enumerate(seqlens):
+        length = start + n_new
+        if length == 0 or q.shape[2] == 0:
+            continue
+        kb, vb = cache_gather(k_cache, b, length, block_table), cache_gather(v_cache, b, length, block_table)
+        out[b:b + 1] = attention_forward_cpu(q[b:b + 1], kb, vb, scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk)
+    return out

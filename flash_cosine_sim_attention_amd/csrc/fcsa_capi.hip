@@ -318,7 +318,7 @@ int fcsa_debug(char* buf, size_t buf_bytes) {
     snprintf(buf, buf_bytes,
              "libfcsa_hip abi=%d arch=gfx950 dtypes=f32,f16,bf16 dim_head=16,32,64,96,128 "
              "kernels=l2norm,l2norm_pair,fwd(32 rows/wave; lean two-wave form at D=96/128),fwd2(64 rows/wave),fwd3(D=128: 64 rows/wave, 1 wave/SIMD),fwd_ksplit(128 rows, wave halves split the keys),fwd_split+combine,"
-             "fwd_dyn(per-row shift),bwd_dq(+split-key; key-split form on 8 waves),bwd_dkv(+lean; query-split form on 8 waves; grouped-query K/V head sweep),bwd_dbias,finalize kv_heads=divisors of heads",
+             "fwd_dyn(per-row shift),bwd_dq(+split-key; key-split form on 8 waves),bwd_dkv(+lean; query-split form on 8 waves; grouped-query K/V head sweep),bwd_dbias,finalize,kv_append+decode+decode_combine(kv cache) kv_heads=divisors of heads",
              FCSA_ABI_VERSION);
   }
   return FCSA_ABI_VERSION;
@@ -395,6 +395,118 @@ int fcsa_forward_varlen(const fcsa_forward_args* a, const fcsa_varlen* seqs) {
   return forward_impl(&pa, &vl);
 }
 
+
+}  // extern "C"
+
+namespace {
+
+// ---- decoding against a key/value cache (fcsa_forward_kvcache) -------------------------------------------------------------------------
+// The plan of a decode call: row tiles of the G x N rows of a K/V head, and the split count of the key range (fcsa::decode_splits: a pure
+// function of the shapes and the CU count, never of device table contents).
+struct DecodePlan { int row_tiles, splits; size_t ws_o, ws_ml, total; };
+DecodePlan decode_plan(const fcsa_problem& p, const fcsa_kvcache& kv) {
+  DecodePlan d;
+  const int G = p.kv_heads > 0 ? p.heads / p.kv_heads : 0;
+  d.row_tiles = std::max(fcsa::decode_row_tiles(G * p.q_len), 1);
+  const int max_k = std::min(std::max(p.k_len, 0), std::max(kv.capacity, 0));
+  d.splits = fcsa::decode_splits(p.batch, p.kv_heads, d.row_tiles, max_k, p.dim_head, fcsa::cu_count());
+  const size_t rows = (size_t)std::max(p.batch, 0) * std::max(p.heads, 0) * std::max(p.q_len, 0);
+  d.ws_o = 0;
+  d.ws_ml = align256(rows * d.splits * std::max(p.dim_head, 0) * 4);
+  d.total = rows == 0 ? 0 : d.ws_ml + align256(rows * d.splits * 8);
+  return d;
+}
+
+int check_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv) {
+  if (a == nullptr || kv == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache: null argument");
+  const fcsa_problem& p = a->p;
+  if (int rc = check_problem(p)) return rc;
+  if (a->inv_l != nullptr || a->mask != nullptr || a->attn_bias != nullptr)
+    return fail(FCSA_ERR_INVALID_ARG, "kvcache: inv_l, mask and attn_bias must be NULL (forward only, no mask or bias)");
+  if (kv->capacity < 0 || kv->new_len < 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache: negative capacity (%d) or new_len (%d)", kv->capacity, kv->new_len);
+  if (kv->block_table != nullptr) {
+    if (kv->page_size <= 0 || kv->page_size % 16 != 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache: page_size %d must be a positive multiple of 16", kv->page_size);
+    if (kv->capacity % kv->page_size != 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache: capacity %d is not a whole number of pages of %d", kv->capacity, kv->page_size);
+    if (kv->capacity > 0 && kv->num_blocks < 1) return fail(FCSA_ERR_INVALID_ARG, "kvcache: paged cache without blocks");
+    if (kv->block_table_stride < kv->capacity / kv->page_size) return fail(FCSA_ERR_INVALID_ARG, "kvcache: block_table row stride %lld below %d entries", (long long)kv->block_table_stride, kv->capacity / kv->page_size);
+  } else if (kv->page_size != 0) {
+    return fail(FCSA_ERR_INVALID_ARG, "kvcache: page_size %d without a block_table", kv->page_size);
+  }
+  const int es = elem_size(p.dtype);
+  const bool rows = p.batch > 0 && p.heads > 0 && p.q_len > 0;
+  const bool cache = p.batch > 0 && kv->capacity > 0;
+  if (rows) {
+    if (int rc = check_tensor("q", a->q, es, true)) return rc;
+    if (int rc = check_tensor("o", a->o, es, true)) return rc;
+  }
+  if (cache) {
+    if (int rc = check_tensor("k_cache", kv->k_cache, es, true)) return rc;
+    if (int rc = check_tensor("v_cache", kv->v_cache, es, true)) return rc;
+  }
+  if (cache && kv->new_len > 0) {
+    if (int rc = check_tensor("k_new", kv->k_new, es, true)) return rc;
+    if (int rc = check_tensor("v_new", kv->v_new, es, true)) return rc;
+  }
+  if (rows) {
+    const DecodePlan d = decode_plan(p, *kv);
+    if ((int64_t)p.batch * p.kv_heads * d.row_tiles * d.splits > INT32_MAX) return fail(FCSA_ERR_UNSUPPORTED, "kvcache: grid above 2^31 workgroups");
+  }
+  return FCSA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t fcsa_forward_kvcache_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv) {
+  if (p == nullptr || kv == nullptr) return 0;
+  return decode_plan(*p, *kv).total;
+}
+
+int fcsa_forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv) {
+  if (int rc = check_kvcache(a, kv)) return rc;
+  const fcsa_problem& p = a->p;
+  if (p.batch == 0) return FCSA_OK;
+  const int es = elem_size(p.dtype);
+  hipStream_t s = static_cast<hipStream_t>(a->stream);
+  const DecodePlan d = decode_plan(p, *kv);
+  const bool rows = p.heads > 0 && p.q_len > 0;
+  if (rows) {
+    if (a->workspace == nullptr || a->workspace_bytes < d.total)
+      return fail(FCSA_ERR_WORKSPACE, "kvcache: workspace too small: %zu < %zu bytes", a->workspace_bytes, d.total);
+    if ((reinterpret_cast<uintptr_t>(a->workspace) & 255) != 0) return fail(FCSA_ERR_WORKSPACE, "kvcache: workspace not 256-byte aligned");
+  }
+  fcsa::DecodeParams dp;
+  dp.q = view(a->q, es);
+  dp.o = view(a->o, es);
+  dp.kc = view(kv->k_cache, es);
+  dp.vc = view(kv->v_cache, es);
+  dp.kn = view(kv->k_new, es);
+  dp.vn = view(kv->v_new, es);
+  dp.seqlens = kv->cache_seqlens;
+  dp.table = kv->block_table;
+  dp.table_stride = kv->block_table_stride;
+  dp.capacity = kv->capacity;
+  dp.page = kv->block_table != nullptr ? kv->page_size : 0;
+  dp.num_blocks = kv->num_blocks;
+  dp.new_len = kv->new_len;
+  dp.B = p.batch; dp.H = p.heads; dp.Hk = p.kv_heads; dp.G = p.heads / p.kv_heads; dp.N = p.q_len;
+  dp.row_tiles = d.row_tiles; dp.splits = d.splits;
+  dp.causal = p.causal; dp.l2norm = p.l2norm_qk; dp.groups = p.l2norm_qk ? p.groups : 1;
+  dp.c1 = p.scale * kLog2e;
+  dp.c2 = exponent_shift(p, false) * kLog2e;
+  dp.l_eps = rowsum_eps(p, false);
+  dp.dyn = dynamic_shift(p, false) ? 1 : 0;
+  dp.ws_o = static_cast<float*>(a->workspace);
+  dp.ws_ml = reinterpret_cast<float*>(static_cast<char*>(a->workspace) + d.ws_ml);
+  // 1. the append (before anything reads the cache: same stream), 2. the split partials, 3. their combine
+  if (kv->new_len > 0 && kv->capacity > 0) {
+    if (int rc = timed("kv_append", "kv append", s, [&] { return fcsa::launch_kv_append(p.dtype, p.dim_head, dp, s); })) return rc;
+  }
+  if (!rows) return FCSA_OK;
+  if (int rc = timed("decode", "decode", s, [&] { return fcsa::launch_decode(p.dtype, p.dim_head, dp, s); })) return rc;
+  return timed("decode_combine", "decode combine", s, [&] { return fcsa::launch_decode_combine(p.dtype, p.dim_head, dp, s); });
+}
 }  // extern "C"
 
 namespace {

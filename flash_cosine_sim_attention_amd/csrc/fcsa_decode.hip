@@ -1,0 +1,510 @@
+// fcsa_decode.hip -- decoding against a key/value cache (fcsa_forward_kvcache, include/fcsa.h).
+//
+//   kv_append_kernel      k_new / v_new -> the cache slots [cache_seqlens[b], + new_len) (through the block table when paged)
+//   decode_kernel         one single-wave workgroup per (batch, K/V head, row tile, key split): the G = H / Hk query heads x N queries
+//                         of the K/V head are the 16 rows of a tile, so each K/V byte is read once per row tile.  Keys stream straight
+//                         from the cache into registers (one 16-byte load per lane and fragment), are l2-normalised there, and
+//                         S^T = K^ Q^T runs on mfma_f32_16x16x32 (float32: 16x16x4) with the query row on the lane.  V goes through a
+//                         wave-private LDS block for the transposed reads of O^T = V^T P~^T.  Partials (P~V, row max, row sum) in f32.
+//   decode_combine_kernel reconciles the splits of every row (a per-split row max in the per-row-shift regime, a common shift
+//                         otherwise) and normalises.
+#include "fcsa_common.cuh"
+
+#include <cmath>
+#include <type_traits>
+
+namespace fcsa {
+
+FCSA_TRACE_SITE(decode)
+
+namespace {
+
+// LDS plan of the decode kernel, for the kernel and its launcher: one 32-key V block, rows of D elements padded by 16 bytes; the form for
+// group widths that straddle a lane's fragment (GEN) adds a float32 scratch of 16 rows x D squares and 16 rows x D group sums behind it
+template <int D, int ES, bool GEN> struct DecodeLds {
+  static constexpr int PITCH = D * ES + 16;
+  static constexpr int VBYTES = kDecodeBlock * PITCH;
+  static constexpr int NORM = GEN ? 2 * kDecodeRows * D * 4 : 0;
+  static constexpr int BYTES = VBYTES + NORM;
+};
+
+// the lane's fragment of a row: NJ units of UE elements, unit j holds features (4 j + hi) * UE ... + UE - 1 (hi = lane >> 4)
+template <typename T> struct Unit;
+template <> struct Unit<BF16> {
+  static constexpr int UE = 8;
+  static FCSA_DEV f32x4 mfma(u32x4 a, u32x4 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+  }
+};
+template <> struct Unit<F16> {
+  static constexpr int UE = 8;
+  static FCSA_DEV f32x4 mfma(u32x4 a, u32x4 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+  }
+};
+template <> struct Unit<F32> {
+  static constexpr int UE = 4;
+};
+
+template <typename T> FCSA_DEV void unpack(const u32x4& u, float (&x)[Unit<T>::UE]) {
+  if constexpr (Traits<T>::ES == 4) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) x[e] = as_f32(u[e]);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { x[2 * e] = Traits<T>::lo(u[e]); x[2 * e + 1] = Traits<T>::hi(u[e]); }
+  }
+}
+template <typename T> FCSA_DEV u32x4 pack(const float (&x)[Unit<T>::UE], float mul) {
+  u32x4 u;
+  if constexpr (Traits<T>::ES == 4) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) u[e] = __builtin_bit_cast(uint32_t, x[e] * mul);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) u[e] = Traits<T>::pack2(x[2 * e] * mul, x[2 * e + 1] * mul);
+  }
+  return u;
+}
+
+// Grouped l2norm of one row held by the four lanes x, x + 16, x + 32, x + 48 (x = lane & 15): x *= 1 / max(||group||, 1e-12), the l2norm
+// kernel's formula.  gs = features per group (decode_groups_fast: one group, a divisor of UE, or UE times a power of two).  Every lane runs
+// every shuffle (gs is uniform).
+template <int NJ, int UE> FCSA_DEV void group_normalise(float (&x)[NJ][UE], int gs, int D) {
+  float ss[NJ][UE];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+#pragma unroll
+    for (int e = 0; e < UE; ++e) ss[j][e] = x[j][e] * x[j][e];
+  if (gs == D) {
+    float t = 0.f;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int e = 0; e < UE; ++e) t += ss[j][e];
+    t += __shfl_xor(t, 16, 64);
+    t += __shfl_xor(t, 32, 64);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int e = 0; e < UE; ++e) ss[j][e] = t;
+  } else if (gs <= UE) {
+#pragma unroll
+    for (int s = 1; s < UE; s *= 2) {
+      if (s < gs) {
+        float n[NJ][UE];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+          for (int e = 0; e < UE; ++e) n[j][e] = ss[j][e] + ss[j][e ^ s];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+          for (int e = 0; e < UE; ++e) ss[j][e] = n[j][e];
+      }
+    }
+  } else {
+    const int units = gs / UE;
+    float u[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      u[j] = 0.f;
+#pragma unroll
+      for (int e = 0; e < UE; ++e) u[j] += ss[j][e];
+    }
+    if (units >= 2) {
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) u[j] += __shfl_xor(u[j], 16, 64);
+    }
+    if (units >= 4) {
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) u[j] += __shfl_xor(u[j], 32, 64);
+    }
+#pragma unroll
+    for (int s = 1; s < NJ; s *= 2) {
+      if (4 * s < units) {
+        float n[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) n[j] = (j ^ s) < NJ ? u[j] + u[j ^ s] : u[j];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) u[j] = n[j];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int e = 0; e < UE; ++e) ss[j][e] = u[j];
+  }
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+#pragma unroll
+    for (int e = 0; e < UE; ++e) x[j][e] *= 1.f / fmaxf(sqrtf(ss[j][e]), 1e-12f);
+}
+
+// Any group width (the GEN form: D = 96 with 48, 24, 12, 6 or 3 features per group, which straddle the lanes' fragments): each lane
+// writes its squares to row (lane & 15) of an LDS scratch, the four lanes of the row sum every fourth group, and each element reads its
+// group's sum back.  Same formula as group_normalise; only the order of the additions differs.
+template <int NJ, int UE, int D> FCSA_DEV void group_normalise_lds(float (&x)[NJ][UE], int gs, float* scratch, int lane) {
+  const int r = lane & 15, hi = lane >> 4;
+  float* sq = scratch + r * D;
+  float* gsum = scratch + kDecodeRows * D + r * D;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int f0 = (4 * j + hi) * UE;
+    if (f0 < D) {
+#pragma unroll
+      for (int e = 0; e < UE; ++e) sq[f0 + e] = x[j][e] * x[j][e];
+    }
+  }
+  __syncthreads();
+  const int groups = D / gs;
+  for (int g = hi; g < groups; g += 4) {
+    float t = 0.f;
+    for (int i = 0; i < gs; ++i) t += sq[g * gs + i];
+    gsum[g] = t;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int f0 = (4 * j + hi) * UE;
+#pragma unroll
+    for (int e = 0; e < UE; ++e)
+      if (f0 < D) x[j][e] *= 1.f / fmaxf(sqrtf(gsum[(f0 + e) / gs]), 1e-12f);
+  }
+  __syncthreads();      // the next row set rewrites the scratch
+}
+
+// Address of cache position `first` (a multiple of 16, uniform) of sequence b, K/V head kvh: a block-table lookup per 16 positions
+// (pages are multiples of 16 positions, so the 16 keys of a fragment never straddle two pages).  Block ids are clamped to the pool.
+FCSA_DEV const char* cache_base(const DecodeParams& p, const View& v, int b, int kvh, int first) {
+  if (p.table != nullptr) {
+    int blk = p.table[(int64_t)b * p.table_stride + first / p.page];
+    blk = min(max(blk, 0), p.num_blocks - 1);
+    return v.p + (int64_t)blk * v.sb + (int64_t)kvh * v.sh + (int64_t)(first % p.page) * v.sn;
+  }
+  return v.p + (int64_t)b * v.sb + (int64_t)kvh * v.sh + (int64_t)first * v.sn;
+}
+
+template <typename T, int D> struct DecodeRegs {
+  static constexpr int ES = Traits<T>::ES;
+  static constexpr int UE = Unit<T>::UE;
+  static constexpr int NJ = ES == 2 ? (D + 31) / 32 : D / 16;     // fragments of a row per lane
+  static constexpr int CPR = D * ES / 16;                          // 16-byte chunks of a row
+  static constexpr int VCH = kDecodeBlock * CPR / 64;              // V chunks per lane of a 32-key block
+  u32x4 k[2][NJ];
+  u32x4 v[VCH];
+
+  // the 32-key block from `kb`; positions at or beyond `end` read position end - 1 (in bounds) and their V chunks are zeroed
+  FCSA_DEV void load(const DecodeParams& p, int b, int kvh, int kb, int end, int lane) {
+    const int x = lane & 15, hi = lane >> 4;
+    const int last16 = (end - 1) & ~15;
+    const char* kbase[2];
+    const char* vbase[2];
+    int first[2];
+#pragma unroll
+    for (int sb = 0; sb < 2; ++sb) {
+      first[sb] = min(kb + 16 * sb, last16);
+      kbase[sb] = cache_base(p, p.kc, b, kvh, first[sb]);
+      vbase[sb] = cache_base(p, p.vc, b, kvh, first[sb]);
+    }
+#pragma unroll
+    for (int sb = 0; sb < 2; ++sb) {
+      const int pos = min(kb + 16 * sb + x, end - 1);
+      const char* row = kbase[sb] + (int64_t)(pos - first[sb]) * p.kc.sn;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const int f = (4 * j + hi) * UE;
+        k[sb][j] = f < D ? *reinterpret_cast<const u32x4*>(row + f * ES) : u32x4{0u, 0u, 0u, 0u};
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < VCH; ++t) {
+      const int c = lane + 64 * t, kk = c / CPR, ch = c % CPR, sb = kk >> 4;
+      const int pos = min(kb + kk, end - 1);
+      const char* src = (sb ? vbase[1] : vbase[0]) + (int64_t)(pos - (sb ? first[1] : first[0])) * p.vc.sn + ch * 16;
+      const u32x4 val = *reinterpret_cast<const u32x4*>(src);
+      v[t] = kb + kk < end ? val : u32x4{0u, 0u, 0u, 0u};
+    }
+  }
+};
+
+template <typename T, int D, bool DYN, bool GEN>
+__global__ __launch_bounds__(64) void decode_kernel(DecodeParams p) {
+  typedef DecodeRegs<T, D> R;
+  typedef DecodeLds<D, R::ES, GEN> LP;
+  constexpr int ES = R::ES, UE = R::UE, NJ = R::NJ, CPR = R::CPR, VCH = R::VCH;
+  constexpr int FB = D / 16;                       // 16-feature blocks of O^T
+  constexpr bool PREFETCH = ES == 2;               // 16-bit: the next block's loads are in flight during this block's math
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  TraceRec<TraceSite_decode, kTraceWg, 0, false> tr;
+  tr.start();
+
+  const int lane = threadIdx.x, x = lane & 15, hi = lane >> 4;
+  int id = blockIdx.x;
+  const int split = id % p.splits;
+  id /= p.splits;
+  const int rt = id % p.row_tiles;
+  id /= p.row_tiles;
+  const int kvh = id % p.Hk, b = id / p.Hk;
+  const int L = decode_len(p.seqlens != nullptr, p.seqlens != nullptr ? p.seqlens[b] : 0, p.new_len, p.capacity);
+  int lo, n;
+  decode_window(L, split, p.splits, lo, n);
+  const int end = lo + n;
+
+  // this lane's query row: the column of every MFMA result
+  const int r = rt * kDecodeRows + x;
+  const bool row_ok = r < p.G * p.N;
+  const int g = row_ok ? r / p.N : 0, qi = row_ok ? r % p.N : 0;
+  const int h = kvh * p.G + g;
+  const int last_key = L - p.N + qi;               // causal: key j is visible iff j <= last_key
+  const int gs = D / p.groups;
+  float* norm_scratch = reinterpret_cast<float*>(smem + LP::VBYTES);
+  auto normalise = [&](float (&xr)[NJ][UE]) {
+    if constexpr (GEN) group_normalise_lds<NJ, UE, D>(xr, gs, norm_scratch, lane);
+    else group_normalise<NJ, UE>(xr, gs, D);
+  };
+
+  u32x4 qf[NJ];
+  {
+    float xq[NJ][UE];
+    const char* qrow = p.q.p + (int64_t)b * p.q.sb + (int64_t)h * p.q.sh + (int64_t)qi * p.q.sn;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int f = (4 * j + hi) * UE;
+      const u32x4 u = (row_ok && f < D) ? *reinterpret_cast<const u32x4*>(qrow + f * ES) : u32x4{0u, 0u, 0u, 0u};
+      unpack<T>(u, xq[j]);
+    }
+    if (p.l2norm) normalise(xq);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) qf[j] = pack<T>(xq[j], p.l2norm ? p.c1 : 1.f);     // c1 * q^, one rounding (the dense kernels' qn)
+  }
+  const float smul = p.l2norm ? 1.f : p.c1;
+
+  f32x4 acc[FB];
+#pragma unroll
+  for (int fb = 0; fb < FB; ++fb) acc[fb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m = DYN ? -INFINITY : p.c2, l = 0.f;
+
+  R cur, nxt;
+  if (PREFETCH && n > 0) cur.load(p, b, kvh, lo, end, lane);
+  for (int kb = lo; kb < end; kb += kDecodeBlock) {
+    if constexpr (PREFETCH) {
+      if (kb + kDecodeBlock < end) nxt.load(p, b, kvh, kb + kDecodeBlock, end, lane);
+    } else {
+      cur.load(p, b, kvh, kb, end, lane);
+    }
+    // S^T = K^ Q^T for the two 16-key halves: s[sb][rr] = logit of key kb + 16 sb + 4 hi + rr for row x (log2 units)
+    f32x4 s[2];
+#pragma unroll
+    for (int sb = 0; sb < 2; ++sb) {
+      float xk[NJ][UE];
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) unpack<T>(cur.k[sb][j], xk[j]);
+      if (p.l2norm) normalise(xk);
+      s[sb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const u32x4 kf = pack<T>(xk[j], 1.f);       // k^ rounded to the type, as the l2norm kernel writes it
+        if constexpr (ES == 2) {
+          s[sb] = Unit<T>::mfma(kf, qf[j], s[sb]);
+        } else {
+#pragma unroll
+          for (int t = 0; t < 4; ++t) s[sb] = __builtin_amdgcn_mfma_f32_16x16x4f32(as_f32(kf[t]), as_f32(qf[j][t]), s[sb], 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        const int key = kb + 16 * sb + 4 * hi + rr;
+        const bool vis = key < end && (!p.causal || key <= last_key);
+        s[sb][rr] = vis ? s[sb][rr] * smul : -INFINITY;
+      }
+    }
+    float shift = p.c2;
+    if constexpr (DYN) {
+      float bm = fmaxf(fmaxf(fmaxf(s[0][0], s[0][1]), fmaxf(s[0][2], s[0][3])), fmaxf(fmaxf(s[1][0], s[1][1]), fmaxf(s[1][2], s[1][3])));
+      bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
+      bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
+      const float mn = fmaxf(m, bm);
+      shift = mn == -INFINITY ? 0.f : mn;
+      const float alpha = fast_exp2(m - shift);      // 0 while the row has seen no key
+#pragma unroll
+      for (int fb = 0; fb < FB; ++fb) acc[fb] *= alpha;
+      l *= alpha;
+      m = mn;
+    }
+    f32x4 pr[2];
+#pragma unroll
+    for (int sb = 0; sb < 2; ++sb)
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        pr[sb][rr] = fast_exp2(s[sb][rr] - shift);
+        l += pr[sb][rr];
+      }
+
+    // V block -> LDS (row-major, padded rows), then O^T += V^T P~^T
+#pragma unroll
+    for (int t = 0; t < VCH; ++t) {
+      const int c = lane + 64 * t;
+      *reinterpret_cast<u32x4*>(smem + (c / CPR) * LP::PITCH + (c % CPR) * 16) = cur.v[t];
+    }
+    __syncthreads();
+    if constexpr (ES == 2) {
+      // k-slot (hi, e) of the P~V product is key 16 (e >> 2) + 4 hi + (e & 3): P~ is used where the first product left it
+      u32x4 pb;
+      pb[0] = Traits<T>::pack2(pr[0][0], pr[0][1]);
+      pb[1] = Traits<T>::pack2(pr[0][2], pr[0][3]);
+      pb[2] = Traits<T>::pack2(pr[1][0], pr[1][1]);
+      pb[3] = Traits<T>::pack2(pr[1][2], pr[1][3]);
+      typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+      // lane 4q + p of the 16-lane group hi addresses key 4 hi + q, features 16 fb + 4p ... + 3; lane x receives feature 16 fb + x
+      const char* a0 = smem + (4 * hi + (x >> 2)) * LP::PITCH + 8 * (x & 3);
+#pragma unroll
+      for (int fb = 0; fb < FB; ++fb) {
+        const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0 + 32 * fb));
+        const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0 + 16 * LP::PITCH + 32 * fb));
+        const u32x2 u0 = __builtin_bit_cast(u32x2, v0), u1 = __builtin_bit_cast(u32x2, v1);
+        acc[fb] = Unit<T>::mfma(u32x4{u0[0], u0[1], u1[0], u1[1]}, pb, acc[fb]);
+      }
+    } else {
+#pragma unroll
+      for (int fb = 0; fb < FB; ++fb)
+#pragma unroll
+        for (int sb = 0; sb < 2; ++sb)
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) {
+            const float a = *reinterpret_cast<const float*>(smem + (16 * sb + 4 * hi + rr) * LP::PITCH + (16 * fb + x) * 4);
+            acc[fb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, pr[sb][rr], acc[fb], 0, 0, 0);
+          }
+    }
+    __syncthreads();
+    if constexpr (PREFETCH) cur = nxt;
+  }
+
+  // partials of row x: O^T[16 fb + 4 hi + rr][x] in acc[fb][rr]; the row sum over the four lanes of the row
+  l += __shfl_xor(l, 16, 64);
+  l += __shfl_xor(l, 32, 64);
+  if (row_ok) {
+    const int64_t rows = (int64_t)p.B * p.H * p.N;
+    const int64_t row = ((int64_t)b * p.H + h) * p.N + qi;
+    float* wo = p.ws_o + ((int64_t)split * rows + row) * D;
+#pragma unroll
+    for (int fb = 0; fb < FB; ++fb) *reinterpret_cast<f32x4*>(wo + 16 * fb + 4 * hi) = acc[fb];
+    if (hi == 0) *reinterpret_cast<f32x2*>(p.ws_ml + ((int64_t)split * rows + row) * 2) = f32x2{m, l};
+  }
+  tr.finish(Trace{}, 0, false, 0);
+}
+
+// o = sum_s 2^(m_s - M) P~V_s / sum_s 2^(m_s - M) l_s over the splits of a row (static regime: every m_s is the common shift, weight 1)
+template <typename T, int D>
+__global__ __launch_bounds__(256) void decode_combine_kernel(DecodeParams p) {
+  constexpr int ES = Traits<T>::ES;
+  constexpr int TPR = D / 4;                       // threads per row: four features each
+  const int64_t rows = (int64_t)p.B * p.H * p.N;
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t row = t / TPR;
+  const int c = (int)(t % TPR);
+  if (row >= rows) return;
+  float M = -INFINITY;
+  for (int s = 0; s < p.splits; ++s) M = fmaxf(M, p.ws_ml[(s * rows + row) * 2]);
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  float l = 0.f;
+  if (M != -INFINITY) {
+    for (int s = 0; s < p.splits; ++s) {
+      const f32x2 ml = *reinterpret_cast<const f32x2*>(p.ws_ml + (s * rows + row) * 2);
+      const float w = exp2f(ml[0] - M);
+      l += w * ml[1];
+      acc += w * *reinterpret_cast<const f32x4*>(p.ws_o + (s * rows + row) * D + 4 * c);
+    }
+  }
+  const float inv = p.dyn ? (l > 0.f ? 1.f / l : 0.f) : 1.f / fmaxf(l, p.l_eps);
+  acc *= inv;
+  const int i = (int)(row % p.N);
+  const int64_t bh = row / p.N;
+  const int h = (int)(bh % p.H), b = (int)(bh / p.H);
+  char* dst = p.o.p + (int64_t)b * p.o.sb + (int64_t)h * p.o.sh + (int64_t)i * p.o.sn + 4 * c * ES;
+  if constexpr (ES == 4) {
+    *reinterpret_cast<f32x4*>(dst) = acc;
+  } else {
+    *reinterpret_cast<u32x2*>(dst) = u32x2{Traits<T>::pack2(acc[0], acc[1]), Traits<T>::pack2(acc[2], acc[3])};
+  }
+}
+
+// one thread per 16-byte chunk of an appended row; slots at or beyond the capacity are dropped
+template <typename T, int D>
+__global__ __launch_bounds__(256) void kv_append_kernel(DecodeParams p) {
+  constexpr int CPR = D * Traits<T>::ES / 16;
+  const int64_t total = (int64_t)p.B * p.Hk * p.new_len * CPR;
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= total) return;
+  const int ch = (int)(t % CPR);
+  int64_t rest = t / CPR;
+  const int tn = (int)(rest % p.new_len);
+  rest /= p.new_len;
+  const int kvh = (int)(rest % p.Hk), b = (int)(rest / p.Hk);
+  const int64_t start = p.seqlens != nullptr ? min(max((int64_t)p.seqlens[b], (int64_t)0), (int64_t)p.capacity) : (int64_t)p.capacity;
+  const int64_t pos = start + tn;
+  if (pos >= p.capacity) return;
+  int64_t kdst, vdst;
+  if (p.table != nullptr) {
+    int blk = p.table[(int64_t)b * p.table_stride + pos / p.page];
+    blk = min(max(blk, 0), p.num_blocks - 1);
+    kdst = (int64_t)blk * p.kc.sb + (int64_t)kvh * p.kc.sh + (pos % p.page) * p.kc.sn;
+    vdst = (int64_t)blk * p.vc.sb + (int64_t)kvh * p.vc.sh + (pos % p.page) * p.vc.sn;
+  } else {
+    kdst = (int64_t)b * p.kc.sb + (int64_t)kvh * p.kc.sh + pos * p.kc.sn;
+    vdst = (int64_t)b * p.vc.sb + (int64_t)kvh * p.vc.sh + pos * p.vc.sn;
+  }
+  const int64_t ksrc = (int64_t)b * p.kn.sb + (int64_t)kvh * p.kn.sh + (int64_t)tn * p.kn.sn;
+  const int64_t vsrc = (int64_t)b * p.vn.sb + (int64_t)kvh * p.vn.sh + (int64_t)tn * p.vn.sn;
+  *reinterpret_cast<u32x4*>(p.kc.p + kdst + ch * 16) = *reinterpret_cast<const u32x4*>(p.kn.p + ksrc + ch * 16);
+  *reinterpret_cast<u32x4*>(p.vc.p + vdst + ch * 16) = *reinterpret_cast<const u32x4*>(p.vn.p + vsrc + ch * 16);
+}
+
+int64_t blocks_of(int64_t threads) { return (threads + 255) / 256; }
+
+}  // namespace
+
+hipError_t launch_kv_append(int dtype, int D, const DecodeParams& p, hipStream_t s) {
+  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    const int64_t threads = (int64_t)p.B * p.Hk * p.new_len * (DD * Traits<T>::ES / 16);
+    if (threads <= 0) return hipSuccess;
+    hipLaunchKernelGGL((kv_append_kernel<T, DD>), dim3((unsigned)blocks_of(threads)), dim3(256), 0, s, p);
+    return hipGetLastError();
+  });
+}
+
+hipError_t launch_decode(int dtype, int D, const DecodeParams& p, hipStream_t s) {
+  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    constexpr int ES = Traits<T>::ES;
+    const dim3 grid((unsigned)((int64_t)p.B * p.Hk * p.row_tiles * p.splits));
+    auto go = [&](auto dyn, auto gen) -> hipError_t {
+      constexpr bool DY = decltype(dyn)::value, GN = decltype(gen)::value;
+      return launch_with_lds<decode_kernel<T, DD, DY, GN>>(grid, dim3(64), DecodeLds<DD, ES, GN>::BYTES, s, p);
+    };
+    using Y = std::true_type;
+    using N = std::false_type;
+    // group widths that straddle the lanes' fragments exist at D = 96 only (decode_groups_fast holds for every divisor of the others)
+    if (p.l2norm && !decode_groups_fast(DD, p.groups, Unit<T>::UE)) {
+      if constexpr (DD == 96) return p.dyn ? go(Y{}, Y{}) : go(N{}, Y{});
+      else return hipErrorInvalidValue;
+    }
+    return p.dyn ? go(Y{}, N{}) : go(N{}, N{});
+  });
+}
+
+hipError_t launch_decode_combine(int dtype, int D, const DecodeParams& p, hipStream_t s) {
+  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    const int64_t threads = (int64_t)p.B * p.H * p.N * (DD / 4);
+    if (threads <= 0) return hipSuccess;
+    hipLaunchKernelGGL((decode_combine_kernel<T, DD>), dim3((unsigned)blocks_of(threads)), dim3(256), 0, s, p);
+    return hipGetLastError();
+  });
+}
+
+}  // namespace fcsa

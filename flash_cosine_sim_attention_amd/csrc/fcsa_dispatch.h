@@ -131,6 +131,51 @@ constexpr void seq_span(int64_t lo, int64_t hi, int total, int max_len, int& sta
 // sequence) has no work and exits at once
 constexpr bool seq_pair_idle(int pair, int len, int tile, int causal) { return pair >= tile_pairs(tile_count(len, tile), causal); }
 
+// ---- decoding against a key/value cache (fcsa_forward_kvcache, csrc/fcsa_decode.hip) ----------------------------------------------------
+// One single-wave workgroup per (batch, K/V head, row tile, key split).  The rows of a tile are the G = H / Hk query heads x N queries
+// of one K/V head (16 per tile, the M of mfma_f32_16x16x32), so each K/V byte leaves HBM once per row tile.  The key range of sequence b
+// (its own L_b, read on the device) is cut into `splits` windows of whole 32-key blocks; an empty window writes a zero partial.
+constexpr int kDecodeRows = 16;            // query rows per tile
+constexpr int kDecodeBlock = 32;           // keys per step of the key loop
+constexpr int kDecodeMaxSplits = 128;
+constexpr int kDecodeWavesPerCu = 8;       // the grid aims at this many waves per CU
+constexpr int decode_row_tiles(int groups_x_queries) { return (groups_x_queries + kDecodeRows - 1) / kDecodeRows; }
+// fewest keys a split is given: 64 KiB of 16-bit K + V rows (128 keys at D = 128)
+constexpr int decode_min_split_keys(int D) { return std::max(16384 / std::max(D, 1), kDecodeBlock); }
+// Split count: enough workgroups for kDecodeWavesPerCu waves per CU, each split at least decode_min_split_keys(D) keys of the longest
+// sequence (max_k), at most kDecodeMaxSplits.
+inline int decode_splits(int64_t batch, int kv_heads, int row_tiles, int max_k, int D, int cus) {
+  const int64_t base = batch * (int64_t)kv_heads * row_tiles;
+  if (base <= 0 || max_k <= 0) return 1;
+  int64_t s = ((int64_t)cus * kDecodeWavesPerCu + base - 1) / base;
+  s = std::min<int64_t>(s, std::max(1, max_k / decode_min_split_keys(D)));
+  s = std::min<int64_t>(s, kDecodeMaxSplits);
+  return (int)std::max<int64_t>(s, 1);
+}
+// Window of split `split` over a sequence of `len` keys: [lo, lo + n), whole 32-key blocks except at the sequence's end.
+constexpr void decode_window(int len, int split, int splits, int& lo, int& n) {
+  const int per = (std::max(len, 0) + splits - 1) / std::max(splits, 1);
+  const int chunk = (per + kDecodeBlock - 1) / kDecodeBlock * kDecodeBlock;
+  lo = std::min(split * chunk, std::max(len, 0));
+  n = std::max(std::min(lo + chunk, len) - lo, 0);
+}
+// Cached positions of a sequence after the append, from the raw device table entry (NULL table: every sequence full)
+constexpr int decode_len(bool has_table, int64_t cached, int new_len, int capacity) {
+  const int64_t c = has_table ? std::min<int64_t>(std::max<int64_t>(cached, 0), capacity) : capacity;
+  return (int)std::min<int64_t>(c + std::max(new_len, 0), capacity);
+}
+// l2norm groups the decode kernel reduces in registers, across the four lanes of a row: one group, or `D / groups` features dividing the
+// lane's fragment of `unit` elements (8 for 16-bit, 4 for float32), or that fragment times a power of two.  Every other width (only
+// possible at D = 96: 48, 24, 12, 6 or 3 features) takes the kernel form that sums each group's squares through LDS.
+constexpr bool decode_groups_fast(int D, int groups, int unit) {
+  if (groups < 1 || D % groups != 0) return false;
+  const int gs = D / groups;
+  if (groups == 1 || unit % gs == 0) return true;
+  if (gs % unit != 0) return false;
+  const int u = gs / unit;
+  return (u & (u - 1)) == 0;
+}
+
 // workgroups of `tile`-position tiles over `len` positions for `batch_heads` (batch x heads)
 inline int64_t tile_workgroups(int64_t batch_heads, int len, int tile, bool causal) {
   return batch_heads * tile_pairs(tile_count(len, tile), causal);

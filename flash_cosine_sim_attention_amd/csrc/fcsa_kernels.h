@@ -101,6 +101,30 @@ struct NormBwdParams {      // dx = reduce_heads(slab) then (optionally) l2norm 
   float xn_scale;           // x^ = xn_scale * xn   (1/c1 when xn was written with out_scale = c1)
 };
 
+// Decoding against a key/value cache (fcsa_forward_kvcache, csrc/fcsa_decode.hip).  Views carry BYTE strides; kc / vc are the caches
+// (sb = batch stride, or block stride when `table` is set), kn / vn the appended rows [B, Hk, new_len, D].
+struct DecodeParams {
+  View q, o;                // [B, H, N, D]
+  View kc, vc;              // caches
+  View kn, vn;              // new rows (append kernel only)
+  const int32_t* seqlens;   // [B] tokens cached before the append, or nullptr: every sequence full
+  const int32_t* table;     // [B, capacity / page] block ids, or nullptr: contiguous cache
+  int64_t table_stride;     // elements between table rows
+  int capacity, page, num_blocks, new_len;
+  int B, H, Hk, G, N;       // G = H / Hk query heads per K/V head; rows of a tile: r = g * N + i
+  int row_tiles, splits;
+  int causal, l2norm, groups;
+  float c1;                 // scale * log2(e)
+  float c2;                 // static exponent shift * log2(e) (dyn == 0)
+  float l_eps;              // row-sum clamp of the static regime
+  int dyn;                  // 1: per-row running max (the per-row-shift regime), kept per split and reconciled by the combine
+  float* ws_o;              // [splits][B*H*N][D] f32 partial P~V
+  float* ws_ml;             // [splits][B*H*N][2] f32 (row max in log2 units, row sum)
+};
+hipError_t launch_kv_append(int dtype, int D, const DecodeParams& p, hipStream_t s);
+hipError_t launch_decode(int dtype, int D, const DecodeParams& p, hipStream_t s);
+hipError_t launch_decode_combine(int dtype, int D, const DecodeParams& p, hipStream_t s);
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE property of a kernel: raise it once per (instantiation, device).
 // `done` is the instantiation's bit mask of devices that have it (one static per launcher); thread safe, idempotent.
 template <typename K>

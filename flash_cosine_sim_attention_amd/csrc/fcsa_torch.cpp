@@ -15,6 +15,7 @@
 #include <dlfcn.h>
 
 #include <atomic>
+#include <cstring>
 #include <chrono>
 #include <tuple>
 
@@ -36,6 +37,9 @@ struct Abi {
   int (*forward_varlen)(const fcsa_forward_args*, const fcsa_varlen*) = &fcsa_forward_varlen;
   int (*backward_varlen)(const fcsa_backward_args*, const fcsa_varlen*) = &fcsa_backward_varlen;
   size_t (*backward_varlen_ws)(const fcsa_problem*, const fcsa_varlen*) = &fcsa_backward_varlen_workspace_bytes;
+  // decoding against a key/value cache: null in a swapped-in library that does not export it (the kvcache op then raises)
+  int (*forward_kvcache)(const fcsa_forward_args*, const fcsa_kvcache*) = &fcsa_forward_kvcache;
+  size_t (*forward_kvcache_ws)(const fcsa_problem*, const fcsa_kvcache*) = &fcsa_forward_kvcache_workspace_bytes;
 } g_abi;
 
 using at::Tensor;
@@ -564,6 +568,109 @@ Tensor varlen_attention_plain(const Tensor& q, const Tensor& k, const Tensor& v,
   return std::get<0>(varlen_forward(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, false));
 }
 
+
+// ---- decoding against a key/value cache (fcsa_forward_kvcache) --------------------------------------------------------------------------
+// q [B, H, N, D]; k_cache / v_cache [B, Hk, capacity, D] or, with a block_table, [num_blocks, Hk, page_size, D] (any strides with the
+// feature dim contiguous: they are written in place, so they are never copied); k_new / v_new [B, Hk, N_new, D]; cache_seqlens int32 [B]
+// and block_table int32 [B, max_blocks] on q's device.  Table contents are never read on the host: the call does not synchronise.
+Tensor kvcache_forward(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const optional<Tensor>& k_new, const optional<Tensor>& v_new,
+                       const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table, int64_t max_seqlen_k, double scale, bool causal,
+                       bool l2norm_qk, int64_t groups) {
+  TORCH_CHECK(g_abi.forward_kvcache != nullptr && g_abi.forward_kvcache_ws != nullptr,
+              "flash_cosine_sim_attention_with_kvcache: the loaded libfcsa_hip.so does not export fcsa_forward_kvcache");
+  TORCH_CHECK(q.is_cuda(), "flash_cosine_sim_attention_with_kvcache: q and the caches must be GPU tensors (HIP kernels only)");
+  auto same_dev = [&](const char* name, const Tensor& t) {
+    TORCH_CHECK_VALUE(t.device() == q.device(), name, " is on ", t.device(), " but q is on ", q.device(), ": all tensors must live on q's GPU");
+  };
+  same_dev("k_cache", k_cache);
+  same_dev("v_cache", v_cache);
+  TORCH_CHECK_TYPE(q.scalar_type() == k_cache.scalar_type() && q.scalar_type() == v_cache.scalar_type(), "q, k_cache, v_cache must share a dtype");
+  dtype_code(q.scalar_type());
+  TORCH_CHECK_VALUE(q.dim() == 4 && k_cache.dim() == 4 && v_cache.dim() == 4, "q, k_cache, v_cache must have 4 dimensions");
+  TORCH_CHECK_VALUE(k_cache.sizes() == v_cache.sizes(), "k_cache and v_cache must have the same shape");
+  const int64_t B = q.size(0), H = q.size(1), N = q.size(2), D = q.size(3), Hk = k_cache.size(1);
+  TORCH_CHECK_VALUE(k_cache.size(3) == D, "query, key, value dimensions must be the same");
+  TORCH_CHECK_VALUE(D == 16 || D == 32 || D == 64 || D == 96 || D == 128, "only dimensions (16, 32, 64, 96, 128) allowed for now, got ", D);
+  TORCH_CHECK_VALUE(Hk >= 1 && H % Hk == 0, "k/v heads must divide q heads (", H, "), got ", Hk);
+  TORCH_CHECK_VALUE(!l2norm_qk || (groups >= 1 && D % groups == 0), "groups (", groups, ") must divide the head dimension (", D, ")");
+  TORCH_CHECK_VALUE(rows_ok(k_cache) && rows_ok(v_cache), "k_cache / v_cache: the feature dim must be contiguous and rows 16-byte aligned "
+                    "(the caches are updated in place, so they are not copied)");
+  const bool paged = block_table.has_value();
+  int64_t capacity = k_cache.size(2), page = 0, num_blocks = 0;
+  fcsa_kvcache kv;
+  if (paged) {
+    same_dev("block_table", *block_table);
+    TORCH_CHECK_TYPE(block_table->scalar_type() == at::kInt, "block_table must be int32");
+    TORCH_CHECK_VALUE(block_table->dim() == 2 && block_table->size(0) == B, "block_table must be [batch, max_blocks]");
+    page = k_cache.size(2);
+    num_blocks = k_cache.size(0);
+    capacity = block_table->size(1) * page;
+    TORCH_CHECK_VALUE(page > 0 && page % 16 == 0, "page_size (", page, ") must be a positive multiple of 16");
+    TORCH_CHECK_VALUE(num_blocks >= 1, "a paged cache needs at least one block");
+  } else {
+    TORCH_CHECK_VALUE(k_cache.size(0) == B, "batch mismatch between q (", B, ") and the caches (", k_cache.size(0), ")");
+  }
+  TORCH_CHECK_VALUE(capacity <= INT32_MAX, "cache capacity must stay below 2^31");
+  Tensor tab = paged ? block_table->contiguous() : Tensor();
+  Tensor kn, vn;
+  TORCH_CHECK_VALUE(k_new.has_value() == v_new.has_value(), "k_new and v_new must be given together");
+  int64_t new_len = 0;
+  if (k_new.has_value()) {
+    same_dev("k_new", *k_new);
+    same_dev("v_new", *v_new);
+    TORCH_CHECK_TYPE(k_new->scalar_type() == q.scalar_type() && v_new->scalar_type() == q.scalar_type(), "k_new / v_new must have q's dtype");
+    TORCH_CHECK_VALUE(k_new->dim() == 4 && k_new->sizes() == v_new->sizes() && k_new->size(0) == B && k_new->size(1) == Hk && k_new->size(3) == D,
+                      "k_new / v_new must be [batch, kv_heads, N_new, dim_head], got ", k_new->sizes(), " and ", v_new->sizes());
+    new_len = k_new->size(2);
+    kn = prep(*k_new);
+    vn = prep(*v_new);
+  }
+  Tensor sl;
+  if (cache_seqlens.has_value()) {
+    same_dev("cache_seqlens", *cache_seqlens);
+    TORCH_CHECK_TYPE(cache_seqlens->scalar_type() == at::kInt, "cache_seqlens must be int32");
+    TORCH_CHECK_VALUE(cache_seqlens->dim() == 1 && cache_seqlens->size(0) == B, "cache_seqlens must be [batch]");
+    sl = cache_seqlens->contiguous();
+  }
+  TORCH_CHECK_VALUE(max_seqlen_k >= 0, "max_seqlen_k must be non-negative");
+  c10::DeviceGuard guard(q.device());
+  const Tensor q4 = prep(q);
+  Tensor o = at::empty({B, H, N, D}, q.options());
+  fcsa_forward_args a;
+  std::memset(&a, 0, sizeof(a));
+  a.p.dtype = dtype_code(q.scalar_type());
+  a.p.batch = (int32_t)B; a.p.heads = (int32_t)H; a.p.kv_heads = (int32_t)Hk;
+  a.p.q_len = (int32_t)N; a.p.k_len = (int32_t)std::min<int64_t>(max_seqlen_k, capacity); a.p.dim_head = (int32_t)D;
+  a.p.causal = causal; a.p.bias_batch_dim = 0; a.p.l2norm_qk = l2norm_qk;
+  a.p.groups = l2norm_qk ? (int32_t)groups : 1;
+  a.p.scale = (float)scale;
+  a.q = view4(q4);
+  a.o = view4(o);
+  kv.k_cache = view4(k_cache);
+  kv.v_cache = view4(v_cache);
+  kv.capacity = (int32_t)capacity;
+  kv.page_size = (int32_t)page;
+  kv.num_blocks = (int32_t)num_blocks;
+  kv.new_len = (int32_t)new_len;
+  kv.cache_seqlens = sl.defined() ? sl.data_ptr<int32_t>() : nullptr;
+  kv.block_table = paged ? tab.data_ptr<int32_t>() : nullptr;
+  kv.block_table_stride = paged ? tab.size(1) : 0;
+  fcsa_tensor none;
+  std::memset(&none, 0, sizeof(none));
+  kv.k_new = kn.defined() && new_len > 0 ? view4(kn) : none;
+  kv.v_new = vn.defined() && new_len > 0 ? view4(vn) : none;
+  const size_t wsb = g_abi.forward_kvcache_ws(&a.p, &kv);
+  Tensor ws;
+  if (wsb > 0) {
+    ws = at::empty({(int64_t)wsb}, q.options().dtype(at::kByte));      // the caching allocator
+    a.workspace = ws.data_ptr();
+    a.workspace_bytes = wsb;
+  }
+  a.stream = stream_of(q);
+  check(g_abi.forward_kvcache(&a, &kv), "fcsa_forward_kvcache");
+  return o;
+}
+
 }  // namespace
 
 // Measurement hook: read (and reset) the host-time counters above.
@@ -586,6 +693,8 @@ extern "C" int fcsa_torch_use_library(const char* path) {
   a.forward_varlen = reinterpret_cast<decltype(a.forward_varlen)>(dlsym(h, "fcsa_forward_varlen"));
   a.backward_varlen = reinterpret_cast<decltype(a.backward_varlen)>(dlsym(h, "fcsa_backward_varlen"));
   a.backward_varlen_ws = reinterpret_cast<decltype(a.backward_varlen_ws)>(dlsym(h, "fcsa_backward_varlen_workspace_bytes"));
+  a.forward_kvcache = reinterpret_cast<decltype(a.forward_kvcache)>(dlsym(h, "fcsa_forward_kvcache"));
+  a.forward_kvcache_ws = reinterpret_cast<decltype(a.forward_kvcache_ws)>(dlsym(h, "fcsa_forward_kvcache_workspace_bytes"));
   if (!a.forward || !a.backward || !a.forward_ws || !a.backward_ws || !a.needs_qn || !a.last_error) { dlclose(h); return -2; }
   // Only libraries of THIS ABI: the binding allocates for the struct layouts and buffer contracts of include/fcsa.h as compiled in
   // (e.g. ABI 3 writes d_bias once in the bias dtype into an uninitialised buffer; an ABI-2 library would accumulate float32 into
@@ -613,6 +722,9 @@ TORCH_LIBRARY(fcsa, m) {
         "int groups) -> (Tensor, Tensor, Tensor)");
   m.def("varlen_attention(Tensor q, Tensor k, Tensor v, Tensor cu_seqlens_q, Tensor cu_seqlens_k, int max_seqlen_q, int max_seqlen_k, "
         "float scale, bool causal, bool l2norm_qk, int groups) -> Tensor");
+  // decoding against a key/value cache (forward only): appends k_new / v_new to the caches in place, then attends
+  m.def("kvcache_forward(Tensor q, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor? k_new, Tensor? v_new, Tensor? cache_seqlens, "
+        "Tensor? block_table, int max_seqlen_k, float scale, bool causal, bool l2norm_qk, int groups) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(fcsa, CUDA, m) {       // ROCm builds of PyTorch dispatch HIP tensors under the CUDA key
@@ -622,6 +734,7 @@ TORCH_LIBRARY_IMPL(fcsa, CUDA, m) {       // ROCm builds of PyTorch dispatch HIP
   m.impl("varlen_forward", &varlen_forward);
   m.impl("varlen_backward", &varlen_backward);
   m.impl("varlen_attention", &varlen_attention_plain);
+  m.impl("kvcache_forward", &kvcache_forward);
 }
 
 TORCH_LIBRARY_IMPL(fcsa, Autograd, m) {

@@ -216,3 +216,96 @@ def flash_cosine_sim_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_s
     cu_k = cu_seqlens_k.to(q.device, non_blocking=True)
     return _torch_ops.load().varlen_attention(q, k, v, cu_q, cu_k, int(max_seqlen_q), int(max_seqlen_k), float(scale), bool(causal),
                                               bool(l2norm_qk), int(groups))
+
+
+# ---------------------------------------------------------------------------------------------
+# decoding against a key/value cache (flash-attn's kvcache convention; no reference counterpart)
+# ---------------------------------------------------------------------------------------------
+
+def flash_cosine_sim_attention_with_kvcache(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlens=None, block_table=None,
+                                            max_seqlen_k=None, scale=8, groups=1, causal=False, l2norm_qk=True):
+    """Forward-only attention of new queries against a key/value cache, with an optional in-place append.
+
+    q [B, H, N, D] (N = 1: plain decode; a few: speculative or chunked steps).  k_cache, v_cache: [B, Hk, capacity, D] or, with a
+    block_table, paged [num_blocks, Hk, page_size, D] (page_size a multiple of 16); any strides with the feature dim contiguous, so a
+    [B, capacity, Hk, D] (vLLM: [num_blocks, page_size, Hk, D]) buffer passed as .transpose(1, 2) works.  Hk divides H.
+    block_table: int32 [B, max_blocks]; entry [b, i] is the block holding positions [i * page_size, (i + 1) * page_size) of sequence b.
+    cache_seqlens: int32 [B] (device or host) or an int: tokens already cached per sequence; None: every sequence is full.
+    k_new, v_new: [B, Hk, N_new, D], written into the cache at [cache_seqlens[b], cache_seqlens[b] + N_new) before attention reads it
+    (cache_seqlens itself is not advanced).  With L_b = cache_seqlens[b] + N_new, o[b] equals flash_cosine_sim_attention(q[b:b+1], K_b,
+    V_b, scale=, groups=, causal=, l2norm_qk=) over the first L_b cached positions (causal: bottom-right alignment; L_b == 0 gives 0).
+    The cache holds raw keys; with l2norm_qk they are normalised as they are read.
+    max_seqlen_k: an upper bound on every L_b that sizes the launch grid (default: the capacity), so the call never reads device tables
+    on the host and a decode step can be captured in a HIP graph.  Host tables are validated; device tables are trusted (the kernels
+    clamp lengths and block ids, so a malformed table gives wrong rows, never an access outside the tensors).  Two sequences appending
+    into the same page slot is undefined behaviour.  CPU tensors take the forward-only path of `cpu.py`."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_new, v_new)):
+        raise RuntimeError("flash_cosine_sim_attention_with_kvcache is forward-only: q, k_new and v_new must not require grad "
+                           "(run it under torch.no_grad())")
+    for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
+        if t.dim() != 4:
+            raise ValueError(f"{name} must have 4 dimensions, got {tuple(t.shape)}")
+    if k_cache.shape != v_cache.shape:
+        raise ValueError(f"k_cache and v_cache must have the same shape, got {tuple(k_cache.shape)} and {tuple(v_cache.shape)}")
+    if (k_new is None) != (v_new is None):
+        raise ValueError("k_new and v_new must be given together")
+    B, H, N, D = q.shape
+    Hk = k_cache.shape[1]
+    if k_cache.shape[3] != D:
+        raise ValueError("query, key, value dimensions must be the same")
+    if Hk < 1 or H % Hk:
+        raise ValueError(f"k/v heads must divide q heads ({H}), got {Hk}")
+    if k_new is not None:
+        if k_new.shape != v_new.shape or k_new.dim() != 4 or tuple(k_new.shape[:2]) != (B, Hk) or k_new.shape[3] != D:
+            raise ValueError(f"k_new / v_new must be [{B}, {Hk}, N_new, {D}], got {tuple(k_new.shape)} and {tuple(v_new.shape)}")
+    n_new = 0 if k_new is None else k_new.shape[2]
+    if block_table is not None:
+        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B:
+            raise TypeError(f"block_table must be an int32 [batch, max_blocks] tensor")
+        page = k_cache.shape[2]
+        if page <= 0 or page % 16:
+            raise ValueError(f"page_size ({page}) must be a positive multiple of 16")
+        capacity = block_table.shape[1] * page
+    else:
+        if k_cache.shape[0] != B:
+            raise ValueError(f"batch mismatch between q ({B}) and the caches ({k_cache.shape[0]})")
+        capacity = k_cache.shape[2]
+    host_lens = None
+    if cache_seqlens is None:
+        if n_new:
+            raise ValueError("k_new given but cache_seqlens is None (every sequence full): there is no slot to append to")
+    elif isinstance(cache_seqlens, int):
+        host_lens = [int(cache_seqlens)] * B
+    else:
+        if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32 or cache_seqlens.shape != (B,):
+            raise TypeError(f"cache_seqlens must be an int or an int32 tensor of shape ({B},)")
+        if cache_seqlens.device.type == "cpu":
+            host_lens = [int(x) for x in cache_seqlens.tolist()]
+    if host_lens is not None:
+        for b, n0 in enumerate(host_lens):
+            if n0 < 0 or n0 + n_new > capacity:
+                raise ValueError(f"sequence {b}: cache_seqlens {n0} + {n_new} new tokens outside [0, capacity {capacity}]")
+        if block_table is not None and block_table.device.type == "cpu":
+            nb = k_cache.shape[0]
+            for b, n0 in enumerate(host_lens):
+                used = block_table[b, :(n0 + n_new + page - 1) // page]
+                if used.numel() and (int(used.min()) < 0 or int(used.max()) >= nb):
+                    raise ValueError(f"sequence {b}: block_table entries outside [0, {nb})")
+    if max_seqlen_k is not None and (int(max_seqlen_k) != max_seqlen_k or max_seqlen_k < 0):
+        raise ValueError(f"max_seqlen_k must be a non-negative integer, got {max_seqlen_k}")
+    if q.device.type == "cpu":
+        lens = host_lens if host_lens is not None else [capacity - n_new] * B
+        if cache_seqlens is not None and host_lens is None:
+            raise ValueError("CPU tensors take host cache_seqlens")
+        detach = lambda t: None if t is None else t.detach()          # (grad mode is off here, or nothing requires grad)
+        return _cpu.attention_forward_kvcache_cpu(q.detach(), k_cache, v_cache, detach(k_new), detach(v_new), lens, block_table,
+                                                  scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk)
+    if isinstance(cache_seqlens, int):
+        cache_seqlens = torch.full((B,), cache_seqlens, dtype=torch.int32, device=q.device)
+    elif cache_seqlens is not None:
+        cache_seqlens = cache_seqlens.to(q.device, non_blocking=True)
+    if block_table is not None:
+        block_table = block_table.to(q.device, non_blocking=True)
+    max_k = capacity if max_seqlen_k is None else min(int(max_seqlen_k), capacity)
+    return _torch_ops.load().kvcache_forward(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, int(max_k), float(scale),
+                                             bool(causal), bool(l2norm_qk), int(groups))

@@ -208,6 +208,43 @@ int    fcsa_backward_varlen(const fcsa_backward_args* args, const fcsa_varlen* s
 /* Scratch fcsa_backward_varlen needs (delta [1, H, total_q], f32 slabs [1, H, total_q or total_k, D] where needed) */
 size_t fcsa_backward_varlen_workspace_bytes(const fcsa_problem* p, const fcsa_varlen* seqs);
 
+/* Decoding against a key/value cache (no reference counterpart; flash-attn's kvcache convention).  Forward only.
+ * Sequence b of the batch holds L_b = min(cache_seqlens[b] + new_len, capacity) cached positions AFTER the append: first the new keys /
+ * values k_new[b], v_new[b] are written into the cache at positions [cache_seqlens[b], cache_seqlens[b] + new_len) (slots at or beyond
+ * the capacity are dropped), then q[b] attends to positions [0, L_b) of its cache.  o[b] is what fcsa_forward computes for the batch-1
+ * problem (q[b], the first L_b cached keys / values) with the same scale, groups, causal (bottom-right: key j visible to query i iff
+ * j - (L_b - N) <= i) and l2norm_qk.  The cache holds keys as the caller gave them (raw); with l2norm_qk they are normalised as they are
+ * read, every call, and nothing is written back.  cache_seqlens is not advanced (the caller does that).
+ * The fcsa_forward_args fields are read as follows:
+ *   p.q_len = N (queries per sequence), p.k_len = max_seqlen_k: an upper bound on every L_b that sizes the grid (clamped to the capacity)
+ *   q, o       : [B, H, N, D] as in fcsa_forward
+ *   k, v       : ignored (the cache views below replace them); norm: unused
+ *   inv_l, mask, attn_bias: must be NULL (FCSA_ERR_INVALID_ARG)
+ *   workspace  : >= fcsa_forward_kvcache_workspace_bytes() bytes, 256-byte aligned (split partials: required, the combine kernel reads them)
+ * Cache layouts (any element strides, feature dim contiguous, rows 16-byte aligned):
+ *   contiguous (block_table NULL): k_cache, v_cache [B, Hk, capacity, D]; stride0 = batch stride
+ *   paged      (block_table set) : k_cache, v_cache [num_blocks, Hk, page_size, D]; stride0 = block stride.  block_table [B, *] int32
+ *               (row stride block_table_stride): entry [b, i] is the block holding positions [i * page_size, (i + 1) * page_size) of
+ *               sequence b; capacity = (entries per row) * page_size; page_size a positive multiple of 16.
+ * Device tables are trusted: the kernels clamp cache_seqlens to [0, capacity] and block ids to [0, num_blocks), so a malformed table gives
+ * wrong rows, never an access outside the tensors.  Two sequences appending into the same page slot is undefined behaviour.
+ * Every l2norm `groups` that divides dim_head is supported.
+ * Launches: the append kernel ("kv_append", when new_len > 0), the decode kernel ("decode") and the split combine ("decode_combine"). */
+typedef struct fcsa_kvcache {
+  fcsa_tensor    k_cache, v_cache;    /* see above */
+  int32_t        capacity;            /* positions per sequence: contiguous: dim 2 of the cache; paged: entries per table row * page_size */
+  int32_t        page_size;           /* 0: contiguous cache; else positions per block (multiple of 16) */
+  int32_t        num_blocks;          /* paged: blocks in the pool */
+  int32_t        new_len;             /* N_new: keys / values appended per sequence (0: none) */
+  const int32_t* cache_seqlens;       /* device [B]: tokens already cached per sequence, or NULL: every sequence full (L_b = capacity) */
+  const int32_t* block_table;         /* device [B, capacity / page_size] or NULL (contiguous cache) */
+  int64_t        block_table_stride;  /* elements between the rows of block_table */
+  fcsa_tensor    k_new, v_new;        /* [B, Hk, new_len, D] (ptr may be NULL when new_len == 0) */
+} fcsa_kvcache;
+int    fcsa_forward_kvcache(const fcsa_forward_args* args, const fcsa_kvcache* cache);
+/* Scratch fcsa_forward_kvcache needs: f32 partial P~V and (max, row sum) of every split, [splits][B * H * N][D + 2] */
+size_t fcsa_forward_kvcache_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* cache);
+
 /* Bytes of optional forward scratch that enable the split-key forward for this problem (0: never split). */
 size_t fcsa_forward_workspace_bytes(const fcsa_problem* p);
 
