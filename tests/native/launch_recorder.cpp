@@ -7,6 +7,10 @@
 //   cus dtype D B H Hk N M causal mask bias l2norm groups scale layout rowstride fwd_form kv_form
 //   bias: 0 none, 1 per head, 2 per batch;  layout: 0 [B,H,L,D] contiguous, 1 [B,L,H,D];  rowstride: 0, or the row stride in BYTES of
 //   q / k / v ([B,H,L,D] order, rows rowstride apart);  fwd_form / kv_form: the debug knobs fcsa_debug_forward_form / kv_group_form.
+//   Optional tail "varlen S total_q total_k": packed sequences through fcsa_forward_varlen / fcsa_backward_varlen (B = S sequences, N / M
+//   = max_seqlen_q / max_seqlen_k, packed [total, H, D] tensors, fake cu_seqlens tables; mask, bias, layout and rowstride must be 0, else
+//   the line's output is "<input> | rc -1 malformed varlen line ...").  The
+//   saved norm state follows the PyTorch binding's autograd call: qn only where fcsa_forward_needs_qn of the packed rows asks for it.
 // Output, one line per problem: the input, " | ws <forward workspace> qn <fcsa_forward_needs_qn without / with backward>", the forward's
 // launches, " | ws <backward workspace>", the backward's launches; each launch "; kernel<args> <grid x>x<grid y> <block> <LDS> <fields>".
 #include <dlfcn.h>
@@ -105,14 +109,23 @@ int main(int argc, char** argv) {
 #define SYM(name) auto name = reinterpret_cast<decltype(&::name)>(dlsym(lib, #name)); if (name == nullptr) { std::fprintf(stderr, "missing %s\n", #name); return 2; }
   SYM(fcsa_forward) SYM(fcsa_backward) SYM(fcsa_forward_workspace_bytes) SYM(fcsa_backward_workspace_bytes) SYM(fcsa_forward_needs_qn)
   SYM(fcsa_debug_forward_form) SYM(fcsa_debug_kv_group_form) SYM(fcsa_last_error)
+  SYM(fcsa_forward_varlen) SYM(fcsa_backward_varlen) SYM(fcsa_backward_varlen_workspace_bytes)
   std::map<int, int> dev_of_cus;      // cu_count() caches per device: one fake device per CU count
   char line[512];
   while (std::fgets(line, sizeof(line), stdin) != nullptr) {
     int cus, dtype, D, B, H, Hk, N, M, causal, mask, bias, l2, groups, layout, ff, kf;
-    long long rowstride;
+    long long rowstride, total_q = 0, total_k = 0;
     float scale;
-    if (std::sscanf(line, "%d %d %d %d %d %d %d %d %d %d %d %d %d %f %d %lld %d %d", &cus, &dtype, &D, &B, &H, &Hk, &N, &M, &causal, &mask, &bias,
-                    &l2, &groups, &scale, &layout, &rowstride, &ff, &kf) != 18) continue;
+    int used = 0, seqs = 0;
+    if (std::sscanf(line, "%d %d %d %d %d %d %d %d %d %d %d %d %d %f %d %lld %d %d%n", &cus, &dtype, &D, &B, &H, &Hk, &N, &M, &causal, &mask, &bias,
+                    &l2, &groups, &scale, &layout, &rowstride, &ff, &kf, &used) != 18) continue;
+    const bool varlen = std::sscanf(line + used, " varlen %d %lld %lld", &seqs, &total_q, &total_k) == 3;
+    if (std::strstr(line + used, "varlen") != nullptr && (!varlen || seqs != B || mask || bias || layout || rowstride)) {
+      // a malformed varlen line still gets its output line, so a caller that counts or checks lines sees it
+      line[std::strcspn(line, "\n")] = 0;
+      std::printf("%s | rc -1 malformed varlen line (S != B, or mask / bias / layout / rowstride set, or missing totals)\n", line);
+      continue;
+    }
     if (!dev_of_cus.count(cus)) { const int d = (int)dev_of_cus.size(); dev_of_cus[cus] = d; g_cus[d] = cus; }
     g_device = dev_of_cus[cus];
     fcsa_debug_forward_form(ff);
@@ -128,7 +141,8 @@ int main(int argc, char** argv) {
     auto addr = [&]() { next += (uintptr_t)1 << 40; return reinterpret_cast<void*>(next); };
     auto tensor = [&](int heads, int len) {
       fcsa_tensor t{addr(), 0, 0, 0};
-      if (layout == 1) { t.stride2 = (int64_t)heads * D; t.stride1 = D; t.stride0 = (int64_t)len * heads * D; }
+      if (varlen) { t.stride2 = (int64_t)heads * D; t.stride1 = D; t.stride0 = 0; }      // packed [total, heads, D]
+      else if (layout == 1) { t.stride2 = (int64_t)heads * D; t.stride1 = D; t.stride0 = (int64_t)len * heads * D; }
       else { t.stride2 = D; t.stride1 = (int64_t)len * D; t.stride0 = (int64_t)heads * len * D; }
       return t;
     };
@@ -144,12 +158,18 @@ int main(int argc, char** argv) {
     fa.inv_l = static_cast<float*>(addr());
     fa.mask = mask ? static_cast<const uint8_t*>(addr()) : nullptr;
     fa.attn_bias = bias ? addr() : nullptr;
-    if (l2) { fa.norm.qn = addr(); fa.norm.kn = addr(); fa.norm.rq = static_cast<float*>(addr()); fa.norm.rk = static_cast<float*>(addr()); }
-    const size_t fws = fcsa_forward_workspace_bytes(&p);
+    fcsa_varlen vt{static_cast<const int32_t*>(addr()), static_cast<const int32_t*>(addr()), total_q, total_k};
+    fcsa_problem pp = p;          // the packed rows' problem (varlen): what the row kernels and fcsa_forward_needs_qn see
+    if (varlen) { pp.batch = 1; pp.q_len = (int32_t)total_q; pp.k_len = (int32_t)total_k; }
+    if (l2) {
+      fa.norm.qn = !varlen || fcsa_forward_needs_qn(&pp, 1) ? addr() : nullptr;
+      fa.norm.kn = addr(); fa.norm.rq = static_cast<float*>(addr()); fa.norm.rk = static_cast<float*>(addr());
+    }
+    const size_t fws = varlen ? 0 : fcsa_forward_workspace_bytes(&p);      // packed sequences never split the key range
     fa.workspace = fws > 0 ? addr() : nullptr;
     fa.workspace_bytes = fws;
-    std::printf(" ws %zu qn %d%d", fws, fcsa_forward_needs_qn(&p, 0), fcsa_forward_needs_qn(&p, 1));
-    int rc = fcsa_forward(&fa);
+    std::printf(" ws %zu qn %d%d", fws, fcsa_forward_needs_qn(&pp, 0), fcsa_forward_needs_qn(&pp, 1));
+    int rc = varlen ? fcsa_forward_varlen(&fa, &vt) : fcsa_forward(&fa);
     if (rc != 0) std::printf("; rc %d %s", rc, fcsa_last_error());
     fcsa_backward_args ba;
     std::memset(&ba, 0, sizeof(ba));
@@ -158,10 +178,10 @@ int main(int argc, char** argv) {
     ba.mask = fa.mask; ba.attn_bias = fa.attn_bias; ba.norm = fa.norm;
     ba.dq = tensor(H, N); ba.dk = tensor(Hk, M); ba.dv = tensor(Hk, M);
     ba.d_bias = bias ? addr() : nullptr;
-    const size_t bws = fcsa_backward_workspace_bytes(&p);
+    const size_t bws = varlen ? fcsa_backward_varlen_workspace_bytes(&p, &vt) : fcsa_backward_workspace_bytes(&p);
     ba.workspace = addr(); ba.workspace_bytes = bws;
     std::printf(" | ws %zu", bws);
-    rc = fcsa_backward(&ba);
+    rc = varlen ? fcsa_backward_varlen(&ba, &vt) : fcsa_backward(&ba);
     if (rc != 0) std::printf("; rc %d %s", rc, fcsa_last_error());
     std::printf("\n");
   }

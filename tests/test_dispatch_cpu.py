@@ -2,9 +2,12 @@
 calls fcsa_forward / fcsa_backward of the built libfcsa_hip.so with fake device addresses and prints, one line per problem, the workspace
 sizes and every launch (kernel instantiation, grid, block, dynamic LDS, the dispatch fields of its parameters).
 tests/golden/dispatch_launches.txt holds those lines for 252 problems that together launch every kernel instantiation, every split path and
-the group sweep at 256, 304 and 80 CUs; a dispatch change shows up as a diff of it.
+the group sweep at 256, 304 and 80 CUs, followed by a block of packed-sequence problems (fcsa_forward_varlen / fcsa_backward_varlen, lines
+ending "varlen S total_q total_k"): varlen_cover() of varlen_grid(), every instantiation those reach at 256 CUs and every workgroup count
+of the grid's threshold shapes; a dispatch change shows up as a diff of it.
 
-    python tests/test_dispatch_cpu.py LIB [--full]     prints the lines of LIB for the golden problems (or the full grid) to stdout
+    python tests/test_dispatch_cpu.py LIB [--full | --varlen]     prints the lines of LIB for the golden problems (or the full grid, or
+                                                                  the varlen block) to stdout
 """
 import itertools
 import os
@@ -37,8 +40,10 @@ def record(exe, lib, problems):
     return r.stdout
 
 
-def line(cus, dtype, D, B, H, Hk, N, M, causal=0, mask=0, bias=0, l2=0, groups=1, scale=8.0, layout=0, rowstride=0, ff=1, kf=1):
-    return f"{cus} {dtype} {D} {B} {H} {Hk} {N} {M} {causal} {mask} {bias} {l2} {groups} {scale:g} {layout} {rowstride} {ff} {kf}\n"
+def line(cus, dtype, D, B, H, Hk, N, M, causal=0, mask=0, bias=0, l2=0, groups=1, scale=8.0, layout=0, rowstride=0, ff=1, kf=1, packed=None):
+    """one recorder input line; packed = (total_q, total_k): B packed sequences of at most N / M rows (fcsa_forward_varlen)"""
+    tail = "" if packed is None else f" varlen {B} {packed[0]} {packed[1]}"
+    return f"{cus} {dtype} {D} {B} {H} {Hk} {N} {M} {causal} {mask} {bias} {l2} {groups} {scale:g} {layout} {rowstride} {ff} {kf}{tail}\n"
 
 
 def knobs(dtype, D, H, Hk):
@@ -94,6 +99,59 @@ def full_grid():
         # outputs whose (batch, head) is not one flat index ([B, L, H, D]): the split paths that need it step aside
         for dtype, D, causal, hk, (B, H, N, M) in itertools.product((0, 2), (64, 128), (0, 1), (8, 1, 2), ((1, 8, 1024, 8192), (1, 8, 8192, 1024))):
             yield line(cus, dtype, D, B, H, hk, N, M, causal, layout=1)
+    yield from varlen_grid()
+
+
+def varlen_grid(cus=256):
+    """Packed sequences (fcsa_forward_varlen / fcsa_backward_varlen): every dtype x head dim x causal x shift / l2norm mode x K/V grouping
+    on grids of S sequences x H heads x the tiles of max_seqlen on both sides of each threshold of tile_waves and choose_* -- the 7/8 of
+    the CUs of an 8-wave grid, the CU count of 128-position tiles, a last round of 256-position tiles filled up to / beyond 55 %, and the
+    >= 512 queries of the query-split dK/dV.  The dispatch reads only S x H and max_seqlen; the packed totals size the row kernels."""
+    # (l2norm, groups or -1: non-fusable D // 4, scale: 80 = per-row shift)
+    norms = ((0, 1, 1.0), (1, 1, 8.0), (1, 1, 80.0), (1, -1, 8.0))
+    targets = {1, 2}
+    for f in (1 / 2, 7 / 8, 1, 1.5, 1.55, 1.6, 2, 3):
+        for d in (-1, 0, 1):
+            targets.add(max(1, int(cus * f) + d))
+    shapes = set()
+    for t in sorted(targets):
+        for n, ms in ((256, (256, 1000)), (512, (512, 300)), (1024, (1024, 2048))):
+            tiles = (n + 255) // 256
+            if t % tiles == 0 or t < tiles:
+                s = max(1, t // tiles)
+                for m in ms:
+                    shapes.add((s, 1, n, m))
+                    if s % 8 == 0:
+                        shapes.add((s // 8, 8, n, m))
+    for dtype, D, causal, (l2, g, scale), hk, (S, H, N, M) in itertools.product(
+            (0, 1, 2), DIMS, (0, 1), norms, ("H", "H/4", "1"), sorted(shapes)):
+        Hk = {"H": H, "H/4": H // 4, "1": 1}[hk]
+        if Hk < 1 or (hk != "H" and H == 1):
+            continue
+        groups = (D // 4 if g < 0 else g) if l2 else 1
+        yield line(cus, dtype, D, S, H, Hk, N, M, causal, 0, 0, l2, groups, scale, packed=(S * N // 2 + 1, S * M // 2 + 1))
+
+
+def varlen_cover(log):
+    """the lines of a recorded varlen_grid() the golden file keeps: a greedy cover of every kernel instantiation they launch and, per class
+    of rows (element size, rows <= 128 bytes), every count of 256-position workgroups over the queries and over the keys"""
+    def features(ln):
+        f = ln.split()
+        dtype, D, S, H, N, M, causal = (int(x) for x in (f[1], f[2], f[3], f[4], f[6], f[7], f[8]))
+        rows = (dtype != 0, D * (4 if dtype == 0 else 2) <= 128)
+        out = {p.split()[0] for p in ln.split(" | ", 1)[1].replace(" | ", "; ").split("; ")[1:]}
+        for side, n in (("q", N), ("k", M)):
+            t = (n + 255) // 256
+            out.add((side, rows, S * H * ((t + 1) // 2 if causal else t)))
+        return out
+    lines = log.splitlines(keepends=True)
+    feats = [features(ln) for ln in lines]
+    todo, keep = set().union(*feats), []
+    while todo:
+        i = max(range(len(lines)), key=lambda j: (len(feats[j] & todo), -j))
+        keep.append(i)
+        todo -= feats[i]
+    return [lines[i] for i in sorted(keep, key=lambda j: [float(x) for x in lines[j].split(" |")[0].split() if x != "varlen"])]
 
 
 def parse(log):
@@ -141,6 +199,8 @@ def test_launches_match_golden(tmp_path):
 if __name__ == "__main__":
     import tempfile
     lib = os.path.abspath(sys.argv[1])
-    problems = list(dict.fromkeys(full_grid())) if "--full" in sys.argv else list(parse(open(GOLDEN).read()))
+    problems = list(dict.fromkeys(full_grid())) if "--full" in sys.argv else list(dict.fromkeys(varlen_grid())) if "--varlen" in sys.argv \
+        else list(parse(open(GOLDEN).read()))
     with tempfile.TemporaryDirectory() as d:
-        sys.stdout.write(record(build_recorder(d), lib, problems))
+        log = record(build_recorder(d), lib, problems)
+        sys.stdout.write("".join(varlen_cover(log)) if "--varlen" in sys.argv else log)

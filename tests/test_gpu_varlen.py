@@ -11,7 +11,9 @@ import numpy as np
 import pytest
 import torch
 
+import cases as GC
 import tolerances as T
+import varlen_form_cases as VF
 from oracle import cosine_sim_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -79,14 +81,17 @@ def _run(q, k, v, do, lq, lk, kw, max_q=None, max_k=None):
     return o.detach(), q.grad, k.grad, v.grad
 
 
-def _check(dtype, got, ref, lq, lk, label):
+def _check(dtype, got, ref, lq, lk, label, atol_scale=1.0, excess_ref=None):
+    """excess_ref: the reference of the elementwise forward check where it is not ref's o (see test_varlen_forms)"""
     o, dq, dk, dv = got
     ro, rdq, rdk, rdv = ref
     atol, rtol, rel = T.FWD_TOL[dtype]
+    atol *= atol_scale
     go = _np(o)
     for nm, g in zip(("o", "dq", "dk", "dv"), (o, dq, dk, dv)):
         assert torch.isfinite(g).all(), (label, nm)
-    assert T.check(label + "/fwd-excess", dtype, float((np.abs(go - ro) - rtol * np.abs(ro)).max(initial=0.0)), atol), label
+    re = ro if excess_ref is None else excess_ref
+    assert T.check(label + "/fwd-excess", dtype, float((np.abs(go - re) - rtol * np.abs(re)).max(initial=0.0)), atol), label
     assert T.check(label + "/fwd-rel", dtype, _rel(go, ro), rel), label
     bar = T.GRAD_TOL[dtype] * T.SPLIT_GRAD_FACTOR[dtype]
     for nm, g, r in (("dq", dq, rdq), ("dk", dk, rdk), ("dv", dv, rdv)):
@@ -142,6 +147,56 @@ def test_varlen_parity(name, dtype, lq, lk, H, Hk, D, kw):
     _check(dtype, got, _oracle(q, k, v, do, lq, lk, H, Hk, kw), lq, lk, name)
 
 
+@pytest.mark.parametrize("name,dtype,D,lq,lk,H,Hk,mx,kw", VF.CASES, ids=[c[0] for c in VF.CASES])
+def test_varlen_forms(name, dtype, D, lq, lk, H, Hk, mx, kw):
+    """every kernel form a packed call can reach (tests/varlen_form_cases.py; test_varlen_forms_cpu.py checks that the table launches them
+    all): 8-wave 256-position tiles, lean, two-wave dQ, key / query split halves and 4-wave forms, on ragged spans"""
+    q, k, v, do = _packed_inputs(dtype, lq, lk, H, Hk, D, seed=sum(map(ord, name)), l2norm=kw.get("l2norm_qk", True))
+    got = _run(q, k, v, do, lq, lk, kw, max_q=mx, max_k=mx)
+    l2, scale, groups = kw.get("l2norm_qk", True), kw.get("scale", 8.0), kw.get("groups", 1)
+    atol_scale, excess_ref = 1.0, None
+    if GC.dynamic_shift_regime(dtype, scale, groups, l2, False):
+        if dtype == "f32":
+            atol_scale = T.f32_per_row_excess_factor(scale, groups)
+        else:
+            excess_ref = _oracle_forward_kernel_k(q, k, v, lq, lk, H, Hk, kw, mx)
+    _check(dtype, got, _oracle(q, k, v, do, lq, lk, H, Hk, kw), lq, lk, name, atol_scale, excess_ref)
+
+
+def _oracle_forward_kernel_k(q, k, v, lq, lk, H, Hk, kw, mx):
+    """16-bit, per-row shift: the operand-faithful forward reference (exact math on the 16-bit operands) with K^ as the kernel rounded it.
+    The l2norm kernel normalises in float32; where an element of the float64 K^ lies within float32 error of a rounding midpoint, its
+    16-bit K^ is the other neighbour than the oracle's.  At scale x groups = 80 one such element of a dominant key moves an output by
+    up to 0.03 (bf16: 2.7e-2 excess against the 2e-2 bar, with the kernel's K^ 2e-5) -- a property of normalising before rounding, not
+    of a form.  The saved K^ is checked here against the float64 one: equal after rounding except at a few midpoints, one ulp off."""
+    from flash_cosine_sim_attention_amd import _torch_ops
+    scale, groups, causal = kw.get("scale", 8.0), kw.get("groups", 1), kw.get("causal", False)
+    opd = {torch.float16: "f16", torch.bfloat16: "bf16"}[q.dtype]
+    kn = _torch_ops.load().varlen_forward(q, k, v, _cu(lq).cuda(), _cu(lk).cuda(), mx or max(lq), mx or max(lk), float(scale), bool(causal),
+                                          True, int(groups), True)[3]
+    kn = kn.double().cpu().numpy()                                      # [Hk, total_k, D]
+    kh = O.l2norm(_np(k).transpose(1, 0, 2)[None], groups)[0]
+    other = kn != O.round_to(kh, opd)
+    # (midpoints within float32 error: ~1e-5 of the bf16 elements, ~1e-4 of the f16 ones, three more bits; measured 1.4e-4 at most)
+    assert other.mean() <= (1e-4 if opd == "bf16" else 1e-3), ("saved K^ differs from the rounded float64 K^ in", int(other.sum()), "elements")
+    one_ulp = 2.0 ** (-7 if opd == "bf16" else -10)
+    assert (np.abs(kn - kh) <= one_ulp * np.abs(kh))[other].all(), "saved K^ more than one 16-bit step from the float64 K^"
+    G = H // Hk
+    ro = np.zeros(q.shape)
+    nq, nv = _np(q), _np(v)
+    cq, ck = np.concatenate([[0], np.cumsum(lq)]), np.concatenate([[0], np.cumsum(lk)])
+    for s in range(len(lq)):
+        if lq[s] == 0 or lk[s] == 0:
+            continue
+        sq, sk = slice(cq[s], cq[s + 1]), slice(ck[s], ck[s + 1])
+        qh = O.l2norm(nq[sq].transpose(1, 0, 2)[None], groups)
+        khs = np.repeat(kn[:, sk][None], G, axis=1)
+        vs = np.repeat(nv[sk].transpose(1, 0, 2)[None], G, axis=1)
+        o, _ = O.attention_forward_stats(qh, khs, vs, scale=scale, causal=causal, l2norm_qk=False, eps=1e-300, operand_dtype=opd)
+        ro[sq] = o[0].transpose(1, 0, 2)
+    return ro
+
+
 def test_varlen_many_short_sequences_and_large_max_seqlen():
     rng = np.random.default_rng(5)
     lq = rng.integers(0, 40, size=520).tolist()
@@ -171,23 +226,31 @@ def test_varlen_strided_views_of_one_packed_qkv():
     assert torch.equal(leaf.grad[:, 0], ref[1]) and torch.equal(leaf.grad[:, 1], ref[2]) and torch.equal(leaf.grad[:, 2], ref[3])
 
 
-# equal-length sequences, shapes on which the dense dispatch takes no split, fwd2 / fwd3 or group sweep (grids that cover 256 CUs)
+# equal-length sequences, shapes on which the dense dispatch takes no split, fwd2 / fwd3 or group sweep (grids that cover 256 CUs); then
+# the 8-wave forms of varlen_form_cases.BIT_CASES
 BIT_CASES = [
     ("bf16_d64_causal", "bf16", 8, 8, 1024, 64, True),
     ("f16_d64_noncausal", "f16", 4, 8, 1024, 64, False),
     ("bf16_d128_causal", "bf16", 8, 8, 1024, 128, True),
     ("bf16_d32_noncausal", "bf16", 4, 16, 512, 32, False),
-]
+] + VF.BIT_CASES
 
 
 @pytest.mark.parametrize("name,dtype,S,H,L,D,causal", BIT_CASES, ids=[c[0] for c in BIT_CASES])
 def test_varlen_equal_lengths_match_dense_bit_for_bit(name, dtype, S, H, L, D, causal):
     import flash_cosine_sim_attention_amd as F
+    from flash_cosine_sim_attention_amd import _lib
     dt = DT[dtype]
     g = torch.Generator(device="cuda").manual_seed(7)
     q, k, v, do = (torch.randn(S, H, L, D, device="cuda", generator=g).to(dt) for _ in range(4))
     dense = [t.clone().requires_grad_() for t in (q, k, v)]
-    o = F.flash_cosine_sim_attention(*dense, causal=causal)
+    # (D = 128: the dense call must not take the 64-rows-per-wave forward, which packed sequences never run)
+    prev = _lib.forward_form(0) if D == 128 else None
+    try:
+        o = F.flash_cosine_sim_attention(*dense, causal=causal)
+    finally:
+        if prev is not None:
+            _lib.forward_form(prev)
     o.backward(do)
     pack = lambda t: t.permute(0, 2, 1, 3).reshape(S * L, H, D)
     packed = [pack(t).clone().requires_grad_() for t in (q, k, v)]
@@ -241,7 +304,7 @@ BOUNDS = [
     ("f32_d96_groups2_single_kv", "f32", [70, 131], [131, 0], 2, 1, 96, dict(groups=2, scale=4.0)),
     ("bf16_d96_one_group", "bf16", [200, 3], [129, 9], 2, 2, 96, dict(causal=True)),
     ("f16_d64_per_row_shift", "f16", [150, 0, 40], [40, 20, 0], 2, 2, 64, dict(scale=16.0)),
-]
+] + VF.BOUNDS_CASES
 
 
 @pytest.mark.parametrize("name,dtype,lq,lk,H,Hk,D,kw", BOUNDS, ids=[b[0] for b in BOUNDS])

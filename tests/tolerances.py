@@ -28,6 +28,14 @@ GRAD_TOL = {"f16": 1.4e-3, "bf16": 8.5e-3, "f32": 2e-5}
 # smallest splits (tests/test_gpu_split_forward.py), f16 / f32 like everywhere else
 SPLIT_GRAD_FACTOR = {"f16": 1.0, "bf16": 1.4, "f32": 1.0}
 
+# float32 in the per-row-shift regime (scale x groups > 75): the forward's elementwise atol times max(1, scale x groups / 64), the factor
+# test_gpu_online_reference.py applies there -- a logit of magnitude L carries ~2^-24 L into the exponent.  Measured on the packed-sequence
+# forms at scale x groups = 80 (test_gpu_varlen.py::test_varlen_forms): up to 1.28e-5 against the plain 1e-5, each sequence's packed
+# output bit-identical to the dense call on that sequence alone; worst 1.13e-5 of the 1.25e-5 this gives on the committed case table.
+def f32_per_row_excess_factor(scale, groups):
+    return max(1.0, abs(scale) * groups / 64.0)
+
+
 _LOG = os.environ.get("FCSA_TOL_LOG")
 
 
