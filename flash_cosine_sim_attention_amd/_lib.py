@@ -81,12 +81,14 @@ BackwardArgs = _STRUCTS["fcsa_backward_args"]
 KernelStat = _STRUCTS["fcsa_kernel_stat"]
 Varlen = _STRUCTS["fcsa_varlen"]
 KvCache = _STRUCTS["fcsa_kvcache"]
+Window = _STRUCTS["fcsa_window"]
 
 
 EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fcsa_forward_workspace_bytes", "fcsa_forward_needs_qn",
            "fcsa_l2norm", "fcsa_debug", "fcsa_debug_forward_form", "fcsa_debug_kv_group_form", "fcsa_last_error", "fcsa_profile_enable", "fcsa_profile_collect",
            "fcsa_forward_varlen", "fcsa_backward_varlen", "fcsa_backward_varlen_workspace_bytes", "fcsa_forward_kvcache",
-           "fcsa_forward_kvcache_workspace_bytes")
+           "fcsa_forward_kvcache_workspace_bytes", "fcsa_forward_window", "fcsa_backward_window", "fcsa_backward_window_workspace_bytes",
+           "fcsa_forward_kvcache_window", "fcsa_forward_kvcache_window_workspace_bytes")
 
 _lib = None
 
@@ -148,6 +150,17 @@ def load():
     lib.fcsa_forward_kvcache.restype = C.c_int
     lib.fcsa_forward_kvcache_workspace_bytes.argtypes = [C.POINTER(Problem), C.POINTER(KvCache)]
     lib.fcsa_forward_kvcache_workspace_bytes.restype = C.c_size_t
+    if hasattr(lib, "fcsa_forward_window"):      # (an FCSA_LIB build of the same ABI from before the sliding window has none of these)
+        lib.fcsa_forward_window.argtypes = [C.POINTER(ForwardArgs), C.POINTER(Varlen), C.POINTER(Window)]
+        lib.fcsa_forward_window.restype = C.c_int
+        lib.fcsa_backward_window.argtypes = [C.POINTER(BackwardArgs), C.POINTER(Varlen), C.POINTER(Window)]
+        lib.fcsa_backward_window.restype = C.c_int
+        lib.fcsa_backward_window_workspace_bytes.argtypes = [C.POINTER(Problem), C.POINTER(Varlen), C.POINTER(Window)]
+        lib.fcsa_backward_window_workspace_bytes.restype = C.c_size_t
+        lib.fcsa_forward_kvcache_window.argtypes = [C.POINTER(ForwardArgs), C.POINTER(KvCache), C.POINTER(Window)]
+        lib.fcsa_forward_kvcache_window.restype = C.c_int
+        lib.fcsa_forward_kvcache_window_workspace_bytes.argtypes = [C.POINTER(Problem), C.POINTER(KvCache), C.POINTER(Window)]
+        lib.fcsa_forward_kvcache_window_workspace_bytes.restype = C.c_size_t
     lib.fcsa_last_error.argtypes = []
     lib.fcsa_last_error.restype = C.c_char_p
     ver = lib.fcsa_debug(None, 0)

@@ -38,22 +38,27 @@ def _canon_dims(q, k):
     return merged, B, H, Hk, N, M, D
 
 
+def _saved_state(q, rows_q, rows_k, D, l2norm_qk, groups, need_backward):
+    """(inv_l, qn, kn, rq, rk) as the binding returns them; rows_q / rows_k: the leading dims of the q-side / k-side saved tensors --
+    (B, H, N) / (B, Hk, M) for a dense call, (H, total_q) / (Hk, total_k) for packed rows (a batch-1 problem).  Empty where not produced."""
+    f32 = dict(device=q.device, dtype=torch.float32)
+    none32, none = q.new_empty((0,), dtype=torch.float32), q.new_empty((0,))
+    inv_l = torch.empty(rows_q, **f32) if need_backward else none32
+    # (an inference call of the 16-bit kernels saves no normalised q: fcsa_forward_needs_qn, include/fcsa.h)
+    blocks = (D // groups) // 8          # fcsa_capi.hip log2_blocks_per_group: 8 * 2^k features per group, or ONE group of any width (D = 96)
+    fusable = D % groups == 0 and (D // groups) % 8 == 0 and (blocks & (blocks - 1) == 0 or groups == 1)
+    qn = q.new_empty((*rows_q, D)) if (l2norm_qk and (need_backward or q.dtype == torch.float32 or not fusable)) else none
+    kn = q.new_empty((*rows_k, D)) if l2norm_qk else none
+    rq = torch.empty((*rows_q, groups), **f32) if (l2norm_qk and need_backward) else none32
+    rk = torch.empty((*rows_k, groups), **f32) if (l2norm_qk and need_backward) else none32
+    return inv_l, qn, kn, rq, rk
+
+
 def _register_fakes():
     @torch.library.register_fake("fcsa::forward")
     def _(q, k, v, mask, attn_bias, attn_bias_batch_dim, scale, causal, l2norm_qk, groups, need_backward):
         merged, B, H, Hk, N, M, D = _canon_dims(q, k)
-        f32 = dict(device=q.device, dtype=torch.float32)
-        o = q.new_empty(q.shape)
-        none32, none = q.new_empty((0,), dtype=torch.float32), q.new_empty((0,))
-        inv_l = torch.empty((B, H, N), **f32) if need_backward else none32
-        # (an inference call of the 16-bit kernels saves no normalised q: fcsa_forward_needs_qn, include/fcsa.h)
-        blocks = (D // groups) // 8          # fcsa_capi.hip log2_blocks_per_group: 8 * 2^k features per group, or ONE group of any width (D = 96)
-        fusable = D % groups == 0 and (D // groups) % 8 == 0 and (blocks & (blocks - 1) == 0 or groups == 1)
-        qn = q.new_empty((B, H, N, D)) if (l2norm_qk and (need_backward or q.dtype == torch.float32 or not fusable)) else none
-        kn = q.new_empty((B, Hk, M, D)) if l2norm_qk else none
-        rq = torch.empty((B, H, N, groups), **f32) if (l2norm_qk and need_backward) else none32
-        rk = torch.empty((B, Hk, M, groups), **f32) if (l2norm_qk and need_backward) else none32
-        return o, inv_l, qn, kn, rq, rk
+        return (q.new_empty(q.shape), *_saved_state(q, (B, H, N), (B, Hk, M), D, l2norm_qk, groups, need_backward))
 
     @torch.library.register_fake("fcsa::attention")
     def _(q, k, v, mask, attn_bias, attn_bias_batch_dim, scale, causal, l2norm_qk, groups):
@@ -61,18 +66,7 @@ def _register_fakes():
 
     @torch.library.register_fake("fcsa::varlen_forward")
     def _(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, scale, causal, l2norm_qk, groups, need_backward):
-        TQ, H, D = q.shape
-        TK, Hk = k.shape[0], k.shape[1]
-        f32 = dict(device=q.device, dtype=torch.float32)
-        none32, none = q.new_empty((0,), dtype=torch.float32), q.new_empty((0,))
-        inv_l = torch.empty((H, TQ), **f32) if need_backward else none32
-        blocks = (D // groups) // 8          # as fcsa::forward: the packed rows are a batch-1 problem
-        fusable = D % groups == 0 and (D // groups) % 8 == 0 and (blocks & (blocks - 1) == 0 or groups == 1)
-        qn = q.new_empty((H, TQ, D)) if (l2norm_qk and (need_backward or q.dtype == torch.float32 or not fusable)) else none
-        kn = q.new_empty((Hk, TK, D)) if l2norm_qk else none
-        rq = torch.empty((H, TQ, groups), **f32) if (l2norm_qk and need_backward) else none32
-        rk = torch.empty((Hk, TK, groups), **f32) if (l2norm_qk and need_backward) else none32
-        return q.new_empty(q.shape), inv_l, qn, kn, rq, rk
+        return (q.new_empty(q.shape), *_saved_state(q, (q.shape[1], q.shape[0]), (k.shape[1], k.shape[0]), q.shape[2], l2norm_qk, groups, need_backward))
 
     @torch.library.register_fake("fcsa::varlen_backward")
     def _(d_out, o, inv_l, q, k, v, cu_seqlens_q, cu_seqlens_k, qn, kn, rq, rk, max_seqlen_q, max_seqlen_k, scale, causal, l2norm_qk,
@@ -86,6 +80,39 @@ def _register_fakes():
     @torch.library.register_fake("fcsa::kvcache_forward")
     def _(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups):
         return q.new_empty(q.shape)      # (the caches are mutated in place: declared by the schema's (a!) / (b!))
+
+    # sliding-window ops: the shapes of their un-windowed twins
+    @torch.library.register_fake("fcsa::window_forward")
+    def _(q, k, v, scale, causal, l2norm_qk, groups, need_backward, window_left, window_right):
+        B, H, N, D = q.shape
+        return (q.new_empty(q.shape), *_saved_state(q, (B, H, N), (B, k.shape[1], k.shape[2]), D, l2norm_qk, groups, need_backward))
+
+    @torch.library.register_fake("fcsa::window_backward")
+    def _(d_out, o, inv_l, q, k, v, qn, kn, rq, rk, scale, causal, l2norm_qk, groups, window_left, window_right):
+        return q.new_empty(q.shape), k.new_empty(k.shape), v.new_empty(v.shape)
+
+    @torch.library.register_fake("fcsa::window_attention")
+    def _(q, k, v, scale, causal, l2norm_qk, groups, window_left, window_right):
+        return q.new_empty(q.shape)
+
+    @torch.library.register_fake("fcsa::varlen_window_forward")
+    def _(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, scale, causal, l2norm_qk, groups, need_backward, window_left,
+          window_right):
+        return (q.new_empty(q.shape), *_saved_state(q, (q.shape[1], q.shape[0]), (k.shape[1], k.shape[0]), q.shape[2], l2norm_qk, groups, need_backward))
+
+    @torch.library.register_fake("fcsa::varlen_window_backward")
+    def _(d_out, o, inv_l, q, k, v, cu_seqlens_q, cu_seqlens_k, qn, kn, rq, rk, max_seqlen_q, max_seqlen_k, scale, causal, l2norm_qk,
+          groups, window_left, window_right):
+        return q.new_empty(q.shape), k.new_empty(k.shape), v.new_empty(v.shape)
+
+    @torch.library.register_fake("fcsa::varlen_window_attention")
+    def _(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, scale, causal, l2norm_qk, groups, window_left, window_right):
+        return q.new_empty(q.shape)
+
+    @torch.library.register_fake("fcsa::kvcache_window_forward")
+    def _(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups, window_left,
+          window_right):
+        return q.new_empty(q.shape)
 
     @torch.library.register_fake("fcsa::backward")
     def _(d_out, o, inv_l, q, k, v, mask, attn_bias, qn, kn, rq, rk, attn_bias_batch_dim, scale, causal, l2norm_qk, groups,

@@ -46,9 +46,41 @@ def expand_kv_heads(t: torch.Tensor, heads: int) -> torch.Tensor:
     return t.repeat_interleave(heads // hk, dim=1)
 
 
+def window_sides(window_size, causal):
+    """(left, right) of a sliding window as the loops below use them: None for an unbounded side, `causal` caps right at 0."""
+    left, right = window_index(window_size)
+    return (None if left < 0 else left), (0 if causal else None if right < 0 else right)
+
+
+def window_index(window_size):
+    """(left, right) of a window_size argument as two Python ints >= -1: any integer type (operator.index), no bool, no float."""
+    import operator
+    try:
+        left, right = window_size
+    except (TypeError, ValueError):
+        raise ValueError(f"window_size must be a pair (left, right), got {window_size!r}") from None
+    out = []
+    for side in (left, right):
+        if isinstance(side, bool):
+            raise ValueError(f"window_size sides must be integers, got {window_size!r}")
+        try:
+            side = operator.index(side)
+        except TypeError:
+            raise ValueError(f"window_size sides must be integers, got {window_size!r}") from None
+        if side < -1:
+            raise ValueError(f"window_size sides must be >= 0, or -1 for unbounded, got {window_size!r}")
+        out.append(side)
+    return tuple(out)
+
+
 def attention_forward_cpu(q, k, v, mask=None, attn_bias=None, scale=8.0, groups=1, causal=False, l2norm_qk=True,
-                          attn_bias_batch_dim=False, row_block=256, key_block=1024):
-    """Forward-only blockwise cosine-sim attention on host tensors.  Same argument meaning as the GPU operator."""
+                          attn_bias_batch_dim=False, row_block=256, key_block=1024, window_size=(-1, -1)):
+    """Forward-only blockwise cosine-sim attention on host tensors.  Same argument meaning as the GPU operator.
+    window_size = (left, right): query i sees key j iff i + (M - N) - left <= j <= i + (M - N) + right (-1: unbounded; causal caps
+    right at 0); the key blocks outside a row block's band are never touched."""
+    w_left, w_right = window_sides(window_size, causal)
+    if tuple(window_index(window_size)) != (-1, -1) and (mask is not None or attn_bias is not None):      # (as the C ABI: any window)
+        raise ValueError("a sliding window takes no mask and no attn_bias")
     for name, t in (("q", q), ("k", k), ("v", v), ("attn_bias", attn_bias)):
         if t is not None and t.requires_grad:
             raise RuntimeError(f"{name} requires grad: the CPU path of flash_cosine_sim_attention is forward-only "
@@ -86,19 +118,23 @@ def attention_forward_cpu(q, k, v, mask=None, attn_bias=None, scale=8.0, groups=
     top = torch.full((B, H, N, 1), float("-inf"), dtype=torch.float32)
     for r0 in range(0, N, row_block):
         r1 = min(N, r0 + row_block)
-        last = M if not causal else min(M, r1 + offset)   # keys >= last are invisible to every row of this block
+        last = M if w_right is None else min(M, r1 + offset + w_right)      # keys >= last are invisible to every row of this block
+        first = 0 if w_left is None else min(max(r0 + offset - w_left, 0), max(last, 0))     # ... and so are keys < first
         rows = qf[:, :, r0:r1]
         a, s, t = acc[:, :, r0:r1], total[:, :, r0:r1], top[:, :, r0:r1]
-        for c0 in range(0, max(last, 0), key_block):
+        for c0 in range(first, max(last, 0), key_block):
             c1 = min(last, c0 + key_block)
             logits = torch.matmul(rows, kt[..., c0:c1]) * scale
             if bias is not None:
                 logits = logits + bias[:, :, r0:r1, c0:c1]
             visible = None
-            if causal and c1 - 1 > r0 + offset:           # the block touches the diagonal
-                ii = torch.arange(r0, r1).unsqueeze(1) + offset
-                jj = torch.arange(c0, c1).unsqueeze(0)
-                visible = (jj <= ii)
+            ii = torch.arange(r0, r1).unsqueeze(1) + offset
+            jj = torch.arange(c0, c1).unsqueeze(0)
+            if w_right is not None and c1 - 1 > r0 + offset + w_right:           # the block touches the (right) diagonal
+                visible = (jj <= ii + w_right)
+            if w_left is not None and c0 < r1 - 1 + offset - w_left:              # ... the window's left edge
+                inside = (jj >= ii - w_left)
+                visible = inside if visible is None else (visible & inside)
             if keep_keys is not None:
                 visible = keep_keys[..., c0:c1] if visible is None else (visible & keep_keys[..., c0:c1])
             if visible is not None:
@@ -116,7 +152,8 @@ def attention_forward_cpu(q, k, v, mask=None, attn_bias=None, scale=8.0, groups=
     return out.reshape(out_shape).to(out_dtype)
 
 
-def attention_forward_varlen_cpu(q, k, v, cu_seqlens_q, cu_seqlens_k, scale=8.0, groups=1, causal=False, l2norm_qk=True):
+def attention_forward_varlen_cpu(q, k, v, cu_seqlens_q, cu_seqlens_k, scale=8.0, groups=1, causal=False, l2norm_qk=True,
+                                 window_size=(-1, -1)):
     """Forward-only path of `flash_cosine_sim_attention_varlen` on host tensors: packed q [total_q, H, D], k / v [total_k, Hk, D] and
     validated host tables; each sequence runs through `attention_forward_cpu` as a batch-1 problem, so its rows are exactly what the
     dense CPU path gives for that sequence alone."""
@@ -128,7 +165,7 @@ def attention_forward_varlen_cpu(q, k, v, cu_seqlens_q, cu_seqlens_k, scale=8.0,
         vs = v[ck[s]:ck[s + 1]].permute(1, 0, 2).unsqueeze(0)
         if qs.shape[2] == 0:
             continue
-        o = attention_forward_cpu(qs, ks, vs, scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk)
+        o = attention_forward_cpu(qs, ks, vs, scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, window_size=window_size)
         out[cq[s]:cq[s + 1]] = o[0].permute(1, 0, 2)
     return out
 
@@ -165,7 +202,7 @@ def append_kvcache_cpu(k_cache, v_cache, k_new, v_new, seqlens, block_table=None
 
 
 def attention_forward_kvcache_cpu(q, k_cache, v_cache, k_new, v_new, seqlens, block_table=None, scale=8.0, groups=1, causal=False,
-                                  l2norm_qk=True):
+                                  l2norm_qk=True, window_size=(-1, -1)):
     """Forward-only path of `flash_cosine_sim_attention_with_kvcache` on host tensors: the append as an indexed copy, then the dense CPU
     forward of every sequence over its first L_b = seqlens[b] + N_new cached positions (o = 0 where L_b == 0).  seqlens: host ints."""
     if k_new is not None:
@@ -177,5 +214,6 @@ def attention_forward_kvcache_cpu(q, k_cache, v_cache, k_new, v_new, seqlens, bl
         if length == 0 or q.shape[2] == 0:
             continue
         kb, vb = cache_gather(k_cache, b, length, block_table), cache_gather(v_cache, b, length, block_table)
-        out[b:b + 1] = attention_forward_cpu(q[b:b + 1], kb, vb, scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk)
+        out[b:b + 1] = attention_forward_cpu(q[b:b + 1], kb, vb, scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk,
+                                             window_size=window_size)
     return out

@@ -51,11 +51,12 @@ FCSA_TRACE_SITE(dkv)
 // =============================================================================================
 // MODE: 0 = every pair valid, 1 = causal diagonal tiles (select per logit), 2 = key mask / ragged tail of a non-causal launch
 // (rank-1 MFMA per block, key_mask_rank1)
-template <typename T, int D, int MODE, bool BIAS, bool TWO>
+// WIN (sliding window, MODE 1): the select also clears the keys left of the row's window, j < i + dlo
+template <typename T, int D, int MODE, bool BIAS, bool TWO, bool WIN = false>
 FCSA_DEV void dq_tile(const char* kt, const char* vt, const FragAddr<T, D>& fa,
                       const u32x4 (&qf)[TileGeom<D, Traits<T>::ES>::KS], const u32x4 (&dof)[TileGeom<D, Traits<T>::ES>::KS],
                       f32x16 (&dq)[TileGeom<D, Traits<T>::ES>::DB], float lc, float delta, const BwdParams& p, uint64_t word,
-                      uint32_t ncm, int i, int j0, int diff, const char* bias_row, int m_lim) {
+                      uint32_t ncm, int i, int j0, int diff, const char* bias_row, int m_lim, int dlo = 0) {
   typedef TileGeom<D, Traits<T>::ES> G;
   typedef Traits<T> TR;
   constexpr bool MASKED = MODE == 1, KEYM = MODE == 2;
@@ -65,6 +66,7 @@ FCSA_DEV void dq_tile(const char* kt, const char* vt, const FragAddr<T, D>& fa,
     uint32_t w = 0xffffffffu;
     if constexpr (MASKED)
       w = ((uint32_t)(word >> (32 * jb)) >> (4 * fa.hi)) & (le_mask(i + diff - (j0 + 32 * jb + 4 * fa.hi)) | ncm);
+    if constexpr (MASKED && WIN) w &= ge_mask(i + dlo - (j0 + 32 * jb + 4 * fa.hi));
     // request every row fragment of this 32-key block first (just-in-time ds_read_b128 in front of their
     // dependent MFMA were the most expensive item of the forward tile, see fwd_tile)
     // (requests are batched PF k-steps at a time so the live fragments stay within the register budget)
@@ -126,11 +128,11 @@ template <typename T, int D> struct DqPipe {
   }
 };
 
-template <typename T, int D, int MODE>
+template <typename T, int D, int MODE, bool WIN = false>
 FCSA_DEV void dq_tile_pipe(const char* kt, const char* vt, const char* knext, const char* vnext, int next_tile, int t,
                            const FragAddr<T, D>& fa, const u32x4 (&qf)[TileGeom<D, Traits<T>::ES>::KS],
                            const u32x4 (&dof)[TileGeom<D, Traits<T>::ES>::KS], f32x16 (&dq)[TileGeom<D, Traits<T>::ES>::DB],
-                           float lc, float delta, uint64_t word, uint32_t ncm, int i, int j0, int diff, DqPipe<T, D>& pp_) {
+                           float lc, float delta, uint64_t word, uint32_t ncm, int i, int j0, int diff, DqPipe<T, D>& pp_, int dlo = 0) {
   typedef TileGeom<D, Traits<T>::ES> G;
   typedef Traits<T> TR;
   constexpr bool MASKED = MODE == 1, KEYM = MODE == 2;
@@ -140,6 +142,7 @@ FCSA_DEV void dq_tile_pipe(const char* kt, const char* vt, const char* knext, co
     uint32_t w = 0xffffffffu;
     if constexpr (MASKED)
       w = ((uint32_t)(word >> (32 * jb)) >> (4 * fa.hi)) & (le_mask(i + diff - (j0 + 32 * jb + 4 * fa.hi)) | ncm);
+    if constexpr (MASKED && WIN) w &= ge_mask(i + dlo - (j0 + 32 * jb + 4 * fa.hi));
     FCSA_FENCE();
     // ---- M1
     f32x16 s, dp;
@@ -235,9 +238,12 @@ template <typename T, int D, int NW, int BMQ, bool BIAS, bool LEAN, bool RING, b
 // KSPLIT (8 waves, the two-wave tile with or without a bias, SUB = 2): the workgroup owns 128 query rows and its wave halves split the KEYS -- waves 0-3 take
 // the even 64-key tile of a stage, waves 4-7 the odd one -- and add their dQ partials through the LDS at the end of the pass (see
 // fwd_kernel, KSPLIT): for grids of at most one 128-row workgroup per CU, whose four waves would each have a SIMD to themselves.
-template <typename T, int D, int NW, bool BIAS, int SUB, bool TWO, bool KM, bool KSPLIT = false>
-__global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const BwdParams p_) {
-  BwdParams p = p_;      // a varlen launch rebinds it to the workgroup's sequence (varlen_bind); dense launches use it as given
+// WIN (bwd_dq_win_kernel; never BIAS / KM, no split): a sliding window, as in fwd_kernel -- every pass runs on the keys of its row tile's
+// band (win_key_window: the split-key sub-problem [k_lo, k_lo + Mk)), tile loops select | plain | select
+template <typename T, int D, int NW, bool BIAS, int SUB, bool TWO, bool KM, bool KSPLIT, bool WIN>
+FCSA_DEV void bwd_dq_body(const std::conditional_t<WIN, BwdWinParams, BwdParams>& p_) {
+  static_assert(!WIN || (!BIAS && !KM), "sliding window: no bias, the per-logit select");
+  std::conditional_t<WIN, BwdWinParams, BwdParams> p = p_;      // a varlen launch rebinds it to the workgroup's sequence (varlen_bind); dense launches use it as given
   static_assert(!KSPLIT || (NW == 8 && TWO && SUB == 2 && Traits<T>::ES == 2), "key-split form: 8 waves, two-wave tile, 16 bit, 2 tiles per stage");
   // (same type and value as p.causal: the causal instantiations compile to what they were.  The key-split form's !KM twin is only ever
   //  launched causal -- choose_dq -- and says so: at 256-byte rows the kernel sits at its 256 registers)
@@ -273,6 +279,7 @@ __global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const Bw
   int k_lo = 0, Mk = p.M;
   if (p.dq_splits > 1 && !causal) key_split(p.M, (int)blockIdx.y, p.dq_splits, BN, k_lo, Mk);
   int diff = p.M - p.N - k_lo;
+  int dlo = 0;                                      // WIN: the left edge's diagonal (key j of the sub-problem is visible from j >= i + dlo)
   const uint32_t ncm = causal ? 0u : 0xffffffffu;   // OR-ed into the causal bit mask: all ones when not causal
   Trace ts;
   ts.reset();
@@ -310,6 +317,11 @@ __global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const Bw
         key_split_causal(p.N, p.M, m0_, BM, (int)blockIdx.y, p.dq_splits, BN, k_lo, Mk);
         diff = p.M - p.N - k_lo;
       }
+    }
+    if constexpr (WIN) {
+      win_key_window(p.N, p.M, m0_, BM, p.win_lo, p.win_hi, BN, k_lo, Mk);
+      diff = p.M - p.N + p.win_hi - k_lo;
+      dlo = p.M - p.N - p.win_lo - k_lo;
     }
     nt_ = key_tiles(Mk, m0_, BM, diff, causal, BN);
   };
@@ -472,6 +484,8 @@ __global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const Bw
     if (causal) t_split = min(t_split, max(0, mw + diff + 1) / BN);
     t_split = min(t_split, nt);
   }
+  int t_front = 0;      // WIN: tiles [0, t_front) cross the window's left edge for this wave (select), [t_front, t_split) are plain
+  if constexpr (WIN) win_unmasked_tiles(Mk, nt, mw, 32, diff, dlo, BN, t_front, t_split);
 
   tr.loop_begin();
   DqPipe<T, D> pipe;
@@ -529,12 +543,14 @@ __global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const Bw
       if constexpr (TR::ES == 2 && !BIAS && !TWO) {      // pipelined tile: one wave per SIMD only
         bool skip = false;
         if constexpr (MASKED) skip = causal && (j0 > mw + 31 + diff);
+        if constexpr (MASKED && WIN) skip = skip || (j0 + BN - 1 < mw + dlo);      // (left of the window of every row of the wave)
         const bool next_here = !last_of_stage;              // the next key tile sits in this stage's buffer
-        if (!skip) dq_tile_pipe<T, D, tile_mode<MODE>()>(kcur, vcur, next_here ? kcur + TILE_B : kcur, next_here ? vcur + TILE_B : vcur,
-                                              next_here ? t + 1 : -1, t, fa, qf, dof, dq, lc, delta, word, ncm, i, j0, diff, pipe);
+        if (!skip) dq_tile_pipe<T, D, tile_mode<MODE>(), WIN>(kcur, vcur, next_here ? kcur + TILE_B : kcur, next_here ? vcur + TILE_B : vcur,
+                                              next_here ? t + 1 : -1, t, fa, qf, dof, dq, lc, delta, word, ncm, i, j0, diff, pipe, dlo);
       } else if constexpr (MASKED) {
-        const bool skip = causal && (j0 > mw + 31 + diff);
-        if (!skip) dq_tile<T, D, tile_mode<MODE>(), BIAS, TWO>(kcur, vcur, fa, qf, dof, dq, lc, delta, p, word, ncm, i, j0, diff, bias_row, Mk);
+        bool skip = causal && (j0 > mw + 31 + diff);
+        if constexpr (WIN) skip = skip || (j0 + BN - 1 < mw + dlo);
+        if (!skip) dq_tile<T, D, tile_mode<MODE>(), BIAS, TWO, WIN>(kcur, vcur, fa, qf, dof, dq, lc, delta, p, word, ncm, i, j0, diff, bias_row, Mk, dlo);
       } else {
         dq_tile<T, D, 0, BIAS, TWO>(kcur, vcur, fa, qf, dof, dq, lc, delta, p, 0, ncm, i, j0, diff, bias_row, Mk);
       }
@@ -568,7 +584,16 @@ __global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const Bw
     }
   };
   tr.mark(pass, 1);
-  if constexpr (!KSPLIT) {
+  if constexpr (WIN && !KSPLIT) {
+    // select [0, t_front) | plain [t_front, t_split) | select [t_split, nt): the two loop bodies once each, walked twice
+    int sb = 0, se = t_front, ub = t_front, ue = t_split;
+#pragma nounroll
+    for (int seg = 0; seg < 2; ++seg) {
+      run(std::integral_constant<int, 1>{}, sb, se);
+      run(std::integral_constant<int, 0>{}, ub, ue);
+      sb = t_split; se = nt; ub = nt; ue = nt;
+    }
+  } else if constexpr (!KSPLIT) {
     run(std::integral_constant<int, 0>{}, 0, t_split);
     tr.mark(pass, 2);
     run(std::integral_constant<int, KM ? 2 : 1>{}, t_split, nt);
@@ -602,15 +627,27 @@ __global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const Bw
       }
       bool skip = t >= nt;
       if constexpr (MODE == 1) skip = skip || (causal && j0 > mw + 31 + diff);
-      if (!skip) dq_tile<T, D, tile_mode<MODE>(), BIAS, TWO>(kcur, vcur, fa, qf, dof, dq, lc, delta, p, word, ncm, i, j0, diff, bias_row, Mk);
+      if constexpr (MODE == 1 && WIN) skip = skip || (j0 + BN - 1 < mw + dlo);
+      if (!skip) dq_tile<T, D, tile_mode<MODE>(), BIAS, TWO, WIN>(kcur, vcur, fa, qf, dof, dq, lc, delta, p, word, ncm, i, j0, diff, bias_row, Mk, dlo);
       if (more) dma_wait();
       FCSA_BAR_BEGIN(tr);
       __syncthreads();
       FCSA_BAR_END(tr);
     };
+    if constexpr (WIN) {
+      const int u_front = min(nst, max(0, (t_front - half + 1) / 2)), u_end = max(u_front, u_split);
+      int sb = 0, se = u_front, ub = u_front, ue = u_end;
+#pragma nounroll
+      for (int seg = 0; seg < 2; ++seg) {
+        for (int u = sb; u < se; ++u) stage(std::integral_constant<int, 1>{}, u);
+        for (int u = ub; u < ue; ++u) stage(std::integral_constant<int, 0>{}, u);
+        sb = u_end; se = nst; ub = nst; ue = nst;
+      }
+    } else {
     for (int u = 0; u < u_split; ++u) stage(std::integral_constant<int, 0>{}, u);
     tr.mark(pass, 2);
     for (int u = u_split; u < nst; ++u) stage(std::integral_constant<int, KM ? 2 : 1>{}, u);
+    }
   }
   tr.mark(pass, 3);
   tr.loop_end();
@@ -659,6 +696,16 @@ __global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const Bw
   tr.mark(pass, 4);
   }   // pass
   tr.finish(ts, wave, (wave & 2) == 0, trace_row8(wave));      // pass intervals: prologue | unmasked tiles | masked tiles | epilogue
+}
+
+template <typename T, int D, int NW, bool BIAS, int SUB, bool TWO, bool KM, bool KSPLIT = false>
+__global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const BwdParams p_) {
+  bwd_dq_body<T, D, NW, BIAS, SUB, TWO, KM, KSPLIT, false>(p_);
+}
+// the sliding-window forms (launch_dq_nw, p.window): an entry point of their own, so that bwd_dq_kernel's instantiations are what they were
+template <typename T, int D, int NW, int SUB, bool TWO, bool KSPLIT>
+__global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_win_kernel(const BwdWinParams p_) {
+  bwd_dq_body<T, D, NW, false, SUB, TWO, false, KSPLIT, true>(p_);
 }
 
 // =============================================================================================
@@ -860,13 +907,14 @@ static hipError_t launch_dbias_t(const BwdParams& p, hipStream_t s) {
 // fragments this is what lets the kernel run two waves per SIMD at 16-bit D = 96 / 128.
 // MODE: 0 / 1 as in dq_tile; 2 = key mask of a non-causal launch: the lanes ARE the keys here (S = Q K^T, columns = keys), so the
 // rank-1 term is ones (A, query rows) x this lane's 0 / -inf (B): `kmb` = the B operand's k-slot-0 register pair, set up once per pass
-template <typename T, int D, int BMQ, int MODE, bool BIAS, bool LEAN = false>
+// WIN (sliding window, MODE 1): the select also clears the queries past the key's window, i > j - dlo
+template <typename T, int D, int BMQ, int MODE, bool BIAS, bool LEAN = false, bool WIN = false>
 FCSA_DEV void dkv_tile(const char* qt, const char* dot, const float* lcs, const float* dls, const FragAddr<T, D>& fa,
                        const u32x4 (&kf)[TileGeom<D, Traits<T>::ES>::KS], const u32x4 (&vf)[TileGeom<D, Traits<T>::ES>::KS],
                        f32x16 (&dk)[TileGeom<D, Traits<T>::ES>::DB], f32x16 (&dv)[TileGeom<D, Traits<T>::ES>::DB],
                        const BwdParams& p, uint32_t kmask, uint32_t ncm, int j, int i0, int diff, const char* bias_col, Trace& ts,
                        BiasBlock<T>& bb, char* bscr, const char* bias_blk, bool bvec, int next_i0, int lane, const char* vown = nullptr,
-                       int vrow0 = 0, bool young = false) {
+                       int vrow0 = 0, bool young = false, int dlo = 0) {
   typedef TileGeom<D, Traits<T>::ES> G;
   typedef Traits<T> TR;
   constexpr bool MASKED = MODE == 1, KEYM = MODE == 2;
@@ -888,6 +936,7 @@ FCSA_DEV void dkv_tile(const char* qt, const char* dot, const float* lcs, const 
     // Branch-free and before the MFMA chains on purpose (see fwd_tile).
     uint32_t w = 0xffffffffu;
     if constexpr (MASKED) w = kmask & (ge_mask(j - diff - (i0 + 32 * ib + 4 * fa.hi)) | ncm);
+    if constexpr (MASKED && WIN) w &= le_mask(j - dlo - (i0 + 32 * ib + 4 * fa.hi));
     f32x16 s, dp;
 #pragma unroll
     for (int rq = 0; rq < 4; ++rq) {      // per-query log-normaliser and -delta (negated at staging) as the accumulators' initial values
@@ -989,12 +1038,12 @@ struct DkvPipe {
 // for the others, phase trace.)  `fresh`: nothing is in flight for this tile (first tile of a pass, or the previous one was skipped).
 // QS (query-split form of the kernel): this wave works on BMQ rows of a staged tile of 2 * BMQ, starting `hq` rows (`hoff` bytes) into it;
 // qt / dot / lcs / dls point at its share already, `nxt` at the next staged tile's start
-template <typename T, int D, int BMQ, int MODE, bool RING = false, bool QS = false>
+template <typename T, int D, int BMQ, int MODE, bool RING = false, bool QS = false, bool WIN = false>
 FCSA_DEV void dkv_tile_pipe(const char* qt, const char* dot, const float* lcs, const float* dls, const FragAddr<T, D>& fa,
                             const u32x4 (&kf)[TileGeom<D, Traits<T>::ES>::KS], const u32x4 (&vf)[TileGeom<D, Traits<T>::ES>::KS],
                             f32x16 (&dk)[TileGeom<D, Traits<T>::ES>::DB], f32x16 (&dv)[TileGeom<D, Traits<T>::ES>::DB],
                             uint32_t kmask, uint32_t ncm, int j, int i0, int diff, Trace& ts, DkvPipe<T, D, BMQ>& pp_, bool fresh = true,
-                            const char* nxt = nullptr, bool young = false, int hoff = 0, int hq = 0) {
+                            const char* nxt = nullptr, bool young = false, int hoff = 0, int hq = 0, int dlo = 0) {
   typedef TileGeom<D, Traits<T>::ES> G;
   typedef Traits<T> TR;
   constexpr bool MASKED = MODE == 1, KEYM = MODE == 2;
@@ -1004,6 +1053,7 @@ FCSA_DEV void dkv_tile_pipe(const char* qt, const char* dot, const float* lcs, c
   for (int ib = 0; ib < NB; ++ib) {
     uint32_t w = 0xffffffffu;
     if constexpr (MASKED) w = kmask & (ge_mask(j - diff - (i0 + 32 * ib + 4 * fa.hi)) | ncm);
+    if constexpr (MASKED && WIN) w &= le_mask(j - dlo - (i0 + 32 * ib + 4 * fa.hi));
     FCSA_FENCE();
     if constexpr (kPrioBwd == 1) {      // (`young` is wave-uniform and lives in an SGPR: a scalar branch around one s_setprio)
       if (ib == 0) { if (young) __builtin_amdgcn_s_setprio(1); }
@@ -1085,9 +1135,12 @@ FCSA_DEV void dkv_tile_pipe(const char* qt, const char* dot, const float* lcs, c
 // head) and, in every pass, walks the kv_group query heads of its group one after the other, each through the same query-tile loop.  dK^ / dV
 // stay in registers across the heads and the epilogue writes the group's sum once (no slabs, no finalize).  The Q / dO stream runs on
 // across the head seam: the tile requested ahead of the last tile of head g is the first tile of head g + 1, so the pipeline does not drain.
-template <typename T, int D, int NW, int BMQ, bool BIAS, bool LEAN, bool KM, bool RING = false, bool QSPLIT = false, bool SWEEP = false>      // KM: not causal, masked tiles in the rank-1 form (see fwd_kernel)
-__global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes || LEAN) ? 2 : 1)) bwd_dkv_kernel(const BwdParams p_) {
-  BwdParams p = p_;      // a varlen launch rebinds it to the workgroup's sequence (varlen_bind); dense launches use it as given
+// WIN (bwd_dkv_win_kernel; never BIAS / KM / SWEEP, no split): a sliding window -- every pass runs on the query tiles [t0, QT) its key tile
+// sees (win_query_tiles), tile loops select | plain | select
+template <typename T, int D, int NW, int BMQ, bool BIAS, bool LEAN, bool KM, bool RING, bool QSPLIT, bool SWEEP, bool WIN>      // KM: not causal, masked tiles in the rank-1 form (see fwd_kernel)
+FCSA_DEV void bwd_dkv_body(const std::conditional_t<WIN, BwdWinParams, BwdParams>& p_) {
+  static_assert(!WIN || (!BIAS && !KM && !SWEEP), "sliding window: no bias, the per-logit select, no group sweep");
+  std::conditional_t<WIN, BwdWinParams, BwdParams> p = p_;      // a varlen launch rebinds it to the workgroup's sequence (varlen_bind); dense launches use it as given
   static_assert(!QSPLIT || (NW == 8 && !LEAN && (RING || BIAS) && BMQ % 64 == 0), "query-split form: 8 waves; pipelined ring tile, or the generic tile with a bias");
   static_assert(!SWEEP || (!BIAS && !QSPLIT && Traits<T>::ES == 2), "group sweep: 16-bit, bias-free, key tiles of whole workgroups");
   const int causal = KM ? 0 : p.causal;      // (same type and value as p.causal: the causal instantiations compile to what they were)
@@ -1125,7 +1178,12 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
   }
   const int KT = tile_count(p.M, BNK);
   const int npass = pair_passes(KT, pt, causal);
-  const int diff = p.M - p.N;
+  int diff_ = p.M - p.N, dlo_ = 0;                     // WIN: the right edge moves the diagonal; dlo: the left edge's diagonal
+  if constexpr (WIN) {                                 //      (query i sees key j iff j - diff <= i <= j - dlo)
+    diff_ = p.M - p.N + p.win_hi;
+    dlo_ = p.M - p.N - p.win_lo;
+  }
+  const int diff = diff_, dlo = dlo_;
   const int64_t rk_bh = (int64_t)b * (p.H / p.kv_group) + hk;      // (batch, K/V head) row block of rk
   Trace ts;
   ts.reset();
@@ -1224,6 +1282,7 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
     if constexpr (!KM && NW == 4 && !LEAN && !QSPLIT && !BIAS) {      // (the form causal split launches take; the others compile to what they were)
       if (p.dkv_splits > 1 && causal) query_split_causal(QT_all, t0_, (int)blockIdx.y, p.dkv_splits, t0_, QT);
     }
+    if constexpr (WIN) win_query_tiles(p.N, p.M, n0_, BNK, p.win_lo, p.win_hi, BMQ, t0_, QT);
   };
   // requests of a pass that need nothing but a free staging buffer 0: first Q / dO tile (DMA form) with its per-query terms, this
   // lane's K / V fragments, its key-mask byte and the inverse norms its epilogue will use
@@ -1383,6 +1442,8 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
     t_m = t0;
     if (causal) t_m = min(QT, max(t0, (nw + 31 - diff - hq + BMQ - 1) / BMQ));      // (QSPLIT: of this wave's rows of the tile)
   }
+  int t_e = QT;         // WIN: tiles [t_e, QT) cross the window's left edge for this wave (select), [t_m, t_e) are plain
+  if constexpr (WIN) win_unmasked_query_tiles(t0, QT, n0 + BNK <= p.M, nw, hq, BMS, BMQ, diff, dlo, t_m, t_e);
   // SWEEP: this wave skips the first tile of every head (see `skip` below): the last tile of a head must not prefetch into it
   const bool head_skip0 = SWEEP && causal && t_m > t0 && t0 * BMQ + hq + BMS - 1 + diff < nw;
 
@@ -1434,31 +1495,32 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
       {
       bool skip = false;
       if constexpr (MASKED) skip = causal && (i0 + hq + BMS - 1 + diff < nw);  // no valid pair for this wave
+      if constexpr (MASKED && WIN) skip = skip || (i0 + hq > nw + 31 - dlo);   // (past the window of every key of the wave)
       if constexpr (PIPE) {
         if constexpr (RING) {
           if (!skip) {
             const bool has_next = t + 1 < QT || (SWEEP && gi + 1 < p.kv_group && !head_skip0);      // (else: the request reads this tile's buffer again and is never used)
             if constexpr (QSPLIT)
-              dkv_tile_pipe<T, D, BMS, tile_mode<MODE>(), true, true>(cur + hoff, cur + TILE_B + hoff, lcs + hq, dls + hq, fa, kf, vf, dk, dv, kmask, ncm, j, i0 + hq, diff, ts,
-                                                          pipe, pipe_tile != t, has_next ? smem + par_nxt * BUF_B : cur, wave >= 4, hoff, hq);
+              dkv_tile_pipe<T, D, BMS, tile_mode<MODE>(), true, true, WIN>(cur + hoff, cur + TILE_B + hoff, lcs + hq, dls + hq, fa, kf, vf, dk, dv, kmask, ncm, j, i0 + hq, diff, ts,
+                                                          pipe, pipe_tile != t, has_next ? smem + par_nxt * BUF_B : cur, wave >= 4, hoff, hq, dlo);
             else
-            dkv_tile_pipe<T, D, BMQ, tile_mode<MODE>(), true>(cur, cur + TILE_B, lcs, dls, fa, kf, vf, dk, dv, kmask, ncm, j, i0, diff, ts, pipe, pipe_tile != t,
-                                                  has_next ? smem + par_nxt * BUF_B : cur, NW == 8 && wave >= 4);
+            dkv_tile_pipe<T, D, BMQ, tile_mode<MODE>(), true, false, WIN>(cur, cur + TILE_B, lcs, dls, fa, kf, vf, dk, dv, kmask, ncm, j, i0, diff, ts, pipe, pipe_tile != t,
+                                                  has_next ? smem + par_nxt * BUF_B : cur, NW == 8 && wave >= 4, 0, 0, dlo);
             pipe_tile = has_next ? (t + 1 < QT ? t + 1 : t0) : -1;      // (SWEEP: the next head starts at t0)
           }
           ring = par_nxt;
         } else {
-          if (!skip) dkv_tile_pipe<T, D, BMQ, tile_mode<MODE>()>(cur, cur + TILE_B, lcs, dls, fa, kf, vf, dk, dv, kmask, ncm, j, i0, diff, ts, pipe, true, nullptr,
-                                                    NW == 8 && wave >= 4);
+          if (!skip) dkv_tile_pipe<T, D, BMQ, tile_mode<MODE>(), false, false, WIN>(cur, cur + TILE_B, lcs, dls, fa, kf, vf, dk, dv, kmask, ncm, j, i0, diff, ts, pipe, true, nullptr,
+                                                    NW == 8 && wave >= 4, 0, 0, dlo);
         }
       } else if constexpr (LEAN) {
-        if (!skip) dkv_tile<T, D, BMQ, tile_mode<MODE>(), false, true>(cur, cur + TILE_B, lcs, dls, fa, kf, vf, dk, dv, p, kmask, ncm, j, i0, diff, nullptr, ts,
-                                                            bb, bscr, nullptr, false, -1, lane, smem + LDS::VOWN, wave * 32, NW == 8 && wave >= 4);
+        if (!skip) dkv_tile<T, D, BMQ, tile_mode<MODE>(), false, true, WIN>(cur, cur + TILE_B, lcs, dls, fa, kf, vf, dk, dv, p, kmask, ncm, j, i0, diff, nullptr, ts,
+                                                            bb, bscr, nullptr, false, -1, lane, smem + LDS::VOWN, wave * 32, NW == 8 && wave >= 4, dlo);
       } else {
         const int next_i0 = more ? i0 + hq + BMQ : -1;      // (QSPLIT: of this wave's rows of the next staged tile)
         if (!skip) {
-          dkv_tile<T, D, BMS, tile_mode<MODE>(), BIAS>(cur + hoff, cur + TILE_B + hoff, lcs + hq, dls + hq, fa, kf, vf, dk, dv, p, kmask, ncm, j, i0 + hq, diff, bias_col, ts, bb, bscr,
-                                            bias_blk, bvec, next_i0, lane);
+          dkv_tile<T, D, BMS, tile_mode<MODE>(), BIAS, false, WIN>(cur + hoff, cur + TILE_B + hoff, lcs + hq, dls + hq, fa, kf, vf, dk, dv, p, kmask, ncm, j, i0 + hq, diff, bias_col, ts, bb, bscr,
+                                            bias_blk, bvec, next_i0, lane, nullptr, 0, false, dlo);
         } else if constexpr (BIAS) {      // the block requested for this tile is not used: request the next tile's first block instead
           if (bvec && more) bb.request(bias_blk, min(next_i0 + (lane & 31), p.N - 1), (int64_t)p.M * TR::ES, fa.hi);
         }
@@ -1478,9 +1540,20 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
   tr.mark(pass, 1);
   tpar = 0;
   for (gi = 0; gi < (SWEEP ? p.kv_group : 1); ++gi) {      // (SWEEP: the heads of the group, in order; dk / dv accumulate across them)
+    if constexpr (WIN) {
+      // select [t0, t_m) | plain [t_m, t_e) | select [t_e, QT): the two loop bodies once each, walked twice
+      int sb = t0, se = t_m, ub = t_m, ue = t_e;
+#pragma nounroll
+      for (int seg = 0; seg < 2; ++seg) {
+        run(std::integral_constant<int, 1>{}, sb, se);
+        run(std::integral_constant<int, 0>{}, ub, ue);
+        sb = t_e; se = QT; ub = QT; ue = QT;
+      }
+    } else {
     run(std::integral_constant<int, KM ? 2 : 1>{}, t0, t_m);
     tr.mark(pass, 2);
     run(std::integral_constant<int, 0>{}, t_m, QT);
+    }
   }
   tr.mark(pass, 3);
   tr.loop_end();
@@ -1535,8 +1608,18 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes ||
   tr.finish(ts, wave, (wave & 2) == 0, trace_row8(wave));      // pass intervals: prologue | masked tiles | unmasked tiles | epilogue
 }
 
+template <typename T, int D, int NW, int BMQ, bool BIAS, bool LEAN, bool KM, bool RING = false, bool QSPLIT = false, bool SWEEP = false>
+__global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes || LEAN) ? 2 : 1)) bwd_dkv_kernel(const BwdParams p_) {
+  bwd_dkv_body<T, D, NW, BMQ, BIAS, LEAN, KM, RING, QSPLIT, SWEEP, false>(p_);
+}
+// the sliding-window forms (launch_dkv_nw, p.window): an entry point of their own, so that bwd_dkv_kernel's instantiations are what they were
+template <typename T, int D, int NW, int BMQ, bool LEAN, bool RING, bool QSPLIT>
+__global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes || LEAN) ? 2 : 1)) bwd_dkv_win_kernel(const BwdWinParams p_) {
+  bwd_dkv_body<T, D, NW, BMQ, false, LEAN, false, RING, QSPLIT, false, true>(p_);
+}
+
 template <typename T, int D, bool BIAS, int NW, bool TWO, bool KSPLIT = false>
-static hipError_t launch_dq_nw(const BwdParams& p, hipStream_t s) {
+static hipError_t launch_dq_nw(const BwdWinParams& p, hipStream_t s) {
   // 128-key stages (one barrier per 128 keys) in the 8-wave form and, with LDS-DMA staging (no staging registers), also for the
   // one-wave-per-SIMD configurations (16-bit D >= 96: one workgroup per CU, the LDS is there)
   // 8-wave form: 256-key stages where they arrive by LDS-DMA (no staging registers), 128-key stages through registers (f32)
@@ -1546,15 +1629,24 @@ static hipError_t launch_dq_nw(const BwdParams& p, hipStream_t s) {
   // (two instantiations, see launch_fwd_nw.  The two-wave form of 256-byte rows sits at its 256 registers: its non-causal
   //  instantiation came out with spill reloads inside the tile loops -- +5.6 % time -- so those launches keep the general kernel)
   constexpr bool GENERAL_ONLY = TWO && D * Traits<T>::ES >= 256;      // (its non-causal twin is not even instantiated)
-  if constexpr (!GENERAL_ONLY) {
-    if (!p.causal) return launch_with_lds<bwd_dq_kernel<T, D, NW, BIAS, SUB, TWO, true, KSPLIT>>(grid, dim3(NW * 64), LDS::TOTAL, s, p);
+  if (p.window) {
+    // (rows wider than 128 bytes never take the two-wave tile under a window -- choose_dq -- so those forms are not compiled)
+    if constexpr (!BIAS && !(TWO && D * Traits<T>::ES > kDq2WBytes)) {
+      if (!p.causal || p.dq_splits > 1 || p.mask != nullptr) return hipErrorInvalidValue;
+      return launch_with_lds<bwd_dq_win_kernel<T, D, NW, SUB, TWO, KSPLIT>>(grid, dim3(NW * 64), LDS::TOTAL, s, p);
+    }
+    return hipErrorInvalidValue;
   }
-  return launch_with_lds<bwd_dq_kernel<T, D, NW, BIAS, SUB, TWO, false, KSPLIT>>(grid, dim3(NW * 64), LDS::TOTAL, s, p);
+  const BwdParams& bp = p;      // (the un-windowed kernels take the BwdParams part alone)
+  if constexpr (!GENERAL_ONLY) {
+    if (!p.causal) return launch_with_lds<bwd_dq_kernel<T, D, NW, BIAS, SUB, TWO, true, KSPLIT>>(grid, dim3(NW * 64), LDS::TOTAL, s, bp);
+  }
+  return launch_with_lds<bwd_dq_kernel<T, D, NW, BIAS, SUB, TWO, false, KSPLIT>>(grid, dim3(NW * 64), LDS::TOTAL, s, bp);
 }
 
 // the instantiation of form f (choose_dq, fcsa_dispatch.h)
 template <typename T, int D, bool BIAS>
-static hipError_t launch_dq_form(DqForm f, const BwdParams& p, hipStream_t s) {
+static hipError_t launch_dq_form(DqForm f, const BwdWinParams& p, hipStream_t s) {
   constexpr int ES = Traits<T>::ES;
   constexpr bool NARROW = D * ES <= kDq2WBytes;      // rows <= 128 bytes: two waves per SIMD whatever the grid
   switch (f) {
@@ -1574,7 +1666,7 @@ static hipError_t launch_dq_form(DqForm f, const BwdParams& p, hipStream_t s) {
 }
 
 template <typename T, int D, bool BIAS, int NW, bool LEAN = false, bool QSPLIT = false, bool SWEEP = false>
-static hipError_t launch_dkv_nw(const BwdParams& p, hipStream_t s) {
+static hipError_t launch_dkv_nw(const BwdWinParams& p, hipStream_t s) {
   // staged query tile: 32 rows for wide feature rows (16-bit D >= 96, f32 D >= 64: VGPR budget of the staging registers),
   // else 64; 128 in the 8-wave form (one workgroup per CU: the LDS is there, and half the barriers per key tile: -4.5%)
   // (the pipelined LDS-DMA form has no staging registers: wide rows can take deeper tiles too -> fragment prefetch across
@@ -1590,9 +1682,17 @@ static hipError_t launch_dkv_nw(const BwdParams& p, hipStream_t s) {
   typedef DkvLds<T, D, NW, BMQ, BIAS, LEAN, RING, QSPLIT> LDS;
   const dim3 grid((unsigned)(p.B * (SWEEP ? p.H / p.kv_group : p.H) * tile_pairs(tile_count(p.M, 32 * LDS::RWAVES), p.causal)),
                   (unsigned)(p.dkv_splits > 1 ? p.dkv_splits : 1));
+  if (p.window) {
+    if constexpr (!BIAS && !SWEEP) {
+      if (!p.causal || p.dkv_splits > 1 || p.mask != nullptr) return hipErrorInvalidValue;
+      return launch_with_lds<bwd_dkv_win_kernel<T, D, NW, BMQ, LEAN, RING, QSPLIT>>(grid, dim3(NW * 64), LDS::TOTAL, s, p);
+    }
+    return hipErrorInvalidValue;
+  }
   // (two instantiations, see launch_fwd_nw)
-  return p.causal ? launch_with_lds<bwd_dkv_kernel<T, D, NW, BMQ, BIAS, LEAN, false, RING, QSPLIT, SWEEP>>(grid, dim3(NW * 64), LDS::TOTAL, s, p)
-                  : launch_with_lds<bwd_dkv_kernel<T, D, NW, BMQ, BIAS, LEAN, true, RING, QSPLIT, SWEEP>>(grid, dim3(NW * 64), LDS::TOTAL, s, p);
+  const BwdParams& bp = p;      // (the un-windowed kernels take the BwdParams part alone)
+  return p.causal ? launch_with_lds<bwd_dkv_kernel<T, D, NW, BMQ, BIAS, LEAN, false, RING, QSPLIT, SWEEP>>(grid, dim3(NW * 64), LDS::TOTAL, s, bp)
+                  : launch_with_lds<bwd_dkv_kernel<T, D, NW, BMQ, BIAS, LEAN, true, RING, QSPLIT, SWEEP>>(grid, dim3(NW * 64), LDS::TOTAL, s, bp);
 }
 
 static std::atomic<int> g_kv_group_mode{1};
@@ -1603,7 +1703,7 @@ int kv_group_mode(int set) {
 
 // the instantiation of form f (choose_dkv, fcsa_dispatch.h)
 template <typename T, int D, bool BIAS>
-static hipError_t launch_dkv_form(DkvForm f, const BwdParams& p, hipStream_t s) {
+static hipError_t launch_dkv_form(DkvForm f, const BwdWinParams& p, hipStream_t s) {
   constexpr int ES = Traits<T>::ES;
   constexpr bool NARROW = D * ES <= kDkv2WBytes;
   switch (f) {
@@ -1625,9 +1725,9 @@ static hipError_t launch_dkv_form(DkvForm f, const BwdParams& p, hipStream_t s) 
   return hipErrorInvalidValue;
 }
 
-static BwdProblem bwd_problem(int dtype, int D, const BwdParams& p, int splits) {
+static BwdProblem bwd_problem(int dtype, int D, const BwdWinParams& p, int splits) {
   return {dtype == 0 ? 4 : 2, D, (int64_t)p.B * p.H, p.N, p.M, p.causal != 0, p.bias != nullptr, splits, p.kv_sweep != 0,
-          p.seq.cu_q != nullptr};
+          p.seq.cu_q != nullptr || p.window != 0, p.window != 0};
 }
 
 hipError_t launch_backward_dbias(int dtype, int D, const BwdParams& p, hipStream_t s) {
@@ -1635,7 +1735,7 @@ hipError_t launch_backward_dbias(int dtype, int D, const BwdParams& p, hipStream
   return dispatch_dtype_d(dtype, D, [&](auto td) { return launch_dbias_t<typename decltype(td)::T, decltype(td)::D>(p, s); });
 }
 
-hipError_t launch_backward_dq(int dtype, int D, const BwdParams& p, hipStream_t s) {
+hipError_t launch_backward_dq(int dtype, int D, const BwdWinParams& p, hipStream_t s) {
   if (p.B * p.H == 0 || p.N == 0) return hipSuccess;
   const DqForm f = choose_dq(bwd_problem(dtype, D, p, p.dq_splits), cu_count());
   return dispatch_dtype_d(dtype, D, [&](auto td) {
@@ -1645,7 +1745,7 @@ hipError_t launch_backward_dq(int dtype, int D, const BwdParams& p, hipStream_t 
   });
 }
 
-hipError_t launch_backward_dkv(int dtype, int D, const BwdParams& p, hipStream_t s) {
+hipError_t launch_backward_dkv(int dtype, int D, const BwdWinParams& p, hipStream_t s) {
   if (p.B * p.H == 0 || p.M == 0) return hipSuccess;
   const DkvForm f = choose_dkv(bwd_problem(dtype, D, p, p.dkv_splits), cu_count());
   return dispatch_dtype_d(dtype, D, [&](auto td) {

@@ -269,8 +269,17 @@ fcsa_tensor packed(fcsa_tensor t) {       // stride0 of a packed tensor is meani
   return t;
 }
 
-int forward_impl(const fcsa_forward_args* a, const VarlenCall* vl);
-int backward_impl(const fcsa_backward_args* a, const VarlenCall* vl);
+// a sliding-window call after the host's normalisation (fcsa::win_normalise): the sides as the kernels take them
+struct WindowCall { int lo, hi; };
+int check_window(const fcsa_window* w, bool mask, bool bias) {
+  if (w == nullptr) return fail(FCSA_ERR_INVALID_ARG, "window: null window");
+  if (w->left < -1 || w->right < -1) return fail(FCSA_ERR_INVALID_ARG, "window: left / right (%d, %d) must be >= 0, or -1 for unbounded", w->left, w->right);
+  if (mask || bias) return fail(FCSA_ERR_INVALID_ARG, "window: mask and attn_bias are not supported with a sliding window");
+  return FCSA_OK;
+}
+
+int forward_impl(const fcsa_forward_args* a, const VarlenCall* vl, const WindowCall* win = nullptr);
+int backward_impl(const fcsa_backward_args* a, const VarlenCall* vl, const WindowCall* win = nullptr);
 
 }  // namespace
 
@@ -318,7 +327,8 @@ int fcsa_debug(char* buf, size_t buf_bytes) {
     snprintf(buf, buf_bytes,
              "libfcsa_hip abi=%d arch=gfx950 dtypes=f32,f16,bf16 dim_head=16,32,64,96,128 "
              "kernels=l2norm,l2norm_pair,fwd(32 rows/wave; lean two-wave form at D=96/128),fwd2(64 rows/wave),fwd3(D=128: 64 rows/wave, 1 wave/SIMD),fwd_ksplit(128 rows, wave halves split the keys),fwd_split+combine,"
-             "fwd_dyn(per-row shift),bwd_dq(+split-key; key-split form on 8 waves),bwd_dkv(+lean; query-split form on 8 waves; grouped-query K/V head sweep),bwd_dbias,finalize,kv_append+decode+decode_combine(kv cache) kv_heads=divisors of heads",
+             "fwd_dyn(per-row shift),bwd_dq(+split-key; key-split form on 8 waves),bwd_dkv(+lean; query-split form on 8 waves; grouped-query K/V head sweep),bwd_dbias,finalize,kv_append+decode+decode_combine(kv cache),"
+             "window(fwd_win,bwd_dq_win,bwd_dkv_win,decode_win: sliding-window forms) kv_heads=divisors of heads",
              FCSA_ABI_VERSION);
   }
   return FCSA_ABI_VERSION;
@@ -384,7 +394,7 @@ static int zero_rows(const char* name, const fcsa_tensor& t, int es, int B, int 
 
 int fcsa_forward(const fcsa_forward_args* a) { return forward_impl(a, nullptr); }
 
-int fcsa_forward_varlen(const fcsa_forward_args* a, const fcsa_varlen* seqs) {
+static int forward_varlen(const fcsa_forward_args* a, const fcsa_varlen* seqs, const WindowCall* win) {
   if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
   if (int rc = check_problem(a->p)) return rc;
   if (int rc = check_varlen(a->p, seqs, a->mask != nullptr, a->attn_bias != nullptr)) return rc;
@@ -392,7 +402,20 @@ int fcsa_forward_varlen(const fcsa_forward_args* a, const fcsa_varlen* seqs) {
   pa.q = packed(pa.q); pa.k = packed(pa.k); pa.v = packed(pa.v); pa.o = packed(pa.o);
   pa.p = packed_problem(a->p, *seqs);
   const VarlenCall vl = {seqs, a->p.batch, a->p.q_len, a->p.k_len};
-  return forward_impl(&pa, &vl);
+  return forward_impl(&pa, &vl, win);
+}
+int fcsa_forward_varlen(const fcsa_forward_args* a, const fcsa_varlen* seqs) { return forward_varlen(a, seqs, nullptr); }
+
+int fcsa_forward_window(const fcsa_forward_args* a, const fcsa_varlen* seqs, const fcsa_window* w) {
+  if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
+  if (int rc = check_problem(a->p)) return rc;
+  if (int rc = check_window(w, a->mask != nullptr, a->attn_bias != nullptr)) return rc;
+  WindowCall win;
+  const fcsa::WinKind kind = fcsa::win_normalise(a->p.q_len, a->p.k_len, a->p.causal != 0, w->left, w->right, win.lo, win.hi);
+  if (kind == fcsa::WinKind::Window) return seqs != nullptr ? forward_varlen(a, seqs, &win) : forward_impl(a, nullptr, &win);
+  fcsa_forward_args na = *a;
+  na.p.causal = kind == fcsa::WinKind::Causal ? 1 : 0;
+  return seqs != nullptr ? fcsa_forward_varlen(&na, seqs) : fcsa_forward(&na);
 }
 
 
@@ -404,11 +427,12 @@ namespace {
 // The plan of a decode call: row tiles of the G x N rows of a K/V head, and the split count of the key range (fcsa::decode_splits: a pure
 // function of the shapes and the CU count, never of device table contents).
 struct DecodePlan { int row_tiles, splits; size_t ws_o, ws_ml, total; };
-DecodePlan decode_plan(const fcsa_problem& p, const fcsa_kvcache& kv) {
+DecodePlan decode_plan(const fcsa_problem& p, const fcsa_kvcache& kv, int win_lo = -1) {
   DecodePlan d;
   const int G = p.kv_heads > 0 ? p.heads / p.kv_heads : 0;
   d.row_tiles = std::max(fcsa::decode_row_tiles(G * p.q_len), 1);
-  const int max_k = std::min(std::max(p.k_len, 0), std::max(kv.capacity, 0));
+  int max_k = std::min(std::max(p.k_len, 0), std::max(kv.capacity, 0));
+  if (win_lo >= 0) max_k = fcsa::win_decode_keys(max_k, p.q_len, win_lo);      // all a sequence reads under a window
   d.splits = fcsa::decode_splits(p.batch, p.kv_heads, d.row_tiles, max_k, p.dim_head, fcsa::cu_count());
   const size_t rows = (size_t)std::max(p.batch, 0) * std::max(p.heads, 0) * std::max(p.q_len, 0);
   d.ws_o = 0;
@@ -463,20 +487,47 @@ size_t fcsa_forward_kvcache_workspace_bytes(const fcsa_problem* p, const fcsa_kv
   return decode_plan(*p, *kv).total;
 }
 
-int fcsa_forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv) {
+// the kernels' window sides of a decode call, or false: the call is fcsa_forward_kvcache itself (`causal` says which)
+static bool decode_window_sides(const fcsa_problem& p, const fcsa_kvcache& kv, const fcsa_window& w, WindowCall& win, int& causal) {
+  const int max_k = std::min(std::max(p.k_len, 0), std::max(kv.capacity, 0));
+  const fcsa::WinKind kind = fcsa::win_normalise(p.q_len, max_k, p.causal != 0, w.left, w.right, win.lo, win.hi);
+  causal = kind == fcsa::WinKind::Causal ? 1 : kind == fcsa::WinKind::Full ? 0 : p.causal;
+  return kind == fcsa::WinKind::Window;
+}
+static int forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv, const WindowCall* win);
+
+size_t fcsa_forward_kvcache_window_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv, const fcsa_window* w) {
+  if (p == nullptr || kv == nullptr || w == nullptr) return 0;
+  WindowCall win;
+  int causal = 0;
+  return decode_window_sides(*p, *kv, *w, win, causal) ? decode_plan(*p, *kv, win.lo).total : decode_plan(*p, *kv).total;
+}
+
+int fcsa_forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv) { return forward_kvcache(a, kv, nullptr); }
+
+int fcsa_forward_kvcache_window(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_window* w) {
+  if (int rc = check_kvcache(a, kv)) return rc;
+  if (int rc = check_window(w, false, false)) return rc;
+  WindowCall win;
+  fcsa_forward_args na = *a;
+  if (!decode_window_sides(a->p, *kv, *w, win, na.p.causal)) return forward_kvcache(&na, kv, nullptr);
+  return forward_kvcache(a, kv, &win);
+}
+
+static int forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv, const WindowCall* win) {
   if (int rc = check_kvcache(a, kv)) return rc;
   const fcsa_problem& p = a->p;
   if (p.batch == 0) return FCSA_OK;
   const int es = elem_size(p.dtype);
   hipStream_t s = static_cast<hipStream_t>(a->stream);
-  const DecodePlan d = decode_plan(p, *kv);
+  const DecodePlan d = decode_plan(p, *kv, win != nullptr ? win->lo : -1);
   const bool rows = p.heads > 0 && p.q_len > 0;
   if (rows) {
     if (a->workspace == nullptr || a->workspace_bytes < d.total)
       return fail(FCSA_ERR_WORKSPACE, "kvcache: workspace too small: %zu < %zu bytes", a->workspace_bytes, d.total);
     if ((reinterpret_cast<uintptr_t>(a->workspace) & 255) != 0) return fail(FCSA_ERR_WORKSPACE, "kvcache: workspace not 256-byte aligned");
   }
-  fcsa::DecodeParams dp;
+  fcsa::DecodeWinParams dp;
   dp.q = view(a->q, es);
   dp.o = view(a->o, es);
   dp.kc = view(kv->k_cache, es);
@@ -499,6 +550,7 @@ int fcsa_forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv) {
   dp.dyn = dynamic_shift(p, false) ? 1 : 0;
   dp.ws_o = static_cast<float*>(a->workspace);
   dp.ws_ml = reinterpret_cast<float*>(static_cast<char*>(a->workspace) + d.ws_ml);
+  if (win != nullptr) { dp.window = 1; dp.win_lo = win->lo; dp.win_hi = win->hi; }
   // 1. the append (before anything reads the cache: same stream), 2. the split partials, 3. their combine
   if (kv->new_len > 0 && kv->capacity > 0) {
     if (int rc = timed("kv_append", "kv append", s, [&] { return fcsa::launch_kv_append(p.dtype, p.dim_head, dp, s); })) return rc;
@@ -512,7 +564,8 @@ int fcsa_forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv) {
 namespace {
 
 // vl != nullptr: packed sequences; a->p is then the problem of the packed rows (packed_problem)
-int forward_impl(const fcsa_forward_args* a, const VarlenCall* vl) {
+// win != nullptr: a sliding window (the windowed kernel forms; no split)
+int forward_impl(const fcsa_forward_args* a, const VarlenCall* vl, const WindowCall* win) {
   if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
   const fcsa_problem& p = a->p;
   if (int rc = check_problem(p)) return rc;
@@ -537,7 +590,7 @@ int forward_impl(const fcsa_forward_args* a, const VarlenCall* vl) {
   hipStream_t s = static_cast<hipStream_t>(a->stream);
   const bool single = p.kv_heads == 1 && p.heads > 1;      // one K/V head: stride-0 head views; grouped K/V: kv_group query heads per K/V head
 
-  fcsa::FwdParams fp;
+  fcsa::FwdWinParams fp;
   fp.kv_group = single ? 1 : p.heads / p.kv_heads;
   bool fuse_q = false;
   fp.q = view(a->q, es);
@@ -576,6 +629,7 @@ int forward_impl(const fcsa_forward_args* a, const VarlenCall* vl) {
   fp.seq = seq_table(vl);
   if (vl != nullptr) { fp.B = vl->batch; fp.N = vl->max_q; fp.M = vl->max_k; }
   fp.causal = p.causal; fp.bias_batch = p.bias_batch_dim;
+  if (win != nullptr) { fp.window = 1; fp.win_lo = win->lo; fp.win_hi = win->hi; fp.causal = 1; }      // (a causal launch with moved diagonals: fcsa_dispatch.h)
   fp.c1 = p.scale * kLog2e;
   const bool has_bias = a->attn_bias != nullptr;
   fp.c2 = exponent_shift(p, has_bias) * kLog2e;
@@ -588,7 +642,7 @@ int forward_impl(const fcsa_forward_args* a, const VarlenCall* vl) {
   fp.G = p.groups; fp.lgm = fuse_q ? log2_blocks_per_group(p) : 0; fp.norm_eps = 1e-12f;
   fp.dyn = dynamic_shift(p, has_bias) ? 1 : 0;      // then inv_l holds log2 of the normaliser
   fp.splits = 1; fp.ws_o = nullptr; fp.ws_l = nullptr;
-  if (a->workspace != nullptr && a->attn_bias == nullptr && vl == nullptr) {
+  if (a->workspace != nullptr && a->attn_bias == nullptr && vl == nullptr && win == nullptr) {
     const int sp = forward_splits(p);
     if (sp > 1 && a->workspace_bytes >= forward_ws_bytes(p, sp) && (reinterpret_cast<uintptr_t>(a->workspace) & 255) == 0) {
       const size_t rows = (size_t)sp * p.batch * p.heads * p.q_len;
@@ -622,7 +676,32 @@ size_t fcsa_backward_varlen_workspace_bytes(const fcsa_problem* p, const fcsa_va
 
 int fcsa_backward(const fcsa_backward_args* a) { return backward_impl(a, nullptr); }
 
-int fcsa_backward_varlen(const fcsa_backward_args* a, const fcsa_varlen* seqs) {
+static int backward_varlen(const fcsa_backward_args* a, const fcsa_varlen* seqs, const WindowCall* win);
+int fcsa_backward_varlen(const fcsa_backward_args* a, const fcsa_varlen* seqs) { return backward_varlen(a, seqs, nullptr); }
+
+size_t fcsa_backward_window_workspace_bytes(const fcsa_problem* p, const fcsa_varlen* seqs, const fcsa_window* w) {
+  if (p == nullptr || w == nullptr) return 0;
+  WindowCall win;
+  const fcsa::WinKind kind = fcsa::win_normalise(p->q_len, p->k_len, p->causal != 0, w->left, w->right, win.lo, win.hi);
+  fcsa_problem np = *p;
+  if (kind != fcsa::WinKind::Window) np.causal = kind == fcsa::WinKind::Causal ? 1 : 0;
+  if (seqs != nullptr) return fcsa_backward_varlen_workspace_bytes(&np, seqs);
+  return kind == fcsa::WinKind::Window ? bwd_layout(np, true).total : bwd_layout(np).total;
+}
+
+int fcsa_backward_window(const fcsa_backward_args* a, const fcsa_varlen* seqs, const fcsa_window* w) {
+  if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
+  if (int rc = check_problem(a->p)) return rc;
+  if (int rc = check_window(w, a->mask != nullptr, a->attn_bias != nullptr || a->d_bias != nullptr)) return rc;
+  WindowCall win;
+  const fcsa::WinKind kind = fcsa::win_normalise(a->p.q_len, a->p.k_len, a->p.causal != 0, w->left, w->right, win.lo, win.hi);
+  if (kind == fcsa::WinKind::Window) return seqs != nullptr ? backward_varlen(a, seqs, &win) : backward_impl(a, nullptr, &win);
+  fcsa_backward_args na = *a;
+  na.p.causal = kind == fcsa::WinKind::Causal ? 1 : 0;
+  return seqs != nullptr ? fcsa_backward_varlen(&na, seqs) : fcsa_backward(&na);
+}
+
+static int backward_varlen(const fcsa_backward_args* a, const fcsa_varlen* seqs, const WindowCall* win) {
   if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
   if (int rc = check_problem(a->p)) return rc;
   if (int rc = check_varlen(a->p, seqs, a->mask != nullptr, a->attn_bias != nullptr || a->d_bias != nullptr)) return rc;
@@ -631,14 +710,15 @@ int fcsa_backward_varlen(const fcsa_backward_args* a, const fcsa_varlen* seqs) {
   pa.dq = packed(pa.dq); pa.dk = packed(pa.dk); pa.dv = packed(pa.dv);
   pa.p = packed_problem(a->p, *seqs);
   const VarlenCall vl = {seqs, a->p.batch, a->p.q_len, a->p.k_len};
-  return backward_impl(&pa, &vl);
+  return backward_impl(&pa, &vl, win);
 }
 
 }  // extern "C"
 
 namespace {
 
-int backward_impl(const fcsa_backward_args* a, const VarlenCall* vl) {
+// win != nullptr: a sliding window (the windowed kernel forms; the plan of a packed call: no split, no group sweep)
+int backward_impl(const fcsa_backward_args* a, const VarlenCall* vl, const WindowCall* win) {
   if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
   const fcsa_problem& p = a->p;
   if (int rc = check_problem(p)) return rc;
@@ -665,7 +745,8 @@ int backward_impl(const fcsa_backward_args* a, const VarlenCall* vl) {
   }
   if (a->inv_l == nullptr) return fail(FCSA_ERR_INVALID_ARG, "inv_l: null pointer");
   if (a->attn_bias == nullptr && a->d_bias != nullptr) return fail(FCSA_ERR_INVALID_ARG, "d_bias without attn_bias");
-  const BwdLayout L = bwd_layout(p, vl != nullptr);
+  const bool no_split = vl != nullptr || win != nullptr;
+  const BwdLayout L = bwd_layout(p, no_split);
   if (a->workspace == nullptr || a->workspace_bytes < L.total)
     return fail(FCSA_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", a->workspace_bytes, L.total);
   if ((reinterpret_cast<uintptr_t>(a->workspace) & 255) != 0) return fail(FCSA_ERR_WORKSPACE, "workspace not 256-byte aligned");
@@ -675,12 +756,12 @@ int backward_impl(const fcsa_backward_args* a, const VarlenCall* vl) {
   const bool grouped = p.kv_heads != p.heads;             // single-headed or grouped-query K/V: dk / dv are sums over query heads
   const BwdCall call = {a->attn_bias != nullptr, a->dq.stride0 == (int64_t)p.heads * a->dq.stride1,
                         a->dk.stride0 == (int64_t)p.heads * a->dk.stride1 && a->dv.stride0 == (int64_t)p.heads * a->dv.stride1};
-  const BwdPlan plan = bwd_plan(p, &call, vl != nullptr);
+  const BwdPlan plan = bwd_plan(p, &call, no_split);
   const int dq_splits = plan.dq_splits, dkv_splits = plan.dkv_splits;
   const bool dq_slab = plan.dq_slab, dk_slab = plan.dk_slab, dv_slab = plan.dv_slab;
   char* ws = static_cast<char*>(a->workspace);
 
-  fcsa::BwdParams bp;
+  fcsa::BwdWinParams bp;
   bp.kv_group = single ? 1 : p.heads / p.kv_heads;
   bp.kv_sweep = plan.kv_sweep ? 1 : 0;
   if (p.l2norm_qk) {
@@ -729,6 +810,7 @@ int backward_impl(const fcsa_backward_args* a, const VarlenCall* vl) {
   bp.seq = seq_table(vl);
   if (vl != nullptr) { bp.B = vl->batch; bp.N = vl->max_q; bp.M = vl->max_k; }
   bp.causal = p.causal; bp.bias_batch = p.bias_batch_dim;
+  if (win != nullptr) { bp.window = 1; bp.win_lo = win->lo; bp.win_hi = win->hi; bp.causal = 1; }
   bp.c1 = p.scale * kLog2e;
   bp.c2 = exponent_shift(p, a->attn_bias != nullptr) * kLog2e;
   bp.invl_log2 = dynamic_shift(p, a->attn_bias != nullptr) ? 1 : 0;

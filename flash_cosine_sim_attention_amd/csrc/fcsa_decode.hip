@@ -228,8 +228,10 @@ template <typename T, int D> struct DecodeRegs {
   }
 };
 
-template <typename T, int D, bool DYN, bool GEN>
-__global__ __launch_bounds__(64) void decode_kernel(DecodeParams p) {
+// WIN (decode_win_kernel): a sliding window -- the key range of the sequence starts at the 32-key block that holds the first key its
+// first query sees (win_decode_first) instead of 0, and the window's two bounds join the visibility test
+template <typename T, int D, bool DYN, bool GEN, bool WIN>
+FCSA_DEV void decode_body(const std::conditional_t<WIN, DecodeWinParams, DecodeParams>& p) {
   typedef DecodeRegs<T, D> R;
   typedef DecodeLds<D, R::ES, GEN> LP;
   constexpr int ES = R::ES, UE = R::UE, NJ = R::NJ, CPR = R::CPR, VCH = R::VCH;
@@ -248,7 +250,13 @@ __global__ __launch_bounds__(64) void decode_kernel(DecodeParams p) {
   const int kvh = id % p.Hk, b = id / p.Hk;
   const int L = decode_len(p.seqlens != nullptr, p.seqlens != nullptr ? p.seqlens[b] : 0, p.new_len, p.capacity);
   int lo, n;
-  decode_window(L, split, p.splits, lo, n);
+  if constexpr (WIN) {
+    const int first = win_decode_first(L, p.N, p.win_lo);
+    decode_window(L - first, split, p.splits, lo, n);
+    lo += first;
+  } else {
+    decode_window(L, split, p.splits, lo, n);
+  }
   const int end = lo + n;
 
   // this lane's query row: the column of every MFMA result
@@ -315,7 +323,8 @@ __global__ __launch_bounds__(64) void decode_kernel(DecodeParams p) {
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) {
         const int key = kb + 16 * sb + 4 * hi + rr;
-        const bool vis = key < end && (!p.causal || key <= last_key);
+        bool vis = key < end && (!p.causal || key <= last_key);
+        if constexpr (WIN) vis = key < end && key <= last_key + p.win_hi && key >= last_key - p.win_lo;
         s[sb][rr] = vis ? s[sb][rr] * smul : -INFINITY;
       }
     }
@@ -392,6 +401,16 @@ __global__ __launch_bounds__(64) void decode_kernel(DecodeParams p) {
     if (hi == 0) *reinterpret_cast<f32x2*>(p.ws_ml + ((int64_t)split * rows + row) * 2) = f32x2{m, l};
   }
   tr.finish(Trace{}, 0, false, 0);
+}
+
+template <typename T, int D, bool DYN, bool GEN>
+__global__ __launch_bounds__(64) void decode_kernel(DecodeParams p) {
+  decode_body<T, D, DYN, GEN, false>(p);
+}
+// the sliding-window form (launch_decode, p.window): an entry point of its own, so that decode_kernel's instantiations are what they were
+template <typename T, int D, bool DYN, bool GEN>
+__global__ __launch_bounds__(64) void decode_win_kernel(DecodeWinParams p) {
+  decode_body<T, D, DYN, GEN, true>(p);
 }
 
 // o = sum_s 2^(m_s - M) P~V_s / sum_s 2^(m_s - M) l_s over the splits of a row (static regime: every m_s is the common shift, weight 1)
@@ -475,7 +494,7 @@ hipError_t launch_kv_append(int dtype, int D, const DecodeParams& p, hipStream_t
   });
 }
 
-hipError_t launch_decode(int dtype, int D, const DecodeParams& p, hipStream_t s) {
+hipError_t launch_decode(int dtype, int D, const DecodeWinParams& p, hipStream_t s) {
   return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
     using T = typename decltype(td)::T;
     constexpr int DD = decltype(td)::D;
@@ -483,7 +502,8 @@ hipError_t launch_decode(int dtype, int D, const DecodeParams& p, hipStream_t s)
     const dim3 grid((unsigned)((int64_t)p.B * p.Hk * p.row_tiles * p.splits));
     auto go = [&](auto dyn, auto gen) -> hipError_t {
       constexpr bool DY = decltype(dyn)::value, GN = decltype(gen)::value;
-      return launch_with_lds<decode_kernel<T, DD, DY, GN>>(grid, dim3(64), DecodeLds<DD, ES, GN>::BYTES, s, p);
+      if (p.window) return launch_with_lds<decode_win_kernel<T, DD, DY, GN>>(grid, dim3(64), DecodeLds<DD, ES, GN>::BYTES, s, p);
+      return launch_with_lds<decode_kernel<T, DD, DY, GN>>(grid, dim3(64), DecodeLds<DD, ES, GN>::BYTES, s, static_cast<const DecodeParams&>(p));
     };
     using Y = std::true_type;
     using N = std::false_type;

@@ -117,6 +117,64 @@ constexpr void query_split_causal(int tiles, int first, int split, int splits, i
   hi = std::min(lo + tps, tiles);
 }
 
+// Sliding-window launches (fcsa_forward_window / fcsa_backward_window): query i of N sees key j of M iff
+//   i + (M - N) - lo <= j <= i + (M - N) + hi
+// with lo / hi the normalised sides of the window (win_normalise: kWinOpen for an unbounded side).  The kernels run such a launch as a causal
+// one whose diagonal is moved by `hi` (diff = M - N + hi; an open right side leaves nothing to mask there) plus a second, mirrored
+// diagonal on the left: per row tile (key tile) the loop and the streams start at the band's first tile and end at its last, and only the
+// tiles an edge crosses take the per-logit select.  The causal pairing of tiles (tile_pairs) is kept: a pair is two tiles of about
+// lo + hi + tile positions each, so it neither helps nor hurts, and the grids, varlen_bind and block_work stay the ones of a causal launch.
+constexpr int kWinOpen = 1 << 28;
+// The host's normalisation (include/fcsa.h, fcsa_window): a side that reaches past the problem's corner -- right >= N - 1: query 0 sees key
+// M - 1; left >= M - 1: query N - 1 sees key 0 -- is open; causal makes the right side 0.  Then (open, open) is the un-windowed problem and
+// (open, 0) the causal one, which today's kernels serve; everything else is a windowed launch.
+enum class WinKind { Full, Causal, Window };
+constexpr WinKind win_normalise(int N, int M, bool causal, int left, int right, int& lo, int& hi) {
+  hi = causal ? 0 : (right < 0 || right >= N - 1) ? kWinOpen : right;
+  lo = (left < 0 || left >= M - 1) ? kWinOpen : left;
+  return lo != kWinOpen ? WinKind::Window : hi == kWinOpen ? WinKind::Full : hi == 0 ? WinKind::Causal : WinKind::Window;
+}
+// forward / dQ: the keys [k_lo, k_lo + len) the row tile [m0, m0 + bm) runs over -- from the `bn`-key tile that holds the first key its
+// first row sees to the last key its last row sees; len == 0: no row of the tile sees a key
+constexpr void win_key_window(int N, int M, int m0, int bm, int lo, int hi, int bn, int& k_lo, int& len) {
+  const int d = M - N, r1 = std::min(m0 + bm, N) - 1;
+  const int first = std::max(m0 + d - lo, 0), last = std::min(r1 + d + hi, M - 1);
+  k_lo = 0;
+  len = 0;
+  if (r1 < m0 || last < first) return;
+  k_lo = first / bn * bn;
+  len = last + 1 - k_lo;
+}
+// ... and of its `nt` tiles (numbered from k_lo) the range [a, b) that needs no select for the `rows` rows from row mw: whole tiles
+// inside the window's keys, at or left of the first row's right edge (diff = M - N + hi - k_lo), at or right of the last row's left edge
+// (dlo = M - N - lo - k_lo).  Tiles [0, a) and [b, nt) take the per-logit select.
+constexpr void win_unmasked_tiles(int len, int nt, int mw, int rows, int diff, int dlo, int bn, int& a, int& b) {
+  const int hi_t = std::min(len / bn, std::max(0, mw + diff + 1) / bn);
+  const int edge = mw + rows - 1 + dlo;
+  a = std::min(edge <= 0 ? 0 : (edge + bn - 1) / bn, nt);
+  b = std::max(a, std::min(hi_t, nt));
+}
+// dK/dV: the query tiles [t0, t1) of `bmq` rows the key tile [n0, n0 + bnk) sees (empty: t0 == t1 == 0)
+constexpr void win_query_tiles(int N, int M, int n0, int bnk, int lo, int hi, int bmq, int& t0, int& t1) {
+  const int d = M - N, k1 = std::min(n0 + bnk, M) - 1;
+  const int first = std::max(n0 - d - hi, 0), last = std::min(k1 - d + lo, N - 1);
+  t0 = 0;
+  t1 = 0;
+  if (k1 < n0 || last < first) return;
+  t0 = first / bmq;
+  t1 = last / bmq + 1;
+}
+// ... and of those the range [a, b) that needs no select for the 32 keys from key nw against rows [hq, hq + bms) of every tile (whole:
+// the key tile lies inside M): below the last key's right-edge diagonal (diff = M - N + hi), above the first key's left-edge one
+// (dlo = M - N - lo).  Tiles [t0, a) and [b, t1) take the per-logit select.
+constexpr void win_unmasked_query_tiles(int t0, int t1, bool whole, int nw, int hq, int bms, int bmq, int diff, int dlo, int& a, int& b) {
+  a = t1;
+  b = t1;
+  if (!whole) return;
+  a = std::min(t1, std::max(t0, (nw + 31 - diff - hq + bmq - 1) / bmq));
+  const int64_t x = (int64_t)nw - dlo - hq - bms + 1;
+  b = std::min<int64_t>(t1, std::max<int64_t>(a, x < 0 ? 0 : x / bmq + 1));
+}
 // Variable-length launches (packed sequences, fcsa_forward_varlen / fcsa_backward_varlen): sequence s owns the packed rows
 // [cu[s], cu[s + 1]).  The grid is the dense one for (batch = sequences, len = max_len); each workgroup reads its sequence's two table
 // entries and works on that span.  The span is clamped so that ANY table contents stay inside the `total` packed rows: a malformed table
@@ -176,6 +234,15 @@ constexpr bool decode_groups_fast(int D, int groups, int unit) {
   return (u & (u - 1)) == 0;
 }
 
+// Sliding window (win_normalise: lo keys to the left): the N queries of a sequence of `len` keys are its last N positions, so its rows read
+// the keys from win_decode_first on (a whole 32-key block boundary), and the split count is sized by the keys a sequence can read
+constexpr int win_decode_first(int len, int N, int lo) {
+  return lo >= kWinOpen ? 0 : std::max(len - N - lo, 0) / kDecodeBlock * kDecodeBlock;
+}
+constexpr int win_decode_keys(int max_k, int N, int lo) {
+  return lo >= kWinOpen ? max_k : (int)std::min<int64_t>(max_k, (int64_t)lo + N + kDecodeBlock - 1);
+}
+
 // workgroups of `tile`-position tiles over `len` positions for `batch_heads` (batch x heads)
 inline int64_t tile_workgroups(int64_t batch_heads, int len, int tile, bool causal) {
   return batch_heads * tile_pairs(tile_count(len, tile), causal);
@@ -222,7 +289,7 @@ struct FwdProblem {
   int splits;
   int64_t q_row_bytes, k_row_bytes, v_row_bytes;      // row strides of q, k, v (the 32-bit offsets of fwd3)
   int wide128_mode;                                   // fcsa_debug_forward_form: 0 = never fwd3
-  bool varlen = false;                                // packed sequences (seq_span): no Fwd2 / Fwd3, no key split
+  bool varlen = false;                                // packed sequences (seq_span), sliding window: no Fwd2 / Fwd3, no key split
 };
 
 // fwd3_kernel (fcsa_fwd3.hip): 16-bit D = 128, static exponent shift, no bias, no key mask, no key split, a grid of 256-row (causal: paired)
@@ -289,7 +356,8 @@ struct BwdProblem {
   bool causal, bias;
   int splits;           // dq_splits / dkv_splits of the launch
   bool kv_sweep;        // the dK/dV launch runs the group sweep (dkv_sweep below, decided by the C ABI)
-  bool varlen = false;  // packed sequences (seq_span): never a split form or the group sweep
+  bool varlen = false;  // packed sequences (seq_span), sliding window: never a split form or the group sweep
+  bool window = false;  // sliding window (the windowed kernel entry points)
 };
 
 // Sweep builds: FCSA_DQ_FORM = 1 row tiles of 8 waves (16-bit D = 96 / 128: four waves, two-wave tile), 2 key-split 8 waves (D = 96 / 128:
@@ -297,6 +365,10 @@ struct BwdProblem {
 inline DqForm choose_dq(const BwdProblem& b, int cus) {
   if (b.splits > 1 && !b.varlen) return DqForm::Waves4;       // split-key path: 128-row tiles x key ranges (the key-split form measured level there)
   const bool narrow = b.D * b.es <= kDq2WBytes, two = dq_can_two_waves(b.es, b.D) && !b.bias;
+  // sliding window, rows wider than 128 bytes: the one-wave pipelined form.  The two-wave tile sits at its 256 registers there, and with the
+  // window's second diagonal and third loop segment it spills into the tile loops (16-bit D = 128: 240 registers to scratch, the
+  // backward twice the time per tile of the dense causal call, profiles/window_ab.txt)
+  if (b.window && !narrow) return DqForm::Waves4;
   if (const int env = sweep_env("FCSA_DQ_FORM"); bwd_ksplit(b.es, b.D, b.bias) && (narrow || two)) {
     if (env == 1) return narrow ? DqForm::Waves8 : DqForm::Waves4Two;
     if (env == 2 && (narrow || b.causal)) return DqForm::KSplit8;

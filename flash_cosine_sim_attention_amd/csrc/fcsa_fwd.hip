@@ -168,12 +168,13 @@ FCSA_DEV void fwd_softmax_block(f32x16& s, SecondB<T>& pb, float& l, f32x16& lac
 // with all four waves bursting their K reads at once).
 // MODE: 0 = every pair valid, 1 = causal tiles on the diagonal (and their ragged tails): select per logit, 2 = key mask / ragged
 // tail of a non-causal problem: rank-1 MFMA per block (key_mask_rank1)
-template <typename T, int D, int MODE, bool BIAS, bool LEAN, bool ONL, typename Mid>
+// WIN (sliding window, MODE 1 only): the select also clears the keys left of the row's window, j < i + dlo
+template <typename T, int D, int MODE, bool BIAS, bool LEAN, bool ONL, bool WIN = false, typename Mid>
 FCSA_DEV void fwd_tile(const char* vt, u32x4 (&kf)[2][TileGeom<D, Traits<T>::ES>::KS], const FragAddr<T, D>& fa,
                        const u32x4 (&qf)[TileGeom<D, Traits<T>::ES>::KS], f32x16 (&o)[TileGeom<D, Traits<T>::ES>::DB],
                        float& l, f32x16& lacc, const FwdParams& p, float& c2row, float& rmax, uint64_t word, uint32_t ncm, int i, int j0, int diff,
                        const char* bias_row, Trace& ts, Mid&& mid, const char* knext, bool more_k, const char* kt,
-                       u32x4 (*braw)[2][2] = nullptr, bool use_raw = false, int next_j0 = -1) {
+                       u32x4 (*braw)[2][2] = nullptr, bool use_raw = false, int next_j0 = -1, int dlo = 0) {
 
   typedef TileGeom<D, Traits<T>::ES> G;
   typedef Traits<T> TR;
@@ -188,6 +189,10 @@ FCSA_DEV void fwd_tile(const char* vt, u32x4 (&kf)[2][TileGeom<D, Traits<T>::ES>
 #pragma unroll
     for (int jb = 0; jb < 2; ++jb)
       w[jb] = ((uint32_t)(word >> (32 * jb)) >> (4 * fa.hi)) & (le_mask(i + diff - (j0 + 32 * jb + 4 * fa.hi)) | ncm);
+    if constexpr (WIN) {
+#pragma unroll
+      for (int jb = 0; jb < 2; ++jb) w[jb] &= ge_mask(i + dlo - (j0 + 32 * jb + 4 * fa.hi));
+    }
   }
 
   if constexpr (LEAN) {
@@ -455,9 +460,13 @@ template <typename T, int D, int NW, bool DYN, bool KSPLIT> struct FwdLds {
 // every SIMD two waves: 256 four-wave workgroups (C2: 4 x 8 x 1024 rows; C5 at D = 128, where the four-wave form runs ONE wave per
 // SIMD whatever the grid) are one wave per SIMD; this form keeps the grid and doubles the waves, and the partner wave hides what the
 // lean form does not prefetch.
-template <typename T, int D, int NW, bool BIAS, bool DYN, bool LEAN, bool KM, bool KSPLIT = false>
-__global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ? 2 : 1)) fwd_kernel(const FwdParams p_) {
-  FwdParams p = p_;      // a varlen launch rebinds it to the workgroup's sequence (varlen_bind); dense launches use it as given
+// WIN (fwd_win_kernel; never BIAS / KM, no split): a sliding window (fcsa_dispatch.h, win_key_window) -- every pass runs on the keys of
+// its row tile's band only, which is the split-key machinery's sub-problem [k_lo, k_lo + Mk) with the diagonals renumbered, and its tile
+// loops are select | plain | select instead of plain | select.
+template <typename T, int D, int NW, bool BIAS, bool DYN, bool LEAN, bool KM, bool KSPLIT, bool WIN>
+FCSA_DEV void fwd_body(const std::conditional_t<WIN, FwdWinParams, FwdParams>& p_) {
+  static_assert(!WIN || (!BIAS && !KM), "sliding window: no bias, the per-logit select");
+  std::conditional_t<WIN, FwdWinParams, FwdParams> p = p_;      // a varlen launch rebinds it to the workgroup's sequence (varlen_bind); dense launches use it as given
   static_assert(!KSPLIT || (NW == 8 && (LEAN != BIAS) && Traits<T>::ES == 2), "key-split form: 8 waves, 16 bit; lean tile, or the generic tile with a bias");
   const int causal = KM ? 0 : p.causal;      // (same type and value as p.causal: the causal instantiations compile to what they were)
   typedef TileGeom<D, Traits<T>::ES> G;
@@ -489,6 +498,7 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ?
   int k_lo = 0, Mk = p.M;
   if (p.splits > 1 && !causal) key_split(p.M, (int)blockIdx.y, p.splits, BN, k_lo, Mk);
   int diff = p.M - p.N - k_lo;                    // cu:1097 seq_len_diff (in the sub-problem's key numbering)
+  int dlo = 0;                                    // WIN: the left edge's diagonal in the same numbering (key j is visible from j >= i + dlo)
   const uint32_t ncm = causal ? 0u : 0xffffffffu;   // OR-ed into the causal bit mask: all ones when not causal
   Trace ts;
   ts.reset();
@@ -502,6 +512,11 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ?
   if (p.splits > 1 && causal) {
     key_split_causal(p.N, p.M, m0, BM, (int)blockIdx.y, p.splits, BN, k_lo, Mk);
     diff = p.M - p.N - k_lo;
+  }
+  if constexpr (WIN) {
+    win_key_window(p.N, p.M, m0, BM, p.win_lo, p.win_hi, BN, k_lo, Mk);
+    diff = p.M - p.N + p.win_hi - k_lo;
+    dlo = p.M - p.N - p.win_lo - k_lo;
   }
   const int nt = key_tiles(Mk, m0, BM, diff, causal, BN);      // key tiles this workgroup needs
 
@@ -631,6 +646,8 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ?
     if (causal) t_split = min(t_split, max(0, mw + diff + 1) / BN);  // needs (t+1)*BN - 1 <= mw + diff
     t_split = min(t_split, nt);
   }
+  int t_front = 0;      // WIN: tiles [0, t_front) cross the window's left edge for this wave (select), [t_front, t_split) are plain
+  if constexpr (WIN) win_unmasked_tiles(Mk, nt, mw, 32, diff, dlo, BN, t_front, t_split);
 
   tr.loop_begin();
   auto run = [&](auto masked_tag, int t_begin, int t_end) {
@@ -705,21 +722,31 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ?
       const bool bfut_ok = BIAS_AHEAD && t + 1 < nt && bias_rows16 && j0 + 2 * BN <= p.M;
       bool skip = false;
       if constexpr (MASKED) skip = causal && (j0 > mw + 31 + diff);              // no valid pair for this wave
+      if constexpr (MASKED && WIN) skip = skip || (j0 + BN - 1 < mw + dlo);      // (left of the window of every row of the wave)
       if (!LEAN && !PREFETCH_K && !skip) request_k(vcur - SUB * TILE_B);
       if (skip) {
         bnext_ok = false;                  // (nothing was requested for the next tile; once a wave skips it skips to the end of the pass)
         mid();
         if (PREFETCH_K && t + 1 < nt) request_k(knxt);
       } else {
-        fwd_tile<T, D, tile_mode<MODE>(), BIAS, LEAN, DYN>(vcur, kf, fa, qf, o, l, lacc, p, c2row, rmax, word, ncm, i, j0, diff, bias_row, ts, mid, knxt, t + 1 < nt,
-                                     vcur - SUB * TILE_B, BIAS_AHEAD ? &bnext : nullptr, bcur_ok, bfut_ok ? j0 + BN : -1);
+        fwd_tile<T, D, tile_mode<MODE>(), BIAS, LEAN, DYN, WIN>(vcur, kf, fa, qf, o, l, lacc, p, c2row, rmax, word, ncm, i, j0, diff, bias_row, ts, mid, knxt, t + 1 < nt,
+                                     vcur - SUB * TILE_B, BIAS_AHEAD ? &bnext : nullptr, bcur_ok, bfut_ok ? j0 + BN : -1, dlo);
         bnext_ok = bfut_ok;
       }
       FCSA_STAMP(ts, 10);
       if constexpr (!MASKED) ts.close(10);     // trace: unmasked tiles only
     }
   };
-  if constexpr (!KSPLIT) {
+  if constexpr (WIN && !KSPLIT) {
+    // select [0, t_front) | plain [t_front, t_split) | select [t_split, nt): the two loop bodies once each, walked twice
+    int sb = 0, se = t_front, ub = t_front, ue = t_split;
+#pragma nounroll
+    for (int seg = 0; seg < 2; ++seg) {
+      run(std::integral_constant<int, 1>{}, sb, se);
+      run(std::integral_constant<int, 0>{}, ub, ue);
+      sb = t_split; se = nt; ub = nt; ue = nt;
+    }
+  } else if constexpr (!KSPLIT) {
     run(std::integral_constant<int, 0>{}, 0, t_split);
     run(std::integral_constant<int, KM ? 2 : 1>{}, t_split, nt);
   } else {
@@ -758,16 +785,28 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ?
       };
       bool skip = t >= nt;
       if constexpr (MODE == 1) skip = skip || (causal && j0 > mw + 31 + diff);
+      if constexpr (MODE == 1 && WIN) skip = skip || (j0 + BN - 1 < mw + dlo);
       if (skip) {
         mid();
         return;
       }
       if constexpr (!LEAN) request_k(buf + half * TILE_B);      // (bias form: the generic tile takes its K fragments from registers; nothing is prefetched across stages)
-      fwd_tile<T, D, tile_mode<MODE>(), BIAS, LEAN, DYN>(buf + (SUB + half) * TILE_B, kf, fa, qf, o, l, lacc, p, c2row, rmax, word, ncm, i, j0, diff, bias_row, ts, mid,
-                                           nullptr, false, buf + half * TILE_B);
+      fwd_tile<T, D, tile_mode<MODE>(), BIAS, LEAN, DYN, WIN>(buf + (SUB + half) * TILE_B, kf, fa, qf, o, l, lacc, p, c2row, rmax, word, ncm, i, j0, diff, bias_row, ts, mid,
+                                           nullptr, false, buf + half * TILE_B, nullptr, false, -1, dlo);
     };
+    if constexpr (WIN) {
+      const int u_front = min(ns, max(0, (t_front - half + 1) / 2)), u_end = max(u_front, u_split);
+      int sb = 0, se = u_front, ub = u_front, ue = u_end;
+#pragma nounroll
+      for (int seg = 0; seg < 2; ++seg) {
+        for (int u = sb; u < se; ++u) stage(std::integral_constant<int, 1>{}, u);
+        for (int u = ub; u < ue; ++u) stage(std::integral_constant<int, 0>{}, u);
+        sb = u_end; se = ns; ub = ns; ue = ns;
+      }
+    } else {
     for (int u = 0; u < u_split; ++u) stage(std::integral_constant<int, 0>{}, u);
     for (int u = u_split; u < ns; ++u) stage(std::integral_constant<int, KM ? 2 : 1>{}, u);
+    }
   }
   tr.mark(pass, 3);
   tr.loop_end();
@@ -837,6 +876,16 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ?
     out[22] = tr.marks[0][0] - tr.t0;
     for (int ps = 0; ps < 2; ++ps) { out[23 + 2 * ps] = tr.first[ps][0]; out[24 + 2 * ps] = tr.first[ps][1]; }
   });
+}
+
+template <typename T, int D, int NW, bool BIAS, bool DYN, bool LEAN, bool KM, bool KSPLIT = false>
+__global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ? 2 : 1)) fwd_kernel(const FwdParams p_) {
+  fwd_body<T, D, NW, BIAS, DYN, LEAN, KM, KSPLIT, false>(p_);
+}
+// the sliding-window forms (launch_fwd_nw, p.window): an entry point of their own, so that fwd_kernel's instantiations are what they were
+template <typename T, int D, int NW, bool DYN, bool LEAN, bool KSPLIT>
+__global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ? 2 : 1)) fwd_win_kernel(const FwdWinParams p_) {
+  fwd_body<T, D, NW, false, DYN, LEAN, false, KSPLIT, true>(p_);
 }
 
 // =============================================================================================
@@ -1186,18 +1235,26 @@ __global__ void __launch_bounds__(256) fwd_combine_kernel(const FwdParams p) {
 }
 
 template <typename T, int D, bool BIAS, int NW, bool DYN, bool LEAN = false, bool KSPLIT = false>
-static hipError_t launch_fwd_nw(const FwdParams& p, hipStream_t s) {
+static hipError_t launch_fwd_nw(const FwdWinParams& p, hipStream_t s) {
   typedef FwdLds<T, D, NW, DYN, KSPLIT> LDS;
   constexpr int BM = 32 * LDS::RWAVES;
   static_assert(!KSPLIT || LDS::TILE_B % 1024 == 0, "key-split form: whole 1 KiB LDS-DMA pieces per tile");
   // two instantiations: causal launches (select per logit on the diagonal tiles) and the others (key masks as a rank-1 MFMA)
   const dim3 grid((unsigned)(p.B * p.H * tile_pairs(tile_count(p.N, BM), p.causal)), (unsigned)(p.splits > 1 ? p.splits : 1));
-  const hipError_t e = p.causal ? launch_with_lds<fwd_kernel<T, D, NW, BIAS, DYN, LEAN, false, KSPLIT>>(grid, dim3(NW * 64), LDS::TOTAL, s, p)
-                                : launch_with_lds<fwd_kernel<T, D, NW, BIAS, DYN, LEAN, true, KSPLIT>>(grid, dim3(NW * 64), LDS::TOTAL, s, p);
+  if (p.window) {
+    if constexpr (!BIAS) {
+      if (!p.causal || p.splits > 1 || p.mask != nullptr) return hipErrorInvalidValue;
+      return launch_with_lds<fwd_win_kernel<T, D, NW, DYN, LEAN, KSPLIT>>(grid, dim3(NW * 64), LDS::TOTAL, s, p);
+    }
+    return hipErrorInvalidValue;
+  }
+  const FwdParams& fp = p;      // (the un-windowed kernels take the FwdParams part alone)
+  const hipError_t e = p.causal ? launch_with_lds<fwd_kernel<T, D, NW, BIAS, DYN, LEAN, false, KSPLIT>>(grid, dim3(NW * 64), LDS::TOTAL, s, fp)
+                                : launch_with_lds<fwd_kernel<T, D, NW, BIAS, DYN, LEAN, true, KSPLIT>>(grid, dim3(NW * 64), LDS::TOTAL, s, fp);
   if (e != hipSuccess) return e;
   if (p.splits > 1) {
     const int64_t items = (int64_t)p.B * p.H * p.N * (D / 8);
-    hipLaunchKernelGGL((fwd_combine_kernel<T, D>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p);
+    hipLaunchKernelGGL((fwd_combine_kernel<T, D>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, fp);
   }
   return hipGetLastError();
 }
@@ -1210,7 +1267,7 @@ static hipError_t launch_fwd2(const FwdParams& p, hipStream_t s) {
 
 // the instantiation of form f (choose_forward, fcsa_dispatch.h)
 template <typename T, int D, bool BIAS, bool DYN>
-static hipError_t launch_fwd_form(FwdForm f, const FwdParams& p, hipStream_t s) {
+static hipError_t launch_fwd_form(FwdForm f, const FwdWinParams& p, hipStream_t s) {
   constexpr int ES = Traits<T>::ES;
   switch (f) {
     case FwdForm::Rows8:
@@ -1233,10 +1290,10 @@ static hipError_t launch_fwd_form(FwdForm f, const FwdParams& p, hipStream_t s) 
   return hipErrorInvalidValue;
 }
 
-hipError_t launch_forward(int dtype, int D, const FwdParams& p, hipStream_t s) {
+hipError_t launch_forward(int dtype, int D, const FwdWinParams& p, hipStream_t s) {
   if (p.B * p.H == 0 || p.N == 0) return hipSuccess;
   const FwdProblem fp = {dtype == 0 ? 4 : 2, D, (int64_t)p.B * p.H, p.N, p.M, p.causal != 0, p.bias != nullptr, p.mask != nullptr, p.dyn != 0,
-                         p.splits, p.q.sn, p.k.sn, p.v.sn, forward_wide128_mode(-1), p.seq.cu_q != nullptr};
+                         p.splits, p.q.sn, p.k.sn, p.v.sn, forward_wide128_mode(-1), p.seq.cu_q != nullptr || p.window != 0};
   const FwdForm f = choose_forward(fp, cu_count());
   if (f == FwdForm::Fwd3) return launch_forward_wide128(dtype, p, s);
   return dispatch_dtype_d(dtype, D, [&](auto td) {

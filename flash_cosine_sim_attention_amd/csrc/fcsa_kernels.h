@@ -48,6 +48,12 @@ struct FwdParams {
   float* ws_l;              // [splits][B*H][N]    f32 partial row sums
   SeqTable seq;             // packed sequences (seq.cu_q != nullptr): no split, no bias, no key mask
 };
+// What the launchers take: FwdParams plus the sliding window.  The windowed kernels (fwd_win_kernel) get the whole block; every other
+// kernel is launched with the FwdParams part alone, so its kernel arguments -- and its code -- are what they were without the feature.
+struct FwdWinParams : FwdParams {
+  int window = 0;           // 1: sliding window (causal is 1 then, no split, no bias, no key mask); sides as win_normalise gives them:
+  int win_lo = 0, win_hi = 0;   //    query i sees key j iff i + M - N - win_lo <= j <= i + M - N + win_hi
+};
 
 struct BwdParams {
   View q, k, v, o, d_out;   // q,k normalised
@@ -78,6 +84,10 @@ struct BwdParams {
   int G, lgm;               // groups; log2(group size / 8)
   float norm_eps;           // 1e-12
   SeqTable seq;             // packed sequences (seq.cu_q != nullptr): no split, no bias, no key mask, no group sweep
+};
+struct BwdWinParams : BwdParams {      // (see FwdWinParams; bwd_dq_win_kernel / bwd_dkv_win_kernel)
+  int window = 0;
+  int win_lo = 0, win_hi = 0;
 };
 
 struct NormParams {         // grouped l2norm forward:  x -> xn, inv_norm
@@ -121,8 +131,12 @@ struct DecodeParams {
   float* ws_o;              // [splits][B*H*N][D] f32 partial P~V
   float* ws_ml;             // [splits][B*H*N][2] f32 (row max in log2 units, row sum)
 };
+struct DecodeWinParams : DecodeParams {      // (see FwdWinParams; decode_win_kernel)
+  int window = 0;           // 1: sliding window, sides as win_normalise gives them (causal: win_hi = 0):
+  int win_lo = 0, win_hi = 0;   //    the query at position t sees key j iff t - win_lo <= j <= t + win_hi
+};
 hipError_t launch_kv_append(int dtype, int D, const DecodeParams& p, hipStream_t s);
-hipError_t launch_decode(int dtype, int D, const DecodeParams& p, hipStream_t s);
+hipError_t launch_decode(int dtype, int D, const DecodeWinParams& p, hipStream_t s);
 hipError_t launch_decode_combine(int dtype, int D, const DecodeParams& p, hipStream_t s);
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE property of a kernel: raise it once per (instantiation, device).
@@ -174,13 +188,13 @@ inline int cu_count() {
 }
 
 // dtype: 1 = f16, 2 = bf16 (fcsa_dtype); returns hipError_t of the launch
-hipError_t launch_forward(int dtype, int D, const FwdParams& p, hipStream_t s);
+hipError_t launch_forward(int dtype, int D, const FwdWinParams& p, hipStream_t s);
 // fcsa_fwd3.hip: the 64-rows-per-wave, one-wave-per-SIMD forward for 16-bit D = 128 (launch_forward dispatches to it)
 int forward_wide128_mode(int set);      // debug knob behind fcsa_debug_forward_form: set < 0 queries; returns the previous value
 hipError_t launch_forward_wide128(int dtype, const FwdParams& p, hipStream_t s);
-hipError_t launch_backward_dq(int dtype, int D, const BwdParams& p, hipStream_t s);
+hipError_t launch_backward_dq(int dtype, int D, const BwdWinParams& p, hipStream_t s);
 hipError_t launch_backward_dbias(int dtype, int D, const BwdParams& p, hipStream_t s);   // d_bias from recomputed dS tiles (after dq: needs delta)
-hipError_t launch_backward_dkv(int dtype, int D, const BwdParams& p, hipStream_t s);
+hipError_t launch_backward_dkv(int dtype, int D, const BwdWinParams& p, hipStream_t s);
 int kv_group_mode(int set);             // debug knob behind fcsa_debug_kv_group_form: set < 0 queries; returns the previous value
 hipError_t launch_l2norm(int dtype, const NormParams& p, hipStream_t s);
 hipError_t launch_l2norm_pair(int dtype, const NormParams& a, const NormParams& b, hipStream_t s);   // q and k in one grid

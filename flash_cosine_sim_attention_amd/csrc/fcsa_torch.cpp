@@ -40,6 +40,12 @@ struct Abi {
   // decoding against a key/value cache: null in a swapped-in library that does not export it (the kvcache op then raises)
   int (*forward_kvcache)(const fcsa_forward_args*, const fcsa_kvcache*) = &fcsa_forward_kvcache;
   size_t (*forward_kvcache_ws)(const fcsa_problem*, const fcsa_kvcache*) = &fcsa_forward_kvcache_workspace_bytes;
+  // sliding window: null in a swapped-in library that does not export it (the window ops then raise)
+  int (*forward_window)(const fcsa_forward_args*, const fcsa_varlen*, const fcsa_window*) = &fcsa_forward_window;
+  int (*backward_window)(const fcsa_backward_args*, const fcsa_varlen*, const fcsa_window*) = &fcsa_backward_window;
+  size_t (*backward_window_ws)(const fcsa_problem*, const fcsa_varlen*, const fcsa_window*) = &fcsa_backward_window_workspace_bytes;
+  int (*forward_kvcache_window)(const fcsa_forward_args*, const fcsa_kvcache*, const fcsa_window*) = &fcsa_forward_kvcache_window;
+  size_t (*forward_kvcache_window_ws)(const fcsa_problem*, const fcsa_kvcache*, const fcsa_window*) = &fcsa_forward_kvcache_window_workspace_bytes;
 } g_abi;
 
 using at::Tensor;
@@ -167,9 +173,23 @@ void check(int rc, const char* what) {
 void* stream_of(const Tensor& t) { return c10::hip::getCurrentHIPStream(t.device().index()).stream(); }
 
 // (o, inv_l, qn, kn, rq, rk); the saved-state tensors are empty (numel 0) where they are not produced
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> forward(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& mask,
-                                                                    const optional<Tensor>& attn_bias, bool attn_bias_batch_dim, double scale,
-                                                                    bool causal, bool l2norm_qk, int64_t groups, bool need_backward) {
+// sliding window of a call (window ops): the library's struct, after the checks every window op shares; nullptr: no window
+struct Win {
+  fcsa_window w;
+  Win(int64_t left, int64_t right) {
+    TORCH_CHECK(g_abi.forward_window != nullptr && g_abi.backward_window != nullptr && g_abi.backward_window_ws != nullptr &&
+                g_abi.forward_kvcache_window != nullptr && g_abi.forward_kvcache_window_ws != nullptr,
+                "sliding window: the loaded libfcsa_hip.so does not export fcsa_forward_window / fcsa_backward_window");
+    TORCH_CHECK_VALUE(left >= -1 && right >= -1, "window_size (", left, ", ", right, "): each side must be >= 0, or -1 for unbounded");
+    w.left = (int32_t)std::min<int64_t>(left, INT32_MAX);
+    w.right = (int32_t)std::min<int64_t>(right, INT32_MAX);
+  }
+};
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> forward_impl(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& mask,
+                                                                         const optional<Tensor>& attn_bias, bool attn_bias_batch_dim, double scale,
+                                                                         bool causal, bool l2norm_qk, int64_t groups, bool need_backward,
+                                                                         const fcsa_window* win) {
   Lap lap;
   const Canon c = canonicalise(q, k, v, mask, attn_bias, attn_bias_batch_dim, causal);
   TORCH_CHECK_VALUE(!l2norm_qk || (groups >= 1 && c.D % groups == 0), "groups (", groups, ") must divide the head dimension (", c.D, ")");
@@ -203,25 +223,43 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> forward(const Tensor&
   a.norm.rk = (l2norm_qk && need_backward) ? rk.data_ptr<float>() : nullptr;
   Tensor ws;
   a.workspace = nullptr; a.workspace_bytes = 0;
-  if (const size_t need = g_abi.forward_ws(&a.p); need > 0) {      // 0 unless the key range is split (grids that cannot fill the chip)
+  size_t fws = g_abi.forward_ws(&a.p);      // 0 unless the key range is split (grids that cannot fill the chip)
+  if (win != nullptr) {      // a window that IS the un-windowed or the causal call splits like that call: room for either
+    fcsa_problem other = a.p;
+    other.causal = !other.causal;
+    fws = std::max(fws, g_abi.forward_ws(&other));
+  }
+  if (const size_t need = fws; need > 0) {
     ws = at::empty({(int64_t)need}, opt.dtype(at::kByte));
     a.workspace = ws.data_ptr(); a.workspace_bytes = need;
   }
   a.stream = stream_of(q);
   lap.mark(1);
-  check(g_abi.forward(&a), "fcsa_forward");
+  if (win != nullptr) check(g_abi.forward_window(&a, nullptr, win), "fcsa_forward_window");
+  else check(g_abi.forward(&a), "fcsa_forward");
   lap.mark(2);
   g_host_ns[6].fetch_add(1, std::memory_order_relaxed);
   if (c.merged) o = o.squeeze(1);                                                                                  // cu:1740-1741
   return std::make_tuple(o, inv_l, qn, kn, rq, rk);
 }
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> forward(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& mask,
+                                                                    const optional<Tensor>& attn_bias, bool attn_bias_batch_dim, double scale,
+                                                                    bool causal, bool l2norm_qk, int64_t groups, bool need_backward) {
+  return forward_impl(q, k, v, mask, attn_bias, attn_bias_batch_dim, scale, causal, l2norm_qk, groups, need_backward, nullptr);
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> window_forward(const Tensor& q, const Tensor& k, const Tensor& v, double scale, bool causal,
+                                                                           bool l2norm_qk, int64_t groups, bool need_backward, int64_t left,
+                                                                           int64_t right) {
+  const Win win(left, right);
+  return forward_impl(q, k, v, c10::nullopt, c10::nullopt, false, scale, causal, l2norm_qk, groups, need_backward, &win.w);
+}
 
 // (dq, dk, dv, d_bias) in the shapes / dtype of the inputs; d_bias is empty when not requested
-std::tuple<Tensor, Tensor, Tensor, Tensor> backward(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k,
-                                                    const Tensor& v, const optional<Tensor>& mask, const optional<Tensor>& attn_bias,
-                                                    const Tensor& qn, const Tensor& kn, const Tensor& rq, const Tensor& rk,
-                                                    bool attn_bias_batch_dim, double scale, bool causal, bool l2norm_qk, int64_t groups,
-                                                    bool need_bias_grad) {
+std::tuple<Tensor, Tensor, Tensor, Tensor> backward_impl(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k,
+                                                         const Tensor& v, const optional<Tensor>& mask, const optional<Tensor>& attn_bias,
+                                                         const Tensor& qn, const Tensor& kn, const Tensor& rq, const Tensor& rk,
+                                                         bool attn_bias_batch_dim, double scale, bool causal, bool l2norm_qk, int64_t groups,
+                                                         bool need_bias_grad, const fcsa_window* win) {
   Lap lap;
   const Canon c = canonicalise(q, k, v, mask, attn_bias, attn_bias_batch_dim, causal);
   c10::DeviceGuard guard(q.device());
@@ -262,7 +300,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> backward(const Tensor& d_out, const T
   Tensor db = (c.bias.has_value() && need_bias_grad) ? at::empty(c.bias->sizes(), opt) : at::empty({0}, opt);
   fcsa_backward_args a;
   a.p = problem(c, q.scalar_type(), causal, l2norm_qk, groups, scale);
-  size_t wsb = g_abi.backward_ws(&a.p);
+  size_t wsb = win != nullptr ? g_abi.backward_window_ws(&a.p, nullptr, win) : g_abi.backward_ws(&a.p);
   if (wsb < 256) wsb = 256;
   Tensor ws = at::empty({(int64_t)wsb}, opt.dtype(at::kByte));
   a.d_out = view4(do4); a.o = view4(o4);
@@ -279,10 +317,26 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> backward(const Tensor& d_out, const T
   a.workspace = ws.data_ptr(); a.workspace_bytes = wsb;
   a.stream = stream_of(q);
   lap.mark(4);
-  check(g_abi.backward(&a), "fcsa_backward");
+  if (win != nullptr) check(g_abi.backward_window(&a, nullptr, win), "fcsa_backward_window");
+  else check(g_abi.backward(&a), "fcsa_backward");
   lap.mark(5);
   g_host_ns[7].fetch_add(1, std::memory_order_relaxed);
   return std::make_tuple(dq.reshape(q.sizes()), dk.reshape(k.sizes()), dv.reshape(v.sizes()), db);
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor> backward(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k,
+                                                    const Tensor& v, const optional<Tensor>& mask, const optional<Tensor>& attn_bias,
+                                                    const Tensor& qn, const Tensor& kn, const Tensor& rq, const Tensor& rk,
+                                                    bool attn_bias_batch_dim, double scale, bool causal, bool l2norm_qk, int64_t groups,
+                                                    bool need_bias_grad) {
+  return backward_impl(d_out, o, inv_l, q, k, v, mask, attn_bias, qn, kn, rq, rk, attn_bias_batch_dim, scale, causal, l2norm_qk, groups,
+                       need_bias_grad, nullptr);
+}
+std::tuple<Tensor, Tensor, Tensor> window_backward(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k,
+                                                   const Tensor& v, const Tensor& qn, const Tensor& kn, const Tensor& rq, const Tensor& rk,
+                                                   double scale, bool causal, bool l2norm_qk, int64_t groups, int64_t left, int64_t right) {
+  const Win win(left, right);
+  auto g = backward_impl(d_out, o, inv_l, q, k, v, c10::nullopt, c10::nullopt, qn, kn, rq, rk, false, scale, causal, l2norm_qk, groups, false, &win.w);
+  return std::make_tuple(std::get<0>(g), std::get<1>(g), std::get<2>(g));
 }
 
 
@@ -360,9 +414,10 @@ void need_varlen_abi() {
 
 // (o, inv_l, qn, kn, rq, rk): o [total_q, H, D]; inv_l [H, total_q]; qn [H, total_q, D], kn [Hk, total_k, D], rq / rk [.., G]; empty where
 // not produced
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> varlen_forward(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q,
-                                                                           const Tensor& cu_k, int64_t max_q, int64_t max_k, double scale,
-                                                                           bool causal, bool l2norm_qk, int64_t groups, bool need_backward) {
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> varlen_forward_impl(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q,
+                                                                                const Tensor& cu_k, int64_t max_q, int64_t max_k, double scale,
+                                                                                bool causal, bool l2norm_qk, int64_t groups, bool need_backward,
+                                                                                const fcsa_window* win) {
   need_varlen_abi();
   const VCanon c = canonicalise_varlen(q, k, v, cu_q, cu_k, max_q, max_k);
   TORCH_CHECK_VALUE(!l2norm_qk || (groups >= 1 && c.D % groups == 0), "groups (", groups, ") must divide the head dimension (", c.D, ")");
@@ -396,15 +451,28 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> varlen_forward(const 
   a.norm.rk = (l2norm_qk && need_backward) ? rk.data_ptr<float>() : nullptr;
   a.workspace = nullptr; a.workspace_bytes = 0;      // packed sequences never split the key range
   a.stream = stream_of(q);
-  check(g_abi.forward_varlen(&a, &t), "fcsa_forward_varlen");
+  if (win != nullptr) check(g_abi.forward_window(&a, &t, win), "fcsa_forward_window");
+  else check(g_abi.forward_varlen(&a, &t), "fcsa_forward_varlen");
   return std::make_tuple(o, inv_l, qn, kn, rq, rk);
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> varlen_forward(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q,
+                                                                           const Tensor& cu_k, int64_t max_q, int64_t max_k, double scale,
+                                                                           bool causal, bool l2norm_qk, int64_t groups, bool need_backward) {
+  return varlen_forward_impl(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, need_backward, nullptr);
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> varlen_window_forward(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q,
+                                                                                  const Tensor& cu_k, int64_t max_q, int64_t max_k, double scale,
+                                                                                  bool causal, bool l2norm_qk, int64_t groups, bool need_backward,
+                                                                                  int64_t left, int64_t right) {
+  const Win win(left, right);
+  return varlen_forward_impl(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, need_backward, &win.w);
 }
 
 // (dq, dk, dv) shaped like q, k, v
-std::tuple<Tensor, Tensor, Tensor> varlen_backward(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k,
-                                                   const Tensor& v, const Tensor& cu_q, const Tensor& cu_k, const Tensor& qn, const Tensor& kn,
-                                                   const Tensor& rq, const Tensor& rk, int64_t max_q, int64_t max_k, double scale, bool causal,
-                                                   bool l2norm_qk, int64_t groups) {
+std::tuple<Tensor, Tensor, Tensor> varlen_backward_impl(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k,
+                                                        const Tensor& v, const Tensor& cu_q, const Tensor& cu_k, const Tensor& qn, const Tensor& kn,
+                                                        const Tensor& rq, const Tensor& rk, int64_t max_q, int64_t max_k, double scale, bool causal,
+                                                        bool l2norm_qk, int64_t groups, const fcsa_window* win) {
   need_varlen_abi();
   const VCanon c = canonicalise_varlen(q, k, v, cu_q, cu_k, max_q, max_k);
   c10::DeviceGuard guard(q.device());
@@ -433,7 +501,7 @@ std::tuple<Tensor, Tensor, Tensor> varlen_backward(const Tensor& d_out, const Te
   fcsa_backward_args a;
   a.p = varlen_problem(c, q.scalar_type(), max_q, max_k, causal, l2norm_qk, groups, scale);
   const fcsa_varlen t = varlen_table(c);
-  size_t wsb = g_abi.backward_varlen_ws(&a.p, &t);
+  size_t wsb = win != nullptr ? g_abi.backward_window_ws(&a.p, &t, win) : g_abi.backward_varlen_ws(&a.p, &t);
   if (wsb < 256) wsb = 256;
   Tensor ws = at::empty({(int64_t)wsb}, opt.dtype(at::kByte));      // the caching allocator
   a.d_out = packed3(do3); a.o = packed3(o3);
@@ -449,8 +517,22 @@ std::tuple<Tensor, Tensor, Tensor> varlen_backward(const Tensor& d_out, const Te
   a.d_bias = nullptr;
   a.workspace = ws.data_ptr(); a.workspace_bytes = wsb;
   a.stream = stream_of(q);
-  check(g_abi.backward_varlen(&a, &t), "fcsa_backward_varlen");
+  if (win != nullptr) check(g_abi.backward_window(&a, &t, win), "fcsa_backward_window");
+  else check(g_abi.backward_varlen(&a, &t), "fcsa_backward_varlen");
   return std::make_tuple(dq, dk, dv);
+}
+std::tuple<Tensor, Tensor, Tensor> varlen_backward(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k,
+                                                   const Tensor& v, const Tensor& cu_q, const Tensor& cu_k, const Tensor& qn, const Tensor& kn,
+                                                   const Tensor& rq, const Tensor& rk, int64_t max_q, int64_t max_k, double scale, bool causal,
+                                                   bool l2norm_qk, int64_t groups) {
+  return varlen_backward_impl(d_out, o, inv_l, q, k, v, cu_q, cu_k, qn, kn, rq, rk, max_q, max_k, scale, causal, l2norm_qk, groups, nullptr);
+}
+std::tuple<Tensor, Tensor, Tensor> varlen_window_backward(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k,
+                                                          const Tensor& v, const Tensor& cu_q, const Tensor& cu_k, const Tensor& qn,
+                                                          const Tensor& kn, const Tensor& rq, const Tensor& rk, int64_t max_q, int64_t max_k,
+                                                          double scale, bool causal, bool l2norm_qk, int64_t groups, int64_t left, int64_t right) {
+  const Win win(left, right);
+  return varlen_backward_impl(d_out, o, inv_l, q, k, v, cu_q, cu_k, qn, kn, rq, rk, max_q, max_k, scale, causal, l2norm_qk, groups, &win.w);
 }
 
 // ---- autograd in C++ (reference: the Python autograd.Function FlashCosineSimAttention, flash_cosine_sim_attention.py:245-302).
@@ -569,13 +651,112 @@ Tensor varlen_attention_plain(const Tensor& q, const Tensor& k, const Tensor& v,
 }
 
 
+// the differentiable sliding-window ops: the same node pattern, over fcsa::window_forward / window_backward and their varlen twins
+struct WindowAttentionFn : public torch::autograd::Function<WindowAttentionFn> {
+  static Tensor forward(AutogradContext* ctx, const Tensor& q, const Tensor& k, const Tensor& v, double scale, bool causal, bool l2norm_qk,
+                        int64_t groups, int64_t left, int64_t right) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("fcsa::window_forward", "")
+        .typed<std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, double, bool, bool, int64_t,
+                                                                           bool, int64_t, int64_t)>();
+    auto r = op.call(q, k, v, scale, causal, l2norm_qk, groups, true, left, right);
+    ctx->save_for_backward({std::get<0>(r), std::get<1>(r), q, k, v, std::get<2>(r), std::get<3>(r), std::get<4>(r), std::get<5>(r)});
+    ctx->saved_data["scale"] = scale;
+    ctx->saved_data["causal"] = causal;
+    ctx->saved_data["l2norm_qk"] = l2norm_qk;
+    ctx->saved_data["groups"] = groups;
+    ctx->saved_data["left"] = left;
+    ctx->saved_data["right"] = right;
+    return std::get<0>(r);
+  }
+
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    const auto s = ctx->get_saved_variables();
+    static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("fcsa::window_backward", "")
+        .typed<std::tuple<Tensor, Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
+                                                  const Tensor&, const Tensor&, const Tensor&, const Tensor&, double, bool, bool, int64_t, int64_t,
+                                                  int64_t)>();
+    auto g = op.call(grads[0], s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8], ctx->saved_data["scale"].toDouble(),
+                     ctx->saved_data["causal"].toBool(), ctx->saved_data["l2norm_qk"].toBool(), ctx->saved_data["groups"].toInt(),
+                     ctx->saved_data["left"].toInt(), ctx->saved_data["right"].toInt());
+    return {std::get<0>(g), std::get<1>(g), std::get<2>(g), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+  }
+};
+
+Tensor window_attention_plain(const Tensor& q, const Tensor& k, const Tensor& v, double scale, bool causal, bool l2norm_qk, int64_t groups,
+                              int64_t left, int64_t right) {
+  return std::get<0>(window_forward(q, k, v, scale, causal, l2norm_qk, groups, false, left, right));
+}
+
+Tensor window_attention_autograd(const Tensor& q, const Tensor& k, const Tensor& v, double scale, bool causal, bool l2norm_qk, int64_t groups,
+                                 int64_t left, int64_t right) {
+  const bool tracked = at::GradMode::is_enabled() && (q.requires_grad() || k.requires_grad() || v.requires_grad());
+  if (!tracked) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    return window_attention_plain(q, k, v, scale, causal, l2norm_qk, groups, left, right);
+  }
+  return WindowAttentionFn::apply(q, k, v, scale, causal, l2norm_qk, groups, left, right);
+}
+
+struct VarlenWindowAttentionFn : public torch::autograd::Function<VarlenWindowAttentionFn> {
+  static Tensor forward(AutogradContext* ctx, const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q, const Tensor& cu_k,
+                        int64_t max_q, int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups, int64_t left, int64_t right) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("fcsa::varlen_window_forward", "")
+        .typed<std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, const Tensor&,
+                                                                           const Tensor&, int64_t, int64_t, double, bool, bool, int64_t, bool,
+                                                                           int64_t, int64_t)>();
+    auto r = op.call(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, true, left, right);
+    ctx->save_for_backward({std::get<0>(r), std::get<1>(r), q, k, v, cu_q, cu_k, std::get<2>(r), std::get<3>(r), std::get<4>(r), std::get<5>(r)});
+    ctx->saved_data["max_q"] = max_q;
+    ctx->saved_data["max_k"] = max_k;
+    ctx->saved_data["scale"] = scale;
+    ctx->saved_data["causal"] = causal;
+    ctx->saved_data["l2norm_qk"] = l2norm_qk;
+    ctx->saved_data["groups"] = groups;
+    ctx->saved_data["left"] = left;
+    ctx->saved_data["right"] = right;
+    return std::get<0>(r);
+  }
+
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    const auto s = ctx->get_saved_variables();
+    static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("fcsa::varlen_window_backward", "")
+        .typed<std::tuple<Tensor, Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
+                                                  const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
+                                                  int64_t, int64_t, double, bool, bool, int64_t, int64_t, int64_t)>();
+    auto g = op.call(grads[0], s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8], s[9], s[10], ctx->saved_data["max_q"].toInt(),
+                     ctx->saved_data["max_k"].toInt(), ctx->saved_data["scale"].toDouble(), ctx->saved_data["causal"].toBool(),
+                     ctx->saved_data["l2norm_qk"].toBool(), ctx->saved_data["groups"].toInt(), ctx->saved_data["left"].toInt(),
+                     ctx->saved_data["right"].toInt());
+    return {std::get<0>(g), std::get<1>(g), std::get<2>(g), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(),
+            Tensor(), Tensor()};
+  }
+};
+
+Tensor varlen_window_attention_plain(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q, const Tensor& cu_k, int64_t max_q,
+                                     int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups, int64_t left, int64_t right) {
+  return std::get<0>(varlen_window_forward(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, false, left, right));
+}
+
+Tensor varlen_window_attention_autograd(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q, const Tensor& cu_k, int64_t max_q,
+                                        int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups, int64_t left, int64_t right) {
+  const bool tracked = at::GradMode::is_enabled() && (q.requires_grad() || k.requires_grad() || v.requires_grad());
+  if (!tracked) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    return varlen_window_attention_plain(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, left, right);
+  }
+  return VarlenWindowAttentionFn::apply(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, left, right);
+}
+
+
 // ---- decoding against a key/value cache (fcsa_forward_kvcache) --------------------------------------------------------------------------
 // q [B, H, N, D]; k_cache / v_cache [B, Hk, capacity, D] or, with a block_table, [num_blocks, Hk, page_size, D] (any strides with the
 // feature dim contiguous: they are written in place, so they are never copied); k_new / v_new [B, Hk, N_new, D]; cache_seqlens int32 [B]
 // and block_table int32 [B, max_blocks] on q's device.  Table contents are never read on the host: the call does not synchronise.
-Tensor kvcache_forward(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const optional<Tensor>& k_new, const optional<Tensor>& v_new,
-                       const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table, int64_t max_seqlen_k, double scale, bool causal,
-                       bool l2norm_qk, int64_t groups) {
+Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const optional<Tensor>& k_new, const optional<Tensor>& v_new,
+                            const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table, int64_t max_seqlen_k, double scale, bool causal,
+                            bool l2norm_qk, int64_t groups, const fcsa_window* win) {
   TORCH_CHECK(g_abi.forward_kvcache != nullptr && g_abi.forward_kvcache_ws != nullptr,
               "flash_cosine_sim_attention_with_kvcache: the loaded libfcsa_hip.so does not export fcsa_forward_kvcache");
   TORCH_CHECK(q.is_cuda(), "flash_cosine_sim_attention_with_kvcache: q and the caches must be GPU tensors (HIP kernels only)");
@@ -659,7 +840,7 @@ Tensor kvcache_forward(const Tensor& q, const Tensor& k_cache, const Tensor& v_c
   std::memset(&none, 0, sizeof(none));
   kv.k_new = kn.defined() && new_len > 0 ? view4(kn) : none;
   kv.v_new = vn.defined() && new_len > 0 ? view4(vn) : none;
-  const size_t wsb = g_abi.forward_kvcache_ws(&a.p, &kv);
+  const size_t wsb = win != nullptr ? g_abi.forward_kvcache_window_ws(&a.p, &kv, win) : g_abi.forward_kvcache_ws(&a.p, &kv);
   Tensor ws;
   if (wsb > 0) {
     ws = at::empty({(int64_t)wsb}, q.options().dtype(at::kByte));      // the caching allocator
@@ -667,8 +848,20 @@ Tensor kvcache_forward(const Tensor& q, const Tensor& k_cache, const Tensor& v_c
     a.workspace_bytes = wsb;
   }
   a.stream = stream_of(q);
-  check(g_abi.forward_kvcache(&a, &kv), "fcsa_forward_kvcache");
+  if (win != nullptr) check(g_abi.forward_kvcache_window(&a, &kv, win), "fcsa_forward_kvcache_window");
+  else check(g_abi.forward_kvcache(&a, &kv), "fcsa_forward_kvcache");
   return o;
+}
+Tensor kvcache_forward(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const optional<Tensor>& k_new, const optional<Tensor>& v_new,
+                       const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table, int64_t max_seqlen_k, double scale, bool causal,
+                       bool l2norm_qk, int64_t groups) {
+  return kvcache_forward_impl(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups, nullptr);
+}
+Tensor kvcache_window_forward(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const optional<Tensor>& k_new,
+                              const optional<Tensor>& v_new, const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table,
+                              int64_t max_seqlen_k, double scale, bool causal, bool l2norm_qk, int64_t groups, int64_t left, int64_t right) {
+  const Win win(left, right);
+  return kvcache_forward_impl(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups, &win.w);
 }
 
 }  // namespace
@@ -695,6 +888,11 @@ extern "C" int fcsa_torch_use_library(const char* path) {
   a.backward_varlen_ws = reinterpret_cast<decltype(a.backward_varlen_ws)>(dlsym(h, "fcsa_backward_varlen_workspace_bytes"));
   a.forward_kvcache = reinterpret_cast<decltype(a.forward_kvcache)>(dlsym(h, "fcsa_forward_kvcache"));
   a.forward_kvcache_ws = reinterpret_cast<decltype(a.forward_kvcache_ws)>(dlsym(h, "fcsa_forward_kvcache_workspace_bytes"));
+  a.forward_window = reinterpret_cast<decltype(a.forward_window)>(dlsym(h, "fcsa_forward_window"));
+  a.backward_window = reinterpret_cast<decltype(a.backward_window)>(dlsym(h, "fcsa_backward_window"));
+  a.backward_window_ws = reinterpret_cast<decltype(a.backward_window_ws)>(dlsym(h, "fcsa_backward_window_workspace_bytes"));
+  a.forward_kvcache_window = reinterpret_cast<decltype(a.forward_kvcache_window)>(dlsym(h, "fcsa_forward_kvcache_window"));
+  a.forward_kvcache_window_ws = reinterpret_cast<decltype(a.forward_kvcache_window_ws)>(dlsym(h, "fcsa_forward_kvcache_window_workspace_bytes"));
   if (!a.forward || !a.backward || !a.forward_ws || !a.backward_ws || !a.needs_qn || !a.last_error) { dlclose(h); return -2; }
   // Only libraries of THIS ABI: the binding allocates for the struct layouts and buffer contracts of include/fcsa.h as compiled in
   // (e.g. ABI 3 writes d_bias once in the bias dtype into an uninitialised buffer; an ABI-2 library would accumulate float32 into
@@ -725,6 +923,23 @@ TORCH_LIBRARY(fcsa, m) {
   // decoding against a key/value cache (forward only): appends k_new / v_new to the caches in place, then attends
   m.def("kvcache_forward(Tensor q, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor? k_new, Tensor? v_new, Tensor? cache_seqlens, "
         "Tensor? block_table, int max_seqlen_k, float scale, bool causal, bool l2norm_qk, int groups) -> Tensor");
+  // sliding-window (local) attention: the ops above with window_left / window_right (-1: unbounded); no mask, no attn_bias
+  m.def("window_forward(Tensor q, Tensor k, Tensor v, float scale, bool causal, bool l2norm_qk, int groups, bool need_backward, "
+        "int window_left, int window_right) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("window_backward(Tensor d_out, Tensor o, Tensor inv_l, Tensor q, Tensor k, Tensor v, Tensor qn, Tensor kn, Tensor rq, Tensor rk, "
+        "float scale, bool causal, bool l2norm_qk, int groups, int window_left, int window_right) -> (Tensor, Tensor, Tensor)");
+  m.def("window_attention(Tensor q, Tensor k, Tensor v, float scale, bool causal, bool l2norm_qk, int groups, int window_left, "
+        "int window_right) -> Tensor");
+  m.def("varlen_window_forward(Tensor q, Tensor k, Tensor v, Tensor cu_seqlens_q, Tensor cu_seqlens_k, int max_seqlen_q, int max_seqlen_k, "
+        "float scale, bool causal, bool l2norm_qk, int groups, bool need_backward, int window_left, int window_right) "
+        "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("varlen_window_backward(Tensor d_out, Tensor o, Tensor inv_l, Tensor q, Tensor k, Tensor v, Tensor cu_seqlens_q, Tensor cu_seqlens_k, "
+        "Tensor qn, Tensor kn, Tensor rq, Tensor rk, int max_seqlen_q, int max_seqlen_k, float scale, bool causal, bool l2norm_qk, "
+        "int groups, int window_left, int window_right) -> (Tensor, Tensor, Tensor)");
+  m.def("varlen_window_attention(Tensor q, Tensor k, Tensor v, Tensor cu_seqlens_q, Tensor cu_seqlens_k, int max_seqlen_q, int max_seqlen_k, "
+        "float scale, bool causal, bool l2norm_qk, int groups, int window_left, int window_right) -> Tensor");
+  m.def("kvcache_window_forward(Tensor q, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor? k_new, Tensor? v_new, Tensor? cache_seqlens, "
+        "Tensor? block_table, int max_seqlen_k, float scale, bool causal, bool l2norm_qk, int groups, int window_left, int window_right) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(fcsa, CUDA, m) {       // ROCm builds of PyTorch dispatch HIP tensors under the CUDA key
@@ -735,9 +950,18 @@ TORCH_LIBRARY_IMPL(fcsa, CUDA, m) {       // ROCm builds of PyTorch dispatch HIP
   m.impl("varlen_backward", &varlen_backward);
   m.impl("varlen_attention", &varlen_attention_plain);
   m.impl("kvcache_forward", &kvcache_forward);
+  m.impl("window_forward", &window_forward);
+  m.impl("window_backward", &window_backward);
+  m.impl("window_attention", &window_attention_plain);
+  m.impl("varlen_window_forward", &varlen_window_forward);
+  m.impl("varlen_window_backward", &varlen_window_backward);
+  m.impl("varlen_window_attention", &varlen_window_attention_plain);
+  m.impl("kvcache_window_forward", &kvcache_window_forward);
 }
 
 TORCH_LIBRARY_IMPL(fcsa, Autograd, m) {
   m.impl("attention", &attention_autograd);
   m.impl("varlen_attention", &varlen_attention_autograd);
+  m.impl("window_attention", &window_attention_autograd);
+  m.impl("varlen_window_attention", &varlen_window_attention_autograd);
 }

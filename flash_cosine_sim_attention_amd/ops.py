@@ -146,6 +146,31 @@ def flash_cosine_sim_attention(q, k, v, mask=None, attn_bias=None, scale=8, grou
 
 
 # ---------------------------------------------------------------------------------------------
+# sliding-window (local) attention (flash-attn's window_size convention; no reference counterpart)
+# ---------------------------------------------------------------------------------------------
+
+def _window(window_size):
+    """(left, right) as two ints >= -1 (any integer type; no bool, no float): the rule of `cpu.window_index`."""
+    return _cpu.window_index(window_size)
+
+
+def flash_cosine_sim_attention_local(q, k, v, window_size, scale=8, groups=1, causal=False, l2norm_qk=True):
+    """Fused cosine-similarity attention under a sliding window: query i of N sees key j of M iff
+    i + (M - N) - left <= j <= i + (M - N) + right, with window_size = (left, right), -1 for an unbounded side and the bottom-right
+    alignment `causal` uses; causal=True caps right at 0.  Rows without a visible key give 0 (and zero gradients).  Otherwise
+    `flash_cosine_sim_attention` without mask and attn_bias: 4-D q, k, v (k, v heads dividing q's), differentiable w.r.t. q, k, v.
+    Only the tiles of the band are visited, so time and traffic go with N * (left + right), not N * M.  A window that hides no pair
+    of the problem -- and (-1, 0), which is causal=True -- runs the un-windowed kernels, bit for bit.
+    CPU tensors take the forward-only path of `cpu.py`."""
+    left, right = _window(window_size)
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise ValueError("flash_cosine_sim_attention_local takes 4-D q, k, v ([batch, heads, length, dim_head])")
+    if q.device.type == "cpu":
+        return _cpu.attention_forward_cpu(q, k, v, scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, window_size=(left, right))
+    return _torch_ops.load().window_attention(q, k, v, float(scale), bool(causal), bool(l2norm_qk), int(groups), left, right)
+
+
+# ---------------------------------------------------------------------------------------------
 # packed variable-length sequences (the flash-attn cu_seqlens convention; no reference counterpart)
 # ---------------------------------------------------------------------------------------------
 
@@ -164,7 +189,7 @@ def _check_host_cu(name, cu, total, max_len):
 
 
 def flash_cosine_sim_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, scale=8, groups=1,
-                                      causal=False, l2norm_qk=True):
+                                      causal=False, l2norm_qk=True, window_size=(-1, -1)):
     """Fused cosine-similarity attention over packed variable-length sequences.
 
     q [total_q, H, D] and k, v [total_k, Hk, D] (Hk dividing H) hold S sequences back to back; sequence s owns the query rows
@@ -176,7 +201,9 @@ def flash_cosine_sim_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_s
     Tables on the host are validated fully (and copied to q's device); tables already on the device are trusted, as in flash-attn --
     a malformed device table gives wrong rows, never an access outside the tensors.  max_seqlen_q / max_seqlen_k must be at least
     the longest span: the launch grid is sized by them.  When None they are computed from the tables, which synchronises the device
-    when the tables live there.  CPU tensors take the forward-only path of `cpu.py`, one dense CPU call per sequence."""
+    when the tables live there.  CPU tensors take the forward-only path of `cpu.py`, one dense CPU call per sequence.
+    window_size = (left, right): a sliding window as in `flash_cosine_sim_attention_local`, every sequence with its own alignment."""
+    window = _window(window_size)
     for name, t in (("q", q), ("k", k), ("v", v)):
         if t.dim() != 3:
             raise ValueError(f"{name} must be a packed [total, heads, dim_head] tensor, got {tuple(t.shape)}")
@@ -206,7 +233,7 @@ def flash_cosine_sim_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_s
         if cu_seqlens_q.device.type != "cpu" or cu_seqlens_k.device.type != "cpu":
             raise ValueError("CPU tensors take host cu_seqlens tables")
         return _cpu.attention_forward_varlen_cpu(q, k, v, cu_seqlens_q, cu_seqlens_k, scale=scale, groups=groups, causal=causal,
-                                                 l2norm_qk=l2norm_qk)
+                                                 l2norm_qk=l2norm_qk, window_size=window)
     # device tables are trusted; a max_seqlen left to us costs one device synchronisation per table
     if max_seqlen_q is None:
         max_seqlen_q = int((cu_seqlens_q[1:] - cu_seqlens_q[:-1]).max().item()) if cu_seqlens_q.numel() > 1 else 0
@@ -214,6 +241,9 @@ def flash_cosine_sim_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_s
         max_seqlen_k = int((cu_seqlens_k[1:] - cu_seqlens_k[:-1]).max().item()) if cu_seqlens_k.numel() > 1 else 0
     cu_q = cu_seqlens_q.to(q.device, non_blocking=True)
     cu_k = cu_seqlens_k.to(q.device, non_blocking=True)
+    if window != (-1, -1):
+        return _torch_ops.load().varlen_window_attention(q, k, v, cu_q, cu_k, int(max_seqlen_q), int(max_seqlen_k), float(scale),
+                                                         bool(causal), bool(l2norm_qk), int(groups), window[0], window[1])
     return _torch_ops.load().varlen_attention(q, k, v, cu_q, cu_k, int(max_seqlen_q), int(max_seqlen_k), float(scale), bool(causal),
                                               bool(l2norm_qk), int(groups))
 
@@ -223,7 +253,7 @@ def flash_cosine_sim_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_s
 # ---------------------------------------------------------------------------------------------
 
 def flash_cosine_sim_attention_with_kvcache(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlens=None, block_table=None,
-                                            max_seqlen_k=None, scale=8, groups=1, causal=False, l2norm_qk=True):
+                                            max_seqlen_k=None, scale=8, groups=1, causal=False, l2norm_qk=True, window_size=(-1, -1)):
     """Forward-only attention of new queries against a key/value cache, with an optional in-place append.
 
     q [B, H, N, D] (N = 1: plain decode; a few: speculative or chunked steps).  k_cache, v_cache: [B, Hk, capacity, D] or, with a
@@ -238,7 +268,10 @@ def flash_cosine_sim_attention_with_kvcache(q, k_cache, v_cache, k_new=None, v_n
     max_seqlen_k: an upper bound on every L_b that sizes the launch grid (default: the capacity), so the call never reads device tables
     on the host and a decode step can be captured in a HIP graph.  Host tables are validated; device tables are trusted (the kernels
     clamp lengths and block ids, so a malformed table gives wrong rows, never an access outside the tensors).  Two sequences appending
-    into the same page slot is undefined behaviour.  CPU tensors take the forward-only path of `cpu.py`."""
+    into the same page slot is undefined behaviour.  CPU tensors take the forward-only path of `cpu.py`.
+    window_size = (left, right): a sliding window -- the query at position t of its sequence sees the cached keys [t - left, t + right]
+    (-1: unbounded; causal caps right at 0); only the cache blocks from the first visible key on are read."""
+    window = _window(window_size)
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_new, v_new)):
         raise RuntimeError("flash_cosine_sim_attention_with_kvcache is forward-only: q, k_new and v_new must not require grad "
                            "(run it under torch.no_grad())")
@@ -299,7 +332,7 @@ def flash_cosine_sim_attention_with_kvcache(q, k_cache, v_cache, k_new=None, v_n
             raise ValueError("CPU tensors take host cache_seqlens")
         detach = lambda t: None if t is None else t.detach()          # (grad mode is off here, or nothing requires grad)
         return _cpu.attention_forward_kvcache_cpu(q.detach(), k_cache, v_cache, detach(k_new), detach(v_new), lens, block_table,
-                                                  scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk)
+                                                  scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, window_size=window)
     if isinstance(cache_seqlens, int):
         cache_seqlens = torch.full((B,), cache_seqlens, dtype=torch.int32, device=q.device)
     elif cache_seqlens is not None:
@@ -307,5 +340,8 @@ def flash_cosine_sim_attention_with_kvcache(q, k_cache, v_cache, k_new=None, v_n
     if block_table is not None:
         block_table = block_table.to(q.device, non_blocking=True)
     max_k = capacity if max_seqlen_k is None else min(int(max_seqlen_k), capacity)
+    if window != (-1, -1):
+        return _torch_ops.load().kvcache_window_forward(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, int(max_k),
+                                                        float(scale), bool(causal), bool(l2norm_qk), int(groups), window[0], window[1])
     return _torch_ops.load().kvcache_forward(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, int(max_k), float(scale),
                                              bool(causal), bool(l2norm_qk), int(groups))

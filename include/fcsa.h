@@ -245,6 +245,35 @@ int    fcsa_forward_kvcache(const fcsa_forward_args* args, const fcsa_kvcache* c
 /* Scratch fcsa_forward_kvcache needs: f32 partial P~V and (max, row sum) of every split, [splits][B * H * N][D + 2] */
 size_t fcsa_forward_kvcache_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* cache);
 
+/* Sliding-window (local) attention (no reference counterpart; flash-attn's window_size = (left, right) convention).  With the
+ * bottom-right alignment of `causal`, query i of N sees key j of M iff
+ *     i + (M - N) - left <= j <= i + (M - N) + right;
+ * -1 leaves that side unbounded (any other negative value: FCSA_ERR_INVALID_ARG), and p.causal caps `right` at 0.  Rows without a visible
+ * key give o = 0 and zero gradients.  mask, attn_bias and d_bias must be NULL (FCSA_ERR_INVALID_ARG), as for packed sequences.
+ * `seqs` NULL: a dense call, args as fcsa_forward / fcsa_backward read them; else packed sequences, args as fcsa_forward_varlen /
+ * fcsa_backward_varlen read them, every sequence with its own alignment M_s - N_s.
+ * Normalisation, done on the host before anything is launched.  A side hides nothing when it is unbounded or reaches past the problem's
+ * corner: right >= N - 1 (query 0 sees key M - 1), left >= M - 1 (query N - 1 sees key 0), with N / M the problem's q_len / k_len (packed:
+ * the longest spans, which bound every sequence's own).  With p.causal the right side is 0 whatever was given.  Then: both sides hide
+ * nothing -> the un-windowed call; left hides nothing and right == 0 -> the causal call.  Both are served by
+ * fcsa_forward[_varlen] / fcsa_backward[_varlen] themselves, bit for bit.  Every other window runs the windowed kernel forms: per row tile
+ * (key tile) only the tiles of the band are visited, and only the tiles an edge crosses pay the per-logit select.  Such a call takes
+ * no split launch, 64-rows-per-wave forward form or grouped-query head sweep (the forms of a packed call). */
+typedef struct fcsa_window {
+  int32_t left, right;                /* keys visible to the left / right of a query's own (bottom-right aligned) position; -1: unbounded */
+} fcsa_window;
+int    fcsa_forward_window(const fcsa_forward_args* args, const fcsa_varlen* seqs, const fcsa_window* window);
+int    fcsa_backward_window(const fcsa_backward_args* args, const fcsa_varlen* seqs, const fcsa_window* window);
+/* Scratch fcsa_backward_window needs for this problem, table (NULL: dense) and window */
+size_t fcsa_backward_window_workspace_bytes(const fcsa_problem* p, const fcsa_varlen* seqs, const fcsa_window* window);
+/* fcsa_forward_kvcache under a window: the query at position t of its sequence (the N queries are the last N of the L_b cached positions)
+ * sees the cached keys [t - left, t + right]; causal caps right at 0.  Only the 32-key blocks from the first visible key on are read, and
+ * the split count is sized by min(max_seqlen_k, left + N) keys.  Normalised like the dense call with M = min(p.k_len, capacity): left
+ * unbounded or >= M - 1 and right unbounded, >= N - 1 or 0 is fcsa_forward_kvcache itself (causal for 0), bit for bit.  The append is
+ * unchanged. */
+int    fcsa_forward_kvcache_window(const fcsa_forward_args* args, const fcsa_kvcache* cache, const fcsa_window* window);
+size_t fcsa_forward_kvcache_window_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* cache, const fcsa_window* window);
+
 /* Bytes of optional forward scratch that enable the split-key forward for this problem (0: never split). */
 size_t fcsa_forward_workspace_bytes(const fcsa_problem* p);
 
