@@ -16,72 +16,9 @@ import numpy as np
 import pytest
 import torch
 
+from fullsize_reference import grads_operand_faithful as _grads_operand_faithful, ref_slice as _ref_slice
+
 pytestmark = pytest.mark.gpu
-
-
-def _ref_slice(q, k, v, mask, causal, scale, groups, ref_dtype=torch.float32, operand_dtype=None):
-    """PyTorch evaluation of softmax(scale * qn kn^T) v for [n, d] x [m, d] slices in `ref_dtype` (float32 or float64).
-    operand_dtype: round the normalised operands to that dtype first -- c1 * q^ (c1 = scale * log2 e, as the kernels fold it) and
-    k^ -- i.e. the "operand-faithful" reference: what exact arithmetic gives on the 16-bit operands every implementation of this op
-    (the reference's too, py:57-65) feeds its S product.  It separates the error inherent to 16-bit operands, which grows with
-    scale * groups, from everything else, so that check needs no range-dependent tolerance."""
-    q, k, v = q.to(ref_dtype), k.to(ref_dtype), v.to(ref_dtype)
-    d = q.shape[-1]
-
-    def nrm(t):
-        tg = t.reshape(t.shape[0], groups, d // groups)
-        return torch.nn.functional.normalize(tg, dim=-1).reshape(t.shape)
-
-    qn, kn = nrm(q), nrm(k)
-    if operand_dtype is not None:
-        c1 = scale * 1.4426950408889634
-        qn = (qn * c1).to(operand_dtype).to(ref_dtype) / c1
-        kn = kn.to(operand_dtype).to(ref_dtype)
-    s = (qn @ kn.t()) * scale
-    n, m = s.shape
-    if causal:
-        s = s.masked_fill(torch.ones(n, m, dtype=torch.bool, device=s.device).triu(m - n + 1), float("-inf"))
-    if mask is not None:
-        s = s.masked_fill(~mask[None, :], float("-inf"))
-    return torch.softmax(s, dim=-1) @ v
-
-
-def _grads_operand_faithful(q, k, v, do, mask, causal, scale, groups, dtype):
-    """Gradients of one (batch, head) slice by the kernel's own formulas in float64 on the 16-bit OPERANDS:
-    c1 * q^ and k^ rounded to `dtype` feed S, dQ^ = scale dS K^, dK^ = scale dS^T Q^ and the projection of the l2norm backward
-    (what oracle.attention_backward(operand_dtype=...) computes, here in torch on the GPU so that full-size slices take
-    milliseconds).  Returns (dq, dk, dv) w.r.t. the raw slices; pinned to the numpy oracle by test_operand_faithful_helper..."""
-    q, k, v, do = (t.double() for t in (q, k, v, do))
-    n, d = q.shape
-    m = k.shape[0]
-
-    def nrm(t):
-        tg = t.reshape(t.shape[0], groups, d // groups)
-        inv = 1.0 / tg.norm(dim=-1, keepdim=True).clamp_min(1e-12)
-        return (tg * inv).reshape(t.shape), inv
-
-    qn, rq = nrm(q)
-    kn, rk = nrm(k)
-    c1 = abs(scale) * 1.4426950408889634
-    qr = (qn * c1).to(dtype).double() / c1
-    kr = kn.to(dtype).double()
-    s = (qr @ kr.t()) * scale
-    if causal:
-        s = s.masked_fill(torch.ones(n, m, dtype=torch.bool, device=s.device).triu(m - n + 1), float("-inf"))
-    if mask is not None:
-        s = s.masked_fill(~mask[None, :], float("-inf"))
-    p = torch.softmax(s, dim=-1)
-    o = p @ v
-    delta = (do * o).sum(-1, keepdim=True)
-    dv = p.t() @ do
-    ds = p * (do @ v.t() - delta)
-    dqh, dkh = scale * (ds @ kr), scale * (ds.t() @ qr)
-
-    def nrm_bwd(g, xh, inv):
-        gg, xg = g.reshape(g.shape[0], groups, -1), xh.reshape(g.shape[0], groups, -1)
-        return (inv * (gg - xg * (gg * xg).sum(-1, keepdim=True))).reshape(g.shape)
-
-    return nrm_bwd(dqh, qr, rq), nrm_bwd(dkh, kr, rk), dv
 
 
 def _configs():
