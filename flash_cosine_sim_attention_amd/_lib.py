@@ -82,13 +82,16 @@ KernelStat = _STRUCTS["fcsa_kernel_stat"]
 Varlen = _STRUCTS["fcsa_varlen"]
 KvCache = _STRUCTS["fcsa_kvcache"]
 Window = _STRUCTS["fcsa_window"]
+KvCacheQuant = _STRUCTS["fcsa_kvcache_quant"]
+FCSA_CACHE_E4M3 = _MACROS["FCSA_CACHE_E4M3"]
 
 
 EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fcsa_forward_workspace_bytes", "fcsa_forward_needs_qn",
            "fcsa_l2norm", "fcsa_debug", "fcsa_debug_forward_form", "fcsa_debug_kv_group_form", "fcsa_last_error", "fcsa_profile_enable", "fcsa_profile_collect",
            "fcsa_forward_varlen", "fcsa_backward_varlen", "fcsa_backward_varlen_workspace_bytes", "fcsa_forward_kvcache",
            "fcsa_forward_kvcache_workspace_bytes", "fcsa_forward_window", "fcsa_backward_window", "fcsa_backward_window_workspace_bytes",
-           "fcsa_forward_kvcache_window", "fcsa_forward_kvcache_window_workspace_bytes")
+           "fcsa_forward_kvcache_window", "fcsa_forward_kvcache_window_workspace_bytes", "fcsa_forward_kvcache_quant",
+           "fcsa_forward_kvcache_quant_workspace_bytes")
 
 _lib = None
 
@@ -161,6 +164,12 @@ def load():
         lib.fcsa_forward_kvcache_window.restype = C.c_int
         lib.fcsa_forward_kvcache_window_workspace_bytes.argtypes = [C.POINTER(Problem), C.POINTER(KvCache), C.POINTER(Window)]
         lib.fcsa_forward_kvcache_window_workspace_bytes.restype = C.c_size_t
+    if hasattr(lib, "fcsa_forward_kvcache_quant"):      # (likewise: an FCSA_LIB build from before the fp8 cache)
+        lib.fcsa_forward_kvcache_quant.argtypes = [C.POINTER(ForwardArgs), C.POINTER(KvCache), C.POINTER(KvCacheQuant), C.POINTER(Window)]
+        lib.fcsa_forward_kvcache_quant.restype = C.c_int
+        lib.fcsa_forward_kvcache_quant_workspace_bytes.argtypes = [C.POINTER(Problem), C.POINTER(KvCache), C.POINTER(KvCacheQuant),
+                                                                   C.POINTER(Window)]
+        lib.fcsa_forward_kvcache_quant_workspace_bytes.restype = C.c_size_t
     lib.fcsa_last_error.argtypes = []
     lib.fcsa_last_error.restype = C.c_char_p
     ver = lib.fcsa_debug(None, 0)

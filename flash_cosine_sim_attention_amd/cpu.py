@@ -201,12 +201,30 @@ def append_kvcache_cpu(k_cache, v_cache, k_new, v_new, seqlens, block_table=None
                 v_cache[blk, :, pos % page] = v_new[b, :, t]
 
 
+E4M3_MAX = 448.0
+
+
+def quantise_e4m3(x, scale):
+    """The append rule of an fp8 cache: e4m3_rne(clamp(float(x) / scale, -448, 448)) as float8_e4m3fn; scale broadcasts against x.  The
+    divide is float32's correctly rounded one, finite values saturate at +-448 (the explicit clamp), NaN stays NaN."""
+    return (x.float() / scale).clamp(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn)
+
+
 def attention_forward_kvcache_cpu(q, k_cache, v_cache, k_new, v_new, seqlens, block_table=None, scale=8.0, groups=1, causal=False,
-                                  l2norm_qk=True, window_size=(-1, -1)):
+                                  l2norm_qk=True, window_size=(-1, -1), k_scale=None, v_scale=None):
     """Forward-only path of `flash_cosine_sim_attention_with_kvcache` on host tensors: the append as an indexed copy, then the dense CPU
-    forward of every sequence over its first L_b = seqlens[b] + N_new cached positions (o = 0 where L_b == 0).  seqlens: host ints."""
+    forward of every sequence over its first L_b = seqlens[b] + N_new cached positions (o = 0 where L_b == 0).  seqlens: host ints.
+    k_scale / v_scale (float32 [B, Hk], both or neither): the caches are float8_e4m3fn codes meaning scale * code -- the append quantises
+    (quantise_e4m3), and each sequence's keys and values are dequantised to float32 for the dense forward, whose result is cast to q's
+    dtype."""
+    fp8 = k_scale is not None
     if k_new is not None:
-        append_kvcache_cpu(k_cache, v_cache, k_new, v_new, seqlens, block_table)
+        if fp8:
+            append_kvcache_cpu(k_cache.view(torch.uint8), v_cache.view(torch.uint8),
+                               quantise_e4m3(k_new, k_scale[:, :, None, None]).view(torch.uint8),
+                               quantise_e4m3(v_new, v_scale[:, :, None, None]).view(torch.uint8), seqlens, block_table)
+        else:
+            append_kvcache_cpu(k_cache, v_cache, k_new, v_new, seqlens, block_table)
     n_new = 0 if k_new is None else k_new.shape[2]
     out = torch.zeros_like(q)
     for b, start in enumerate(seqlens):
@@ -214,6 +232,10 @@ def attention_forward_kvcache_cpu(q, k_cache, v_cache, k_new, v_new, seqlens, bl
         if length == 0 or q.shape[2] == 0:
             continue
         kb, vb = cache_gather(k_cache, b, length, block_table), cache_gather(v_cache, b, length, block_table)
-        out[b:b + 1] = attention_forward_cpu(q[b:b + 1], kb, vb, scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk,
+        qb = q[b:b + 1]
+        if fp8:
+            qb = qb.float()
+            kb, vb = kb.float() * k_scale[b][None, :, None, None], vb.float() * v_scale[b][None, :, None, None]
+        out[b:b + 1] = attention_forward_cpu(qb, kb, vb, scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk,
                                              window_size=window_size)
     return out

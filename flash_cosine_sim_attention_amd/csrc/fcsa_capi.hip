@@ -328,7 +328,8 @@ int fcsa_debug(char* buf, size_t buf_bytes) {
              "libfcsa_hip abi=%d arch=gfx950 dtypes=f32,f16,bf16 dim_head=16,32,64,96,128 "
              "kernels=l2norm,l2norm_pair,fwd(32 rows/wave; lean two-wave form at D=96/128),fwd2(64 rows/wave),fwd3(D=128: 64 rows/wave, 1 wave/SIMD),fwd_ksplit(128 rows, wave halves split the keys),fwd_split+combine,"
              "fwd_dyn(per-row shift),bwd_dq(+split-key; key-split form on 8 waves),bwd_dkv(+lean; query-split form on 8 waves; grouped-query K/V head sweep),bwd_dbias,finalize,kv_append+decode+decode_combine(kv cache),"
-             "window(fwd_win,bwd_dq_win,bwd_dkv_win,decode_win: sliding-window forms) kv_heads=divisors of heads",
+             "window(fwd_win,bwd_dq_win,bwd_dkv_win,decode_win: sliding-window forms),"
+             "kv_append_fp8+decode_fp8+decode_combine_fp8(e4m3fn kv cache, f16/bf16 queries) kv_heads=divisors of heads",
              FCSA_ABI_VERSION);
   }
   return FCSA_ABI_VERSION;
@@ -441,7 +442,8 @@ DecodePlan decode_plan(const fcsa_problem& p, const fcsa_kvcache& kv, int win_lo
   return d;
 }
 
-int check_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv) {
+// cache_es: bytes of a cache element (0: the problem's type; 1: an fp8 cache, fcsa_forward_kvcache_quant)
+int check_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv, int cache_es = 0) {
   if (a == nullptr || kv == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache: null argument");
   const fcsa_problem& p = a->p;
   if (int rc = check_problem(p)) return rc;
@@ -459,13 +461,14 @@ int check_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv) {
   const int es = elem_size(p.dtype);
   const bool rows = p.batch > 0 && p.heads > 0 && p.q_len > 0;
   const bool cache = p.batch > 0 && kv->capacity > 0;
+  const int ces = cache_es > 0 ? cache_es : es;
   if (rows) {
     if (int rc = check_tensor("q", a->q, es, true)) return rc;
     if (int rc = check_tensor("o", a->o, es, true)) return rc;
   }
   if (cache) {
-    if (int rc = check_tensor("k_cache", kv->k_cache, es, true)) return rc;
-    if (int rc = check_tensor("v_cache", kv->v_cache, es, true)) return rc;
+    if (int rc = check_tensor("k_cache", kv->k_cache, ces, true)) return rc;
+    if (int rc = check_tensor("v_cache", kv->v_cache, ces, true)) return rc;
   }
   if (cache && kv->new_len > 0) {
     if (int rc = check_tensor("k_new", kv->k_new, es, true)) return rc;
@@ -494,7 +497,7 @@ static bool decode_window_sides(const fcsa_problem& p, const fcsa_kvcache& kv, c
   causal = kind == fcsa::WinKind::Causal ? 1 : kind == fcsa::WinKind::Full ? 0 : p.causal;
   return kind == fcsa::WinKind::Window;
 }
-static int forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv, const WindowCall* win);
+static int forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv, const WindowCall* win, const fcsa_kvcache_quant* qz = nullptr);
 
 size_t fcsa_forward_kvcache_window_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv, const fcsa_window* w) {
   if (p == nullptr || kv == nullptr || w == nullptr) return 0;
@@ -514,8 +517,33 @@ int fcsa_forward_kvcache_window(const fcsa_forward_args* a, const fcsa_kvcache* 
   return forward_kvcache(a, kv, &win);
 }
 
-static int forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv, const WindowCall* win) {
-  if (int rc = check_kvcache(a, kv)) return rc;
+// what fcsa_forward_kvcache_quant checks before anything else
+static int check_quant(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_kvcache_quant* qz) {
+  if (a == nullptr || kv == nullptr || qz == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_quant: null argument");
+  if (qz->cache_dtype != FCSA_CACHE_E4M3)
+    return fail(FCSA_ERR_UNSUPPORTED, "kvcache_quant: cache type %d not supported (expected FCSA_CACHE_E4M3 = %d, OCP e4m3fn)", qz->cache_dtype, FCSA_CACHE_E4M3);
+  if (a->p.dtype == FCSA_F32) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_quant: float32 queries with an fp8 cache are not supported (f16 or bf16)");
+  if (qz->k_scale == nullptr || qz->v_scale == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_quant: null k_scale / v_scale");
+  return check_kvcache(a, kv, 1);
+}
+
+size_t fcsa_forward_kvcache_quant_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv, const fcsa_kvcache_quant* qz, const fcsa_window* w) {
+  if (qz == nullptr) return 0;
+  return w != nullptr ? fcsa_forward_kvcache_window_workspace_bytes(p, kv, w) : fcsa_forward_kvcache_workspace_bytes(p, kv);
+}
+
+int fcsa_forward_kvcache_quant(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_kvcache_quant* qz, const fcsa_window* w) {
+  if (int rc = check_quant(a, kv, qz)) return rc;
+  if (w == nullptr) return forward_kvcache(a, kv, nullptr, qz);
+  if (int rc = check_window(w, false, false)) return rc;
+  WindowCall win;
+  fcsa_forward_args na = *a;
+  if (!decode_window_sides(a->p, *kv, *w, win, na.p.causal)) return forward_kvcache(&na, kv, nullptr, qz);
+  return forward_kvcache(a, kv, &win, qz);
+}
+
+static int forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv, const WindowCall* win, const fcsa_kvcache_quant* qz) {
+  if (int rc = qz != nullptr ? check_quant(a, kv, qz) : check_kvcache(a, kv)) return rc;
   const fcsa_problem& p = a->p;
   if (p.batch == 0) return FCSA_OK;
   const int es = elem_size(p.dtype);
@@ -527,11 +555,12 @@ static int forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv, c
       return fail(FCSA_ERR_WORKSPACE, "kvcache: workspace too small: %zu < %zu bytes", a->workspace_bytes, d.total);
     if ((reinterpret_cast<uintptr_t>(a->workspace) & 255) != 0) return fail(FCSA_ERR_WORKSPACE, "kvcache: workspace not 256-byte aligned");
   }
-  fcsa::DecodeWinParams dp;
+  fcsa::DecodeFp8Params dp;      // the 16-bit kernels get its DecodeParams / DecodeWinParams part
+  const int ces = qz != nullptr ? 1 : es;
   dp.q = view(a->q, es);
   dp.o = view(a->o, es);
-  dp.kc = view(kv->k_cache, es);
-  dp.vc = view(kv->v_cache, es);
+  dp.kc = view(kv->k_cache, ces);
+  dp.vc = view(kv->v_cache, ces);
   dp.kn = view(kv->k_new, es);
   dp.vn = view(kv->v_new, es);
   dp.seqlens = kv->cache_seqlens;
@@ -551,6 +580,17 @@ static int forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv, c
   dp.ws_o = static_cast<float*>(a->workspace);
   dp.ws_ml = reinterpret_cast<float*>(static_cast<char*>(a->workspace) + d.ws_ml);
   if (win != nullptr) { dp.window = 1; dp.win_lo = win->lo; dp.win_hi = win->hi; }
+  if (qz != nullptr) {
+    dp.k_scale = qz->k_scale; dp.v_scale = qz->v_scale;
+    dp.ks_b = qz->k_scale_stride0; dp.ks_h = qz->k_scale_stride1;
+    dp.vs_b = qz->v_scale_stride0; dp.vs_h = qz->v_scale_stride1;
+    if (kv->new_len > 0 && kv->capacity > 0) {
+      if (int rc = timed("kv_append_fp8", "kv append (fp8)", s, [&] { return fcsa::launch_kv_append_fp8(p.dtype, p.dim_head, dp, s); })) return rc;
+    }
+    if (!rows) return FCSA_OK;
+    if (int rc = timed("decode_fp8", "decode (fp8)", s, [&] { return fcsa::launch_decode_fp8(p.dtype, p.dim_head, dp, s); })) return rc;
+    return timed("decode_combine_fp8", "decode combine (fp8)", s, [&] { return fcsa::launch_decode_combine_fp8(p.dtype, p.dim_head, dp, s); });
+  }
   // 1. the append (before anything reads the cache: same stream), 2. the split partials, 3. their combine
   if (kv->new_len > 0 && kv->capacity > 0) {
     if (int rc = timed("kv_append", "kv append", s, [&] { return fcsa::launch_kv_append(p.dtype, p.dim_head, dp, s); })) return rc;

@@ -8,6 +8,10 @@
 //                         wave-private LDS block for the transposed reads of O^T = V^T P~^T.  Partials (P~V, row max, row sum) in f32.
 //   decode_combine_kernel reconciles the splits of every row (a per-split row max in the per-row-shift regime, a common shift
 //                         otherwise) and normalises.
+// An fp8 cache (fcsa_forward_kvcache_quant: one-byte OCP e4m3fn codes and a float32 scale per (batch, K/V head)) has entry points of its
+// own -- kv_append_fp8_kernel, decode_fp8_kernel (decode_body with FP8), decode_combine_fp8_kernel -- so the kernels above are what
+// they were.  A lane reads 8 key bytes per fragment (the same features as its 16-bit fragment) and converts them with v_cvt_pk_f32_fp8;
+// every code is exact in f16 and bf16, so the operands of both MFMA products are what a 16-bit cache holding the codes would feed.
 #include "fcsa_common.cuh"
 
 #include <cmath>
@@ -53,6 +57,14 @@ template <typename T> FCSA_DEV void unpack(const u32x4& u, float (&x)[Unit<T>::U
   } else {
 #pragma unroll
     for (int e = 0; e < 4; ++e) { x[2 * e] = Traits<T>::lo(u[e]); x[2 * e + 1] = Traits<T>::hi(u[e]); }
+  }
+}
+// eight e4m3fn codes (byte e of the pair = element e) -> their exact float32 values
+FCSA_DEV void unpack_fp8(const u32x2& u, float (&x)[8]) {
+#pragma unroll
+  for (int w = 0; w < 2; ++w) {
+    const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)u[w], false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)u[w], true);
+    x[4 * w] = a[0]; x[4 * w + 1] = a[1]; x[4 * w + 2] = b[0]; x[4 * w + 3] = b[1];
   }
 }
 template <typename T> FCSA_DEV u32x4 pack(const float (&x)[Unit<T>::UE], float mul) {
@@ -185,13 +197,17 @@ FCSA_DEV const char* cache_base(const DecodeParams& p, const View& v, int b, int
   return v.p + (int64_t)b * v.sb + (int64_t)kvh * v.sh + (int64_t)first * v.sn;
 }
 
-template <typename T, int D> struct DecodeRegs {
+// FP8: the cache holds one-byte codes -- a K fragment is 8 bytes, a 16-byte V chunk 16 features (at D = 16 half the lanes have none)
+template <typename T, int D, bool FP8 = false> struct DecodeRegs {
   static constexpr int ES = Traits<T>::ES;
+  static constexpr int CES = FP8 ? 1 : ES;                         // bytes of a cache element
   static constexpr int UE = Unit<T>::UE;
   static constexpr int NJ = ES == 2 ? (D + 31) / 32 : D / 16;     // fragments of a row per lane
-  static constexpr int CPR = D * ES / 16;                          // 16-byte chunks of a row
-  static constexpr int VCH = kDecodeBlock * CPR / 64;              // V chunks per lane of a 32-key block
-  u32x4 k[2][NJ];
+  static constexpr int CPR = D * CES / 16;                         // 16-byte chunks of a row
+  static constexpr int VTOT = kDecodeBlock * CPR;                  // V chunks of a 32-key block
+  static constexpr int VCH = (VTOT + 63) / 64;                     // ... per lane
+  typedef std::conditional_t<FP8, u32x2, u32x4> KFrag;
+  KFrag k[2][NJ];
   u32x4 v[VCH];
 
   // the 32-key block from `kb`; positions at or beyond `end` read position end - 1 (in bounds) and their V chunks are zeroed
@@ -214,12 +230,15 @@ template <typename T, int D> struct DecodeRegs {
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
         const int f = (4 * j + hi) * UE;
-        k[sb][j] = f < D ? *reinterpret_cast<const u32x4*>(row + f * ES) : u32x4{0u, 0u, 0u, 0u};
+        k[sb][j] = f < D ? *reinterpret_cast<const KFrag*>(row + f * CES) : KFrag{};
       }
     }
 #pragma unroll
     for (int t = 0; t < VCH; ++t) {
       const int c = lane + 64 * t, kk = c / CPR, ch = c % CPR, sb = kk >> 4;
+      if constexpr (VTOT % 64 != 0) {
+        if (c >= VTOT) { v[t] = u32x4{0u, 0u, 0u, 0u}; continue; }
+      }
       const int pos = min(kb + kk, end - 1);
       const char* src = (sb ? vbase[1] : vbase[0]) + (int64_t)(pos - (sb ? first[1] : first[0])) * p.vc.sn + ch * 16;
       const u32x4 val = *reinterpret_cast<const u32x4*>(src);
@@ -230,9 +249,13 @@ template <typename T, int D> struct DecodeRegs {
 
 // WIN (decode_win_kernel): a sliding window -- the key range of the sequence starts at the 32-key block that holds the first key its
 // first query sees (win_decode_first) instead of 0, and the window's two bounds join the visibility test
-template <typename T, int D, bool DYN, bool GEN, bool WIN>
-FCSA_DEV void decode_body(const std::conditional_t<WIN, DecodeWinParams, DecodeParams>& p) {
-  typedef DecodeRegs<T, D> R;
+// FP8 (decode_fp8_kernel): an e4m3fn cache.  K: with l2norm the codes are scaled by k_scale, normalised and rounded as 16-bit keys are;
+// without it the exact codes are the operands and k_scale joins the float32 logit multiplier.  V: converted to T on the way into LDS
+// (exact); v_scale is applied by the combine.
+template <typename T, int D, bool DYN, bool GEN, bool WIN, bool FP8 = false>
+FCSA_DEV void decode_body(const std::conditional_t<FP8, DecodeFp8Params, std::conditional_t<WIN, DecodeWinParams, DecodeParams>>& p) {
+  static_assert(!FP8 || Traits<T>::ES == 2, "an fp8 cache is read with 16-bit queries");
+  typedef DecodeRegs<T, D, FP8> R;
   typedef DecodeLds<D, R::ES, GEN> LP;
   constexpr int ES = R::ES, UE = R::UE, NJ = R::NJ, CPR = R::CPR, VCH = R::VCH;
   constexpr int FB = D / 16;                       // 16-feature blocks of O^T
@@ -286,7 +309,12 @@ FCSA_DEV void decode_body(const std::conditional_t<WIN, DecodeWinParams, DecodeP
 #pragma unroll
     for (int j = 0; j < NJ; ++j) qf[j] = pack<T>(xq[j], p.l2norm ? p.c1 : 1.f);     // c1 * q^, one rounding (the dense kernels' qn)
   }
-  const float smul = p.l2norm ? 1.f : p.c1;
+  float smul = p.l2norm ? 1.f : p.c1;
+  float kscale = 1.f;
+  if constexpr (FP8) {
+    kscale = p.k_scale[(int64_t)b * p.ks_b + (int64_t)kvh * p.ks_h];
+    if (!p.l2norm) smul *= kscale;
+  }
 
   f32x4 acc[FB];
 #pragma unroll
@@ -307,7 +335,18 @@ FCSA_DEV void decode_body(const std::conditional_t<WIN, DecodeWinParams, DecodeP
     for (int sb = 0; sb < 2; ++sb) {
       float xk[NJ][UE];
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) unpack<T>(cur.k[sb][j], xk[j]);
+      for (int j = 0; j < NJ; ++j) {
+        if constexpr (FP8) unpack_fp8(cur.k[sb][j], xk[j]);
+        else unpack<T>(cur.k[sb][j], xk[j]);
+      }
+      if constexpr (FP8) {
+        if (p.l2norm) {
+#pragma unroll
+          for (int j = 0; j < NJ; ++j)
+#pragma unroll
+            for (int e = 0; e < UE; ++e) xk[j][e] *= kscale;
+        }
+      }
       if (p.l2norm) normalise(xk);
       s[sb] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -354,7 +393,22 @@ FCSA_DEV void decode_body(const std::conditional_t<WIN, DecodeWinParams, DecodeP
 #pragma unroll
     for (int t = 0; t < VCH; ++t) {
       const int c = lane + 64 * t;
-      *reinterpret_cast<u32x4*>(smem + (c / CPR) * LP::PITCH + (c % CPR) * 16) = cur.v[t];
+      if constexpr (FP8) {
+        if (R::VTOT % 64 == 0 || c < R::VTOT) {
+          u32x4 w[2];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)cur.v[t][e], false), b2 = __builtin_amdgcn_cvt_pk_f32_fp8((int)cur.v[t][e], true);
+            w[e >> 1][2 * (e & 1)] = Traits<T>::pack2(a[0], a[1]);
+            w[e >> 1][2 * (e & 1) + 1] = Traits<T>::pack2(b2[0], b2[1]);
+          }
+          u32x4* dst = reinterpret_cast<u32x4*>(smem + (c / CPR) * LP::PITCH + (c % CPR) * 32);
+          dst[0] = w[0];
+          dst[1] = w[1];
+        }
+      } else {
+        *reinterpret_cast<u32x4*>(smem + (c / CPR) * LP::PITCH + (c % CPR) * 16) = cur.v[t];
+      }
     }
     __syncthreads();
     if constexpr (ES == 2) {
@@ -413,6 +467,11 @@ __global__ __launch_bounds__(64) void decode_win_kernel(DecodeWinParams p) {
   decode_body<T, D, DYN, GEN, true>(p);
 }
 
+template <typename T, int D, bool DYN, bool GEN, bool WIN>
+__global__ __launch_bounds__(64) void decode_fp8_kernel(DecodeFp8Params p) {
+  decode_body<T, D, DYN, GEN, WIN, true>(p);
+}
+
 // o = sum_s 2^(m_s - M) P~V_s / sum_s 2^(m_s - M) l_s over the splits of a row (static regime: every m_s is the common shift, weight 1)
 template <typename T, int D>
 __global__ __launch_bounds__(256) void decode_combine_kernel(DecodeParams p) {
@@ -447,6 +506,55 @@ __global__ __launch_bounds__(256) void decode_combine_kernel(DecodeParams p) {
     *reinterpret_cast<u32x2*>(dst) = u32x2{Traits<T>::pack2(acc[0], acc[1]), Traits<T>::pack2(acc[2], acc[3])};
   }
 }
+// decode_combine_kernel for an fp8 cache (16-bit T): the cache's values are v_scale * code, so the row's v_scale joins the normaliser
+template <typename T, int D>
+__global__ __launch_bounds__(256) void decode_combine_fp8_kernel(DecodeFp8Params p) {
+  constexpr int TPR = D / 4;
+  const int64_t rows = (int64_t)p.B * p.H * p.N;
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t row = t / TPR;
+  const int c = (int)(t % TPR);
+  if (row >= rows) return;
+  float M = -INFINITY;
+  for (int s = 0; s < p.splits; ++s) M = fmaxf(M, p.ws_ml[(s * rows + row) * 2]);
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  float l = 0.f;
+  if (M != -INFINITY) {
+    for (int s = 0; s < p.splits; ++s) {
+      const f32x2 ml = *reinterpret_cast<const f32x2*>(p.ws_ml + (s * rows + row) * 2);
+      const float w = exp2f(ml[0] - M);
+      l += w * ml[1];
+      acc += w * *reinterpret_cast<const f32x4*>(p.ws_o + (s * rows + row) * D + 4 * c);
+    }
+  }
+  const int i = (int)(row % p.N);
+  const int64_t bh = row / p.N;
+  const int h = (int)(bh % p.H), b = (int)(bh / p.H);
+  const float inv = p.dyn ? (l > 0.f ? 1.f / l : 0.f) : 1.f / fmaxf(l, p.l_eps);
+  acc *= inv * p.v_scale[(int64_t)b * p.vs_b + (int64_t)(h / p.G) * p.vs_h];
+  char* dst = p.o.p + (int64_t)b * p.o.sb + (int64_t)h * p.o.sh + (int64_t)i * p.o.sn + 4 * c * 2;
+  *reinterpret_cast<u32x2*>(dst) = u32x2{Traits<T>::pack2(acc[0], acc[1]), Traits<T>::pack2(acc[2], acc[3])};
+}
+
+// 16 elements of T (two 16-byte chunks) -> 16 e4m3fn codes: e4m3_rne(clamp(x / scale, -448, 448)).  The divide is the correctly rounded
+// float32 one; the clamp is explicit, so saturation does not hang on the conversion's overflow mode; NaN passes the clamp as NaN.
+template <typename T> FCSA_DEV u32x4 quantise16(const u32x4& a, const u32x4& b, float scale) {
+  u32x4 out;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const u32x4& src = w < 2 ? a : b;
+    float x[4] = {Traits<T>::lo(src[2 * (w & 1)]), Traits<T>::hi(src[2 * (w & 1)]), Traits<T>::lo(src[2 * (w & 1) + 1]), Traits<T>::hi(src[2 * (w & 1) + 1])};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float y = x[e] / scale;
+      x[e] = y != y ? y : fminf(fmaxf(y, -448.f), 448.f);
+    }
+    int code = __builtin_amdgcn_cvt_pk_fp8_f32(x[0], x[1], 0, false);
+    code = __builtin_amdgcn_cvt_pk_fp8_f32(x[2], x[3], code, true);
+    out[w] = (uint32_t)code;
+  }
+  return out;
+}
 
 // one thread per 16-byte chunk of an appended row; slots at or beyond the capacity are dropped
 template <typename T, int D>
@@ -477,6 +585,37 @@ __global__ __launch_bounds__(256) void kv_append_kernel(DecodeParams p) {
   const int64_t vsrc = (int64_t)b * p.vn.sb + (int64_t)kvh * p.vn.sh + (int64_t)tn * p.vn.sn;
   *reinterpret_cast<u32x4*>(p.kc.p + kdst + ch * 16) = *reinterpret_cast<const u32x4*>(p.kn.p + ksrc + ch * 16);
   *reinterpret_cast<u32x4*>(p.vc.p + vdst + ch * 16) = *reinterpret_cast<const u32x4*>(p.vn.p + vsrc + ch * 16);
+}
+
+// kv_append_kernel for an fp8 cache: one thread per 16 OUTPUT bytes -- 32 bytes of k_new / v_new (16-bit T) become 16 codes
+template <typename T, int D>
+__global__ __launch_bounds__(256) void kv_append_fp8_kernel(DecodeFp8Params p) {
+  constexpr int CPR = D / 16;
+  const int64_t total = (int64_t)p.B * p.Hk * p.new_len * CPR;
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= total) return;
+  const int ch = (int)(t % CPR);
+  int64_t rest = t / CPR;
+  const int tn = (int)(rest % p.new_len);
+  rest /= p.new_len;
+  const int kvh = (int)(rest % p.Hk), b = (int)(rest / p.Hk);
+  const int64_t start = p.seqlens != nullptr ? min(max((int64_t)p.seqlens[b], (int64_t)0), (int64_t)p.capacity) : (int64_t)p.capacity;
+  const int64_t pos = start + tn;
+  if (pos >= p.capacity) return;
+  int64_t kdst, vdst;
+  if (p.table != nullptr) {
+    int blk = p.table[(int64_t)b * p.table_stride + pos / p.page];
+    blk = min(max(blk, 0), p.num_blocks - 1);
+    kdst = (int64_t)blk * p.kc.sb + (int64_t)kvh * p.kc.sh + (pos % p.page) * p.kc.sn;
+    vdst = (int64_t)blk * p.vc.sb + (int64_t)kvh * p.vc.sh + (pos % p.page) * p.vc.sn;
+  } else {
+    kdst = (int64_t)b * p.kc.sb + (int64_t)kvh * p.kc.sh + pos * p.kc.sn;
+    vdst = (int64_t)b * p.vc.sb + (int64_t)kvh * p.vc.sh + pos * p.vc.sn;
+  }
+  const u32x4* ks = reinterpret_cast<const u32x4*>(p.kn.p + (int64_t)b * p.kn.sb + (int64_t)kvh * p.kn.sh + (int64_t)tn * p.kn.sn + ch * 32);
+  const u32x4* vs = reinterpret_cast<const u32x4*>(p.vn.p + (int64_t)b * p.vn.sb + (int64_t)kvh * p.vn.sh + (int64_t)tn * p.vn.sn + ch * 32);
+  *reinterpret_cast<u32x4*>(p.kc.p + kdst + ch * 16) = quantise16<T>(ks[0], ks[1], p.k_scale[(int64_t)b * p.ks_b + (int64_t)kvh * p.ks_h]);
+  *reinterpret_cast<u32x4*>(p.vc.p + vdst + ch * 16) = quantise16<T>(vs[0], vs[1], p.v_scale[(int64_t)b * p.vs_b + (int64_t)kvh * p.vs_h]);
 }
 
 int64_t blocks_of(int64_t threads) { return (threads + 255) / 256; }
@@ -513,6 +652,64 @@ hipError_t launch_decode(int dtype, int D, const DecodeWinParams& p, hipStream_t
       else return hipErrorInvalidValue;
     }
     return p.dyn ? go(Y{}, N{}) : go(N{}, N{});
+  });
+}
+
+// ---- the fp8 cache: 16-bit q / o only ----
+hipError_t launch_kv_append_fp8(int dtype, int D, const DecodeFp8Params& p, hipStream_t s) {
+  if (dtype != 1 && dtype != 2) return hipErrorInvalidValue;
+  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    if constexpr (Traits<T>::ES == 2) {
+      const int64_t threads = (int64_t)p.B * p.Hk * p.new_len * (DD / 16);
+      if (threads <= 0) return hipSuccess;
+      hipLaunchKernelGGL((kv_append_fp8_kernel<T, DD>), dim3((unsigned)blocks_of(threads)), dim3(256), 0, s, p);
+      return hipGetLastError();
+    } else {
+      return hipErrorInvalidValue;
+    }
+  });
+}
+
+hipError_t launch_decode_fp8(int dtype, int D, const DecodeFp8Params& p, hipStream_t s) {
+  if (dtype != 1 && dtype != 2) return hipErrorInvalidValue;
+  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    if constexpr (Traits<T>::ES == 2) {
+      const dim3 grid((unsigned)((int64_t)p.B * p.Hk * p.row_tiles * p.splits));
+      auto go = [&](auto dyn, auto gen) -> hipError_t {
+        constexpr bool DY = decltype(dyn)::value, GN = decltype(gen)::value;
+        if (p.window) return launch_with_lds<decode_fp8_kernel<T, DD, DY, GN, true>>(grid, dim3(64), DecodeLds<DD, 2, GN>::BYTES, s, p);
+        return launch_with_lds<decode_fp8_kernel<T, DD, DY, GN, false>>(grid, dim3(64), DecodeLds<DD, 2, GN>::BYTES, s, p);
+      };
+      using Y = std::true_type;
+      using N = std::false_type;
+      if (p.l2norm && !decode_groups_fast(DD, p.groups, Unit<T>::UE)) {
+        if constexpr (DD == 96) return p.dyn ? go(Y{}, Y{}) : go(N{}, Y{});
+        else return hipErrorInvalidValue;
+      }
+      return p.dyn ? go(Y{}, N{}) : go(N{}, N{});
+    } else {
+      return hipErrorInvalidValue;
+    }
+  });
+}
+
+hipError_t launch_decode_combine_fp8(int dtype, int D, const DecodeFp8Params& p, hipStream_t s) {
+  if (dtype != 1 && dtype != 2) return hipErrorInvalidValue;
+  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    if constexpr (Traits<T>::ES == 2) {
+      const int64_t threads = (int64_t)p.B * p.H * p.N * (DD / 4);
+      if (threads <= 0) return hipSuccess;
+      hipLaunchKernelGGL((decode_combine_fp8_kernel<T, DD>), dim3((unsigned)blocks_of(threads)), dim3(256), 0, s, p);
+      return hipGetLastError();
+    } else {
+      return hipErrorInvalidValue;
+    }
   });
 }
 

@@ -135,9 +135,21 @@ struct DecodeWinParams : DecodeParams {      // (see FwdWinParams; decode_win_ke
   int window = 0;           // 1: sliding window, sides as win_normalise gives them (causal: win_hi = 0):
   int win_lo = 0, win_hi = 0;   //    the query at position t sees key j iff t - win_lo <= j <= t + win_hi
 };
+// An fp8 cache (fcsa_forward_kvcache_quant): kc / vc hold one-byte OCP e4m3fn codes (views in bytes), and the cache means
+// k_scale[b, kvh] * code, v_scale[b, kvh] * code.  Only the fp8 kernels (kv_append_fp8_kernel, decode_fp8_kernel,
+// decode_combine_fp8_kernel) get this block; the 16-bit kernels are launched with the part they always had.
+struct DecodeFp8Params : DecodeWinParams {
+  const float* k_scale = nullptr;   // element [b * ks_b + kvh * ks_h]; a stride of 0 broadcasts
+  const float* v_scale = nullptr;
+  int64_t ks_b = 0, ks_h = 0, vs_b = 0, vs_h = 0;
+};
 hipError_t launch_kv_append(int dtype, int D, const DecodeParams& p, hipStream_t s);
 hipError_t launch_decode(int dtype, int D, const DecodeWinParams& p, hipStream_t s);
 hipError_t launch_decode_combine(int dtype, int D, const DecodeParams& p, hipStream_t s);
+// dtype: the type of q, o and the appended rows (f16 or bf16; float32 is refused)
+hipError_t launch_kv_append_fp8(int dtype, int D, const DecodeFp8Params& p, hipStream_t s);
+hipError_t launch_decode_fp8(int dtype, int D, const DecodeFp8Params& p, hipStream_t s);
+hipError_t launch_decode_combine_fp8(int dtype, int D, const DecodeFp8Params& p, hipStream_t s);
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE property of a kernel: raise it once per (instantiation, device).
 // `done` is the instantiation's bit mask of devices that have it (one static per launcher); thread safe, idempotent.

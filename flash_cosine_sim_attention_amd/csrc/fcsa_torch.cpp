@@ -46,6 +46,10 @@ struct Abi {
   size_t (*backward_window_ws)(const fcsa_problem*, const fcsa_varlen*, const fcsa_window*) = &fcsa_backward_window_workspace_bytes;
   int (*forward_kvcache_window)(const fcsa_forward_args*, const fcsa_kvcache*, const fcsa_window*) = &fcsa_forward_kvcache_window;
   size_t (*forward_kvcache_window_ws)(const fcsa_problem*, const fcsa_kvcache*, const fcsa_window*) = &fcsa_forward_kvcache_window_workspace_bytes;
+  // fp8 key/value cache: null in a swapped-in library that does not export it (the fp8 op then raises)
+  int (*forward_kvcache_quant)(const fcsa_forward_args*, const fcsa_kvcache*, const fcsa_kvcache_quant*, const fcsa_window*) = &fcsa_forward_kvcache_quant;
+  size_t (*forward_kvcache_quant_ws)(const fcsa_problem*, const fcsa_kvcache*, const fcsa_kvcache_quant*, const fcsa_window*) =
+      &fcsa_forward_kvcache_quant_workspace_bytes;
 } g_abi;
 
 using at::Tensor;
@@ -756,16 +760,29 @@ Tensor varlen_window_attention_autograd(const Tensor& q, const Tensor& k, const 
 // and block_table int32 [B, max_blocks] on q's device.  Table contents are never read on the host: the call does not synchronise.
 Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const optional<Tensor>& k_new, const optional<Tensor>& v_new,
                             const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table, int64_t max_seqlen_k, double scale, bool causal,
-                            bool l2norm_qk, int64_t groups, const fcsa_window* win) {
+                            bool l2norm_qk, int64_t groups, const fcsa_window* win, const Tensor* k_scale = nullptr, const Tensor* v_scale = nullptr) {
+  const bool fp8 = k_scale != nullptr;      // an e4m3fn cache with its two scale tensors (kvcache_fp8_forward)
   TORCH_CHECK(g_abi.forward_kvcache != nullptr && g_abi.forward_kvcache_ws != nullptr,
               "flash_cosine_sim_attention_with_kvcache: the loaded libfcsa_hip.so does not export fcsa_forward_kvcache");
+  TORCH_CHECK(!fp8 || (g_abi.forward_kvcache_quant != nullptr && g_abi.forward_kvcache_quant_ws != nullptr),
+              "flash_cosine_sim_attention_with_kvcache: the loaded libfcsa_hip.so does not export fcsa_forward_kvcache_quant");
   TORCH_CHECK(q.is_cuda(), "flash_cosine_sim_attention_with_kvcache: q and the caches must be GPU tensors (HIP kernels only)");
   auto same_dev = [&](const char* name, const Tensor& t) {
     TORCH_CHECK_VALUE(t.device() == q.device(), name, " is on ", t.device(), " but q is on ", q.device(), ": all tensors must live on q's GPU");
   };
   same_dev("k_cache", k_cache);
   same_dev("v_cache", v_cache);
-  TORCH_CHECK_TYPE(q.scalar_type() == k_cache.scalar_type() && q.scalar_type() == v_cache.scalar_type(), "q, k_cache, v_cache must share a dtype");
+  if (fp8) {
+    // the codes travel as bytes (the Python entry point passes float8_e4m3fn caches as their uint8 views: the dispatcher's own machinery
+    // -- opcheck, functionalisation -- runs arithmetic on mutated arguments, which float8 tensors do not support)
+    TORCH_CHECK_TYPE(k_cache.scalar_type() == at::kByte && v_cache.scalar_type() == at::kByte,
+                     "kvcache_fp8_forward takes the e4m3fn codes of both caches as uint8 tensors (cache.view(torch.uint8)), got ",
+                     k_cache.scalar_type(), " and ", v_cache.scalar_type());
+    TORCH_CHECK_TYPE(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16,
+                     "fp8 caches take float16 or bfloat16 queries, got ", q.scalar_type());
+  } else {
+    TORCH_CHECK_TYPE(q.scalar_type() == k_cache.scalar_type() && q.scalar_type() == v_cache.scalar_type(), "q, k_cache, v_cache must share a dtype");
+  }
   dtype_code(q.scalar_type());
   TORCH_CHECK_VALUE(q.dim() == 4 && k_cache.dim() == 4 && v_cache.dim() == 4, "q, k_cache, v_cache must have 4 dimensions");
   TORCH_CHECK_VALUE(k_cache.sizes() == v_cache.sizes(), "k_cache and v_cache must have the same shape");
@@ -840,7 +857,28 @@ Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor
   std::memset(&none, 0, sizeof(none));
   kv.k_new = kn.defined() && new_len > 0 ? view4(kn) : none;
   kv.v_new = vn.defined() && new_len > 0 ? view4(vn) : none;
-  const size_t wsb = win != nullptr ? g_abi.forward_kvcache_window_ws(&a.p, &kv, win) : g_abi.forward_kvcache_ws(&a.p, &kv);
+  fcsa_kvcache_quant qz;
+  std::memset(&qz, 0, sizeof(qz));
+  Tensor ks, vs;
+  if (fp8) {
+    // float32 [], [Hk] or [B, Hk] on q's device: element strides of (batch, K/V head), 0 where the scale broadcasts
+    auto scale_of = [&](const char* name, const Tensor& t, int64_t& s0, int64_t& s1) {
+      same_dev(name, t);
+      TORCH_CHECK_TYPE(t.scalar_type() == at::kFloat, name, " must be float32");
+      const bool ok = t.dim() == 0 || (t.dim() == 1 && t.size(0) == Hk) || (t.dim() == 2 && t.size(0) == B && t.size(1) == Hk);
+      TORCH_CHECK_VALUE(ok, name, " must have shape [], [", Hk, "] or [", B, ", ", Hk, "], got ", t.sizes());
+      s0 = t.dim() == 2 ? t.stride(0) : 0;
+      s1 = t.dim() == 2 ? t.stride(1) : t.dim() == 1 ? t.stride(0) : 0;
+      return t;
+    };
+    ks = scale_of("k_scale", *k_scale, qz.k_scale_stride0, qz.k_scale_stride1);
+    vs = scale_of("v_scale", *v_scale, qz.v_scale_stride0, qz.v_scale_stride1);
+    qz.cache_dtype = FCSA_CACHE_E4M3;
+    qz.k_scale = ks.data_ptr<float>();
+    qz.v_scale = vs.data_ptr<float>();
+  }
+  const size_t wsb = fp8 ? g_abi.forward_kvcache_quant_ws(&a.p, &kv, &qz, win)
+                         : win != nullptr ? g_abi.forward_kvcache_window_ws(&a.p, &kv, win) : g_abi.forward_kvcache_ws(&a.p, &kv);
   Tensor ws;
   if (wsb > 0) {
     ws = at::empty({(int64_t)wsb}, q.options().dtype(at::kByte));      // the caching allocator
@@ -848,7 +886,8 @@ Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor
     a.workspace_bytes = wsb;
   }
   a.stream = stream_of(q);
-  if (win != nullptr) check(g_abi.forward_kvcache_window(&a, &kv, win), "fcsa_forward_kvcache_window");
+  if (fp8) check(g_abi.forward_kvcache_quant(&a, &kv, &qz, win), "fcsa_forward_kvcache_quant");
+  else if (win != nullptr) check(g_abi.forward_kvcache_window(&a, &kv, win), "fcsa_forward_kvcache_window");
   else check(g_abi.forward_kvcache(&a, &kv), "fcsa_forward_kvcache");
   return o;
 }
@@ -862,6 +901,15 @@ Tensor kvcache_window_forward(const Tensor& q, const Tensor& k_cache, const Tens
                               int64_t max_seqlen_k, double scale, bool causal, bool l2norm_qk, int64_t groups, int64_t left, int64_t right) {
   const Win win(left, right);
   return kvcache_forward_impl(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups, &win.w);
+}
+
+// an e4m3fn cache: window sides of (-1, -1) are the un-windowed call
+Tensor kvcache_fp8_forward(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const optional<Tensor>& k_new, const optional<Tensor>& v_new,
+                           const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table, const Tensor& k_scale, const Tensor& v_scale,
+                           int64_t max_seqlen_k, double scale, bool causal, bool l2norm_qk, int64_t groups, int64_t left, int64_t right) {
+  const Win win(left, right);
+  return kvcache_forward_impl(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups,
+                              left == -1 && right == -1 ? nullptr : &win.w, &k_scale, &v_scale);
 }
 
 }  // namespace
@@ -893,6 +941,8 @@ extern "C" int fcsa_torch_use_library(const char* path) {
   a.backward_window_ws = reinterpret_cast<decltype(a.backward_window_ws)>(dlsym(h, "fcsa_backward_window_workspace_bytes"));
   a.forward_kvcache_window = reinterpret_cast<decltype(a.forward_kvcache_window)>(dlsym(h, "fcsa_forward_kvcache_window"));
   a.forward_kvcache_window_ws = reinterpret_cast<decltype(a.forward_kvcache_window_ws)>(dlsym(h, "fcsa_forward_kvcache_window_workspace_bytes"));
+  a.forward_kvcache_quant = reinterpret_cast<decltype(a.forward_kvcache_quant)>(dlsym(h, "fcsa_forward_kvcache_quant"));
+  a.forward_kvcache_quant_ws = reinterpret_cast<decltype(a.forward_kvcache_quant_ws)>(dlsym(h, "fcsa_forward_kvcache_quant_workspace_bytes"));
   if (!a.forward || !a.backward || !a.forward_ws || !a.backward_ws || !a.needs_qn || !a.last_error) { dlclose(h); return -2; }
   // Only libraries of THIS ABI: the binding allocates for the struct layouts and buffer contracts of include/fcsa.h as compiled in
   // (e.g. ABI 3 writes d_bias once in the bias dtype into an uninitialised buffer; an ABI-2 library would accumulate float32 into
@@ -940,6 +990,10 @@ TORCH_LIBRARY(fcsa, m) {
         "float scale, bool causal, bool l2norm_qk, int groups, int window_left, int window_right) -> Tensor");
   m.def("kvcache_window_forward(Tensor q, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor? k_new, Tensor? v_new, Tensor? cache_seqlens, "
         "Tensor? block_table, int max_seqlen_k, float scale, bool causal, bool l2norm_qk, int groups, int window_left, int window_right) -> Tensor");
+  // an fp8 (e4m3fn) cache, its codes as uint8 tensors: k_scale / v_scale float32 [], [Hk] or [B, Hk]; the append quantises k_new / v_new
+  m.def("kvcache_fp8_forward(Tensor q, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor? k_new, Tensor? v_new, Tensor? cache_seqlens, "
+        "Tensor? block_table, Tensor k_scale, Tensor v_scale, int max_seqlen_k, float scale, bool causal, bool l2norm_qk, int groups, "
+        "int window_left, int window_right) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(fcsa, CUDA, m) {       // ROCm builds of PyTorch dispatch HIP tensors under the CUDA key
@@ -957,6 +1011,7 @@ TORCH_LIBRARY_IMPL(fcsa, CUDA, m) {       // ROCm builds of PyTorch dispatch HIP
   m.impl("varlen_window_backward", &varlen_window_backward);
   m.impl("varlen_window_attention", &varlen_window_attention_plain);
   m.impl("kvcache_window_forward", &kvcache_window_forward);
+  m.impl("kvcache_fp8_forward", &kvcache_fp8_forward);
 }
 
 TORCH_LIBRARY_IMPL(fcsa, Autograd, m) {

@@ -252,8 +252,27 @@ def flash_cosine_sim_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_s
 # decoding against a key/value cache (flash-attn's kvcache convention; no reference counterpart)
 # ---------------------------------------------------------------------------------------------
 
+def _cache_scale(name, s, B, Hk, device):
+    """k_scale / v_scale of an fp8 cache as a float32 tensor of shape [], [Hk] or [B, Hk] on `device`.  None: 1.0.  Values the host can
+    see (a number, a host tensor) must be finite and > 0; a tensor already on a GPU is trusted, so the call does not synchronise."""
+    if s is None:
+        s = 1.0
+    if isinstance(s, torch.Tensor):
+        if s.dtype != torch.float32 or tuple(s.shape) not in ((), (Hk,), (B, Hk)):
+            raise TypeError(f"{name} must be a float or a float32 tensor of shape [], [{Hk}] or [{B}, {Hk}], got {s.dtype} {tuple(s.shape)}")
+        if s.device.type == "cpu" and not bool((torch.isfinite(s) & (s > 0)).all()):
+            raise ValueError(f"{name} must be finite and > 0")
+        return s.detach().to(device, non_blocking=True)
+    if isinstance(s, bool) or not isinstance(s, (int, float)):
+        raise TypeError(f"{name} must be a float or a float32 tensor, got {type(s).__name__}")
+    if not (s > 0 and s != float("inf")):
+        raise ValueError(f"{name} must be finite and > 0, got {s}")
+    return torch.full((), float(s), dtype=torch.float32, device=device)
+
+
 def flash_cosine_sim_attention_with_kvcache(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlens=None, block_table=None,
-                                            max_seqlen_k=None, scale=8, groups=1, causal=False, l2norm_qk=True, window_size=(-1, -1)):
+                                            max_seqlen_k=None, scale=8, groups=1, causal=False, l2norm_qk=True, k_scale=None, v_scale=None,
+                                            window_size=(-1, -1)):
     """Forward-only attention of new queries against a key/value cache, with an optional in-place append.
 
     q [B, H, N, D] (N = 1: plain decode; a few: speculative or chunked steps).  k_cache, v_cache: [B, Hk, capacity, D] or, with a
@@ -270,8 +289,31 @@ def flash_cosine_sim_attention_with_kvcache(q, k_cache, v_cache, k_new=None, v_n
     clamp lengths and block ids, so a malformed table gives wrong rows, never an access outside the tensors).  Two sequences appending
     into the same page slot is undefined behaviour.  CPU tensors take the forward-only path of `cpu.py`.
     window_size = (left, right): a sliding window -- the query at position t of its sequence sees the cached keys [t - left, t + right]
-    (-1: unbounded; causal caps right at 0); only the cache blocks from the first visible key on are read."""
+    (-1: unbounded; causal caps right at 0); only the cache blocks from the first visible key on are read.
+    fp8 caches: when k_cache and v_cache are both torch.float8_e4m3fn (OCP e4m3; q, k_new, v_new float16 or bfloat16) they hold one-byte
+    codes that mean k_scale[b, kvh] * code and v_scale[b, kvh] * code, and the result is what this function computes on those values.
+    k_scale, v_scale: a Python float, or a float32 tensor of shape [], [Hk] or [B, Hk]; None is 1.0.  Host scales are checked to be finite
+    and > 0; device tensors are trusted (and with device cache_seqlens and max_seqlen_k given the call does not synchronise).  The append
+    quantises: code = e4m3_rne(clamp(float(x) / scale, -448, 448)), NaN stays NaN.  Choosing scales: for V the per-head amax / 448 uses
+    the whole code range; for K under l2norm_qk the scale cancels (the keys are normalised as they are read), so any value that keeps
+    K's codes in range serves -- amax / 448 again, or 1.0 for keys of ordinary size; without l2norm_qk choose it as for V."""
     window = _window(window_size)
+    fp8_types = tuple(getattr(torch, n) for n in ("float8_e4m3fn", "float8_e4m3fnuz", "float8_e5m2", "float8_e5m2fnuz") if hasattr(torch, n))
+    fp8 = k_cache.dtype in fp8_types or v_cache.dtype in fp8_types
+    if fp8:
+        if k_cache.dtype != v_cache.dtype:
+            raise TypeError(f"one fp8 cache and one {min(k_cache.dtype, v_cache.dtype, key=lambda d: d in fp8_types)} cache: k_cache and "
+                            f"v_cache must both be torch.float8_e4m3fn, got {k_cache.dtype} and {v_cache.dtype}")
+        if k_cache.dtype != torch.float8_e4m3fn:
+            raise TypeError(f"{k_cache.dtype} caches are not supported: an fp8 cache is torch.float8_e4m3fn (OCP e4m3, the gfx950 encoding; "
+                            "float8_e4m3fnuz is MI300's, float8_e5m2 is out of scope)")
+        if q.dtype not in (torch.float16, torch.bfloat16):
+            raise TypeError(f"fp8 caches take float16 or bfloat16 q, k_new and v_new, got a {q.dtype} q")
+        for name, t in (("k_new", k_new), ("v_new", v_new)):
+            if t is not None and t.dtype != q.dtype:
+                raise TypeError(f"{name} must have q's dtype ({q.dtype}), got {t.dtype}")
+    elif k_scale is not None or v_scale is not None:
+        raise TypeError(f"k_scale / v_scale given with {k_cache.dtype} caches: scales belong to torch.float8_e4m3fn caches")
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_new, v_new)):
         raise RuntimeError("flash_cosine_sim_attention_with_kvcache is forward-only: q, k_new and v_new must not require grad "
                            "(run it under torch.no_grad())")
@@ -326,13 +368,16 @@ def flash_cosine_sim_attention_with_kvcache(q, k_cache, v_cache, k_new=None, v_n
                     raise ValueError(f"sequence {b}: block_table entries outside [0, {nb})")
     if max_seqlen_k is not None and (int(max_seqlen_k) != max_seqlen_k or max_seqlen_k < 0):
         raise ValueError(f"max_seqlen_k must be a non-negative integer, got {max_seqlen_k}")
+    if fp8:
+        k_scale, v_scale = _cache_scale("k_scale", k_scale, B, Hk, q.device), _cache_scale("v_scale", v_scale, B, Hk, q.device)
     if q.device.type == "cpu":
         lens = host_lens if host_lens is not None else [capacity - n_new] * B
         if cache_seqlens is not None and host_lens is None:
             raise ValueError("CPU tensors take host cache_seqlens")
         detach = lambda t: None if t is None else t.detach()          # (grad mode is off here, or nothing requires grad)
+        quant = dict(k_scale=k_scale.expand(B, Hk), v_scale=v_scale.expand(B, Hk)) if fp8 else {}
         return _cpu.attention_forward_kvcache_cpu(q.detach(), k_cache, v_cache, detach(k_new), detach(v_new), lens, block_table,
-                                                  scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, window_size=window)
+                                                  scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, window_size=window, **quant)
     if isinstance(cache_seqlens, int):
         cache_seqlens = torch.full((B,), cache_seqlens, dtype=torch.int32, device=q.device)
     elif cache_seqlens is not None:
@@ -340,6 +385,10 @@ def flash_cosine_sim_attention_with_kvcache(q, k_cache, v_cache, k_new=None, v_n
     if block_table is not None:
         block_table = block_table.to(q.device, non_blocking=True)
     max_k = capacity if max_seqlen_k is None else min(int(max_seqlen_k), capacity)
+    if fp8:
+        # (the op takes the codes as bytes: same storage, so the append lands in the caller's caches)
+        return _torch_ops.load().kvcache_fp8_forward(q, k_cache.view(torch.uint8), v_cache.view(torch.uint8), k_new, v_new, cache_seqlens, block_table, k_scale, v_scale,
+                                                     int(max_k), float(scale), bool(causal), bool(l2norm_qk), int(groups), window[0], window[1])
     if window != (-1, -1):
         return _torch_ops.load().kvcache_window_forward(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, int(max_k),
                                                         float(scale), bool(causal), bool(l2norm_qk), int(groups), window[0], window[1])

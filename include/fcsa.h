@@ -274,6 +274,34 @@ size_t fcsa_backward_window_workspace_bytes(const fcsa_problem* p, const fcsa_va
 int    fcsa_forward_kvcache_window(const fcsa_forward_args* args, const fcsa_kvcache* cache, const fcsa_window* window);
 size_t fcsa_forward_kvcache_window_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* cache, const fcsa_window* window);
 
+/* fcsa_forward_kvcache against a QUANTISED cache: k_cache / v_cache hold one-byte OCP e4m3fn codes (the gfx950 encoding; MI300's e4m3fnuz
+ * is a different encoding and is not accepted) and MEAN the values k_scale[b, kvh] * float(code), v_scale[b, kvh] * float(code).  The
+ * result is what fcsa_forward_kvcache[_window] computes on those values: regimes, causal alignment, window rule, o = 0 for L_b == 0 and the
+ * clamping of lengths and block ids are unchanged.  p.dtype stays the type of q, o, k_new and v_new: FCSA_F16 or FCSA_BF16 (FCSA_F32:
+ * FCSA_ERR_UNSUPPORTED).  The cache views keep ELEMENT strides, an element being one byte here: rows 16-byte aligned, feature dim
+ * contiguous, contiguous or paged as above.
+ * The append quantises: the code written for an element x of k_new / v_new is e4m3_rne(clamp(float(x) / scale, -448, 448)) -- one
+ * correctly rounded float32 divide, an explicit clamp (finite values saturate at +-448, never to NaN), round to nearest even; NaN stays
+ * NaN.  Slots at or beyond the capacity are dropped and cache_seqlens is not advanced, as in fcsa_forward_kvcache.
+ * With l2norm_qk the keys are normalised as they are read, so k_scale cancels in exact arithmetic: any positive value that keeps K's codes
+ * in range serves.  Without it k_scale is folded into the float32 logit multiplier and the codes enter the S product exactly.  v_scale
+ * multiplies each output row once, in float32 (amax / 448 per K/V head is the usual choice).  The scales are trusted device data: they
+ * must be finite and > 0.
+ * Launches: "kv_append_fp8" (when new_len > 0), "decode_fp8" and "decode_combine_fp8".  window NULL: no window. */
+#define FCSA_CACHE_E4M3 1             /* fcsa_kvcache_quant.cache_dtype: OCP e4m3fn */
+typedef struct fcsa_kvcache_quant {
+  int32_t      cache_dtype;           /* FCSA_CACHE_E4M3 (anything else: FCSA_ERR_UNSUPPORTED) */
+  const float* k_scale;               /* device float32: element [b * k_scale_stride0 + kvh * k_scale_stride1] */
+  const float* v_scale;               /* device float32, likewise */
+  int64_t      k_scale_stride0, k_scale_stride1;   /* element strides of batch and K/V head; 0 broadcasts: (0, 0) a scalar, (0, 1) [Hk], */
+  int64_t      v_scale_stride0, v_scale_stride1;   /* (Hk, 1) [B, Hk] */
+} fcsa_kvcache_quant;
+int    fcsa_forward_kvcache_quant(const fcsa_forward_args* args, const fcsa_kvcache* cache, const fcsa_kvcache_quant* quant,
+                                  const fcsa_window* window);
+/* Scratch fcsa_forward_kvcache_quant needs: that of the 16-bit call on the same problem (the split rule counts keys) */
+size_t fcsa_forward_kvcache_quant_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* cache, const fcsa_kvcache_quant* quant,
+                                                  const fcsa_window* window);
+
 /* Bytes of optional forward scratch that enable the split-key forward for this problem (0: never split). */
 size_t fcsa_forward_workspace_bytes(const fcsa_problem* p);
 
