@@ -91,7 +91,7 @@ EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fc
            "fcsa_forward_varlen", "fcsa_backward_varlen", "fcsa_backward_varlen_workspace_bytes", "fcsa_forward_kvcache",
            "fcsa_forward_kvcache_workspace_bytes", "fcsa_forward_window", "fcsa_backward_window", "fcsa_backward_window_workspace_bytes",
            "fcsa_forward_kvcache_window", "fcsa_forward_kvcache_window_workspace_bytes", "fcsa_forward_kvcache_quant",
-           "fcsa_forward_kvcache_quant_workspace_bytes")
+           "fcsa_forward_kvcache_quant_workspace_bytes", "fcsa_forward_kvcache_varlen", "fcsa_forward_kvcache_varlen_workspace_bytes")
 
 _lib = None
 
@@ -170,6 +170,13 @@ def load():
         lib.fcsa_forward_kvcache_quant_workspace_bytes.argtypes = [C.POINTER(Problem), C.POINTER(KvCache), C.POINTER(KvCacheQuant),
                                                                    C.POINTER(Window)]
         lib.fcsa_forward_kvcache_quant_workspace_bytes.restype = C.c_size_t
+    if hasattr(lib, "fcsa_forward_kvcache_varlen"):      # (likewise: an FCSA_LIB build from before the ragged decode step)
+        lib.fcsa_forward_kvcache_varlen.argtypes = [C.POINTER(ForwardArgs), C.POINTER(KvCache), C.POINTER(Varlen), C.POINTER(KvCacheQuant),
+                                                    C.POINTER(Window)]
+        lib.fcsa_forward_kvcache_varlen.restype = C.c_int
+        lib.fcsa_forward_kvcache_varlen_workspace_bytes.argtypes = [C.POINTER(Problem), C.POINTER(KvCache), C.POINTER(Varlen),
+                                                                    C.POINTER(KvCacheQuant), C.POINTER(Window)]
+        lib.fcsa_forward_kvcache_varlen_workspace_bytes.restype = C.c_size_t
     lib.fcsa_last_error.argtypes = []
     lib.fcsa_last_error.restype = C.c_char_p
     ver = lib.fcsa_debug(None, 0)

@@ -119,6 +119,11 @@ def _register_fakes():
           window_left, window_right):
         return q.new_empty(q.shape)
 
+    @torch.library.register_fake("fcsa::kvcache_varlen_forward")
+    def _(q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, k_scale, v_scale, max_seqlen_q, max_seqlen_k, scale,
+          causal, l2norm_qk, groups, window_left, window_right):
+        return q.new_empty(q.shape)
+
     @torch.library.register_fake("fcsa::backward")
     def _(d_out, o, inv_l, q, k, v, mask, attn_bias, qn, kn, rq, rk, attn_bias_batch_dim, scale, causal, l2norm_qk, groups,
           need_bias_grad):

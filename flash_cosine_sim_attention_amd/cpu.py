@@ -239,3 +239,25 @@ def attention_forward_kvcache_cpu(q, k_cache, v_cache, k_new, v_new, seqlens, bl
         out[b:b + 1] = attention_forward_cpu(qb, kb, vb, scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk,
                                              window_size=window_size)
     return out
+
+
+def attention_forward_kvcache_varlen_cpu(q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, seqlens, block_table=None, scale=8.0, groups=1,
+                                         causal=False, l2norm_qk=True, window_size=(-1, -1), k_scale=None, v_scale=None):
+    """Forward-only path of `flash_cosine_sim_attention_varlen_with_kvcache` on host tensors: packed q [total_q, H, D] and k_new / v_new
+    [total_q, Hk, D] with a validated host table; sequence b's N_b rows run through `attention_forward_kvcache_cpu` as a batch-1 call on
+    its own cache (a view: the append lands in the caller's caches), so its rows and its cache slots are exactly what the equal-N path
+    gives for that sequence alone.  seqlens: host ints, tokens cached before the append."""
+    out = torch.zeros_like(q)
+    cq = cu_seqlens_q.tolist()
+    for b in range(len(cq) - 1):
+        lo, hi = cq[b], cq[b + 1]
+        if hi == lo:
+            continue
+        rows = lambda t: None if t is None else t[lo:hi].permute(1, 0, 2).unsqueeze(0)      # [1, heads, N_b, D]
+        paged = block_table is not None
+        kc, vc = (k_cache, v_cache) if paged else (k_cache[b:b + 1], v_cache[b:b + 1])
+        quant = {} if k_scale is None else dict(k_scale=k_scale[b:b + 1], v_scale=v_scale[b:b + 1])
+        o = attention_forward_kvcache_cpu(rows(q), kc, vc, rows(k_new), rows(v_new), [seqlens[b]], block_table[b:b + 1] if paged else None,
+                                          scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, window_size=window_size, **quant)
+        out[lo:hi] = o[0].permute(1, 0, 2)
+    return out

@@ -329,7 +329,8 @@ int fcsa_debug(char* buf, size_t buf_bytes) {
              "kernels=l2norm,l2norm_pair,fwd(32 rows/wave; lean two-wave form at D=96/128),fwd2(64 rows/wave),fwd3(D=128: 64 rows/wave, 1 wave/SIMD),fwd_ksplit(128 rows, wave halves split the keys),fwd_split+combine,"
              "fwd_dyn(per-row shift),bwd_dq(+split-key; key-split form on 8 waves),bwd_dkv(+lean; query-split form on 8 waves; grouped-query K/V head sweep),bwd_dbias,finalize,kv_append+decode+decode_combine(kv cache),"
              "window(fwd_win,bwd_dq_win,bwd_dkv_win,decode_win: sliding-window forms),"
-             "kv_append_fp8+decode_fp8+decode_combine_fp8(e4m3fn kv cache, f16/bf16 queries) kv_heads=divisors of heads",
+             "kv_append_fp8+decode_fp8+decode_combine_fp8(e4m3fn kv cache, f16/bf16 queries),"
+             "kv_append_ragged+decode_ragged+decode_combine_ragged(+_fp8: packed queries with per-sequence counts against the kv cache) kv_heads=divisors of heads",
              FCSA_ABI_VERSION);
   }
   return FCSA_ABI_VERSION;
@@ -598,6 +599,126 @@ static int forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv, c
   if (!rows) return FCSA_OK;
   if (int rc = timed("decode", "decode", s, [&] { return fcsa::launch_decode(p.dtype, p.dim_head, dp, s); })) return rc;
   return timed("decode_combine", "decode combine", s, [&] { return fcsa::launch_decode_combine(p.dtype, p.dim_head, dp, s); });
+}
+
+// ---- ragged decode steps (fcsa_forward_kvcache_varlen): packed queries with per-sequence counts against the cache --------------------
+// The plan: fcsa::ragged_slots flat row-tile slots per K/V head (sized from total_q, never from batch x max_seqlen_q) and the split count
+// of fcsa::decode_splits over them -- a pure function of the shapes and the CU count, never of device table contents.
+struct RaggedPlan { int64_t slots; int splits; size_t ws_ml, total; };
+static RaggedPlan ragged_plan(const fcsa_problem& p, const fcsa_kvcache& kv, int64_t total_q, int win_lo) {
+  RaggedPlan d;
+  const int G = p.kv_heads > 0 ? p.heads / p.kv_heads : 0;
+  total_q = std::max<int64_t>(total_q, 0);
+  d.slots = fcsa::ragged_slots(total_q, std::max(p.batch, 0), G);
+  int max_k = std::min(std::max(p.k_len, 0), std::max(kv.capacity, 0));
+  max_k = fcsa::win_decode_keys(max_k, std::max(p.q_len, 0), win_lo);      // all a sequence reads under a window (open: max_k itself)
+  d.splits = fcsa::decode_splits(1, p.kv_heads, (int)std::min<int64_t>(d.slots, INT32_MAX), max_k, p.dim_head, fcsa::cu_count());
+  const size_t rows = (size_t)total_q * std::max(p.heads, 0);
+  d.ws_ml = align256(rows * d.splits * std::max(p.dim_head, 0) * 4);
+  d.total = rows == 0 ? 0 : d.ws_ml + align256(rows * d.splits * 8);
+  return d;
+}
+// the kernels' window sides: no collapsing onto the un-windowed call (every sequence has its own N_b and L_b; the one entry point serves
+// open sides as well)
+static void ragged_window_sides(const fcsa_problem& p, const fcsa_window* w, int& lo, int& hi) {
+  lo = w == nullptr || w->left < 0 ? fcsa::kWinOpen : std::min(w->left, fcsa::kWinOpen);
+  hi = p.causal ? 0 : (w == nullptr || w->right < 0 ? fcsa::kWinOpen : std::min(w->right, fcsa::kWinOpen));
+}
+static int check_kvcache_varlen(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_kvcache_quant* qz,
+                                const fcsa_window* w) {
+  if (a == nullptr || kv == nullptr || seqs == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_varlen: null argument");
+  if (seqs->total_q < 0 || seqs->total_q > INT32_MAX) return fail(FCSA_ERR_INVALID_ARG, "kvcache_varlen: total_q (%lld) outside [0, 2^31)", (long long)seqs->total_q);
+  if (a->p.batch > 0 && seqs->cu_seqlens_q == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_varlen: null cu_seqlens_q");
+  if (kv->new_len != 0 && kv->new_len != 1) return fail(FCSA_ERR_INVALID_ARG, "kvcache_varlen: new_len (%d) is a flag here: 0 (no append) or 1 (every query row brings its key and value)", kv->new_len);
+  if (w != nullptr)
+    if (int rc = check_window(w, false, false)) return rc;
+  // the equal-N checks, on the problem of the packed rows (q_len = total_q: which tensors must be there) with packed views
+  fcsa_forward_args pa = *a;
+  fcsa_kvcache pk = *kv;
+  pa.q = packed(pa.q); pa.o = packed(pa.o);
+  pk.k_new = packed(pk.k_new); pk.v_new = packed(pk.v_new);
+  pa.p.q_len = (int32_t)seqs->total_q;
+  pa.p.batch = std::min(a->p.batch, 1);
+  pk.new_len = kv->new_len != 0 && seqs->total_q > 0 ? 1 : 0;
+  if (a->p.q_len < 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_varlen: negative max_seqlen_q (%d)", a->p.q_len);
+  if ((int64_t)std::max(a->p.heads, 0) * seqs->total_q > INT32_MAX) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_varlen: heads x packed rows above 2^31");
+  if (int rc = qz != nullptr ? check_quant(&pa, &pk, qz) : check_kvcache(&pa, &pk)) return rc;
+  int lo, hi;
+  ragged_window_sides(a->p, w, lo, hi);
+  const RaggedPlan d = ragged_plan(a->p, *kv, seqs->total_q, lo);
+  if (d.slots * std::max(a->p.kv_heads, 1) * d.splits > INT32_MAX) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_varlen: grid above 2^31 workgroups");
+  return FCSA_OK;
+}
+
+size_t fcsa_forward_kvcache_varlen_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv, const fcsa_varlen* seqs,
+                                                   const fcsa_kvcache_quant* qz, const fcsa_window* w) {
+  (void)qz;      // (the split rule counts keys: an fp8 cache needs what the 16-bit call needs)
+  if (p == nullptr || kv == nullptr || seqs == nullptr) return 0;
+  int lo, hi;
+  ragged_window_sides(*p, w, lo, hi);
+  return ragged_plan(*p, *kv, seqs->total_q, lo).total;
+}
+
+int fcsa_forward_kvcache_varlen(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_kvcache_quant* qz,
+                                const fcsa_window* w) {
+  if (int rc = check_kvcache_varlen(a, kv, seqs, qz, w)) return rc;
+  const fcsa_problem& p = a->p;
+  if (p.batch == 0 || seqs->total_q == 0) return FCSA_OK;      // no sequence, or no packed row: nothing to append, nothing to write
+  const int es = elem_size(p.dtype);
+  hipStream_t s = static_cast<hipStream_t>(a->stream);
+  fcsa::DecodeRaggedParams dp;
+  ragged_window_sides(p, w, dp.win_lo, dp.win_hi);
+  dp.window = 1;
+  const RaggedPlan d = ragged_plan(p, *kv, seqs->total_q, dp.win_lo);
+  const bool rows = p.heads > 0;
+  if (rows) {
+    if (a->workspace == nullptr || a->workspace_bytes < d.total)
+      return fail(FCSA_ERR_WORKSPACE, "kvcache_varlen: workspace too small: %zu < %zu bytes", a->workspace_bytes, d.total);
+    if ((reinterpret_cast<uintptr_t>(a->workspace) & 255) != 0) return fail(FCSA_ERR_WORKSPACE, "kvcache_varlen: workspace not 256-byte aligned");
+  }
+  const bool fp8 = qz != nullptr;
+  const int ces = fp8 ? 1 : es;
+  dp.q = view(packed(a->q), es);
+  dp.o = view(packed(a->o), es);
+  dp.kc = view(kv->k_cache, ces);
+  dp.vc = view(kv->v_cache, ces);
+  dp.kn = view(packed(kv->k_new), es);
+  dp.vn = view(packed(kv->v_new), es);
+  dp.seqlens = kv->cache_seqlens;
+  dp.table = kv->block_table;
+  dp.table_stride = kv->block_table_stride;
+  dp.capacity = kv->capacity;
+  dp.page = kv->block_table != nullptr ? kv->page_size : 0;
+  dp.num_blocks = kv->num_blocks;
+  dp.new_len = 0;
+  dp.B = p.batch; dp.H = p.heads; dp.Hk = p.kv_heads; dp.G = p.heads / p.kv_heads; dp.N = 0;
+  dp.row_tiles = 0; dp.splits = d.splits;
+  dp.causal = p.causal; dp.l2norm = p.l2norm_qk; dp.groups = p.l2norm_qk ? p.groups : 1;
+  dp.c1 = p.scale * kLog2e;
+  dp.c2 = exponent_shift(p, false) * kLog2e;
+  dp.l_eps = rowsum_eps(p, false);
+  dp.dyn = dynamic_shift(p, false) ? 1 : 0;
+  dp.ws_o = static_cast<float*>(a->workspace);
+  dp.ws_ml = reinterpret_cast<float*>(static_cast<char*>(a->workspace) + d.ws_ml);
+  dp.cu_q = seqs->cu_seqlens_q;
+  dp.total_q = (int)seqs->total_q;
+  dp.slots = (int)d.slots;
+  dp.append = kv->new_len != 0 ? 1 : 0;
+  if (fp8) {
+    dp.k_scale = qz->k_scale; dp.v_scale = qz->v_scale;
+    dp.ks_b = qz->k_scale_stride0; dp.ks_h = qz->k_scale_stride1;
+    dp.vs_b = qz->v_scale_stride0; dp.vs_h = qz->v_scale_stride1;
+  }
+  // 1. the append (before anything reads the cache: same stream), 2. the split partials, 3. their combine
+  if (dp.append && kv->capacity > 0) {
+    if (int rc = timed(fp8 ? "kv_append_ragged_fp8" : "kv_append_ragged", "kv append (ragged)", s,
+                       [&] { return fcsa::launch_kv_append_ragged(p.dtype, p.dim_head, fp8, dp, s); })) return rc;
+  }
+  if (!rows) return FCSA_OK;
+  if (int rc = timed(fp8 ? "decode_ragged_fp8" : "decode_ragged", "decode (ragged)", s,
+                     [&] { return fcsa::launch_decode_ragged(p.dtype, p.dim_head, fp8, dp, s); })) return rc;
+  return timed(fp8 ? "decode_combine_ragged_fp8" : "decode_combine_ragged", "decode combine (ragged)", s,
+               [&] { return fcsa::launch_decode_combine_ragged(p.dtype, p.dim_head, fp8, dp, s); });
 }
 }  // extern "C"
 

@@ -8,6 +8,8 @@
 //                         wave-private LDS block for the transposed reads of O^T = V^T P~^T.  Partials (P~V, row max, row sum) in f32.
 //   decode_combine_kernel reconciles the splits of every row (a per-split row max in the per-row-shift regime, a common shift
 //                         otherwise) and normalises.
+// A ragged step (fcsa_forward_kvcache_varlen: packed queries, per-sequence counts) has entry points of its own as well --
+// kv_append_ragged_kernel, decode_ragged[_fp8]_kernel (decode_body with RAGGED), decode_combine_ragged_kernel.
 // An fp8 cache (fcsa_forward_kvcache_quant: one-byte OCP e4m3fn codes and a float32 scale per (batch, K/V head)) has entry points of its
 // own -- kv_append_fp8_kernel, decode_fp8_kernel (decode_body with FP8), decode_combine_fp8_kernel -- so the kernels above are what
 // they were.  A lane reads 8 key bytes per fragment (the same features as its 16-bit fragment) and converts them with v_cvt_pk_f32_fp8;
@@ -252,9 +254,14 @@ template <typename T, int D, bool FP8 = false> struct DecodeRegs {
 // FP8 (decode_fp8_kernel): an e4m3fn cache.  K: with l2norm the codes are scaled by k_scale, normalised and rounded as 16-bit keys are;
 // without it the exact codes are the operands and k_scale joins the float32 logit multiplier.  V: converted to T on the way into LDS
 // (exact); v_scale is applied by the combine.
-template <typename T, int D, bool DYN, bool GEN, bool WIN, bool FP8 = false>
-FCSA_DEV void decode_body(const std::conditional_t<FP8, DecodeFp8Params, std::conditional_t<WIN, DecodeWinParams, DecodeParams>>& p) {
+// RAGGED (decode_ragged_kernel, decode_ragged_fp8_kernel): a ragged step -- packed queries, sequence b with its own N_b rows.  The
+// workgroup is a (row-tile slot, K/V head, split); it finds its sequence and row tile in the table (ragged_tile: idle slots exit at once)
+// and from there on runs the code below with N = N_b.  Always WIN, with open sides when the call has no window.
+template <typename T, int D, bool DYN, bool GEN, bool WIN, bool FP8 = false, bool RAGGED = false>
+FCSA_DEV void decode_body(const std::conditional_t<RAGGED, DecodeRaggedParams,
+                                                   std::conditional_t<FP8, DecodeFp8Params, std::conditional_t<WIN, DecodeWinParams, DecodeParams>>>& p) {
   static_assert(!FP8 || Traits<T>::ES == 2, "an fp8 cache is read with 16-bit queries");
+  static_assert(!RAGGED || WIN, "the ragged entry points carry the window fields");
   typedef DecodeRegs<T, D, FP8> R;
   typedef DecodeLds<D, R::ES, GEN> LP;
   constexpr int ES = R::ES, UE = R::UE, NJ = R::NJ, CPR = R::CPR, VCH = R::VCH;
@@ -268,13 +275,22 @@ FCSA_DEV void decode_body(const std::conditional_t<FP8, DecodeFp8Params, std::co
   int id = blockIdx.x;
   const int split = id % p.splits;
   id /= p.splits;
-  const int rt = id % p.row_tiles;
-  id /= p.row_tiles;
-  const int kvh = id % p.Hk, b = id / p.Hk;
-  const int L = decode_len(p.seqlens != nullptr, p.seqlens != nullptr ? p.seqlens[b] : 0, p.new_len, p.capacity);
+  int rt, kvh, b, N, q0 = 0, new_len;     // q0: the sequence's first packed row (RAGGED)
+  if constexpr (RAGGED) {
+    kvh = id % p.Hk;
+    if (!ragged_tile(p.cu_q, p.B, p.total_q, p.G, id / p.Hk, b, rt, q0, N)) return;
+    new_len = p.append ? N : 0;
+  } else {
+    rt = id % p.row_tiles;
+    id /= p.row_tiles;
+    kvh = id % p.Hk, b = id / p.Hk;
+    N = p.N;
+    new_len = p.new_len;
+  }
+  const int L = decode_len(p.seqlens != nullptr, p.seqlens != nullptr ? p.seqlens[b] : 0, new_len, p.capacity);
   int lo, n;
   if constexpr (WIN) {
-    const int first = win_decode_first(L, p.N, p.win_lo);
+    const int first = win_decode_first(L, N, p.win_lo);
     decode_window(L - first, split, p.splits, lo, n);
     lo += first;
   } else {
@@ -284,10 +300,10 @@ FCSA_DEV void decode_body(const std::conditional_t<FP8, DecodeFp8Params, std::co
 
   // this lane's query row: the column of every MFMA result
   const int r = rt * kDecodeRows + x;
-  const bool row_ok = r < p.G * p.N;
-  const int g = row_ok ? r / p.N : 0, qi = row_ok ? r % p.N : 0;
+  const bool row_ok = r < p.G * N;
+  const int g = row_ok ? r / N : 0, qi = row_ok ? r % N : 0;
   const int h = kvh * p.G + g;
-  const int last_key = L - p.N + qi;               // causal: key j is visible iff j <= last_key
+  const int last_key = L - N + qi;               // causal: key j is visible iff j <= last_key
   const int gs = D / p.groups;
   float* norm_scratch = reinterpret_cast<float*>(smem + LP::VBYTES);
   auto normalise = [&](float (&xr)[NJ][UE]) {
@@ -298,7 +314,7 @@ FCSA_DEV void decode_body(const std::conditional_t<FP8, DecodeFp8Params, std::co
   u32x4 qf[NJ];
   {
     float xq[NJ][UE];
-    const char* qrow = p.q.p + (int64_t)b * p.q.sb + (int64_t)h * p.q.sh + (int64_t)qi * p.q.sn;
+    const char* qrow = p.q.p + (RAGGED ? 0 : (int64_t)b * p.q.sb) + (int64_t)h * p.q.sh + (int64_t)(q0 + qi) * p.q.sn;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       const int f = (4 * j + hi) * UE;
@@ -447,8 +463,15 @@ FCSA_DEV void decode_body(const std::conditional_t<FP8, DecodeFp8Params, std::co
   l += __shfl_xor(l, 16, 64);
   l += __shfl_xor(l, 32, 64);
   if (row_ok) {
-    const int64_t rows = (int64_t)p.B * p.H * p.N;
-    const int64_t row = ((int64_t)b * p.H + h) * p.N + qi;
+    // partial rows: [B, H, N]; RAGGED: [total_q, H]
+    int64_t rows, row;
+    if constexpr (RAGGED) {
+      rows = (int64_t)p.total_q * p.H;
+      row = (int64_t)(q0 + qi) * p.H + h;
+    } else {
+      rows = (int64_t)p.B * p.H * N;
+      row = ((int64_t)b * p.H + h) * N + qi;
+    }
     float* wo = p.ws_o + ((int64_t)split * rows + row) * D;
 #pragma unroll
     for (int fb = 0; fb < FB; ++fb) *reinterpret_cast<f32x4*>(wo + 16 * fb + 4 * hi) = acc[fb];
@@ -470,6 +493,16 @@ __global__ __launch_bounds__(64) void decode_win_kernel(DecodeWinParams p) {
 template <typename T, int D, bool DYN, bool GEN, bool WIN>
 __global__ __launch_bounds__(64) void decode_fp8_kernel(DecodeFp8Params p) {
   decode_body<T, D, DYN, GEN, WIN, true>(p);
+}
+
+// the ragged step (launch_decode_ragged): one entry point per cache type, with or without a window
+template <typename T, int D, bool DYN, bool GEN>
+__global__ __launch_bounds__(64) void decode_ragged_kernel(DecodeRaggedParams p) {
+  decode_body<T, D, DYN, GEN, true, false, true>(p);
+}
+template <typename T, int D, bool DYN, bool GEN>
+__global__ __launch_bounds__(64) void decode_ragged_fp8_kernel(DecodeRaggedParams p) {
+  decode_body<T, D, DYN, GEN, true, true, true>(p);
 }
 
 // o = sum_s 2^(m_s - M) P~V_s / sum_s 2^(m_s - M) l_s over the splits of a row (static regime: every m_s is the common shift, weight 1)
@@ -618,6 +651,86 @@ __global__ __launch_bounds__(256) void kv_append_fp8_kernel(DecodeFp8Params p) {
   *reinterpret_cast<u32x4*>(p.vc.p + vdst + ch * 16) = quantise16<T>(vs[0], vs[1], p.v_scale[(int64_t)b * p.vs_b + (int64_t)kvh * p.vs_h]);
 }
 
+// decode_combine_kernel / decode_combine_fp8_kernel for a ragged step: partial row (tok, h) of the [total_q, H] rows goes to packed row
+// `tok` of o; an fp8 cache's v_scale is that of the sequence owning the row (ragged_seq_of)
+template <typename T, int D, bool FP8>
+__global__ __launch_bounds__(256) void decode_combine_ragged_kernel(DecodeRaggedParams p) {
+  constexpr int ES = Traits<T>::ES;
+  constexpr int TPR = D / 4;
+  const int64_t rows = (int64_t)p.total_q * p.H;
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t row = t / TPR;
+  const int c = (int)(t % TPR);
+  if (row >= rows) return;
+  float M = -INFINITY;
+  for (int s = 0; s < p.splits; ++s) M = fmaxf(M, p.ws_ml[(s * rows + row) * 2]);
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  float l = 0.f;
+  if (M != -INFINITY) {
+    for (int s = 0; s < p.splits; ++s) {
+      const f32x2 ml = *reinterpret_cast<const f32x2*>(p.ws_ml + (s * rows + row) * 2);
+      const float w = exp2f(ml[0] - M);
+      l += w * ml[1];
+      acc += w * *reinterpret_cast<const f32x4*>(p.ws_o + (s * rows + row) * D + 4 * c);
+    }
+  }
+  const int64_t tok = row / p.H;
+  const int h = (int)(row % p.H);
+  const float inv = p.dyn ? (l > 0.f ? 1.f / l : 0.f) : 1.f / fmaxf(l, p.l_eps);
+  if constexpr (FP8) {
+    const int b = ragged_seq_of(p.cu_q, p.B, p.total_q, tok);
+    acc *= inv * p.v_scale[(int64_t)b * p.vs_b + (int64_t)(h / p.G) * p.vs_h];
+  } else {
+    acc *= inv;
+  }
+  char* dst = p.o.p + (int64_t)h * p.o.sh + tok * p.o.sn + 4 * c * ES;
+  if constexpr (ES == 4) {
+    *reinterpret_cast<f32x4*>(dst) = acc;
+  } else {
+    *reinterpret_cast<u32x2*>(dst) = u32x2{Traits<T>::pack2(acc[0], acc[1]), Traits<T>::pack2(acc[2], acc[3])};
+  }
+}
+
+// kv_append_kernel / kv_append_fp8_kernel for a ragged step: one thread per 16 bytes written of packed row `tok` of kn / vn ([total_q, Hk,
+// D]); the thread finds the row's sequence in the table and writes slot cache_seqlens[b] + (tok - cu_q[b])
+template <typename T, int D, bool FP8>
+__global__ __launch_bounds__(256) void kv_append_ragged_kernel(DecodeRaggedParams p) {
+  constexpr int CPR = FP8 ? D / 16 : D * Traits<T>::ES / 16;
+  const int64_t total = (int64_t)p.total_q * p.Hk * CPR;
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= total) return;
+  const int ch = (int)(t % CPR);
+  const int64_t rest = t / CPR;
+  const int kvh = (int)(rest % p.Hk);
+  const int64_t tok = rest / p.Hk;
+  const int b = ragged_seq_of(p.cu_q, p.B, p.total_q, tok);
+  const int64_t q0 = ragged_cu(p.cu_q[b], p.total_q), q1 = ragged_cu(p.cu_q[b + 1], p.total_q);
+  if (tok < q0 || tok >= q1) return;          // (a malformed table: the row belongs to no sequence)
+  const int64_t start = p.seqlens != nullptr ? min(max((int64_t)p.seqlens[b], (int64_t)0), (int64_t)p.capacity) : (int64_t)p.capacity;
+  const int64_t pos = start + (tok - q0);
+  if (pos >= p.capacity) return;
+  int64_t kdst, vdst;
+  if (p.table != nullptr) {
+    int blk = p.table[(int64_t)b * p.table_stride + pos / p.page];
+    blk = min(max(blk, 0), p.num_blocks - 1);
+    kdst = (int64_t)blk * p.kc.sb + (int64_t)kvh * p.kc.sh + (pos % p.page) * p.kc.sn;
+    vdst = (int64_t)blk * p.vc.sb + (int64_t)kvh * p.vc.sh + (pos % p.page) * p.vc.sn;
+  } else {
+    kdst = (int64_t)b * p.kc.sb + (int64_t)kvh * p.kc.sh + pos * p.kc.sn;
+    vdst = (int64_t)b * p.vc.sb + (int64_t)kvh * p.vc.sh + pos * p.vc.sn;
+  }
+  const int64_t ksrc = (int64_t)kvh * p.kn.sh + tok * p.kn.sn, vsrc = (int64_t)kvh * p.vn.sh + tok * p.vn.sn;
+  if constexpr (FP8) {
+    const u32x4* ks = reinterpret_cast<const u32x4*>(p.kn.p + ksrc + ch * 32);
+    const u32x4* vs = reinterpret_cast<const u32x4*>(p.vn.p + vsrc + ch * 32);
+    *reinterpret_cast<u32x4*>(p.kc.p + kdst + ch * 16) = quantise16<T>(ks[0], ks[1], p.k_scale[(int64_t)b * p.ks_b + (int64_t)kvh * p.ks_h]);
+    *reinterpret_cast<u32x4*>(p.vc.p + vdst + ch * 16) = quantise16<T>(vs[0], vs[1], p.v_scale[(int64_t)b * p.vs_b + (int64_t)kvh * p.vs_h]);
+  } else {
+    *reinterpret_cast<u32x4*>(p.kc.p + kdst + ch * 16) = *reinterpret_cast<const u32x4*>(p.kn.p + ksrc + ch * 16);
+    *reinterpret_cast<u32x4*>(p.vc.p + vdst + ch * 16) = *reinterpret_cast<const u32x4*>(p.vn.p + vsrc + ch * 16);
+  }
+}
+
 int64_t blocks_of(int64_t threads) { return (threads + 255) / 256; }
 
 }  // namespace
@@ -710,6 +823,66 @@ hipError_t launch_decode_combine_fp8(int dtype, int D, const DecodeFp8Params& p,
     } else {
       return hipErrorInvalidValue;
     }
+  });
+}
+
+// ---- ragged steps (fcsa_forward_kvcache_varlen) ----
+hipError_t launch_kv_append_ragged(int dtype, int D, bool fp8, const DecodeRaggedParams& p, hipStream_t s) {
+  if (fp8 && dtype != 1 && dtype != 2) return hipErrorInvalidValue;
+  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    const int64_t threads = (int64_t)p.total_q * p.Hk * (fp8 ? DD / 16 : DD * Traits<T>::ES / 16);
+    if (threads <= 0 || p.B <= 0) return hipSuccess;
+    if (fp8) {
+      if constexpr (Traits<T>::ES == 2) hipLaunchKernelGGL((kv_append_ragged_kernel<T, DD, true>), dim3((unsigned)blocks_of(threads)), dim3(256), 0, s, p);
+      else return hipErrorInvalidValue;
+    } else {
+      hipLaunchKernelGGL((kv_append_ragged_kernel<T, DD, false>), dim3((unsigned)blocks_of(threads)), dim3(256), 0, s, p);
+    }
+    return hipGetLastError();
+  });
+}
+
+hipError_t launch_decode_ragged(int dtype, int D, bool fp8, const DecodeRaggedParams& p, hipStream_t s) {
+  if (fp8 && dtype != 1 && dtype != 2) return hipErrorInvalidValue;
+  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    constexpr int ES = Traits<T>::ES;
+    const dim3 grid((unsigned)((int64_t)p.slots * p.Hk * p.splits));
+    auto go = [&](auto dyn, auto gen) -> hipError_t {
+      constexpr bool DY = decltype(dyn)::value, GN = decltype(gen)::value;
+      if (fp8) {
+        if constexpr (ES == 2) return launch_with_lds<decode_ragged_fp8_kernel<T, DD, DY, GN>>(grid, dim3(64), DecodeLds<DD, ES, GN>::BYTES, s, p);
+        else return hipErrorInvalidValue;
+      }
+      return launch_with_lds<decode_ragged_kernel<T, DD, DY, GN>>(grid, dim3(64), DecodeLds<DD, ES, GN>::BYTES, s, p);
+    };
+    using Y = std::true_type;
+    using N = std::false_type;
+    if (p.l2norm && !decode_groups_fast(DD, p.groups, Unit<T>::UE)) {
+      if constexpr (DD == 96) return p.dyn ? go(Y{}, Y{}) : go(N{}, Y{});
+      else return hipErrorInvalidValue;
+    }
+    return p.dyn ? go(Y{}, N{}) : go(N{}, N{});
+  });
+}
+
+hipError_t launch_decode_combine_ragged(int dtype, int D, bool fp8, const DecodeRaggedParams& p, hipStream_t s) {
+  if (fp8 && dtype != 1 && dtype != 2) return hipErrorInvalidValue;
+  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    const int64_t threads = (int64_t)p.total_q * p.H * (DD / 4);
+    if (threads <= 0) return hipSuccess;
+    if (fp8) {
+      if constexpr (Traits<T>::ES == 2) hipLaunchKernelGGL((decode_combine_ragged_kernel<T, DD, true>), dim3((unsigned)blocks_of(threads)), dim3(256), 0, s, p);
+      else return hipErrorInvalidValue;
+    } else {
+      hipLaunchKernelGGL((decode_combine_ragged_kernel<T, DD, false>), dim3((unsigned)blocks_of(threads)), dim3(256), 0, s, p);
+    }
+    return hipGetLastError();
   });
 }
 

@@ -243,6 +243,42 @@ constexpr int win_decode_keys(int max_k, int N, int lo) {
   return lo >= kWinOpen ? max_k : (int)std::min<int64_t>(max_k, (int64_t)lo + N + kDecodeBlock - 1);
 }
 
+// Ragged decode steps (fcsa_forward_kvcache_varlen): sequence b brings N_b = cu[b + 1] - cu[b] packed query rows, so a K/V head of it has
+// ceil(G * N_b / 16) row tiles.  The grid has ragged_slots(total_q, B, G) = floor(G * total_q / 16) + B flat tile slots per K/V head, and
+// sequence b's tiles sit from slot ragged_base(cu[b], b, G) = floor(G * cu[b] / 16) + b on.  Consecutive bases differ by
+// floor(G cu[b + 1] / 16) - floor(G cu[b] / 16) + 1 >= floor(G N_b / 16) + 1 >= ceil(G N_b / 16): the tiles of a sequence never reach the next
+// base, and the bases grow strictly with b, so a workgroup finds its sequence by a binary search over the table alone (no prefix sums, no
+// prologue launch); a slot between a sequence's last tile and the next base is idle (at most B of them, one per sequence).
+// Table entries are clamped into [0, total] (ragged_cu), so ANY table contents keep every row index inside the packed tensors.
+constexpr int64_t ragged_cu(int64_t raw, int64_t total) { return std::min(std::max(raw, (int64_t)0), total); }
+constexpr int64_t ragged_base(int64_t cu_b, int b, int G) { return (int64_t)G * cu_b / kDecodeRows + b; }
+constexpr int64_t ragged_slots(int64_t total_q, int64_t B, int G) { return (int64_t)G * total_q / kDecodeRows + B; }
+// The sequence that owns packed row `tok`: the last b with cu[b] <= tok (empty sequences share their start with the next one and own
+// nothing).  B >= 1.
+constexpr int ragged_seq_of(const int32_t* cu, int B, int64_t total, int64_t tok) {
+  int lo = 0, hi = B - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) / 2;
+    if (ragged_cu(cu[mid], total) <= tok) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+// Slot -> (sequence b, row tile rt of its G * len rows, first packed row `start`, rows `len`); false: the slot is idle.  B >= 1.
+constexpr bool ragged_tile(const int32_t* cu, int B, int64_t total, int G, int64_t slot, int& b, int& rt, int& start, int& len) {
+  int lo = 0, hi = B - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) / 2;
+    if (ragged_base(ragged_cu(cu[mid], total), mid, G) <= slot) lo = mid; else hi = mid - 1;
+  }
+  const int64_t st = ragged_cu(cu[lo], total), en = std::max(ragged_cu(cu[lo + 1], total), st);
+  const int64_t t = slot - ragged_base(st, lo, G);
+  b = lo;
+  start = (int)st;
+  len = (int)(en - st);
+  rt = (int)t;
+  return t >= 0 && t < ((int64_t)G * (en - st) + kDecodeRows - 1) / kDecodeRows;
+}
+
 // workgroups of `tile`-position tiles over `len` positions for `batch_heads` (batch x heads)
 inline int64_t tile_workgroups(int64_t batch_heads, int len, int tile, bool causal) {
   return batch_heads * tile_pairs(tile_count(len, tile), causal);

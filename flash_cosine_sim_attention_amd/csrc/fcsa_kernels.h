@@ -143,6 +143,17 @@ struct DecodeFp8Params : DecodeWinParams {
   const float* v_scale = nullptr;
   int64_t ks_b = 0, ks_h = 0, vs_b = 0, vs_h = 0;
 };
+// A ragged decode step (fcsa_forward_kvcache_varlen): q / o are packed [total_q, H, D] views and kn / vn packed [total_q, Hk, D] ones (sb
+// unused), sequence b owning the packed rows [cu_q[b], cu_q[b + 1]).  N, new_len and row_tiles of the base block are unused: every
+// workgroup takes its sequence's own row count from the table (fcsa::ragged_tile).  The window fields are always live: open sides
+// (kWinOpen; causal: win_hi = 0) for a call without a window, so one decode entry point per cache type serves every call.  Only the
+// ragged kernels (kv_append_ragged*_kernel, decode_ragged*_kernel, decode_combine_ragged_kernel) get this block.
+struct DecodeRaggedParams : DecodeFp8Params {
+  const int32_t* cu_q = nullptr;    // [B + 1] device
+  int total_q = 0;                  // packed rows of q, o, kn, vn
+  int slots = 0;                    // flat row-tile slots per K/V head: fcsa::ragged_slots(total_q, B, G)
+  int append = 0;                   // 1: every query row brings its key and value (L_b counts them)
+};
 hipError_t launch_kv_append(int dtype, int D, const DecodeParams& p, hipStream_t s);
 hipError_t launch_decode(int dtype, int D, const DecodeWinParams& p, hipStream_t s);
 hipError_t launch_decode_combine(int dtype, int D, const DecodeParams& p, hipStream_t s);
@@ -150,6 +161,10 @@ hipError_t launch_decode_combine(int dtype, int D, const DecodeParams& p, hipStr
 hipError_t launch_kv_append_fp8(int dtype, int D, const DecodeFp8Params& p, hipStream_t s);
 hipError_t launch_decode_fp8(int dtype, int D, const DecodeFp8Params& p, hipStream_t s);
 hipError_t launch_decode_combine_fp8(int dtype, int D, const DecodeFp8Params& p, hipStream_t s);
+// ragged steps; fp8: an e4m3fn cache (16-bit dtype only)
+hipError_t launch_kv_append_ragged(int dtype, int D, bool fp8, const DecodeRaggedParams& p, hipStream_t s);
+hipError_t launch_decode_ragged(int dtype, int D, bool fp8, const DecodeRaggedParams& p, hipStream_t s);
+hipError_t launch_decode_combine_ragged(int dtype, int D, bool fp8, const DecodeRaggedParams& p, hipStream_t s);
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE property of a kernel: raise it once per (instantiation, device).
 // `done` is the instantiation's bit mask of devices that have it (one static per launcher); thread safe, idempotent.

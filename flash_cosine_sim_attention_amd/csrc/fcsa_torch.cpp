@@ -50,6 +50,11 @@ struct Abi {
   int (*forward_kvcache_quant)(const fcsa_forward_args*, const fcsa_kvcache*, const fcsa_kvcache_quant*, const fcsa_window*) = &fcsa_forward_kvcache_quant;
   size_t (*forward_kvcache_quant_ws)(const fcsa_problem*, const fcsa_kvcache*, const fcsa_kvcache_quant*, const fcsa_window*) =
       &fcsa_forward_kvcache_quant_workspace_bytes;
+  // ragged decode steps (packed queries with per-sequence counts): likewise
+  int (*forward_kvcache_varlen)(const fcsa_forward_args*, const fcsa_kvcache*, const fcsa_varlen*, const fcsa_kvcache_quant*, const fcsa_window*) =
+      &fcsa_forward_kvcache_varlen;
+  size_t (*forward_kvcache_varlen_ws)(const fcsa_problem*, const fcsa_kvcache*, const fcsa_varlen*, const fcsa_kvcache_quant*, const fcsa_window*) =
+      &fcsa_forward_kvcache_varlen_workspace_bytes;
 } g_abi;
 
 using at::Tensor;
@@ -758,9 +763,15 @@ Tensor varlen_window_attention_autograd(const Tensor& q, const Tensor& k, const 
 // q [B, H, N, D]; k_cache / v_cache [B, Hk, capacity, D] or, with a block_table, [num_blocks, Hk, page_size, D] (any strides with the
 // feature dim contiguous: they are written in place, so they are never copied); k_new / v_new [B, Hk, N_new, D]; cache_seqlens int32 [B]
 // and block_table int32 [B, max_blocks] on q's device.  Table contents are never read on the host: the call does not synchronise.
+// cu_q (kvcache_varlen_forward): a ragged step -- q [total_q, H, D] packed by the int32 table cu_q [B + 1], k_new / v_new [total_q, Hk, D],
+// max_seqlen_q an upper bound on the rows of a sequence; o is shaped like q.
 Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const optional<Tensor>& k_new, const optional<Tensor>& v_new,
                             const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table, int64_t max_seqlen_k, double scale, bool causal,
-                            bool l2norm_qk, int64_t groups, const fcsa_window* win, const Tensor* k_scale = nullptr, const Tensor* v_scale = nullptr) {
+                            bool l2norm_qk, int64_t groups, const fcsa_window* win, const Tensor* k_scale = nullptr, const Tensor* v_scale = nullptr,
+                            const Tensor* cu_q = nullptr, int64_t max_seqlen_q = 0) {
+  const bool ragged = cu_q != nullptr;
+  TORCH_CHECK(!ragged || (g_abi.forward_kvcache_varlen != nullptr && g_abi.forward_kvcache_varlen_ws != nullptr),
+              "flash_cosine_sim_attention_varlen_with_kvcache: the loaded libfcsa_hip.so does not export fcsa_forward_kvcache_varlen");
   const bool fp8 = k_scale != nullptr;      // an e4m3fn cache with its two scale tensors (kvcache_fp8_forward)
   TORCH_CHECK(g_abi.forward_kvcache != nullptr && g_abi.forward_kvcache_ws != nullptr,
               "flash_cosine_sim_attention_with_kvcache: the loaded libfcsa_hip.so does not export fcsa_forward_kvcache");
@@ -784,9 +795,21 @@ Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor
     TORCH_CHECK_TYPE(q.scalar_type() == k_cache.scalar_type() && q.scalar_type() == v_cache.scalar_type(), "q, k_cache, v_cache must share a dtype");
   }
   dtype_code(q.scalar_type());
-  TORCH_CHECK_VALUE(q.dim() == 4 && k_cache.dim() == 4 && v_cache.dim() == 4, "q, k_cache, v_cache must have 4 dimensions");
+  TORCH_CHECK_VALUE(q.dim() == (ragged ? 3 : 4) && k_cache.dim() == 4 && v_cache.dim() == 4,
+                    ragged ? "q must be a packed [total_q, heads, dim_head] tensor and k_cache, v_cache must have 4 dimensions"
+                           : "q, k_cache, v_cache must have 4 dimensions");
   TORCH_CHECK_VALUE(k_cache.sizes() == v_cache.sizes(), "k_cache and v_cache must have the same shape");
-  const int64_t B = q.size(0), H = q.size(1), N = q.size(2), D = q.size(3), Hk = k_cache.size(1);
+  Tensor cu;
+  if (ragged) {
+    same_dev("cu_seqlens_q", *cu_q);
+    TORCH_CHECK_TYPE(cu_q->scalar_type() == at::kInt, "cu_seqlens_q must be int32");
+    TORCH_CHECK_VALUE(cu_q->dim() == 1 && cu_q->numel() >= 1, "cu_seqlens_q must be 1-D with sequences + 1 entries, got ", cu_q->sizes());
+    TORCH_CHECK_VALUE(max_seqlen_q >= 0 && max_seqlen_q <= INT32_MAX, "max_seqlen_q must lie in [0, 2^31), got ", max_seqlen_q);
+    TORCH_CHECK_VALUE(q.size(0) * std::max<int64_t>(q.size(1), 1) <= INT32_MAX, "heads x packed rows must stay below 2^31");
+    cu = cu_q->contiguous();
+  }
+  // ragged: N is the number of packed rows
+  const int64_t B = ragged ? cu.numel() - 1 : q.size(0), H = q.size(1), N = ragged ? q.size(0) : q.size(2), D = q.size(-1), Hk = k_cache.size(1);
   TORCH_CHECK_VALUE(k_cache.size(3) == D, "query, key, value dimensions must be the same");
   TORCH_CHECK_VALUE(D == 16 || D == 32 || D == 64 || D == 96 || D == 128, "only dimensions (16, 32, 64, 96, 128) allowed for now, got ", D);
   TORCH_CHECK_VALUE(Hk >= 1 && H % Hk == 0, "k/v heads must divide q heads (", H, "), got ", Hk);
@@ -817,9 +840,14 @@ Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor
     same_dev("k_new", *k_new);
     same_dev("v_new", *v_new);
     TORCH_CHECK_TYPE(k_new->scalar_type() == q.scalar_type() && v_new->scalar_type() == q.scalar_type(), "k_new / v_new must have q's dtype");
-    TORCH_CHECK_VALUE(k_new->dim() == 4 && k_new->sizes() == v_new->sizes() && k_new->size(0) == B && k_new->size(1) == Hk && k_new->size(3) == D,
-                      "k_new / v_new must be [batch, kv_heads, N_new, dim_head], got ", k_new->sizes(), " and ", v_new->sizes());
-    new_len = k_new->size(2);
+    if (ragged) {
+      TORCH_CHECK_VALUE(k_new->dim() == 3 && k_new->sizes() == v_new->sizes() && k_new->size(0) == N && k_new->size(1) == Hk && k_new->size(2) == D,
+                        "k_new / v_new must be packed [total_q, kv_heads, dim_head] like q, got ", k_new->sizes(), " and ", v_new->sizes());
+    } else {
+      TORCH_CHECK_VALUE(k_new->dim() == 4 && k_new->sizes() == v_new->sizes() && k_new->size(0) == B && k_new->size(1) == Hk && k_new->size(3) == D,
+                        "k_new / v_new must be [batch, kv_heads, N_new, dim_head], got ", k_new->sizes(), " and ", v_new->sizes());
+    }
+    new_len = ragged ? 1 : k_new->size(2);
     kn = prep(*k_new);
     vn = prep(*v_new);
   }
@@ -833,17 +861,17 @@ Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor
   TORCH_CHECK_VALUE(max_seqlen_k >= 0, "max_seqlen_k must be non-negative");
   c10::DeviceGuard guard(q.device());
   const Tensor q4 = prep(q);
-  Tensor o = at::empty({B, H, N, D}, q.options());
+  Tensor o = ragged ? at::empty({N, H, D}, q.options()) : at::empty({B, H, N, D}, q.options());
   fcsa_forward_args a;
   std::memset(&a, 0, sizeof(a));
   a.p.dtype = dtype_code(q.scalar_type());
   a.p.batch = (int32_t)B; a.p.heads = (int32_t)H; a.p.kv_heads = (int32_t)Hk;
-  a.p.q_len = (int32_t)N; a.p.k_len = (int32_t)std::min<int64_t>(max_seqlen_k, capacity); a.p.dim_head = (int32_t)D;
+  a.p.q_len = (int32_t)(ragged ? max_seqlen_q : N); a.p.k_len = (int32_t)std::min<int64_t>(max_seqlen_k, capacity); a.p.dim_head = (int32_t)D;
   a.p.causal = causal; a.p.bias_batch_dim = 0; a.p.l2norm_qk = l2norm_qk;
   a.p.groups = l2norm_qk ? (int32_t)groups : 1;
   a.p.scale = (float)scale;
-  a.q = view4(q4);
-  a.o = view4(o);
+  a.q = ragged ? packed3(q4) : view4(q4);
+  a.o = ragged ? packed3(o) : view4(o);
   kv.k_cache = view4(k_cache);
   kv.v_cache = view4(v_cache);
   kv.capacity = (int32_t)capacity;
@@ -855,8 +883,14 @@ Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor
   kv.block_table_stride = paged ? tab.size(1) : 0;
   fcsa_tensor none;
   std::memset(&none, 0, sizeof(none));
-  kv.k_new = kn.defined() && new_len > 0 ? view4(kn) : none;
-  kv.v_new = vn.defined() && new_len > 0 ? view4(vn) : none;
+  kv.k_new = kn.defined() && new_len > 0 ? (ragged ? packed3(kn) : view4(kn)) : none;
+  kv.v_new = vn.defined() && new_len > 0 ? (ragged ? packed3(vn) : view4(vn)) : none;
+  fcsa_varlen seqs;
+  std::memset(&seqs, 0, sizeof(seqs));
+  if (ragged) {
+    seqs.cu_seqlens_q = cu.data_ptr<int32_t>();
+    seqs.total_q = N;
+  }
   fcsa_kvcache_quant qz;
   std::memset(&qz, 0, sizeof(qz));
   Tensor ks, vs;
@@ -877,7 +911,8 @@ Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor
     qz.k_scale = ks.data_ptr<float>();
     qz.v_scale = vs.data_ptr<float>();
   }
-  const size_t wsb = fp8 ? g_abi.forward_kvcache_quant_ws(&a.p, &kv, &qz, win)
+  const size_t wsb = ragged ? g_abi.forward_kvcache_varlen_ws(&a.p, &kv, &seqs, fp8 ? &qz : nullptr, win)
+                     : fp8 ? g_abi.forward_kvcache_quant_ws(&a.p, &kv, &qz, win)
                          : win != nullptr ? g_abi.forward_kvcache_window_ws(&a.p, &kv, win) : g_abi.forward_kvcache_ws(&a.p, &kv);
   Tensor ws;
   if (wsb > 0) {
@@ -886,7 +921,8 @@ Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor
     a.workspace_bytes = wsb;
   }
   a.stream = stream_of(q);
-  if (fp8) check(g_abi.forward_kvcache_quant(&a, &kv, &qz, win), "fcsa_forward_kvcache_quant");
+  if (ragged) check(g_abi.forward_kvcache_varlen(&a, &kv, &seqs, fp8 ? &qz : nullptr, win), "fcsa_forward_kvcache_varlen");
+  else if (fp8) check(g_abi.forward_kvcache_quant(&a, &kv, &qz, win), "fcsa_forward_kvcache_quant");
   else if (win != nullptr) check(g_abi.forward_kvcache_window(&a, &kv, win), "fcsa_forward_kvcache_window");
   else check(g_abi.forward_kvcache(&a, &kv), "fcsa_forward_kvcache");
   return o;
@@ -910,6 +946,19 @@ Tensor kvcache_fp8_forward(const Tensor& q, const Tensor& k_cache, const Tensor&
   const Win win(left, right);
   return kvcache_forward_impl(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups,
                               left == -1 && right == -1 ? nullptr : &win.w, &k_scale, &v_scale);
+}
+
+// a ragged step: packed q [total_q, H, D] with cu_seqlens_q [B + 1]; k_scale / v_scale given: an e4m3fn cache (its codes as uint8 tensors);
+// window sides of (-1, -1): no window
+Tensor kvcache_varlen_forward(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& cu_seqlens_q, const optional<Tensor>& k_new,
+                              const optional<Tensor>& v_new, const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table,
+                              const optional<Tensor>& k_scale, const optional<Tensor>& v_scale, int64_t max_seqlen_q, int64_t max_seqlen_k, double scale,
+                              bool causal, bool l2norm_qk, int64_t groups, int64_t left, int64_t right) {
+  TORCH_CHECK_VALUE(k_scale.has_value() == v_scale.has_value(), "k_scale and v_scale must be given together");
+  const Win win(left, right);
+  return kvcache_forward_impl(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups,
+                              left == -1 && right == -1 ? nullptr : &win.w, k_scale.has_value() ? &*k_scale : nullptr,
+                              v_scale.has_value() ? &*v_scale : nullptr, &cu_seqlens_q, max_seqlen_q);
 }
 
 }  // namespace
@@ -943,6 +992,8 @@ extern "C" int fcsa_torch_use_library(const char* path) {
   a.forward_kvcache_window_ws = reinterpret_cast<decltype(a.forward_kvcache_window_ws)>(dlsym(h, "fcsa_forward_kvcache_window_workspace_bytes"));
   a.forward_kvcache_quant = reinterpret_cast<decltype(a.forward_kvcache_quant)>(dlsym(h, "fcsa_forward_kvcache_quant"));
   a.forward_kvcache_quant_ws = reinterpret_cast<decltype(a.forward_kvcache_quant_ws)>(dlsym(h, "fcsa_forward_kvcache_quant_workspace_bytes"));
+  a.forward_kvcache_varlen = reinterpret_cast<decltype(a.forward_kvcache_varlen)>(dlsym(h, "fcsa_forward_kvcache_varlen"));
+  a.forward_kvcache_varlen_ws = reinterpret_cast<decltype(a.forward_kvcache_varlen_ws)>(dlsym(h, "fcsa_forward_kvcache_varlen_workspace_bytes"));
   if (!a.forward || !a.backward || !a.forward_ws || !a.backward_ws || !a.needs_qn || !a.last_error) { dlclose(h); return -2; }
   // Only libraries of THIS ABI: the binding allocates for the struct layouts and buffer contracts of include/fcsa.h as compiled in
   // (e.g. ABI 3 writes d_bias once in the bias dtype into an uninitialised buffer; an ABI-2 library would accumulate float32 into
@@ -994,6 +1045,10 @@ TORCH_LIBRARY(fcsa, m) {
   m.def("kvcache_fp8_forward(Tensor q, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor? k_new, Tensor? v_new, Tensor? cache_seqlens, "
         "Tensor? block_table, Tensor k_scale, Tensor v_scale, int max_seqlen_k, float scale, bool causal, bool l2norm_qk, int groups, "
         "int window_left, int window_right) -> Tensor");
+  // a ragged step: q [total_q, H, D] and k_new / v_new [total_q, Hk, D] packed by cu_seqlens_q [B + 1]; k_scale / v_scale: an fp8 cache
+  m.def("kvcache_varlen_forward(Tensor q, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor cu_seqlens_q, Tensor? k_new, Tensor? v_new, "
+        "Tensor? cache_seqlens, Tensor? block_table, Tensor? k_scale, Tensor? v_scale, int max_seqlen_q, int max_seqlen_k, float scale, "
+        "bool causal, bool l2norm_qk, int groups, int window_left, int window_right) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(fcsa, CUDA, m) {       // ROCm builds of PyTorch dispatch HIP tensors under the CUDA key
@@ -1012,6 +1067,7 @@ TORCH_LIBRARY_IMPL(fcsa, CUDA, m) {       // ROCm builds of PyTorch dispatch HIP
   m.impl("varlen_window_attention", &varlen_window_attention_plain);
   m.impl("kvcache_window_forward", &kvcache_window_forward);
   m.impl("kvcache_fp8_forward", &kvcache_fp8_forward);
+  m.impl("kvcache_varlen_forward", &kvcache_varlen_forward);
 }
 
 TORCH_LIBRARY_IMPL(fcsa, Autograd, m) {

@@ -394,3 +394,133 @@ def flash_cosine_sim_attention_with_kvcache(q, k_cache, v_cache, k_new=None, v_n
                                                         float(scale), bool(causal), bool(l2norm_qk), int(groups), window[0], window[1])
     return _torch_ops.load().kvcache_forward(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, int(max_k), float(scale),
                                              bool(causal), bool(l2norm_qk), int(groups))
+
+
+def flash_cosine_sim_attention_varlen_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new=None, v_new=None, cache_seqlens=None,
+                                                   block_table=None, max_seqlen_q=None, max_seqlen_k=None, scale=8, groups=1, causal=False,
+                                                   l2norm_qk=True, k_scale=None, v_scale=None, window_size=(-1, -1)):
+    """A ragged decode step: `flash_cosine_sim_attention_with_kvcache` with a per-sequence number of queries, in one call.
+
+    The step of a continuous-batching engine is never rectangular -- plain decodes bring 1 token, speculative sequences a few, a prompt
+    chunk many.  q [total_q, H, D] packs the queries of B sequences back to back, as in `flash_cosine_sim_attention_varlen`: sequence b owns
+    the rows [cu_seqlens_q[b], cu_seqlens_q[b + 1]) (int32 [B + 1]), N_b of them; N_b may be 0.  Returns o shaped like q.  Forward only.
+    k_cache, v_cache, block_table, cache_seqlens, max_seqlen_k, k_scale / v_scale with float8_e4m3fn caches, window_size and every layout,
+    stride and page rule are those of `flash_cosine_sim_attention_with_kvcache`.
+    k_new, v_new: [total_q, Hk, D], packed by the same table -- every query token brings its key and value.  Sequence b's N_b rows are
+    written at [cache_seqlens[b], cache_seqlens[b] + N_b) before attention reads the cache (slots at or beyond the capacity are dropped,
+    cache_seqlens is not advanced, fp8 caches quantise as usual), and L_b = cache_seqlens[b] + N_b.  Without them L_b = cache_seqlens[b]
+    (None: the capacity).
+    Sequence b's rows equal `flash_cosine_sim_attention_with_kvcache` on that sequence alone (q_b [1, H, N_b, D], its own cache, the same
+    keywords): causal is bottom-right aligned against L_b (query i sees keys j <= L_b - N_b + i), the window applies per sequence, rows
+    without a visible key -- L_b == 0, or N_b > L_b under causal -- give 0.
+    Host tables (cu_seqlens_q, cache_seqlens) are validated; device tables are trusted and clamped on the device, so a malformed table gives
+    wrong rows, never an access outside the tensors.  max_seqlen_q (default total_q) and max_seqlen_k (default the capacity) are upper
+    bounds that only size the launch: a wrong bound changes speed, never the result.  With device tables the call does not synchronise, so
+    a step can be captured in a HIP graph.  CPU tensors take the forward-only path of `cpu.py` (host tables).
+    The launch has one row-tile slot per 16 rows of G * N_b (about G * total_q / 16 + B per K/V head, whatever the longest sequence is), and
+    every row tile re-reads and re-normalises its keys: this is the call for steps of one to a few dozen tokens per sequence.  Long prompt
+    chunks work, at the decode kernel's efficiency."""
+    window = _window(window_size)
+    fp8_types = tuple(getattr(torch, n) for n in ("float8_e4m3fn", "float8_e4m3fnuz", "float8_e5m2", "float8_e5m2fnuz") if hasattr(torch, n))
+    fp8 = k_cache.dtype in fp8_types or v_cache.dtype in fp8_types
+    if fp8:
+        if k_cache.dtype != torch.float8_e4m3fn or v_cache.dtype != torch.float8_e4m3fn:
+            raise TypeError(f"an fp8 cache is torch.float8_e4m3fn for both k_cache and v_cache (OCP e4m3, the gfx950 encoding), got "
+                            f"{k_cache.dtype} and {v_cache.dtype}")
+        if q.dtype not in (torch.float16, torch.bfloat16):
+            raise TypeError(f"fp8 caches take float16 or bfloat16 q, k_new and v_new, got a {q.dtype} q")
+        for name, t in (("k_new", k_new), ("v_new", v_new)):
+            if t is not None and t.dtype != q.dtype:
+                raise TypeError(f"{name} must have q's dtype ({q.dtype}), got {t.dtype}")
+    elif k_scale is not None or v_scale is not None:
+        raise TypeError(f"k_scale / v_scale given with {k_cache.dtype} caches: scales belong to torch.float8_e4m3fn caches")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_new, v_new)):
+        raise RuntimeError("flash_cosine_sim_attention_varlen_with_kvcache is forward-only: q, k_new and v_new must not require grad "
+                           "(run it under torch.no_grad())")
+    if q.dim() != 3:
+        raise ValueError(f"q must be a packed [total_q, heads, dim_head] tensor, got {tuple(q.shape)}")
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if t.dim() != 4:
+            raise ValueError(f"{name} must have 4 dimensions, got {tuple(t.shape)}")
+    if k_cache.shape != v_cache.shape:
+        raise ValueError(f"k_cache and v_cache must have the same shape, got {tuple(k_cache.shape)} and {tuple(v_cache.shape)}")
+    if (k_new is None) != (v_new is None):
+        raise ValueError("k_new and v_new must be given together")
+    if not isinstance(cu_seqlens_q, torch.Tensor) or cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 1:
+        raise TypeError("cu_seqlens_q must be a 1-D int32 tensor of sequences + 1 entries")
+    total_q, H, D = q.shape
+    B = cu_seqlens_q.numel() - 1
+    Hk = k_cache.shape[1]
+    if k_cache.shape[3] != D:
+        raise ValueError("query, key, value dimensions must be the same")
+    if Hk < 1 or H % Hk:
+        raise ValueError(f"k/v heads must divide q heads ({H}), got {Hk}")
+    if k_new is not None and (k_new.shape != v_new.shape or tuple(k_new.shape) != (total_q, Hk, D)):
+        raise ValueError(f"k_new / v_new must be packed like q, [{total_q}, {Hk}, {D}], got {tuple(k_new.shape)} and {tuple(v_new.shape)}")
+    if block_table is not None:
+        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B:
+            raise TypeError(f"block_table must be an int32 [sequences, max_blocks] tensor")
+        page = k_cache.shape[2]
+        if page <= 0 or page % 16:
+            raise ValueError(f"page_size ({page}) must be a positive multiple of 16")
+        capacity = block_table.shape[1] * page
+    else:
+        if k_cache.shape[0] != B:
+            raise ValueError(f"batch mismatch between cu_seqlens_q ({B} sequences) and the caches ({k_cache.shape[0]})")
+        capacity = k_cache.shape[2]
+    for name, m in (("max_seqlen_q", max_seqlen_q), ("max_seqlen_k", max_seqlen_k)):
+        if m is not None and (int(m) != m or m < 0):
+            raise ValueError(f"{name} must be a non-negative integer, got {m}")
+    host_counts = None
+    if cu_seqlens_q.device.type == "cpu":
+        _check_host_cu("cu_seqlens_q", cu_seqlens_q, total_q, None)
+        c = cu_seqlens_q.tolist()
+        host_counts = [b - a for a, b in zip(c[:-1], c[1:])]
+    host_lens = None
+    if cache_seqlens is None:
+        if k_new is not None:
+            raise ValueError("k_new given but cache_seqlens is None (every sequence full): there is no slot to append to")
+    elif isinstance(cache_seqlens, int):
+        host_lens = [int(cache_seqlens)] * B
+    else:
+        if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32 or cache_seqlens.shape != (B,):
+            raise TypeError(f"cache_seqlens must be an int or an int32 tensor of shape ({B},)")
+        if cache_seqlens.device.type == "cpu":
+            host_lens = [int(x) for x in cache_seqlens.tolist()]
+    if host_lens is not None:
+        for b, n0 in enumerate(host_lens):
+            n_new = host_counts[b] if (k_new is not None and host_counts is not None) else 0
+            if n0 < 0 or n0 + n_new > capacity:
+                raise ValueError(f"sequence {b}: cache_seqlens {n0} + {n_new} new tokens outside [0, capacity {capacity}]")
+        if block_table is not None and block_table.device.type == "cpu":
+            nb = k_cache.shape[0]
+            for b, n0 in enumerate(host_lens):
+                n_new = host_counts[b] if (k_new is not None and host_counts is not None) else 0
+                used = block_table[b, :(n0 + n_new + page - 1) // page]
+                if used.numel() and (int(used.min()) < 0 or int(used.max()) >= nb):
+                    raise ValueError(f"sequence {b}: block_table entries outside [0, {nb})")
+    if fp8:
+        k_scale, v_scale = _cache_scale("k_scale", k_scale, B, Hk, q.device), _cache_scale("v_scale", v_scale, B, Hk, q.device)
+    if q.device.type == "cpu":
+        if host_counts is None or (cache_seqlens is not None and host_lens is None):
+            raise ValueError("CPU tensors take host cu_seqlens_q and cache_seqlens tables")
+        lens = host_lens if host_lens is not None else [capacity] * B
+        detach = lambda t: None if t is None else t.detach()          # (grad mode is off here, or nothing requires grad)
+        quant = dict(k_scale=k_scale.expand(B, Hk), v_scale=v_scale.expand(B, Hk)) if fp8 else {}
+        return _cpu.attention_forward_kvcache_varlen_cpu(q.detach(), k_cache, v_cache, cu_seqlens_q, detach(k_new), detach(v_new), lens,
+                                                         block_table, scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk,
+                                                         window_size=window, **quant)
+    cu_q = cu_seqlens_q.to(q.device, non_blocking=True)
+    if isinstance(cache_seqlens, int):
+        cache_seqlens = torch.full((B,), cache_seqlens, dtype=torch.int32, device=q.device)
+    elif cache_seqlens is not None:
+        cache_seqlens = cache_seqlens.to(q.device, non_blocking=True)
+    if block_table is not None:
+        block_table = block_table.to(q.device, non_blocking=True)
+    max_q = total_q if max_seqlen_q is None else min(int(max_seqlen_q), total_q)
+    max_k = capacity if max_seqlen_k is None else min(int(max_seqlen_k), capacity)
+    if fp8:      # (the op takes the codes as bytes: same storage, so the append lands in the caller's caches)
+        k_cache, v_cache = k_cache.view(torch.uint8), v_cache.view(torch.uint8)
+    return _torch_ops.load().kvcache_varlen_forward(q, k_cache, v_cache, cu_q, k_new, v_new, cache_seqlens, block_table, k_scale, v_scale,
+                                                    int(max_q), int(max_k), float(scale), bool(causal), bool(l2norm_qk), int(groups),
+                                                    window[0], window[1])

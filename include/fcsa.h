@@ -302,6 +302,33 @@ int    fcsa_forward_kvcache_quant(const fcsa_forward_args* args, const fcsa_kvca
 size_t fcsa_forward_kvcache_quant_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* cache, const fcsa_kvcache_quant* quant,
                                                   const fcsa_window* window);
 
+/* A ragged decode step: fcsa_forward_kvcache[_window / _quant] with PACKED queries and a per-sequence query count, the step of a
+ * continuous-batching engine (plain decodes bring 1 token, speculative sequences a few, a prompt chunk many).  Sequence b owns the packed
+ * rows [cu_seqlens_q[b], cu_seqlens_q[b + 1]) of q and o, N_b of them (0 is allowed); its rows are what fcsa_forward_kvcache computes for
+ * the batch-1 call (q_b [1, H, N_b, D], the sequence's own cache, the same problem fields, quant and window): bottom-right causal alignment
+ * against its own L_b, the window per sequence, o = 0 for rows without a visible key (L_b == 0, or N_b > L_b under causal).
+ * The arguments are read as follows:
+ *   p.batch = sequences, p.q_len = max_seqlen_q, p.k_len = max_seqlen_k: upper bounds that only size the split count (the grid has
+ *             floor(G * total_q / 16) + batch row-tile slots per K/V head, whatever max_seqlen_q says) -- a wrong bound changes speed,
+ *             never the result
+ *   q, o    : packed [total_q, H, D] views as in fcsa_forward_varlen (stride0 ignored, stride1 = head stride, stride2 = token stride)
+ *   seqs    : cu_seqlens_q (device, [batch + 1]) and total_q; cu_seqlens_k and total_k are ignored
+ *   cache   : as in fcsa_forward_kvcache, except the append: k_new / v_new are packed [total_q, Hk, D] views (every query row brings its
+ *             key and value) and new_len is a flag -- 1: sequence b's N_b rows are written at [cache_seqlens[b], cache_seqlens[b] + N_b)
+ *             first (slots at or beyond the capacity are dropped) and L_b = min(cache_seqlens[b] + N_b, capacity); 0: no append, L_b =
+ *             cache_seqlens[b] (NULL: the capacity).  Any other value: FCSA_ERR_INVALID_ARG.  cache_seqlens is not advanced.
+ *   quant   : NULL, or an e4m3fn cache as in fcsa_forward_kvcache_quant (scales indexed by sequence and K/V head)
+ *   window  : NULL, or the window of fcsa_forward_kvcache_window, applied per sequence
+ *   workspace: >= fcsa_forward_kvcache_varlen_workspace_bytes() bytes, 256-byte aligned: the split partials over total_q * H rows
+ * The tables are device data, never read by the host and clamped on the device: a malformed table gives wrong rows, never an access
+ * outside the tensors.  Each row tile re-reads and re-normalises its keys, so this is the call for steps of one to a few dozen tokens per
+ * sequence; long prompt chunks work, at the decode kernel's efficiency.
+ * Launches: "kv_append_ragged" (when appending), "decode_ragged" and "decode_combine_ragged"; with quant each name ends in "_fp8". */
+int    fcsa_forward_kvcache_varlen(const fcsa_forward_args* args, const fcsa_kvcache* cache, const fcsa_varlen* seqs,
+                                   const fcsa_kvcache_quant* quant, const fcsa_window* window);
+size_t fcsa_forward_kvcache_varlen_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* cache, const fcsa_varlen* seqs,
+                                                   const fcsa_kvcache_quant* quant, const fcsa_window* window);
+
 /* Bytes of optional forward scratch that enable the split-key forward for this problem (0: never split). */
 size_t fcsa_forward_workspace_bytes(const fcsa_problem* p);
 
