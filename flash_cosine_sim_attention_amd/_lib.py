@@ -84,6 +84,9 @@ KvCache = _STRUCTS["fcsa_kvcache"]
 Window = _STRUCTS["fcsa_window"]
 KvCacheQuant = _STRUCTS["fcsa_kvcache_quant"]
 FCSA_CACHE_E4M3 = _MACROS["FCSA_CACHE_E4M3"]
+LseOut = _STRUCTS["fcsa_lse_out"]
+MergeArgs = _STRUCTS["fcsa_merge_args"]
+MERGE_MAX_STATES = _MACROS["FCSA_MERGE_MAX_STATES"]
 
 
 EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fcsa_forward_workspace_bytes", "fcsa_forward_needs_qn",
@@ -91,7 +94,8 @@ EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fc
            "fcsa_forward_varlen", "fcsa_backward_varlen", "fcsa_backward_varlen_workspace_bytes", "fcsa_forward_kvcache",
            "fcsa_forward_kvcache_workspace_bytes", "fcsa_forward_window", "fcsa_backward_window", "fcsa_backward_window_workspace_bytes",
            "fcsa_forward_kvcache_window", "fcsa_forward_kvcache_window_workspace_bytes", "fcsa_forward_kvcache_quant",
-           "fcsa_forward_kvcache_quant_workspace_bytes", "fcsa_forward_kvcache_varlen", "fcsa_forward_kvcache_varlen_workspace_bytes")
+           "fcsa_forward_kvcache_quant_workspace_bytes", "fcsa_forward_kvcache_varlen", "fcsa_forward_kvcache_varlen_workspace_bytes",
+           "fcsa_forward_kvcache_lse", "fcsa_merge_states")
 
 _lib = None
 
@@ -177,6 +181,12 @@ def load():
         lib.fcsa_forward_kvcache_varlen_workspace_bytes.argtypes = [C.POINTER(Problem), C.POINTER(KvCache), C.POINTER(Varlen),
                                                                     C.POINTER(KvCacheQuant), C.POINTER(Window)]
         lib.fcsa_forward_kvcache_varlen_workspace_bytes.restype = C.c_size_t
+    if hasattr(lib, "fcsa_forward_kvcache_lse"):      # (likewise: an FCSA_LIB build from before the log-sum-exp and the state merge)
+        lib.fcsa_forward_kvcache_lse.argtypes = [C.POINTER(ForwardArgs), C.POINTER(KvCache), C.POINTER(Varlen), C.POINTER(KvCacheQuant),
+                                                 C.POINTER(Window), C.POINTER(LseOut)]
+        lib.fcsa_forward_kvcache_lse.restype = C.c_int
+        lib.fcsa_merge_states.argtypes = [C.POINTER(MergeArgs)]
+        lib.fcsa_merge_states.restype = C.c_int
     lib.fcsa_last_error.argtypes = []
     lib.fcsa_last_error.restype = C.c_char_p
     ver = lib.fcsa_debug(None, 0)

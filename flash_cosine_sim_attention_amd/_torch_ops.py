@@ -124,6 +124,16 @@ def _register_fakes():
           causal, l2norm_qk, groups, window_left, window_right):
         return q.new_empty(q.shape)
 
+    @torch.library.register_fake("fcsa::kvcache_lse_forward")
+    def _(q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, k_scale, v_scale, max_seqlen_q, max_seqlen_k, scale,
+          causal, l2norm_qk, groups, window_left, window_right):
+        # lse: float32 [B, H, N]; a ragged step (q [total_q, H, D]): [total_q, H]
+        return q.new_empty(q.shape), q.new_empty(q.shape[:-1], dtype=torch.float32)
+
+    @torch.library.register_fake("fcsa::merge_states")
+    def _(os, lses):
+        return os[0].new_empty(os[0].shape), os[0].new_empty(os[0].shape[:-1], dtype=torch.float32)
+
     @torch.library.register_fake("fcsa::backward")
     def _(d_out, o, inv_l, q, k, v, mask, attn_bias, qn, kn, rq, rk, attn_bias_batch_dim, scale, causal, l2norm_qk, groups,
           need_bias_grad):

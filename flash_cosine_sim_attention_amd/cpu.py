@@ -74,10 +74,12 @@ def window_index(window_size):
 
 
 def attention_forward_cpu(q, k, v, mask=None, attn_bias=None, scale=8.0, groups=1, causal=False, l2norm_qk=True,
-                          attn_bias_batch_dim=False, row_block=256, key_block=1024, window_size=(-1, -1)):
+                          attn_bias_batch_dim=False, row_block=256, key_block=1024, window_size=(-1, -1), return_lse=False):
     """Forward-only blockwise cosine-sim attention on host tensors.  Same argument meaning as the GPU operator.
     window_size = (left, right): query i sees key j iff i + (M - N) - left <= j <= i + (M - N) + right (-1: unbounded; causal caps
-    right at 0); the key blocks outside a row block's band are never touched."""
+    right at 0); the key blocks outside a row block's band are never touched.
+    return_lse: also return the rows' log-sum-exp, float32 of q's shape without the feature dim: log(sum over the visible keys of
+    exp(logit)), from the running max and row sum the loop holds; -inf for a row without a visible key."""
     w_left, w_right = window_sides(window_size, causal)
     if tuple(window_index(window_size)) != (-1, -1) and (mask is not None or attn_bias is not None):      # (as the C ABI: any window)
         raise ValueError("a sliding window takes no mask and no attn_bias")
@@ -149,7 +151,12 @@ def attention_forward_cpu(q, k, v, mask=None, attn_bias=None, scale=8.0, groups=
             s += w.sum(dim=-1, keepdim=True)
             t.copy_(t_new)
     out = acc / total.clamp_min(1e-30)                    # rows without a valid key: 0 / tiny = 0
-    return out.reshape(out_shape).to(out_dtype)
+    out = out.reshape(out_shape).to(out_dtype)
+    if not return_lse:
+        return out
+    seen = total > 0                                      # (a row that saw no key has top = -inf and total = 0)
+    lse = torch.where(seen, top + torch.log(torch.where(seen, total, torch.ones_like(total))), torch.full_like(top, float("-inf")))
+    return out, lse.reshape(out_shape[:-1])
 
 
 def attention_forward_varlen_cpu(q, k, v, cu_seqlens_q, cu_seqlens_k, scale=8.0, groups=1, causal=False, l2norm_qk=True,
@@ -211,12 +218,13 @@ def quantise_e4m3(x, scale):
 
 
 def attention_forward_kvcache_cpu(q, k_cache, v_cache, k_new, v_new, seqlens, block_table=None, scale=8.0, groups=1, causal=False,
-                                  l2norm_qk=True, window_size=(-1, -1), k_scale=None, v_scale=None):
+                                  l2norm_qk=True, window_size=(-1, -1), k_scale=None, v_scale=None, return_lse=False):
     """Forward-only path of `flash_cosine_sim_attention_with_kvcache` on host tensors: the append as an indexed copy, then the dense CPU
     forward of every sequence over its first L_b = seqlens[b] + N_new cached positions (o = 0 where L_b == 0).  seqlens: host ints.
     k_scale / v_scale (float32 [B, Hk], both or neither): the caches are float8_e4m3fn codes meaning scale * code -- the append quantises
     (quantise_e4m3), and each sequence's keys and values are dequantised to float32 for the dense forward, whose result is cast to q's
-    dtype."""
+    dtype.  return_lse: also the rows' log-sum-exp, float32 [B, H, N] (-inf where a row sees no key; k_scale is inside the logits, v_scale
+    is not)."""
     fp8 = k_scale is not None
     if k_new is not None:
         if fp8:
@@ -227,6 +235,7 @@ def attention_forward_kvcache_cpu(q, k_cache, v_cache, k_new, v_new, seqlens, bl
             append_kvcache_cpu(k_cache, v_cache, k_new, v_new, seqlens, block_table)
     n_new = 0 if k_new is None else k_new.shape[2]
     out = torch.zeros_like(q)
+    lse = torch.full(q.shape[:-1], float("-inf"), dtype=torch.float32)
     for b, start in enumerate(seqlens):
         length = start + n_new
         if length == 0 or q.shape[2] == 0:
@@ -236,18 +245,20 @@ def attention_forward_kvcache_cpu(q, k_cache, v_cache, k_new, v_new, seqlens, bl
         if fp8:
             qb = qb.float()
             kb, vb = kb.float() * k_scale[b][None, :, None, None], vb.float() * v_scale[b][None, :, None, None]
-        out[b:b + 1] = attention_forward_cpu(qb, kb, vb, scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk,
-                                             window_size=window_size)
-    return out
+        out[b:b + 1], lse[b:b + 1] = attention_forward_cpu(qb, kb, vb, scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk,
+                                                           window_size=window_size, return_lse=True)
+    return (out, lse) if return_lse else out
 
 
 def attention_forward_kvcache_varlen_cpu(q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, seqlens, block_table=None, scale=8.0, groups=1,
-                                         causal=False, l2norm_qk=True, window_size=(-1, -1), k_scale=None, v_scale=None):
+                                         causal=False, l2norm_qk=True, window_size=(-1, -1), k_scale=None, v_scale=None,
+                                         return_lse=False):
     """Forward-only path of `flash_cosine_sim_attention_varlen_with_kvcache` on host tensors: packed q [total_q, H, D] and k_new / v_new
     [total_q, Hk, D] with a validated host table; sequence b's N_b rows run through `attention_forward_kvcache_cpu` as a batch-1 call on
     its own cache (a view: the append lands in the caller's caches), so its rows and its cache slots are exactly what the equal-N path
-    gives for that sequence alone.  seqlens: host ints, tokens cached before the append."""
+    gives for that sequence alone.  seqlens: host ints, tokens cached before the append.  return_lse: also the rows' log-sum-exp, float32 [total_q, H]."""
     out = torch.zeros_like(q)
+    lse = torch.full(q.shape[:-1], float("-inf"), dtype=torch.float32)
     cq = cu_seqlens_q.tolist()
     for b in range(len(cq) - 1):
         lo, hi = cq[b], cq[b + 1]
@@ -257,7 +268,34 @@ def attention_forward_kvcache_varlen_cpu(q, k_cache, v_cache, cu_seqlens_q, k_ne
         paged = block_table is not None
         kc, vc = (k_cache, v_cache) if paged else (k_cache[b:b + 1], v_cache[b:b + 1])
         quant = {} if k_scale is None else dict(k_scale=k_scale[b:b + 1], v_scale=v_scale[b:b + 1])
-        o = attention_forward_kvcache_cpu(rows(q), kc, vc, rows(k_new), rows(v_new), [seqlens[b]], block_table[b:b + 1] if paged else None,
-                                          scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, window_size=window_size, **quant)
+        o, l = attention_forward_kvcache_cpu(rows(q), kc, vc, rows(k_new), rows(v_new), [seqlens[b]], block_table[b:b + 1] if paged else None,
+                                             scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, window_size=window_size,
+                                             return_lse=True, **quant)
         out[lo:hi] = o[0].permute(1, 0, 2)
-    return out
+        lse[lo:hi] = l[0].permute(1, 0)
+    return (out, lse) if return_lse else out
+
+
+def merge_attention_states_cpu(os, lses):
+    """`merge_attention_states` on host tensors, in float32: M = max_s lse_s; every state empty (M == -inf): o = 0, lse = -inf; else
+    w_s = exp(lse_s - M), W = sum_s w_s, o = (sum_s w_s * o_s) / W rounded once, lse = M + log(W).  A state of weight 0 is skipped, as in
+    the kernel: its o_s cannot leak (NaN included), and the first live product of a row is assigned rather than added to +0, so one state
+    beside empty ones comes back bit for bit, -0 included."""
+    lse = torch.stack([l.float() for l in lses])                       # [S, ...]
+    top = lse.amax(dim=0)
+    live = top > float("-inf")
+    safe = torch.where(live, top, torch.zeros_like(top))
+    w = torch.where(lse > float("-inf"), torch.exp(lse - safe), torch.zeros_like(lse))
+    total = w.sum(dim=0)
+    zero = torch.zeros((), dtype=torch.float32)
+    acc = torch.zeros(os[0].shape, dtype=torch.float32)
+    started = torch.zeros(top.shape, dtype=torch.bool).unsqueeze(-1)
+    for s, o in enumerate(os):
+        alive = (w[s] != 0).unsqueeze(-1)
+        term = w[s].unsqueeze(-1) * o.float()
+        acc = torch.where(alive, torch.where(started, acc + term, term), acc)
+        started = started | alive
+    total = torch.where(live, total, torch.ones_like(total))
+    out = torch.where(live.unsqueeze(-1), acc / total.unsqueeze(-1), zero)
+    out_lse = torch.where(live, safe + torch.log(total), torch.full_like(top, float("-inf")))
+    return out.to(os[0].dtype).contiguous(), out_lse.contiguous()

@@ -498,7 +498,9 @@ static bool decode_window_sides(const fcsa_problem& p, const fcsa_kvcache& kv, c
   causal = kind == fcsa::WinKind::Causal ? 1 : kind == fcsa::WinKind::Full ? 0 : p.causal;
   return kind == fcsa::WinKind::Window;
 }
-static int forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv, const WindowCall* win, const fcsa_kvcache_quant* qz = nullptr);
+// lse: NULL, or where the combine also writes the rows' log-sum-exp (fcsa_forward_kvcache_lse: the "decode_combine_lse*" launches)
+static int forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv, const WindowCall* win, const fcsa_kvcache_quant* qz = nullptr,
+                           const fcsa_lse_out* lse = nullptr);
 
 size_t fcsa_forward_kvcache_window_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv, const fcsa_window* w) {
   if (p == nullptr || kv == nullptr || w == nullptr) return 0;
@@ -543,7 +545,8 @@ int fcsa_forward_kvcache_quant(const fcsa_forward_args* a, const fcsa_kvcache* k
   return forward_kvcache(a, kv, &win, qz);
 }
 
-static int forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv, const WindowCall* win, const fcsa_kvcache_quant* qz) {
+static int forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv, const WindowCall* win, const fcsa_kvcache_quant* qz,
+                           const fcsa_lse_out* lse) {
   if (int rc = qz != nullptr ? check_quant(a, kv, qz) : check_kvcache(a, kv)) return rc;
   const fcsa_problem& p = a->p;
   if (p.batch == 0) return FCSA_OK;
@@ -581,6 +584,7 @@ static int forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv, c
   dp.ws_o = static_cast<float*>(a->workspace);
   dp.ws_ml = reinterpret_cast<float*>(static_cast<char*>(a->workspace) + d.ws_ml);
   if (win != nullptr) { dp.window = 1; dp.win_lo = win->lo; dp.win_hi = win->hi; }
+  const fcsa::DecodeLseOut lo = lse != nullptr ? fcsa::DecodeLseOut{lse->lse, lse->stride0, lse->stride1, lse->stride2} : fcsa::DecodeLseOut{};
   if (qz != nullptr) {
     dp.k_scale = qz->k_scale; dp.v_scale = qz->v_scale;
     dp.ks_b = qz->k_scale_stride0; dp.ks_h = qz->k_scale_stride1;
@@ -590,6 +594,8 @@ static int forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv, c
     }
     if (!rows) return FCSA_OK;
     if (int rc = timed("decode_fp8", "decode (fp8)", s, [&] { return fcsa::launch_decode_fp8(p.dtype, p.dim_head, dp, s); })) return rc;
+    if (lse != nullptr)
+      return timed("decode_combine_lse_fp8", "decode combine (lse, fp8)", s, [&] { return fcsa::launch_decode_combine_lse_fp8(p.dtype, p.dim_head, dp, lo, s); });
     return timed("decode_combine_fp8", "decode combine (fp8)", s, [&] { return fcsa::launch_decode_combine_fp8(p.dtype, p.dim_head, dp, s); });
   }
   // 1. the append (before anything reads the cache: same stream), 2. the split partials, 3. their combine
@@ -598,6 +604,8 @@ static int forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv, c
   }
   if (!rows) return FCSA_OK;
   if (int rc = timed("decode", "decode", s, [&] { return fcsa::launch_decode(p.dtype, p.dim_head, dp, s); })) return rc;
+  if (lse != nullptr)
+    return timed("decode_combine_lse", "decode combine (lse)", s, [&] { return fcsa::launch_decode_combine_lse(p.dtype, p.dim_head, dp, lo, s); });
   return timed("decode_combine", "decode combine", s, [&] { return fcsa::launch_decode_combine(p.dtype, p.dim_head, dp, s); });
 }
 
@@ -659,8 +667,16 @@ size_t fcsa_forward_kvcache_varlen_workspace_bytes(const fcsa_problem* p, const 
   return ragged_plan(*p, *kv, seqs->total_q, lo).total;
 }
 
+static int forward_kvcache_varlen(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_kvcache_quant* qz,
+                                  const fcsa_window* w, const fcsa_lse_out* lse);
 int fcsa_forward_kvcache_varlen(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_kvcache_quant* qz,
                                 const fcsa_window* w) {
+  return forward_kvcache_varlen(a, kv, seqs, qz, w, nullptr);
+}
+
+// lse: NULL, or where the combine also writes the log-sum-exp of every packed row (fcsa_forward_kvcache_lse)
+static int forward_kvcache_varlen(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_kvcache_quant* qz,
+                                  const fcsa_window* w, const fcsa_lse_out* lse) {
   if (int rc = check_kvcache_varlen(a, kv, seqs, qz, w)) return rc;
   const fcsa_problem& p = a->p;
   if (p.batch == 0 || seqs->total_q == 0) return FCSA_OK;      // no sequence, or no packed row: nothing to append, nothing to write
@@ -717,8 +733,65 @@ int fcsa_forward_kvcache_varlen(const fcsa_forward_args* a, const fcsa_kvcache* 
   if (!rows) return FCSA_OK;
   if (int rc = timed(fp8 ? "decode_ragged_fp8" : "decode_ragged", "decode (ragged)", s,
                      [&] { return fcsa::launch_decode_ragged(p.dtype, p.dim_head, fp8, dp, s); })) return rc;
+  if (lse != nullptr) {
+    const fcsa::DecodeLseOut lo = {lse->lse, 0, lse->stride1, lse->stride2};
+    return timed(fp8 ? "decode_combine_lse_ragged_fp8" : "decode_combine_lse_ragged", "decode combine (lse, ragged)", s,
+                 [&] { return fcsa::launch_decode_combine_lse_ragged(p.dtype, p.dim_head, fp8, dp, lo, s); });
+  }
   return timed(fp8 ? "decode_combine_ragged_fp8" : "decode_combine_ragged", "decode combine (ragged)", s,
                [&] { return fcsa::launch_decode_combine_ragged(p.dtype, p.dim_head, fp8, dp, s); });
+}
+
+// ---- the decode calls with the rows' log-sum-exp (fcsa_forward_kvcache_lse), and merging attention states (fcsa_merge_states) ----------
+// Each route is the corresponding entry point's own code with `lse` handed down: the same checks, window normalisation, plan and append /
+// decode launches, so o and the caches are that entry point's bit for bit.
+int fcsa_forward_kvcache_lse(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_kvcache_quant* qz,
+                             const fcsa_window* w, const fcsa_lse_out* lse) {
+  if (a == nullptr || kv == nullptr || lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_lse: null argument");
+  const bool rows = a->p.batch > 0 && a->p.heads > 0 && (seqs != nullptr ? seqs->total_q > 0 : a->p.q_len > 0);
+  if (rows && lse->lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_lse: lse: null pointer");
+  if (seqs != nullptr) return forward_kvcache_varlen(a, kv, seqs, qz, w, lse);
+  if (int rc = qz != nullptr ? check_quant(a, kv, qz) : check_kvcache(a, kv)) return rc;
+  if (w == nullptr) return forward_kvcache(a, kv, nullptr, qz, lse);
+  if (int rc = check_window(w, false, false)) return rc;
+  WindowCall win;
+  fcsa_forward_args na = *a;
+  if (!decode_window_sides(a->p, *kv, *w, win, na.p.causal)) return forward_kvcache(&na, kv, nullptr, qz, lse);
+  return forward_kvcache(a, kv, &win, qz, lse);
+}
+
+int fcsa_merge_states(const fcsa_merge_args* a) {
+  static_assert(FCSA_MERGE_MAX_STATES == fcsa::kMergeMaxStates && sizeof(a->o_in) / sizeof(a->o_in[0]) == FCSA_MERGE_MAX_STATES, "fcsa_merge_args");
+  if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "merge_states: null args");
+  if (a->dtype != FCSA_F32 && a->dtype != FCSA_F16 && a->dtype != FCSA_BF16) return fail(FCSA_ERR_UNSUPPORTED, "merge_states: dtype %d not supported", a->dtype);
+  if (a->states < 1 || a->states > FCSA_MERGE_MAX_STATES)
+    return fail(FCSA_ERR_INVALID_ARG, "merge_states: %d states outside [1, %d] (merge more in two steps)", a->states, FCSA_MERGE_MAX_STATES);
+  if (a->size0 < 0 || a->size1 < 0 || a->size2 < 0) return fail(FCSA_ERR_INVALID_ARG, "merge_states: negative size");
+  // rows 16-byte aligned: whole 16-byte chunks per row, 4 float32 or 8 16-bit features
+  const int per16 = 16 / elem_size(a->dtype);
+  if (a->dim_head < per16 || a->dim_head % per16 != 0)
+    return fail(FCSA_ERR_UNSUPPORTED, "merge_states: dim_head %d is not a positive multiple of %d (16-byte rows)", a->dim_head, per16);
+  const int64_t rows = (int64_t)a->size0 * a->size1 * a->size2;
+  if (rows == 0) return FCSA_OK;
+  if (rows * (a->dim_head / 4) > (int64_t)INT32_MAX * 256) return fail(FCSA_ERR_UNSUPPORTED, "merge_states: grid above 2^31 workgroups");
+  const int es = elem_size(a->dtype);
+  fcsa::MergeParams mp;
+  for (int s = 0; s < FCSA_MERGE_MAX_STATES; ++s) {
+    const int t = std::min(s, a->states - 1);      // (the unused slots repeat the last state: never read, never null)
+    if (s < a->states) {
+      if (int rc = check_tensor("merge_states: o_in", a->o_in[s], es, true)) return rc;
+      if (a->lse_in[s].lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "merge_states: lse_in[%d]: null pointer", s);
+    }
+    mp.o_in[s] = view(a->o_in[t], es);
+    mp.lse_in[s] = fcsa::DecodeLseOut{a->lse_in[t].lse, a->lse_in[t].stride0, a->lse_in[t].stride1, a->lse_in[t].stride2};
+  }
+  if (int rc = check_tensor("merge_states: o", a->o, es, true)) return rc;
+  if (a->lse.lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "merge_states: lse: null pointer");
+  mp.o = view(a->o, es);
+  mp.lse = fcsa::DecodeLseOut{a->lse.lse, a->lse.stride0, a->lse.stride1, a->lse.stride2};
+  mp.n0 = a->size0; mp.n1 = a->size1; mp.n2 = a->size2; mp.D = a->dim_head; mp.S = a->states;
+  hipStream_t s = static_cast<hipStream_t>(a->stream);
+  return timed("merge_states", "merge states", s, [&] { return fcsa::launch_merge_states(a->dtype, mp, s); });
 }
 }  // extern "C"
 

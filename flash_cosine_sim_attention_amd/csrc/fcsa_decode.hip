@@ -8,6 +8,8 @@
 //                         wave-private LDS block for the transposed reads of O^T = V^T P~^T.  Partials (P~V, row max, row sum) in f32.
 //   decode_combine_kernel reconciles the splits of every row (a per-split row max in the per-row-shift regime, a common shift
 //                         otherwise) and normalises.
+//   decode_combine_lse*   the same combine, also writing the rows' log-sum-exp (fcsa_forward_kvcache_lse): one body (decode_combine_body)
+//                         behind every combine entry point, the LSE forms as entry points of their own.
 // A ragged step (fcsa_forward_kvcache_varlen: packed queries, per-sequence counts) has entry points of its own as well --
 // kv_append_ragged_kernel, decode_ragged[_fp8]_kernel (decode_body with RAGGED), decode_combine_ragged_kernel.
 // An fp8 cache (fcsa_forward_kvcache_quant: one-byte OCP e4m3fn codes and a float32 scale per (batch, K/V head)) has entry points of its
@@ -505,12 +507,20 @@ __global__ __launch_bounds__(64) void decode_ragged_fp8_kernel(DecodeRaggedParam
   decode_body<T, D, DYN, GEN, true, true, true>(p);
 }
 
-// o = sum_s 2^(m_s - M) P~V_s / sum_s 2^(m_s - M) l_s over the splits of a row (static regime: every m_s is the common shift, weight 1)
-template <typename T, int D>
-__global__ __launch_bounds__(256) void decode_combine_kernel(DecodeParams p) {
+// The combine of one row's splits, shared by every combine entry point: o = sum_s 2^(m_s - M) P~V_s / sum_s 2^(m_s - M) l_s (static
+// regime: every m_s is the common shift, weight 1).
+// FP8: the cache's values are v_scale * code, so the row's v_scale joins the normaliser.
+// RAGGED: partial row (tok, h) of the [total_q, H] rows goes to packed row `tok` of o; an fp8 cache's v_scale is that of the sequence
+// owning the row (ragged_seq_of).
+// LSE (decode_combine_lse*_kernel, fcsa_forward_kvcache_lse): the thread of the row's first four features also writes the row's
+// log-sum-exp, from M and the UNCLAMPED l (decode_row_lse).  The statements that make o are the same either way.
+template <typename T, int D, bool FP8, bool RAGGED, bool LSE, typename P>
+FCSA_DEV void decode_combine_body(const P& p, const DecodeLseOut& lo) {
   constexpr int ES = Traits<T>::ES;
   constexpr int TPR = D / 4;                       // threads per row: four features each
-  const int64_t rows = (int64_t)p.B * p.H * p.N;
+  int64_t rows;
+  if constexpr (RAGGED) rows = (int64_t)p.total_q * p.H;
+  else rows = (int64_t)p.B * p.H * p.N;
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t row = t / TPR;
   const int c = (int)(t % TPR);
@@ -528,45 +538,57 @@ __global__ __launch_bounds__(256) void decode_combine_kernel(DecodeParams p) {
     }
   }
   const float inv = p.dyn ? (l > 0.f ? 1.f / l : 0.f) : 1.f / fmaxf(l, p.l_eps);
-  acc *= inv;
-  const int i = (int)(row % p.N);
-  const int64_t bh = row / p.N;
-  const int h = (int)(bh % p.H), b = (int)(bh / p.H);
-  char* dst = p.o.p + (int64_t)b * p.o.sb + (int64_t)h * p.o.sh + (int64_t)i * p.o.sn + 4 * c * ES;
+  int h;
+  char* dst;
+  if constexpr (RAGGED) {
+    const int64_t tok = row / p.H;
+    h = (int)(row % p.H);
+    if constexpr (FP8) {
+      const int b = ragged_seq_of(p.cu_q, p.B, p.total_q, tok);
+      acc *= inv * p.v_scale[(int64_t)b * p.vs_b + (int64_t)(h / p.G) * p.vs_h];
+    } else {
+      acc *= inv;
+    }
+    dst = p.o.p + (int64_t)h * p.o.sh + tok * p.o.sn + 4 * c * ES;
+    if constexpr (LSE) {
+      if (c == 0) lo.lse[(int64_t)h * lo.sh + tok * lo.sn] = decode_row_lse(M, l);
+    }
+  } else {
+    const int i = (int)(row % p.N);
+    const int64_t bh = row / p.N;
+    h = (int)(bh % p.H);
+    const int b = (int)(bh / p.H);
+    if constexpr (FP8) acc *= inv * p.v_scale[(int64_t)b * p.vs_b + (int64_t)(h / p.G) * p.vs_h];
+    else acc *= inv;
+    dst = p.o.p + (int64_t)b * p.o.sb + (int64_t)h * p.o.sh + (int64_t)i * p.o.sn + 4 * c * ES;
+    if constexpr (LSE) {
+      if (c == 0) lo.lse[(int64_t)b * lo.sb + (int64_t)h * lo.sh + (int64_t)i * lo.sn] = decode_row_lse(M, l);
+    }
+  }
   if constexpr (ES == 4) {
     *reinterpret_cast<f32x4*>(dst) = acc;
   } else {
     *reinterpret_cast<u32x2*>(dst) = u32x2{Traits<T>::pack2(acc[0], acc[1]), Traits<T>::pack2(acc[2], acc[3])};
   }
 }
-// decode_combine_kernel for an fp8 cache (16-bit T): the cache's values are v_scale * code, so the row's v_scale joins the normaliser
+
+template <typename T, int D>
+__global__ __launch_bounds__(256) void decode_combine_kernel(DecodeParams p) {
+  decode_combine_body<T, D, false, false, false>(p, DecodeLseOut{});
+}
+// decode_combine_kernel for an fp8 cache (16-bit T)
 template <typename T, int D>
 __global__ __launch_bounds__(256) void decode_combine_fp8_kernel(DecodeFp8Params p) {
-  constexpr int TPR = D / 4;
-  const int64_t rows = (int64_t)p.B * p.H * p.N;
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t row = t / TPR;
-  const int c = (int)(t % TPR);
-  if (row >= rows) return;
-  float M = -INFINITY;
-  for (int s = 0; s < p.splits; ++s) M = fmaxf(M, p.ws_ml[(s * rows + row) * 2]);
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  float l = 0.f;
-  if (M != -INFINITY) {
-    for (int s = 0; s < p.splits; ++s) {
-      const f32x2 ml = *reinterpret_cast<const f32x2*>(p.ws_ml + (s * rows + row) * 2);
-      const float w = exp2f(ml[0] - M);
-      l += w * ml[1];
-      acc += w * *reinterpret_cast<const f32x4*>(p.ws_o + (s * rows + row) * D + 4 * c);
-    }
-  }
-  const int i = (int)(row % p.N);
-  const int64_t bh = row / p.N;
-  const int h = (int)(bh % p.H), b = (int)(bh / p.H);
-  const float inv = p.dyn ? (l > 0.f ? 1.f / l : 0.f) : 1.f / fmaxf(l, p.l_eps);
-  acc *= inv * p.v_scale[(int64_t)b * p.vs_b + (int64_t)(h / p.G) * p.vs_h];
-  char* dst = p.o.p + (int64_t)b * p.o.sb + (int64_t)h * p.o.sh + (int64_t)i * p.o.sn + 4 * c * 2;
-  *reinterpret_cast<u32x2*>(dst) = u32x2{Traits<T>::pack2(acc[0], acc[1]), Traits<T>::pack2(acc[2], acc[3])};
+  decode_combine_body<T, D, true, false, false>(p, DecodeLseOut{});
+}
+// the combines that also write the rows' log-sum-exp: entry points of their own, so that the ones above are what they were
+template <typename T, int D>
+__global__ __launch_bounds__(256) void decode_combine_lse_kernel(DecodeParams p, DecodeLseOut lo) {
+  decode_combine_body<T, D, false, false, true>(p, lo);
+}
+template <typename T, int D>
+__global__ __launch_bounds__(256) void decode_combine_lse_fp8_kernel(DecodeFp8Params p, DecodeLseOut lo) {
+  decode_combine_body<T, D, true, false, true>(p, lo);
 }
 
 // 16 elements of T (two 16-byte chunks) -> 16 e4m3fn codes: e4m3_rne(clamp(x / scale, -448, 448)).  The divide is the correctly rounded
@@ -651,44 +673,14 @@ __global__ __launch_bounds__(256) void kv_append_fp8_kernel(DecodeFp8Params p) {
   *reinterpret_cast<u32x4*>(p.vc.p + vdst + ch * 16) = quantise16<T>(vs[0], vs[1], p.v_scale[(int64_t)b * p.vs_b + (int64_t)kvh * p.vs_h]);
 }
 
-// decode_combine_kernel / decode_combine_fp8_kernel for a ragged step: partial row (tok, h) of the [total_q, H] rows goes to packed row
-// `tok` of o; an fp8 cache's v_scale is that of the sequence owning the row (ragged_seq_of)
+// decode_combine_kernel / decode_combine_fp8_kernel for a ragged step, and the form that also writes the log-sum-exp of every packed row
 template <typename T, int D, bool FP8>
 __global__ __launch_bounds__(256) void decode_combine_ragged_kernel(DecodeRaggedParams p) {
-  constexpr int ES = Traits<T>::ES;
-  constexpr int TPR = D / 4;
-  const int64_t rows = (int64_t)p.total_q * p.H;
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t row = t / TPR;
-  const int c = (int)(t % TPR);
-  if (row >= rows) return;
-  float M = -INFINITY;
-  for (int s = 0; s < p.splits; ++s) M = fmaxf(M, p.ws_ml[(s * rows + row) * 2]);
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  float l = 0.f;
-  if (M != -INFINITY) {
-    for (int s = 0; s < p.splits; ++s) {
-      const f32x2 ml = *reinterpret_cast<const f32x2*>(p.ws_ml + (s * rows + row) * 2);
-      const float w = exp2f(ml[0] - M);
-      l += w * ml[1];
-      acc += w * *reinterpret_cast<const f32x4*>(p.ws_o + (s * rows + row) * D + 4 * c);
-    }
-  }
-  const int64_t tok = row / p.H;
-  const int h = (int)(row % p.H);
-  const float inv = p.dyn ? (l > 0.f ? 1.f / l : 0.f) : 1.f / fmaxf(l, p.l_eps);
-  if constexpr (FP8) {
-    const int b = ragged_seq_of(p.cu_q, p.B, p.total_q, tok);
-    acc *= inv * p.v_scale[(int64_t)b * p.vs_b + (int64_t)(h / p.G) * p.vs_h];
-  } else {
-    acc *= inv;
-  }
-  char* dst = p.o.p + (int64_t)h * p.o.sh + tok * p.o.sn + 4 * c * ES;
-  if constexpr (ES == 4) {
-    *reinterpret_cast<f32x4*>(dst) = acc;
-  } else {
-    *reinterpret_cast<u32x2*>(dst) = u32x2{Traits<T>::pack2(acc[0], acc[1]), Traits<T>::pack2(acc[2], acc[3])};
-  }
+  decode_combine_body<T, D, FP8, true, false>(p, DecodeLseOut{});
+}
+template <typename T, int D, bool FP8>
+__global__ __launch_bounds__(256) void decode_combine_lse_ragged_kernel(DecodeRaggedParams p, DecodeLseOut lo) {
+  decode_combine_body<T, D, FP8, true, true>(p, lo);
 }
 
 // kv_append_kernel / kv_append_fp8_kernel for a ragged step: one thread per 16 bytes written of packed row `tok` of kn / vn ([total_q, Hk,
@@ -881,6 +873,51 @@ hipError_t launch_decode_combine_ragged(int dtype, int D, bool fp8, const Decode
       else return hipErrorInvalidValue;
     } else {
       hipLaunchKernelGGL((decode_combine_ragged_kernel<T, DD, false>), dim3((unsigned)blocks_of(threads)), dim3(256), 0, s, p);
+    }
+    return hipGetLastError();
+  });
+}
+
+// ---- the combines that also write the rows' log-sum-exp (fcsa_forward_kvcache_lse): the grids of their twins ----
+hipError_t launch_decode_combine_lse(int dtype, int D, const DecodeParams& p, const DecodeLseOut& lse, hipStream_t s) {
+  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    const int64_t threads = (int64_t)p.B * p.H * p.N * (DD / 4);
+    if (threads <= 0) return hipSuccess;
+    hipLaunchKernelGGL((decode_combine_lse_kernel<T, DD>), dim3((unsigned)blocks_of(threads)), dim3(256), 0, s, p, lse);
+    return hipGetLastError();
+  });
+}
+
+hipError_t launch_decode_combine_lse_fp8(int dtype, int D, const DecodeFp8Params& p, const DecodeLseOut& lse, hipStream_t s) {
+  if (dtype != 1 && dtype != 2) return hipErrorInvalidValue;
+  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    if constexpr (Traits<T>::ES == 2) {
+      const int64_t threads = (int64_t)p.B * p.H * p.N * (DD / 4);
+      if (threads <= 0) return hipSuccess;
+      hipLaunchKernelGGL((decode_combine_lse_fp8_kernel<T, DD>), dim3((unsigned)blocks_of(threads)), dim3(256), 0, s, p, lse);
+      return hipGetLastError();
+    } else {
+      return hipErrorInvalidValue;
+    }
+  });
+}
+
+hipError_t launch_decode_combine_lse_ragged(int dtype, int D, bool fp8, const DecodeRaggedParams& p, const DecodeLseOut& lse, hipStream_t s) {
+  if (fp8 && dtype != 1 && dtype != 2) return hipErrorInvalidValue;
+  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    const int64_t threads = (int64_t)p.total_q * p.H * (DD / 4);
+    if (threads <= 0) return hipSuccess;
+    if (fp8) {
+      if constexpr (Traits<T>::ES == 2) hipLaunchKernelGGL((decode_combine_lse_ragged_kernel<T, DD, true>), dim3((unsigned)blocks_of(threads)), dim3(256), 0, s, p, lse);
+      else return hipErrorInvalidValue;
+    } else {
+      hipLaunchKernelGGL((decode_combine_lse_ragged_kernel<T, DD, false>), dim3((unsigned)blocks_of(threads)), dim3(256), 0, s, p, lse);
     }
     return hipGetLastError();
   });

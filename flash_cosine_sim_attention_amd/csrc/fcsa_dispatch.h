@@ -7,6 +7,7 @@
 #pragma once
 #include <stdint.h>
 #include <algorithm>
+#include <cmath>
 
 #include "../../include/fcsa.h"
 #ifdef FCSA_VAR_SPLIT_ENV
@@ -277,6 +278,44 @@ constexpr bool ragged_tile(const int32_t* cu, int B, int64_t total, int G, int64
   len = (int)(en - st);
   rt = (int)t;
   return t >= 0 && t < ((int64_t)G * (en - st) + kDecodeRows - 1) / kDecodeRows;
+}
+
+// ---- log-sum-exp of a decoded row, and merging attention states (fcsa_forward_kvcache_lse, fcsa_merge_states) --------------------------
+// The two functions below call expf / log / log2, which are no constant expressions: they are host functions for the C++ compiler
+// (tests/native/merge_states_check.cpp) and host + device functions for hipcc (decode_combine_lse*, merge_states_kernel).
+#if defined(__HIPCC__)
+#define FCSA_HOST_DEVICE __host__ __device__
+#else
+#define FCSA_HOST_DEVICE
+#endif
+constexpr int kMergeMaxStates = 8;
+// Natural-log LSE of a row from what the decode combine holds: M (the row's exponent reference in log2 units: its reconciled max, or the
+// constant shift) and l = sum 2^(s - M) over the visible keys, UNCLAMPED.  sum exp(s_nat) = 2^M * l, so lse = ln 2 * (M + log2 l); a row
+// without a visible key (M == -inf, or l == 0 under the constant shift) is -inf exactly, never NaN.  Once per row, so in double.
+FCSA_HOST_DEVICE inline float decode_row_lse(float M, float l) {
+  if (!(M > -INFINITY) || !(l > 0.f)) return -INFINITY;
+  return (float)(0.6931471805599453 * ((double)M + log2((double)l)));
+}
+// Weights of S attention states of one row (S <= kMergeMaxStates): M = max_s lse[s]; every state empty (M == -inf): all weights 0,
+// lse_out = -inf, returns 0.  Else w[s] = exp(lse[s] - M) -- exactly 0 for an empty state -- and lse_out = M + log(W) with W = sum_s w[s],
+// which is returned.  The caller forms o = (sum over the states with w[s] != 0 of w[s] * o_s) / W: a state of weight 0 is SKIPPED, not
+// multiplied, so whatever its o_s holds (NaN included) cannot leak.  One state, or one state beside empty ones: w = 1, W = 1, so o and lse
+// come back bit for bit.
+FCSA_HOST_DEVICE inline float merge_row_weights(const float* lse, int S, float* w, float& lse_out) {
+  float M = -INFINITY;
+  for (int s = 0; s < S; ++s) M = lse[s] > M ? lse[s] : M;
+  if (!(M > -INFINITY)) {
+    for (int s = 0; s < S; ++s) w[s] = 0.f;
+    lse_out = -INFINITY;
+    return 0.f;
+  }
+  float W = 0.f;
+  for (int s = 0; s < S; ++s) {
+    w[s] = lse[s] > -INFINITY ? expf(lse[s] - M) : 0.f;
+    W += w[s];
+  }
+  lse_out = M + logf(W);
+  return W;
 }
 
 // workgroups of `tile`-position tiles over `len` positions for `batch_heads` (batch x heads)

@@ -165,6 +165,27 @@ hipError_t launch_decode_combine_fp8(int dtype, int D, const DecodeFp8Params& p,
 hipError_t launch_kv_append_ragged(int dtype, int D, bool fp8, const DecodeRaggedParams& p, hipStream_t s);
 hipError_t launch_decode_ragged(int dtype, int D, bool fp8, const DecodeRaggedParams& p, hipStream_t s);
 hipError_t launch_decode_combine_ragged(int dtype, int D, bool fp8, const DecodeRaggedParams& p, hipStream_t s);
+// The rows' log-sum-exp as a second result of a decode call (fcsa_forward_kvcache_lse): a second kernel argument of the combine entry
+// points that write it (decode_combine_lse*_kernel), so that the parameter blocks above -- and the kernels launched with them alone --
+// are what they were.  ELEMENT strides: [b, h, i] at b * sb + h * sh + i * sn (ragged: [tok, h] at h * sh + tok * sn).
+struct DecodeLseOut {
+  float*  lse;
+  int64_t sb, sh, sn;
+};
+hipError_t launch_decode_combine_lse(int dtype, int D, const DecodeParams& p, const DecodeLseOut& lse, hipStream_t s);
+hipError_t launch_decode_combine_lse_fp8(int dtype, int D, const DecodeFp8Params& p, const DecodeLseOut& lse, hipStream_t s);
+hipError_t launch_decode_combine_lse_ragged(int dtype, int D, bool fp8, const DecodeRaggedParams& p, const DecodeLseOut& lse, hipStream_t s);
+
+// Merging attention states (fcsa_merge_states, csrc/fcsa_merge.hip): S states (o_s, lse_s) of the rows [n0, n1, n2] -> (o, lse).  o views
+// carry BYTE strides, lse views ELEMENT strides.
+struct MergeParams {
+  View         o_in[8];
+  DecodeLseOut lse_in[8];
+  View         o;
+  DecodeLseOut lse;
+  int n0, n1, n2, D, S;
+};
+hipError_t launch_merge_states(int dtype, const MergeParams& p, hipStream_t s);
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE property of a kernel: raise it once per (instantiation, device).
 // `done` is the instantiation's bit mask of devices that have it (one static per launcher); thread safe, idempotent.

@@ -55,6 +55,10 @@ struct Abi {
       &fcsa_forward_kvcache_varlen;
   size_t (*forward_kvcache_varlen_ws)(const fcsa_problem*, const fcsa_kvcache*, const fcsa_varlen*, const fcsa_kvcache_quant*, const fcsa_window*) =
       &fcsa_forward_kvcache_varlen_workspace_bytes;
+  // the decode calls with the rows' log-sum-exp, and merging attention states: likewise
+  int (*forward_kvcache_lse)(const fcsa_forward_args*, const fcsa_kvcache*, const fcsa_varlen*, const fcsa_kvcache_quant*, const fcsa_window*,
+                             const fcsa_lse_out*) = &fcsa_forward_kvcache_lse;
+  int (*merge_states)(const fcsa_merge_args*) = &fcsa_merge_states;
 } g_abi;
 
 using at::Tensor;
@@ -768,8 +772,10 @@ Tensor varlen_window_attention_autograd(const Tensor& q, const Tensor& k, const 
 Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const optional<Tensor>& k_new, const optional<Tensor>& v_new,
                             const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table, int64_t max_seqlen_k, double scale, bool causal,
                             bool l2norm_qk, int64_t groups, const fcsa_window* win, const Tensor* k_scale = nullptr, const Tensor* v_scale = nullptr,
-                            const Tensor* cu_q = nullptr, int64_t max_seqlen_q = 0) {
+                            const Tensor* cu_q = nullptr, int64_t max_seqlen_q = 0, Tensor* lse_out = nullptr) {
   const bool ragged = cu_q != nullptr;
+  TORCH_CHECK(lse_out == nullptr || g_abi.forward_kvcache_lse != nullptr,
+              "return_lse: the loaded libfcsa_hip.so does not export fcsa_forward_kvcache_lse");
   TORCH_CHECK(!ragged || (g_abi.forward_kvcache_varlen != nullptr && g_abi.forward_kvcache_varlen_ws != nullptr),
               "flash_cosine_sim_attention_varlen_with_kvcache: the loaded libfcsa_hip.so does not export fcsa_forward_kvcache_varlen");
   const bool fp8 = k_scale != nullptr;      // an e4m3fn cache with its two scale tensors (kvcache_fp8_forward)
@@ -921,6 +927,17 @@ Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor
     a.workspace_bytes = wsb;
   }
   a.stream = stream_of(q);
+  if (lse_out != nullptr) {
+    // float32 [B, H, N], or [total_q, H] for a ragged step; the workspace is that of the call without it
+    *lse_out = ragged ? at::empty({N, H}, q.options().dtype(at::kFloat)) : at::empty({B, H, N}, q.options().dtype(at::kFloat));
+    fcsa_lse_out lo;
+    lo.lse = lse_out->data_ptr<float>();
+    lo.stride0 = ragged ? 0 : lse_out->stride(0);
+    lo.stride1 = lse_out->stride(1);
+    lo.stride2 = ragged ? lse_out->stride(0) : lse_out->stride(2);
+    check(g_abi.forward_kvcache_lse(&a, &kv, ragged ? &seqs : nullptr, fp8 ? &qz : nullptr, win, &lo), "fcsa_forward_kvcache_lse");
+    return o;
+  }
   if (ragged) check(g_abi.forward_kvcache_varlen(&a, &kv, &seqs, fp8 ? &qz : nullptr, win), "fcsa_forward_kvcache_varlen");
   else if (fp8) check(g_abi.forward_kvcache_quant(&a, &kv, &qz, win), "fcsa_forward_kvcache_quant");
   else if (win != nullptr) check(g_abi.forward_kvcache_window(&a, &kv, win), "fcsa_forward_kvcache_window");
@@ -961,6 +978,86 @@ Tensor kvcache_varlen_forward(const Tensor& q, const Tensor& k_cache, const Tens
                               v_scale.has_value() ? &*v_scale : nullptr, &cu_seqlens_q, max_seqlen_q);
 }
 
+// Every decode route with the rows' log-sum-exp as a second result (return_lse=True): cu_seqlens_q given: a ragged step; k_scale / v_scale
+// given: an e4m3fn cache (its codes as uint8 tensors); window sides of (-1, -1): no window.  o and the caches are what the op of that
+// route gives, bit for bit; lse is float32 [B, H, N] ([total_q, H] for a ragged step).
+std::tuple<Tensor, Tensor> kvcache_lse_forward(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const optional<Tensor>& cu_seqlens_q,
+                                               const optional<Tensor>& k_new, const optional<Tensor>& v_new, const optional<Tensor>& cache_seqlens,
+                                               const optional<Tensor>& block_table, const optional<Tensor>& k_scale, const optional<Tensor>& v_scale,
+                                               int64_t max_seqlen_q, int64_t max_seqlen_k, double scale, bool causal, bool l2norm_qk, int64_t groups,
+                                               int64_t left, int64_t right) {
+  TORCH_CHECK_VALUE(k_scale.has_value() == v_scale.has_value(), "k_scale and v_scale must be given together");
+  const bool windowed = !(left == -1 && right == -1);
+  fcsa_window w;
+  if (windowed) w = Win(left, right).w;
+  Tensor lse;
+  Tensor o = kvcache_forward_impl(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups,
+                                  windowed ? &w : nullptr, k_scale.has_value() ? &*k_scale : nullptr, v_scale.has_value() ? &*v_scale : nullptr,
+                                  cu_seqlens_q.has_value() ? &*cu_seqlens_q : nullptr, max_seqlen_q, &lse);
+  return {o, lse};
+}
+
+// merge_attention_states: S <= 8 states (o_s [..., D] 4-D or [total_q, H, D], lse_s float32 without the feature dim) -> fresh contiguous
+// (o, lse).  The states are read in place through their strides (feature dim contiguous, rows 16-byte aligned; anything else is copied).
+std::tuple<Tensor, Tensor> merge_states(at::TensorList os, at::TensorList lses) {
+  TORCH_CHECK(g_abi.merge_states != nullptr, "merge_attention_states: the loaded libfcsa_hip.so does not export fcsa_merge_states");
+  const int64_t S = (int64_t)os.size();
+  TORCH_CHECK_VALUE(S >= 1 && S <= FCSA_MERGE_MAX_STATES && (int64_t)lses.size() == S,
+                    "merge_states takes 1 to ", FCSA_MERGE_MAX_STATES, " states and as many lses, got ", S, " and ", lses.size());
+  const Tensor& o0 = os[0];
+  TORCH_CHECK(o0.is_cuda(), "merge_states: GPU tensors only (HIP kernels only)");
+  TORCH_CHECK_VALUE(o0.dim() == 3 || o0.dim() == 4, "merge_states: os must be 4-D [..., D] or 3-D [total_q, H, D], got ", o0.sizes());
+  const int64_t D = o0.size(-1);
+  const int64_t per16 = 16 / o0.element_size();      // rows are whole 16-byte chunks
+  TORCH_CHECK_VALUE(D >= per16 && D % per16 == 0, "merge_states: the feature dim (", D, ") must be a positive multiple of ", per16);
+  c10::DeviceGuard guard(o0.device());
+  fcsa_merge_args a;
+  std::memset(&a, 0, sizeof(a));
+  a.dtype = dtype_code(o0.scalar_type());
+  const bool packed = o0.dim() == 3;
+  for (int64_t d = 0; d + 1 < o0.dim(); ++d) TORCH_CHECK_VALUE(o0.size(d) <= INT32_MAX, "merge_states: sizes must stay below 2^31");
+  a.size0 = packed ? 1 : (int32_t)o0.size(0);
+  a.size1 = (int32_t)o0.size(packed ? 0 : 1);
+  a.size2 = (int32_t)o0.size(packed ? 1 : 2);
+  a.dim_head = (int32_t)D;
+  a.states = (int32_t)S;
+  std::vector<Tensor> keep;
+  keep.reserve((size_t)S);
+  const auto lead = o0.sizes().slice(0, o0.dim() - 1);
+  for (int64_t s = 0; s < S; ++s) {
+    const Tensor& o = os[s];
+    const Tensor& l = lses[s];
+    TORCH_CHECK_VALUE(o.device() == o0.device() && l.device() == o0.device(), "merge_states: every tensor must live on the first one's GPU");
+    TORCH_CHECK_TYPE(o.scalar_type() == o0.scalar_type(), "merge_states: os must share a dtype, got ", o0.scalar_type(), " and ", o.scalar_type());
+    TORCH_CHECK_VALUE(o.sizes() == o0.sizes(), "merge_states: os must share a shape, got ", o0.sizes(), " and ", o.sizes());
+    TORCH_CHECK_TYPE(l.scalar_type() == at::kFloat, "merge_states: lses must be float32, got ", l.scalar_type());
+    TORCH_CHECK_VALUE(l.sizes() == lead, "merge_states: an lse must have its o's shape without the feature dim, ", lead, ", got ", l.sizes());
+    keep.push_back(prep(o));
+    const Tensor& oc = keep.back();
+    a.o_in[s].ptr = oc.data_ptr();
+    a.o_in[s].stride0 = packed ? 0 : oc.stride(0);
+    a.o_in[s].stride1 = oc.stride(packed ? 0 : 1);
+    a.o_in[s].stride2 = oc.stride(packed ? 1 : 2);
+    a.lse_in[s].lse = l.data_ptr<float>();
+    a.lse_in[s].stride0 = packed ? 0 : l.stride(0);
+    a.lse_in[s].stride1 = l.stride(packed ? 0 : 1);
+    a.lse_in[s].stride2 = l.stride(packed ? 1 : 2);
+  }
+  Tensor o = at::empty(o0.sizes(), o0.options());
+  Tensor lse = at::empty(lead, o0.options().dtype(at::kFloat));
+  a.o.ptr = o.data_ptr();
+  a.o.stride0 = packed ? 0 : o.stride(0);
+  a.o.stride1 = o.stride(packed ? 0 : 1);
+  a.o.stride2 = o.stride(packed ? 1 : 2);
+  a.lse.lse = lse.data_ptr<float>();
+  a.lse.stride0 = packed ? 0 : lse.stride(0);
+  a.lse.stride1 = lse.stride(packed ? 0 : 1);
+  a.lse.stride2 = lse.stride(packed ? 1 : 2);
+  a.stream = stream_of(o0);
+  if (o.numel() > 0) check(g_abi.merge_states(&a), "fcsa_merge_states");
+  return {o, lse};
+}
+
 }  // namespace
 
 // Measurement hook: read (and reset) the host-time counters above.
@@ -994,6 +1091,8 @@ extern "C" int fcsa_torch_use_library(const char* path) {
   a.forward_kvcache_quant_ws = reinterpret_cast<decltype(a.forward_kvcache_quant_ws)>(dlsym(h, "fcsa_forward_kvcache_quant_workspace_bytes"));
   a.forward_kvcache_varlen = reinterpret_cast<decltype(a.forward_kvcache_varlen)>(dlsym(h, "fcsa_forward_kvcache_varlen"));
   a.forward_kvcache_varlen_ws = reinterpret_cast<decltype(a.forward_kvcache_varlen_ws)>(dlsym(h, "fcsa_forward_kvcache_varlen_workspace_bytes"));
+  a.forward_kvcache_lse = reinterpret_cast<decltype(a.forward_kvcache_lse)>(dlsym(h, "fcsa_forward_kvcache_lse"));
+  a.merge_states = reinterpret_cast<decltype(a.merge_states)>(dlsym(h, "fcsa_merge_states"));
   if (!a.forward || !a.backward || !a.forward_ws || !a.backward_ws || !a.needs_qn || !a.last_error) { dlclose(h); return -2; }
   // Only libraries of THIS ABI: the binding allocates for the struct layouts and buffer contracts of include/fcsa.h as compiled in
   // (e.g. ABI 3 writes d_bias once in the bias dtype into an uninitialised buffer; an ABI-2 library would accumulate float32 into
@@ -1049,6 +1148,12 @@ TORCH_LIBRARY(fcsa, m) {
   m.def("kvcache_varlen_forward(Tensor q, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor cu_seqlens_q, Tensor? k_new, Tensor? v_new, "
         "Tensor? cache_seqlens, Tensor? block_table, Tensor? k_scale, Tensor? v_scale, int max_seqlen_q, int max_seqlen_k, float scale, "
         "bool causal, bool l2norm_qk, int groups, int window_left, int window_right) -> Tensor");
+  // every decode route with the rows' log-sum-exp (float32 [B, H, N]; ragged: [total_q, H]) as a second result
+  m.def("kvcache_lse_forward(Tensor q, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor? cu_seqlens_q, Tensor? k_new, Tensor? v_new, "
+        "Tensor? cache_seqlens, Tensor? block_table, Tensor? k_scale, Tensor? v_scale, int max_seqlen_q, int max_seqlen_k, float scale, "
+        "bool causal, bool l2norm_qk, int groups, int window_left, int window_right) -> (Tensor, Tensor)");
+  // attention states over disjoint key sets of the same queries -> the state over the union
+  m.def("merge_states(Tensor[] os, Tensor[] lses) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(fcsa, CUDA, m) {       // ROCm builds of PyTorch dispatch HIP tensors under the CUDA key
@@ -1068,6 +1173,8 @@ TORCH_LIBRARY_IMPL(fcsa, CUDA, m) {       // ROCm builds of PyTorch dispatch HIP
   m.impl("kvcache_window_forward", &kvcache_window_forward);
   m.impl("kvcache_fp8_forward", &kvcache_fp8_forward);
   m.impl("kvcache_varlen_forward", &kvcache_varlen_forward);
+  m.impl("kvcache_lse_forward", &kvcache_lse_forward);
+  m.impl("merge_states", &merge_states);
 }
 
 TORCH_LIBRARY_IMPL(fcsa, Autograd, m) {

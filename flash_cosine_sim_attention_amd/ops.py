@@ -270,9 +270,16 @@ def _cache_scale(name, s, B, Hk, device):
     return torch.full((), float(s), dtype=torch.float32, device=device)
 
 
+def _check_return_lse(return_lse):
+    """return_lse sits where a positional window_size used to land (window_size stays the last parameter): anything but a bool is refused
+    rather than read as a flag."""
+    if not isinstance(return_lse, bool):
+        raise TypeError(f"return_lse must be a bool, got {return_lse!r} (pass window_size by keyword)")
+
+
 def flash_cosine_sim_attention_with_kvcache(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlens=None, block_table=None,
                                             max_seqlen_k=None, scale=8, groups=1, causal=False, l2norm_qk=True, k_scale=None, v_scale=None,
-                                            window_size=(-1, -1)):
+                                            return_lse=False, window_size=(-1, -1)):
     """Forward-only attention of new queries against a key/value cache, with an optional in-place append.
 
     q [B, H, N, D] (N = 1: plain decode; a few: speculative or chunked steps).  k_cache, v_cache: [B, Hk, capacity, D] or, with a
@@ -296,7 +303,13 @@ def flash_cosine_sim_attention_with_kvcache(q, k_cache, v_cache, k_new=None, v_n
     and > 0; device tensors are trusted (and with device cache_seqlens and max_seqlen_k given the call does not synchronise).  The append
     quantises: code = e4m3_rne(clamp(float(x) / scale, -448, 448)), NaN stays NaN.  Choosing scales: for V the per-head amax / 448 uses
     the whole code range; for K under l2norm_qk the scale cancels (the keys are normalised as they are read), so any value that keeps
-    K's codes in range serves -- amax / 448 again, or 1.0 for keys of ordinary size; without l2norm_qk choose it as for V."""
+    K's codes in range serves -- amax / 448 again, or 1.0 for keys of ordinary size; without l2norm_qk choose it as for V.
+    return_lse=True: returns (o, lse).  lse is float32 [B, H, N]: the natural log of the sum over the row's visible keys of exp(logit), the
+    logit being scale * (sum over the groups of q^ . k^), or scale * q . k without l2norm_qk; with an fp8 cache k_scale is inside it and
+    v_scale is not.  A row without a visible key has lse = -inf (and o = 0).  o and the caches are bit for bit those of the call without
+    it.  (o, lse) is an attention state: `merge_attention_states` combines the states of the same queries over disjoint sets of keys.
+    return_lse must be a bool and window_size is best passed by keyword: return_lse precedes it in the signature."""
+    _check_return_lse(return_lse)
     window = _window(window_size)
     fp8_types = tuple(getattr(torch, n) for n in ("float8_e4m3fn", "float8_e4m3fnuz", "float8_e5m2", "float8_e5m2fnuz") if hasattr(torch, n))
     fp8 = k_cache.dtype in fp8_types or v_cache.dtype in fp8_types
@@ -377,7 +390,8 @@ def flash_cosine_sim_attention_with_kvcache(q, k_cache, v_cache, k_new=None, v_n
         detach = lambda t: None if t is None else t.detach()          # (grad mode is off here, or nothing requires grad)
         quant = dict(k_scale=k_scale.expand(B, Hk), v_scale=v_scale.expand(B, Hk)) if fp8 else {}
         return _cpu.attention_forward_kvcache_cpu(q.detach(), k_cache, v_cache, detach(k_new), detach(v_new), lens, block_table,
-                                                  scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, window_size=window, **quant)
+                                                  scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, window_size=window,
+                                                  return_lse=bool(return_lse), **quant)
     if isinstance(cache_seqlens, int):
         cache_seqlens = torch.full((B,), cache_seqlens, dtype=torch.int32, device=q.device)
     elif cache_seqlens is not None:
@@ -385,6 +399,12 @@ def flash_cosine_sim_attention_with_kvcache(q, k_cache, v_cache, k_new=None, v_n
     if block_table is not None:
         block_table = block_table.to(q.device, non_blocking=True)
     max_k = capacity if max_seqlen_k is None else min(int(max_seqlen_k), capacity)
+    if return_lse:      # every route through one op: the same append and decode launches, a combine that also writes the lse
+        if fp8:
+            k_cache, v_cache = k_cache.view(torch.uint8), v_cache.view(torch.uint8)
+        o, lse = _torch_ops.load().kvcache_lse_forward(q, k_cache, v_cache, None, k_new, v_new, cache_seqlens, block_table, k_scale, v_scale, 0,
+                                                       int(max_k), float(scale), bool(causal), bool(l2norm_qk), int(groups), window[0], window[1])
+        return o, lse
     if fp8:
         # (the op takes the codes as bytes: same storage, so the append lands in the caller's caches)
         return _torch_ops.load().kvcache_fp8_forward(q, k_cache.view(torch.uint8), v_cache.view(torch.uint8), k_new, v_new, cache_seqlens, block_table, k_scale, v_scale,
@@ -398,7 +418,7 @@ def flash_cosine_sim_attention_with_kvcache(q, k_cache, v_cache, k_new=None, v_n
 
 def flash_cosine_sim_attention_varlen_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new=None, v_new=None, cache_seqlens=None,
                                                    block_table=None, max_seqlen_q=None, max_seqlen_k=None, scale=8, groups=1, causal=False,
-                                                   l2norm_qk=True, k_scale=None, v_scale=None, window_size=(-1, -1)):
+                                                   l2norm_qk=True, k_scale=None, v_scale=None, return_lse=False, window_size=(-1, -1)):
     """A ragged decode step: `flash_cosine_sim_attention_with_kvcache` with a per-sequence number of queries, in one call.
 
     The step of a continuous-batching engine is never rectangular -- plain decodes bring 1 token, speculative sequences a few, a prompt
@@ -419,7 +439,9 @@ def flash_cosine_sim_attention_varlen_with_kvcache(q, k_cache, v_cache, cu_seqle
     a step can be captured in a HIP graph.  CPU tensors take the forward-only path of `cpu.py` (host tables).
     The launch has one row-tile slot per 16 rows of G * N_b (about G * total_q / 16 + B per K/V head, whatever the longest sequence is), and
     every row tile re-reads and re-normalises its keys: this is the call for steps of one to a few dozen tokens per sequence.  Long prompt
-    chunks work, at the decode kernel's efficiency."""
+    chunks work, at the decode kernel's efficiency.
+    return_lse=True: returns (o, lse) with lse float32 [total_q, H], as in `flash_cosine_sim_attention_with_kvcache`."""
+    _check_return_lse(return_lse)
     window = _window(window_size)
     fp8_types = tuple(getattr(torch, n) for n in ("float8_e4m3fn", "float8_e4m3fnuz", "float8_e5m2", "float8_e5m2fnuz") if hasattr(torch, n))
     fp8 = k_cache.dtype in fp8_types or v_cache.dtype in fp8_types
@@ -509,7 +531,7 @@ def flash_cosine_sim_attention_varlen_with_kvcache(q, k_cache, v_cache, cu_seqle
         quant = dict(k_scale=k_scale.expand(B, Hk), v_scale=v_scale.expand(B, Hk)) if fp8 else {}
         return _cpu.attention_forward_kvcache_varlen_cpu(q.detach(), k_cache, v_cache, cu_seqlens_q, detach(k_new), detach(v_new), lens,
                                                          block_table, scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk,
-                                                         window_size=window, **quant)
+                                                         window_size=window, return_lse=bool(return_lse), **quant)
     cu_q = cu_seqlens_q.to(q.device, non_blocking=True)
     if isinstance(cache_seqlens, int):
         cache_seqlens = torch.full((B,), cache_seqlens, dtype=torch.int32, device=q.device)
@@ -521,6 +543,173 @@ def flash_cosine_sim_attention_varlen_with_kvcache(q, k_cache, v_cache, cu_seqle
     max_k = capacity if max_seqlen_k is None else min(int(max_seqlen_k), capacity)
     if fp8:      # (the op takes the codes as bytes: same storage, so the append lands in the caller's caches)
         k_cache, v_cache = k_cache.view(torch.uint8), v_cache.view(torch.uint8)
+    if return_lse:
+        o, lse = _torch_ops.load().kvcache_lse_forward(q, k_cache, v_cache, cu_q, k_new, v_new, cache_seqlens, block_table, k_scale, v_scale,
+                                                       int(max_q), int(max_k), float(scale), bool(causal), bool(l2norm_qk), int(groups),
+                                                       window[0], window[1])
+        return o, lse
     return _torch_ops.load().kvcache_varlen_forward(q, k_cache, v_cache, cu_q, k_new, v_new, cache_seqlens, block_table, k_scale, v_scale,
                                                     int(max_q), int(max_k), float(scale), bool(causal), bool(l2norm_qk), int(groups),
                                                     window[0], window[1])
+
+
+# ---------------------------------------------------------------------------------------------
+# attention states: merging the results of the same queries over disjoint sets of keys, and the shared-prefix decode step built on it
+# ---------------------------------------------------------------------------------------------
+
+MERGE_MAX_STATES = 8
+
+
+def merge_attention_states(os, lses):
+    """Merges S attention states (o_s, lse_s) of the same queries, each over its own set of keys, into the state over all the keys.
+
+    os: a sequence of 1 <= S <= 8 tensors of one shape and dtype (float16, bfloat16 or float32), 4-D [..., D] or packed [total_q, H, D];
+    the feature dim a multiple of 4 (float32) or 8 (16-bit); any strides with the feature dim contiguous and rows 16-byte aligned are read
+    in place (other layouts are copied).  lses: the matching
+    float32 tensors without the feature dim, any strides -- what `return_lse=True` of the cache calls returns.  Returns (o, lse), freshly
+    allocated and contiguous.  Per row, in float32: M = max_s lse_s; w_s = exp(lse_s - M); W = sum_s w_s; o = (sum_s w_s * o_s) / W,
+    rounded once; lse = M + log(W).  A state with lse_s = -inf (no visible key) contributes exactly nothing whatever its o_s holds, and
+    when every state is empty o = 0 and lse = -inf.  Deterministic.  +inf or NaN LSEs are not supported.
+    More than 8 states: merge in two steps (the result is a state again).  GPU tensors run one launch of the merge kernel; CPU tensors
+    take the path of `cpu.py`.  Forward only."""
+    os, lses = list(os), list(lses)
+    if not os or len(os) != len(lses):
+        raise ValueError(f"merge_attention_states takes as many lses as os and at least one state, got {len(os)} and {len(lses)}")
+    if len(os) > MERGE_MAX_STATES:
+        raise ValueError(f"merge_attention_states merges at most {MERGE_MAX_STATES} states in one call, got {len(os)}: merge in two steps "
+                         "(the result of a merge is a state again)")
+    o0 = os[0]
+    if not isinstance(o0, torch.Tensor) or o0.dim() not in (3, 4):
+        raise ValueError("os must be 4-D [..., D] or packed 3-D [total_q, H, D] tensors")
+    if o0.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise TypeError(f"os must be float32, float16 or bfloat16, got {o0.dtype}")
+    per16 = 16 // o0.element_size()                    # rows are whole 16-byte chunks: 4 float32 or 8 16-bit features
+    if o0.shape[-1] < per16 or o0.shape[-1] % per16:
+        raise ValueError(f"the feature dim must be a positive multiple of {per16} for {o0.dtype}, got {o0.shape[-1]}")
+    for s, (o, l) in enumerate(zip(os, lses)):
+        if not isinstance(o, torch.Tensor) or not isinstance(l, torch.Tensor):
+            raise TypeError("os and lses must be tensors")
+        if o.dtype != o0.dtype:
+            raise TypeError(f"os must share a dtype, got {o0.dtype} and {o.dtype} (state {s})")
+        if o.shape != o0.shape:
+            raise ValueError(f"os must share a shape, got {tuple(o0.shape)} and {tuple(o.shape)} (state {s})")
+        if l.dtype != torch.float32:
+            raise TypeError(f"lses must be float32, got {l.dtype} (state {s})")
+        if l.shape != o0.shape[:-1]:
+            raise ValueError(f"lse {s} must have the shape of its o without the feature dim, {tuple(o0.shape[:-1])}, got {tuple(l.shape)}")
+        if o.device != o0.device or l.device != o0.device:
+            raise ValueError("os and lses must live on one device")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in os + lses):
+        raise RuntimeError("merge_attention_states is forward-only: run it under torch.no_grad()")
+    if o0.device.type == "cpu":
+        return _cpu.merge_attention_states_cpu(os, lses)
+    o, lse = _torch_ops.load().merge_states(os, lses)
+    return o, lse
+
+
+def flash_cosine_sim_attention_with_shared_prefix(q, prefix_k_cache, prefix_v_cache, k_cache, v_cache, prefix_len=None, prefix_block_table=None,
+                                                  cu_seqlens_q=None, k_new=None, v_new=None, cache_seqlens=None, block_table=None,
+                                                  max_seqlen_q=None, max_seqlen_k=None, scale=8, groups=1, causal=False, l2norm_qk=True,
+                                                  k_scale=None, v_scale=None, prefix_k_scale=None, prefix_v_scale=None, return_lse=False,
+                                                  window_size=(-1, -1)):
+    """A decode step of a batch whose sequences share a prefix (a system prompt) that is cached ONCE ("cascade" decoding).
+
+    Every sequence's keys are the P = prefix_len shared positions followed by its own L_b cached positions (after the append), and its
+    queries are the last N_b of those P + L_b positions.  The result is what `flash_cosine_sim_attention_with_kvcache` gives on caches that
+    each hold a copy of the prefix in front of the sequence's own positions -- or, with cu_seqlens_q (q packed [total_q, H, D]), what
+    `flash_cosine_sim_attention_varlen_with_kvcache` gives -- without the copies, and with every prefix byte read and normalised once per
+    16 query rows of the whole BATCH instead of once per sequence.
+    It is three phases of existing pieces: the prefix phase, one B = 1 cache call over all the batch's query rows as one sequence
+    (non-causal: every prefix key precedes every query); the suffix phase, the ordinary call on the per-sequence caches, append included;
+    and one `merge_attention_states` of the two (o, lse) pairs, which reads the prefix phase's result through strided views in place.
+    prefix_k_cache, prefix_v_cache: what a B = 1 cache call takes: [1, Hk, capacity, D], or a paged pool [num_blocks, Hk, page_size, D]
+    with prefix_block_table int32 [1, n] -- the pool may be the very tensors passed as k_cache / v_cache.  Nothing is ever appended to the
+    prefix.  prefix_len: an int, or a one-element int32 tensor (device: the call does not read it on the host); None: the whole prefix
+    capacity.  P == 0 (known on the host) returns the suffix call's result bit for bit.  fp8 prefix caches take prefix_k_scale /
+    prefix_v_scale (a float, or float32 of shape [] or [Hk]).
+    q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q, max_seqlen_k, scale, groups, causal,
+    l2norm_qk, k_scale, v_scale: those of the two cache functions, for the sequences' own caches; cache_seqlens counts own positions only.
+    causal is bottom-right against P + L_b.  It requires N_b <= L_b + 1 for every sequence: every query sits behind the prefix, as it does
+    whenever the step's tokens are appended in this call (k_new) or were before (N_b = L_b + 1: the first query sees the prefix alone).  A
+    query placed INSIDE the prefix would need a causal cut of the prefix that the one-sequence prefix phase cannot express; host tables are
+    checked for it, device tables are trusted (such a row would see the whole prefix).
+    window_size other than (-1, -1) raises ValueError: a window that reaches into the prefix needs a per-sequence alignment against P +
+    L_b that the B = 1 prefix call cannot express.
+    With a device prefix_len, device tables and max_seqlen_k given, the call does not synchronise and can be captured in a HIP graph; all
+    launches go to the current stream, one after another.  Returns o shaped like q, or (o, lse) with return_lse=True.  Forward only."""
+    _check_return_lse(return_lse)
+    if _window(window_size) != (-1, -1):
+        raise ValueError("flash_cosine_sim_attention_with_shared_prefix takes no window_size: a window that reaches into the shared prefix "
+                         "needs a per-sequence alignment against prefix_len + L_b, which the single B = 1 prefix call cannot express")
+    ragged = cu_seqlens_q is not None
+    for name, t in (("prefix_k_cache", prefix_k_cache), ("prefix_v_cache", prefix_v_cache)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError(f"{name} must be a 4-D tensor ([1, Hk, capacity, D], or a paged pool with prefix_block_table)")
+    if prefix_block_table is not None:
+        if not isinstance(prefix_block_table, torch.Tensor) or prefix_block_table.dtype != torch.int32 or prefix_block_table.dim() != 2 \
+                or prefix_block_table.shape[0] != 1:
+            raise TypeError("prefix_block_table must be an int32 [1, n] tensor")
+        prefix_cap = prefix_block_table.shape[1] * prefix_k_cache.shape[2]
+    else:
+        if prefix_k_cache.shape[0] != 1:
+            raise ValueError(f"the shared prefix is one sequence: prefix_k_cache must be [1, Hk, capacity, D], got {tuple(prefix_k_cache.shape)}")
+        prefix_cap = prefix_k_cache.shape[2]
+    if q.dim() != (3 if ragged else 4):
+        raise ValueError("q must be [B, H, N, D], or packed [total_q, H, D] with cu_seqlens_q")
+    if prefix_len is None:
+        plen = prefix_cap
+    elif isinstance(prefix_len, torch.Tensor):
+        if prefix_len.dtype != torch.int32 or prefix_len.numel() != 1:
+            raise TypeError("prefix_len must be an int or a one-element int32 tensor")
+        plen = int(prefix_len.item()) if prefix_len.device.type == "cpu" else prefix_len.reshape(1)
+    elif isinstance(prefix_len, bool) or not isinstance(prefix_len, int):
+        raise TypeError("prefix_len must be an int or a one-element int32 tensor")
+    else:
+        plen = prefix_len
+    if isinstance(plen, int) and not 0 <= plen <= prefix_cap:
+        raise ValueError(f"prefix_len {plen} outside [0, prefix capacity {prefix_cap}]")
+    if causal:      # N_b <= L_b + 1 with L_b = cached + appended, as far as the host can see the tables
+        counts = appended = None
+        if ragged:
+            if isinstance(cu_seqlens_q, torch.Tensor) and cu_seqlens_q.device.type == "cpu" and cu_seqlens_q.dim() == 1:
+                c = cu_seqlens_q.tolist()
+                counts = [hi - lo for lo, hi in zip(c[:-1], c[1:])]
+                appended = counts if k_new is not None else [0] * len(counts)
+        else:
+            counts = [q.shape[2]] * q.shape[0]
+            appended = [k_new.shape[2] if isinstance(k_new, torch.Tensor) and k_new.dim() == 4 else 0] * q.shape[0]
+        lens = None
+        if counts is not None:
+            if cache_seqlens is None and k_cache.dim() == 4:      # every sequence full
+                lens = [block_table.shape[1] * k_cache.shape[2] if isinstance(block_table, torch.Tensor) and block_table.dim() == 2
+                        else k_cache.shape[2]] * len(counts)
+            elif isinstance(cache_seqlens, int):
+                lens = [cache_seqlens] * len(counts)
+            elif isinstance(cache_seqlens, torch.Tensor) and cache_seqlens.device.type == "cpu":
+                lens = cache_seqlens.tolist()
+        if lens is not None and any(n > length + new + 1 for n, length, new in zip(counts, lens, appended)):
+            raise ValueError("causal with a shared prefix needs every query behind the prefix (N_b <= L_b + 1, L_b counting this call's "
+                             "append): a query placed inside the prefix needs a causal cut that the one-sequence prefix phase cannot express")
+    own = dict(k_new=k_new, v_new=v_new, cache_seqlens=cache_seqlens, block_table=block_table, max_seqlen_k=max_seqlen_k, scale=scale,
+               groups=groups, causal=causal, l2norm_qk=l2norm_qk, k_scale=k_scale, v_scale=v_scale, return_lse=True)
+    # suffix phase: the ordinary call (every check of its arguments, and the append)
+    if ragged:
+        o_s, lse_s = flash_cosine_sim_attention_varlen_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, max_seqlen_q=max_seqlen_q, **own)
+    else:
+        o_s, lse_s = flash_cosine_sim_attention_with_kvcache(q, k_cache, v_cache, **own)
+    rows = q.shape[0] if ragged else q.shape[0] * q.shape[2]
+    if (isinstance(plen, int) and plen == 0) or rows == 0 or q.shape[1] == 0:
+        return (o_s, lse_s) if return_lse else o_s
+    # prefix phase: all the batch's query rows as ONE sequence [1, H, rows, D] -- packed q is a transposed view, rectangular q one small copy
+    H, D = q.shape[1], q.shape[-1]
+    q1 = q.transpose(0, 1).unsqueeze(0) if ragged else q.transpose(0, 1).reshape(1, H, rows, D)
+    o_p, lse_p = flash_cosine_sim_attention_with_kvcache(q1, prefix_k_cache, prefix_v_cache, cache_seqlens=plen, block_table=prefix_block_table,
+                                                         scale=scale, groups=groups, causal=False, l2norm_qk=l2norm_qk,
+                                                         k_scale=prefix_k_scale, v_scale=prefix_v_scale, return_lse=True)
+    if ragged:
+        o_pv, lse_pv = o_p[0].transpose(0, 1), lse_p[0].transpose(0, 1)                       # [total_q, H, D], [total_q, H]
+    else:
+        B, N = q.shape[0], q.shape[2]
+        o_pv, lse_pv = o_p[0].view(H, B, N, D).transpose(0, 1), lse_p[0].view(H, B, N).transpose(0, 1)
+    o, lse = merge_attention_states([o_pv, o_s], [lse_pv, lse_s])
+    return (o, lse) if return_lse else o

@@ -329,6 +329,58 @@ int    fcsa_forward_kvcache_varlen(const fcsa_forward_args* args, const fcsa_kvc
 size_t fcsa_forward_kvcache_varlen_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* cache, const fcsa_varlen* seqs,
                                                    const fcsa_kvcache_quant* quant, const fcsa_window* window);
 
+/* The decode calls with the rows' log-sum-exp (LSE) as a second result: what a caller needs to combine the attention over one set of keys
+ * with the attention over another (a shared prefix, a cache sharded by position, any split of one attention over two calls -- see
+ * fcsa_merge_states).  Forward only, like the calls themselves.
+ * fcsa_forward_kvcache_lse reads args, cache, seqs, quant and window exactly as the corresponding entry point does:
+ *   seqs NULL : fcsa_forward_kvcache (quant and window NULL), fcsa_forward_kvcache_window (window set) or fcsa_forward_kvcache_quant (quant set)
+ *   seqs set  : fcsa_forward_kvcache_varlen
+ * o and the caches after the append are bit for bit what that entry point gives: the append and decode kernels are launched unchanged, only
+ * the combine differs (it does the same arithmetic for o).  The workspace is that entry point's *_workspace_bytes.  lse_out must be given.
+ *   lse[row] = log(sum over the row's visible keys of exp(s)), natural log, float32; s is the row's true logit: scale * sum over the l2norm
+ *   groups of q^ . k^, or scale * q . k without l2norm_qk.  With an fp8 cache s is the logit on the values the codes mean: k_scale is
+ *   inside it, v_scale is not (it scales o only).
+ * The value is the same in the constant-shift and the per-row-shift regime (see fcsa_problem.scale): the library's internal exponent shift
+ * never shows.  A row without a visible key (L_b == 0, causal with N_b > L_b, a window that hides everything) gives lse = -inf exactly, and
+ * o = 0 as always; a NaN never appears there.  In the constant-shift regime o keeps its 1 / max(l, eps) clamp while lse is taken from the
+ * UNCLAMPED row sum l: where the clamp acts (a row whose every visible logit lies far below the shift) o is attenuated towards 0 and
+ * exp(lse) is still the true normaliser, so o * exp(lse) is no longer the un-normalised sum there.
+ * Strides of fcsa_lse_out are in ELEMENTS.  Equal-N calls read them as (batch, head, query): element [b, h, i] is at
+ * b * stride0 + h * stride1 + i * stride2.  Ragged calls ignore stride0 and read (head, token): [tok, h] is at h * stride1 + tok * stride2.
+ * Launches: the append and decode launches of the corresponding entry point, then "decode_combine_lse", "decode_combine_lse_fp8",
+ * "decode_combine_lse_ragged" or "decode_combine_lse_ragged_fp8" in place of its combine. */
+typedef struct fcsa_lse_out {
+  float*  lse;
+  int64_t stride0;
+  int64_t stride1;
+  int64_t stride2;
+} fcsa_lse_out;
+int    fcsa_forward_kvcache_lse(const fcsa_forward_args* args, const fcsa_kvcache* cache, const fcsa_varlen* seqs,
+                                const fcsa_kvcache_quant* quant, const fcsa_window* window, const fcsa_lse_out* lse_out);
+
+/* Merging attention states: `states` pairs (o_s, lse_s) over disjoint key sets of the same queries -> the pair over the union.
+ * Per row, in float32:  M = max_s lse_s;  M == -inf: o = 0, lse = -inf;  else w_s = exp(lse_s - M), W = sum_s w_s,
+ * o = (sum_s w_s * o_s) / W rounded once to `dtype`, lse = M + log(W).  A state with lse_s == -inf (or one whose weight underflows to 0)
+ * contributes exactly nothing, whatever its o_s holds: it is skipped, not multiplied, so a NaN-filled o_s cannot leak.  Deterministic.
+ * +inf and NaN LSEs are the caller's problem (the library never produces them from finite inputs).
+ * Rows are given as three leading sizes [size0, size1, size2] (a packed [total_q, H, D] tensor: size0 = 1); every view brings its own
+ * element strides, the feature dim contiguous and rows 16-byte aligned as everywhere; dim_head a multiple of 4 (float32) or 8 (16-bit): whole
+ * 16-byte chunks per row.  1 <= states <= 8
+ * (more: merge in two steps).  Launch: "merge_states". */
+#define FCSA_MERGE_MAX_STATES 8
+typedef struct fcsa_merge_args {
+  int32_t      dtype;              /* fcsa_dtype of every o_in and of o */
+  int32_t      size0, size1, size2;
+  int32_t      dim_head;
+  int32_t      states;             /* S */
+  fcsa_tensor  o_in[8];            /* [size0, size1, size2, dim_head] views (borrowed); entries beyond `states` are ignored */
+  fcsa_lse_out lse_in[8];          /* [size0, size1, size2] float32 views */
+  fcsa_tensor  o;                  /* out */
+  fcsa_lse_out lse;                /* out */
+  void*        stream;
+} fcsa_merge_args;
+int    fcsa_merge_states(const fcsa_merge_args* args);
+
 /* Bytes of optional forward scratch that enable the split-key forward for this problem (0: never split). */
 size_t fcsa_forward_workspace_bytes(const fcsa_problem* p);
 
