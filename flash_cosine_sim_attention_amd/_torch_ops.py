@@ -54,32 +54,32 @@ def _saved_state(q, rows_q, rows_k, D, l2norm_qk, groups, need_backward):
     return inv_l, qn, kn, rq, rk
 
 
+# ops whose one result is shaped like q, their first argument (the cache ops mutate their caches in place: declared by the schema's
+# (a!) / (b!)), and ops that return (dq, dk, dv) shaped like (q, k, v), which follow (d_out, o, inv_l)
+_LIKE_Q = ("attention", "varlen_attention", "window_attention", "varlen_window_attention", "kvcache_forward", "kvcache_window_forward",
+           "kvcache_fp8_forward", "kvcache_varlen_forward")
+_LIKE_QKV = ("varlen_backward", "window_backward", "varlen_window_backward")
+
+
 def _register_fakes():
+    for op in _LIKE_Q:
+        @torch.library.register_fake("fcsa::" + op)
+        def _(*args):
+            return args[0].new_empty(args[0].shape)
+
+    for op in _LIKE_QKV:
+        @torch.library.register_fake("fcsa::" + op)
+        def _(*args):
+            return tuple(t.new_empty(t.shape) for t in args[3:6])
+
     @torch.library.register_fake("fcsa::forward")
     def _(q, k, v, mask, attn_bias, attn_bias_batch_dim, scale, causal, l2norm_qk, groups, need_backward):
         merged, B, H, Hk, N, M, D = _canon_dims(q, k)
         return (q.new_empty(q.shape), *_saved_state(q, (B, H, N), (B, Hk, M), D, l2norm_qk, groups, need_backward))
 
-    @torch.library.register_fake("fcsa::attention")
-    def _(q, k, v, mask, attn_bias, attn_bias_batch_dim, scale, causal, l2norm_qk, groups):
-        return q.new_empty(q.shape)
-
     @torch.library.register_fake("fcsa::varlen_forward")
     def _(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, scale, causal, l2norm_qk, groups, need_backward):
         return (q.new_empty(q.shape), *_saved_state(q, (q.shape[1], q.shape[0]), (k.shape[1], k.shape[0]), q.shape[2], l2norm_qk, groups, need_backward))
-
-    @torch.library.register_fake("fcsa::varlen_backward")
-    def _(d_out, o, inv_l, q, k, v, cu_seqlens_q, cu_seqlens_k, qn, kn, rq, rk, max_seqlen_q, max_seqlen_k, scale, causal, l2norm_qk,
-          groups):
-        return q.new_empty(q.shape), k.new_empty(k.shape), v.new_empty(v.shape)
-
-    @torch.library.register_fake("fcsa::varlen_attention")
-    def _(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, scale, causal, l2norm_qk, groups):
-        return q.new_empty(q.shape)
-
-    @torch.library.register_fake("fcsa::kvcache_forward")
-    def _(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups):
-        return q.new_empty(q.shape)      # (the caches are mutated in place: declared by the schema's (a!) / (b!))
 
     # sliding-window ops: the shapes of their un-windowed twins
     @torch.library.register_fake("fcsa::window_forward")
@@ -87,42 +87,10 @@ def _register_fakes():
         B, H, N, D = q.shape
         return (q.new_empty(q.shape), *_saved_state(q, (B, H, N), (B, k.shape[1], k.shape[2]), D, l2norm_qk, groups, need_backward))
 
-    @torch.library.register_fake("fcsa::window_backward")
-    def _(d_out, o, inv_l, q, k, v, qn, kn, rq, rk, scale, causal, l2norm_qk, groups, window_left, window_right):
-        return q.new_empty(q.shape), k.new_empty(k.shape), v.new_empty(v.shape)
-
-    @torch.library.register_fake("fcsa::window_attention")
-    def _(q, k, v, scale, causal, l2norm_qk, groups, window_left, window_right):
-        return q.new_empty(q.shape)
-
     @torch.library.register_fake("fcsa::varlen_window_forward")
     def _(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, scale, causal, l2norm_qk, groups, need_backward, window_left,
           window_right):
         return (q.new_empty(q.shape), *_saved_state(q, (q.shape[1], q.shape[0]), (k.shape[1], k.shape[0]), q.shape[2], l2norm_qk, groups, need_backward))
-
-    @torch.library.register_fake("fcsa::varlen_window_backward")
-    def _(d_out, o, inv_l, q, k, v, cu_seqlens_q, cu_seqlens_k, qn, kn, rq, rk, max_seqlen_q, max_seqlen_k, scale, causal, l2norm_qk,
-          groups, window_left, window_right):
-        return q.new_empty(q.shape), k.new_empty(k.shape), v.new_empty(v.shape)
-
-    @torch.library.register_fake("fcsa::varlen_window_attention")
-    def _(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, scale, causal, l2norm_qk, groups, window_left, window_right):
-        return q.new_empty(q.shape)
-
-    @torch.library.register_fake("fcsa::kvcache_window_forward")
-    def _(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups, window_left,
-          window_right):
-        return q.new_empty(q.shape)
-
-    @torch.library.register_fake("fcsa::kvcache_fp8_forward")
-    def _(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, k_scale, v_scale, max_seqlen_k, scale, causal, l2norm_qk, groups,
-          window_left, window_right):
-        return q.new_empty(q.shape)
-
-    @torch.library.register_fake("fcsa::kvcache_varlen_forward")
-    def _(q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, k_scale, v_scale, max_seqlen_q, max_seqlen_k, scale,
-          causal, l2norm_qk, groups, window_left, window_right):
-        return q.new_empty(q.shape)
 
     @torch.library.register_fake("fcsa::kvcache_lse_forward")
     def _(q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, k_scale, v_scale, max_seqlen_q, max_seqlen_k, scale,

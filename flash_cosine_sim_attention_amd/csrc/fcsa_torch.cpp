@@ -9,6 +9,7 @@
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
+#include <c10/util/accumulate.h>
 #include <torch/csrc/autograd/custom_function.h>
 #include <torch/library.h>
 
@@ -18,6 +19,8 @@
 #include <cstring>
 #include <chrono>
 #include <tuple>
+#include <type_traits>
+#include <utility>
 
 #include "../../include/fcsa.h"
 
@@ -25,55 +28,73 @@ namespace {
 
 // The C ABI is called through pointers so that measurement tools can swap in another build of the same ABI at run time
 // (fcsa_torch_use_library, tools/ab_libs.py: interleaved A/B of kernel variants in ONE process).  Default: the library this
-// module is linked against.
+// module is linked against.  Every entry point is named once, here -- X(member, exported symbol, required) -- and the members
+// (typed by the declarations of include/fcsa.h), the dlsym pass and the "required" check of fcsa_torch_use_library derive from
+// the list.  An optional one is null when a swapped-in library does not export it; the ops that need it then raise (need_abi).
+#define FCSA_ABI(X)                                                                       \
+  X(forward, fcsa_forward, true)                                                          \
+  X(backward, fcsa_backward, true)                                                        \
+  X(forward_ws, fcsa_forward_workspace_bytes, true)                                       \
+  X(backward_ws, fcsa_backward_workspace_bytes, true)                                     \
+  X(needs_qn, fcsa_forward_needs_qn, true)                                                \
+  X(last_error, fcsa_last_error, true)                                                    \
+  /* packed sequences */                                                                  \
+  X(forward_varlen, fcsa_forward_varlen, false)                                           \
+  X(backward_varlen, fcsa_backward_varlen, false)                                         \
+  X(backward_varlen_ws, fcsa_backward_varlen_workspace_bytes, false)                      \
+  /* decoding against a key/value cache */                                                \
+  X(forward_kvcache, fcsa_forward_kvcache, false)                                         \
+  X(forward_kvcache_ws, fcsa_forward_kvcache_workspace_bytes, false)                      \
+  /* sliding window */                                                                    \
+  X(forward_window, fcsa_forward_window, false)                                           \
+  X(backward_window, fcsa_backward_window, false)                                         \
+  X(backward_window_ws, fcsa_backward_window_workspace_bytes, false)                      \
+  X(forward_kvcache_window, fcsa_forward_kvcache_window, false)                           \
+  X(forward_kvcache_window_ws, fcsa_forward_kvcache_window_workspace_bytes, false)        \
+  /* fp8 key/value cache */                                                               \
+  X(forward_kvcache_quant, fcsa_forward_kvcache_quant, false)                             \
+  X(forward_kvcache_quant_ws, fcsa_forward_kvcache_quant_workspace_bytes, false)          \
+  /* ragged decode steps (packed queries with per-sequence counts) */                     \
+  X(forward_kvcache_varlen, fcsa_forward_kvcache_varlen, false)                           \
+  X(forward_kvcache_varlen_ws, fcsa_forward_kvcache_varlen_workspace_bytes, false)        \
+  /* the decode calls with the rows' log-sum-exp, and merging attention states */         \
+  X(forward_kvcache_lse, fcsa_forward_kvcache_lse, false)                                 \
+  X(merge_states, fcsa_merge_states, false)
+
 struct Abi {
-  int (*forward)(const fcsa_forward_args*) = &fcsa_forward;
-  int (*backward)(const fcsa_backward_args*) = &fcsa_backward;
-  size_t (*forward_ws)(const fcsa_problem*) = &fcsa_forward_workspace_bytes;
-  size_t (*backward_ws)(const fcsa_problem*) = &fcsa_backward_workspace_bytes;
-  int (*needs_qn)(const fcsa_problem*, int32_t) = &fcsa_forward_needs_qn;
-  const char* (*last_error)(void) = &fcsa_last_error;
-  // packed sequences: null when a library swapped in by fcsa_torch_use_library does not export them (the varlen ops then raise)
-  int (*forward_varlen)(const fcsa_forward_args*, const fcsa_varlen*) = &fcsa_forward_varlen;
-  int (*backward_varlen)(const fcsa_backward_args*, const fcsa_varlen*) = &fcsa_backward_varlen;
-  size_t (*backward_varlen_ws)(const fcsa_problem*, const fcsa_varlen*) = &fcsa_backward_varlen_workspace_bytes;
-  // decoding against a key/value cache: null in a swapped-in library that does not export it (the kvcache op then raises)
-  int (*forward_kvcache)(const fcsa_forward_args*, const fcsa_kvcache*) = &fcsa_forward_kvcache;
-  size_t (*forward_kvcache_ws)(const fcsa_problem*, const fcsa_kvcache*) = &fcsa_forward_kvcache_workspace_bytes;
-  // sliding window: null in a swapped-in library that does not export it (the window ops then raise)
-  int (*forward_window)(const fcsa_forward_args*, const fcsa_varlen*, const fcsa_window*) = &fcsa_forward_window;
-  int (*backward_window)(const fcsa_backward_args*, const fcsa_varlen*, const fcsa_window*) = &fcsa_backward_window;
-  size_t (*backward_window_ws)(const fcsa_problem*, const fcsa_varlen*, const fcsa_window*) = &fcsa_backward_window_workspace_bytes;
-  int (*forward_kvcache_window)(const fcsa_forward_args*, const fcsa_kvcache*, const fcsa_window*) = &fcsa_forward_kvcache_window;
-  size_t (*forward_kvcache_window_ws)(const fcsa_problem*, const fcsa_kvcache*, const fcsa_window*) = &fcsa_forward_kvcache_window_workspace_bytes;
-  // fp8 key/value cache: null in a swapped-in library that does not export it (the fp8 op then raises)
-  int (*forward_kvcache_quant)(const fcsa_forward_args*, const fcsa_kvcache*, const fcsa_kvcache_quant*, const fcsa_window*) = &fcsa_forward_kvcache_quant;
-  size_t (*forward_kvcache_quant_ws)(const fcsa_problem*, const fcsa_kvcache*, const fcsa_kvcache_quant*, const fcsa_window*) =
-      &fcsa_forward_kvcache_quant_workspace_bytes;
-  // ragged decode steps (packed queries with per-sequence counts): likewise
-  int (*forward_kvcache_varlen)(const fcsa_forward_args*, const fcsa_kvcache*, const fcsa_varlen*, const fcsa_kvcache_quant*, const fcsa_window*) =
-      &fcsa_forward_kvcache_varlen;
-  size_t (*forward_kvcache_varlen_ws)(const fcsa_problem*, const fcsa_kvcache*, const fcsa_varlen*, const fcsa_kvcache_quant*, const fcsa_window*) =
-      &fcsa_forward_kvcache_varlen_workspace_bytes;
-  // the decode calls with the rows' log-sum-exp, and merging attention states: likewise
-  int (*forward_kvcache_lse)(const fcsa_forward_args*, const fcsa_kvcache*, const fcsa_varlen*, const fcsa_kvcache_quant*, const fcsa_window*,
-                             const fcsa_lse_out*) = &fcsa_forward_kvcache_lse;
-  int (*merge_states)(const fcsa_merge_args*) = &fcsa_merge_states;
+#define X(member, symbol, required) decltype(&symbol) member = &symbol;
+  FCSA_ABI(X)
+#undef X
 } g_abi;
+
+// an op refuses to run when the loaded library lacks an entry point it needs
+template <class... Fn>
+void need_abi(const char* who, const char* symbols, Fn... members) {
+  TORCH_CHECK(((members != nullptr) && ...), who, ": the loaded libfcsa_hip.so does not export ", symbols);
+}
 
 using at::Tensor;
 using c10::optional;
 
-// Host-time accounting of the two ops (tools/host_overhead.py; small problems are bound by host time per call, not by the
+// Host-time accounting of the two dense ops (tools/host_overhead.py; small problems are bound by host time per call, not by the
 // kernels): nanoseconds spent in [0] forward checks / canonicalisation, [1] forward allocations, [2] fcsa_forward (validation +
-// launches), [3..5] the same for backward, [6] forward calls, [7] backward calls.  Two clock reads per section, always on.
+// launches), [3..5] the same for backward, [6] forward calls, [7] backward calls.  Two clock reads per section, always on for a
+// dense call; the packed calls share the bodies and leave the counters alone (on == false).
 std::atomic<uint64_t> g_host_ns[8];
 struct Lap {
-  std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+  const bool on;
+  std::chrono::steady_clock::time_point t;
+  explicit Lap(bool dense) : on(dense) {
+    if (on) t = std::chrono::steady_clock::now();
+  }
   void mark(int slot) {
+    if (!on) return;
     const auto n = std::chrono::steady_clock::now();
     g_host_ns[slot].fetch_add((uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(n - t).count(), std::memory_order_relaxed);
     t = n;
+  }
+  void count(int slot) {
+    if (on) g_host_ns[slot].fetch_add(1, std::memory_order_relaxed);
   }
 };
 
@@ -98,24 +119,63 @@ bool rows_ok(const Tensor& t) {
 }
 Tensor prep(const Tensor& t) { return rows_ok(t) ? t : t.contiguous(); }
 
-fcsa_tensor view4(const Tensor& t) {
-  fcsa_tensor v;
-  v.ptr = t.data_ptr();
-  v.stride0 = t.stride(0);
-  v.stride1 = t.stride(1);
-  v.stride2 = t.stride(2);
+// Which dims of a tensor give the ABI's (stride0, stride1, stride2) = (batch, head, position) strides; a feature dim may follow them.
+struct Layout {
+  int batch, head, pos;      // batch < 0: no such dim (stride0 = 0, ignored by the library)
+};
+constexpr Layout kDense{0, 1, 2};       // [B, H, N, D], [B, H, N]
+constexpr Layout kPacked{-1, 1, 0};     // packed [total, H, D], [total, H]: stride1 = head stride, stride2 = token stride
+constexpr Layout kRows3{-1, 0, 1};      // merge_states, which has no heads: a 3-D state's rows as [1, size(0), size(1)]
+
+// the strided view of `t` that the library takes: V = fcsa_tensor, or fcsa_lse_out for a float32 tensor without the feature dim
+template <class V = fcsa_tensor>
+V strided(const Tensor& t, Layout l = kDense) {
+  V v;
+  if constexpr (std::is_same_v<V, fcsa_lse_out>) v.lse = t.data_ptr<float>();
+  else v.ptr = t.data_ptr();
+  v.stride0 = l.batch < 0 ? 0 : t.stride(l.batch);
+  v.stride1 = t.stride(l.head);
+  v.stride2 = t.stride(l.pos);
   return v;
 }
 
-struct Canon {
-  Tensor q, k, v;                 // 4-D, rows ok
-  optional<Tensor> mask, bias;    // contiguous
-  bool bias_batch, merged;
-  int64_t B, H, Hk, N, M, D;
+void check(int rc, const char* what) {
+  TORCH_CHECK(rc == FCSA_OK, what, " failed (status ", rc, "): ", g_abi.last_error());
+}
+
+void* stream_of(const Tensor& t) { return c10::hip::getCurrentHIPStream(t.device().index()).stream(); }
+
+// ---- the dense and the packed calls ---------------------------------------------------------------------------------------------------------
+// One canonicalised call, dense -- q [B, H, N, D], k / v [B, Hk, M, D] -- or packed variable-length sequences (fcsa_forward_varlen /
+// fcsa_backward_varlen): q [total_q, H, D], k / v [total_k, Hk, D], cu_seqlens_* int32 [S + 1] on q's device.  The tables are passed to the
+// library as they are: their contents are never read on the host (the Python wrapper validates host tables before they are moved to the
+// device).  canonicalise / canonicalise_varlen build it; everything after them (forward_body, backward_body) exists once.
+struct Call {
+  Tensor q, k, v;                 // rows ok
+  optional<Tensor> mask, bias;    // dense only; contiguous
+  Tensor cu_q, cu_k;              // packed only; contiguous
+  bool merged = false;            // dense only: q came with batch and heads merged, [B * H, N, D]
+  at::DimVector rows_q, rows_k;   // leading dims of the q-side / k-side saved tensors: (B, H, N) / (B, Hk, M); packed (H, total_q) / (Hk, total_k)
+  int64_t D = 0, groups = 1;      // groups as the caller gave it (p.groups is 1 without l2norm_qk)
+  fcsa_problem p;
+  bool packed() const { return cu_q.defined(); }
+  Layout layout() const { return packed() ? kPacked : kDense; }
 };
 
-Canon canonicalise(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& mask, const optional<Tensor>& bias,
-                   bool bias_batch, bool causal) {
+void set_problem(Call& c, at::ScalarType dt, int64_t batch, int64_t q_len, int64_t k_len, bool bias_batch, double scale, bool causal,
+                 bool l2norm_qk, int64_t groups) {
+  c.D = c.q.size(-1);
+  c.groups = groups;
+  c.p.dtype = dtype_code(dt);
+  c.p.batch = (int32_t)batch; c.p.heads = (int32_t)c.q.size(1); c.p.kv_heads = (int32_t)c.k.size(1);
+  c.p.q_len = (int32_t)q_len; c.p.k_len = (int32_t)k_len; c.p.dim_head = (int32_t)c.D;
+  c.p.causal = causal; c.p.bias_batch_dim = bias_batch; c.p.l2norm_qk = l2norm_qk;
+  c.p.groups = l2norm_qk ? (int32_t)groups : 1;
+  c.p.scale = (float)scale;
+}
+
+Call canonicalise(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& mask, const optional<Tensor>& bias,
+                  bool bias_batch, double scale, bool causal, bool l2norm_qk, int64_t groups) {
   TORCH_CHECK(q.is_cuda(), "flash_cosine_sim_attention_amd: q, k, v must be GPU tensors (HIP kernels only, no CPU fallback)");
   auto same_dev = [&](const char* name, const Tensor& t) {
     TORCH_CHECK_VALUE(t.device() == q.device(), name, " is on ", t.device(), " but q is on ", q.device(), ": all tensors must live on q's GPU");
@@ -128,12 +188,11 @@ Canon canonicalise(const Tensor& q, const Tensor& k, const Tensor& v, const opti
                    q.scalar_type(), ", ", k.scalar_type(), ", ", v.scalar_type());
   dtype_code(q.scalar_type());
   TORCH_CHECK_VALUE(!(causal && mask.has_value()), "mask should not be supplied if causality is needed");       // fcsa.py:88, cu:1675
-  Canon c;
+  Call c;
   c.merged = q.dim() == 3;
-  c.bias_batch = bias_batch;
   if (c.merged) {
     TORCH_CHECK_VALUE(k.dim() == 3 && v.dim() == 3, "if batch and heads are merged for queries, keys and values must also have 3 dimensions");
-    c.bias_batch = true;                                                                                          // cu:1652
+    bias_batch = true;                                                                                            // cu:1652
     c.q = q.unsqueeze(1);
   } else {
     TORCH_CHECK_VALUE(q.dim() == 4, "q must have 3 or 4 dimensions, got ", q.dim());
@@ -142,227 +201,38 @@ Canon canonicalise(const Tensor& q, const Tensor& k, const Tensor& v, const opti
   c.k = k.dim() == 3 ? k.unsqueeze(1) : k;
   c.v = v.dim() == 3 ? v.unsqueeze(1) : v;
   TORCH_CHECK_VALUE(c.k.dim() == 4 && c.v.dim() == 4, "k and v must have 3 or 4 dimensions");
-  c.B = c.q.size(0); c.H = c.q.size(1); c.N = c.q.size(2); c.D = c.q.size(3);
-  c.Hk = c.k.size(1); c.M = c.k.size(2);
+  const int64_t B = c.q.size(0), H = c.q.size(1), N = c.q.size(2), D = c.q.size(3), Hk = c.k.size(1), M = c.k.size(2);
   TORCH_CHECK_VALUE(c.v.sizes() == c.k.sizes(), "k and v must have the same shape, got ", k.sizes(), " and ", v.sizes());
-  TORCH_CHECK_VALUE(c.k.size(3) == c.D, "query, key, value dimensions must be the same");                          // cu:1673
-  TORCH_CHECK_VALUE(c.D == 16 || c.D == 32 || c.D == 64 || c.D == 96 || c.D == 128,
-                    "only dimensions (16, 32, 64, 96, 128) allowed for now, got ", c.D);                            // cu:1674
-  TORCH_CHECK_VALUE(c.k.size(0) == c.B, "batch mismatch between q (", c.B, ") and k/v (", c.k.size(0), ")");
+  TORCH_CHECK_VALUE(c.k.size(3) == D, "query, key, value dimensions must be the same");                            // cu:1673
+  TORCH_CHECK_VALUE(D == 16 || D == 32 || D == 64 || D == 96 || D == 128,
+                    "only dimensions (16, 32, 64, 96, 128) allowed for now, got ", D);                              // cu:1674
+  TORCH_CHECK_VALUE(c.k.size(0) == B, "batch mismatch between q (", B, ") and k/v (", c.k.size(0), ")");
   // grouped-query attention: query head h reads K/V head h / (H / Hk); single-headed (Hk == 1) and Hk == H are the two ends
-  TORCH_CHECK_VALUE(c.Hk == c.H || (c.Hk >= 1 && c.H % c.Hk == 0),
-                    "k/v heads must divide q heads (", c.H, "): grouped-query attention needs H % Hk == 0, got Hk = ", c.Hk);
+  TORCH_CHECK_VALUE(Hk == H || (Hk >= 1 && H % Hk == 0),
+                    "k/v heads must divide q heads (", H, "): grouped-query attention needs H % Hk == 0, got Hk = ", Hk);
   if (mask.has_value()) {
-    TORCH_CHECK_VALUE(mask->scalar_type() == at::kBool && mask->dim() == 2 && mask->size(0) == c.B && mask->size(1) == c.M,
-                      "mask must be a bool tensor of shape (", c.B, ", ", c.M, "), got ", mask->scalar_type(), " ", mask->sizes());
+    TORCH_CHECK_VALUE(mask->scalar_type() == at::kBool && mask->dim() == 2 && mask->size(0) == B && mask->size(1) == M,
+                      "mask must be a bool tensor of shape (", B, ", ", M, "), got ", mask->scalar_type(), " ", mask->sizes());
     c.mask = mask->contiguous();
   }
   if (bias.has_value()) {
-    const int64_t lead = c.bias_batch ? c.B : c.H;
-    TORCH_CHECK_VALUE(bias->dim() == 3 && bias->size(0) == lead && bias->size(1) == c.N && bias->size(2) == c.M,
-                      "attn_bias must have shape (", lead, ", ", c.N, ", ", c.M, "), got ", bias->sizes());
+    const int64_t lead = bias_batch ? B : H;
+    TORCH_CHECK_VALUE(bias->dim() == 3 && bias->size(0) == lead && bias->size(1) == N && bias->size(2) == M,
+                      "attn_bias must have shape (", lead, ", ", N, ", ", M, "), got ", bias->sizes());
     TORCH_CHECK_TYPE(bias->scalar_type() == q.scalar_type(), "attn_bias must have the dtype of q");
     c.bias = bias->contiguous();
   }
   c.q = prep(c.q); c.k = prep(c.k); c.v = prep(c.v);
+  c.rows_q = {B, H, N};
+  c.rows_k = {B, Hk, M};
+  set_problem(c, q.scalar_type(), B, N, M, bias_batch, scale, causal, l2norm_qk, groups);
   return c;
 }
 
-fcsa_problem problem(const Canon& c, at::ScalarType dt, bool causal, bool l2norm_qk, int64_t groups, double scale) {
-  fcsa_problem p;
-  p.dtype = dtype_code(dt);
-  p.batch = (int32_t)c.B; p.heads = (int32_t)c.H; p.kv_heads = (int32_t)c.Hk;
-  p.q_len = (int32_t)c.N; p.k_len = (int32_t)c.M; p.dim_head = (int32_t)c.D;
-  p.causal = causal; p.bias_batch_dim = c.bias_batch; p.l2norm_qk = l2norm_qk;
-  p.groups = l2norm_qk ? (int32_t)groups : 1;
-  p.scale = (float)scale;
-  return p;
-}
-
-void check(int rc, const char* what) {
-  TORCH_CHECK(rc == FCSA_OK, what, " failed (status ", rc, "): ", g_abi.last_error());
-}
-
-void* stream_of(const Tensor& t) { return c10::hip::getCurrentHIPStream(t.device().index()).stream(); }
-
-// (o, inv_l, qn, kn, rq, rk); the saved-state tensors are empty (numel 0) where they are not produced
-// sliding window of a call (window ops): the library's struct, after the checks every window op shares; nullptr: no window
-struct Win {
-  fcsa_window w;
-  Win(int64_t left, int64_t right) {
-    TORCH_CHECK(g_abi.forward_window != nullptr && g_abi.backward_window != nullptr && g_abi.backward_window_ws != nullptr &&
-                g_abi.forward_kvcache_window != nullptr && g_abi.forward_kvcache_window_ws != nullptr,
-                "sliding window: the loaded libfcsa_hip.so does not export fcsa_forward_window / fcsa_backward_window");
-    TORCH_CHECK_VALUE(left >= -1 && right >= -1, "window_size (", left, ", ", right, "): each side must be >= 0, or -1 for unbounded");
-    w.left = (int32_t)std::min<int64_t>(left, INT32_MAX);
-    w.right = (int32_t)std::min<int64_t>(right, INT32_MAX);
-  }
-};
-
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> forward_impl(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& mask,
-                                                                         const optional<Tensor>& attn_bias, bool attn_bias_batch_dim, double scale,
-                                                                         bool causal, bool l2norm_qk, int64_t groups, bool need_backward,
-                                                                         const fcsa_window* win) {
-  Lap lap;
-  const Canon c = canonicalise(q, k, v, mask, attn_bias, attn_bias_batch_dim, causal);
-  TORCH_CHECK_VALUE(!l2norm_qk || (groups >= 1 && c.D % groups == 0), "groups (", groups, ") must divide the head dimension (", c.D, ")");
-  c10::DeviceGuard guard(q.device());
-  lap.mark(0);
-  const auto opt = q.options();
-  const auto f32 = opt.dtype(at::kFloat);
-  fcsa_forward_args a;
-  a.p = problem(c, q.scalar_type(), causal, l2norm_qk, groups, scale);
-  Tensor o = at::empty({c.B, c.H, c.N, c.D}, opt);
-  Tensor none = at::empty({0}, f32);
-  Tensor inv_l = need_backward ? at::empty({c.B, c.H, c.N}, f32) : none;
-  Tensor qn = at::empty({0}, opt), kn = qn, rq = none, rk = none;
-  if (l2norm_qk) {
-    // An inference call (need_backward false) gets kn only -- and qn where q takes the row kernel (fcsa_forward_needs_qn): the
-    // 16-bit forward kernels then write nothing but `o` (the reference's need_store_rowsum == false path, cu:1086, cu:1241).
-    if (g_abi.needs_qn(&a.p, need_backward ? 1 : 0) != 0) qn = at::empty({c.B, c.H, c.N, c.D}, opt);
-    kn = at::empty({c.B, c.Hk, c.M, c.D}, opt);
-    if (need_backward) {
-      rq = at::empty({c.B, c.H, c.N, groups}, f32);
-      rk = at::empty({c.B, c.Hk, c.M, groups}, f32);
-    }
-  }
-  a.q = view4(c.q); a.k = view4(c.k); a.v = view4(c.v); a.o = view4(o);
-  a.inv_l = need_backward ? inv_l.data_ptr<float>() : nullptr;
-  a.mask = c.mask.has_value() ? static_cast<const uint8_t*>(c.mask->data_ptr()) : nullptr;
-  a.attn_bias = c.bias.has_value() ? c.bias->data_ptr() : nullptr;
-  a.norm.qn = qn.numel() > 0 ? qn.data_ptr() : nullptr;
-  a.norm.kn = l2norm_qk ? kn.data_ptr() : nullptr;
-  a.norm.rq = (l2norm_qk && need_backward) ? rq.data_ptr<float>() : nullptr;
-  a.norm.rk = (l2norm_qk && need_backward) ? rk.data_ptr<float>() : nullptr;
-  Tensor ws;
-  a.workspace = nullptr; a.workspace_bytes = 0;
-  size_t fws = g_abi.forward_ws(&a.p);      // 0 unless the key range is split (grids that cannot fill the chip)
-  if (win != nullptr) {      // a window that IS the un-windowed or the causal call splits like that call: room for either
-    fcsa_problem other = a.p;
-    other.causal = !other.causal;
-    fws = std::max(fws, g_abi.forward_ws(&other));
-  }
-  if (const size_t need = fws; need > 0) {
-    ws = at::empty({(int64_t)need}, opt.dtype(at::kByte));
-    a.workspace = ws.data_ptr(); a.workspace_bytes = need;
-  }
-  a.stream = stream_of(q);
-  lap.mark(1);
-  if (win != nullptr) check(g_abi.forward_window(&a, nullptr, win), "fcsa_forward_window");
-  else check(g_abi.forward(&a), "fcsa_forward");
-  lap.mark(2);
-  g_host_ns[6].fetch_add(1, std::memory_order_relaxed);
-  if (c.merged) o = o.squeeze(1);                                                                                  // cu:1740-1741
-  return std::make_tuple(o, inv_l, qn, kn, rq, rk);
-}
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> forward(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& mask,
-                                                                    const optional<Tensor>& attn_bias, bool attn_bias_batch_dim, double scale,
-                                                                    bool causal, bool l2norm_qk, int64_t groups, bool need_backward) {
-  return forward_impl(q, k, v, mask, attn_bias, attn_bias_batch_dim, scale, causal, l2norm_qk, groups, need_backward, nullptr);
-}
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> window_forward(const Tensor& q, const Tensor& k, const Tensor& v, double scale, bool causal,
-                                                                           bool l2norm_qk, int64_t groups, bool need_backward, int64_t left,
-                                                                           int64_t right) {
-  const Win win(left, right);
-  return forward_impl(q, k, v, c10::nullopt, c10::nullopt, false, scale, causal, l2norm_qk, groups, need_backward, &win.w);
-}
-
-// (dq, dk, dv, d_bias) in the shapes / dtype of the inputs; d_bias is empty when not requested
-std::tuple<Tensor, Tensor, Tensor, Tensor> backward_impl(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k,
-                                                         const Tensor& v, const optional<Tensor>& mask, const optional<Tensor>& attn_bias,
-                                                         const Tensor& qn, const Tensor& kn, const Tensor& rq, const Tensor& rk,
-                                                         bool attn_bias_batch_dim, double scale, bool causal, bool l2norm_qk, int64_t groups,
-                                                         bool need_bias_grad, const fcsa_window* win) {
-  Lap lap;
-  const Canon c = canonicalise(q, k, v, mask, attn_bias, attn_bias_batch_dim, causal);
-  c10::DeviceGuard guard(q.device());
-  const auto opt = q.options();
-  Tensor o4 = prep(o.dim() == 3 ? o.unsqueeze(1) : o);
-  Tensor do4 = d_out.dim() == 3 ? d_out.unsqueeze(1) : d_out;
-  // A broadcast gradient (`out.sum().backward()`, the reference's own timing protocol, benchmark.py:46-48: one scalar expanded with
-  // all strides 0) is not materialised at [B,H,N,D]: one contiguous feature row is, and the kernels read it with a row pitch of 0.
-  bool broadcast = do4.numel() > 0;
-  for (int64_t d = 0; d < do4.dim(); ++d) broadcast = broadcast && (do4.stride(d) == 0 || do4.size(d) == 1);
-  if (broadcast && do4.dim() == 4) {
-    Tensor row = do4.as_strided({do4.size(3)}, {0}).to(q.scalar_type()).contiguous();                  // [D], a D-element copy kernel
-    do4 = row.as_strided(do4.sizes(), {0, 0, 0, 1});
-  }
-  if (do4.scalar_type() != q.scalar_type()) do4 = do4.to(q.scalar_type());
-  do4 = prep(do4);
-  TORCH_CHECK_VALUE(do4.sizes() == o4.sizes(), "d_out must have the shape of the output");
-  TORCH_CHECK_VALUE(o4.size(0) == c.B && o4.size(1) == c.H && o4.size(2) == c.N && o4.size(3) == c.D, "o does not belong to these inputs");
-  // this op is public (torch.ops.fcsa.backward, ext.backward): everything a kernel dereferences is checked, not only its size
-  auto saved_ok = [&](const char* name, const Tensor& t, at::ScalarType st, int64_t numel) {
-    TORCH_CHECK_VALUE(t.defined() && t.device() == q.device() && t.scalar_type() == st && t.numel() == numel && t.is_contiguous(),
-                      name, " does not belong to these inputs (expected a contiguous ", st, " tensor of ", numel, " elements on ", q.device(), ")");
-  };
-  TORCH_CHECK_TYPE(o4.scalar_type() == q.scalar_type() && o4.device() == q.device(), "o must have the dtype and device of q");
-  TORCH_CHECK_VALUE(do4.device() == q.device(), "d_out is on ", do4.device(), " but q is on ", q.device());
-  saved_ok("inv_l", inv_l, at::kFloat, c.B * c.H * c.N);
-  if (l2norm_qk) {
-    saved_ok("qn", qn, q.scalar_type(), c.B * c.H * c.N * c.D);
-    saved_ok("kn", kn, q.scalar_type(), c.B * c.Hk * c.M * c.D);
-    saved_ok("rq", rq, at::kFloat, c.B * c.H * c.N * groups);
-    saved_ok("rk", rk, at::kFloat, c.B * c.Hk * c.M * groups);
-  }
-  lap.mark(3);
-  Tensor dq = at::empty({c.B, c.H, c.N, c.D}, opt);
-  Tensor dk = at::empty({c.B, c.Hk, c.M, c.D}, opt);
-  Tensor dv = at::empty({c.B, c.Hk, c.M, c.D}, opt);
-  // d_bias in the bias dtype, every element written once by the library: no zero-fill, no f32 tensor, no cast pass (cf. cu:1827, cu:1912)
-  Tensor db = (c.bias.has_value() && need_bias_grad) ? at::empty(c.bias->sizes(), opt) : at::empty({0}, opt);
-  fcsa_backward_args a;
-  a.p = problem(c, q.scalar_type(), causal, l2norm_qk, groups, scale);
-  size_t wsb = win != nullptr ? g_abi.backward_window_ws(&a.p, nullptr, win) : g_abi.backward_ws(&a.p);
-  if (wsb < 256) wsb = 256;
-  Tensor ws = at::empty({(int64_t)wsb}, opt.dtype(at::kByte));
-  a.d_out = view4(do4); a.o = view4(o4);
-  a.inv_l = inv_l.data_ptr<float>();
-  a.q = view4(c.q); a.k = view4(c.k); a.v = view4(c.v);
-  a.mask = c.mask.has_value() ? static_cast<const uint8_t*>(c.mask->data_ptr()) : nullptr;
-  a.attn_bias = c.bias.has_value() ? c.bias->data_ptr() : nullptr;
-  a.norm.qn = l2norm_qk ? qn.data_ptr() : nullptr;
-  a.norm.kn = l2norm_qk ? kn.data_ptr() : nullptr;
-  a.norm.rq = l2norm_qk ? rq.data_ptr<float>() : nullptr;
-  a.norm.rk = l2norm_qk ? rk.data_ptr<float>() : nullptr;
-  a.dq = view4(dq); a.dk = view4(dk); a.dv = view4(dv);
-  a.d_bias = db.numel() > 0 ? db.data_ptr() : nullptr;
-  a.workspace = ws.data_ptr(); a.workspace_bytes = wsb;
-  a.stream = stream_of(q);
-  lap.mark(4);
-  if (win != nullptr) check(g_abi.backward_window(&a, nullptr, win), "fcsa_backward_window");
-  else check(g_abi.backward(&a), "fcsa_backward");
-  lap.mark(5);
-  g_host_ns[7].fetch_add(1, std::memory_order_relaxed);
-  return std::make_tuple(dq.reshape(q.sizes()), dk.reshape(k.sizes()), dv.reshape(v.sizes()), db);
-}
-std::tuple<Tensor, Tensor, Tensor, Tensor> backward(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k,
-                                                    const Tensor& v, const optional<Tensor>& mask, const optional<Tensor>& attn_bias,
-                                                    const Tensor& qn, const Tensor& kn, const Tensor& rq, const Tensor& rk,
-                                                    bool attn_bias_batch_dim, double scale, bool causal, bool l2norm_qk, int64_t groups,
-                                                    bool need_bias_grad) {
-  return backward_impl(d_out, o, inv_l, q, k, v, mask, attn_bias, qn, kn, rq, rk, attn_bias_batch_dim, scale, causal, l2norm_qk, groups,
-                       need_bias_grad, nullptr);
-}
-std::tuple<Tensor, Tensor, Tensor> window_backward(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k,
-                                                   const Tensor& v, const Tensor& qn, const Tensor& kn, const Tensor& rq, const Tensor& rk,
-                                                   double scale, bool causal, bool l2norm_qk, int64_t groups, int64_t left, int64_t right) {
-  const Win win(left, right);
-  auto g = backward_impl(d_out, o, inv_l, q, k, v, c10::nullopt, c10::nullopt, qn, kn, rq, rk, false, scale, causal, l2norm_qk, groups, false, &win.w);
-  return std::make_tuple(std::get<0>(g), std::get<1>(g), std::get<2>(g));
-}
-
-
-// ---- packed variable-length sequences (fcsa_forward_varlen / fcsa_backward_varlen) ----------------------------------------------------
-// q [total_q, H, D], k / v [total_k, Hk, D], cu_seqlens_* int32 [S + 1] on q's device.  The tables are passed to the library as they are:
-// their contents are never read on the host (the Python wrapper validates host tables before they are moved to the device).
-struct VCanon {
-  Tensor q, k, v, cu_q, cu_k;     // rows ok; tables contiguous
-  int64_t S, H, Hk, TQ, TK, D;
-};
-
-VCanon canonicalise_varlen(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q, const Tensor& cu_k, int64_t max_q,
-                           int64_t max_k) {
+Call canonicalise_varlen(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q, const Tensor& cu_k, int64_t max_q,
+                         int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups) {
+  need_abi("flash_cosine_sim_attention_varlen", "fcsa_forward_varlen / fcsa_backward_varlen", g_abi.forward_varlen, g_abi.backward_varlen,
+           g_abi.backward_varlen_ws);
   TORCH_CHECK(q.is_cuda(), "flash_cosine_sim_attention_varlen: q, k, v must be GPU tensors (HIP kernels only, no CPU fallback)");
   for (const auto& [name, t] : {std::pair<const char*, const Tensor*>{"k", &k}, {"v", &v}, {"cu_seqlens_q", &cu_q}, {"cu_seqlens_k", &cu_k}})
     TORCH_CHECK_VALUE(t->device() == q.device(), name, " is on ", t->device(), " but q is on ", q.device(), ": all tensors must live on q's GPU");
@@ -374,392 +244,454 @@ VCanon canonicalise_varlen(const Tensor& q, const Tensor& k, const Tensor& v, co
   TORCH_CHECK_TYPE(cu_q.scalar_type() == at::kInt && cu_k.scalar_type() == at::kInt, "cu_seqlens_q / cu_seqlens_k must be int32");
   TORCH_CHECK_VALUE(cu_q.dim() == 1 && cu_k.dim() == 1 && cu_q.numel() >= 1 && cu_q.numel() == cu_k.numel(),
                     "cu_seqlens_q and cu_seqlens_k must be 1-D of the same length (sequences + 1), got ", cu_q.sizes(), " and ", cu_k.sizes());
-  VCanon c;
-  c.S = cu_q.numel() - 1;
-  c.TQ = q.size(0); c.H = q.size(1); c.D = q.size(2);
-  c.TK = k.size(0); c.Hk = k.size(1);
-  TORCH_CHECK_VALUE(k.size(2) == c.D, "query, key, value dimensions must be the same");
-  TORCH_CHECK_VALUE(c.D == 16 || c.D == 32 || c.D == 64 || c.D == 96 || c.D == 128,
-                    "only dimensions (16, 32, 64, 96, 128) allowed for now, got ", c.D);
-  TORCH_CHECK_VALUE(c.Hk >= 1 && c.H % c.Hk == 0, "k/v heads must divide q heads (", c.H, "), got ", c.Hk);
-  TORCH_CHECK_VALUE(max_q >= 0 && max_k >= 0 && max_q <= INT32_MAX && max_k <= INT32_MAX && c.S <= INT32_MAX,
+  const int64_t S = cu_q.numel() - 1, TQ = q.size(0), H = q.size(1), D = q.size(2), TK = k.size(0), Hk = k.size(1);
+  TORCH_CHECK_VALUE(k.size(2) == D, "query, key, value dimensions must be the same");
+  TORCH_CHECK_VALUE(D == 16 || D == 32 || D == 64 || D == 96 || D == 128, "only dimensions (16, 32, 64, 96, 128) allowed for now, got ", D);
+  TORCH_CHECK_VALUE(Hk >= 1 && H % Hk == 0, "k/v heads must divide q heads (", H, "), got ", Hk);
+  TORCH_CHECK_VALUE(max_q >= 0 && max_k >= 0 && max_q <= INT32_MAX && max_k <= INT32_MAX && S <= INT32_MAX,
                     "max_seqlen_q / max_seqlen_k must lie in [0, 2^31), got ", max_q, ", ", max_k);
-  TORCH_CHECK_VALUE(c.H * std::max(c.TQ, c.TK) <= INT32_MAX, "varlen: heads x packed rows must stay below 2^31");
+  TORCH_CHECK_VALUE(H * std::max(TQ, TK) <= INT32_MAX, "varlen: heads x packed rows must stay below 2^31");
+  Call c;
   c.q = prep(q); c.k = prep(k); c.v = prep(v);
   c.cu_q = cu_q.contiguous(); c.cu_k = cu_k.contiguous();
+  c.rows_q = {H, TQ};
+  c.rows_k = {Hk, TK};
+  set_problem(c, q.scalar_type(), S, max_q, max_k, false, scale, causal, l2norm_qk, groups);
   return c;
 }
 
-fcsa_problem varlen_problem(const VCanon& c, at::ScalarType dt, int64_t max_q, int64_t max_k, bool causal, bool l2norm_qk, int64_t groups,
-                            double scale) {
-  fcsa_problem p;
-  p.dtype = dtype_code(dt);
-  p.batch = (int32_t)c.S; p.heads = (int32_t)c.H; p.kv_heads = (int32_t)c.Hk;
-  p.q_len = (int32_t)max_q; p.k_len = (int32_t)max_k; p.dim_head = (int32_t)c.D;
-  p.causal = causal; p.bias_batch_dim = 0; p.l2norm_qk = l2norm_qk;
-  p.groups = l2norm_qk ? (int32_t)groups : 1;
-  p.scale = (float)scale;
-  return p;
-}
-
-fcsa_varlen varlen_table(const VCanon& c) {
+fcsa_varlen varlen_table(const Call& c) {
   fcsa_varlen t;
   t.cu_seqlens_q = c.cu_q.data_ptr<int32_t>();
   t.cu_seqlens_k = c.cu_k.data_ptr<int32_t>();
-  t.total_q = c.TQ; t.total_k = c.TK;
+  t.total_q = c.q.size(0); t.total_k = c.k.size(0);
   return t;
 }
 
-// packed [total, heads, D] -> the ABI's view: stride0 ignored, stride1 = head stride, stride2 = token stride
-fcsa_tensor packed3(const Tensor& t) {
-  fcsa_tensor v;
-  v.ptr = t.data_ptr();
-  v.stride0 = 0;
-  v.stride1 = t.stride(1);
-  v.stride2 = t.stride(0);
-  return v;
+at::DimVector with_last(at::DimVector rows, int64_t last) {
+  rows.push_back(last);
+  return rows;
 }
 
-void need_varlen_abi() {
-  TORCH_CHECK(g_abi.forward_varlen != nullptr && g_abi.backward_varlen != nullptr && g_abi.backward_varlen_ws != nullptr,
-              "flash_cosine_sim_attention_varlen: the loaded libfcsa_hip.so does not export fcsa_forward_varlen / fcsa_backward_varlen");
-}
+// sliding window of a call (window ops): the library's struct, after the checks every window op shares; nullptr: no window
+struct Win {
+  fcsa_window w;
+  Win(int64_t left, int64_t right) {
+    need_abi("sliding window", "fcsa_forward_window / fcsa_backward_window", g_abi.forward_window, g_abi.backward_window, g_abi.backward_window_ws,
+             g_abi.forward_kvcache_window, g_abi.forward_kvcache_window_ws);
+    TORCH_CHECK_VALUE(left >= -1 && right >= -1, "window_size (", left, ", ", right, "): each side must be >= 0, or -1 for unbounded");
+    w.left = (int32_t)std::min<int64_t>(left, INT32_MAX);
+    w.right = (int32_t)std::min<int64_t>(right, INT32_MAX);
+  }
+};
 
-// (o, inv_l, qn, kn, rq, rk): o [total_q, H, D]; inv_l [H, total_q]; qn [H, total_q, D], kn [Hk, total_k, D], rq / rk [.., G]; empty where
-// not produced
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> varlen_forward_impl(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q,
-                                                                                const Tensor& cu_k, int64_t max_q, int64_t max_k, double scale,
-                                                                                bool causal, bool l2norm_qk, int64_t groups, bool need_backward,
-                                                                                const fcsa_window* win) {
-  need_varlen_abi();
-  const VCanon c = canonicalise_varlen(q, k, v, cu_q, cu_k, max_q, max_k);
-  TORCH_CHECK_VALUE(!l2norm_qk || (groups >= 1 && c.D % groups == 0), "groups (", groups, ") must divide the head dimension (", c.D, ")");
-  c10::DeviceGuard guard(q.device());
-  const auto opt = q.options();
+// (o, inv_l, qn, kn, rq, rk): o shaped like q; inv_l float32 [rows_q]; qn [rows_q, D], kn [rows_k, D] in q's dtype; rq / rk float32
+// [rows_q, G] / [rows_k, G].  The saved-state tensors are empty (numel 0) where they are not produced.
+using Saved = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
+
+Saved forward_body(const Call& c, bool need_backward, const fcsa_window* win, Lap& lap) {
+  const bool l2norm_qk = c.p.l2norm_qk != 0;
+  TORCH_CHECK_VALUE(!l2norm_qk || (c.groups >= 1 && c.D % c.groups == 0), "groups (", c.groups, ") must divide the head dimension (", c.D, ")");
+  c10::DeviceGuard guard(c.q.device());
+  lap.mark(0);
+  const auto opt = c.q.options();
   const auto f32 = opt.dtype(at::kFloat);
   fcsa_forward_args a;
-  a.p = varlen_problem(c, q.scalar_type(), max_q, max_k, causal, l2norm_qk, groups, scale);
-  const fcsa_varlen t = varlen_table(c);
-  Tensor o = at::empty({c.TQ, c.H, c.D}, opt);
+  a.p = c.p;
+  Tensor o = at::empty(c.q.sizes(), opt);
   Tensor none = at::empty({0}, f32);
-  Tensor inv_l = need_backward ? at::empty({c.H, c.TQ}, f32) : none;
+  Tensor inv_l = need_backward ? at::empty(c.rows_q, f32) : none;
   Tensor qn = at::empty({0}, opt), kn = qn, rq = none, rk = none;
   if (l2norm_qk) {
-    fcsa_problem pp = a.p;      // fcsa_forward_needs_qn of the packed rows (batch 1, q_len = total_q)
-    pp.batch = 1; pp.q_len = (int32_t)c.TQ; pp.k_len = (int32_t)c.TK;
-    if (g_abi.needs_qn(&pp, need_backward ? 1 : 0) != 0) qn = at::empty({c.H, c.TQ, c.D}, opt);
-    kn = at::empty({c.Hk, c.TK, c.D}, opt);
+    // An inference call (need_backward false) gets kn only -- and qn where q takes the row kernel (fcsa_forward_needs_qn): the
+    // 16-bit forward kernels then write nothing but `o` (the reference's need_store_rowsum == false path, cu:1086, cu:1241).
+    fcsa_problem rows = c.p;
+    if (c.packed()) {      // the question is asked of the packed rows: batch 1, q_len = total_q
+      rows.batch = 1; rows.q_len = (int32_t)c.q.size(0); rows.k_len = (int32_t)c.k.size(0);
+    }
+    if (g_abi.needs_qn(&rows, need_backward ? 1 : 0) != 0) qn = at::empty(with_last(c.rows_q, c.D), opt);
+    kn = at::empty(with_last(c.rows_k, c.D), opt);
     if (need_backward) {
-      rq = at::empty({c.H, c.TQ, groups}, f32);
-      rk = at::empty({c.Hk, c.TK, groups}, f32);
+      rq = at::empty(with_last(c.rows_q, c.groups), f32);
+      rk = at::empty(with_last(c.rows_k, c.groups), f32);
     }
   }
-  a.q = packed3(c.q); a.k = packed3(c.k); a.v = packed3(c.v); a.o = packed3(o);
+  const Layout l = c.layout();
+  a.q = strided(c.q, l); a.k = strided(c.k, l); a.v = strided(c.v, l); a.o = strided(o, l);
   a.inv_l = need_backward ? inv_l.data_ptr<float>() : nullptr;
-  a.mask = nullptr;
-  a.attn_bias = nullptr;
+  a.mask = c.mask.has_value() ? static_cast<const uint8_t*>(c.mask->data_ptr()) : nullptr;
+  a.attn_bias = c.bias.has_value() ? c.bias->data_ptr() : nullptr;
   a.norm.qn = qn.numel() > 0 ? qn.data_ptr() : nullptr;
-  a.norm.kn = (l2norm_qk && kn.numel() > 0) ? kn.data_ptr() : nullptr;
+  a.norm.kn = l2norm_qk ? kn.data_ptr() : nullptr;
   a.norm.rq = (l2norm_qk && need_backward) ? rq.data_ptr<float>() : nullptr;
   a.norm.rk = (l2norm_qk && need_backward) ? rk.data_ptr<float>() : nullptr;
-  a.workspace = nullptr; a.workspace_bytes = 0;      // packed sequences never split the key range
-  a.stream = stream_of(q);
-  if (win != nullptr) check(g_abi.forward_window(&a, &t, win), "fcsa_forward_window");
-  else check(g_abi.forward_varlen(&a, &t), "fcsa_forward_varlen");
+  Tensor ws;
+  a.workspace = nullptr; a.workspace_bytes = 0;
+  if (!c.packed()) {      // packed sequences never split the key range
+    size_t need = g_abi.forward_ws(&a.p);      // 0 unless the key range is split (grids that cannot fill the chip)
+    if (win != nullptr) {      // a window that IS the un-windowed or the causal call splits like that call: room for either
+      fcsa_problem other = a.p;
+      other.causal = !other.causal;
+      need = std::max(need, g_abi.forward_ws(&other));
+    }
+    if (need > 0) {
+      ws = at::empty({(int64_t)need}, opt.dtype(at::kByte));
+      a.workspace = ws.data_ptr(); a.workspace_bytes = need;
+    }
+  }
+  a.stream = stream_of(c.q);
+  lap.mark(1);
+  if (c.packed()) {
+    const fcsa_varlen t = varlen_table(c);
+    if (win != nullptr) check(g_abi.forward_window(&a, &t, win), "fcsa_forward_window");
+    else check(g_abi.forward_varlen(&a, &t), "fcsa_forward_varlen");
+  } else {
+    if (win != nullptr) check(g_abi.forward_window(&a, nullptr, win), "fcsa_forward_window");
+    else check(g_abi.forward(&a), "fcsa_forward");
+  }
+  lap.mark(2);
+  lap.count(6);
+  if (c.merged) o = o.squeeze(1);                                                                                  // cu:1740-1741
   return std::make_tuple(o, inv_l, qn, kn, rq, rk);
 }
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> varlen_forward(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q,
-                                                                           const Tensor& cu_k, int64_t max_q, int64_t max_k, double scale,
-                                                                           bool causal, bool l2norm_qk, int64_t groups, bool need_backward) {
-  return varlen_forward_impl(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, need_backward, nullptr);
+
+Saved forward(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& mask, const optional<Tensor>& attn_bias,
+              bool attn_bias_batch_dim, double scale, bool causal, bool l2norm_qk, int64_t groups, bool need_backward) {
+  Lap lap(true);
+  return forward_body(canonicalise(q, k, v, mask, attn_bias, attn_bias_batch_dim, scale, causal, l2norm_qk, groups), need_backward, nullptr, lap);
 }
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> varlen_window_forward(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q,
-                                                                                  const Tensor& cu_k, int64_t max_q, int64_t max_k, double scale,
-                                                                                  bool causal, bool l2norm_qk, int64_t groups, bool need_backward,
-                                                                                  int64_t left, int64_t right) {
+Saved window_forward(const Tensor& q, const Tensor& k, const Tensor& v, double scale, bool causal, bool l2norm_qk, int64_t groups,
+                     bool need_backward, int64_t left, int64_t right) {
   const Win win(left, right);
-  return varlen_forward_impl(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, need_backward, &win.w);
+  Lap lap(true);
+  return forward_body(canonicalise(q, k, v, c10::nullopt, c10::nullopt, false, scale, causal, l2norm_qk, groups), need_backward, &win.w, lap);
+}
+Saved varlen_forward(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q, const Tensor& cu_k, int64_t max_q, int64_t max_k,
+                     double scale, bool causal, bool l2norm_qk, int64_t groups, bool need_backward) {
+  Lap lap(false);
+  return forward_body(canonicalise_varlen(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups), need_backward, nullptr, lap);
+}
+Saved varlen_window_forward(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q, const Tensor& cu_k, int64_t max_q,
+                            int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups, bool need_backward, int64_t left,
+                            int64_t right) {
+  Lap lap(false);
+  const Win win(left, right);
+  return forward_body(canonicalise_varlen(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups), need_backward, &win.w, lap);
+}
+
+// (dq, dk, dv, d_bias) in the shapes / dtype of the canonical inputs; d_bias (dense only) is empty when not requested and undefined for a
+// packed call
+using Grads = std::tuple<Tensor, Tensor, Tensor, Tensor>;
+
+Grads backward_body(const Call& c, const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& qn, const Tensor& kn, const Tensor& rq,
+                    const Tensor& rk, bool need_bias_grad, const fcsa_window* win, Lap& lap) {
+  const bool l2norm_qk = c.p.l2norm_qk != 0;
+  const at::ScalarType dt = c.q.scalar_type();
+  const auto dev = c.q.device();
+  c10::DeviceGuard guard(dev);
+  const auto opt = c.q.options();
+  Tensor oc = o, doc = d_out;
+  if (!c.packed()) {
+    if (oc.dim() == 3) oc = oc.unsqueeze(1);
+    if (doc.dim() == 3) doc = doc.unsqueeze(1);
+    // A broadcast gradient (`out.sum().backward()`, the reference's own timing protocol, benchmark.py:46-48: one scalar expanded with
+    // all strides 0) is not materialised at [B,H,N,D]: one contiguous feature row is, and the kernels read it with a row pitch of 0.
+    bool broadcast = doc.numel() > 0;
+    for (int64_t d = 0; d < doc.dim(); ++d) broadcast = broadcast && (doc.stride(d) == 0 || doc.size(d) == 1);
+    if (broadcast && doc.dim() == 4) {
+      Tensor row = doc.as_strided({doc.size(3)}, {0}).to(dt).contiguous();                             // [D], a D-element copy kernel
+      doc = row.as_strided(doc.sizes(), {0, 0, 0, 1});
+    }
+  }
+  oc = prep(oc);
+  if (doc.scalar_type() != dt) doc = doc.to(dt);
+  doc = prep(doc);
+  TORCH_CHECK_VALUE(doc.sizes() == oc.sizes(), "d_out must have the shape of the output");
+  TORCH_CHECK_VALUE(oc.sizes() == c.q.sizes(), "o does not belong to these inputs");
+  // these ops are public (torch.ops.fcsa.backward, ext.backward): everything a kernel dereferences is checked, not only its size
+  auto saved_ok = [&](const char* name, const Tensor& t, at::ScalarType st, const at::DimVector& rows, int64_t last) {
+    const int64_t numel = c10::multiply_integers(rows) * last;
+    TORCH_CHECK_VALUE(t.defined() && t.device() == dev && t.scalar_type() == st && t.numel() == numel && t.is_contiguous(),
+                      name, " does not belong to these inputs (expected a contiguous ", st, " tensor of ", numel, " elements on ", dev, ")");
+  };
+  TORCH_CHECK_TYPE(oc.scalar_type() == dt && oc.device() == dev, "o must have the dtype and device of q");
+  TORCH_CHECK_VALUE(doc.device() == dev, "d_out is on ", doc.device(), " but q is on ", dev);
+  saved_ok("inv_l", inv_l, at::kFloat, c.rows_q, 1);
+  if (l2norm_qk) {
+    saved_ok("qn", qn, dt, c.rows_q, c.D);
+    saved_ok("kn", kn, dt, c.rows_k, c.D);
+    saved_ok("rq", rq, at::kFloat, c.rows_q, c.groups);
+    saved_ok("rk", rk, at::kFloat, c.rows_k, c.groups);
+  }
+  lap.mark(3);
+  Tensor dq = at::empty(c.q.sizes(), opt);
+  Tensor dk = at::empty(c.k.sizes(), opt);
+  Tensor dv = at::empty(c.k.sizes(), opt);
+  // d_bias in the bias dtype, every element written once by the library: no zero-fill, no f32 tensor, no cast pass (cf. cu:1827, cu:1912)
+  Tensor db;
+  if (!c.packed()) db = (c.bias.has_value() && need_bias_grad) ? at::empty(c.bias->sizes(), opt) : at::empty({0}, opt);
+  fcsa_backward_args a;
+  a.p = c.p;
+  fcsa_varlen t;
+  if (c.packed()) t = varlen_table(c);
+  const fcsa_varlen* seqs = c.packed() ? &t : nullptr;
+  size_t wsb = win != nullptr ? g_abi.backward_window_ws(&a.p, seqs, win)
+               : seqs != nullptr ? g_abi.backward_varlen_ws(&a.p, seqs) : g_abi.backward_ws(&a.p);
+  if (wsb < 256) wsb = 256;
+  Tensor ws = at::empty({(int64_t)wsb}, opt.dtype(at::kByte));      // the caching allocator
+  const Layout l = c.layout();
+  a.d_out = strided(doc, l); a.o = strided(oc, l);
+  a.inv_l = inv_l.data_ptr<float>();
+  a.q = strided(c.q, l); a.k = strided(c.k, l); a.v = strided(c.v, l);
+  a.mask = c.mask.has_value() ? static_cast<const uint8_t*>(c.mask->data_ptr()) : nullptr;
+  a.attn_bias = c.bias.has_value() ? c.bias->data_ptr() : nullptr;
+  a.norm.qn = l2norm_qk ? qn.data_ptr() : nullptr;
+  a.norm.kn = l2norm_qk ? kn.data_ptr() : nullptr;
+  a.norm.rq = l2norm_qk ? rq.data_ptr<float>() : nullptr;
+  a.norm.rk = l2norm_qk ? rk.data_ptr<float>() : nullptr;
+  a.dq = strided(dq, l); a.dk = strided(dk, l); a.dv = strided(dv, l);
+  a.d_bias = (db.defined() && db.numel() > 0) ? db.data_ptr() : nullptr;
+  a.workspace = ws.data_ptr(); a.workspace_bytes = wsb;
+  a.stream = stream_of(c.q);
+  lap.mark(4);
+  if (win != nullptr) check(g_abi.backward_window(&a, seqs, win), "fcsa_backward_window");
+  else if (seqs != nullptr) check(g_abi.backward_varlen(&a, seqs), "fcsa_backward_varlen");
+  else check(g_abi.backward(&a), "fcsa_backward");
+  lap.mark(5);
+  lap.count(7);
+  return std::make_tuple(dq, dk, dv, db);
+}
+
+// the dense gradients in the shapes the caller's q, k, v came in (merged batch-heads, 3-D k / v)
+Grads dense_backward(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k, const Tensor& v,
+                     const optional<Tensor>& mask, const optional<Tensor>& attn_bias, const Tensor& qn, const Tensor& kn, const Tensor& rq,
+                     const Tensor& rk, bool attn_bias_batch_dim, double scale, bool causal, bool l2norm_qk, int64_t groups, bool need_bias_grad,
+                     const fcsa_window* win) {
+  Lap lap(true);
+  auto [dq, dk, dv, db] = backward_body(canonicalise(q, k, v, mask, attn_bias, attn_bias_batch_dim, scale, causal, l2norm_qk, groups), d_out, o, inv_l,
+                                        qn, kn, rq, rk, need_bias_grad, win, lap);
+  return std::make_tuple(dq.reshape(q.sizes()), dk.reshape(k.sizes()), dv.reshape(v.sizes()), db);
+}
+Grads backward(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k, const Tensor& v,
+               const optional<Tensor>& mask, const optional<Tensor>& attn_bias, const Tensor& qn, const Tensor& kn, const Tensor& rq,
+               const Tensor& rk, bool attn_bias_batch_dim, double scale, bool causal, bool l2norm_qk, int64_t groups, bool need_bias_grad) {
+  return dense_backward(d_out, o, inv_l, q, k, v, mask, attn_bias, qn, kn, rq, rk, attn_bias_batch_dim, scale, causal, l2norm_qk, groups,
+                        need_bias_grad, nullptr);
 }
 
 // (dq, dk, dv) shaped like q, k, v
-std::tuple<Tensor, Tensor, Tensor> varlen_backward_impl(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k,
-                                                        const Tensor& v, const Tensor& cu_q, const Tensor& cu_k, const Tensor& qn, const Tensor& kn,
-                                                        const Tensor& rq, const Tensor& rk, int64_t max_q, int64_t max_k, double scale, bool causal,
-                                                        bool l2norm_qk, int64_t groups, const fcsa_window* win) {
-  need_varlen_abi();
-  const VCanon c = canonicalise_varlen(q, k, v, cu_q, cu_k, max_q, max_k);
-  c10::DeviceGuard guard(q.device());
-  const auto opt = q.options();
-  Tensor o3 = prep(o);
-  Tensor do3 = d_out.scalar_type() != q.scalar_type() ? d_out.to(q.scalar_type()) : d_out;
-  do3 = prep(do3);
-  TORCH_CHECK_VALUE(o3.dim() == 3 && o3.size(0) == c.TQ && o3.size(1) == c.H && o3.size(2) == c.D, "o does not belong to these inputs");
-  TORCH_CHECK_VALUE(do3.sizes() == o3.sizes(), "d_out must have the shape of the output");
-  TORCH_CHECK_TYPE(o3.scalar_type() == q.scalar_type() && o3.device() == q.device(), "o must have the dtype and device of q");
-  TORCH_CHECK_VALUE(do3.device() == q.device(), "d_out is on ", do3.device(), " but q is on ", q.device());
-  auto saved_ok = [&](const char* name, const Tensor& t, at::ScalarType st, int64_t numel) {
-    TORCH_CHECK_VALUE(t.defined() && t.device() == q.device() && t.scalar_type() == st && t.numel() == numel && t.is_contiguous(),
-                      name, " does not belong to these inputs (expected a contiguous ", st, " tensor of ", numel, " elements on ", q.device(), ")");
-  };
-  saved_ok("inv_l", inv_l, at::kFloat, c.H * c.TQ);
-  if (l2norm_qk) {
-    saved_ok("qn", qn, q.scalar_type(), c.H * c.TQ * c.D);
-    saved_ok("kn", kn, q.scalar_type(), c.Hk * c.TK * c.D);
-    saved_ok("rq", rq, at::kFloat, c.H * c.TQ * groups);
-    saved_ok("rk", rk, at::kFloat, c.Hk * c.TK * groups);
-  }
-  Tensor dq = at::empty({c.TQ, c.H, c.D}, opt);
-  Tensor dk = at::empty({c.TK, c.Hk, c.D}, opt);
-  Tensor dv = at::empty({c.TK, c.Hk, c.D}, opt);
-  fcsa_backward_args a;
-  a.p = varlen_problem(c, q.scalar_type(), max_q, max_k, causal, l2norm_qk, groups, scale);
-  const fcsa_varlen t = varlen_table(c);
-  size_t wsb = win != nullptr ? g_abi.backward_window_ws(&a.p, &t, win) : g_abi.backward_varlen_ws(&a.p, &t);
-  if (wsb < 256) wsb = 256;
-  Tensor ws = at::empty({(int64_t)wsb}, opt.dtype(at::kByte));      // the caching allocator
-  a.d_out = packed3(do3); a.o = packed3(o3);
-  a.inv_l = inv_l.numel() > 0 ? inv_l.data_ptr<float>() : nullptr;
-  a.q = packed3(c.q); a.k = packed3(c.k); a.v = packed3(c.v);
-  a.mask = nullptr;
-  a.attn_bias = nullptr;
-  a.norm.qn = (l2norm_qk && qn.numel() > 0) ? qn.data_ptr() : nullptr;
-  a.norm.kn = (l2norm_qk && kn.numel() > 0) ? kn.data_ptr() : nullptr;
-  a.norm.rq = (l2norm_qk && rq.numel() > 0) ? rq.data_ptr<float>() : nullptr;
-  a.norm.rk = (l2norm_qk && rk.numel() > 0) ? rk.data_ptr<float>() : nullptr;
-  a.dq = packed3(dq); a.dk = packed3(dk); a.dv = packed3(dv);
-  a.d_bias = nullptr;
-  a.workspace = ws.data_ptr(); a.workspace_bytes = wsb;
-  a.stream = stream_of(q);
-  if (win != nullptr) check(g_abi.backward_window(&a, &t, win), "fcsa_backward_window");
-  else check(g_abi.backward_varlen(&a, &t), "fcsa_backward_varlen");
-  return std::make_tuple(dq, dk, dv);
-}
-std::tuple<Tensor, Tensor, Tensor> varlen_backward(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k,
-                                                   const Tensor& v, const Tensor& cu_q, const Tensor& cu_k, const Tensor& qn, const Tensor& kn,
-                                                   const Tensor& rq, const Tensor& rk, int64_t max_q, int64_t max_k, double scale, bool causal,
-                                                   bool l2norm_qk, int64_t groups) {
-  return varlen_backward_impl(d_out, o, inv_l, q, k, v, cu_q, cu_k, qn, kn, rq, rk, max_q, max_k, scale, causal, l2norm_qk, groups, nullptr);
-}
-std::tuple<Tensor, Tensor, Tensor> varlen_window_backward(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k,
-                                                          const Tensor& v, const Tensor& cu_q, const Tensor& cu_k, const Tensor& qn,
-                                                          const Tensor& kn, const Tensor& rq, const Tensor& rk, int64_t max_q, int64_t max_k,
-                                                          double scale, bool causal, bool l2norm_qk, int64_t groups, int64_t left, int64_t right) {
+using Grads3 = std::tuple<Tensor, Tensor, Tensor>;
+Grads3 first3(const Grads& g) { return std::make_tuple(std::get<0>(g), std::get<1>(g), std::get<2>(g)); }
+
+Grads3 window_backward(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k, const Tensor& v,
+                       const Tensor& qn, const Tensor& kn, const Tensor& rq, const Tensor& rk, double scale, bool causal, bool l2norm_qk,
+                       int64_t groups, int64_t left, int64_t right) {
   const Win win(left, right);
-  return varlen_backward_impl(d_out, o, inv_l, q, k, v, cu_q, cu_k, qn, kn, rq, rk, max_q, max_k, scale, causal, l2norm_qk, groups, &win.w);
+  return first3(dense_backward(d_out, o, inv_l, q, k, v, c10::nullopt, c10::nullopt, qn, kn, rq, rk, false, scale, causal, l2norm_qk, groups, false,
+                               &win.w));
+}
+Grads3 varlen_backward(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k, const Tensor& v,
+                       const Tensor& cu_q, const Tensor& cu_k, const Tensor& qn, const Tensor& kn, const Tensor& rq, const Tensor& rk,
+                       int64_t max_q, int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups) {
+  Lap lap(false);
+  return first3(backward_body(canonicalise_varlen(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups), d_out, o, inv_l, qn, kn, rq,
+                              rk, false, nullptr, lap));
+}
+Grads3 varlen_window_backward(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k, const Tensor& v,
+                              const Tensor& cu_q, const Tensor& cu_k, const Tensor& qn, const Tensor& kn, const Tensor& rq, const Tensor& rk,
+                              int64_t max_q, int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups, int64_t left,
+                              int64_t right) {
+  Lap lap(false);
+  const Win win(left, right);
+  return first3(backward_body(canonicalise_varlen(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups), d_out, o, inv_l, qn, kn, rq,
+                              rk, false, &win.w, lap));
 }
 
 // ---- autograd in C++ (reference: the Python autograd.Function FlashCosineSimAttention, flash_cosine_sim_attention.py:245-302).
 // A Python Function costs ~60 us of interpreter / engine hand-over per forward+backward; this node costs a few.  forward and
-// backward go through the dispatcher (fcsa::forward / fcsa::backward), so torch.compile traces them with the fake kernels.
+// backward go through the dispatcher by op name (fcsa::forward / fcsa::backward, ...), so torch.compile traces them with the fake kernels.
+//
+// One node for the four differentiable ops.  A family names its op pair and what rides along besides q, k, v: Extra, the tensors
+// between v and the scalars; Scalars, up to need_backward; Window, the scalars after it.  With them
+//   the forward op  takes (q, k, v, Extra..., Scalars..., need_backward, Window...)                 -- the attention op's arguments and the flag,
+//   the backward op takes (d_out, o, inv_l, q, k, v, Extra..., qn, kn, rq, rk, Scalars..., Window...) -- with need_bias_grad after Scalars where
+// the family has a bias gradient.  Everything is resolved at compile time: the calls are the typed dispatcher calls of the four former nodes.
 using torch::autograd::AutogradContext;
 using torch::autograd::variable_list;
 
-struct AttentionFn : public torch::autograd::Function<AttentionFn> {
-  static Tensor forward(AutogradContext* ctx, const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& mask,
-                        const optional<Tensor>& attn_bias, bool attn_bias_batch_dim, double scale, bool causal, bool l2norm_qk,
-                        int64_t groups) {
-    // (Function::apply runs this with grad mode OFF: the no_grad case is decided by the caller, attention_autograd)
+struct DenseOps {
+  static constexpr const char* forward_name = "fcsa::forward";
+  static constexpr const char* backward_name = "fcsa::backward";
+  static constexpr auto fwd = &forward;
+  static constexpr auto bwd = &backward;
+  using Extra = std::tuple<optional<Tensor>, optional<Tensor>>;      // mask, attn_bias
+  using Scalars = std::tuple<bool, double, bool, bool, int64_t>;     // attn_bias_batch_dim, scale, causal, l2norm_qk, groups
+  using Window = std::tuple<>;
+  static constexpr bool bias_grad = true;
+};
+struct VarlenOps {
+  static constexpr const char* forward_name = "fcsa::varlen_forward";
+  static constexpr const char* backward_name = "fcsa::varlen_backward";
+  static constexpr auto fwd = &varlen_forward;
+  static constexpr auto bwd = &varlen_backward;
+  using Extra = std::tuple<Tensor, Tensor>;                                    // cu_seqlens_q, cu_seqlens_k
+  using Scalars = std::tuple<int64_t, int64_t, double, bool, bool, int64_t>;   // max_seqlen_q, max_seqlen_k, scale, causal, l2norm_qk, groups
+  using Window = std::tuple<>;
+  static constexpr bool bias_grad = false;
+};
+struct WindowOps {
+  static constexpr const char* forward_name = "fcsa::window_forward";
+  static constexpr const char* backward_name = "fcsa::window_backward";
+  static constexpr auto fwd = &window_forward;
+  static constexpr auto bwd = &window_backward;
+  using Extra = std::tuple<>;
+  using Scalars = std::tuple<double, bool, bool, int64_t>;      // scale, causal, l2norm_qk, groups
+  using Window = std::tuple<int64_t, int64_t>;                  // window_left, window_right
+  static constexpr bool bias_grad = false;
+};
+struct VarlenWindowOps {
+  static constexpr const char* forward_name = "fcsa::varlen_window_forward";
+  static constexpr const char* backward_name = "fcsa::varlen_window_backward";
+  static constexpr auto fwd = &varlen_window_forward;
+  static constexpr auto bwd = &varlen_window_backward;
+  using Extra = VarlenOps::Extra;
+  using Scalars = VarlenOps::Scalars;
+  using Window = WindowOps::Window;
+  static constexpr bool bias_grad = false;
+};
+
+// a tuple's elements by reference (the argument lists below are concatenations of such tuples: nothing is copied)
+template <class... T>
+std::tuple<const T&...> refs(const std::tuple<T...>& t) {
+  return std::apply([](const T&... e) { return std::tie(e...); }, t);
+}
+
+template <class F>
+auto forward_args(const Tensor& q, const Tensor& k, const Tensor& v, const typename F::Extra& x, const typename F::Scalars& s, bool need,
+                  const typename F::Window& w) {
+  return std::tuple_cat(std::tie(q, k, v), refs(x), refs(s), std::make_tuple(need), refs(w));      // references to the arguments, the flag by value
+}
+
+// the dispatcher op `name`, typed like the function that implements it
+template <class Fn>
+auto typed_op(const char* name, Fn*) {
+  return c10::Dispatcher::singleton().findSchemaOrThrow(name, "").typed<Fn>();
+}
+
+// an extra tensor as a saved variable (an absent optional: undefined), and back in the type the backward op takes it in
+Tensor saveable(const Tensor& t) { return t; }
+Tensor saveable(const optional<Tensor>& t) { return t.has_value() ? *t : Tensor(); }
+template <class T>
+T restored(const Tensor& t) {
+  if constexpr (std::is_same_v<T, Tensor>) return t;
+  else return t.defined() ? T(t) : T();
+}
+template <class X, size_t... I>
+X restored_tuple(const variable_list& saved, size_t at, std::index_sequence<I...>) {
+  return X{restored<std::tuple_element_t<I, X>>(saved[at + I])...};
+}
+
+template <class F>
+struct AttentionNode : public torch::autograd::Function<AttentionNode<F>> {
+  using Extra = typename F::Extra;
+  using Scalars = typename F::Scalars;
+  using Window = typename F::Window;
+  static constexpr size_t kExtra = std::tuple_size_v<Extra>;
+
+  // attn_bias is an argument of its own so that the engine sees the one extra tensor that takes a gradient; Extra holds it too (dense op)
+  static Tensor forward(AutogradContext* ctx, const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& attn_bias, const Extra& x,
+                        const Scalars& s, const Window& w) {
+    // (Function::apply runs this with grad mode OFF: the no_grad case is decided by the caller, differentiable())
     const bool bias_grad = attn_bias.has_value() && attn_bias->requires_grad();
     const bool need = q.requires_grad() || k.requires_grad() || v.requires_grad() || bias_grad;                    // cu:1689
     at::AutoDispatchBelowADInplaceOrView guard;
-    static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("fcsa::forward", "")
-        .typed<std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, const optional<Tensor>&,
-                                                                           const optional<Tensor>&, bool, double, bool, bool, int64_t, bool)>();
-    auto r = op.call(q, k, v, mask, attn_bias, attn_bias_batch_dim, scale, causal, l2norm_qk, groups, need);
+    static auto op = typed_op(F::forward_name, F::fwd);
+    auto r = std::apply([](const auto&... a) { return op.call(a...); }, forward_args<F>(q, k, v, x, s, need, w));
     if (need) {
-      ctx->save_for_backward({std::get<0>(r), std::get<1>(r), q, k, v, mask.has_value() ? *mask : Tensor(),
-                              attn_bias.has_value() ? *attn_bias : Tensor(), std::get<2>(r), std::get<3>(r), std::get<4>(r), std::get<5>(r)});
-      ctx->saved_data["bias_batch"] = attn_bias_batch_dim;
-      ctx->saved_data["scale"] = scale;
-      ctx->saved_data["causal"] = causal;
-      ctx->saved_data["l2norm_qk"] = l2norm_qk;
-      ctx->saved_data["groups"] = groups;
+      variable_list save{std::get<0>(r), std::get<1>(r), q, k, v, std::get<2>(r), std::get<3>(r), std::get<4>(r), std::get<5>(r)};
+      std::apply([&](const auto&... e) { (save.push_back(saveable(e)), ...); }, x);
+      ctx->save_for_backward(std::move(save));
+      ctx->saved_data["scalars"] = c10::IValue(s);
+      if constexpr (std::tuple_size_v<Window> > 0) ctx->saved_data["window"] = c10::IValue(w);
       ctx->saved_data["bias_grad"] = bias_grad;
     }
     return std::get<0>(r);
   }
 
+  // one entry per forward argument: q, k, v, attn_bias, and nothing for Extra, Scalars, Window
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    const auto s = ctx->get_saved_variables();
-    const optional<Tensor> mask = s[5].defined() ? optional<Tensor>(s[5]) : c10::nullopt;
-    const optional<Tensor> bias = s[6].defined() ? optional<Tensor>(s[6]) : c10::nullopt;
+    const auto t = ctx->get_saved_variables();      // o, inv_l, q, k, v, qn, kn, rq, rk, Extra...
+    const Extra x = restored_tuple<Extra>(t, 9, std::make_index_sequence<kExtra>());
+    const Scalars s = ctx->saved_data["scalars"].template to<Scalars>();
+    Window w;
+    if constexpr (std::tuple_size_v<Window> > 0) w = ctx->saved_data["window"].template to<Window>();
     const bool bias_grad = ctx->saved_data["bias_grad"].toBool();
-    static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("fcsa::backward", "")
-        .typed<std::tuple<Tensor, Tensor, Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
-                                                          const optional<Tensor>&, const optional<Tensor>&, const Tensor&, const Tensor&,
-                                                          const Tensor&, const Tensor&, bool, double, bool, bool, int64_t, bool)>();
-    auto g = op.call(grads[0], s[0], s[1], s[2], s[3], s[4], mask, bias, s[7], s[8], s[9], s[10], ctx->saved_data["bias_batch"].toBool(),
-                     ctx->saved_data["scale"].toDouble(), ctx->saved_data["causal"].toBool(), ctx->saved_data["l2norm_qk"].toBool(),
-                     ctx->saved_data["groups"].toInt(), bias_grad);
-    return {std::get<0>(g), std::get<1>(g), std::get<2>(g), Tensor(), bias_grad ? std::get<3>(g) : Tensor(), Tensor(), Tensor(), Tensor(),
-            Tensor(), Tensor()};
+    static auto op = typed_op(F::backward_name, F::bwd);
+    auto call = [](const auto&... a) { return op.call(a...); };
+    const auto head = std::tuple_cat(std::tie(grads[0], t[0], t[1], t[2], t[3], t[4]), refs(x), std::tie(t[5], t[6], t[7], t[8]), refs(s));
+    if constexpr (F::bias_grad) {
+      auto g = std::apply(call, std::tuple_cat(head, std::tie(bias_grad), refs(w)));
+      return {std::get<0>(g), std::get<1>(g), std::get<2>(g), bias_grad ? std::get<3>(g) : Tensor(), Tensor(), Tensor(), Tensor()};
+    } else {
+      auto g = std::apply(call, std::tuple_cat(head, refs(w)));
+      return {std::get<0>(g), std::get<1>(g), std::get<2>(g), Tensor(), Tensor(), Tensor(), Tensor()};
+    }
   }
 };
 
-Tensor attention_autograd(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& mask, const optional<Tensor>& attn_bias,
-                          bool attn_bias_batch_dim, double scale, bool causal, bool l2norm_qk, int64_t groups) {
+// no autograd (inference / inputs that do not require grad): forward without saved state
+template <class F>
+Tensor inference(const Tensor& q, const Tensor& k, const Tensor& v, const typename F::Extra& x, const typename F::Scalars& s,
+                 const typename F::Window& w) {
+  return std::get<0>(std::apply(F::fwd, forward_args<F>(q, k, v, x, s, false, w)));
+}
+
+template <class F>
+Tensor differentiable(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& attn_bias, const typename F::Extra& x,
+                      const typename F::Scalars& s, const typename F::Window& w) {
   // under torch.no_grad() nothing will ever call backward, whatever the inputs' requires_grad says: take the inference path
   // (no saved state, no inv_l / inverse-norm / normalised-q writes), like a Python Function's ctx.needs_input_grad would
   const bool tracked = at::GradMode::is_enabled() &&
                        (q.requires_grad() || k.requires_grad() || v.requires_grad() || (attn_bias.has_value() && attn_bias->requires_grad()));
   if (!tracked) {
     at::AutoDispatchBelowADInplaceOrView guard;
-    return std::get<0>(forward(q, k, v, mask, attn_bias, attn_bias_batch_dim, scale, causal, l2norm_qk, groups, false));
+    return inference<F>(q, k, v, x, s, w);
   }
-  return AttentionFn::apply(q, k, v, mask, attn_bias, attn_bias_batch_dim, scale, causal, l2norm_qk, groups);
+  return AttentionNode<F>::apply(q, k, v, attn_bias, x, s, w);
 }
 
-// no autograd (inference / inputs that do not require grad): forward without saved state
+// the registered entry points (the dispatcher wants one function per op and key): CUDA key -> *_plain, Autograd key -> *_autograd
 Tensor attention_plain(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& mask, const optional<Tensor>& attn_bias,
                        bool attn_bias_batch_dim, double scale, bool causal, bool l2norm_qk, int64_t groups) {
-  return std::get<0>(forward(q, k, v, mask, attn_bias, attn_bias_batch_dim, scale, causal, l2norm_qk, groups, false));
+  return inference<DenseOps>(q, k, v, {mask, attn_bias}, {attn_bias_batch_dim, scale, causal, l2norm_qk, groups}, {});
 }
-
-
-// the differentiable varlen op: the same node pattern as AttentionFn, over fcsa::varlen_forward / fcsa::varlen_backward
-struct VarlenAttentionFn : public torch::autograd::Function<VarlenAttentionFn> {
-  static Tensor forward(AutogradContext* ctx, const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q, const Tensor& cu_k,
-                        int64_t max_q, int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups) {
-    at::AutoDispatchBelowADInplaceOrView guard;
-    static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("fcsa::varlen_forward", "")
-        .typed<std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, const Tensor&,
-                                                                           const Tensor&, int64_t, int64_t, double, bool, bool, int64_t, bool)>();
-    auto r = op.call(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, true);
-    ctx->save_for_backward({std::get<0>(r), std::get<1>(r), q, k, v, cu_q, cu_k, std::get<2>(r), std::get<3>(r), std::get<4>(r), std::get<5>(r)});
-    ctx->saved_data["max_q"] = max_q;
-    ctx->saved_data["max_k"] = max_k;
-    ctx->saved_data["scale"] = scale;
-    ctx->saved_data["causal"] = causal;
-    ctx->saved_data["l2norm_qk"] = l2norm_qk;
-    ctx->saved_data["groups"] = groups;
-    return std::get<0>(r);
-  }
-
-  static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    const auto s = ctx->get_saved_variables();
-    static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("fcsa::varlen_backward", "")
-        .typed<std::tuple<Tensor, Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
-                                                  const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
-                                                  int64_t, int64_t, double, bool, bool, int64_t)>();
-    auto g = op.call(grads[0], s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8], s[9], s[10], ctx->saved_data["max_q"].toInt(),
-                     ctx->saved_data["max_k"].toInt(), ctx->saved_data["scale"].toDouble(), ctx->saved_data["causal"].toBool(),
-                     ctx->saved_data["l2norm_qk"].toBool(), ctx->saved_data["groups"].toInt());
-    return {std::get<0>(g), std::get<1>(g), std::get<2>(g), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
-  }
-};
-
-Tensor varlen_attention_autograd(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q, const Tensor& cu_k, int64_t max_q,
-                                 int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups) {
-  const bool tracked = at::GradMode::is_enabled() && (q.requires_grad() || k.requires_grad() || v.requires_grad());
-  if (!tracked) {
-    at::AutoDispatchBelowADInplaceOrView guard;
-    return std::get<0>(varlen_forward(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, false));
-  }
-  return VarlenAttentionFn::apply(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups);
+Tensor attention_autograd(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& mask, const optional<Tensor>& attn_bias,
+                          bool attn_bias_batch_dim, double scale, bool causal, bool l2norm_qk, int64_t groups) {
+  return differentiable<DenseOps>(q, k, v, attn_bias, {mask, attn_bias}, {attn_bias_batch_dim, scale, causal, l2norm_qk, groups}, {});
 }
-
 Tensor varlen_attention_plain(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q, const Tensor& cu_k, int64_t max_q,
                               int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups) {
-  return std::get<0>(varlen_forward(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, false));
+  return inference<VarlenOps>(q, k, v, {cu_q, cu_k}, {max_q, max_k, scale, causal, l2norm_qk, groups}, {});
 }
-
-
-// the differentiable sliding-window ops: the same node pattern, over fcsa::window_forward / window_backward and their varlen twins
-struct WindowAttentionFn : public torch::autograd::Function<WindowAttentionFn> {
-  static Tensor forward(AutogradContext* ctx, const Tensor& q, const Tensor& k, const Tensor& v, double scale, bool causal, bool l2norm_qk,
-                        int64_t groups, int64_t left, int64_t right) {
-    at::AutoDispatchBelowADInplaceOrView guard;
-    static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("fcsa::window_forward", "")
-        .typed<std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, double, bool, bool, int64_t,
-                                                                           bool, int64_t, int64_t)>();
-    auto r = op.call(q, k, v, scale, causal, l2norm_qk, groups, true, left, right);
-    ctx->save_for_backward({std::get<0>(r), std::get<1>(r), q, k, v, std::get<2>(r), std::get<3>(r), std::get<4>(r), std::get<5>(r)});
-    ctx->saved_data["scale"] = scale;
-    ctx->saved_data["causal"] = causal;
-    ctx->saved_data["l2norm_qk"] = l2norm_qk;
-    ctx->saved_data["groups"] = groups;
-    ctx->saved_data["left"] = left;
-    ctx->saved_data["right"] = right;
-    return std::get<0>(r);
-  }
-
-  static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    const auto s = ctx->get_saved_variables();
-    static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("fcsa::window_backward", "")
-        .typed<std::tuple<Tensor, Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
-                                                  const Tensor&, const Tensor&, const Tensor&, const Tensor&, double, bool, bool, int64_t, int64_t,
-                                                  int64_t)>();
-    auto g = op.call(grads[0], s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8], ctx->saved_data["scale"].toDouble(),
-                     ctx->saved_data["causal"].toBool(), ctx->saved_data["l2norm_qk"].toBool(), ctx->saved_data["groups"].toInt(),
-                     ctx->saved_data["left"].toInt(), ctx->saved_data["right"].toInt());
-    return {std::get<0>(g), std::get<1>(g), std::get<2>(g), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
-  }
-};
-
+Tensor varlen_attention_autograd(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q, const Tensor& cu_k, int64_t max_q,
+                                 int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups) {
+  return differentiable<VarlenOps>(q, k, v, c10::nullopt, {cu_q, cu_k}, {max_q, max_k, scale, causal, l2norm_qk, groups}, {});
+}
 Tensor window_attention_plain(const Tensor& q, const Tensor& k, const Tensor& v, double scale, bool causal, bool l2norm_qk, int64_t groups,
                               int64_t left, int64_t right) {
-  return std::get<0>(window_forward(q, k, v, scale, causal, l2norm_qk, groups, false, left, right));
+  return inference<WindowOps>(q, k, v, {}, {scale, causal, l2norm_qk, groups}, {left, right});
 }
-
 Tensor window_attention_autograd(const Tensor& q, const Tensor& k, const Tensor& v, double scale, bool causal, bool l2norm_qk, int64_t groups,
                                  int64_t left, int64_t right) {
-  const bool tracked = at::GradMode::is_enabled() && (q.requires_grad() || k.requires_grad() || v.requires_grad());
-  if (!tracked) {
-    at::AutoDispatchBelowADInplaceOrView guard;
-    return window_attention_plain(q, k, v, scale, causal, l2norm_qk, groups, left, right);
-  }
-  return WindowAttentionFn::apply(q, k, v, scale, causal, l2norm_qk, groups, left, right);
+  return differentiable<WindowOps>(q, k, v, c10::nullopt, {}, {scale, causal, l2norm_qk, groups}, {left, right});
 }
-
-struct VarlenWindowAttentionFn : public torch::autograd::Function<VarlenWindowAttentionFn> {
-  static Tensor forward(AutogradContext* ctx, const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q, const Tensor& cu_k,
-                        int64_t max_q, int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups, int64_t left, int64_t right) {
-    at::AutoDispatchBelowADInplaceOrView guard;
-    static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("fcsa::varlen_window_forward", "")
-        .typed<std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, const Tensor&,
-                                                                           const Tensor&, int64_t, int64_t, double, bool, bool, int64_t, bool,
-                                                                           int64_t, int64_t)>();
-    auto r = op.call(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, true, left, right);
-    ctx->save_for_backward({std::get<0>(r), std::get<1>(r), q, k, v, cu_q, cu_k, std::get<2>(r), std::get<3>(r), std::get<4>(r), std::get<5>(r)});
-    ctx->saved_data["max_q"] = max_q;
-    ctx->saved_data["max_k"] = max_k;
-    ctx->saved_data["scale"] = scale;
-    ctx->saved_data["causal"] = causal;
-    ctx->saved_data["l2norm_qk"] = l2norm_qk;
-    ctx->saved_data["groups"] = groups;
-    ctx->saved_data["left"] = left;
-    ctx->saved_data["right"] = right;
-    return std::get<0>(r);
-  }
-
-  static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    const auto s = ctx->get_saved_variables();
-    static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("fcsa::varlen_window_backward", "")
-        .typed<std::tuple<Tensor, Tensor, Tensor>(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
-                                                  const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
-                                                  int64_t, int64_t, double, bool, bool, int64_t, int64_t, int64_t)>();
-    auto g = op.call(grads[0], s[0], s[1], s[2], s[3], s[4], s[5], s[6], s[7], s[8], s[9], s[10], ctx->saved_data["max_q"].toInt(),
-                     ctx->saved_data["max_k"].toInt(), ctx->saved_data["scale"].toDouble(), ctx->saved_data["causal"].toBool(),
-                     ctx->saved_data["l2norm_qk"].toBool(), ctx->saved_data["groups"].toInt(), ctx->saved_data["left"].toInt(),
-                     ctx->saved_data["right"].toInt());
-    return {std::get<0>(g), std::get<1>(g), std::get<2>(g), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(),
-            Tensor(), Tensor()};
-  }
-};
-
 Tensor varlen_window_attention_plain(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q, const Tensor& cu_k, int64_t max_q,
                                      int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups, int64_t left, int64_t right) {
-  return std::get<0>(varlen_window_forward(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, false, left, right));
+  return inference<VarlenWindowOps>(q, k, v, {cu_q, cu_k}, {max_q, max_k, scale, causal, l2norm_qk, groups}, {left, right});
 }
-
 Tensor varlen_window_attention_autograd(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q, const Tensor& cu_k, int64_t max_q,
                                         int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups, int64_t left, int64_t right) {
-  const bool tracked = at::GradMode::is_enabled() && (q.requires_grad() || k.requires_grad() || v.requires_grad());
-  if (!tracked) {
-    at::AutoDispatchBelowADInplaceOrView guard;
-    return varlen_window_attention_plain(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, left, right);
-  }
-  return VarlenWindowAttentionFn::apply(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, left, right);
+  return differentiable<VarlenWindowOps>(q, k, v, c10::nullopt, {cu_q, cu_k}, {max_q, max_k, scale, causal, l2norm_qk, groups}, {left, right});
 }
 
 
@@ -774,15 +706,15 @@ Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor
                             bool l2norm_qk, int64_t groups, const fcsa_window* win, const Tensor* k_scale = nullptr, const Tensor* v_scale = nullptr,
                             const Tensor* cu_q = nullptr, int64_t max_seqlen_q = 0, Tensor* lse_out = nullptr) {
   const bool ragged = cu_q != nullptr;
-  TORCH_CHECK(lse_out == nullptr || g_abi.forward_kvcache_lse != nullptr,
-              "return_lse: the loaded libfcsa_hip.so does not export fcsa_forward_kvcache_lse");
-  TORCH_CHECK(!ragged || (g_abi.forward_kvcache_varlen != nullptr && g_abi.forward_kvcache_varlen_ws != nullptr),
-              "flash_cosine_sim_attention_varlen_with_kvcache: the loaded libfcsa_hip.so does not export fcsa_forward_kvcache_varlen");
+  const Layout ql = ragged ? kPacked : kDense;      // of q, o, k_new, v_new and the lse
+  if (lse_out != nullptr) need_abi("return_lse", "fcsa_forward_kvcache_lse", g_abi.forward_kvcache_lse);
+  if (ragged)
+    need_abi("flash_cosine_sim_attention_varlen_with_kvcache", "fcsa_forward_kvcache_varlen", g_abi.forward_kvcache_varlen,
+             g_abi.forward_kvcache_varlen_ws);
   const bool fp8 = k_scale != nullptr;      // an e4m3fn cache with its two scale tensors (kvcache_fp8_forward)
-  TORCH_CHECK(g_abi.forward_kvcache != nullptr && g_abi.forward_kvcache_ws != nullptr,
-              "flash_cosine_sim_attention_with_kvcache: the loaded libfcsa_hip.so does not export fcsa_forward_kvcache");
-  TORCH_CHECK(!fp8 || (g_abi.forward_kvcache_quant != nullptr && g_abi.forward_kvcache_quant_ws != nullptr),
-              "flash_cosine_sim_attention_with_kvcache: the loaded libfcsa_hip.so does not export fcsa_forward_kvcache_quant");
+  need_abi("flash_cosine_sim_attention_with_kvcache", "fcsa_forward_kvcache", g_abi.forward_kvcache, g_abi.forward_kvcache_ws);
+  if (fp8)
+    need_abi("flash_cosine_sim_attention_with_kvcache", "fcsa_forward_kvcache_quant", g_abi.forward_kvcache_quant, g_abi.forward_kvcache_quant_ws);
   TORCH_CHECK(q.is_cuda(), "flash_cosine_sim_attention_with_kvcache: q and the caches must be GPU tensors (HIP kernels only)");
   auto same_dev = [&](const char* name, const Tensor& t) {
     TORCH_CHECK_VALUE(t.device() == q.device(), name, " is on ", t.device(), " but q is on ", q.device(), ": all tensors must live on q's GPU");
@@ -876,10 +808,10 @@ Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor
   a.p.causal = causal; a.p.bias_batch_dim = 0; a.p.l2norm_qk = l2norm_qk;
   a.p.groups = l2norm_qk ? (int32_t)groups : 1;
   a.p.scale = (float)scale;
-  a.q = ragged ? packed3(q4) : view4(q4);
-  a.o = ragged ? packed3(o) : view4(o);
-  kv.k_cache = view4(k_cache);
-  kv.v_cache = view4(v_cache);
+  a.q = strided(q4, ql);
+  a.o = strided(o, ql);
+  kv.k_cache = strided(k_cache);
+  kv.v_cache = strided(v_cache);
   kv.capacity = (int32_t)capacity;
   kv.page_size = (int32_t)page;
   kv.num_blocks = (int32_t)num_blocks;
@@ -889,8 +821,8 @@ Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor
   kv.block_table_stride = paged ? tab.size(1) : 0;
   fcsa_tensor none;
   std::memset(&none, 0, sizeof(none));
-  kv.k_new = kn.defined() && new_len > 0 ? (ragged ? packed3(kn) : view4(kn)) : none;
-  kv.v_new = vn.defined() && new_len > 0 ? (ragged ? packed3(vn) : view4(vn)) : none;
+  kv.k_new = kn.defined() && new_len > 0 ? strided(kn, ql) : none;
+  kv.v_new = vn.defined() && new_len > 0 ? strided(vn, ql) : none;
   fcsa_varlen seqs;
   std::memset(&seqs, 0, sizeof(seqs));
   if (ragged) {
@@ -930,11 +862,7 @@ Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor
   if (lse_out != nullptr) {
     // float32 [B, H, N], or [total_q, H] for a ragged step; the workspace is that of the call without it
     *lse_out = ragged ? at::empty({N, H}, q.options().dtype(at::kFloat)) : at::empty({B, H, N}, q.options().dtype(at::kFloat));
-    fcsa_lse_out lo;
-    lo.lse = lse_out->data_ptr<float>();
-    lo.stride0 = ragged ? 0 : lse_out->stride(0);
-    lo.stride1 = lse_out->stride(1);
-    lo.stride2 = ragged ? lse_out->stride(0) : lse_out->stride(2);
+    const fcsa_lse_out lo = strided<fcsa_lse_out>(*lse_out, ql);
     check(g_abi.forward_kvcache_lse(&a, &kv, ragged ? &seqs : nullptr, fp8 ? &qz : nullptr, win, &lo), "fcsa_forward_kvcache_lse");
     return o;
   }
@@ -1000,7 +928,7 @@ std::tuple<Tensor, Tensor> kvcache_lse_forward(const Tensor& q, const Tensor& k_
 // merge_attention_states: S <= 8 states (o_s [..., D] 4-D or [total_q, H, D], lse_s float32 without the feature dim) -> fresh contiguous
 // (o, lse).  The states are read in place through their strides (feature dim contiguous, rows 16-byte aligned; anything else is copied).
 std::tuple<Tensor, Tensor> merge_states(at::TensorList os, at::TensorList lses) {
-  TORCH_CHECK(g_abi.merge_states != nullptr, "merge_attention_states: the loaded libfcsa_hip.so does not export fcsa_merge_states");
+  need_abi("merge_attention_states", "fcsa_merge_states", g_abi.merge_states);
   const int64_t S = (int64_t)os.size();
   TORCH_CHECK_VALUE(S >= 1 && S <= FCSA_MERGE_MAX_STATES && (int64_t)lses.size() == S,
                     "merge_states takes 1 to ", FCSA_MERGE_MAX_STATES, " states and as many lses, got ", S, " and ", lses.size());
@@ -1014,11 +942,11 @@ std::tuple<Tensor, Tensor> merge_states(at::TensorList os, at::TensorList lses) 
   fcsa_merge_args a;
   std::memset(&a, 0, sizeof(a));
   a.dtype = dtype_code(o0.scalar_type());
-  const bool packed = o0.dim() == 3;
+  const Layout l = o0.dim() == 3 ? kRows3 : kDense;
   for (int64_t d = 0; d + 1 < o0.dim(); ++d) TORCH_CHECK_VALUE(o0.size(d) <= INT32_MAX, "merge_states: sizes must stay below 2^31");
-  a.size0 = packed ? 1 : (int32_t)o0.size(0);
-  a.size1 = (int32_t)o0.size(packed ? 0 : 1);
-  a.size2 = (int32_t)o0.size(packed ? 1 : 2);
+  a.size0 = l.batch < 0 ? 1 : (int32_t)o0.size(l.batch);
+  a.size1 = (int32_t)o0.size(l.head);
+  a.size2 = (int32_t)o0.size(l.pos);
   a.dim_head = (int32_t)D;
   a.states = (int32_t)S;
   std::vector<Tensor> keep;
@@ -1026,33 +954,20 @@ std::tuple<Tensor, Tensor> merge_states(at::TensorList os, at::TensorList lses) 
   const auto lead = o0.sizes().slice(0, o0.dim() - 1);
   for (int64_t s = 0; s < S; ++s) {
     const Tensor& o = os[s];
-    const Tensor& l = lses[s];
-    TORCH_CHECK_VALUE(o.device() == o0.device() && l.device() == o0.device(), "merge_states: every tensor must live on the first one's GPU");
+    const Tensor& ls = lses[s];
+    TORCH_CHECK_VALUE(o.device() == o0.device() && ls.device() == o0.device(), "merge_states: every tensor must live on the first one's GPU");
     TORCH_CHECK_TYPE(o.scalar_type() == o0.scalar_type(), "merge_states: os must share a dtype, got ", o0.scalar_type(), " and ", o.scalar_type());
     TORCH_CHECK_VALUE(o.sizes() == o0.sizes(), "merge_states: os must share a shape, got ", o0.sizes(), " and ", o.sizes());
-    TORCH_CHECK_TYPE(l.scalar_type() == at::kFloat, "merge_states: lses must be float32, got ", l.scalar_type());
-    TORCH_CHECK_VALUE(l.sizes() == lead, "merge_states: an lse must have its o's shape without the feature dim, ", lead, ", got ", l.sizes());
+    TORCH_CHECK_TYPE(ls.scalar_type() == at::kFloat, "merge_states: lses must be float32, got ", ls.scalar_type());
+    TORCH_CHECK_VALUE(ls.sizes() == lead, "merge_states: an lse must have its o's shape without the feature dim, ", lead, ", got ", ls.sizes());
     keep.push_back(prep(o));
-    const Tensor& oc = keep.back();
-    a.o_in[s].ptr = oc.data_ptr();
-    a.o_in[s].stride0 = packed ? 0 : oc.stride(0);
-    a.o_in[s].stride1 = oc.stride(packed ? 0 : 1);
-    a.o_in[s].stride2 = oc.stride(packed ? 1 : 2);
-    a.lse_in[s].lse = l.data_ptr<float>();
-    a.lse_in[s].stride0 = packed ? 0 : l.stride(0);
-    a.lse_in[s].stride1 = l.stride(packed ? 0 : 1);
-    a.lse_in[s].stride2 = l.stride(packed ? 1 : 2);
+    a.o_in[s] = strided(keep.back(), l);
+    a.lse_in[s] = strided<fcsa_lse_out>(ls, l);
   }
   Tensor o = at::empty(o0.sizes(), o0.options());
   Tensor lse = at::empty(lead, o0.options().dtype(at::kFloat));
-  a.o.ptr = o.data_ptr();
-  a.o.stride0 = packed ? 0 : o.stride(0);
-  a.o.stride1 = o.stride(packed ? 0 : 1);
-  a.o.stride2 = o.stride(packed ? 1 : 2);
-  a.lse.lse = lse.data_ptr<float>();
-  a.lse.stride0 = packed ? 0 : lse.stride(0);
-  a.lse.stride1 = lse.stride(packed ? 0 : 1);
-  a.lse.stride2 = lse.stride(packed ? 1 : 2);
+  a.o = strided(o, l);
+  a.lse = strided<fcsa_lse_out>(lse, l);
   a.stream = stream_of(o0);
   if (o.numel() > 0) check(g_abi.merge_states(&a), "fcsa_merge_states");
   return {o, lse};
@@ -1070,30 +985,13 @@ extern "C" int fcsa_torch_use_library(const char* path) {
   void* h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
   if (h == nullptr) return -1;
   Abi a;
-  a.forward = reinterpret_cast<decltype(a.forward)>(dlsym(h, "fcsa_forward"));
-  a.backward = reinterpret_cast<decltype(a.backward)>(dlsym(h, "fcsa_backward"));
-  a.forward_ws = reinterpret_cast<decltype(a.forward_ws)>(dlsym(h, "fcsa_forward_workspace_bytes"));
-  a.backward_ws = reinterpret_cast<decltype(a.backward_ws)>(dlsym(h, "fcsa_backward_workspace_bytes"));
-  a.needs_qn = reinterpret_cast<decltype(a.needs_qn)>(dlsym(h, "fcsa_forward_needs_qn"));
-  a.last_error = reinterpret_cast<decltype(a.last_error)>(dlsym(h, "fcsa_last_error"));
-  // optional: a build without packed-sequence support leaves them null, and only the varlen ops refuse to run
-  a.forward_varlen = reinterpret_cast<decltype(a.forward_varlen)>(dlsym(h, "fcsa_forward_varlen"));
-  a.backward_varlen = reinterpret_cast<decltype(a.backward_varlen)>(dlsym(h, "fcsa_backward_varlen"));
-  a.backward_varlen_ws = reinterpret_cast<decltype(a.backward_varlen_ws)>(dlsym(h, "fcsa_backward_varlen_workspace_bytes"));
-  a.forward_kvcache = reinterpret_cast<decltype(a.forward_kvcache)>(dlsym(h, "fcsa_forward_kvcache"));
-  a.forward_kvcache_ws = reinterpret_cast<decltype(a.forward_kvcache_ws)>(dlsym(h, "fcsa_forward_kvcache_workspace_bytes"));
-  a.forward_window = reinterpret_cast<decltype(a.forward_window)>(dlsym(h, "fcsa_forward_window"));
-  a.backward_window = reinterpret_cast<decltype(a.backward_window)>(dlsym(h, "fcsa_backward_window"));
-  a.backward_window_ws = reinterpret_cast<decltype(a.backward_window_ws)>(dlsym(h, "fcsa_backward_window_workspace_bytes"));
-  a.forward_kvcache_window = reinterpret_cast<decltype(a.forward_kvcache_window)>(dlsym(h, "fcsa_forward_kvcache_window"));
-  a.forward_kvcache_window_ws = reinterpret_cast<decltype(a.forward_kvcache_window_ws)>(dlsym(h, "fcsa_forward_kvcache_window_workspace_bytes"));
-  a.forward_kvcache_quant = reinterpret_cast<decltype(a.forward_kvcache_quant)>(dlsym(h, "fcsa_forward_kvcache_quant"));
-  a.forward_kvcache_quant_ws = reinterpret_cast<decltype(a.forward_kvcache_quant_ws)>(dlsym(h, "fcsa_forward_kvcache_quant_workspace_bytes"));
-  a.forward_kvcache_varlen = reinterpret_cast<decltype(a.forward_kvcache_varlen)>(dlsym(h, "fcsa_forward_kvcache_varlen"));
-  a.forward_kvcache_varlen_ws = reinterpret_cast<decltype(a.forward_kvcache_varlen_ws)>(dlsym(h, "fcsa_forward_kvcache_varlen_workspace_bytes"));
-  a.forward_kvcache_lse = reinterpret_cast<decltype(a.forward_kvcache_lse)>(dlsym(h, "fcsa_forward_kvcache_lse"));
-  a.merge_states = reinterpret_cast<decltype(a.merge_states)>(dlsym(h, "fcsa_merge_states"));
-  if (!a.forward || !a.backward || !a.forward_ws || !a.backward_ws || !a.needs_qn || !a.last_error) { dlclose(h); return -2; }
+  bool complete = true;      // optional entry points stay null where the library lacks them, and only the ops that need them refuse to run
+#define X(member, symbol, required)                                     \
+  a.member = reinterpret_cast<decltype(a.member)>(dlsym(h, #symbol)); \
+  complete = complete && (a.member != nullptr || !(required));
+  FCSA_ABI(X)
+#undef X
+  if (!complete) { dlclose(h); return -2; }
   // Only libraries of THIS ABI: the binding allocates for the struct layouts and buffer contracts of include/fcsa.h as compiled in
   // (e.g. ABI 3 writes d_bias once in the bias dtype into an uninitialised buffer; an ABI-2 library would accumulate float32 into
   // it -- twice the buffer's size for the 16-bit types).  -3: the library reports another version.

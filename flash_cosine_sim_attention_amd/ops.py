@@ -277,6 +277,136 @@ def _check_return_lse(return_lse):
         raise TypeError(f"return_lse must be a bool, got {return_lse!r} (pass window_size by keyword)")
 
 
+_FP8_TYPES = tuple(getattr(torch, n) for n in ("float8_e4m3fn", "float8_e4m3fnuz", "float8_e5m2", "float8_e5m2fnuz") if hasattr(torch, n))
+
+
+def _host_view(q, cu_seqlens_q, k_new, cache_seqlens):
+    """What the host can see of a decode step's per-sequence tables without reading a device tensor: (counts, lens, appended) -- the query
+    rows, the cached positions and the positions this call appends, each a list with one entry per sequence, or None where the table
+    lives on the device (lens also for cache_seqlens=None: every sequence full).  cu_seqlens_q None: a rectangular q [B, H, N, D].  It
+    judges nothing: an argument it cannot read counts as unseen, and the checks of the cache functions refuse it."""
+    host = lambda t: isinstance(t, torch.Tensor) and t.device.type == "cpu" and t.dim() == 1
+    if cu_seqlens_q is None:
+        B = q.shape[0]
+        counts = [q.shape[2]] * B
+        appended = [k_new.shape[2] if isinstance(k_new, torch.Tensor) and k_new.dim() == 4 else 0] * B
+    else:
+        B = cu_seqlens_q.numel() - 1 if isinstance(cu_seqlens_q, torch.Tensor) else 0
+        counts = appended = None
+        if host(cu_seqlens_q):
+            c = cu_seqlens_q.tolist()
+            counts = [hi - lo for lo, hi in zip(c[:-1], c[1:])]
+            appended = counts if k_new is not None else [0] * B
+    lens = None
+    if isinstance(cache_seqlens, int):
+        lens = [int(cache_seqlens)] * B
+    elif host(cache_seqlens):
+        lens = cache_seqlens.tolist()
+    return counts, lens, appended
+
+
+class _CacheCall:
+    """The front end that `flash_cosine_sim_attention_with_kvcache` and `flash_cosine_sim_attention_varlen_with_kvcache` share: the checks of
+    the caches (here), of the tables, bounds and scales of a step of B sequences (`tables`), and the moves to q's device (`on_device`).
+    Nothing here reads a device tensor on the host."""
+
+    def __init__(self, fn, q, q_fault, k_cache, v_cache, k_new, v_new, k_scale, v_scale):
+        """q_fault: the caller's verdict on q's rank, None or the message to refuse it with (raised where the rank checks stand)."""
+        self.q, self.k_cache, self.v_cache, self.k_new, self.k_scale, self.v_scale = q, k_cache, v_cache, k_new, k_scale, v_scale
+        self.fp8 = k_cache.dtype in _FP8_TYPES or v_cache.dtype in _FP8_TYPES
+        if self.fp8:
+            if k_cache.dtype != v_cache.dtype:
+                raise TypeError(f"one fp8 cache and one {min(k_cache.dtype, v_cache.dtype, key=lambda d: d in _FP8_TYPES)} cache: k_cache and "
+                                f"v_cache must both be torch.float8_e4m3fn, got {k_cache.dtype} and {v_cache.dtype}")
+            if k_cache.dtype != torch.float8_e4m3fn:
+                raise TypeError(f"{k_cache.dtype} caches are not supported: an fp8 cache is torch.float8_e4m3fn (OCP e4m3, the gfx950 encoding; "
+                                "float8_e4m3fnuz is MI300's, float8_e5m2 is out of scope)")
+            if q.dtype not in (torch.float16, torch.bfloat16):
+                raise TypeError(f"fp8 caches take float16 or bfloat16 q, k_new and v_new, got a {q.dtype} q")
+            for name, t in (("k_new", k_new), ("v_new", v_new)):
+                if t is not None and t.dtype != q.dtype:
+                    raise TypeError(f"{name} must have q's dtype ({q.dtype}), got {t.dtype}")
+        elif k_scale is not None or v_scale is not None:
+            raise TypeError(f"k_scale / v_scale given with {k_cache.dtype} caches: scales belong to torch.float8_e4m3fn caches")
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_new, v_new)):
+            raise RuntimeError(f"{fn} is forward-only: q, k_new and v_new must not require grad (run it under torch.no_grad())")
+        if q_fault is not None:
+            raise ValueError(q_fault)
+        for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+            if t.dim() != 4:
+                raise ValueError(f"{name} must have 4 dimensions, got {tuple(t.shape)}")
+        if k_cache.shape != v_cache.shape:
+            raise ValueError(f"k_cache and v_cache must have the same shape, got {tuple(k_cache.shape)} and {tuple(v_cache.shape)}")
+        if (k_new is None) != (v_new is None):
+            raise ValueError("k_new and v_new must be given together")
+        H, self.Hk, self.D = q.shape[1], k_cache.shape[1], q.shape[-1]
+        if k_cache.shape[3] != self.D:
+            raise ValueError("query, key, value dimensions must be the same")
+        if self.Hk < 1 or H % self.Hk:
+            raise ValueError(f"k/v heads must divide q heads ({H}), got {self.Hk}")
+
+    def tables(self, B, cu_seqlens_q, appends, cache_seqlens, block_table, max_seqlen_k):
+        """The step's tables, checked: B sequences; cu_seqlens_q (checked by the caller) or None for a rectangular q; appends: whether
+        k_new brings anything to append.  Sets capacity, max_k, the host's view (counts, lens, appended: `_host_view`) and the scales
+        as tensors."""
+        k_cache = self.k_cache
+        if block_table is not None:
+            if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B:
+                raise TypeError("block_table must be an int32 [sequences, max_blocks] tensor")
+            page = k_cache.shape[2]
+            if page <= 0 or page % 16:
+                raise ValueError(f"page_size ({page}) must be a positive multiple of 16")
+            capacity = block_table.shape[1] * page
+        else:
+            if k_cache.shape[0] != B:
+                raise ValueError(f"batch mismatch between the step ({B} sequences) and the caches ({k_cache.shape[0]})")
+            capacity = k_cache.shape[2]
+        if cache_seqlens is None:
+            if appends:
+                raise ValueError("k_new given but cache_seqlens is None (every sequence full): there is no slot to append to")
+        elif not isinstance(cache_seqlens, int) and (not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32
+                                                     or cache_seqlens.shape != (B,)):
+            raise TypeError(f"cache_seqlens must be an int or an int32 tensor of shape ({B},)")
+        self.counts, self.lens, self.appended = _host_view(self.q, cu_seqlens_q, self.k_new, cache_seqlens)
+        if self.lens is not None:
+            ends = [n0 + n_new for n0, n_new in zip(self.lens, self.appended or [0] * B)]
+            for b, (n0, end) in enumerate(zip(self.lens, ends)):
+                if n0 < 0 or end > capacity:
+                    raise ValueError(f"sequence {b}: cache_seqlens {n0} + {end - n0} new tokens outside [0, capacity {capacity}]")
+            if block_table is not None and block_table.device.type == "cpu":
+                nb = k_cache.shape[0]
+                for b, end in enumerate(ends):
+                    used = block_table[b, :(end + page - 1) // page]
+                    if used.numel() and (int(used.min()) < 0 or int(used.max()) >= nb):
+                        raise ValueError(f"sequence {b}: block_table entries outside [0, {nb})")
+        if max_seqlen_k is not None and (int(max_seqlen_k) != max_seqlen_k or max_seqlen_k < 0):
+            raise ValueError(f"max_seqlen_k must be a non-negative integer, got {max_seqlen_k}")
+        if self.fp8:
+            dev = self.q.device
+            self.k_scale, self.v_scale = _cache_scale("k_scale", self.k_scale, B, self.Hk, dev), _cache_scale("v_scale", self.v_scale, B, self.Hk, dev)
+        self.B, self.capacity = B, capacity
+        self.max_k = capacity if max_seqlen_k is None else min(int(max_seqlen_k), capacity)
+        self.cache_seqlens, self.block_table = cache_seqlens, block_table
+
+    def cpu_quant(self):
+        """the scale keywords of the CPU paths"""
+        return dict(k_scale=self.k_scale.expand(self.B, self.Hk), v_scale=self.v_scale.expand(self.B, self.Hk)) if self.fp8 else {}
+
+    def on_device(self):
+        """(k_cache, v_cache, cache_seqlens, block_table) as the ops take them: the tables on q's device, and the codes of fp8 caches as
+        bytes (same storage, so the append lands in the caller's caches)."""
+        dev, cache_seqlens, block_table = self.q.device, self.cache_seqlens, self.block_table
+        if isinstance(cache_seqlens, int):
+            cache_seqlens = torch.full((self.B,), cache_seqlens, dtype=torch.int32, device=dev)
+        elif cache_seqlens is not None:
+            cache_seqlens = cache_seqlens.to(dev, non_blocking=True)
+        if block_table is not None:
+            block_table = block_table.to(dev, non_blocking=True)
+        if self.fp8:
+            return self.k_cache.view(torch.uint8), self.v_cache.view(torch.uint8), cache_seqlens, block_table
+        return self.k_cache, self.v_cache, cache_seqlens, block_table
+
+
 def flash_cosine_sim_attention_with_kvcache(q, k_cache, v_cache, k_new=None, v_new=None, cache_seqlens=None, block_table=None,
                                             max_seqlen_k=None, scale=8, groups=1, causal=False, l2norm_qk=True, k_scale=None, v_scale=None,
                                             return_lse=False, window_size=(-1, -1)):
@@ -311,109 +441,34 @@ def flash_cosine_sim_attention_with_kvcache(q, k_cache, v_cache, k_new=None, v_n
     return_lse must be a bool and window_size is best passed by keyword: return_lse precedes it in the signature."""
     _check_return_lse(return_lse)
     window = _window(window_size)
-    fp8_types = tuple(getattr(torch, n) for n in ("float8_e4m3fn", "float8_e4m3fnuz", "float8_e5m2", "float8_e5m2fnuz") if hasattr(torch, n))
-    fp8 = k_cache.dtype in fp8_types or v_cache.dtype in fp8_types
-    if fp8:
-        if k_cache.dtype != v_cache.dtype:
-            raise TypeError(f"one fp8 cache and one {min(k_cache.dtype, v_cache.dtype, key=lambda d: d in fp8_types)} cache: k_cache and "
-                            f"v_cache must both be torch.float8_e4m3fn, got {k_cache.dtype} and {v_cache.dtype}")
-        if k_cache.dtype != torch.float8_e4m3fn:
-            raise TypeError(f"{k_cache.dtype} caches are not supported: an fp8 cache is torch.float8_e4m3fn (OCP e4m3, the gfx950 encoding; "
-                            "float8_e4m3fnuz is MI300's, float8_e5m2 is out of scope)")
-        if q.dtype not in (torch.float16, torch.bfloat16):
-            raise TypeError(f"fp8 caches take float16 or bfloat16 q, k_new and v_new, got a {q.dtype} q")
-        for name, t in (("k_new", k_new), ("v_new", v_new)):
-            if t is not None and t.dtype != q.dtype:
-                raise TypeError(f"{name} must have q's dtype ({q.dtype}), got {t.dtype}")
-    elif k_scale is not None or v_scale is not None:
-        raise TypeError(f"k_scale / v_scale given with {k_cache.dtype} caches: scales belong to torch.float8_e4m3fn caches")
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_new, v_new)):
-        raise RuntimeError("flash_cosine_sim_attention_with_kvcache is forward-only: q, k_new and v_new must not require grad "
-                           "(run it under torch.no_grad())")
-    for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
-        if t.dim() != 4:
-            raise ValueError(f"{name} must have 4 dimensions, got {tuple(t.shape)}")
-    if k_cache.shape != v_cache.shape:
-        raise ValueError(f"k_cache and v_cache must have the same shape, got {tuple(k_cache.shape)} and {tuple(v_cache.shape)}")
-    if (k_new is None) != (v_new is None):
-        raise ValueError("k_new and v_new must be given together")
+    q_fault = None if q.dim() == 4 else f"q must have 4 dimensions, got {tuple(q.shape)}"
+    c = _CacheCall("flash_cosine_sim_attention_with_kvcache", q, q_fault, k_cache, v_cache, k_new, v_new, k_scale, v_scale)
     B, H, N, D = q.shape
-    Hk = k_cache.shape[1]
-    if k_cache.shape[3] != D:
-        raise ValueError("query, key, value dimensions must be the same")
-    if Hk < 1 or H % Hk:
-        raise ValueError(f"k/v heads must divide q heads ({H}), got {Hk}")
     if k_new is not None:
-        if k_new.shape != v_new.shape or k_new.dim() != 4 or tuple(k_new.shape[:2]) != (B, Hk) or k_new.shape[3] != D:
-            raise ValueError(f"k_new / v_new must be [{B}, {Hk}, N_new, {D}], got {tuple(k_new.shape)} and {tuple(v_new.shape)}")
+        if k_new.shape != v_new.shape or k_new.dim() != 4 or tuple(k_new.shape[:2]) != (B, c.Hk) or k_new.shape[3] != D:
+            raise ValueError(f"k_new / v_new must be [{B}, {c.Hk}, N_new, {D}], got {tuple(k_new.shape)} and {tuple(v_new.shape)}")
     n_new = 0 if k_new is None else k_new.shape[2]
-    if block_table is not None:
-        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B:
-            raise TypeError(f"block_table must be an int32 [batch, max_blocks] tensor")
-        page = k_cache.shape[2]
-        if page <= 0 or page % 16:
-            raise ValueError(f"page_size ({page}) must be a positive multiple of 16")
-        capacity = block_table.shape[1] * page
-    else:
-        if k_cache.shape[0] != B:
-            raise ValueError(f"batch mismatch between q ({B}) and the caches ({k_cache.shape[0]})")
-        capacity = k_cache.shape[2]
-    host_lens = None
-    if cache_seqlens is None:
-        if n_new:
-            raise ValueError("k_new given but cache_seqlens is None (every sequence full): there is no slot to append to")
-    elif isinstance(cache_seqlens, int):
-        host_lens = [int(cache_seqlens)] * B
-    else:
-        if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32 or cache_seqlens.shape != (B,):
-            raise TypeError(f"cache_seqlens must be an int or an int32 tensor of shape ({B},)")
-        if cache_seqlens.device.type == "cpu":
-            host_lens = [int(x) for x in cache_seqlens.tolist()]
-    if host_lens is not None:
-        for b, n0 in enumerate(host_lens):
-            if n0 < 0 or n0 + n_new > capacity:
-                raise ValueError(f"sequence {b}: cache_seqlens {n0} + {n_new} new tokens outside [0, capacity {capacity}]")
-        if block_table is not None and block_table.device.type == "cpu":
-            nb = k_cache.shape[0]
-            for b, n0 in enumerate(host_lens):
-                used = block_table[b, :(n0 + n_new + page - 1) // page]
-                if used.numel() and (int(used.min()) < 0 or int(used.max()) >= nb):
-                    raise ValueError(f"sequence {b}: block_table entries outside [0, {nb})")
-    if max_seqlen_k is not None and (int(max_seqlen_k) != max_seqlen_k or max_seqlen_k < 0):
-        raise ValueError(f"max_seqlen_k must be a non-negative integer, got {max_seqlen_k}")
-    if fp8:
-        k_scale, v_scale = _cache_scale("k_scale", k_scale, B, Hk, q.device), _cache_scale("v_scale", v_scale, B, Hk, q.device)
+    c.tables(B, None, bool(n_new), cache_seqlens, block_table, max_seqlen_k)
     if q.device.type == "cpu":
-        lens = host_lens if host_lens is not None else [capacity - n_new] * B
-        if cache_seqlens is not None and host_lens is None:
+        if cache_seqlens is not None and c.lens is None:
             raise ValueError("CPU tensors take host cache_seqlens")
+        lens = c.lens if c.lens is not None else [c.capacity - n_new] * B
         detach = lambda t: None if t is None else t.detach()          # (grad mode is off here, or nothing requires grad)
-        quant = dict(k_scale=k_scale.expand(B, Hk), v_scale=v_scale.expand(B, Hk)) if fp8 else {}
         return _cpu.attention_forward_kvcache_cpu(q.detach(), k_cache, v_cache, detach(k_new), detach(v_new), lens, block_table,
                                                   scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, window_size=window,
-                                                  return_lse=bool(return_lse), **quant)
-    if isinstance(cache_seqlens, int):
-        cache_seqlens = torch.full((B,), cache_seqlens, dtype=torch.int32, device=q.device)
-    elif cache_seqlens is not None:
-        cache_seqlens = cache_seqlens.to(q.device, non_blocking=True)
-    if block_table is not None:
-        block_table = block_table.to(q.device, non_blocking=True)
-    max_k = capacity if max_seqlen_k is None else min(int(max_seqlen_k), capacity)
+                                                  return_lse=bool(return_lse), **c.cpu_quant())
+    k_cache, v_cache, cache_seqlens, block_table = c.on_device()
+    tail = (float(scale), bool(causal), bool(l2norm_qk), int(groups))
     if return_lse:      # every route through one op: the same append and decode launches, a combine that also writes the lse
-        if fp8:
-            k_cache, v_cache = k_cache.view(torch.uint8), v_cache.view(torch.uint8)
-        o, lse = _torch_ops.load().kvcache_lse_forward(q, k_cache, v_cache, None, k_new, v_new, cache_seqlens, block_table, k_scale, v_scale, 0,
-                                                       int(max_k), float(scale), bool(causal), bool(l2norm_qk), int(groups), window[0], window[1])
-        return o, lse
-    if fp8:
-        # (the op takes the codes as bytes: same storage, so the append lands in the caller's caches)
-        return _torch_ops.load().kvcache_fp8_forward(q, k_cache.view(torch.uint8), v_cache.view(torch.uint8), k_new, v_new, cache_seqlens, block_table, k_scale, v_scale,
-                                                     int(max_k), float(scale), bool(causal), bool(l2norm_qk), int(groups), window[0], window[1])
+        return _torch_ops.load().kvcache_lse_forward(q, k_cache, v_cache, None, k_new, v_new, cache_seqlens, block_table, c.k_scale, c.v_scale, 0,
+                                                     c.max_k, *tail, window[0], window[1])
+    if c.fp8:
+        return _torch_ops.load().kvcache_fp8_forward(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, c.k_scale, c.v_scale, c.max_k,
+                                                     *tail, window[0], window[1])
     if window != (-1, -1):
-        return _torch_ops.load().kvcache_window_forward(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, int(max_k),
-                                                        float(scale), bool(causal), bool(l2norm_qk), int(groups), window[0], window[1])
-    return _torch_ops.load().kvcache_forward(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, int(max_k), float(scale),
-                                             bool(causal), bool(l2norm_qk), int(groups))
+        return _torch_ops.load().kvcache_window_forward(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, c.max_k, *tail,
+                                                        window[0], window[1])
+    return _torch_ops.load().kvcache_forward(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, c.max_k, *tail)
 
 
 def flash_cosine_sim_attention_varlen_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new=None, v_new=None, cache_seqlens=None,
@@ -443,114 +498,33 @@ def flash_cosine_sim_attention_varlen_with_kvcache(q, k_cache, v_cache, cu_seqle
     return_lse=True: returns (o, lse) with lse float32 [total_q, H], as in `flash_cosine_sim_attention_with_kvcache`."""
     _check_return_lse(return_lse)
     window = _window(window_size)
-    fp8_types = tuple(getattr(torch, n) for n in ("float8_e4m3fn", "float8_e4m3fnuz", "float8_e5m2", "float8_e5m2fnuz") if hasattr(torch, n))
-    fp8 = k_cache.dtype in fp8_types or v_cache.dtype in fp8_types
-    if fp8:
-        if k_cache.dtype != torch.float8_e4m3fn or v_cache.dtype != torch.float8_e4m3fn:
-            raise TypeError(f"an fp8 cache is torch.float8_e4m3fn for both k_cache and v_cache (OCP e4m3, the gfx950 encoding), got "
-                            f"{k_cache.dtype} and {v_cache.dtype}")
-        if q.dtype not in (torch.float16, torch.bfloat16):
-            raise TypeError(f"fp8 caches take float16 or bfloat16 q, k_new and v_new, got a {q.dtype} q")
-        for name, t in (("k_new", k_new), ("v_new", v_new)):
-            if t is not None and t.dtype != q.dtype:
-                raise TypeError(f"{name} must have q's dtype ({q.dtype}), got {t.dtype}")
-    elif k_scale is not None or v_scale is not None:
-        raise TypeError(f"k_scale / v_scale given with {k_cache.dtype} caches: scales belong to torch.float8_e4m3fn caches")
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_new, v_new)):
-        raise RuntimeError("flash_cosine_sim_attention_varlen_with_kvcache is forward-only: q, k_new and v_new must not require grad "
-                           "(run it under torch.no_grad())")
-    if q.dim() != 3:
-        raise ValueError(f"q must be a packed [total_q, heads, dim_head] tensor, got {tuple(q.shape)}")
-    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
-        if t.dim() != 4:
-            raise ValueError(f"{name} must have 4 dimensions, got {tuple(t.shape)}")
-    if k_cache.shape != v_cache.shape:
-        raise ValueError(f"k_cache and v_cache must have the same shape, got {tuple(k_cache.shape)} and {tuple(v_cache.shape)}")
-    if (k_new is None) != (v_new is None):
-        raise ValueError("k_new and v_new must be given together")
+    q_fault = None if q.dim() == 3 else f"q must be a packed [total_q, heads, dim_head] tensor, got {tuple(q.shape)}"
+    c = _CacheCall("flash_cosine_sim_attention_varlen_with_kvcache", q, q_fault, k_cache, v_cache, k_new, v_new, k_scale, v_scale)
     if not isinstance(cu_seqlens_q, torch.Tensor) or cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 1:
         raise TypeError("cu_seqlens_q must be a 1-D int32 tensor of sequences + 1 entries")
     total_q, H, D = q.shape
     B = cu_seqlens_q.numel() - 1
-    Hk = k_cache.shape[1]
-    if k_cache.shape[3] != D:
-        raise ValueError("query, key, value dimensions must be the same")
-    if Hk < 1 or H % Hk:
-        raise ValueError(f"k/v heads must divide q heads ({H}), got {Hk}")
-    if k_new is not None and (k_new.shape != v_new.shape or tuple(k_new.shape) != (total_q, Hk, D)):
-        raise ValueError(f"k_new / v_new must be packed like q, [{total_q}, {Hk}, {D}], got {tuple(k_new.shape)} and {tuple(v_new.shape)}")
-    if block_table is not None:
-        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B:
-            raise TypeError(f"block_table must be an int32 [sequences, max_blocks] tensor")
-        page = k_cache.shape[2]
-        if page <= 0 or page % 16:
-            raise ValueError(f"page_size ({page}) must be a positive multiple of 16")
-        capacity = block_table.shape[1] * page
-    else:
-        if k_cache.shape[0] != B:
-            raise ValueError(f"batch mismatch between cu_seqlens_q ({B} sequences) and the caches ({k_cache.shape[0]})")
-        capacity = k_cache.shape[2]
-    for name, m in (("max_seqlen_q", max_seqlen_q), ("max_seqlen_k", max_seqlen_k)):
-        if m is not None and (int(m) != m or m < 0):
-            raise ValueError(f"{name} must be a non-negative integer, got {m}")
-    host_counts = None
+    if k_new is not None and (k_new.shape != v_new.shape or tuple(k_new.shape) != (total_q, c.Hk, D)):
+        raise ValueError(f"k_new / v_new must be packed like q, [{total_q}, {c.Hk}, {D}], got {tuple(k_new.shape)} and {tuple(v_new.shape)}")
+    if max_seqlen_q is not None and (int(max_seqlen_q) != max_seqlen_q or max_seqlen_q < 0):
+        raise ValueError(f"max_seqlen_q must be a non-negative integer, got {max_seqlen_q}")
     if cu_seqlens_q.device.type == "cpu":
         _check_host_cu("cu_seqlens_q", cu_seqlens_q, total_q, None)
-        c = cu_seqlens_q.tolist()
-        host_counts = [b - a for a, b in zip(c[:-1], c[1:])]
-    host_lens = None
-    if cache_seqlens is None:
-        if k_new is not None:
-            raise ValueError("k_new given but cache_seqlens is None (every sequence full): there is no slot to append to")
-    elif isinstance(cache_seqlens, int):
-        host_lens = [int(cache_seqlens)] * B
-    else:
-        if not isinstance(cache_seqlens, torch.Tensor) or cache_seqlens.dtype != torch.int32 or cache_seqlens.shape != (B,):
-            raise TypeError(f"cache_seqlens must be an int or an int32 tensor of shape ({B},)")
-        if cache_seqlens.device.type == "cpu":
-            host_lens = [int(x) for x in cache_seqlens.tolist()]
-    if host_lens is not None:
-        for b, n0 in enumerate(host_lens):
-            n_new = host_counts[b] if (k_new is not None and host_counts is not None) else 0
-            if n0 < 0 or n0 + n_new > capacity:
-                raise ValueError(f"sequence {b}: cache_seqlens {n0} + {n_new} new tokens outside [0, capacity {capacity}]")
-        if block_table is not None and block_table.device.type == "cpu":
-            nb = k_cache.shape[0]
-            for b, n0 in enumerate(host_lens):
-                n_new = host_counts[b] if (k_new is not None and host_counts is not None) else 0
-                used = block_table[b, :(n0 + n_new + page - 1) // page]
-                if used.numel() and (int(used.min()) < 0 or int(used.max()) >= nb):
-                    raise ValueError(f"sequence {b}: block_table entries outside [0, {nb})")
-    if fp8:
-        k_scale, v_scale = _cache_scale("k_scale", k_scale, B, Hk, q.device), _cache_scale("v_scale", v_scale, B, Hk, q.device)
+    c.tables(B, cu_seqlens_q, k_new is not None, cache_seqlens, block_table, max_seqlen_k)
     if q.device.type == "cpu":
-        if host_counts is None or (cache_seqlens is not None and host_lens is None):
+        if c.counts is None or (cache_seqlens is not None and c.lens is None):
             raise ValueError("CPU tensors take host cu_seqlens_q and cache_seqlens tables")
-        lens = host_lens if host_lens is not None else [capacity] * B
+        lens = c.lens if c.lens is not None else [c.capacity] * B
         detach = lambda t: None if t is None else t.detach()          # (grad mode is off here, or nothing requires grad)
-        quant = dict(k_scale=k_scale.expand(B, Hk), v_scale=v_scale.expand(B, Hk)) if fp8 else {}
         return _cpu.attention_forward_kvcache_varlen_cpu(q.detach(), k_cache, v_cache, cu_seqlens_q, detach(k_new), detach(v_new), lens,
                                                          block_table, scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk,
-                                                         window_size=window, return_lse=bool(return_lse), **quant)
+                                                         window_size=window, return_lse=bool(return_lse), **c.cpu_quant())
     cu_q = cu_seqlens_q.to(q.device, non_blocking=True)
-    if isinstance(cache_seqlens, int):
-        cache_seqlens = torch.full((B,), cache_seqlens, dtype=torch.int32, device=q.device)
-    elif cache_seqlens is not None:
-        cache_seqlens = cache_seqlens.to(q.device, non_blocking=True)
-    if block_table is not None:
-        block_table = block_table.to(q.device, non_blocking=True)
+    k_cache, v_cache, cache_seqlens, block_table = c.on_device()
     max_q = total_q if max_seqlen_q is None else min(int(max_seqlen_q), total_q)
-    max_k = capacity if max_seqlen_k is None else min(int(max_seqlen_k), capacity)
-    if fp8:      # (the op takes the codes as bytes: same storage, so the append lands in the caller's caches)
-        k_cache, v_cache = k_cache.view(torch.uint8), v_cache.view(torch.uint8)
-    if return_lse:
-        o, lse = _torch_ops.load().kvcache_lse_forward(q, k_cache, v_cache, cu_q, k_new, v_new, cache_seqlens, block_table, k_scale, v_scale,
-                                                       int(max_q), int(max_k), float(scale), bool(causal), bool(l2norm_qk), int(groups),
-                                                       window[0], window[1])
-        return o, lse
-    return _torch_ops.load().kvcache_varlen_forward(q, k_cache, v_cache, cu_q, k_new, v_new, cache_seqlens, block_table, k_scale, v_scale,
-                                                    int(max_q), int(max_k), float(scale), bool(causal), bool(l2norm_qk), int(groups),
-                                                    window[0], window[1])
+    op = _torch_ops.load().kvcache_lse_forward if return_lse else _torch_ops.load().kvcache_varlen_forward
+    return op(q, k_cache, v_cache, cu_q, k_new, v_new, cache_seqlens, block_table, c.k_scale, c.v_scale, max_q, c.max_k, float(scale), bool(causal),
+              bool(l2norm_qk), int(groups), window[0], window[1])
 
 
 # ---------------------------------------------------------------------------------------------
@@ -669,25 +643,11 @@ def flash_cosine_sim_attention_with_shared_prefix(q, prefix_k_cache, prefix_v_ca
     if isinstance(plen, int) and not 0 <= plen <= prefix_cap:
         raise ValueError(f"prefix_len {plen} outside [0, prefix capacity {prefix_cap}]")
     if causal:      # N_b <= L_b + 1 with L_b = cached + appended, as far as the host can see the tables
-        counts = appended = None
-        if ragged:
-            if isinstance(cu_seqlens_q, torch.Tensor) and cu_seqlens_q.device.type == "cpu" and cu_seqlens_q.dim() == 1:
-                c = cu_seqlens_q.tolist()
-                counts = [hi - lo for lo, hi in zip(c[:-1], c[1:])]
-                appended = counts if k_new is not None else [0] * len(counts)
-        else:
-            counts = [q.shape[2]] * q.shape[0]
-            appended = [k_new.shape[2] if isinstance(k_new, torch.Tensor) and k_new.dim() == 4 else 0] * q.shape[0]
-        lens = None
-        if counts is not None:
-            if cache_seqlens is None and k_cache.dim() == 4:      # every sequence full
-                lens = [block_table.shape[1] * k_cache.shape[2] if isinstance(block_table, torch.Tensor) and block_table.dim() == 2
-                        else k_cache.shape[2]] * len(counts)
-            elif isinstance(cache_seqlens, int):
-                lens = [cache_seqlens] * len(counts)
-            elif isinstance(cache_seqlens, torch.Tensor) and cache_seqlens.device.type == "cpu":
-                lens = cache_seqlens.tolist()
-        if lens is not None and any(n > length + new + 1 for n, length, new in zip(counts, lens, appended)):
+        counts, lens, appended = _host_view(q, cu_seqlens_q, k_new, cache_seqlens)
+        if counts is not None and cache_seqlens is None and k_cache.dim() == 4:      # every sequence full
+            lens = [block_table.shape[1] * k_cache.shape[2] if isinstance(block_table, torch.Tensor) and block_table.dim() == 2
+                    else k_cache.shape[2]] * len(counts)
+        if counts is not None and lens is not None and any(n > length + new + 1 for n, length, new in zip(counts, lens, appended)):
             raise ValueError("causal with a shared prefix needs every query behind the prefix (N_b <= L_b + 1, L_b counting this call's "
                              "append): a query placed inside the prefix needs a causal cut that the one-sequence prefix phase cannot express")
     own = dict(k_new=k_new, v_new=v_new, cache_seqlens=cache_seqlens, block_table=block_table, max_seqlen_k=max_seqlen_k, scale=scale,
