@@ -362,8 +362,6 @@ int fcsa_l2norm(int32_t dtype, int32_t batch, int32_t heads, int32_t len, int32_
   return timed("l2norm", "l2norm", s, [&] { return fcsa::launch_l2norm(dtype, np, s); });
 }
 
-static size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-
 // split-key forward (fcsa::forward_splits: bias-free launches only): the count, and its workspace -- partial P~V, then partial row sums
 static int forward_splits(const fcsa_problem& p) {
   if (p.batch <= 0 || p.heads <= 0 || p.q_len <= 0 || p.dim_head <= 0) return 1;
@@ -372,7 +370,7 @@ static int forward_splits(const fcsa_problem& p) {
 static size_t forward_ws_bytes(const fcsa_problem& p, int splits) {
   if (splits <= 1) return 0;
   const size_t rows = (size_t)splits * p.batch * p.heads * p.q_len;
-  return align256(rows * p.dim_head * 4) + align256(rows * 4);
+  return align_up(rows * p.dim_head * 4, 256) + align_up(rows * 4, 256);
 }
 
 size_t fcsa_forward_workspace_bytes(const fcsa_problem* p) { return p == nullptr ? 0 : forward_ws_bytes(*p, forward_splits(*p)); }
@@ -425,22 +423,69 @@ int fcsa_forward_window(const fcsa_forward_args* a, const fcsa_varlen* seqs, con
 
 namespace {
 
-// ---- decoding against a key/value cache (fcsa_forward_kvcache) -------------------------------------------------------------------------
-// The plan of a decode call: row tiles of the G x N rows of a K/V head, and the split count of the key range (fcsa::decode_splits: a pure
-// function of the shapes and the CU count, never of device table contents).
-struct DecodePlan { int row_tiles, splits; size_t ws_o, ws_ml, total; };
-DecodePlan decode_plan(const fcsa_problem& p, const fcsa_kvcache& kv, int win_lo = -1) {
+// ---- decoding against a key/value cache (fcsa_forward_kvcache and its _window, _quant, _varlen and _lse forms) ------------------------
+// One description of a decode call, one plan and one implementation (decode_call) behind the five entry points: what an entry point adds
+// to the plain call is an optional part of the description.
+struct DecodeCall {
+  const fcsa_forward_args* a;
+  const fcsa_kvcache* kv;
+  const fcsa_varlen* seqs;            // a ragged step (fcsa_forward_kvcache_varlen): packed queries with per-sequence counts, or NULL
+  const fcsa_kvcache_quant* qz;       // an fp8 cache (fcsa_forward_kvcache_quant), or NULL
+  const fcsa_window* w;               // a sliding window as the caller gave it, or NULL
+  const fcsa_lse_out* lse;            // where the combine also writes the rows' log-sum-exp (fcsa_forward_kvcache_lse), or NULL
+};
+
+// The window of a decode call as the kernels take it.  A rectangular call is normalised (fcsa::win_normalise): a window that hides nothing
+// is fcsa_forward_kvcache itself (windowed == 0) with `causal` saying which of its two forms.  A ragged step does no collapsing (every
+// sequence has its own N_b and L_b): its one entry point per cache type always gets sides, open ones (kWinOpen; causal: hi = 0) for a call
+// without a window.
+struct DecodeWindow {
+  int windowed, lo, hi, causal;
+  int reach() const { return windowed ? lo : fcsa::kWinOpen; }      // the left side the split rule counts keys with
+};
+DecodeWindow decode_window(const fcsa_problem& p, const fcsa_kvcache& kv, bool ragged, const fcsa_window* w) {
+  if (ragged) {
+    const int lo = w == nullptr || w->left < 0 ? fcsa::kWinOpen : std::min(w->left, fcsa::kWinOpen);
+    const int hi = p.causal ? 0 : (w == nullptr || w->right < 0 ? fcsa::kWinOpen : std::min(w->right, fcsa::kWinOpen));
+    return {1, lo, hi, p.causal};
+  }
+  if (w == nullptr) return {0, 0, 0, p.causal};
+  int lo, hi;
+  const int max_k = std::min(std::max(p.k_len, 0), std::max(kv.capacity, 0));
+  const fcsa::WinKind kind = fcsa::win_normalise(p.q_len, max_k, p.causal != 0, w->left, w->right, lo, hi);
+  if (kind == fcsa::WinKind::Window) return {1, lo, hi, p.causal};
+  return {0, 0, 0, kind == fcsa::WinKind::Causal ? 1 : 0};
+}
+
+// The plan of a decode call: the row tiles of a K/V head -- rectangular: row_tiles per sequence over its G x N rows; ragged: fcsa::ragged_slots
+// flat slots over all sequences (sized from total_q, never from batch x max_seqlen_q) -- the split count of the key range over them
+// (fcsa::decode_splits) and the workspace: f32 partial P~V, then (row max, row sum), of every split of every row.  A pure function of the
+// shapes and the CU count, never of device table contents.  win_lo: DecodeWindow::reach().
+struct DecodePlan { int row_tiles; int64_t slots; int splits; size_t ws_ml, total; };
+DecodePlan decode_plan(const fcsa_problem& p, const fcsa_kvcache& kv, const fcsa_varlen* seqs, int win_lo) {
   DecodePlan d;
   const int G = p.kv_heads > 0 ? p.heads / p.kv_heads : 0;
-  d.row_tiles = std::max(fcsa::decode_row_tiles(G * p.q_len), 1);
-  int max_k = std::min(std::max(p.k_len, 0), std::max(kv.capacity, 0));
-  if (win_lo >= 0) max_k = fcsa::win_decode_keys(max_k, p.q_len, win_lo);      // all a sequence reads under a window
-  d.splits = fcsa::decode_splits(p.batch, p.kv_heads, d.row_tiles, max_k, p.dim_head, fcsa::cu_count());
-  const size_t rows = (size_t)std::max(p.batch, 0) * std::max(p.heads, 0) * std::max(p.q_len, 0);
-  d.ws_o = 0;
-  d.ws_ml = align256(rows * d.splits * std::max(p.dim_head, 0) * 4);
-  d.total = rows == 0 ? 0 : d.ws_ml + align256(rows * d.splits * 8);
+  const int max_k = fcsa::win_decode_keys(std::min(std::max(p.k_len, 0), std::max(kv.capacity, 0)), std::max(p.q_len, 0), win_lo);
+  size_t rows;
+  if (seqs != nullptr) {
+    const int64_t total_q = std::max<int64_t>(seqs->total_q, 0);
+    d.row_tiles = 0;
+    d.slots = fcsa::ragged_slots(total_q, std::max(p.batch, 0), G);
+    d.splits = fcsa::decode_splits(1, p.kv_heads, (int)std::min<int64_t>(d.slots, INT32_MAX), max_k, p.dim_head, fcsa::cu_count());
+    rows = (size_t)total_q * std::max(p.heads, 0);
+  } else {
+    d.row_tiles = std::max(fcsa::decode_row_tiles(G * p.q_len), 1);
+    d.slots = 0;
+    d.splits = fcsa::decode_splits(p.batch, p.kv_heads, d.row_tiles, max_k, p.dim_head, fcsa::cu_count());
+    rows = (size_t)std::max(p.batch, 0) * std::max(p.heads, 0) * std::max(p.q_len, 0);
+  }
+  d.ws_ml = align_up(rows * d.splits * std::max(p.dim_head, 0) * 4, 256);
+  d.total = rows == 0 ? 0 : d.ws_ml + align_up(rows * d.splits * 8, 256);
   return d;
+}
+size_t decode_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_window* w) {
+  if (p == nullptr || kv == nullptr) return 0;
+  return decode_plan(*p, *kv, seqs, decode_window(*p, *kv, seqs != nullptr, w).reach()).total;
 }
 
 // cache_es: bytes of a cache element (0: the problem's type; 1: an fp8 cache, fcsa_forward_kvcache_quant)
@@ -476,52 +521,14 @@ int check_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv, int cache_
     if (int rc = check_tensor("v_new", kv->v_new, es, true)) return rc;
   }
   if (rows) {
-    const DecodePlan d = decode_plan(p, *kv);
+    const DecodePlan d = decode_plan(p, *kv, nullptr, fcsa::kWinOpen);
     if ((int64_t)p.batch * p.kv_heads * d.row_tiles * d.splits > INT32_MAX) return fail(FCSA_ERR_UNSUPPORTED, "kvcache: grid above 2^31 workgroups");
   }
   return FCSA_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t fcsa_forward_kvcache_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv) {
-  if (p == nullptr || kv == nullptr) return 0;
-  return decode_plan(*p, *kv).total;
-}
-
-// the kernels' window sides of a decode call, or false: the call is fcsa_forward_kvcache itself (`causal` says which)
-static bool decode_window_sides(const fcsa_problem& p, const fcsa_kvcache& kv, const fcsa_window& w, WindowCall& win, int& causal) {
-  const int max_k = std::min(std::max(p.k_len, 0), std::max(kv.capacity, 0));
-  const fcsa::WinKind kind = fcsa::win_normalise(p.q_len, max_k, p.causal != 0, w.left, w.right, win.lo, win.hi);
-  causal = kind == fcsa::WinKind::Causal ? 1 : kind == fcsa::WinKind::Full ? 0 : p.causal;
-  return kind == fcsa::WinKind::Window;
-}
-// lse: NULL, or where the combine also writes the rows' log-sum-exp (fcsa_forward_kvcache_lse: the "decode_combine_lse*" launches)
-static int forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv, const WindowCall* win, const fcsa_kvcache_quant* qz = nullptr,
-                           const fcsa_lse_out* lse = nullptr);
-
-size_t fcsa_forward_kvcache_window_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv, const fcsa_window* w) {
-  if (p == nullptr || kv == nullptr || w == nullptr) return 0;
-  WindowCall win;
-  int causal = 0;
-  return decode_window_sides(*p, *kv, *w, win, causal) ? decode_plan(*p, *kv, win.lo).total : decode_plan(*p, *kv).total;
-}
-
-int fcsa_forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv) { return forward_kvcache(a, kv, nullptr); }
-
-int fcsa_forward_kvcache_window(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_window* w) {
-  if (int rc = check_kvcache(a, kv)) return rc;
-  if (int rc = check_window(w, false, false)) return rc;
-  WindowCall win;
-  fcsa_forward_args na = *a;
-  if (!decode_window_sides(a->p, *kv, *w, win, na.p.causal)) return forward_kvcache(&na, kv, nullptr);
-  return forward_kvcache(a, kv, &win);
-}
-
-// what fcsa_forward_kvcache_quant checks before anything else
-static int check_quant(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_kvcache_quant* qz) {
+// an fp8 cache: what is checked before anything else, then the cache checks with one-byte elements
+int check_quant(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_kvcache_quant* qz) {
   if (a == nullptr || kv == nullptr || qz == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_quant: null argument");
   if (qz->cache_dtype != FCSA_CACHE_E4M3)
     return fail(FCSA_ERR_UNSUPPORTED, "kvcache_quant: cache type %d not supported (expected FCSA_CACHE_E4M3 = %d, OCP e4m3fn)", qz->cache_dtype, FCSA_CACHE_E4M3);
@@ -530,116 +537,17 @@ static int check_quant(const fcsa_forward_args* a, const fcsa_kvcache* kv, const
   return check_kvcache(a, kv, 1);
 }
 
-size_t fcsa_forward_kvcache_quant_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv, const fcsa_kvcache_quant* qz, const fcsa_window* w) {
-  if (qz == nullptr) return 0;
-  return w != nullptr ? fcsa_forward_kvcache_window_workspace_bytes(p, kv, w) : fcsa_forward_kvcache_workspace_bytes(p, kv);
-}
-
-int fcsa_forward_kvcache_quant(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_kvcache_quant* qz, const fcsa_window* w) {
-  if (int rc = check_quant(a, kv, qz)) return rc;
-  if (w == nullptr) return forward_kvcache(a, kv, nullptr, qz);
-  if (int rc = check_window(w, false, false)) return rc;
-  WindowCall win;
-  fcsa_forward_args na = *a;
-  if (!decode_window_sides(a->p, *kv, *w, win, na.p.causal)) return forward_kvcache(&na, kv, nullptr, qz);
-  return forward_kvcache(a, kv, &win, qz);
-}
-
-static int forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv, const WindowCall* win, const fcsa_kvcache_quant* qz,
-                           const fcsa_lse_out* lse) {
-  if (int rc = qz != nullptr ? check_quant(a, kv, qz) : check_kvcache(a, kv)) return rc;
-  const fcsa_problem& p = a->p;
-  if (p.batch == 0) return FCSA_OK;
-  const int es = elem_size(p.dtype);
-  hipStream_t s = static_cast<hipStream_t>(a->stream);
-  const DecodePlan d = decode_plan(p, *kv, win != nullptr ? win->lo : -1);
-  const bool rows = p.heads > 0 && p.q_len > 0;
-  if (rows) {
-    if (a->workspace == nullptr || a->workspace_bytes < d.total)
-      return fail(FCSA_ERR_WORKSPACE, "kvcache: workspace too small: %zu < %zu bytes", a->workspace_bytes, d.total);
-    if ((reinterpret_cast<uintptr_t>(a->workspace) & 255) != 0) return fail(FCSA_ERR_WORKSPACE, "kvcache: workspace not 256-byte aligned");
-  }
-  fcsa::DecodeFp8Params dp;      // the 16-bit kernels get its DecodeParams / DecodeWinParams part
-  const int ces = qz != nullptr ? 1 : es;
-  dp.q = view(a->q, es);
-  dp.o = view(a->o, es);
-  dp.kc = view(kv->k_cache, ces);
-  dp.vc = view(kv->v_cache, ces);
-  dp.kn = view(kv->k_new, es);
-  dp.vn = view(kv->v_new, es);
-  dp.seqlens = kv->cache_seqlens;
-  dp.table = kv->block_table;
-  dp.table_stride = kv->block_table_stride;
-  dp.capacity = kv->capacity;
-  dp.page = kv->block_table != nullptr ? kv->page_size : 0;
-  dp.num_blocks = kv->num_blocks;
-  dp.new_len = kv->new_len;
-  dp.B = p.batch; dp.H = p.heads; dp.Hk = p.kv_heads; dp.G = p.heads / p.kv_heads; dp.N = p.q_len;
-  dp.row_tiles = d.row_tiles; dp.splits = d.splits;
-  dp.causal = p.causal; dp.l2norm = p.l2norm_qk; dp.groups = p.l2norm_qk ? p.groups : 1;
-  dp.c1 = p.scale * kLog2e;
-  dp.c2 = exponent_shift(p, false) * kLog2e;
-  dp.l_eps = rowsum_eps(p, false);
-  dp.dyn = dynamic_shift(p, false) ? 1 : 0;
-  dp.ws_o = static_cast<float*>(a->workspace);
-  dp.ws_ml = reinterpret_cast<float*>(static_cast<char*>(a->workspace) + d.ws_ml);
-  if (win != nullptr) { dp.window = 1; dp.win_lo = win->lo; dp.win_hi = win->hi; }
-  const fcsa::DecodeLseOut lo = lse != nullptr ? fcsa::DecodeLseOut{lse->lse, lse->stride0, lse->stride1, lse->stride2} : fcsa::DecodeLseOut{};
-  if (qz != nullptr) {
-    dp.k_scale = qz->k_scale; dp.v_scale = qz->v_scale;
-    dp.ks_b = qz->k_scale_stride0; dp.ks_h = qz->k_scale_stride1;
-    dp.vs_b = qz->v_scale_stride0; dp.vs_h = qz->v_scale_stride1;
-    if (kv->new_len > 0 && kv->capacity > 0) {
-      if (int rc = timed("kv_append_fp8", "kv append (fp8)", s, [&] { return fcsa::launch_kv_append_fp8(p.dtype, p.dim_head, dp, s); })) return rc;
-    }
-    if (!rows) return FCSA_OK;
-    if (int rc = timed("decode_fp8", "decode (fp8)", s, [&] { return fcsa::launch_decode_fp8(p.dtype, p.dim_head, dp, s); })) return rc;
-    if (lse != nullptr)
-      return timed("decode_combine_lse_fp8", "decode combine (lse, fp8)", s, [&] { return fcsa::launch_decode_combine_lse_fp8(p.dtype, p.dim_head, dp, lo, s); });
-    return timed("decode_combine_fp8", "decode combine (fp8)", s, [&] { return fcsa::launch_decode_combine_fp8(p.dtype, p.dim_head, dp, s); });
-  }
-  // 1. the append (before anything reads the cache: same stream), 2. the split partials, 3. their combine
-  if (kv->new_len > 0 && kv->capacity > 0) {
-    if (int rc = timed("kv_append", "kv append", s, [&] { return fcsa::launch_kv_append(p.dtype, p.dim_head, dp, s); })) return rc;
-  }
-  if (!rows) return FCSA_OK;
-  if (int rc = timed("decode", "decode", s, [&] { return fcsa::launch_decode(p.dtype, p.dim_head, dp, s); })) return rc;
-  if (lse != nullptr)
-    return timed("decode_combine_lse", "decode combine (lse)", s, [&] { return fcsa::launch_decode_combine_lse(p.dtype, p.dim_head, dp, lo, s); });
-  return timed("decode_combine", "decode combine", s, [&] { return fcsa::launch_decode_combine(p.dtype, p.dim_head, dp, s); });
-}
-
-// ---- ragged decode steps (fcsa_forward_kvcache_varlen): packed queries with per-sequence counts against the cache --------------------
-// The plan: fcsa::ragged_slots flat row-tile slots per K/V head (sized from total_q, never from batch x max_seqlen_q) and the split count
-// of fcsa::decode_splits over them -- a pure function of the shapes and the CU count, never of device table contents.
-struct RaggedPlan { int64_t slots; int splits; size_t ws_ml, total; };
-static RaggedPlan ragged_plan(const fcsa_problem& p, const fcsa_kvcache& kv, int64_t total_q, int win_lo) {
-  RaggedPlan d;
-  const int G = p.kv_heads > 0 ? p.heads / p.kv_heads : 0;
-  total_q = std::max<int64_t>(total_q, 0);
-  d.slots = fcsa::ragged_slots(total_q, std::max(p.batch, 0), G);
-  int max_k = std::min(std::max(p.k_len, 0), std::max(kv.capacity, 0));
-  max_k = fcsa::win_decode_keys(max_k, std::max(p.q_len, 0), win_lo);      // all a sequence reads under a window (open: max_k itself)
-  d.splits = fcsa::decode_splits(1, p.kv_heads, (int)std::min<int64_t>(d.slots, INT32_MAX), max_k, p.dim_head, fcsa::cu_count());
-  const size_t rows = (size_t)total_q * std::max(p.heads, 0);
-  d.ws_ml = align256(rows * d.splits * std::max(p.dim_head, 0) * 4);
-  d.total = rows == 0 ? 0 : d.ws_ml + align256(rows * d.splits * 8);
-  return d;
-}
-// the kernels' window sides: no collapsing onto the un-windowed call (every sequence has its own N_b and L_b; the one entry point serves
-// open sides as well)
-static void ragged_window_sides(const fcsa_problem& p, const fcsa_window* w, int& lo, int& hi) {
-  lo = w == nullptr || w->left < 0 ? fcsa::kWinOpen : std::min(w->left, fcsa::kWinOpen);
-  hi = p.causal ? 0 : (w == nullptr || w->right < 0 ? fcsa::kWinOpen : std::min(w->right, fcsa::kWinOpen));
-}
-static int check_kvcache_varlen(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_kvcache_quant* qz,
-                                const fcsa_window* w) {
+// a ragged step: its own arguments, then the equal-N checks on the problem of the packed rows
+int check_kvcache_varlen(const DecodeCall& c) {
+  const fcsa_forward_args* a = c.a;
+  const fcsa_kvcache* kv = c.kv;
+  const fcsa_varlen* seqs = c.seqs;
   if (a == nullptr || kv == nullptr || seqs == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_varlen: null argument");
   if (seqs->total_q < 0 || seqs->total_q > INT32_MAX) return fail(FCSA_ERR_INVALID_ARG, "kvcache_varlen: total_q (%lld) outside [0, 2^31)", (long long)seqs->total_q);
   if (a->p.batch > 0 && seqs->cu_seqlens_q == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_varlen: null cu_seqlens_q");
   if (kv->new_len != 0 && kv->new_len != 1) return fail(FCSA_ERR_INVALID_ARG, "kvcache_varlen: new_len (%d) is a flag here: 0 (no append) or 1 (every query row brings its key and value)", kv->new_len);
-  if (w != nullptr)
-    if (int rc = check_window(w, false, false)) return rc;
+  if (c.w != nullptr)
+    if (int rc = check_window(c.w, false, false)) return rc;
   // the equal-N checks, on the problem of the packed rows (q_len = total_q: which tensors must be there) with packed views
   fcsa_forward_args pa = *a;
   fcsa_kvcache pk = *kv;
@@ -650,114 +558,143 @@ static int check_kvcache_varlen(const fcsa_forward_args* a, const fcsa_kvcache* 
   pk.new_len = kv->new_len != 0 && seqs->total_q > 0 ? 1 : 0;
   if (a->p.q_len < 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_varlen: negative max_seqlen_q (%d)", a->p.q_len);
   if ((int64_t)std::max(a->p.heads, 0) * seqs->total_q > INT32_MAX) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_varlen: heads x packed rows above 2^31");
-  if (int rc = qz != nullptr ? check_quant(&pa, &pk, qz) : check_kvcache(&pa, &pk)) return rc;
-  int lo, hi;
-  ragged_window_sides(a->p, w, lo, hi);
-  const RaggedPlan d = ragged_plan(a->p, *kv, seqs->total_q, lo);
-  if (d.slots * std::max(a->p.kv_heads, 1) * d.splits > INT32_MAX) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_varlen: grid above 2^31 workgroups");
-  return FCSA_OK;
+  return c.qz != nullptr ? check_quant(&pa, &pk, c.qz) : check_kvcache(&pa, &pk);
 }
 
-size_t fcsa_forward_kvcache_varlen_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv, const fcsa_varlen* seqs,
-                                                   const fcsa_kvcache_quant* qz, const fcsa_window* w) {
-  (void)qz;      // (the split rule counts keys: an fp8 cache needs what the 16-bit call needs)
-  if (p == nullptr || kv == nullptr || seqs == nullptr) return 0;
-  int lo, hi;
-  ragged_window_sides(*p, w, lo, hi);
-  return ragged_plan(*p, *kv, seqs->total_q, lo).total;
-}
+// the fcsa_profile_* name and the launch-error label of each launch, by [ragged][fp8] (and [lse] for the combine)
+struct LaunchName { const char* name; const char* what; };
+constexpr LaunchName kAppendName[2][2] = {{{"kv_append", "kv append"}, {"kv_append_fp8", "kv append (fp8)"}},
+                                          {{"kv_append_ragged", "kv append (ragged)"}, {"kv_append_ragged_fp8", "kv append (ragged)"}}};
+constexpr LaunchName kDecodeName[2][2] = {{{"decode", "decode"}, {"decode_fp8", "decode (fp8)"}},
+                                          {{"decode_ragged", "decode (ragged)"}, {"decode_ragged_fp8", "decode (ragged)"}}};
+constexpr LaunchName kCombineName[2][2][2] = {
+    {{{"decode_combine", "decode combine"}, {"decode_combine_lse", "decode combine (lse)"}},
+     {{"decode_combine_fp8", "decode combine (fp8)"}, {"decode_combine_lse_fp8", "decode combine (lse, fp8)"}}},
+    {{{"decode_combine_ragged", "decode combine (ragged)"}, {"decode_combine_lse_ragged", "decode combine (lse, ragged)"}},
+     {{"decode_combine_ragged_fp8", "decode combine (ragged)"}, {"decode_combine_lse_ragged_fp8", "decode combine (lse, ragged)"}}}};
 
-static int forward_kvcache_varlen(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_kvcache_quant* qz,
-                                  const fcsa_window* w, const fcsa_lse_out* lse);
-int fcsa_forward_kvcache_varlen(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_kvcache_quant* qz,
-                                const fcsa_window* w) {
-  return forward_kvcache_varlen(a, kv, seqs, qz, w, nullptr);
-}
-
-// lse: NULL, or where the combine also writes the log-sum-exp of every packed row (fcsa_forward_kvcache_lse)
-static int forward_kvcache_varlen(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_kvcache_quant* qz,
-                                  const fcsa_window* w, const fcsa_lse_out* lse) {
-  if (int rc = check_kvcache_varlen(a, kv, seqs, qz, w)) return rc;
-  const fcsa_problem& p = a->p;
-  if (p.batch == 0 || seqs->total_q == 0) return FCSA_OK;      // no sequence, or no packed row: nothing to append, nothing to write
-  const int es = elem_size(p.dtype);
-  hipStream_t s = static_cast<hipStream_t>(a->stream);
-  fcsa::DecodeRaggedParams dp;
-  ragged_window_sides(p, w, dp.win_lo, dp.win_hi);
-  dp.window = 1;
-  const RaggedPlan d = ragged_plan(p, *kv, seqs->total_q, dp.win_lo);
-  const bool rows = p.heads > 0;
-  if (rows) {
-    if (a->workspace == nullptr || a->workspace_bytes < d.total)
-      return fail(FCSA_ERR_WORKSPACE, "kvcache_varlen: workspace too small: %zu < %zu bytes", a->workspace_bytes, d.total);
-    if ((reinterpret_cast<uintptr_t>(a->workspace) & 255) != 0) return fail(FCSA_ERR_WORKSPACE, "kvcache_varlen: workspace not 256-byte aligned");
+int decode_call(const DecodeCall& c) {
+  const bool ragged = c.seqs != nullptr, fp8 = c.qz != nullptr;
+  // the checks, once; a rectangular call's window comes after its cache checks, a ragged step's among its own arguments
+  if (ragged) {
+    if (int rc = check_kvcache_varlen(c)) return rc;
+  } else {
+    if (int rc = fp8 ? check_quant(c.a, c.kv, c.qz) : check_kvcache(c.a, c.kv)) return rc;
+    if (c.w != nullptr)
+      if (int rc = check_window(c.w, false, false)) return rc;
   }
-  const bool fp8 = qz != nullptr;
-  const int ces = fp8 ? 1 : es;
-  dp.q = view(packed(a->q), es);
-  dp.o = view(packed(a->o), es);
+  const fcsa_forward_args* a = c.a;
+  const fcsa_kvcache* kv = c.kv;
+  const fcsa_problem& p = a->p;
+  const DecodeWindow win = decode_window(p, *kv, ragged, c.w);
+  const DecodePlan d = decode_plan(p, *kv, c.seqs, win.reach());
+  if (ragged && d.slots * std::max(p.kv_heads, 1) * d.splits > INT32_MAX) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_varlen: grid above 2^31 workgroups");
+  if (p.batch == 0) return FCSA_OK;
+  if (ragged && c.seqs->total_q == 0) return FCSA_OK;      // no packed row: nothing to append, nothing to write
+  const bool rows = p.heads > 0 && (ragged || p.q_len > 0);
+  if (rows) {
+    const char* who = ragged ? "kvcache_varlen" : "kvcache";
+    if (a->workspace == nullptr || a->workspace_bytes < d.total)
+      return fail(FCSA_ERR_WORKSPACE, "%s: workspace too small: %zu < %zu bytes", who, a->workspace_bytes, d.total);
+    if ((reinterpret_cast<uintptr_t>(a->workspace) & 255) != 0) return fail(FCSA_ERR_WORKSPACE, "%s: workspace not 256-byte aligned", who);
+  }
+  // One fill of the most derived block: every kernel gets the part it takes (fcsa_kernels.h).  A ragged step has packed q / o / k_new /
+  // v_new views, per-sequence row counts in place of N / row_tiles / new_len, and an lse view without a batch stride.
+  const int es = elem_size(p.dtype), ces = fp8 ? 1 : es;
+  auto rows_view = [&](const fcsa_tensor& t) { return view(ragged ? packed(t) : t, es); };
+  fcsa::DecodeRaggedParams dp{};
+  dp.q = rows_view(a->q);
+  dp.o = rows_view(a->o);
   dp.kc = view(kv->k_cache, ces);
   dp.vc = view(kv->v_cache, ces);
-  dp.kn = view(packed(kv->k_new), es);
-  dp.vn = view(packed(kv->v_new), es);
+  dp.kn = rows_view(kv->k_new);
+  dp.vn = rows_view(kv->v_new);
   dp.seqlens = kv->cache_seqlens;
   dp.table = kv->block_table;
   dp.table_stride = kv->block_table_stride;
   dp.capacity = kv->capacity;
   dp.page = kv->block_table != nullptr ? kv->page_size : 0;
   dp.num_blocks = kv->num_blocks;
-  dp.new_len = 0;
-  dp.B = p.batch; dp.H = p.heads; dp.Hk = p.kv_heads; dp.G = p.heads / p.kv_heads; dp.N = 0;
-  dp.row_tiles = 0; dp.splits = d.splits;
-  dp.causal = p.causal; dp.l2norm = p.l2norm_qk; dp.groups = p.l2norm_qk ? p.groups : 1;
+  dp.new_len = ragged ? 0 : kv->new_len;
+  dp.B = p.batch; dp.H = p.heads; dp.Hk = p.kv_heads; dp.G = p.heads / p.kv_heads; dp.N = ragged ? 0 : p.q_len;
+  dp.row_tiles = d.row_tiles; dp.splits = d.splits;
+  dp.causal = win.causal; dp.l2norm = p.l2norm_qk; dp.groups = p.l2norm_qk ? p.groups : 1;
   dp.c1 = p.scale * kLog2e;
   dp.c2 = exponent_shift(p, false) * kLog2e;
   dp.l_eps = rowsum_eps(p, false);
   dp.dyn = dynamic_shift(p, false) ? 1 : 0;
   dp.ws_o = static_cast<float*>(a->workspace);
   dp.ws_ml = reinterpret_cast<float*>(static_cast<char*>(a->workspace) + d.ws_ml);
-  dp.cu_q = seqs->cu_seqlens_q;
-  dp.total_q = (int)seqs->total_q;
-  dp.slots = (int)d.slots;
-  dp.append = kv->new_len != 0 ? 1 : 0;
+  dp.window = win.windowed; dp.win_lo = win.lo; dp.win_hi = win.hi;
   if (fp8) {
-    dp.k_scale = qz->k_scale; dp.v_scale = qz->v_scale;
-    dp.ks_b = qz->k_scale_stride0; dp.ks_h = qz->k_scale_stride1;
-    dp.vs_b = qz->v_scale_stride0; dp.vs_h = qz->v_scale_stride1;
+    dp.k_scale = c.qz->k_scale; dp.v_scale = c.qz->v_scale;
+    dp.ks_b = c.qz->k_scale_stride0; dp.ks_h = c.qz->k_scale_stride1;
+    dp.vs_b = c.qz->v_scale_stride0; dp.vs_h = c.qz->v_scale_stride1;
   }
+  if (ragged) {
+    dp.cu_q = c.seqs->cu_seqlens_q;
+    dp.total_q = (int)c.seqs->total_q;
+    dp.slots = (int)d.slots;
+    dp.append = kv->new_len != 0 ? 1 : 0;
+  }
+  const fcsa::DecodeLseOut lo = c.lse != nullptr ? fcsa::DecodeLseOut{c.lse->lse, ragged ? 0 : c.lse->stride0, c.lse->stride1, c.lse->stride2} : fcsa::DecodeLseOut{};
   // 1. the append (before anything reads the cache: same stream), 2. the split partials, 3. their combine
-  if (dp.append && kv->capacity > 0) {
-    if (int rc = timed(fp8 ? "kv_append_ragged_fp8" : "kv_append_ragged", "kv append (ragged)", s,
-                       [&] { return fcsa::launch_kv_append_ragged(p.dtype, p.dim_head, fp8, dp, s); })) return rc;
+  const fcsa::DecodeForm form = {fp8, ragged};
+  hipStream_t s = static_cast<hipStream_t>(a->stream);
+  if (kv->new_len > 0 && kv->capacity > 0) {
+    const LaunchName& n = kAppendName[ragged][fp8];
+    if (int rc = timed(n.name, n.what, s, [&] { return fcsa::launch_kv_append(p.dtype, p.dim_head, form, dp, s); })) return rc;
   }
   if (!rows) return FCSA_OK;
-  if (int rc = timed(fp8 ? "decode_ragged_fp8" : "decode_ragged", "decode (ragged)", s,
-                     [&] { return fcsa::launch_decode_ragged(p.dtype, p.dim_head, fp8, dp, s); })) return rc;
-  if (lse != nullptr) {
-    const fcsa::DecodeLseOut lo = {lse->lse, 0, lse->stride1, lse->stride2};
-    return timed(fp8 ? "decode_combine_lse_ragged_fp8" : "decode_combine_lse_ragged", "decode combine (lse, ragged)", s,
-                 [&] { return fcsa::launch_decode_combine_lse_ragged(p.dtype, p.dim_head, fp8, dp, lo, s); });
-  }
-  return timed(fp8 ? "decode_combine_ragged_fp8" : "decode_combine_ragged", "decode combine (ragged)", s,
-               [&] { return fcsa::launch_decode_combine_ragged(p.dtype, p.dim_head, fp8, dp, s); });
+  const LaunchName& n = kDecodeName[ragged][fp8];
+  if (int rc = timed(n.name, n.what, s, [&] { return fcsa::launch_decode(p.dtype, p.dim_head, form, dp, s); })) return rc;
+  const LaunchName& m = kCombineName[ragged][fp8][c.lse != nullptr];
+  return timed(m.name, m.what, s, [&] { return fcsa::launch_decode_combine(p.dtype, p.dim_head, form, dp, c.lse != nullptr ? &lo : nullptr, s); });
+}
+
+}  // namespace
+
+extern "C" {
+
+int fcsa_forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv) { return decode_call({a, kv, nullptr, nullptr, nullptr, nullptr}); }
+size_t fcsa_forward_kvcache_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv) { return decode_workspace_bytes(p, kv, nullptr, nullptr); }
+
+int fcsa_forward_kvcache_window(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_window* w) {
+  if (w == nullptr) return check_window(w, false, false);
+  return decode_call({a, kv, nullptr, nullptr, w, nullptr});
+}
+size_t fcsa_forward_kvcache_window_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv, const fcsa_window* w) {
+  return w == nullptr ? 0 : decode_workspace_bytes(p, kv, nullptr, w);
+}
+
+int fcsa_forward_kvcache_quant(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_kvcache_quant* qz, const fcsa_window* w) {
+  if (qz == nullptr) return check_quant(a, kv, qz);
+  return decode_call({a, kv, nullptr, qz, w, nullptr});
+}
+// (the split rule counts keys: an fp8 cache needs what the 16-bit call needs)
+size_t fcsa_forward_kvcache_quant_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv, const fcsa_kvcache_quant* qz, const fcsa_window* w) {
+  return qz == nullptr ? 0 : decode_workspace_bytes(p, kv, nullptr, w);
+}
+
+int fcsa_forward_kvcache_varlen(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_kvcache_quant* qz,
+                                const fcsa_window* w) {
+  if (seqs == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_varlen: null argument");
+  return decode_call({a, kv, seqs, qz, w, nullptr});
+}
+size_t fcsa_forward_kvcache_varlen_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv, const fcsa_varlen* seqs,
+                                                   const fcsa_kvcache_quant*, const fcsa_window* w) {
+  return seqs == nullptr ? 0 : decode_workspace_bytes(p, kv, seqs, w);
 }
 
 // ---- the decode calls with the rows' log-sum-exp (fcsa_forward_kvcache_lse), and merging attention states (fcsa_merge_states) ----------
-// Each route is the corresponding entry point's own code with `lse` handed down: the same checks, window normalisation, plan and append /
+// Each route is the corresponding entry point's call description with `lse` added: the same checks, window normalisation, plan and append /
 // decode launches, so o and the caches are that entry point's bit for bit.
 int fcsa_forward_kvcache_lse(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_kvcache_quant* qz,
                              const fcsa_window* w, const fcsa_lse_out* lse) {
   if (a == nullptr || kv == nullptr || lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_lse: null argument");
   const bool rows = a->p.batch > 0 && a->p.heads > 0 && (seqs != nullptr ? seqs->total_q > 0 : a->p.q_len > 0);
   if (rows && lse->lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_lse: lse: null pointer");
-  if (seqs != nullptr) return forward_kvcache_varlen(a, kv, seqs, qz, w, lse);
-  if (int rc = qz != nullptr ? check_quant(a, kv, qz) : check_kvcache(a, kv)) return rc;
-  if (w == nullptr) return forward_kvcache(a, kv, nullptr, qz, lse);
-  if (int rc = check_window(w, false, false)) return rc;
-  WindowCall win;
-  fcsa_forward_args na = *a;
-  if (!decode_window_sides(a->p, *kv, *w, win, na.p.causal)) return forward_kvcache(&na, kv, nullptr, qz, lse);
-  return forward_kvcache(a, kv, &win, qz, lse);
+  return decode_call({a, kv, seqs, qz, w, lse});
 }
 
 int fcsa_merge_states(const fcsa_merge_args* a) {
@@ -882,7 +819,7 @@ int forward_impl(const fcsa_forward_args* a, const VarlenCall* vl, const WindowC
       const size_t rows = (size_t)sp * p.batch * p.heads * p.q_len;
       fp.splits = sp;
       fp.ws_o = static_cast<float*>(a->workspace);
-      fp.ws_l = reinterpret_cast<float*>(static_cast<char*>(a->workspace) + align256(rows * p.dim_head * 4));
+      fp.ws_l = reinterpret_cast<float*>(static_cast<char*>(a->workspace) + align_up(rows * p.dim_head * 4, 256));
     }
   }
   return timed("fwd", "forward", s, [&] { return fcsa::launch_forward(p.dtype, p.dim_head, fp, s); });

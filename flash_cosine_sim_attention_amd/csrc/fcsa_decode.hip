@@ -16,6 +16,9 @@
 // own -- kv_append_fp8_kernel, decode_fp8_kernel (decode_body with FP8), decode_combine_fp8_kernel -- so the kernels above are what
 // they were.  A lane reads 8 key bytes per fragment (the same features as its 16-bit fragment) and converts them with v_cvt_pk_f32_fp8;
 // every code is exact in f16 and bf16, so the operands of both MFMA products are what a 16-bit cache holding the codes would feed.
+// Host side: three launchers at the end of the file, one per job -- launch_kv_append, launch_decode, launch_decode_combine -- over one
+// parameter block (DecodeRaggedParams, fcsa_kernels.h).  Each dispatches dtype, head dim and form (fp8, ragged) once, works out its grid
+// once, and hands the entry point it picks the part of the block that entry point declares (launch_part).
 #include "fcsa_common.cuh"
 
 #include <cmath>
@@ -497,7 +500,7 @@ __global__ __launch_bounds__(64) void decode_fp8_kernel(DecodeFp8Params p) {
   decode_body<T, D, DYN, GEN, WIN, true>(p);
 }
 
-// the ragged step (launch_decode_ragged): one entry point per cache type, with or without a window
+// the ragged step (launch_decode with the ragged form): one entry point per cache type, with or without a window
 template <typename T, int D, bool DYN, bool GEN>
 __global__ __launch_bounds__(64) void decode_ragged_kernel(DecodeRaggedParams p) {
   decode_body<T, D, DYN, GEN, true, false, true>(p);
@@ -725,29 +728,70 @@ __global__ __launch_bounds__(256) void kv_append_ragged_kernel(DecodeRaggedParam
 
 int64_t blocks_of(int64_t threads) { return (threads + 255) / 256; }
 
-}  // namespace
-
-hipError_t launch_kv_append(int dtype, int D, const DecodeParams& p, hipStream_t s) {
-  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
-    using T = typename decltype(td)::T;
-    constexpr int DD = decltype(td)::D;
-    const int64_t threads = (int64_t)p.B * p.Hk * p.new_len * (DD * Traits<T>::ES / 16);
-    if (threads <= 0) return hipSuccess;
-    hipLaunchKernelGGL((kv_append_kernel<T, DD>), dim3((unsigned)blocks_of(threads)), dim3(256), 0, s, p);
+// ---- the launchers: one per job (append, decode, combine) over every form of the call ----------------------------------------------
+// The parameter block a kernel entry point takes, and the launch of `Kernel` with that part of the call's one block (a base-class slice;
+// LDS > 0: dynamic LDS, raised once per device) -- so no launcher can hand an entry point another block than the one it declares.
+template <typename P, typename... More> P block_of(void (*)(P, More...));
+template <auto Kernel, int LDS, typename... More>
+hipError_t launch_part(dim3 grid, dim3 block, hipStream_t s, const DecodeRaggedParams& p, const More&... more) {
+  using P = decltype(block_of(Kernel));
+  if constexpr (LDS > 0) {
+    return launch_with_lds<Kernel>(grid, block, LDS, s, static_cast<const P&>(p), more...);
+  } else {
+    hipLaunchKernelGGL(Kernel, grid, block, 0, s, static_cast<const P&>(p), more...);
     return hipGetLastError();
+  }
+}
+
+// The one dtype / head-dim / form dispatch: fn(TypeDim<T, D>, FP8, RAGGED), the flags as std::bool_constant.  An fp8 cache exists for the
+// 16-bit types only, so nothing with FP8 is instantiated for float32.
+template <typename F> hipError_t dispatch_decode(int dtype, int D, DecodeForm f, F&& fn) {
+  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
+    using Y = std::true_type;
+    using N = std::false_type;
+    if (f.fp8) {
+      if constexpr (Traits<typename decltype(td)::T>::ES == 2) return f.ragged ? fn(td, Y{}, Y{}) : fn(td, Y{}, N{});
+      else return hipErrorInvalidValue;
+    }
+    return f.ragged ? fn(td, N{}, Y{}) : fn(td, N{}, N{});
   });
 }
 
-hipError_t launch_decode(int dtype, int D, const DecodeWinParams& p, hipStream_t s) {
-  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
+}  // namespace
+
+// one thread per 16 bytes WRITTEN of an appended row (an fp8 row is D bytes); ragged: the packed rows bring one key and value each
+hipError_t launch_kv_append(int dtype, int D, DecodeForm f, const DecodeRaggedParams& p, hipStream_t s) {
+  return dispatch_decode(dtype, D, f, [&](auto td, auto fp8, auto ragged) -> hipError_t {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    constexpr bool FP8 = decltype(fp8)::value, RAGGED = decltype(ragged)::value;
+    constexpr int CHUNKS = FP8 ? DD / 16 : DD * Traits<T>::ES / 16;
+    const int64_t threads = (RAGGED ? (int64_t)p.total_q : (int64_t)p.B * p.new_len) * p.Hk * CHUNKS;
+    if (threads <= 0 || (RAGGED && p.B <= 0)) return hipSuccess;
+    const dim3 grid((unsigned)blocks_of(threads)), block(256);
+    if constexpr (RAGGED) return launch_part<kv_append_ragged_kernel<T, DD, FP8>, 0>(grid, block, s, p);
+    else if constexpr (FP8) return launch_part<kv_append_fp8_kernel<T, DD>, 0>(grid, block, s, p);
+    else return launch_part<kv_append_kernel<T, DD>, 0>(grid, block, s, p);
+  });
+}
+
+// one single-wave workgroup per (K/V head, row tile, key split): row_tiles per sequence, or the flat slots of a ragged step
+hipError_t launch_decode(int dtype, int D, DecodeForm f, const DecodeRaggedParams& p, hipStream_t s) {
+  return dispatch_decode(dtype, D, f, [&](auto td, auto fp8, auto ragged) -> hipError_t {
     using T = typename decltype(td)::T;
     constexpr int DD = decltype(td)::D;
     constexpr int ES = Traits<T>::ES;
-    const dim3 grid((unsigned)((int64_t)p.B * p.Hk * p.row_tiles * p.splits));
+    constexpr bool FP8 = decltype(fp8)::value, RAGGED = decltype(ragged)::value;
+    const dim3 grid((unsigned)((RAGGED ? (int64_t)p.slots : (int64_t)p.B * p.row_tiles) * p.Hk * p.splits)), block(64);
     auto go = [&](auto dyn, auto gen) -> hipError_t {
       constexpr bool DY = decltype(dyn)::value, GN = decltype(gen)::value;
-      if (p.window) return launch_with_lds<decode_win_kernel<T, DD, DY, GN>>(grid, dim3(64), DecodeLds<DD, ES, GN>::BYTES, s, p);
-      return launch_with_lds<decode_kernel<T, DD, DY, GN>>(grid, dim3(64), DecodeLds<DD, ES, GN>::BYTES, s, static_cast<const DecodeParams&>(p));
+      constexpr int LDS = DecodeLds<DD, ES, GN>::BYTES;
+      if constexpr (RAGGED && FP8) return launch_part<decode_ragged_fp8_kernel<T, DD, DY, GN>, LDS>(grid, block, s, p);
+      else if constexpr (RAGGED) return launch_part<decode_ragged_kernel<T, DD, DY, GN>, LDS>(grid, block, s, p);
+      else if constexpr (FP8) return p.window ? launch_part<decode_fp8_kernel<T, DD, DY, GN, true>, LDS>(grid, block, s, p)
+                                              : launch_part<decode_fp8_kernel<T, DD, DY, GN, false>, LDS>(grid, block, s, p);
+      else return p.window ? launch_part<decode_win_kernel<T, DD, DY, GN>, LDS>(grid, block, s, p)
+                           : launch_part<decode_kernel<T, DD, DY, GN>, LDS>(grid, block, s, p);
     };
     using Y = std::true_type;
     using N = std::false_type;
@@ -760,177 +804,23 @@ hipError_t launch_decode(int dtype, int D, const DecodeWinParams& p, hipStream_t
   });
 }
 
-// ---- the fp8 cache: 16-bit q / o only ----
-hipError_t launch_kv_append_fp8(int dtype, int D, const DecodeFp8Params& p, hipStream_t s) {
-  if (dtype != 1 && dtype != 2) return hipErrorInvalidValue;
-  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
+// one thread per four features of an output row; lse: nullptr, or the entry points that also write the rows' log-sum-exp
+hipError_t launch_decode_combine(int dtype, int D, DecodeForm f, const DecodeRaggedParams& p, const DecodeLseOut* lse, hipStream_t s) {
+  return dispatch_decode(dtype, D, f, [&](auto td, auto fp8, auto ragged) -> hipError_t {
     using T = typename decltype(td)::T;
     constexpr int DD = decltype(td)::D;
-    if constexpr (Traits<T>::ES == 2) {
-      const int64_t threads = (int64_t)p.B * p.Hk * p.new_len * (DD / 16);
-      if (threads <= 0) return hipSuccess;
-      hipLaunchKernelGGL((kv_append_fp8_kernel<T, DD>), dim3((unsigned)blocks_of(threads)), dim3(256), 0, s, p);
-      return hipGetLastError();
-    } else {
-      return hipErrorInvalidValue;
-    }
-  });
-}
-
-hipError_t launch_decode_fp8(int dtype, int D, const DecodeFp8Params& p, hipStream_t s) {
-  if (dtype != 1 && dtype != 2) return hipErrorInvalidValue;
-  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
-    using T = typename decltype(td)::T;
-    constexpr int DD = decltype(td)::D;
-    if constexpr (Traits<T>::ES == 2) {
-      const dim3 grid((unsigned)((int64_t)p.B * p.Hk * p.row_tiles * p.splits));
-      auto go = [&](auto dyn, auto gen) -> hipError_t {
-        constexpr bool DY = decltype(dyn)::value, GN = decltype(gen)::value;
-        if (p.window) return launch_with_lds<decode_fp8_kernel<T, DD, DY, GN, true>>(grid, dim3(64), DecodeLds<DD, 2, GN>::BYTES, s, p);
-        return launch_with_lds<decode_fp8_kernel<T, DD, DY, GN, false>>(grid, dim3(64), DecodeLds<DD, 2, GN>::BYTES, s, p);
-      };
-      using Y = std::true_type;
-      using N = std::false_type;
-      if (p.l2norm && !decode_groups_fast(DD, p.groups, Unit<T>::UE)) {
-        if constexpr (DD == 96) return p.dyn ? go(Y{}, Y{}) : go(N{}, Y{});
-        else return hipErrorInvalidValue;
-      }
-      return p.dyn ? go(Y{}, N{}) : go(N{}, N{});
-    } else {
-      return hipErrorInvalidValue;
-    }
-  });
-}
-
-hipError_t launch_decode_combine_fp8(int dtype, int D, const DecodeFp8Params& p, hipStream_t s) {
-  if (dtype != 1 && dtype != 2) return hipErrorInvalidValue;
-  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
-    using T = typename decltype(td)::T;
-    constexpr int DD = decltype(td)::D;
-    if constexpr (Traits<T>::ES == 2) {
-      const int64_t threads = (int64_t)p.B * p.H * p.N * (DD / 4);
-      if (threads <= 0) return hipSuccess;
-      hipLaunchKernelGGL((decode_combine_fp8_kernel<T, DD>), dim3((unsigned)blocks_of(threads)), dim3(256), 0, s, p);
-      return hipGetLastError();
-    } else {
-      return hipErrorInvalidValue;
-    }
-  });
-}
-
-// ---- ragged steps (fcsa_forward_kvcache_varlen) ----
-hipError_t launch_kv_append_ragged(int dtype, int D, bool fp8, const DecodeRaggedParams& p, hipStream_t s) {
-  if (fp8 && dtype != 1 && dtype != 2) return hipErrorInvalidValue;
-  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
-    using T = typename decltype(td)::T;
-    constexpr int DD = decltype(td)::D;
-    const int64_t threads = (int64_t)p.total_q * p.Hk * (fp8 ? DD / 16 : DD * Traits<T>::ES / 16);
-    if (threads <= 0 || p.B <= 0) return hipSuccess;
-    if (fp8) {
-      if constexpr (Traits<T>::ES == 2) hipLaunchKernelGGL((kv_append_ragged_kernel<T, DD, true>), dim3((unsigned)blocks_of(threads)), dim3(256), 0, s, p);
-      else return hipErrorInvalidValue;
-    } else {
-      hipLaunchKernelGGL((kv_append_ragged_kernel<T, DD, false>), dim3((unsigned)blocks_of(threads)), dim3(256), 0, s, p);
-    }
-    return hipGetLastError();
-  });
-}
-
-hipError_t launch_decode_ragged(int dtype, int D, bool fp8, const DecodeRaggedParams& p, hipStream_t s) {
-  if (fp8 && dtype != 1 && dtype != 2) return hipErrorInvalidValue;
-  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
-    using T = typename decltype(td)::T;
-    constexpr int DD = decltype(td)::D;
-    constexpr int ES = Traits<T>::ES;
-    const dim3 grid((unsigned)((int64_t)p.slots * p.Hk * p.splits));
-    auto go = [&](auto dyn, auto gen) -> hipError_t {
-      constexpr bool DY = decltype(dyn)::value, GN = decltype(gen)::value;
-      if (fp8) {
-        if constexpr (ES == 2) return launch_with_lds<decode_ragged_fp8_kernel<T, DD, DY, GN>>(grid, dim3(64), DecodeLds<DD, ES, GN>::BYTES, s, p);
-        else return hipErrorInvalidValue;
-      }
-      return launch_with_lds<decode_ragged_kernel<T, DD, DY, GN>>(grid, dim3(64), DecodeLds<DD, ES, GN>::BYTES, s, p);
-    };
-    using Y = std::true_type;
-    using N = std::false_type;
-    if (p.l2norm && !decode_groups_fast(DD, p.groups, Unit<T>::UE)) {
-      if constexpr (DD == 96) return p.dyn ? go(Y{}, Y{}) : go(N{}, Y{});
-      else return hipErrorInvalidValue;
-    }
-    return p.dyn ? go(Y{}, N{}) : go(N{}, N{});
-  });
-}
-
-hipError_t launch_decode_combine_ragged(int dtype, int D, bool fp8, const DecodeRaggedParams& p, hipStream_t s) {
-  if (fp8 && dtype != 1 && dtype != 2) return hipErrorInvalidValue;
-  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
-    using T = typename decltype(td)::T;
-    constexpr int DD = decltype(td)::D;
-    const int64_t threads = (int64_t)p.total_q * p.H * (DD / 4);
+    constexpr bool FP8 = decltype(fp8)::value, RAGGED = decltype(ragged)::value;
+    const int64_t threads = (RAGGED ? (int64_t)p.total_q : (int64_t)p.B * p.N) * p.H * (DD / 4);
     if (threads <= 0) return hipSuccess;
-    if (fp8) {
-      if constexpr (Traits<T>::ES == 2) hipLaunchKernelGGL((decode_combine_ragged_kernel<T, DD, true>), dim3((unsigned)blocks_of(threads)), dim3(256), 0, s, p);
-      else return hipErrorInvalidValue;
-    } else {
-      hipLaunchKernelGGL((decode_combine_ragged_kernel<T, DD, false>), dim3((unsigned)blocks_of(threads)), dim3(256), 0, s, p);
+    const dim3 grid((unsigned)blocks_of(threads)), block(256);
+    if (lse != nullptr) {
+      if constexpr (RAGGED) return launch_part<decode_combine_lse_ragged_kernel<T, DD, FP8>, 0>(grid, block, s, p, *lse);
+      else if constexpr (FP8) return launch_part<decode_combine_lse_fp8_kernel<T, DD>, 0>(grid, block, s, p, *lse);
+      else return launch_part<decode_combine_lse_kernel<T, DD>, 0>(grid, block, s, p, *lse);
     }
-    return hipGetLastError();
-  });
-}
-
-// ---- the combines that also write the rows' log-sum-exp (fcsa_forward_kvcache_lse): the grids of their twins ----
-hipError_t launch_decode_combine_lse(int dtype, int D, const DecodeParams& p, const DecodeLseOut& lse, hipStream_t s) {
-  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
-    using T = typename decltype(td)::T;
-    constexpr int DD = decltype(td)::D;
-    const int64_t threads = (int64_t)p.B * p.H * p.N * (DD / 4);
-    if (threads <= 0) return hipSuccess;
-    hipLaunchKernelGGL((decode_combine_lse_kernel<T, DD>), dim3((unsigned)blocks_of(threads)), dim3(256), 0, s, p, lse);
-    return hipGetLastError();
-  });
-}
-
-hipError_t launch_decode_combine_lse_fp8(int dtype, int D, const DecodeFp8Params& p, const DecodeLseOut& lse, hipStream_t s) {
-  if (dtype != 1 && dtype != 2) return hipErrorInvalidValue;
-  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
-    using T = typename decltype(td)::T;
-    constexpr int DD = decltype(td)::D;
-    if constexpr (Traits<T>::ES == 2) {
-      const int64_t threads = (int64_t)p.B * p.H * p.N * (DD / 4);
-      if (threads <= 0) return hipSuccess;
-      hipLaunchKernelGGL((decode_combine_lse_fp8_kernel<T, DD>), dim3((unsigned)blocks_of(threads)), dim3(256), 0, s, p, lse);
-      return hipGetLastError();
-    } else {
-      return hipErrorInvalidValue;
-    }
-  });
-}
-
-hipError_t launch_decode_combine_lse_ragged(int dtype, int D, bool fp8, const DecodeRaggedParams& p, const DecodeLseOut& lse, hipStream_t s) {
-  if (fp8 && dtype != 1 && dtype != 2) return hipErrorInvalidValue;
-  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
-    using T = typename decltype(td)::T;
-    constexpr int DD = decltype(td)::D;
-    const int64_t threads = (int64_t)p.total_q * p.H * (DD / 4);
-    if (threads <= 0) return hipSuccess;
-    if (fp8) {
-      if constexpr (Traits<T>::ES == 2) hipLaunchKernelGGL((decode_combine_lse_ragged_kernel<T, DD, true>), dim3((unsigned)blocks_of(threads)), dim3(256), 0, s, p, lse);
-      else return hipErrorInvalidValue;
-    } else {
-      hipLaunchKernelGGL((decode_combine_lse_ragged_kernel<T, DD, false>), dim3((unsigned)blocks_of(threads)), dim3(256), 0, s, p, lse);
-    }
-    return hipGetLastError();
-  });
-}
-
-hipError_t launch_decode_combine(int dtype, int D, const DecodeParams& p, hipStream_t s) {
-  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
-    using T = typename decltype(td)::T;
-    constexpr int DD = decltype(td)::D;
-    const int64_t threads = (int64_t)p.B * p.H * p.N * (DD / 4);
-    if (threads <= 0) return hipSuccess;
-    hipLaunchKernelGGL((decode_combine_kernel<T, DD>), dim3((unsigned)blocks_of(threads)), dim3(256), 0, s, p);
-    return hipGetLastError();
+    if constexpr (RAGGED) return launch_part<decode_combine_ragged_kernel<T, DD, FP8>, 0>(grid, block, s, p);
+    else if constexpr (FP8) return launch_part<decode_combine_fp8_kernel<T, DD>, 0>(grid, block, s, p);
+    else return launch_part<decode_combine_kernel<T, DD>, 0>(grid, block, s, p);
   });
 }
 

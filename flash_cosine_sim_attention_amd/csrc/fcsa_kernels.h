@@ -111,9 +111,12 @@ struct NormBwdParams {      // dx = reduce_heads(slab) then (optionally) l2norm 
   float xn_scale;           // x^ = xn_scale * xn   (1/c1 when xn was written with out_scale = c1)
 };
 
-// Decoding against a key/value cache (fcsa_forward_kvcache, csrc/fcsa_decode.hip).  Views carry BYTE strides; kc / vc are the caches
-// (sb = batch stride, or block stride when `table` is set), kn / vn the appended rows [B, Hk, new_len, D].
-struct DecodeParams {
+// Decoding against a key/value cache (fcsa_forward_kvcache and its _window, _quant, _varlen and _lse forms; csrc/fcsa_decode.hip).  The C ABI
+// fills ONE block per call -- DecodeRaggedParams, the most derived of the chain below -- and the three launchers hand every kernel entry
+// point the part of it that entry point takes (a base-class slice), so the kernel arguments of each entry point -- and its code -- are what
+// they were before the later features existed.  Views carry BYTE strides; kc / vc are the caches (sb = batch stride, or block stride when
+// `table` is set), kn / vn the appended rows [B, Hk, new_len, D].
+struct DecodeParams {        // decode_kernel, kv_append_kernel, decode_combine[_lse]_kernel
   View q, o;                // [B, H, N, D]
   View kc, vc;              // caches
   View kn, vn;              // new rows (append kernel only)
@@ -131,40 +134,28 @@ struct DecodeParams {
   float* ws_o;              // [splits][B*H*N][D] f32 partial P~V
   float* ws_ml;             // [splits][B*H*N][2] f32 (row max in log2 units, row sum)
 };
-struct DecodeWinParams : DecodeParams {      // (see FwdWinParams; decode_win_kernel)
+struct DecodeWinParams : DecodeParams {      // decode_win_kernel (see FwdWinParams)
   int window = 0;           // 1: sliding window, sides as win_normalise gives them (causal: win_hi = 0):
   int win_lo = 0, win_hi = 0;   //    the query at position t sees key j iff t - win_lo <= j <= t + win_hi
 };
 // An fp8 cache (fcsa_forward_kvcache_quant): kc / vc hold one-byte OCP e4m3fn codes (views in bytes), and the cache means
-// k_scale[b, kvh] * code, v_scale[b, kvh] * code.  Only the fp8 kernels (kv_append_fp8_kernel, decode_fp8_kernel,
-// decode_combine_fp8_kernel) get this block; the 16-bit kernels are launched with the part they always had.
-struct DecodeFp8Params : DecodeWinParams {
+// k_scale[b, kvh] * code, v_scale[b, kvh] * code.
+struct DecodeFp8Params : DecodeWinParams {   // kv_append_fp8_kernel, decode_fp8_kernel, decode_combine[_lse]_fp8_kernel
   const float* k_scale = nullptr;   // element [b * ks_b + kvh * ks_h]; a stride of 0 broadcasts
   const float* v_scale = nullptr;
   int64_t ks_b = 0, ks_h = 0, vs_b = 0, vs_h = 0;
 };
 // A ragged decode step (fcsa_forward_kvcache_varlen): q / o are packed [total_q, H, D] views and kn / vn packed [total_q, Hk, D] ones (sb
-// unused), sequence b owning the packed rows [cu_q[b], cu_q[b + 1]).  N, new_len and row_tiles of the base block are unused: every
+// unused), sequence b owning the packed rows [cu_q[b], cu_q[b + 1]).  N, new_len and row_tiles of the base block are 0 and unused: every
 // workgroup takes its sequence's own row count from the table (fcsa::ragged_tile).  The window fields are always live: open sides
-// (kWinOpen; causal: win_hi = 0) for a call without a window, so one decode entry point per cache type serves every call.  Only the
-// ragged kernels (kv_append_ragged*_kernel, decode_ragged*_kernel, decode_combine_ragged_kernel) get this block.
-struct DecodeRaggedParams : DecodeFp8Params {
+// (kWinOpen; causal: win_hi = 0) for a call without a window, so one decode entry point per cache type serves every call.  The four
+// fields below are 0 in a rectangular call.
+struct DecodeRaggedParams : DecodeFp8Params {   // kv_append_ragged_kernel, decode_ragged[_fp8]_kernel, decode_combine[_lse]_ragged_kernel
   const int32_t* cu_q = nullptr;    // [B + 1] device
   int total_q = 0;                  // packed rows of q, o, kn, vn
   int slots = 0;                    // flat row-tile slots per K/V head: fcsa::ragged_slots(total_q, B, G)
   int append = 0;                   // 1: every query row brings its key and value (L_b counts them)
 };
-hipError_t launch_kv_append(int dtype, int D, const DecodeParams& p, hipStream_t s);
-hipError_t launch_decode(int dtype, int D, const DecodeWinParams& p, hipStream_t s);
-hipError_t launch_decode_combine(int dtype, int D, const DecodeParams& p, hipStream_t s);
-// dtype: the type of q, o and the appended rows (f16 or bf16; float32 is refused)
-hipError_t launch_kv_append_fp8(int dtype, int D, const DecodeFp8Params& p, hipStream_t s);
-hipError_t launch_decode_fp8(int dtype, int D, const DecodeFp8Params& p, hipStream_t s);
-hipError_t launch_decode_combine_fp8(int dtype, int D, const DecodeFp8Params& p, hipStream_t s);
-// ragged steps; fp8: an e4m3fn cache (16-bit dtype only)
-hipError_t launch_kv_append_ragged(int dtype, int D, bool fp8, const DecodeRaggedParams& p, hipStream_t s);
-hipError_t launch_decode_ragged(int dtype, int D, bool fp8, const DecodeRaggedParams& p, hipStream_t s);
-hipError_t launch_decode_combine_ragged(int dtype, int D, bool fp8, const DecodeRaggedParams& p, hipStream_t s);
 // The rows' log-sum-exp as a second result of a decode call (fcsa_forward_kvcache_lse): a second kernel argument of the combine entry
 // points that write it (decode_combine_lse*_kernel), so that the parameter blocks above -- and the kernels launched with them alone --
 // are what they were.  ELEMENT strides: [b, h, i] at b * sb + h * sh + i * sn (ragged: [tok, h] at h * sh + tok * sn).
@@ -172,9 +163,13 @@ struct DecodeLseOut {
   float*  lse;
   int64_t sb, sh, sn;
 };
-hipError_t launch_decode_combine_lse(int dtype, int D, const DecodeParams& p, const DecodeLseOut& lse, hipStream_t s);
-hipError_t launch_decode_combine_lse_fp8(int dtype, int D, const DecodeFp8Params& p, const DecodeLseOut& lse, hipStream_t s);
-hipError_t launch_decode_combine_lse_ragged(int dtype, int D, bool fp8, const DecodeRaggedParams& p, const DecodeLseOut& lse, hipStream_t s);
+// The three jobs of a decode call, each one launcher over every form.  fp8: an e4m3fn cache (q, o and the appended rows f16 or bf16; float32
+// is refused); ragged: a ragged step; the window of a rectangular call is p.window; lse: nullptr, or where the combine also writes the
+// rows' log-sum-exp.
+struct DecodeForm { bool fp8, ragged; };
+hipError_t launch_kv_append(int dtype, int D, DecodeForm f, const DecodeRaggedParams& p, hipStream_t s);
+hipError_t launch_decode(int dtype, int D, DecodeForm f, const DecodeRaggedParams& p, hipStream_t s);
+hipError_t launch_decode_combine(int dtype, int D, DecodeForm f, const DecodeRaggedParams& p, const DecodeLseOut* lse, hipStream_t s);
 
 // Merging attention states (fcsa_merge_states, csrc/fcsa_merge.hip): S states (o_s, lse_s) of the rows [n0, n1, n2] -> (o, lse).  o views
 // carry BYTE strides, lse views ELEMENT strides.

@@ -46,3 +46,18 @@ def sd():
 bench("SDPA forward + sum().backward()", sd)
 bench("SDPA forward only (grad)", lambda: torch.nn.functional.scaled_dot_product_attention(q, k, v, is_causal=True))
 bench("torch.empty x 6", lambda: [torch.empty(4, 8, N, 64, device="cuda", dtype=torch.bfloat16) for _ in range(6)])
+# Decoding against a key/value cache is launch-bound (an append-free step is two launches of a few us), so the host time of its call path
+# is part of its speed: B4 H8 Hk2 N1 D64 bf16 against a full cache of 256 positions, device tables and max_seqlen_k given (no call
+# reads a device tensor on the host)
+B, H, Hk, D, L = 4, 8, 2, 64, 256
+dq = torch.randn(B, H, 1, D, device="cuda", dtype=torch.bfloat16)
+kc, vc = (torch.randn(B, Hk, L, D, device="cuda", dtype=torch.bfloat16) for _ in range(2))
+k8, v8 = kc.to(torch.float8_e4m3fn), vc.to(torch.float8_e4m3fn)
+ones = torch.ones(B, Hk, device="cuda")
+step = dict(cache_seqlens=torch.full((B,), L, dtype=torch.int32, device="cuda"), max_seqlen_k=L, causal=True)
+pq = dq.reshape(B, H, D)                      # the same queries packed [total_q, H, D], one per sequence
+cu = torch.arange(B + 1, dtype=torch.int32, device="cuda")
+bench("kvcache decode", lambda: F.flash_cosine_sim_attention_with_kvcache(dq, kc, vc, **step))
+bench("kvcache decode, fp8 cache", lambda: F.flash_cosine_sim_attention_with_kvcache(dq, k8, v8, k_scale=ones, v_scale=ones, **step))
+bench("kvcache decode, ragged step", lambda: F.flash_cosine_sim_attention_varlen_with_kvcache(pq, kc, vc, cu, max_seqlen_q=1, **step))
+bench("kvcache decode, return_lse", lambda: F.flash_cosine_sim_attention_with_kvcache(dq, kc, vc, return_lse=True, **step))
