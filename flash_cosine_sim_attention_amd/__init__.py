@@ -3,6 +3,7 @@ lucidrains/flash-cosine-sim-attention).  Same public names as the reference pack
 (flash_cosine_sim_attention/__init__.py:1)."""
 from .ops import (flash_cosine_sim_attention, flash_cosine_sim_attention_local, flash_cosine_sim_attention_varlen,
                   flash_cosine_sim_attention_with_kvcache, flash_cosine_sim_attention_varlen_with_kvcache,
+                  flash_cosine_sim_attention_prefill_with_kvcache,
                   flash_cosine_sim_attention_with_shared_prefix, merge_attention_states,
                   plain_cosine_sim_attention, l2norm_tensors, FlashCosineSimAttention)
 from .ext import debug
@@ -10,5 +11,6 @@ from .ext import debug
 __version__ = '0.3.0'
 __all__ = ['flash_cosine_sim_attention', 'flash_cosine_sim_attention_local', 'flash_cosine_sim_attention_varlen',
            'flash_cosine_sim_attention_with_kvcache', 'flash_cosine_sim_attention_varlen_with_kvcache',
+           'flash_cosine_sim_attention_prefill_with_kvcache',
            'flash_cosine_sim_attention_with_shared_prefix', 'merge_attention_states',
            'plain_cosine_sim_attention', 'l2norm_tensors', 'debug', 'FlashCosineSimAttention']

@@ -95,7 +95,7 @@ EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fc
            "fcsa_forward_kvcache_workspace_bytes", "fcsa_forward_window", "fcsa_backward_window", "fcsa_backward_window_workspace_bytes",
            "fcsa_forward_kvcache_window", "fcsa_forward_kvcache_window_workspace_bytes", "fcsa_forward_kvcache_quant",
            "fcsa_forward_kvcache_quant_workspace_bytes", "fcsa_forward_kvcache_varlen", "fcsa_forward_kvcache_varlen_workspace_bytes",
-           "fcsa_forward_kvcache_lse", "fcsa_merge_states")
+           "fcsa_forward_kvcache_lse", "fcsa_merge_states", "fcsa_forward_kvcache_prefill")
 
 _lib = None
 
@@ -187,6 +187,9 @@ def load():
         lib.fcsa_forward_kvcache_lse.restype = C.c_int
         lib.fcsa_merge_states.argtypes = [C.POINTER(MergeArgs)]
         lib.fcsa_merge_states.restype = C.c_int
+    if hasattr(lib, "fcsa_forward_kvcache_prefill"):      # (likewise: an FCSA_LIB build from before the prefill kernel)
+        lib.fcsa_forward_kvcache_prefill.argtypes = [C.POINTER(ForwardArgs), C.POINTER(KvCache), C.POINTER(Varlen), C.POINTER(LseOut)]
+        lib.fcsa_forward_kvcache_prefill.restype = C.c_int
     lib.fcsa_last_error.argtypes = []
     lib.fcsa_last_error.restype = C.c_char_p
     ver = lib.fcsa_debug(None, 0)

@@ -98,6 +98,12 @@ def _register_fakes():
         # lse: float32 [B, H, N]; a ragged step (q [total_q, H, D]): [total_q, H]
         return q.new_empty(q.shape), q.new_empty(q.shape[:-1], dtype=torch.float32)
 
+    # the prefill op lives in a namespace of its own (fcsa_prefill): same results as the ragged lse op
+    @torch.library.register_fake("fcsa_prefill::kvcache_prefill_forward")
+    def _(q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q, max_seqlen_k, scale, causal, l2norm_qk,
+          groups):
+        return q.new_empty(q.shape), q.new_empty(q.shape[:-1], dtype=torch.float32)
+
     @torch.library.register_fake("fcsa::merge_states")
     def _(os, lses):
         return os[0].new_empty(os[0].shape), os[0].new_empty(os[0].shape[:-1], dtype=torch.float32)

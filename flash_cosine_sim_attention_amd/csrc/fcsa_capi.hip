@@ -573,6 +573,53 @@ constexpr LaunchName kCombineName[2][2][2] = {
     {{{"decode_combine_ragged", "decode combine (ragged)"}, {"decode_combine_lse_ragged", "decode combine (lse, ragged)"}},
      {{"decode_combine_ragged_fp8", "decode combine (ragged)"}, {"decode_combine_lse_ragged_fp8", "decode combine (lse, ragged)"}}}};
 
+// One fill of the most derived block: every kernel gets the part it takes (fcsa_kernels.h).  A ragged step has packed q / o / k_new /
+// v_new views, per-sequence row counts in place of N / row_tiles / new_len, and an lse view without a batch stride.
+fcsa::DecodeRaggedParams decode_params(const DecodeCall& c, const DecodeWindow& win, const DecodePlan& d) {
+  const bool ragged = c.seqs != nullptr, fp8 = c.qz != nullptr;
+  const fcsa_forward_args* a = c.a;
+  const fcsa_kvcache* kv = c.kv;
+  const fcsa_problem& p = a->p;
+  const int es = elem_size(p.dtype), ces = fp8 ? 1 : es;
+  auto rows_view = [&](const fcsa_tensor& t) { return view(ragged ? packed(t) : t, es); };
+  fcsa::DecodeRaggedParams dp{};
+  dp.q = rows_view(a->q);
+  dp.o = rows_view(a->o);
+  dp.kc = view(kv->k_cache, ces);
+  dp.vc = view(kv->v_cache, ces);
+  dp.kn = rows_view(kv->k_new);
+  dp.vn = rows_view(kv->v_new);
+  dp.seqlens = kv->cache_seqlens;
+  dp.table = kv->block_table;
+  dp.table_stride = kv->block_table_stride;
+  dp.capacity = kv->capacity;
+  dp.page = kv->block_table != nullptr ? kv->page_size : 0;
+  dp.num_blocks = kv->num_blocks;
+  dp.new_len = ragged ? 0 : kv->new_len;
+  dp.B = p.batch; dp.H = p.heads; dp.Hk = p.kv_heads; dp.G = p.heads / p.kv_heads; dp.N = ragged ? 0 : p.q_len;
+  dp.row_tiles = d.row_tiles; dp.splits = d.splits;
+  dp.causal = win.causal; dp.l2norm = p.l2norm_qk; dp.groups = p.l2norm_qk ? p.groups : 1;
+  dp.c1 = p.scale * kLog2e;
+  dp.c2 = exponent_shift(p, false) * kLog2e;
+  dp.l_eps = rowsum_eps(p, false);
+  dp.dyn = dynamic_shift(p, false) ? 1 : 0;
+  dp.ws_o = static_cast<float*>(a->workspace);
+  dp.ws_ml = a->workspace != nullptr ? reinterpret_cast<float*>(static_cast<char*>(a->workspace) + d.ws_ml) : nullptr;
+  dp.window = win.windowed; dp.win_lo = win.lo; dp.win_hi = win.hi;
+  if (fp8) {
+    dp.k_scale = c.qz->k_scale; dp.v_scale = c.qz->v_scale;
+    dp.ks_b = c.qz->k_scale_stride0; dp.ks_h = c.qz->k_scale_stride1;
+    dp.vs_b = c.qz->v_scale_stride0; dp.vs_h = c.qz->v_scale_stride1;
+  }
+  if (ragged) {
+    dp.cu_q = c.seqs->cu_seqlens_q;
+    dp.total_q = (int)c.seqs->total_q;
+    dp.slots = (int)d.slots;
+    dp.append = kv->new_len != 0 ? 1 : 0;
+  }
+  return dp;
+}
+
 int decode_call(const DecodeCall& c) {
   const bool ragged = c.seqs != nullptr, fp8 = c.qz != nullptr;
   // the checks, once; a rectangular call's window comes after its cache checks, a ragged step's among its own arguments
@@ -598,45 +645,7 @@ int decode_call(const DecodeCall& c) {
       return fail(FCSA_ERR_WORKSPACE, "%s: workspace too small: %zu < %zu bytes", who, a->workspace_bytes, d.total);
     if ((reinterpret_cast<uintptr_t>(a->workspace) & 255) != 0) return fail(FCSA_ERR_WORKSPACE, "%s: workspace not 256-byte aligned", who);
   }
-  // One fill of the most derived block: every kernel gets the part it takes (fcsa_kernels.h).  A ragged step has packed q / o / k_new /
-  // v_new views, per-sequence row counts in place of N / row_tiles / new_len, and an lse view without a batch stride.
-  const int es = elem_size(p.dtype), ces = fp8 ? 1 : es;
-  auto rows_view = [&](const fcsa_tensor& t) { return view(ragged ? packed(t) : t, es); };
-  fcsa::DecodeRaggedParams dp{};
-  dp.q = rows_view(a->q);
-  dp.o = rows_view(a->o);
-  dp.kc = view(kv->k_cache, ces);
-  dp.vc = view(kv->v_cache, ces);
-  dp.kn = rows_view(kv->k_new);
-  dp.vn = rows_view(kv->v_new);
-  dp.seqlens = kv->cache_seqlens;
-  dp.table = kv->block_table;
-  dp.table_stride = kv->block_table_stride;
-  dp.capacity = kv->capacity;
-  dp.page = kv->block_table != nullptr ? kv->page_size : 0;
-  dp.num_blocks = kv->num_blocks;
-  dp.new_len = ragged ? 0 : kv->new_len;
-  dp.B = p.batch; dp.H = p.heads; dp.Hk = p.kv_heads; dp.G = p.heads / p.kv_heads; dp.N = ragged ? 0 : p.q_len;
-  dp.row_tiles = d.row_tiles; dp.splits = d.splits;
-  dp.causal = win.causal; dp.l2norm = p.l2norm_qk; dp.groups = p.l2norm_qk ? p.groups : 1;
-  dp.c1 = p.scale * kLog2e;
-  dp.c2 = exponent_shift(p, false) * kLog2e;
-  dp.l_eps = rowsum_eps(p, false);
-  dp.dyn = dynamic_shift(p, false) ? 1 : 0;
-  dp.ws_o = static_cast<float*>(a->workspace);
-  dp.ws_ml = reinterpret_cast<float*>(static_cast<char*>(a->workspace) + d.ws_ml);
-  dp.window = win.windowed; dp.win_lo = win.lo; dp.win_hi = win.hi;
-  if (fp8) {
-    dp.k_scale = c.qz->k_scale; dp.v_scale = c.qz->v_scale;
-    dp.ks_b = c.qz->k_scale_stride0; dp.ks_h = c.qz->k_scale_stride1;
-    dp.vs_b = c.qz->v_scale_stride0; dp.vs_h = c.qz->v_scale_stride1;
-  }
-  if (ragged) {
-    dp.cu_q = c.seqs->cu_seqlens_q;
-    dp.total_q = (int)c.seqs->total_q;
-    dp.slots = (int)d.slots;
-    dp.append = kv->new_len != 0 ? 1 : 0;
-  }
+  const fcsa::DecodeRaggedParams dp = decode_params(c, win, d);
   const fcsa::DecodeLseOut lo = c.lse != nullptr ? fcsa::DecodeLseOut{c.lse->lse, ragged ? 0 : c.lse->stride0, c.lse->stride1, c.lse->stride2} : fcsa::DecodeLseOut{};
   // 1. the append (before anything reads the cache: same stream), 2. the split partials, 3. their combine
   const fcsa::DecodeForm form = {fp8, ragged};
@@ -650,6 +659,37 @@ int decode_call(const DecodeCall& c) {
   if (int rc = timed(n.name, n.what, s, [&] { return fcsa::launch_decode(p.dtype, p.dim_head, form, dp, s); })) return rc;
   const LaunchName& m = kCombineName[ragged][fp8][c.lse != nullptr];
   return timed(m.name, m.what, s, [&] { return fcsa::launch_decode_combine(p.dtype, p.dim_head, form, dp, c.lse != nullptr ? &lo : nullptr, s); });
+}
+
+// A prompt chunk against the cache (fcsa_forward_kvcache_prefill): the ragged step's checks, its append with the parameter block the ragged
+// call fills, then one launch of the multi-wave kernel (fcsa_prefill.hip) with 128-row slots, one split and no workspace.
+int prefill_call(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_lse_out* lse) {
+  const DecodeCall c = {a, kv, seqs, nullptr, nullptr, lse};
+  if (int rc = check_kvcache_varlen(c)) return rc;
+  const fcsa_problem& p = a->p;
+  if (p.dtype != FCSA_F16 && p.dtype != FCSA_BF16)
+    return fail(FCSA_ERR_UNSUPPORTED, "kvcache_prefill: float32 is not supported (f16 or bf16; fcsa_forward_kvcache_varlen takes float32)");
+  if (p.dim_head != 64 && p.dim_head != 128)
+    return fail(FCSA_ERR_UNSUPPORTED, "kvcache_prefill: dim_head %d is not supported (64 or 128; fcsa_forward_kvcache_varlen takes the others)", p.dim_head);
+  const int G = p.heads / p.kv_heads;
+  const int64_t slots = fcsa::prefill_slots(seqs->total_q, std::max(p.batch, 0), G, fcsa::kPrefillRows);
+  if (slots * p.kv_heads > INT32_MAX) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_prefill: grid above 2^31 workgroups");
+  if (p.batch == 0 || seqs->total_q == 0) return FCSA_OK;      // no packed row: nothing to append, nothing to write
+  if (p.heads > 0 && lse != nullptr && lse->lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_prefill: lse: null pointer");
+  const DecodeWindow win = decode_window(p, *kv, true, nullptr);
+  fcsa::DecodeRaggedParams dp = decode_params(c, win, decode_plan(p, *kv, seqs, win.reach()));
+  hipStream_t s = static_cast<hipStream_t>(a->stream);
+  if (kv->new_len > 0 && kv->capacity > 0) {
+    const LaunchName& n = kAppendName[1][0];
+    if (int rc = timed(n.name, n.what, s, [&] { return fcsa::launch_kv_append(p.dtype, p.dim_head, {false, true}, dp, s); })) return rc;
+  }
+  if (p.heads <= 0) return FCSA_OK;
+  dp.slots = (int)slots;
+  dp.splits = 1;
+  dp.ws_o = nullptr;
+  dp.ws_ml = nullptr;
+  const fcsa::DecodeLseOut lo = lse != nullptr ? fcsa::DecodeLseOut{lse->lse, 0, lse->stride1, lse->stride2} : fcsa::DecodeLseOut{};
+  return timed("prefill", "prefill", s, [&] { return fcsa::launch_prefill(p.dtype, p.dim_head, dp, lse != nullptr ? &lo : nullptr, s); });
 }
 
 }  // namespace
@@ -695,6 +735,11 @@ int fcsa_forward_kvcache_lse(const fcsa_forward_args* a, const fcsa_kvcache* kv,
   const bool rows = a->p.batch > 0 && a->p.heads > 0 && (seqs != nullptr ? seqs->total_q > 0 : a->p.q_len > 0);
   if (rows && lse->lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_lse: lse: null pointer");
   return decode_call({a, kv, seqs, qz, w, lse});
+}
+
+int fcsa_forward_kvcache_prefill(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_lse_out* lse) {
+  if (a == nullptr || kv == nullptr || seqs == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_prefill: null argument");
+  return prefill_call(a, kv, seqs, lse);
 }
 
 int fcsa_merge_states(const fcsa_merge_args* a) {

@@ -20,6 +20,7 @@
 // parameter block (DecodeRaggedParams, fcsa_kernels.h).  Each dispatches dtype, head dim and form (fp8, ragged) once, works out its grid
 // once, and hands the entry point it picks the part of the block that entry point declares (launch_part).
 #include "fcsa_common.cuh"
+#include "fcsa_decode_common.cuh"
 
 #include <cmath>
 #include <type_traits>
@@ -39,33 +40,6 @@ template <int D, int ES, bool GEN> struct DecodeLds {
   static constexpr int BYTES = VBYTES + NORM;
 };
 
-// the lane's fragment of a row: NJ units of UE elements, unit j holds features (4 j + hi) * UE ... + UE - 1 (hi = lane >> 4)
-template <typename T> struct Unit;
-template <> struct Unit<BF16> {
-  static constexpr int UE = 8;
-  static FCSA_DEV f32x4 mfma(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  }
-};
-template <> struct Unit<F16> {
-  static constexpr int UE = 8;
-  static FCSA_DEV f32x4 mfma(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  }
-};
-template <> struct Unit<F32> {
-  static constexpr int UE = 4;
-};
-
-template <typename T> FCSA_DEV void unpack(const u32x4& u, float (&x)[Unit<T>::UE]) {
-  if constexpr (Traits<T>::ES == 4) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) x[e] = as_f32(u[e]);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { x[2 * e] = Traits<T>::lo(u[e]); x[2 * e + 1] = Traits<T>::hi(u[e]); }
-  }
-}
 // eight e4m3fn codes (byte e of the pair = element e) -> their exact float32 values
 FCSA_DEV void unpack_fp8(const u32x2& u, float (&x)[8]) {
 #pragma unroll
@@ -73,91 +47,6 @@ FCSA_DEV void unpack_fp8(const u32x2& u, float (&x)[8]) {
     const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)u[w], false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)u[w], true);
     x[4 * w] = a[0]; x[4 * w + 1] = a[1]; x[4 * w + 2] = b[0]; x[4 * w + 3] = b[1];
   }
-}
-template <typename T> FCSA_DEV u32x4 pack(const float (&x)[Unit<T>::UE], float mul) {
-  u32x4 u;
-  if constexpr (Traits<T>::ES == 4) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) u[e] = __builtin_bit_cast(uint32_t, x[e] * mul);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) u[e] = Traits<T>::pack2(x[2 * e] * mul, x[2 * e + 1] * mul);
-  }
-  return u;
-}
-
-// Grouped l2norm of one row held by the four lanes x, x + 16, x + 32, x + 48 (x = lane & 15): x *= 1 / max(||group||, 1e-12), the l2norm
-// kernel's formula.  gs = features per group (decode_groups_fast: one group, a divisor of UE, or UE times a power of two).  Every lane runs
-// every shuffle (gs is uniform).
-template <int NJ, int UE> FCSA_DEV void group_normalise(float (&x)[NJ][UE], int gs, int D) {
-  float ss[NJ][UE];
-#pragma unroll
-  for (int j = 0; j < NJ; ++j)
-#pragma unroll
-    for (int e = 0; e < UE; ++e) ss[j][e] = x[j][e] * x[j][e];
-  if (gs == D) {
-    float t = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int e = 0; e < UE; ++e) t += ss[j][e];
-    t += __shfl_xor(t, 16, 64);
-    t += __shfl_xor(t, 32, 64);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int e = 0; e < UE; ++e) ss[j][e] = t;
-  } else if (gs <= UE) {
-#pragma unroll
-    for (int s = 1; s < UE; s *= 2) {
-      if (s < gs) {
-        float n[NJ][UE];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-          for (int e = 0; e < UE; ++e) n[j][e] = ss[j][e] + ss[j][e ^ s];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-          for (int e = 0; e < UE; ++e) ss[j][e] = n[j][e];
-      }
-    }
-  } else {
-    const int units = gs / UE;
-    float u[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      u[j] = 0.f;
-#pragma unroll
-      for (int e = 0; e < UE; ++e) u[j] += ss[j][e];
-    }
-    if (units >= 2) {
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) u[j] += __shfl_xor(u[j], 16, 64);
-    }
-    if (units >= 4) {
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) u[j] += __shfl_xor(u[j], 32, 64);
-    }
-#pragma unroll
-    for (int s = 1; s < NJ; s *= 2) {
-      if (4 * s < units) {
-        float n[NJ];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) n[j] = (j ^ s) < NJ ? u[j] + u[j ^ s] : u[j];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) u[j] = n[j];
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int e = 0; e < UE; ++e) ss[j][e] = u[j];
-  }
-#pragma unroll
-  for (int j = 0; j < NJ; ++j)
-#pragma unroll
-    for (int e = 0; e < UE; ++e) x[j][e] *= 1.f / fmaxf(sqrtf(ss[j][e]), 1e-12f);
 }
 
 // Any group width (the GEN form: D = 96 with 48, 24, 12, 6 or 3 features per group, which straddle the lanes' fragments): each lane
@@ -193,16 +82,6 @@ template <int NJ, int UE, int D> FCSA_DEV void group_normalise_lds(float (&x)[NJ
   __syncthreads();      // the next row set rewrites the scratch
 }
 
-// Address of cache position `first` (a multiple of 16, uniform) of sequence b, K/V head kvh: a block-table lookup per 16 positions
-// (pages are multiples of 16 positions, so the 16 keys of a fragment never straddle two pages).  Block ids are clamped to the pool.
-FCSA_DEV const char* cache_base(const DecodeParams& p, const View& v, int b, int kvh, int first) {
-  if (p.table != nullptr) {
-    int blk = p.table[(int64_t)b * p.table_stride + first / p.page];
-    blk = min(max(blk, 0), p.num_blocks - 1);
-    return v.p + (int64_t)blk * v.sb + (int64_t)kvh * v.sh + (int64_t)(first % p.page) * v.sn;
-  }
-  return v.p + (int64_t)b * v.sb + (int64_t)kvh * v.sh + (int64_t)first * v.sn;
-}
 
 // FP8: the cache holds one-byte codes -- a K fragment is 8 bytes, a 16-byte V chunk 16 features (at D = 16 half the lanes have none)
 template <typename T, int D, bool FP8 = false> struct DecodeRegs {

@@ -280,6 +280,39 @@ constexpr bool ragged_tile(const int32_t* cu, int B, int64_t total, int G, int64
   return t >= 0 && t < ((int64_t)G * (en - st) + kDecodeRows - 1) / kDecodeRows;
 }
 
+// Prefill against the cache (fcsa_forward_kvcache_prefill, csrc/fcsa_prefill.hip): the same flat slots with the tile height `rows` as a
+// parameter (kPrefillRows for the kernel).  The argument above holds for any height: consecutive bases differ by at least
+// floor(G N_b / rows) + 1 >= ceil(G N_b / rows).  The rows of a sequence's K/V head are ordered TOKEN-major here, r = i * G + g, so a tile
+// covers consecutive tokens and its causal key range is tight.
+constexpr int kPrefillRows = 128;          // query rows per workgroup: 4 waves x 2 MFMA tiles of 16
+constexpr int kPrefillStage = 64;          // keys per LDS stage (two 32-key blocks of the decode key loop)
+constexpr int64_t prefill_base(int64_t cu_b, int b, int G, int rows) { return (int64_t)G * cu_b / rows + b; }
+constexpr int64_t prefill_slots(int64_t total_q, int64_t B, int G, int rows) { return (int64_t)G * total_q / rows + B; }
+// Slot -> (sequence b, row tile rt of its G * len rows, first packed row `start`, rows `len`); false: the slot is idle.  B >= 1.
+constexpr bool prefill_tile(const int32_t* cu, int B, int64_t total, int G, int rows, int64_t slot, int& b, int& rt, int& start, int& len) {
+  int lo = 0, hi = B - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) / 2;
+    if (prefill_base(ragged_cu(cu[mid], total), mid, G, rows) <= slot) lo = mid; else hi = mid - 1;
+  }
+  const int64_t st = ragged_cu(cu[lo], total), en = std::max(ragged_cu(cu[lo + 1], total), st);
+  const int64_t t = slot - prefill_base(st, lo, G, rows);
+  b = lo;
+  start = (int)st;
+  len = (int)(en - st);
+  rt = (int)t;
+  return t >= 0 && t < ((int64_t)G * (en - st) + rows - 1) / rows;
+}
+// The key range [0, kend) that the rows [first, first + count) of a sequence's K/V head visit (token-major rows, N tokens against L cached
+// positions): every key without `causal`; under it, one past the last key visible to the last token among the rows (bottom-right
+// alignment: token i sees keys j <= L - N + i), clamped to [0, L].  Rows at or beyond G * N do not count.
+constexpr int prefill_kend(int L, int N, int G, int64_t first, int count, bool causal) {
+  const int64_t last = std::min(first + count, (int64_t)G * N) - 1;
+  if (last < first || L <= 0) return 0;
+  if (!causal) return L;
+  return (int)std::min<int64_t>(std::max<int64_t>((int64_t)L - N + last / G + 1, 0), L);
+}
+
 // ---- log-sum-exp of a decoded row, and merging attention states (fcsa_forward_kvcache_lse, fcsa_merge_states) --------------------------
 // The two functions below call expf / log / log2, which are no constant expressions: they are host functions for the C++ compiler
 // (tests/native/merge_states_check.cpp) and host + device functions for hipcc (decode_combine_lse*, merge_states_kernel).

@@ -170,6 +170,10 @@ struct DecodeForm { bool fp8, ragged; };
 hipError_t launch_kv_append(int dtype, int D, DecodeForm f, const DecodeRaggedParams& p, hipStream_t s);
 hipError_t launch_decode(int dtype, int D, DecodeForm f, const DecodeRaggedParams& p, hipStream_t s);
 hipError_t launch_decode_combine(int dtype, int D, DecodeForm f, const DecodeRaggedParams& p, const DecodeLseOut* lse, hipStream_t s);
+// A prompt chunk against the cache (fcsa_forward_kvcache_prefill; csrc/fcsa_prefill.hip): the ragged step's block with slots =
+// fcsa::prefill_slots(total_q, B, G, kPrefillRows), one split and no workspace; f16 / bf16, D = 64 / 128 (anything else: hipErrorInvalidValue).
+// One kernel writes o and, where lse is not nullptr, the rows' log-sum-exp.
+hipError_t launch_prefill(int dtype, int D, const DecodeRaggedParams& p, const DecodeLseOut* lse, hipStream_t s);
 
 // Merging attention states (fcsa_merge_states, csrc/fcsa_merge.hip): S states (o_s, lse_s) of the rows [n0, n1, n2] -> (o, lse).  o views
 // carry BYTE strides, lse views ELEMENT strides.

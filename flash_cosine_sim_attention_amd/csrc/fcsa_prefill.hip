@@ -1,0 +1,268 @@
+// fcsa_prefill.hip -- a prompt chunk against the key/value cache (fcsa_forward_kvcache_prefill, include/fcsa.h).
+//
+//   prefill_kernel   one 4-wave workgroup per (row-tile slot, K/V head): 128 token-major rows (r = i * G + g) of one sequence's K/V head, two
+//                    16-row MFMA tiles per wave.  The keys [0, kend) of the tile (prefill_kend: under `causal` it stops at the last key the
+//                    tile's last token sees) go through LDS in 64-key stages, double-buffered: wave w loads the stage's keys 16 w ... 16 w + 15
+//                    in the decode kernel's register layout (key on lane & 15, feature quarter on lane >> 4), l2-normalises them with the
+//                    decode kernel's group_normalise, rounds them to the type and writes K^ -- once per workgroup, not once per 16 rows --
+//                    and V raw.  The next stage's global loads are in flight during the current stage's math.
+//                    Per wave, 32-key block and row tile the math is decode_body's, statement for statement (S^T = K^ Q^T on
+//                    mfma_f32_16x16x32 with the query row on the lane, the same mask and exponent regime, ds_read_tr16_b64 for V^T P~^T), and
+//                    the epilogue is decode_combine_body's arithmetic at one split, so o and lse are bit for bit those of the ragged call
+//                    with one key split.  Every K^ fragment and transposed V read from LDS feeds both row tiles of the wave.
+// The append before it is the ragged call's (launch_kv_append with the same parameter block).  16-bit types, D = 64 / 128 only.
+#include "fcsa_common.cuh"
+#include "fcsa_decode_common.cuh"
+
+#include <cmath>
+#include <type_traits>
+
+namespace fcsa {
+
+namespace {
+
+constexpr int kPrefillWaves = 4;
+constexpr int kPrefillTiles = kPrefillRows / kDecodeRows / kPrefillWaves;     // 16-row MFMA tiles per wave
+
+// LDS plan, for the kernel and its launcher: two stage buffers, each K^ [64][PITCH] then V [64][PITCH]; rows of D elements padded by 16
+// bytes (the decode kernel's V pitch: the transposed reads address a 32-key block exactly as they do there)
+template <int D> struct PrefillLds {
+  static constexpr int PITCH = D * 2 + 16;
+  static constexpr int TILE = kPrefillStage * PITCH;
+  static constexpr int BUF = 2 * TILE;
+  static constexpr int BYTES = 2 * BUF;
+};
+
+// A wave's 16 keys of a stage in registers: lane (x, hi) holds features (4 j + hi) * 8 ... + 7 of key `first16 + x` of K and of V
+template <typename T, int D> struct PrefillRegs {
+  static constexpr int NJ = D / 32;
+  u32x4 k[NJ], v[NJ];
+
+  // positions at or beyond L read position L - 1 (in bounds) and their V is zeroed: DecodeRegs::load's rule
+  FCSA_DEV void load(const DecodeParams& p, int b, int kvh, int first16, int L, int lane) {
+    const int x = lane & 15, hi = lane >> 4;
+    const int first = min(first16, (L - 1) & ~15);
+    const int pos = min(first16 + x, L - 1);
+    const char* krow = cache_base(p, p.kc, b, kvh, first) + (int64_t)(pos - first) * p.kc.sn;
+    const char* vrow = cache_base(p, p.vc, b, kvh, first) + (int64_t)(pos - first) * p.vc.sn;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int f = (4 * j + hi) * 8;
+      k[j] = *reinterpret_cast<const u32x4*>(krow + f * 2);
+      const u32x4 val = *reinterpret_cast<const u32x4*>(vrow + f * 2);
+      v[j] = first16 + x < L ? val : u32x4{0u, 0u, 0u, 0u};
+    }
+  }
+
+  // K^ (normalised and rounded as decode_body does before its first product) and raw V -> row `row` of a stage buffer
+  FCSA_DEV void store(char* buf, int row, int lane, bool l2norm, int gs) const {
+    constexpr int PITCH = PrefillLds<D>::PITCH;
+    const int hi = lane >> 4;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) *reinterpret_cast<u32x4*>(buf + PrefillLds<D>::TILE + row * PITCH + (4 * j + hi) * 16) = v[j];
+    float xk[NJ][8];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) unpack<T>(k[j], xk[j]);
+    if (l2norm) group_normalise<NJ, 8>(xk, gs, D);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) *reinterpret_cast<u32x4*>(buf + row * PITCH + (4 * j + hi) * 16) = pack<T>(xk[j], 1.f);
+  }
+};
+
+// Waves per SIMD the register allocation aims at: two (two workgroups per CU, at most 256 registers) wherever that leaves no scratch.  The
+// f16 D = 128 instantiations take 257 - 259 registers and spill 1 - 9 of them when held to 256 (bf16: 253 - 255, none), so they run one wave
+// per SIMD.
+template <typename T, int D> constexpr int kPrefillWavesPerSimd = (std::is_same_v<T, F16> && D == 128) ? 1 : 2;
+
+template <typename T, int D, bool DYN>
+__global__ __launch_bounds__(64 * kPrefillWaves, (kPrefillWavesPerSimd<T, D>)) void prefill_kernel(DecodeRaggedParams p, DecodeLseOut lo) {
+  typedef PrefillLds<D> LP;
+  typedef PrefillRegs<T, D> R;
+  constexpr int NJ = R::NJ, FB = D / 16, NT = kPrefillTiles;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+
+  const int lane = threadIdx.x & 63, x = lane & 15, hi = lane >> 4;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int kvh = blockIdx.x % p.Hk;
+  int b, rt, q0, N;
+  if (!prefill_tile(p.cu_q, p.B, p.total_q, p.G, kPrefillRows, blockIdx.x / p.Hk, b, rt, q0, N)) return;
+  const int L = decode_len(p.seqlens != nullptr, p.seqlens != nullptr ? p.seqlens[b] : 0, p.append ? N : 0, p.capacity);
+  const int64_t row0 = (int64_t)rt * kPrefillRows;
+  const int kend = prefill_kend(L, N, p.G, row0, kPrefillRows, p.causal != 0);
+  // a wave stops at the last key its own 32 rows see; it still loads its share of every stage and joins every barrier
+  const int wave_kend = prefill_kend(L, N, p.G, row0 + wave * (NT * kDecodeRows), NT * kDecodeRows, p.causal != 0);
+  const int gs = D / p.groups;
+
+  // this lane's query rows, one per row tile: the column of every MFMA result
+  int last_key[NT];
+  u32x4 qf[NT][NJ];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int64_t r = row0 + (wave * NT + t) * kDecodeRows + x;
+    const bool row_ok = r < (int64_t)p.G * N;
+    const int g = row_ok ? (int)(r % p.G) : 0, qi = row_ok ? (int)(r / p.G) : 0;
+    last_key[t] = L - N + qi;                  // causal: key j is visible iff j <= last_key
+    float xq[NJ][8];
+    const char* qrow = p.q.p + (int64_t)(kvh * p.G + g) * p.q.sh + (int64_t)(q0 + qi) * p.q.sn;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int f = (4 * j + hi) * 8;
+      const u32x4 u = row_ok ? *reinterpret_cast<const u32x4*>(qrow + f * 2) : u32x4{0u, 0u, 0u, 0u};
+      unpack<T>(u, xq[j]);
+    }
+    if (p.l2norm) group_normalise<NJ, 8>(xq, gs, D);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) qf[t][j] = pack<T>(xq[j], p.l2norm ? p.c1 : 1.f);     // c1 * q^, one rounding
+  }
+  const float smul = p.l2norm ? 1.f : p.c1;
+
+  f32x4 acc[NT][FB];
+  float m[NT], l[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+#pragma unroll
+    for (int fb = 0; fb < FB; ++fb) acc[t][fb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    m[t] = DYN ? -INFINITY : p.c2;
+    l[t] = 0.f;
+  }
+
+  const int stages = (kend + kPrefillStage - 1) / kPrefillStage;
+  const int my_row = wave * 16 + x;              // the stage row this lane loads
+  R regs;
+  if (stages > 0) {
+    regs.load(p, b, kvh, wave * 16, L, lane);
+    regs.store(smem, my_row, lane, p.l2norm != 0, gs);
+  }
+  __syncthreads();
+  for (int st = 0; st < stages; ++st) {
+    const bool more = st + 1 < stages;
+    if (more) regs.load(p, b, kvh, (st + 1) * kPrefillStage + wave * 16, L, lane);
+    const char* ks = smem + (st & 1) * LP::BUF;
+    const char* vs = ks + LP::TILE;
+#pragma unroll
+    for (int blk = 0; blk < kPrefillStage / kDecodeBlock; ++blk) {
+      const int kb = st * kPrefillStage + blk * kDecodeBlock;
+      if (kb >= wave_kend) break;
+      // S^T = K^ Q^T for the two 16-key halves: s[t][sb][rr] = logit of key kb + 16 sb + 4 hi + rr for row x of tile t (log2 units)
+      f32x4 s[NT][2];
+#pragma unroll
+      for (int sb = 0; sb < 2; ++sb) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) s[t][sb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          const u32x4 kf = *reinterpret_cast<const u32x4*>(ks + (blk * kDecodeBlock + 16 * sb + x) * LP::PITCH + (4 * j + hi) * 16);
+#pragma unroll
+          for (int t = 0; t < NT; ++t) s[t][sb] = Unit<T>::mfma(kf, qf[t][j], s[t][sb]);
+        }
+      }
+      u32x4 pb[NT];
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+#pragma unroll
+        for (int sb = 0; sb < 2; ++sb)
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) {
+            const int key = kb + 16 * sb + 4 * hi + rr;
+            const bool vis = key < L && (!p.causal || key <= last_key[t]);
+            s[t][sb][rr] = vis ? s[t][sb][rr] * smul : -INFINITY;
+          }
+        float shift = p.c2;
+        if constexpr (DYN) {
+          float bm = fmaxf(fmaxf(fmaxf(s[t][0][0], s[t][0][1]), fmaxf(s[t][0][2], s[t][0][3])),
+                           fmaxf(fmaxf(s[t][1][0], s[t][1][1]), fmaxf(s[t][1][2], s[t][1][3])));
+          bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
+          bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
+          const float mn = fmaxf(m[t], bm);
+          shift = mn == -INFINITY ? 0.f : mn;
+          const float alpha = fast_exp2(m[t] - shift);      // 0 while the row has seen no key
+#pragma unroll
+          for (int fb = 0; fb < FB; ++fb) acc[t][fb] *= alpha;
+          l[t] *= alpha;
+          m[t] = mn;
+        }
+        f32x4 pr[2];
+#pragma unroll
+        for (int sb = 0; sb < 2; ++sb)
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) {
+            pr[sb][rr] = fast_exp2(s[t][sb][rr] - shift);
+            l[t] += pr[sb][rr];
+          }
+        // k-slot (hi, e) of the P~V product is key 16 (e >> 2) + 4 hi + (e & 3): P~ is used where the first product left it
+        pb[t][0] = Traits<T>::pack2(pr[0][0], pr[0][1]);
+        pb[t][1] = Traits<T>::pack2(pr[0][2], pr[0][3]);
+        pb[t][2] = Traits<T>::pack2(pr[1][0], pr[1][1]);
+        pb[t][3] = Traits<T>::pack2(pr[1][2], pr[1][3]);
+      }
+      // O^T += V^T P~^T: lane 4q + p of the 16-lane group hi addresses key 4 hi + q, features 16 fb + 4p ... + 3; lane x receives feature 16 fb + x
+      typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+      const char* a0 = vs + (blk * kDecodeBlock + 4 * hi + (x >> 2)) * LP::PITCH + 8 * (x & 3);
+#pragma unroll
+      for (int fb = 0; fb < FB; ++fb) {
+        const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0 + 32 * fb));
+        const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0 + 16 * LP::PITCH + 32 * fb));
+        const u32x2 u0 = __builtin_bit_cast(u32x2, v0), u1 = __builtin_bit_cast(u32x2, v1);
+        const u32x4 vf = u32x4{u0[0], u0[1], u1[0], u1[1]};
+#pragma unroll
+        for (int t = 0; t < NT; ++t) acc[t][fb] = Unit<T>::mfma(vf, pb[t], acc[t][fb]);
+      }
+    }
+    // the other buffer was last read before the barrier that ended the previous iteration
+    if (more) regs.store(smem + ((st + 1) & 1) * LP::BUF, my_row, lane, p.l2norm != 0, gs);
+    __syncthreads();
+  }
+
+  // Row x of tile t: O^T[16 fb + 4 hi + rr][x] in acc[t][fb][rr].  The combine of one split (decode_combine_body): weight exp2(m - M) = 1.
+  // The row's head and token are worked out again here (from an opaque lane id), so that no address lives through the key loop.
+  const int xe = opaque(lane) & 15, hie = opaque(lane) >> 4;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    float ls = l[t];
+    ls += __shfl_xor(ls, 16, 64);
+    ls += __shfl_xor(ls, 32, 64);
+    const int64_t r = row0 + (wave * NT + t) * kDecodeRows + xe;
+    if (r >= (int64_t)p.G * N) continue;
+    const int h = kvh * p.G + (int)(r % p.G);
+    const int64_t tok = q0 + r / p.G;
+    const float M = m[t];
+    const bool any = M != -INFINITY;
+    const float w = exp2f(M - M);
+    float lsum = 0.f;
+    if (any) lsum += w * ls;
+    const float inv = p.dyn ? (lsum > 0.f ? 1.f / lsum : 0.f) : 1.f / fmaxf(lsum, p.l_eps);
+    char* dst = p.o.p + (int64_t)h * p.o.sh + tok * p.o.sn + 4 * hie * 2;
+#pragma unroll
+    for (int fb = 0; fb < FB; ++fb) {
+      f32x4 a = {0.f, 0.f, 0.f, 0.f};
+      if (any) a += w * acc[t][fb];
+      a *= inv;
+      *reinterpret_cast<u32x2*>(dst + 16 * fb * 2) = u32x2{Traits<T>::pack2(a[0], a[1]), Traits<T>::pack2(a[2], a[3])};
+    }
+    if (lo.lse != nullptr && hie == 0) lo.lse[(int64_t)h * lo.sh + tok * lo.sn] = decode_row_lse(M, lsum);
+  }
+}
+
+}  // namespace
+
+// one 4-wave workgroup per (row-tile slot of 128 rows, K/V head); lse: nullptr, or where the rows' log-sum-exp goes as well
+hipError_t launch_prefill(int dtype, int D, const DecodeRaggedParams& p, const DecodeLseOut* lse, hipStream_t s) {
+  if (dtype != FCSA_F16 && dtype != FCSA_BF16) return hipErrorInvalidValue;
+  if (D != 64 && D != 128) return hipErrorInvalidValue;
+  if (p.l2norm && !decode_groups_fast(D, p.groups, 8)) return hipErrorInvalidValue;
+  if ((int64_t)p.slots * p.Hk <= 0) return hipSuccess;
+  const dim3 grid((unsigned)((int64_t)p.slots * p.Hk)), block(64 * kPrefillWaves);
+  const DecodeLseOut lo = lse != nullptr ? *lse : DecodeLseOut{};
+  auto go = [&](auto t, auto d) -> hipError_t {
+    using T = decltype(t);
+    constexpr int DD = decltype(d)::value;
+    return p.dyn ? launch_with_lds<prefill_kernel<T, DD, true>>(grid, block, PrefillLds<DD>::BYTES, s, p, lo)
+                 : launch_with_lds<prefill_kernel<T, DD, false>>(grid, block, PrefillLds<DD>::BYTES, s, p, lo);
+  };
+  using D64 = std::integral_constant<int, 64>;
+  using D128 = std::integral_constant<int, 128>;
+  if (dtype == FCSA_BF16) return D == 64 ? go(BF16{}, D64{}) : go(BF16{}, D128{});
+  return D == 64 ? go(F16{}, D64{}) : go(F16{}, D128{});
+}
+
+}  // namespace fcsa

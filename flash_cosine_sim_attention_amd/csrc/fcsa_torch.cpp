@@ -59,7 +59,9 @@ namespace {
   X(forward_kvcache_varlen_ws, fcsa_forward_kvcache_varlen_workspace_bytes, false)        \
   /* the decode calls with the rows' log-sum-exp, and merging attention states */         \
   X(forward_kvcache_lse, fcsa_forward_kvcache_lse, false)                                 \
-  X(merge_states, fcsa_merge_states, false)
+  X(merge_states, fcsa_merge_states, false)                                               \
+  /* prompt chunks against the cache (the multi-wave prefill kernel) */                   \
+  X(forward_kvcache_prefill, fcsa_forward_kvcache_prefill, false)
 
 struct Abi {
 #define X(member, symbol, required) decltype(&symbol) member = &symbol;
@@ -704,8 +706,10 @@ Tensor varlen_window_attention_autograd(const Tensor& q, const Tensor& k, const 
 Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const optional<Tensor>& k_new, const optional<Tensor>& v_new,
                             const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table, int64_t max_seqlen_k, double scale, bool causal,
                             bool l2norm_qk, int64_t groups, const fcsa_window* win, const Tensor* k_scale = nullptr, const Tensor* v_scale = nullptr,
-                            const Tensor* cu_q = nullptr, int64_t max_seqlen_q = 0, Tensor* lse_out = nullptr) {
+                            const Tensor* cu_q = nullptr, int64_t max_seqlen_q = 0, Tensor* lse_out = nullptr, bool prefill = false) {
   const bool ragged = cu_q != nullptr;
+  if (prefill)      // kvcache_prefill_forward: a ragged step through fcsa_forward_kvcache_prefill (no workspace; the lse always)
+    need_abi("flash_cosine_sim_attention_prefill_with_kvcache", "fcsa_forward_kvcache_prefill", g_abi.forward_kvcache_prefill);
   const Layout ql = ragged ? kPacked : kDense;      // of q, o, k_new, v_new and the lse
   if (lse_out != nullptr) need_abi("return_lse", "fcsa_forward_kvcache_lse", g_abi.forward_kvcache_lse);
   if (ragged)
@@ -849,7 +853,8 @@ Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor
     qz.k_scale = ks.data_ptr<float>();
     qz.v_scale = vs.data_ptr<float>();
   }
-  const size_t wsb = ragged ? g_abi.forward_kvcache_varlen_ws(&a.p, &kv, &seqs, fp8 ? &qz : nullptr, win)
+  const size_t wsb = prefill ? 0
+                     : ragged ? g_abi.forward_kvcache_varlen_ws(&a.p, &kv, &seqs, fp8 ? &qz : nullptr, win)
                      : fp8 ? g_abi.forward_kvcache_quant_ws(&a.p, &kv, &qz, win)
                          : win != nullptr ? g_abi.forward_kvcache_window_ws(&a.p, &kv, win) : g_abi.forward_kvcache_ws(&a.p, &kv);
   Tensor ws;
@@ -863,6 +868,10 @@ Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor
     // float32 [B, H, N], or [total_q, H] for a ragged step; the workspace is that of the call without it
     *lse_out = ragged ? at::empty({N, H}, q.options().dtype(at::kFloat)) : at::empty({B, H, N}, q.options().dtype(at::kFloat));
     const fcsa_lse_out lo = strided<fcsa_lse_out>(*lse_out, ql);
+    if (prefill) {
+      check(g_abi.forward_kvcache_prefill(&a, &kv, &seqs, &lo), "fcsa_forward_kvcache_prefill");
+      return o;
+    }
     check(g_abi.forward_kvcache_lse(&a, &kv, ragged ? &seqs : nullptr, fp8 ? &qz : nullptr, win, &lo), "fcsa_forward_kvcache_lse");
     return o;
   }
@@ -922,6 +931,18 @@ std::tuple<Tensor, Tensor> kvcache_lse_forward(const Tensor& q, const Tensor& k_
   Tensor o = kvcache_forward_impl(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups,
                                   windowed ? &w : nullptr, k_scale.has_value() ? &*k_scale : nullptr, v_scale.has_value() ? &*v_scale : nullptr,
                                   cu_seqlens_q.has_value() ? &*cu_seqlens_q : nullptr, max_seqlen_q, &lse);
+  return {o, lse};
+}
+
+// A prompt chunk against the cache on the multi-wave prefill kernel: kvcache_lse_forward's ragged step without scales and window sides.
+// f16 / bf16 and D = 64 / 128 only (the library refuses the rest).
+std::tuple<Tensor, Tensor> kvcache_prefill_forward(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& cu_seqlens_q,
+                                                   const optional<Tensor>& k_new, const optional<Tensor>& v_new, const optional<Tensor>& cache_seqlens,
+                                                   const optional<Tensor>& block_table, int64_t max_seqlen_q, int64_t max_seqlen_k, double scale,
+                                                   bool causal, bool l2norm_qk, int64_t groups) {
+  Tensor lse;
+  Tensor o = kvcache_forward_impl(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups,
+                                  nullptr, nullptr, nullptr, &cu_seqlens_q, max_seqlen_q, &lse, true);
   return {o, lse};
 }
 
@@ -1074,6 +1095,14 @@ TORCH_LIBRARY_IMPL(fcsa, CUDA, m) {       // ROCm builds of PyTorch dispatch HIP
   m.impl("kvcache_lse_forward", &kvcache_lse_forward);
   m.impl("merge_states", &merge_states);
 }
+
+// The prefill op has a namespace of its own: the op set of `fcsa` is pinned.  Forward only: no Autograd kernel.
+TORCH_LIBRARY(fcsa_prefill, m) {
+  m.def("kvcache_prefill_forward(Tensor q, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor cu_seqlens_q, Tensor? k_new, Tensor? v_new, "
+        "Tensor? cache_seqlens, Tensor? block_table, int max_seqlen_q, int max_seqlen_k, float scale, bool causal, bool l2norm_qk, "
+        "int groups) -> (Tensor, Tensor)");
+}
+TORCH_LIBRARY_IMPL(fcsa_prefill, CUDA, m) { m.impl("kvcache_prefill_forward", &kvcache_prefill_forward); }
 
 TORCH_LIBRARY_IMPL(fcsa, Autograd, m) {
   m.impl("attention", &attention_autograd);

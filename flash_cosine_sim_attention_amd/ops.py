@@ -471,6 +471,36 @@ def flash_cosine_sim_attention_with_kvcache(q, k_cache, v_cache, k_new=None, v_n
     return _torch_ops.load().kvcache_forward(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, c.max_k, *tail)
 
 
+def _ragged_step(fn, q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q, max_seqlen_k, k_scale, v_scale,
+                 window, cpu_kw):
+    """What `flash_cosine_sim_attention_varlen_with_kvcache` and `flash_cosine_sim_attention_prefill_with_kvcache` share: the checks of a
+    packed step (q's rank, the caches, cu_seqlens_q, the packed new rows, the bounds, the tables) and, for CPU tensors, the forward-only
+    path of `cpu.py`.  Returns (the _CacheCall, the CPU result or None, cu_seqlens_q on q's device, max_seqlen_q clamped to total_q)."""
+    q_fault = None if q.dim() == 3 else f"q must be a packed [total_q, heads, dim_head] tensor, got {tuple(q.shape)}"
+    c = _CacheCall(fn, q, q_fault, k_cache, v_cache, k_new, v_new, k_scale, v_scale)
+    if not isinstance(cu_seqlens_q, torch.Tensor) or cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 1:
+        raise TypeError("cu_seqlens_q must be a 1-D int32 tensor of sequences + 1 entries")
+    total_q, H, D = q.shape
+    B = cu_seqlens_q.numel() - 1
+    if k_new is not None and (k_new.shape != v_new.shape or tuple(k_new.shape) != (total_q, c.Hk, D)):
+        raise ValueError(f"k_new / v_new must be packed like q, [{total_q}, {c.Hk}, {D}], got {tuple(k_new.shape)} and {tuple(v_new.shape)}")
+    if max_seqlen_q is not None and (int(max_seqlen_q) != max_seqlen_q or max_seqlen_q < 0):
+        raise ValueError(f"max_seqlen_q must be a non-negative integer, got {max_seqlen_q}")
+    if cu_seqlens_q.device.type == "cpu":
+        _check_host_cu("cu_seqlens_q", cu_seqlens_q, total_q, None)
+    c.tables(B, cu_seqlens_q, k_new is not None, cache_seqlens, block_table, max_seqlen_k)
+    if q.device.type == "cpu":
+        if c.counts is None or (cache_seqlens is not None and c.lens is None):
+            raise ValueError("CPU tensors take host cu_seqlens_q and cache_seqlens tables")
+        lens = c.lens if c.lens is not None else [c.capacity] * B
+        detach = lambda t: None if t is None else t.detach()          # (grad mode is off here, or nothing requires grad)
+        out = _cpu.attention_forward_kvcache_varlen_cpu(q.detach(), k_cache, v_cache, cu_seqlens_q, detach(k_new), detach(v_new), lens, block_table,
+                                                        window_size=window, **cpu_kw, **c.cpu_quant())
+        return c, out, None, None
+    max_q = total_q if max_seqlen_q is None else min(int(max_seqlen_q), total_q)
+    return c, None, cu_seqlens_q.to(q.device, non_blocking=True), max_q
+
+
 def flash_cosine_sim_attention_varlen_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new=None, v_new=None, cache_seqlens=None,
                                                    block_table=None, max_seqlen_q=None, max_seqlen_k=None, scale=8, groups=1, causal=False,
                                                    l2norm_qk=True, k_scale=None, v_scale=None, return_lse=False, window_size=(-1, -1)):
@@ -494,37 +524,70 @@ def flash_cosine_sim_attention_varlen_with_kvcache(q, k_cache, v_cache, cu_seqle
     a step can be captured in a HIP graph.  CPU tensors take the forward-only path of `cpu.py` (host tables).
     The launch has one row-tile slot per 16 rows of G * N_b (about G * total_q / 16 + B per K/V head, whatever the longest sequence is), and
     every row tile re-reads and re-normalises its keys: this is the call for steps of one to a few dozen tokens per sequence.  Long prompt
-    chunks work, at the decode kernel's efficiency.
+    chunks work, at the decode kernel's efficiency; `flash_cosine_sim_attention_prefill_with_kvcache` is the call for those.
     return_lse=True: returns (o, lse) with lse float32 [total_q, H], as in `flash_cosine_sim_attention_with_kvcache`."""
     _check_return_lse(return_lse)
     window = _window(window_size)
-    q_fault = None if q.dim() == 3 else f"q must be a packed [total_q, heads, dim_head] tensor, got {tuple(q.shape)}"
-    c = _CacheCall("flash_cosine_sim_attention_varlen_with_kvcache", q, q_fault, k_cache, v_cache, k_new, v_new, k_scale, v_scale)
-    if not isinstance(cu_seqlens_q, torch.Tensor) or cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 1:
-        raise TypeError("cu_seqlens_q must be a 1-D int32 tensor of sequences + 1 entries")
-    total_q, H, D = q.shape
-    B = cu_seqlens_q.numel() - 1
-    if k_new is not None and (k_new.shape != v_new.shape or tuple(k_new.shape) != (total_q, c.Hk, D)):
-        raise ValueError(f"k_new / v_new must be packed like q, [{total_q}, {c.Hk}, {D}], got {tuple(k_new.shape)} and {tuple(v_new.shape)}")
-    if max_seqlen_q is not None and (int(max_seqlen_q) != max_seqlen_q or max_seqlen_q < 0):
-        raise ValueError(f"max_seqlen_q must be a non-negative integer, got {max_seqlen_q}")
-    if cu_seqlens_q.device.type == "cpu":
-        _check_host_cu("cu_seqlens_q", cu_seqlens_q, total_q, None)
-    c.tables(B, cu_seqlens_q, k_new is not None, cache_seqlens, block_table, max_seqlen_k)
+    c, cpu_result, cu_q, max_q = _ragged_step("flash_cosine_sim_attention_varlen_with_kvcache", q, k_cache, v_cache, cu_seqlens_q, k_new, v_new,
+                                              cache_seqlens, block_table, max_seqlen_q, max_seqlen_k, k_scale, v_scale, window,
+                                              dict(scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, return_lse=bool(return_lse)))
     if q.device.type == "cpu":
-        if c.counts is None or (cache_seqlens is not None and c.lens is None):
-            raise ValueError("CPU tensors take host cu_seqlens_q and cache_seqlens tables")
-        lens = c.lens if c.lens is not None else [c.capacity] * B
-        detach = lambda t: None if t is None else t.detach()          # (grad mode is off here, or nothing requires grad)
-        return _cpu.attention_forward_kvcache_varlen_cpu(q.detach(), k_cache, v_cache, cu_seqlens_q, detach(k_new), detach(v_new), lens,
-                                                         block_table, scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk,
-                                                         window_size=window, return_lse=bool(return_lse), **c.cpu_quant())
-    cu_q = cu_seqlens_q.to(q.device, non_blocking=True)
+        return cpu_result
     k_cache, v_cache, cache_seqlens, block_table = c.on_device()
-    max_q = total_q if max_seqlen_q is None else min(int(max_seqlen_q), total_q)
     op = _torch_ops.load().kvcache_lse_forward if return_lse else _torch_ops.load().kvcache_varlen_forward
     return op(q, k_cache, v_cache, cu_q, k_new, v_new, cache_seqlens, block_table, c.k_scale, c.v_scale, max_q, c.max_k, float(scale), bool(causal),
               bool(l2norm_qk), int(groups), window[0], window[1])
+
+
+def flash_cosine_sim_attention_prefill_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new=None, v_new=None, cache_seqlens=None,
+                                                    block_table=None, max_seqlen_q=None, max_seqlen_k=None, scale=8, groups=1, causal=False,
+                                                    l2norm_qk=True, k_scale=None, v_scale=None, return_lse=False, window_size=(-1, -1)):
+    """Prompt chunks against the key/value cache: `flash_cosine_sim_attention_varlen_with_kvcache` on a kernel built for many rows per
+    sequence.
+
+    Arguments, layouts, the append of k_new / v_new before attention reads the cache, the per-sequence bottom-right causal alignment, o = 0
+    and lse = -inf for rows without a visible key, N_b = 0, host tables validated and device tables trusted and clamped, no synchronisation
+    with device tables (so the call can be captured in a HIP graph): all as in `flash_cosine_sim_attention_varlen_with_kvcache`, whose
+    result this is -- bit for bit (o, lse and the caches) wherever that call runs one key split.
+    The kernel: four waves own 128 token-major rows of one sequence's K/V head, share each 64-key stage of the cache through LDS and
+    normalise every key once per workgroup (the ragged call: once per 16 rows); under causal a workgroup stops at its last visible key.
+    There are NO key splits: the grid is about G * total_q / 128 + B workgroups per K/V head, so this is the call for chunks long enough to
+    fill the chip with 128-row tiles (a few hundred tokens per sequence and up; max_seqlen_q and max_seqlen_k are accepted and size
+    nothing).  Steps of one to a few dozen tokens per sequence belong to `flash_cosine_sim_attention_varlen_with_kvcache`.
+    Supported: q, the caches and the new rows all float16 or all bfloat16; dim_head 64 or 128; any groups dividing it; any Hk dividing H.
+    float32, float8_e4m3fn caches (k_scale / v_scale), other head dims and a window_size other than (-1, -1) are refused:
+    `flash_cosine_sim_attention_varlen_with_kvcache` takes them.  CPU tensors are refused the same things and otherwise take the forward-only
+    path of `cpu.py`.  Forward only.
+    return_lse=True: returns (o, lse) with lse float32 [total_q, H]."""
+    fn, other = "flash_cosine_sim_attention_prefill_with_kvcache", "flash_cosine_sim_attention_varlen_with_kvcache"
+    _check_return_lse(return_lse)
+    window = _window(window_size)
+    # what this kernel does not take, before anything else (and before the device branch: CPU tensors are refused the same things)
+    if k_scale is not None or v_scale is not None or k_cache.dtype in _FP8_TYPES or v_cache.dtype in _FP8_TYPES:
+        raise TypeError(f"{fn} does not take float8 caches or k_scale / v_scale: {other} takes them")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError(f"{fn} takes float16 or bfloat16 tensors, got {q.dtype}: {other} takes float32")
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache), ("k_new", k_new), ("v_new", v_new)):
+        if t is not None and t.dtype != q.dtype:
+            raise TypeError(f"{name} must have q's dtype ({q.dtype}), got {t.dtype}")
+    if q.dim() == 3 and q.shape[-1] not in (64, 128):
+        raise ValueError(f"{fn} takes head dimensions 64 and 128, got {q.shape[-1]}: {other} takes the others")
+    if window != (-1, -1):
+        raise ValueError(f"{fn} takes no sliding window (window_size {tuple(window_size)}): {other} takes one")
+    c, cpu_result, cu_q, max_q = _ragged_step(fn, q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q,
+                                              max_seqlen_k, None, None, window,
+                                              dict(scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, return_lse=bool(return_lse)))
+    if q.device.type == "cpu":
+        return cpu_result
+    total_q, H = q.shape[:2]
+    if total_q == 0:      # nothing to append, nothing to write: no launch
+        o = q.new_empty(q.shape)
+        return (o, q.new_empty((0, H), dtype=torch.float32)) if return_lse else o
+    k_cache, v_cache, cache_seqlens, block_table = c.on_device()
+    _torch_ops.load()
+    o, lse = torch.ops.fcsa_prefill.kvcache_prefill_forward(q, k_cache, v_cache, cu_q, k_new, v_new, cache_seqlens, block_table, max_q, c.max_k,
+                                                            float(scale), bool(causal), bool(l2norm_qk), int(groups))
+    return (o, lse) if return_lse else o
 
 
 # ---------------------------------------------------------------------------------------------

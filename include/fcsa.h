@@ -322,7 +322,7 @@ size_t fcsa_forward_kvcache_quant_workspace_bytes(const fcsa_problem* p, const f
  *   workspace: >= fcsa_forward_kvcache_varlen_workspace_bytes() bytes, 256-byte aligned: the split partials over total_q * H rows
  * The tables are device data, never read by the host and clamped on the device: a malformed table gives wrong rows, never an access
  * outside the tensors.  Each row tile re-reads and re-normalises its keys, so this is the call for steps of one to a few dozen tokens per
- * sequence; long prompt chunks work, at the decode kernel's efficiency.
+ * sequence; long prompt chunks work, at the decode kernel's efficiency -- fcsa_forward_kvcache_prefill is the call for those.
  * Launches: "kv_append_ragged" (when appending), "decode_ragged" and "decode_combine_ragged"; with quant each name ends in "_fp8". */
 int    fcsa_forward_kvcache_varlen(const fcsa_forward_args* args, const fcsa_kvcache* cache, const fcsa_varlen* seqs,
                                    const fcsa_kvcache_quant* quant, const fcsa_window* window);
@@ -357,6 +357,23 @@ typedef struct fcsa_lse_out {
 } fcsa_lse_out;
 int    fcsa_forward_kvcache_lse(const fcsa_forward_args* args, const fcsa_kvcache* cache, const fcsa_varlen* seqs,
                                 const fcsa_kvcache_quant* quant, const fcsa_window* window, const fcsa_lse_out* lse_out);
+
+/* Prompt chunks against the cache: fcsa_forward_kvcache_varlen (no quant, no window) on a kernel built for MANY rows per sequence.  A
+ * workgroup of four waves owns 128 token-major rows (r = token * G + head of the group) of one sequence's K/V head; the keys go through LDS
+ * in 64-key stages and every key is read and l2-normalised once per workgroup, not once per 16 rows; under `causal` a workgroup stops at the
+ * last key its last token sees.  args, cache and seqs are read exactly as fcsa_forward_kvcache_varlen reads them and its checks apply;
+ * args->workspace is ignored (there are no key splits and no partials: one kernel writes o).  lse_out: NULL, or where the rows'
+ * log-sum-exp goes, as in fcsa_forward_kvcache_lse for a ragged call.
+ * o, lse and the caches after the append are bit for bit those of fcsa_forward_kvcache_varlen / _lse wherever that call runs one key split
+ * (the per-row arithmetic, its order and the combine are the decode kernel's).
+ * Supported: FCSA_F16 / FCSA_BF16 (q, the caches and the new rows), dim_head 64 or 128, every `groups` dividing dim_head, every kv_heads
+ * dividing heads, both exponent regimes.  FCSA_F32 and other head dims: FCSA_ERR_UNSUPPORTED (fp8 caches and windows have no argument
+ * here: fcsa_forward_kvcache_varlen takes them).
+ * The grid has floor(G * total_q / 128) + batch workgroups per K/V head and no key splits, so this is the call for chunks long enough to
+ * fill the chip with 128-row tiles; steps of a few tokens per sequence belong to fcsa_forward_kvcache_varlen.
+ * Launches: "kv_append_ragged" (when appending; the ragged call's launch, unchanged) and "prefill". */
+int    fcsa_forward_kvcache_prefill(const fcsa_forward_args* args, const fcsa_kvcache* cache, const fcsa_varlen* seqs,
+                                    const fcsa_lse_out* lse_out);
 
 /* Merging attention states: `states` pairs (o_s, lse_s) over disjoint key sets of the same queries -> the pair over the union.
  * Per row, in float32:  M = max_s lse_s;  M == -inf: o = 0, lse = -inf;  else w_s = exp(lse_s - M), W = sum_s w_s,
