@@ -6,6 +6,7 @@
 //                         from the cache into registers (one 16-byte load per lane and fragment), are l2-normalised there, and
 //                         S^T = K^ Q^T runs on mfma_f32_16x16x32 (float32: 16x16x4) with the query row on the lane.  V goes through a
 //                         wave-private LDS block for the transposed reads of O^T = V^T P~^T.  Partials (P~V, row max, row sum) in f32.
+//                         The softmax step, the P~V product and the combine weight are functions of fcsa_decode_common.cuh (prefill too).
 //   decode_combine_kernel reconciles the splits of every row (a per-split row max in the per-row-shift regime, a common shift
 //                         otherwise) and normalises.
 //   decode_combine_lse*   the same combine, also writing the rows' log-sum-exp (fcsa_forward_kvcache_lse): one body (decode_combine_body)
@@ -34,7 +35,7 @@ namespace {
 // LDS plan of the decode kernel, for the kernel and its launcher: one 32-key V block, rows of D elements padded by 16 bytes; the form for
 // group widths that straddle a lane's fragment (GEN) adds a float32 scratch of 16 rows x D squares and 16 rows x D group sums behind it
 template <int D, int ES, bool GEN> struct DecodeLds {
-  static constexpr int PITCH = D * ES + 16;
+  static constexpr int PITCH = kKvPitch<D, ES>;
   static constexpr int VBYTES = kDecodeBlock * PITCH;
   static constexpr int NORM = GEN ? 2 * kDecodeRows * D * 4 : 0;
   static constexpr int BYTES = VBYTES + NORM;
@@ -82,7 +83,6 @@ template <int NJ, int UE, int D> FCSA_DEV void group_normalise_lds(float (&x)[NJ
   __syncthreads();      // the next row set rewrites the scratch
 }
 
-
 // FP8: the cache holds one-byte codes -- a K fragment is 8 bytes, a 16-byte V chunk 16 features (at D = 16 half the lanes have none)
 template <typename T, int D, bool FP8 = false> struct DecodeRegs {
   static constexpr int ES = Traits<T>::ES;
@@ -96,23 +96,21 @@ template <typename T, int D, bool FP8 = false> struct DecodeRegs {
   KFrag k[2][NJ];
   u32x4 v[VCH];
 
-  // the 32-key block from `kb`; positions at or beyond `end` read position end - 1 (in bounds) and their V chunks are zeroed
+  // the 32-key block from `kb`, each 16-key half under the load rule (clamped_first, clamped_off)
   FCSA_DEV void load(const DecodeParams& p, int b, int kvh, int kb, int end, int lane) {
     const int x = lane & 15, hi = lane >> 4;
-    const int last16 = (end - 1) & ~15;
     const char* kbase[2];
     const char* vbase[2];
     int first[2];
 #pragma unroll
     for (int sb = 0; sb < 2; ++sb) {
-      first[sb] = min(kb + 16 * sb, last16);
+      first[sb] = clamped_first(kb + 16 * sb, end);
       kbase[sb] = cache_base(p, p.kc, b, kvh, first[sb]);
       vbase[sb] = cache_base(p, p.vc, b, kvh, first[sb]);
     }
 #pragma unroll
     for (int sb = 0; sb < 2; ++sb) {
-      const int pos = min(kb + 16 * sb + x, end - 1);
-      const char* row = kbase[sb] + (int64_t)(pos - first[sb]) * p.kc.sn;
+      const char* row = kbase[sb] + (int64_t)clamped_off(kb + 16 * sb + x, first[sb], end) * p.kc.sn;
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
         const int f = (4 * j + hi) * UE;
@@ -125,9 +123,8 @@ template <typename T, int D, bool FP8 = false> struct DecodeRegs {
       if constexpr (VTOT % 64 != 0) {
         if (c >= VTOT) { v[t] = u32x4{0u, 0u, 0u, 0u}; continue; }
       }
-      const int pos = min(kb + kk, end - 1);
-      const char* src = (sb ? vbase[1] : vbase[0]) + (int64_t)(pos - (sb ? first[1] : first[0])) * p.vc.sn + ch * 16;
-      const u32x4 val = *reinterpret_cast<const u32x4*>(src);
+      const int off = clamped_off(kb + kk, sb ? first[1] : first[0], end);
+      const u32x4 val = *reinterpret_cast<const u32x4*>((sb ? vbase[1] : vbase[0]) + (int64_t)off * p.vc.sn + ch * 16);
       v[t] = kb + kk < end ? val : u32x4{0u, 0u, 0u, 0u};
     }
   }
@@ -267,27 +264,8 @@ FCSA_DEV void decode_body(const std::conditional_t<RAGGED, DecodeRaggedParams,
         s[sb][rr] = vis ? s[sb][rr] * smul : -INFINITY;
       }
     }
-    float shift = p.c2;
-    if constexpr (DYN) {
-      float bm = fmaxf(fmaxf(fmaxf(s[0][0], s[0][1]), fmaxf(s[0][2], s[0][3])), fmaxf(fmaxf(s[1][0], s[1][1]), fmaxf(s[1][2], s[1][3])));
-      bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
-      bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
-      const float mn = fmaxf(m, bm);
-      shift = mn == -INFINITY ? 0.f : mn;
-      const float alpha = fast_exp2(m - shift);      // 0 while the row has seen no key
-#pragma unroll
-      for (int fb = 0; fb < FB; ++fb) acc[fb] *= alpha;
-      l *= alpha;
-      m = mn;
-    }
     f32x4 pr[2];
-#pragma unroll
-    for (int sb = 0; sb < 2; ++sb)
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        pr[sb][rr] = fast_exp2(s[sb][rr] - shift);
-        l += pr[sb][rr];
-      }
+    softmax_step<DYN>(s, m, l, acc, p.c2, pr);
 
     // V block -> LDS (row-major, padded rows), then O^T += V^T P~^T
 #pragma unroll
@@ -318,16 +296,7 @@ FCSA_DEV void decode_body(const std::conditional_t<RAGGED, DecodeRaggedParams,
       pb[1] = Traits<T>::pack2(pr[0][2], pr[0][3]);
       pb[2] = Traits<T>::pack2(pr[1][0], pr[1][1]);
       pb[3] = Traits<T>::pack2(pr[1][2], pr[1][3]);
-      typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-      // lane 4q + p of the 16-lane group hi addresses key 4 hi + q, features 16 fb + 4p ... + 3; lane x receives feature 16 fb + x
-      const char* a0 = smem + (4 * hi + (x >> 2)) * LP::PITCH + 8 * (x & 3);
-#pragma unroll
-      for (int fb = 0; fb < FB; ++fb) {
-        const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0 + 32 * fb));
-        const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0 + 16 * LP::PITCH + 32 * fb));
-        const u32x2 u0 = __builtin_bit_cast(u32x2, v0), u1 = __builtin_bit_cast(u32x2, v1);
-        acc[fb] = Unit<T>::mfma(u32x4{u0[0], u0[1], u1[0], u1[1]}, pb, acc[fb]);
-      }
+      pv_block<T, D, 1>(smem, 0, x, hi, &pb, &acc);
     } else {
 #pragma unroll
       for (int fb = 0; fb < FB; ++fb)
@@ -414,12 +383,12 @@ FCSA_DEV void decode_combine_body(const P& p, const DecodeLseOut& lo) {
   if (M != -INFINITY) {
     for (int s = 0; s < p.splits; ++s) {
       const f32x2 ml = *reinterpret_cast<const f32x2*>(p.ws_ml + (s * rows + row) * 2);
-      const float w = exp2f(ml[0] - M);
+      const float w = combine_weight(ml[0], M);
       l += w * ml[1];
       acc += w * *reinterpret_cast<const f32x4*>(p.ws_o + (s * rows + row) * D + 4 * c);
     }
   }
-  const float inv = p.dyn ? (l > 0.f ? 1.f / l : 0.f) : 1.f / fmaxf(l, p.l_eps);
+  const float inv = combine_inv(p.dyn != 0, l, p.l_eps);
   int h;
   char* dst;
   if constexpr (RAGGED) {

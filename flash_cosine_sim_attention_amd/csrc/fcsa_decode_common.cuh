@@ -1,7 +1,8 @@
-// fcsa_decode_common.cuh -- the device helpers that the kernels reading a key/value cache share: the lane's fragment of a row (Unit),
-// its unpack / pack, the grouped l2norm across the four lanes of a row (group_normalise) and the address of a cache position
-// (cache_base).  Included by fcsa_decode.hip (the single-wave decode kernels) and fcsa_prefill.hip (the multi-wave prefill kernel), which
-// must normalise and round a key to the same bits.  Each translation unit gets its own internal copies (anonymous namespace).
+// fcsa_decode_common.cuh -- the device code shared by fcsa_decode.hip (the single-wave decode kernels) and fcsa_prefill.hip (the multi-wave
+// prefill kernel), whose results must agree bit for bit: what is here is written once and both call it (DESIGN.md 4.7.4 lists what is
+// still written in both).  A row in registers: Unit, unpack / pack, group_normalise.  Reading the cache: cache_base, clamped_first / clamped_off,
+// kKvPitch.  A 32-key block step: softmax_step, pv_block.  The end of a row: combine_weight, combine_inv.
+// Each translation unit gets its own internal copies (anonymous namespace).
 #pragma once
 #include "fcsa_common.cuh"
 
@@ -131,6 +132,65 @@ FCSA_DEV const char* cache_base(const DecodeParams& p, const View& v, int b, int
   }
   return v.p + (int64_t)b * v.sb + (int64_t)kvh * v.sh + (int64_t)first * v.sn;
 }
+
+// The load rule: a position at or beyond `end` reads position end - 1 (in bounds) and its V is zeroed.  clamped_first: what to hand cache_base
+// for the 16 positions from first16 (one lookup per 16 positions).  clamped_off: the distance of position `pos` of those 16 from it.
+FCSA_DEV int clamped_first(int first16, int end) { return min(first16, (end - 1) & ~15); }
+FCSA_DEV int clamped_off(int pos, int first, int end) { return min(pos, end - 1) - first; }
+
+// Bytes between two rows of a K^ / V block in LDS: D elements padded by 16 bytes.  The transposed V reads (pv_block) address a 32-key
+// block at this pitch, in the decode kernel's LDS (DecodeLds) and in the prefill kernel's (PrefillLds) alike.
+template <int D, int ES> constexpr int kKvPitch = D * ES + 16;
+
+// The softmax step of one 32-key block for one row: s = the lane's masked logits (log2 units), m / l / acc = the row's running shift, row
+// sum (this lane's share) and O^T.  DYN: the row maximum over the row's four lanes joins m, and acc and l are rescaled to it; otherwise the
+// shift is the constant c2.  pr = P~ = 2^(s - shift).
+template <bool DYN, int FB> FCSA_DEV void softmax_step(const f32x4 (&s)[2], float& m, float& l, f32x4 (&acc)[FB], float c2, f32x4 (&pr)[2]) {
+  float shift = c2;
+  if constexpr (DYN) {
+    float bm = fmaxf(fmaxf(fmaxf(s[0][0], s[0][1]), fmaxf(s[0][2], s[0][3])), fmaxf(fmaxf(s[1][0], s[1][1]), fmaxf(s[1][2], s[1][3])));
+    bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
+    bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
+    const float mn = fmaxf(m, bm);
+    shift = mn == -INFINITY ? 0.f : mn;
+    const float alpha = fast_exp2(m - shift);      // 0 while the row has seen no key
+#pragma unroll
+    for (int fb = 0; fb < FB; ++fb) acc[fb] *= alpha;
+    l *= alpha;
+    m = mn;
+  }
+#pragma unroll
+  for (int sb = 0; sb < 2; ++sb)
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      pr[sb][rr] = fast_exp2(s[sb][rr] - shift);
+      l += pr[sb][rr];
+    }
+}
+
+// O^T += V^T P~^T for the 32-key block of 16-bit V at rows row0 ... row0 + 31 of `v` in LDS (pitch kKvPitch<D, 2>): lane 4q + p of the
+// 16-lane group hi (x = lane & 15 = 4q + p) addresses key 4 hi + q, features 16 fb + 4p ... + 3; lane x receives feature 16 fb + x.  Every
+// transposed read feeds the NT row tiles pb[0 .. NT) -> acc[0 .. NT).
+template <typename T, int D, int NT> FCSA_DEV void pv_block(const char* v, int row0, int x, int hi, const u32x4* pb, f32x4 (*acc)[D / 16]) {
+  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+  constexpr int PITCH = kKvPitch<D, 2>;
+  const char* a0 = v + (row0 + 4 * hi + (x >> 2)) * PITCH + 8 * (x & 3);
+#pragma unroll
+  for (int fb = 0; fb < D / 16; ++fb) {
+    const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0 + 32 * fb));
+    const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0 + 16 * PITCH + 32 * fb));
+    const u32x2 u0 = __builtin_bit_cast(u32x2, v0), u1 = __builtin_bit_cast(u32x2, v1);
+    const u32x4 vf = u32x4{u0[0], u0[1], u1[0], u1[1]};
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t][fb] = Unit<T>::mfma(vf, pb[t], acc[t][fb]);
+  }
+}
+
+// The combine of a row: a split's partials (row shift m_s, row sum l_s, P~V) join l and acc with the weight 2^(m_s - M), M = the largest m_s
+// of the row (static regime: every m_s is the common shift, weight 1); the normaliser is 1 / l (0 for a row that saw no key) in the
+// per-row-shift regime, 1 / max(l, l_eps) otherwise
+FCSA_DEV float combine_weight(float m_s, float M) { return exp2f(m_s - M); }
+FCSA_DEV float combine_inv(bool dyn, float l, float l_eps) { return dyn ? (l > 0.f ? 1.f / l : 0.f) : 1.f / fmaxf(l, l_eps); }
 
 }  // namespace
 }  // namespace fcsa

@@ -6,10 +6,10 @@
 //                    in the decode kernel's register layout (key on lane & 15, feature quarter on lane >> 4), l2-normalises them with the
 //                    decode kernel's group_normalise, rounds them to the type and writes K^ -- once per workgroup, not once per 16 rows --
 //                    and V raw.  The next stage's global loads are in flight during the current stage's math.
-//                    Per wave, 32-key block and row tile the math is decode_body's, statement for statement (S^T = K^ Q^T on
-//                    mfma_f32_16x16x32 with the query row on the lane, the same mask and exponent regime, ds_read_tr16_b64 for V^T P~^T), and
-//                    the epilogue is decode_combine_body's arithmetic at one split, so o and lse are bit for bit those of the ragged call
-//                    with one key split.  Every K^ fragment and transposed V read from LDS feeds both row tiles of the wave.
+//                    Per wave, 32-key block and row tile the math is decode_body's (S^T = K^ Q^T on mfma_f32_16x16x32 with the query row on
+//                    the lane, its mask and P~ pack, and the same functions of fcsa_decode_common.cuh: softmax_step, pv_block), and the
+//                    epilogue is decode_combine_body's (combine_weight, combine_inv) at one split, so o and lse are bit for bit those of
+//                    the ragged call with one key split.  Every K^ fragment and transposed V read from LDS feeds both row tiles of the wave.
 // The append before it is the ragged call's (launch_kv_append with the same parameter block).  16-bit types, D = 64 / 128 only.
 #include "fcsa_common.cuh"
 #include "fcsa_decode_common.cuh"
@@ -24,10 +24,9 @@ namespace {
 constexpr int kPrefillWaves = 4;
 constexpr int kPrefillTiles = kPrefillRows / kDecodeRows / kPrefillWaves;     // 16-row MFMA tiles per wave
 
-// LDS plan, for the kernel and its launcher: two stage buffers, each K^ [64][PITCH] then V [64][PITCH]; rows of D elements padded by 16
-// bytes (the decode kernel's V pitch: the transposed reads address a 32-key block exactly as they do there)
+// LDS plan, for the kernel and its launcher: two stage buffers, each K^ [64][PITCH] then V [64][PITCH] at the pitch pv_block reads
 template <int D> struct PrefillLds {
-  static constexpr int PITCH = D * 2 + 16;
+  static constexpr int PITCH = kKvPitch<D, 2>;
   static constexpr int TILE = kPrefillStage * PITCH;
   static constexpr int BUF = 2 * TILE;
   static constexpr int BYTES = 2 * BUF;
@@ -38,13 +37,13 @@ template <typename T, int D> struct PrefillRegs {
   static constexpr int NJ = D / 32;
   u32x4 k[NJ], v[NJ];
 
-  // positions at or beyond L read position L - 1 (in bounds) and their V is zeroed: DecodeRegs::load's rule
+  // the 16 positions from first16 of a sequence of L, under the load rule (clamped_first, clamped_off)
   FCSA_DEV void load(const DecodeParams& p, int b, int kvh, int first16, int L, int lane) {
     const int x = lane & 15, hi = lane >> 4;
-    const int first = min(first16, (L - 1) & ~15);
-    const int pos = min(first16 + x, L - 1);
-    const char* krow = cache_base(p, p.kc, b, kvh, first) + (int64_t)(pos - first) * p.kc.sn;
-    const char* vrow = cache_base(p, p.vc, b, kvh, first) + (int64_t)(pos - first) * p.vc.sn;
+    const int first = clamped_first(first16, L);
+    const int off = clamped_off(first16 + x, first, L);
+    const char* krow = cache_base(p, p.kc, b, kvh, first) + (int64_t)off * p.kc.sn;
+    const char* vrow = cache_base(p, p.vc, b, kvh, first) + (int64_t)off * p.vc.sn;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       const int f = (4 * j + hi) * 8;
@@ -167,53 +166,22 @@ __global__ __launch_bounds__(64 * kPrefillWaves, (kPrefillWavesPerSimd<T, D>)) v
             const bool vis = key < L && (!p.causal || key <= last_key[t]);
             s[t][sb][rr] = vis ? s[t][sb][rr] * smul : -INFINITY;
           }
-        float shift = p.c2;
-        if constexpr (DYN) {
-          float bm = fmaxf(fmaxf(fmaxf(s[t][0][0], s[t][0][1]), fmaxf(s[t][0][2], s[t][0][3])),
-                           fmaxf(fmaxf(s[t][1][0], s[t][1][1]), fmaxf(s[t][1][2], s[t][1][3])));
-          bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
-          bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
-          const float mn = fmaxf(m[t], bm);
-          shift = mn == -INFINITY ? 0.f : mn;
-          const float alpha = fast_exp2(m[t] - shift);      // 0 while the row has seen no key
-#pragma unroll
-          for (int fb = 0; fb < FB; ++fb) acc[t][fb] *= alpha;
-          l[t] *= alpha;
-          m[t] = mn;
-        }
         f32x4 pr[2];
-#pragma unroll
-        for (int sb = 0; sb < 2; ++sb)
-#pragma unroll
-          for (int rr = 0; rr < 4; ++rr) {
-            pr[sb][rr] = fast_exp2(s[t][sb][rr] - shift);
-            l[t] += pr[sb][rr];
-          }
+        softmax_step<DYN>(s[t], m[t], l[t], acc[t], p.c2, pr);
         // k-slot (hi, e) of the P~V product is key 16 (e >> 2) + 4 hi + (e & 3): P~ is used where the first product left it
         pb[t][0] = Traits<T>::pack2(pr[0][0], pr[0][1]);
         pb[t][1] = Traits<T>::pack2(pr[0][2], pr[0][3]);
         pb[t][2] = Traits<T>::pack2(pr[1][0], pr[1][1]);
         pb[t][3] = Traits<T>::pack2(pr[1][2], pr[1][3]);
       }
-      // O^T += V^T P~^T: lane 4q + p of the 16-lane group hi addresses key 4 hi + q, features 16 fb + 4p ... + 3; lane x receives feature 16 fb + x
-      typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-      const char* a0 = vs + (blk * kDecodeBlock + 4 * hi + (x >> 2)) * LP::PITCH + 8 * (x & 3);
-#pragma unroll
-      for (int fb = 0; fb < FB; ++fb) {
-        const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0 + 32 * fb));
-        const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0 + 16 * LP::PITCH + 32 * fb));
-        const u32x2 u0 = __builtin_bit_cast(u32x2, v0), u1 = __builtin_bit_cast(u32x2, v1);
-        const u32x4 vf = u32x4{u0[0], u0[1], u1[0], u1[1]};
-#pragma unroll
-        for (int t = 0; t < NT; ++t) acc[t][fb] = Unit<T>::mfma(vf, pb[t], acc[t][fb]);
-      }
+      pv_block<T, D, NT>(vs, blk * kDecodeBlock, x, hi, pb, acc);
     }
     // the other buffer was last read before the barrier that ended the previous iteration
     if (more) regs.store(smem + ((st + 1) & 1) * LP::BUF, my_row, lane, p.l2norm != 0, gs);
     __syncthreads();
   }
 
-  // Row x of tile t: O^T[16 fb + 4 hi + rr][x] in acc[t][fb][rr].  The combine of one split (decode_combine_body): weight exp2(m - M) = 1.
+  // Row x of tile t: O^T[16 fb + 4 hi + rr][x] in acc[t][fb][rr].  The combine of its one split (decode_combine_body's functions), in registers.
   // The row's head and token are worked out again here (from an opaque lane id), so that no address lives through the key loop.
   const int xe = opaque(lane) & 15, hie = opaque(lane) >> 4;
 #pragma unroll
@@ -227,10 +195,10 @@ __global__ __launch_bounds__(64 * kPrefillWaves, (kPrefillWavesPerSimd<T, D>)) v
     const int64_t tok = q0 + r / p.G;
     const float M = m[t];
     const bool any = M != -INFINITY;
-    const float w = exp2f(M - M);
+    const float w = combine_weight(M, M);      // the one split's weight: 1
     float lsum = 0.f;
     if (any) lsum += w * ls;
-    const float inv = p.dyn ? (lsum > 0.f ? 1.f / lsum : 0.f) : 1.f / fmaxf(lsum, p.l_eps);
+    const float inv = combine_inv(p.dyn != 0, lsum, p.l_eps);
     char* dst = p.o.p + (int64_t)h * p.o.sh + tok * p.o.sn + 4 * hie * 2;
 #pragma unroll
     for (int fb = 0; fb < FB; ++fb) {
