@@ -5,6 +5,7 @@ from .ops import (flash_cosine_sim_attention, flash_cosine_sim_attention_local, 
                   flash_cosine_sim_attention_with_kvcache, flash_cosine_sim_attention_varlen_with_kvcache,
                   flash_cosine_sim_attention_prefill_with_kvcache,
                   flash_cosine_sim_attention_with_shared_prefix, merge_attention_states,
+                  flash_cosine_sim_attention_with_lse, merge_attention_states_with_grad,
                   plain_cosine_sim_attention, l2norm_tensors, FlashCosineSimAttention)
 from .ext import debug
 
@@ -13,4 +14,5 @@ __all__ = ['flash_cosine_sim_attention', 'flash_cosine_sim_attention_local', 'fl
            'flash_cosine_sim_attention_with_kvcache', 'flash_cosine_sim_attention_varlen_with_kvcache',
            'flash_cosine_sim_attention_prefill_with_kvcache',
            'flash_cosine_sim_attention_with_shared_prefix', 'merge_attention_states',
+           'flash_cosine_sim_attention_with_lse', 'merge_attention_states_with_grad',
            'plain_cosine_sim_attention', 'l2norm_tensors', 'debug', 'FlashCosineSimAttention']

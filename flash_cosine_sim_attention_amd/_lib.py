@@ -87,6 +87,7 @@ FCSA_CACHE_E4M3 = _MACROS["FCSA_CACHE_E4M3"]
 LseOut = _STRUCTS["fcsa_lse_out"]
 MergeArgs = _STRUCTS["fcsa_merge_args"]
 MERGE_MAX_STATES = _MACROS["FCSA_MERGE_MAX_STATES"]
+MergeBackwardArgs = _STRUCTS["fcsa_merge_backward_args"]
 
 
 EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fcsa_forward_workspace_bytes", "fcsa_forward_needs_qn",
@@ -95,7 +96,8 @@ EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fc
            "fcsa_forward_kvcache_workspace_bytes", "fcsa_forward_window", "fcsa_backward_window", "fcsa_backward_window_workspace_bytes",
            "fcsa_forward_kvcache_window", "fcsa_forward_kvcache_window_workspace_bytes", "fcsa_forward_kvcache_quant",
            "fcsa_forward_kvcache_quant_workspace_bytes", "fcsa_forward_kvcache_varlen", "fcsa_forward_kvcache_varlen_workspace_bytes",
-           "fcsa_forward_kvcache_lse", "fcsa_merge_states", "fcsa_forward_kvcache_prefill")
+           "fcsa_forward_kvcache_lse", "fcsa_merge_states", "fcsa_forward_kvcache_prefill",
+           "fcsa_attention_lse", "fcsa_backward_state", "fcsa_merge_states_backward")
 
 _lib = None
 
@@ -190,6 +192,13 @@ def load():
     if hasattr(lib, "fcsa_forward_kvcache_prefill"):      # (likewise: an FCSA_LIB build from before the prefill kernel)
         lib.fcsa_forward_kvcache_prefill.argtypes = [C.POINTER(ForwardArgs), C.POINTER(KvCache), C.POINTER(Varlen), C.POINTER(LseOut)]
         lib.fcsa_forward_kvcache_prefill.restype = C.c_int
+    if hasattr(lib, "fcsa_attention_lse"):      # (likewise: an FCSA_LIB build from before the attention states for training)
+        lib.fcsa_attention_lse.argtypes = [C.POINTER(Problem), C.c_void_p, C.POINTER(Varlen), C.POINTER(Window), C.POINTER(LseOut), C.c_void_p]
+        lib.fcsa_attention_lse.restype = C.c_int
+        lib.fcsa_backward_state.argtypes = [C.POINTER(BackwardArgs), C.POINTER(Varlen), C.POINTER(Window), C.c_void_p]
+        lib.fcsa_backward_state.restype = C.c_int
+        lib.fcsa_merge_states_backward.argtypes = [C.POINTER(MergeBackwardArgs)]
+        lib.fcsa_merge_states_backward.restype = C.c_int
     lib.fcsa_last_error.argtypes = []
     lib.fcsa_last_error.restype = C.c_char_p
     ver = lib.fcsa_debug(None, 0)

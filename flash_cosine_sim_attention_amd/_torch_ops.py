@@ -108,6 +108,34 @@ def _register_fakes():
     def _(os, lses):
         return os[0].new_empty(os[0].shape), os[0].new_empty(os[0].shape[:-1], dtype=torch.float32)
 
+    # attention states for training (namespace fcsa_state): lse float32 [B, H, N], packed [total_q, H]; the saved state always
+    def _state_rows(q, k):
+        packed = q.dim() == 3
+        return ((q.shape[1], q.shape[0]), (k.shape[1], k.shape[0])) if packed else (tuple(q.shape[:3]), tuple(k.shape[:3]))
+
+    @torch.library.register_fake("fcsa_state::attention_state_forward")
+    def _(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, scale, causal, l2norm_qk, groups, window_left, window_right):
+        rows_q, rows_k = _state_rows(q, k)
+        return (q.new_empty(q.shape), q.new_empty(q.shape[:-1], dtype=torch.float32),
+                *_saved_state(q, rows_q, rows_k, q.shape[-1], l2norm_qk, groups, True))
+
+    @torch.library.register_fake("fcsa_state::attention_state")
+    def _(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, scale, causal, l2norm_qk, groups, window_left, window_right):
+        return q.new_empty(q.shape), q.new_empty(q.shape[:-1], dtype=torch.float32)
+
+    @torch.library.register_fake("fcsa_state::attention_state_backward")
+    def _(d_out, d_lse, o, inv_l, q, k, v, cu_seqlens_q, cu_seqlens_k, qn, kn, rq, rk, max_seqlen_q, max_seqlen_k, scale, causal, l2norm_qk,
+          groups, window_left, window_right):
+        return q.new_empty(q.shape), k.new_empty(k.shape), v.new_empty(v.shape)
+
+    @torch.library.register_fake("fcsa_state::merge_state")
+    def _(os, lses):
+        return os[0].new_empty(os[0].shape), os[0].new_empty(os[0].shape[:-1], dtype=torch.float32)
+
+    @torch.library.register_fake("fcsa_state::merge_state_backward")
+    def _(d_o, d_lse, os, lses):
+        return ([o.new_empty(o.shape) for o in os], [o.new_empty(o.shape[:-1], dtype=torch.float32) for o in os])
+
     @torch.library.register_fake("fcsa::backward")
     def _(d_out, o, inv_l, q, k, v, mask, attn_bias, qn, kn, rq, rk, attn_bias_batch_dim, scale, causal, l2norm_qk, groups,
           need_bias_grad):

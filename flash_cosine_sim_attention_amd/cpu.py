@@ -177,6 +177,28 @@ def attention_forward_varlen_cpu(q, k, v, cu_seqlens_q, cu_seqlens_k, scale=8.0,
     return out
 
 
+def attention_state_cpu(q, k, v, cu_seqlens_q=None, cu_seqlens_k=None, scale=8.0, groups=1, causal=False, l2norm_qk=True,
+                        window_size=(-1, -1)):
+    """Forward-only path of `flash_cosine_sim_attention_with_lse` on host tensors: (o, lse) of the dense / local call (4-D q, k, v; lse
+    float32 [B, H, N]) or, with validated host tables, of the packed call (lse [total_q, H]), each sequence as a batch-1 problem.  o is
+    what `attention_forward_cpu` / `attention_forward_varlen_cpu` give; lse = -inf for a row without a visible key."""
+    kw = dict(scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, window_size=window_size, return_lse=True)
+    if cu_seqlens_q is None:
+        return attention_forward_cpu(q.detach(), k.detach(), v.detach(), **kw)
+    out = torch.zeros_like(q)
+    lse = torch.full(q.shape[:-1], float("-inf"), dtype=torch.float32)
+    cq, ck = cu_seqlens_q.tolist(), cu_seqlens_k.tolist()
+    for s in range(len(cq) - 1):
+        if cq[s + 1] == cq[s]:
+            continue
+        qs, ks, vs = (t.detach()[lo:hi].permute(1, 0, 2).unsqueeze(0) for t, lo, hi in ((q, cq[s], cq[s + 1]), (k, ck[s], ck[s + 1]),
+                                                                                       (v, ck[s], ck[s + 1])))
+        o, l = attention_forward_cpu(qs, ks, vs, **kw)
+        out[cq[s]:cq[s + 1]] = o[0].permute(1, 0, 2)
+        lse[cq[s]:cq[s + 1]] = l[0].permute(1, 0)
+    return out, lse
+
+
 def cache_gather(cache, b, length, block_table=None):
     """Positions [0, length) of sequence b of a key or value cache: [1, Hk, length, D].  Contiguous caches are [B, Hk, capacity, D]; paged
     ones [num_blocks, Hk, page_size, D] with block_table[b, i] holding positions [i * page_size, (i + 1) * page_size)."""
@@ -280,7 +302,9 @@ def merge_attention_states_cpu(os, lses):
     """`merge_attention_states` on host tensors, in float32: M = max_s lse_s; every state empty (M == -inf): o = 0, lse = -inf; else
     w_s = exp(lse_s - M), W = sum_s w_s, o = (sum_s w_s * o_s) / W rounded once, lse = M + log(W).  A state of weight 0 is skipped, as in
     the kernel: its o_s cannot leak (NaN included), and the first live product of a row is assigned rather than added to +0, so one state
-    beside empty ones comes back bit for bit, -0 included."""
+    beside empty ones comes back bit for bit, -0 included.  Made of torch ops that autograd differentiates
+    (`merge_attention_states_with_grad`): a skipped state's o_s is replaced by 0 BEFORE the product, so its NaNs reach neither the result
+    nor a gradient."""
     lse = torch.stack([l.float() for l in lses])                       # [S, ...]
     top = lse.amax(dim=0)
     live = top > float("-inf")
@@ -292,7 +316,7 @@ def merge_attention_states_cpu(os, lses):
     started = torch.zeros(top.shape, dtype=torch.bool).unsqueeze(-1)
     for s, o in enumerate(os):
         alive = (w[s] != 0).unsqueeze(-1)
-        term = w[s].unsqueeze(-1) * o.float()
+        term = w[s].unsqueeze(-1) * torch.where(alive, o.float(), zero)
         acc = torch.where(alive, torch.where(started, acc + term, term), acc)
         started = started | alive
     total = torch.where(live, total, torch.ones_like(total))

@@ -435,6 +435,11 @@ FCSA_DEV void bwd_dq_body(const std::conditional_t<WIN, BwdWinParams, BwdParams>
     rinvl = i < p.N ? p.inv_l[((int64_t)b * p.H + h) * p.N + i] : 1.f;
   }
   delta = xhalf_sum(delta);
+  // a gradient of the row's log-sum-exp (fcsa_backward_state): d lse_i / d s_ij = P_ij, so dS = P (dP - (delta - dlse)).  In every key
+  // split, before the publish: the dK/dV kernels read the same value.  A workgroup-uniform pointer test; the load sits HERE in both
+  // forms, not with rinvl in request_ahead: carried across the previous epilogue it cost every SEP instantiation a register (1 - 6
+  // VGPRs measured) whether or not a call brings a dlse.  Here it is live for three instructions, before the dQ accumulators exist.
+  if (p.dlse != nullptr && i < p.N) delta -= p.dlse[((int64_t)b * p.H + h) * p.N + i];
   if (i < p.N) {
     const int64_t ridx = ((int64_t)b * p.H + h) * p.N + i;
     lc = (p.invl_log2 ? rinvl : __builtin_amdgcn_logf(rinvl)) - p.c2;     // v_log_f32 = log2

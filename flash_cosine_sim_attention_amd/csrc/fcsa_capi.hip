@@ -279,7 +279,7 @@ int check_window(const fcsa_window* w, bool mask, bool bias) {
 }
 
 int forward_impl(const fcsa_forward_args* a, const VarlenCall* vl, const WindowCall* win = nullptr);
-int backward_impl(const fcsa_backward_args* a, const VarlenCall* vl, const WindowCall* win = nullptr);
+int backward_impl(const fcsa_backward_args* a, const VarlenCall* vl, const WindowCall* win = nullptr, const float* dlse = nullptr);
 
 }  // namespace
 
@@ -892,7 +892,7 @@ size_t fcsa_backward_varlen_workspace_bytes(const fcsa_problem* p, const fcsa_va
 
 int fcsa_backward(const fcsa_backward_args* a) { return backward_impl(a, nullptr); }
 
-static int backward_varlen(const fcsa_backward_args* a, const fcsa_varlen* seqs, const WindowCall* win);
+static int backward_varlen(const fcsa_backward_args* a, const fcsa_varlen* seqs, const WindowCall* win, const float* dlse = nullptr);
 int fcsa_backward_varlen(const fcsa_backward_args* a, const fcsa_varlen* seqs) { return backward_varlen(a, seqs, nullptr); }
 
 size_t fcsa_backward_window_workspace_bytes(const fcsa_problem* p, const fcsa_varlen* seqs, const fcsa_window* w) {
@@ -905,19 +905,94 @@ size_t fcsa_backward_window_workspace_bytes(const fcsa_problem* p, const fcsa_va
   return kind == fcsa::WinKind::Window ? bwd_layout(np, true).total : bwd_layout(np).total;
 }
 
-int fcsa_backward_window(const fcsa_backward_args* a, const fcsa_varlen* seqs, const fcsa_window* w) {
+// dlse: the LSE gradient of fcsa_backward_state, or nullptr
+static int backward_window(const fcsa_backward_args* a, const fcsa_varlen* seqs, const fcsa_window* w, const float* dlse) {
   if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
   if (int rc = check_problem(a->p)) return rc;
   if (int rc = check_window(w, a->mask != nullptr, a->attn_bias != nullptr || a->d_bias != nullptr)) return rc;
   WindowCall win;
   const fcsa::WinKind kind = fcsa::win_normalise(a->p.q_len, a->p.k_len, a->p.causal != 0, w->left, w->right, win.lo, win.hi);
-  if (kind == fcsa::WinKind::Window) return seqs != nullptr ? backward_varlen(a, seqs, &win) : backward_impl(a, nullptr, &win);
+  if (kind == fcsa::WinKind::Window) return seqs != nullptr ? backward_varlen(a, seqs, &win, dlse) : backward_impl(a, nullptr, &win, dlse);
   fcsa_backward_args na = *a;
   na.p.causal = kind == fcsa::WinKind::Causal ? 1 : 0;
-  return seqs != nullptr ? fcsa_backward_varlen(&na, seqs) : fcsa_backward(&na);
+  return seqs != nullptr ? backward_varlen(&na, seqs, nullptr, dlse) : backward_impl(&na, nullptr, nullptr, dlse);
+}
+int fcsa_backward_window(const fcsa_backward_args* a, const fcsa_varlen* seqs, const fcsa_window* w) { return backward_window(a, seqs, w, nullptr); }
+
+int fcsa_backward_state(const fcsa_backward_args* a, const fcsa_varlen* seqs, const fcsa_window* w, const float* d_lse) {
+  if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "backward_state: null args");
+  if (a->mask != nullptr || a->attn_bias != nullptr || a->d_bias != nullptr)
+    return fail(FCSA_ERR_INVALID_ARG, "backward_state: mask, attn_bias and d_bias are not supported with attention states (the log-sum-exp)");
+  if (w != nullptr) return backward_window(a, seqs, w, d_lse);
+  return seqs != nullptr ? backward_varlen(a, seqs, nullptr, d_lse) : backward_impl(a, nullptr, nullptr, d_lse);
 }
 
-static int backward_varlen(const fcsa_backward_args* a, const fcsa_varlen* seqs, const WindowCall* win) {
+int fcsa_attention_lse(const fcsa_problem* pp, const float* inv_l, const fcsa_varlen* seqs, const fcsa_window* w, const fcsa_lse_out* lse_out,
+                       void* stream) {
+  if (pp == nullptr || lse_out == nullptr) return fail(FCSA_ERR_INVALID_ARG, "attention_lse: null argument");
+  const fcsa_problem& p = *pp;
+  if (int rc = check_problem(p)) return rc;
+  if (seqs != nullptr) {
+    if (int rc = check_varlen(p, seqs, false, false)) return rc;
+  }
+  if (w != nullptr) {
+    if (int rc = check_window(w, false, false)) return rc;
+  }
+  if (p.batch == 0 || p.heads == 0 || p.q_len == 0 || (seqs != nullptr && seqs->total_q == 0)) return FCSA_OK;      // no row
+  if (lse_out->lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "attention_lse: lse_out: null pointer");
+  if (inv_l == nullptr) return fail(FCSA_ERR_INVALID_ARG, "attention_lse: inv_l: null pointer");
+  fcsa::StateLseParams sp;
+  sp.inv_l = inv_l;
+  sp.out = fcsa::DecodeLseOut{lse_out->lse, lse_out->stride0, lse_out->stride1, lse_out->stride2};
+  sp.B = p.batch; sp.H = p.heads; sp.N = p.q_len; sp.M = p.k_len;
+  // the sides as every windowed launch takes them: (open, open) no mask, (open, 0) causal
+  (void)fcsa::win_normalise(p.q_len, p.k_len, p.causal != 0, w != nullptr ? w->left : -1, w != nullptr ? w->right : -1, sp.win_lo, sp.win_hi);
+  sp.c2 = exponent_shift(p, false) * kLog2e;
+  sp.invl_log2 = dynamic_shift(p, false) ? 1 : 0;
+  sp.seq = seqs != nullptr ? fcsa::SeqTable{seqs->cu_seqlens_q, seqs->cu_seqlens_k, (int)seqs->total_q, (int)seqs->total_k}
+                           : fcsa::SeqTable{nullptr, nullptr, 0, 0};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return timed("state_lse", "state lse", s, [&] { return fcsa::launch_state_lse(sp, s); });
+}
+
+int fcsa_merge_states_backward(const fcsa_merge_backward_args* a) {
+  if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "merge_states_backward: null args");
+  if (a->dtype != FCSA_F32 && a->dtype != FCSA_F16 && a->dtype != FCSA_BF16)
+    return fail(FCSA_ERR_UNSUPPORTED, "merge_states_backward: dtype %d not supported", a->dtype);
+  if (a->states < 1 || a->states > FCSA_MERGE_MAX_STATES)
+    return fail(FCSA_ERR_INVALID_ARG, "merge_states_backward: %d states outside [1, %d]", a->states, FCSA_MERGE_MAX_STATES);
+  if (a->size0 < 0 || a->size1 < 0 || a->size2 < 0) return fail(FCSA_ERR_INVALID_ARG, "merge_states_backward: negative size");
+  const int per16 = 16 / elem_size(a->dtype);
+  if (a->dim_head < per16 || a->dim_head % per16 != 0)
+    return fail(FCSA_ERR_UNSUPPORTED, "merge_states_backward: dim_head %d is not a positive multiple of %d (16-byte rows)", a->dim_head, per16);
+  const int64_t rows = (int64_t)a->size0 * a->size1 * a->size2;
+  if (rows == 0) return FCSA_OK;
+  if (rows / 16 > (int64_t)INT32_MAX - 1) return fail(FCSA_ERR_UNSUPPORTED, "merge_states_backward: grid above 2^31 workgroups");
+  const int es = elem_size(a->dtype);
+  fcsa::MergeBwdParams mp;
+  auto lse_view = [](const fcsa_lse_out& l) { return fcsa::DecodeLseOut{l.lse, l.stride0, l.stride1, l.stride2}; };
+  for (int s = 0; s < FCSA_MERGE_MAX_STATES; ++s) {
+    const int t = std::min(s, a->states - 1);      // (the unused slots repeat the last state: never read, never written, never null)
+    if (s < a->states) {
+      if (int rc = check_tensor("merge_states_backward: o_in", a->o_in[s], es, true)) return rc;
+      if (int rc = check_tensor("merge_states_backward: d_o_in", a->d_o_in[s], es, true)) return rc;
+      if (a->lse_in[s].lse == nullptr || a->d_lse_in[s].lse == nullptr)
+        return fail(FCSA_ERR_INVALID_ARG, "merge_states_backward: lse_in[%d] / d_lse_in[%d]: null pointer", s, s);
+    }
+    mp.o_in[s] = view(a->o_in[t], es);
+    mp.lse_in[s] = lse_view(a->lse_in[t]);
+    mp.d_o_in[s] = view(a->d_o_in[t], es);
+    mp.d_lse_in[s] = lse_view(a->d_lse_in[t]);
+  }
+  if (int rc = check_tensor("merge_states_backward: d_o", a->d_o, es, true)) return rc;
+  mp.d_o = view(a->d_o, es);
+  mp.d_lse = lse_view(a->d_lse);
+  mp.n0 = a->size0; mp.n1 = a->size1; mp.n2 = a->size2; mp.D = a->dim_head; mp.S = a->states;
+  hipStream_t s = static_cast<hipStream_t>(a->stream);
+  return timed("merge_states_bwd", "merge states backward", s, [&] { return fcsa::launch_merge_states_backward(a->dtype, mp, s); });
+}
+
+static int backward_varlen(const fcsa_backward_args* a, const fcsa_varlen* seqs, const WindowCall* win, const float* dlse) {
   if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
   if (int rc = check_problem(a->p)) return rc;
   if (int rc = check_varlen(a->p, seqs, a->mask != nullptr, a->attn_bias != nullptr || a->d_bias != nullptr)) return rc;
@@ -926,7 +1001,7 @@ static int backward_varlen(const fcsa_backward_args* a, const fcsa_varlen* seqs,
   pa.dq = packed(pa.dq); pa.dk = packed(pa.dk); pa.dv = packed(pa.dv);
   pa.p = packed_problem(a->p, *seqs);
   const VarlenCall vl = {seqs, a->p.batch, a->p.q_len, a->p.k_len};
-  return backward_impl(&pa, &vl, win);
+  return backward_impl(&pa, &vl, win, dlse);
 }
 
 }  // extern "C"
@@ -934,7 +1009,7 @@ static int backward_varlen(const fcsa_backward_args* a, const fcsa_varlen* seqs,
 namespace {
 
 // win != nullptr: a sliding window (the windowed kernel forms; the plan of a packed call: no split, no group sweep)
-int backward_impl(const fcsa_backward_args* a, const VarlenCall* vl, const WindowCall* win) {
+int backward_impl(const fcsa_backward_args* a, const VarlenCall* vl, const WindowCall* win, const float* dlse) {
   if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
   const fcsa_problem& p = a->p;
   if (int rc = check_problem(p)) return rc;
@@ -1019,6 +1094,7 @@ int backward_impl(const fcsa_backward_args* a, const VarlenCall* vl, const Windo
   }
   bp.inv_l = a->inv_l;
   bp.delta = reinterpret_cast<float*>(ws + L.delta);
+  bp.dlse = dlse;
   bp.mask = a->mask;
   bp.bias = static_cast<const char*>(a->attn_bias);
   bp.d_bias = a->d_bias;

@@ -964,6 +964,7 @@ FCSA_DEV bool varlen_bind(BwdParams& p, int& bh, int pair, int tile, int causal,
   varlen_rebase(p.dv, k0);
   p.inv_l += qrow;
   p.delta += qrow;
+  if (p.dlse != nullptr) p.dlse += qrow;
   if (p.rq != nullptr) p.rq += qrow * p.G;
   if (p.rk != nullptr) p.rk += krow * p.G;
   p.B = 1;

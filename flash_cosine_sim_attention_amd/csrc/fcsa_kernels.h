@@ -84,6 +84,9 @@ struct BwdParams {
   int G, lgm;               // groups; log2(group size / 8)
   float norm_eps;           // 1e-12
   SeqTable seq;             // packed sequences (seq.cu_q != nullptr): no split, no bias, no key mask, no group sweep
+  const float* dlse = nullptr;   // [B,H,N] like inv_l: the gradient of the rows' log-sum-exp (fcsa_backward_state), or nullptr: none.  The dQ
+                            //    kernel publishes delta - dlse (d lse_i / d s_ij = P_ij, so dS = P (dP - (delta - dlse))); every reader of
+                            //    delta gets it from there.  (Last field: the ones above keep their places.)
 };
 struct BwdWinParams : BwdParams {      // (see FwdWinParams; bwd_dq_win_kernel / bwd_dkv_win_kernel)
   int window = 0;
@@ -185,6 +188,32 @@ struct MergeParams {
   int n0, n1, n2, D, S;
 };
 hipError_t launch_merge_states(int dtype, const MergeParams& p, hipStream_t s);
+// Its backward (fcsa_merge_states_backward): the gradients (d_o, d_lse) of the merged state -> (d_o_in[s], d_lse_in[s]) of every state.
+// d_lse.lse == nullptr: no gradient for the merged lse (0).
+struct MergeBwdParams {
+  View         o_in[8];
+  DecodeLseOut lse_in[8];
+  View         d_o;
+  DecodeLseOut d_lse;
+  View         d_o_in[8];
+  DecodeLseOut d_lse_in[8];
+  int n0, n1, n2, D, S;
+};
+hipError_t launch_merge_states_backward(int dtype, const MergeBwdParams& p, hipStream_t s);
+
+// The rows' log-sum-exp of a training forward from its saved inv_l (fcsa_attention_lse, csrc/fcsa_state.hip).  B / N / M as in FwdParams
+// (packed: sequences and the longest spans); inv_l [B, H, N] (packed: [1, H, total_q]); out in ELEMENT strides ([b, h, i], packed
+// [tok, h]); win_lo / win_hi: the sides win_normalise gives -- (kWinOpen, kWinOpen) no mask, (kWinOpen, 0) causal.
+struct StateLseParams {
+  const float* inv_l;
+  DecodeLseOut out;
+  int B, H, N, M;
+  int win_lo, win_hi;
+  float c2;                 // shift * log2(e) (0 with invl_log2)
+  int invl_log2;            // inv_l holds log2 of the normaliser (the per-row-shift regime)
+  SeqTable seq;
+};
+hipError_t launch_state_lse(const StateLseParams& p, hipStream_t s);
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE property of a kernel: raise it once per (instantiation, device).
 // `done` is the instantiation's bit mask of devices that have it (one static per launcher); thread safe, idempotent.

@@ -16,6 +16,7 @@
 #include <dlfcn.h>
 
 #include <atomic>
+#include <cmath>
 #include <cstring>
 #include <chrono>
 #include <tuple>
@@ -61,7 +62,11 @@ namespace {
   X(forward_kvcache_lse, fcsa_forward_kvcache_lse, false)                                 \
   X(merge_states, fcsa_merge_states, false)                                               \
   /* prompt chunks against the cache (the multi-wave prefill kernel) */                   \
-  X(forward_kvcache_prefill, fcsa_forward_kvcache_prefill, false)
+  X(forward_kvcache_prefill, fcsa_forward_kvcache_prefill, false)                         \
+  /* attention states for training: the forward's log-sum-exp, its gradient, the merge's backward */ \
+  X(attention_lse, fcsa_attention_lse, false)                                             \
+  X(backward_state, fcsa_backward_state, false)                                           \
+  X(merge_states_backward, fcsa_merge_states_backward, false)
 
 struct Abi {
 #define X(member, symbol, required) decltype(&symbol) member = &symbol;
@@ -386,7 +391,7 @@ Saved varlen_window_forward(const Tensor& q, const Tensor& k, const Tensor& v, c
 using Grads = std::tuple<Tensor, Tensor, Tensor, Tensor>;
 
 Grads backward_body(const Call& c, const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& qn, const Tensor& kn, const Tensor& rq,
-                    const Tensor& rk, bool need_bias_grad, const fcsa_window* win, Lap& lap) {
+                    const Tensor& rk, bool need_bias_grad, const fcsa_window* win, Lap& lap, const Tensor* d_lse = nullptr) {
   const bool l2norm_qk = c.p.l2norm_qk != 0;
   const at::ScalarType dt = c.q.scalar_type();
   const auto dev = c.q.device();
@@ -425,6 +430,15 @@ Grads backward_body(const Call& c, const Tensor& d_out, const Tensor& o, const T
     saved_ok("rq", rq, at::kFloat, c.rows_q, c.groups);
     saved_ok("rk", rk, at::kFloat, c.rows_k, c.groups);
   }
+  // the gradient of the rows' log-sum-exp (attention_state_backward), brought into inv_l's layout whatever its strides: float32
+  // contiguous [B, H, N], packed [H, total_q] from the public [total_q, H]
+  Tensor gl;
+  if (d_lse != nullptr) {
+    need_abi("attention_state_backward", "fcsa_backward_state", g_abi.backward_state);
+    gl = c.packed() ? d_lse->transpose(0, 1) : *d_lse;
+    TORCH_CHECK_VALUE(gl.device() == dev && gl.sizes() == at::IntArrayRef(c.rows_q), "d_lse must have the shape of lse on q's device");
+    gl = gl.to(at::kFloat).contiguous();
+  }
   lap.mark(3);
   Tensor dq = at::empty(c.q.sizes(), opt);
   Tensor dk = at::empty(c.k.sizes(), opt);
@@ -456,7 +470,8 @@ Grads backward_body(const Call& c, const Tensor& d_out, const Tensor& o, const T
   a.workspace = ws.data_ptr(); a.workspace_bytes = wsb;
   a.stream = stream_of(c.q);
   lap.mark(4);
-  if (win != nullptr) check(g_abi.backward_window(&a, seqs, win), "fcsa_backward_window");
+  if (gl.defined()) check(g_abi.backward_state(&a, seqs, win, gl.data_ptr<float>()), "fcsa_backward_state");
+  else if (win != nullptr) check(g_abi.backward_window(&a, seqs, win), "fcsa_backward_window");
   else if (seqs != nullptr) check(g_abi.backward_varlen(&a, seqs), "fcsa_backward_varlen");
   else check(g_abi.backward(&a), "fcsa_backward");
   lap.mark(5);
@@ -994,6 +1009,208 @@ std::tuple<Tensor, Tensor> merge_states(at::TensorList os, at::TensorList lses) 
   return {o, lse};
 }
 
+// ---- attention states for training (namespace fcsa_state): the forward's log-sum-exp as a second differentiable result, and a
+// differentiable merge.  One op family serves the dense, the local and the packed operator: cu_seqlens given: packed q [total_q, H, D];
+// window sides of (-1, -1): no window.  o, the saved state and -- with no gradient for the lse -- dq, dk, dv are those of the op of that
+// route, bit for bit: the same forward_body / backward_body, the same launches.
+// (o, lse, inv_l, qn, kn, rq, rk): lse float32 [B, H, N], packed [total_q, H].  The saved state is always produced: the lse is read off inv_l.
+using StateSaved = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
+
+Call state_call(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& cu_q, const optional<Tensor>& cu_k, int64_t max_q,
+                int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups) {
+  TORCH_CHECK_VALUE(cu_q.has_value() == cu_k.has_value(), "cu_seqlens_q and cu_seqlens_k must be given together");
+  if (cu_q.has_value()) return canonicalise_varlen(q, k, v, *cu_q, *cu_k, max_q, max_k, scale, causal, l2norm_qk, groups);
+  TORCH_CHECK_VALUE(q.dim() == 4 && k.dim() == 4 && v.dim() == 4, "attention_state takes 4-D q, k, v, or packed 3-D ones with cu_seqlens");
+  return canonicalise(q, k, v, c10::nullopt, c10::nullopt, false, scale, causal, l2norm_qk, groups);
+}
+
+StateSaved attention_state_forward(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& cu_q, const optional<Tensor>& cu_k,
+                                   int64_t max_q, int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups, int64_t left,
+                                   int64_t right) {
+  need_abi("attention_state", "fcsa_attention_lse", g_abi.attention_lse);
+  const bool windowed = !(left == -1 && right == -1);
+  fcsa_window w{-1, -1};
+  if (windowed) w = Win(left, right).w;
+  const Call c = state_call(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups);
+  Lap lap(false);
+  auto [o, inv_l, qn, kn, rq, rk] = forward_body(c, true, windowed ? &w : nullptr, lap);
+  c10::DeviceGuard guard(c.q.device());
+  const auto f32 = c.q.options().dtype(at::kFloat);
+  Tensor lse = c.packed() ? at::empty({c.q.size(0), c.q.size(1)}, f32) : at::empty(c.rows_q, f32);
+  if (lse.numel() > 0) {
+    // Which normaliser the lse is read off.  The 16-bit forward's row sum adds the P~ values ROUNDED to the type, so
+    // ln(l) carries up to one unit roundoff u of the type.  With l2norm_qk the rounding of the operands c1 q^, k^ already moves every logit
+    // by up to 2 u |scale| groups, and the row sum's u disappears in that.  Where it does not -- the caller's q, k ARE the operands
+    // (l2norm_qk off), or |scale| groups < 1/2 -- the lse is taken from the inv_l of a second, float32 forward on the same values: float32
+    // row sums of un-rounded P~.  o, the saved state and every gradient stay those of the 16-bit call.
+    const bool exact = c.p.dtype != FCSA_F32 && (c.p.l2norm_qk == 0 || 2.0 * std::fabs(scale) * (double)c.p.groups < 1.0);
+    Call c32;
+    Tensor inv_l32;
+    if (exact) {
+      c32 = state_call(q.to(at::kFloat), k.to(at::kFloat), v.to(at::kFloat), cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups);
+      Lap lap32(false);
+      inv_l32 = std::get<1>(forward_body(c32, true, windowed ? &w : nullptr, lap32));
+    }
+    const Call& lc = exact ? c32 : c;
+    const fcsa_lse_out lo = strided<fcsa_lse_out>(lse, c.layout());
+    fcsa_varlen t;
+    if (c.packed()) t = varlen_table(c);
+    check(g_abi.attention_lse(&lc.p, (exact ? inv_l32 : inv_l).data_ptr<float>(), c.packed() ? &t : nullptr, windowed ? &w : nullptr, &lo,
+                              stream_of(c.q)),
+          "fcsa_attention_lse");
+  }
+  return std::make_tuple(o, lse, inv_l, qn, kn, rq, rk);
+}
+
+// d_out / d_lse: the gradients of o / lse; an absent d_out is zeros, an absent d_lse runs the backward of the op without the lse, bit for bit
+Grads3 attention_state_backward(const optional<Tensor>& d_out, const optional<Tensor>& d_lse, const Tensor& o, const Tensor& inv_l, const Tensor& q,
+                                const Tensor& k, const Tensor& v, const optional<Tensor>& cu_q, const optional<Tensor>& cu_k, const Tensor& qn,
+                                const Tensor& kn, const Tensor& rq, const Tensor& rk, int64_t max_q, int64_t max_k, double scale, bool causal,
+                                bool l2norm_qk, int64_t groups, int64_t left, int64_t right) {
+  const bool windowed = !(left == -1 && right == -1);
+  fcsa_window w{-1, -1};
+  if (windowed) w = Win(left, right).w;
+  const Call c = state_call(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups);
+  Lap lap(false);
+  const Tensor go = d_out.has_value() ? *d_out : at::zeros_like(o);
+  return first3(backward_body(c, go, o, inv_l, qn, kn, rq, rk, false, windowed ? &w : nullptr, lap, d_lse.has_value() ? &*d_lse : nullptr));
+}
+
+using StateScalars = std::tuple<int64_t, int64_t, double, bool, bool, int64_t, int64_t, int64_t>;   // max_q, max_k, scale, causal, l2norm_qk, groups, left, right
+
+struct AttentionStateNode : public torch::autograd::Function<AttentionStateNode> {
+  static variable_list forward(AutogradContext* ctx, const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& cu_q,
+                               const optional<Tensor>& cu_k, const StateScalars& s) {
+    ctx->set_materialize_grads(false);      // an absent gradient stays absent: no lse gradient -> the existing backward, bit for bit
+    at::AutoDispatchBelowADInplaceOrView guard;
+    static auto op = typed_op("fcsa_state::attention_state_forward", &attention_state_forward);
+    auto r = std::apply([&](const auto&... e) { return op.call(q, k, v, cu_q, cu_k, e...); }, s);
+    ctx->save_for_backward({std::get<0>(r), std::get<2>(r), q, k, v, std::get<3>(r), std::get<4>(r), std::get<5>(r), std::get<6>(r),
+                            saveable(cu_q), saveable(cu_k)});
+    ctx->saved_data["scalars"] = c10::IValue(s);
+    return {std::get<0>(r), std::get<1>(r)};
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    const auto t = ctx->get_saved_variables();      // o, inv_l, q, k, v, qn, kn, rq, rk, cu_q, cu_k
+    const StateScalars s = ctx->saved_data["scalars"].to<StateScalars>();
+    static auto op = typed_op("fcsa_state::attention_state_backward", &attention_state_backward);
+    const optional<Tensor> go = restored<optional<Tensor>>(grads[0]), gl = restored<optional<Tensor>>(grads[1]);
+    const optional<Tensor> cu_q = restored<optional<Tensor>>(t[9]), cu_k = restored<optional<Tensor>>(t[10]);
+    auto g = std::apply([&](const auto&... e) { return op.call(go, gl, t[0], t[1], t[2], t[3], t[4], cu_q, cu_k, t[5], t[6], t[7], t[8], e...); }, s);
+    return {std::get<0>(g), std::get<1>(g), std::get<2>(g), Tensor(), Tensor(), Tensor()};
+  }
+};
+
+std::tuple<Tensor, Tensor> attention_state_plain(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& cu_q,
+                                                 const optional<Tensor>& cu_k, int64_t max_q, int64_t max_k, double scale, bool causal,
+                                                 bool l2norm_qk, int64_t groups, int64_t left, int64_t right) {
+  auto r = attention_state_forward(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, left, right);
+  return {std::get<0>(r), std::get<1>(r)};
+}
+std::tuple<Tensor, Tensor> attention_state_autograd(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& cu_q,
+                                                    const optional<Tensor>& cu_k, int64_t max_q, int64_t max_k, double scale, bool causal,
+                                                    bool l2norm_qk, int64_t groups, int64_t left, int64_t right) {
+  if (!(at::GradMode::is_enabled() && (q.requires_grad() || k.requires_grad() || v.requires_grad()))) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    return attention_state_plain(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, left, right);
+  }
+  auto r = AttentionStateNode::apply(q, k, v, cu_q, cu_k, StateScalars{max_q, max_k, scale, causal, l2norm_qk, groups, left, right});
+  return {r[0], r[1]};
+}
+
+// merge_state: merge_states (the same function: the forward kernel, bit for bit) with a backward.
+// merge_state_backward: (d_o?, d_lse?, os, lses) -> (d_os, d_lses); an absent d_o is zeros, an absent d_lse is no gradient for the lse.
+std::tuple<std::vector<Tensor>, std::vector<Tensor>> merge_state_backward(const optional<Tensor>& d_o, const optional<Tensor>& d_lse, at::TensorList os,
+                                                                          at::TensorList lses) {
+  need_abi("merge_attention_states_with_grad", "fcsa_merge_states_backward", g_abi.merge_states_backward);
+  const int64_t S = (int64_t)os.size();
+  TORCH_CHECK_VALUE(S >= 1 && S <= FCSA_MERGE_MAX_STATES && (int64_t)lses.size() == S,
+                    "merge_state_backward takes 1 to ", FCSA_MERGE_MAX_STATES, " states and as many lses, got ", S, " and ", lses.size());
+  const Tensor& o0 = os[0];
+  TORCH_CHECK(o0.is_cuda(), "merge_state_backward: GPU tensors only (HIP kernels only)");
+  TORCH_CHECK_VALUE(o0.dim() == 3 || o0.dim() == 4, "merge_state_backward: os must be 4-D [..., D] or 3-D [total_q, H, D], got ", o0.sizes());
+  const int64_t D = o0.size(-1);
+  const int64_t per16 = 16 / o0.element_size();
+  TORCH_CHECK_VALUE(D >= per16 && D % per16 == 0, "merge_state_backward: the feature dim (", D, ") must be a positive multiple of ", per16);
+  c10::DeviceGuard guard(o0.device());
+  fcsa_merge_backward_args a;
+  std::memset(&a, 0, sizeof(a));
+  a.dtype = dtype_code(o0.scalar_type());
+  const Layout l = o0.dim() == 3 ? kRows3 : kDense;
+  for (int64_t d = 0; d + 1 < o0.dim(); ++d) TORCH_CHECK_VALUE(o0.size(d) <= INT32_MAX, "merge_state_backward: sizes must stay below 2^31");
+  a.size0 = l.batch < 0 ? 1 : (int32_t)o0.size(l.batch);
+  a.size1 = (int32_t)o0.size(l.head);
+  a.size2 = (int32_t)o0.size(l.pos);
+  a.dim_head = (int32_t)D;
+  a.states = (int32_t)S;
+  const auto lead = o0.sizes().slice(0, o0.dim() - 1);
+  const auto f32 = o0.options().dtype(at::kFloat);
+  std::vector<Tensor> keep, d_os, d_lses;
+  for (int64_t s = 0; s < S; ++s) {
+    const Tensor& o = os[s];
+    const Tensor& ls = lses[s];
+    TORCH_CHECK_VALUE(o.device() == o0.device() && ls.device() == o0.device(), "merge_state_backward: every tensor must live on the first one's GPU");
+    TORCH_CHECK_TYPE(o.scalar_type() == o0.scalar_type() && ls.scalar_type() == at::kFloat, "merge_state_backward: os must share a dtype and lses be float32");
+    TORCH_CHECK_VALUE(o.sizes() == o0.sizes() && ls.sizes() == lead, "merge_state_backward: os must share a shape and every lse have it without the feature dim");
+    keep.push_back(prep(o));
+    d_os.push_back(at::empty(o0.sizes(), o0.options()));
+    d_lses.push_back(at::empty(lead, f32));
+    a.o_in[s] = strided(keep.back(), l);
+    a.lse_in[s] = strided<fcsa_lse_out>(ls, l);
+    a.d_o_in[s] = strided(d_os.back(), l);
+    a.d_lse_in[s] = strided<fcsa_lse_out>(d_lses.back(), l);
+  }
+  Tensor go = d_o.has_value() ? *d_o : at::zeros(o0.sizes(), o0.options());
+  TORCH_CHECK_VALUE(go.sizes() == o0.sizes() && go.device() == o0.device(), "merge_state_backward: d_o must have the shape of o on its device");
+  if (go.scalar_type() != o0.scalar_type()) go = go.to(o0.scalar_type());
+  go = prep(go);
+  a.d_o = strided(go, l);
+  Tensor gl;
+  if (d_lse.has_value()) {
+    TORCH_CHECK_VALUE(d_lse->sizes() == lead && d_lse->device() == o0.device(), "merge_state_backward: d_lse must have the shape of lse on its device");
+    gl = d_lse->to(at::kFloat);
+    a.d_lse = strided<fcsa_lse_out>(gl, l);
+  }
+  a.stream = stream_of(o0);
+  if (o0.numel() > 0) check(g_abi.merge_states_backward(&a), "fcsa_merge_states_backward");
+  return {d_os, d_lses};
+}
+
+struct MergeStateNode : public torch::autograd::Function<MergeStateNode> {
+  static variable_list forward(AutogradContext* ctx, at::TensorList os, at::TensorList lses) {
+    ctx->set_materialize_grads(false);
+    at::AutoDispatchBelowADInplaceOrView guard;
+    static auto op = typed_op("fcsa::merge_states", &merge_states);
+    auto r = op.call(os, lses);
+    variable_list save(os.begin(), os.end());
+    save.insert(save.end(), lses.begin(), lses.end());
+    ctx->save_for_backward(std::move(save));
+    return {std::get<0>(r), std::get<1>(r)};
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    const auto t = ctx->get_saved_variables();      // os..., lses...
+    const size_t S = t.size() / 2;
+    static auto op = typed_op("fcsa_state::merge_state_backward", &merge_state_backward);
+    auto g = op.call(restored<optional<Tensor>>(grads[0]), restored<optional<Tensor>>(grads[1]), at::TensorList(t.data(), S),
+                     at::TensorList(t.data() + S, S));
+    variable_list out = std::get<0>(g);
+    out.insert(out.end(), std::get<1>(g).begin(), std::get<1>(g).end());
+    return out;
+  }
+};
+
+std::tuple<Tensor, Tensor> merge_state_autograd(at::TensorList os, at::TensorList lses) {
+  bool tracked = false;
+  for (const Tensor& t : os) tracked = tracked || t.requires_grad();
+  for (const Tensor& t : lses) tracked = tracked || t.requires_grad();
+  if (!(at::GradMode::is_enabled() && tracked)) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    return merge_states(os, lses);
+  }
+  auto r = MergeStateNode::apply(os, lses);
+  return {r[0], r[1]};
+}
+
 }  // namespace
 
 // Measurement hook: read (and reset) the host-time counters above.
@@ -1103,6 +1320,33 @@ TORCH_LIBRARY(fcsa_prefill, m) {
         "int groups) -> (Tensor, Tensor)");
 }
 TORCH_LIBRARY_IMPL(fcsa_prefill, CUDA, m) { m.impl("kvcache_prefill_forward", &kvcache_prefill_forward); }
+
+// Attention states for training, in a namespace of their own (the op set of `fcsa` is pinned): the attention op with the rows'
+// log-sum-exp as a second differentiable result -- dense, local (window sides other than (-1, -1)) or packed (cu_seqlens given) -- and
+// the differentiable merge, each with its forward and backward op.
+TORCH_LIBRARY(fcsa_state, m) {
+  m.def("attention_state_forward(Tensor q, Tensor k, Tensor v, Tensor? cu_seqlens_q, Tensor? cu_seqlens_k, int max_seqlen_q, int max_seqlen_k, "
+        "float scale, bool causal, bool l2norm_qk, int groups, int window_left, int window_right) "
+        "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("attention_state_backward(Tensor? d_out, Tensor? d_lse, Tensor o, Tensor inv_l, Tensor q, Tensor k, Tensor v, Tensor? cu_seqlens_q, "
+        "Tensor? cu_seqlens_k, Tensor qn, Tensor kn, Tensor rq, Tensor rk, int max_seqlen_q, int max_seqlen_k, float scale, bool causal, "
+        "bool l2norm_qk, int groups, int window_left, int window_right) -> (Tensor, Tensor, Tensor)");
+  m.def("attention_state(Tensor q, Tensor k, Tensor v, Tensor? cu_seqlens_q, Tensor? cu_seqlens_k, int max_seqlen_q, int max_seqlen_k, "
+        "float scale, bool causal, bool l2norm_qk, int groups, int window_left, int window_right) -> (Tensor, Tensor)");
+  m.def("merge_state_backward(Tensor? d_o, Tensor? d_lse, Tensor[] os, Tensor[] lses) -> (Tensor[], Tensor[])");
+  m.def("merge_state(Tensor[] os, Tensor[] lses) -> (Tensor, Tensor)");
+}
+TORCH_LIBRARY_IMPL(fcsa_state, CUDA, m) {
+  m.impl("attention_state_forward", &attention_state_forward);
+  m.impl("attention_state_backward", &attention_state_backward);
+  m.impl("attention_state", &attention_state_plain);
+  m.impl("merge_state_backward", &merge_state_backward);
+  m.impl("merge_state", &merge_states);
+}
+TORCH_LIBRARY_IMPL(fcsa_state, Autograd, m) {
+  m.impl("attention_state", &attention_state_autograd);
+  m.impl("merge_state", &merge_state_autograd);
+}
 
 TORCH_LIBRARY_IMPL(fcsa, Autograd, m) {
   m.impl("attention", &attention_autograd);

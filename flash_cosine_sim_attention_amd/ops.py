@@ -188,22 +188,9 @@ def _check_host_cu(name, cu, total, max_len):
     return longest
 
 
-def flash_cosine_sim_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, scale=8, groups=1,
-                                      causal=False, l2norm_qk=True, window_size=(-1, -1)):
-    """Fused cosine-similarity attention over packed variable-length sequences.
-
-    q [total_q, H, D] and k, v [total_k, Hk, D] (Hk dividing H) hold S sequences back to back; sequence s owns the query rows
-    [cu_seqlens_q[s], cu_seqlens_q[s + 1]) and the key rows [cu_seqlens_k[s], cu_seqlens_k[s + 1]) (int32 tables of S + 1 entries).
-    Each sequence's output rows are what `flash_cosine_sim_attention` returns for that sequence alone as a [1, H, N_s, D] problem
-    (causal alignment per sequence, rows without a visible key give 0).  Returns o shaped like q; differentiable w.r.t. q, k, v.
-    There is no mask or attn_bias.
-
-    Tables on the host are validated fully (and copied to q's device); tables already on the device are trusted, as in flash-attn --
-    a malformed device table gives wrong rows, never an access outside the tensors.  max_seqlen_q / max_seqlen_k must be at least
-    the longest span: the launch grid is sized by them.  When None they are computed from the tables, which synchronises the device
-    when the tables live there.  CPU tensors take the forward-only path of `cpu.py`, one dense CPU call per sequence.
-    window_size = (left, right): a sliding window as in `flash_cosine_sim_attention_local`, every sequence with its own alignment."""
-    window = _window(window_size)
+def _check_packed(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k):
+    """The checks of a packed call (`flash_cosine_sim_attention_varlen`, `flash_cosine_sim_attention_with_lse`): shapes, dtypes, tables;
+    host tables are validated fully.  Returns (max_seqlen_q, max_seqlen_k), filled in from host tables where they were None."""
     for name, t in (("q", q), ("k", k), ("v", v)):
         if t.dim() != 3:
             raise ValueError(f"{name} must be a packed [total, heads, dim_head] tensor, got {tuple(t.shape)}")
@@ -229,18 +216,42 @@ def flash_cosine_sim_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_s
     if cu_seqlens_k.device.type == "cpu":
         longest = _check_host_cu("cu_seqlens_k", cu_seqlens_k, k.shape[0], max_seqlen_k)
         max_seqlen_k = longest if max_seqlen_k is None else max_seqlen_k
-    if q.device.type == "cpu":
-        if cu_seqlens_q.device.type != "cpu" or cu_seqlens_k.device.type != "cpu":
-            raise ValueError("CPU tensors take host cu_seqlens tables")
-        return _cpu.attention_forward_varlen_cpu(q, k, v, cu_seqlens_q, cu_seqlens_k, scale=scale, groups=groups, causal=causal,
-                                                 l2norm_qk=l2norm_qk, window_size=window)
-    # device tables are trusted; a max_seqlen left to us costs one device synchronisation per table
+    if q.device.type == "cpu" and (cu_seqlens_q.device.type != "cpu" or cu_seqlens_k.device.type != "cpu"):
+        raise ValueError("CPU tensors take host cu_seqlens tables")
+    return max_seqlen_q, max_seqlen_k
+
+
+def _packed_on_device(q, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k):
+    """(cu_seqlens_q, cu_seqlens_k on q's device, max_seqlen_q, max_seqlen_k as ints): device tables are trusted; a max_seqlen left to us
+    costs one device synchronisation per table."""
     if max_seqlen_q is None:
         max_seqlen_q = int((cu_seqlens_q[1:] - cu_seqlens_q[:-1]).max().item()) if cu_seqlens_q.numel() > 1 else 0
     if max_seqlen_k is None:
         max_seqlen_k = int((cu_seqlens_k[1:] - cu_seqlens_k[:-1]).max().item()) if cu_seqlens_k.numel() > 1 else 0
-    cu_q = cu_seqlens_q.to(q.device, non_blocking=True)
-    cu_k = cu_seqlens_k.to(q.device, non_blocking=True)
+    return cu_seqlens_q.to(q.device, non_blocking=True), cu_seqlens_k.to(q.device, non_blocking=True), int(max_seqlen_q), int(max_seqlen_k)
+
+
+def flash_cosine_sim_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, scale=8, groups=1,
+                                      causal=False, l2norm_qk=True, window_size=(-1, -1)):
+    """Fused cosine-similarity attention over packed variable-length sequences.
+
+    q [total_q, H, D] and k, v [total_k, Hk, D] (Hk dividing H) hold S sequences back to back; sequence s owns the query rows
+    [cu_seqlens_q[s], cu_seqlens_q[s + 1]) and the key rows [cu_seqlens_k[s], cu_seqlens_k[s + 1]) (int32 tables of S + 1 entries).
+    Each sequence's output rows are what `flash_cosine_sim_attention` returns for that sequence alone as a [1, H, N_s, D] problem
+    (causal alignment per sequence, rows without a visible key give 0).  Returns o shaped like q; differentiable w.r.t. q, k, v.
+    There is no mask or attn_bias.
+
+    Tables on the host are validated fully (and copied to q's device); tables already on the device are trusted, as in flash-attn --
+    a malformed device table gives wrong rows, never an access outside the tensors.  max_seqlen_q / max_seqlen_k must be at least
+    the longest span: the launch grid is sized by them.  When None they are computed from the tables, which synchronises the device
+    when the tables live there.  CPU tensors take the forward-only path of `cpu.py`, one dense CPU call per sequence.
+    window_size = (left, right): a sliding window as in `flash_cosine_sim_attention_local`, every sequence with its own alignment."""
+    window = _window(window_size)
+    max_seqlen_q, max_seqlen_k = _check_packed(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
+    if q.device.type == "cpu":
+        return _cpu.attention_forward_varlen_cpu(q, k, v, cu_seqlens_q, cu_seqlens_k, scale=scale, groups=groups, causal=causal,
+                                                 l2norm_qk=l2norm_qk, window_size=window)
+    cu_q, cu_k, max_seqlen_q, max_seqlen_k = _packed_on_device(q, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
     if window != (-1, -1):
         return _torch_ops.load().varlen_window_attention(q, k, v, cu_q, cu_k, int(max_seqlen_q), int(max_seqlen_k), float(scale),
                                                          bool(causal), bool(l2norm_qk), int(groups), window[0], window[1])
@@ -609,6 +620,17 @@ def merge_attention_states(os, lses):
     when every state is empty o = 0 and lse = -inf.  Deterministic.  +inf or NaN LSEs are not supported.
     More than 8 states: merge in two steps (the result is a state again).  GPU tensors run one launch of the merge kernel; CPU tensors
     take the path of `cpu.py`.  Forward only."""
+    os, lses = _check_states(os, lses)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in os + lses):
+        raise RuntimeError("merge_attention_states is forward-only: run it under torch.no_grad()")
+    if os[0].device.type == "cpu":
+        return _cpu.merge_attention_states_cpu(os, lses)
+    o, lse = _torch_ops.load().merge_states(os, lses)
+    return o, lse
+
+
+def _check_states(os, lses):
+    """The argument checks of `merge_attention_states` and `merge_attention_states_with_grad`; returns (os, lses) as lists."""
     os, lses = list(os), list(lses)
     if not os or len(os) != len(lses):
         raise ValueError(f"merge_attention_states takes as many lses as os and at least one state, got {len(os)} and {len(lses)}")
@@ -636,11 +658,71 @@ def merge_attention_states(os, lses):
             raise ValueError(f"lse {s} must have the shape of its o without the feature dim, {tuple(o0.shape[:-1])}, got {tuple(l.shape)}")
         if o.device != o0.device or l.device != o0.device:
             raise ValueError("os and lses must live on one device")
-    if torch.is_grad_enabled() and any(t.requires_grad for t in os + lses):
-        raise RuntimeError("merge_attention_states is forward-only: run it under torch.no_grad()")
-    if o0.device.type == "cpu":
+    return os, lses
+
+
+# ---------------------------------------------------------------------------------------------
+# attention states for training: the forward's log-sum-exp as a differentiable result, and a differentiable merge
+# ---------------------------------------------------------------------------------------------
+
+def flash_cosine_sim_attention_with_lse(q, k, v, scale=8, groups=1, causal=False, l2norm_qk=True, window_size=(-1, -1), cu_seqlens_q=None,
+                                        cu_seqlens_k=None, max_seqlen_q=None, max_seqlen_k=None):
+    """`flash_cosine_sim_attention` (4-D q, k, v), `flash_cosine_sim_attention_local` (with a window_size) or
+    `flash_cosine_sim_attention_varlen` (packed 3-D q, k, v with cu_seqlens_q / cu_seqlens_k) returning (o, lse): an attention STATE, both
+    parts differentiable w.r.t. q, k, v -- what context-parallel (ring) training, blockwise training over key chunks and loss terms on the
+    log-partition need.  `merge_attention_states_with_grad` joins the states of the same queries over disjoint key sets.
+
+    o is the o of the operator underneath, bit for bit, and with no gradient flowing into lse so are dq, dk, dv: the same kernels run.
+    lse: float32 [B, H, N] (packed: [total_q, H]), the natural log of the sum over the row's visible keys of exp(logit), the logit being
+    scale * (sum over the groups of q^ . k^), or scale * q . k without l2norm_qk.  It is read off the normaliser the forward saves:
+    lse = ln 2 * (c2 - L) with L the log2 the backward kernels seed their logit accumulators with -- the same in both exponent regimes.
+    A row without a visible key (no keys; causal with N > M; a window past the keys) has lse = -inf exactly and o = 0, and takes no
+    gradient whatever its lse gradient holds.  Where the constant-shift clamp acts (a row whose every visible logit lies far below the
+    shift) the value is ln(max(l, eps)) + shift: consistent with o (o * exp(lse) is the un-normalised sum), unlike the unclamped LSE of
+    the cache calls.  Accuracy, 16-bit types: the forward's row sum adds the P~ values rounded to the type, so lse carries up to one unit
+    roundoff of it (3.9e-3 bfloat16, 4.9e-4 float16) -- below what the rounding of the operands q^, k^ already does to the logits (2 u
+    |scale| groups).  Where it would not be (l2norm_qk=False: the caller's q, k are the operands; or |scale| * groups < 1/2) the lse is
+    read off a second, float32 forward of the same call instead: float32-accurate, at the price of that pass.  A gradient for lse costs one subtraction per row in the dQ kernel: dS = P (dP - (delta - dlse)).
+    Every dtype, head dim, K/V grouping and scale of the operators underneath.  There is no mask and no attn_bias (a mask needs a
+    per-batch emptiness rule: not supported with the lse).  Table checks and max_seqlen rules of `flash_cosine_sim_attention_varlen`.
+    CPU tensors: forward only, like the other CPU paths."""
+    window = _window(window_size)
+    packed = cu_seqlens_q is not None or cu_seqlens_k is not None
+    if packed:
+        if cu_seqlens_q is None or cu_seqlens_k is None:
+            raise ValueError("cu_seqlens_q and cu_seqlens_k must be given together")
+        max_seqlen_q, max_seqlen_k = _check_packed(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
+    else:
+        if max_seqlen_q is not None or max_seqlen_k is not None:
+            raise ValueError("max_seqlen_q / max_seqlen_k belong to packed calls (cu_seqlens_q, cu_seqlens_k)")
+        if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+            raise ValueError("flash_cosine_sim_attention_with_lse takes 4-D q, k, v ([batch, heads, length, dim_head]), or packed 3-D ones "
+                             "with cu_seqlens_q and cu_seqlens_k")
+    if q.device.type == "cpu":
+        if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
+            raise RuntimeError("flash_cosine_sim_attention_with_lse is forward-only on CPU tensors: run it under torch.no_grad()")
+        return _cpu.attention_state_cpu(q, k, v, cu_seqlens_q, cu_seqlens_k, scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk,
+                                        window_size=window)
+    cu_q = cu_k = None
+    max_q = max_k = 0
+    if packed:
+        cu_q, cu_k, max_q, max_k = _packed_on_device(q, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
+    _torch_ops.load()
+    return torch.ops.fcsa_state.attention_state(q, k, v, cu_q, cu_k, max_q, max_k, float(scale), bool(causal), bool(l2norm_qk), int(groups),
+                                                window[0], window[1])
+
+
+def merge_attention_states_with_grad(os, lses):
+    """`merge_attention_states`, differentiable w.r.t. every o_s and lse_s: the same checks, and on GPU tensors the same forward kernel, bit
+    for bit.  With a_s = w_s / W the merge weights: d o_s = a_s * do (rounded once) and d lse_s = a_s * (dlse + <do, o_s> - sum_t a_t
+    <do, o_t>), one launch of the merge backward kernel (float32 dot products reduced inside a wave: deterministic).  A state of weight 0
+    (lse_s = -inf) gets zero gradients and its o_s is never read.  CPU tensors: `cpu.merge_attention_states_cpu`, which torch autograd
+    differentiates."""
+    os, lses = _check_states(os, lses)
+    if os[0].device.type == "cpu":
         return _cpu.merge_attention_states_cpu(os, lses)
-    o, lse = _torch_ops.load().merge_states(os, lses)
+    _torch_ops.load()
+    o, lse = torch.ops.fcsa_state.merge_state(os, lses)
     return o, lse
 
 

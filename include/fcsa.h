@@ -398,6 +398,54 @@ typedef struct fcsa_merge_args {
 } fcsa_merge_args;
 int    fcsa_merge_states(const fcsa_merge_args* args);
 
+/* Attention states for training: the log-sum-exp of the training forward as a second, differentiable result, and a differentiable merge
+ * (context-parallel / ring training, blockwise training over key chunks, loss terms on the log-partition).  Additive entry points: no
+ * existing struct changes and FCSA_ABI_VERSION stays 4.
+ *
+ * fcsa_attention_lse: the rows' LSE of a fcsa_forward / fcsa_forward_varlen / fcsa_forward_window call from the inv_l that call saved.
+ *   lse = ln 2 * (c2 - L),  L = log2(inv_l) under the constant shift (c2 = shift * log2(e)), L = inv_l itself in the per-row-shift regime
+ *   (c2 = 0): the value the backward kernels seed their S accumulators with, negated.  No forward kernel is involved; o is untouched.
+ *   `p`, `seqs` (NULL: dense) and `window` (NULL: none) are those of the forward call; inv_l is laid out as that call wrote it ([B, H, N];
+ *   packed: [1, H, total_q]).  lse_out: float32 in ELEMENT strides, read as fcsa_lse_out describes ([b, h, i]; packed calls ignore stride0
+ *   and read [tok, h] at h * stride1 + tok * stride2).  A row without a visible key gets exactly -inf, decided from the geometry (k_len == 0
+ *   or an empty key span: every row; causal / windowed rows whose interval [i + (M - N) - left, i + (M - N) + right] misses [0, M)), never
+ *   from inv_l (which holds a finite number there).  Where the constant-shift clamp acts (row sum l < eps) the value is ln(max(l, eps)) +
+ *   shift: consistent with the o the forward returned (o * exp(lse) is the un-normalised sum) -- the decode LSE above is unclamped.
+ *   Accuracy: that of the row sum behind inv_l.  The 16-bit forwards add the P~ values ROUNDED to the type, so lse carries up to one unit
+ *   roundoff of it (2^-8 bfloat16, 2^-11 float16); float32 forwards give float32 accuracy.  A caller that needs more than the 16-bit
+ *   figure (l2norm_qk == 0, where q and k are exact operands, or |scale| * groups < 1/2) passes the inv_l of a float32 fcsa_forward on
+ *   the same values, with `p` of THAT call -- what the PyTorch binding does.
+ *   The forward must have run without mask and attn_bias (there is no argument for them here).  Launch: "state_lse".
+ * fcsa_backward_state: fcsa_backward (seqs, window NULL), fcsa_backward_varlen (seqs set) or fcsa_backward_window (window set) with a
+ *   gradient for the LSE: d_lse float32, laid out and indexed exactly as inv_l.  d lse_i / d s_ij = P_ij, so dS = P (dP - (delta_i -
+ *   d_lse_i)): the dQ kernel subtracts it from delta once per row and every gradient follows.  d_lse NULL: the corresponding entry point,
+ *   bit for bit.  Rows without a visible key take no gradient whatever their d_lse holds.  A non-finite d_lse is the caller's problem.
+ *   mask, attn_bias and d_bias must be NULL (FCSA_ERR_INVALID_ARG: a mask needs a per-batch emptiness rule for the LSE).  The workspace is
+ *   that of the corresponding entry point.  Launches: those of that entry point. */
+int    fcsa_attention_lse(const fcsa_problem* p, const float* inv_l, const fcsa_varlen* seqs, const fcsa_window* window,
+                          const fcsa_lse_out* lse_out, void* stream);
+int    fcsa_backward_state(const fcsa_backward_args* args, const fcsa_varlen* seqs, const fcsa_window* window, const float* d_lse);
+
+/* Backward of fcsa_merge_states.  With a_s = w_s / W:  d_o_in[s] = a_s * d_o (rounded once to `dtype`),
+ * d_lse_in[s] = a_s * (d_lse + <d_o, o_s> - sum_t a_t <d_o, o_t>) in float32.  d_lse.lse NULL: no gradient for the merged lse (0).
+ * A state of weight 0 gets d_o_in[s] = 0 and d_lse_in[s] = 0 exactly and its o_s is never read (a NaN-filled o_s cannot leak); when
+ * every state is empty everything is 0.  The dot products are reduced in float32 inside one wave, in a fixed order: deterministic.
+ * Sizes, strides and alignment as in fcsa_merge_args; entries beyond `states` are ignored.  Launch: "merge_states_bwd". */
+typedef struct fcsa_merge_backward_args {
+  int32_t      dtype;              /* fcsa_dtype of every o_in, of d_o and of every d_o_in */
+  int32_t      size0, size1, size2;
+  int32_t      dim_head;
+  int32_t      states;
+  fcsa_tensor  o_in[8];            /* the states the forward merged (borrowed) */
+  fcsa_lse_out lse_in[8];
+  fcsa_tensor  d_o;                /* gradient of the merged o */
+  fcsa_lse_out d_lse;              /* gradient of the merged lse, float32; lse NULL: zero */
+  fcsa_tensor  d_o_in[8];          /* out */
+  fcsa_lse_out d_lse_in[8];        /* out, float32 */
+  void*        stream;
+} fcsa_merge_backward_args;
+int    fcsa_merge_states_backward(const fcsa_merge_backward_args* args);
+
 /* Bytes of optional forward scratch that enable the split-key forward for this problem (0: never split). */
 size_t fcsa_forward_workspace_bytes(const fcsa_problem* p);
 
