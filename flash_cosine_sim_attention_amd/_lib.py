@@ -88,6 +88,8 @@ LseOut = _STRUCTS["fcsa_lse_out"]
 MergeArgs = _STRUCTS["fcsa_merge_args"]
 MERGE_MAX_STATES = _MACROS["FCSA_MERGE_MAX_STATES"]
 MergeBackwardArgs = _STRUCTS["fcsa_merge_backward_args"]
+KvCacheStep = _STRUCTS["fcsa_kvcache_step"]
+STEP_CHUNK_ROWS = _MACROS["FCSA_STEP_CHUNK_ROWS"]
 
 
 EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fcsa_forward_workspace_bytes", "fcsa_forward_needs_qn",
@@ -97,7 +99,8 @@ EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fc
            "fcsa_forward_kvcache_window", "fcsa_forward_kvcache_window_workspace_bytes", "fcsa_forward_kvcache_quant",
            "fcsa_forward_kvcache_quant_workspace_bytes", "fcsa_forward_kvcache_varlen", "fcsa_forward_kvcache_varlen_workspace_bytes",
            "fcsa_forward_kvcache_lse", "fcsa_merge_states", "fcsa_forward_kvcache_prefill",
-           "fcsa_attention_lse", "fcsa_backward_state", "fcsa_merge_states_backward")
+           "fcsa_attention_lse", "fcsa_backward_state", "fcsa_merge_states_backward",
+           "fcsa_forward_kvcache_step", "fcsa_forward_kvcache_step_workspace_bytes")
 
 _lib = None
 
@@ -199,6 +202,13 @@ def load():
         lib.fcsa_backward_state.restype = C.c_int
         lib.fcsa_merge_states_backward.argtypes = [C.POINTER(MergeBackwardArgs)]
         lib.fcsa_merge_states_backward.restype = C.c_int
+    if hasattr(lib, "fcsa_forward_kvcache_step"):      # (likewise: an FCSA_LIB build from before the engine step)
+        lib.fcsa_forward_kvcache_step.argtypes = [C.POINTER(ForwardArgs), C.POINTER(KvCache), C.POINTER(Varlen), C.POINTER(KvCacheQuant),
+                                                  C.POINTER(Window), C.POINTER(KvCacheStep), C.POINTER(LseOut)]
+        lib.fcsa_forward_kvcache_step.restype = C.c_int
+        lib.fcsa_forward_kvcache_step_workspace_bytes.argtypes = [C.POINTER(Problem), C.POINTER(KvCache), C.POINTER(Varlen),
+                                                                  C.POINTER(KvCacheQuant), C.POINTER(Window), C.POINTER(KvCacheStep)]
+        lib.fcsa_forward_kvcache_step_workspace_bytes.restype = C.c_size_t
     lib.fcsa_last_error.argtypes = []
     lib.fcsa_last_error.restype = C.c_char_p
     ver = lib.fcsa_debug(None, 0)

@@ -104,6 +104,12 @@ def _register_fakes():
           groups):
         return q.new_empty(q.shape), q.new_empty(q.shape[:-1], dtype=torch.float32)
 
+    # so does the engine step (fcsa_step)
+    @torch.library.register_fake("fcsa_step::kvcache_step_forward")
+    def _(q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, k_scale, v_scale, max_seqlen_q, max_seqlen_k, scale,
+          causal, l2norm_qk, groups, window_left, window_right, chunk_rows, max_decode_tokens, no_decode, no_chunk):
+        return q.new_empty(q.shape), q.new_empty(q.shape[:-1], dtype=torch.float32)
+
     @torch.library.register_fake("fcsa::merge_states")
     def _(os, lses):
         return os[0].new_empty(os[0].shape), os[0].new_empty(os[0].shape[:-1], dtype=torch.float32)

@@ -433,6 +433,7 @@ struct DecodeCall {
   const fcsa_kvcache_quant* qz;       // an fp8 cache (fcsa_forward_kvcache_quant), or NULL
   const fcsa_window* w;               // a sliding window as the caller gave it, or NULL
   const fcsa_lse_out* lse;            // where the combine also writes the rows' log-sum-exp (fcsa_forward_kvcache_lse), or NULL
+  const fcsa_kvcache_step* step = nullptr;      // an engine step (fcsa_forward_kvcache_step): the routing of a ragged step, or NULL
 };
 
 // The window of a decode call as the kernels take it.  A rectangular call is normalised (fcsa::win_normalise): a window that hides nothing
@@ -461,8 +462,10 @@ DecodeWindow decode_window(const fcsa_problem& p, const fcsa_kvcache& kv, bool r
 // flat slots over all sequences (sized from total_q, never from batch x max_seqlen_q) -- the split count of the key range over them
 // (fcsa::decode_splits) and the workspace: f32 partial P~V, then (row max, row sum), of every split of every row.  A pure function of the
 // shapes and the CU count, never of device table contents.  win_lo: DecodeWindow::reach().
+// decode_rows (an engine step): an upper bound on the packed rows the decode kernel is given, which sizes the split count in place of
+// total_q (< 0: total_q, the ragged call's plan); the slots and the workspace rows stay those of the full table.
 struct DecodePlan { int row_tiles; int64_t slots; int splits; size_t ws_ml, total; };
-DecodePlan decode_plan(const fcsa_problem& p, const fcsa_kvcache& kv, const fcsa_varlen* seqs, int win_lo) {
+DecodePlan decode_plan(const fcsa_problem& p, const fcsa_kvcache& kv, const fcsa_varlen* seqs, int win_lo, int64_t decode_rows = -1) {
   DecodePlan d;
   const int G = p.kv_heads > 0 ? p.heads / p.kv_heads : 0;
   const int max_k = fcsa::win_decode_keys(std::min(std::max(p.k_len, 0), std::max(kv.capacity, 0)), std::max(p.q_len, 0), win_lo);
@@ -471,7 +474,8 @@ DecodePlan decode_plan(const fcsa_problem& p, const fcsa_kvcache& kv, const fcsa
     const int64_t total_q = std::max<int64_t>(seqs->total_q, 0);
     d.row_tiles = 0;
     d.slots = fcsa::ragged_slots(total_q, std::max(p.batch, 0), G);
-    d.splits = fcsa::decode_splits(1, p.kv_heads, (int)std::min<int64_t>(d.slots, INT32_MAX), max_k, p.dim_head, fcsa::cu_count());
+    const int64_t split_slots = decode_rows < 0 ? d.slots : fcsa::ragged_slots(std::min(decode_rows, total_q), std::max(p.batch, 0), G);
+    d.splits = fcsa::decode_splits(1, p.kv_heads, (int)std::min<int64_t>(split_slots, INT32_MAX), max_k, p.dim_head, fcsa::cu_count());
     rows = (size_t)total_q * std::max(p.heads, 0);
   } else {
     d.row_tiles = std::max(fcsa::decode_row_tiles(G * p.q_len), 1);
@@ -692,9 +696,106 @@ int prefill_call(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_
   return timed("prefill", "prefill", s, [&] { return fcsa::launch_prefill(p.dtype, p.dim_head, dp, lse != nullptr ? &lo : nullptr, s); });
 }
 
+// An engine step (fcsa_forward_kvcache_step): the ragged step's description with the `step` part -- its checks, its window, its plan with the
+// split count sized by the decode-routed rows, its append; then the step decode and combine launches over the full table and the chunk
+// launch over 128-row slots, each skipped where the caller promises it has no work.  Where the chunk kernel is not compiled for the problem
+// the call is decode_call.
+bool step_has_chunk_kernel(const fcsa_problem& p) {
+  return (p.dtype == FCSA_F16 || p.dtype == FCSA_BF16) && (p.dim_head == 64 || p.dim_head == 128);
+}
+static_assert(fcsa::kStepChunkRows == FCSA_STEP_CHUNK_ROWS, "the default threshold of include/fcsa.h");
+int check_step(const fcsa_kvcache_step* st) {
+  if (st == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_step: null argument");
+  if ((st->no_decode != 0 && st->no_decode != 1) || (st->no_chunk != 0 && st->no_chunk != 1) || st->reserved != 0)
+    return fail(FCSA_ERR_INVALID_ARG, "kvcache_step: no_decode (%d) and no_chunk (%d) are flags (0 or 1) and reserved (%d) is 0", st->no_decode,
+                st->no_chunk, st->reserved);
+  if (st->max_decode_tokens > INT32_MAX) return fail(FCSA_ERR_INVALID_ARG, "kvcache_step: max_decode_tokens (%lld) above 2^31", (long long)st->max_decode_tokens);
+  return FCSA_OK;
+}
+// the decode-rows bound of the plan: nothing under no_decode, else the caller's bound or total_q
+int64_t step_decode_rows(const fcsa_kvcache_step& st, const fcsa_varlen& seqs) {
+  const int64_t total_q = std::max<int64_t>(seqs.total_q, 0);
+  if (st.no_decode) return 0;
+  return st.max_decode_tokens < 0 ? total_q : std::min<int64_t>(st.max_decode_tokens, total_q);
+}
+DecodePlan step_plan(const fcsa_problem& p, const fcsa_kvcache& kv, const fcsa_varlen& seqs, const fcsa_kvcache_step& st, int win_lo) {
+  DecodePlan d = decode_plan(p, kv, &seqs, win_lo, step_decode_rows(st, seqs));
+  if (st.no_decode) { d.splits = 1; d.ws_ml = 0; d.total = 0; }      // no decode launch: no partials
+  return d;
+}
+constexpr LaunchName kStepDecodeName[2] = {{"step_decode", "step decode"}, {"step_decode_fp8", "step decode (fp8)"}};
+constexpr LaunchName kStepCombineName[2][2] = {{{"step_combine", "step combine"}, {"step_combine_lse", "step combine (lse)"}},
+                                               {{"step_combine_fp8", "step combine (fp8)"}, {"step_combine_lse_fp8", "step combine (lse, fp8)"}}};
+
+int step_call(const DecodeCall& c) {
+  if (int rc = check_kvcache_varlen(c)) return rc;
+  if (int rc = check_step(c.step)) return rc;
+  const fcsa_forward_args* a = c.a;
+  const fcsa_kvcache* kv = c.kv;
+  const fcsa_problem& p = a->p;
+  const fcsa_kvcache_step& st = *c.step;
+  const bool rows = p.batch > 0 && p.heads > 0 && c.seqs->total_q > 0;
+  if (rows && c.lse != nullptr && c.lse->lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_step: lse: null pointer");
+  if (!step_has_chunk_kernel(p)) return decode_call({c.a, c.kv, c.seqs, c.qz, c.w, c.lse});
+  const bool fp8 = c.qz != nullptr;
+  const DecodeWindow win = decode_window(p, *kv, true, c.w);
+  const DecodePlan d = step_plan(p, *kv, *c.seqs, st, win.reach());
+  const int G = p.heads / p.kv_heads;
+  const int64_t chunk_slots = fcsa::prefill_slots(c.seqs->total_q, std::max(p.batch, 0), G, fcsa::kPrefillRows);
+  if (d.slots * std::max(p.kv_heads, 1) * d.splits > INT32_MAX || chunk_slots * std::max(p.kv_heads, 1) > INT32_MAX)
+    return fail(FCSA_ERR_UNSUPPORTED, "kvcache_step: grid above 2^31 workgroups");
+  if (p.batch == 0 || c.seqs->total_q == 0) return FCSA_OK;      // no packed row: nothing to append, nothing to write
+  if (rows && !st.no_decode) {
+    if (a->workspace == nullptr || a->workspace_bytes < d.total)
+      return fail(FCSA_ERR_WORKSPACE, "kvcache_step: workspace too small: %zu < %zu bytes", a->workspace_bytes, d.total);
+    if ((reinterpret_cast<uintptr_t>(a->workspace) & 255) != 0) return fail(FCSA_ERR_WORKSPACE, "kvcache_step: workspace not 256-byte aligned");
+  }
+  fcsa::DecodeStepParams sp{};
+  static_cast<fcsa::DecodeRaggedParams&>(sp) = decode_params(c, win, d);
+  sp.chunk_rows = st.chunk_rows < 0 ? fcsa::kStepChunkRows : st.chunk_rows;
+  const fcsa::DecodeLseOut lo = c.lse != nullptr ? fcsa::DecodeLseOut{c.lse->lse, 0, c.lse->stride1, c.lse->stride2} : fcsa::DecodeLseOut{};
+  const fcsa::DecodeLseOut* lop = c.lse != nullptr ? &lo : nullptr;
+  hipStream_t s = static_cast<hipStream_t>(a->stream);
+  // 1. the ragged call's append, once, with the base part of the block
+  if (kv->new_len > 0 && kv->capacity > 0) {
+    const LaunchName& n = kAppendName[1][fp8];
+    if (int rc = timed(n.name, n.what, s, [&] { return fcsa::launch_kv_append(p.dtype, p.dim_head, {fp8, true}, sp, s); })) return rc;
+  }
+  if (!rows) return FCSA_OK;
+  // 2. the decode-routed sequences: split partials and their combine over the slots and rows of the full table
+  if (!st.no_decode) {
+    const LaunchName& n = kStepDecodeName[fp8];
+    if (int rc = timed(n.name, n.what, s, [&] { return fcsa::launch_step_decode(p.dtype, p.dim_head, fp8, sp, s); })) return rc;
+    const LaunchName& m = kStepCombineName[fp8][c.lse != nullptr];
+    if (int rc = timed(m.name, m.what, s, [&] { return fcsa::launch_step_combine(p.dtype, p.dim_head, fp8, sp, lop, s); })) return rc;
+  }
+  // 3. the chunk-routed sequences: one launch, one split, no workspace
+  if (!st.no_chunk) {
+    fcsa::DecodeStepParams cp = sp;
+    cp.slots = (int)chunk_slots;
+    cp.splits = 1;
+    cp.ws_o = nullptr;
+    cp.ws_ml = nullptr;
+    if (int rc = timed("step_prefill", "step prefill", s, [&] { return fcsa::launch_step_prefill(p.dtype, p.dim_head, fp8, cp, lop, s); })) return rc;
+  }
+  return FCSA_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int fcsa_forward_kvcache_step(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_kvcache_quant* qz,
+                              const fcsa_window* w, const fcsa_kvcache_step* step, const fcsa_lse_out* lse) {
+  if (a == nullptr || kv == nullptr || seqs == nullptr || step == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_step: null argument");
+  return step_call({a, kv, seqs, qz, w, lse, step});
+}
+size_t fcsa_forward_kvcache_step_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_kvcache_quant*,
+                                                 const fcsa_window* w, const fcsa_kvcache_step* step) {
+  if (p == nullptr || kv == nullptr || seqs == nullptr || step == nullptr) return 0;
+  if (!step_has_chunk_kernel(*p)) return decode_workspace_bytes(p, kv, seqs, w);
+  return step_plan(*p, *kv, *seqs, *step, decode_window(*p, *kv, true, w).reach()).total;
+}
 
 int fcsa_forward_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv) { return decode_call({a, kv, nullptr, nullptr, nullptr, nullptr}); }
 size_t fcsa_forward_kvcache_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv) { return decode_workspace_bytes(p, kv, nullptr, nullptr); }

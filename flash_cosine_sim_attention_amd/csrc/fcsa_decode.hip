@@ -41,15 +41,6 @@ template <int D, int ES, bool GEN> struct DecodeLds {
   static constexpr int BYTES = VBYTES + NORM;
 };
 
-// eight e4m3fn codes (byte e of the pair = element e) -> their exact float32 values
-FCSA_DEV void unpack_fp8(const u32x2& u, float (&x)[8]) {
-#pragma unroll
-  for (int w = 0; w < 2; ++w) {
-    const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)u[w], false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)u[w], true);
-    x[4 * w] = a[0]; x[4 * w + 1] = a[1]; x[4 * w + 2] = b[0]; x[4 * w + 3] = b[1];
-  }
-}
-
 // Any group width (the GEN form: D = 96 with 48, 24, 12, 6 or 3 features per group, which straddle the lanes' fragments): each lane
 // writes its squares to row (lane & 15) of an LDS scratch, the four lanes of the row sum every fourth group, and each element reads its
 // group's sum back.  Same formula as group_normalise; only the order of the additions differs.
@@ -138,11 +129,14 @@ template <typename T, int D, bool FP8 = false> struct DecodeRegs {
 // RAGGED (decode_ragged_kernel, decode_ragged_fp8_kernel): a ragged step -- packed queries, sequence b with its own N_b rows.  The
 // workgroup is a (row-tile slot, K/V head, split); it finds its sequence and row tile in the table (ragged_tile: idle slots exit at once)
 // and from there on runs the code below with N = N_b.  Always WIN, with open sides when the call has no window.
-template <typename T, int D, bool DYN, bool GEN, bool WIN, bool FP8 = false, bool RAGGED = false>
-FCSA_DEV void decode_body(const std::conditional_t<RAGGED, DecodeRaggedParams,
-                                                   std::conditional_t<FP8, DecodeFp8Params, std::conditional_t<WIN, DecodeWinParams, DecodeParams>>>& p) {
+// STEP (step_decode_kernel, step_decode_fp8_kernel): the decode side of an engine step -- a ragged step whose workgroups leave the sequences
+// of step_is_chunk to the chunk kernel (fcsa_prefill.hip) and exit as soon as they know their sequence.
+template <typename T, int D, bool DYN, bool GEN, bool WIN, bool FP8 = false, bool RAGGED = false, bool STEP = false>
+FCSA_DEV void decode_body(const std::conditional_t<STEP, DecodeStepParams, std::conditional_t<RAGGED, DecodeRaggedParams,
+                                                   std::conditional_t<FP8, DecodeFp8Params, std::conditional_t<WIN, DecodeWinParams, DecodeParams>>>>& p) {
   static_assert(!FP8 || Traits<T>::ES == 2, "an fp8 cache is read with 16-bit queries");
   static_assert(!RAGGED || WIN, "the ragged entry points carry the window fields");
+  static_assert(!STEP || RAGGED, "a step is a ragged step");
   typedef DecodeRegs<T, D, FP8> R;
   typedef DecodeLds<D, R::ES, GEN> LP;
   constexpr int ES = R::ES, UE = R::UE, NJ = R::NJ, CPR = R::CPR, VCH = R::VCH;
@@ -160,6 +154,9 @@ FCSA_DEV void decode_body(const std::conditional_t<RAGGED, DecodeRaggedParams,
   if constexpr (RAGGED) {
     kvh = id % p.Hk;
     if (!ragged_tile(p.cu_q, p.B, p.total_q, p.G, id / p.Hk, b, rt, q0, N)) return;
+    if constexpr (STEP) {
+      if (step_is_chunk(p.G, N, p.chunk_rows)) return;
+    }
     new_len = p.append ? N : 0;
   } else {
     rt = id % p.row_tiles;
@@ -357,6 +354,15 @@ template <typename T, int D, bool DYN, bool GEN>
 __global__ __launch_bounds__(64) void decode_ragged_fp8_kernel(DecodeRaggedParams p) {
   decode_body<T, D, DYN, GEN, true, true, true>(p);
 }
+// the decode side of an engine step (launch_step_decode): 16-bit types and D = 64 / 128, where every group width is reduced in registers
+template <typename T, int D, bool DYN>
+__global__ __launch_bounds__(64) void step_decode_kernel(DecodeStepParams p) {
+  decode_body<T, D, DYN, false, true, false, true, true>(p);
+}
+template <typename T, int D, bool DYN>
+__global__ __launch_bounds__(64) void step_decode_fp8_kernel(DecodeStepParams p) {
+  decode_body<T, D, DYN, false, true, true, true, true>(p);
+}
 
 // The combine of one row's splits, shared by every combine entry point: o = sum_s 2^(m_s - M) P~V_s / sum_s 2^(m_s - M) l_s (static
 // regime: every m_s is the common shift, weight 1).
@@ -365,7 +371,9 @@ __global__ __launch_bounds__(64) void decode_ragged_fp8_kernel(DecodeRaggedParam
 // owning the row (ragged_seq_of).
 // LSE (decode_combine_lse*_kernel, fcsa_forward_kvcache_lse): the thread of the row's first four features also writes the row's
 // log-sum-exp, from M and the UNCLAMPED l (decode_row_lse).  The statements that make o are the same either way.
-template <typename T, int D, bool FP8, bool RAGGED, bool LSE, typename P>
+// STEP (step_combine[_lse]_kernel): the rows of the sequences of step_is_chunk are the chunk kernel's: their threads exit before they read
+// a partial (none was written).
+template <typename T, int D, bool FP8, bool RAGGED, bool LSE, bool STEP = false, typename P>
 FCSA_DEV void decode_combine_body(const P& p, const DecodeLseOut& lo) {
   constexpr int ES = Traits<T>::ES;
   constexpr int TPR = D / 4;                       // threads per row: four features each
@@ -376,6 +384,12 @@ FCSA_DEV void decode_combine_body(const P& p, const DecodeLseOut& lo) {
   const int64_t row = t / TPR;
   const int c = (int)(t % TPR);
   if (row >= rows) return;
+  if constexpr (STEP) {
+    const int64_t tok = row / p.H;
+    const int b = ragged_seq_of(p.cu_q, p.B, p.total_q, tok);
+    const int64_t q0 = ragged_cu(p.cu_q[b], p.total_q), q1 = max(ragged_cu(p.cu_q[b + 1], p.total_q), q0);      // ragged_tile's N_b
+    if (step_is_chunk(p.G, q1 - q0, p.chunk_rows)) return;
+  }
   float M = -INFINITY;
   for (int s = 0; s < p.splits; ++s) M = fmaxf(M, p.ws_ml[(s * rows + row) * 2]);
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -534,6 +548,16 @@ __global__ __launch_bounds__(256) void decode_combine_lse_ragged_kernel(DecodeRa
   decode_combine_body<T, D, FP8, true, true>(p, lo);
 }
 
+// the combine of an engine step's decode side (launch_step_combine)
+template <typename T, int D, bool FP8>
+__global__ __launch_bounds__(256) void step_combine_kernel(DecodeStepParams p) {
+  decode_combine_body<T, D, FP8, true, false, true>(p, DecodeLseOut{});
+}
+template <typename T, int D, bool FP8>
+__global__ __launch_bounds__(256) void step_combine_lse_kernel(DecodeStepParams p, DecodeLseOut lo) {
+  decode_combine_body<T, D, FP8, true, true, true>(p, lo);
+}
+
 // kv_append_kernel / kv_append_fp8_kernel for a ragged step: one thread per 16 bytes written of packed row `tok` of kn / vn ([total_q, Hk,
 // D]); the thread finds the row's sequence in the table and writes slot cache_seqlens[b] + (tok - cu_q[b])
 template <typename T, int D, bool FP8>
@@ -669,6 +693,60 @@ hipError_t launch_decode_combine(int dtype, int D, DecodeForm f, const DecodeRag
     if constexpr (RAGGED) return launch_part<decode_combine_ragged_kernel<T, DD, FP8>, 0>(grid, block, s, p);
     else if constexpr (FP8) return launch_part<decode_combine_fp8_kernel<T, DD>, 0>(grid, block, s, p);
     else return launch_part<decode_combine_kernel<T, DD>, 0>(grid, block, s, p);
+  });
+}
+
+// ---- an engine step (fcsa_forward_kvcache_step): the decode side, after the ragged call's append -------------------------------------
+namespace {
+// fn(T, std::integral_constant<int, D>) for the 16-bit types and D = 64 / 128: where the chunk kernel exists
+template <typename F> hipError_t dispatch_step(int dtype, int D, F&& fn) {
+  using D64 = std::integral_constant<int, 64>;
+  using D128 = std::integral_constant<int, 128>;
+  if (D != 64 && D != 128) return hipErrorInvalidValue;
+  if (dtype == FCSA_BF16) return D == 64 ? fn(BF16{}, D64{}) : fn(BF16{}, D128{});
+  if (dtype == FCSA_F16) return D == 64 ? fn(F16{}, D64{}) : fn(F16{}, D128{});
+  return hipErrorInvalidValue;
+}
+template <auto Kernel, int LDS, typename... More>
+hipError_t launch_step(dim3 grid, dim3 block, hipStream_t s, const DecodeStepParams& p, const More&... more) {
+  if constexpr (LDS > 0) {
+    return launch_with_lds<Kernel>(grid, block, LDS, s, p, more...);
+  } else {
+    hipLaunchKernelGGL(Kernel, grid, block, 0, s, p, more...);
+    return hipGetLastError();
+  }
+}
+}  // namespace
+
+// one single-wave workgroup per (flat slot of the FULL table, K/V head, key split): the slots of chunk sequences exit at once
+hipError_t launch_step_decode(int dtype, int D, bool fp8, const DecodeStepParams& p, hipStream_t s) {
+  return dispatch_step(dtype, D, [&](auto t, auto d) -> hipError_t {
+    using T = decltype(t);
+    constexpr int DD = decltype(d)::value;
+    if (p.l2norm && !decode_groups_fast(DD, p.groups, Unit<T>::UE)) return hipErrorInvalidValue;
+    const int64_t wgs = (int64_t)p.slots * p.Hk * p.splits;
+    if (wgs <= 0) return hipSuccess;
+    const dim3 grid((unsigned)wgs), block(64);
+    constexpr int LDS = DecodeLds<DD, 2, false>::BYTES;
+    if (fp8) return p.dyn ? launch_step<step_decode_fp8_kernel<T, DD, true>, LDS>(grid, block, s, p)
+                          : launch_step<step_decode_fp8_kernel<T, DD, false>, LDS>(grid, block, s, p);
+    return p.dyn ? launch_step<step_decode_kernel<T, DD, true>, LDS>(grid, block, s, p)
+                 : launch_step<step_decode_kernel<T, DD, false>, LDS>(grid, block, s, p);
+  });
+}
+
+// one thread per four features of a packed output row; the rows of chunk sequences exit at once
+hipError_t launch_step_combine(int dtype, int D, bool fp8, const DecodeStepParams& p, const DecodeLseOut* lse, hipStream_t s) {
+  return dispatch_step(dtype, D, [&](auto t, auto d) -> hipError_t {
+    using T = decltype(t);
+    constexpr int DD = decltype(d)::value;
+    const int64_t threads = (int64_t)p.total_q * p.H * (DD / 4);
+    if (threads <= 0 || p.B <= 0) return hipSuccess;
+    const dim3 grid((unsigned)blocks_of(threads)), block(256);
+    if (lse != nullptr) return fp8 ? launch_step<step_combine_lse_kernel<T, DD, true>, 0>(grid, block, s, p, *lse)
+                                   : launch_step<step_combine_lse_kernel<T, DD, false>, 0>(grid, block, s, p, *lse);
+    return fp8 ? launch_step<step_combine_kernel<T, DD, true>, 0>(grid, block, s, p)
+               : launch_step<step_combine_kernel<T, DD, false>, 0>(grid, block, s, p);
   });
 }
 

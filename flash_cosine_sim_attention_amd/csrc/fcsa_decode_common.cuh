@@ -1,6 +1,6 @@
 // fcsa_decode_common.cuh -- the device code shared by fcsa_decode.hip (the single-wave decode kernels) and fcsa_prefill.hip (the multi-wave
 // prefill kernel), whose results must agree bit for bit: what is here is written once and both call it (DESIGN.md 4.7.4 lists what is
-// still written in both).  A row in registers: Unit, unpack / pack, group_normalise.  Reading the cache: cache_base, clamped_first / clamped_off,
+// still written in both).  A row in registers: Unit, unpack / pack, unpack_fp8 (an e4m3fn cache), group_normalise.  Reading the cache: cache_base, clamped_first / clamped_off,
 // kKvPitch.  A 32-key block step: softmax_step, pv_block.  The end of a row: combine_weight, combine_inv.
 // Each translation unit gets its own internal copies (anonymous namespace).
 #pragma once
@@ -46,6 +46,15 @@ template <typename T> FCSA_DEV u32x4 pack(const float (&x)[Unit<T>::UE], float m
     for (int e = 0; e < 4; ++e) u[e] = Traits<T>::pack2(x[2 * e] * mul, x[2 * e + 1] * mul);
   }
   return u;
+}
+
+// eight e4m3fn codes (byte e of the pair = element e) -> their exact float32 values
+FCSA_DEV void unpack_fp8(const u32x2& u, float (&x)[8]) {
+#pragma unroll
+  for (int w = 0; w < 2; ++w) {
+    const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)u[w], false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)u[w], true);
+    x[4 * w] = a[0]; x[4 * w + 1] = a[1]; x[4 * w + 2] = b[0]; x[4 * w + 3] = b[1];
+  }
 }
 
 // Grouped l2norm of one row held by the four lanes x, x + 16, x + 32, x + 48 (x = lane & 15): x *= 1 / max(||group||, 1e-12), the l2norm

@@ -312,6 +312,24 @@ constexpr int prefill_kend(int L, int N, int G, int64_t first, int count, bool c
   if (!causal) return L;
   return (int)std::min<int64_t>(std::max<int64_t>((int64_t)L - N + last / G + 1, 0), L);
 }
+// Under a sliding window (the ragged kernel's sides: lo / hi keys left / right of a token's own position, kWinOpen for an open side, causal
+// as hi = 0) the same rows visit [prefill_kstart, prefill_win_kend).  The start is the first key the first token among the rows sees,
+// rounded down to a whole LDS stage, so the 32-key blocks a tile walks are the absolute ones the ragged kernel walks from win_decode_first
+// (a multiple of 32).  The end is prefill_kend's under an open or causal right side, and one past the last key the last token sees otherwise.
+constexpr int prefill_kstart(int L, int N, int G, int64_t first, int lo) {
+  if (lo >= kWinOpen) return 0;
+  return (int)(std::max<int64_t>((int64_t)L - N + first / G - lo, 0) / kPrefillStage * kPrefillStage);
+}
+constexpr int prefill_win_kend(int L, int N, int G, int64_t first, int count, int hi) {
+  if (hi >= kWinOpen || hi == 0) return prefill_kend(L, N, G, first, count, hi == 0);
+  const int64_t last = std::min(first + count, (int64_t)G * N) - 1;
+  if (last < first || L <= 0) return 0;
+  return (int)std::min<int64_t>(std::max<int64_t>((int64_t)L - N + last / G + hi + 1, 0), L);
+}
+// An engine step (fcsa_forward_kvcache_step): a sequence of N rows takes the chunk kernel iff G * N >= chunk_rows, the decode kernels
+// otherwise.  Both sides evaluate this one function on the N their tile maps give them (ragged_tile, prefill_tile: the same clamped entries).
+constexpr bool step_is_chunk(int G, int64_t N, int chunk_rows) { return (int64_t)G * N >= chunk_rows; }
+constexpr int kStepChunkRows = 1024;       // the default threshold: G * N_b of eight 128-row tiles (profiles/step_ab.txt)
 
 // ---- log-sum-exp of a decoded row, and merging attention states (fcsa_forward_kvcache_lse, fcsa_merge_states) --------------------------
 // The two functions below call expf / log / log2, which are no constant expressions: they are host functions for the C++ compiler

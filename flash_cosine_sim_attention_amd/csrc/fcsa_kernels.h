@@ -177,6 +177,18 @@ hipError_t launch_decode_combine(int dtype, int D, DecodeForm f, const DecodeRag
 // fcsa::prefill_slots(total_q, B, G, kPrefillRows), one split and no workspace; f16 / bf16, D = 64 / 128 (anything else: hipErrorInvalidValue).
 // One kernel writes o and, where lse is not nullptr, the rows' log-sum-exp.
 hipError_t launch_prefill(int dtype, int D, const DecodeRaggedParams& p, const DecodeLseOut* lse, hipStream_t s);
+// An engine step (fcsa_forward_kvcache_step): the ragged step's block plus the routing threshold.  Sequence b takes the chunk kernel
+// (step_prefill_kernel) iff G * N_b >= chunk_rows and the decode kernels (step_decode[_fp8]_kernel, step_combine[_lse]_kernel) otherwise;
+// all of them evaluate that on the device from the clamped table (ragged_cu), so every row is written by exactly one of them.
+struct DecodeStepParams : DecodeRaggedParams {   // step_decode[_fp8]_kernel, step_combine[_lse]_kernel, step_prefill_kernel
+  int chunk_rows = 0;
+};
+// The three launches of a step after the ragged call's append.  16-bit types and D = 64 / 128 only (anything else: hipErrorInvalidValue).
+// Decode and combine take the block as the ragged call fills it (slots = fcsa::ragged_slots); the chunk launch takes slots =
+// fcsa::prefill_slots(total_q, B, G, kPrefillRows) and writes o (and the lse) itself.  fp8: an e4m3fn cache.
+hipError_t launch_step_decode(int dtype, int D, bool fp8, const DecodeStepParams& p, hipStream_t s);
+hipError_t launch_step_combine(int dtype, int D, bool fp8, const DecodeStepParams& p, const DecodeLseOut* lse, hipStream_t s);
+hipError_t launch_step_prefill(int dtype, int D, bool fp8, const DecodeStepParams& p, const DecodeLseOut* lse, hipStream_t s);
 
 // Merging attention states (fcsa_merge_states, csrc/fcsa_merge.hip): S states (o_s, lse_s) of the rows [n0, n1, n2] -> (o, lse).  o views
 // carry BYTE strides, lse views ELEMENT strides.

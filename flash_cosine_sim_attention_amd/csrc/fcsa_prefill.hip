@@ -10,6 +10,12 @@
 //                    the lane, its mask and P~ pack, and the same functions of fcsa_decode_common.cuh: softmax_step, pv_block), and the
 //                    epilogue is decode_combine_body's (combine_weight, combine_inv) at one split, so o and lse are bit for bit those of
 //                    the ragged call with one key split.  Every K^ fragment and transposed V read from LDS feeds both row tiles of the wave.
+//   step_prefill_kernel  the chunk side of an engine step (fcsa_forward_kvcache_step): the same body (prefill_body)
+//                    with up to three additions.  STEP: a workgroup whose sequence is no chunk (step_is_chunk) exits -- those rows are the
+//                    step decode kernels'.  WIN: the ragged kernel's visibility test, and a key range that starts at the LDS stage holding the
+//                    first key the tile's first token sees (prefill_kstart).  FP8: an e4m3fn cache -- a lane loads 8 bytes per K and V fragment,
+//                    K becomes K^ exactly as decode_body<FP8> makes it, V's codes are converted to the type on the way into LDS, and the
+//                    epilogue multiplies by v_scale as decode_combine_body<FP8> does.
 // The append before it is the ragged call's (launch_kv_append with the same parameter block).  16-bit types, D = 64 / 128 only.
 #include "fcsa_common.cuh"
 #include "fcsa_decode_common.cuh"
@@ -33,9 +39,12 @@ template <int D> struct PrefillLds {
 };
 
 // A wave's 16 keys of a stage in registers: lane (x, hi) holds features (4 j + hi) * 8 ... + 7 of key `first16 + x` of K and of V
-template <typename T, int D> struct PrefillRegs {
+// FP8: the same features as one-byte codes (DecodeRegs<T, D, true>'s K layout, for K and V alike)
+template <typename T, int D, bool FP8 = false> struct PrefillRegs {
   static constexpr int NJ = D / 32;
-  u32x4 k[NJ], v[NJ];
+  static constexpr int CES = FP8 ? 1 : 2;                          // bytes of a cache element
+  typedef std::conditional_t<FP8, u32x2, u32x4> Frag;
+  Frag k[NJ], v[NJ];
 
   // the 16 positions from first16 of a sequence of L, under the load rule (clamped_first, clamped_off)
   FCSA_DEV void load(const DecodeParams& p, int b, int kvh, int first16, int L, int lane) {
@@ -47,21 +56,38 @@ template <typename T, int D> struct PrefillRegs {
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       const int f = (4 * j + hi) * 8;
-      k[j] = *reinterpret_cast<const u32x4*>(krow + f * 2);
-      const u32x4 val = *reinterpret_cast<const u32x4*>(vrow + f * 2);
-      v[j] = first16 + x < L ? val : u32x4{0u, 0u, 0u, 0u};
+      k[j] = *reinterpret_cast<const Frag*>(krow + f * CES);
+      const Frag val = *reinterpret_cast<const Frag*>(vrow + f * CES);
+      v[j] = first16 + x < L ? val : Frag{};
     }
   }
 
   // K^ (normalised and rounded as decode_body does before its first product) and raw V -> row `row` of a stage buffer
-  FCSA_DEV void store(char* buf, int row, int lane, bool l2norm, int gs) const {
+  // FP8: V's codes converted to T (exact); K's codes times kscale under l2norm (decode_body<FP8>: otherwise kscale is in the logit multiplier)
+  FCSA_DEV void store(char* buf, int row, int lane, bool l2norm, int gs, float kscale = 1.f) const {
     constexpr int PITCH = PrefillLds<D>::PITCH;
     const int hi = lane >> 4;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) *reinterpret_cast<u32x4*>(buf + PrefillLds<D>::TILE + row * PITCH + (4 * j + hi) * 16) = v[j];
     float xk[NJ][8];
+    if constexpr (FP8) {
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) unpack<T>(k[j], xk[j]);
+      for (int j = 0; j < NJ; ++j) {
+        float xv[8];
+        unpack_fp8(v[j], xv);
+        *reinterpret_cast<u32x4*>(buf + PrefillLds<D>::TILE + row * PITCH + (4 * j + hi) * 16) = pack<T>(xv, 1.f);
+        unpack_fp8(k[j], xk[j]);
+      }
+      if (l2norm) {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) xk[j][e] *= kscale;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) *reinterpret_cast<u32x4*>(buf + PrefillLds<D>::TILE + row * PITCH + (4 * j + hi) * 16) = v[j];
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) unpack<T>(k[j], xk[j]);
+    }
     if (l2norm) group_normalise<NJ, 8>(xk, gs, D);
 #pragma unroll
     for (int j = 0; j < NJ; ++j) *reinterpret_cast<u32x4*>(buf + row * PITCH + (4 * j + hi) * 16) = pack<T>(xk[j], 1.f);
@@ -73,10 +99,15 @@ template <typename T, int D> struct PrefillRegs {
 // per SIMD.
 template <typename T, int D> constexpr int kPrefillWavesPerSimd = (std::is_same_v<T, F16> && D == 128) ? 1 : 2;
 
-template <typename T, int D, bool DYN>
-__global__ __launch_bounds__(64 * kPrefillWaves, (kPrefillWavesPerSimd<T, D>)) void prefill_kernel(DecodeRaggedParams p, DecodeLseOut lo) {
+// ... and of the step forms (step_prefill_kernel): the plain and windowed forms as above (f16 D = 128: 257 - 260 registers); an fp8 cache's
+// key and value fragments are half as wide in registers, and every fp8 form stays below 256 (247 - 249 at D = 128, no scratch)
+template <typename T, int D, bool WIN, bool FP8> constexpr int kStepPrefillWavesPerSimd = FP8 ? 2 : kPrefillWavesPerSimd<T, D>;
+
+template <typename T, int D, bool DYN, bool STEP = false, bool WIN = false, bool FP8 = false>
+FCSA_DEV void prefill_body(const std::conditional_t<STEP, DecodeStepParams, DecodeRaggedParams>& p, const DecodeLseOut& lo) {
+  static_assert(STEP || (!WIN && !FP8), "windows and fp8 caches come with the step entry points");
   typedef PrefillLds<D> LP;
-  typedef PrefillRegs<T, D> R;
+  typedef PrefillRegs<T, D, FP8> R;
   constexpr int NJ = R::NJ, FB = D / 16, NT = kPrefillTiles;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -85,11 +116,22 @@ __global__ __launch_bounds__(64 * kPrefillWaves, (kPrefillWavesPerSimd<T, D>)) v
   const int kvh = blockIdx.x % p.Hk;
   int b, rt, q0, N;
   if (!prefill_tile(p.cu_q, p.B, p.total_q, p.G, kPrefillRows, blockIdx.x / p.Hk, b, rt, q0, N)) return;
+  if constexpr (STEP) {
+    if (!step_is_chunk(p.G, N, p.chunk_rows)) return;
+  }
   const int L = decode_len(p.seqlens != nullptr, p.seqlens != nullptr ? p.seqlens[b] : 0, p.append ? N : 0, p.capacity);
   const int64_t row0 = (int64_t)rt * kPrefillRows;
-  const int kend = prefill_kend(L, N, p.G, row0, kPrefillRows, p.causal != 0);
+  // the tile's keys [kstart, kend): kstart a whole number of stages (0 without a window)
+  int kstart = 0, kend, wave_kend;
   // a wave stops at the last key its own 32 rows see; it still loads its share of every stage and joins every barrier
-  const int wave_kend = prefill_kend(L, N, p.G, row0 + wave * (NT * kDecodeRows), NT * kDecodeRows, p.causal != 0);
+  if constexpr (WIN) {
+    kstart = prefill_kstart(L, N, p.G, row0, p.win_lo);
+    kend = prefill_win_kend(L, N, p.G, row0, kPrefillRows, p.win_hi);
+    wave_kend = prefill_win_kend(L, N, p.G, row0 + wave * (NT * kDecodeRows), NT * kDecodeRows, p.win_hi);
+  } else {
+    kend = prefill_kend(L, N, p.G, row0, kPrefillRows, p.causal != 0);
+    wave_kend = prefill_kend(L, N, p.G, row0 + wave * (NT * kDecodeRows), NT * kDecodeRows, p.causal != 0);
+  }
   const int gs = D / p.groups;
 
   // this lane's query rows, one per row tile: the column of every MFMA result
@@ -113,7 +155,12 @@ __global__ __launch_bounds__(64 * kPrefillWaves, (kPrefillWavesPerSimd<T, D>)) v
 #pragma unroll
     for (int j = 0; j < NJ; ++j) qf[t][j] = pack<T>(xq[j], p.l2norm ? p.c1 : 1.f);     // c1 * q^, one rounding
   }
-  const float smul = p.l2norm ? 1.f : p.c1;
+  float smul = p.l2norm ? 1.f : p.c1;
+  float kscale = 1.f;
+  if constexpr (FP8) {
+    kscale = p.k_scale[(int64_t)b * p.ks_b + (int64_t)kvh * p.ks_h];
+    if (!p.l2norm) smul *= kscale;
+  }
 
   f32x4 acc[NT][FB];
   float m[NT], l[NT];
@@ -125,22 +172,24 @@ __global__ __launch_bounds__(64 * kPrefillWaves, (kPrefillWavesPerSimd<T, D>)) v
     l[t] = 0.f;
   }
 
-  const int stages = (kend + kPrefillStage - 1) / kPrefillStage;
+  int stages = (kend + kPrefillStage - 1) / kPrefillStage;
+  if constexpr (WIN) stages = kend > kstart ? (kend - kstart + kPrefillStage - 1) / kPrefillStage : 0;
   const int my_row = wave * 16 + x;              // the stage row this lane loads
   R regs;
   if (stages > 0) {
-    regs.load(p, b, kvh, wave * 16, L, lane);
-    regs.store(smem, my_row, lane, p.l2norm != 0, gs);
+    regs.load(p, b, kvh, kstart + wave * 16, L, lane);
+    if constexpr (FP8) regs.store(smem, my_row, lane, p.l2norm != 0, gs, kscale);
+    else regs.store(smem, my_row, lane, p.l2norm != 0, gs);
   }
   __syncthreads();
   for (int st = 0; st < stages; ++st) {
     const bool more = st + 1 < stages;
-    if (more) regs.load(p, b, kvh, (st + 1) * kPrefillStage + wave * 16, L, lane);
+    if (more) regs.load(p, b, kvh, kstart + (st + 1) * kPrefillStage + wave * 16, L, lane);
     const char* ks = smem + (st & 1) * LP::BUF;
     const char* vs = ks + LP::TILE;
 #pragma unroll
     for (int blk = 0; blk < kPrefillStage / kDecodeBlock; ++blk) {
-      const int kb = st * kPrefillStage + blk * kDecodeBlock;
+      const int kb = kstart + st * kPrefillStage + blk * kDecodeBlock;
       if (kb >= wave_kend) break;
       // S^T = K^ Q^T for the two 16-key halves: s[t][sb][rr] = logit of key kb + 16 sb + 4 hi + rr for row x of tile t (log2 units)
       f32x4 s[NT][2];
@@ -163,7 +212,8 @@ __global__ __launch_bounds__(64 * kPrefillWaves, (kPrefillWavesPerSimd<T, D>)) v
 #pragma unroll
           for (int rr = 0; rr < 4; ++rr) {
             const int key = kb + 16 * sb + 4 * hi + rr;
-            const bool vis = key < L && (!p.causal || key <= last_key[t]);
+            bool vis = key < L && (!p.causal || key <= last_key[t]);
+            if constexpr (WIN) vis = key < L && key <= last_key[t] + p.win_hi && key >= last_key[t] - p.win_lo;
             s[t][sb][rr] = vis ? s[t][sb][rr] * smul : -INFINITY;
           }
         f32x4 pr[2];
@@ -177,7 +227,11 @@ __global__ __launch_bounds__(64 * kPrefillWaves, (kPrefillWavesPerSimd<T, D>)) v
       pv_block<T, D, NT>(vs, blk * kDecodeBlock, x, hi, pb, acc);
     }
     // the other buffer was last read before the barrier that ended the previous iteration
-    if (more) regs.store(smem + ((st + 1) & 1) * LP::BUF, my_row, lane, p.l2norm != 0, gs);
+    if constexpr (FP8) {
+      if (more) regs.store(smem + ((st + 1) & 1) * LP::BUF, my_row, lane, p.l2norm != 0, gs, kscale);
+    } else {
+      if (more) regs.store(smem + ((st + 1) & 1) * LP::BUF, my_row, lane, p.l2norm != 0, gs);
+    }
     __syncthreads();
   }
 
@@ -198,7 +252,8 @@ __global__ __launch_bounds__(64 * kPrefillWaves, (kPrefillWavesPerSimd<T, D>)) v
     const float w = combine_weight(M, M);      // the one split's weight: 1
     float lsum = 0.f;
     if (any) lsum += w * ls;
-    const float inv = combine_inv(p.dyn != 0, lsum, p.l_eps);
+    float inv = combine_inv(p.dyn != 0, lsum, p.l_eps);
+    if constexpr (FP8) inv = inv * p.v_scale[(int64_t)b * p.vs_b + (int64_t)kvh * p.vs_h];      // decode_combine_body<FP8>: acc *= inv * v_scale
     char* dst = p.o.p + (int64_t)h * p.o.sh + tok * p.o.sn + 4 * hie * 2;
 #pragma unroll
     for (int fb = 0; fb < FB; ++fb) {
@@ -209,6 +264,19 @@ __global__ __launch_bounds__(64 * kPrefillWaves, (kPrefillWavesPerSimd<T, D>)) v
     }
     if (lo.lse != nullptr && hie == 0) lo.lse[(int64_t)h * lo.sh + tok * lo.sn] = decode_row_lse(M, lsum);
   }
+}
+
+template <typename T, int D, bool DYN>
+__global__ __launch_bounds__(64 * kPrefillWaves, (kPrefillWavesPerSimd<T, D>)) void prefill_kernel(DecodeRaggedParams p, DecodeLseOut lo) {
+  prefill_body<T, D, DYN>(p, lo);
+}
+
+// The chunk side of an engine step: entry points of their own, so that prefill_kernel's instantiations are what they were.  Un-windowed
+// calls on 16-bit caches take the plain form (WIN = false: prefill_kernel's code behind the routing test); an fp8 cache always takes the
+// windowed form, with open sides when the call has no window, as the ragged kernel does.
+template <typename T, int D, bool DYN, bool WIN, bool FP8>
+__global__ __launch_bounds__(64 * kPrefillWaves, (kStepPrefillWavesPerSimd<T, D, WIN, FP8>)) void step_prefill_kernel(DecodeStepParams p, DecodeLseOut lo) {
+  prefill_body<T, D, DYN, true, WIN, FP8>(p, lo);
 }
 
 }  // namespace
@@ -226,6 +294,34 @@ hipError_t launch_prefill(int dtype, int D, const DecodeRaggedParams& p, const D
     constexpr int DD = decltype(d)::value;
     return p.dyn ? launch_with_lds<prefill_kernel<T, DD, true>>(grid, block, PrefillLds<DD>::BYTES, s, p, lo)
                  : launch_with_lds<prefill_kernel<T, DD, false>>(grid, block, PrefillLds<DD>::BYTES, s, p, lo);
+  };
+  using D64 = std::integral_constant<int, 64>;
+  using D128 = std::integral_constant<int, 128>;
+  if (dtype == FCSA_BF16) return D == 64 ? go(BF16{}, D64{}) : go(BF16{}, D128{});
+  return D == 64 ? go(F16{}, D64{}) : go(F16{}, D128{});
+}
+
+// the chunk side of an engine step: p.slots = fcsa::prefill_slots(total_q, B, G, kPrefillRows); the workgroups of decode sequences exit at once
+hipError_t launch_step_prefill(int dtype, int D, bool fp8, const DecodeStepParams& p, const DecodeLseOut* lse, hipStream_t s) {
+  if (dtype != FCSA_F16 && dtype != FCSA_BF16) return hipErrorInvalidValue;
+  if (D != 64 && D != 128) return hipErrorInvalidValue;
+  if (p.l2norm && !decode_groups_fast(D, p.groups, 8)) return hipErrorInvalidValue;
+  if ((int64_t)p.slots * p.Hk <= 0) return hipSuccess;
+  const dim3 grid((unsigned)((int64_t)p.slots * p.Hk)), block(64 * kPrefillWaves);
+  const DecodeLseOut lo = lse != nullptr ? *lse : DecodeLseOut{};
+  // the window test is needed when a side is bounded on the left or strictly inside on the right (open and causal sides are prefill_kernel's)
+  const bool win = p.win_lo < kWinOpen || (p.win_hi < kWinOpen && !(p.causal && p.win_hi == 0));
+  auto go = [&](auto t, auto d) -> hipError_t {
+    using T = decltype(t);
+    constexpr int DD = decltype(d)::value;
+    constexpr int LDS = PrefillLds<DD>::BYTES;
+    auto form = [&](auto dyn) -> hipError_t {
+      constexpr bool DY = decltype(dyn)::value;
+      if (fp8) return launch_with_lds<step_prefill_kernel<T, DD, DY, true, true>>(grid, block, LDS, s, p, lo);
+      if (win) return launch_with_lds<step_prefill_kernel<T, DD, DY, true, false>>(grid, block, LDS, s, p, lo);
+      return launch_with_lds<step_prefill_kernel<T, DD, DY, false, false>>(grid, block, LDS, s, p, lo);
+    };
+    return p.dyn ? form(std::true_type{}) : form(std::false_type{});
   };
   using D64 = std::integral_constant<int, 64>;
   using D128 = std::integral_constant<int, 128>;

@@ -66,7 +66,10 @@ namespace {
   /* attention states for training: the forward's log-sum-exp, its gradient, the merge's backward */ \
   X(attention_lse, fcsa_attention_lse, false)                                             \
   X(backward_state, fcsa_backward_state, false)                                           \
-  X(merge_states_backward, fcsa_merge_states_backward, false)
+  X(merge_states_backward, fcsa_merge_states_backward, false)                             \
+  /* the engine step: chunks and decodes routed in one call */                            \
+  X(forward_kvcache_step, fcsa_forward_kvcache_step, false)                               \
+  X(forward_kvcache_step_ws, fcsa_forward_kvcache_step_workspace_bytes, false)
 
 struct Abi {
 #define X(member, symbol, required) decltype(&symbol) member = &symbol;
@@ -721,8 +724,11 @@ Tensor varlen_window_attention_autograd(const Tensor& q, const Tensor& k, const 
 Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const optional<Tensor>& k_new, const optional<Tensor>& v_new,
                             const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table, int64_t max_seqlen_k, double scale, bool causal,
                             bool l2norm_qk, int64_t groups, const fcsa_window* win, const Tensor* k_scale = nullptr, const Tensor* v_scale = nullptr,
-                            const Tensor* cu_q = nullptr, int64_t max_seqlen_q = 0, Tensor* lse_out = nullptr, bool prefill = false) {
+                            const Tensor* cu_q = nullptr, int64_t max_seqlen_q = 0, Tensor* lse_out = nullptr, bool prefill = false,
+                            const fcsa_kvcache_step* step = nullptr) {
   const bool ragged = cu_q != nullptr;
+  if (step != nullptr)      // kvcache_step_forward: a ragged step through fcsa_forward_kvcache_step (its own workspace; the lse always)
+    need_abi("flash_cosine_sim_attention_step_with_kvcache", "fcsa_forward_kvcache_step", g_abi.forward_kvcache_step, g_abi.forward_kvcache_step_ws);
   if (prefill)      // kvcache_prefill_forward: a ragged step through fcsa_forward_kvcache_prefill (no workspace; the lse always)
     need_abi("flash_cosine_sim_attention_prefill_with_kvcache", "fcsa_forward_kvcache_prefill", g_abi.forward_kvcache_prefill);
   const Layout ql = ragged ? kPacked : kDense;      // of q, o, k_new, v_new and the lse
@@ -869,6 +875,7 @@ Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor
     qz.v_scale = vs.data_ptr<float>();
   }
   const size_t wsb = prefill ? 0
+                     : step != nullptr ? g_abi.forward_kvcache_step_ws(&a.p, &kv, &seqs, fp8 ? &qz : nullptr, win, step)
                      : ragged ? g_abi.forward_kvcache_varlen_ws(&a.p, &kv, &seqs, fp8 ? &qz : nullptr, win)
                      : fp8 ? g_abi.forward_kvcache_quant_ws(&a.p, &kv, &qz, win)
                          : win != nullptr ? g_abi.forward_kvcache_window_ws(&a.p, &kv, win) : g_abi.forward_kvcache_ws(&a.p, &kv);
@@ -885,6 +892,10 @@ Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor
     const fcsa_lse_out lo = strided<fcsa_lse_out>(*lse_out, ql);
     if (prefill) {
       check(g_abi.forward_kvcache_prefill(&a, &kv, &seqs, &lo), "fcsa_forward_kvcache_prefill");
+      return o;
+    }
+    if (step != nullptr) {
+      check(g_abi.forward_kvcache_step(&a, &kv, &seqs, fp8 ? &qz : nullptr, win, step, &lo), "fcsa_forward_kvcache_step");
       return o;
     }
     check(g_abi.forward_kvcache_lse(&a, &kv, ragged ? &seqs : nullptr, fp8 ? &qz : nullptr, win, &lo), "fcsa_forward_kvcache_lse");
@@ -958,6 +969,33 @@ std::tuple<Tensor, Tensor> kvcache_prefill_forward(const Tensor& q, const Tensor
   Tensor lse;
   Tensor o = kvcache_forward_impl(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups,
                                   nullptr, nullptr, nullptr, &cu_seqlens_q, max_seqlen_q, &lse, true);
+  return {o, lse};
+}
+
+// An engine step: kvcache_lse_forward's ragged step with the routing fields of fcsa_kvcache_step (chunk_rows / max_decode_tokens < 0: the
+// library's default / total_q; no_decode, no_chunk: the caller's promises, which skip a launch).
+std::tuple<Tensor, Tensor> kvcache_step_forward(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& cu_seqlens_q,
+                                                const optional<Tensor>& k_new, const optional<Tensor>& v_new, const optional<Tensor>& cache_seqlens,
+                                                const optional<Tensor>& block_table, const optional<Tensor>& k_scale, const optional<Tensor>& v_scale,
+                                                int64_t max_seqlen_q, int64_t max_seqlen_k, double scale, bool causal, bool l2norm_qk, int64_t groups,
+                                                int64_t left, int64_t right, int64_t chunk_rows, int64_t max_decode_tokens, bool no_decode,
+                                                bool no_chunk) {
+  TORCH_CHECK_VALUE(k_scale.has_value() == v_scale.has_value(), "k_scale and v_scale must be given together");
+  TORCH_CHECK_VALUE(chunk_rows >= -1, "chunk_rows must be a non-negative integer (or -1: the default), got ", chunk_rows);
+  TORCH_CHECK_VALUE(max_decode_tokens >= -1, "max_decode_tokens must be a non-negative integer (or -1: total_q), got ", max_decode_tokens);
+  const bool windowed = !(left == -1 && right == -1);
+  fcsa_window w;
+  if (windowed) w = Win(left, right).w;
+  fcsa_kvcache_step st;
+  std::memset(&st, 0, sizeof(st));
+  st.chunk_rows = (int32_t)std::min<int64_t>(chunk_rows, INT32_MAX);
+  st.max_decode_tokens = std::min<int64_t>(max_decode_tokens, INT32_MAX);
+  st.no_decode = no_decode;
+  st.no_chunk = no_chunk;
+  Tensor lse;
+  Tensor o = kvcache_forward_impl(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups,
+                                  windowed ? &w : nullptr, k_scale.has_value() ? &*k_scale : nullptr, v_scale.has_value() ? &*v_scale : nullptr,
+                                  &cu_seqlens_q, max_seqlen_q, &lse, false, &st);
   return {o, lse};
 }
 
@@ -1320,6 +1358,15 @@ TORCH_LIBRARY(fcsa_prefill, m) {
         "int groups) -> (Tensor, Tensor)");
 }
 TORCH_LIBRARY_IMPL(fcsa_prefill, CUDA, m) { m.impl("kvcache_prefill_forward", &kvcache_prefill_forward); }
+
+// The engine step, likewise in a namespace of its own.  Forward only: no Autograd kernel.
+TORCH_LIBRARY(fcsa_step, m) {
+  m.def("kvcache_step_forward(Tensor q, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor cu_seqlens_q, Tensor? k_new, Tensor? v_new, "
+        "Tensor? cache_seqlens, Tensor? block_table, Tensor? k_scale, Tensor? v_scale, int max_seqlen_q, int max_seqlen_k, float scale, "
+        "bool causal, bool l2norm_qk, int groups, int window_left, int window_right, int chunk_rows, int max_decode_tokens, bool no_decode, "
+        "bool no_chunk) -> (Tensor, Tensor)");
+}
+TORCH_LIBRARY_IMPL(fcsa_step, CUDA, m) { m.impl("kvcache_step_forward", &kvcache_step_forward); }
 
 // Attention states for training, in a namespace of their own (the op set of `fcsa` is pinned): the attention op with the rows'
 // log-sum-exp as a second differentiable result -- dense, local (window sides other than (-1, -1)) or packed (cu_seqlens given) -- and

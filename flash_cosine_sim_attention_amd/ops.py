@@ -21,6 +21,7 @@ from __future__ import annotations
 import torch
 from torch.autograd import Function
 
+from . import _lib
 from . import _torch_ops
 from . import cpu as _cpu
 
@@ -598,6 +599,70 @@ def flash_cosine_sim_attention_prefill_with_kvcache(q, k_cache, v_cache, cu_seql
     _torch_ops.load()
     o, lse = torch.ops.fcsa_prefill.kvcache_prefill_forward(q, k_cache, v_cache, cu_q, k_new, v_new, cache_seqlens, block_table, max_q, c.max_k,
                                                             float(scale), bool(causal), bool(l2norm_qk), int(groups))
+    return (o, lse) if return_lse else o
+
+
+def _step_count(name, value):
+    """chunk_rows / max_decode_tokens: None or a non-negative integer"""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, int):
+        raise TypeError(f"{name} must be None or a non-negative integer, got {value!r}")
+    if value < 0:
+        raise ValueError(f"{name} must be None or a non-negative integer, got {value}")
+    return value
+
+
+def flash_cosine_sim_attention_step_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new=None, v_new=None, cache_seqlens=None,
+                                                 block_table=None, max_seqlen_q=None, max_seqlen_k=None, scale=8, groups=1, causal=False,
+                                                 l2norm_qk=True, k_scale=None, v_scale=None, return_lse=False, window_size=(-1, -1),
+                                                 chunk_rows=None, max_decode_tokens=None):
+    """The step of a continuous-batching engine against the key/value cache, in one call: a packed batch where most sequences bring one
+    token, some a few and one or two a prompt chunk, each sequence sent to the kernel built for its row count.
+
+    The two single-kernel calls are `flash_cosine_sim_attention_varlen_with_kvcache` (the ragged decode kernel: one wave per 16 rows, key
+    splits) and `flash_cosine_sim_attention_prefill_with_kvcache` (the chunk kernel: 128 rows per workgroup, keys normalised once, no
+    splits); each of them runs the whole batch on its one kernel.  This call takes the ragged call's arguments and returns the ragged call's
+    result, and appends k_new / v_new once.
+    Routing rule: sequence b, with N_b packed rows and G = H / Hk, takes the chunk kernel iff G * N_b >= chunk_rows and the decode kernel
+    (with key splits) otherwise.  chunk_rows=None is the library default (1024: eight 128-row tiles); 0 sends every sequence to the chunk
+    kernel, a value above G * total_q every sequence to the decode kernel.  Both kernels evaluate the rule on the device from the clamped
+    table, so every row is written exactly once whatever a device table holds.
+    Everything else -- arguments and layouts (contiguous or paged), float8_e4m3fn caches with k_scale / v_scale, window_size, the append,
+    the per-sequence bottom-right causal alignment, o = 0 and lse = -inf for rows without a visible key, N_b = 0, host tables validated and
+    device tables trusted and clamped, no synchronisation with device tables (so a step can be captured in a HIP graph), return_lse -- is
+    as in `flash_cosine_sim_attention_varlen_with_kvcache`.  o, lse and both caches are that call's: a chunk-routed sequence's rows are bit
+    for bit its rows at one key split, a decode-routed sequence's rows bit for bit its rows at this call's split count.
+    max_decode_tokens: an upper bound on the packed rows of all decode-routed sequences (default total_q).  Like max_seqlen_q / max_seqlen_k
+    it only sizes the split count: a wrong bound changes speed, never the result.  With a host cu_seqlens_q it is not needed: the count is
+    taken from the table, and a launch that would find no sequence is skipped.  With a device table both launches always run.
+    float32 tensors and head dimensions other than 64 and 128 have no chunk kernel: there this call is the ragged call (chunk_rows and
+    max_decode_tokens are checked and otherwise ignored).  CPU tensors take the forward-only path of `cpu.py`.  Forward only."""
+    fn = "flash_cosine_sim_attention_step_with_kvcache"
+    _check_return_lse(return_lse)
+    window = _window(window_size)
+    chunk_rows = _step_count("chunk_rows", chunk_rows)
+    max_decode_tokens = _step_count("max_decode_tokens", max_decode_tokens)
+    c, cpu_result, cu_q, max_q = _ragged_step(fn, q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q,
+                                              max_seqlen_k, k_scale, v_scale, window,
+                                              dict(scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, return_lse=bool(return_lse)))
+    if q.device.type == "cpu":
+        return cpu_result
+    total_q, H = q.shape[:2]
+    if total_q == 0:      # nothing to append, nothing to write: no launch
+        o = q.new_empty(q.shape)
+        return (o, q.new_empty((0, H), dtype=torch.float32)) if return_lse else o
+    threshold = _lib.STEP_CHUNK_ROWS if chunk_rows is None else min(chunk_rows, 2 ** 31 - 1)
+    bound, no_decode, no_chunk = (-1 if max_decode_tokens is None else min(max_decode_tokens, total_q)), False, False
+    if c.counts is not None:      # a host table: the decode-routed rows exactly, and which launch would find no sequence
+        G = H // c.Hk
+        decode = [n for n in c.counts if n > 0 and G * n < threshold]
+        bound, no_decode, no_chunk = sum(decode), not decode, len(decode) == sum(1 for n in c.counts if n > 0)
+    k_cache, v_cache, cache_seqlens, block_table = c.on_device()
+    _torch_ops.load()
+    o, lse = torch.ops.fcsa_step.kvcache_step_forward(q, k_cache, v_cache, cu_q, k_new, v_new, cache_seqlens, block_table, c.k_scale, c.v_scale,
+                                                      max_q, c.max_k, float(scale), bool(causal), bool(l2norm_qk), int(groups), window[0], window[1],
+                                                      threshold, bound, no_decode, no_chunk)
     return (o, lse) if return_lse else o
 
 

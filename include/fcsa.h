@@ -375,6 +375,44 @@ int    fcsa_forward_kvcache_lse(const fcsa_forward_args* args, const fcsa_kvcach
 int    fcsa_forward_kvcache_prefill(const fcsa_forward_args* args, const fcsa_kvcache* cache, const fcsa_varlen* seqs,
                                     const fcsa_lse_out* lse_out);
 
+/* An engine step: fcsa_forward_kvcache_varlen / _lse with every sequence of the packed batch sent to the kernel built for its row count,
+ * in one call with one append.  Sequence b (N_b packed rows, G = heads / kv_heads) takes the chunk kernel of fcsa_forward_kvcache_prefill
+ * iff G * N_b >= chunk_rows, and the ragged decode kernel with key splits otherwise.  Both kernels evaluate that test on the device from the
+ * clamped table entries, so every row is written exactly once whatever the table holds.
+ * args, cache, seqs, quant and window are read exactly as fcsa_forward_kvcache_varlen reads them and its checks apply (additive: no
+ * existing struct changes and FCSA_ABI_VERSION stays 4); lse_out: NULL, or as in fcsa_forward_kvcache_lse for a ragged call.  The chunk
+ * kernel of a step takes fp8 caches and windows too.
+ * Result: o, lse and the caches are those of fcsa_forward_kvcache_varlen on the same arguments; a chunk-routed sequence's rows are bit for
+ * bit that call's rows at ONE key split, a decode-routed sequence's rows bit for bit that call's rows at the step's split count.
+ *   chunk_rows        : the threshold; < 0: the library default, FCSA_STEP_CHUNK_ROWS.  0 sends every sequence to the chunk kernel, a value above
+ *                       G * total_q every sequence to the decode kernel.
+ *   max_decode_tokens : an upper bound on the packed rows of all decode-routed sequences; < 0: total_q.  Like p.q_len / p.k_len it only
+ *                       sizes the split count: a wrong bound changes speed, never the result.
+ *   no_decode, no_chunk: promises of a caller who knows the table -- "no sequence is decode-routed", "no sequence is chunk-routed".  The
+ *                       launches that would find no work are skipped (and with no_decode the call needs no workspace).  A promise is
+ *                       TRUSTED, like a device table: a false one leaves the rows of the skipped route unwritten; nothing is ever
+ *                       accessed out of bounds.  0 / 0 is always right.
+ * workspace: >= fcsa_forward_kvcache_step_workspace_bytes() bytes for the same arguments, 256-byte aligned: the split partials over
+ * total_q * H rows at the step's split count -- a function of shapes and the bound, never of table contents.
+ * Where the chunk kernel does not exist for the problem (FCSA_F32, or dim_head other than 64 and 128) the call IS
+ * fcsa_forward_kvcache_varlen / _lse: the same launches and workspace; `step` is checked and otherwise ignored.
+ * Launches: "kv_append_ragged[_fp8]" (when appending; the ragged call's launch, unchanged), "step_decode[_fp8]",
+ * "step_combine[_lse][_fp8]" (both skipped under no_decode), "step_prefill" (skipped under no_chunk). */
+#define FCSA_STEP_CHUNK_ROWS 1024
+typedef struct fcsa_kvcache_step {
+  int32_t chunk_rows;
+  int32_t no_decode;
+  int64_t max_decode_tokens;
+  int32_t no_chunk;
+  int32_t reserved;          /* 0 */
+} fcsa_kvcache_step;
+int    fcsa_forward_kvcache_step(const fcsa_forward_args* args, const fcsa_kvcache* cache, const fcsa_varlen* seqs,
+                                 const fcsa_kvcache_quant* quant, const fcsa_window* window, const fcsa_kvcache_step* step,
+                                 const fcsa_lse_out* lse_out);
+size_t fcsa_forward_kvcache_step_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* cache, const fcsa_varlen* seqs,
+                                                 const fcsa_kvcache_quant* quant, const fcsa_window* window,
+                                                 const fcsa_kvcache_step* step);
+
 /* Merging attention states: `states` pairs (o_s, lse_s) over disjoint key sets of the same queries -> the pair over the union.
  * Per row, in float32:  M = max_s lse_s;  M == -inf: o = 0, lse = -inf;  else w_s = exp(lse_s - M), W = sum_s w_s,
  * o = (sum_s w_s * o_s) / W rounded once to `dtype`, lse = M + log(W).  A state with lse_s == -inf (or one whose weight underflows to 0)
