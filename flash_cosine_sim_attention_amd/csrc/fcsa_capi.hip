@@ -578,15 +578,16 @@ constexpr LaunchName kCombineName[2][2][2] = {
      {{"decode_combine_ragged_fp8", "decode combine (ragged)"}, {"decode_combine_lse_ragged_fp8", "decode combine (lse, ragged)"}}}};
 
 // One fill of the most derived block: every kernel gets the part it takes (fcsa_kernels.h).  A ragged step has packed q / o / k_new /
-// v_new views, per-sequence row counts in place of N / row_tiles / new_len, and an lse view without a batch stride.
-fcsa::DecodeRaggedParams decode_params(const DecodeCall& c, const DecodeWindow& win, const DecodePlan& d) {
+// v_new views, per-sequence row counts in place of N / row_tiles / new_len, and an lse view without a batch stride.  chunk_rows stays 0:
+// the routing threshold is the engine step's to set.
+fcsa::DecodeStepParams decode_params(const DecodeCall& c, const DecodeWindow& win, const DecodePlan& d) {
   const bool ragged = c.seqs != nullptr, fp8 = c.qz != nullptr;
   const fcsa_forward_args* a = c.a;
   const fcsa_kvcache* kv = c.kv;
   const fcsa_problem& p = a->p;
   const int es = elem_size(p.dtype), ces = fp8 ? 1 : es;
   auto rows_view = [&](const fcsa_tensor& t) { return view(ragged ? packed(t) : t, es); };
-  fcsa::DecodeRaggedParams dp{};
+  fcsa::DecodeStepParams dp{};
   dp.q = rows_view(a->q);
   dp.o = rows_view(a->o);
   dp.kc = view(kv->k_cache, ces);
@@ -624,6 +625,38 @@ fcsa::DecodeRaggedParams decode_params(const DecodeCall& c, const DecodeWindow& 
   return dp;
 }
 
+// ---- what the three call functions below (decode_call, prefill_call, step_call) do in the same words ---------------------------------
+// the rows' log-sum-exp as the kernels take it; packed: [tok, h] rows, no batch stride
+fcsa::DecodeLseOut lse_view(const fcsa_lse_out& l, bool packed = false) { return {l.lse, packed ? 0 : l.stride0, l.stride1, l.stride2}; }
+
+// where the chunk kernel (fcsa_prefill.hip) and the step kernels exist: the 16-bit types at dim_head 64 / 128
+bool has_chunk_kernel(const fcsa_problem& p) { return p.dtype != FCSA_F32 && (p.dim_head == 64 || p.dim_head == 128); }
+
+// the workspace of the split partials: d.total bytes, 256-byte aligned
+int check_workspace(const char* who, const fcsa_forward_args& a, const DecodePlan& d) {
+  if (a.workspace == nullptr || a.workspace_bytes < d.total)
+    return fail(FCSA_ERR_WORKSPACE, "%s: workspace too small: %zu < %zu bytes", who, a.workspace_bytes, d.total);
+  if ((reinterpret_cast<uintptr_t>(a.workspace) & 255) != 0) return fail(FCSA_ERR_WORKSPACE, "%s: workspace not 256-byte aligned", who);
+  return FCSA_OK;
+}
+
+// the append (before anything reads the cache: same stream), where the call brings rows and the cache has room for any
+int append_launch(const DecodeCall& c, fcsa::DecodeForm form, const fcsa::DecodeStepParams& dp, hipStream_t s) {
+  if (c.kv->new_len <= 0 || c.kv->capacity <= 0) return FCSA_OK;
+  const LaunchName& n = kAppendName[form.ragged][form.fp8];
+  return timed(n.name, n.what, s, [&] { return fcsa::launch_kv_append(c.a->p.dtype, c.a->p.dim_head, form, dp, s); });
+}
+
+// the chunk launch: the call's block with 128-row slots, one split and no workspace
+int chunk_launch(const LaunchName& n, const DecodeCall& c, fcsa::DecodeForm form, fcsa::DecodeStepParams dp, int64_t slots, hipStream_t s) {
+  dp.slots = (int)slots;
+  dp.splits = 1;
+  dp.ws_o = nullptr;
+  dp.ws_ml = nullptr;
+  const fcsa::DecodeLseOut lo = c.lse != nullptr ? lse_view(*c.lse, true) : fcsa::DecodeLseOut{};
+  return timed(n.name, n.what, s, [&] { return fcsa::launch_prefill(c.a->p.dtype, c.a->p.dim_head, form, dp, c.lse != nullptr ? &lo : nullptr, s); });
+}
+
 int decode_call(const DecodeCall& c) {
   const bool ragged = c.seqs != nullptr, fp8 = c.qz != nullptr;
   // the checks, once; a rectangular call's window comes after its cache checks, a ragged step's among its own arguments
@@ -643,21 +676,14 @@ int decode_call(const DecodeCall& c) {
   if (p.batch == 0) return FCSA_OK;
   if (ragged && c.seqs->total_q == 0) return FCSA_OK;      // no packed row: nothing to append, nothing to write
   const bool rows = p.heads > 0 && (ragged || p.q_len > 0);
-  if (rows) {
-    const char* who = ragged ? "kvcache_varlen" : "kvcache";
-    if (a->workspace == nullptr || a->workspace_bytes < d.total)
-      return fail(FCSA_ERR_WORKSPACE, "%s: workspace too small: %zu < %zu bytes", who, a->workspace_bytes, d.total);
-    if ((reinterpret_cast<uintptr_t>(a->workspace) & 255) != 0) return fail(FCSA_ERR_WORKSPACE, "%s: workspace not 256-byte aligned", who);
-  }
-  const fcsa::DecodeRaggedParams dp = decode_params(c, win, d);
-  const fcsa::DecodeLseOut lo = c.lse != nullptr ? fcsa::DecodeLseOut{c.lse->lse, ragged ? 0 : c.lse->stride0, c.lse->stride1, c.lse->stride2} : fcsa::DecodeLseOut{};
-  // 1. the append (before anything reads the cache: same stream), 2. the split partials, 3. their combine
+  if (rows)
+    if (int rc = check_workspace(ragged ? "kvcache_varlen" : "kvcache", *a, d)) return rc;
+  const fcsa::DecodeStepParams dp = decode_params(c, win, d);
+  const fcsa::DecodeLseOut lo = c.lse != nullptr ? lse_view(*c.lse, ragged) : fcsa::DecodeLseOut{};
+  // 1. the append, 2. the split partials, 3. their combine
   const fcsa::DecodeForm form = {fp8, ragged};
   hipStream_t s = static_cast<hipStream_t>(a->stream);
-  if (kv->new_len > 0 && kv->capacity > 0) {
-    const LaunchName& n = kAppendName[ragged][fp8];
-    if (int rc = timed(n.name, n.what, s, [&] { return fcsa::launch_kv_append(p.dtype, p.dim_head, form, dp, s); })) return rc;
-  }
+  if (int rc = append_launch(c, form, dp, s)) return rc;
   if (!rows) return FCSA_OK;
   const LaunchName& n = kDecodeName[ragged][fp8];
   if (int rc = timed(n.name, n.what, s, [&] { return fcsa::launch_decode(p.dtype, p.dim_head, form, dp, s); })) return rc;
@@ -667,42 +693,31 @@ int decode_call(const DecodeCall& c) {
 
 // A prompt chunk against the cache (fcsa_forward_kvcache_prefill): the ragged step's checks, its append with the parameter block the ragged
 // call fills, then one launch of the multi-wave kernel (fcsa_prefill.hip) with 128-row slots, one split and no workspace.
-int prefill_call(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_lse_out* lse) {
-  const DecodeCall c = {a, kv, seqs, nullptr, nullptr, lse};
+int prefill_call(const DecodeCall& c) {
   if (int rc = check_kvcache_varlen(c)) return rc;
-  const fcsa_problem& p = a->p;
-  if (p.dtype != FCSA_F16 && p.dtype != FCSA_BF16)
-    return fail(FCSA_ERR_UNSUPPORTED, "kvcache_prefill: float32 is not supported (f16 or bf16; fcsa_forward_kvcache_varlen takes float32)");
-  if (p.dim_head != 64 && p.dim_head != 128)
-    return fail(FCSA_ERR_UNSUPPORTED, "kvcache_prefill: dim_head %d is not supported (64 or 128; fcsa_forward_kvcache_varlen takes the others)", p.dim_head);
+  const fcsa_problem& p = c.a->p;
+  if (!has_chunk_kernel(p))
+    return p.dtype == FCSA_F32
+               ? fail(FCSA_ERR_UNSUPPORTED, "kvcache_prefill: float32 is not supported (f16 or bf16; fcsa_forward_kvcache_varlen takes float32)")
+               : fail(FCSA_ERR_UNSUPPORTED, "kvcache_prefill: dim_head %d is not supported (64 or 128; fcsa_forward_kvcache_varlen takes the others)", p.dim_head);
   const int G = p.heads / p.kv_heads;
-  const int64_t slots = fcsa::prefill_slots(seqs->total_q, std::max(p.batch, 0), G, fcsa::kPrefillRows);
+  const int64_t slots = fcsa::prefill_slots(c.seqs->total_q, std::max(p.batch, 0), G, fcsa::kPrefillRows);
   if (slots * p.kv_heads > INT32_MAX) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_prefill: grid above 2^31 workgroups");
-  if (p.batch == 0 || seqs->total_q == 0) return FCSA_OK;      // no packed row: nothing to append, nothing to write
-  if (p.heads > 0 && lse != nullptr && lse->lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_prefill: lse: null pointer");
-  const DecodeWindow win = decode_window(p, *kv, true, nullptr);
-  fcsa::DecodeRaggedParams dp = decode_params(c, win, decode_plan(p, *kv, seqs, win.reach()));
-  hipStream_t s = static_cast<hipStream_t>(a->stream);
-  if (kv->new_len > 0 && kv->capacity > 0) {
-    const LaunchName& n = kAppendName[1][0];
-    if (int rc = timed(n.name, n.what, s, [&] { return fcsa::launch_kv_append(p.dtype, p.dim_head, {false, true}, dp, s); })) return rc;
-  }
+  if (p.batch == 0 || c.seqs->total_q == 0) return FCSA_OK;      // no packed row: nothing to append, nothing to write
+  if (p.heads > 0 && c.lse != nullptr && c.lse->lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_prefill: lse: null pointer");
+  const DecodeWindow win = decode_window(p, *c.kv, true, nullptr);
+  const fcsa::DecodeStepParams dp = decode_params(c, win, decode_plan(p, *c.kv, c.seqs, win.reach()));
+  const fcsa::DecodeForm form = {false, true};
+  hipStream_t s = static_cast<hipStream_t>(c.a->stream);
+  if (int rc = append_launch(c, form, dp, s)) return rc;
   if (p.heads <= 0) return FCSA_OK;
-  dp.slots = (int)slots;
-  dp.splits = 1;
-  dp.ws_o = nullptr;
-  dp.ws_ml = nullptr;
-  const fcsa::DecodeLseOut lo = lse != nullptr ? fcsa::DecodeLseOut{lse->lse, 0, lse->stride1, lse->stride2} : fcsa::DecodeLseOut{};
-  return timed("prefill", "prefill", s, [&] { return fcsa::launch_prefill(p.dtype, p.dim_head, dp, lse != nullptr ? &lo : nullptr, s); });
+  return chunk_launch({"prefill", "prefill"}, c, form, dp, slots, s);
 }
 
 // An engine step (fcsa_forward_kvcache_step): the ragged step's description with the `step` part -- its checks, its window, its plan with the
 // split count sized by the decode-routed rows, its append; then the step decode and combine launches over the full table and the chunk
 // launch over 128-row slots, each skipped where the caller promises it has no work.  Where the chunk kernel is not compiled for the problem
 // the call is decode_call.
-bool step_has_chunk_kernel(const fcsa_problem& p) {
-  return (p.dtype == FCSA_F16 || p.dtype == FCSA_BF16) && (p.dim_head == 64 || p.dim_head == 128);
-}
 static_assert(fcsa::kStepChunkRows == FCSA_STEP_CHUNK_ROWS, "the default threshold of include/fcsa.h");
 int check_step(const fcsa_kvcache_step* st) {
   if (st == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_step: null argument");
@@ -736,7 +751,7 @@ int step_call(const DecodeCall& c) {
   const fcsa_kvcache_step& st = *c.step;
   const bool rows = p.batch > 0 && p.heads > 0 && c.seqs->total_q > 0;
   if (rows && c.lse != nullptr && c.lse->lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_step: lse: null pointer");
-  if (!step_has_chunk_kernel(p)) return decode_call({c.a, c.kv, c.seqs, c.qz, c.w, c.lse});
+  if (!has_chunk_kernel(p)) return decode_call({c.a, c.kv, c.seqs, c.qz, c.w, c.lse});
   const bool fp8 = c.qz != nullptr;
   const DecodeWindow win = decode_window(p, *kv, true, c.w);
   const DecodePlan d = step_plan(p, *kv, *c.seqs, st, win.reach());
@@ -745,39 +760,27 @@ int step_call(const DecodeCall& c) {
   if (d.slots * std::max(p.kv_heads, 1) * d.splits > INT32_MAX || chunk_slots * std::max(p.kv_heads, 1) > INT32_MAX)
     return fail(FCSA_ERR_UNSUPPORTED, "kvcache_step: grid above 2^31 workgroups");
   if (p.batch == 0 || c.seqs->total_q == 0) return FCSA_OK;      // no packed row: nothing to append, nothing to write
-  if (rows && !st.no_decode) {
-    if (a->workspace == nullptr || a->workspace_bytes < d.total)
-      return fail(FCSA_ERR_WORKSPACE, "kvcache_step: workspace too small: %zu < %zu bytes", a->workspace_bytes, d.total);
-    if ((reinterpret_cast<uintptr_t>(a->workspace) & 255) != 0) return fail(FCSA_ERR_WORKSPACE, "kvcache_step: workspace not 256-byte aligned");
-  }
-  fcsa::DecodeStepParams sp{};
-  static_cast<fcsa::DecodeRaggedParams&>(sp) = decode_params(c, win, d);
+  if (rows && !st.no_decode)
+    if (int rc = check_workspace("kvcache_step", *a, d)) return rc;
+  fcsa::DecodeStepParams sp = decode_params(c, win, d);
   sp.chunk_rows = st.chunk_rows < 0 ? fcsa::kStepChunkRows : st.chunk_rows;
-  const fcsa::DecodeLseOut lo = c.lse != nullptr ? fcsa::DecodeLseOut{c.lse->lse, 0, c.lse->stride1, c.lse->stride2} : fcsa::DecodeLseOut{};
-  const fcsa::DecodeLseOut* lop = c.lse != nullptr ? &lo : nullptr;
+  const fcsa::DecodeLseOut lo = c.lse != nullptr ? lse_view(*c.lse, true) : fcsa::DecodeLseOut{};
+  const fcsa::DecodeForm form = {fp8, true, true};
   hipStream_t s = static_cast<hipStream_t>(a->stream);
-  // 1. the ragged call's append, once, with the base part of the block
-  if (kv->new_len > 0 && kv->capacity > 0) {
-    const LaunchName& n = kAppendName[1][fp8];
-    if (int rc = timed(n.name, n.what, s, [&] { return fcsa::launch_kv_append(p.dtype, p.dim_head, {fp8, true}, sp, s); })) return rc;
-  }
+  // 1. the ragged call's append, once
+  if (int rc = append_launch(c, form, sp, s)) return rc;
   if (!rows) return FCSA_OK;
   // 2. the decode-routed sequences: split partials and their combine over the slots and rows of the full table
   if (!st.no_decode) {
     const LaunchName& n = kStepDecodeName[fp8];
-    if (int rc = timed(n.name, n.what, s, [&] { return fcsa::launch_step_decode(p.dtype, p.dim_head, fp8, sp, s); })) return rc;
+    if (int rc = timed(n.name, n.what, s, [&] { return fcsa::launch_decode(p.dtype, p.dim_head, form, sp, s); })) return rc;
     const LaunchName& m = kStepCombineName[fp8][c.lse != nullptr];
-    if (int rc = timed(m.name, m.what, s, [&] { return fcsa::launch_step_combine(p.dtype, p.dim_head, fp8, sp, lop, s); })) return rc;
+    if (int rc = timed(m.name, m.what, s, [&] { return fcsa::launch_decode_combine(p.dtype, p.dim_head, form, sp, c.lse != nullptr ? &lo : nullptr, s); }))
+      return rc;
   }
-  // 3. the chunk-routed sequences: one launch, one split, no workspace
-  if (!st.no_chunk) {
-    fcsa::DecodeStepParams cp = sp;
-    cp.slots = (int)chunk_slots;
-    cp.splits = 1;
-    cp.ws_o = nullptr;
-    cp.ws_ml = nullptr;
-    if (int rc = timed("step_prefill", "step prefill", s, [&] { return fcsa::launch_step_prefill(p.dtype, p.dim_head, fp8, cp, lop, s); })) return rc;
-  }
+  // 3. the chunk-routed sequences
+  if (!st.no_chunk)
+    if (int rc = chunk_launch({"step_prefill", "step prefill"}, c, form, sp, chunk_slots, s)) return rc;
   return FCSA_OK;
 }
 
@@ -793,7 +796,7 @@ int fcsa_forward_kvcache_step(const fcsa_forward_args* a, const fcsa_kvcache* kv
 size_t fcsa_forward_kvcache_step_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_kvcache_quant*,
                                                  const fcsa_window* w, const fcsa_kvcache_step* step) {
   if (p == nullptr || kv == nullptr || seqs == nullptr || step == nullptr) return 0;
-  if (!step_has_chunk_kernel(*p)) return decode_workspace_bytes(p, kv, seqs, w);
+  if (!has_chunk_kernel(*p)) return decode_workspace_bytes(p, kv, seqs, w);
   return step_plan(*p, *kv, *seqs, *step, decode_window(*p, *kv, true, w).reach()).total;
 }
 
@@ -840,7 +843,7 @@ int fcsa_forward_kvcache_lse(const fcsa_forward_args* a, const fcsa_kvcache* kv,
 
 int fcsa_forward_kvcache_prefill(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_lse_out* lse) {
   if (a == nullptr || kv == nullptr || seqs == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_prefill: null argument");
-  return prefill_call(a, kv, seqs, lse);
+  return prefill_call({a, kv, seqs, nullptr, nullptr, lse});
 }
 
 int fcsa_merge_states(const fcsa_merge_args* a) {
@@ -866,12 +869,12 @@ int fcsa_merge_states(const fcsa_merge_args* a) {
       if (a->lse_in[s].lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "merge_states: lse_in[%d]: null pointer", s);
     }
     mp.o_in[s] = view(a->o_in[t], es);
-    mp.lse_in[s] = fcsa::DecodeLseOut{a->lse_in[t].lse, a->lse_in[t].stride0, a->lse_in[t].stride1, a->lse_in[t].stride2};
+    mp.lse_in[s] = lse_view(a->lse_in[t]);
   }
   if (int rc = check_tensor("merge_states: o", a->o, es, true)) return rc;
   if (a->lse.lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "merge_states: lse: null pointer");
   mp.o = view(a->o, es);
-  mp.lse = fcsa::DecodeLseOut{a->lse.lse, a->lse.stride0, a->lse.stride1, a->lse.stride2};
+  mp.lse = lse_view(a->lse);
   mp.n0 = a->size0; mp.n1 = a->size1; mp.n2 = a->size2; mp.D = a->dim_head; mp.S = a->states;
   hipStream_t s = static_cast<hipStream_t>(a->stream);
   return timed("merge_states", "merge states", s, [&] { return fcsa::launch_merge_states(a->dtype, mp, s); });
@@ -1044,7 +1047,7 @@ int fcsa_attention_lse(const fcsa_problem* pp, const float* inv_l, const fcsa_va
   if (inv_l == nullptr) return fail(FCSA_ERR_INVALID_ARG, "attention_lse: inv_l: null pointer");
   fcsa::StateLseParams sp;
   sp.inv_l = inv_l;
-  sp.out = fcsa::DecodeLseOut{lse_out->lse, lse_out->stride0, lse_out->stride1, lse_out->stride2};
+  sp.out = lse_view(*lse_out);
   sp.B = p.batch; sp.H = p.heads; sp.N = p.q_len; sp.M = p.k_len;
   // the sides as every windowed launch takes them: (open, open) no mask, (open, 0) causal
   (void)fcsa::win_normalise(p.q_len, p.k_len, p.causal != 0, w != nullptr ? w->left : -1, w != nullptr ? w->right : -1, sp.win_lo, sp.win_hi);
@@ -1071,7 +1074,6 @@ int fcsa_merge_states_backward(const fcsa_merge_backward_args* a) {
   if (rows / 16 > (int64_t)INT32_MAX - 1) return fail(FCSA_ERR_UNSUPPORTED, "merge_states_backward: grid above 2^31 workgroups");
   const int es = elem_size(a->dtype);
   fcsa::MergeBwdParams mp;
-  auto lse_view = [](const fcsa_lse_out& l) { return fcsa::DecodeLseOut{l.lse, l.stride0, l.stride1, l.stride2}; };
   for (int s = 0; s < FCSA_MERGE_MAX_STATES; ++s) {
     const int t = std::min(s, a->states - 1);      // (the unused slots repeat the last state: never read, never written, never null)
     if (s < a->states) {

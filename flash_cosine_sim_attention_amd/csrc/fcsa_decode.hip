@@ -1,6 +1,6 @@
 // fcsa_decode.hip -- decoding against a key/value cache (fcsa_forward_kvcache, include/fcsa.h).
 //
-//   kv_append_kernel      k_new / v_new -> the cache slots [cache_seqlens[b], + new_len) (through the block table when paged)
+//   kv_append_kernel      k_new / v_new -> the cache slots [cache_seqlens[b], + new_len) below the capacity (through the block table when paged)
 //   decode_kernel         one single-wave workgroup per (batch, K/V head, row tile, key split): the G = H / Hk query heads x N queries
 //                         of the K/V head are the 16 rows of a tile, so each K/V byte is read once per row tile.  Keys stream straight
 //                         from the cache into registers (one 16-byte load per lane and fragment), are l2-normalised there, and
@@ -17,9 +17,14 @@
 // own -- kv_append_fp8_kernel, decode_fp8_kernel (decode_body with FP8), decode_combine_fp8_kernel -- so the kernels above are what
 // they were.  A lane reads 8 key bytes per fragment (the same features as its 16-bit fragment) and converts them with v_cvt_pk_f32_fp8;
 // every code is exact in f16 and bf16, so the operands of both MFMA products are what a 16-bit cache holding the codes would feed.
+// An engine step (fcsa_forward_kvcache_step) has the decode and combine entry points of its decode side here --
+// step_decode[_fp8]_kernel (decode_body with STEP), step_combine[_lse]_kernel -- and its chunk side in fcsa_prefill.hip.
+// The append is written once for every form: where a new row goes (append_pos: the cache_seqlens clamp and the drop at the capacity), the
+// address of that position (cache_base of fcsa_decode_common.cuh, the readers' own rule) and the row write (append_chunk: a copy, or the
+// quantisation of an fp8 cache).  The three append entry points are the index decomposition of their layout and calls to those.
 // Host side: three launchers at the end of the file, one per job -- launch_kv_append, launch_decode, launch_decode_combine -- over one
-// parameter block (DecodeRaggedParams, fcsa_kernels.h).  Each dispatches dtype, head dim and form (fp8, ragged) once, works out its grid
-// once, and hands the entry point it picks the part of the block that entry point declares (launch_part).
+// parameter block (DecodeStepParams, fcsa_kernels.h).  Each dispatches dtype, head dim and form (fp8, ragged, step) once, works out its
+// grid once, and hands the entry point it picks the part of the block that entry point declares (launch_part, fcsa_decode_common.cuh).
 #include "fcsa_common.cuh"
 #include "fcsa_decode_common.cuh"
 
@@ -354,7 +359,7 @@ template <typename T, int D, bool DYN, bool GEN>
 __global__ __launch_bounds__(64) void decode_ragged_fp8_kernel(DecodeRaggedParams p) {
   decode_body<T, D, DYN, GEN, true, true, true>(p);
 }
-// the decode side of an engine step (launch_step_decode): 16-bit types and D = 64 / 128, where every group width is reduced in registers
+// the decode side of an engine step (launch_decode with the step form): 16-bit types and D = 64 / 128, where every group width is reduced in registers
 template <typename T, int D, bool DYN>
 __global__ __launch_bounds__(64) void step_decode_kernel(DecodeStepParams p) {
   decode_body<T, D, DYN, false, true, false, true, true>(p);
@@ -476,41 +481,38 @@ template <typename T> FCSA_DEV u32x4 quantise16(const u32x4& a, const u32x4& b, 
   return out;
 }
 
-// one thread per 16-byte chunk of an appended row; slots at or beyond the capacity are dropped
-template <typename T, int D>
-__global__ __launch_bounds__(256) void kv_append_kernel(DecodeParams p) {
-  constexpr int CPR = D * Traits<T>::ES / 16;
-  const int64_t total = (int64_t)p.B * p.Hk * p.new_len * CPR;
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= total) return;
-  const int ch = (int)(t % CPR);
-  int64_t rest = t / CPR;
-  const int tn = (int)(rest % p.new_len);
-  rest /= p.new_len;
-  const int kvh = (int)(rest % p.Hk), b = (int)(rest / p.Hk);
+// ---- the append: one rule for where a new row goes, one row write, three entry points -----------------------------------------------
+// Where new row `i` of sequence b goes: position clamp(cache_seqlens[b], 0, capacity) + i.  False: the row is dropped -- its position is at
+// or beyond the capacity (every row, when seqlens is null: every sequence is full).  A position it gives is inside [0, capacity).
+FCSA_DEV bool append_pos(const DecodeParams& p, int b, int64_t i, int& pos) {
   const int64_t start = p.seqlens != nullptr ? min(max((int64_t)p.seqlens[b], (int64_t)0), (int64_t)p.capacity) : (int64_t)p.capacity;
-  const int64_t pos = start + tn;
-  if (pos >= p.capacity) return;
-  int64_t kdst, vdst;
-  if (p.table != nullptr) {
-    int blk = p.table[(int64_t)b * p.table_stride + pos / p.page];
-    blk = min(max(blk, 0), p.num_blocks - 1);
-    kdst = (int64_t)blk * p.kc.sb + (int64_t)kvh * p.kc.sh + (pos % p.page) * p.kc.sn;
-    vdst = (int64_t)blk * p.vc.sb + (int64_t)kvh * p.vc.sh + (pos % p.page) * p.vc.sn;
-  } else {
-    kdst = (int64_t)b * p.kc.sb + (int64_t)kvh * p.kc.sh + pos * p.kc.sn;
-    vdst = (int64_t)b * p.vc.sb + (int64_t)kvh * p.vc.sh + pos * p.vc.sn;
-  }
-  const int64_t ksrc = (int64_t)b * p.kn.sb + (int64_t)kvh * p.kn.sh + (int64_t)tn * p.kn.sn;
-  const int64_t vsrc = (int64_t)b * p.vn.sb + (int64_t)kvh * p.vn.sh + (int64_t)tn * p.vn.sn;
-  *reinterpret_cast<u32x4*>(p.kc.p + kdst + ch * 16) = *reinterpret_cast<const u32x4*>(p.kn.p + ksrc + ch * 16);
-  *reinterpret_cast<u32x4*>(p.vc.p + vdst + ch * 16) = *reinterpret_cast<const u32x4*>(p.vn.p + vsrc + ch * 16);
+  if (start + i >= p.capacity) return false;
+  pos = (int)(start + i);
+  return true;
 }
 
-// kv_append_kernel for an fp8 cache: one thread per 16 OUTPUT bytes -- 32 bytes of k_new / v_new (16-bit T) become 16 codes
-template <typename T, int D>
-__global__ __launch_bounds__(256) void kv_append_fp8_kernel(DecodeFp8Params p) {
-  constexpr int CPR = D / 16;
+// 16-byte chunk `ch` of cache position `pos` (cache_base) of K and of V from the new rows at ksrc / vsrc: a copy, or (FP8, P = the fp8
+// block) the codes of 32 source bytes under the (b, kvh) scales
+template <typename T, bool FP8, typename P>
+FCSA_DEV void append_chunk(const P& p, int b, int kvh, int pos, int ch, const char* ksrc, const char* vsrc) {
+  u32x4* kdst = reinterpret_cast<u32x4*>(cache_base(p, p.kc, b, kvh, pos) + ch * 16);
+  u32x4* vdst = reinterpret_cast<u32x4*>(cache_base(p, p.vc, b, kvh, pos) + ch * 16);
+  if constexpr (FP8) {
+    const u32x4* ks = reinterpret_cast<const u32x4*>(ksrc + ch * 32);
+    const u32x4* vs = reinterpret_cast<const u32x4*>(vsrc + ch * 32);
+    *kdst = quantise16<T>(ks[0], ks[1], p.k_scale[(int64_t)b * p.ks_b + (int64_t)kvh * p.ks_h]);
+    *vdst = quantise16<T>(vs[0], vs[1], p.v_scale[(int64_t)b * p.vs_b + (int64_t)kvh * p.vs_h]);
+  } else {
+    *kdst = *reinterpret_cast<const u32x4*>(ksrc + ch * 16);
+    *vdst = *reinterpret_cast<const u32x4*>(vsrc + ch * 16);
+  }
+}
+
+// A rectangular append: one thread per 16 bytes WRITTEN of new row tn of (b, kvh) -- a 16-byte chunk of the row, or (FP8) 32 bytes of it
+// that become 16 codes
+template <typename T, int D, bool FP8, typename P>
+FCSA_DEV void kv_append_body(const P& p) {
+  constexpr int CPR = FP8 ? D / 16 : D * Traits<T>::ES / 16;
   const int64_t total = (int64_t)p.B * p.Hk * p.new_len * CPR;
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (t >= total) return;
@@ -519,23 +521,18 @@ __global__ __launch_bounds__(256) void kv_append_fp8_kernel(DecodeFp8Params p) {
   const int tn = (int)(rest % p.new_len);
   rest /= p.new_len;
   const int kvh = (int)(rest % p.Hk), b = (int)(rest / p.Hk);
-  const int64_t start = p.seqlens != nullptr ? min(max((int64_t)p.seqlens[b], (int64_t)0), (int64_t)p.capacity) : (int64_t)p.capacity;
-  const int64_t pos = start + tn;
-  if (pos >= p.capacity) return;
-  int64_t kdst, vdst;
-  if (p.table != nullptr) {
-    int blk = p.table[(int64_t)b * p.table_stride + pos / p.page];
-    blk = min(max(blk, 0), p.num_blocks - 1);
-    kdst = (int64_t)blk * p.kc.sb + (int64_t)kvh * p.kc.sh + (pos % p.page) * p.kc.sn;
-    vdst = (int64_t)blk * p.vc.sb + (int64_t)kvh * p.vc.sh + (pos % p.page) * p.vc.sn;
-  } else {
-    kdst = (int64_t)b * p.kc.sb + (int64_t)kvh * p.kc.sh + pos * p.kc.sn;
-    vdst = (int64_t)b * p.vc.sb + (int64_t)kvh * p.vc.sh + pos * p.vc.sn;
-  }
-  const u32x4* ks = reinterpret_cast<const u32x4*>(p.kn.p + (int64_t)b * p.kn.sb + (int64_t)kvh * p.kn.sh + (int64_t)tn * p.kn.sn + ch * 32);
-  const u32x4* vs = reinterpret_cast<const u32x4*>(p.vn.p + (int64_t)b * p.vn.sb + (int64_t)kvh * p.vn.sh + (int64_t)tn * p.vn.sn + ch * 32);
-  *reinterpret_cast<u32x4*>(p.kc.p + kdst + ch * 16) = quantise16<T>(ks[0], ks[1], p.k_scale[(int64_t)b * p.ks_b + (int64_t)kvh * p.ks_h]);
-  *reinterpret_cast<u32x4*>(p.vc.p + vdst + ch * 16) = quantise16<T>(vs[0], vs[1], p.v_scale[(int64_t)b * p.vs_b + (int64_t)kvh * p.vs_h]);
+  int pos;
+  if (!append_pos(p, b, tn, pos)) return;
+  append_chunk<T, FP8>(p, b, kvh, pos, ch, p.kn.p + (int64_t)b * p.kn.sb + (int64_t)kvh * p.kn.sh + (int64_t)tn * p.kn.sn,
+                       p.vn.p + (int64_t)b * p.vn.sb + (int64_t)kvh * p.vn.sh + (int64_t)tn * p.vn.sn);
+}
+template <typename T, int D>
+__global__ __launch_bounds__(256) void kv_append_kernel(DecodeParams p) {
+  kv_append_body<T, D, false>(p);
+}
+template <typename T, int D>
+__global__ __launch_bounds__(256) void kv_append_fp8_kernel(DecodeFp8Params p) {
+  kv_append_body<T, D, true>(p);
 }
 
 // decode_combine_kernel / decode_combine_fp8_kernel for a ragged step, and the form that also writes the log-sum-exp of every packed row
@@ -548,7 +545,7 @@ __global__ __launch_bounds__(256) void decode_combine_lse_ragged_kernel(DecodeRa
   decode_combine_body<T, D, FP8, true, true>(p, lo);
 }
 
-// the combine of an engine step's decode side (launch_step_combine)
+// the combine of an engine step's decode side (launch_decode_combine with the step form)
 template <typename T, int D, bool FP8>
 __global__ __launch_bounds__(256) void step_combine_kernel(DecodeStepParams p) {
   decode_combine_body<T, D, FP8, true, false, true>(p, DecodeLseOut{});
@@ -573,51 +570,19 @@ __global__ __launch_bounds__(256) void kv_append_ragged_kernel(DecodeRaggedParam
   const int b = ragged_seq_of(p.cu_q, p.B, p.total_q, tok);
   const int64_t q0 = ragged_cu(p.cu_q[b], p.total_q), q1 = ragged_cu(p.cu_q[b + 1], p.total_q);
   if (tok < q0 || tok >= q1) return;          // (a malformed table: the row belongs to no sequence)
-  const int64_t start = p.seqlens != nullptr ? min(max((int64_t)p.seqlens[b], (int64_t)0), (int64_t)p.capacity) : (int64_t)p.capacity;
-  const int64_t pos = start + (tok - q0);
-  if (pos >= p.capacity) return;
-  int64_t kdst, vdst;
-  if (p.table != nullptr) {
-    int blk = p.table[(int64_t)b * p.table_stride + pos / p.page];
-    blk = min(max(blk, 0), p.num_blocks - 1);
-    kdst = (int64_t)blk * p.kc.sb + (int64_t)kvh * p.kc.sh + (pos % p.page) * p.kc.sn;
-    vdst = (int64_t)blk * p.vc.sb + (int64_t)kvh * p.vc.sh + (pos % p.page) * p.vc.sn;
-  } else {
-    kdst = (int64_t)b * p.kc.sb + (int64_t)kvh * p.kc.sh + pos * p.kc.sn;
-    vdst = (int64_t)b * p.vc.sb + (int64_t)kvh * p.vc.sh + pos * p.vc.sn;
-  }
-  const int64_t ksrc = (int64_t)kvh * p.kn.sh + tok * p.kn.sn, vsrc = (int64_t)kvh * p.vn.sh + tok * p.vn.sn;
-  if constexpr (FP8) {
-    const u32x4* ks = reinterpret_cast<const u32x4*>(p.kn.p + ksrc + ch * 32);
-    const u32x4* vs = reinterpret_cast<const u32x4*>(p.vn.p + vsrc + ch * 32);
-    *reinterpret_cast<u32x4*>(p.kc.p + kdst + ch * 16) = quantise16<T>(ks[0], ks[1], p.k_scale[(int64_t)b * p.ks_b + (int64_t)kvh * p.ks_h]);
-    *reinterpret_cast<u32x4*>(p.vc.p + vdst + ch * 16) = quantise16<T>(vs[0], vs[1], p.v_scale[(int64_t)b * p.vs_b + (int64_t)kvh * p.vs_h]);
-  } else {
-    *reinterpret_cast<u32x4*>(p.kc.p + kdst + ch * 16) = *reinterpret_cast<const u32x4*>(p.kn.p + ksrc + ch * 16);
-    *reinterpret_cast<u32x4*>(p.vc.p + vdst + ch * 16) = *reinterpret_cast<const u32x4*>(p.vn.p + vsrc + ch * 16);
-  }
+  int pos;
+  if (!append_pos(p, b, tok - q0, pos)) return;
+  append_chunk<T, FP8>(p, b, kvh, pos, ch, p.kn.p + (int64_t)kvh * p.kn.sh + tok * p.kn.sn, p.vn.p + (int64_t)kvh * p.vn.sh + tok * p.vn.sn);
 }
 
 int64_t blocks_of(int64_t threads) { return (threads + 255) / 256; }
 
 // ---- the launchers: one per job (append, decode, combine) over every form of the call ----------------------------------------------
-// The parameter block a kernel entry point takes, and the launch of `Kernel` with that part of the call's one block (a base-class slice;
-// LDS > 0: dynamic LDS, raised once per device) -- so no launcher can hand an entry point another block than the one it declares.
-template <typename P, typename... More> P block_of(void (*)(P, More...));
-template <auto Kernel, int LDS, typename... More>
-hipError_t launch_part(dim3 grid, dim3 block, hipStream_t s, const DecodeRaggedParams& p, const More&... more) {
-  using P = decltype(block_of(Kernel));
-  if constexpr (LDS > 0) {
-    return launch_with_lds<Kernel>(grid, block, LDS, s, static_cast<const P&>(p), more...);
-  } else {
-    hipLaunchKernelGGL(Kernel, grid, block, 0, s, static_cast<const P&>(p), more...);
-    return hipGetLastError();
-  }
-}
-
 // The one dtype / head-dim / form dispatch: fn(TypeDim<T, D>, FP8, RAGGED), the flags as std::bool_constant.  An fp8 cache exists for the
-// 16-bit types only, so nothing with FP8 is instantiated for float32.
+// 16-bit types only, so nothing with FP8 is instantiated for float32.  f.step (an engine step) stays a run-time flag: each launcher picks
+// the step entry points under `if constexpr (kStepKernels<...>)`, so they are instantiated where they exist and nowhere else.
 template <typename F> hipError_t dispatch_decode(int dtype, int D, DecodeForm f, F&& fn) {
+  if (f.step && !f.ragged) return hipErrorInvalidValue;      // a step is a ragged step
   return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
     using Y = std::true_type;
     using N = std::false_type;
@@ -628,11 +593,15 @@ template <typename F> hipError_t dispatch_decode(int dtype, int D, DecodeForm f,
     return f.ragged ? fn(td, N{}, Y{}) : fn(td, N{}, N{});
   });
 }
+// the step entry points exist for ragged calls where the chunk kernel does (16-bit types, D = 64 / 128: every group width is reduced in
+// registers there, so there is no GEN form of them)
+template <typename T, int D, bool RAGGED, bool GEN = false> constexpr bool kStepKernels = RAGGED && !GEN && kHasChunkKernel<T, D>;
 
 }  // namespace
 
-// one thread per 16 bytes WRITTEN of an appended row (an fp8 row is D bytes); ragged: the packed rows bring one key and value each
-hipError_t launch_kv_append(int dtype, int D, DecodeForm f, const DecodeRaggedParams& p, hipStream_t s) {
+// one thread per 16 bytes WRITTEN of an appended row (an fp8 row is D bytes); ragged: the packed rows bring one key and value each.  The
+// append of an engine step is the ragged call's (f.step is not looked at).
+hipError_t launch_kv_append(int dtype, int D, DecodeForm f, const DecodeStepParams& p, hipStream_t s) {
   return dispatch_decode(dtype, D, f, [&](auto td, auto fp8, auto ragged) -> hipError_t {
     using T = typename decltype(td)::T;
     constexpr int DD = decltype(td)::D;
@@ -647,17 +616,27 @@ hipError_t launch_kv_append(int dtype, int D, DecodeForm f, const DecodeRaggedPa
   });
 }
 
-// one single-wave workgroup per (K/V head, row tile, key split): row_tiles per sequence, or the flat slots of a ragged step
-hipError_t launch_decode(int dtype, int D, DecodeForm f, const DecodeRaggedParams& p, hipStream_t s) {
+// one single-wave workgroup per (K/V head, row tile, key split): row_tiles per sequence, or the flat slots of a ragged step.  f.step: the
+// step entry points over the slots of the FULL table (the slots of chunk sequences exit at once); nothing to launch without a workgroup.
+hipError_t launch_decode(int dtype, int D, DecodeForm f, const DecodeStepParams& p, hipStream_t s) {
   return dispatch_decode(dtype, D, f, [&](auto td, auto fp8, auto ragged) -> hipError_t {
     using T = typename decltype(td)::T;
     constexpr int DD = decltype(td)::D;
     constexpr int ES = Traits<T>::ES;
     constexpr bool FP8 = decltype(fp8)::value, RAGGED = decltype(ragged)::value;
-    const dim3 grid((unsigned)((RAGGED ? (int64_t)p.slots : (int64_t)p.B * p.row_tiles) * p.Hk * p.splits)), block(64);
+    if (f.step && !kStepKernels<T, DD, RAGGED>) return hipErrorInvalidValue;
+    const int64_t wgs = (RAGGED ? (int64_t)p.slots : (int64_t)p.B * p.row_tiles) * p.Hk * p.splits;
+    const dim3 grid((unsigned)wgs), block(64);
     auto go = [&](auto dyn, auto gen) -> hipError_t {
       constexpr bool DY = decltype(dyn)::value, GN = decltype(gen)::value;
       constexpr int LDS = DecodeLds<DD, ES, GN>::BYTES;
+      if constexpr (kStepKernels<T, DD, RAGGED, GN>) {
+        if (f.step) {
+          if (wgs <= 0) return hipSuccess;
+          if constexpr (FP8) return launch_part<step_decode_fp8_kernel<T, DD, DY>, LDS>(grid, block, s, p);
+          else return launch_part<step_decode_kernel<T, DD, DY>, LDS>(grid, block, s, p);
+        }
+      }
       if constexpr (RAGGED && FP8) return launch_part<decode_ragged_fp8_kernel<T, DD, DY, GN>, LDS>(grid, block, s, p);
       else if constexpr (RAGGED) return launch_part<decode_ragged_kernel<T, DD, DY, GN>, LDS>(grid, block, s, p);
       else if constexpr (FP8) return p.window ? launch_part<decode_fp8_kernel<T, DD, DY, GN, true>, LDS>(grid, block, s, p)
@@ -676,15 +655,21 @@ hipError_t launch_decode(int dtype, int D, DecodeForm f, const DecodeRaggedParam
   });
 }
 
-// one thread per four features of an output row; lse: nullptr, or the entry points that also write the rows' log-sum-exp
-hipError_t launch_decode_combine(int dtype, int D, DecodeForm f, const DecodeRaggedParams& p, const DecodeLseOut* lse, hipStream_t s) {
+// one thread per four features of an output row; lse: nullptr, or the entry points that also write the rows' log-sum-exp.  f.step: the
+// step entry points (the rows of chunk sequences exit at once); nothing to launch without a sequence.
+hipError_t launch_decode_combine(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeLseOut* lse, hipStream_t s) {
   return dispatch_decode(dtype, D, f, [&](auto td, auto fp8, auto ragged) -> hipError_t {
     using T = typename decltype(td)::T;
     constexpr int DD = decltype(td)::D;
     constexpr bool FP8 = decltype(fp8)::value, RAGGED = decltype(ragged)::value;
+    if (f.step && !kStepKernels<T, DD, RAGGED>) return hipErrorInvalidValue;
     const int64_t threads = (RAGGED ? (int64_t)p.total_q : (int64_t)p.B * p.N) * p.H * (DD / 4);
-    if (threads <= 0) return hipSuccess;
+    if (threads <= 0 || (f.step && p.B <= 0)) return hipSuccess;
     const dim3 grid((unsigned)blocks_of(threads)), block(256);
+    if constexpr (kStepKernels<T, DD, RAGGED>) {
+      if (f.step) return lse != nullptr ? launch_part<step_combine_lse_kernel<T, DD, FP8>, 0>(grid, block, s, p, *lse)
+                                        : launch_part<step_combine_kernel<T, DD, FP8>, 0>(grid, block, s, p);
+    }
     if (lse != nullptr) {
       if constexpr (RAGGED) return launch_part<decode_combine_lse_ragged_kernel<T, DD, FP8>, 0>(grid, block, s, p, *lse);
       else if constexpr (FP8) return launch_part<decode_combine_lse_fp8_kernel<T, DD>, 0>(grid, block, s, p, *lse);
@@ -693,60 +678,6 @@ hipError_t launch_decode_combine(int dtype, int D, DecodeForm f, const DecodeRag
     if constexpr (RAGGED) return launch_part<decode_combine_ragged_kernel<T, DD, FP8>, 0>(grid, block, s, p);
     else if constexpr (FP8) return launch_part<decode_combine_fp8_kernel<T, DD>, 0>(grid, block, s, p);
     else return launch_part<decode_combine_kernel<T, DD>, 0>(grid, block, s, p);
-  });
-}
-
-// ---- an engine step (fcsa_forward_kvcache_step): the decode side, after the ragged call's append -------------------------------------
-namespace {
-// fn(T, std::integral_constant<int, D>) for the 16-bit types and D = 64 / 128: where the chunk kernel exists
-template <typename F> hipError_t dispatch_step(int dtype, int D, F&& fn) {
-  using D64 = std::integral_constant<int, 64>;
-  using D128 = std::integral_constant<int, 128>;
-  if (D != 64 && D != 128) return hipErrorInvalidValue;
-  if (dtype == FCSA_BF16) return D == 64 ? fn(BF16{}, D64{}) : fn(BF16{}, D128{});
-  if (dtype == FCSA_F16) return D == 64 ? fn(F16{}, D64{}) : fn(F16{}, D128{});
-  return hipErrorInvalidValue;
-}
-template <auto Kernel, int LDS, typename... More>
-hipError_t launch_step(dim3 grid, dim3 block, hipStream_t s, const DecodeStepParams& p, const More&... more) {
-  if constexpr (LDS > 0) {
-    return launch_with_lds<Kernel>(grid, block, LDS, s, p, more...);
-  } else {
-    hipLaunchKernelGGL(Kernel, grid, block, 0, s, p, more...);
-    return hipGetLastError();
-  }
-}
-}  // namespace
-
-// one single-wave workgroup per (flat slot of the FULL table, K/V head, key split): the slots of chunk sequences exit at once
-hipError_t launch_step_decode(int dtype, int D, bool fp8, const DecodeStepParams& p, hipStream_t s) {
-  return dispatch_step(dtype, D, [&](auto t, auto d) -> hipError_t {
-    using T = decltype(t);
-    constexpr int DD = decltype(d)::value;
-    if (p.l2norm && !decode_groups_fast(DD, p.groups, Unit<T>::UE)) return hipErrorInvalidValue;
-    const int64_t wgs = (int64_t)p.slots * p.Hk * p.splits;
-    if (wgs <= 0) return hipSuccess;
-    const dim3 grid((unsigned)wgs), block(64);
-    constexpr int LDS = DecodeLds<DD, 2, false>::BYTES;
-    if (fp8) return p.dyn ? launch_step<step_decode_fp8_kernel<T, DD, true>, LDS>(grid, block, s, p)
-                          : launch_step<step_decode_fp8_kernel<T, DD, false>, LDS>(grid, block, s, p);
-    return p.dyn ? launch_step<step_decode_kernel<T, DD, true>, LDS>(grid, block, s, p)
-                 : launch_step<step_decode_kernel<T, DD, false>, LDS>(grid, block, s, p);
-  });
-}
-
-// one thread per four features of a packed output row; the rows of chunk sequences exit at once
-hipError_t launch_step_combine(int dtype, int D, bool fp8, const DecodeStepParams& p, const DecodeLseOut* lse, hipStream_t s) {
-  return dispatch_step(dtype, D, [&](auto t, auto d) -> hipError_t {
-    using T = decltype(t);
-    constexpr int DD = decltype(d)::value;
-    const int64_t threads = (int64_t)p.total_q * p.H * (DD / 4);
-    if (threads <= 0 || p.B <= 0) return hipSuccess;
-    const dim3 grid((unsigned)blocks_of(threads)), block(256);
-    if (lse != nullptr) return fp8 ? launch_step<step_combine_lse_kernel<T, DD, true>, 0>(grid, block, s, p, *lse)
-                                   : launch_step<step_combine_lse_kernel<T, DD, false>, 0>(grid, block, s, p, *lse);
-    return fp8 ? launch_step<step_combine_kernel<T, DD, true>, 0>(grid, block, s, p)
-               : launch_step<step_combine_kernel<T, DD, false>, 0>(grid, block, s, p);
   });
 }
 

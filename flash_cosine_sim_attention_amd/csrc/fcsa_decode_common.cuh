@@ -1,7 +1,8 @@
 // fcsa_decode_common.cuh -- the device code shared by fcsa_decode.hip (the single-wave decode kernels) and fcsa_prefill.hip (the multi-wave
 // prefill kernel), whose results must agree bit for bit: what is here is written once and both call it (DESIGN.md 4.7.4 lists what is
 // still written in both).  A row in registers: Unit, unpack / pack, unpack_fp8 (an e4m3fn cache), group_normalise.  Reading the cache: cache_base, clamped_first / clamped_off,
-// kKvPitch.  A 32-key block step: softmax_step, pv_block.  The end of a row: combine_weight, combine_inv.
+// kKvPitch.  A 32-key block step: softmax_step, pv_block.  The end of a row: combine_weight, combine_inv.  Host side: launch_part (every
+// entry point gets the slice of the call's block it declares) and dispatch_chunk (the one f16 / bf16 x D 64 / 128 ladder).
 // Each translation unit gets its own internal copies (anonymous namespace).
 #pragma once
 #include "fcsa_common.cuh"
@@ -131,15 +132,17 @@ template <int NJ, int UE> FCSA_DEV void group_normalise(float (&x)[NJ][UE], int 
     for (int e = 0; e < UE; ++e) x[j][e] *= 1.f / fmaxf(sqrtf(ss[j][e]), 1e-12f);
 }
 
-// Address of cache position `first` (a multiple of 16, uniform) of sequence b, K/V head kvh: a block-table lookup per 16 positions
-// (pages are multiples of 16 positions, so the 16 keys of a fragment never straddle two pages).  Block ids are clamped to the pool.
-FCSA_DEV const char* cache_base(const DecodeParams& p, const View& v, int b, int kvh, int first) {
+// THE address rule of the caches, for the kernels that read them and the append kernels that write them: cache position `pos` (in
+// [0, capacity)) of sequence b, K/V head kvh -- through the block table when the cache is paged, the block id clamped to the pool, and
+// contiguous otherwise.  The readers call it once per 16 positions, with a uniform multiple of 16 (pages are multiples of 16 positions, so
+// the 16 keys of a fragment never straddle two pages).
+FCSA_DEV char* cache_base(const DecodeParams& p, const View& v, int b, int kvh, int pos) {
   if (p.table != nullptr) {
-    int blk = p.table[(int64_t)b * p.table_stride + first / p.page];
+    int blk = p.table[(int64_t)b * p.table_stride + pos / p.page];
     blk = min(max(blk, 0), p.num_blocks - 1);
-    return v.p + (int64_t)blk * v.sb + (int64_t)kvh * v.sh + (int64_t)(first % p.page) * v.sn;
+    return v.p + (int64_t)blk * v.sb + (int64_t)kvh * v.sh + (int64_t)(pos % p.page) * v.sn;
   }
-  return v.p + (int64_t)b * v.sb + (int64_t)kvh * v.sh + (int64_t)first * v.sn;
+  return v.p + (int64_t)b * v.sb + (int64_t)kvh * v.sh + (int64_t)pos * v.sn;
 }
 
 // The load rule: a position at or beyond `end` reads position end - 1 (in bounds) and its V is zeroed.  clamped_first: what to hand cache_base
@@ -200,6 +203,31 @@ template <typename T, int D, int NT> FCSA_DEV void pv_block(const char* v, int r
 // per-row-shift regime, 1 / max(l, l_eps) otherwise
 FCSA_DEV float combine_weight(float m_s, float M) { return exp2f(m_s - M); }
 FCSA_DEV float combine_inv(bool dyn, float l, float l_eps) { return dyn ? (l > 0.f ? 1.f / l : 0.f) : 1.f / fmaxf(l, l_eps); }
+
+// ---- host side: what the launchers of both files share ------------------------------------------------------------------------------
+// The parameter block a kernel entry point takes, and the launch of `Kernel` with that part of the call's one block (a base-class slice;
+// LDS > 0: dynamic LDS, raised once per device) -- so no launcher can hand an entry point another block than the one it declares.
+template <typename P, typename... More> P block_of(void (*)(P, More...));
+template <auto Kernel, int LDS, typename... More>
+hipError_t launch_part(dim3 grid, dim3 block, hipStream_t s, const DecodeStepParams& p, const More&... more) {
+  using P = decltype(block_of(Kernel));
+  if constexpr (LDS > 0) {
+    return launch_with_lds<Kernel>(grid, block, LDS, s, static_cast<const P&>(p), more...);
+  } else {
+    hipLaunchKernelGGL(Kernel, grid, block, 0, s, static_cast<const P&>(p), more...);
+    return hipGetLastError();
+  }
+}
+
+// Where the chunk kernel -- and with it every kernel of an engine step -- is compiled: the 16-bit types at D = 64 / 128.  dispatch_chunk:
+// fn(TypeDim<T, D>) there, hipErrorInvalidValue for every other problem.
+template <typename T, int D> constexpr bool kHasChunkKernel = Traits<T>::ES == 2 && (D == 64 || D == 128);
+template <typename F> hipError_t dispatch_chunk(int dtype, int D, F&& fn) {
+  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
+    if constexpr (kHasChunkKernel<typename decltype(td)::T, decltype(td)::D>) return fn(td);
+    else return hipErrorInvalidValue;
+  });
+}
 
 }  // namespace
 }  // namespace fcsa

@@ -114,10 +114,10 @@ struct NormBwdParams {      // dx = reduce_heads(slab) then (optionally) l2norm 
   float xn_scale;           // x^ = xn_scale * xn   (1/c1 when xn was written with out_scale = c1)
 };
 
-// Decoding against a key/value cache (fcsa_forward_kvcache and its _window, _quant, _varlen and _lse forms; csrc/fcsa_decode.hip).  The C ABI
-// fills ONE block per call -- DecodeRaggedParams, the most derived of the chain below -- and the three launchers hand every kernel entry
-// point the part of it that entry point takes (a base-class slice), so the kernel arguments of each entry point -- and its code -- are what
-// they were before the later features existed.  Views carry BYTE strides; kc / vc are the caches (sb = batch stride, or block stride when
+// Decoding against a key/value cache (fcsa_forward_kvcache and its _window, _quant, _varlen, _lse, _prefill and _step forms;
+// csrc/fcsa_decode.hip, csrc/fcsa_prefill.hip).  The C ABI fills ONE block per call -- DecodeStepParams, the most derived of the chain
+// below -- and the launchers hand every kernel entry point the part of it that entry point takes (a base-class slice), so the kernel
+// arguments of each entry point -- and its code -- are what they were before the later features existed.  Views carry BYTE strides; kc / vc are the caches (sb = batch stride, or block stride when
 // `table` is set), kn / vn the appended rows [B, Hk, new_len, D].
 struct DecodeParams {        // decode_kernel, kv_append_kernel, decode_combine[_lse]_kernel
   View q, o;                // [B, H, N, D]
@@ -166,29 +166,26 @@ struct DecodeLseOut {
   float*  lse;
   int64_t sb, sh, sn;
 };
-// The three jobs of a decode call, each one launcher over every form.  fp8: an e4m3fn cache (q, o and the appended rows f16 or bf16; float32
-// is refused); ragged: a ragged step; the window of a rectangular call is p.window; lse: nullptr, or where the combine also writes the
-// rows' log-sum-exp.
-struct DecodeForm { bool fp8, ragged; };
-hipError_t launch_kv_append(int dtype, int D, DecodeForm f, const DecodeRaggedParams& p, hipStream_t s);
-hipError_t launch_decode(int dtype, int D, DecodeForm f, const DecodeRaggedParams& p, hipStream_t s);
-hipError_t launch_decode_combine(int dtype, int D, DecodeForm f, const DecodeRaggedParams& p, const DecodeLseOut* lse, hipStream_t s);
-// A prompt chunk against the cache (fcsa_forward_kvcache_prefill; csrc/fcsa_prefill.hip): the ragged step's block with slots =
-// fcsa::prefill_slots(total_q, B, G, kPrefillRows), one split and no workspace; f16 / bf16, D = 64 / 128 (anything else: hipErrorInvalidValue).
-// One kernel writes o and, where lse is not nullptr, the rows' log-sum-exp.
-hipError_t launch_prefill(int dtype, int D, const DecodeRaggedParams& p, const DecodeLseOut* lse, hipStream_t s);
 // An engine step (fcsa_forward_kvcache_step): the ragged step's block plus the routing threshold.  Sequence b takes the chunk kernel
 // (step_prefill_kernel) iff G * N_b >= chunk_rows and the decode kernels (step_decode[_fp8]_kernel, step_combine[_lse]_kernel) otherwise;
 // all of them evaluate that on the device from the clamped table (ragged_cu), so every row is written by exactly one of them.
 struct DecodeStepParams : DecodeRaggedParams {   // step_decode[_fp8]_kernel, step_combine[_lse]_kernel, step_prefill_kernel
-  int chunk_rows = 0;
+  int chunk_rows = 0;               // 0 outside a step
 };
-// The three launches of a step after the ragged call's append.  16-bit types and D = 64 / 128 only (anything else: hipErrorInvalidValue).
-// Decode and combine take the block as the ragged call fills it (slots = fcsa::ragged_slots); the chunk launch takes slots =
-// fcsa::prefill_slots(total_q, B, G, kPrefillRows) and writes o (and the lse) itself.  fp8: an e4m3fn cache.
-hipError_t launch_step_decode(int dtype, int D, bool fp8, const DecodeStepParams& p, hipStream_t s);
-hipError_t launch_step_combine(int dtype, int D, bool fp8, const DecodeStepParams& p, const DecodeLseOut* lse, hipStream_t s);
-hipError_t launch_step_prefill(int dtype, int D, bool fp8, const DecodeStepParams& p, const DecodeLseOut* lse, hipStream_t s);
+// The launch layer of the whole family: the C ABI fills ONE block per call, DecodeStepParams -- the most derived type -- and four
+// launchers, one per job, each dispatch dtype, head dim and form once and hand the entry point they pick the base-class slice it declares.
+// fp8: an e4m3fn cache (q, o and the appended rows f16 or bf16; float32 is refused); ragged: a ragged step; step: an engine step, which is
+// a ragged step (step without ragged: hipErrorInvalidValue) and exists for the 16-bit types at D = 64 / 128 (anything else:
+// hipErrorInvalidValue); the window of a rectangular call is p.window; lse: nullptr, or where the rows' log-sum-exp goes as well.
+struct DecodeForm { bool fp8, ragged, step; };
+hipError_t launch_kv_append(int dtype, int D, DecodeForm f, const DecodeStepParams& p, hipStream_t s);      // (a step's append is the ragged call's)
+hipError_t launch_decode(int dtype, int D, DecodeForm f, const DecodeStepParams& p, hipStream_t s);
+hipError_t launch_decode_combine(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeLseOut* lse, hipStream_t s);
+// A prompt chunk against the cache (fcsa_forward_kvcache_prefill, and with f.step the chunk side of an engine step; csrc/fcsa_prefill.hip):
+// the block with slots = fcsa::prefill_slots(total_q, B, G, kPrefillRows), one split and no workspace; f16 / bf16, D = 64 / 128 (anything
+// else: hipErrorInvalidValue).  One kernel writes o and, where lse is not nullptr, the rows' log-sum-exp.  An fp8 cache and a window come
+// with f.step only (fp8 without it: hipErrorInvalidValue).
+hipError_t launch_prefill(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeLseOut* lse, hipStream_t s);
 
 // Merging attention states (fcsa_merge_states, csrc/fcsa_merge.hip): S states (o_s, lse_s) of the rows [n0, n1, n2] -> (o, lse).  o views
 // carry BYTE strides, lse views ELEMENT strides.

@@ -17,6 +17,8 @@
 //                    K becomes K^ exactly as decode_body<FP8> makes it, V's codes are converted to the type on the way into LDS, and the
 //                    epilogue multiplies by v_scale as decode_combine_body<FP8> does.
 // The append before it is the ragged call's (launch_kv_append with the same parameter block).  16-bit types, D = 64 / 128 only.
+// Host side: one launcher, launch_prefill, for both entry points -- one copy of the refusals and of the grid; the form (DecodeForm::step,
+// fp8, and the window sides of the block) picks the entry point, which gets the part of the block it declares (launch_part).
 #include "fcsa_common.cuh"
 #include "fcsa_decode_common.cuh"
 
@@ -281,52 +283,30 @@ __global__ __launch_bounds__(64 * kPrefillWaves, (kStepPrefillWavesPerSimd<T, D,
 
 }  // namespace
 
-// one 4-wave workgroup per (row-tile slot of 128 rows, K/V head); lse: nullptr, or where the rows' log-sum-exp goes as well
-hipError_t launch_prefill(int dtype, int D, const DecodeRaggedParams& p, const DecodeLseOut* lse, hipStream_t s) {
-  if (dtype != FCSA_F16 && dtype != FCSA_BF16) return hipErrorInvalidValue;
-  if (D != 64 && D != 128) return hipErrorInvalidValue;
-  if (p.l2norm && !decode_groups_fast(D, p.groups, 8)) return hipErrorInvalidValue;
-  if ((int64_t)p.slots * p.Hk <= 0) return hipSuccess;
-  const dim3 grid((unsigned)((int64_t)p.slots * p.Hk)), block(64 * kPrefillWaves);
-  const DecodeLseOut lo = lse != nullptr ? *lse : DecodeLseOut{};
-  auto go = [&](auto t, auto d) -> hipError_t {
-    using T = decltype(t);
-    constexpr int DD = decltype(d)::value;
-    return p.dyn ? launch_with_lds<prefill_kernel<T, DD, true>>(grid, block, PrefillLds<DD>::BYTES, s, p, lo)
-                 : launch_with_lds<prefill_kernel<T, DD, false>>(grid, block, PrefillLds<DD>::BYTES, s, p, lo);
-  };
-  using D64 = std::integral_constant<int, 64>;
-  using D128 = std::integral_constant<int, 128>;
-  if (dtype == FCSA_BF16) return D == 64 ? go(BF16{}, D64{}) : go(BF16{}, D128{});
-  return D == 64 ? go(F16{}, D64{}) : go(F16{}, D128{});
-}
-
-// the chunk side of an engine step: p.slots = fcsa::prefill_slots(total_q, B, G, kPrefillRows); the workgroups of decode sequences exit at once
-hipError_t launch_step_prefill(int dtype, int D, bool fp8, const DecodeStepParams& p, const DecodeLseOut* lse, hipStream_t s) {
-  if (dtype != FCSA_F16 && dtype != FCSA_BF16) return hipErrorInvalidValue;
-  if (D != 64 && D != 128) return hipErrorInvalidValue;
-  if (p.l2norm && !decode_groups_fast(D, p.groups, 8)) return hipErrorInvalidValue;
-  if ((int64_t)p.slots * p.Hk <= 0) return hipSuccess;
-  const dim3 grid((unsigned)((int64_t)p.slots * p.Hk)), block(64 * kPrefillWaves);
-  const DecodeLseOut lo = lse != nullptr ? *lse : DecodeLseOut{};
-  // the window test is needed when a side is bounded on the left or strictly inside on the right (open and causal sides are prefill_kernel's)
-  const bool win = p.win_lo < kWinOpen || (p.win_hi < kWinOpen && !(p.causal && p.win_hi == 0));
-  auto go = [&](auto t, auto d) -> hipError_t {
-    using T = decltype(t);
-    constexpr int DD = decltype(d)::value;
+// One 4-wave workgroup per (row-tile slot of 128 rows, K/V head): p.slots = fcsa::prefill_slots(total_q, B, G, kPrefillRows).  lse: nullptr,
+// or where the rows' log-sum-exp goes as well.  f.step: the chunk side of an engine step (the workgroups of decode sequences exit at
+// once), which has the forms for a window and an fp8 cache; without it an fp8 cache is refused -- prefill_kernel has no such form.
+hipError_t launch_prefill(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeLseOut* lse, hipStream_t s) {
+  if (f.fp8 && !f.step) return hipErrorInvalidValue;
+  return dispatch_chunk(dtype, D, [&](auto td) -> hipError_t {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
     constexpr int LDS = PrefillLds<DD>::BYTES;
-    auto form = [&](auto dyn) -> hipError_t {
+    if (p.l2norm && !decode_groups_fast(DD, p.groups, 8)) return hipErrorInvalidValue;
+    if ((int64_t)p.slots * p.Hk <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((int64_t)p.slots * p.Hk)), block(64 * kPrefillWaves);
+    const DecodeLseOut lo = lse != nullptr ? *lse : DecodeLseOut{};
+    // the window test is needed when a side is bounded on the left or strictly inside on the right (open and causal sides are prefill_kernel's)
+    const bool win = p.win_lo < kWinOpen || (p.win_hi < kWinOpen && !(p.causal && p.win_hi == 0));
+    auto go = [&](auto dyn) -> hipError_t {
       constexpr bool DY = decltype(dyn)::value;
-      if (fp8) return launch_with_lds<step_prefill_kernel<T, DD, DY, true, true>>(grid, block, LDS, s, p, lo);
-      if (win) return launch_with_lds<step_prefill_kernel<T, DD, DY, true, false>>(grid, block, LDS, s, p, lo);
-      return launch_with_lds<step_prefill_kernel<T, DD, DY, false, false>>(grid, block, LDS, s, p, lo);
+      if (!f.step) return launch_part<prefill_kernel<T, DD, DY>, LDS>(grid, block, s, p, lo);
+      if (f.fp8) return launch_part<step_prefill_kernel<T, DD, DY, true, true>, LDS>(grid, block, s, p, lo);
+      if (win) return launch_part<step_prefill_kernel<T, DD, DY, true, false>, LDS>(grid, block, s, p, lo);
+      return launch_part<step_prefill_kernel<T, DD, DY, false, false>, LDS>(grid, block, s, p, lo);
     };
-    return p.dyn ? form(std::true_type{}) : form(std::false_type{});
-  };
-  using D64 = std::integral_constant<int, 64>;
-  using D128 = std::integral_constant<int, 128>;
-  if (dtype == FCSA_BF16) return D == 64 ? go(BF16{}, D64{}) : go(BF16{}, D128{});
-  return D == 64 ? go(F16{}, D64{}) : go(F16{}, D128{});
+    return p.dyn ? go(std::true_type{}) : go(std::false_type{});
+  });
 }
 
 }  // namespace fcsa

@@ -24,8 +24,7 @@
 #include <map>
 #include <string>
 
-#include "fcsa_kernels.h"
-#include "../../include/fcsa.h"
+#include "decode_block_text.h"
 
 #define main launch_recorder_main
 #define hipLaunchKernel launch_recorder_launch
@@ -33,42 +32,11 @@
 #undef hipLaunchKernel
 #undef main
 
-static void print_view(const char* name, const fcsa::View& v) {
-  std::printf(" %s=%p/%lld/%lld/%lld", name, (void*)v.p, (long long)v.sb, (long long)v.sh, (long long)v.sn);
-}
-
 extern "C" hipError_t hipLaunchKernel(const void* f, dim3 grid, dim3 block, void** args, size_t lds, hipStream_t s) {
   std::printf("\n  ");
   (void)launch_recorder_launch(f, grid, block, args, lds, s);
   auto it = g_names.find(f);
-  const std::string name = it == g_names.end() ? "" : it->second;
-  const bool ragged = name.find("18DecodeRaggedParams") != std::string::npos, fp8 = ragged || name.find("15DecodeFp8Params") != std::string::npos;
-  const bool win = fp8 || name.find("15DecodeWinParams") != std::string::npos;
-  if (!win && name.find("12DecodeParams") == std::string::npos) return hipSuccess;
-  const auto& p = *static_cast<const fcsa::DecodeParams*>(args[0]);
-  print_view("q", p.q); print_view("o", p.o); print_view("kc", p.kc); print_view("vc", p.vc); print_view("kn", p.kn); print_view("vn", p.vn);
-  std::printf(" seqlens=%p table=%p table_stride=%lld capacity=%d page=%d num_blocks=%d new_len=%d B=%d H=%d Hk=%d G=%d N=%d row_tiles=%d splits=%d"
-              " causal=%d l2norm=%d groups=%d c1=%.9g c2=%.9g l_eps=%.9g dyn=%d ws_o=%p ws_ml=%p",
-              (const void*)p.seqlens, (const void*)p.table, (long long)p.table_stride, p.capacity, p.page, p.num_blocks, p.new_len, p.B, p.H, p.Hk,
-              p.G, p.N, p.row_tiles, p.splits, p.causal, p.l2norm, p.groups, (double)p.c1, (double)p.c2, (double)p.l_eps, p.dyn, (void*)p.ws_o,
-              (void*)p.ws_ml);
-  if (win) {
-    const auto& w = *static_cast<const fcsa::DecodeWinParams*>(args[0]);
-    std::printf(" window=%d win_lo=%d win_hi=%d", w.window, w.win_lo, w.win_hi);
-  }
-  if (fp8) {
-    const auto& q = *static_cast<const fcsa::DecodeFp8Params*>(args[0]);
-    std::printf(" k_scale=%p v_scale=%p ks_b=%lld ks_h=%lld vs_b=%lld vs_h=%lld", (const void*)q.k_scale, (const void*)q.v_scale, (long long)q.ks_b,
-                (long long)q.ks_h, (long long)q.vs_b, (long long)q.vs_h);
-  }
-  if (ragged) {
-    const auto& r = *static_cast<const fcsa::DecodeRaggedParams*>(args[0]);
-    std::printf(" cu_q=%p total_q=%d slots=%d append=%d", (const void*)r.cu_q, r.total_q, r.slots, r.append);
-  }
-  if (name.find("12DecodeLseOut") != std::string::npos) {
-    const auto& l = *static_cast<const fcsa::DecodeLseOut*>(args[1]);
-    std::printf(" lse=%p/%lld/%lld/%lld", (void*)l.lse, (long long)l.sb, (long long)l.sh, (long long)l.sn);
-  }
+  std::printf("%s", decode_args_text(it == g_names.end() ? "" : it->second, args, ScaleText::strides).c_str());
   return hipSuccess;
 }
 

@@ -15,15 +15,13 @@
 // "  append: same as the ragged call" / "  append: none", then "  launches: the ragged call's" where every launch of the two calls is the
 // same text, then "  rc <code> <message>" if the step call was refused.
 #include <dlfcn.h>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <map>
 #include <string>
 #include <vector>
 
-#include "fcsa_kernels.h"
-#include "../../include/fcsa.h"
+#include "decode_block_text.h"
 
 #define main launch_recorder_main
 #define hipLaunchKernel launch_recorder_launch
@@ -34,46 +32,12 @@
 static std::vector<std::string> g_launches;
 static bool g_default_threshold = false;      // the call asked for the library's default chunk_rows: printed as "default", so no fixture pins its value
 
-static void add(std::string& out, const char* fmt, ...) {
-  char buf[1024];
-  va_list ap;
-  va_start(ap, fmt);
-  std::vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  out += buf;
-}
-static void add_view(std::string& out, const char* name, const fcsa::View& v) {
-  add(out, " %s=%p/%lld/%lld/%lld", name, (void*)v.p, (long long)v.sb, (long long)v.sh, (long long)v.sn);
-}
-
 extern "C" hipError_t hipLaunchKernel(const void* f, dim3 grid, dim3 block, void** args, size_t lds, hipStream_t) {
   auto it = g_names.find(f);
   const std::string name = it == g_names.end() ? "?" : it->second;
   std::string out;
   add(out, "; %s %ux%u %u %zu", short_name(name).c_str(), grid.x, grid.y, block.x, lds);
-  const bool step = name.find("16DecodeStepParams") != std::string::npos;
-  if (step || name.find("18DecodeRaggedParams") != std::string::npos) {
-    // (a DecodeStepParams argument starts with its DecodeRaggedParams base)
-    const auto& p = step ? static_cast<const fcsa::DecodeRaggedParams&>(*static_cast<const fcsa::DecodeStepParams*>(args[0]))
-                         : *static_cast<const fcsa::DecodeRaggedParams*>(args[0]);
-    add_view(out, "q", p.q); add_view(out, "o", p.o); add_view(out, "kc", p.kc); add_view(out, "vc", p.vc); add_view(out, "kn", p.kn); add_view(out, "vn", p.vn);
-    add(out, " seqlens=%p table=%p table_stride=%lld capacity=%d page=%d num_blocks=%d new_len=%d B=%d H=%d Hk=%d G=%d N=%d row_tiles=%d splits=%d"
-             " causal=%d l2norm=%d groups=%d c1=%.9g c2=%.9g l_eps=%.9g dyn=%d ws_o=%p ws_ml=%p",
-        (const void*)p.seqlens, (const void*)p.table, (long long)p.table_stride, p.capacity, p.page, p.num_blocks, p.new_len, p.B, p.H, p.Hk, p.G,
-        p.N, p.row_tiles, p.splits, p.causal, p.l2norm, p.groups, (double)p.c1, (double)p.c2, (double)p.l_eps, p.dyn, (void*)p.ws_o, (void*)p.ws_ml);
-    add(out, " window=%d win_lo=%d win_hi=%d k_scale=%p/%lld/%lld v_scale=%p/%lld/%lld cu_q=%p total_q=%d slots=%d append=%d", p.window, p.win_lo,
-        p.win_hi, (const void*)p.k_scale, (long long)p.ks_b, (long long)p.ks_h, (const void*)p.v_scale, (long long)p.vs_b, (long long)p.vs_h,
-        (const void*)p.cu_q, p.total_q, p.slots, p.append);
-    if (step) {
-      const int t = static_cast<const fcsa::DecodeStepParams*>(args[0])->chunk_rows;
-      if (g_default_threshold && t == FCSA_STEP_CHUNK_ROWS) add(out, " chunk_rows=default");
-      else add(out, " chunk_rows=%d", t);
-    }
-  }
-  if (name.find("12DecodeLseOut") != std::string::npos) {
-    const auto& l = *static_cast<const fcsa::DecodeLseOut*>(args[1]);
-    add(out, " lse=%p/%lld/%lld/%lld", (void*)l.lse, (long long)l.sb, (long long)l.sh, (long long)l.sn);
-  }
+  out += decode_args_text(name, args, ScaleText::slashed, g_default_threshold);
   g_launches.push_back(out);
   return hipSuccess;
 }

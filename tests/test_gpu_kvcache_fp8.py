@@ -320,6 +320,79 @@ def test_fp8_append_nan_stays_nan_and_capacity_drops():
     assert (ku[0, 0, :cap - 1] == 0).all()
 
 
+@pytest.mark.parametrize("layout", ["contiguous", "paged"])
+@pytest.mark.parametrize("call", ["rectangular", "ragged"])
+@pytest.mark.parametrize("cache", ["bf16", "fp8"])
+def test_append_rule_on_every_form(cache, call, layout):
+    """The append's one rule -- start at cache_seqlens, drop at the capacity, through the block table when paged -- over every append entry
+    point.  Sequence 0 holds capacity - 1 positions and brings 3 rows: one lands in the last slot, two cross the capacity and are dropped.
+    Sequence 1 holds 5 and takes all of its rows.  The caches live in sentinel-filled arenas (NaN; for fp8 the byte 0xff, a code no finite
+    input quantises to) with a guard of one whole sequence's cache on either side, and sequence 0's last page is not the last in memory,
+    so a row that was not dropped would land inside the arena.  Written slots equal the new rows bit for bit (fp8: the codes of the CPU
+    rule), every other byte of the arenas keeps its bits, and o is finite."""
+    import flash_cosine_sim_attention_amd as F
+    B, H, Hk, D, cap, page, blocks = 2, 2, 1, 32, 32, 16, 4
+    fp8, ragged, is_paged = cache == "fp8", call == "ragged", layout == "paged"
+    seq, counts = [cap - 1, 5], ([3, 1] if ragged else [3, 3])
+    g = torch.Generator().manual_seed(7)
+    rnd = lambda *shape: torch.randn(*shape, generator=g).bfloat16()
+    guard = Hk * cap * D
+    ks, vs = torch.tensor([[0.75], [1.5]]), torch.tensor([[0.3], [2.0]])
+    table = [[2, 0], [3, 1]] if is_paged else None           # shuffled; sequence 0's last page is block 0
+    shape = (blocks, Hk, page, D) if is_paged else (B, Hk, cap, D)
+    n = shape[0] * shape[1] * shape[2] * shape[3]
+
+    def slot(c, b, pos):
+        return c[table[b][pos // page], :, pos % page] if is_paged else c[b, :, pos]
+
+    def code(x, s, b):       # what a slot holds of row x [Hk, D] of sequence b: the row itself, or its codes under the (b, kvh) scales
+        return _rule(x, s[b][:, None]) if fp8 else x
+
+    arenas, caches = [], []
+    for s in (ks, vs):
+        arena = torch.full((2 * guard + n,), 0xff, dtype=torch.uint8) if fp8 else torch.full((2 * guard + n,), float("nan"), dtype=torch.bfloat16)
+        c = arena[guard:guard + n].view(shape)
+        for b in range(B):
+            for pos in range(seq[b]):
+                slot(c, b, pos).copy_(code(rnd(Hk, D), s, b))
+        arenas.append(arena)
+        caches.append(c)
+    total = sum(counts)
+    q, kn, vn = rnd(total, H, D), rnd(total, Hk, D), rnd(total, Hk, D)
+    expect = [a.clone() for a in arenas]
+    for e, new, s in zip(expect, (kn, vn), (ks, vs)):
+        c = e[guard:guard + n].view(shape)
+        for b in range(B):
+            for i in range(counts[b]):
+                if seq[b] + i < cap:
+                    slot(c, b, seq[b] + i).copy_(code(new[sum(counts[:b]) + i], s, b))
+    dev = [a.cuda() for a in arenas]
+    kc, vc = (a[guard:guard + n].view(shape) for a in dev)
+    if fp8:
+        kc, vc = kc.view(E4M3), vc.view(E4M3)
+    kw = dict(cache_seqlens=torch.tensor(seq, dtype=torch.int32, device="cuda"),
+              block_table=torch.tensor(table, dtype=torch.int32, device="cuda") if is_paged else None)
+    if fp8:
+        kw.update(k_scale=ks.cuda(), v_scale=vs.cuda())
+    packed = lambda t: t.cuda()
+    rect = lambda t: t.view(B, 3, -1, D).transpose(1, 2).contiguous().cuda()      # [B * 3, heads, D] -> [B, heads, 3, D]
+    with torch.no_grad():
+        if ragged:
+            cu = torch.tensor([0, 3, 4], dtype=torch.int32, device="cuda")
+            o = F.flash_cosine_sim_attention_varlen_with_kvcache(packed(q), kc, vc, cu, packed(kn), packed(vn), **kw)
+        else:
+            o = F.flash_cosine_sim_attention_with_kvcache(rect(q), kc, vc, rect(kn), rect(vn), **kw)
+    torch.cuda.synchronize()
+    bits = lambda t: t.view(torch.uint8) if fp8 else t.view(torch.int16)
+    for name, got, want, before in zip("kv", dev, expect, arenas):
+        got = bits(got.cpu())
+        assert torch.equal(got[:guard], bits(before)[:guard]) and torch.equal(got[-guard:], bits(before)[-guard:]), f"{name}: a guard band was written"
+        diff = (got != bits(want)).nonzero().flatten()
+        assert diff.numel() == 0, f"{name}: {diff.numel()} elements differ from the expected arena, first at {int(diff[0]) - guard} of the cache"
+        assert (bits(want) != bits(before)).any()      # the call did append
+    assert torch.isfinite(o).all()
+
+
 # ---- window -------------------------------------------------------------------------------------------------------------------------------
 
 def _band(N, M, left, right, causal):

@@ -7,7 +7,8 @@ passes them all.  Run once per library, each in its own process, and compare the
 The table reaches: bf16 / f16 / float32 decode at D 16, 64, 96 (groups 4: the LDS form of the l2norm) and 128, both exponent regimes, l2norm
 off, causal and not, G = 1 and 4, sequence lengths 0, 1, 31, 32, 33, 63, 64, 65, 129, rows without a visible key, a window, an fp8 cache, a
 ragged batch (counts 1, 4, 0, 37), a paged cache with a shuffled table, caches long enough for tens of key splits, and the prefill kernel
-(D 64 / 128) on the same lengths, the ragged batch and a 130-token chunk on 70 cached keys.  Digests are cut to 16 hex digits per tensor;
+(D 64 / 128) on the same lengths, the ragged batch and a 130-token chunk on 70 cached keys, and the engine step on a batch (counts 1, 4, 0,
+37, 130) that takes both routes: 16-bit and fp8 caches, paged, windowed, and with the decode or the chunk launch skipped.  Digests are cut to 16 hex digits per tensor;
 the last line is the SHA-256 over all the uncut ones.  Nothing is asserted: this is no test.
 usage: decode_bits.py [--only SUBSTRING]"""
 import argparse
@@ -93,14 +94,17 @@ def decode(name, dtype, D, H, Hk, N, lens, append, cap=160, page=0, fp8=False, *
     show(name, o=o, o_lse=o2, lse=lse, k=k1, v=v1)
 
 
-def packed(name, fn, dtype, D, H, Hk, counts, cached, append, cap=256, page=0, fp8=False, **kw):
-    """a packed step through fn (the ragged decode call or the prefill call) with return_lse; cached = positions before the append"""
+def packed(name, fn, dtype, D, H, Hk, counts, cached, append, cap=256, page=0, fp8=False, host_cu=False, **kw):
+    """a packed step through fn (the ragged decode call, the prefill call or the engine step) with return_lse; cached = positions before
+    the append; host_cu: the table on the host (the engine step then skips the launch that would find no sequence)"""
     r = Rnd(name, dtype)
     unit = not kw.get("l2norm_qk", True)
     B, total = len(counts), sum(counts)
     q, kc, vc = r(total, H, D, unit=unit), r(B, Hk, cap, D, unit=unit), r(B, Hk, cap, D)
     kn, vn = (r(total, Hk, D, unit=unit), r(total, Hk, D)) if append else (None, None)
     cu = i32([0] + [sum(counts[:b + 1]) for b in range(B)])
+    if host_cu:
+        cu = cu.cpu()
     table = None
     if page:
         kc, vc, table = paged(kc, vc, page, seed=D)
@@ -159,6 +163,17 @@ def cases():
     yield packed, ("ragged_f32_d64_mixed", ragged, "f32", 64, 4, 1, [1, 4, 0, 37], [0, 17, 5, 63], True), dict(scale=120.0, causal=True)
     yield packed, ("ragged_f16_d128_fp8_mixed", ragged, "f16", 128, 8, 2, [1, 4, 0, 37], [0, 17, 5, 63], True), dict(fp8=True, causal=True)
     yield packed, ("ragged_bf16_d64_window_mixed", ragged, "bf16", 64, 8, 2, [1, 4, 0, 37], [0, 17, 5, 63], True), dict(window_size=(20, 0))
+    # the engine step: G = 4, so chunk_rows = 128 sends the sequences of 37 and 130 rows to the chunk kernel and those of 1 and 4 rows to
+    # the decode kernels; a host table with chunk_rows 0 / above every count skips the decode / the chunk launch (no_decode / no_chunk)
+    step = F.flash_cosine_sim_attention_step_with_kvcache
+    mixed = ([1, 4, 0, 37, 130], [0, 17, 5, 63, 70], True)
+    yield packed, ("step_bf16_d64_static_causal_mixed", step, "bf16", 64, 8, 2, *mixed), dict(chunk_rows=128, causal=True)
+    yield packed, ("step_f16_d128_per_row_full_mixed", step, "f16", 128, 8, 2, *mixed), dict(chunk_rows=128, scale=16.0)
+    yield packed, ("step_f16_d128_fp8_mixed", step, "f16", 128, 8, 2, *mixed), dict(chunk_rows=128, fp8=True, causal=True)
+    yield packed, ("step_bf16_d64_fp8_paged16_mixed", step, "bf16", 64, 8, 2, *mixed), dict(chunk_rows=128, fp8=True, page=16)
+    yield packed, ("step_bf16_d64_window_mixed", step, "bf16", 64, 8, 2, *mixed), dict(chunk_rows=128, window_size=(20, 0))
+    yield packed, ("step_bf16_d128_no_decode", step, "bf16", 128, 8, 2, *mixed), dict(chunk_rows=0, host_cu=True, causal=True)
+    yield packed, ("step_f16_d64_no_chunk", step, "f16", 64, 8, 2, *mixed), dict(chunk_rows=10 ** 6, host_cu=True, causal=True)
 
 
 def main():
