@@ -4,7 +4,8 @@ lucidrains/flash-cosine-sim-attention).  Same public names as the reference pack
 from .ops import (flash_cosine_sim_attention, flash_cosine_sim_attention_local, flash_cosine_sim_attention_varlen,
                   flash_cosine_sim_attention_with_kvcache, flash_cosine_sim_attention_varlen_with_kvcache,
                   flash_cosine_sim_attention_prefill_with_kvcache,
-                  flash_cosine_sim_attention_step_with_kvcache,
+                  flash_cosine_sim_attention_step_with_kvcache, flash_cosine_sim_attention_tree_with_kvcache,
+                  kvcache_keep_accepted,
                   flash_cosine_sim_attention_with_shared_prefix, merge_attention_states,
                   flash_cosine_sim_attention_with_lse, merge_attention_states_with_grad,
                   plain_cosine_sim_attention, l2norm_tensors, FlashCosineSimAttention)
@@ -14,7 +15,8 @@ __version__ = '0.3.0'
 __all__ = ['flash_cosine_sim_attention', 'flash_cosine_sim_attention_local', 'flash_cosine_sim_attention_varlen',
            'flash_cosine_sim_attention_with_kvcache', 'flash_cosine_sim_attention_varlen_with_kvcache',
            'flash_cosine_sim_attention_prefill_with_kvcache',
-           'flash_cosine_sim_attention_step_with_kvcache',
+           'flash_cosine_sim_attention_step_with_kvcache', 'flash_cosine_sim_attention_tree_with_kvcache',
+           'kvcache_keep_accepted',
            'flash_cosine_sim_attention_with_shared_prefix', 'merge_attention_states',
            'flash_cosine_sim_attention_with_lse', 'merge_attention_states_with_grad',
            'plain_cosine_sim_attention', 'l2norm_tensors', 'debug', 'FlashCosineSimAttention']

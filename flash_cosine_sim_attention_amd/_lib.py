@@ -90,6 +90,7 @@ MERGE_MAX_STATES = _MACROS["FCSA_MERGE_MAX_STATES"]
 MergeBackwardArgs = _STRUCTS["fcsa_merge_backward_args"]
 KvCacheStep = _STRUCTS["fcsa_kvcache_step"]
 STEP_CHUNK_ROWS = _MACROS["FCSA_STEP_CHUNK_ROWS"]
+TreeMask = _STRUCTS["fcsa_tree_mask"]
 
 
 EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fcsa_forward_workspace_bytes", "fcsa_forward_needs_qn",
@@ -100,7 +101,8 @@ EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fc
            "fcsa_forward_kvcache_quant_workspace_bytes", "fcsa_forward_kvcache_varlen", "fcsa_forward_kvcache_varlen_workspace_bytes",
            "fcsa_forward_kvcache_lse", "fcsa_merge_states", "fcsa_forward_kvcache_prefill",
            "fcsa_attention_lse", "fcsa_backward_state", "fcsa_merge_states_backward",
-           "fcsa_forward_kvcache_step", "fcsa_forward_kvcache_step_workspace_bytes")
+           "fcsa_forward_kvcache_step", "fcsa_forward_kvcache_step_workspace_bytes",
+           "fcsa_forward_kvcache_tree", "fcsa_kvcache_compact")
 
 _lib = None
 
@@ -209,6 +211,13 @@ def load():
         lib.fcsa_forward_kvcache_step_workspace_bytes.argtypes = [C.POINTER(Problem), C.POINTER(KvCache), C.POINTER(Varlen),
                                                                   C.POINTER(KvCacheQuant), C.POINTER(Window), C.POINTER(KvCacheStep)]
         lib.fcsa_forward_kvcache_step_workspace_bytes.restype = C.c_size_t
+    if hasattr(lib, "fcsa_forward_kvcache_tree"):      # (likewise: an FCSA_LIB build from before tree attention)
+        lib.fcsa_forward_kvcache_tree.argtypes = [C.POINTER(ForwardArgs), C.POINTER(KvCache), C.POINTER(Varlen), C.POINTER(KvCacheQuant),
+                                                  C.POINTER(TreeMask), C.POINTER(LseOut)]
+        lib.fcsa_forward_kvcache_tree.restype = C.c_int
+        lib.fcsa_kvcache_compact.argtypes = [C.POINTER(KvCache), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
+                                             C.c_void_p, C.c_void_p]
+        lib.fcsa_kvcache_compact.restype = C.c_int
     lib.fcsa_last_error.argtypes = []
     lib.fcsa_last_error.restype = C.c_char_p
     ver = lib.fcsa_debug(None, 0)

@@ -110,6 +110,16 @@ def _register_fakes():
           causal, l2norm_qk, groups, window_left, window_right, chunk_rows, max_decode_tokens, no_decode, no_chunk):
         return q.new_empty(q.shape), q.new_empty(q.shape[:-1], dtype=torch.float32)
 
+    # and tree attention for speculative decoding (fcsa_tree): the ragged lse op's results; the compaction returns nothing
+    @torch.library.register_fake("fcsa_tree::kvcache_tree_forward")
+    def _(q, k_cache, v_cache, cu_seqlens_q, tree_mask, k_new, v_new, cache_seqlens, block_table, k_scale, v_scale, max_seqlen_q, max_seqlen_k,
+          scale, l2norm_qk, groups):
+        return q.new_empty(q.shape), q.new_empty(q.shape[:-1], dtype=torch.float32)
+
+    @torch.library.register_fake("fcsa_tree::kvcache_compact")
+    def _(k_cache, v_cache, cache_seqlens, accepted, num_accepted, block_table):
+        return None
+
     @torch.library.register_fake("fcsa::merge_states")
     def _(os, lses):
         return os[0].new_empty(os[0].shape), os[0].new_empty(os[0].shape[:-1], dtype=torch.float32)

@@ -74,13 +74,18 @@ def window_index(window_size):
 
 
 def attention_forward_cpu(q, k, v, mask=None, attn_bias=None, scale=8.0, groups=1, causal=False, l2norm_qk=True,
-                          attn_bias_batch_dim=False, row_block=256, key_block=1024, window_size=(-1, -1), return_lse=False):
+                          attn_bias_batch_dim=False, row_block=256, key_block=1024, window_size=(-1, -1), return_lse=False, tail_mask=None):
     """Forward-only blockwise cosine-sim attention on host tensors.  Same argument meaning as the GPU operator.
     window_size = (left, right): query i sees key j iff i + (M - N) - left <= j <= i + (M - N) + right (-1: unbounded; causal caps
     right at 0); the key blocks outside a row block's band are never touched.
     return_lse: also return the rows' log-sum-exp, float32 of q's shape without the feature dim: log(sum over the visible keys of
-    exp(logit)), from the running max and row sum the loop holds; -inf for a row without a visible key."""
+    exp(logit)), from the running max and row sum the loop holds; -inf for a row without a visible key.
+    tail_mask: bool [N, T], T <= M (a tree step, `tree_tail`): query i sees every key before the last T and key M - T + t iff tail_mask[i, t].
+    It takes no causal, window, mask or bias.  A row block stops at the last key any of its rows sees, as a causal one does, and an
+    invisible logit is -inf either way, so a lower-triangular mask gives the causal call's bits and a full one the plain call's."""
     w_left, w_right = window_sides(window_size, causal)
+    if tail_mask is not None and (causal or mask is not None or attn_bias is not None or tuple(window_index(window_size)) != (-1, -1)):
+        raise ValueError("tail_mask states the visibility: no causal, window_size, mask or attn_bias with it")
     if tuple(window_index(window_size)) != (-1, -1) and (mask is not None or attn_bias is not None):      # (as the C ABI: any window)
         raise ValueError("a sliding window takes no mask and no attn_bias")
     for name, t in (("q", q), ("k", k), ("v", v), ("attn_bias", attn_bias)):
@@ -122,6 +127,10 @@ def attention_forward_cpu(q, k, v, mask=None, attn_bias=None, scale=8.0, groups=
         r1 = min(N, r0 + row_block)
         last = M if w_right is None else min(M, r1 + offset + w_right)      # keys >= last are invisible to every row of this block
         first = 0 if w_left is None else min(max(r0 + offset - w_left, 0), max(last, 0))     # ... and so are keys < first
+        if tail_mask is not None:
+            tail0 = M - tail_mask.shape[1]
+            cols = tail_mask[r0:r1].any(dim=0).nonzero()
+            last = tail0 + (int(cols.max()) + 1 if cols.numel() else 0)
         rows = qf[:, :, r0:r1]
         a, s, t = acc[:, :, r0:r1], total[:, :, r0:r1], top[:, :, r0:r1]
         for c0 in range(first, max(last, 0), key_block):
@@ -139,6 +148,9 @@ def attention_forward_cpu(q, k, v, mask=None, attn_bias=None, scale=8.0, groups=
                 visible = inside if visible is None else (visible & inside)
             if keep_keys is not None:
                 visible = keep_keys[..., c0:c1] if visible is None else (visible & keep_keys[..., c0:c1])
+            if tail_mask is not None and c1 > tail0:
+                visible = torch.ones((r1 - r0, c1 - c0), dtype=torch.bool)
+                visible[:, max(c0, tail0) - c0:] = tail_mask[r0:r1, max(c0, tail0) - tail0:c1 - tail0]
             if visible is not None:
                 logits = logits.masked_fill(~visible, float("-inf"))
             t_new = torch.maximum(t, logits.amax(dim=-1, keepdim=True))
@@ -240,13 +252,14 @@ def quantise_e4m3(x, scale):
 
 
 def attention_forward_kvcache_cpu(q, k_cache, v_cache, k_new, v_new, seqlens, block_table=None, scale=8.0, groups=1, causal=False,
-                                  l2norm_qk=True, window_size=(-1, -1), k_scale=None, v_scale=None, return_lse=False):
+                                  l2norm_qk=True, window_size=(-1, -1), k_scale=None, v_scale=None, return_lse=False, tree_words=None):
     """Forward-only path of `flash_cosine_sim_attention_with_kvcache` on host tensors: the append as an indexed copy, then the dense CPU
     forward of every sequence over its first L_b = seqlens[b] + N_new cached positions (o = 0 where L_b == 0).  seqlens: host ints.
     k_scale / v_scale (float32 [B, Hk], both or neither): the caches are float8_e4m3fn codes meaning scale * code -- the append quantises
     (quantise_e4m3), and each sequence's keys and values are dequantised to float32 for the dense forward, whose result is cast to q's
     dtype.  return_lse: also the rows' log-sum-exp, float32 [B, H, N] (-inf where a row sees no key; k_scale is inside the logits, v_scale
-    is not)."""
+    is not).  tree_words: int64 [N] (batch 1, the varlen path below): the rows' visibility words over the last N positions (`tree_tail`) in
+    place of causal."""
     fp8 = k_scale is not None
     if k_new is not None:
         if fp8:
@@ -267,18 +280,35 @@ def attention_forward_kvcache_cpu(q, k_cache, v_cache, k_new, v_new, seqlens, bl
         if fp8:
             qb = qb.float()
             kb, vb = kb.float() * k_scale[b][None, :, None, None], vb.float() * v_scale[b][None, :, None, None]
+        tail = None if tree_words is None else tree_tail(tree_words, length)
         out[b:b + 1], lse[b:b + 1] = attention_forward_cpu(qb, kb, vb, scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk,
-                                                           window_size=window_size, return_lse=True)
+                                                           window_size=window_size, return_lse=True, tail_mask=tail)
     return (out, lse) if return_lse else out
+
+
+TREE_MAX_TOKENS = 64
+
+
+def tree_tail(words, length):
+    """The visibility words of a tree step's N <= 64 rows (int64 [N], read as unsigned: bit t of word i set = query i sees the step's token
+    t, cache position length - N + t) as the bool matrix [N, T] over the last T = min(N, length) positions: positions below 0 do not exist."""
+    n = words.numel()
+    bits = ((words.reshape(n, 1) >> torch.arange(TREE_MAX_TOKENS, dtype=torch.int64)) & 1).bool()[:, :n]      # (>> is arithmetic: & 1 keeps the bit)
+    return bits[:, n - min(n, length):]
 
 
 def attention_forward_kvcache_varlen_cpu(q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, seqlens, block_table=None, scale=8.0, groups=1,
                                          causal=False, l2norm_qk=True, window_size=(-1, -1), k_scale=None, v_scale=None,
-                                         return_lse=False):
+                                         return_lse=False, tree_mask=None):
     """Forward-only path of `flash_cosine_sim_attention_varlen_with_kvcache` on host tensors: packed q [total_q, H, D] and k_new / v_new
     [total_q, Hk, D] with a validated host table; sequence b's N_b rows run through `attention_forward_kvcache_cpu` as a batch-1 call on
     its own cache (a view: the append lands in the caller's caches), so its rows and its cache slots are exactly what the equal-N path
-    gives for that sequence alone.  seqlens: host ints, tokens cached before the append.  return_lse: also the rows' log-sum-exp, float32 [total_q, H]."""
+    gives for that sequence alone.  seqlens: host ints, tokens cached before the append.  return_lse: also the rows' log-sum-exp, float32 [total_q, H].
+    tree_mask (`flash_cosine_sim_attention_tree_with_kvcache`): int64 [total_q] packed like q (no causal, no window with it): with
+    P_b = L_b - N_b every query of sequence b sees the cache positions before P_b, and query i sees position P_b + t iff bit t of its word is set; a sequence with N_b > 64 ignores its words and is
+    causal."""
+    if tree_mask is not None and (causal or tuple(window_index(window_size)) != (-1, -1)):
+        raise ValueError("tree_mask states the visibility: no causal and no window_size with it")
     out = torch.zeros_like(q)
     lse = torch.full(q.shape[:-1], float("-inf"), dtype=torch.float32)
     cq = cu_seqlens_q.tolist()
@@ -290,9 +320,10 @@ def attention_forward_kvcache_varlen_cpu(q, k_cache, v_cache, cu_seqlens_q, k_ne
         paged = block_table is not None
         kc, vc = (k_cache, v_cache) if paged else (k_cache[b:b + 1], v_cache[b:b + 1])
         quant = {} if k_scale is None else dict(k_scale=k_scale[b:b + 1], v_scale=v_scale[b:b + 1])
+        words = tree_mask[lo:hi] if tree_mask is not None and hi - lo <= TREE_MAX_TOKENS else None
         o, l = attention_forward_kvcache_cpu(rows(q), kc, vc, rows(k_new), rows(v_new), [seqlens[b]], block_table[b:b + 1] if paged else None,
-                                             scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, window_size=window_size,
-                                             return_lse=True, **quant)
+                                             scale=scale, groups=groups, causal=causal or (tree_mask is not None and words is None),
+                                             l2norm_qk=l2norm_qk, window_size=window_size, return_lse=True, tree_words=words, **quant)
         out[lo:hi] = o[0].permute(1, 0, 2)
         lse[lo:hi] = l[0].permute(1, 0)
     return (out, lse) if return_lse else out
@@ -323,3 +354,27 @@ def merge_attention_states_cpu(os, lses):
     out = torch.where(live.unsqueeze(-1), acc / total.unsqueeze(-1), zero)
     out_lse = torch.where(live, safe + torch.log(total), torch.full_like(top, float("-inf")))
     return out.to(os[0].dtype).contiguous(), out_lse.contiguous()
+
+
+def kvcache_keep_accepted_cpu(k_cache, v_cache, seqlens, accepted, num_accepted, block_table=None):
+    """`kvcache_keep_accepted` on host tensors, in place: for i < num_accepted[b] the row at cache position seqlens[b] + accepted[b][i] moves
+    to seqlens[b] + i, in K and in V, for every K/V head.  Every source row is read before the first is written (destination i of one move
+    can be the source of another); a move whose source or destination is at or beyond the capacity is skipped.  seqlens, accepted and
+    num_accepted: host lists (validated by the caller).  Rows move as they are, so fp8 caches go through their uint8 views."""
+    page = k_cache.shape[2]
+    capacity = page * block_table.shape[1] if block_table is not None else k_cache.shape[2]
+    if k_cache.dtype == getattr(torch, "float8_e4m3fn", None):
+        k_cache, v_cache = k_cache.view(torch.uint8), v_cache.view(torch.uint8)
+
+    def row(cache, b, pos):
+        if block_table is None:
+            return cache[b, :, pos]
+        return cache[int(block_table[b, pos // page]), :, pos % page]
+
+    for b, start in enumerate(seqlens):
+        moves = [(start + accepted[b][i], start + i) for i in range(num_accepted[b])]
+        moves = [(src, dst) for src, dst in moves if src != dst and src < capacity and dst < capacity]
+        held = [(row(k_cache, b, src).clone(), row(v_cache, b, src).clone()) for src, _ in moves]
+        for (_, dst), (kr, vr) in zip(moves, held):
+            row(k_cache, b, dst).copy_(kr)
+            row(v_cache, b, dst).copy_(vr)

@@ -330,7 +330,8 @@ int fcsa_debug(char* buf, size_t buf_bytes) {
              "fwd_dyn(per-row shift),bwd_dq(+split-key; key-split form on 8 waves),bwd_dkv(+lean; query-split form on 8 waves; grouped-query K/V head sweep),bwd_dbias,finalize,kv_append+decode+decode_combine(kv cache),"
              "window(fwd_win,bwd_dq_win,bwd_dkv_win,decode_win: sliding-window forms),"
              "kv_append_fp8+decode_fp8+decode_combine_fp8(e4m3fn kv cache, f16/bf16 queries),"
-             "kv_append_ragged+decode_ragged+decode_combine_ragged(+_fp8: packed queries with per-sequence counts against the kv cache) kv_heads=divisors of heads",
+             "kv_append_ragged+decode_ragged+decode_combine_ragged(+_fp8: packed queries with per-sequence counts against the kv cache),"
+             "decode_tree(+_fp8: a per-row bit set over the step's tokens, tree attention for speculative decoding)+kv_compact(the accepted path to the front of its slots) kv_heads=divisors of heads",
              FCSA_ABI_VERSION);
   }
   return FCSA_ABI_VERSION;
@@ -434,6 +435,7 @@ struct DecodeCall {
   const fcsa_window* w;               // a sliding window as the caller gave it, or NULL
   const fcsa_lse_out* lse;            // where the combine also writes the rows' log-sum-exp (fcsa_forward_kvcache_lse), or NULL
   const fcsa_kvcache_step* step = nullptr;      // an engine step (fcsa_forward_kvcache_step): the routing of a ragged step, or NULL
+  const fcsa_tree_mask* tree = nullptr;         // a tree step (fcsa_forward_kvcache_tree): the visibility words of a ragged step, or NULL
 };
 
 // The window of a decode call as the kernels take it.  A rectangular call is normalised (fcsa::win_normalise): a window that hides nothing
@@ -657,6 +659,9 @@ int chunk_launch(const LaunchName& n, const DecodeCall& c, fcsa::DecodeForm form
   return timed(n.name, n.what, s, [&] { return fcsa::launch_prefill(c.a->p.dtype, c.a->p.dim_head, form, dp, c.lse != nullptr ? &lo : nullptr, s); });
 }
 
+// c.tree (a tree step): the ragged call without a window and without `causal` -- its checks, plan, workspace, append and combine -- with the
+// decode launch on the entry points that read the visibility words.
+constexpr LaunchName kTreeName[2] = {{"decode_tree", "decode (tree)"}, {"decode_tree_fp8", "decode (tree)"}};
 int decode_call(const DecodeCall& c) {
   const bool ragged = c.seqs != nullptr, fp8 = c.qz != nullptr;
   // the checks, once; a rectangular call's window comes after its cache checks, a ragged step's among its own arguments
@@ -685,8 +690,14 @@ int decode_call(const DecodeCall& c) {
   hipStream_t s = static_cast<hipStream_t>(a->stream);
   if (int rc = append_launch(c, form, dp, s)) return rc;
   if (!rows) return FCSA_OK;
-  const LaunchName& n = kDecodeName[ragged][fp8];
-  if (int rc = timed(n.name, n.what, s, [&] { return fcsa::launch_decode(p.dtype, p.dim_head, form, dp, s); })) return rc;
+  if (c.tree != nullptr) {
+    const LaunchName& n = kTreeName[fp8];
+    const fcsa::DecodeTreeMask tm = {c.tree->mask};
+    if (int rc = timed(n.name, n.what, s, [&] { return fcsa::launch_decode_tree(p.dtype, p.dim_head, form, dp, tm, s); })) return rc;
+  } else {
+    const LaunchName& n = kDecodeName[ragged][fp8];
+    if (int rc = timed(n.name, n.what, s, [&] { return fcsa::launch_decode(p.dtype, p.dim_head, form, dp, s); })) return rc;
+  }
   const LaunchName& m = kCombineName[ragged][fp8][c.lse != nullptr];
   return timed(m.name, m.what, s, [&] { return fcsa::launch_decode_combine(p.dtype, p.dim_head, form, dp, c.lse != nullptr ? &lo : nullptr, s); });
 }
@@ -839,6 +850,57 @@ int fcsa_forward_kvcache_lse(const fcsa_forward_args* a, const fcsa_kvcache* kv,
   const bool rows = a->p.batch > 0 && a->p.heads > 0 && (seqs != nullptr ? seqs->total_q > 0 : a->p.q_len > 0);
   if (rows && lse->lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_lse: lse: null pointer");
   return decode_call({a, kv, seqs, qz, w, lse});
+}
+
+int fcsa_forward_kvcache_tree(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_kvcache_quant* qz,
+                              const fcsa_tree_mask* tree, const fcsa_lse_out* lse) {
+  if (a == nullptr || kv == nullptr || seqs == nullptr || tree == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_tree: null argument");
+  if (a->p.causal != 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_tree: causal must be 0 (the mask states the visibility)");
+  if (tree->reserved != 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_tree: reserved (%lld) is 0", (long long)tree->reserved);
+  const bool rows = a->p.batch > 0 && a->p.heads > 0 && seqs->total_q > 0;
+  if (rows && tree->mask == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_tree: mask: null pointer");
+  if ((reinterpret_cast<uintptr_t>(tree->mask) & 7) != 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_tree: mask not 8-byte aligned");
+  if (rows && lse != nullptr && lse->lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_tree: lse: null pointer");
+  return decode_call({a, kv, seqs, qz, nullptr, lse, nullptr, tree});
+}
+
+int fcsa_kvcache_compact(const fcsa_kvcache* kv, int32_t batch, int32_t kv_heads, int32_t dim_head, int32_t elem_bytes, const int32_t* accepted,
+                         int64_t accepted_stride, int32_t max_accepted, const int32_t* num_accepted, void* stream) {
+  if (kv == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_compact: null argument");
+  if (batch < 0 || kv_heads < 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_compact: negative size (B=%d Hk=%d)", batch, kv_heads);
+  if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_compact: elem_bytes %d not in {1, 2, 4}", elem_bytes);
+  if (!dim_ok(dim_head)) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_compact: dim_head %d not in {16, 32, 64, 96, 128}", dim_head);
+  if (max_accepted < 1 || max_accepted > fcsa::kCompactSlots)
+    return fail(FCSA_ERR_INVALID_ARG, "kvcache_compact: max_accepted (%d) outside [1, %d]", max_accepted, fcsa::kCompactSlots);
+  if (accepted_stride < max_accepted) return fail(FCSA_ERR_INVALID_ARG, "kvcache_compact: accepted row stride %lld below %d entries", (long long)accepted_stride, max_accepted);
+  if (kv->capacity < 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_compact: negative capacity (%d)", kv->capacity);
+  if (kv->block_table != nullptr) {
+    if (kv->page_size <= 0 || kv->page_size % 16 != 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_compact: page_size %d must be a positive multiple of 16", kv->page_size);
+    if (kv->capacity % kv->page_size != 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_compact: capacity %d is not a whole number of pages of %d", kv->capacity, kv->page_size);
+    if (kv->capacity > 0 && kv->num_blocks < 1) return fail(FCSA_ERR_INVALID_ARG, "kvcache_compact: paged cache without blocks");
+    if (kv->block_table_stride < kv->capacity / kv->page_size) return fail(FCSA_ERR_INVALID_ARG, "kvcache_compact: block_table row stride %lld below %d entries", (long long)kv->block_table_stride, kv->capacity / kv->page_size);
+  } else if (kv->page_size != 0) {
+    return fail(FCSA_ERR_INVALID_ARG, "kvcache_compact: page_size %d without a block_table", kv->page_size);
+  }
+  if (batch == 0 || kv_heads == 0 || kv->capacity == 0) return FCSA_OK;      // no row to move
+  if (accepted == nullptr || num_accepted == nullptr || kv->cache_seqlens == nullptr)
+    return fail(FCSA_ERR_INVALID_ARG, "kvcache_compact: null accepted, num_accepted or cache_seqlens");
+  if (int rc = check_tensor("k_cache", kv->k_cache, elem_bytes, true)) return rc;
+  if (int rc = check_tensor("v_cache", kv->v_cache, elem_bytes, true)) return rc;
+  if ((int64_t)batch * kv_heads > INT32_MAX) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_compact: grid above 2^31 workgroups");
+  fcsa::DecodeParams dp{};
+  dp.kc = view(kv->k_cache, elem_bytes);
+  dp.vc = view(kv->v_cache, elem_bytes);
+  dp.seqlens = kv->cache_seqlens;
+  dp.table = kv->block_table;
+  dp.table_stride = kv->block_table_stride;
+  dp.capacity = kv->capacity;
+  dp.page = kv->block_table != nullptr ? kv->page_size : 0;
+  dp.num_blocks = kv->num_blocks;
+  dp.B = batch; dp.Hk = kv_heads;
+  const fcsa::CompactParams cp = {accepted, num_accepted, accepted_stride, max_accepted, dim_head * elem_bytes};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return timed("kv_compact", "kv compact", s, [&] { return fcsa::launch_kv_compact(dp, cp, s); });
 }
 
 int fcsa_forward_kvcache_prefill(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_lse_out* lse) {

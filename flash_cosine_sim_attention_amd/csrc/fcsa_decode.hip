@@ -19,6 +19,9 @@
 // every code is exact in f16 and bf16, so the operands of both MFMA products are what a 16-bit cache holding the codes would feed.
 // An engine step (fcsa_forward_kvcache_step) has the decode and combine entry points of its decode side here --
 // step_decode[_fp8]_kernel (decode_body with STEP), step_combine[_lse]_kernel -- and its chunk side in fcsa_prefill.hip.
+// A tree step (fcsa_forward_kvcache_tree) is a ragged step whose decode launch reads a 64-bit visibility word per
+// packed row -- decode_tree[_fp8]_kernel (decode_body with TREE; launch_decode_tree) -- between the ragged call's own append and combine;
+// kv_compact_kernel (fcsa_kvcache_compact; launch_kv_compact) then moves the accepted path to the front of the slots the step appended.
 // The append is written once for every form: where a new row goes (append_pos: the cache_seqlens clamp and the drop at the capacity), the
 // address of that position (cache_base of fcsa_decode_common.cuh, the readers' own rule) and the row write (append_chunk: a copy, or the
 // quantisation of an fp8 cache).  The three append entry points are the index decomposition of their layout and calls to those.
@@ -136,12 +139,18 @@ template <typename T, int D, bool FP8 = false> struct DecodeRegs {
 // and from there on runs the code below with N = N_b.  Always WIN, with open sides when the call has no window.
 // STEP (step_decode_kernel, step_decode_fp8_kernel): the decode side of an engine step -- a ragged step whose workgroups leave the sequences
 // of step_is_chunk to the chunk kernel (fcsa_prefill.hip) and exit as soon as they know their sequence.
-template <typename T, int D, bool DYN, bool GEN, bool WIN, bool FP8 = false, bool RAGGED = false, bool STEP = false>
+// TREE (decode_tree_kernel, decode_tree_fp8_kernel): a tree step -- a ragged step without a window whose rows bring a 64-bit word each
+// (tm.words, loaded once per lane next to last_key).  With P = L - N: a key before the step (key < P) is visible to every row, the step's
+// token t (key P + t) iff bit t of the row's word is set; a sequence with N > 64 ignores its words and is causal.  Only the per-logit test
+// differs from the ragged form: key range, splits, loads, both products and the partials are its own.
+template <typename T, int D, bool DYN, bool GEN, bool WIN, bool FP8 = false, bool RAGGED = false, bool STEP = false, bool TREE = false>
 FCSA_DEV void decode_body(const std::conditional_t<STEP, DecodeStepParams, std::conditional_t<RAGGED, DecodeRaggedParams,
-                                                   std::conditional_t<FP8, DecodeFp8Params, std::conditional_t<WIN, DecodeWinParams, DecodeParams>>>>& p) {
+                                                   std::conditional_t<FP8, DecodeFp8Params, std::conditional_t<WIN, DecodeWinParams, DecodeParams>>>>& p,
+                          const DecodeTreeMask& tm = DecodeTreeMask{}) {
   static_assert(!FP8 || Traits<T>::ES == 2, "an fp8 cache is read with 16-bit queries");
   static_assert(!RAGGED || WIN, "the ragged entry points carry the window fields");
   static_assert(!STEP || RAGGED, "a step is a ragged step");
+  static_assert(!TREE || (RAGGED && !STEP), "a tree step is a ragged step");
   typedef DecodeRegs<T, D, FP8> R;
   typedef DecodeLds<D, R::ES, GEN> LP;
   constexpr int ES = R::ES, UE = R::UE, NJ = R::NJ, CPR = R::CPR, VCH = R::VCH;
@@ -187,6 +196,13 @@ FCSA_DEV void decode_body(const std::conditional_t<STEP, DecodeStepParams, std::
   const int g = row_ok ? r / N : 0, qi = row_ok ? r % N : 0;
   const int h = kvh * p.G + g;
   const int last_key = L - N + qi;               // causal: key j is visible iff j <= last_key
+  // TREE: the row's word (no bit for a row the tile does not have), the first position of the step and whether the words count
+  [[maybe_unused]] uint64_t word = 0;
+  [[maybe_unused]] const int P = L - N;
+  [[maybe_unused]] const bool use_bits = N <= kCompactSlots;
+  if constexpr (TREE) {
+    if (row_ok) word = tm.words[q0 + qi];
+  }
   const int gs = D / p.groups;
   float* norm_scratch = reinterpret_cast<float*>(smem + LP::VBYTES);
   auto normalise = [&](float (&xr)[NJ][UE]) {
@@ -263,6 +279,7 @@ FCSA_DEV void decode_body(const std::conditional_t<STEP, DecodeStepParams, std::
         const int key = kb + 16 * sb + 4 * hi + rr;
         bool vis = key < end && (!p.causal || key <= last_key);
         if constexpr (WIN) vis = key < end && key <= last_key + p.win_hi && key >= last_key - p.win_lo;
+        if constexpr (TREE) vis = key < end && (key < P || (use_bits ? ((word >> ((key - P) & 63)) & 1) != 0 : key <= last_key));
         s[sb][rr] = vis ? s[sb][rr] * smul : -INFINITY;
       }
     }
@@ -358,6 +375,15 @@ __global__ __launch_bounds__(64) void decode_ragged_kernel(DecodeRaggedParams p)
 template <typename T, int D, bool DYN, bool GEN>
 __global__ __launch_bounds__(64) void decode_ragged_fp8_kernel(DecodeRaggedParams p) {
   decode_body<T, D, DYN, GEN, true, true, true>(p);
+}
+// a tree step (launch_decode_tree): the ragged entry points' block, and the visibility words as a second argument
+template <typename T, int D, bool DYN, bool GEN>
+__global__ __launch_bounds__(64) void decode_tree_kernel(DecodeRaggedParams p, DecodeTreeMask tm) {
+  decode_body<T, D, DYN, GEN, true, false, true, false, true>(p, tm);
+}
+template <typename T, int D, bool DYN, bool GEN>
+__global__ __launch_bounds__(64) void decode_tree_fp8_kernel(DecodeRaggedParams p, DecodeTreeMask tm) {
+  decode_body<T, D, DYN, GEN, true, true, true, false, true>(p, tm);
 }
 // the decode side of an engine step (launch_decode with the step form): 16-bit types and D = 64 / 128, where every group width is reduced in registers
 template <typename T, int D, bool DYN>
@@ -575,6 +601,45 @@ __global__ __launch_bounds__(256) void kv_append_ragged_kernel(DecodeRaggedParam
   append_chunk<T, FP8>(p, b, kvh, pos, ch, p.kn.p + (int64_t)kvh * p.kn.sh + tok * p.kn.sn, p.vn.p + (int64_t)kvh * p.vn.sh + tok * p.vn.sn);
 }
 
+// ---- compaction of the accepted path of a tree step (fcsa_kvcache_compact) -----------------------------------------------------------
+// One workgroup owns ALL moves of a (sequence, K/V head) pair: move i takes the row at position start + accepted[b, i] to start + i, K and
+// V alike, start = clamp(cache_seqlens[b], 0, capacity).  Destination i of one move can be the source of another (accepted = [1, 2, 3, ...]
+// shifts everything by one), so the workgroup reads every source row into LDS, passes a barrier and only then writes: no move is split
+// across workgroups, and no write can reach a row another move still has to read.  Rows are bytes (16-byte chunks): every cache type, fp8
+// codes included.  The tables are clamped -- num_accepted to [0, A], indices to [0, kCompactSlots) -- and a move whose source or
+// destination is at or beyond the capacity is skipped, so nothing outside [start, start + kCompactSlots) is written whatever they hold.
+// Dynamic LDS: 2 * A * row_bytes (K then V, move-major).
+__global__ __launch_bounds__(256) void kv_compact_kernel(DecodeParams p, CompactParams c) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __shared__ int src_pos[kCompactSlots];          // the cache position move i reads, or -1: no move
+  const int kvh = blockIdx.x % p.Hk, b = blockIdx.x / p.Hk;
+  const int64_t start = min(max((int64_t)p.seqlens[b], (int64_t)0), (int64_t)p.capacity);
+  if (threadIdx.x < kCompactSlots) {
+    const int i = threadIdx.x;
+    const int n = min(max(c.num_accepted[b], 0), c.A);
+    int sp = -1;
+    if (i < n) {
+      const int t = min(max(c.accepted[(int64_t)b * c.accepted_stride + i], 0), kCompactSlots - 1);
+      if (t != i && start + t < p.capacity && start + i < p.capacity) sp = (int)(start + t);
+    }
+    src_pos[i] = sp;
+  }
+  __syncthreads();
+  const int cpr = c.row_bytes / 16;               // 16-byte chunks of a row
+  const int total = 2 * c.A * cpr;                // chunk id = (tensor * A + move) * cpr + chunk
+  for (int id = threadIdx.x; id < total; id += 256) {
+    const int ch = id % cpr, i = id / cpr % c.A, sp = src_pos[i];
+    if (sp >= 0)
+      *reinterpret_cast<u32x4*>(smem + (int64_t)id * 16) = *reinterpret_cast<const u32x4*>(cache_base(p, id / cpr < c.A ? p.kc : p.vc, b, kvh, sp) + ch * 16);
+  }
+  __syncthreads();
+  for (int id = threadIdx.x; id < total; id += 256) {
+    const int ch = id % cpr, i = id / cpr % c.A;
+    if (src_pos[i] >= 0)
+      *reinterpret_cast<u32x4*>(cache_base(p, id / cpr < c.A ? p.kc : p.vc, b, kvh, (int)(start + i)) + ch * 16) = *reinterpret_cast<const u32x4*>(smem + (int64_t)id * 16);
+  }
+}
+
 int64_t blocks_of(int64_t threads) { return (threads + 255) / 256; }
 
 // ---- the launchers: one per job (append, decode, combine) over every form of the call ----------------------------------------------
@@ -679,6 +744,47 @@ hipError_t launch_decode_combine(int dtype, int D, DecodeForm f, const DecodeSte
     else if constexpr (FP8) return launch_part<decode_combine_fp8_kernel<T, DD>, 0>(grid, block, s, p);
     else return launch_part<decode_combine_kernel<T, DD>, 0>(grid, block, s, p);
   });
+}
+
+// launch_decode's ragged form on the entry points that take the visibility words: the same workgroups, block and LDS
+hipError_t launch_decode_tree(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeTreeMask& tree, hipStream_t s) {
+  if (!f.ragged || f.step || tree.words == nullptr) return hipErrorInvalidValue;
+  return dispatch_decode(dtype, D, f, [&](auto td, auto fp8, auto ragged) -> hipError_t {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    constexpr int ES = Traits<T>::ES;
+    constexpr bool FP8 = decltype(fp8)::value, RAGGED = decltype(ragged)::value;
+    if constexpr (!RAGGED) {
+      return hipErrorInvalidValue;
+    } else {
+      const int64_t wgs = (int64_t)p.slots * p.Hk * p.splits;
+      const dim3 grid((unsigned)wgs), block(64);
+      auto go = [&](auto dyn, auto gen) -> hipError_t {
+        constexpr bool DY = decltype(dyn)::value, GN = decltype(gen)::value;
+        constexpr int LDS = DecodeLds<DD, ES, GN>::BYTES;
+        if constexpr (FP8) return launch_part<decode_tree_fp8_kernel<T, DD, DY, GN>, LDS>(grid, block, s, p, tree);
+        else return launch_part<decode_tree_kernel<T, DD, DY, GN>, LDS>(grid, block, s, p, tree);
+      };
+      using Y = std::true_type;
+      using N = std::false_type;
+      if (p.l2norm && !decode_groups_fast(DD, p.groups, Unit<T>::UE)) {
+        if constexpr (DD == 96) return p.dyn ? go(Y{}, Y{}) : go(N{}, Y{});
+        else return hipErrorInvalidValue;
+      }
+      return p.dyn ? go(Y{}, N{}) : go(N{}, N{});
+    }
+  });
+}
+
+// one workgroup per (sequence, K/V head); the LDS limit is raised once per device to the largest stage (64 rows of 512 bytes, twice)
+hipError_t launch_kv_compact(const DecodeParams& cache, const CompactParams& c, hipStream_t s) {
+  constexpr int kMaxRowBytes = 512;
+  if (c.A < 1 || c.A > kCompactSlots || c.row_bytes < 16 || c.row_bytes % 16 != 0 || c.row_bytes > kMaxRowBytes) return hipErrorInvalidValue;
+  if (cache.B <= 0 || cache.Hk <= 0) return hipSuccess;
+  static std::atomic<uint64_t> done{0};
+  if (hipError_t e = ensure_dynamic_lds(kv_compact_kernel, 2 * kCompactSlots * kMaxRowBytes, done); e != hipSuccess) return e;
+  hipLaunchKernelGGL(kv_compact_kernel, dim3((unsigned)((int64_t)cache.B * cache.Hk)), dim3(256), (size_t)2 * c.A * c.row_bytes, s, cache, c);
+  return hipGetLastError();
 }
 
 }  // namespace fcsa

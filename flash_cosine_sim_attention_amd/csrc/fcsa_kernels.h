@@ -166,6 +166,12 @@ struct DecodeLseOut {
   float*  lse;
   int64_t sb, sh, sn;
 };
+// The per-row visibility words of a tree step (fcsa_forward_kvcache_tree): a second kernel argument of the decode entry points that read
+// them (decode_tree[_fp8]_kernel), as DecodeLseOut is of the combines -- the blocks above, and the kernels launched with them alone, are
+// what they were.  words[tok]: bit t set = packed row `tok` sees token t of its own sequence's step (cache position L_b - N_b + t).
+struct DecodeTreeMask {
+  const uint64_t* words;            // [total_q] device
+};
 // An engine step (fcsa_forward_kvcache_step): the ragged step's block plus the routing threshold.  Sequence b takes the chunk kernel
 // (step_prefill_kernel) iff G * N_b >= chunk_rows and the decode kernels (step_decode[_fp8]_kernel, step_combine[_lse]_kernel) otherwise;
 // all of them evaluate that on the device from the clamped table (ragged_cu), so every row is written by exactly one of them.
@@ -181,6 +187,22 @@ struct DecodeForm { bool fp8, ragged, step; };
 hipError_t launch_kv_append(int dtype, int D, DecodeForm f, const DecodeStepParams& p, hipStream_t s);      // (a step's append is the ragged call's)
 hipError_t launch_decode(int dtype, int D, DecodeForm f, const DecodeStepParams& p, hipStream_t s);
 hipError_t launch_decode_combine(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeLseOut* lse, hipStream_t s);
+// The decode launch of a tree step (fcsa_forward_kvcache_tree): launch_decode's ragged form -- the same grid, LDS and block -- on the entry
+// points that take the visibility words (decode_tree[_fp8]_kernel).  f.ragged must be set and f.step clear (hipErrorInvalidValue).  The
+// append and the combine of a tree step are launch_kv_append and launch_decode_combine, unchanged.
+hipError_t launch_decode_tree(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeTreeMask& tree, hipStream_t s);
+// Compaction of the accepted path of a tree step (fcsa_kvcache_compact; kv_compact_kernel in csrc/fcsa_decode.hip): rows of the caches
+// are moved as bytes inside the window [cache_seqlens[b], cache_seqlens[b] + kCompactSlots) of every sequence.  The caches, seqlens,
+// table, capacity, page, num_blocks, B and Hk of `cache` address them (cache_base); row_bytes = bytes of one cached row (a multiple of 16).
+constexpr int kCompactSlots = 64;   // step tokens a tree can have: the bits of a visibility word
+struct CompactParams {
+  const int32_t* accepted;          // [B, A] device: step-token indices, strictly increasing over the first num_accepted[b]
+  const int32_t* num_accepted;      // [B] device
+  int64_t accepted_stride;          // elements between the rows of `accepted`
+  int A;                            // 1 <= A <= kCompactSlots
+  int row_bytes;
+};
+hipError_t launch_kv_compact(const DecodeParams& cache, const CompactParams& c, hipStream_t s);
 // A prompt chunk against the cache (fcsa_forward_kvcache_prefill, and with f.step the chunk side of an engine step; csrc/fcsa_prefill.hip):
 // the block with slots = fcsa::prefill_slots(total_q, B, G, kPrefillRows), one split and no workspace; f16 / bf16, D = 64 / 128 (anything
 // else: hipErrorInvalidValue).  One kernel writes o and, where lse is not nullptr, the rows' log-sum-exp.  An fp8 cache and a window come

@@ -69,7 +69,10 @@ namespace {
   X(merge_states_backward, fcsa_merge_states_backward, false)                             \
   /* the engine step: chunks and decodes routed in one call */                            \
   X(forward_kvcache_step, fcsa_forward_kvcache_step, false)                               \
-  X(forward_kvcache_step_ws, fcsa_forward_kvcache_step_workspace_bytes, false)
+  X(forward_kvcache_step_ws, fcsa_forward_kvcache_step_workspace_bytes, false)        \
+  /* tree attention for speculative decoding, and the compaction of the accepted path */ \
+  X(forward_kvcache_tree, fcsa_forward_kvcache_tree, false)                               \
+  X(kvcache_compact, fcsa_kvcache_compact, false)
 
 struct Abi {
 #define X(member, symbol, required) decltype(&symbol) member = &symbol;
@@ -725,8 +728,10 @@ Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor
                             const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table, int64_t max_seqlen_k, double scale, bool causal,
                             bool l2norm_qk, int64_t groups, const fcsa_window* win, const Tensor* k_scale = nullptr, const Tensor* v_scale = nullptr,
                             const Tensor* cu_q = nullptr, int64_t max_seqlen_q = 0, Tensor* lse_out = nullptr, bool prefill = false,
-                            const fcsa_kvcache_step* step = nullptr) {
+                            const fcsa_kvcache_step* step = nullptr, const Tensor* tree = nullptr) {
   const bool ragged = cu_q != nullptr;
+  if (tree != nullptr)      // kvcache_tree_forward: a ragged step through fcsa_forward_kvcache_tree (the ragged call's workspace; the lse always)
+    need_abi("tree_mask", "fcsa_forward_kvcache_tree", g_abi.forward_kvcache_tree);
   if (step != nullptr)      // kvcache_step_forward: a ragged step through fcsa_forward_kvcache_step (its own workspace; the lse always)
     need_abi("flash_cosine_sim_attention_step_with_kvcache", "fcsa_forward_kvcache_step", g_abi.forward_kvcache_step, g_abi.forward_kvcache_step_ws);
   if (prefill)      // kvcache_prefill_forward: a ragged step through fcsa_forward_kvcache_prefill (no workspace; the lse always)
@@ -770,6 +775,14 @@ Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor
     TORCH_CHECK_VALUE(max_seqlen_q >= 0 && max_seqlen_q <= INT32_MAX, "max_seqlen_q must lie in [0, 2^31), got ", max_seqlen_q);
     TORCH_CHECK_VALUE(q.size(0) * std::max<int64_t>(q.size(1), 1) <= INT32_MAX, "heads x packed rows must stay below 2^31");
     cu = cu_q->contiguous();
+  }
+  Tensor words;
+  if (tree != nullptr) {
+    TORCH_CHECK_TYPE(tree->scalar_type() == at::kLong, "tree_mask must be int64, got ", tree->scalar_type());
+    same_dev("tree_mask", *tree);
+    TORCH_CHECK_VALUE(ragged && tree->dim() == 1 && tree->size(0) == q.size(0), "tree_mask must be [total_q] (", q.size(0), "), packed like q, got ",
+                      tree->sizes());
+    words = tree->contiguous();
   }
   // ragged: N is the number of packed rows
   const int64_t B = ragged ? cu.numel() - 1 : q.size(0), H = q.size(1), N = ragged ? q.size(0) : q.size(2), D = q.size(-1), Hk = k_cache.size(1);
@@ -898,6 +911,13 @@ Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor
       check(g_abi.forward_kvcache_step(&a, &kv, &seqs, fp8 ? &qz : nullptr, win, step, &lo), "fcsa_forward_kvcache_step");
       return o;
     }
+    if (tree != nullptr) {
+      fcsa_tree_mask tm;
+      std::memset(&tm, 0, sizeof(tm));
+      tm.mask = reinterpret_cast<const uint64_t*>(words.data_ptr<int64_t>());
+      check(g_abi.forward_kvcache_tree(&a, &kv, &seqs, fp8 ? &qz : nullptr, &tm, &lo), "fcsa_forward_kvcache_tree");
+      return o;
+    }
     check(g_abi.forward_kvcache_lse(&a, &kv, ragged ? &seqs : nullptr, fp8 ? &qz : nullptr, win, &lo), "fcsa_forward_kvcache_lse");
     return o;
   }
@@ -997,6 +1017,78 @@ std::tuple<Tensor, Tensor> kvcache_step_forward(const Tensor& q, const Tensor& k
                                   windowed ? &w : nullptr, k_scale.has_value() ? &*k_scale : nullptr, v_scale.has_value() ? &*v_scale : nullptr,
                                   &cu_seqlens_q, max_seqlen_q, &lse, false, &st);
   return {o, lse};
+}
+
+// A tree step: kvcache_lse_forward's ragged step without a window and without `causal`, the visibility of the step's own tokens given per
+// packed row by tree_mask (int64 [total_q], read as unsigned 64-bit words).
+std::tuple<Tensor, Tensor> kvcache_tree_forward(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& cu_seqlens_q,
+                                                const Tensor& tree_mask, const optional<Tensor>& k_new, const optional<Tensor>& v_new,
+                                                const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table,
+                                                const optional<Tensor>& k_scale, const optional<Tensor>& v_scale, int64_t max_seqlen_q,
+                                                int64_t max_seqlen_k, double scale, bool l2norm_qk, int64_t groups) {
+  TORCH_CHECK_VALUE(k_scale.has_value() == v_scale.has_value(), "k_scale and v_scale must be given together");
+  Tensor lse;
+  Tensor o = kvcache_forward_impl(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, false, l2norm_qk, groups,
+                                  nullptr, k_scale.has_value() ? &*k_scale : nullptr, v_scale.has_value() ? &*v_scale : nullptr, &cu_seqlens_q,
+                                  max_seqlen_q, &lse, false, nullptr, &tree_mask);
+  return {o, lse};
+}
+
+// kvcache_keep_accepted: the rows cache_seqlens[b] + accepted[b, i] of both caches move to cache_seqlens[b] + i (i < num_accepted[b]), in
+// place, as bytes (any cache dtype; fp8 codes as their uint8 views).  Tables int32 on the caches' device, never read on the host.
+void kvcache_compact(const Tensor& k_cache, const Tensor& v_cache, const Tensor& cache_seqlens, const Tensor& accepted, const Tensor& num_accepted,
+                     const optional<Tensor>& block_table) {
+  need_abi("kvcache_keep_accepted", "fcsa_kvcache_compact", g_abi.kvcache_compact);
+  TORCH_CHECK(k_cache.is_cuda(), "kvcache_keep_accepted: the caches must be GPU tensors (HIP kernels only)");
+  auto same_dev = [&](const char* name, const Tensor& t) {
+    TORCH_CHECK_VALUE(t.device() == k_cache.device(), name, " is on ", t.device(), " but k_cache is on ", k_cache.device());
+  };
+  same_dev("v_cache", v_cache);
+  TORCH_CHECK_TYPE(k_cache.scalar_type() == v_cache.scalar_type(), "k_cache and v_cache must share a dtype");
+  TORCH_CHECK_VALUE(k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes(), "k_cache and v_cache must have 4 dimensions and the same shape");
+  const int64_t es = k_cache.element_size(), D = k_cache.size(3), Hk = k_cache.size(1);
+  TORCH_CHECK_TYPE(es == 1 || es == 2 || es == 4, "cache elements of 1, 2 or 4 bytes, got ", k_cache.scalar_type());
+  TORCH_CHECK_VALUE(rows_ok(k_cache) && rows_ok(v_cache), "k_cache / v_cache: the feature dim must be contiguous and rows 16-byte aligned "
+                    "(the caches are updated in place, so they are not copied)");
+  same_dev("cache_seqlens", cache_seqlens);
+  same_dev("accepted", accepted);
+  same_dev("num_accepted", num_accepted);
+  TORCH_CHECK_TYPE(cache_seqlens.scalar_type() == at::kInt && accepted.scalar_type() == at::kInt && num_accepted.scalar_type() == at::kInt,
+                   "cache_seqlens, accepted and num_accepted must be int32");
+  TORCH_CHECK_VALUE(accepted.dim() == 2 && accepted.size(1) >= 1 && accepted.size(1) <= 64, "accepted must be [sequences, A] with 1 <= A <= 64, got ",
+                    accepted.sizes());
+  const int64_t B = accepted.size(0);
+  TORCH_CHECK_VALUE(cache_seqlens.dim() == 1 && cache_seqlens.size(0) == B && num_accepted.dim() == 1 && num_accepted.size(0) == B,
+                    "cache_seqlens and num_accepted must be [", B, "]");
+  const bool paged = block_table.has_value();
+  fcsa_kvcache kv;
+  std::memset(&kv, 0, sizeof(kv));
+  int64_t capacity = k_cache.size(2);
+  Tensor tab;
+  if (paged) {
+    same_dev("block_table", *block_table);
+    TORCH_CHECK_TYPE(block_table->scalar_type() == at::kInt, "block_table must be int32");
+    TORCH_CHECK_VALUE(block_table->dim() == 2 && block_table->size(0) == B, "block_table must be [sequences, max_blocks]");
+    tab = block_table->contiguous();
+    kv.page_size = (int32_t)k_cache.size(2);
+    kv.num_blocks = (int32_t)k_cache.size(0);
+    capacity = tab.size(1) * k_cache.size(2);
+    kv.block_table = tab.data_ptr<int32_t>();
+    kv.block_table_stride = tab.size(1);
+  } else {
+    TORCH_CHECK_VALUE(k_cache.size(0) == B, "batch mismatch between accepted (", B, ") and the caches (", k_cache.size(0), ")");
+  }
+  TORCH_CHECK_VALUE(capacity <= INT32_MAX, "cache capacity must stay below 2^31");
+  if (B == 0 || Hk == 0 || capacity == 0) return;
+  c10::DeviceGuard guard(k_cache.device());
+  const Tensor sl = cache_seqlens.contiguous(), acc = accepted.stride(1) == 1 ? accepted : accepted.contiguous(), na = num_accepted.contiguous();
+  kv.k_cache = strided(k_cache);
+  kv.v_cache = strided(v_cache);
+  kv.capacity = (int32_t)capacity;
+  kv.cache_seqlens = sl.data_ptr<int32_t>();
+  check(g_abi.kvcache_compact(&kv, (int32_t)B, (int32_t)Hk, (int32_t)D, (int32_t)es, acc.data_ptr<int32_t>(), acc.stride(0), (int32_t)acc.size(1),
+                              na.data_ptr<int32_t>(), stream_of(k_cache)),
+        "fcsa_kvcache_compact");
 }
 
 // merge_attention_states: S <= 8 states (o_s [..., D] 4-D or [total_q, H, D], lse_s float32 without the feature dim) -> fresh contiguous
@@ -1367,6 +1459,19 @@ TORCH_LIBRARY(fcsa_step, m) {
         "bool no_chunk) -> (Tensor, Tensor)");
 }
 TORCH_LIBRARY_IMPL(fcsa_step, CUDA, m) { m.impl("kvcache_step_forward", &kvcache_step_forward); }
+
+// tree attention for speculative decoding in a namespace of its own, as above
+TORCH_LIBRARY(fcsa_tree, m) {
+  m.def("kvcache_tree_forward(Tensor q, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor cu_seqlens_q, Tensor tree_mask, Tensor? k_new, "
+        "Tensor? v_new, Tensor? cache_seqlens, Tensor? block_table, Tensor? k_scale, Tensor? v_scale, int max_seqlen_q, int max_seqlen_k, "
+        "float scale, bool l2norm_qk, int groups) -> (Tensor, Tensor)");
+  m.def("kvcache_compact(Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor cache_seqlens, Tensor accepted, Tensor num_accepted, "
+        "Tensor? block_table) -> ()");
+}
+TORCH_LIBRARY_IMPL(fcsa_tree, CUDA, m) {
+  m.impl("kvcache_tree_forward", &kvcache_tree_forward);
+  m.impl("kvcache_compact", &kvcache_compact);
+}
 
 // Attention states for training, in a namespace of their own (the op set of `fcsa` is pinned): the attention op with the rows'
 // log-sum-exp as a second differentiable result -- dense, local (window sides other than (-1, -1)) or packed (cu_seqlens given) -- and

@@ -450,7 +450,9 @@ def flash_cosine_sim_attention_with_kvcache(q, k_cache, v_cache, k_new=None, v_n
     logit being scale * (sum over the groups of q^ . k^), or scale * q . k without l2norm_qk; with an fp8 cache k_scale is inside it and
     v_scale is not.  A row without a visible key has lse = -inf (and o = 0).  o and the caches are bit for bit those of the call without
     it.  (o, lse) is an attention state: `merge_attention_states` combines the states of the same queries over disjoint sets of keys.
-    return_lse must be a bool and window_size is best passed by keyword: return_lse precedes it in the signature."""
+    return_lse must be a bool and window_size is best passed by keyword: return_lse precedes it in the signature.
+    Tree attention (a tree_mask over the step's tokens, for speculative decoding) is not taken here: pass cu_seqlens_q = arange(B + 1) * N
+    and the packed q to `flash_cosine_sim_attention_tree_with_kvcache`, which takes one."""
     _check_return_lse(return_lse)
     window = _window(window_size)
     q_fault = None if q.dim() == 4 else f"q must have 4 dimensions, got {tuple(q.shape)}"
@@ -537,7 +539,9 @@ def flash_cosine_sim_attention_varlen_with_kvcache(q, k_cache, v_cache, cu_seqle
     The launch has one row-tile slot per 16 rows of G * N_b (about G * total_q / 16 + B per K/V head, whatever the longest sequence is), and
     every row tile re-reads and re-normalises its keys: this is the call for steps of one to a few dozen tokens per sequence.  Long prompt
     chunks work, at the decode kernel's efficiency; `flash_cosine_sim_attention_prefill_with_kvcache` is the call for those.
-    return_lse=True: returns (o, lse) with lse float32 [total_q, H], as in `flash_cosine_sim_attention_with_kvcache`."""
+    return_lse=True: returns (o, lse) with lse float32 [total_q, H], as in `flash_cosine_sim_attention_with_kvcache`.
+    Tree attention for speculative decoding (a tree_mask over the step's own tokens in place of causal) is this call under another name:
+    `flash_cosine_sim_attention_tree_with_kvcache`, which takes these arguments and tree_mask."""
     _check_return_lse(return_lse)
     window = _window(window_size)
     c, cpu_result, cu_q, max_q = _ragged_step("flash_cosine_sim_attention_varlen_with_kvcache", q, k_cache, v_cache, cu_seqlens_q, k_new, v_new,
@@ -664,6 +668,139 @@ def flash_cosine_sim_attention_step_with_kvcache(q, k_cache, v_cache, cu_seqlens
                                                       max_q, c.max_k, float(scale), bool(causal), bool(l2norm_qk), int(groups), window[0], window[1],
                                                       threshold, bound, no_decode, no_chunk)
     return (o, lse) if return_lse else o
+
+
+# ---------------------------------------------------------------------------------------------
+# attention states: merging the results of the same queries over disjoint sets of keys, and the shared-prefix decode step built on it
+# ---------------------------------------------------------------------------------------------
+
+MERGE_MAX_STATES = 8
+
+
+def flash_cosine_sim_attention_tree_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new=None, v_new=None, cache_seqlens=None,
+                                                 block_table=None, max_seqlen_q=None, max_seqlen_k=None, scale=8, groups=1, causal=False,
+                                                 l2norm_qk=True, k_scale=None, v_scale=None, return_lse=False, window_size=(-1, -1),
+                                                 tree_mask=None):
+    """Tree attention for speculative decoding against the key/value cache: `flash_cosine_sim_attention_varlen_with_kvcache`
+    with one more, last keyword.  The arguments are that call's, in its order; tree_mask=None IS that call, bit for bit, launching
+    exactly what it launches.
+
+    A speculative decoder (Medusa, EAGLE, SpecInfer, sequoia-style trees) drafts a tree of tokens per sequence and verifies it in one
+    step: token t must see the cache, its ancestors and itself, but not its siblings or cousins, which sit in the same step; causal treats
+    the step's tokens as a chain.
+    tree_mask (tree attention for speculative decoding): an int64 tensor [total_q] on q's device, packed by cu_seqlens_q like q -- word
+    tree_mask[cu_seqlens_q[b] + i] belongs to query i of sequence b -- that states which of the step's own tokens a query sees, in place
+    of causal.  With L_b as the ragged call defines it (cache_seqlens[b] + N_b with an append, cache_seqlens[b] without) and
+    P_b = L_b - N_b: every query of sequence b sees the cache positions j < P_b (everything before the
+    step); query i sees position P_b + t, 0 <= t < N_b (the step's token t), iff bit t of its word is set (bit 0 the least significant,
+    the word read as unsigned; bits t >= N_b are never looked at; positions below 0, N_b > L_b, do not exist).  A drafted tree sets, for
+    token i, the bits of its ancestors and its own; but nothing requires a tree, the diagonal or a lower-triangular mask: a word is a
+    per-row bit set over the step's tokens.  A sequence with N_b > 64 ignores its words and is causal, bottom-right, exactly as
+    causal=True treats it (decided on the device from the clamped table), so a prompt chunk can ride in the same packed batch.  A row
+    without a visible key gives o = 0 and lse = -inf.  causal=True or a window_size other than (-1, -1) with a mask: ValueError.  Everything
+    else combines as without it: return_lse, fp8 caches, paged caches, k_new=None, device tables without synchronisation, graph capture
+    (the mask is device data, never read by the host).  The launch is planned as the non-causal call on the same shapes and only the
+    per-logit visibility test differs, so the chain mask (word i = bits 0 .. i) gives causal=True's o, lse and caches bit for bit, and
+    all bits set give causal=False's.  After verification `kvcache_keep_accepted` moves the accepted path to the front of the step's
+    slots.  The equal-N call takes no mask: pass cu_seqlens_q = arange(B + 1) * N here; the prefill, engine-step and shared-prefix
+    calls take none either."""
+    fn = "flash_cosine_sim_attention_tree_with_kvcache"
+    if tree_mask is None:
+        return flash_cosine_sim_attention_varlen_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q,
+                                                              max_seqlen_k, scale, groups, causal, l2norm_qk, k_scale, v_scale, return_lse, window_size)
+    _check_return_lse(return_lse)
+    window = _window(window_size)
+    if causal:
+        raise ValueError("tree_mask states the visibility of the step's tokens: causal=True cannot be given with it")
+    if window != (-1, -1):
+        raise ValueError(f"tree_mask takes no sliding window (window_size {tuple(window_size)})")
+    if not isinstance(tree_mask, torch.Tensor) or tree_mask.dtype != torch.int64:
+        raise TypeError(f"tree_mask must be an int64 tensor of shape [total_q], got {getattr(tree_mask, 'dtype', type(tree_mask).__name__)}")
+    if q.dim() == 3 and tuple(tree_mask.shape) != (q.shape[0],):
+        raise ValueError(f"tree_mask must have shape [{q.shape[0]}] (one word per packed query row), got {tuple(tree_mask.shape)}")
+    if tree_mask.device != q.device:
+        raise ValueError(f"tree_mask is on {tree_mask.device} but q is on {q.device}")
+    c, cpu_result, cu_q, max_q = _ragged_step(fn, q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q,
+                                              max_seqlen_k, k_scale, v_scale, window,
+                                              dict(scale=scale, groups=groups, l2norm_qk=l2norm_qk, return_lse=bool(return_lse), tree_mask=tree_mask))
+    if q.device.type == "cpu":
+        return cpu_result
+    if q.shape[0] == 0:      # nothing to append, nothing to write: no launch
+        o = q.new_empty(q.shape)
+        return (o, q.new_empty((0, q.shape[1]), dtype=torch.float32)) if return_lse else o
+    k_cache, v_cache, cache_seqlens, block_table = c.on_device()
+    _torch_ops.load()
+    o, lse = torch.ops.fcsa_tree.kvcache_tree_forward(q, k_cache, v_cache, cu_q, tree_mask, k_new, v_new, cache_seqlens, block_table, c.k_scale,
+                                                      c.v_scale, max_q, c.max_k, float(scale), bool(l2norm_qk), int(groups))
+    return (o, lse) if return_lse else o
+
+
+def kvcache_keep_accepted(k_cache, v_cache, cache_seqlens, accepted, num_accepted, block_table=None):
+    """Moves the accepted path of a tree step to the front of the slots the step appended, in place.  Returns None.
+
+    A tree step (`flash_cosine_sim_attention_tree_with_kvcache` with tree_mask and k_new / v_new) appends sequence b's N_b drafted tokens
+    at [cache_seqlens[b], cache_seqlens[b] + N_b).  After verification the accepted tokens are a root-to-leaf path scattered over those
+    slots; before the next step they must be its first num_accepted[b] slots.
+    accepted: int32 [B, A], 1 <= A <= 64; num_accepted: int32 [B].  For i < num_accepted[b], accepted[b, i] is a step-token index in
+    [0, 64), strictly increasing in i (so accepted[b, i] >= i); entries beyond num_accepted[b] are ignored.  The row at cache position
+    cache_seqlens[b] + accepted[b, i] moves to cache_seqlens[b] + i, in K and in V, for every K/V head.  cache_seqlens (int32 [B]) is NOT
+    advanced: the caller adds num_accepted.
+    k_cache, v_cache, block_table: the layouts, strides and page rule of `flash_cosine_sim_attention_with_kvcache`.  Rows move as bytes,
+    so every cache dtype works unchanged, float8_e4m3fn codes included (the scales are per sequence and K/V head).
+    Host tables are validated (range, strict increase, num_accepted <= A, slots inside the capacity); device tables are trusted and
+    clamped -- num_accepted to [0, A], indices to [0, 63] -- and a move whose source or destination is at or beyond the capacity is
+    skipped, so nothing outside [cache_seqlens[b], cache_seqlens[b] + 64) of a sequence is ever written.  With device tables the call does
+    not synchronise and can be captured in a HIP graph.  One workgroup owns all moves of a (sequence, K/V head) pair and reads every
+    source row before it writes the first, so a destination that is another move's source (accepted = [1, 2, 3, ...]) is safe.
+    CPU tensors take the path of `cpu.py` (host tables)."""
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError(f"{name} must be a tensor of 4 dimensions")
+    if k_cache.shape != v_cache.shape or k_cache.dtype != v_cache.dtype or k_cache.device != v_cache.device:
+        raise ValueError("k_cache and v_cache must have the same shape, dtype and device")
+    if not isinstance(accepted, torch.Tensor) or accepted.dtype != torch.int32 or accepted.dim() != 2:
+        raise TypeError("accepted must be an int32 [sequences, A] tensor")
+    B, A = accepted.shape
+    if not 1 <= A <= 64:
+        raise ValueError(f"accepted must have 1 <= A <= 64 columns, got {A}")
+    for name, t in (("num_accepted", num_accepted), ("cache_seqlens", cache_seqlens)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (B,):
+            raise TypeError(f"{name} must be an int32 tensor of shape ({B},)")
+    page = k_cache.shape[2]
+    if block_table is not None:
+        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B:
+            raise TypeError("block_table must be an int32 [sequences, max_blocks] tensor")
+        if page <= 0 or page % 16:
+            raise ValueError(f"page_size ({page}) must be a positive multiple of 16")
+        capacity = block_table.shape[1] * page
+    else:
+        if k_cache.shape[0] != B:
+            raise ValueError(f"batch mismatch between accepted ({B} sequences) and the caches ({k_cache.shape[0]})")
+        capacity = page
+    host = lambda t: t.device.type == "cpu"
+    if host(num_accepted):
+        counts = num_accepted.tolist()
+        if any(n < 0 or n > A for n in counts):
+            raise ValueError(f"num_accepted must lie in [0, {A}], got {counts}")
+        if host(accepted):
+            for b, n in enumerate(counts):
+                path = accepted[b, :n].tolist()
+                if any(t < 0 or t >= 64 for t in path) or any(y <= x for x, y in zip(path, path[1:])):
+                    raise ValueError(f"sequence {b}: accepted must be strictly increasing step-token indices in [0, 64), got {path}")
+    if host(cache_seqlens) and any(n < 0 or n > capacity for n in cache_seqlens.tolist()):
+        raise ValueError(f"cache_seqlens must lie in [0, capacity {capacity}], got {cache_seqlens.tolist()}")
+    dev = k_cache.device
+    if dev.type == "cpu":
+        if not (host(accepted) and host(num_accepted) and host(cache_seqlens)) or (block_table is not None and not host(block_table)):
+            raise ValueError("CPU caches take host tables")
+        _cpu.kvcache_keep_accepted_cpu(k_cache, v_cache, cache_seqlens.tolist(), accepted.tolist(), num_accepted.tolist(), block_table)
+        return None
+    if k_cache.dtype in _FP8_TYPES:      # the codes travel as bytes (same storage)
+        k_cache, v_cache = k_cache.view(torch.uint8), v_cache.view(torch.uint8)
+    move = lambda t: None if t is None else t.to(dev, non_blocking=True)
+    _torch_ops.load()
+    torch.ops.fcsa_tree.kvcache_compact(k_cache, v_cache, move(cache_seqlens), move(accepted), move(num_accepted), move(block_table))
+    return None
 
 
 # ---------------------------------------------------------------------------------------------
@@ -820,7 +957,8 @@ def flash_cosine_sim_attention_with_shared_prefix(q, prefix_k_cache, prefix_v_ca
     window_size other than (-1, -1) raises ValueError: a window that reaches into the prefix needs a per-sequence alignment against P +
     L_b that the B = 1 prefix call cannot express.
     With a device prefix_len, device tables and max_seqlen_k given, the call does not synchronise and can be captured in a HIP graph; all
-    launches go to the current stream, one after another.  Returns o shaped like q, or (o, lse) with return_lse=True.  Forward only."""
+    launches go to the current stream, one after another.  Returns o shaped like q, or (o, lse) with return_lse=True.  Forward only.
+    Tree attention (a tree_mask over the step's tokens) is not taken here: `flash_cosine_sim_attention_tree_with_kvcache` takes one."""
     _check_return_lse(return_lse)
     if _window(window_size) != (-1, -1):
         raise ValueError("flash_cosine_sim_attention_with_shared_prefix takes no window_size: a window that reaches into the shared prefix "

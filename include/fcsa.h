@@ -413,6 +413,55 @@ size_t fcsa_forward_kvcache_step_workspace_bytes(const fcsa_problem* p, const fc
                                                  const fcsa_kvcache_quant* quant, const fcsa_window* window,
                                                  const fcsa_kvcache_step* step);
 
+/* Tree attention for speculative decoding: fcsa_forward_kvcache_varlen / _lse with a per-row bit set over the step's own tokens in place
+ * of `causal`.  A speculative decoder drafts a TREE of tokens per sequence and verifies them in one step: token t must see the cache, its
+ * ancestors and itself, but not its siblings or cousins, which sit in the same step.
+ * args, cache, seqs and quant are read exactly as fcsa_forward_kvcache_varlen reads them and its checks apply (additive: no existing struct
+ * changes and FCSA_ABI_VERSION stays 4); lse_out: NULL, or as in fcsa_forward_kvcache_lse for a ragged call.  There is no window.
+ *   tree->mask : device, [total_q] 64-bit words packed like q (8-byte aligned): word [cu_seqlens_q[b] + i] belongs to query i of sequence b.
+ * With L_b as that call defines it (min(cache_seqlens[b] + N_b, capacity) with an append, cache_seqlens[b] without) and P_b = L_b - N_b:
+ *   - cache position j < P_b (everything before the step) is visible to every query of the sequence;
+ *   - cache position P_b + t, 0 <= t < N_b (the step's token t), is visible to query i iff bit t of its word is set (bit 0 the least
+ *     significant, the word read as unsigned); bits t >= N_b are never looked at; positions below 0 (N_b > L_b) do not exist;
+ *   - a sequence with N_b > 64 ignores its words and is causal, bottom-right aligned, exactly as p.causal treats it -- decided on the device
+ *     from the clamped table, so a prompt chunk can ride in the same packed batch;
+ *   - a row without a visible key gives o = 0 and lse = -inf, as everywhere.
+ * Nothing requires the words to describe a tree, to contain the diagonal or to be lower-triangular: a word is a bit set over the step's
+ * tokens.  The mask is device data, never read by the host; the call does not synchronise and can be captured in a graph.
+ * p.causal != 0: FCSA_ERR_INVALID_ARG (the mask states the visibility); tree or tree->mask NULL, a misaligned mask, reserved != 0:
+ * FCSA_ERR_INVALID_ARG.
+ * The call is planned exactly as fcsa_forward_kvcache_varlen without a window on the same arguments -- the same split count, grid and
+ * workspace, fcsa_forward_kvcache_varlen_workspace_bytes(p, cache, seqs, quant, NULL) bytes -- and only the per-logit visibility test of
+ * the decode kernel differs, so with the chain mask (word i = bits 0 .. i) o, lse and the caches are bit for bit those of that call with
+ * p.causal = 1, and with all bits set those of that call with p.causal = 0.
+ * Launches: "kv_append_ragged[_fp8]" (when appending) and "decode_combine[_lse]_ragged[_fp8]", the ragged call's launches unchanged, and
+ * "decode_tree[_fp8]" between them. */
+typedef struct fcsa_tree_mask {
+  const uint64_t* mask;               /* device [total_q] */
+  int64_t         reserved;           /* 0 */
+} fcsa_tree_mask;
+int    fcsa_forward_kvcache_tree(const fcsa_forward_args* args, const fcsa_kvcache* cache, const fcsa_varlen* seqs,
+                                 const fcsa_kvcache_quant* quant, const fcsa_tree_mask* tree, const fcsa_lse_out* lse_out);
+
+/* Compaction of the accepted path after a tree step.  The step appended N_b tokens at [cache_seqlens[b], cache_seqlens[b] + N_b); the
+ * verifier accepted a root-to-leaf path of them, which must sit at the front of those slots before the next step.  In place:
+ *   for i < num_accepted[b]: the row at cache position cache_seqlens[b] + accepted[b, i] moves to cache_seqlens[b] + i, in K and in V, for
+ *   every K/V head.  accepted[b, i] is a step-token index in [0, 64), strictly increasing in i (so accepted[b, i] >= i).
+ * cache_seqlens is not advanced: the caller adds num_accepted.  Rows move as BYTES, so every cache type works unchanged, fp8 codes
+ * included (the scales are per sequence and K/V head): elem_bytes is the size of a cache element (4, 2 or 1) and row_bytes = dim_head *
+ * elem_bytes a multiple of 16, at most 512.  cache: k_cache / v_cache, capacity, page_size, num_blocks, cache_seqlens (required),
+ * block_table and block_table_stride as in fcsa_forward_kvcache, the strides in elements of elem_bytes; new_len, k_new and v_new are
+ * ignored.  accepted: device int32 [batch, A] with the row stride accepted_stride, 1 <= A = max_accepted <= 64; num_accepted: device
+ * int32 [batch].
+ * The tables are device data, trusted and clamped: num_accepted to [0, A], indices to [0, 63], cache_seqlens to [0, capacity], block ids
+ * to the pool; a move whose source or destination lies at or beyond the capacity is skipped.  Nothing outside [cache_seqlens[b],
+ * cache_seqlens[b] + 64) of a sequence is ever written, whatever the tables hold.  No host synchronisation; can be captured in a graph.
+ * Destination i of one move can be the source of another (accepted = 1, 2, 3, ... shifts everything by one): one workgroup owns all moves
+ * of a (sequence, K/V head) pair, reads every source row, passes a barrier and then writes.  Launch: "kv_compact". */
+int    fcsa_kvcache_compact(const fcsa_kvcache* cache, int32_t batch, int32_t kv_heads, int32_t dim_head, int32_t elem_bytes,
+                            const int32_t* accepted, int64_t accepted_stride, int32_t max_accepted, const int32_t* num_accepted,
+                            void* stream);
+
 /* Merging attention states: `states` pairs (o_s, lse_s) over disjoint key sets of the same queries -> the pair over the union.
  * Per row, in float32:  M = max_s lse_s;  M == -inf: o = 0, lse = -inf;  else w_s = exp(lse_s - M), W = sum_s w_s,
  * o = (sum_s w_s * o_s) / W rounded once to `dtype`, lse = M + log(W).  A state with lse_s == -inf (or one whose weight underflows to 0)
