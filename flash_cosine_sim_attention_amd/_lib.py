@@ -91,6 +91,7 @@ MergeBackwardArgs = _STRUCTS["fcsa_merge_backward_args"]
 KvCacheStep = _STRUCTS["fcsa_kvcache_step"]
 STEP_CHUNK_ROWS = _MACROS["FCSA_STEP_CHUNK_ROWS"]
 TreeMask = _STRUCTS["fcsa_tree_mask"]
+Alibi = _STRUCTS["fcsa_alibi"]
 
 
 EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fcsa_forward_workspace_bytes", "fcsa_forward_needs_qn",
@@ -102,7 +103,7 @@ EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fc
            "fcsa_forward_kvcache_lse", "fcsa_merge_states", "fcsa_forward_kvcache_prefill",
            "fcsa_attention_lse", "fcsa_backward_state", "fcsa_merge_states_backward",
            "fcsa_forward_kvcache_step", "fcsa_forward_kvcache_step_workspace_bytes",
-           "fcsa_forward_kvcache_tree", "fcsa_kvcache_compact")
+           "fcsa_forward_kvcache_tree", "fcsa_kvcache_compact", "fcsa_forward_kvcache_alibi")
 
 _lib = None
 
@@ -211,6 +212,10 @@ def load():
         lib.fcsa_forward_kvcache_step_workspace_bytes.argtypes = [C.POINTER(Problem), C.POINTER(KvCache), C.POINTER(Varlen),
                                                                   C.POINTER(KvCacheQuant), C.POINTER(Window), C.POINTER(KvCacheStep)]
         lib.fcsa_forward_kvcache_step_workspace_bytes.restype = C.c_size_t
+    if hasattr(lib, "fcsa_forward_kvcache_alibi"):      # (likewise: an FCSA_LIB build from before the position bias of the cached calls)
+        lib.fcsa_forward_kvcache_alibi.argtypes = [C.POINTER(ForwardArgs), C.POINTER(KvCache), C.POINTER(Varlen), C.POINTER(KvCacheQuant),
+                                                   C.POINTER(Window), C.POINTER(KvCacheStep), C.POINTER(Alibi), C.POINTER(LseOut)]
+        lib.fcsa_forward_kvcache_alibi.restype = C.c_int
     if hasattr(lib, "fcsa_forward_kvcache_tree"):      # (likewise: an FCSA_LIB build from before tree attention)
         lib.fcsa_forward_kvcache_tree.argtypes = [C.POINTER(ForwardArgs), C.POINTER(KvCache), C.POINTER(Varlen), C.POINTER(KvCacheQuant),
                                                   C.POINTER(TreeMask), C.POINTER(LseOut)]

@@ -116,6 +116,12 @@ def _register_fakes():
           scale, l2norm_qk, groups):
         return q.new_empty(q.shape), q.new_empty(q.shape[:-1], dtype=torch.float32)
 
+    # the engine step with a linear position bias (fcsa_alibi): the step op's results
+    @torch.library.register_fake("fcsa_alibi::kvcache_alibi_forward")
+    def _(q, k_cache, v_cache, cu_seqlens_q, alibi_slopes, k_new, v_new, cache_seqlens, block_table, k_scale, v_scale, max_seqlen_q,
+          max_seqlen_k, scale, causal, l2norm_qk, groups, window_left, window_right, chunk_rows, max_decode_tokens, no_decode, no_chunk):
+        return q.new_empty(q.shape), q.new_empty(q.shape[:-1], dtype=torch.float32)
+
     @torch.library.register_fake("fcsa_tree::kvcache_compact")
     def _(k_cache, v_cache, cache_seqlens, accepted, num_accepted, block_table):
         return None

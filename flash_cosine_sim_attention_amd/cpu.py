@@ -74,7 +74,8 @@ def window_index(window_size):
 
 
 def attention_forward_cpu(q, k, v, mask=None, attn_bias=None, scale=8.0, groups=1, causal=False, l2norm_qk=True,
-                          attn_bias_batch_dim=False, row_block=256, key_block=1024, window_size=(-1, -1), return_lse=False, tail_mask=None):
+                          attn_bias_batch_dim=False, row_block=256, key_block=1024, window_size=(-1, -1), return_lse=False, tail_mask=None,
+                          alibi_slopes=None):
     """Forward-only blockwise cosine-sim attention on host tensors.  Same argument meaning as the GPU operator.
     window_size = (left, right): query i sees key j iff i + (M - N) - left <= j <= i + (M - N) + right (-1: unbounded; causal caps
     right at 0); the key blocks outside a row block's band are never touched.
@@ -82,8 +83,13 @@ def attention_forward_cpu(q, k, v, mask=None, attn_bias=None, scale=8.0, groups=
     exp(logit)), from the running max and row sum the loop holds; -inf for a row without a visible key.
     tail_mask: bool [N, T], T <= M (a tree step, `tree_tail`): query i sees every key before the last T and key M - T + t iff tail_mask[i, t].
     It takes no causal, window, mask or bias.  A row block stops at the last key any of its rows sees, as a causal one does, and an
-    invisible logit is -inf either way, so a lower-triangular mask gives the causal call's bits and a full one the plain call's."""
+    invisible logit is -inf either way, so a lower-triangular mask gives the causal call's bits and a full one the plain call's.
+    alibi_slopes: float32 [H] (the cached calls' linear position bias): the logit of key j for query i gains -slope[h] * |i + (M - N) - j|
+    after the scale, and is part of the lse.  It is computed per block, never materialised, and -- unlike attn_bias -- combines with a
+    window; it takes no tail_mask and no attn_bias."""
     w_left, w_right = window_sides(window_size, causal)
+    if alibi_slopes is not None and (tail_mask is not None or attn_bias is not None):
+        raise ValueError("alibi_slopes takes no tail_mask and no attn_bias")
     if tail_mask is not None and (causal or mask is not None or attn_bias is not None or tuple(window_index(window_size)) != (-1, -1)):
         raise ValueError("tail_mask states the visibility: no causal, window_size, mask or attn_bias with it")
     if tuple(window_index(window_size)) != (-1, -1) and (mask is not None or attn_bias is not None):      # (as the C ABI: any window)
@@ -141,6 +147,8 @@ def attention_forward_cpu(q, k, v, mask=None, attn_bias=None, scale=8.0, groups=
             visible = None
             ii = torch.arange(r0, r1).unsqueeze(1) + offset
             jj = torch.arange(c0, c1).unsqueeze(0)
+            if alibi_slopes is not None:
+                logits = logits - alibi_slopes.float().reshape(1, -1, 1, 1) * (ii - jj).abs().float()
             if w_right is not None and c1 - 1 > r0 + offset + w_right:           # the block touches the (right) diagonal
                 visible = (jj <= ii + w_right)
             if w_left is not None and c0 < r1 - 1 + offset - w_left:              # ... the window's left edge
@@ -252,14 +260,15 @@ def quantise_e4m3(x, scale):
 
 
 def attention_forward_kvcache_cpu(q, k_cache, v_cache, k_new, v_new, seqlens, block_table=None, scale=8.0, groups=1, causal=False,
-                                  l2norm_qk=True, window_size=(-1, -1), k_scale=None, v_scale=None, return_lse=False, tree_words=None):
+                                  l2norm_qk=True, window_size=(-1, -1), k_scale=None, v_scale=None, return_lse=False, tree_words=None,
+                                  alibi_slopes=None):
     """Forward-only path of `flash_cosine_sim_attention_with_kvcache` on host tensors: the append as an indexed copy, then the dense CPU
     forward of every sequence over its first L_b = seqlens[b] + N_new cached positions (o = 0 where L_b == 0).  seqlens: host ints.
     k_scale / v_scale (float32 [B, Hk], both or neither): the caches are float8_e4m3fn codes meaning scale * code -- the append quantises
     (quantise_e4m3), and each sequence's keys and values are dequantised to float32 for the dense forward, whose result is cast to q's
     dtype.  return_lse: also the rows' log-sum-exp, float32 [B, H, N] (-inf where a row sees no key; k_scale is inside the logits, v_scale
     is not).  tree_words: int64 [N] (batch 1, the varlen path below): the rows' visibility words over the last N positions (`tree_tail`) in
-    place of causal."""
+    place of causal.  alibi_slopes: float32 [H] or [B, H]: the linear position bias of `attention_forward_cpu`, per sequence."""
     fp8 = k_scale is not None
     if k_new is not None:
         if fp8:
@@ -281,8 +290,9 @@ def attention_forward_kvcache_cpu(q, k_cache, v_cache, k_new, v_new, seqlens, bl
             qb = qb.float()
             kb, vb = kb.float() * k_scale[b][None, :, None, None], vb.float() * v_scale[b][None, :, None, None]
         tail = None if tree_words is None else tree_tail(tree_words, length)
+        slopes = None if alibi_slopes is None else (alibi_slopes if alibi_slopes.dim() == 1 else alibi_slopes[b])
         out[b:b + 1], lse[b:b + 1] = attention_forward_cpu(qb, kb, vb, scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk,
-                                                           window_size=window_size, return_lse=True, tail_mask=tail)
+                                                           window_size=window_size, return_lse=True, tail_mask=tail, alibi_slopes=slopes)
     return (out, lse) if return_lse else out
 
 
@@ -299,16 +309,20 @@ def tree_tail(words, length):
 
 def attention_forward_kvcache_varlen_cpu(q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, seqlens, block_table=None, scale=8.0, groups=1,
                                          causal=False, l2norm_qk=True, window_size=(-1, -1), k_scale=None, v_scale=None,
-                                         return_lse=False, tree_mask=None):
+                                         return_lse=False, tree_mask=None, alibi_slopes=None):
     """Forward-only path of `flash_cosine_sim_attention_varlen_with_kvcache` on host tensors: packed q [total_q, H, D] and k_new / v_new
     [total_q, Hk, D] with a validated host table; sequence b's N_b rows run through `attention_forward_kvcache_cpu` as a batch-1 call on
     its own cache (a view: the append lands in the caller's caches), so its rows and its cache slots are exactly what the equal-N path
     gives for that sequence alone.  seqlens: host ints, tokens cached before the append.  return_lse: also the rows' log-sum-exp, float32 [total_q, H].
     tree_mask (`flash_cosine_sim_attention_tree_with_kvcache`): int64 [total_q] packed like q (no causal, no window with it): with
     P_b = L_b - N_b every query of sequence b sees the cache positions before P_b, and query i sees position P_b + t iff bit t of its word is set; a sequence with N_b > 64 ignores its words and is
-    causal."""
+    causal.
+    alibi_slopes (`flash_cosine_sim_attention_alibi_with_kvcache`): float32 [H] or [B, H]: the logit of key j for query i of sequence b gains
+    -slope[b, h] * |L_b - N_b + i - j|.  It combines with causal and window_size, not with tree_mask."""
     if tree_mask is not None and (causal or tuple(window_index(window_size)) != (-1, -1)):
         raise ValueError("tree_mask states the visibility: no causal and no window_size with it")
+    if tree_mask is not None and alibi_slopes is not None:
+        raise ValueError("alibi_slopes is not taken with a tree_mask: a tree token's position is its depth, not its slot")
     out = torch.zeros_like(q)
     lse = torch.full(q.shape[:-1], float("-inf"), dtype=torch.float32)
     cq = cu_seqlens_q.tolist()
@@ -321,9 +335,11 @@ def attention_forward_kvcache_varlen_cpu(q, k_cache, v_cache, cu_seqlens_q, k_ne
         kc, vc = (k_cache, v_cache) if paged else (k_cache[b:b + 1], v_cache[b:b + 1])
         quant = {} if k_scale is None else dict(k_scale=k_scale[b:b + 1], v_scale=v_scale[b:b + 1])
         words = tree_mask[lo:hi] if tree_mask is not None and hi - lo <= TREE_MAX_TOKENS else None
+        slopes = None if alibi_slopes is None else (alibi_slopes if alibi_slopes.dim() == 1 else alibi_slopes[b])      # [H] of this sequence
         o, l = attention_forward_kvcache_cpu(rows(q), kc, vc, rows(k_new), rows(v_new), [seqlens[b]], block_table[b:b + 1] if paged else None,
                                              scale=scale, groups=groups, causal=causal or (tree_mask is not None and words is None),
-                                             l2norm_qk=l2norm_qk, window_size=window_size, return_lse=True, tree_words=words, **quant)
+                                             l2norm_qk=l2norm_qk, window_size=window_size, return_lse=True, tree_words=words,
+                                             alibi_slopes=slopes, **quant)
         out[lo:hi] = o[0].permute(1, 0, 2)
         lse[lo:hi] = l[0].permute(1, 0)
     return (out, lse) if return_lse else out

@@ -436,6 +436,7 @@ struct DecodeCall {
   const fcsa_lse_out* lse;            // where the combine also writes the rows' log-sum-exp (fcsa_forward_kvcache_lse), or NULL
   const fcsa_kvcache_step* step = nullptr;      // an engine step (fcsa_forward_kvcache_step): the routing of a ragged step, or NULL
   const fcsa_tree_mask* tree = nullptr;         // a tree step (fcsa_forward_kvcache_tree): the visibility words of a ragged step, or NULL
+  const fcsa_alibi* alibi = nullptr;            // a linear position bias (fcsa_forward_kvcache_alibi) on a ragged or engine step, or NULL
 };
 
 // The window of a decode call as the kernels take it.  A rectangular call is normalised (fcsa::win_normalise): a window that hides nothing
@@ -624,6 +625,12 @@ fcsa::DecodeStepParams decode_params(const DecodeCall& c, const DecodeWindow& wi
     dp.slots = (int)d.slots;
     dp.append = kv->new_len != 0 ? 1 : 0;
   }
+  if (c.alibi != nullptr) {
+    // device slopes of any sign cannot be bounded here: always the per-row-shift regime, as a dense call with a bias it cannot bound
+    dp.c2 = 0.f;
+    dp.l_eps = 1e-30f;
+    dp.dyn = 1;
+  }
   return dp;
 }
 
@@ -649,14 +656,33 @@ int append_launch(const DecodeCall& c, fcsa::DecodeForm form, const fcsa::Decode
   return timed(n.name, n.what, s, [&] { return fcsa::launch_kv_append(c.a->p.dtype, c.a->p.dim_head, form, dp, s); });
 }
 
-// the chunk launch: the call's block with 128-row slots, one split and no workspace
-int chunk_launch(const LaunchName& n, const DecodeCall& c, fcsa::DecodeForm form, fcsa::DecodeStepParams dp, int64_t slots, hipStream_t s) {
+// c.alibi (a linear position bias): the slopes as the kernels take them, and the names of the launches that apply them
+fcsa::DecodeAlibi alibi_view(const fcsa_alibi& al) { return {al.slopes, al.stride_b, al.stride_h}; }
+constexpr LaunchName kAlibiDecodeName[2] = {{"alibi_decode", "decode (alibi)"}, {"alibi_decode_fp8", "decode (alibi, fp8)"}};
+constexpr LaunchName kAlibiPrefillName[2] = {{"alibi_prefill", "prefill (alibi)"}, {"alibi_prefill_fp8", "prefill (alibi, fp8)"}};
+
+// the decode launch of a ragged or engine step under the name `plain`; c.alibi: the entry points that take the slopes, under their own name
+int decode_launch(const LaunchName& plain, const DecodeCall& c, fcsa::DecodeForm form, const fcsa::DecodeStepParams& dp, hipStream_t s) {
+  const fcsa_problem& p = c.a->p;
+  if (c.alibi == nullptr) return timed(plain.name, plain.what, s, [&] { return fcsa::launch_decode(p.dtype, p.dim_head, form, dp, s); });
+  const LaunchName& n = kAlibiDecodeName[form.fp8];
+  const fcsa::DecodeAlibi al = alibi_view(*c.alibi);
+  return timed(n.name, n.what, s, [&] { return fcsa::launch_decode_alibi(p.dtype, p.dim_head, form, dp, al, s); });
+}
+
+// the chunk launch under the name `plain`: the call's block with 128-row slots, one split and no workspace; c.alibi: as in decode_launch
+int chunk_launch(const LaunchName& plain, const DecodeCall& c, fcsa::DecodeForm form, fcsa::DecodeStepParams dp, int64_t slots, hipStream_t s) {
   dp.slots = (int)slots;
   dp.splits = 1;
   dp.ws_o = nullptr;
   dp.ws_ml = nullptr;
   const fcsa::DecodeLseOut lo = c.lse != nullptr ? lse_view(*c.lse, true) : fcsa::DecodeLseOut{};
-  return timed(n.name, n.what, s, [&] { return fcsa::launch_prefill(c.a->p.dtype, c.a->p.dim_head, form, dp, c.lse != nullptr ? &lo : nullptr, s); });
+  const fcsa::DecodeLseOut* lse = c.lse != nullptr ? &lo : nullptr;
+  if (c.alibi == nullptr)
+    return timed(plain.name, plain.what, s, [&] { return fcsa::launch_prefill(c.a->p.dtype, c.a->p.dim_head, form, dp, lse, s); });
+  const LaunchName& n = kAlibiPrefillName[form.fp8];
+  const fcsa::DecodeAlibi al = alibi_view(*c.alibi);
+  return timed(n.name, n.what, s, [&] { return fcsa::launch_prefill_alibi(c.a->p.dtype, c.a->p.dim_head, form, dp, al, lse, s); });
 }
 
 // c.tree (a tree step): the ragged call without a window and without `causal` -- its checks, plan, workspace, append and combine -- with the
@@ -695,8 +721,7 @@ int decode_call(const DecodeCall& c) {
     const fcsa::DecodeTreeMask tm = {c.tree->mask};
     if (int rc = timed(n.name, n.what, s, [&] { return fcsa::launch_decode_tree(p.dtype, p.dim_head, form, dp, tm, s); })) return rc;
   } else {
-    const LaunchName& n = kDecodeName[ragged][fp8];
-    if (int rc = timed(n.name, n.what, s, [&] { return fcsa::launch_decode(p.dtype, p.dim_head, form, dp, s); })) return rc;
+    if (int rc = decode_launch(kDecodeName[ragged][fp8], c, form, dp, s)) return rc;
   }
   const LaunchName& m = kCombineName[ragged][fp8][c.lse != nullptr];
   return timed(m.name, m.what, s, [&] { return fcsa::launch_decode_combine(p.dtype, p.dim_head, form, dp, c.lse != nullptr ? &lo : nullptr, s); });
@@ -762,7 +787,7 @@ int step_call(const DecodeCall& c) {
   const fcsa_kvcache_step& st = *c.step;
   const bool rows = p.batch > 0 && p.heads > 0 && c.seqs->total_q > 0;
   if (rows && c.lse != nullptr && c.lse->lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_step: lse: null pointer");
-  if (!has_chunk_kernel(p)) return decode_call({c.a, c.kv, c.seqs, c.qz, c.w, c.lse});
+  if (!has_chunk_kernel(p)) return decode_call({c.a, c.kv, c.seqs, c.qz, c.w, c.lse, nullptr, nullptr, c.alibi});
   const bool fp8 = c.qz != nullptr;
   const DecodeWindow win = decode_window(p, *kv, true, c.w);
   const DecodePlan d = step_plan(p, *kv, *c.seqs, st, win.reach());
@@ -783,8 +808,7 @@ int step_call(const DecodeCall& c) {
   if (!rows) return FCSA_OK;
   // 2. the decode-routed sequences: split partials and their combine over the slots and rows of the full table
   if (!st.no_decode) {
-    const LaunchName& n = kStepDecodeName[fp8];
-    if (int rc = timed(n.name, n.what, s, [&] { return fcsa::launch_decode(p.dtype, p.dim_head, form, sp, s); })) return rc;
+    if (int rc = decode_launch(kStepDecodeName[fp8], c, form, sp, s)) return rc;
     const LaunchName& m = kStepCombineName[fp8][c.lse != nullptr];
     if (int rc = timed(m.name, m.what, s, [&] { return fcsa::launch_decode_combine(p.dtype, p.dim_head, form, sp, c.lse != nullptr ? &lo : nullptr, s); }))
       return rc;
@@ -862,6 +886,16 @@ int fcsa_forward_kvcache_tree(const fcsa_forward_args* a, const fcsa_kvcache* kv
   if ((reinterpret_cast<uintptr_t>(tree->mask) & 7) != 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_tree: mask not 8-byte aligned");
   if (rows && lse != nullptr && lse->lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_tree: lse: null pointer");
   return decode_call({a, kv, seqs, qz, nullptr, lse, nullptr, tree});
+}
+
+int fcsa_forward_kvcache_alibi(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_kvcache_quant* qz,
+                               const fcsa_window* w, const fcsa_kvcache_step* step, const fcsa_alibi* alibi, const fcsa_lse_out* lse) {
+  if (a == nullptr || kv == nullptr || seqs == nullptr || step == nullptr || alibi == nullptr)
+    return fail(FCSA_ERR_INVALID_ARG, "kvcache_alibi: null argument");
+  if (alibi->slopes == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_alibi: slopes: null pointer");
+  if ((reinterpret_cast<uintptr_t>(alibi->slopes) & 3) != 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_alibi: slopes not 4-byte aligned");
+  if (alibi->reserved != 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_alibi: reserved (%lld) is 0", (long long)alibi->reserved);
+  return step_call({a, kv, seqs, qz, w, lse, step, nullptr, alibi});
 }
 
 int fcsa_kvcache_compact(const fcsa_kvcache* kv, int32_t batch, int32_t kv_heads, int32_t dim_head, int32_t elem_bytes, const int32_t* accepted,

@@ -22,6 +22,8 @@
 // A tree step (fcsa_forward_kvcache_tree) is a ragged step whose decode launch reads a 64-bit visibility word per
 // packed row -- decode_tree[_fp8]_kernel (decode_body with TREE; launch_decode_tree) -- between the ragged call's own append and combine;
 // kv_compact_kernel (fcsa_kvcache_compact; launch_kv_compact) then moves the accepted path to the front of the slots the step appended.
+// A call with a linear position bias (fcsa_forward_kvcache_alibi) is a ragged or engine step whose decode launch
+// reads a slope per (sequence, head) -- alibi_decode[_fp8]_kernel (decode_body with ALIBI; launch_decode_alibi), per-row-shift regime only.
 // The append is written once for every form: where a new row goes (append_pos: the cache_seqlens clamp and the drop at the capacity), the
 // address of that position (cache_base of fcsa_decode_common.cuh, the readers' own rule) and the row write (append_chunk: a copy, or the
 // quantisation of an fp8 cache).  The three append entry points are the index decomposition of their layout and calls to those.
@@ -143,14 +145,18 @@ template <typename T, int D, bool FP8 = false> struct DecodeRegs {
 // (tm.words, loaded once per lane next to last_key).  With P = L - N: a key before the step (key < P) is visible to every row, the step's
 // token t (key P + t) iff bit t of the row's word is set; a sequence with N > 64 ignores its words and is causal.  Only the per-logit test
 // differs from the ragged form: key range, splits, loads, both products and the partials are its own.
-template <typename T, int D, bool DYN, bool GEN, bool WIN, bool FP8 = false, bool RAGGED = false, bool STEP = false, bool TREE = false>
+// ALIBI (alibi_decode_kernel, alibi_decode_fp8_kernel): a ragged or step form in the per-row-shift regime whose logits gain the linear
+// position bias -slope[b, h] * |last_key - key| (al.slopes; alibi_slope / alibi_logit of fcsa_decode_common.cuh): the slope is loaded once per
+// lane row, the float distance to the block once per block, and the bias joins the logit where the scale does, so the row max includes it.
+template <typename T, int D, bool DYN, bool GEN, bool WIN, bool FP8 = false, bool RAGGED = false, bool STEP = false, bool TREE = false, bool ALIBI = false>
 FCSA_DEV void decode_body(const std::conditional_t<STEP, DecodeStepParams, std::conditional_t<RAGGED, DecodeRaggedParams,
                                                    std::conditional_t<FP8, DecodeFp8Params, std::conditional_t<WIN, DecodeWinParams, DecodeParams>>>>& p,
-                          const DecodeTreeMask& tm = DecodeTreeMask{}) {
+                          const DecodeTreeMask& tm = DecodeTreeMask{}, const DecodeAlibi& al = DecodeAlibi{}) {
   static_assert(!FP8 || Traits<T>::ES == 2, "an fp8 cache is read with 16-bit queries");
   static_assert(!RAGGED || WIN, "the ragged entry points carry the window fields");
   static_assert(!STEP || RAGGED, "a step is a ragged step");
   static_assert(!TREE || (RAGGED && !STEP), "a tree step is a ragged step");
+  static_assert(!ALIBI || (RAGGED && DYN && !TREE), "a position bias comes with the ragged and step forms, in the per-row-shift regime");
   typedef DecodeRegs<T, D, FP8> R;
   typedef DecodeLds<D, R::ES, GEN> LP;
   constexpr int ES = R::ES, UE = R::UE, NJ = R::NJ, CPR = R::CPR, VCH = R::VCH;
@@ -203,6 +209,8 @@ FCSA_DEV void decode_body(const std::conditional_t<STEP, DecodeStepParams, std::
   if constexpr (TREE) {
     if (row_ok) word = tm.words[q0 + qi];
   }
+  [[maybe_unused]] float nslope = 0.f;
+  if constexpr (ALIBI) nslope = alibi_slope(al, b, h);
   const int gs = D / p.groups;
   float* norm_scratch = reinterpret_cast<float*>(smem + LP::VBYTES);
   auto normalise = [&](float (&xr)[NJ][UE]) {
@@ -263,6 +271,8 @@ FCSA_DEV void decode_body(const std::conditional_t<STEP, DecodeStepParams, std::
         }
       }
       if (p.l2norm) normalise(xk);
+      [[maybe_unused]] float d0 = 0.f;             // ALIBI: from the row's position to the first key this lane holds of the block
+      if constexpr (ALIBI) d0 = (float)(last_key - kb - 4 * hi);
       s[sb] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
@@ -280,7 +290,8 @@ FCSA_DEV void decode_body(const std::conditional_t<STEP, DecodeStepParams, std::
         bool vis = key < end && (!p.causal || key <= last_key);
         if constexpr (WIN) vis = key < end && key <= last_key + p.win_hi && key >= last_key - p.win_lo;
         if constexpr (TREE) vis = key < end && (key < P || (use_bits ? ((word >> ((key - P) & 63)) & 1) != 0 : key <= last_key));
-        s[sb][rr] = vis ? s[sb][rr] * smul : -INFINITY;
+        if constexpr (ALIBI) s[sb][rr] = vis ? alibi_logit(s[sb][rr], smul, nslope, d0, 16 * sb + rr) : -INFINITY;
+        else s[sb][rr] = vis ? s[sb][rr] * smul : -INFINITY;
       }
     }
     f32x4 pr[2];
@@ -384,6 +395,16 @@ __global__ __launch_bounds__(64) void decode_tree_kernel(DecodeRaggedParams p, D
 template <typename T, int D, bool DYN, bool GEN>
 __global__ __launch_bounds__(64) void decode_tree_fp8_kernel(DecodeRaggedParams p, DecodeTreeMask tm) {
   decode_body<T, D, DYN, GEN, true, true, true, false, true>(p, tm);
+}
+// a call with a linear position bias (launch_decode_alibi): the ragged entry points' block or, with STEP, the step entry points', and the
+// slopes as a second argument.  The per-row-shift regime only.
+template <typename T, int D, bool GEN, bool STEP>
+__global__ __launch_bounds__(64) void alibi_decode_kernel(std::conditional_t<STEP, DecodeStepParams, DecodeRaggedParams> p, DecodeAlibi al) {
+  decode_body<T, D, true, GEN, true, false, true, STEP, false, true>(p, DecodeTreeMask{}, al);
+}
+template <typename T, int D, bool GEN, bool STEP>
+__global__ __launch_bounds__(64) void alibi_decode_fp8_kernel(std::conditional_t<STEP, DecodeStepParams, DecodeRaggedParams> p, DecodeAlibi al) {
+  decode_body<T, D, true, GEN, true, true, true, STEP, false, true>(p, DecodeTreeMask{}, al);
 }
 // the decode side of an engine step (launch_decode with the step form): 16-bit types and D = 64 / 128, where every group width is reduced in registers
 template <typename T, int D, bool DYN>
@@ -772,6 +793,38 @@ hipError_t launch_decode_tree(int dtype, int D, DecodeForm f, const DecodeStepPa
         else return hipErrorInvalidValue;
       }
       return p.dyn ? go(Y{}, N{}) : go(N{}, N{});
+    }
+  });
+}
+
+// launch_decode's ragged form -- or, where the step kernels exist, its step form: f.step must say which (one form per problem is
+// compiled) -- on the entry points that take the slopes: the same workgroups, block and LDS.  The per-row-shift regime only.
+hipError_t launch_decode_alibi(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeAlibi& alibi, hipStream_t s) {
+  if (!f.ragged || !p.dyn || alibi.slopes == nullptr) return hipErrorInvalidValue;
+  return dispatch_decode(dtype, D, f, [&](auto td, auto fp8, auto ragged) -> hipError_t {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    constexpr int ES = Traits<T>::ES;
+    constexpr bool FP8 = decltype(fp8)::value, RAGGED = decltype(ragged)::value;
+    if constexpr (!RAGGED) {
+      return hipErrorInvalidValue;
+    } else {
+      constexpr bool STEP = kStepKernels<T, DD, RAGGED>;
+      if (f.step != STEP) return hipErrorInvalidValue;
+      const int64_t wgs = (int64_t)p.slots * p.Hk * p.splits;
+      if (wgs <= 0) return hipSuccess;
+      const dim3 grid((unsigned)wgs), block(64);
+      auto go = [&](auto gen) -> hipError_t {
+        constexpr bool GN = decltype(gen)::value;
+        constexpr int LDS = DecodeLds<DD, ES, GN>::BYTES;
+        if constexpr (FP8) return launch_part<alibi_decode_fp8_kernel<T, DD, GN, STEP>, LDS>(grid, block, s, p, alibi);
+        else return launch_part<alibi_decode_kernel<T, DD, GN, STEP>, LDS>(grid, block, s, p, alibi);
+      };
+      if (p.l2norm && !decode_groups_fast(DD, p.groups, Unit<T>::UE)) {
+        if constexpr (DD == 96) return go(std::true_type{});
+        else return hipErrorInvalidValue;
+      }
+      return go(std::false_type{});
     }
   });
 }

@@ -180,6 +180,14 @@ template <bool DYN, int FB> FCSA_DEV void softmax_step(const f32x4 (&s)[2], floa
     }
 }
 
+// The linear position bias of the ALIBI forms (fcsa_forward_kvcache_alibi), for both kernels.  alibi_slope: -slope * log2(e) of the row's
+// (sequence, head), loaded once per lane row.  alibi_logit: the biased logit in log2 units, s * smul - slope * log2(e) * |d0 - c|, where d0 is
+// the float distance from the row's position to a point of the key block (hoisted by the caller) and c the key's offset from that point: one
+// subtract and one fma (the |.| is an operand modifier) on top of the multiply every form does.  Distances are integers in float32, exact
+// below 2^24, and the product with the slope is rounded once, inside the fma.
+FCSA_DEV float alibi_slope(const DecodeAlibi& al, int b, int h) { return -(al.slopes[(int64_t)b * al.sb + (int64_t)h * al.sh] * 1.4426950408889634f); }
+FCSA_DEV float alibi_logit(float s, float smul, float nslope, float d0, int c) { return fmaf(nslope, fabsf(d0 - (float)c), s * smul); }
+
 // O^T += V^T P~^T for the 32-key block of 16-bit V at rows row0 ... row0 + 31 of `v` in LDS (pitch kKvPitch<D, 2>): lane 4q + p of the
 // 16-lane group hi (x = lane & 15 = 4q + p) addresses key 4 hi + q, features 16 fb + 4p ... + 3; lane x receives feature 16 fb + x.  Every
 // transposed read feeds the NT row tiles pb[0 .. NT) -> acc[0 .. NT).

@@ -172,6 +172,13 @@ struct DecodeLseOut {
 struct DecodeTreeMask {
   const uint64_t* words;            // [total_q] device
 };
+// The per-head slopes of a linear position bias (fcsa_forward_kvcache_alibi): a second kernel argument of the entry points that apply it
+// (alibi_decode[_fp8]_kernel, alibi_prefill_kernel), as DecodeTreeMask is of the tree entry points.  The logit of key j for the query at
+// position pos = L_b - N_b + i gains -slopes[b * sb + h * sh] * |pos - j| (natural units).  ELEMENT strides; sb = 0: one row for every sequence.
+struct DecodeAlibi {
+  const float* slopes;              // device
+  int64_t sb, sh;
+};
 // An engine step (fcsa_forward_kvcache_step): the ragged step's block plus the routing threshold.  Sequence b takes the chunk kernel
 // (step_prefill_kernel) iff G * N_b >= chunk_rows and the decode kernels (step_decode[_fp8]_kernel, step_combine[_lse]_kernel) otherwise;
 // all of them evaluate that on the device from the clamped table (ragged_cu), so every row is written by exactly one of them.
@@ -208,6 +215,12 @@ hipError_t launch_kv_compact(const DecodeParams& cache, const CompactParams& c, 
 // else: hipErrorInvalidValue).  One kernel writes o and, where lse is not nullptr, the rows' log-sum-exp.  An fp8 cache and a window come
 // with f.step only (fp8 without it: hipErrorInvalidValue).
 hipError_t launch_prefill(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeLseOut* lse, hipStream_t s);
+// The decode and chunk launches of a call with a linear position bias (fcsa_forward_kvcache_alibi): launch_decode's ragged or step form and
+// launch_prefill's step form -- the same grids, LDS and blocks -- on the entry points that take the slopes.  They exist in the per-row-shift
+// regime only (p.dyn must be set) and always carry the window sides, open where the call has none; f.ragged must be set, and f.step exactly
+// where the step kernels exist (16-bit types, D = 64 / 128: one decode form per problem is compiled); hipErrorInvalidValue otherwise.  Append and combine are launch_kv_append / launch_decode_combine.
+hipError_t launch_decode_alibi(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeAlibi& alibi, hipStream_t s);
+hipError_t launch_prefill_alibi(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeAlibi& alibi, const DecodeLseOut* lse, hipStream_t s);
 
 // Merging attention states (fcsa_merge_states, csrc/fcsa_merge.hip): S states (o_s, lse_s) of the rows [n0, n1, n2] -> (o, lse).  o views
 // carry BYTE strides, lse views ELEMENT strides.

@@ -16,6 +16,8 @@
 //                    first key the tile's first token sees (prefill_kstart).  FP8: an e4m3fn cache -- a lane loads 8 bytes per K and V fragment,
 //                    K becomes K^ exactly as decode_body<FP8> makes it, V's codes are converted to the type on the way into LDS, and the
 //                    epilogue multiplies by v_scale as decode_combine_body<FP8> does.
+//   alibi_prefill_kernel  the chunk side of a call with a linear position bias (fcsa_forward_kvcache_alibi): the
+//                    windowed step form in the per-row-shift regime with ALIBI -- the slopes as a third kernel argument (launch_prefill_alibi).
 // The append before it is the ragged call's (launch_kv_append with the same parameter block).  16-bit types, D = 64 / 128 only.
 // Host side: one launcher, launch_prefill, for both entry points -- one copy of the refusals and of the grid; the form (DecodeForm::step,
 // fp8, and the window sides of the block) picks the entry point, which gets the part of the block it declares (launch_part).
@@ -105,9 +107,18 @@ template <typename T, int D> constexpr int kPrefillWavesPerSimd = (std::is_same_
 // key and value fragments are half as wide in registers, and every fp8 form stays below 256 (247 - 249 at D = 128, no scratch)
 template <typename T, int D, bool WIN, bool FP8> constexpr int kStepPrefillWavesPerSimd = FP8 ? 2 : kPrefillWavesPerSimd<T, D>;
 
-template <typename T, int D, bool DYN, bool STEP = false, bool WIN = false, bool FP8 = false>
-FCSA_DEV void prefill_body(const std::conditional_t<STEP, DecodeStepParams, DecodeRaggedParams>& p, const DecodeLseOut& lo) {
+// ... and of the forms with a position bias (alibi_prefill_kernel; profiles/alibi_resources.txt): the slopes and the float distances take the
+// bf16 D = 128 form on a 16-bit cache past 256 registers too (24 bytes of scratch when held to them), so both 16-bit-cache forms at D = 128 run
+// one wave per SIMD; the fp8 forms stay at 253, no scratch
+template <typename T, int D, bool FP8> constexpr int kAlibiPrefillWavesPerSimd = (!FP8 && D == 128) ? 1 : 2;
+
+// ALIBI (alibi_prefill_kernel): the windowed step form in the per-row-shift regime whose logits gain the linear position bias of
+// decode_body<ALIBI> -- the same two functions (alibi_slope, alibi_logit), the slope once per lane row, the float distance once per block.
+template <typename T, int D, bool DYN, bool STEP = false, bool WIN = false, bool FP8 = false, bool ALIBI = false>
+FCSA_DEV void prefill_body(const std::conditional_t<STEP, DecodeStepParams, DecodeRaggedParams>& p, const DecodeLseOut& lo,
+                           const DecodeAlibi& al = DecodeAlibi{}) {
   static_assert(STEP || (!WIN && !FP8), "windows and fp8 caches come with the step entry points");
+  static_assert(!ALIBI || (STEP && WIN && DYN), "a position bias comes with the windowed step form, in the per-row-shift regime");
   typedef PrefillLds<D> LP;
   typedef PrefillRegs<T, D, FP8> R;
   constexpr int NJ = R::NJ, FB = D / 16, NT = kPrefillTiles;
@@ -138,6 +149,7 @@ FCSA_DEV void prefill_body(const std::conditional_t<STEP, DecodeStepParams, Deco
 
   // this lane's query rows, one per row tile: the column of every MFMA result
   int last_key[NT];
+  [[maybe_unused]] float nslope[NT];
   u32x4 qf[NT][NJ];
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
@@ -145,6 +157,7 @@ FCSA_DEV void prefill_body(const std::conditional_t<STEP, DecodeStepParams, Deco
     const bool row_ok = r < (int64_t)p.G * N;
     const int g = row_ok ? (int)(r % p.G) : 0, qi = row_ok ? (int)(r / p.G) : 0;
     last_key[t] = L - N + qi;                  // causal: key j is visible iff j <= last_key
+    if constexpr (ALIBI) nslope[t] = alibi_slope(al, b, kvh * p.G + g);
     float xq[NJ][8];
     const char* qrow = p.q.p + (int64_t)(kvh * p.G + g) * p.q.sh + (int64_t)(q0 + qi) * p.q.sn;
 #pragma unroll
@@ -209,6 +222,8 @@ FCSA_DEV void prefill_body(const std::conditional_t<STEP, DecodeStepParams, Deco
       u32x4 pb[NT];
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
+        [[maybe_unused]] float d0 = 0.f;           // ALIBI: from the row's position to the first key this lane holds of the block
+        if constexpr (ALIBI) d0 = (float)(last_key[t] - kb - 4 * hi);
 #pragma unroll
         for (int sb = 0; sb < 2; ++sb)
 #pragma unroll
@@ -216,7 +231,8 @@ FCSA_DEV void prefill_body(const std::conditional_t<STEP, DecodeStepParams, Deco
             const int key = kb + 16 * sb + 4 * hi + rr;
             bool vis = key < L && (!p.causal || key <= last_key[t]);
             if constexpr (WIN) vis = key < L && key <= last_key[t] + p.win_hi && key >= last_key[t] - p.win_lo;
-            s[t][sb][rr] = vis ? s[t][sb][rr] * smul : -INFINITY;
+            if constexpr (ALIBI) s[t][sb][rr] = vis ? alibi_logit(s[t][sb][rr], smul, nslope[t], d0, 16 * sb + rr) : -INFINITY;
+            else s[t][sb][rr] = vis ? s[t][sb][rr] * smul : -INFINITY;
           }
         f32x4 pr[2];
         softmax_step<DYN>(s[t], m[t], l[t], acc[t], p.c2, pr);
@@ -281,6 +297,13 @@ __global__ __launch_bounds__(64 * kPrefillWaves, (kStepPrefillWavesPerSimd<T, D,
   prefill_body<T, D, DYN, true, WIN, FP8>(p, lo);
 }
 
+// The chunk side of a call with a linear position bias (launch_prefill_alibi): the windowed step form with the slopes as a third argument.
+template <typename T, int D, bool FP8>
+__global__ __launch_bounds__(64 * kPrefillWaves, (kAlibiPrefillWavesPerSimd<T, D, FP8>)) void alibi_prefill_kernel(DecodeStepParams p, DecodeLseOut lo,
+                                                                                                                 DecodeAlibi al) {
+  prefill_body<T, D, true, true, true, FP8, true>(p, lo, al);
+}
+
 }  // namespace
 
 // One 4-wave workgroup per (row-tile slot of 128 rows, K/V head): p.slots = fcsa::prefill_slots(total_q, B, G, kPrefillRows).  lse: nullptr,
@@ -306,6 +329,23 @@ hipError_t launch_prefill(int dtype, int D, DecodeForm f, const DecodeStepParams
       return launch_part<step_prefill_kernel<T, DD, DY, false, false>, LDS>(grid, block, s, p, lo);
     };
     return p.dyn ? go(std::true_type{}) : go(std::false_type{});
+  });
+}
+
+// launch_prefill's step form on the entry points that take the slopes: the same grid, block and LDS; always the windowed form, with the
+// sides of the block (open ones where the call has no window)
+hipError_t launch_prefill_alibi(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeAlibi& alibi, const DecodeLseOut* lse, hipStream_t s) {
+  if (!f.step || !f.ragged || !p.dyn || alibi.slopes == nullptr) return hipErrorInvalidValue;
+  return dispatch_chunk(dtype, D, [&](auto td) -> hipError_t {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    constexpr int LDS = PrefillLds<DD>::BYTES;
+    if (p.l2norm && !decode_groups_fast(DD, p.groups, 8)) return hipErrorInvalidValue;
+    if ((int64_t)p.slots * p.Hk <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((int64_t)p.slots * p.Hk)), block(64 * kPrefillWaves);
+    const DecodeLseOut lo = lse != nullptr ? *lse : DecodeLseOut{};
+    if (f.fp8) return launch_part<alibi_prefill_kernel<T, DD, true>, LDS>(grid, block, s, p, lo, alibi);
+    return launch_part<alibi_prefill_kernel<T, DD, false>, LDS>(grid, block, s, p, lo, alibi);
   });
 }
 

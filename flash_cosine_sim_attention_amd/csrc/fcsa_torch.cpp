@@ -72,7 +72,9 @@ namespace {
   X(forward_kvcache_step_ws, fcsa_forward_kvcache_step_workspace_bytes, false)        \
   /* tree attention for speculative decoding, and the compaction of the accepted path */ \
   X(forward_kvcache_tree, fcsa_forward_kvcache_tree, false)                               \
-  X(kvcache_compact, fcsa_kvcache_compact, false)
+  X(kvcache_compact, fcsa_kvcache_compact, false)                                         \
+  /* a linear position bias (ALiBi) on the engine step */                                 \
+  X(forward_kvcache_alibi, fcsa_forward_kvcache_alibi, false)
 
 struct Abi {
 #define X(member, symbol, required) decltype(&symbol) member = &symbol;
@@ -728,8 +730,10 @@ Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor
                             const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table, int64_t max_seqlen_k, double scale, bool causal,
                             bool l2norm_qk, int64_t groups, const fcsa_window* win, const Tensor* k_scale = nullptr, const Tensor* v_scale = nullptr,
                             const Tensor* cu_q = nullptr, int64_t max_seqlen_q = 0, Tensor* lse_out = nullptr, bool prefill = false,
-                            const fcsa_kvcache_step* step = nullptr, const Tensor* tree = nullptr) {
+                            const fcsa_kvcache_step* step = nullptr, const Tensor* tree = nullptr, const Tensor* alibi = nullptr) {
   const bool ragged = cu_q != nullptr;
+  if (alibi != nullptr)     // kvcache_alibi_forward: an engine step through fcsa_forward_kvcache_alibi (the step's workspace; the lse always)
+    need_abi("alibi_slopes", "fcsa_forward_kvcache_alibi", g_abi.forward_kvcache_alibi);
   if (tree != nullptr)      // kvcache_tree_forward: a ragged step through fcsa_forward_kvcache_tree (the ragged call's workspace; the lse always)
     need_abi("tree_mask", "fcsa_forward_kvcache_tree", g_abi.forward_kvcache_tree);
   if (step != nullptr)      // kvcache_step_forward: a ragged step through fcsa_forward_kvcache_step (its own workspace; the lse always)
@@ -785,6 +789,16 @@ Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor
     words = tree->contiguous();
   }
   // ragged: N is the number of packed rows
+  Tensor slopes;
+  if (alibi != nullptr) {
+    TORCH_CHECK_TYPE(alibi->scalar_type() == at::kFloat, "alibi_slopes must be float32, got ", alibi->scalar_type());
+    same_dev("alibi_slopes", *alibi);
+    TORCH_CHECK_VALUE(ragged && step != nullptr && lse_out != nullptr, "alibi_slopes come with the engine step");
+    const int64_t seqs_n = cu.numel() - 1;
+    TORCH_CHECK_VALUE((alibi->dim() == 1 && alibi->size(0) == q.size(1)) || (alibi->dim() == 2 && alibi->size(0) == seqs_n && alibi->size(1) == q.size(1)),
+                      "alibi_slopes must be [heads] (", q.size(1), ") or [sequences, heads] (", seqs_n, ", ", q.size(1), "), got ", alibi->sizes());
+    slopes = *alibi;      // any strides: the kernels take element strides, and a view keeps in-place updates visible to a captured graph
+  }
   const int64_t B = ragged ? cu.numel() - 1 : q.size(0), H = q.size(1), N = ragged ? q.size(0) : q.size(2), D = q.size(-1), Hk = k_cache.size(1);
   TORCH_CHECK_VALUE(k_cache.size(3) == D, "query, key, value dimensions must be the same");
   TORCH_CHECK_VALUE(D == 16 || D == 32 || D == 64 || D == 96 || D == 128, "only dimensions (16, 32, 64, 96, 128) allowed for now, got ", D);
@@ -907,6 +921,15 @@ Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor
       check(g_abi.forward_kvcache_prefill(&a, &kv, &seqs, &lo), "fcsa_forward_kvcache_prefill");
       return o;
     }
+    if (alibi != nullptr) {
+      fcsa_alibi al;
+      std::memset(&al, 0, sizeof(al));
+      al.slopes = slopes.data_ptr<float>();
+      al.stride_b = slopes.dim() == 2 ? slopes.stride(0) : 0;
+      al.stride_h = slopes.stride(-1);
+      check(g_abi.forward_kvcache_alibi(&a, &kv, &seqs, fp8 ? &qz : nullptr, win, step, &al, &lo), "fcsa_forward_kvcache_alibi");
+      return o;
+    }
     if (step != nullptr) {
       check(g_abi.forward_kvcache_step(&a, &kv, &seqs, fp8 ? &qz : nullptr, win, step, &lo), "fcsa_forward_kvcache_step");
       return o;
@@ -1016,6 +1039,33 @@ std::tuple<Tensor, Tensor> kvcache_step_forward(const Tensor& q, const Tensor& k
   Tensor o = kvcache_forward_impl(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups,
                                   windowed ? &w : nullptr, k_scale.has_value() ? &*k_scale : nullptr, v_scale.has_value() ? &*v_scale : nullptr,
                                   &cu_seqlens_q, max_seqlen_q, &lse, false, &st);
+  return {o, lse};
+}
+
+// An engine step with a linear position bias: kvcache_step_forward with alibi_slopes (float32 [H] or [B, H] on q's device, never read on
+// the host), through fcsa_forward_kvcache_alibi.
+std::tuple<Tensor, Tensor> kvcache_alibi_forward(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& cu_seqlens_q,
+                                                 const Tensor& alibi_slopes, const optional<Tensor>& k_new, const optional<Tensor>& v_new,
+                                                 const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table,
+                                                 const optional<Tensor>& k_scale, const optional<Tensor>& v_scale, int64_t max_seqlen_q,
+                                                 int64_t max_seqlen_k, double scale, bool causal, bool l2norm_qk, int64_t groups, int64_t left,
+                                                 int64_t right, int64_t chunk_rows, int64_t max_decode_tokens, bool no_decode, bool no_chunk) {
+  TORCH_CHECK_VALUE(k_scale.has_value() == v_scale.has_value(), "k_scale and v_scale must be given together");
+  TORCH_CHECK_VALUE(chunk_rows >= -1, "chunk_rows must be a non-negative integer (or -1: the default), got ", chunk_rows);
+  TORCH_CHECK_VALUE(max_decode_tokens >= -1, "max_decode_tokens must be a non-negative integer (or -1: total_q), got ", max_decode_tokens);
+  const bool windowed = !(left == -1 && right == -1);
+  fcsa_window w;
+  if (windowed) w = Win(left, right).w;
+  fcsa_kvcache_step st;
+  std::memset(&st, 0, sizeof(st));
+  st.chunk_rows = (int32_t)std::min<int64_t>(chunk_rows, INT32_MAX);
+  st.max_decode_tokens = std::min<int64_t>(max_decode_tokens, INT32_MAX);
+  st.no_decode = no_decode;
+  st.no_chunk = no_chunk;
+  Tensor lse;
+  Tensor o = kvcache_forward_impl(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups,
+                                  windowed ? &w : nullptr, k_scale.has_value() ? &*k_scale : nullptr, v_scale.has_value() ? &*v_scale : nullptr,
+                                  &cu_seqlens_q, max_seqlen_q, &lse, false, &st, nullptr, &alibi_slopes);
   return {o, lse};
 }
 
@@ -1472,6 +1522,15 @@ TORCH_LIBRARY_IMPL(fcsa_tree, CUDA, m) {
   m.impl("kvcache_tree_forward", &kvcache_tree_forward);
   m.impl("kvcache_compact", &kvcache_compact);
 }
+
+// the engine step with a linear position bias, likewise.  Forward only: no Autograd kernel.
+TORCH_LIBRARY(fcsa_alibi, m) {
+  m.def("kvcache_alibi_forward(Tensor q, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor cu_seqlens_q, Tensor alibi_slopes, Tensor? k_new, "
+        "Tensor? v_new, Tensor? cache_seqlens, Tensor? block_table, Tensor? k_scale, Tensor? v_scale, int max_seqlen_q, int max_seqlen_k, "
+        "float scale, bool causal, bool l2norm_qk, int groups, int window_left, int window_right, int chunk_rows, int max_decode_tokens, "
+        "bool no_decode, bool no_chunk) -> (Tensor, Tensor)");
+}
+TORCH_LIBRARY_IMPL(fcsa_alibi, CUDA, m) { m.impl("kvcache_alibi_forward", &kvcache_alibi_forward); }
 
 // Attention states for training, in a namespace of their own (the op set of `fcsa` is pinned): the attention op with the rows'
 // log-sum-exp as a second differentiable result -- dense, local (window sides other than (-1, -1)) or packed (cu_seqlens given) -- and

@@ -617,6 +617,17 @@ def _step_count(name, value):
     return value
 
 
+def _step_routing(c, total_q, H, chunk_rows, max_decode_tokens):
+    """The routing fields of an engine step, for every call that is one: (chunk_rows threshold, decode-rows bound, no_decode, no_chunk)"""
+    threshold = _lib.STEP_CHUNK_ROWS if chunk_rows is None else min(chunk_rows, 2 ** 31 - 1)
+    bound, no_decode, no_chunk = (-1 if max_decode_tokens is None else min(max_decode_tokens, total_q)), False, False
+    if c.counts is not None:      # a host table: the decode-routed rows exactly, and which launch would find no sequence
+        G = H // c.Hk
+        decode = [n for n in c.counts if n > 0 and G * n < threshold]
+        bound, no_decode, no_chunk = sum(decode), not decode, len(decode) == sum(1 for n in c.counts if n > 0)
+    return threshold, bound, no_decode, no_chunk
+
+
 def flash_cosine_sim_attention_step_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new=None, v_new=None, cache_seqlens=None,
                                                  block_table=None, max_seqlen_q=None, max_seqlen_k=None, scale=8, groups=1, causal=False,
                                                  l2norm_qk=True, k_scale=None, v_scale=None, return_lse=False, window_size=(-1, -1),
@@ -656,12 +667,7 @@ def flash_cosine_sim_attention_step_with_kvcache(q, k_cache, v_cache, cu_seqlens
     if total_q == 0:      # nothing to append, nothing to write: no launch
         o = q.new_empty(q.shape)
         return (o, q.new_empty((0, H), dtype=torch.float32)) if return_lse else o
-    threshold = _lib.STEP_CHUNK_ROWS if chunk_rows is None else min(chunk_rows, 2 ** 31 - 1)
-    bound, no_decode, no_chunk = (-1 if max_decode_tokens is None else min(max_decode_tokens, total_q)), False, False
-    if c.counts is not None:      # a host table: the decode-routed rows exactly, and which launch would find no sequence
-        G = H // c.Hk
-        decode = [n for n in c.counts if n > 0 and G * n < threshold]
-        bound, no_decode, no_chunk = sum(decode), not decode, len(decode) == sum(1 for n in c.counts if n > 0)
+    threshold, bound, no_decode, no_chunk = _step_routing(c, total_q, H, chunk_rows, max_decode_tokens)
     k_cache, v_cache, cache_seqlens, block_table = c.on_device()
     _torch_ops.load()
     o, lse = torch.ops.fcsa_step.kvcache_step_forward(q, k_cache, v_cache, cu_q, k_new, v_new, cache_seqlens, block_table, c.k_scale, c.v_scale,
@@ -675,6 +681,75 @@ def flash_cosine_sim_attention_step_with_kvcache(q, k_cache, v_cache, cu_seqlens
 # ---------------------------------------------------------------------------------------------
 
 MERGE_MAX_STATES = 8
+
+
+def flash_cosine_sim_attention_alibi_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new=None, v_new=None, cache_seqlens=None,
+                                                  block_table=None, max_seqlen_q=None, max_seqlen_k=None, scale=8, groups=1, causal=False,
+                                                  l2norm_qk=True, k_scale=None, v_scale=None, return_lse=False, window_size=(-1, -1),
+                                                  chunk_rows=None, max_decode_tokens=None, alibi_slopes=None):
+    """A linear position bias (ALiBi) for the cached calls: `flash_cosine_sim_attention_step_with_kvcache` with one more, last keyword.
+    The arguments are that call's, in its order; alibi_slopes=None IS that call, bit for bit, launching exactly what it launches.
+
+    A model trained with a distance bias (`flash_cosine_sim_attention(..., attn_bias=-slope_h * |i - j|)`) is served through this call: a
+    materialised [H, N, M] bias is no answer for a cache that grows every step, the linear form is one multiply-add per logit in registers.
+    One function serves decode, prompt chunks and mixed steps: chunk_rows above G * total_q sends every sequence to the ragged decode kernel
+    with key splits, chunk_rows=0 every sequence to the chunk kernel, the default routes each by its row count.  Equal-N users pass
+    cu_seqlens_q = arange(B + 1) * N and the packed q.
+    alibi_slopes: a float32 tensor [H] (every sequence) or [B, H].  With pos_i = L_b - N_b + i, the position of query i of sequence b (the
+    bottom-right alignment of causal and of the window; L_b as the ragged call defines it), the logit of key j gains
+    -alibi_slopes[b, h] * |pos_i - j|, in natural units after scale (with fp8 caches after k_scale), and is part of lse.  Any sign is
+    allowed; non-causal calls bias the keys to the right by the absolute distance.  A host tensor is checked to be finite and moved to q's
+    device without blocking; a device tensor is trusted and never read on the host, so the call does not synchronise and can be captured in
+    a graph (slopes changed in place are picked up on replay).
+    causal, window_size, paged / strided / float8_e4m3fn caches, return_lse, the append, N_b = 0 and rows without a visible key (o = 0,
+    lse = -inf) combine with the bias exactly as in the step call.
+    Numerics: the slopes are device data the host cannot bound and a negative slope gives a positive bias, so every call with slopes runs
+    the per-row-shift regime (the online row maximum includes the bias) whatever dtype, scale and l2norm_qk say.  Zero slopes therefore
+    equal the step call bit for bit only where that call runs the same regime (e.g. float16 at scale 16), and within rounding elsewhere.
+    Not taken by: the tree call (a tree token's position is its depth, not its slot), the shared-prefix call (its prefix phase mixes
+    sequences with different positions in one B = 1 call) and the training kernels (training keeps attn_bias).  CPU tensors take the
+    forward-only path of `cpu.py` (host slopes).  Forward only."""
+    fn = "flash_cosine_sim_attention_alibi_with_kvcache"
+    if alibi_slopes is None:
+        return flash_cosine_sim_attention_step_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q,
+                                                            max_seqlen_k, scale, groups, causal, l2norm_qk, k_scale, v_scale, return_lse, window_size,
+                                                            chunk_rows, max_decode_tokens)
+    _check_return_lse(return_lse)
+    window = _window(window_size)
+    chunk_rows = _step_count("chunk_rows", chunk_rows)
+    max_decode_tokens = _step_count("max_decode_tokens", max_decode_tokens)
+    if not isinstance(alibi_slopes, torch.Tensor) or alibi_slopes.dtype != torch.float32:
+        raise TypeError(f"alibi_slopes must be a float32 tensor of shape [heads] or [sequences, heads], got "
+                        f"{getattr(alibi_slopes, 'dtype', type(alibi_slopes).__name__)}")
+    if q.dim() == 3 and isinstance(cu_seqlens_q, torch.Tensor) and cu_seqlens_q.dim() == 1:
+        H, B = q.shape[1], cu_seqlens_q.numel() - 1
+        if tuple(alibi_slopes.shape) not in ((H,), (B, H)):
+            raise ValueError(f"alibi_slopes must have shape [{H}] or [{B}, {H}] (heads, or sequences x heads), got {tuple(alibi_slopes.shape)}")
+    if alibi_slopes.device.type == "cpu":
+        if not bool(torch.isfinite(alibi_slopes).all()):
+            raise ValueError("alibi_slopes must be finite")
+    elif alibi_slopes.device != q.device:
+        raise ValueError(f"alibi_slopes is on {alibi_slopes.device} but q is on {q.device}")
+    if q.device.type == "cpu" and alibi_slopes.device.type != "cpu":
+        raise ValueError("CPU tensors take host alibi_slopes")
+    c, cpu_result, cu_q, max_q = _ragged_step(fn, q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q,
+                                              max_seqlen_k, k_scale, v_scale, window,
+                                              dict(scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, return_lse=bool(return_lse),
+                                                   alibi_slopes=alibi_slopes.detach()))
+    if q.device.type == "cpu":
+        return cpu_result
+    total_q, H = q.shape[:2]
+    if total_q == 0:      # nothing to append, nothing to write: no launch
+        o = q.new_empty(q.shape)
+        return (o, q.new_empty((0, H), dtype=torch.float32)) if return_lse else o
+    threshold, bound, no_decode, no_chunk = _step_routing(c, total_q, H, chunk_rows, max_decode_tokens)
+    k_cache, v_cache, cache_seqlens, block_table = c.on_device()
+    slopes = alibi_slopes.detach().to(q.device, non_blocking=True)
+    _torch_ops.load()
+    o, lse = torch.ops.fcsa_alibi.kvcache_alibi_forward(q, k_cache, v_cache, cu_q, slopes, k_new, v_new, cache_seqlens, block_table, c.k_scale,
+                                                        c.v_scale, max_q, c.max_k, float(scale), bool(causal), bool(l2norm_qk), int(groups),
+                                                        window[0], window[1], threshold, bound, no_decode, no_chunk)
+    return (o, lse) if return_lse else o
 
 
 def flash_cosine_sim_attention_tree_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new=None, v_new=None, cache_seqlens=None,

@@ -443,6 +443,41 @@ typedef struct fcsa_tree_mask {
 int    fcsa_forward_kvcache_tree(const fcsa_forward_args* args, const fcsa_kvcache* cache, const fcsa_varlen* seqs,
                                  const fcsa_kvcache_quant* quant, const fcsa_tree_mask* tree, const fcsa_lse_out* lse_out);
 
+/* A linear position bias (ALiBi) for the cached calls: fcsa_forward_kvcache_step with one more argument, the per-head slopes.  Models
+ * trained with a distance bias (the dense call's attn_bias = -slope_h * |i - j|) are served through this entry: a materialised [H, N, M]
+ * bias is no answer for a cache that grows every step, and the linear form costs one multiply-add per logit in registers.
+ * args, cache, seqs, quant, window, step and lse_out are read exactly as fcsa_forward_kvcache_step reads them, and its checks, routing
+ * (chunk_rows, max_decode_tokens, no_decode, no_chunk), append, split plan and workspace -- fcsa_forward_kvcache_step_workspace_bytes() on
+ * the same arguments -- apply (additive: no existing struct changes and FCSA_ABI_VERSION stays 4).
+ *   alibi->slopes   : device float32 (4-byte aligned); the slope of sequence b, query head h is slopes[b * stride_b + h * stride_h]
+ *                     (ELEMENT strides; stride_b = 0: one [H] row for every sequence).  Any sign; the values are device data, never read
+ *                     by the host: the call does not synchronise and can be captured in a graph.
+ * Meaning: with L_b as the ragged call defines it and pos_i = L_b - N_b + i (the position of query i: the bottom-right alignment of
+ * `causal` and of the window), the logit of key j gains  -slope[b, h] * |pos_i - j|  in natural units, after p.scale (and after k_scale
+ * with an fp8 cache).  It is part of lse.  `causal`, the window, paged / strided / fp8 caches, the append, N_b = 0 and rows without a
+ * visible key (o = 0, lse = -inf) are the step call's.  The distance is a float32 integer (exact below 2^24 positions) and its product
+ * with slope * log2(e) is rounded once, inside the fused multiply-add that adds it to the logit.
+ * Regime: the slopes cannot be bounded by the host and a negative slope gives a positive bias, so every call runs the per-row-shift
+ * regime (the online row maximum includes the bias), whatever dtype, scale and l2norm_qk say -- as the dense call does for f16 with a
+ * bias.  A slope of 0 therefore equals fcsa_forward_kvcache_step bit for bit only where that call runs the same regime.
+ * Where the chunk kernel does not exist for the problem (FCSA_F32, or dim_head other than 64 and 128) every sequence takes the decode
+ * kernel with key splits (the ragged call's plan and workspace, as in fcsa_forward_kvcache_step); `step` is checked and otherwise ignored.
+ * alibi or alibi->slopes NULL, slopes not 4-byte aligned, reserved != 0: FCSA_ERR_INVALID_ARG, before any launch.
+ * Not offered: a bias on fcsa_forward_kvcache_tree (a tree token's position is its depth, not its slot) and on the training kernels
+ * (fcsa_forward takes attn_bias).
+ * Launches: "kv_append_ragged[_fp8]" (when appending) and the combine of the step call ("step_combine[_lse][_fp8]", or
+ * "decode_combine[_lse]_ragged[_fp8]" where there is no chunk kernel), unchanged; "alibi_decode[_fp8]" (skipped under no_decode) and
+ * "alibi_prefill[_fp8]" (skipped under no_chunk). */
+typedef struct fcsa_alibi {
+  const float* slopes;                /* device */
+  int64_t      stride_b;              /* elements; 0: [H] slopes shared by every sequence */
+  int64_t      stride_h;              /* elements */
+  int64_t      reserved;              /* 0 */
+} fcsa_alibi;
+int    fcsa_forward_kvcache_alibi(const fcsa_forward_args* args, const fcsa_kvcache* cache, const fcsa_varlen* seqs,
+                                  const fcsa_kvcache_quant* quant, const fcsa_window* window, const fcsa_kvcache_step* step,
+                                  const fcsa_alibi* alibi, const fcsa_lse_out* lse_out);
+
 /* Compaction of the accepted path after a tree step.  The step appended N_b tokens at [cache_seqlens[b], cache_seqlens[b] + N_b); the
  * verifier accepted a root-to-leaf path of them, which must sit at the front of those slots before the next step.  In place:
  *   for i < num_accepted[b]: the row at cache position cache_seqlens[b] + accepted[b, i] moves to cache_seqlens[b] + i, in K and in V, for
