@@ -59,6 +59,10 @@ def _saved_state(q, rows_q, rows_k, D, l2norm_qk, groups, need_backward):
 _LIKE_Q = ("attention", "varlen_attention", "window_attention", "varlen_window_attention", "kvcache_forward", "kvcache_window_forward",
            "kvcache_fp8_forward", "kvcache_varlen_forward")
 _LIKE_QKV = ("varlen_backward", "window_backward", "varlen_window_backward")
+# the cache ops that return (o, lse), by qualified name (the later ones live in namespaces of their own): o shaped like q, their first
+# argument; lse float32 [B, H, N], or [total_q, H] for a ragged step (q [total_q, H, D])
+_O_LSE = ("fcsa::kvcache_lse_forward", "fcsa_prefill::kvcache_prefill_forward", "fcsa_step::kvcache_step_forward",
+          "fcsa_tree::kvcache_tree_forward", "fcsa_alibi::kvcache_alibi_forward")
 
 
 def _register_fakes():
@@ -92,35 +96,10 @@ def _register_fakes():
           window_right):
         return (q.new_empty(q.shape), *_saved_state(q, (q.shape[1], q.shape[0]), (k.shape[1], k.shape[0]), q.shape[2], l2norm_qk, groups, need_backward))
 
-    @torch.library.register_fake("fcsa::kvcache_lse_forward")
-    def _(q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, k_scale, v_scale, max_seqlen_q, max_seqlen_k, scale,
-          causal, l2norm_qk, groups, window_left, window_right):
-        # lse: float32 [B, H, N]; a ragged step (q [total_q, H, D]): [total_q, H]
-        return q.new_empty(q.shape), q.new_empty(q.shape[:-1], dtype=torch.float32)
-
-    # the prefill op lives in a namespace of its own (fcsa_prefill): same results as the ragged lse op
-    @torch.library.register_fake("fcsa_prefill::kvcache_prefill_forward")
-    def _(q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q, max_seqlen_k, scale, causal, l2norm_qk,
-          groups):
-        return q.new_empty(q.shape), q.new_empty(q.shape[:-1], dtype=torch.float32)
-
-    # so does the engine step (fcsa_step)
-    @torch.library.register_fake("fcsa_step::kvcache_step_forward")
-    def _(q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, k_scale, v_scale, max_seqlen_q, max_seqlen_k, scale,
-          causal, l2norm_qk, groups, window_left, window_right, chunk_rows, max_decode_tokens, no_decode, no_chunk):
-        return q.new_empty(q.shape), q.new_empty(q.shape[:-1], dtype=torch.float32)
-
-    # and tree attention for speculative decoding (fcsa_tree): the ragged lse op's results; the compaction returns nothing
-    @torch.library.register_fake("fcsa_tree::kvcache_tree_forward")
-    def _(q, k_cache, v_cache, cu_seqlens_q, tree_mask, k_new, v_new, cache_seqlens, block_table, k_scale, v_scale, max_seqlen_q, max_seqlen_k,
-          scale, l2norm_qk, groups):
-        return q.new_empty(q.shape), q.new_empty(q.shape[:-1], dtype=torch.float32)
-
-    # the engine step with a linear position bias (fcsa_alibi): the step op's results
-    @torch.library.register_fake("fcsa_alibi::kvcache_alibi_forward")
-    def _(q, k_cache, v_cache, cu_seqlens_q, alibi_slopes, k_new, v_new, cache_seqlens, block_table, k_scale, v_scale, max_seqlen_q,
-          max_seqlen_k, scale, causal, l2norm_qk, groups, window_left, window_right, chunk_rows, max_decode_tokens, no_decode, no_chunk):
-        return q.new_empty(q.shape), q.new_empty(q.shape[:-1], dtype=torch.float32)
+    for op in _O_LSE:
+        @torch.library.register_fake(op)
+        def _(q, *args):
+            return q.new_empty(q.shape), q.new_empty(q.shape[:-1], dtype=torch.float32)
 
     @torch.library.register_fake("fcsa_tree::kvcache_compact")
     def _(k_cache, v_cache, cache_seqlens, accepted, num_accepted, block_table):

@@ -495,6 +495,18 @@ size_t decode_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv, con
   return decode_plan(*p, *kv, seqs, decode_window(*p, *kv, seqs != nullptr, w).reach()).total;
 }
 
+// the paged-table fields of a cache (capacity already known to be >= 0), for every call that takes one; who: the message prefix
+int check_cache_table(const char* who, const fcsa_kvcache& kv) {
+  if (kv.block_table == nullptr)
+    return kv.page_size == 0 ? FCSA_OK : fail(FCSA_ERR_INVALID_ARG, "%s: page_size %d without a block_table", who, kv.page_size);
+  if (kv.page_size <= 0 || kv.page_size % 16 != 0) return fail(FCSA_ERR_INVALID_ARG, "%s: page_size %d must be a positive multiple of 16", who, kv.page_size);
+  if (kv.capacity % kv.page_size != 0) return fail(FCSA_ERR_INVALID_ARG, "%s: capacity %d is not a whole number of pages of %d", who, kv.capacity, kv.page_size);
+  if (kv.capacity > 0 && kv.num_blocks < 1) return fail(FCSA_ERR_INVALID_ARG, "%s: paged cache without blocks", who);
+  if (kv.block_table_stride < kv.capacity / kv.page_size)
+    return fail(FCSA_ERR_INVALID_ARG, "%s: block_table row stride %lld below %d entries", who, (long long)kv.block_table_stride, kv.capacity / kv.page_size);
+  return FCSA_OK;
+}
+
 // cache_es: bytes of a cache element (0: the problem's type; 1: an fp8 cache, fcsa_forward_kvcache_quant)
 int check_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv, int cache_es = 0) {
   if (a == nullptr || kv == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache: null argument");
@@ -503,14 +515,7 @@ int check_kvcache(const fcsa_forward_args* a, const fcsa_kvcache* kv, int cache_
   if (a->inv_l != nullptr || a->mask != nullptr || a->attn_bias != nullptr)
     return fail(FCSA_ERR_INVALID_ARG, "kvcache: inv_l, mask and attn_bias must be NULL (forward only, no mask or bias)");
   if (kv->capacity < 0 || kv->new_len < 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache: negative capacity (%d) or new_len (%d)", kv->capacity, kv->new_len);
-  if (kv->block_table != nullptr) {
-    if (kv->page_size <= 0 || kv->page_size % 16 != 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache: page_size %d must be a positive multiple of 16", kv->page_size);
-    if (kv->capacity % kv->page_size != 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache: capacity %d is not a whole number of pages of %d", kv->capacity, kv->page_size);
-    if (kv->capacity > 0 && kv->num_blocks < 1) return fail(FCSA_ERR_INVALID_ARG, "kvcache: paged cache without blocks");
-    if (kv->block_table_stride < kv->capacity / kv->page_size) return fail(FCSA_ERR_INVALID_ARG, "kvcache: block_table row stride %lld below %d entries", (long long)kv->block_table_stride, kv->capacity / kv->page_size);
-  } else if (kv->page_size != 0) {
-    return fail(FCSA_ERR_INVALID_ARG, "kvcache: page_size %d without a block_table", kv->page_size);
-  }
+  if (int rc = check_cache_table("kvcache", *kv)) return rc;
   const int es = elem_size(p.dtype);
   const bool rows = p.batch > 0 && p.heads > 0 && p.q_len > 0;
   const bool cache = p.batch > 0 && kv->capacity > 0;
@@ -908,14 +913,7 @@ int fcsa_kvcache_compact(const fcsa_kvcache* kv, int32_t batch, int32_t kv_heads
     return fail(FCSA_ERR_INVALID_ARG, "kvcache_compact: max_accepted (%d) outside [1, %d]", max_accepted, fcsa::kCompactSlots);
   if (accepted_stride < max_accepted) return fail(FCSA_ERR_INVALID_ARG, "kvcache_compact: accepted row stride %lld below %d entries", (long long)accepted_stride, max_accepted);
   if (kv->capacity < 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_compact: negative capacity (%d)", kv->capacity);
-  if (kv->block_table != nullptr) {
-    if (kv->page_size <= 0 || kv->page_size % 16 != 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_compact: page_size %d must be a positive multiple of 16", kv->page_size);
-    if (kv->capacity % kv->page_size != 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_compact: capacity %d is not a whole number of pages of %d", kv->capacity, kv->page_size);
-    if (kv->capacity > 0 && kv->num_blocks < 1) return fail(FCSA_ERR_INVALID_ARG, "kvcache_compact: paged cache without blocks");
-    if (kv->block_table_stride < kv->capacity / kv->page_size) return fail(FCSA_ERR_INVALID_ARG, "kvcache_compact: block_table row stride %lld below %d entries", (long long)kv->block_table_stride, kv->capacity / kv->page_size);
-  } else if (kv->page_size != 0) {
-    return fail(FCSA_ERR_INVALID_ARG, "kvcache_compact: page_size %d without a block_table", kv->page_size);
-  }
+  if (int rc = check_cache_table("kvcache_compact", *kv)) return rc;
   if (batch == 0 || kv_heads == 0 || kv->capacity == 0) return FCSA_OK;      // no row to move
   if (accepted == nullptr || num_accepted == nullptr || kv->cache_seqlens == nullptr)
     return fail(FCSA_ERR_INVALID_ARG, "kvcache_compact: null accepted, num_accepted or cache_seqlens");

@@ -83,10 +83,11 @@ struct Abi {
 } g_abi;
 
 // an op refuses to run when the loaded library lacks an entry point it needs
-template <class... Fn>
-void need_abi(const char* who, const char* symbols, Fn... members) {
-  TORCH_CHECK(((members != nullptr) && ...), who, ": the loaded libfcsa_hip.so does not export ", symbols);
+void need_abi(const char* who, const char* symbols, bool present) {
+  TORCH_CHECK(present, who, ": the loaded libfcsa_hip.so does not export ", symbols);
 }
+template <class... Fn>
+void need_abi(const char* who, const char* symbols, Fn... members) { need_abi(who, symbols, ((members != nullptr) && ...)); }
 
 using at::Tensor;
 using c10::optional;
@@ -720,42 +721,107 @@ Tensor varlen_window_attention_autograd(const Tensor& q, const Tensor& k, const 
 }
 
 
-// ---- decoding against a key/value cache (fcsa_forward_kvcache) --------------------------------------------------------------------------
+// ---- decoding against a key/value cache (fcsa_forward_kvcache and the entry points built on it) ---------------------------------------
 // q [B, H, N, D]; k_cache / v_cache [B, Hk, capacity, D] or, with a block_table, [num_blocks, Hk, page_size, D] (any strides with the
 // feature dim contiguous: they are written in place, so they are never copied); k_new / v_new [B, Hk, N_new, D]; cache_seqlens int32 [B]
 // and block_table int32 [B, max_blocks] on q's device.  Table contents are never read on the host: the call does not synchronise.
-// cu_q (kvcache_varlen_forward): a ragged step -- q [total_q, H, D] packed by the int32 table cu_q [B + 1], k_new / v_new [total_q, Hk, D],
-// max_seqlen_q an upper bound on the rows of a sequence; o is shaped like q.
-Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const optional<Tensor>& k_new, const optional<Tensor>& v_new,
-                            const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table, int64_t max_seqlen_k, double scale, bool causal,
-                            bool l2norm_qk, int64_t groups, const fcsa_window* win, const Tensor* k_scale = nullptr, const Tensor* v_scale = nullptr,
-                            const Tensor* cu_q = nullptr, int64_t max_seqlen_q = 0, Tensor* lse_out = nullptr, bool prefill = false,
-                            const fcsa_kvcache_step* step = nullptr, const Tensor* tree = nullptr, const Tensor* alibi = nullptr) {
-  const bool ragged = cu_q != nullptr;
-  if (alibi != nullptr)     // kvcache_alibi_forward: an engine step through fcsa_forward_kvcache_alibi (the step's workspace; the lse always)
-    need_abi("alibi_slopes", "fcsa_forward_kvcache_alibi", g_abi.forward_kvcache_alibi);
-  if (tree != nullptr)      // kvcache_tree_forward: a ragged step through fcsa_forward_kvcache_tree (the ragged call's workspace; the lse always)
-    need_abi("tree_mask", "fcsa_forward_kvcache_tree", g_abi.forward_kvcache_tree);
-  if (step != nullptr)      // kvcache_step_forward: a ragged step through fcsa_forward_kvcache_step (its own workspace; the lse always)
-    need_abi("flash_cosine_sim_attention_step_with_kvcache", "fcsa_forward_kvcache_step", g_abi.forward_kvcache_step, g_abi.forward_kvcache_step_ws);
-  if (prefill)      // kvcache_prefill_forward: a ragged step through fcsa_forward_kvcache_prefill (no workspace; the lse always)
-    need_abi("flash_cosine_sim_attention_prefill_with_kvcache", "fcsa_forward_kvcache_prefill", g_abi.forward_kvcache_prefill);
-  const Layout ql = ragged ? kPacked : kDense;      // of q, o, k_new, v_new and the lse
-  if (lse_out != nullptr) need_abi("return_lse", "fcsa_forward_kvcache_lse", g_abi.forward_kvcache_lse);
-  if (ragged)
-    need_abi("flash_cosine_sim_attention_varlen_with_kvcache", "fcsa_forward_kvcache_varlen", g_abi.forward_kvcache_varlen,
-             g_abi.forward_kvcache_varlen_ws);
-  const bool fp8 = k_scale != nullptr;      // an e4m3fn cache with its two scale tensors (kvcache_fp8_forward)
-  need_abi("flash_cosine_sim_attention_with_kvcache", "fcsa_forward_kvcache", g_abi.forward_kvcache, g_abi.forward_kvcache_ws);
-  if (fp8)
-    need_abi("flash_cosine_sim_attention_with_kvcache", "fcsa_forward_kvcache_quant", g_abi.forward_kvcache_quant, g_abi.forward_kvcache_quant_ws);
+// cu_q: a ragged step -- q [total_q, H, D] packed by the int32 table cu_q [B + 1], k_new / v_new [total_q, Hk, D], max_seqlen_q an upper
+// bound on the rows of a sequence; o is shaped like q.
+//
+// One description of a call, CacheCall: every op function fills the members it has and hands it to kvcache_call, which runs the checks
+// (cache_checks), fills the library's structs (fill_lib_call) and dispatches through the one table of entry points (kEntries).
+enum class Route { Plain, Prefill, Step, Tree, Alibi };
+
+struct CacheCall {
+  // what every op has
+  const Tensor &q, &k_cache, &v_cache;
+  const optional<Tensor> &k_new, &v_new, &cache_seqlens, &block_table;
+  int64_t max_seqlen_k; double scale; bool causal, l2norm_qk; int64_t groups;
+  // what some have
+  const fcsa_window* win = nullptr;                       // a sliding window
+  const Tensor *k_scale = nullptr, *v_scale = nullptr;    // an e4m3fn cache (its codes as uint8 tensors) with its two scale tensors
+  const Tensor* cu_q = nullptr; int64_t max_seqlen_q = 0; // a ragged step: packed q [total_q, H, D], with the bound on a sequence's rows
+  bool lse = false;                                       // the rows' log-sum-exp as a second result
+  Route route = Route::Plain;
+  fcsa_kvcache_step step{};                               // Step, Alibi: the routing fields
+  const Tensor* extra = nullptr;                          // Tree: tree_mask; Alibi: alibi_slopes
+  bool ragged() const { return cu_q != nullptr; }
+  bool fp8() const { return k_scale != nullptr; }
+};
+
+const Tensor* ptr(const optional<Tensor>& t) { return t.has_value() ? &*t : nullptr; }
+
+// window sides as the cache ops take them: (-1, -1) is the un-windowed call (ptr() null), anything else passes Win's checks
+struct OptWin {
+  fcsa_window w{};
+  const bool on;
+  OptWin(int64_t left, int64_t right) : on(!(left == -1 && right == -1)) { if (on) w = Win(left, right).w; }
+  const fcsa_window* ptr() const { return on ? &w : nullptr; }
+};
+
+void set_scales(CacheCall& c, const optional<Tensor>& k_scale, const optional<Tensor>& v_scale) {
+  TORCH_CHECK_VALUE(k_scale.has_value() == v_scale.has_value(), "k_scale and v_scale must be given together");
+  c.k_scale = ptr(k_scale); c.v_scale = ptr(v_scale);
+}
+
+// the routing fields of an engine step (chunk_rows / max_decode_tokens < 0: the library's default / total_q; no_decode, no_chunk: the
+// caller's promises, which skip a launch)
+fcsa_kvcache_step step_fields(int64_t chunk_rows, int64_t max_decode_tokens, bool no_decode, bool no_chunk) {
+  TORCH_CHECK_VALUE(chunk_rows >= -1, "chunk_rows must be a non-negative integer (or -1: the default), got ", chunk_rows);
+  TORCH_CHECK_VALUE(max_decode_tokens >= -1, "max_decode_tokens must be a non-negative integer (or -1: total_q), got ", max_decode_tokens);
+  fcsa_kvcache_step st{};
+  st.chunk_rows = (int32_t)std::min<int64_t>(chunk_rows, INT32_MAX);
+  st.max_decode_tokens = std::min<int64_t>(max_decode_tokens, INT32_MAX);
+  st.no_decode = no_decode; st.no_chunk = no_chunk;
+  return st;
+}
+
+// The geometry of a cache that serves B sequences, contiguous or paged by block_table: the table's checks, the capacity, and the table
+// fields of fcsa_kvcache.  The forward calls say "batch" and count q's sequences, kvcache_compact says "sequences" and counts accepted's.
+struct Geometry {
+  Tensor tab;      // block_table, contiguous; undefined for a contiguous cache
+  int64_t capacity = 0, page = 0, num_blocks = 0;
+  void fill(fcsa_kvcache& kv) const {
+    kv.capacity = (int32_t)capacity; kv.page_size = (int32_t)page; kv.num_blocks = (int32_t)num_blocks;
+    kv.block_table = tab.defined() ? tab.data_ptr<int32_t>() : nullptr;
+    kv.block_table_stride = tab.defined() ? tab.size(1) : 0;
+  }
+};
+template <class SameDev>
+Geometry cache_geometry(const Tensor& k_cache, const optional<Tensor>& block_table, int64_t B, const SameDev& same_dev, const char* rows,
+                        const char* counted) {
+  Geometry g;
+  g.capacity = k_cache.size(2);
+  if (block_table.has_value()) {
+    same_dev("block_table", *block_table);
+    TORCH_CHECK_TYPE(block_table->scalar_type() == at::kInt, "block_table must be int32");
+    TORCH_CHECK_VALUE(block_table->dim() == 2 && block_table->size(0) == B, "block_table must be [", rows, ", max_blocks]");
+    g.page = k_cache.size(2); g.num_blocks = k_cache.size(0); g.capacity = block_table->size(1) * g.page;
+    g.tab = block_table->contiguous();
+  } else {
+    TORCH_CHECK_VALUE(k_cache.size(0) == B, "batch mismatch between ", counted, " (", B, ") and the caches (", k_cache.size(0), ")");
+  }
+  return g;
+}
+
+// What the checks of a call return: the canonical tensors, kept alive until the call has been issued, and the sizes read off them.
+struct CacheKeep {
+  Tensor q, cu, words, slopes, kn, vn, sl;
+  Geometry g;
+  int64_t B = 0, H = 0, N = 0, D = 0, Hk = 0, new_len = 0;      // ragged: N is the number of packed rows
+};
+
+CacheKeep cache_checks(const CacheCall& c) {
+  const Tensor &q = c.q, &k_cache = c.k_cache, &v_cache = c.v_cache;
+  const bool ragged = c.ragged();
+  CacheKeep k;
   TORCH_CHECK(q.is_cuda(), "flash_cosine_sim_attention_with_kvcache: q and the caches must be GPU tensors (HIP kernels only)");
   auto same_dev = [&](const char* name, const Tensor& t) {
     TORCH_CHECK_VALUE(t.device() == q.device(), name, " is on ", t.device(), " but q is on ", q.device(), ": all tensors must live on q's GPU");
   };
   same_dev("k_cache", k_cache);
   same_dev("v_cache", v_cache);
-  if (fp8) {
+  if (c.fp8()) {
     // the codes travel as bytes (the Python entry point passes float8_e4m3fn caches as their uint8 views: the dispatcher's own machinery
     // -- opcheck, functionalisation -- runs arithmetic on mutated arguments, which float8 tensors do not support)
     TORCH_CHECK_TYPE(k_cache.scalar_type() == at::kByte && v_cache.scalar_type() == at::kByte,
@@ -771,61 +837,47 @@ Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor
                     ragged ? "q must be a packed [total_q, heads, dim_head] tensor and k_cache, v_cache must have 4 dimensions"
                            : "q, k_cache, v_cache must have 4 dimensions");
   TORCH_CHECK_VALUE(k_cache.sizes() == v_cache.sizes(), "k_cache and v_cache must have the same shape");
-  Tensor cu;
   if (ragged) {
-    same_dev("cu_seqlens_q", *cu_q);
-    TORCH_CHECK_TYPE(cu_q->scalar_type() == at::kInt, "cu_seqlens_q must be int32");
-    TORCH_CHECK_VALUE(cu_q->dim() == 1 && cu_q->numel() >= 1, "cu_seqlens_q must be 1-D with sequences + 1 entries, got ", cu_q->sizes());
-    TORCH_CHECK_VALUE(max_seqlen_q >= 0 && max_seqlen_q <= INT32_MAX, "max_seqlen_q must lie in [0, 2^31), got ", max_seqlen_q);
+    const Tensor& cu_q = *c.cu_q;
+    same_dev("cu_seqlens_q", cu_q);
+    TORCH_CHECK_TYPE(cu_q.scalar_type() == at::kInt, "cu_seqlens_q must be int32");
+    TORCH_CHECK_VALUE(cu_q.dim() == 1 && cu_q.numel() >= 1, "cu_seqlens_q must be 1-D with sequences + 1 entries, got ", cu_q.sizes());
+    TORCH_CHECK_VALUE(c.max_seqlen_q >= 0 && c.max_seqlen_q <= INT32_MAX, "max_seqlen_q must lie in [0, 2^31), got ", c.max_seqlen_q);
     TORCH_CHECK_VALUE(q.size(0) * std::max<int64_t>(q.size(1), 1) <= INT32_MAX, "heads x packed rows must stay below 2^31");
-    cu = cu_q->contiguous();
+    k.cu = cu_q.contiguous();
   }
-  Tensor words;
-  if (tree != nullptr) {
-    TORCH_CHECK_TYPE(tree->scalar_type() == at::kLong, "tree_mask must be int64, got ", tree->scalar_type());
-    same_dev("tree_mask", *tree);
-    TORCH_CHECK_VALUE(ragged && tree->dim() == 1 && tree->size(0) == q.size(0), "tree_mask must be [total_q] (", q.size(0), "), packed like q, got ",
-                      tree->sizes());
-    words = tree->contiguous();
+  if (c.route == Route::Tree) {
+    const Tensor& tree = *c.extra;
+    TORCH_CHECK_TYPE(tree.scalar_type() == at::kLong, "tree_mask must be int64, got ", tree.scalar_type());
+    same_dev("tree_mask", tree);
+    TORCH_CHECK_VALUE(tree.dim() == 1 && tree.size(0) == q.size(0), "tree_mask must be [total_q] (", q.size(0), "), packed like q, got ", tree.sizes());
+    k.words = tree.contiguous();
   }
-  // ragged: N is the number of packed rows
-  Tensor slopes;
-  if (alibi != nullptr) {
-    TORCH_CHECK_TYPE(alibi->scalar_type() == at::kFloat, "alibi_slopes must be float32, got ", alibi->scalar_type());
-    same_dev("alibi_slopes", *alibi);
-    TORCH_CHECK_VALUE(ragged && step != nullptr && lse_out != nullptr, "alibi_slopes come with the engine step");
-    const int64_t seqs_n = cu.numel() - 1;
-    TORCH_CHECK_VALUE((alibi->dim() == 1 && alibi->size(0) == q.size(1)) || (alibi->dim() == 2 && alibi->size(0) == seqs_n && alibi->size(1) == q.size(1)),
-                      "alibi_slopes must be [heads] (", q.size(1), ") or [sequences, heads] (", seqs_n, ", ", q.size(1), "), got ", alibi->sizes());
-    slopes = *alibi;      // any strides: the kernels take element strides, and a view keeps in-place updates visible to a captured graph
+  if (c.route == Route::Alibi) {
+    const Tensor& alibi = *c.extra;
+    TORCH_CHECK_TYPE(alibi.scalar_type() == at::kFloat, "alibi_slopes must be float32, got ", alibi.scalar_type());
+    same_dev("alibi_slopes", alibi);
+    const int64_t seqs_n = k.cu.numel() - 1;
+    TORCH_CHECK_VALUE((alibi.dim() == 1 && alibi.size(0) == q.size(1)) || (alibi.dim() == 2 && alibi.size(0) == seqs_n && alibi.size(1) == q.size(1)),
+                      "alibi_slopes must be [heads] (", q.size(1), ") or [sequences, heads] (", seqs_n, ", ", q.size(1), "), got ", alibi.sizes());
+    k.slopes = alibi;      // any strides: the kernels take element strides, and a view keeps in-place updates visible to a captured graph
   }
-  const int64_t B = ragged ? cu.numel() - 1 : q.size(0), H = q.size(1), N = ragged ? q.size(0) : q.size(2), D = q.size(-1), Hk = k_cache.size(1);
+  const int64_t B = k.B = ragged ? k.cu.numel() - 1 : q.size(0), H = k.H = q.size(1), N = k.N = ragged ? q.size(0) : q.size(2);
+  const int64_t D = k.D = q.size(-1), Hk = k.Hk = k_cache.size(1);
   TORCH_CHECK_VALUE(k_cache.size(3) == D, "query, key, value dimensions must be the same");
   TORCH_CHECK_VALUE(D == 16 || D == 32 || D == 64 || D == 96 || D == 128, "only dimensions (16, 32, 64, 96, 128) allowed for now, got ", D);
   TORCH_CHECK_VALUE(Hk >= 1 && H % Hk == 0, "k/v heads must divide q heads (", H, "), got ", Hk);
-  TORCH_CHECK_VALUE(!l2norm_qk || (groups >= 1 && D % groups == 0), "groups (", groups, ") must divide the head dimension (", D, ")");
+  TORCH_CHECK_VALUE(!c.l2norm_qk || (c.groups >= 1 && D % c.groups == 0), "groups (", c.groups, ") must divide the head dimension (", D, ")");
   TORCH_CHECK_VALUE(rows_ok(k_cache) && rows_ok(v_cache), "k_cache / v_cache: the feature dim must be contiguous and rows 16-byte aligned "
                     "(the caches are updated in place, so they are not copied)");
-  const bool paged = block_table.has_value();
-  int64_t capacity = k_cache.size(2), page = 0, num_blocks = 0;
-  fcsa_kvcache kv;
-  if (paged) {
-    same_dev("block_table", *block_table);
-    TORCH_CHECK_TYPE(block_table->scalar_type() == at::kInt, "block_table must be int32");
-    TORCH_CHECK_VALUE(block_table->dim() == 2 && block_table->size(0) == B, "block_table must be [batch, max_blocks]");
-    page = k_cache.size(2);
-    num_blocks = k_cache.size(0);
-    capacity = block_table->size(1) * page;
-    TORCH_CHECK_VALUE(page > 0 && page % 16 == 0, "page_size (", page, ") must be a positive multiple of 16");
-    TORCH_CHECK_VALUE(num_blocks >= 1, "a paged cache needs at least one block");
-  } else {
-    TORCH_CHECK_VALUE(k_cache.size(0) == B, "batch mismatch between q (", B, ") and the caches (", k_cache.size(0), ")");
+  k.g = cache_geometry(k_cache, c.block_table, B, same_dev, "batch", "q");
+  if (k.g.tab.defined()) {      // the page rule (kvcache_compact leaves it to the library)
+    TORCH_CHECK_VALUE(k.g.page > 0 && k.g.page % 16 == 0, "page_size (", k.g.page, ") must be a positive multiple of 16");
+    TORCH_CHECK_VALUE(k.g.num_blocks >= 1, "a paged cache needs at least one block");
   }
-  TORCH_CHECK_VALUE(capacity <= INT32_MAX, "cache capacity must stay below 2^31");
-  Tensor tab = paged ? block_table->contiguous() : Tensor();
-  Tensor kn, vn;
+  TORCH_CHECK_VALUE(k.g.capacity <= INT32_MAX, "cache capacity must stay below 2^31");
+  const optional<Tensor>&k_new = c.k_new, &v_new = c.v_new;
   TORCH_CHECK_VALUE(k_new.has_value() == v_new.has_value(), "k_new and v_new must be given together");
-  int64_t new_len = 0;
   if (k_new.has_value()) {
     same_dev("k_new", *k_new);
     same_dev("v_new", *v_new);
@@ -837,138 +889,180 @@ Tensor kvcache_forward_impl(const Tensor& q, const Tensor& k_cache, const Tensor
       TORCH_CHECK_VALUE(k_new->dim() == 4 && k_new->sizes() == v_new->sizes() && k_new->size(0) == B && k_new->size(1) == Hk && k_new->size(3) == D,
                         "k_new / v_new must be [batch, kv_heads, N_new, dim_head], got ", k_new->sizes(), " and ", v_new->sizes());
     }
-    new_len = ragged ? 1 : k_new->size(2);
-    kn = prep(*k_new);
-    vn = prep(*v_new);
+    k.new_len = ragged ? 1 : k_new->size(2);
+    k.kn = prep(*k_new);
+    k.vn = prep(*v_new);
   }
-  Tensor sl;
-  if (cache_seqlens.has_value()) {
-    same_dev("cache_seqlens", *cache_seqlens);
-    TORCH_CHECK_TYPE(cache_seqlens->scalar_type() == at::kInt, "cache_seqlens must be int32");
-    TORCH_CHECK_VALUE(cache_seqlens->dim() == 1 && cache_seqlens->size(0) == B, "cache_seqlens must be [batch]");
-    sl = cache_seqlens->contiguous();
+  if (c.cache_seqlens.has_value()) {
+    const Tensor& cache_seqlens = *c.cache_seqlens;
+    same_dev("cache_seqlens", cache_seqlens);
+    TORCH_CHECK_TYPE(cache_seqlens.scalar_type() == at::kInt, "cache_seqlens must be int32");
+    TORCH_CHECK_VALUE(cache_seqlens.dim() == 1 && cache_seqlens.size(0) == B, "cache_seqlens must be [batch]");
+    k.sl = cache_seqlens.contiguous();
   }
-  TORCH_CHECK_VALUE(max_seqlen_k >= 0, "max_seqlen_k must be non-negative");
-  c10::DeviceGuard guard(q.device());
-  const Tensor q4 = prep(q);
-  Tensor o = ragged ? at::empty({N, H, D}, q.options()) : at::empty({B, H, N, D}, q.options());
-  fcsa_forward_args a;
-  std::memset(&a, 0, sizeof(a));
-  a.p.dtype = dtype_code(q.scalar_type());
-  a.p.batch = (int32_t)B; a.p.heads = (int32_t)H; a.p.kv_heads = (int32_t)Hk;
-  a.p.q_len = (int32_t)(ragged ? max_seqlen_q : N); a.p.k_len = (int32_t)std::min<int64_t>(max_seqlen_k, capacity); a.p.dim_head = (int32_t)D;
-  a.p.causal = causal; a.p.bias_batch_dim = 0; a.p.l2norm_qk = l2norm_qk;
-  a.p.groups = l2norm_qk ? (int32_t)groups : 1;
-  a.p.scale = (float)scale;
-  a.q = strided(q4, ql);
-  a.o = strided(o, ql);
-  kv.k_cache = strided(k_cache);
-  kv.v_cache = strided(v_cache);
-  kv.capacity = (int32_t)capacity;
-  kv.page_size = (int32_t)page;
-  kv.num_blocks = (int32_t)num_blocks;
-  kv.new_len = (int32_t)new_len;
-  kv.cache_seqlens = sl.defined() ? sl.data_ptr<int32_t>() : nullptr;
-  kv.block_table = paged ? tab.data_ptr<int32_t>() : nullptr;
-  kv.block_table_stride = paged ? tab.size(1) : 0;
-  fcsa_tensor none;
-  std::memset(&none, 0, sizeof(none));
-  kv.k_new = kn.defined() && new_len > 0 ? strided(kn, ql) : none;
-  kv.v_new = vn.defined() && new_len > 0 ? strided(vn, ql) : none;
-  fcsa_varlen seqs;
-  std::memset(&seqs, 0, sizeof(seqs));
-  if (ragged) {
-    seqs.cu_seqlens_q = cu.data_ptr<int32_t>();
-    seqs.total_q = N;
-  }
-  fcsa_kvcache_quant qz;
-  std::memset(&qz, 0, sizeof(qz));
-  Tensor ks, vs;
-  if (fp8) {
-    // float32 [], [Hk] or [B, Hk] on q's device: element strides of (batch, K/V head), 0 where the scale broadcasts
-    auto scale_of = [&](const char* name, const Tensor& t, int64_t& s0, int64_t& s1) {
-      same_dev(name, t);
-      TORCH_CHECK_TYPE(t.scalar_type() == at::kFloat, name, " must be float32");
-      const bool ok = t.dim() == 0 || (t.dim() == 1 && t.size(0) == Hk) || (t.dim() == 2 && t.size(0) == B && t.size(1) == Hk);
-      TORCH_CHECK_VALUE(ok, name, " must have shape [], [", Hk, "] or [", B, ", ", Hk, "], got ", t.sizes());
-      s0 = t.dim() == 2 ? t.stride(0) : 0;
-      s1 = t.dim() == 2 ? t.stride(1) : t.dim() == 1 ? t.stride(0) : 0;
-      return t;
-    };
-    ks = scale_of("k_scale", *k_scale, qz.k_scale_stride0, qz.k_scale_stride1);
-    vs = scale_of("v_scale", *v_scale, qz.v_scale_stride0, qz.v_scale_stride1);
-    qz.cache_dtype = FCSA_CACHE_E4M3;
-    qz.k_scale = ks.data_ptr<float>();
-    qz.v_scale = vs.data_ptr<float>();
-  }
-  const size_t wsb = prefill ? 0
-                     : step != nullptr ? g_abi.forward_kvcache_step_ws(&a.p, &kv, &seqs, fp8 ? &qz : nullptr, win, step)
-                     : ragged ? g_abi.forward_kvcache_varlen_ws(&a.p, &kv, &seqs, fp8 ? &qz : nullptr, win)
-                     : fp8 ? g_abi.forward_kvcache_quant_ws(&a.p, &kv, &qz, win)
-                         : win != nullptr ? g_abi.forward_kvcache_window_ws(&a.p, &kv, win) : g_abi.forward_kvcache_ws(&a.p, &kv);
-  Tensor ws;
-  if (wsb > 0) {
-    ws = at::empty({(int64_t)wsb}, q.options().dtype(at::kByte));      // the caching allocator
-    a.workspace = ws.data_ptr();
-    a.workspace_bytes = wsb;
-  }
-  a.stream = stream_of(q);
-  if (lse_out != nullptr) {
-    // float32 [B, H, N], or [total_q, H] for a ragged step; the workspace is that of the call without it
-    *lse_out = ragged ? at::empty({N, H}, q.options().dtype(at::kFloat)) : at::empty({B, H, N}, q.options().dtype(at::kFloat));
-    const fcsa_lse_out lo = strided<fcsa_lse_out>(*lse_out, ql);
-    if (prefill) {
-      check(g_abi.forward_kvcache_prefill(&a, &kv, &seqs, &lo), "fcsa_forward_kvcache_prefill");
-      return o;
+  TORCH_CHECK_VALUE(c.max_seqlen_k >= 0, "max_seqlen_k must be non-negative");
+  if (c.fp8()) {
+    // float32 [], [Hk] or [B, Hk] on q's device
+    for (const auto& [name, t] : {std::pair<const char*, const Tensor*>{"k_scale", c.k_scale}, {"v_scale", c.v_scale}}) {
+      same_dev(name, *t);
+      TORCH_CHECK_TYPE(t->scalar_type() == at::kFloat, name, " must be float32");
+      const bool ok = t->dim() == 0 || (t->dim() == 1 && t->size(0) == Hk) || (t->dim() == 2 && t->size(0) == B && t->size(1) == Hk);
+      TORCH_CHECK_VALUE(ok, name, " must have shape [], [", Hk, "] or [", B, ", ", Hk, "], got ", t->sizes());
     }
-    if (alibi != nullptr) {
-      fcsa_alibi al;
-      std::memset(&al, 0, sizeof(al));
-      al.slopes = slopes.data_ptr<float>();
-      al.stride_b = slopes.dim() == 2 ? slopes.stride(0) : 0;
-      al.stride_h = slopes.stride(-1);
-      check(g_abi.forward_kvcache_alibi(&a, &kv, &seqs, fp8 ? &qz : nullptr, win, step, &al, &lo), "fcsa_forward_kvcache_alibi");
-      return o;
-    }
-    if (step != nullptr) {
-      check(g_abi.forward_kvcache_step(&a, &kv, &seqs, fp8 ? &qz : nullptr, win, step, &lo), "fcsa_forward_kvcache_step");
-      return o;
-    }
-    if (tree != nullptr) {
-      fcsa_tree_mask tm;
-      std::memset(&tm, 0, sizeof(tm));
-      tm.mask = reinterpret_cast<const uint64_t*>(words.data_ptr<int64_t>());
-      check(g_abi.forward_kvcache_tree(&a, &kv, &seqs, fp8 ? &qz : nullptr, &tm, &lo), "fcsa_forward_kvcache_tree");
-      return o;
-    }
-    check(g_abi.forward_kvcache_lse(&a, &kv, ragged ? &seqs : nullptr, fp8 ? &qz : nullptr, win, &lo), "fcsa_forward_kvcache_lse");
-    return o;
   }
-  if (ragged) check(g_abi.forward_kvcache_varlen(&a, &kv, &seqs, fp8 ? &qz : nullptr, win), "fcsa_forward_kvcache_varlen");
-  else if (fp8) check(g_abi.forward_kvcache_quant(&a, &kv, &qz, win), "fcsa_forward_kvcache_quant");
-  else if (win != nullptr) check(g_abi.forward_kvcache_window(&a, &kv, win), "fcsa_forward_kvcache_window");
-  else check(g_abi.forward_kvcache(&a, &kv), "fcsa_forward_kvcache");
-  return o;
+  k.q = prep(q);
+  return k;
 }
+
+// What one call hands to the library: the structs of include/fcsa.h, filled from the call and its canonical tensors.
+struct LibCall {
+  fcsa_forward_args a; fcsa_kvcache kv; fcsa_varlen seqs; fcsa_lse_out lo;
+  fcsa_kvcache_quant qz; fcsa_tree_mask tree; fcsa_alibi alibi;
+  const fcsa_window* win; const fcsa_kvcache_step* step;
+  bool ragged, fp8;
+  const fcsa_kvcache_quant* quant() const { return fp8 ? &qz : nullptr; }
+};
+
+// everything but the workspace and the lse, which kvcache_call allocates once the entry point has sized the former
+void fill_lib_call(LibCall& l, const CacheCall& c, const CacheKeep& k, const Tensor& o) {
+  const Layout ql = c.ragged() ? kPacked : kDense;      // of q, o, k_new, v_new and the lse
+  std::memset(&l, 0, sizeof(l));
+  l.ragged = c.ragged(); l.fp8 = c.fp8(); l.win = c.win;
+  l.step = c.route == Route::Step || c.route == Route::Alibi ? &c.step : nullptr;
+  fcsa_problem& p = l.a.p;
+  p.dtype = dtype_code(c.q.scalar_type());
+  p.batch = (int32_t)k.B; p.heads = (int32_t)k.H; p.kv_heads = (int32_t)k.Hk;
+  p.q_len = (int32_t)(l.ragged ? c.max_seqlen_q : k.N); p.k_len = (int32_t)std::min<int64_t>(c.max_seqlen_k, k.g.capacity); p.dim_head = (int32_t)k.D;
+  p.causal = c.causal; p.bias_batch_dim = 0; p.l2norm_qk = c.l2norm_qk;
+  p.groups = c.l2norm_qk ? (int32_t)c.groups : 1;
+  p.scale = (float)c.scale;
+  l.a.q = strided(k.q, ql); l.a.o = strided(o, ql); l.a.stream = stream_of(c.q);
+  l.kv.k_cache = strided(c.k_cache); l.kv.v_cache = strided(c.v_cache);
+  k.g.fill(l.kv);
+  l.kv.new_len = (int32_t)k.new_len;
+  l.kv.cache_seqlens = k.sl.defined() ? k.sl.data_ptr<int32_t>() : nullptr;
+  if (k.kn.defined() && k.new_len > 0) { l.kv.k_new = strided(k.kn, ql); l.kv.v_new = strided(k.vn, ql); }
+  if (l.ragged) { l.seqs.cu_seqlens_q = k.cu.data_ptr<int32_t>(); l.seqs.total_q = k.N; }
+  if (l.fp8) {      // float32 [], [Hk] or [B, Hk]: element strides of (batch, K/V head), 0 where the scale broadcasts
+    const Tensor &ks = *c.k_scale, &vs = *c.v_scale;
+    l.qz = {FCSA_CACHE_E4M3, ks.data_ptr<float>(), vs.data_ptr<float>(), ks.dim() == 2 ? ks.stride(0) : 0, ks.dim() >= 1 ? ks.stride(-1) : 0,
+            vs.dim() == 2 ? vs.stride(0) : 0, vs.dim() >= 1 ? vs.stride(-1) : 0};
+  }
+  if (k.words.defined()) l.tree.mask = reinterpret_cast<const uint64_t*>(k.words.data_ptr<int64_t>());
+  if (k.slopes.defined()) {
+    l.alibi.slopes = k.slopes.data_ptr<float>();
+    l.alibi.stride_b = k.slopes.dim() == 2 ? k.slopes.stride(0) : 0;
+    l.alibi.stride_h = k.slopes.stride(-1);
+  }
+}
+
+// The entry points of the family, one row each: the symbol (as errors name it), who asks for it when the loaded library lacks it, whether
+// the library has it, the workspace it needs and the call itself.  The one place that knows which C function serves which call.
+struct EntryPoint {
+  const char *symbol, *who;
+  bool (*present)();
+  size_t (*workspace)(const LibCall&);      // null: that of the call without the lse
+  int (*run)(const LibCall&);
+};
+enum Entry { kKvcache, kWindow, kQuant, kVarlen, kLse, kPrefill, kStep, kTree, kAlibi };
+const EntryPoint kEntries[] = {
+    /* kKvcache */ {"fcsa_forward_kvcache", "flash_cosine_sim_attention_with_kvcache",
+                    [] { return g_abi.forward_kvcache != nullptr && g_abi.forward_kvcache_ws != nullptr; },
+                    [](const LibCall& l) { return g_abi.forward_kvcache_ws(&l.a.p, &l.kv); },
+                    [](const LibCall& l) { return g_abi.forward_kvcache(&l.a, &l.kv); }},
+    /* kWindow */ {"fcsa_forward_kvcache_window", "sliding window",
+                   [] { return g_abi.forward_kvcache_window != nullptr && g_abi.forward_kvcache_window_ws != nullptr; },
+                   [](const LibCall& l) { return g_abi.forward_kvcache_window_ws(&l.a.p, &l.kv, l.win); },
+                   [](const LibCall& l) { return g_abi.forward_kvcache_window(&l.a, &l.kv, l.win); }},
+    /* kQuant */ {"fcsa_forward_kvcache_quant", "flash_cosine_sim_attention_with_kvcache",
+                  [] { return g_abi.forward_kvcache_quant != nullptr && g_abi.forward_kvcache_quant_ws != nullptr; },
+                  [](const LibCall& l) { return g_abi.forward_kvcache_quant_ws(&l.a.p, &l.kv, &l.qz, l.win); },
+                  [](const LibCall& l) { return g_abi.forward_kvcache_quant(&l.a, &l.kv, &l.qz, l.win); }},
+    /* kVarlen */ {"fcsa_forward_kvcache_varlen", "flash_cosine_sim_attention_varlen_with_kvcache",
+                   [] { return g_abi.forward_kvcache_varlen != nullptr && g_abi.forward_kvcache_varlen_ws != nullptr; },
+                   [](const LibCall& l) { return g_abi.forward_kvcache_varlen_ws(&l.a.p, &l.kv, &l.seqs, l.quant(), l.win); },
+                   [](const LibCall& l) { return g_abi.forward_kvcache_varlen(&l.a, &l.kv, &l.seqs, l.quant(), l.win); }},
+    /* kLse: every Plain call with the lse */ {"fcsa_forward_kvcache_lse", "return_lse", [] { return g_abi.forward_kvcache_lse != nullptr; }, nullptr,
+     [](const LibCall& l) { return g_abi.forward_kvcache_lse(&l.a, &l.kv, l.ragged ? &l.seqs : nullptr, l.quant(), l.win, &l.lo); }},
+    /* kPrefill: no workspace */ {"fcsa_forward_kvcache_prefill", "flash_cosine_sim_attention_prefill_with_kvcache",
+     [] { return g_abi.forward_kvcache_prefill != nullptr; },
+     [](const LibCall&) { return (size_t)0; }, [](const LibCall& l) { return g_abi.forward_kvcache_prefill(&l.a, &l.kv, &l.seqs, &l.lo); }},
+    /* kStep */ {"fcsa_forward_kvcache_step", "flash_cosine_sim_attention_step_with_kvcache",
+                 [] { return g_abi.forward_kvcache_step != nullptr && g_abi.forward_kvcache_step_ws != nullptr; },
+                 [](const LibCall& l) { return g_abi.forward_kvcache_step_ws(&l.a.p, &l.kv, &l.seqs, l.quant(), l.win, l.step); },
+                 [](const LibCall& l) { return g_abi.forward_kvcache_step(&l.a, &l.kv, &l.seqs, l.quant(), l.win, l.step, &l.lo); }},
+    /* kTree: the ragged call's workspace */ {"fcsa_forward_kvcache_tree", "tree_mask", [] { return g_abi.forward_kvcache_tree != nullptr; },
+     [](const LibCall& l) { return g_abi.forward_kvcache_varlen_ws(&l.a.p, &l.kv, &l.seqs, l.quant(), l.win); },
+     [](const LibCall& l) { return g_abi.forward_kvcache_tree(&l.a, &l.kv, &l.seqs, l.quant(), &l.tree, &l.lo); }},
+    /* kAlibi: the step's workspace */ {"fcsa_forward_kvcache_alibi", "alibi_slopes", [] { return g_abi.forward_kvcache_alibi != nullptr; },
+     [](const LibCall& l) { return g_abi.forward_kvcache_step_ws(&l.a.p, &l.kv, &l.seqs, l.quant(), l.win, l.step); },
+     [](const LibCall& l) { return g_abi.forward_kvcache_alibi(&l.a, &l.kv, &l.seqs, l.quant(), l.win, l.step, &l.alibi, &l.lo); }},
+};
+
+// the entry point of a Plain call without the lse: by the ragged / fp8 / window facts
+Entry plain_entry(const CacheCall& c) { return c.ragged() ? kVarlen : c.fp8() ? kQuant : c.win != nullptr ? kWindow : kKvcache; }
+constexpr Entry kOfRoute[] = {kKvcache /* Plain: by the facts instead */, kPrefill, kStep, kTree, kAlibi};      // in Route's order
+static_assert(sizeof(kEntries) / sizeof(kEntries[0]) == kAlibi + 1 && sizeof(kOfRoute) / sizeof(kOfRoute[0]) == (int)Route::Alibi + 1,
+              "kEntries has one row per Entry, in its order, and kOfRoute one entry per Route");
+Entry entry_of(const CacheCall& c) { return c.route != Route::Plain ? kOfRoute[(int)c.route] : c.lse ? kLse : plain_entry(c); }
+// a call needs its own entry point and those of the calls it is built on
+void need_entries(const CacheCall& c, Entry own) {
+  auto need = [](Entry e) { need_abi(kEntries[e].who, kEntries[e].symbol, kEntries[e].present()); };
+  if (c.route != Route::Plain) need(own);
+  if (c.lse) need(kLse);
+  if (c.ragged()) need(kVarlen);
+  need(kKvcache);
+  if (c.fp8()) need(kQuant);
+  need(own);
+}
+
+// (o, lse): lse float32 [B, H, N], or [total_q, H] for a ragged step; undefined unless the call asks for it
+std::tuple<Tensor, Tensor> kvcache_call(const CacheCall& c) {
+  const Entry own = entry_of(c);
+  need_entries(c, own);
+  const CacheKeep k = cache_checks(c);
+  c10::DeviceGuard guard(c.q.device());
+  const auto opts = c.q.options();
+  Tensor o = c.ragged() ? at::empty({k.N, k.H, k.D}, opts) : at::empty({k.B, k.H, k.N, k.D}, opts);
+  LibCall l;
+  fill_lib_call(l, c, k, o);
+  const EntryPoint& e = kEntries[own];
+  const size_t wsb = (e.workspace != nullptr ? e : kEntries[plain_entry(c)]).workspace(l);
+  Tensor ws, lse;
+  if (wsb > 0) {
+    ws = at::empty({(int64_t)wsb}, opts.dtype(at::kByte));      // the caching allocator
+    l.a.workspace = ws.data_ptr(); l.a.workspace_bytes = wsb;
+  }
+  if (c.lse) {
+    lse = c.ragged() ? at::empty({k.N, k.H}, opts.dtype(at::kFloat)) : at::empty({k.B, k.H, k.N}, opts.dtype(at::kFloat));
+    l.lo = strided<fcsa_lse_out>(lse, c.ragged() ? kPacked : kDense);
+  }
+  check(e.run(l), e.symbol);
+  return {o, lse};
+}
+
 Tensor kvcache_forward(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const optional<Tensor>& k_new, const optional<Tensor>& v_new,
                        const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table, int64_t max_seqlen_k, double scale, bool causal,
                        bool l2norm_qk, int64_t groups) {
-  return kvcache_forward_impl(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups, nullptr);
+  return std::get<0>(kvcache_call({q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups}));
 }
 Tensor kvcache_window_forward(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const optional<Tensor>& k_new,
                               const optional<Tensor>& v_new, const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table,
                               int64_t max_seqlen_k, double scale, bool causal, bool l2norm_qk, int64_t groups, int64_t left, int64_t right) {
-  const Win win(left, right);
-  return kvcache_forward_impl(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups, &win.w);
+  const Win win(left, right);      // this op takes its sides as they are: (-1, -1) is a window too
+  CacheCall c{q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups};
+  c.win = &win.w;
+  return std::get<0>(kvcache_call(c));
 }
 
 // an e4m3fn cache: window sides of (-1, -1) are the un-windowed call
 Tensor kvcache_fp8_forward(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const optional<Tensor>& k_new, const optional<Tensor>& v_new,
                            const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table, const Tensor& k_scale, const Tensor& v_scale,
                            int64_t max_seqlen_k, double scale, bool causal, bool l2norm_qk, int64_t groups, int64_t left, int64_t right) {
-  const Win win(left, right);
-  return kvcache_forward_impl(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups,
-                              left == -1 && right == -1 ? nullptr : &win.w, &k_scale, &v_scale);
+  const OptWin win(left, right);
+  CacheCall c{q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups};
+  c.win = win.ptr(); c.k_scale = &k_scale; c.v_scale = &v_scale;
+  return std::get<0>(kvcache_call(c));
 }
 
 // a ragged step: packed q [total_q, H, D] with cu_seqlens_q [B + 1]; k_scale / v_scale given: an e4m3fn cache (its codes as uint8 tensors);
@@ -977,11 +1071,11 @@ Tensor kvcache_varlen_forward(const Tensor& q, const Tensor& k_cache, const Tens
                               const optional<Tensor>& v_new, const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table,
                               const optional<Tensor>& k_scale, const optional<Tensor>& v_scale, int64_t max_seqlen_q, int64_t max_seqlen_k, double scale,
                               bool causal, bool l2norm_qk, int64_t groups, int64_t left, int64_t right) {
-  TORCH_CHECK_VALUE(k_scale.has_value() == v_scale.has_value(), "k_scale and v_scale must be given together");
-  const Win win(left, right);
-  return kvcache_forward_impl(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups,
-                              left == -1 && right == -1 ? nullptr : &win.w, k_scale.has_value() ? &*k_scale : nullptr,
-                              v_scale.has_value() ? &*v_scale : nullptr, &cu_seqlens_q, max_seqlen_q);
+  CacheCall c{q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups};
+  set_scales(c, k_scale, v_scale);
+  const OptWin win(left, right);
+  c.win = win.ptr(); c.cu_q = &cu_seqlens_q; c.max_seqlen_q = max_seqlen_q;
+  return std::get<0>(kvcache_call(c));
 }
 
 // Every decode route with the rows' log-sum-exp as a second result (return_lse=True): cu_seqlens_q given: a ragged step; k_scale / v_scale
@@ -992,15 +1086,11 @@ std::tuple<Tensor, Tensor> kvcache_lse_forward(const Tensor& q, const Tensor& k_
                                                const optional<Tensor>& block_table, const optional<Tensor>& k_scale, const optional<Tensor>& v_scale,
                                                int64_t max_seqlen_q, int64_t max_seqlen_k, double scale, bool causal, bool l2norm_qk, int64_t groups,
                                                int64_t left, int64_t right) {
-  TORCH_CHECK_VALUE(k_scale.has_value() == v_scale.has_value(), "k_scale and v_scale must be given together");
-  const bool windowed = !(left == -1 && right == -1);
-  fcsa_window w;
-  if (windowed) w = Win(left, right).w;
-  Tensor lse;
-  Tensor o = kvcache_forward_impl(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups,
-                                  windowed ? &w : nullptr, k_scale.has_value() ? &*k_scale : nullptr, v_scale.has_value() ? &*v_scale : nullptr,
-                                  cu_seqlens_q.has_value() ? &*cu_seqlens_q : nullptr, max_seqlen_q, &lse);
-  return {o, lse};
+  CacheCall c{q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups};
+  set_scales(c, k_scale, v_scale);
+  const OptWin win(left, right);
+  c.win = win.ptr(); c.cu_q = ptr(cu_seqlens_q); c.max_seqlen_q = max_seqlen_q; c.lse = true;
+  return kvcache_call(c);
 }
 
 // A prompt chunk against the cache on the multi-wave prefill kernel: kvcache_lse_forward's ragged step without scales and window sides.
@@ -1009,64 +1099,41 @@ std::tuple<Tensor, Tensor> kvcache_prefill_forward(const Tensor& q, const Tensor
                                                    const optional<Tensor>& k_new, const optional<Tensor>& v_new, const optional<Tensor>& cache_seqlens,
                                                    const optional<Tensor>& block_table, int64_t max_seqlen_q, int64_t max_seqlen_k, double scale,
                                                    bool causal, bool l2norm_qk, int64_t groups) {
-  Tensor lse;
-  Tensor o = kvcache_forward_impl(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups,
-                                  nullptr, nullptr, nullptr, &cu_seqlens_q, max_seqlen_q, &lse, true);
-  return {o, lse};
+  CacheCall c{q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups};
+  c.cu_q = &cu_seqlens_q; c.max_seqlen_q = max_seqlen_q; c.lse = true; c.route = Route::Prefill;
+  return kvcache_call(c);
 }
 
-// An engine step: kvcache_lse_forward's ragged step with the routing fields of fcsa_kvcache_step (chunk_rows / max_decode_tokens < 0: the
-// library's default / total_q; no_decode, no_chunk: the caller's promises, which skip a launch).
+// An engine step: kvcache_lse_forward's ragged step with the routing fields of fcsa_kvcache_step.  slopes given (kvcache_alibi_forward): the
+// step with a linear position bias (float32 [H] or [B, H] on q's device, never read on the host), through fcsa_forward_kvcache_alibi.
+// c: the call with the members every op has.
+std::tuple<Tensor, Tensor> step_call(CacheCall c, const Tensor* slopes, const Tensor& cu_seqlens_q, const optional<Tensor>& k_scale,
+                                     const optional<Tensor>& v_scale, int64_t max_seqlen_q, int64_t left, int64_t right, int64_t chunk_rows,
+                                     int64_t max_decode_tokens, bool no_decode, bool no_chunk) {
+  set_scales(c, k_scale, v_scale);
+  c.step = step_fields(chunk_rows, max_decode_tokens, no_decode, no_chunk);
+  const OptWin win(left, right);
+  c.win = win.ptr(); c.cu_q = &cu_seqlens_q; c.max_seqlen_q = max_seqlen_q; c.lse = true;
+  c.route = slopes != nullptr ? Route::Alibi : Route::Step; c.extra = slopes;
+  return kvcache_call(c);
+}
 std::tuple<Tensor, Tensor> kvcache_step_forward(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& cu_seqlens_q,
                                                 const optional<Tensor>& k_new, const optional<Tensor>& v_new, const optional<Tensor>& cache_seqlens,
                                                 const optional<Tensor>& block_table, const optional<Tensor>& k_scale, const optional<Tensor>& v_scale,
                                                 int64_t max_seqlen_q, int64_t max_seqlen_k, double scale, bool causal, bool l2norm_qk, int64_t groups,
                                                 int64_t left, int64_t right, int64_t chunk_rows, int64_t max_decode_tokens, bool no_decode,
                                                 bool no_chunk) {
-  TORCH_CHECK_VALUE(k_scale.has_value() == v_scale.has_value(), "k_scale and v_scale must be given together");
-  TORCH_CHECK_VALUE(chunk_rows >= -1, "chunk_rows must be a non-negative integer (or -1: the default), got ", chunk_rows);
-  TORCH_CHECK_VALUE(max_decode_tokens >= -1, "max_decode_tokens must be a non-negative integer (or -1: total_q), got ", max_decode_tokens);
-  const bool windowed = !(left == -1 && right == -1);
-  fcsa_window w;
-  if (windowed) w = Win(left, right).w;
-  fcsa_kvcache_step st;
-  std::memset(&st, 0, sizeof(st));
-  st.chunk_rows = (int32_t)std::min<int64_t>(chunk_rows, INT32_MAX);
-  st.max_decode_tokens = std::min<int64_t>(max_decode_tokens, INT32_MAX);
-  st.no_decode = no_decode;
-  st.no_chunk = no_chunk;
-  Tensor lse;
-  Tensor o = kvcache_forward_impl(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups,
-                                  windowed ? &w : nullptr, k_scale.has_value() ? &*k_scale : nullptr, v_scale.has_value() ? &*v_scale : nullptr,
-                                  &cu_seqlens_q, max_seqlen_q, &lse, false, &st);
-  return {o, lse};
+  return step_call({q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups}, nullptr,
+                   cu_seqlens_q, k_scale, v_scale, max_seqlen_q, left, right, chunk_rows, max_decode_tokens, no_decode, no_chunk);
 }
-
-// An engine step with a linear position bias: kvcache_step_forward with alibi_slopes (float32 [H] or [B, H] on q's device, never read on
-// the host), through fcsa_forward_kvcache_alibi.
 std::tuple<Tensor, Tensor> kvcache_alibi_forward(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& cu_seqlens_q,
                                                  const Tensor& alibi_slopes, const optional<Tensor>& k_new, const optional<Tensor>& v_new,
                                                  const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table,
                                                  const optional<Tensor>& k_scale, const optional<Tensor>& v_scale, int64_t max_seqlen_q,
                                                  int64_t max_seqlen_k, double scale, bool causal, bool l2norm_qk, int64_t groups, int64_t left,
                                                  int64_t right, int64_t chunk_rows, int64_t max_decode_tokens, bool no_decode, bool no_chunk) {
-  TORCH_CHECK_VALUE(k_scale.has_value() == v_scale.has_value(), "k_scale and v_scale must be given together");
-  TORCH_CHECK_VALUE(chunk_rows >= -1, "chunk_rows must be a non-negative integer (or -1: the default), got ", chunk_rows);
-  TORCH_CHECK_VALUE(max_decode_tokens >= -1, "max_decode_tokens must be a non-negative integer (or -1: total_q), got ", max_decode_tokens);
-  const bool windowed = !(left == -1 && right == -1);
-  fcsa_window w;
-  if (windowed) w = Win(left, right).w;
-  fcsa_kvcache_step st;
-  std::memset(&st, 0, sizeof(st));
-  st.chunk_rows = (int32_t)std::min<int64_t>(chunk_rows, INT32_MAX);
-  st.max_decode_tokens = std::min<int64_t>(max_decode_tokens, INT32_MAX);
-  st.no_decode = no_decode;
-  st.no_chunk = no_chunk;
-  Tensor lse;
-  Tensor o = kvcache_forward_impl(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups,
-                                  windowed ? &w : nullptr, k_scale.has_value() ? &*k_scale : nullptr, v_scale.has_value() ? &*v_scale : nullptr,
-                                  &cu_seqlens_q, max_seqlen_q, &lse, false, &st, nullptr, &alibi_slopes);
-  return {o, lse};
+  return step_call({q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups}, &alibi_slopes,
+                   cu_seqlens_q, k_scale, v_scale, max_seqlen_q, left, right, chunk_rows, max_decode_tokens, no_decode, no_chunk);
 }
 
 // A tree step: kvcache_lse_forward's ragged step without a window and without `causal`, the visibility of the step's own tokens given per
@@ -1076,12 +1143,10 @@ std::tuple<Tensor, Tensor> kvcache_tree_forward(const Tensor& q, const Tensor& k
                                                 const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table,
                                                 const optional<Tensor>& k_scale, const optional<Tensor>& v_scale, int64_t max_seqlen_q,
                                                 int64_t max_seqlen_k, double scale, bool l2norm_qk, int64_t groups) {
-  TORCH_CHECK_VALUE(k_scale.has_value() == v_scale.has_value(), "k_scale and v_scale must be given together");
-  Tensor lse;
-  Tensor o = kvcache_forward_impl(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, false, l2norm_qk, groups,
-                                  nullptr, k_scale.has_value() ? &*k_scale : nullptr, v_scale.has_value() ? &*v_scale : nullptr, &cu_seqlens_q,
-                                  max_seqlen_q, &lse, false, nullptr, &tree_mask);
-  return {o, lse};
+  CacheCall c{q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, false, l2norm_qk, groups};
+  set_scales(c, k_scale, v_scale);
+  c.cu_q = &cu_seqlens_q; c.max_seqlen_q = max_seqlen_q; c.lse = true; c.route = Route::Tree; c.extra = &tree_mask;
+  return kvcache_call(c);
 }
 
 // kvcache_keep_accepted: the rows cache_seqlens[b] + accepted[b, i] of both caches move to cache_seqlens[b] + i (i < num_accepted[b]), in
@@ -1110,31 +1175,16 @@ void kvcache_compact(const Tensor& k_cache, const Tensor& v_cache, const Tensor&
   const int64_t B = accepted.size(0);
   TORCH_CHECK_VALUE(cache_seqlens.dim() == 1 && cache_seqlens.size(0) == B && num_accepted.dim() == 1 && num_accepted.size(0) == B,
                     "cache_seqlens and num_accepted must be [", B, "]");
-  const bool paged = block_table.has_value();
-  fcsa_kvcache kv;
-  std::memset(&kv, 0, sizeof(kv));
-  int64_t capacity = k_cache.size(2);
-  Tensor tab;
-  if (paged) {
-    same_dev("block_table", *block_table);
-    TORCH_CHECK_TYPE(block_table->scalar_type() == at::kInt, "block_table must be int32");
-    TORCH_CHECK_VALUE(block_table->dim() == 2 && block_table->size(0) == B, "block_table must be [sequences, max_blocks]");
-    tab = block_table->contiguous();
-    kv.page_size = (int32_t)k_cache.size(2);
-    kv.num_blocks = (int32_t)k_cache.size(0);
-    capacity = tab.size(1) * k_cache.size(2);
-    kv.block_table = tab.data_ptr<int32_t>();
-    kv.block_table_stride = tab.size(1);
-  } else {
-    TORCH_CHECK_VALUE(k_cache.size(0) == B, "batch mismatch between accepted (", B, ") and the caches (", k_cache.size(0), ")");
-  }
-  TORCH_CHECK_VALUE(capacity <= INT32_MAX, "cache capacity must stay below 2^31");
-  if (B == 0 || Hk == 0 || capacity == 0) return;
+  const Geometry g = cache_geometry(k_cache, block_table, B, same_dev, "sequences", "accepted");
+  TORCH_CHECK_VALUE(g.capacity <= INT32_MAX, "cache capacity must stay below 2^31");
+  if (B == 0 || Hk == 0 || g.capacity == 0) return;
   c10::DeviceGuard guard(k_cache.device());
   const Tensor sl = cache_seqlens.contiguous(), acc = accepted.stride(1) == 1 ? accepted : accepted.contiguous(), na = num_accepted.contiguous();
+  fcsa_kvcache kv;
+  std::memset(&kv, 0, sizeof(kv));
   kv.k_cache = strided(k_cache);
   kv.v_cache = strided(v_cache);
-  kv.capacity = (int32_t)capacity;
+  g.fill(kv);
   kv.cache_seqlens = sl.data_ptr<int32_t>();
   check(g_abi.kvcache_compact(&kv, (int32_t)B, (int32_t)Hk, (int32_t)D, (int32_t)es, acc.data_ptr<int32_t>(), acc.stride(0), (int32_t)acc.size(1),
                               na.data_ptr<int32_t>(), stream_of(k_cache)),

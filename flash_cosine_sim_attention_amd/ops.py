@@ -18,6 +18,8 @@ plain_cosine_sim_attention.  There is no limit on scale (only float16 refuses |s
 """
 from __future__ import annotations
 
+import types
+
 import torch
 from torch.autograd import Function
 
@@ -317,10 +319,25 @@ def _host_view(q, cu_seqlens_q, k_new, cache_seqlens):
     return counts, lens, appended
 
 
+def _cache_capacity(k_cache, block_table, B, counted):
+    """The positions per sequence of a cache that serves B sequences: contiguous [B, Hk, capacity, D], or paged by block_table (checked:
+    int32 [B, max_blocks], pages a positive multiple of 16).  counted: whose B sequences the caches must match, for the message."""
+    if block_table is None:
+        if k_cache.shape[0] != B:
+            raise ValueError(f"batch mismatch between {counted} ({B} sequences) and the caches ({k_cache.shape[0]})")
+        return k_cache.shape[2]
+    if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B:
+        raise TypeError("block_table must be an int32 [sequences, max_blocks] tensor")
+    page = k_cache.shape[2]
+    if page <= 0 or page % 16:
+        raise ValueError(f"page_size ({page}) must be a positive multiple of 16")
+    return block_table.shape[1] * page
+
+
 class _CacheCall:
-    """The front end that `flash_cosine_sim_attention_with_kvcache` and `flash_cosine_sim_attention_varlen_with_kvcache` share: the checks of
-    the caches (here), of the tables, bounds and scales of a step of B sequences (`tables`), and the moves to q's device (`on_device`).
-    Nothing here reads a device tensor on the host."""
+    """The front end that every cache function shares, the equal-N one (`flash_cosine_sim_attention_with_kvcache`) and, through
+    `_packed_call`, the packed ones (ragged, prefill, engine step, ALiBi, tree): the checks of the caches (here), of the tables, bounds and
+    scales of a step of B sequences (`tables`), and the moves to q's device (`on_device`).  Nothing here reads a device tensor on the host."""
 
     def __init__(self, fn, q, q_fault, k_cache, v_cache, k_new, v_new, k_scale, v_scale):
         """q_fault: the caller's verdict on q's rank, None or the message to refuse it with (raised where the rank checks stand)."""
@@ -361,18 +378,8 @@ class _CacheCall:
         """The step's tables, checked: B sequences; cu_seqlens_q (checked by the caller) or None for a rectangular q; appends: whether
         k_new brings anything to append.  Sets capacity, max_k, the host's view (counts, lens, appended: `_host_view`) and the scales
         as tensors."""
-        k_cache = self.k_cache
-        if block_table is not None:
-            if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B:
-                raise TypeError("block_table must be an int32 [sequences, max_blocks] tensor")
-            page = k_cache.shape[2]
-            if page <= 0 or page % 16:
-                raise ValueError(f"page_size ({page}) must be a positive multiple of 16")
-            capacity = block_table.shape[1] * page
-        else:
-            if k_cache.shape[0] != B:
-                raise ValueError(f"batch mismatch between the step ({B} sequences) and the caches ({k_cache.shape[0]})")
-            capacity = k_cache.shape[2]
+        k_cache, page = self.k_cache, self.k_cache.shape[2]
+        capacity = _cache_capacity(k_cache, block_table, B, "the step")
         if cache_seqlens is None:
             if appends:
                 raise ValueError("k_new given but cache_seqlens is None (every sequence full): there is no slot to append to")
@@ -485,11 +492,48 @@ def flash_cosine_sim_attention_with_kvcache(q, k_cache, v_cache, k_new=None, v_n
     return _torch_ops.load().kvcache_forward(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, c.max_k, *tail)
 
 
-def _ragged_step(fn, q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q, max_seqlen_k, k_scale, v_scale,
-                 window, cpu_kw):
-    """What `flash_cosine_sim_attention_varlen_with_kvcache` and `flash_cosine_sim_attention_prefill_with_kvcache` share: the checks of a
-    packed step (q's rank, the caches, cu_seqlens_q, the packed new rows, the bounds, the tables) and, for CPU tensors, the forward-only
-    path of `cpu.py`.  Returns (the _CacheCall, the CPU result or None, cu_seqlens_q on q's device, max_seqlen_q clamped to total_q)."""
+def _step_count(name, value):
+    """chunk_rows / max_decode_tokens: None or a non-negative integer"""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, int):
+        raise TypeError(f"{name} must be None or a non-negative integer, got {value!r}")
+    if value < 0:
+        raise ValueError(f"{name} must be None or a non-negative integer, got {value}")
+    return value
+
+
+def _step_routing(c, total_q, H, chunk_rows, max_decode_tokens):
+    """The routing fields of an engine step, for every call that is one: (chunk_rows threshold, decode-rows bound, no_decode, no_chunk)"""
+    threshold = _lib.STEP_CHUNK_ROWS if chunk_rows is None else min(chunk_rows, 2 ** 31 - 1)
+    bound, no_decode, no_chunk = (-1 if max_decode_tokens is None else min(max_decode_tokens, total_q)), False, False
+    if c.counts is not None:      # a host table: the decode-routed rows exactly, and which launch would find no sequence
+        G = H // c.Hk
+        decode = [n for n in c.counts if n > 0 and G * n < threshold]
+        bound, no_decode, no_chunk = sum(decode), not decode, len(decode) == sum(1 for n in c.counts if n > 0)
+    return threshold, bound, no_decode, no_chunk
+
+
+def _empty_result(q, return_lse):
+    """a packed step without rows: nothing to append, nothing to write, no launch"""
+    o = q.new_empty(q.shape)
+    return (o, q.new_empty((0, q.shape[1]), dtype=torch.float32)) if return_lse else o
+
+
+def _step_arguments(return_lse, window_size, chunk_rows=None, max_decode_tokens=None):
+    """The argument checks that open every packed cache function, before its own: returns (window, chunk_rows, max_decode_tokens)."""
+    _check_return_lse(return_lse)
+    return _window(window_size), _step_count("chunk_rows", chunk_rows), _step_count("max_decode_tokens", max_decode_tokens)
+
+
+def _packed_call(fn, q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q, max_seqlen_k, k_scale, v_scale,
+                 *, return_lse, window, cpu_kw, op, routing=None, launch_empty=False):
+    """What the packed cache functions share once their own arguments are checked: the checks of a packed step (q's rank, the caches,
+    cu_seqlens_q, the packed new rows, the bounds, the tables); for CPU tensors the forward-only path of `cpu.py` with the keywords
+    cpu_kw; the empty result of a step without rows (unless launch_empty); the moves to q's device; the op; and the choice of o or (o, lse).
+    op(s) makes the function's op call and returns (o, lse).  s holds what the ops take beyond the function's own arguments: k_cache,
+    v_cache, cache_seqlens, block_table (`_CacheCall.on_device`), cu_q, k_scale, v_scale, max_q, max_k and, with routing = (chunk_rows,
+    max_decode_tokens), routing: the four fields of `_step_routing`."""
     q_fault = None if q.dim() == 3 else f"q must be a packed [total_q, heads, dim_head] tensor, got {tuple(q.shape)}"
     c = _CacheCall(fn, q, q_fault, k_cache, v_cache, k_new, v_new, k_scale, v_scale)
     if not isinstance(cu_seqlens_q, torch.Tensor) or cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 1:
@@ -508,11 +552,19 @@ def _ragged_step(fn, q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seql
             raise ValueError("CPU tensors take host cu_seqlens_q and cache_seqlens tables")
         lens = c.lens if c.lens is not None else [c.capacity] * B
         detach = lambda t: None if t is None else t.detach()          # (grad mode is off here, or nothing requires grad)
-        out = _cpu.attention_forward_kvcache_varlen_cpu(q.detach(), k_cache, v_cache, cu_seqlens_q, detach(k_new), detach(v_new), lens, block_table,
-                                                        window_size=window, **cpu_kw, **c.cpu_quant())
-        return c, out, None, None
+        return _cpu.attention_forward_kvcache_varlen_cpu(q.detach(), k_cache, v_cache, cu_seqlens_q, detach(k_new), detach(v_new), lens, block_table,
+                                                         window_size=window, return_lse=return_lse, **cpu_kw, **c.cpu_quant())
     max_q = total_q if max_seqlen_q is None else min(int(max_seqlen_q), total_q)
-    return c, None, cu_seqlens_q.to(q.device, non_blocking=True), max_q
+    cu_q = cu_seqlens_q.to(q.device, non_blocking=True)
+    if total_q == 0 and not launch_empty:
+        return _empty_result(q, return_lse)
+    routing = None if routing is None else _step_routing(c, total_q, H, *routing)
+    k_cache, v_cache, cache_seqlens, block_table = c.on_device()
+    s = types.SimpleNamespace(k_cache=k_cache, v_cache=v_cache, cache_seqlens=cache_seqlens, block_table=block_table, cu_q=cu_q,
+                              k_scale=c.k_scale, v_scale=c.v_scale, max_q=max_q, max_k=c.max_k, routing=routing)
+    _torch_ops.load()
+    o, lse = op(s)
+    return (o, lse) if return_lse else o
 
 
 def flash_cosine_sim_attention_varlen_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new=None, v_new=None, cache_seqlens=None,
@@ -542,17 +594,15 @@ def flash_cosine_sim_attention_varlen_with_kvcache(q, k_cache, v_cache, cu_seqle
     return_lse=True: returns (o, lse) with lse float32 [total_q, H], as in `flash_cosine_sim_attention_with_kvcache`.
     Tree attention for speculative decoding (a tree_mask over the step's own tokens in place of causal) is this call under another name:
     `flash_cosine_sim_attention_tree_with_kvcache`, which takes these arguments and tree_mask."""
-    _check_return_lse(return_lse)
-    window = _window(window_size)
-    c, cpu_result, cu_q, max_q = _ragged_step("flash_cosine_sim_attention_varlen_with_kvcache", q, k_cache, v_cache, cu_seqlens_q, k_new, v_new,
-                                              cache_seqlens, block_table, max_seqlen_q, max_seqlen_k, k_scale, v_scale, window,
-                                              dict(scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, return_lse=bool(return_lse)))
-    if q.device.type == "cpu":
-        return cpu_result
-    k_cache, v_cache, cache_seqlens, block_table = c.on_device()
-    op = _torch_ops.load().kvcache_lse_forward if return_lse else _torch_ops.load().kvcache_varlen_forward
-    return op(q, k_cache, v_cache, cu_q, k_new, v_new, cache_seqlens, block_table, c.k_scale, c.v_scale, max_q, c.max_k, float(scale), bool(causal),
-              bool(l2norm_qk), int(groups), window[0], window[1])
+    window, _, _ = _step_arguments(return_lse, window_size)
+
+    def op(s):      # the two ops take the same arguments; the one without the lse returns o alone
+        args = (q, s.k_cache, s.v_cache, s.cu_q, k_new, v_new, s.cache_seqlens, s.block_table, s.k_scale, s.v_scale, s.max_q, s.max_k,
+                float(scale), bool(causal), bool(l2norm_qk), int(groups), window[0], window[1])
+        return torch.ops.fcsa.kvcache_lse_forward(*args) if return_lse else (torch.ops.fcsa.kvcache_varlen_forward(*args), None)
+    return _packed_call("flash_cosine_sim_attention_varlen_with_kvcache", q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens,
+                        block_table, max_seqlen_q, max_seqlen_k, k_scale, v_scale, return_lse=return_lse, window=window, op=op,
+                        cpu_kw=dict(scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk), launch_empty=True)
 
 
 def flash_cosine_sim_attention_prefill_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new=None, v_new=None, cache_seqlens=None,
@@ -576,8 +626,7 @@ def flash_cosine_sim_attention_prefill_with_kvcache(q, k_cache, v_cache, cu_seql
     path of `cpu.py`.  Forward only.
     return_lse=True: returns (o, lse) with lse float32 [total_q, H]."""
     fn, other = "flash_cosine_sim_attention_prefill_with_kvcache", "flash_cosine_sim_attention_varlen_with_kvcache"
-    _check_return_lse(return_lse)
-    window = _window(window_size)
+    window, _, _ = _step_arguments(return_lse, window_size)
     # what this kernel does not take, before anything else (and before the device branch: CPU tensors are refused the same things)
     if k_scale is not None or v_scale is not None or k_cache.dtype in _FP8_TYPES or v_cache.dtype in _FP8_TYPES:
         raise TypeError(f"{fn} does not take float8 caches or k_scale / v_scale: {other} takes them")
@@ -590,42 +639,10 @@ def flash_cosine_sim_attention_prefill_with_kvcache(q, k_cache, v_cache, cu_seql
         raise ValueError(f"{fn} takes head dimensions 64 and 128, got {q.shape[-1]}: {other} takes the others")
     if window != (-1, -1):
         raise ValueError(f"{fn} takes no sliding window (window_size {tuple(window_size)}): {other} takes one")
-    c, cpu_result, cu_q, max_q = _ragged_step(fn, q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q,
-                                              max_seqlen_k, None, None, window,
-                                              dict(scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, return_lse=bool(return_lse)))
-    if q.device.type == "cpu":
-        return cpu_result
-    total_q, H = q.shape[:2]
-    if total_q == 0:      # nothing to append, nothing to write: no launch
-        o = q.new_empty(q.shape)
-        return (o, q.new_empty((0, H), dtype=torch.float32)) if return_lse else o
-    k_cache, v_cache, cache_seqlens, block_table = c.on_device()
-    _torch_ops.load()
-    o, lse = torch.ops.fcsa_prefill.kvcache_prefill_forward(q, k_cache, v_cache, cu_q, k_new, v_new, cache_seqlens, block_table, max_q, c.max_k,
-                                                            float(scale), bool(causal), bool(l2norm_qk), int(groups))
-    return (o, lse) if return_lse else o
-
-
-def _step_count(name, value):
-    """chunk_rows / max_decode_tokens: None or a non-negative integer"""
-    if value is None:
-        return None
-    if isinstance(value, bool) or not isinstance(value, int):
-        raise TypeError(f"{name} must be None or a non-negative integer, got {value!r}")
-    if value < 0:
-        raise ValueError(f"{name} must be None or a non-negative integer, got {value}")
-    return value
-
-
-def _step_routing(c, total_q, H, chunk_rows, max_decode_tokens):
-    """The routing fields of an engine step, for every call that is one: (chunk_rows threshold, decode-rows bound, no_decode, no_chunk)"""
-    threshold = _lib.STEP_CHUNK_ROWS if chunk_rows is None else min(chunk_rows, 2 ** 31 - 1)
-    bound, no_decode, no_chunk = (-1 if max_decode_tokens is None else min(max_decode_tokens, total_q)), False, False
-    if c.counts is not None:      # a host table: the decode-routed rows exactly, and which launch would find no sequence
-        G = H // c.Hk
-        decode = [n for n in c.counts if n > 0 and G * n < threshold]
-        bound, no_decode, no_chunk = sum(decode), not decode, len(decode) == sum(1 for n in c.counts if n > 0)
-    return threshold, bound, no_decode, no_chunk
+    op = lambda s: torch.ops.fcsa_prefill.kvcache_prefill_forward(q, s.k_cache, s.v_cache, s.cu_q, k_new, v_new, s.cache_seqlens, s.block_table,
+                                                                  s.max_q, s.max_k, float(scale), bool(causal), bool(l2norm_qk), int(groups))
+    return _packed_call(fn, q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q, max_seqlen_k, None, None,
+                        return_lse=return_lse, window=window, op=op, cpu_kw=dict(scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk))
 
 
 def flash_cosine_sim_attention_step_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new=None, v_new=None, cache_seqlens=None,
@@ -653,34 +670,13 @@ def flash_cosine_sim_attention_step_with_kvcache(q, k_cache, v_cache, cu_seqlens
     taken from the table, and a launch that would find no sequence is skipped.  With a device table both launches always run.
     float32 tensors and head dimensions other than 64 and 128 have no chunk kernel: there this call is the ragged call (chunk_rows and
     max_decode_tokens are checked and otherwise ignored).  CPU tensors take the forward-only path of `cpu.py`.  Forward only."""
-    fn = "flash_cosine_sim_attention_step_with_kvcache"
-    _check_return_lse(return_lse)
-    window = _window(window_size)
-    chunk_rows = _step_count("chunk_rows", chunk_rows)
-    max_decode_tokens = _step_count("max_decode_tokens", max_decode_tokens)
-    c, cpu_result, cu_q, max_q = _ragged_step(fn, q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q,
-                                              max_seqlen_k, k_scale, v_scale, window,
-                                              dict(scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, return_lse=bool(return_lse)))
-    if q.device.type == "cpu":
-        return cpu_result
-    total_q, H = q.shape[:2]
-    if total_q == 0:      # nothing to append, nothing to write: no launch
-        o = q.new_empty(q.shape)
-        return (o, q.new_empty((0, H), dtype=torch.float32)) if return_lse else o
-    threshold, bound, no_decode, no_chunk = _step_routing(c, total_q, H, chunk_rows, max_decode_tokens)
-    k_cache, v_cache, cache_seqlens, block_table = c.on_device()
-    _torch_ops.load()
-    o, lse = torch.ops.fcsa_step.kvcache_step_forward(q, k_cache, v_cache, cu_q, k_new, v_new, cache_seqlens, block_table, c.k_scale, c.v_scale,
-                                                      max_q, c.max_k, float(scale), bool(causal), bool(l2norm_qk), int(groups), window[0], window[1],
-                                                      threshold, bound, no_decode, no_chunk)
-    return (o, lse) if return_lse else o
-
-
-# ---------------------------------------------------------------------------------------------
-# attention states: merging the results of the same queries over disjoint sets of keys, and the shared-prefix decode step built on it
-# ---------------------------------------------------------------------------------------------
-
-MERGE_MAX_STATES = 8
+    window, chunk_rows, max_decode_tokens = _step_arguments(return_lse, window_size, chunk_rows, max_decode_tokens)
+    op = lambda s: torch.ops.fcsa_step.kvcache_step_forward(q, s.k_cache, s.v_cache, s.cu_q, k_new, v_new, s.cache_seqlens, s.block_table,
+                                                            s.k_scale, s.v_scale, s.max_q, s.max_k, float(scale), bool(causal), bool(l2norm_qk),
+                                                            int(groups), window[0], window[1], *s.routing)
+    return _packed_call("flash_cosine_sim_attention_step_with_kvcache", q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens,
+                        block_table, max_seqlen_q, max_seqlen_k, k_scale, v_scale, return_lse=return_lse, window=window, op=op,
+                        cpu_kw=dict(scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk), routing=(chunk_rows, max_decode_tokens))
 
 
 def flash_cosine_sim_attention_alibi_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new=None, v_new=None, cache_seqlens=None,
@@ -714,10 +710,7 @@ def flash_cosine_sim_attention_alibi_with_kvcache(q, k_cache, v_cache, cu_seqlen
         return flash_cosine_sim_attention_step_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q,
                                                             max_seqlen_k, scale, groups, causal, l2norm_qk, k_scale, v_scale, return_lse, window_size,
                                                             chunk_rows, max_decode_tokens)
-    _check_return_lse(return_lse)
-    window = _window(window_size)
-    chunk_rows = _step_count("chunk_rows", chunk_rows)
-    max_decode_tokens = _step_count("max_decode_tokens", max_decode_tokens)
+    window, chunk_rows, max_decode_tokens = _step_arguments(return_lse, window_size, chunk_rows, max_decode_tokens)
     if not isinstance(alibi_slopes, torch.Tensor) or alibi_slopes.dtype != torch.float32:
         raise TypeError(f"alibi_slopes must be a float32 tensor of shape [heads] or [sequences, heads], got "
                         f"{getattr(alibi_slopes, 'dtype', type(alibi_slopes).__name__)}")
@@ -732,24 +725,13 @@ def flash_cosine_sim_attention_alibi_with_kvcache(q, k_cache, v_cache, cu_seqlen
         raise ValueError(f"alibi_slopes is on {alibi_slopes.device} but q is on {q.device}")
     if q.device.type == "cpu" and alibi_slopes.device.type != "cpu":
         raise ValueError("CPU tensors take host alibi_slopes")
-    c, cpu_result, cu_q, max_q = _ragged_step(fn, q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q,
-                                              max_seqlen_k, k_scale, v_scale, window,
-                                              dict(scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, return_lse=bool(return_lse),
-                                                   alibi_slopes=alibi_slopes.detach()))
-    if q.device.type == "cpu":
-        return cpu_result
-    total_q, H = q.shape[:2]
-    if total_q == 0:      # nothing to append, nothing to write: no launch
-        o = q.new_empty(q.shape)
-        return (o, q.new_empty((0, H), dtype=torch.float32)) if return_lse else o
-    threshold, bound, no_decode, no_chunk = _step_routing(c, total_q, H, chunk_rows, max_decode_tokens)
-    k_cache, v_cache, cache_seqlens, block_table = c.on_device()
-    slopes = alibi_slopes.detach().to(q.device, non_blocking=True)
-    _torch_ops.load()
-    o, lse = torch.ops.fcsa_alibi.kvcache_alibi_forward(q, k_cache, v_cache, cu_q, slopes, k_new, v_new, cache_seqlens, block_table, c.k_scale,
-                                                        c.v_scale, max_q, c.max_k, float(scale), bool(causal), bool(l2norm_qk), int(groups),
-                                                        window[0], window[1], threshold, bound, no_decode, no_chunk)
-    return (o, lse) if return_lse else o
+    op = lambda s: torch.ops.fcsa_alibi.kvcache_alibi_forward(q, s.k_cache, s.v_cache, s.cu_q, alibi_slopes.detach().to(q.device, non_blocking=True),
+                                                              k_new, v_new, s.cache_seqlens, s.block_table, s.k_scale, s.v_scale, s.max_q, s.max_k,
+                                                              float(scale), bool(causal), bool(l2norm_qk), int(groups), window[0], window[1],
+                                                              *s.routing)
+    return _packed_call(fn, q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q, max_seqlen_k, k_scale,
+                        v_scale, return_lse=return_lse, window=window, op=op, routing=(chunk_rows, max_decode_tokens),
+                        cpu_kw=dict(scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, alibi_slopes=alibi_slopes.detach()))
 
 
 def flash_cosine_sim_attention_tree_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new=None, v_new=None, cache_seqlens=None,
@@ -783,8 +765,7 @@ def flash_cosine_sim_attention_tree_with_kvcache(q, k_cache, v_cache, cu_seqlens
     if tree_mask is None:
         return flash_cosine_sim_attention_varlen_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q,
                                                               max_seqlen_k, scale, groups, causal, l2norm_qk, k_scale, v_scale, return_lse, window_size)
-    _check_return_lse(return_lse)
-    window = _window(window_size)
+    window, _, _ = _step_arguments(return_lse, window_size)
     if causal:
         raise ValueError("tree_mask states the visibility of the step's tokens: causal=True cannot be given with it")
     if window != (-1, -1):
@@ -795,19 +776,11 @@ def flash_cosine_sim_attention_tree_with_kvcache(q, k_cache, v_cache, cu_seqlens
         raise ValueError(f"tree_mask must have shape [{q.shape[0]}] (one word per packed query row), got {tuple(tree_mask.shape)}")
     if tree_mask.device != q.device:
         raise ValueError(f"tree_mask is on {tree_mask.device} but q is on {q.device}")
-    c, cpu_result, cu_q, max_q = _ragged_step(fn, q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q,
-                                              max_seqlen_k, k_scale, v_scale, window,
-                                              dict(scale=scale, groups=groups, l2norm_qk=l2norm_qk, return_lse=bool(return_lse), tree_mask=tree_mask))
-    if q.device.type == "cpu":
-        return cpu_result
-    if q.shape[0] == 0:      # nothing to append, nothing to write: no launch
-        o = q.new_empty(q.shape)
-        return (o, q.new_empty((0, q.shape[1]), dtype=torch.float32)) if return_lse else o
-    k_cache, v_cache, cache_seqlens, block_table = c.on_device()
-    _torch_ops.load()
-    o, lse = torch.ops.fcsa_tree.kvcache_tree_forward(q, k_cache, v_cache, cu_q, tree_mask, k_new, v_new, cache_seqlens, block_table, c.k_scale,
-                                                      c.v_scale, max_q, c.max_k, float(scale), bool(l2norm_qk), int(groups))
-    return (o, lse) if return_lse else o
+    op = lambda s: torch.ops.fcsa_tree.kvcache_tree_forward(q, s.k_cache, s.v_cache, s.cu_q, tree_mask, k_new, v_new, s.cache_seqlens, s.block_table,
+                                                            s.k_scale, s.v_scale, s.max_q, s.max_k, float(scale), bool(l2norm_qk), int(groups))
+    return _packed_call(fn, q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q, max_seqlen_k, k_scale,
+                        v_scale, return_lse=return_lse, window=window, op=op,
+                        cpu_kw=dict(scale=scale, groups=groups, l2norm_qk=l2norm_qk, tree_mask=tree_mask))
 
 
 def kvcache_keep_accepted(k_cache, v_cache, cache_seqlens, accepted, num_accepted, block_table=None):
@@ -841,17 +814,7 @@ def kvcache_keep_accepted(k_cache, v_cache, cache_seqlens, accepted, num_accepte
     for name, t in (("num_accepted", num_accepted), ("cache_seqlens", cache_seqlens)):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (B,):
             raise TypeError(f"{name} must be an int32 tensor of shape ({B},)")
-    page = k_cache.shape[2]
-    if block_table is not None:
-        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != B:
-            raise TypeError("block_table must be an int32 [sequences, max_blocks] tensor")
-        if page <= 0 or page % 16:
-            raise ValueError(f"page_size ({page}) must be a positive multiple of 16")
-        capacity = block_table.shape[1] * page
-    else:
-        if k_cache.shape[0] != B:
-            raise ValueError(f"batch mismatch between accepted ({B} sequences) and the caches ({k_cache.shape[0]})")
-        capacity = page
+    capacity = _cache_capacity(k_cache, block_table, B, "accepted")
     host = lambda t: t.device.type == "cpu"
     if host(num_accepted):
         counts = num_accepted.tolist()

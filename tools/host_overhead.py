@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Where does the per-call host time of a tiny forward+backward go?  (B4 H8 N128 D64 bf16 causal: the GPU work is ~40 us, so
-every number here is host-bound.)  Prints us per call for nested slices of the call path, and the same for SDPA."""
+every number here is host-bound.)  Prints us per call for nested slices of the call path, the same for SDPA, and then every call of the
+key/value-cache family."""
 import os, sys, time, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -61,3 +62,16 @@ bench("kvcache decode", lambda: F.flash_cosine_sim_attention_with_kvcache(dq, kc
 bench("kvcache decode, fp8 cache", lambda: F.flash_cosine_sim_attention_with_kvcache(dq, k8, v8, k_scale=ones, v_scale=ones, **step))
 bench("kvcache decode, ragged step", lambda: F.flash_cosine_sim_attention_varlen_with_kvcache(pq, kc, vc, cu, max_seqlen_q=1, **step))
 bench("kvcache decode, return_lse", lambda: F.flash_cosine_sim_attention_with_kvcache(dq, kc, vc, return_lse=True, **step))
+# the packed calls on the same tiny problem: one query row per sequence, so every line is two or three launches
+bench("kvcache engine step", lambda: F.flash_cosine_sim_attention_step_with_kvcache(pq, kc, vc, cu, max_seqlen_q=1, **step))
+bench("kvcache prefill", lambda: F.flash_cosine_sim_attention_prefill_with_kvcache(pq, kc, vc, cu, max_seqlen_q=1, **step))
+chain = torch.ones(B, dtype=torch.int64, device="cuda")      # one token per sequence: bit 0, the chain mask
+tree = dict(step, causal=False)
+bench("kvcache tree step, chain mask", lambda: F.flash_cosine_sim_attention_tree_with_kvcache(pq, kc, vc, cu, max_seqlen_q=1, tree_mask=chain, **tree))
+slopes = torch.tensor([2.0 ** -(h + 1) for h in range(H)], device="cuda")
+bench("kvcache engine step, alibi_slopes", lambda: F.flash_cosine_sim_attention_alibi_with_kvcache(pq, kc, vc, cu, max_seqlen_q=1, alibi_slopes=slopes, **step))
+# the compaction after a tree step: the first two of four drafted tokens kept (they stay where they are; the launch is the same)
+seqlens = torch.full((B,), L - 4, dtype=torch.int32, device="cuda")
+accepted = torch.arange(4, dtype=torch.int32, device="cuda").repeat(B, 1)
+kept = torch.full((B,), 2, dtype=torch.int32, device="cuda")
+bench("kvcache_keep_accepted", lambda: F.kvcache_keep_accepted(kc, vc, seqlens, accepted, kept))
