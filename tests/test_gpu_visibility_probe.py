@@ -6,7 +6,9 @@ more than its bar.  The randn inputs of the other GPU tests leave such a pair ~1
 Tables: window_cases.DENSE_CASES (flash_cosine_sim_attention_local), window_cases.PACKED_CASES and varlen_form_cases.CASES
 (flash_cosine_sim_attention_varlen), visibility_probe.DENSE_PLAIN_CASES (flash_cosine_sim_attention with a key mask or causal, every dense
 form: test_visibility_probe_cpu.py checks the launches), window_cases.DECODE_CASES and visibility_probe.DECODE_PLAIN_CASES (the cache calls
-with return_lse=True: lse decodes the count of visible keys), visibility_probe.PREFIX_CASES (the shared-prefix step).  A table case with
+with return_lse=True: lse decodes the count of visible keys), visibility_probe.PREFIX_CASES (the shared-prefix step),
+visibility_probe.BIAS_CASES (flash_cosine_sim_attention with an attn_bias of -inf / per-row constants that requires grad: the BIAS = 1
+kernels and bwd_dbias_kernel, d_bias = R dS element by element).  A table case with
 l2norm groups g > 1 runs with groups = 1 and scale * g (same bound, exponent regime and form: the form never depends on the grouping).
 Bars: derived in visibility_probe.py's docstring -- o 2 eps, gradients 4 eps relative to the terms' absolute sum, float32 the rtol of
 tests/tolerances.py, lse 4 eps_f32 max(1, |lse|) -- not calibrated.  Which (case, quantity) pairs cannot decide a single pair in 8
@@ -56,6 +58,21 @@ def test_probe_dense(case):
     finally:
         _lib.forward_form(prev[0]), _lib.kv_group_form(prev[1])
     _judge(dtype, name, got)
+
+
+@pytest.mark.parametrize("case", VP.BIAS_CASES, ids=[c[0] for c in VP.BIAS_CASES])
+def test_probe_bias(case):
+    """attn_bias as a per-(slice, query, key) visibility (-inf / a per-row constant): o, dq, dk, dv and d_bias of every kernel form a
+    problem with a bias can launch, per-head and per-batch, at every read and write path of the bias (M % 8, M % 4, odd, 31 / 33, a
+    misaligned pointer).  d_bias is R dS element by element: exactly 0 on every hidden pair, above 16 tiny on every other."""
+    name, dtype = case[:2]
+    got, bias, geom = VP.run_dense_bias(case, "cuda")
+    torch.cuda.synchronize()
+    _judge(dtype, name, got)
+    assert bias.grad.dtype == bias.dtype and bias.grad.shape == bias.shape
+    assert bool(torch.isfinite(bias.grad).all())
+    hidden = torch.as_tensor(~geom).to(bias.grad.device).expand_as(bias.grad)
+    assert bool((bias.grad[hidden] == 0).all()), "d_bias is not exactly 0 on a pair that causal or the key mask hides"
 
 
 DECODE = VP.decode_cases()

@@ -1,7 +1,8 @@
 """The visibility probe without a GPU (tests/visibility_probe.py): the probe notices every single hidden or leaked pair, the package's
 forward-only CPU path passes it on every surface it has (the visibility builders are written from the docstrings of ops.py, so this is an
 independent check of cpu.py as well), every GPU case of test_gpu_visibility_probe.py is decidable for single pairs up to a stated cap,
-and the probe's dense table launches every dense kernel form at 256 CUs (launch recorder)."""
+the probe's dense table launches every dense kernel form at 256 CUs (launch recorder), and its bias table every form the golden launch
+file shows for a problem with a bias; the bias probe's closed form (d_bias = R dS) against float64 autograd, and its teeth."""
 import os
 import shutil
 
@@ -116,6 +117,98 @@ def test_check_refuses_a_wrong_pair():
         assert not VP.check_lse(dtype, torch.from_numpy(lse), e0["lse"], "count")[0]
 
 
+# ---- 1b. the bias probe: closed form, teeth --------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("l2norm", [True, False], ids=["l2norm", "unit_inputs"])
+@pytest.mark.parametrize("causal", [False, True], ids=["full", "causal"])
+def test_bias_closed_form_matches_autograd(causal, l2norm):
+    """o, dq, dk, dv and d_bias = dS of `expected` over (bias pattern & geometry) against torch float64 autograd with the bias (-inf / a
+    per-row constant) as a leaf added to the logits, at 1e-12; no NaN comes out of the -inf entries.  (With the l2norm, dk of the closed
+    form projects with the ROUNDED k^ as the kernels do: it agrees to that rounding, as in test_closed_form_matches_autograd.)"""
+    D = 16
+    for N, M in ((20, 37), (37, 20), (33, 33), (5, 70)):
+        pattern = VP.bias_vis(3, N, M, D, causal, N + M)
+        bias = VP.bias_values(pattern, VP.bias_rows(3, N, N + M))
+        geom = VP.vis_dense(N, M, causal)
+        for s in range(3):
+            e = VP.expected(pattern[s] & geom, D, "f32", 8.0, l2norm)
+            a = VP.expected_autograd(geom, D, "f32", 8.0, l2norm, bias=bias[s])
+            assert all(np.isfinite(x).all() for x in a.values())
+            for name, ref in (("o", "o"), ("dq", "dq"), ("dk", "dk"), ("dv", "dv"), ("ds", "d_bias")):
+                tol = 1e-6 if name == "dk" and l2norm else 1e-12
+                assert np.abs(e[name] - a[ref]).max() <= tol, (N, M, s, name)
+            assert (np.abs(e["ds"]) <= e["mag_ds"] * (1 + 1e-12)).all() and (e["ds"][~(pattern[s] & geom)] == 0).all()
+            assert (a["d_bias"][~(pattern[s] & geom)] == 0).all()
+    assert np.abs(e["ds"]).max() > 1e-3
+
+
+def _teeth_case(dtype, causal):
+    return (f"teeth_{dtype}_{'causal' if causal else 'full'}", dtype, 64, 2, 3, 3, 140, 200, "causal_n<m" if causal else "plain", dict(), False, False, False)
+
+
+def _rounded(x, dtype):
+    return torch.from_numpy(np.ascontiguousarray(x)).to(VP.DT[dtype]).double()
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "f16", "f32"])
+def test_check_refuses_a_wrong_bias(dtype):
+    """teeth: a "result" that is the float64 expectation of a wrongly read bias, rounded to the dtype, fails `check` for o AND for d_bias:
+    the bias rolled by one column, by one row, the next slice's pattern, the two 16-key halves of one 32-key block swapped in one row, a
+    single pair flipped at column M - 1, at the first column of the last 64-key tile and in row N - 1; under causal a pair flipped on
+    the diagonal and a pair leaked one above it (the geometry's own off-by-one: there the mutation is of the effective visibility).
+    For d_bias alone: one value moved to the neighbouring column, a non-zero value at a hidden pair, and the zeros of a 64-key tile above
+    the causal diagonal extended one tile to the left."""
+    N, M = 140, 200
+    for causal in (False, True):
+        case = _teeth_case(dtype, causal)
+        eff, pattern, geom, _, _ = VP.bias_case_vis(case)
+        e0 = VP.bias_expected(case, eff)
+        for q in ("o", "d_bias"):
+            assert VP.check(dtype, _rounded(e0[q], dtype), e0[q], "self", "o" if q == "o" else "dbias", e0["mag_" + q])[0]
+
+        def single(i, j, of=None):
+            x = (pattern if of is None else of).copy()
+            x[0, i, j] = not x[0, i, j]
+            return x
+
+        diff, i0 = M - N, N - 5
+        swapped = pattern.copy()
+        swapped[0, i0, 64:80], swapped[0, i0, 80:96] = pattern[0, i0, 80:96], pattern[0, i0, 64:80]
+        assert not np.array_equal(swapped[0, i0], pattern[0, i0])
+        mutants = {"column": np.roll(pattern, 1, axis=2) & geom[None], "row": np.roll(pattern, 1, axis=1) & geom[None],
+                   "slice": np.roll(pattern, -1, axis=0) & geom[None], "halves": swapped & geom[None],
+                   "last_row": single(N - 1, 100) & geom[None]}
+        if causal:
+            mutants["diagonal"] = single(70, 70 + diff) & geom[None]
+            mutants["above_diagonal"] = single(70, 71 + diff, of=eff)
+            assert not geom[70, 71 + diff] and mutants["above_diagonal"][0, 70, 71 + diff]
+        else:
+            mutants["last_column"] = single(77, M - 1) & geom[None]
+            mutants["last_tile"] = single(77, (M - 1) // 64 * 64) & geom[None]
+        for label, wrong in mutants.items():
+            assert not np.array_equal(wrong, eff), label
+            e1 = VP.bias_expected(case, wrong, g=e0["g"])
+            for q in ("o", "d_bias"):
+                ok = VP.check(dtype, _rounded(e1[q], dtype), e0[q], label, "o" if q == "o" else "dbias", e0["mag_" + q])[0]
+                assert not ok, (dtype, causal, label, q)
+        # d_bias alone
+        ref = e0["d_bias"]
+        i, j = next((i, j) for i in range(60, N) for j in range(1, diff + i if causal else M - 1) if ref[0, i, j] != 0 and ref[0, i, j + 1] == 0)
+        moved = ref.copy()
+        moved[0, i, j], moved[0, i, j + 1] = 0.0, ref[0, i, j]
+        leak = ref.copy()
+        leak[0, i, j + 1] = np.abs(ref[ref != 0]).min()
+        wrongs = {"moved": moved, "hidden": leak}
+        if causal:
+            j0 = next(j for j in range(0, M, 64) if j > 127 + diff)                 # the first skipped key tile of the first 128-row tile
+            early = ref.copy()
+            early[:, :128, j0 - 64:j0] = 0.0
+            assert np.abs(ref[:, :128, j0 - 64:j0]).max() > 0
+            wrongs["tile_skip"] = early
+        for label, wrong in wrongs.items():
+            assert not VP.check(dtype, _rounded(wrong, dtype), ref, label, "dbias", e0["mag_d_bias"])[0], (dtype, causal, label)
+
+
 # ---- 2. cpu.py on every surface, float32 -----------------------------------------------------------------------------------------------------
 
 def _ok(name, comparisons, dtype="f32"):
@@ -132,6 +225,19 @@ def test_cpu_path_dense_and_local(N, M, causal, window, masked):
     mask = VP.key_mask(M, N) if masked else None
     for scale, l2 in ((8.0, True), (80.0, True), (1.0, False)):
         _ok(f"cpu_dense_n{N}m{M}", VP.run_dense("f32", D, 2, 4, (4, 2, 1)[N % 3], N, M, scale, l2, "cpu", causal, window, mask, seed=N, grads=False))
+
+
+CPU_BIAS = [("cpu_bias_plain", "f32", 32, 2, 4, 2, 129, 257, "plain", dict(), False, False, False),
+            ("cpu_bias_causal_perbatch", "f32", 64, 2, 4, 1, 127, 132, "causal_n<m", dict(scale=80.0), True, False, False),
+            ("cpu_bias_causal_tall", "f32", 16, 2, 4, 4, 260, 127, "causal_n>m", dict(), False, True, False),
+            ("cpu_bias_mask", "f32", 32, 1, 8, 2, 33, 128, "mask", dict(l2norm_qk=False, scale=1.0), False, False, True)]
+
+
+@pytest.mark.parametrize("case", CPU_BIAS, ids=[c[0] for c in CPU_BIAS])
+def test_cpu_path_bias(case):
+    """attn_bias of -inf / per-row constants on BIAS_CASES-style shapes (per-head and per-batch, causal at both signs of M - N, a key
+    mask, the offsets variant, a view one element into a buffer): o at its bar"""
+    _ok(case[0], VP.run_dense_bias(case, "cpu", grads=False)[0])
 
 
 @pytest.mark.parametrize("causal,window", [(False, (-1, -1)), (True, (-1, -1)), (True, (6, 0)), (False, (3, 4)), (False, (40, -1))])
@@ -250,7 +356,20 @@ def prefix_rows():
     return rows
 
 
-TABLES = {"window_dense": window_dense_rows, "dense_plain": dense_plain_rows, "packed": packed_rows, "decode": decode_rows, "prefix": prefix_rows}
+def bias_rows():
+    """o and dv of the first and the last slice of every bias case (dq makes no single-pair claim on this table: visibility_probe.
+    _bias_cases; d_bias decides every pair by construction: test_bias_cases_separate_every_d_bias_element_from_zero)"""
+    rows = []
+    for case in VP.BIAS_CASES:
+        name, dtype, D = case[:3]
+        eff = VP.bias_case_vis(case)[0]
+        scale, l2 = VP.probe_scale(case[9])
+        rows += [(name, q, all(VP.decidable(eff[s], dtype, q, D, scale, l2, seed=len(name) + s) for s in (0, len(eff) - 1))) for q in ("o", "dv")]
+    return rows
+
+
+TABLES = {"window_dense": window_dense_rows, "dense_plain": dense_plain_rows, "packed": packed_rows, "decode": decode_rows, "prefix": prefix_rows,
+          "bias": bias_rows}
 
 
 @pytest.mark.parametrize("table", sorted(TABLES))
@@ -262,6 +381,43 @@ def test_gpu_cases_are_decidable_up_to_the_cap(table):
     cnt times larger.  Those pairs are still compared at the bar on the GPU; only the single-pair
     claim is dropped for them.  The list is printed (and recorded in profiles/visibility_probe_margins.txt)."""
     _table_report(table, TABLES[table]())
+
+
+def test_bias_cases_separate_every_d_bias_element_from_zero():
+    """d_bias decides every single pair of the bias table: the element of a flipped pair moves between exactly 0 (expectation and mag 0:
+    the kernel must write 0 up to tiny) and a value whose size is at least 16 tiny -- after the power-of-two factor on do in float16.  Also
+    what the table promises about itself: sizes, the key lengths of every read and write path, the variants and regimes."""
+    for case in VP.BIAS_CASES:
+        name, dtype, D, B, H, Hk, N, M = case[:8]
+        eff, pattern, geom = VP.bias_case_vis(case)[:3]
+        e = VP.bias_expected(case, eff)
+        ref = e["d_bias"]
+        assert (ref[~eff] == 0).all() and (e["mag_d_bias"][~eff] == 0).all(), name
+        # (a visible pair whose dS is exactly 0 -- a row of keys of one class only -- says nothing; there must be few)
+        assert (ref[eff] != 0).mean() > 0.99, (name, (ref[eff] != 0).mean())
+        assert np.abs(ref[ref != 0]).min() >= 16 * VP.tiny(dtype), (name, np.abs(ref[ref != 0]).min())
+        assert np.abs(ref).max() * 4 < torch.finfo(VP.DT[dtype]).max and e["g"] == 2.0 ** round(np.log2(e["g"])), name
+        assert N * M <= 620_000 and len(eff) <= 30, name
+        live = geom.any(1)
+        cls = (np.arange(N) + M - N) % D
+        own = eff & (np.arange(M)[None, None, :] % D == cls[None, :, None])
+        can = (geom & (np.arange(M)[None, :] % D == cls[:, None])).any(1)
+        assert own.any(2)[:, live & can].all(), name
+        assert not np.array_equal(eff[0], eff[-1]) or len(eff) == 1, name
+    table = VP.BIAS_CASES
+    assert {(c[1], c[2]) for c in table} >= set(VP.BIAS_TYPES)
+    keys = {c[7] for c in table}
+    assert {128, 256, 1104, 132, 260, 1100, 127, 257, 31, 33} <= keys and any(c[6] % 32 for c in table)
+    assert set(VP.LENGTHS) <= {c[6] for c in table} | keys
+    for dtype, D in VP.BIAS_TYPES:
+        assert {c[8] for c in table if (c[1], c[2]) == (dtype, D)} >= set(VP.BIAS_VARIANTS), (dtype, D)
+        assert any(c[10] for c in table if (c[1], c[2]) == (dtype, D)) and any(not c[10] for c in table if (c[1], c[2]) == (dtype, D))
+    mis = [c for c in table if c[12]]
+    assert {c[1] == "f32" for c in mis} == {True, False} and all(c[7] % 8 == 0 for c in mis)
+    assert any(c[1] == "bf16" and c[9].get("scale") == 80.0 for c in table) and any(c[9].get("l2norm_qk") is False for c in table)
+    assert {c[5] for c in table if c[4] == 8} >= {1, 2, 8}
+    for dtype in ("bf16", "f16", "f32"):
+        assert any(c[11] and c[1] == dtype and (c[0][:-len("_offsets")],) == (d[0],) for c in table for d in table), dtype
 
 
 # ---- 4. the dense table reaches every dense form (launch recorder, 256 CUs) ----------------------------------------------------------------
@@ -351,6 +507,59 @@ def test_dense_probe_table_launches_every_dense_form(tmp_path):
     assert NO_MASK <= seen["plain"], sorted(NO_MASK - seen["plain"])
     for side in ("causal_n<m", "causal_n>m"):
         assert DENSE_FORMS <= seen[side], (side, sorted(DENSE_FORMS - seen[side]))
+
+
+def bias_recorder_line(case, cus=256):
+    """the launch recorder's input line of a BIAS_CASES entry: bias field 1 for a per-head bias, 2 for a per-batch one"""
+    name, dtype, D, B, H, Hk, N, M, variant, kw, batch = case[:11]
+    scale, l2 = VP.probe_scale(kw)
+    return R.line(cus, W.DTYPE_CODE[dtype], D, B, H, Hk, N, M, int(variant.startswith("causal")), int(variant == "mask"), 2 if batch else 1, int(l2), 1,
+                  scale)
+
+
+def golden_bias_forms(cus=256):
+    """{form label: set of "full" / "causal"} over the dense lines of the golden file that carry a bias at `cus` CUs"""
+    out = {}
+    for ln in open(R.GOLDEN):
+        f = ln.split(" |", 1)[0].split()
+        if "varlen" in f or int(f[0]) != cus or f[10] == "0":
+            continue
+        for label in forms(ln):
+            out.setdefault(label, set()).add("causal" if f[8] == "1" else "full")
+    return out
+
+
+@pytest.mark.skipif(shutil.which("g++") is None or not os.path.isdir("/opt/rocm/include"), reason="needs g++ and the HIP headers")
+def test_bias_probe_table_launches_every_form_a_bias_can_take(tmp_path):
+    """the bias table at 256 CUs against the golden file: every form label any bias line of tests/golden/dispatch_launches.txt launches
+    at 256 CUs is launched by the table -- with a bias alone, with a key mask, and, where the golden file shows the label under causal at
+    all, under causal at N < M and at N > M (the split-key dQ launch it shows without causal only: with a bias the dispatch gives it to no
+    causal problem of a size this table allows) -- and by a per-batch bias at least once per kernel; every (dtype, D) launches bwd_dbias
+    per-head and per-batch, every case launches it"""
+    assert os.path.exists(R.LIB), "libfcsa_hip.so is not built"
+    want = golden_bias_forms()
+    assert {"fwd:Rows8", "fwd:KSplit8", "fwd:Waves4", "dq:Waves8", "dq:KSplit8", "dq:Waves4", "dq:split-key", "dkv:QSplit8"} <= set(want), sorted(want)
+    log = R.record(R.build_recorder(tmp_path), R.LIB, [bias_recorder_line(c) for c in VP.BIAS_CASES]).splitlines()
+    assert len(log) == len(VP.BIAS_CASES) and not any(" rc " in ln for ln in log)
+    seen = {v: set() for v in VP.BIAS_VARIANTS}
+    per_batch, dbias = set(), set()
+    for case, ln in zip(VP.BIAS_CASES, log):
+        name, dtype, D, B, H, Hk, N, M, variant = case[:9]
+        assert (N < M) == (variant != "causal_n>m") or not variant.startswith("causal"), name
+        seen[variant] |= forms(ln)
+        assert f"bwd_dbias<{dict(f32='f', f16='h', bf16='b')[dtype]},{D}>" in ln, name
+        dbias.add((dtype, D, case[10]))
+        if case[10]:
+            per_batch |= forms(ln)
+    for label, where in sorted(want.items()):
+        for variant in VP.BIAS_VARIANTS:
+            if variant.startswith("causal") and "causal" not in where:
+                continue
+            assert label in seen[variant], (label, variant)
+    assert {lb.split(":")[0] for lb in per_batch} == {"fwd", "dq", "dkv"}, sorted(per_batch)
+    for dtype, D in VP.BIAS_TYPES:
+        assert {(dtype, D, False), (dtype, D, True)} <= dbias, (dtype, D)
+    assert {"dkv:group-slabs", "dkv:single-headed"} <= seen["plain"] | seen["mask"] | seen["causal_n<m"] | seen["causal_n>m"]
 
 
 # ---- 5. the decode table launches what its docstrings say (decode launch recorder, 256 CUs) -------------------------------------------------

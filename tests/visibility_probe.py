@@ -35,6 +35,22 @@ operand: 4 * eps.  float32: the rtol of FWD_TOL and GRAD_TOL of tests/tolerances
 logit + ln cnt with the logit taken from the operands the kernels feed the S product: the dtype's rounding of c1 = scale *
 log2(e) (q^ = e_0, so c1 q^ is c1) times c, back in natural units; without l2norm_qk scale * c.
 
+The bias probe (`bias_vis`, `BIAS_CASES`, `run_dense_bias`).  attn_bias is -inf where a seeded pattern hides the pair and a per-(slice, row)
+integer c[s, i] in -2 .. 2 (exact in every dtype; all 0 on an "offsets" case) where it shows it.  A constant per row leaves the softmax
+uniform over vis_eff = pattern & geometry (causal, key mask), so o, dq, dk, dv keep the expectation above -- one `expected` per slice, dk /
+dv of a K/V head summed over its group's slices -- while the multiply by log2(e) and both exponent regimes run on finite values and a read
+from the wrong row shifts a whole row of weights.  Every slice has its own pattern (30 % random; hidden six-column runs across the 32-,
+64-, 128-, 256-key edges and six-row runs across the 32-, 128-, 256-row edges, one visible pair inside, shifting with row / column /
+slice), so an off-by-one of any of the three indices changes the visible set.  On these inputs dS does not depend on batch or head:
+
+    d_bias[s, i, j] = R dS_s[i, j],   R = B (per-head bias) or H (per-batch bias),   mag = R P (dP + delta)
+
+and a hidden pair has expectation and mag exactly 0: the kernel must write 0 up to tiny.  Bar of d_bias: the row sum of the rounded P~
+(eps / 2), delta from a rounded o (eps / 2 delta) and the one rounding of the store into the bias dtype (eps / 2) are <= 1.5 eps mag to
+first order; 4 eps leaves a factor ~2.7 (float32: the rtol of GRAD_TOL).  float16: the smallest non-zero |d_bias| is delta_i / cnt_i,
+~3.5e-6 at 1100 keys and below tiny = 6.1e-5, so a float16 case multiplies do by a power of two g (exact; every gradient expectation
+scales by it) chosen FROM THE EXPECTATION so that the smallest non-zero |d_bias| is >= 16 tiny.
+
 `decidable`: whether flipping one boundary pair of vis moves the float64 expectation of a quantity by >= 1.5 * bar * mag in some element.
 8 significant bits separate about 1 / (1.5 * bar) keys per feature: ~40 D visible keys for o and ~20 (D - 1) for gradients in bf16.
 """
@@ -61,7 +77,7 @@ def tiny(dtype):
 
 
 def bar(dtype, quantity):
-    """the relative bar of o / dq / dk / dv (module docstring)"""
+    """the relative bar of o / dq / dk / dv / dbias (module docstring)"""
     if dtype == "f32":
         return T.FWD_TOL["f32"][1] if quantity == "o" else T.GRAD_TOL["f32"]
     return (2 if quantity == "o" else 4) * eps(dtype)
@@ -158,8 +174,8 @@ def expected(vis, D, dtype, scale=8.0, l2norm_qk=True, kpos=None, grads=True, qp
     """float64 attention over vis[i, j] on the cone inputs with r = m = 1.  kpos: the keys' positions (default 0 .. M - 1; a shared prefix
     passes prefix positions followed by own positions); qpos: the queries' positions (default i + M - N, the bottom-right alignment: the
     query's diagonal key carries its class).  Returns a dict: o [N, D], lse [N]; with grads dq [N, D], dk, dv [M, D] of ONE query
-    head (dk, dv of a K/V head are the sum over its query group: G times these), and mag_* for every quantity.  Rows without a visible key
-    give o = 0, lse = -inf and contribute no gradient."""
+    head (dk, dv of a K/V head are the sum over its query group: G times these), ds [N, M] (dS = P (dP - delta): what one (batch, head) adds
+    to d_bias) and mag_* for every quantity.  Rows without a visible key give o = 0, lse = -inf and contribute no gradient."""
     vis = np.asarray(vis, bool)
     N, M = vis.shape
     kpos = np.arange(M) if kpos is None else np.asarray(kpos)
@@ -190,12 +206,13 @@ def expected(vis, D, dtype, scale=8.0, l2norm_qk=True, kpos=None, grads=True, qp
     if l2norm_qk:
         dq, mag_dq = _l2_backward(dq, mag_dq, Q, 1.0)
         dk, mag_dk = _l2_backward(dk, mag_dk, K, math.sqrt(2.0))
-    out.update(dq=dq, mag_dq=mag_dq, dk=dk, mag_dk=mag_dk, dv=dv, mag_dv=dv)
+    out.update(dq=dq, mag_dq=mag_dq, dk=dk, mag_dk=mag_dk, dv=dv, mag_dv=dv, ds=dS, mag_ds=magS)
     return out
 
 
-def expected_autograd(vis, D, dtype, scale=8.0, l2norm_qk=True):
-    """the same o, dq, dk, dv from torch float64 autograd through the l2norm: the closed form's cross-check (CPU test)"""
+def expected_autograd(vis, D, dtype, scale=8.0, l2norm_qk=True, bias=None):
+    """the same o, dq, dk, dv from torch float64 autograd through the l2norm: the closed form's cross-check (CPU test).  bias [N, M]
+    (0 / c_i / -inf): added to the logits as a leaf before the fill of vis (the geometry); its gradient comes back as d_bias"""
     vis = torch.as_tensor(np.asarray(vis, bool))
     N, M = vis.shape
     c = cone(dtype)
@@ -209,12 +226,19 @@ def expected_autograd(vis, D, dtype, scale=8.0, l2norm_qk=True):
     q, k, v = (t.requires_grad_() for t in (q, k, v))
     # the normalised keys are c (e_0 + e_.) with the ROUNDED c: the l2norm's Jacobian at the unit vector, times c sqrt(2)
     qh, kh = (q / q.norm(dim=-1, keepdim=True), k / k.norm(dim=-1, keepdim=True) * (c * math.sqrt(2.0))) if l2norm_qk else (q, k)
-    s = (scale * qh @ kh.T).masked_fill(~vis, float("-inf"))
-    some = vis.any(1, keepdim=True)
+    s = scale * qh @ kh.T
+    if bias is not None:
+        bias = torch.as_tensor(np.asarray(bias, np.float64)).requires_grad_()
+        s = s + bias
+    s = s.masked_fill(~vis, float("-inf"))
+    some = torch.isfinite(s).any(1, keepdim=True)
     p = torch.where(some, torch.softmax(torch.where(some, s, torch.zeros_like(s)), -1), torch.zeros_like(s))
     o = p @ v
     o.backward(do)
-    return dict(o=o.detach().numpy(), dq=q.grad.numpy(), dk=k.grad.numpy(), dv=v.grad.numpy())
+    out = dict(o=o.detach().numpy(), dq=q.grad.numpy(), dk=k.grad.numpy(), dv=v.grad.numpy())
+    if bias is not None:
+        out["d_bias"] = bias.grad.numpy()
+    return out
 
 
 # ---- inputs ---------------------------------------------------------------------------------------------------------------------------------
@@ -488,6 +512,135 @@ def dense_plain_vis(case):
     return vis_dense(N, M, causal=causal), None, causal
 
 
+# ---- the bias probe: attn_bias as a per-(slice, query, key) visibility ---------------------------------------------------------------------
+
+def bias_vis(owners, N, M, D, causal, seed, mask=None):
+    """the bias pattern, boolean [owners, N, M] (owners: H for a per-head bias, B for attn_bias_batch_dim=True): True where the bias is
+    finite.  Every slice has its own seeded pattern: ~30 % of the pairs hidden at random; hidden runs of six columns across the 32-, 64-,
+    128- and 256-key edges with one visible key inside, the run's position shifting with the row (and the slice); the same kind of run
+    along the rows across the 32-, 128- and 256-row edges, shifting with the column; the last column and the last row drawn on their own.
+    As in key_mask, every row that the geometry (causal, the key mask if any) leaves a key of its own class (i + M - N) % D keeps one
+    visible (without it dS of the row is 0 and the row decides nothing)."""
+    rng = np.random.default_rng(seed)
+    vis = rng.random((owners, N, M)) > 0.3
+    rows, cols = np.arange(N), np.arange(M)
+    for s in range(owners):
+        for edge in (32, 64, 128, 256):
+            if edge + 3 < M:
+                start = edge - 4 + (rows + s) % 3                       # the run [start, start + 6) crosses the edge for every shift
+                for t in range(6):
+                    vis[s, rows, start + t] = False
+                vis[s, rows, start + 1 + (rows // 3 + s + seed) % 4] = True
+        for edge in (32, 128, 256):
+            if edge + 3 < N:
+                start = edge - 4 + (cols + s) % 3
+                for t in range(6):
+                    vis[s, start + t, cols] = False
+                vis[s, start + 1 + (cols // 3 + s + seed) % 4, cols] = True
+        vis[s, :, M - 1] = rng.random(N) > 0.5
+        vis[s, N - 1, :] = rng.random(M) > 0.5
+    geom = vis_dense(N, M, causal, mask=mask)
+    cls = (rows + M - N) % D
+    own = geom & (cols[None, :] % D == cls[:, None])                    # the keys of each row's own class that the geometry leaves it
+    for s in range(owners):
+        for i in np.flatnonzero(own.any(1) & ~(vis[s] & own).any(1)):
+            cand = np.flatnonzero(own[i])
+            vis[s, i, cand[int(rng.integers(len(cand)))]] = True
+    return vis
+
+
+def bias_rows(owners, N, seed, offsets=False):
+    """c[s, i]: the finite bias value of row i of slice s, an integer in -2 .. 2 (exact in every dtype); all 0 on an "offsets" variant"""
+    c = np.random.default_rng(seed + 1).integers(-2, 3, (owners, N))
+    return np.zeros_like(c) if offsets else c
+
+
+def bias_values(vis_b, c):
+    """the bias as float64 [owners, N, M]: c[s, i] where the pattern shows the pair, -inf where it hides it"""
+    return np.where(vis_b, c[:, :, None].astype(np.float64), -np.inf)
+
+
+def _bias_shape(variant, L, other):
+    """(N, M) of a bias case from a tiled length L and the other side: causal variants order them, the others keep L on the query side"""
+    if variant == "causal_n<m":
+        return min(L, other), max(L, other) + (L == other)
+    if variant == "causal_n>m":
+        return max(L, other) + (L == other), min(L, other)
+    return L, other
+
+
+# (dQ and dK/dV choose differently for rows <= 128 bytes and wider; bwd_dbias_kernel runs two waves per SIMD up to 128-byte rows, one above)
+BIAS_TYPES = (("bf16", 64), ("f16", 128), ("f32", 32), ("bf16", 32), ("f16", 96), ("f16", 16), ("f32", 128))
+BIAS_VARIANTS = ("plain", "causal_n<m", "causal_n>m", "mask")
+# key lengths of the read and write paths: M % 8 == 0, M % 4 == 0 only, odd (1104 / 1100 / 1101 and 31 / 33 are added by hand below)
+BIAS_KEYS = (128, 132, 127, 256, 260, 257, 255, 129)
+
+
+def _bias_cases():
+    """The bias table.  id, dtype, D, B, H, Hk, N, M, variant, kwargs, per-batch bias, offsets variant (all c = 0), misaligned pointer.
+    Grids as in _dense_cases: "full" B 8 / H 30 around N 256 (the 8-wave forms), "small" B 1 / H 8 (4-wave and key-split forms), "split"
+    257 x ~1100 (the split-key dQ launch) and ~600 x ~300 (the query-split dK/dV); test_visibility_probe_cpu.py holds the launches against
+    the bias lines of tests/golden/dispatch_launches.txt.  Every case is decided by o, dv and d_bias; dq is compared at its bar but makes
+    no single-pair claim here: among 256 sampled flips of a random two-dimensional pattern some flip almost surely hits a key that shares
+    its feature 1 + j % (D - 1) with the row's diagonal key, whose term is cnt times larger (the limit key masks already have).  d_bias
+    carries the claim in dq's place: a flipped pair moves it between exactly 0 and a value above 16 tiny."""
+    out, i = [], 0
+
+    def add(tag, dtype, D, B, H, Hk, N, M, variant, kw=None, batch=False, offsets=False, misaligned=False):
+        name = f"{dtype}_d{D}_{tag}_{variant}_n{N}m{M}_b{B}h{H}k{Hk}" + ("_perbatch" if batch else "") + ("_offsets" if offsets else "") + \
+               ("_misaligned" if misaligned else "")
+        out.append((name, dtype, D, B, H, Hk, N, M, variant, dict(kw or {}), batch, offsets, misaligned))
+
+    for ti, (dtype, D) in enumerate(BIAS_TYPES):
+        for gi, grid in enumerate(("full", "small")):
+            for vi, variant in enumerate(BIAS_VARIANTS):
+                L, K = LENGTHS[i % len(LENGTHS)], BIAS_KEYS[i % len(BIAS_KEYS)]
+                if D >= 64 and (i % 3 == 0 or (variant == "mask" and K < 2 * D)):      # (key_mask needs two keys per class to hide one)
+                    K += 148
+                N, M = _bias_shape(variant, L, K)
+                batch = vi == (ti + 2 * gi) % 4                          # one per-batch bias per dtype and grid, the variant rotating
+                B, H = (8, 30) if grid == "full" else (2 if batch else 1, 8)
+                Hk = H if grid == "full" else (H, 2, 1)[i % 3]
+                add(grid, dtype, D, B, H, Hk, N, M, variant, batch=batch)
+                i += 1
+    # the split-key dQ launch: few heads, 257 queries against ~1100 keys of each alignment class (no causal: the dispatch gives a problem
+    # with a bias no causal split launch at sizes this table allows, and the golden file shows none)
+    add("split", "bf16", 64, 1, 8, 8, 257, 1104, "plain")
+    add("split", "f16", 128, 1, 8, 2, 257, 1100, "mask")
+    add("split", "f32", 32, 2, 8, 8, 257, 1101, "plain", batch=True)
+    add("long", "f16", 16, 1, 8, 1, 255, 1100, "plain")
+    # the query-split 8-wave dK/dV (N >= 512)
+    add("qsplit", "bf16", 64, 1, 8, 8, 601, 300, "plain")
+    add("qsplit", "bf16", 64, 1, 8, 2, 600, 257, "mask")
+    add("qsplit", "bf16", 64, 1, 8, 8, 521, 700, "causal_n<m")
+    add("qsplit", "bf16", 64, 1, 8, 1, 601, 300, "causal_n>m")
+    add("qsplit", "f16", 16, 2, 8, 8, 1100, 257, "causal_n>m", batch=True)
+    add("qsplit", "bf16", 32, 1, 8, 8, 601, 132, "plain")
+    # no whole 32-key block, and one block plus one key (D <= M: every row's class has a key)
+    add("small", "f16", 16, 1, 8, 8, 129, 31, "plain")
+    add("small", "f16", 16, 1, 8, 2, 127, 33, "mask")
+    add("small", "bf16", 32, 1, 8, 8, 30, 33, "causal_n<m")
+    add("small", "f32", 32, 2, 8, 8, 129, 33, "causal_n>m", batch=True)
+    add("full", "bf16", 32, 8, 30, 30, 255, 33, "plain")
+    # a bias whose address is no multiple of 16 bytes, at M % 8 == 0: the scalar read path in every kernel
+    add("full", "bf16", 64, 8, 30, 30, 129, 256, "plain", misaligned=True)
+    add("small", "f16", 128, 1, 8, 8, 257, 128, "causal_n>m", misaligned=True)
+    add("small", "f32", 32, 1, 8, 2, 127, 128, "plain", misaligned=True)
+    # the per-row shift in bf16 (scale 80: beyond the constant shift's room), inputs already normalised
+    add("per_row", "bf16", 64, 1, 8, 2, 129, 260, "plain", dict(scale=80.0))
+    add("per_row", "bf16", 64, 8, 30, 30, 255, 257, "causal_n<m", dict(scale=80.0))
+    add("nol2", "bf16", 128, 1, 8, 1, 257, 132, "causal_n>m", dict(l2norm_qk=False, scale=1.0))
+    add("nol2", "f16", 32, 1, 8, 8, 127, 256, "mask", dict(l2norm_qk=False, scale=1.0))
+    # all finite values 0 (the reference's usual additive mask), next to the default with per-row constants
+    for dtype, D, M in (("bf16", 64, 260), ("f16", 128, 257), ("f32", 32, 128)):
+        for offsets in (False, True):
+            add("pair", dtype, D, 1, 8, 2, 129, M, "plain", offsets=offsets)
+    return out
+
+
+BIAS_CASES = _bias_cases()
+
+
 # Decode calls without a window.  page 0: contiguous.  lens: cache_seqlens before the append (0, 1, page -+ 1, and capacity - appended);
 # counts: None for a rectangular q of N rows, else the per-sequence query counts of a ragged step (appended: every query brings its key).
 # id, dtype, D, H, Hk, N, capacity, page, lens, appended keys (rectangular), counts, causal, fp8, kwargs
@@ -585,6 +738,87 @@ def run_dense(dtype, D, B, H, Hk, N, M, scale, l2norm_qk, device, causal=False, 
                 ("dk", "dense", k.grad * m.to(device)[..., None], G * e["dk"], G * e["mag_dk"]),
                 ("dv", "dense", v.grad, G * e["dv"], G * e["mag_dv"])]
     return out
+
+
+def bias_case_vis(case):
+    """(effective visibility [owners, N, M], pattern [owners, N, M], geometry [N, M], key mask or None, causal) of a BIAS_CASES entry"""
+    name, dtype, D, B, H, Hk, N, M, variant, kw, batch = case[:11]
+    seed = sum(map(ord, name))
+    causal = variant.startswith("causal")
+    mask = key_mask(M, seed, D) if variant == "mask" else None
+    geom = vis_dense(N, M, causal, mask=mask)
+    pattern = bias_vis(B if batch else H, N, M, D, causal, seed, mask)
+    return pattern & geom[None], pattern, geom, mask, causal
+
+
+def bias_expected(case, vis_eff=None, g=None):
+    """the float64 expectation of a BIAS_CASES entry from one `expected` per slice: o, dq [owners, N, D]; dk, dv [Hk, M, D] (per-head
+    bias: the sum over the query heads of the group of their slices) or [B, M, D] (per-batch bias: G times the slice); d_bias [owners, N,
+    M] = R dS_s with R the size of the reduced index (B for a per-head bias, H for a per-batch one); mag_* likewise.  "g": the power of two
+    float16 cases multiply do by (every gradient expectation here is already multiplied by it) so that the smallest non-zero |d_bias| is at
+    least 16 tiny -- computed from the expectation alone (or given: the teeth tests hold a mutated pattern to the factor of the right one); 1
+    in the other dtypes, whose tiny is ~1e-38."""
+    name, dtype, D, B, H, Hk, N, M, variant, kw, batch = case[:11]
+    scale, l2 = probe_scale(kw)
+    if vis_eff is None:
+        vis_eff = bias_case_vis(case)[0]
+    per = [expected(v, D, dtype, scale, l2) for v in vis_eff]
+    st = lambda key: np.stack([e[key] for e in per])
+    R, G = (H if batch else B), H // Hk
+    out = dict(o=st("o"), mag_o=st("mag_o"), dq=st("dq"), mag_dq=st("mag_dq"), d_bias=R * st("ds"), mag_d_bias=R * st("mag_ds"))
+    for key in ("dk", "mag_dk", "dv", "mag_dv"):
+        x = st(key)
+        out[key] = G * x if batch else x.reshape(Hk, G, M, D).sum(1)
+    nz = np.abs(out["d_bias"][out["d_bias"] != 0])
+    if g is None:
+        g = 2.0 ** max(0, math.ceil(math.log2(16 * tiny(dtype) / nz.min()))) if dtype == "f16" and nz.size else 1.0
+    for key in list(out):
+        if key not in ("o", "mag_o"):
+            out[key] = out[key] * g
+    out["g"] = g
+    return out
+
+
+def bias_tensor(case, pattern, device="cpu", grads=True):
+    """the bias of a case in its dtype, a leaf (grads: requiring grad): -inf / c[s, i]; a misaligned case makes it a contiguous view one element into a larger
+    buffer, so that its address is no multiple of 16 bytes (the kernels' vector paths must not be taken)"""
+    name, dtype = case[:2]
+    offsets, misaligned = case[11:13]
+    owners, N, M = pattern.shape
+    vals = torch.as_tensor(bias_values(pattern, bias_rows(owners, N, sum(map(ord, name)), offsets))).to(DT[dtype])
+    if not misaligned:
+        return vals.to(device).requires_grad_(grads)
+    buf = torch.zeros(owners * N * M + 8, dtype=DT[dtype], device=device)
+    view = buf[1:1 + owners * N * M].view(owners, N, M)
+    view.copy_(vals)
+    assert view.is_contiguous() and view.data_ptr() % 16 != 0
+    return view.detach().requires_grad_(grads)
+
+
+def run_dense_bias(case, device, grads=True):
+    """flash_cosine_sim_attention with attn_bias on the dense probe: (comparisons o, dq, dk, dv, d_bias; the bias leaf; the geometry's
+    visibility [N, M]).  device "cpu": the forward-only path (grads=False)"""
+    F = _F()
+    name, dtype, D, B, H, Hk, N, M, variant, kw, batch = case[:11]
+    scale, l2 = probe_scale(kw)
+    vis_eff, pattern, geom, mask, causal = bias_case_vis(case)
+    e = bias_expected(case, vis_eff)
+    q, k, v, do, r, m = probe_inputs(dtype, B, H, Hk, N, M, D, l2, len(name))
+    q, k, v, do = (t.to(device) for t in (q, k, v, do * e["g"]))
+    bias = bias_tensor(case, pattern, device, grads)
+    if grads:
+        q, k, v = (t.requires_grad_() for t in (q, k, v))
+    mask_t = None if mask is None else torch.as_tensor(mask).to(device).expand(B, M).contiguous()
+    o = F.flash_cosine_sim_attention(q, k, v, mask=mask_t, attn_bias=bias, attn_bias_batch_dim=batch, scale=scale, causal=causal, l2norm_qk=l2)
+    lead = (lambda x: x[:, None]) if batch else (lambda x: x[None])                       # a slice per batch element / per head
+    out = [("o", "bias", o.detach(), lead(e["o"]), lead(e["mag_o"]))]
+    if grads:
+        o.backward(do)
+        out += [("dq", "bias", q.grad * r.to(device)[..., None], lead(e["dq"]), lead(e["mag_dq"])),
+                ("dk", "bias", k.grad * m.to(device)[..., None], lead(e["dk"]), lead(e["mag_dk"])),
+                ("dv", "bias", v.grad, lead(e["dv"]), lead(e["mag_dv"])),
+                ("dbias", "bias", bias.grad, e["d_bias"], e["mag_d_bias"])]
+    return out, bias, geom
 
 
 def run_packed(dtype, D, H, Hk, lens_q, lens_k, scale, l2norm_qk, device, causal=False, window=(-1, -1), max_seqlen=None, seed=0, grads=True):
