@@ -5,7 +5,7 @@ from .ops import (flash_cosine_sim_attention, flash_cosine_sim_attention_local, 
                   flash_cosine_sim_attention_with_kvcache, flash_cosine_sim_attention_varlen_with_kvcache,
                   flash_cosine_sim_attention_prefill_with_kvcache,
                   flash_cosine_sim_attention_step_with_kvcache, flash_cosine_sim_attention_tree_with_kvcache,
-                  flash_cosine_sim_attention_alibi_with_kvcache,
+                  flash_cosine_sim_attention_alibi_with_kvcache, flash_cosine_sim_attention_alibi,
                   kvcache_keep_accepted,
                   flash_cosine_sim_attention_with_shared_prefix, merge_attention_states,
                   flash_cosine_sim_attention_with_lse, merge_attention_states_with_grad,
@@ -17,7 +17,7 @@ __all__ = ['flash_cosine_sim_attention', 'flash_cosine_sim_attention_local', 'fl
            'flash_cosine_sim_attention_with_kvcache', 'flash_cosine_sim_attention_varlen_with_kvcache',
            'flash_cosine_sim_attention_prefill_with_kvcache',
            'flash_cosine_sim_attention_step_with_kvcache', 'flash_cosine_sim_attention_tree_with_kvcache',
-           'flash_cosine_sim_attention_alibi_with_kvcache',
+           'flash_cosine_sim_attention_alibi_with_kvcache', 'flash_cosine_sim_attention_alibi',
            'kvcache_keep_accepted',
            'flash_cosine_sim_attention_with_shared_prefix', 'merge_attention_states',
            'flash_cosine_sim_attention_with_lse', 'merge_attention_states_with_grad',

@@ -103,7 +103,8 @@ EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fc
            "fcsa_forward_kvcache_lse", "fcsa_merge_states", "fcsa_forward_kvcache_prefill",
            "fcsa_attention_lse", "fcsa_backward_state", "fcsa_merge_states_backward",
            "fcsa_forward_kvcache_step", "fcsa_forward_kvcache_step_workspace_bytes",
-           "fcsa_forward_kvcache_tree", "fcsa_kvcache_compact", "fcsa_forward_kvcache_alibi")
+           "fcsa_forward_kvcache_tree", "fcsa_kvcache_compact", "fcsa_forward_kvcache_alibi",
+           "fcsa_forward_alibi", "fcsa_backward_alibi", "fcsa_forward_alibi_workspace_bytes", "fcsa_backward_alibi_workspace_bytes")
 
 _lib = None
 
@@ -216,6 +217,14 @@ def load():
         lib.fcsa_forward_kvcache_alibi.argtypes = [C.POINTER(ForwardArgs), C.POINTER(KvCache), C.POINTER(Varlen), C.POINTER(KvCacheQuant),
                                                    C.POINTER(Window), C.POINTER(KvCacheStep), C.POINTER(Alibi), C.POINTER(LseOut)]
         lib.fcsa_forward_kvcache_alibi.restype = C.c_int
+    if hasattr(lib, "fcsa_forward_alibi"):      # (likewise: an FCSA_LIB build from before the position bias of the training calls)
+        lib.fcsa_forward_alibi.argtypes = [C.POINTER(ForwardArgs), C.POINTER(Varlen), C.POINTER(Window), C.POINTER(Alibi)]
+        lib.fcsa_forward_alibi.restype = C.c_int
+        lib.fcsa_backward_alibi.argtypes = [C.POINTER(BackwardArgs), C.POINTER(Varlen), C.POINTER(Window), C.POINTER(Alibi)]
+        lib.fcsa_backward_alibi.restype = C.c_int
+        for fn in (lib.fcsa_forward_alibi_workspace_bytes, lib.fcsa_backward_alibi_workspace_bytes):
+            fn.argtypes = [C.POINTER(Problem), C.POINTER(Varlen), C.POINTER(Window)]
+            fn.restype = C.c_size_t
     if hasattr(lib, "fcsa_forward_kvcache_tree"):      # (likewise: an FCSA_LIB build from before tree attention)
         lib.fcsa_forward_kvcache_tree.argtypes = [C.POINTER(ForwardArgs), C.POINTER(KvCache), C.POINTER(Varlen), C.POINTER(KvCacheQuant),
                                                   C.POINTER(TreeMask), C.POINTER(LseOut)]

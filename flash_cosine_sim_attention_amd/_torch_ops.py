@@ -129,6 +129,23 @@ def _register_fakes():
           groups, window_left, window_right):
         return q.new_empty(q.shape), k.new_empty(k.shape), v.new_empty(v.shape)
 
+    # the training calls with a linear position bias (namespace fcsa_alibi_train): the shapes of the fcsa_state ops without the lse
+    @torch.library.register_fake("fcsa_alibi_train::forward")
+    def _(q, k, v, alibi_slopes, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, scale, causal, l2norm_qk, groups, window_left,
+          window_right, need_backward):
+        rows_q, rows_k = _state_rows(q, k)
+        return (q.new_empty(q.shape), *_saved_state(q, rows_q, rows_k, q.shape[-1], l2norm_qk, groups, need_backward))
+
+    @torch.library.register_fake("fcsa_alibi_train::attention")
+    def _(q, k, v, alibi_slopes, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, scale, causal, l2norm_qk, groups, window_left,
+          window_right):
+        return q.new_empty(q.shape)
+
+    @torch.library.register_fake("fcsa_alibi_train::backward")
+    def _(d_out, o, inv_l, q, k, v, alibi_slopes, cu_seqlens_q, cu_seqlens_k, qn, kn, rq, rk, max_seqlen_q, max_seqlen_k, scale, causal,
+          l2norm_qk, groups, window_left, window_right):
+        return q.new_empty(q.shape), k.new_empty(k.shape), v.new_empty(v.shape)
+
     @torch.library.register_fake("fcsa_state::merge_state")
     def _(os, lses):
         return os[0].new_empty(os[0].shape), os[0].new_empty(os[0].shape[:-1], dtype=torch.float32)

@@ -84,7 +84,7 @@ def attention_forward_cpu(q, k, v, mask=None, attn_bias=None, scale=8.0, groups=
     tail_mask: bool [N, T], T <= M (a tree step, `tree_tail`): query i sees every key before the last T and key M - T + t iff tail_mask[i, t].
     It takes no causal, window, mask or bias.  A row block stops at the last key any of its rows sees, as a causal one does, and an
     invisible logit is -inf either way, so a lower-triangular mask gives the causal call's bits and a full one the plain call's.
-    alibi_slopes: float32 [H] (the cached calls' linear position bias): the logit of key j for query i gains -slope[h] * |i + (M - N) - j|
+    alibi_slopes: float32 [H], or [B, H] (the linear position bias of the cached calls and of `flash_cosine_sim_attention_alibi`): the logit of key j for query i gains -slope[h] * |i + (M - N) - j|
     after the scale, and is part of the lse.  It is computed per block, never materialised, and -- unlike attn_bias -- combines with a
     window; it takes no tail_mask and no attn_bias."""
     w_left, w_right = window_sides(window_size, causal)
@@ -148,7 +148,9 @@ def attention_forward_cpu(q, k, v, mask=None, attn_bias=None, scale=8.0, groups=
             ii = torch.arange(r0, r1).unsqueeze(1) + offset
             jj = torch.arange(c0, c1).unsqueeze(0)
             if alibi_slopes is not None:
-                logits = logits - alibi_slopes.float().reshape(1, -1, 1, 1) * (ii - jj).abs().float()
+                slopes = alibi_slopes.float()
+                slopes = slopes.reshape(1, -1, 1, 1) if slopes.dim() == 1 else slopes.reshape(slopes.shape[0], slopes.shape[1], 1, 1)
+                logits = logits - slopes * (ii - jj).abs().float()
             if w_right is not None and c1 - 1 > r0 + offset + w_right:           # the block touches the (right) diagonal
                 visible = (jj <= ii + w_right)
             if w_left is not None and c0 < r1 - 1 + offset - w_left:              # ... the window's left edge
@@ -180,10 +182,10 @@ def attention_forward_cpu(q, k, v, mask=None, attn_bias=None, scale=8.0, groups=
 
 
 def attention_forward_varlen_cpu(q, k, v, cu_seqlens_q, cu_seqlens_k, scale=8.0, groups=1, causal=False, l2norm_qk=True,
-                                 window_size=(-1, -1)):
+                                 window_size=(-1, -1), alibi_slopes=None):
     """Forward-only path of `flash_cosine_sim_attention_varlen` on host tensors: packed q [total_q, H, D], k / v [total_k, Hk, D] and
     validated host tables; each sequence runs through `attention_forward_cpu` as a batch-1 problem, so its rows are exactly what the
-    dense CPU path gives for that sequence alone."""
+    dense CPU path gives for that sequence alone.  alibi_slopes: float32 [H] or [sequences, H], per sequence as in `attention_forward_cpu`."""
     out = torch.zeros_like(q)
     cq, ck = cu_seqlens_q.tolist(), cu_seqlens_k.tolist()
     for s in range(len(cq) - 1):
@@ -192,7 +194,9 @@ def attention_forward_varlen_cpu(q, k, v, cu_seqlens_q, cu_seqlens_k, scale=8.0,
         vs = v[ck[s]:ck[s + 1]].permute(1, 0, 2).unsqueeze(0)
         if qs.shape[2] == 0:
             continue
-        o = attention_forward_cpu(qs, ks, vs, scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, window_size=window_size)
+        slopes = None if alibi_slopes is None else (alibi_slopes if alibi_slopes.dim() == 1 else alibi_slopes[s])
+        o = attention_forward_cpu(qs, ks, vs, scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, window_size=window_size,
+                                  alibi_slopes=slopes)
         out[cq[s]:cq[s + 1]] = o[0].permute(1, 0, 2)
     return out
 

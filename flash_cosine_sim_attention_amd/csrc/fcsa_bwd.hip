@@ -52,11 +52,12 @@ FCSA_TRACE_SITE(dkv)
 // MODE: 0 = every pair valid, 1 = causal diagonal tiles (select per logit), 2 = key mask / ragged tail of a non-causal launch
 // (rank-1 MFMA per block, key_mask_rank1)
 // WIN (sliding window, MODE 1): the select also clears the keys left of the row's window, j < i + dlo
-template <typename T, int D, int MODE, bool BIAS, bool TWO, bool WIN = false>
+// ALIBI (bwd_dq_alibi_kernel): S starts from lc - ab.slope2 * |i + ab.apos - j| (alibi_seed16, fcsa_common.cuh) instead of lc, as in fwd_tile
+template <typename T, int D, int MODE, bool BIAS, bool TWO, bool WIN = false, bool ALIBI = false>
 FCSA_DEV void dq_tile(const char* kt, const char* vt, const FragAddr<T, D>& fa,
                       const u32x4 (&qf)[TileGeom<D, Traits<T>::ES>::KS], const u32x4 (&dof)[TileGeom<D, Traits<T>::ES>::KS],
                       f32x16 (&dq)[TileGeom<D, Traits<T>::ES>::DB], float lc, float delta, const BwdParams& p, uint64_t word,
-                      uint32_t ncm, int i, int j0, int diff, const char* bias_row, int m_lim, int dlo = 0) {
+                      uint32_t ncm, int i, int j0, int diff, const char* bias_row, int m_lim, int dlo = 0, AlibiArg<ALIBI> ab = {}) {
   typedef TileGeom<D, Traits<T>::ES> G;
   typedef Traits<T> TR;
   constexpr bool MASKED = MODE == 1, KEYM = MODE == 2;
@@ -72,8 +73,14 @@ FCSA_DEV void dq_tile(const char* kt, const char* vt, const FragAddr<T, D>& fa,
     // (requests are batched PF k-steps at a time so the live fragments stay within the register budget)
     constexpr int PF = G::KS <= 4 ? G::KS : (G::KS >= 8 && TWO ? 1 : 2);      // (16-bit D = 128 at two waves per SIMD: 256 registers)
     f32x16 s, dp;
+    if constexpr (ALIBI) {
+      alibi_seed16<-1>(s, lc, ab.slope2, i + ab.apos - (j0 + 32 * jb + 4 * fa.hi));
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dp[r] = -delta;
+    } else {
 #pragma unroll
     for (int r = 0; r < 16; ++r) { s[r] = lc; dp[r] = -delta; }  // lc = log2(inv_l) - c2 and -delta ride in as initial values
+    }
     if constexpr (KEYM) s = key_mask_rank1<T>(s, (uint32_t)(word >> (32 * jb)), fa.row_off / G::ROWB, fa.hi);
 #pragma unroll
     for (int k0 = 0; k0 < G::KS; k0 += PF) {
@@ -128,11 +135,11 @@ template <typename T, int D> struct DqPipe {
   }
 };
 
-template <typename T, int D, int MODE, bool WIN = false>
+template <typename T, int D, int MODE, bool WIN = false, bool ALIBI = false>
 FCSA_DEV void dq_tile_pipe(const char* kt, const char* vt, const char* knext, const char* vnext, int next_tile, int t,
                            const FragAddr<T, D>& fa, const u32x4 (&qf)[TileGeom<D, Traits<T>::ES>::KS],
                            const u32x4 (&dof)[TileGeom<D, Traits<T>::ES>::KS], f32x16 (&dq)[TileGeom<D, Traits<T>::ES>::DB],
-                           float lc, float delta, uint64_t word, uint32_t ncm, int i, int j0, int diff, DqPipe<T, D>& pp_, int dlo = 0) {
+                           float lc, float delta, uint64_t word, uint32_t ncm, int i, int j0, int diff, DqPipe<T, D>& pp_, int dlo = 0, AlibiArg<ALIBI> ab = {}) {
   typedef TileGeom<D, Traits<T>::ES> G;
   typedef Traits<T> TR;
   constexpr bool MASKED = MODE == 1, KEYM = MODE == 2;
@@ -146,8 +153,14 @@ FCSA_DEV void dq_tile_pipe(const char* kt, const char* vt, const char* knext, co
     FCSA_FENCE();
     // ---- M1
     f32x16 s, dp;
+    if constexpr (ALIBI) {
+      alibi_seed16<-1>(s, lc, ab.slope2, i + ab.apos - (j0 + 32 * jb + 4 * fa.hi));
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dp[r] = -delta;
+    } else {
 #pragma unroll
     for (int r = 0; r < 16; ++r) { s[r] = lc; dp[r] = -delta; }     // lc = log2(inv_l) - c2 and -delta ride in as initial values
+    }
     if constexpr (KEYM) s = key_mask_rank1<T>(s, (uint32_t)(word >> (32 * jb)), fa.row_off / G::ROWB, fa.hi);
 #pragma unroll
     for (int kk = 0; kk < G::KS; ++kk) s = TR::mfma32(pp_.kfr[kk], qf[kk], s);
@@ -240,9 +253,11 @@ template <typename T, int D, int NW, int BMQ, bool BIAS, bool LEAN, bool RING, b
 // fwd_kernel, KSPLIT): for grids of at most one 128-row workgroup per CU, whose four waves would each have a SIMD to themselves.
 // WIN (bwd_dq_win_kernel; never BIAS / KM, no split): a sliding window, as in fwd_kernel -- every pass runs on the keys of its row tile's
 // band (win_key_window: the split-key sub-problem [k_lo, k_lo + Mk)), tile loops select | plain | select
-template <typename T, int D, int NW, bool BIAS, int SUB, bool TWO, bool KM, bool KSPLIT, bool WIN>
-FCSA_DEV void bwd_dq_body(const std::conditional_t<WIN, BwdWinParams, BwdParams>& p_) {
+// ALIBI (bwd_dq_alibi_kernel; WIN only): the forward's linear position bias, recomputed as the S accumulators' seed (dq_tile)
+template <typename T, int D, int NW, bool BIAS, int SUB, bool TWO, bool KM, bool KSPLIT, bool WIN, bool ALIBI = false>
+FCSA_DEV void bwd_dq_body(const std::conditional_t<WIN, BwdWinParams, BwdParams>& p_, const TrainAlibi* al = nullptr) {
   static_assert(!WIN || (!BIAS && !KM), "sliding window: no bias, the per-logit select");
+  static_assert(!ALIBI || WIN, "linear position bias: the windowed body");
   std::conditional_t<WIN, BwdWinParams, BwdParams> p = p_;      // a varlen launch rebinds it to the workgroup's sequence (varlen_bind); dense launches use it as given
   static_assert(!KSPLIT || (NW == 8 && TWO && SUB == 2 && Traits<T>::ES == 2), "key-split form: 8 waves, two-wave tile, 16 bit, 2 tiles per stage");
   // (same type and value as p.causal: the causal instantiations compile to what they were.  The key-split form's !KM twin is only ever
@@ -267,6 +282,8 @@ FCSA_DEV void bwd_dq_body(const std::conditional_t<WIN, BwdWinParams, BwdParams>
   // (d_bias is not this kernel's business: bwd_dbias_kernel below recomputes the dS tiles of a bias slice and writes it once)
   int bh, pt;
   block_work(blockIdx.x, p.B * p.H, tile_pairs(tile_count(p.N, BM), causal), bh, pt);
+  [[maybe_unused]] AlibiArg<ALIBI> ab;      // ALIBI: slope * log2(e) of this workgroup's (sequence, query head), read before a packed launch rebinds bh
+  if constexpr (ALIBI) ab.slope2 = train_alibi_slope(*al, bh / p.H, bh % p.H);
   if (p.seq.cu_q != nullptr && !varlen_bind<D, Traits<T>::ES>(p, bh, pt, BM, causal, false)) return;
   const int MT = tile_count(p.N, BM);
   const int b = bh / p.H, h = bh % p.H;
@@ -550,12 +567,23 @@ FCSA_DEV void bwd_dq_body(const std::conditional_t<WIN, BwdWinParams, BwdParams>
         if constexpr (MASKED) skip = causal && (j0 > mw + 31 + diff);
         if constexpr (MASKED && WIN) skip = skip || (j0 + BN - 1 < mw + dlo);      // (left of the window of every row of the wave)
         const bool next_here = !last_of_stage;              // the next key tile sits in this stage's buffer
+        if constexpr (ALIBI) {
+          if (!skip) dq_tile_pipe<T, D, tile_mode<MODE>(), WIN, true>(kcur, vcur, next_here ? kcur + TILE_B : kcur, next_here ? vcur + TILE_B : vcur,
+                                                next_here ? t + 1 : -1, t, fa, qf, dof, dq, lc, delta, word, ncm, i, j0, diff, pipe, dlo,
+                                                AlibiArg<true>{ab.slope2, p.M - p.N - k_lo});
+        } else
         if (!skip) dq_tile_pipe<T, D, tile_mode<MODE>(), WIN>(kcur, vcur, next_here ? kcur + TILE_B : kcur, next_here ? vcur + TILE_B : vcur,
                                               next_here ? t + 1 : -1, t, fa, qf, dof, dq, lc, delta, word, ncm, i, j0, diff, pipe, dlo);
       } else if constexpr (MASKED) {
         bool skip = causal && (j0 > mw + 31 + diff);
         if constexpr (WIN) skip = skip || (j0 + BN - 1 < mw + dlo);
+        if constexpr (ALIBI) {
+          if (!skip) dq_tile<T, D, tile_mode<MODE>(), BIAS, TWO, WIN, true>(kcur, vcur, fa, qf, dof, dq, lc, delta, p, word, ncm, i, j0, diff, bias_row, Mk, dlo,
+                                                                         AlibiArg<true>{ab.slope2, p.M - p.N - k_lo});
+        } else
         if (!skip) dq_tile<T, D, tile_mode<MODE>(), BIAS, TWO, WIN>(kcur, vcur, fa, qf, dof, dq, lc, delta, p, word, ncm, i, j0, diff, bias_row, Mk, dlo);
+      } else if constexpr (ALIBI) {
+        dq_tile<T, D, 0, BIAS, TWO, false, true>(kcur, vcur, fa, qf, dof, dq, lc, delta, p, 0, ncm, i, j0, diff, bias_row, Mk, 0, AlibiArg<true>{ab.slope2, p.M - p.N - k_lo});
       } else {
         dq_tile<T, D, 0, BIAS, TWO>(kcur, vcur, fa, qf, dof, dq, lc, delta, p, 0, ncm, i, j0, diff, bias_row, Mk);
       }
@@ -633,6 +661,10 @@ FCSA_DEV void bwd_dq_body(const std::conditional_t<WIN, BwdWinParams, BwdParams>
       bool skip = t >= nt;
       if constexpr (MODE == 1) skip = skip || (causal && j0 > mw + 31 + diff);
       if constexpr (MODE == 1 && WIN) skip = skip || (j0 + BN - 1 < mw + dlo);
+      if constexpr (ALIBI) {
+        if (!skip) dq_tile<T, D, tile_mode<MODE>(), BIAS, TWO, WIN, true>(kcur, vcur, fa, qf, dof, dq, lc, delta, p, word, ncm, i, j0, diff, bias_row, Mk, dlo,
+                                                                       AlibiArg<true>{ab.slope2, p.M - p.N - k_lo});
+      } else
       if (!skip) dq_tile<T, D, tile_mode<MODE>(), BIAS, TWO, WIN>(kcur, vcur, fa, qf, dof, dq, lc, delta, p, word, ncm, i, j0, diff, bias_row, Mk, dlo);
       if (more) dma_wait();
       FCSA_BAR_BEGIN(tr);
@@ -711,6 +743,11 @@ __global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_kernel(const Bw
 template <typename T, int D, int NW, int SUB, bool TWO, bool KSPLIT>
 __global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_win_kernel(const BwdWinParams p_) {
   bwd_dq_body<T, D, NW, false, SUB, TWO, false, KSPLIT, true>(p_);
+}
+// the forms with a linear position bias (launch_backward_dq_alibi): the windowed body again, the slopes as a second argument
+template <typename T, int D, int NW, int SUB, bool TWO, bool KSPLIT>
+__global__ void __launch_bounds__(NW * 64, (TWO ? 2 : 1)) bwd_dq_alibi_kernel(const BwdWinParams p_, const TrainAlibi al) {
+  bwd_dq_body<T, D, NW, false, SUB, TWO, false, KSPLIT, true, true>(p_, &al);
 }
 
 // =============================================================================================
@@ -913,13 +950,15 @@ static hipError_t launch_dbias_t(const BwdParams& p, hipStream_t s) {
 // MODE: 0 / 1 as in dq_tile; 2 = key mask of a non-causal launch: the lanes ARE the keys here (S = Q K^T, columns = keys), so the
 // rank-1 term is ones (A, query rows) x this lane's 0 / -inf (B): `kmb` = the B operand's k-slot-0 register pair, set up once per pass
 // WIN (sliding window, MODE 1): the select also clears the queries past the key's window, i > j - dlo
-template <typename T, int D, int BMQ, int MODE, bool BIAS, bool LEAN = false, bool WIN = false>
+// ALIBI (bwd_dkv_alibi_kernel): the per-query seeds of S gain -ab.slope2 * |i + ab.apos - j| (alibi_add16, fcsa_common.cuh): this lane's row
+// is the key j, its registers the queries i, so position and slope are those of the query row and query head
+template <typename T, int D, int BMQ, int MODE, bool BIAS, bool LEAN = false, bool WIN = false, bool ALIBI = false>
 FCSA_DEV void dkv_tile(const char* qt, const char* dot, const float* lcs, const float* dls, const FragAddr<T, D>& fa,
                        const u32x4 (&kf)[TileGeom<D, Traits<T>::ES>::KS], const u32x4 (&vf)[TileGeom<D, Traits<T>::ES>::KS],
                        f32x16 (&dk)[TileGeom<D, Traits<T>::ES>::DB], f32x16 (&dv)[TileGeom<D, Traits<T>::ES>::DB],
                        const BwdParams& p, uint32_t kmask, uint32_t ncm, int j, int i0, int diff, const char* bias_col, Trace& ts,
                        BiasBlock<T>& bb, char* bscr, const char* bias_blk, bool bvec, int next_i0, int lane, const char* vown = nullptr,
-                       int vrow0 = 0, bool young = false, int dlo = 0) {
+                       int vrow0 = 0, bool young = false, int dlo = 0, AlibiArg<ALIBI> ab = {}) {
   typedef TileGeom<D, Traits<T>::ES> G;
   typedef Traits<T> TR;
   constexpr bool MASKED = MODE == 1, KEYM = MODE == 2;
@@ -950,6 +989,7 @@ FCSA_DEV void dkv_tile(const char* qt, const char* dot, const float* lcs, const 
 #pragma unroll
       for (int e = 0; e < 4; ++e) { s[4 * rq + e] = lc4[e]; dp[4 * rq + e] = nd4[e]; }
     }
+    if constexpr (ALIBI) alibi_add16<1>(s, ab.slope2, i0 + 32 * ib + 4 * fa.hi + ab.apos - j);
     if constexpr (KEYM) s = key_mask_rank1_cols<T>(s, kmask == 0u, fa.hi);
     // (row fragments are requested next to their MFMA here: this kernel sits at its register budget, and
     //  batching the requests as in dq_tile spills)
@@ -1043,12 +1083,12 @@ struct DkvPipe {
 // for the others, phase trace.)  `fresh`: nothing is in flight for this tile (first tile of a pass, or the previous one was skipped).
 // QS (query-split form of the kernel): this wave works on BMQ rows of a staged tile of 2 * BMQ, starting `hq` rows (`hoff` bytes) into it;
 // qt / dot / lcs / dls point at its share already, `nxt` at the next staged tile's start
-template <typename T, int D, int BMQ, int MODE, bool RING = false, bool QS = false, bool WIN = false>
+template <typename T, int D, int BMQ, int MODE, bool RING = false, bool QS = false, bool WIN = false, bool ALIBI = false>
 FCSA_DEV void dkv_tile_pipe(const char* qt, const char* dot, const float* lcs, const float* dls, const FragAddr<T, D>& fa,
                             const u32x4 (&kf)[TileGeom<D, Traits<T>::ES>::KS], const u32x4 (&vf)[TileGeom<D, Traits<T>::ES>::KS],
                             f32x16 (&dk)[TileGeom<D, Traits<T>::ES>::DB], f32x16 (&dv)[TileGeom<D, Traits<T>::ES>::DB],
                             uint32_t kmask, uint32_t ncm, int j, int i0, int diff, Trace& ts, DkvPipe<T, D, BMQ>& pp_, bool fresh = true,
-                            const char* nxt = nullptr, bool young = false, int hoff = 0, int hq = 0, int dlo = 0) {
+                            const char* nxt = nullptr, bool young = false, int hoff = 0, int hq = 0, int dlo = 0, AlibiArg<ALIBI> ab = {}) {
   typedef TileGeom<D, Traits<T>::ES> G;
   typedef Traits<T> TR;
   constexpr bool MASKED = MODE == 1, KEYM = MODE == 2;
@@ -1067,6 +1107,7 @@ FCSA_DEV void dkv_tile_pipe(const char* qt, const char* dot, const float* lcs, c
     if (ib == 1) FCSA_STAMP(ts, 2);
     // ---- M1: S = Q K^T + lc, dP = dO V^T - delta (the per-query terms are the accumulators' initial values)
     f32x16 s = pp_.s, dp = pp_.dp;
+    if constexpr (ALIBI) alibi_add16<1>(s, ab.slope2, i0 + 32 * ib + 4 * fa.hi + ab.apos - j);
     if constexpr (KEYM) s = key_mask_rank1_cols<T>(s, kmask == 0u, fa.hi);
 #pragma unroll
     for (int kk = 0; kk < G::KS; ++kk) s = TR::mfma32(pp_.qa[kk], kf[kk], s);
@@ -1142,8 +1183,10 @@ FCSA_DEV void dkv_tile_pipe(const char* qt, const char* dot, const float* lcs, c
 // across the head seam: the tile requested ahead of the last tile of head g is the first tile of head g + 1, so the pipeline does not drain.
 // WIN (bwd_dkv_win_kernel; never BIAS / KM / SWEEP, no split): a sliding window -- every pass runs on the query tiles [t0, QT) its key tile
 // sees (win_query_tiles), tile loops select | plain | select
-template <typename T, int D, int NW, int BMQ, bool BIAS, bool LEAN, bool KM, bool RING, bool QSPLIT, bool SWEEP, bool WIN>      // KM: not causal, masked tiles in the rank-1 form (see fwd_kernel)
-FCSA_DEV void bwd_dkv_body(const std::conditional_t<WIN, BwdWinParams, BwdParams>& p_) {
+// ALIBI (bwd_dkv_alibi_kernel; WIN only, so never SWEEP: a workgroup has ONE query head): the forward's linear position bias, recomputed in the S seeds (dkv_tile)
+template <typename T, int D, int NW, int BMQ, bool BIAS, bool LEAN, bool KM, bool RING, bool QSPLIT, bool SWEEP, bool WIN, bool ALIBI = false>      // KM: not causal, masked tiles in the rank-1 form (see fwd_kernel)
+FCSA_DEV void bwd_dkv_body(const std::conditional_t<WIN, BwdWinParams, BwdParams>& p_, const TrainAlibi* al = nullptr) {
+  static_assert(!ALIBI || WIN, "linear position bias: the windowed body");
   static_assert(!WIN || (!BIAS && !KM && !SWEEP), "sliding window: no bias, the per-logit select, no group sweep");
   std::conditional_t<WIN, BwdWinParams, BwdParams> p = p_;      // a varlen launch rebinds it to the workgroup's sequence (varlen_bind); dense launches use it as given
   static_assert(!QSPLIT || (NW == 8 && !LEAN && (RING || BIAS) && BMQ % 64 == 0), "query-split form: 8 waves; pipelined ring tile, or the generic tile with a bias");
@@ -1172,13 +1215,16 @@ FCSA_DEV void bwd_dkv_body(const std::conditional_t<WIN, BwdWinParams, BwdParams
 
   // causal: a pair of key tiles per workgroup, the LOW one first: it sees every later query (tile_pairs, fcsa_dispatch.h)
   int bh, pt, b, h, hk;
+  [[maybe_unused]] AlibiArg<ALIBI> ab;      // ALIBI: slope * log2(e) of this workgroup's (sequence, query head), and M - N of its sequence
   if constexpr (SWEEP) {      // grid: (batch, K/V head) x key tiles; h = the group's first query head
     const int HK = p.H / p.kv_group;
     block_work(blockIdx.x, p.B * HK, tile_pairs(tile_count(p.M, BNK), causal), bh, pt);
     b = bh / HK; hk = bh % HK; h = hk * p.kv_group;
   } else {      // (varlen: never the group sweep)
     block_work(blockIdx.x, p.B * p.H, tile_pairs(tile_count(p.M, BNK), causal), bh, pt);
+    if constexpr (ALIBI) ab.slope2 = train_alibi_slope(*al, bh / p.H, bh % p.H);      // (before a packed launch rebinds bh)
     if (p.seq.cu_q != nullptr && !varlen_bind<D, Traits<T>::ES>(p, bh, pt, BNK, causal, true)) return;
+    if constexpr (ALIBI) ab.apos = p.M - p.N;                                           // pos_i - j = i + apos - j
     b = bh / p.H; h = bh % p.H; hk = h / p.kv_group;
   }
   const int KT = tile_count(p.M, BNK);
@@ -1505,6 +1551,14 @@ FCSA_DEV void bwd_dkv_body(const std::conditional_t<WIN, BwdWinParams, BwdParams
         if constexpr (RING) {
           if (!skip) {
             const bool has_next = t + 1 < QT || (SWEEP && gi + 1 < p.kv_group && !head_skip0);      // (else: the request reads this tile's buffer again and is never used)
+            if constexpr (ALIBI) {
+            if constexpr (QSPLIT)
+              dkv_tile_pipe<T, D, BMS, tile_mode<MODE>(), true, true, WIN, true>(cur + hoff, cur + TILE_B + hoff, lcs + hq, dls + hq, fa, kf, vf, dk, dv, kmask, ncm, j, i0 + hq, diff, ts,
+                                                          pipe, pipe_tile != t, has_next ? smem + par_nxt * BUF_B : cur, wave >= 4, hoff, hq, dlo, ab);
+            else
+            dkv_tile_pipe<T, D, BMQ, tile_mode<MODE>(), true, false, WIN, true>(cur, cur + TILE_B, lcs, dls, fa, kf, vf, dk, dv, kmask, ncm, j, i0, diff, ts, pipe, pipe_tile != t,
+                                                  has_next ? smem + par_nxt * BUF_B : cur, NW == 8 && wave >= 4, 0, 0, dlo, ab);
+            } else
             if constexpr (QSPLIT)
               dkv_tile_pipe<T, D, BMS, tile_mode<MODE>(), true, true, WIN>(cur + hoff, cur + TILE_B + hoff, lcs + hq, dls + hq, fa, kf, vf, dk, dv, kmask, ncm, j, i0 + hq, diff, ts,
                                                           pipe, pipe_tile != t, has_next ? smem + par_nxt * BUF_B : cur, wave >= 4, hoff, hq, dlo);
@@ -1515,15 +1569,27 @@ FCSA_DEV void bwd_dkv_body(const std::conditional_t<WIN, BwdWinParams, BwdParams
           }
           ring = par_nxt;
         } else {
+          if constexpr (ALIBI) {
+          if (!skip) dkv_tile_pipe<T, D, BMQ, tile_mode<MODE>(), false, false, WIN, true>(cur, cur + TILE_B, lcs, dls, fa, kf, vf, dk, dv, kmask, ncm, j, i0, diff, ts, pipe, true, nullptr,
+                                                    NW == 8 && wave >= 4, 0, 0, dlo, ab);
+          } else
           if (!skip) dkv_tile_pipe<T, D, BMQ, tile_mode<MODE>(), false, false, WIN>(cur, cur + TILE_B, lcs, dls, fa, kf, vf, dk, dv, kmask, ncm, j, i0, diff, ts, pipe, true, nullptr,
                                                     NW == 8 && wave >= 4, 0, 0, dlo);
         }
       } else if constexpr (LEAN) {
+        if constexpr (ALIBI) {
+        if (!skip) dkv_tile<T, D, BMQ, tile_mode<MODE>(), false, true, WIN, true>(cur, cur + TILE_B, lcs, dls, fa, kf, vf, dk, dv, p, kmask, ncm, j, i0, diff, nullptr, ts,
+                                                            bb, bscr, nullptr, false, -1, lane, smem + LDS::VOWN, wave * 32, NW == 8 && wave >= 4, dlo, ab);
+        } else
         if (!skip) dkv_tile<T, D, BMQ, tile_mode<MODE>(), false, true, WIN>(cur, cur + TILE_B, lcs, dls, fa, kf, vf, dk, dv, p, kmask, ncm, j, i0, diff, nullptr, ts,
                                                             bb, bscr, nullptr, false, -1, lane, smem + LDS::VOWN, wave * 32, NW == 8 && wave >= 4, dlo);
       } else {
         const int next_i0 = more ? i0 + hq + BMQ : -1;      // (QSPLIT: of this wave's rows of the next staged tile)
         if (!skip) {
+          if constexpr (ALIBI)
+          dkv_tile<T, D, BMS, tile_mode<MODE>(), BIAS, false, WIN, true>(cur + hoff, cur + TILE_B + hoff, lcs + hq, dls + hq, fa, kf, vf, dk, dv, p, kmask, ncm, j, i0 + hq, diff, bias_col, ts, bb, bscr,
+                                            bias_blk, bvec, next_i0, lane, nullptr, 0, false, dlo, ab);
+          else
           dkv_tile<T, D, BMS, tile_mode<MODE>(), BIAS, false, WIN>(cur + hoff, cur + TILE_B + hoff, lcs + hq, dls + hq, fa, kf, vf, dk, dv, p, kmask, ncm, j, i0 + hq, diff, bias_col, ts, bb, bscr,
                                             bias_blk, bvec, next_i0, lane, nullptr, 0, false, dlo);
         } else if constexpr (BIAS) {      // the block requested for this tile is not used: request the next tile's first block instead
@@ -1622,9 +1688,14 @@ template <typename T, int D, int NW, int BMQ, bool LEAN, bool RING, bool QSPLIT>
 __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes || LEAN) ? 2 : 1)) bwd_dkv_win_kernel(const BwdWinParams p_) {
   bwd_dkv_body<T, D, NW, BMQ, false, LEAN, false, RING, QSPLIT, false, true>(p_);
 }
+// the forms with a linear position bias (launch_backward_dkv_alibi): the windowed body again, the slopes as a second argument
+template <typename T, int D, int NW, int BMQ, bool LEAN, bool RING, bool QSPLIT>
+__global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= kDkv2WBytes || LEAN) ? 2 : 1)) bwd_dkv_alibi_kernel(const BwdWinParams p_, const TrainAlibi al) {
+  bwd_dkv_body<T, D, NW, BMQ, false, LEAN, false, RING, QSPLIT, false, true, true>(p_, &al);
+}
 
 template <typename T, int D, bool BIAS, int NW, bool TWO, bool KSPLIT = false>
-static hipError_t launch_dq_nw(const BwdWinParams& p, hipStream_t s) {
+static hipError_t launch_dq_nw(const BwdWinParams& p, hipStream_t s, const TrainAlibi* al = nullptr) {
   // 128-key stages (one barrier per 128 keys) in the 8-wave form and, with LDS-DMA staging (no staging registers), also for the
   // one-wave-per-SIMD configurations (16-bit D >= 96: one workgroup per CU, the LDS is there)
   // 8-wave form: 256-key stages where they arrive by LDS-DMA (no staging registers), 128-key stages through registers (f32)
@@ -1638,10 +1709,12 @@ static hipError_t launch_dq_nw(const BwdWinParams& p, hipStream_t s) {
     // (rows wider than 128 bytes never take the two-wave tile under a window -- choose_dq -- so those forms are not compiled)
     if constexpr (!BIAS && !(TWO && D * Traits<T>::ES > kDq2WBytes)) {
       if (!p.causal || p.dq_splits > 1 || p.mask != nullptr) return hipErrorInvalidValue;
+      if (al != nullptr) return launch_with_lds<bwd_dq_alibi_kernel<T, D, NW, SUB, TWO, KSPLIT>>(grid, dim3(NW * 64), LDS::TOTAL, s, p, *al);
       return launch_with_lds<bwd_dq_win_kernel<T, D, NW, SUB, TWO, KSPLIT>>(grid, dim3(NW * 64), LDS::TOTAL, s, p);
     }
     return hipErrorInvalidValue;
   }
+  if (al != nullptr) return hipErrorInvalidValue;      // (slopes: windowed launches only)
   const BwdParams& bp = p;      // (the un-windowed kernels take the BwdParams part alone)
   if constexpr (!GENERAL_ONLY) {
     if (!p.causal) return launch_with_lds<bwd_dq_kernel<T, D, NW, BIAS, SUB, TWO, true, KSPLIT>>(grid, dim3(NW * 64), LDS::TOTAL, s, bp);
@@ -1651,27 +1724,27 @@ static hipError_t launch_dq_nw(const BwdWinParams& p, hipStream_t s) {
 
 // the instantiation of form f (choose_dq, fcsa_dispatch.h)
 template <typename T, int D, bool BIAS>
-static hipError_t launch_dq_form(DqForm f, const BwdWinParams& p, hipStream_t s) {
+static hipError_t launch_dq_form(DqForm f, const BwdWinParams& p, hipStream_t s, const TrainAlibi* al = nullptr) {
   constexpr int ES = Traits<T>::ES;
   constexpr bool NARROW = D * ES <= kDq2WBytes;      // rows <= 128 bytes: two waves per SIMD whatever the grid
   switch (f) {
     case DqForm::Waves4:
-      return launch_dq_nw<T, D, BIAS, 4, NARROW>(p, s);
+      return launch_dq_nw<T, D, BIAS, 4, NARROW>(p, s, al);
     case DqForm::Waves4Two:
-      if constexpr (NARROW || (dq_can_two_waves(ES, D) && !BIAS)) return launch_dq_nw<T, D, BIAS, 4, true>(p, s);
+      if constexpr (NARROW || (dq_can_two_waves(ES, D) && !BIAS)) return launch_dq_nw<T, D, BIAS, 4, true>(p, s, al);
       break;
     case DqForm::Waves8:
-      if constexpr (NARROW) return launch_dq_nw<T, D, BIAS, 8, true>(p, s);
+      if constexpr (NARROW) return launch_dq_nw<T, D, BIAS, 8, true>(p, s, al);
       break;
     case DqForm::KSplit8:
-      if constexpr (bwd_ksplit(ES, D, false) && (NARROW || (dq_can_two_waves(ES, D) && !BIAS))) return launch_dq_nw<T, D, BIAS, 8, true, true>(p, s);
+      if constexpr (bwd_ksplit(ES, D, false) && (NARROW || (dq_can_two_waves(ES, D) && !BIAS))) return launch_dq_nw<T, D, BIAS, 8, true, true>(p, s, al);
       break;
   }
   return hipErrorInvalidValue;
 }
 
 template <typename T, int D, bool BIAS, int NW, bool LEAN = false, bool QSPLIT = false, bool SWEEP = false>
-static hipError_t launch_dkv_nw(const BwdWinParams& p, hipStream_t s) {
+static hipError_t launch_dkv_nw(const BwdWinParams& p, hipStream_t s, const TrainAlibi* al = nullptr) {
   // staged query tile: 32 rows for wide feature rows (16-bit D >= 96, f32 D >= 64: VGPR budget of the staging registers),
   // else 64; 128 in the 8-wave form (one workgroup per CU: the LDS is there, and half the barriers per key tile: -4.5%)
   // (the pipelined LDS-DMA form has no staging registers: wide rows can take deeper tiles too -> fragment prefetch across
@@ -1690,10 +1763,12 @@ static hipError_t launch_dkv_nw(const BwdWinParams& p, hipStream_t s) {
   if (p.window) {
     if constexpr (!BIAS && !SWEEP) {
       if (!p.causal || p.dkv_splits > 1 || p.mask != nullptr) return hipErrorInvalidValue;
+      if (al != nullptr) return launch_with_lds<bwd_dkv_alibi_kernel<T, D, NW, BMQ, LEAN, RING, QSPLIT>>(grid, dim3(NW * 64), LDS::TOTAL, s, p, *al);
       return launch_with_lds<bwd_dkv_win_kernel<T, D, NW, BMQ, LEAN, RING, QSPLIT>>(grid, dim3(NW * 64), LDS::TOTAL, s, p);
     }
     return hipErrorInvalidValue;
   }
+  if (al != nullptr) return hipErrorInvalidValue;      // (slopes: windowed launches only)
   // (two instantiations, see launch_fwd_nw)
   const BwdParams& bp = p;      // (the un-windowed kernels take the BwdParams part alone)
   return p.causal ? launch_with_lds<bwd_dkv_kernel<T, D, NW, BMQ, BIAS, LEAN, false, RING, QSPLIT, SWEEP>>(grid, dim3(NW * 64), LDS::TOTAL, s, bp)
@@ -1708,23 +1783,23 @@ int kv_group_mode(int set) {
 
 // the instantiation of form f (choose_dkv, fcsa_dispatch.h)
 template <typename T, int D, bool BIAS>
-static hipError_t launch_dkv_form(DkvForm f, const BwdWinParams& p, hipStream_t s) {
+static hipError_t launch_dkv_form(DkvForm f, const BwdWinParams& p, hipStream_t s, const TrainAlibi* al = nullptr) {
   constexpr int ES = Traits<T>::ES;
   constexpr bool NARROW = D * ES <= kDkv2WBytes;
   switch (f) {
     case DkvForm::Waves4:
-      return launch_dkv_nw<T, D, BIAS, 4>(p, s);
+      return launch_dkv_nw<T, D, BIAS, 4>(p, s, al);
     case DkvForm::Waves8:
-      if constexpr (NARROW) return launch_dkv_nw<T, D, BIAS, 8>(p, s);
+      if constexpr (NARROW) return launch_dkv_nw<T, D, BIAS, 8>(p, s, al);
       break;
     case DkvForm::Lean8:
-      if constexpr (ES == 2 && !BIAS && !NARROW && D * ES <= 256) return launch_dkv_nw<T, D, BIAS, 8, true>(p, s);
+      if constexpr (ES == 2 && !BIAS && !NARROW && D * ES <= 256) return launch_dkv_nw<T, D, BIAS, 8, true>(p, s, al);
       break;
     case DkvForm::QSplit8:
-      if constexpr (NARROW && bwd_ksplit(ES, D, false)) return launch_dkv_nw<T, D, BIAS, 8, false, true>(p, s);
+      if constexpr (NARROW && bwd_ksplit(ES, D, false)) return launch_dkv_nw<T, D, BIAS, 8, false, true>(p, s, al);
       break;
     case DkvForm::Sweep:
-      if constexpr (dkv_has_sweep(ES, D, BIAS)) return launch_dkv_nw<T, D, BIAS, 8, !NARROW, false, true>(p, s);
+      if constexpr (dkv_has_sweep(ES, D, BIAS)) return launch_dkv_nw<T, D, BIAS, 8, !NARROW, false, true>(p, s, al);
       break;
   }
   return hipErrorInvalidValue;
@@ -1758,6 +1833,24 @@ hipError_t launch_backward_dkv(int dtype, int D, const BwdWinParams& p, hipStrea
     constexpr int DD = decltype(td)::D;
     return p.bias != nullptr ? launch_dkv_form<T, DD, true>(f, p, s) : launch_dkv_form<T, DD, false>(f, p, s);
   });
+}
+
+// The two launches of a backward with a linear position bias (fcsa_backward_alibi): the windowed dispatch of launch_backward_dq / _dkv --
+// p.window must be set, with open sides (kWinOpen) where the call has no window -- on the entry points that take the slopes.
+static bool alibi_launchable(const BwdWinParams& p, const TrainAlibi& al) {
+  return p.window && p.bias == nullptr && p.mask == nullptr && p.dq_splits <= 1 && p.dkv_splits <= 1 && !p.kv_sweep && al.slopes != nullptr;
+}
+hipError_t launch_backward_dq_alibi(int dtype, int D, const BwdWinParams& p, const TrainAlibi& al, hipStream_t s) {
+  if (!alibi_launchable(p, al)) return hipErrorInvalidValue;
+  if (p.B * p.H == 0 || p.N == 0) return hipSuccess;
+  const DqForm f = choose_dq(bwd_problem(dtype, D, p, p.dq_splits), cu_count());
+  return dispatch_dtype_d(dtype, D, [&](auto td) { return launch_dq_form<typename decltype(td)::T, decltype(td)::D, false>(f, p, s, &al); });
+}
+hipError_t launch_backward_dkv_alibi(int dtype, int D, const BwdWinParams& p, const TrainAlibi& al, hipStream_t s) {
+  if (!alibi_launchable(p, al)) return hipErrorInvalidValue;
+  if (p.B * p.H == 0 || p.M == 0) return hipSuccess;
+  const DkvForm f = choose_dkv(bwd_problem(dtype, D, p, p.dkv_splits), cu_count());
+  return dispatch_dtype_d(dtype, D, [&](auto td) { return launch_dkv_form<typename decltype(td)::T, decltype(td)::D, false>(f, p, s, &al); });
 }
 
 }  // namespace fcsa

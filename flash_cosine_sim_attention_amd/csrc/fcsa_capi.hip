@@ -278,8 +278,10 @@ int check_window(const fcsa_window* w, bool mask, bool bias) {
   return FCSA_OK;
 }
 
-int forward_impl(const fcsa_forward_args* a, const VarlenCall* vl, const WindowCall* win = nullptr);
-int backward_impl(const fcsa_backward_args* a, const VarlenCall* vl, const WindowCall* win = nullptr, const float* dlse = nullptr);
+// al != nullptr: a linear position bias (fcsa_forward_alibi / fcsa_backward_alibi; win is set then, with open sides where the call has no window)
+int forward_impl(const fcsa_forward_args* a, const VarlenCall* vl, const WindowCall* win = nullptr, const fcsa::TrainAlibi* al = nullptr);
+int backward_impl(const fcsa_backward_args* a, const VarlenCall* vl, const WindowCall* win = nullptr, const float* dlse = nullptr,
+                  const fcsa::TrainAlibi* al = nullptr);
 
 }  // namespace
 
@@ -395,7 +397,7 @@ static int zero_rows(const char* name, const fcsa_tensor& t, int es, int B, int 
 
 int fcsa_forward(const fcsa_forward_args* a) { return forward_impl(a, nullptr); }
 
-static int forward_varlen(const fcsa_forward_args* a, const fcsa_varlen* seqs, const WindowCall* win) {
+static int forward_varlen(const fcsa_forward_args* a, const fcsa_varlen* seqs, const WindowCall* win, const fcsa::TrainAlibi* al = nullptr) {
   if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
   if (int rc = check_problem(a->p)) return rc;
   if (int rc = check_varlen(a->p, seqs, a->mask != nullptr, a->attn_bias != nullptr)) return rc;
@@ -403,7 +405,7 @@ static int forward_varlen(const fcsa_forward_args* a, const fcsa_varlen* seqs, c
   pa.q = packed(pa.q); pa.k = packed(pa.k); pa.v = packed(pa.v); pa.o = packed(pa.o);
   pa.p = packed_problem(a->p, *seqs);
   const VarlenCall vl = {seqs, a->p.batch, a->p.q_len, a->p.k_len};
-  return forward_impl(&pa, &vl, win);
+  return forward_impl(&pa, &vl, win, al);
 }
 int fcsa_forward_varlen(const fcsa_forward_args* a, const fcsa_varlen* seqs) { return forward_varlen(a, seqs, nullptr); }
 
@@ -418,6 +420,34 @@ int fcsa_forward_window(const fcsa_forward_args* a, const fcsa_varlen* seqs, con
   na.p.causal = kind == fcsa::WinKind::Causal ? 1 : 0;
   return seqs != nullptr ? fcsa_forward_varlen(&na, seqs) : fcsa_forward(&na);
 }
+
+// The checks the two slope calls share, and the sides of their windowed launch: whatever win_normalise makes of the window -- (open, open)
+// and (open, 0) included, which the windowed kernel forms serve like any other pair.
+static int check_alibi(const fcsa_problem& p, const fcsa_varlen* seqs, const fcsa_window* w, const fcsa_alibi* al, bool mask, bool bias,
+                       WindowCall& win, fcsa::TrainAlibi& ta) {
+  if (mask || bias) return fail(FCSA_ERR_INVALID_ARG, "alibi: mask and attn_bias are not supported with alibi_slopes");
+  if (w != nullptr) {
+    if (int rc = check_window(w, false, false)) return rc;
+  }
+  if (al == nullptr || al->slopes == nullptr) return fail(FCSA_ERR_INVALID_ARG, "alibi: null slopes");
+  if ((reinterpret_cast<uintptr_t>(al->slopes) & 3) != 0) return fail(FCSA_ERR_INVALID_ARG, "alibi: slopes not 4-byte aligned");
+  if (al->reserved != 0) return fail(FCSA_ERR_INVALID_ARG, "alibi: reserved must be 0");
+  if (seqs == nullptr && !p.causal && p.q_len > p.k_len)
+    return fail(FCSA_ERR_INVALID_ARG, "alibi: a non-causal call needs q_len <= k_len (%d > %d): rows with pos_i < 0 have no key at distance 0", p.q_len, p.k_len);
+  (void)fcsa::win_normalise(p.q_len, p.k_len, p.causal != 0, w != nullptr ? w->left : -1, w != nullptr ? w->right : -1, win.lo, win.hi);
+  ta = fcsa::TrainAlibi{al->slopes, al->stride_b, al->stride_h};
+  return FCSA_OK;
+}
+
+int fcsa_forward_alibi(const fcsa_forward_args* a, const fcsa_varlen* seqs, const fcsa_window* w, const fcsa_alibi* al) {
+  if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
+  if (int rc = check_problem(a->p)) return rc;
+  WindowCall win;
+  fcsa::TrainAlibi ta;
+  if (int rc = check_alibi(a->p, seqs, w, al, a->mask != nullptr, a->attn_bias != nullptr, win, ta)) return rc;
+  return seqs != nullptr ? forward_varlen(a, seqs, &win, &ta) : forward_impl(a, nullptr, &win, &ta);
+}
+size_t fcsa_forward_alibi_workspace_bytes(const fcsa_problem*, const fcsa_varlen*, const fcsa_window*) { return 0; }
 
 
 }  // extern "C"
@@ -979,7 +1009,7 @@ namespace {
 
 // vl != nullptr: packed sequences; a->p is then the problem of the packed rows (packed_problem)
 // win != nullptr: a sliding window (the windowed kernel forms; no split)
-int forward_impl(const fcsa_forward_args* a, const VarlenCall* vl, const WindowCall* win) {
+int forward_impl(const fcsa_forward_args* a, const VarlenCall* vl, const WindowCall* win, const fcsa::TrainAlibi* al) {
   if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
   const fcsa_problem& p = a->p;
   if (int rc = check_problem(p)) return rc;
@@ -1065,6 +1095,7 @@ int forward_impl(const fcsa_forward_args* a, const VarlenCall* vl, const WindowC
       fp.ws_l = reinterpret_cast<float*>(static_cast<char*>(a->workspace) + align_up(rows * p.dim_head * 4, 256));
     }
   }
+  if (al != nullptr) return timed("fwd", "forward", s, [&] { return fcsa::launch_forward_alibi(p.dtype, p.dim_head, fp, *al, s); });
   return timed("fwd", "forward", s, [&] { return fcsa::launch_forward(p.dtype, p.dim_head, fp, s); });
 }
 
@@ -1090,7 +1121,8 @@ size_t fcsa_backward_varlen_workspace_bytes(const fcsa_problem* p, const fcsa_va
 
 int fcsa_backward(const fcsa_backward_args* a) { return backward_impl(a, nullptr); }
 
-static int backward_varlen(const fcsa_backward_args* a, const fcsa_varlen* seqs, const WindowCall* win, const float* dlse = nullptr);
+static int backward_varlen(const fcsa_backward_args* a, const fcsa_varlen* seqs, const WindowCall* win, const float* dlse = nullptr,
+                           const fcsa::TrainAlibi* al = nullptr);
 int fcsa_backward_varlen(const fcsa_backward_args* a, const fcsa_varlen* seqs) { return backward_varlen(a, seqs, nullptr); }
 
 size_t fcsa_backward_window_workspace_bytes(const fcsa_problem* p, const fcsa_varlen* seqs, const fcsa_window* w) {
@@ -1116,6 +1148,21 @@ static int backward_window(const fcsa_backward_args* a, const fcsa_varlen* seqs,
   return seqs != nullptr ? backward_varlen(&na, seqs, nullptr, dlse) : backward_impl(&na, nullptr, nullptr, dlse);
 }
 int fcsa_backward_window(const fcsa_backward_args* a, const fcsa_varlen* seqs, const fcsa_window* w) { return backward_window(a, seqs, w, nullptr); }
+
+int fcsa_backward_alibi(const fcsa_backward_args* a, const fcsa_varlen* seqs, const fcsa_window* w, const fcsa_alibi* al) {
+  if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
+  if (int rc = check_problem(a->p)) return rc;
+  WindowCall win;
+  fcsa::TrainAlibi ta;
+  if (int rc = check_alibi(a->p, seqs, w, al, a->mask != nullptr, a->attn_bias != nullptr || a->d_bias != nullptr, win, ta)) return rc;
+  return seqs != nullptr ? backward_varlen(a, seqs, &win, nullptr, &ta) : backward_impl(a, nullptr, &win, nullptr, &ta);
+}
+// (always the plan of a windowed launch: no split, no group sweep)
+size_t fcsa_backward_alibi_workspace_bytes(const fcsa_problem* p, const fcsa_varlen* seqs, const fcsa_window*) {
+  if (p == nullptr) return 0;
+  if (seqs != nullptr) return fcsa_backward_varlen_workspace_bytes(p, seqs);
+  return bwd_layout(*p, true).total;
+}
 
 int fcsa_backward_state(const fcsa_backward_args* a, const fcsa_varlen* seqs, const fcsa_window* w, const float* d_lse) {
   if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "backward_state: null args");
@@ -1189,7 +1236,7 @@ int fcsa_merge_states_backward(const fcsa_merge_backward_args* a) {
   return timed("merge_states_bwd", "merge states backward", s, [&] { return fcsa::launch_merge_states_backward(a->dtype, mp, s); });
 }
 
-static int backward_varlen(const fcsa_backward_args* a, const fcsa_varlen* seqs, const WindowCall* win, const float* dlse) {
+static int backward_varlen(const fcsa_backward_args* a, const fcsa_varlen* seqs, const WindowCall* win, const float* dlse, const fcsa::TrainAlibi* al) {
   if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
   if (int rc = check_problem(a->p)) return rc;
   if (int rc = check_varlen(a->p, seqs, a->mask != nullptr, a->attn_bias != nullptr || a->d_bias != nullptr)) return rc;
@@ -1198,7 +1245,7 @@ static int backward_varlen(const fcsa_backward_args* a, const fcsa_varlen* seqs,
   pa.dq = packed(pa.dq); pa.dk = packed(pa.dk); pa.dv = packed(pa.dv);
   pa.p = packed_problem(a->p, *seqs);
   const VarlenCall vl = {seqs, a->p.batch, a->p.q_len, a->p.k_len};
-  return backward_impl(&pa, &vl, win, dlse);
+  return backward_impl(&pa, &vl, win, dlse, al);
 }
 
 }  // extern "C"
@@ -1206,7 +1253,7 @@ static int backward_varlen(const fcsa_backward_args* a, const fcsa_varlen* seqs,
 namespace {
 
 // win != nullptr: a sliding window (the windowed kernel forms; the plan of a packed call: no split, no group sweep)
-int backward_impl(const fcsa_backward_args* a, const VarlenCall* vl, const WindowCall* win, const float* dlse) {
+int backward_impl(const fcsa_backward_args* a, const VarlenCall* vl, const WindowCall* win, const float* dlse, const fcsa::TrainAlibi* al) {
   if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
   const fcsa_problem& p = a->p;
   if (int rc = check_problem(p)) return rc;
@@ -1311,8 +1358,13 @@ int backward_impl(const fcsa_backward_args* a, const VarlenCall* vl, const Windo
   bp.rk = (plan.fuse_norm && (!grouped || plan.kv_sweep) && dkv_splits <= 1) ? a->norm.rk : nullptr;          // fused: dkv kernel writes the final dk
 
   // 1. dQ (also publishes delta), 2. dK/dV, 3. head reduction + l2norm backward where needed
+  if (al != nullptr) {
+    if (int rc = timed("bwd_dq", "backward dq", s, [&] { return fcsa::launch_backward_dq_alibi(p.dtype, p.dim_head, bp, *al, s); })) return rc;
+    if (int rc = timed("bwd_dkv", "backward dkv", s, [&] { return fcsa::launch_backward_dkv_alibi(p.dtype, p.dim_head, bp, *al, s); })) return rc;
+  } else {
   if (int rc = timed("bwd_dq", "backward dq", s, [&] { return fcsa::launch_backward_dq(p.dtype, p.dim_head, bp, s); })) return rc;
   if (int rc = timed("bwd_dkv", "backward dkv", s, [&] { return fcsa::launch_backward_dkv(p.dtype, p.dim_head, bp, s); })) return rc;
+  }
   if (want_dbias) {      // d_bias from recomputed dS tiles; needs delta, which the dQ kernel published
     if (int rc = timed("bwd_dbias", "backward d_bias", s, [&] { return fcsa::launch_backward_dbias(p.dtype, p.dim_head, bp, s); })) return rc;
   }

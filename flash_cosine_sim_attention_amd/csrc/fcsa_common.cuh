@@ -974,6 +974,35 @@ FCSA_DEV bool varlen_bind(BwdParams& p, int& bh, int pair, int tile, int causal,
   return true;
 }
 
+// ---- linear position bias of the training kernels (TrainAlibi, fcsa_kernels.h; fwd_alibi_kernel, bwd_dq_alibi_kernel, bwd_dkv_alibi_kernel) ----
+// The bias is the S accumulator's seed: where the plain kernels start a 32x32 block of logits from a per-row constant (-c2row in the
+// forward, lc in both backward kernels), the ALIBI forms start register r from  seed - slope * log2(e) * |d0 + sgn * crow(r, 0)|,  d0 being
+// the distance pos_i - j of register 0 (an integer converted once per block: exact below 2^24).  One subtract and one fma per logit (the
+// absolute value is an operand modifier), all in front of the MFMA chain.  train_alibi_slope: slope * log2(e) of (sequence b, QUERY head h),
+// loaded once per workgroup.  All three kernels use this pair, so the recomputed P of the backward is the forward's, bit for bit; a slope of
+// 0 gives fma(-0, |d|, seed) == seed, the un-biased kernel's arithmetic.
+// AlibiArg: what a tile function takes -- the slope and `apos`, with pos_i - j = i + apos - j in the tile's own numbering.  It is EMPTY in
+// the forms without a bias, whose code reads as it did: every use sits under `if constexpr (ALIBI)`.
+template <bool ALIBI> struct AlibiArg { float slope2; int apos; };
+template <> struct AlibiArg<false> {};
+FCSA_DEV float train_alibi_slope(const TrainAlibi& al, int b, int h) { return al.slopes[(int64_t)b * al.sb + (int64_t)h * al.sh] * 1.4426950408889634f; }
+FCSA_DEV float train_alibi_logit(float seed, float slope2, float d0, int c) { return fmaf(-slope2, fabsf(d0 + (float)c), seed); }
+// the seeds of one block from one constant.  SGN = -1: the lane's row is a query and its registers are keys (forward, dQ)
+template <int SGN>
+FCSA_DEV void alibi_seed16(f32x16& s, float seed, float slope2, int d0) {
+  const float f0 = (float)d0;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) s[r] = train_alibi_logit(seed, slope2, f0, SGN * crow(r, 0));
+}
+// ... and where the seeds differ per register and are in s already.  SGN = +1: the lane's row is a key and its registers are queries (dK/dV:
+// the per-query lc staged in the LDS)
+template <int SGN>
+FCSA_DEV void alibi_add16(f32x16& s, float slope2, int d0) {
+  const float f0 = (float)d0;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) s[r] = train_alibi_logit(s[r], slope2, f0, SGN * crow(r, 0));
+}
+
 template <typename T, int D>
 FCSA_DEV void load_q_frags(const FwdParams& p, int b, int h, int i, const FragAddr<T, D>& fa,
                            u32x4 (&qf)[TileGeom<D, Traits<T>::ES>::KS]) {

@@ -169,12 +169,13 @@ FCSA_DEV void fwd_softmax_block(f32x16& s, SecondB<T>& pb, float& l, f32x16& lac
 // MODE: 0 = every pair valid, 1 = causal tiles on the diagonal (and their ragged tails): select per logit, 2 = key mask / ragged
 // tail of a non-causal problem: rank-1 MFMA per block (key_mask_rank1)
 // WIN (sliding window, MODE 1 only): the select also clears the keys left of the row's window, j < i + dlo
-template <typename T, int D, int MODE, bool BIAS, bool LEAN, bool ONL, bool WIN = false, typename Mid>
+// ALIBI (fwd_alibi_kernel): the accumulators start from -c2row - ab.slope2 * |i + ab.apos - j| (alibi_seed16, fcsa_common.cuh) instead of -c2row
+template <typename T, int D, int MODE, bool BIAS, bool LEAN, bool ONL, bool WIN = false, bool ALIBI = false, typename Mid>
 FCSA_DEV void fwd_tile(const char* vt, u32x4 (&kf)[2][TileGeom<D, Traits<T>::ES>::KS], const FragAddr<T, D>& fa,
                        const u32x4 (&qf)[TileGeom<D, Traits<T>::ES>::KS], f32x16 (&o)[TileGeom<D, Traits<T>::ES>::DB],
                        float& l, f32x16& lacc, const FwdParams& p, float& c2row, float& rmax, uint64_t word, uint32_t ncm, int i, int j0, int diff,
                        const char* bias_row, Trace& ts, Mid&& mid, const char* knext, bool more_k, const char* kt,
-                       u32x4 (*braw)[2][2] = nullptr, bool use_raw = false, int next_j0 = -1, int dlo = 0) {
+                       u32x4 (*braw)[2][2] = nullptr, bool use_raw = false, int next_j0 = -1, int dlo = 0, AlibiArg<ALIBI> ab = {}) {
 
   typedef TileGeom<D, Traits<T>::ES> G;
   typedef Traits<T> TR;
@@ -201,8 +202,11 @@ FCSA_DEV void fwd_tile(const char* vt, u32x4 (&kf)[2][TileGeom<D, Traits<T>::ES>
 #pragma unroll
     for (int jb = 0; jb < 2; ++jb) {
       f32x16 s;
+      if constexpr (ALIBI) alibi_seed16<-1>(s, -c2row, ab.slope2, i + ab.apos - (j0 + 32 * jb + 4 * fa.hi));
+      else {
 #pragma unroll
       for (int r = 0; r < 16; ++r) s[r] = -c2row;
+      }
       if constexpr (KEYM) s = key_mask_rank1<T>(s, (uint32_t)(word >> (32 * jb)), kx, fa.hi);
       constexpr int PF = 4;
 #pragma unroll
@@ -253,8 +257,13 @@ FCSA_DEV void fwd_tile(const char* vt, u32x4 (&kf)[2][TileGeom<D, Traits<T>::ES>
   } else if constexpr (TR::ES == 2 && !BIAS) {
     constexpr int MFMA = 0x8, VALU = 0x2 | 0x400, DSR = 0x100;
     f32x16 s0, s1;
+    if constexpr (ALIBI) {
+      alibi_seed16<-1>(s0, -c2row, ab.slope2, i + ab.apos - (j0 + 4 * fa.hi));
+      alibi_seed16<-1>(s1, -c2row, ab.slope2, i + ab.apos - (j0 + 32 + 4 * fa.hi));
+    } else {
 #pragma unroll
     for (int r = 0; r < 16; ++r) { s0[r] = -c2row; s1[r] = -c2row; }   // exponent shift (static, or this row's max) as the accumulator's initial value
+    }
     if constexpr (KEYM) {
       s0 = key_mask_rank1<T>(s0, (uint32_t)word, kx, fa.hi);
       s1 = key_mask_rank1<T>(s1, (uint32_t)(word >> 32), kx, fa.hi);
@@ -314,8 +323,11 @@ FCSA_DEV void fwd_tile(const char* vt, u32x4 (&kf)[2][TileGeom<D, Traits<T>::ES>
     if constexpr (ONL) {
       online_recentre<T, G::DB>(bm, c2row, rmax, o, l, lacc, [&](float d) {
         f32x16 t;
+        if constexpr (ALIBI) alibi_seed16<-1>(t, -c2row, ab.slope2, i + ab.apos - (j0 + 4 * fa.hi));
+        else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) t[r] = -c2row;          // (already the new reference)
+        }
         if constexpr (KEYM) t = key_mask_rank1<T>(t, (uint32_t)word, kx, fa.hi);
 #pragma unroll
         for (int kk = 0; kk < G::KS; ++kk) t = TR::mfma32(kf[0][kk], qf[kk], t);
@@ -382,8 +394,11 @@ FCSA_DEV void fwd_tile(const char* vt, u32x4 (&kf)[2][TileGeom<D, Traits<T>::ES>
     auto nothing = [](float) {};
 #pragma unroll
     for (int jb = 0; jb < 2; ++jb) {
+      if constexpr (ALIBI) alibi_seed16<-1>(s[jb], -c2row, ab.slope2, i + ab.apos - (j0 + 32 * jb + 4 * fa.hi));
+      else {
 #pragma unroll
       for (int r = 0; r < 16; ++r) s[jb][r] = -c2row;
+      }
       if constexpr (KEYM) s[jb] = key_mask_rank1<T>(s[jb], (uint32_t)(word >> (32 * jb)), kx, fa.hi);
 #pragma unroll
       for (int kk = 0; kk < G::KS; ++kk) s[jb] = TR::mfma32(kf[jb][kk], qf[kk], s[jb]);
@@ -463,9 +478,12 @@ template <typename T, int D, int NW, bool DYN, bool KSPLIT> struct FwdLds {
 // WIN (fwd_win_kernel; never BIAS / KM, no split): a sliding window (fcsa_dispatch.h, win_key_window) -- every pass runs on the keys of
 // its row tile's band only, which is the split-key machinery's sub-problem [k_lo, k_lo + Mk) with the diagonals renumbered, and its tile
 // loops are select | plain | select instead of plain | select.
-template <typename T, int D, int NW, bool BIAS, bool DYN, bool LEAN, bool KM, bool KSPLIT, bool WIN>
-FCSA_DEV void fwd_body(const std::conditional_t<WIN, FwdWinParams, FwdParams>& p_) {
+// ALIBI (fwd_alibi_kernel; WIN only): a linear position bias -slope[b, h] * |i + M - N - j| rides in as the accumulators' seed (fwd_tile);
+// the launch is a windowed one whose sides may both be open, and nothing else differs.
+template <typename T, int D, int NW, bool BIAS, bool DYN, bool LEAN, bool KM, bool KSPLIT, bool WIN, bool ALIBI = false>
+FCSA_DEV void fwd_body(const std::conditional_t<WIN, FwdWinParams, FwdParams>& p_, const TrainAlibi* al = nullptr) {
   static_assert(!WIN || (!BIAS && !KM), "sliding window: no bias, the per-logit select");
+  static_assert(!ALIBI || WIN, "linear position bias: the windowed body");
   std::conditional_t<WIN, FwdWinParams, FwdParams> p = p_;      // a varlen launch rebinds it to the workgroup's sequence (varlen_bind); dense launches use it as given
   static_assert(!KSPLIT || (NW == 8 && (LEAN != BIAS) && Traits<T>::ES == 2), "key-split form: 8 waves, 16 bit; lean tile, or the generic tile with a bias");
   const int causal = KM ? 0 : p.causal;      // (same type and value as p.causal: the causal instantiations compile to what they were)
@@ -487,6 +505,8 @@ FCSA_DEV void fwd_body(const std::conditional_t<WIN, FwdWinParams, FwdParams>& p
   // a pair of row tiles per workgroup under causal masking (tile_pairs, fcsa_dispatch.h)
   int bh, pt;
   block_work(blockIdx.x, p.B * p.H, tile_pairs(tile_count(p.N, BM), causal), bh, pt);
+  [[maybe_unused]] AlibiArg<ALIBI> ab;      // ALIBI: slope * log2(e) of this workgroup's (sequence, query head), read before a packed launch rebinds bh
+  if constexpr (ALIBI) ab.slope2 = train_alibi_slope(*al, bh / p.H, bh % p.H);
   if (p.seq.cu_q != nullptr && !varlen_bind<D, Traits<T>::ES>(p, bh, pt, BM, causal)) return;
   const int MT = tile_count(p.N, BM);
   const int b = bh / p.H, h = bh % p.H;
@@ -729,6 +749,10 @@ FCSA_DEV void fwd_body(const std::conditional_t<WIN, FwdWinParams, FwdParams>& p
         mid();
         if (PREFETCH_K && t + 1 < nt) request_k(knxt);
       } else {
+        if constexpr (ALIBI)
+          fwd_tile<T, D, tile_mode<MODE>(), BIAS, LEAN, DYN, WIN, true>(vcur, kf, fa, qf, o, l, lacc, p, c2row, rmax, word, ncm, i, j0, diff, bias_row, ts, mid, knxt, t + 1 < nt,
+                                       vcur - SUB * TILE_B, nullptr, false, -1, dlo, AlibiArg<true>{ab.slope2, p.M - p.N - k_lo});
+        else
         fwd_tile<T, D, tile_mode<MODE>(), BIAS, LEAN, DYN, WIN>(vcur, kf, fa, qf, o, l, lacc, p, c2row, rmax, word, ncm, i, j0, diff, bias_row, ts, mid, knxt, t + 1 < nt,
                                      vcur - SUB * TILE_B, BIAS_AHEAD ? &bnext : nullptr, bcur_ok, bfut_ok ? j0 + BN : -1, dlo);
         bnext_ok = bfut_ok;
@@ -791,6 +815,10 @@ FCSA_DEV void fwd_body(const std::conditional_t<WIN, FwdWinParams, FwdParams>& p
         return;
       }
       if constexpr (!LEAN) request_k(buf + half * TILE_B);      // (bias form: the generic tile takes its K fragments from registers; nothing is prefetched across stages)
+      if constexpr (ALIBI)
+        fwd_tile<T, D, tile_mode<MODE>(), BIAS, LEAN, DYN, WIN, true>(buf + (SUB + half) * TILE_B, kf, fa, qf, o, l, lacc, p, c2row, rmax, word, ncm, i, j0, diff, bias_row, ts, mid,
+                                             nullptr, false, buf + half * TILE_B, nullptr, false, -1, dlo, AlibiArg<true>{ab.slope2, p.M - p.N - k_lo});
+      else
       fwd_tile<T, D, tile_mode<MODE>(), BIAS, LEAN, DYN, WIN>(buf + (SUB + half) * TILE_B, kf, fa, qf, o, l, lacc, p, c2row, rmax, word, ncm, i, j0, diff, bias_row, ts, mid,
                                            nullptr, false, buf + half * TILE_B, nullptr, false, -1, dlo);
     };
@@ -886,6 +914,11 @@ __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ?
 template <typename T, int D, int NW, bool DYN, bool LEAN, bool KSPLIT>
 __global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ? 2 : 1)) fwd_win_kernel(const FwdWinParams p_) {
   fwd_body<T, D, NW, false, DYN, LEAN, false, KSPLIT, true>(p_);
+}
+// the forms with a linear position bias (launch_forward_alibi): the windowed body again, the slopes as a second argument
+template <typename T, int D, int NW, bool DYN, bool LEAN, bool KSPLIT>
+__global__ void __launch_bounds__(NW * 64, ((D * Traits<T>::ES <= 128 || LEAN) ? 2 : 1)) fwd_alibi_kernel(const FwdWinParams p_, const TrainAlibi al) {
+  fwd_body<T, D, NW, false, DYN, LEAN, false, KSPLIT, true, true>(p_, &al);
 }
 
 // =============================================================================================
@@ -1235,7 +1268,7 @@ __global__ void __launch_bounds__(256) fwd_combine_kernel(const FwdParams p) {
 }
 
 template <typename T, int D, bool BIAS, int NW, bool DYN, bool LEAN = false, bool KSPLIT = false>
-static hipError_t launch_fwd_nw(const FwdWinParams& p, hipStream_t s) {
+static hipError_t launch_fwd_nw(const FwdWinParams& p, hipStream_t s, const TrainAlibi* al = nullptr) {
   typedef FwdLds<T, D, NW, DYN, KSPLIT> LDS;
   constexpr int BM = 32 * LDS::RWAVES;
   static_assert(!KSPLIT || LDS::TILE_B % 1024 == 0, "key-split form: whole 1 KiB LDS-DMA pieces per tile");
@@ -1244,10 +1277,12 @@ static hipError_t launch_fwd_nw(const FwdWinParams& p, hipStream_t s) {
   if (p.window) {
     if constexpr (!BIAS) {
       if (!p.causal || p.splits > 1 || p.mask != nullptr) return hipErrorInvalidValue;
+      if (al != nullptr) return launch_with_lds<fwd_alibi_kernel<T, D, NW, DYN, LEAN, KSPLIT>>(grid, dim3(NW * 64), LDS::TOTAL, s, p, *al);
       return launch_with_lds<fwd_win_kernel<T, D, NW, DYN, LEAN, KSPLIT>>(grid, dim3(NW * 64), LDS::TOTAL, s, p);
     }
     return hipErrorInvalidValue;
   }
+  if (al != nullptr) return hipErrorInvalidValue;      // (slopes: windowed launches only)
   const FwdParams& fp = p;      // (the un-windowed kernels take the FwdParams part alone)
   const hipError_t e = p.causal ? launch_with_lds<fwd_kernel<T, D, NW, BIAS, DYN, LEAN, false, KSPLIT>>(grid, dim3(NW * 64), LDS::TOTAL, s, fp)
                                 : launch_with_lds<fwd_kernel<T, D, NW, BIAS, DYN, LEAN, true, KSPLIT>>(grid, dim3(NW * 64), LDS::TOTAL, s, fp);
@@ -1267,22 +1302,22 @@ static hipError_t launch_fwd2(const FwdParams& p, hipStream_t s) {
 
 // the instantiation of form f (choose_forward, fcsa_dispatch.h)
 template <typename T, int D, bool BIAS, bool DYN>
-static hipError_t launch_fwd_form(FwdForm f, const FwdWinParams& p, hipStream_t s) {
+static hipError_t launch_fwd_form(FwdForm f, const FwdWinParams& p, hipStream_t s, const TrainAlibi* al = nullptr) {
   constexpr int ES = Traits<T>::ES;
   switch (f) {
     case FwdForm::Rows8:
-      if constexpr (D * ES <= 128) return launch_fwd_nw<T, D, BIAS, 8, DYN>(p, s);
+      if constexpr (D * ES <= 128) return launch_fwd_nw<T, D, BIAS, 8, DYN>(p, s, al);
       break;
     case FwdForm::Lean8:
-      if constexpr (fwd_lean(ES, D, BIAS)) return launch_fwd_nw<T, D, BIAS, 8, DYN, true>(p, s);
+      if constexpr (fwd_lean(ES, D, BIAS)) return launch_fwd_nw<T, D, BIAS, 8, DYN, true>(p, s, al);
       break;
     case FwdForm::KSplit8:
-      if constexpr (fwd_ksplit(ES, D, BIAS)) return launch_fwd_nw<T, D, BIAS, 8, DYN, !BIAS, true>(p, s);
+      if constexpr (fwd_ksplit(ES, D, BIAS)) return launch_fwd_nw<T, D, BIAS, 8, DYN, !BIAS, true>(p, s, al);
       break;
     case FwdForm::Waves4:
-      return launch_fwd_nw<T, D, BIAS, 4, DYN>(p, s);
+      return launch_fwd_nw<T, D, BIAS, 4, DYN>(p, s, al);
     case FwdForm::Fwd2:
-      if constexpr (fwd2_compiled(ES, D) && !BIAS && !DYN) return launch_fwd2<T, D>(p, s);
+      if constexpr (fwd2_compiled(ES, D) && !BIAS && !DYN) { if (al == nullptr) return launch_fwd2<T, D>(p, s); }
       break;
     case FwdForm::Fwd3:
       break;
@@ -1290,10 +1325,15 @@ static hipError_t launch_fwd_form(FwdForm f, const FwdWinParams& p, hipStream_t 
   return hipErrorInvalidValue;
 }
 
+// what choose_forward is asked for a launch (both forward launchers)
+static FwdProblem fwd_problem(int dtype, int D, const FwdWinParams& p) {
+  return {dtype == 0 ? 4 : 2, D, (int64_t)p.B * p.H, p.N, p.M, p.causal != 0, p.bias != nullptr, p.mask != nullptr, p.dyn != 0,
+          p.splits, p.q.sn, p.k.sn, p.v.sn, forward_wide128_mode(-1), p.seq.cu_q != nullptr || p.window != 0};
+}
+
 hipError_t launch_forward(int dtype, int D, const FwdWinParams& p, hipStream_t s) {
   if (p.B * p.H == 0 || p.N == 0) return hipSuccess;
-  const FwdProblem fp = {dtype == 0 ? 4 : 2, D, (int64_t)p.B * p.H, p.N, p.M, p.causal != 0, p.bias != nullptr, p.mask != nullptr, p.dyn != 0,
-                         p.splits, p.q.sn, p.k.sn, p.v.sn, forward_wide128_mode(-1), p.seq.cu_q != nullptr || p.window != 0};
+  const FwdProblem fp = fwd_problem(dtype, D, p);
   const FwdForm f = choose_forward(fp, cu_count());
   if (f == FwdForm::Fwd3) return launch_forward_wide128(dtype, p, s);
   return dispatch_dtype_d(dtype, D, [&](auto td) {
@@ -1301,6 +1341,19 @@ hipError_t launch_forward(int dtype, int D, const FwdWinParams& p, hipStream_t s
     constexpr int DD = decltype(td)::D;
     if (p.bias != nullptr) return p.dyn ? launch_fwd_form<T, DD, true, true>(f, p, s) : launch_fwd_form<T, DD, true, false>(f, p, s);
     return p.dyn ? launch_fwd_form<T, DD, false, true>(f, p, s) : launch_fwd_form<T, DD, false, false>(f, p, s);
+  });
+}
+
+// A call with a linear position bias (fcsa_forward_alibi): launch_forward's windowed dispatch -- p.window must be set, with open sides
+// (kWinOpen) where the call has no window -- on the entry points that take the slopes (fwd_alibi_kernel).  No bias, key mask or split.
+hipError_t launch_forward_alibi(int dtype, int D, const FwdWinParams& p, const TrainAlibi& al, hipStream_t s) {
+  if (!p.window || p.bias != nullptr || p.mask != nullptr || p.splits > 1 || al.slopes == nullptr) return hipErrorInvalidValue;
+  if (p.B * p.H == 0 || p.N == 0) return hipSuccess;
+  const FwdForm f = choose_forward(fwd_problem(dtype, D, p), cu_count());      // (p.window is set: the forms of a windowed launch)
+  return dispatch_dtype_d(dtype, D, [&](auto td) {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    return p.dyn ? launch_fwd_form<T, DD, false, true>(f, p, s, &al) : launch_fwd_form<T, DD, false, false>(f, p, s, &al);
   });
 }
 

@@ -93,6 +93,15 @@ struct BwdWinParams : BwdParams {      // (see FwdWinParams; bwd_dq_win_kernel /
   int win_lo = 0, win_hi = 0;
 };
 
+// The slopes of a linear position bias in the training kernels (fcsa_forward_alibi / fcsa_backward_alibi): a second kernel argument of the
+// entry points that apply it (fwd_alibi_kernel, bwd_dq_alibi_kernel, bwd_dkv_alibi_kernel), as DecodeAlibi is of the cached ones -- the
+// blocks above, and the kernels launched with them alone, are what they were.  The logit of key j for query i gains
+// -slopes[b * sb + h * sh] * |i + M - N - j| (natural units; b: batch entry or packed sequence, h: QUERY head).  ELEMENT strides; sb = 0: [H].
+struct TrainAlibi {
+  const float* slopes;              // device
+  int64_t sb, sh;
+};
+
 struct NormParams {         // grouped l2norm forward:  x -> xn, inv_norm
   View x;                   // [B,H,L,D]
   char* xn;                 // contiguous [B,H,L,D]
@@ -309,6 +318,11 @@ inline int cu_count() {
 
 // dtype: 1 = f16, 2 = bf16 (fcsa_dtype); returns hipError_t of the launch
 hipError_t launch_forward(int dtype, int D, const FwdWinParams& p, hipStream_t s);
+// The same launches with a linear position bias (fcsa_forward_alibi / fcsa_backward_alibi): windowed launches only (p.window set, open
+// sides where the call has no window; no bias, key mask, split or group sweep) on the entry points that take the slopes.
+hipError_t launch_forward_alibi(int dtype, int D, const FwdWinParams& p, const TrainAlibi& al, hipStream_t s);
+hipError_t launch_backward_dq_alibi(int dtype, int D, const BwdWinParams& p, const TrainAlibi& al, hipStream_t s);
+hipError_t launch_backward_dkv_alibi(int dtype, int D, const BwdWinParams& p, const TrainAlibi& al, hipStream_t s);
 // fcsa_fwd3.hip: the 64-rows-per-wave, one-wave-per-SIMD forward for 16-bit D = 128 (launch_forward dispatches to it)
 int forward_wide128_mode(int set);      // debug knob behind fcsa_debug_forward_form: set < 0 queries; returns the previous value
 hipError_t launch_forward_wide128(int dtype, const FwdParams& p, hipStream_t s);

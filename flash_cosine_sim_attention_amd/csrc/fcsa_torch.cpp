@@ -74,7 +74,11 @@ namespace {
   X(forward_kvcache_tree, fcsa_forward_kvcache_tree, false)                               \
   X(kvcache_compact, fcsa_kvcache_compact, false)                                         \
   /* a linear position bias (ALiBi) on the engine step */                                 \
-  X(forward_kvcache_alibi, fcsa_forward_kvcache_alibi, false)
+  X(forward_kvcache_alibi, fcsa_forward_kvcache_alibi, false)                             \
+  /* the same bias in the training kernels, forward and backward */                       \
+  X(forward_alibi, fcsa_forward_alibi, false)                                             \
+  X(backward_alibi, fcsa_backward_alibi, false)                                           \
+  X(backward_alibi_ws, fcsa_backward_alibi_workspace_bytes, false)
 
 struct Abi {
 #define X(member, symbol, required) decltype(&symbol) member = &symbol;
@@ -305,7 +309,8 @@ struct Win {
 // [rows_q, G] / [rows_k, G].  The saved-state tensors are empty (numel 0) where they are not produced.
 using Saved = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
 
-Saved forward_body(const Call& c, bool need_backward, const fcsa_window* win, Lap& lap) {
+// alibi: the slopes of a linear position bias (alibi_train ops; fcsa_forward_alibi takes `win` as it is, NULL included), or nullptr
+Saved forward_body(const Call& c, bool need_backward, const fcsa_window* win, Lap& lap, const fcsa_alibi* alibi = nullptr) {
   const bool l2norm_qk = c.p.l2norm_qk != 0;
   TORCH_CHECK_VALUE(!l2norm_qk || (c.groups >= 1 && c.D % c.groups == 0), "groups (", c.groups, ") must divide the head dimension (", c.D, ")");
   c10::DeviceGuard guard(c.q.device());
@@ -343,7 +348,7 @@ Saved forward_body(const Call& c, bool need_backward, const fcsa_window* win, La
   a.norm.rk = (l2norm_qk && need_backward) ? rk.data_ptr<float>() : nullptr;
   Tensor ws;
   a.workspace = nullptr; a.workspace_bytes = 0;
-  if (!c.packed()) {      // packed sequences never split the key range
+  if (!c.packed() && alibi == nullptr) {      // packed sequences and calls with slopes never split the key range
     size_t need = g_abi.forward_ws(&a.p);      // 0 unless the key range is split (grids that cannot fill the chip)
     if (win != nullptr) {      // a window that IS the un-windowed or the causal call splits like that call: room for either
       fcsa_problem other = a.p;
@@ -357,7 +362,11 @@ Saved forward_body(const Call& c, bool need_backward, const fcsa_window* win, La
   }
   a.stream = stream_of(c.q);
   lap.mark(1);
-  if (c.packed()) {
+  if (alibi != nullptr) {
+    fcsa_varlen t;
+    if (c.packed()) t = varlen_table(c);
+    check(g_abi.forward_alibi(&a, c.packed() ? &t : nullptr, win, alibi), "fcsa_forward_alibi");
+  } else if (c.packed()) {
     const fcsa_varlen t = varlen_table(c);
     if (win != nullptr) check(g_abi.forward_window(&a, &t, win), "fcsa_forward_window");
     else check(g_abi.forward_varlen(&a, &t), "fcsa_forward_varlen");
@@ -400,7 +409,8 @@ Saved varlen_window_forward(const Tensor& q, const Tensor& k, const Tensor& v, c
 using Grads = std::tuple<Tensor, Tensor, Tensor, Tensor>;
 
 Grads backward_body(const Call& c, const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& qn, const Tensor& kn, const Tensor& rq,
-                    const Tensor& rk, bool need_bias_grad, const fcsa_window* win, Lap& lap, const Tensor* d_lse = nullptr) {
+                    const Tensor& rk, bool need_bias_grad, const fcsa_window* win, Lap& lap, const Tensor* d_lse = nullptr,
+                    const fcsa_alibi* alibi = nullptr) {
   const bool l2norm_qk = c.p.l2norm_qk != 0;
   const at::ScalarType dt = c.q.scalar_type();
   const auto dev = c.q.device();
@@ -460,7 +470,8 @@ Grads backward_body(const Call& c, const Tensor& d_out, const Tensor& o, const T
   fcsa_varlen t;
   if (c.packed()) t = varlen_table(c);
   const fcsa_varlen* seqs = c.packed() ? &t : nullptr;
-  size_t wsb = win != nullptr ? g_abi.backward_window_ws(&a.p, seqs, win)
+  size_t wsb = alibi != nullptr ? g_abi.backward_alibi_ws(&a.p, seqs, win)
+               : win != nullptr ? g_abi.backward_window_ws(&a.p, seqs, win)
                : seqs != nullptr ? g_abi.backward_varlen_ws(&a.p, seqs) : g_abi.backward_ws(&a.p);
   if (wsb < 256) wsb = 256;
   Tensor ws = at::empty({(int64_t)wsb}, opt.dtype(at::kByte));      // the caching allocator
@@ -479,7 +490,8 @@ Grads backward_body(const Call& c, const Tensor& d_out, const Tensor& o, const T
   a.workspace = ws.data_ptr(); a.workspace_bytes = wsb;
   a.stream = stream_of(c.q);
   lap.mark(4);
-  if (gl.defined()) check(g_abi.backward_state(&a, seqs, win, gl.data_ptr<float>()), "fcsa_backward_state");
+  if (alibi != nullptr) check(g_abi.backward_alibi(&a, seqs, win, alibi), "fcsa_backward_alibi");
+  else if (gl.defined()) check(g_abi.backward_state(&a, seqs, win, gl.data_ptr<float>()), "fcsa_backward_state");
   else if (win != nullptr) check(g_abi.backward_window(&a, seqs, win), "fcsa_backward_window");
   else if (seqs != nullptr) check(g_abi.backward_varlen(&a, seqs), "fcsa_backward_varlen");
   else check(g_abi.backward(&a), "fcsa_backward");
@@ -1348,6 +1360,87 @@ std::tuple<Tensor, Tensor> attention_state_autograd(const Tensor& q, const Tenso
   return {r[0], r[1]};
 }
 
+// ---- a linear position bias in training (namespace fcsa_alibi_train): one op family for the dense, the local and the packed operator, as
+// attention_state is -- cu_seqlens given: packed q [total_q, H, D]; window sides of (-1, -1): no window -- through the same state_call /
+// forward_body / backward_body, with the slopes handed to fcsa_forward_alibi / fcsa_backward_alibi.  alibi_slopes: float32 [H] or [B, H]
+// (B: batch, packed: sequences) on q's device, any strides, never read on the host.  There is no slope gradient.
+struct TrainSlopes {
+  fcsa_alibi a{};
+  TrainSlopes(const Call& c, const Tensor& slopes) {
+    need_abi("flash_cosine_sim_attention_alibi", "fcsa_forward_alibi / fcsa_backward_alibi", g_abi.forward_alibi, g_abi.backward_alibi, g_abi.backward_alibi_ws);
+    TORCH_CHECK_TYPE(slopes.scalar_type() == at::kFloat, "alibi_slopes must be float32, got ", slopes.scalar_type());
+    TORCH_CHECK_VALUE(slopes.device() == c.q.device(), "alibi_slopes is on ", slopes.device(), " but q is on ", c.q.device(),
+                      ": all tensors must live on q's GPU");
+    const int64_t H = c.p.heads, B = c.p.batch;
+    TORCH_CHECK_VALUE((slopes.dim() == 1 && slopes.size(0) == H) || (slopes.dim() == 2 && slopes.size(0) == B && slopes.size(1) == H),
+                      "alibi_slopes must be [heads] (", H, ") or [", c.packed() ? "sequences" : "batch", ", heads] (", B, ", ", H, "), got ", slopes.sizes());
+    TORCH_CHECK_VALUE(c.packed() || c.p.causal || c.p.q_len <= c.p.k_len, "alibi_slopes: a non-causal call needs q_len <= k_len, got ", c.p.q_len,
+                      " > ", c.p.k_len, " (rows with a negative position have no key at distance 0)");
+    a.slopes = slopes.numel() > 0 ? slopes.data_ptr<float>() : nullptr;
+    a.stride_b = slopes.dim() == 2 ? slopes.stride(0) : 0;
+    a.stride_h = slopes.stride(-1);
+    a.reserved = 0;
+  }
+};
+
+Saved alibi_train_forward(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& alibi_slopes, const optional<Tensor>& cu_q,
+                          const optional<Tensor>& cu_k, int64_t max_q, int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups,
+                          int64_t left, int64_t right, bool need_backward) {
+  const OptWin win(left, right);
+  const Call c = state_call(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups);
+  const TrainSlopes sl(c, alibi_slopes);
+  Lap lap(false);
+  return forward_body(c, need_backward, win.ptr(), lap, &sl.a);
+}
+Grads3 alibi_train_backward(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k, const Tensor& v,
+                            const Tensor& alibi_slopes, const optional<Tensor>& cu_q, const optional<Tensor>& cu_k, const Tensor& qn,
+                            const Tensor& kn, const Tensor& rq, const Tensor& rk, int64_t max_q, int64_t max_k, double scale, bool causal,
+                            bool l2norm_qk, int64_t groups, int64_t left, int64_t right) {
+  const OptWin win(left, right);
+  const Call c = state_call(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups);
+  const TrainSlopes sl(c, alibi_slopes);
+  Lap lap(false);
+  return first3(backward_body(c, d_out, o, inv_l, qn, kn, rq, rk, false, win.ptr(), lap, nullptr, &sl.a));
+}
+
+struct AlibiTrainNode : public torch::autograd::Function<AlibiTrainNode> {
+  static Tensor forward(AutogradContext* ctx, const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& slopes, const optional<Tensor>& cu_q,
+                        const optional<Tensor>& cu_k, const StateScalars& s) {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    static auto op = typed_op("fcsa_alibi_train::forward", &alibi_train_forward);
+    auto r = std::apply([&](const auto&... e) { return op.call(q, k, v, slopes, cu_q, cu_k, e..., true); }, s);
+    ctx->save_for_backward({std::get<0>(r), std::get<1>(r), q, k, v, std::get<2>(r), std::get<3>(r), std::get<4>(r), std::get<5>(r),
+                            saveable(cu_q), saveable(cu_k), slopes});
+    ctx->saved_data["scalars"] = c10::IValue(s);
+    return std::get<0>(r);
+  }
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    const auto t = ctx->get_saved_variables();      // o, inv_l, q, k, v, qn, kn, rq, rk, cu_q, cu_k, slopes
+    const StateScalars s = ctx->saved_data["scalars"].to<StateScalars>();
+    static auto op = typed_op("fcsa_alibi_train::backward", &alibi_train_backward);
+    const optional<Tensor> cu_q = restored<optional<Tensor>>(t[9]), cu_k = restored<optional<Tensor>>(t[10]);
+    auto g = std::apply([&](const auto&... e) { return op.call(grads[0], t[0], t[1], t[2], t[3], t[4], t[11], cu_q, cu_k, t[5], t[6], t[7], t[8], e...); }, s);
+    return {std::get<0>(g), std::get<1>(g), std::get<2>(g), Tensor(), Tensor(), Tensor(), Tensor()};
+  }
+};
+
+Tensor alibi_train_attention_plain(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& alibi_slopes, const optional<Tensor>& cu_q,
+                                   const optional<Tensor>& cu_k, int64_t max_q, int64_t max_k, double scale, bool causal, bool l2norm_qk,
+                                   int64_t groups, int64_t left, int64_t right) {
+  return std::get<0>(alibi_train_forward(q, k, v, alibi_slopes, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, left, right, false));
+}
+Tensor alibi_train_attention_autograd(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& alibi_slopes, const optional<Tensor>& cu_q,
+                                      const optional<Tensor>& cu_k, int64_t max_q, int64_t max_k, double scale, bool causal, bool l2norm_qk,
+                                      int64_t groups, int64_t left, int64_t right) {
+  TORCH_CHECK_VALUE(!alibi_slopes.requires_grad(), "alibi_slopes must not require grad: there is no slope gradient (fixed slopes only)");
+  if (!(at::GradMode::is_enabled() && (q.requires_grad() || k.requires_grad() || v.requires_grad()))) {
+    at::AutoDispatchBelowADInplaceOrView guard;      // (through the dispatcher again, below autograd: fake tensors reach the fake kernel)
+    static auto op = typed_op("fcsa_alibi_train::attention", &alibi_train_attention_plain);
+    return op.call(q, k, v, alibi_slopes, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, left, right);
+  }
+  return AlibiTrainNode::apply(q, k, v, alibi_slopes, cu_q, cu_k, StateScalars{max_q, max_k, scale, causal, l2norm_qk, groups, left, right});
+}
+
 // merge_state: merge_states (the same function: the forward kernel, bit for bit) with a backward.
 // merge_state_backward: (d_o?, d_lse?, os, lses) -> (d_os, d_lses); an absent d_o is zeros, an absent d_lse is no gradient for the lse.
 std::tuple<std::vector<Tensor>, std::vector<Tensor>> merge_state_backward(const optional<Tensor>& d_o, const optional<Tensor>& d_lse, at::TensorList os,
@@ -1608,6 +1701,25 @@ TORCH_LIBRARY_IMPL(fcsa_state, Autograd, m) {
   m.impl("attention_state", &attention_state_autograd);
   m.impl("merge_state", &merge_state_autograd);
 }
+
+// The training calls with a linear position bias, in a namespace of their own (the op sets of `fcsa` and `fcsa_alibi` are pinned): forward,
+// backward, and the differentiable attention op -- dense, local or packed, as in fcsa_state.
+TORCH_LIBRARY(fcsa_alibi_train, m) {
+  m.def("forward(Tensor q, Tensor k, Tensor v, Tensor alibi_slopes, Tensor? cu_seqlens_q, Tensor? cu_seqlens_k, int max_seqlen_q, "
+        "int max_seqlen_k, float scale, bool causal, bool l2norm_qk, int groups, int window_left, int window_right, bool need_backward) "
+        "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("backward(Tensor d_out, Tensor o, Tensor inv_l, Tensor q, Tensor k, Tensor v, Tensor alibi_slopes, Tensor? cu_seqlens_q, "
+        "Tensor? cu_seqlens_k, Tensor qn, Tensor kn, Tensor rq, Tensor rk, int max_seqlen_q, int max_seqlen_k, float scale, bool causal, "
+        "bool l2norm_qk, int groups, int window_left, int window_right) -> (Tensor, Tensor, Tensor)");
+  m.def("attention(Tensor q, Tensor k, Tensor v, Tensor alibi_slopes, Tensor? cu_seqlens_q, Tensor? cu_seqlens_k, int max_seqlen_q, "
+        "int max_seqlen_k, float scale, bool causal, bool l2norm_qk, int groups, int window_left, int window_right) -> Tensor");
+}
+TORCH_LIBRARY_IMPL(fcsa_alibi_train, CUDA, m) {
+  m.impl("forward", &alibi_train_forward);
+  m.impl("backward", &alibi_train_backward);
+  m.impl("attention", &alibi_train_attention_plain);
+}
+TORCH_LIBRARY_IMPL(fcsa_alibi_train, Autograd, m) { m.impl("attention", &alibi_train_attention_autograd); }
 
 TORCH_LIBRARY_IMPL(fcsa, Autograd, m) {
   m.impl("attention", &attention_autograd);

@@ -263,6 +263,83 @@ def flash_cosine_sim_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_s
 
 
 # ---------------------------------------------------------------------------------------------
+# a linear position bias (ALiBi) in training: dense, local and packed calls with per-head slopes, forward and backward
+# ---------------------------------------------------------------------------------------------
+
+def flash_cosine_sim_attention_alibi(q, k, v, alibi_slopes, scale=8, groups=1, causal=False, l2norm_qk=True, window_size=(-1, -1),
+                                     cu_seqlens_q=None, cu_seqlens_k=None, max_seqlen_q=None, max_seqlen_k=None):
+    """`flash_cosine_sim_attention` (4-D q, k, v), `flash_cosine_sim_attention_local` (with a window_size) or
+    `flash_cosine_sim_attention_varlen` (packed 3-D q, k, v with cu_seqlens_q / cu_seqlens_k) with a linear position bias applied in
+    registers: the training side of `flash_cosine_sim_attention_alibi_with_kvcache`, differentiable w.r.t. q, k, v.
+
+    alibi_slopes: a float32 tensor [H] or [B, H] (B: the batch, or the number of sequences of a packed call), indexed by the QUERY head, so
+    with grouped K/V every query head keeps its own slope.  With pos_i = i + M - N (the bottom-right alignment of causal and of the
+    window, per sequence when packed) the logit of key j gains -alibi_slopes[b, h] * |pos_i - j|, in natural units after scale: the
+    definition of the cached call, so a trained model is served unchanged.  Nothing of size [H, N, M] is read or written, and a window
+    or packed sequences -- which refuse attn_bias -- combine with it.
+    Slopes must be >= 0: the bias is a penalty.  Host slopes are checked (finite, non-negative) and moved to q's device without blocking;
+    device slopes are trusted and never read on the host, so the call does not synchronise and can be captured in a graph (slopes
+    changed in place are picked up on replay).  A negative device slope is numerically undefined, never an access out of bounds.
+    There is no slope gradient (alibi_slopes.requires_grad is refused), no mask and no attn_bias.
+    Numerics: the bias is <= 0, so the call runs the exponent regime of the same call without slopes (bfloat16 / float32, and float16 up
+    to scale * groups = 11, keep the static shift); a weight that underflows is an exact 0.  Zero slopes equal the local / packed windowed
+    call on the same window bit for bit.
+    A non-causal call needs N <= M (for every sequence of a host table): a row with pos_i < 0 has no key at distance 0, so a steep slope
+    could push its whole row under the static window.  Under causal with N > M, rows without a visible key give 0, as in every call.
+    Table checks and max_seqlen rules of `flash_cosine_sim_attention_varlen`.  CPU tensors take the forward-only path of `cpu.py`."""
+    window = _window(window_size)
+    if not isinstance(alibi_slopes, torch.Tensor) or alibi_slopes.dtype != torch.float32:
+        raise TypeError(f"alibi_slopes must be a float32 tensor of shape [heads] or [batch, heads], got "
+                        f"{getattr(alibi_slopes, 'dtype', type(alibi_slopes).__name__)}")
+    if alibi_slopes.requires_grad:
+        raise ValueError("alibi_slopes must not require grad: there is no slope gradient (fixed slopes only)")
+    packed = cu_seqlens_q is not None or cu_seqlens_k is not None
+    if packed:
+        if cu_seqlens_q is None or cu_seqlens_k is None:
+            raise ValueError("cu_seqlens_q and cu_seqlens_k must be given together")
+        max_seqlen_q, max_seqlen_k = _check_packed(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
+        H, B = q.shape[1], cu_seqlens_q.numel() - 1
+        if not causal and cu_seqlens_q.device.type == "cpu" and cu_seqlens_k.device.type == "cpu":
+            nq, nk = cu_seqlens_q[1:] - cu_seqlens_q[:-1], cu_seqlens_k[1:] - cu_seqlens_k[:-1]
+            if bool((nq > nk).any()):
+                raise ValueError("alibi_slopes: a non-causal call needs N <= M for every sequence (rows with a negative position have no key "
+                                 "at distance 0)")
+    else:
+        if max_seqlen_q is not None or max_seqlen_k is not None:
+            raise ValueError("max_seqlen_q / max_seqlen_k belong to packed calls (cu_seqlens_q, cu_seqlens_k)")
+        if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+            raise ValueError("flash_cosine_sim_attention_alibi takes 4-D q, k, v ([batch, heads, length, dim_head]), or packed 3-D ones "
+                             "with cu_seqlens_q and cu_seqlens_k")
+        H, B = q.shape[1], q.shape[0]
+        if not causal and q.shape[2] > k.shape[2]:
+            raise ValueError(f"alibi_slopes: a non-causal call needs N <= M, got N = {q.shape[2]} > M = {k.shape[2]} (rows with a negative "
+                             "position have no key at distance 0)")
+    if tuple(alibi_slopes.shape) not in ((H,), (B, H)):
+        raise ValueError(f"alibi_slopes must have shape [{H}] or [{B}, {H}] (heads, or {'sequences' if packed else 'batch'} x heads), got "
+                         f"{tuple(alibi_slopes.shape)}")
+    if alibi_slopes.device.type == "cpu":
+        if not bool(torch.isfinite(alibi_slopes).all()) or bool((alibi_slopes < 0).any()):
+            raise ValueError("alibi_slopes must be finite and >= 0 (the bias is a penalty)")
+    elif alibi_slopes.device != q.device:
+        raise ValueError(f"alibi_slopes is on {alibi_slopes.device} but q is on {q.device}")
+    if q.device.type == "cpu":
+        if alibi_slopes.device.type != "cpu":
+            raise ValueError("CPU tensors take host alibi_slopes")
+        if packed:
+            return _cpu.attention_forward_varlen_cpu(q, k, v, cu_seqlens_q, cu_seqlens_k, scale=scale, groups=groups, causal=causal,
+                                                     l2norm_qk=l2norm_qk, window_size=window, alibi_slopes=alibi_slopes)
+        return _cpu.attention_forward_cpu(q, k, v, scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, window_size=window,
+                                          alibi_slopes=alibi_slopes)
+    cu_q = cu_k = None
+    max_q = max_k = 0
+    if packed:
+        cu_q, cu_k, max_q, max_k = _packed_on_device(q, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
+    _torch_ops.load()
+    return torch.ops.fcsa_alibi_train.attention(q, k, v, alibi_slopes.to(q.device, non_blocking=True), cu_q, cu_k, max_q, max_k, float(scale),
+                                                bool(causal), bool(l2norm_qk), int(groups), window[0], window[1])
+
+
+# ---------------------------------------------------------------------------------------------
 # decoding against a key/value cache (flash-attn's kvcache convention; no reference counterpart)
 # ---------------------------------------------------------------------------------------------
 
@@ -703,7 +780,7 @@ def flash_cosine_sim_attention_alibi_with_kvcache(q, k_cache, v_cache, cu_seqlen
     the per-row-shift regime (the online row maximum includes the bias) whatever dtype, scale and l2norm_qk say.  Zero slopes therefore
     equal the step call bit for bit only where that call runs the same regime (e.g. float16 at scale 16), and within rounding elsewhere.
     Not taken by: the tree call (a tree token's position is its depth, not its slot), the shared-prefix call (its prefix phase mixes
-    sequences with different positions in one B = 1 call) and the training kernels (training keeps attn_bias).  CPU tensors take the
+    sequences with different positions in one B = 1 call).  Training with the same bias: `flash_cosine_sim_attention_alibi`.  CPU tensors take the
     forward-only path of `cpu.py` (host slopes).  Forward only."""
     fn = "flash_cosine_sim_attention_alibi_with_kvcache"
     if alibi_slopes is None:

@@ -463,8 +463,8 @@ int    fcsa_forward_kvcache_tree(const fcsa_forward_args* args, const fcsa_kvcac
  * Where the chunk kernel does not exist for the problem (FCSA_F32, or dim_head other than 64 and 128) every sequence takes the decode
  * kernel with key splits (the ragged call's plan and workspace, as in fcsa_forward_kvcache_step); `step` is checked and otherwise ignored.
  * alibi or alibi->slopes NULL, slopes not 4-byte aligned, reserved != 0: FCSA_ERR_INVALID_ARG, before any launch.
- * Not offered: a bias on fcsa_forward_kvcache_tree (a tree token's position is its depth, not its slot) and on the training kernels
- * (fcsa_forward takes attn_bias).
+ * Not offered: a bias on fcsa_forward_kvcache_tree (a tree token's position is its depth, not its slot).  The training kernels take the
+ * same bias through fcsa_forward_alibi / fcsa_backward_alibi (below).
  * Launches: "kv_append_ragged[_fp8]" (when appending) and the combine of the step call ("step_combine[_lse][_fp8]", or
  * "decode_combine[_lse]_ragged[_fp8]" where there is no chunk kernel), unchanged; "alibi_decode[_fp8]" (skipped under no_decode) and
  * "alibi_prefill[_fp8]" (skipped under no_chunk). */
@@ -477,6 +477,38 @@ typedef struct fcsa_alibi {
 int    fcsa_forward_kvcache_alibi(const fcsa_forward_args* args, const fcsa_kvcache* cache, const fcsa_varlen* seqs,
                                   const fcsa_kvcache_quant* quant, const fcsa_window* window, const fcsa_kvcache_step* step,
                                   const fcsa_alibi* alibi, const fcsa_lse_out* lse_out);
+
+/* The same linear position bias in the training kernels, forward and backward: fcsa_forward_window / fcsa_backward_window with one more
+ * argument, the slopes (additive: no existing struct changes and FCSA_ABI_VERSION stays 4).  A model trained through these entries is
+ * served unchanged by fcsa_forward_kvcache_alibi: the definition is the same.
+ *   seqs, window    : nullable, with the meaning they have on fcsa_forward_window -- seqs NULL: a dense call; window NULL: no window
+ *                     ((-1, -1)).  mask, attn_bias and d_bias must be NULL (FCSA_ERR_INVALID_ARG).
+ *   alibi->slopes   : device float32 (4-byte aligned); the slope of batch entry (packed: sequence) b, QUERY head h is
+ *                     slopes[b * stride_b + h * stride_h] (ELEMENT strides; stride_b = 0: one [H] row for every b).  With grouped K/V
+ *                     every query head keeps its own slope.  Device data, never read by the host: no synchronisation, capturable.
+ * Meaning: with pos_i = i + M - N (the bottom-right alignment of `causal` and of the window; packed: per sequence, M_s - N_s), the logit
+ * of key j gains  -slope[b, h] * |pos_i - j|  in natural units, after p.scale.  The distance is a float32 integer (exact below 2^24
+ * positions); its product with slope * log2(e) is rounded once, inside the fused multiply-add that seeds the logit's accumulator.  The
+ * backward recomputes the same seeds, so its P is the forward's bit for bit; the bias is a constant, so dS = P (dP - delta) needs
+ * nothing else and there is no slope gradient.
+ * Sign rule: slopes must be >= 0 -- the bias is a penalty.  The host cannot check device values; a negative slope is numerically
+ * undefined (weights may overflow the static window), never an access out of bounds.
+ * Regime: the bias is <= 0, so the static exponent shift of the call without slopes stays an upper bound and the call runs that call's
+ * regime (static for FCSA_BF16 / FCSA_F32 and for FCSA_F16 up to scale * groups = 11, per-row shift beyond); a weight that underflows is
+ * an exact 0.  A slope of 0 equals fcsa_forward_window / fcsa_backward_window on the same window and table bit for bit wherever those run
+ * the windowed kernel forms.
+ * N <= M rule: a non-causal dense call with q_len > k_len is refused (FCSA_ERR_INVALID_ARG): its first rows have pos_i < 0 and no key at
+ * distance 0, so a steep slope could push a whole row under the static window.  (Packed calls: the caller checks its own table; the device
+ * table is trusted.)  Under `causal` such rows see no key and give o = 0 and zero gradients, as in every call.
+ * Forms: every call is a windowed launch whose sides may both be unbounded -- the forms of a packed / windowed call: no split launch, no
+ * 64-rows-per-wave forward form, no grouped-query head sweep (grouped K/V: per-query-head slabs plus the finalize kernel).
+ * alibi or alibi->slopes NULL, slopes not 4-byte aligned, reserved != 0: FCSA_ERR_INVALID_ARG, before any launch.
+ * Launches: "l2norm", "fwd" / "bwd_dq", "bwd_dkv", "finalize" as in fcsa_forward_window / fcsa_backward_window. */
+int    fcsa_forward_alibi(const fcsa_forward_args* args, const fcsa_varlen* seqs, const fcsa_window* window, const fcsa_alibi* alibi);
+int    fcsa_backward_alibi(const fcsa_backward_args* args, const fcsa_varlen* seqs, const fcsa_window* window, const fcsa_alibi* alibi);
+/* Scratch the two calls need for this problem, table (NULL: dense) and window (NULL: none); the forward needs none */
+size_t fcsa_forward_alibi_workspace_bytes(const fcsa_problem* p, const fcsa_varlen* seqs, const fcsa_window* window);
+size_t fcsa_backward_alibi_workspace_bytes(const fcsa_problem* p, const fcsa_varlen* seqs, const fcsa_window* window);
 
 /* Compaction of the accepted path after a tree step.  The step appended N_b tokens at [cache_seqlens[b], cache_seqlens[b] + N_b); the
  * verifier accepted a root-to-leaf path of them, which must sit at the front of those slots before the next step.  In place:
