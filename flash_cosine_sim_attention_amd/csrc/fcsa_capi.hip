@@ -260,9 +260,9 @@ fcsa_problem packed_problem(const fcsa_problem& p, const fcsa_varlen& v) {
 }
 // a varlen call: the table and the caller's problem (batch = sequences, q_len / k_len = the longest spans)
 struct VarlenCall { const fcsa_varlen* t; int batch, max_q, max_k; };
-fcsa::SeqTable seq_table(const VarlenCall* v) {
+fcsa::SeqTable seq_table(const fcsa_varlen* v) {      // nullptr: a dense call
   if (v == nullptr) return fcsa::SeqTable{nullptr, nullptr, 0, 0};
-  return fcsa::SeqTable{v->t->cu_seqlens_q, v->t->cu_seqlens_k, (int)v->t->total_q, (int)v->t->total_k};
+  return fcsa::SeqTable{v->cu_seqlens_q, v->cu_seqlens_k, (int)v->total_q, (int)v->total_k};
 }
 fcsa_tensor packed(fcsa_tensor t) {       // stride0 of a packed tensor is meaningless: one "batch" of total rows
   t.stride0 = 0;
@@ -278,10 +278,405 @@ int check_window(const fcsa_window* w, bool mask, bool bias) {
   return FCSA_OK;
 }
 
-// al != nullptr: a linear position bias (fcsa_forward_alibi / fcsa_backward_alibi; win is set then, with open sides where the call has no window)
-int forward_impl(const fcsa_forward_args* a, const VarlenCall* vl, const WindowCall* win = nullptr, const fcsa::TrainAlibi* al = nullptr);
-int backward_impl(const fcsa_backward_args* a, const VarlenCall* vl, const WindowCall* win = nullptr, const float* dlse = nullptr,
-                  const fcsa::TrainAlibi* al = nullptr);
+// the checks of a call with slopes (fcsa_forward_alibi / fcsa_backward_alibi): its options, its window where it has one, the slopes
+int check_alibi(const fcsa_problem& p, const fcsa_varlen* seqs, const fcsa_window* w, const fcsa_alibi* al, bool mask, bool bias) {
+  if (mask || bias) return fail(FCSA_ERR_INVALID_ARG, "alibi: mask and attn_bias are not supported with alibi_slopes");
+  if (w != nullptr) {
+    if (int rc = check_window(w, false, false)) return rc;
+  }
+  if (al == nullptr || al->slopes == nullptr) return fail(FCSA_ERR_INVALID_ARG, "alibi: null slopes");
+  if ((reinterpret_cast<uintptr_t>(al->slopes) & 3) != 0) return fail(FCSA_ERR_INVALID_ARG, "alibi: slopes not 4-byte aligned");
+  if (al->reserved != 0) return fail(FCSA_ERR_INVALID_ARG, "alibi: reserved must be 0");
+  if (seqs == nullptr && !p.causal && p.q_len > p.k_len)
+    return fail(FCSA_ERR_INVALID_ARG, "alibi: a non-causal call needs q_len <= k_len (%d > %d): rows with pos_i < 0 have no key at distance 0", p.q_len, p.k_len);
+  return FCSA_OK;
+}
+
+// split-key forward (fcsa::forward_splits: bias-free launches only): the count, and its workspace -- partial P~V, then partial row sums
+int forward_splits(const fcsa_problem& p) {
+  if (p.batch <= 0 || p.heads <= 0 || p.q_len <= 0 || p.dim_head <= 0) return 1;
+  return fcsa::forward_splits(p, dynamic_shift(p, false), fcsa::cu_count());
+}
+size_t forward_ws_bytes(const fcsa_problem& p, int splits) {
+  if (splits <= 1) return 0;
+  const size_t rows = (size_t)splits * p.batch * p.heads * p.q_len;
+  return align_up(rows * p.dim_head * 4, 256) + align_up(rows * 4, 256);
+}
+
+// Zero-size problems (empty tensors: what torch hands over has NULL data pointers then).  batch, heads or q_len == 0: the forward has no
+// output element; k_len == 0: every query row is a row without a valid key, for which the kernels' semantics are o = 0 (cu:1239) and
+// finite (zero) gradients.  Nothing is launched; the outputs that DO have elements are zero-filled on the caller's stream, row by row
+// (any strides).  The reference launches a zero-sized grid there (a CUDA error it prints and ignores, cu:17-28).
+int zero_rows(const char* name, const fcsa_tensor& t, int es, int B, int H, int L, int D, hipStream_t s) {
+  if (B <= 0 || H <= 0 || L <= 0) return FCSA_OK;
+  if (int rc = check_tensor(name, t, es, true)) return rc;
+  for (int b = 0; b < B; ++b)
+    for (int h = 0; h < H; ++h) {
+      char* base = static_cast<char*>(t.ptr) + ((int64_t)b * t.stride0 + (int64_t)h * t.stride1) * es;
+      const hipError_t e = t.stride2 == D ? hipMemsetAsync(base, 0, (size_t)L * D * es, s)
+                                          : hipMemset2DAsync(base, (size_t)t.stride2 * es, 0, (size_t)D * es, (size_t)L, s);
+      if (e != hipSuccess) return fail(FCSA_ERR_LAUNCH, "%s: zero fill failed: %s", name, hipGetErrorString(e));
+    }
+  return FCSA_OK;
+}
+
+// ---- the training calls (fcsa_forward, fcsa_backward and their _varlen, _window, _alibi and _state forms) -------------------------------
+// One description of a training call, TrainCall, and one implementation per direction (train_forward, train_backward) behind the nine
+// entry points: what an entry point adds to the plain call is an optional part of the description.
+enum class TrainNeeds { Nothing, Seqs, Window, Slopes };      // the part an entry point requires: NULL there is refused, not "absent"
+struct TrainCall {
+  TrainNeeds needs;
+  const fcsa_forward_args* fwd;           // the caller's arguments: of train_forward ...
+  const fcsa_backward_args* bwd;          // ... or of train_backward
+  const fcsa_varlen* seqs;                // packed sequences, or NULL
+  const fcsa_window* w;                   // a sliding window as the caller gave it, or NULL
+  const fcsa_alibi* alibi = nullptr;      // the slopes of a linear position bias (TrainNeeds::Slopes)
+  const float* d_lse = nullptr;           // the LSE gradient of fcsa_backward_state, or NULL
+};
+
+// The window of a training call as the kernels take it (fcsa::win_normalise, on the caller's lengths: a packed call's longest spans).
+// true: a windowed launch (the windowed kernel forms; the plan of a packed call: no split, no group sweep) with the sides in `win`.
+// false: no window, or one that hides nothing, which is the un-windowed or the causal call: p.causal then says which.  A call with slopes
+// always keeps sides -- (open, open) and (open, 0) included, which the windowed kernel forms serve like any other pair.
+bool train_window(fcsa_problem& p, const fcsa_window* w, bool slopes, WindowCall& win) {
+  if (w == nullptr && !slopes) return false;
+  const fcsa::WinKind kind = fcsa::win_normalise(p.q_len, p.k_len, p.causal != 0, w != nullptr ? w->left : -1, w != nullptr ? w->right : -1, win.lo, win.hi);
+  if (slopes || kind == fcsa::WinKind::Window) return true;
+  p.causal = kind == fcsa::WinKind::Causal ? 1 : 0;
+  return false;
+}
+
+// What the launches take of a call's options
+struct TrainLaunch {
+  bool slopes, windowed, packed;
+  fcsa::TrainAlibi al;      // slopes
+  WindowCall win;           // windowed
+  VarlenCall vl;            // packed
+};
+
+// What every training call starts with, once and in this order: the problem; the checks of its options -- the slopes with their window, or
+// the window, then the sequence table --; the window's normalisation; the packing, after which p is the problem of the packed rows.
+int train_options(const TrainCall& c, fcsa_problem& p, bool mask, bool bias, TrainLaunch& t) {
+  if (int rc = check_problem(p)) return rc;
+  t.slopes = c.needs == TrainNeeds::Slopes;
+  if (t.slopes) {
+    if (int rc = check_alibi(p, c.seqs, c.w, c.alibi, mask, bias)) return rc;
+    t.al = fcsa::TrainAlibi{c.alibi->slopes, c.alibi->stride_b, c.alibi->stride_h};
+  } else if (c.w != nullptr || c.needs == TrainNeeds::Window) {
+    if (int rc = check_window(c.w, mask, bias)) return rc;
+  }
+  t.windowed = train_window(p, c.w, t.slopes, t.win);
+  t.packed = c.seqs != nullptr || c.needs == TrainNeeds::Seqs;
+  if (t.packed) {
+    if (int rc = check_varlen(p, c.seqs, mask, bias)) return rc;
+    t.vl = {c.seqs, p.batch, p.q_len, p.k_len};
+    p = packed_problem(p, *c.seqs);
+  }
+  return FCSA_OK;
+}
+
+// The backward workspace of a (p, seqs, window, slopes?) call: that of the launch train_backward makes of it.  (With slopes the window
+// plays no part: always the plan of a windowed launch.)
+size_t bwd_workspace(fcsa_problem p, const fcsa_varlen* seqs, const fcsa_window* w, bool slopes) {
+  if (seqs != nullptr && (seqs->total_q < 0 || seqs->total_k < 0)) return 0;
+  WindowCall win;
+  const bool windowed = train_window(p, w, slopes, win);
+  if (seqs != nullptr) p = packed_problem(p, *seqs);
+  return bwd_layout(p, seqs != nullptr || windowed).total;
+}
+
+int train_forward(const TrainCall& c) {
+  if (c.fwd == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
+  fcsa_forward_args call = *c.fwd;      // the call as the launches see it: a collapsed window's `causal`, a packed call's problem and views
+  TrainLaunch t;
+  if (int rc = train_options(c, call.p, call.mask != nullptr, call.attn_bias != nullptr, t)) return rc;
+  if (t.packed) { call.q = packed(call.q); call.k = packed(call.k); call.v = packed(call.v); call.o = packed(call.o); }
+  const fcsa_forward_args* a = &call;
+  const fcsa_problem& p = a->p;
+  if (p.causal && a->mask != nullptr) return fail(FCSA_ERR_INVALID_ARG, "mask should not be given if causal (cu:1675)");
+  const int es = elem_size(p.dtype);
+  if (p.batch == 0 || p.heads == 0 || p.q_len == 0) return FCSA_OK;      // no output element (k-side saved state is not needed by a backward either)
+  if (p.k_len == 0) {                                                     // rows without a key: o = 0; inv_l = 1 (never read: the backward below has no key to visit)
+    hipStream_t s0 = static_cast<hipStream_t>(a->stream);
+    if (int rc = zero_rows("o", a->o, es, p.batch, p.heads, p.q_len, p.dim_head, s0)) return rc;
+    if (a->inv_l != nullptr) {
+      const float one = 1.f;
+      uint32_t bits; memcpy(&bits, &one, 4);
+      if (hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a->inv_l), (int)bits, (size_t)p.batch * p.heads * p.q_len, s0) != hipSuccess)
+        return fail(FCSA_ERR_LAUNCH, "inv_l: fill failed");
+    }
+    return FCSA_OK;
+  }
+  if (int rc = check_tensor("q", a->q, es, true)) return rc;
+  if (int rc = check_tensor("k", a->k, es, true)) return rc;
+  if (int rc = check_tensor("v", a->v, es, true)) return rc;
+  if (int rc = check_tensor("o", a->o, es, true)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(a->stream);
+  const bool single = p.kv_heads == 1 && p.heads > 1;      // one K/V head: stride-0 head views; grouped K/V: kv_group query heads per K/V head
+
+  fcsa::FwdWinParams fp;
+  fp.kv_group = single ? 1 : p.heads / p.kv_heads;
+  bool fuse_q = false;
+  fp.q = view(a->q, es);
+  fp.k = view(a->k, es, single);
+  fp.v = view(a->v, es, single);
+  fp.o = view(a->o, es);
+  if (p.l2norm_qk) {
+    const fcsa_norm_state& n = a->norm;
+    if (n.kn == nullptr) return fail(FCSA_ERR_INVALID_ARG, "l2norm_qk needs the norm.kn buffer");
+    if (n.qn == nullptr && fcsa_forward_needs_qn(&p, a->inv_l != nullptr || n.rq != nullptr))
+      return fail(FCSA_ERR_INVALID_ARG, "l2norm_qk needs the norm.qn buffer for this problem (fcsa_forward_needs_qn)");
+    fcsa::NormParams nq, nk;
+    nq.eps = nk.eps = 1e-12f;
+    nq.D = nk.D = p.dim_head; nq.G = nk.G = p.groups;
+    nq.x = fp.q; nq.xn = static_cast<char*>(n.qn); nq.inv_norm = n.rq;
+    nq.B = p.batch; nq.H = p.heads; nq.L = p.q_len;
+    nq.out_scale = p.scale * kLog2e;       // qn = c1 * q^ (one rounding): the kernels then need no per-logit multiply
+    nk.x = view(a->k, es); nk.xn = static_cast<char*>(n.kn); nk.inv_norm = n.rk;
+    nk.B = p.batch; nk.H = p.kv_heads; nk.L = p.k_len;
+    nk.out_scale = 1.f;
+    // 16-bit types with group sizes of 8 * 2^k: q is normalised in the forward kernel's prologue (load_q_frags), which also
+    // writes qn / rq for the backward; only k takes the HBM pass.  Otherwise both go through the row kernel.
+    fuse_q = p.dtype != FCSA_F32 && fusable_groups(p);
+    if (fuse_q) {
+      if (int rc = timed("l2norm", "l2norm(k)", s, [&] { return fcsa::launch_l2norm(p.dtype, nk, s); })) return rc;
+    } else {
+      if (int rc = timed("l2norm", "l2norm(q,k)", s, [&] { return fcsa::launch_l2norm_pair(p.dtype, nq, nk, s); })) return rc;
+    }
+    if (!fuse_q) fp.q = contiguous_view(n.qn, p.heads, p.q_len, p.dim_head, es);
+    fp.k = contiguous_view(n.kn, p.kv_heads, p.k_len, p.dim_head, es, single);
+  }
+  fp.inv_l = a->inv_l;
+  fp.mask = a->mask;
+  fp.bias = static_cast<const char*>(a->attn_bias);
+  fp.B = p.batch; fp.H = p.heads; fp.N = p.q_len; fp.M = p.k_len;
+  fp.seq = seq_table(t.packed ? t.vl.t : nullptr);
+  if (t.packed) { fp.B = t.vl.batch; fp.N = t.vl.max_q; fp.M = t.vl.max_k; }      // the sequences and their longest spans
+  fp.causal = p.causal; fp.bias_batch = p.bias_batch_dim;
+  if (t.windowed) { fp.window = 1; fp.win_lo = t.win.lo; fp.win_hi = t.win.hi; fp.causal = 1; }      // (a causal launch with moved diagonals: fcsa_dispatch.h)
+  fp.c1 = p.scale * kLog2e;
+  const bool has_bias = a->attn_bias != nullptr;
+  fp.c2 = exponent_shift(p, has_bias) * kLog2e;
+  fp.bias_c = kLog2e;
+  fp.l_eps = rowsum_eps(p, has_bias);
+  fp.q_scaled = p.l2norm_qk ? 1 : 0;
+  fp.q_raw = fuse_q ? 1 : 0;
+  fp.qn_out = fuse_q ? static_cast<char*>(a->norm.qn) : nullptr;
+  fp.rq_out = fuse_q ? a->norm.rq : nullptr;
+  fp.G = p.groups; fp.lgm = fuse_q ? log2_blocks_per_group(p) : 0; fp.norm_eps = 1e-12f;
+  fp.dyn = dynamic_shift(p, has_bias) ? 1 : 0;      // then inv_l holds log2 of the normaliser
+  fp.splits = 1; fp.ws_o = nullptr; fp.ws_l = nullptr;
+  if (a->workspace != nullptr && a->attn_bias == nullptr && !t.packed && !t.windowed) {      // (packed and windowed launches never split)
+    const int sp = forward_splits(p);
+    if (sp > 1 && a->workspace_bytes >= forward_ws_bytes(p, sp) && (reinterpret_cast<uintptr_t>(a->workspace) & 255) == 0) {
+      const size_t rows = (size_t)sp * p.batch * p.heads * p.q_len;
+      fp.splits = sp;
+      fp.ws_o = static_cast<float*>(a->workspace);
+      fp.ws_l = reinterpret_cast<float*>(static_cast<char*>(a->workspace) + align_up(rows * p.dim_head * 4, 256));
+    }
+  }
+  if (t.slopes) return timed("fwd", "forward", s, [&] { return fcsa::launch_forward_alibi(p.dtype, p.dim_head, fp, t.al, s); });
+  return timed("fwd", "forward", s, [&] { return fcsa::launch_forward(p.dtype, p.dim_head, fp, s); });
+}
+
+int train_backward(const TrainCall& c) {
+  if (c.bwd == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
+  fcsa_backward_args call = *c.bwd;      // the call as the launches see it, as in train_forward
+  TrainLaunch t;
+  if (int rc = train_options(c, call.p, call.mask != nullptr, call.attn_bias != nullptr || call.d_bias != nullptr, t)) return rc;
+  if (t.packed) {
+    call.d_out = packed(call.d_out); call.o = packed(call.o); call.q = packed(call.q); call.k = packed(call.k); call.v = packed(call.v);
+    call.dq = packed(call.dq); call.dk = packed(call.dk); call.dv = packed(call.dv);
+  }
+  const fcsa_backward_args* a = &call;
+  const fcsa_problem& p = a->p;
+  if (p.causal && a->mask != nullptr) return fail(FCSA_ERR_INVALID_ARG, "mask should not be given if causal (cu:1675)");
+  const int es = elem_size(p.dtype);
+  if (p.batch == 0 || p.heads == 0) return FCSA_OK;                        // every gradient is empty
+  if (p.q_len == 0 || p.k_len == 0) {                                      // no (query, key) pair: the gradients that have elements are zero (d_bias has none)
+    hipStream_t s0 = static_cast<hipStream_t>(a->stream);
+    if (int rc = zero_rows("dq", a->dq, es, p.batch, p.heads, p.q_len, p.dim_head, s0)) return rc;
+    if (int rc = zero_rows("dk", a->dk, es, p.batch, p.kv_heads, p.k_len, p.dim_head, s0)) return rc;
+    return zero_rows("dv", a->dv, es, p.batch, p.kv_heads, p.k_len, p.dim_head, s0);
+  }
+  if (int rc = check_tensor("d_out", a->d_out, es, true)) return rc;
+  if (int rc = check_tensor("o", a->o, es, true)) return rc;
+  if (int rc = check_tensor("v", a->v, es, true)) return rc;
+  if (int rc = check_tensor("dq", a->dq, es, true)) return rc;
+  if (int rc = check_tensor("dk", a->dk, es, true)) return rc;
+  if (int rc = check_tensor("dv", a->dv, es, true)) return rc;
+  if (!p.l2norm_qk) {
+    if (int rc = check_tensor("q", a->q, es, true)) return rc;
+    if (int rc = check_tensor("k", a->k, es, true)) return rc;
+  } else if (a->norm.qn == nullptr || a->norm.kn == nullptr || a->norm.rq == nullptr || a->norm.rk == nullptr) {
+    return fail(FCSA_ERR_INVALID_ARG, "l2norm_qk backward needs norm.qn, norm.kn, norm.rq, norm.rk from forward");
+  }
+  if (a->inv_l == nullptr) return fail(FCSA_ERR_INVALID_ARG, "inv_l: null pointer");
+  if (a->attn_bias == nullptr && a->d_bias != nullptr) return fail(FCSA_ERR_INVALID_ARG, "d_bias without attn_bias");
+  const bool no_split = t.packed || t.windowed;
+  const BwdLayout L = bwd_layout(p, no_split);
+  if (a->workspace == nullptr || a->workspace_bytes < L.total)
+    return fail(FCSA_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", a->workspace_bytes, L.total);
+  if ((reinterpret_cast<uintptr_t>(a->workspace) & 255) != 0) return fail(FCSA_ERR_WORKSPACE, "workspace not 256-byte aligned");
+
+  hipStream_t s = static_cast<hipStream_t>(a->stream);
+  const bool single = p.kv_heads == 1 && p.heads > 1;      // stride-0 K/V head views
+  const bool grouped = p.kv_heads != p.heads;             // single-headed or grouped-query K/V: dk / dv are sums over query heads
+  const BwdCall bc = {a->attn_bias != nullptr, a->dq.stride0 == (int64_t)p.heads * a->dq.stride1,
+                      a->dk.stride0 == (int64_t)p.heads * a->dk.stride1 && a->dv.stride0 == (int64_t)p.heads * a->dv.stride1};
+  const BwdPlan plan = bwd_plan(p, &bc, no_split);
+  const int dq_splits = plan.dq_splits, dkv_splits = plan.dkv_splits;
+  const bool dq_slab = plan.dq_slab, dk_slab = plan.dk_slab, dv_slab = plan.dv_slab;
+  char* ws = static_cast<char*>(a->workspace);
+
+  fcsa::BwdWinParams bp;
+  bp.kv_group = single ? 1 : p.heads / p.kv_heads;
+  bp.kv_sweep = plan.kv_sweep ? 1 : 0;
+  if (p.l2norm_qk) {
+    bp.q = contiguous_view(a->norm.qn, p.heads, p.q_len, p.dim_head, es);
+    bp.k = contiguous_view(a->norm.kn, p.kv_heads, p.k_len, p.dim_head, es, single);
+  } else {
+    bp.q = view(a->q, es);
+    bp.k = view(a->k, es, single);
+  }
+  bp.v = view(a->v, es, single);
+  bp.o = view(a->o, es);
+  bp.d_out = view(a->d_out, es);
+  const bool want_dbias = a->attn_bias != nullptr && a->d_bias != nullptr;
+  bp.dq_splits = dq_splits;
+  bp.dq_split_stride = (int64_t)p.q_len * p.dim_head * 4;
+  bp.dkv_splits = dkv_splits;
+  bp.dkv_split_stride = (int64_t)p.k_len * p.dim_head * 4;
+  bp.dq_f32 = dq_slab;
+  bp.dk_f32 = dk_slab;
+  bp.dv_f32 = dv_slab;
+  if (dq_splits > 1) {          // slab layout [batch * heads][split][N][D]: (b, h) block stride = splits * N * D floats
+    bp.dq.p = ws + L.dq_slab;
+    bp.dq.sn = (int64_t)p.dim_head * 4;
+    bp.dq.sh = (int64_t)dq_splits * p.q_len * p.dim_head * 4;
+    bp.dq.sb = (int64_t)p.heads * bp.dq.sh;
+  } else {
+    bp.dq = dq_slab ? contiguous_view(ws + L.dq_slab, p.heads, p.q_len, p.dim_head, 4) : view(a->dq, es);
+  }
+  if (dkv_splits > 1) {         // slab layout [batch * heads][split][M][D], like the split dq slabs
+    bp.dk.p = ws + L.dk_slab;
+    bp.dk.sn = (int64_t)p.dim_head * 4;
+    bp.dk.sh = (int64_t)dkv_splits * p.k_len * p.dim_head * 4;
+    bp.dk.sb = (int64_t)p.heads * bp.dk.sh;
+    bp.dv = bp.dk;
+    bp.dv.p = ws + L.dv_slab;
+  } else {
+    bp.dk = dk_slab ? contiguous_view(ws + L.dk_slab, p.heads, p.k_len, p.dim_head, 4) : view(a->dk, es);
+    bp.dv = dv_slab ? contiguous_view(ws + L.dv_slab, p.heads, p.k_len, p.dim_head, 4) : view(a->dv, es);
+  }
+  bp.inv_l = a->inv_l;
+  bp.delta = reinterpret_cast<float*>(ws + L.delta);
+  bp.dlse = c.d_lse;
+  bp.mask = a->mask;
+  bp.bias = static_cast<const char*>(a->attn_bias);
+  bp.d_bias = a->d_bias;
+  bp.B = p.batch; bp.H = p.heads; bp.N = p.q_len; bp.M = p.k_len;
+  bp.seq = seq_table(t.packed ? t.vl.t : nullptr);
+  if (t.packed) { bp.B = t.vl.batch; bp.N = t.vl.max_q; bp.M = t.vl.max_k; }
+  bp.causal = p.causal; bp.bias_batch = p.bias_batch_dim;
+  if (t.windowed) { bp.window = 1; bp.win_lo = t.win.lo; bp.win_hi = t.win.hi; bp.causal = 1; }
+  bp.c1 = p.scale * kLog2e;
+  bp.c2 = exponent_shift(p, a->attn_bias != nullptr) * kLog2e;
+  bp.invl_log2 = dynamic_shift(p, a->attn_bias != nullptr) ? 1 : 0;
+  bp.bias_c = kLog2e;
+  bp.scale = p.scale;
+  bp.q_scaled = p.l2norm_qk ? 1 : 0;
+  bp.G = p.groups; bp.lgm = plan.fuse_norm ? log2_blocks_per_group(p) : 0; bp.norm_eps = 1e-12f;
+  bp.rq = (plan.fuse_norm && dq_splits <= 1) ? a->norm.rq : nullptr;    // fused: dq kernel writes the final dq
+  bp.rk = (plan.fuse_norm && (!grouped || plan.kv_sweep) && dkv_splits <= 1) ? a->norm.rk : nullptr;          // fused: dkv kernel writes the final dk
+
+  // 1. dQ (also publishes delta), 2. dK/dV, 3. head reduction + l2norm backward where needed
+  if (t.slopes) {
+    if (int rc = timed("bwd_dq", "backward dq", s, [&] { return fcsa::launch_backward_dq_alibi(p.dtype, p.dim_head, bp, t.al, s); })) return rc;
+    if (int rc = timed("bwd_dkv", "backward dkv", s, [&] { return fcsa::launch_backward_dkv_alibi(p.dtype, p.dim_head, bp, t.al, s); })) return rc;
+  } else {
+    if (int rc = timed("bwd_dq", "backward dq", s, [&] { return fcsa::launch_backward_dq(p.dtype, p.dim_head, bp, s); })) return rc;
+    if (int rc = timed("bwd_dkv", "backward dkv", s, [&] { return fcsa::launch_backward_dkv(p.dtype, p.dim_head, bp, s); })) return rc;
+  }
+  if (want_dbias) {      // d_bias from recomputed dS tiles; needs delta, which the dQ kernel published
+    if (int rc = timed("bwd_dbias", "backward d_bias", s, [&] { return fcsa::launch_backward_dbias(p.dtype, p.dim_head, bp, s); })) return rc;
+  }
+
+  fcsa::NormBwdParams nb;
+  nb.eps = 1e-12f;
+  nb.D = p.dim_head;
+  nb.B = p.batch;
+  nb.xn_scale = 1.f;
+  if (dq_splits > 1) {          // sum the split slabs ("heads" of a flat (batch * head) batch), then the l2norm backward if any
+    nb.B = p.batch * p.heads;
+    nb.slab = ws + L.dq_slab; nb.slab_f32 = 1; nb.HS = dq_splits; nb.HO = 1; nb.L = p.q_len;
+    if (p.l2norm_qk) { nb.xn = static_cast<const char*>(a->norm.qn); nb.inv_norm = a->norm.rq; nb.G = p.groups; nb.xn_scale = 1.f / (p.scale * kLog2e); }
+    else             { nb.xn = nullptr; nb.inv_norm = nullptr; nb.G = 1; }
+    nb.dx = view(a->dq, es);
+    nb.dx.sb = nb.dx.sh;          // flat (batch * head) index: stride0 == heads * stride1 (checked above)
+    nb.dx.sh = 0;
+  } else if (dq_slab) {
+    nb.slab = ws + L.dq_slab; nb.slab_f32 = 1; nb.HS = p.heads; nb.HO = p.heads; nb.L = p.q_len;
+    nb.xn = static_cast<const char*>(a->norm.qn); nb.inv_norm = a->norm.rq; nb.G = p.groups;
+    nb.xn_scale = 1.f / (p.scale * kLog2e);           // qn holds c1 * q^
+    nb.dx = view(a->dq, es);
+  }
+  // (the dq pass is launched below, together with the dk / dv passes where there are any: one grid instead of two or three)
+  const fcsa::NormBwdParams nq = nb;
+  nb.B = p.batch;
+  fcsa::NormBwdParams nk = nb, nv = nb;
+  if (dk_slab) {
+    nk.slab = ws + L.dk_slab; nk.slab_f32 = 1; nk.HS = p.heads; nk.HO = p.kv_heads; nk.L = p.k_len;
+    nk.xn_scale = 1.f;
+    if (p.l2norm_qk) { nk.xn = static_cast<const char*>(a->norm.kn); nk.inv_norm = a->norm.rk; nk.G = p.groups; }
+    else             { nk.xn = nullptr; nk.inv_norm = nullptr; nk.G = 1; }
+    nk.dx = view(a->dk, es);
+  }
+  if (dv_slab) {
+    nv.slab = ws + L.dv_slab; nv.slab_f32 = 1; nv.HS = p.heads; nv.HO = p.kv_heads; nv.L = p.k_len;
+    nv.xn = nullptr; nv.inv_norm = nullptr; nv.G = 1; nv.xn_scale = 1.f;
+    nv.dx = view(a->dv, es);
+  }
+  if (dkv_splits > 1) {         // the splits are the "heads" of a flat (batch * head) batch, summed down to one
+    for (fcsa::NormBwdParams* n : {&nk, &nv}) {
+      if (grouped) {              // slabs [batch][heads x splits][M][D]: each K/V head sums its group's heads x splits
+        n->HS = p.heads * dkv_splits; n->HO = p.kv_heads;
+        continue;
+      }
+      n->B = p.batch * p.heads; n->HS = dkv_splits; n->HO = 1;
+      n->dx.sb = n->dx.sh;        // flat (batch * head) index: stride0 == heads * stride1 (checked above)
+      n->dx.sh = 0;
+    }
+  }
+  if (dq_slab && dk_slab && dv_slab) {      // causal problems on small grids (dQ and dK/dV both split), split dQ with single-headed K/V: one launch
+    if (int rc = timed("finalize", "finalize dq+dk+dv", s, [&] { return fcsa::launch_l2norm_bwd_triple(p.dtype, nq, nk, nv, s); })) return rc;
+  } else if (dq_slab && dk_slab) {          // l2norm groups that are not 8 * 2^k features wide
+    if (int rc = timed("finalize", "finalize dq+dk", s, [&] { return fcsa::launch_l2norm_bwd_pair(p.dtype, nq, nk, s); })) return rc;
+  } else {
+    if (dq_slab) {
+      if (int rc = timed("finalize", "finalize dq", s, [&] { return fcsa::launch_l2norm_bwd(p.dtype, nq, s); })) return rc;
+    }
+    if (dk_slab && dv_slab) {      // single-headed K/V, split-query dK/dV: both reductions in one launch
+      if (int rc = timed("finalize", "finalize dk+dv", s, [&] { return fcsa::launch_l2norm_bwd_pair(p.dtype, nk, nv, s); })) return rc;
+    } else if (dk_slab) {
+      if (int rc = timed("finalize", "finalize dk", s, [&] { return fcsa::launch_l2norm_bwd(p.dtype, nk, s); })) return rc;
+    } else if (dv_slab) {
+      if (int rc = timed("finalize", "finalize dv", s, [&] { return fcsa::launch_l2norm_bwd(p.dtype, nv, s); })) return rc;
+    }
+  }
+  // Two degenerate problems whose dq and dk are EXACTLY zero, and for which the kernels' arithmetic is not meaningful:
+  //   scale == 0: the logits do not depend on q, k.  The kernels carry c1 = scale * log2(e) folded into the saved q^ and undo it with
+  //     1 / c1 in the l2norm backward and the dK^ epilogue: 0 * inf = NaN.
+  //   l2norm groups of ONE feature (groups == dim_head): x^ = sign(x), whose derivative is zero; the tangent-space projection
+  //     r (g - x^ <g, x^>) is then a pure cancellation that the 16-bit rounding of c1 * q^ leaves at 2^-11 |g| / |x| -- unbounded for
+  //     elements near zero (measured 0.7 against an exact 0).
+  // The reference's autograd through F.normalize / scale * sim gives zeros in both; dv (and d_bias) are what the kernels wrote.
+  if (p.scale == 0.f || (p.l2norm_qk && p.groups == p.dim_head)) {
+    if (int rc = zero_rows("dq", a->dq, es, p.batch, p.heads, p.q_len, p.dim_head, s)) return rc;
+    if (int rc = zero_rows("dk", a->dk, es, p.batch, p.kv_heads, p.k_len, p.dim_head, s)) return rc;
+  }
+  return FCSA_OK;
+}
 
 }  // namespace
 
@@ -365,91 +760,51 @@ int fcsa_l2norm(int32_t dtype, int32_t batch, int32_t heads, int32_t len, int32_
   return timed("l2norm", "l2norm", s, [&] { return fcsa::launch_l2norm(dtype, np, s); });
 }
 
-// split-key forward (fcsa::forward_splits: bias-free launches only): the count, and its workspace -- partial P~V, then partial row sums
-static int forward_splits(const fcsa_problem& p) {
-  if (p.batch <= 0 || p.heads <= 0 || p.q_len <= 0 || p.dim_head <= 0) return 1;
-  return fcsa::forward_splits(p, dynamic_shift(p, false), fcsa::cu_count());
-}
-static size_t forward_ws_bytes(const fcsa_problem& p, int splits) {
-  if (splits <= 1) return 0;
-  const size_t rows = (size_t)splits * p.batch * p.heads * p.q_len;
-  return align_up(rows * p.dim_head * 4, 256) + align_up(rows * 4, 256);
-}
-
 size_t fcsa_forward_workspace_bytes(const fcsa_problem* p) { return p == nullptr ? 0 : forward_ws_bytes(*p, forward_splits(*p)); }
 
-// Zero-size problems (empty tensors: what torch hands over has NULL data pointers then).  batch, heads or q_len == 0: the forward has no
-// output element; k_len == 0: every query row is a row without a valid key, for which the kernels' semantics are o = 0 (cu:1239) and
-// finite (zero) gradients.  Nothing is launched; the outputs that DO have elements are zero-filled on the caller's stream, row by row
-// (any strides).  The reference launches a zero-sized grid there (a CUDA error it prints and ignores, cu:17-28).
-static int zero_rows(const char* name, const fcsa_tensor& t, int es, int B, int H, int L, int D, hipStream_t s) {
-  if (B <= 0 || H <= 0 || L <= 0) return FCSA_OK;
-  if (int rc = check_tensor(name, t, es, true)) return rc;
-  for (int b = 0; b < B; ++b)
-    for (int h = 0; h < H; ++h) {
-      char* base = static_cast<char*>(t.ptr) + ((int64_t)b * t.stride0 + (int64_t)h * t.stride1) * es;
-      const hipError_t e = t.stride2 == D ? hipMemsetAsync(base, 0, (size_t)L * D * es, s)
-                                          : hipMemset2DAsync(base, (size_t)t.stride2 * es, 0, (size_t)D * es, (size_t)L, s);
-      if (e != hipSuccess) return fail(FCSA_ERR_LAUNCH, "%s: zero fill failed: %s", name, hipGetErrorString(e));
-    }
-  return FCSA_OK;
+int fcsa_forward_needs_qn(const fcsa_problem* p, int32_t need_backward) {
+  if (p == nullptr || !p->l2norm_qk) return 0;
+  if (need_backward) return 1;
+  return (p->dtype != FCSA_F32 && fusable_groups(*p)) ? 0 : 1;
 }
 
-int fcsa_forward(const fcsa_forward_args* a) { return forward_impl(a, nullptr); }
-
-static int forward_varlen(const fcsa_forward_args* a, const fcsa_varlen* seqs, const WindowCall* win, const fcsa::TrainAlibi* al = nullptr) {
-  if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
-  if (int rc = check_problem(a->p)) return rc;
-  if (int rc = check_varlen(a->p, seqs, a->mask != nullptr, a->attn_bias != nullptr)) return rc;
-  fcsa_forward_args pa = *a;
-  pa.q = packed(pa.q); pa.k = packed(pa.k); pa.v = packed(pa.v); pa.o = packed(pa.o);
-  pa.p = packed_problem(a->p, *seqs);
-  const VarlenCall vl = {seqs, a->p.batch, a->p.q_len, a->p.k_len};
-  return forward_impl(&pa, &vl, win, al);
-}
-int fcsa_forward_varlen(const fcsa_forward_args* a, const fcsa_varlen* seqs) { return forward_varlen(a, seqs, nullptr); }
-
+// ---- the training calls: each entry point is its description, handed to train_forward / train_backward
+int fcsa_forward(const fcsa_forward_args* a) { return train_forward({TrainNeeds::Nothing, a, nullptr, nullptr, nullptr}); }
+int fcsa_forward_varlen(const fcsa_forward_args* a, const fcsa_varlen* seqs) { return train_forward({TrainNeeds::Seqs, a, nullptr, seqs, nullptr}); }
 int fcsa_forward_window(const fcsa_forward_args* a, const fcsa_varlen* seqs, const fcsa_window* w) {
-  if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
-  if (int rc = check_problem(a->p)) return rc;
-  if (int rc = check_window(w, a->mask != nullptr, a->attn_bias != nullptr)) return rc;
-  WindowCall win;
-  const fcsa::WinKind kind = fcsa::win_normalise(a->p.q_len, a->p.k_len, a->p.causal != 0, w->left, w->right, win.lo, win.hi);
-  if (kind == fcsa::WinKind::Window) return seqs != nullptr ? forward_varlen(a, seqs, &win) : forward_impl(a, nullptr, &win);
-  fcsa_forward_args na = *a;
-  na.p.causal = kind == fcsa::WinKind::Causal ? 1 : 0;
-  return seqs != nullptr ? fcsa_forward_varlen(&na, seqs) : fcsa_forward(&na);
+  return train_forward({TrainNeeds::Window, a, nullptr, seqs, w});
 }
-
-// The checks the two slope calls share, and the sides of their windowed launch: whatever win_normalise makes of the window -- (open, open)
-// and (open, 0) included, which the windowed kernel forms serve like any other pair.
-static int check_alibi(const fcsa_problem& p, const fcsa_varlen* seqs, const fcsa_window* w, const fcsa_alibi* al, bool mask, bool bias,
-                       WindowCall& win, fcsa::TrainAlibi& ta) {
-  if (mask || bias) return fail(FCSA_ERR_INVALID_ARG, "alibi: mask and attn_bias are not supported with alibi_slopes");
-  if (w != nullptr) {
-    if (int rc = check_window(w, false, false)) return rc;
-  }
-  if (al == nullptr || al->slopes == nullptr) return fail(FCSA_ERR_INVALID_ARG, "alibi: null slopes");
-  if ((reinterpret_cast<uintptr_t>(al->slopes) & 3) != 0) return fail(FCSA_ERR_INVALID_ARG, "alibi: slopes not 4-byte aligned");
-  if (al->reserved != 0) return fail(FCSA_ERR_INVALID_ARG, "alibi: reserved must be 0");
-  if (seqs == nullptr && !p.causal && p.q_len > p.k_len)
-    return fail(FCSA_ERR_INVALID_ARG, "alibi: a non-causal call needs q_len <= k_len (%d > %d): rows with pos_i < 0 have no key at distance 0", p.q_len, p.k_len);
-  (void)fcsa::win_normalise(p.q_len, p.k_len, p.causal != 0, w != nullptr ? w->left : -1, w != nullptr ? w->right : -1, win.lo, win.hi);
-  ta = fcsa::TrainAlibi{al->slopes, al->stride_b, al->stride_h};
-  return FCSA_OK;
-}
-
 int fcsa_forward_alibi(const fcsa_forward_args* a, const fcsa_varlen* seqs, const fcsa_window* w, const fcsa_alibi* al) {
-  if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
-  if (int rc = check_problem(a->p)) return rc;
-  WindowCall win;
-  fcsa::TrainAlibi ta;
-  if (int rc = check_alibi(a->p, seqs, w, al, a->mask != nullptr, a->attn_bias != nullptr, win, ta)) return rc;
-  return seqs != nullptr ? forward_varlen(a, seqs, &win, &ta) : forward_impl(a, nullptr, &win, &ta);
+  return train_forward({TrainNeeds::Slopes, a, nullptr, seqs, w, al});
 }
 size_t fcsa_forward_alibi_workspace_bytes(const fcsa_problem*, const fcsa_varlen*, const fcsa_window*) { return 0; }
 
+int fcsa_backward(const fcsa_backward_args* a) { return train_backward({TrainNeeds::Nothing, nullptr, a, nullptr, nullptr}); }
+int fcsa_backward_varlen(const fcsa_backward_args* a, const fcsa_varlen* seqs) { return train_backward({TrainNeeds::Seqs, nullptr, a, seqs, nullptr}); }
+int fcsa_backward_window(const fcsa_backward_args* a, const fcsa_varlen* seqs, const fcsa_window* w) {
+  return train_backward({TrainNeeds::Window, nullptr, a, seqs, w});
+}
+int fcsa_backward_alibi(const fcsa_backward_args* a, const fcsa_varlen* seqs, const fcsa_window* w, const fcsa_alibi* al) {
+  return train_backward({TrainNeeds::Slopes, nullptr, a, seqs, w, al});
+}
+// attention states: every option is optional, and the call looks at what it cannot take before anything else
+int fcsa_backward_state(const fcsa_backward_args* a, const fcsa_varlen* seqs, const fcsa_window* w, const float* d_lse) {
+  if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "backward_state: null args");
+  if (a->mask != nullptr || a->attn_bias != nullptr || a->d_bias != nullptr)
+    return fail(FCSA_ERR_INVALID_ARG, "backward_state: mask, attn_bias and d_bias are not supported with attention states (the log-sum-exp)");
+  return train_backward({TrainNeeds::Nothing, nullptr, a, seqs, w, nullptr, d_lse});
+}
 
+size_t fcsa_backward_workspace_bytes(const fcsa_problem* p) { return p == nullptr ? 0 : bwd_workspace(*p, nullptr, nullptr, false); }
+size_t fcsa_backward_varlen_workspace_bytes(const fcsa_problem* p, const fcsa_varlen* seqs) {
+  return p == nullptr || seqs == nullptr ? 0 : bwd_workspace(*p, seqs, nullptr, false);
+}
+size_t fcsa_backward_window_workspace_bytes(const fcsa_problem* p, const fcsa_varlen* seqs, const fcsa_window* w) {
+  return p == nullptr || w == nullptr ? 0 : bwd_workspace(*p, seqs, w, false);
+}
+size_t fcsa_backward_alibi_workspace_bytes(const fcsa_problem* p, const fcsa_varlen* seqs, const fcsa_window*) {
+  return p == nullptr ? 0 : bwd_workspace(*p, seqs, nullptr, true);
+}
 }  // extern "C"
 
 namespace {
@@ -1003,175 +1358,8 @@ int fcsa_merge_states(const fcsa_merge_args* a) {
   hipStream_t s = static_cast<hipStream_t>(a->stream);
   return timed("merge_states", "merge states", s, [&] { return fcsa::launch_merge_states(a->dtype, mp, s); });
 }
-}  // extern "C"
 
-namespace {
-
-// vl != nullptr: packed sequences; a->p is then the problem of the packed rows (packed_problem)
-// win != nullptr: a sliding window (the windowed kernel forms; no split)
-int forward_impl(const fcsa_forward_args* a, const VarlenCall* vl, const WindowCall* win, const fcsa::TrainAlibi* al) {
-  if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
-  const fcsa_problem& p = a->p;
-  if (int rc = check_problem(p)) return rc;
-  if (p.causal && a->mask != nullptr) return fail(FCSA_ERR_INVALID_ARG, "mask should not be given if causal (cu:1675)");
-  const int es = elem_size(p.dtype);
-  if (p.batch == 0 || p.heads == 0 || p.q_len == 0) return FCSA_OK;      // no output element (k-side saved state is not needed by a backward either)
-  if (p.k_len == 0) {                                                     // rows without a key: o = 0; inv_l = 1 (never read: the backward below has no key to visit)
-    hipStream_t s0 = static_cast<hipStream_t>(a->stream);
-    if (int rc = zero_rows("o", a->o, es, p.batch, p.heads, p.q_len, p.dim_head, s0)) return rc;
-    if (a->inv_l != nullptr) {
-      const float one = 1.f;
-      uint32_t bits; memcpy(&bits, &one, 4);
-      if (hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a->inv_l), (int)bits, (size_t)p.batch * p.heads * p.q_len, s0) != hipSuccess)
-        return fail(FCSA_ERR_LAUNCH, "inv_l: fill failed");
-    }
-    return FCSA_OK;
-  }
-  if (int rc = check_tensor("q", a->q, es, true)) return rc;
-  if (int rc = check_tensor("k", a->k, es, true)) return rc;
-  if (int rc = check_tensor("v", a->v, es, true)) return rc;
-  if (int rc = check_tensor("o", a->o, es, true)) return rc;
-  hipStream_t s = static_cast<hipStream_t>(a->stream);
-  const bool single = p.kv_heads == 1 && p.heads > 1;      // one K/V head: stride-0 head views; grouped K/V: kv_group query heads per K/V head
-
-  fcsa::FwdWinParams fp;
-  fp.kv_group = single ? 1 : p.heads / p.kv_heads;
-  bool fuse_q = false;
-  fp.q = view(a->q, es);
-  fp.k = view(a->k, es, single);
-  fp.v = view(a->v, es, single);
-  fp.o = view(a->o, es);
-  if (p.l2norm_qk) {
-    const fcsa_norm_state& n = a->norm;
-    if (n.kn == nullptr) return fail(FCSA_ERR_INVALID_ARG, "l2norm_qk needs the norm.kn buffer");
-    if (n.qn == nullptr && fcsa_forward_needs_qn(&p, a->inv_l != nullptr || n.rq != nullptr))
-      return fail(FCSA_ERR_INVALID_ARG, "l2norm_qk needs the norm.qn buffer for this problem (fcsa_forward_needs_qn)");
-    fcsa::NormParams nq, nk;
-    nq.eps = nk.eps = 1e-12f;
-    nq.D = nk.D = p.dim_head; nq.G = nk.G = p.groups;
-    nq.x = fp.q; nq.xn = static_cast<char*>(n.qn); nq.inv_norm = n.rq;
-    nq.B = p.batch; nq.H = p.heads; nq.L = p.q_len;
-    nq.out_scale = p.scale * kLog2e;       // qn = c1 * q^ (one rounding): the kernels then need no per-logit multiply
-    nk.x = view(a->k, es); nk.xn = static_cast<char*>(n.kn); nk.inv_norm = n.rk;
-    nk.B = p.batch; nk.H = p.kv_heads; nk.L = p.k_len;
-    nk.out_scale = 1.f;
-    // 16-bit types with group sizes of 8 * 2^k: q is normalised in the forward kernel's prologue (load_q_frags), which also
-    // writes qn / rq for the backward; only k takes the HBM pass.  Otherwise both go through the row kernel.
-    fuse_q = p.dtype != FCSA_F32 && fusable_groups(p);
-    if (fuse_q) {
-      if (int rc = timed("l2norm", "l2norm(k)", s, [&] { return fcsa::launch_l2norm(p.dtype, nk, s); })) return rc;
-    } else {
-      if (int rc = timed("l2norm", "l2norm(q,k)", s, [&] { return fcsa::launch_l2norm_pair(p.dtype, nq, nk, s); })) return rc;
-    }
-    if (!fuse_q) fp.q = contiguous_view(n.qn, p.heads, p.q_len, p.dim_head, es);
-    fp.k = contiguous_view(n.kn, p.kv_heads, p.k_len, p.dim_head, es, single);
-  }
-  fp.inv_l = a->inv_l;
-  fp.mask = a->mask;
-  fp.bias = static_cast<const char*>(a->attn_bias);
-  fp.B = p.batch; fp.H = p.heads; fp.N = p.q_len; fp.M = p.k_len;
-  fp.seq = seq_table(vl);
-  if (vl != nullptr) { fp.B = vl->batch; fp.N = vl->max_q; fp.M = vl->max_k; }
-  fp.causal = p.causal; fp.bias_batch = p.bias_batch_dim;
-  if (win != nullptr) { fp.window = 1; fp.win_lo = win->lo; fp.win_hi = win->hi; fp.causal = 1; }      // (a causal launch with moved diagonals: fcsa_dispatch.h)
-  fp.c1 = p.scale * kLog2e;
-  const bool has_bias = a->attn_bias != nullptr;
-  fp.c2 = exponent_shift(p, has_bias) * kLog2e;
-  fp.bias_c = kLog2e;
-  fp.l_eps = rowsum_eps(p, has_bias);
-  fp.q_scaled = p.l2norm_qk ? 1 : 0;
-  fp.q_raw = fuse_q ? 1 : 0;
-  fp.qn_out = fuse_q ? static_cast<char*>(a->norm.qn) : nullptr;
-  fp.rq_out = fuse_q ? a->norm.rq : nullptr;
-  fp.G = p.groups; fp.lgm = fuse_q ? log2_blocks_per_group(p) : 0; fp.norm_eps = 1e-12f;
-  fp.dyn = dynamic_shift(p, has_bias) ? 1 : 0;      // then inv_l holds log2 of the normaliser
-  fp.splits = 1; fp.ws_o = nullptr; fp.ws_l = nullptr;
-  if (a->workspace != nullptr && a->attn_bias == nullptr && vl == nullptr && win == nullptr) {
-    const int sp = forward_splits(p);
-    if (sp > 1 && a->workspace_bytes >= forward_ws_bytes(p, sp) && (reinterpret_cast<uintptr_t>(a->workspace) & 255) == 0) {
-      const size_t rows = (size_t)sp * p.batch * p.heads * p.q_len;
-      fp.splits = sp;
-      fp.ws_o = static_cast<float*>(a->workspace);
-      fp.ws_l = reinterpret_cast<float*>(static_cast<char*>(a->workspace) + align_up(rows * p.dim_head * 4, 256));
-    }
-  }
-  if (al != nullptr) return timed("fwd", "forward", s, [&] { return fcsa::launch_forward_alibi(p.dtype, p.dim_head, fp, *al, s); });
-  return timed("fwd", "forward", s, [&] { return fcsa::launch_forward(p.dtype, p.dim_head, fp, s); });
-}
-
-}  // namespace
-
-extern "C" {
-
-int fcsa_forward_needs_qn(const fcsa_problem* p, int32_t need_backward) {
-  if (p == nullptr || !p->l2norm_qk) return 0;
-  if (need_backward) return 1;
-  return (p->dtype != FCSA_F32 && fusable_groups(*p)) ? 0 : 1;
-}
-
-size_t fcsa_backward_workspace_bytes(const fcsa_problem* p) {
-  if (p == nullptr) return 0;
-  return bwd_layout(*p).total;
-}
-
-size_t fcsa_backward_varlen_workspace_bytes(const fcsa_problem* p, const fcsa_varlen* seqs) {
-  if (p == nullptr || seqs == nullptr || seqs->total_q < 0 || seqs->total_k < 0) return 0;
-  return bwd_layout(packed_problem(*p, *seqs), true).total;
-}
-
-int fcsa_backward(const fcsa_backward_args* a) { return backward_impl(a, nullptr); }
-
-static int backward_varlen(const fcsa_backward_args* a, const fcsa_varlen* seqs, const WindowCall* win, const float* dlse = nullptr,
-                           const fcsa::TrainAlibi* al = nullptr);
-int fcsa_backward_varlen(const fcsa_backward_args* a, const fcsa_varlen* seqs) { return backward_varlen(a, seqs, nullptr); }
-
-size_t fcsa_backward_window_workspace_bytes(const fcsa_problem* p, const fcsa_varlen* seqs, const fcsa_window* w) {
-  if (p == nullptr || w == nullptr) return 0;
-  WindowCall win;
-  const fcsa::WinKind kind = fcsa::win_normalise(p->q_len, p->k_len, p->causal != 0, w->left, w->right, win.lo, win.hi);
-  fcsa_problem np = *p;
-  if (kind != fcsa::WinKind::Window) np.causal = kind == fcsa::WinKind::Causal ? 1 : 0;
-  if (seqs != nullptr) return fcsa_backward_varlen_workspace_bytes(&np, seqs);
-  return kind == fcsa::WinKind::Window ? bwd_layout(np, true).total : bwd_layout(np).total;
-}
-
-// dlse: the LSE gradient of fcsa_backward_state, or nullptr
-static int backward_window(const fcsa_backward_args* a, const fcsa_varlen* seqs, const fcsa_window* w, const float* dlse) {
-  if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
-  if (int rc = check_problem(a->p)) return rc;
-  if (int rc = check_window(w, a->mask != nullptr, a->attn_bias != nullptr || a->d_bias != nullptr)) return rc;
-  WindowCall win;
-  const fcsa::WinKind kind = fcsa::win_normalise(a->p.q_len, a->p.k_len, a->p.causal != 0, w->left, w->right, win.lo, win.hi);
-  if (kind == fcsa::WinKind::Window) return seqs != nullptr ? backward_varlen(a, seqs, &win, dlse) : backward_impl(a, nullptr, &win, dlse);
-  fcsa_backward_args na = *a;
-  na.p.causal = kind == fcsa::WinKind::Causal ? 1 : 0;
-  return seqs != nullptr ? backward_varlen(&na, seqs, nullptr, dlse) : backward_impl(&na, nullptr, nullptr, dlse);
-}
-int fcsa_backward_window(const fcsa_backward_args* a, const fcsa_varlen* seqs, const fcsa_window* w) { return backward_window(a, seqs, w, nullptr); }
-
-int fcsa_backward_alibi(const fcsa_backward_args* a, const fcsa_varlen* seqs, const fcsa_window* w, const fcsa_alibi* al) {
-  if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
-  if (int rc = check_problem(a->p)) return rc;
-  WindowCall win;
-  fcsa::TrainAlibi ta;
-  if (int rc = check_alibi(a->p, seqs, w, al, a->mask != nullptr, a->attn_bias != nullptr || a->d_bias != nullptr, win, ta)) return rc;
-  return seqs != nullptr ? backward_varlen(a, seqs, &win, nullptr, &ta) : backward_impl(a, nullptr, &win, nullptr, &ta);
-}
-// (always the plan of a windowed launch: no split, no group sweep)
-size_t fcsa_backward_alibi_workspace_bytes(const fcsa_problem* p, const fcsa_varlen* seqs, const fcsa_window*) {
-  if (p == nullptr) return 0;
-  if (seqs != nullptr) return fcsa_backward_varlen_workspace_bytes(p, seqs);
-  return bwd_layout(*p, true).total;
-}
-
-int fcsa_backward_state(const fcsa_backward_args* a, const fcsa_varlen* seqs, const fcsa_window* w, const float* d_lse) {
-  if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "backward_state: null args");
-  if (a->mask != nullptr || a->attn_bias != nullptr || a->d_bias != nullptr)
-    return fail(FCSA_ERR_INVALID_ARG, "backward_state: mask, attn_bias and d_bias are not supported with attention states (the log-sum-exp)");
-  if (w != nullptr) return backward_window(a, seqs, w, d_lse);
-  return seqs != nullptr ? backward_varlen(a, seqs, nullptr, d_lse) : backward_impl(a, nullptr, nullptr, d_lse);
-}
-
+// ---- attention states for training: the log-sum-exp of a forward call, read off its inv_l, and the merge's backward -------------------
 int fcsa_attention_lse(const fcsa_problem* pp, const float* inv_l, const fcsa_varlen* seqs, const fcsa_window* w, const fcsa_lse_out* lse_out,
                        void* stream) {
   if (pp == nullptr || lse_out == nullptr) return fail(FCSA_ERR_INVALID_ARG, "attention_lse: null argument");
@@ -1194,8 +1382,7 @@ int fcsa_attention_lse(const fcsa_problem* pp, const float* inv_l, const fcsa_va
   (void)fcsa::win_normalise(p.q_len, p.k_len, p.causal != 0, w != nullptr ? w->left : -1, w != nullptr ? w->right : -1, sp.win_lo, sp.win_hi);
   sp.c2 = exponent_shift(p, false) * kLog2e;
   sp.invl_log2 = dynamic_shift(p, false) ? 1 : 0;
-  sp.seq = seqs != nullptr ? fcsa::SeqTable{seqs->cu_seqlens_q, seqs->cu_seqlens_k, (int)seqs->total_q, (int)seqs->total_k}
-                           : fcsa::SeqTable{nullptr, nullptr, 0, 0};
+  sp.seq = seq_table(seqs);
   hipStream_t s = static_cast<hipStream_t>(stream);
   return timed("state_lse", "state lse", s, [&] { return fcsa::launch_state_lse(sp, s); });
 }
@@ -1235,214 +1422,4 @@ int fcsa_merge_states_backward(const fcsa_merge_backward_args* a) {
   hipStream_t s = static_cast<hipStream_t>(a->stream);
   return timed("merge_states_bwd", "merge states backward", s, [&] { return fcsa::launch_merge_states_backward(a->dtype, mp, s); });
 }
-
-static int backward_varlen(const fcsa_backward_args* a, const fcsa_varlen* seqs, const WindowCall* win, const float* dlse, const fcsa::TrainAlibi* al) {
-  if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
-  if (int rc = check_problem(a->p)) return rc;
-  if (int rc = check_varlen(a->p, seqs, a->mask != nullptr, a->attn_bias != nullptr || a->d_bias != nullptr)) return rc;
-  fcsa_backward_args pa = *a;
-  pa.d_out = packed(pa.d_out); pa.o = packed(pa.o); pa.q = packed(pa.q); pa.k = packed(pa.k); pa.v = packed(pa.v);
-  pa.dq = packed(pa.dq); pa.dk = packed(pa.dk); pa.dv = packed(pa.dv);
-  pa.p = packed_problem(a->p, *seqs);
-  const VarlenCall vl = {seqs, a->p.batch, a->p.q_len, a->p.k_len};
-  return backward_impl(&pa, &vl, win, dlse, al);
-}
-
 }  // extern "C"
-
-namespace {
-
-// win != nullptr: a sliding window (the windowed kernel forms; the plan of a packed call: no split, no group sweep)
-int backward_impl(const fcsa_backward_args* a, const VarlenCall* vl, const WindowCall* win, const float* dlse, const fcsa::TrainAlibi* al) {
-  if (a == nullptr) return fail(FCSA_ERR_INVALID_ARG, "null args");
-  const fcsa_problem& p = a->p;
-  if (int rc = check_problem(p)) return rc;
-  if (p.causal && a->mask != nullptr) return fail(FCSA_ERR_INVALID_ARG, "mask should not be given if causal (cu:1675)");
-  const int es = elem_size(p.dtype);
-  if (p.batch == 0 || p.heads == 0) return FCSA_OK;                        // every gradient is empty
-  if (p.q_len == 0 || p.k_len == 0) {                                      // no (query, key) pair: the gradients that have elements are zero (d_bias has none)
-    hipStream_t s0 = static_cast<hipStream_t>(a->stream);
-    if (int rc = zero_rows("dq", a->dq, es, p.batch, p.heads, p.q_len, p.dim_head, s0)) return rc;
-    if (int rc = zero_rows("dk", a->dk, es, p.batch, p.kv_heads, p.k_len, p.dim_head, s0)) return rc;
-    return zero_rows("dv", a->dv, es, p.batch, p.kv_heads, p.k_len, p.dim_head, s0);
-  }
-  if (int rc = check_tensor("d_out", a->d_out, es, true)) return rc;
-  if (int rc = check_tensor("o", a->o, es, true)) return rc;
-  if (int rc = check_tensor("v", a->v, es, true)) return rc;
-  if (int rc = check_tensor("dq", a->dq, es, true)) return rc;
-  if (int rc = check_tensor("dk", a->dk, es, true)) return rc;
-  if (int rc = check_tensor("dv", a->dv, es, true)) return rc;
-  if (!p.l2norm_qk) {
-    if (int rc = check_tensor("q", a->q, es, true)) return rc;
-    if (int rc = check_tensor("k", a->k, es, true)) return rc;
-  } else if (a->norm.qn == nullptr || a->norm.kn == nullptr || a->norm.rq == nullptr || a->norm.rk == nullptr) {
-    return fail(FCSA_ERR_INVALID_ARG, "l2norm_qk backward needs norm.qn, norm.kn, norm.rq, norm.rk from forward");
-  }
-  if (a->inv_l == nullptr) return fail(FCSA_ERR_INVALID_ARG, "inv_l: null pointer");
-  if (a->attn_bias == nullptr && a->d_bias != nullptr) return fail(FCSA_ERR_INVALID_ARG, "d_bias without attn_bias");
-  const bool no_split = vl != nullptr || win != nullptr;
-  const BwdLayout L = bwd_layout(p, no_split);
-  if (a->workspace == nullptr || a->workspace_bytes < L.total)
-    return fail(FCSA_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", a->workspace_bytes, L.total);
-  if ((reinterpret_cast<uintptr_t>(a->workspace) & 255) != 0) return fail(FCSA_ERR_WORKSPACE, "workspace not 256-byte aligned");
-
-  hipStream_t s = static_cast<hipStream_t>(a->stream);
-  const bool single = p.kv_heads == 1 && p.heads > 1;      // stride-0 K/V head views
-  const bool grouped = p.kv_heads != p.heads;             // single-headed or grouped-query K/V: dk / dv are sums over query heads
-  const BwdCall call = {a->attn_bias != nullptr, a->dq.stride0 == (int64_t)p.heads * a->dq.stride1,
-                        a->dk.stride0 == (int64_t)p.heads * a->dk.stride1 && a->dv.stride0 == (int64_t)p.heads * a->dv.stride1};
-  const BwdPlan plan = bwd_plan(p, &call, no_split);
-  const int dq_splits = plan.dq_splits, dkv_splits = plan.dkv_splits;
-  const bool dq_slab = plan.dq_slab, dk_slab = plan.dk_slab, dv_slab = plan.dv_slab;
-  char* ws = static_cast<char*>(a->workspace);
-
-  fcsa::BwdWinParams bp;
-  bp.kv_group = single ? 1 : p.heads / p.kv_heads;
-  bp.kv_sweep = plan.kv_sweep ? 1 : 0;
-  if (p.l2norm_qk) {
-    bp.q = contiguous_view(a->norm.qn, p.heads, p.q_len, p.dim_head, es);
-    bp.k = contiguous_view(a->norm.kn, p.kv_heads, p.k_len, p.dim_head, es, single);
-  } else {
-    bp.q = view(a->q, es);
-    bp.k = view(a->k, es, single);
-  }
-  bp.v = view(a->v, es, single);
-  bp.o = view(a->o, es);
-  bp.d_out = view(a->d_out, es);
-  const bool want_dbias = a->attn_bias != nullptr && a->d_bias != nullptr;
-  bp.dq_splits = dq_splits;
-  bp.dq_split_stride = (int64_t)p.q_len * p.dim_head * 4;
-  bp.dkv_splits = dkv_splits;
-  bp.dkv_split_stride = (int64_t)p.k_len * p.dim_head * 4;
-  bp.dq_f32 = dq_slab;
-  bp.dk_f32 = dk_slab;
-  bp.dv_f32 = dv_slab;
-  if (dq_splits > 1) {          // slab layout [batch * heads][split][N][D]: (b, h) block stride = splits * N * D floats
-    bp.dq.p = ws + L.dq_slab;
-    bp.dq.sn = (int64_t)p.dim_head * 4;
-    bp.dq.sh = (int64_t)dq_splits * p.q_len * p.dim_head * 4;
-    bp.dq.sb = (int64_t)p.heads * bp.dq.sh;
-  } else {
-    bp.dq = dq_slab ? contiguous_view(ws + L.dq_slab, p.heads, p.q_len, p.dim_head, 4) : view(a->dq, es);
-  }
-  if (dkv_splits > 1) {         // slab layout [batch * heads][split][M][D], like the split dq slabs
-    bp.dk.p = ws + L.dk_slab;
-    bp.dk.sn = (int64_t)p.dim_head * 4;
-    bp.dk.sh = (int64_t)dkv_splits * p.k_len * p.dim_head * 4;
-    bp.dk.sb = (int64_t)p.heads * bp.dk.sh;
-    bp.dv = bp.dk;
-    bp.dv.p = ws + L.dv_slab;
-  } else {
-    bp.dk = dk_slab ? contiguous_view(ws + L.dk_slab, p.heads, p.k_len, p.dim_head, 4) : view(a->dk, es);
-    bp.dv = dv_slab ? contiguous_view(ws + L.dv_slab, p.heads, p.k_len, p.dim_head, 4) : view(a->dv, es);
-  }
-  bp.inv_l = a->inv_l;
-  bp.delta = reinterpret_cast<float*>(ws + L.delta);
-  bp.dlse = dlse;
-  bp.mask = a->mask;
-  bp.bias = static_cast<const char*>(a->attn_bias);
-  bp.d_bias = a->d_bias;
-  bp.B = p.batch; bp.H = p.heads; bp.N = p.q_len; bp.M = p.k_len;
-  bp.seq = seq_table(vl);
-  if (vl != nullptr) { bp.B = vl->batch; bp.N = vl->max_q; bp.M = vl->max_k; }
-  bp.causal = p.causal; bp.bias_batch = p.bias_batch_dim;
-  if (win != nullptr) { bp.window = 1; bp.win_lo = win->lo; bp.win_hi = win->hi; bp.causal = 1; }
-  bp.c1 = p.scale * kLog2e;
-  bp.c2 = exponent_shift(p, a->attn_bias != nullptr) * kLog2e;
-  bp.invl_log2 = dynamic_shift(p, a->attn_bias != nullptr) ? 1 : 0;
-  bp.bias_c = kLog2e;
-  bp.scale = p.scale;
-  bp.q_scaled = p.l2norm_qk ? 1 : 0;
-  bp.G = p.groups; bp.lgm = plan.fuse_norm ? log2_blocks_per_group(p) : 0; bp.norm_eps = 1e-12f;
-  bp.rq = (plan.fuse_norm && dq_splits <= 1) ? a->norm.rq : nullptr;    // fused: dq kernel writes the final dq
-  bp.rk = (plan.fuse_norm && (!grouped || plan.kv_sweep) && dkv_splits <= 1) ? a->norm.rk : nullptr;          // fused: dkv kernel writes the final dk
-
-  // 1. dQ (also publishes delta), 2. dK/dV, 3. head reduction + l2norm backward where needed
-  if (al != nullptr) {
-    if (int rc = timed("bwd_dq", "backward dq", s, [&] { return fcsa::launch_backward_dq_alibi(p.dtype, p.dim_head, bp, *al, s); })) return rc;
-    if (int rc = timed("bwd_dkv", "backward dkv", s, [&] { return fcsa::launch_backward_dkv_alibi(p.dtype, p.dim_head, bp, *al, s); })) return rc;
-  } else {
-  if (int rc = timed("bwd_dq", "backward dq", s, [&] { return fcsa::launch_backward_dq(p.dtype, p.dim_head, bp, s); })) return rc;
-  if (int rc = timed("bwd_dkv", "backward dkv", s, [&] { return fcsa::launch_backward_dkv(p.dtype, p.dim_head, bp, s); })) return rc;
-  }
-  if (want_dbias) {      // d_bias from recomputed dS tiles; needs delta, which the dQ kernel published
-    if (int rc = timed("bwd_dbias", "backward d_bias", s, [&] { return fcsa::launch_backward_dbias(p.dtype, p.dim_head, bp, s); })) return rc;
-  }
-
-  fcsa::NormBwdParams nb;
-  nb.eps = 1e-12f;
-  nb.D = p.dim_head;
-  nb.B = p.batch;
-  nb.xn_scale = 1.f;
-  if (dq_splits > 1) {          // sum the split slabs ("heads" of a flat (batch * head) batch), then the l2norm backward if any
-    nb.B = p.batch * p.heads;
-    nb.slab = ws + L.dq_slab; nb.slab_f32 = 1; nb.HS = dq_splits; nb.HO = 1; nb.L = p.q_len;
-    if (p.l2norm_qk) { nb.xn = static_cast<const char*>(a->norm.qn); nb.inv_norm = a->norm.rq; nb.G = p.groups; nb.xn_scale = 1.f / (p.scale * kLog2e); }
-    else             { nb.xn = nullptr; nb.inv_norm = nullptr; nb.G = 1; }
-    nb.dx = view(a->dq, es);
-    nb.dx.sb = nb.dx.sh;          // flat (batch * head) index: stride0 == heads * stride1 (checked above)
-    nb.dx.sh = 0;
-  } else if (dq_slab) {
-    nb.slab = ws + L.dq_slab; nb.slab_f32 = 1; nb.HS = p.heads; nb.HO = p.heads; nb.L = p.q_len;
-    nb.xn = static_cast<const char*>(a->norm.qn); nb.inv_norm = a->norm.rq; nb.G = p.groups;
-    nb.xn_scale = 1.f / (p.scale * kLog2e);           // qn holds c1 * q^
-    nb.dx = view(a->dq, es);
-  }
-  // (the dq pass is launched below, together with the dk / dv passes where there are any: one grid instead of two or three)
-  const fcsa::NormBwdParams nq = nb;
-  nb.B = p.batch;
-  fcsa::NormBwdParams nk = nb, nv = nb;
-  if (dk_slab) {
-    nk.slab = ws + L.dk_slab; nk.slab_f32 = 1; nk.HS = p.heads; nk.HO = p.kv_heads; nk.L = p.k_len;
-    nk.xn_scale = 1.f;
-    if (p.l2norm_qk) { nk.xn = static_cast<const char*>(a->norm.kn); nk.inv_norm = a->norm.rk; nk.G = p.groups; }
-    else             { nk.xn = nullptr; nk.inv_norm = nullptr; nk.G = 1; }
-    nk.dx = view(a->dk, es);
-  }
-  if (dv_slab) {
-    nv.slab = ws + L.dv_slab; nv.slab_f32 = 1; nv.HS = p.heads; nv.HO = p.kv_heads; nv.L = p.k_len;
-    nv.xn = nullptr; nv.inv_norm = nullptr; nv.G = 1; nv.xn_scale = 1.f;
-    nv.dx = view(a->dv, es);
-  }
-  if (dkv_splits > 1) {         // the splits are the "heads" of a flat (batch * head) batch, summed down to one
-    for (fcsa::NormBwdParams* n : {&nk, &nv}) {
-      if (grouped) {              // slabs [batch][heads x splits][M][D]: each K/V head sums its group's heads x splits
-        n->HS = p.heads * dkv_splits; n->HO = p.kv_heads;
-        continue;
-      }
-      n->B = p.batch * p.heads; n->HS = dkv_splits; n->HO = 1;
-      n->dx.sb = n->dx.sh;        // flat (batch * head) index: stride0 == heads * stride1 (checked above)
-      n->dx.sh = 0;
-    }
-  }
-  if (dq_slab && dk_slab && dv_slab) {      // causal problems on small grids (dQ and dK/dV both split), split dQ with single-headed K/V: one launch
-    if (int rc = timed("finalize", "finalize dq+dk+dv", s, [&] { return fcsa::launch_l2norm_bwd_triple(p.dtype, nq, nk, nv, s); })) return rc;
-  } else if (dq_slab && dk_slab) {          // l2norm groups that are not 8 * 2^k features wide
-    if (int rc = timed("finalize", "finalize dq+dk", s, [&] { return fcsa::launch_l2norm_bwd_pair(p.dtype, nq, nk, s); })) return rc;
-  } else {
-    if (dq_slab) {
-      if (int rc = timed("finalize", "finalize dq", s, [&] { return fcsa::launch_l2norm_bwd(p.dtype, nq, s); })) return rc;
-    }
-    if (dk_slab && dv_slab) {      // single-headed K/V, split-query dK/dV: both reductions in one launch
-      if (int rc = timed("finalize", "finalize dk+dv", s, [&] { return fcsa::launch_l2norm_bwd_pair(p.dtype, nk, nv, s); })) return rc;
-    } else if (dk_slab) {
-      if (int rc = timed("finalize", "finalize dk", s, [&] { return fcsa::launch_l2norm_bwd(p.dtype, nk, s); })) return rc;
-    } else if (dv_slab) {
-      if (int rc = timed("finalize", "finalize dv", s, [&] { return fcsa::launch_l2norm_bwd(p.dtype, nv, s); })) return rc;
-    }
-  }
-  // Two degenerate problems whose dq and dk are EXACTLY zero, and for which the kernels' arithmetic is not meaningful:
-  //   scale == 0: the logits do not depend on q, k.  The kernels carry c1 = scale * log2(e) folded into the saved q^ and undo it with
-  //     1 / c1 in the l2norm backward and the dK^ epilogue: 0 * inf = NaN.
-  //   l2norm groups of ONE feature (groups == dim_head): x^ = sign(x), whose derivative is zero; the tangent-space projection
-  //     r (g - x^ <g, x^>) is then a pure cancellation that the 16-bit rounding of c1 * q^ leaves at 2^-11 |g| / |x| -- unbounded for
-  //     elements near zero (measured 0.7 against an exact 0).
-  // The reference's autograd through F.normalize / scale * sim gives zeros in both; dv (and d_bias) are what the kernels wrote.
-  if (p.scale == 0.f || (p.l2norm_qk && p.groups == p.dim_head)) {
-    if (int rc = zero_rows("dq", a->dq, es, p.batch, p.heads, p.q_len, p.dim_head, s)) return rc;
-    if (int rc = zero_rows("dk", a->dk, es, p.batch, p.kv_heads, p.k_len, p.dim_head, s)) return rc;
-  }
-  return FCSA_OK;
-}
-
-}  // namespace

@@ -169,7 +169,8 @@ void* stream_of(const Tensor& t) { return c10::hip::getCurrentHIPStream(t.device
 // One canonicalised call, dense -- q [B, H, N, D], k / v [B, Hk, M, D] -- or packed variable-length sequences (fcsa_forward_varlen /
 // fcsa_backward_varlen): q [total_q, H, D], k / v [total_k, Hk, D], cu_seqlens_* int32 [S + 1] on q's device.  The tables are passed to the
 // library as they are: their contents are never read on the host (the Python wrapper validates host tables before they are moved to the
-// device).  canonicalise / canonicalise_varlen build it; everything after them (forward_body, backward_body) exists once.
+// device).  canonicalise / canonicalise_varlen build it and the op function adds the options it has; everything after them (forward_body,
+// backward_body, the choice of the C function: kTrainEntries) exists once and reads the description.
 struct Call {
   Tensor q, k, v;                 // rows ok
   optional<Tensor> mask, bias;    // dense only; contiguous
@@ -178,8 +179,15 @@ struct Call {
   at::DimVector rows_q, rows_k;   // leading dims of the q-side / k-side saved tensors: (B, H, N) / (B, Hk, M); packed (H, total_q) / (Hk, total_k)
   int64_t D = 0, groups = 1;      // groups as the caller gave it (p.groups is 1 without l2norm_qk)
   fcsa_problem p;
+  fcsa_varlen table{};            // packed only: cu_q / cu_k as the library takes them
+  // what some calls have
+  optional<fcsa_window> win;      // a sliding window (Win's checks passed)
+  optional<fcsa_alibi> alibi;     // the slopes of a linear position bias (TrainSlopes' checks passed)
+  const Tensor* d_lse = nullptr;  // backward only: the gradient of the rows' log-sum-exp (attention_state_backward)
   bool packed() const { return cu_q.defined(); }
   Layout layout() const { return packed() ? kPacked : kDense; }
+  const fcsa_varlen* seqs() const { return packed() ? &table : nullptr; }
+  const fcsa_window* window() const { return win ? &*win : nullptr; }
 };
 
 void set_problem(Call& c, at::ScalarType dt, int64_t batch, int64_t q_len, int64_t k_len, bool bias_batch, double scale, bool causal,
@@ -276,16 +284,9 @@ Call canonicalise_varlen(const Tensor& q, const Tensor& k, const Tensor& v, cons
   c.cu_q = cu_q.contiguous(); c.cu_k = cu_k.contiguous();
   c.rows_q = {H, TQ};
   c.rows_k = {Hk, TK};
+  c.table = {c.cu_q.data_ptr<int32_t>(), c.cu_k.data_ptr<int32_t>(), TQ, TK};
   set_problem(c, q.scalar_type(), S, max_q, max_k, false, scale, causal, l2norm_qk, groups);
   return c;
-}
-
-fcsa_varlen varlen_table(const Call& c) {
-  fcsa_varlen t;
-  t.cu_seqlens_q = c.cu_q.data_ptr<int32_t>();
-  t.cu_seqlens_k = c.cu_k.data_ptr<int32_t>();
-  t.total_q = c.q.size(0); t.total_k = c.k.size(0);
-  return t;
 }
 
 at::DimVector with_last(at::DimVector rows, int64_t last) {
@@ -304,13 +305,50 @@ struct Win {
     w.right = (int32_t)std::min<int64_t>(right, INT32_MAX);
   }
 };
+Call windowed(Call c, const optional<fcsa_window>& w) {
+  c.win = w;
+  return c;
+}
+// window sides where a window is optional: (-1, -1) is the un-windowed call (nullopt), anything else passes Win's checks
+struct OptWin {
+  optional<fcsa_window> w;
+  OptWin(int64_t left, int64_t right) { if (!(left == -1 && right == -1)) w = Win(left, right).w; }
+  const fcsa_window* ptr() const { return w.has_value() ? &*w : nullptr; }
+};
+
+// The entry points of the family, one row each: the forward and backward symbols (as errors name them), the forward call, the backward
+// workspace and the backward call (d_lse: the float32 lse gradient in inv_l's layout).  The one place that knows which C function serves
+// which call; the slopes' entry points take the window as it is, NULL included.
+struct TrainEntry {
+  const char *forward_symbol, *backward_symbol;
+  int (*forward)(const fcsa_forward_args&, const Call&);
+  size_t (*backward_ws)(const Call&);      // null: that of the call without d_lse
+  int (*backward)(const fcsa_backward_args&, const Call&, const float* d_lse);
+};
+enum TrainRoute { kPlainCall, kPackedCall, kWindowCall, kSlopesCall, kStateCall };
+const TrainEntry kTrainEntries[] = {
+    {"fcsa_forward", "fcsa_backward", [](const fcsa_forward_args& a, const Call&) { return g_abi.forward(&a); },
+     [](const Call& c) { return g_abi.backward_ws(&c.p); }, [](const fcsa_backward_args& a, const Call&, const float*) { return g_abi.backward(&a); }},
+    {"fcsa_forward_varlen", "fcsa_backward_varlen", [](const fcsa_forward_args& a, const Call& c) { return g_abi.forward_varlen(&a, c.seqs()); },
+     [](const Call& c) { return g_abi.backward_varlen_ws(&c.p, c.seqs()); },
+     [](const fcsa_backward_args& a, const Call& c, const float*) { return g_abi.backward_varlen(&a, c.seqs()); }},
+    {"fcsa_forward_window", "fcsa_backward_window", [](const fcsa_forward_args& a, const Call& c) { return g_abi.forward_window(&a, c.seqs(), c.window()); },
+     [](const Call& c) { return g_abi.backward_window_ws(&c.p, c.seqs(), c.window()); },
+     [](const fcsa_backward_args& a, const Call& c, const float*) { return g_abi.backward_window(&a, c.seqs(), c.window()); }},
+    {"fcsa_forward_alibi", "fcsa_backward_alibi",
+     [](const fcsa_forward_args& a, const Call& c) { return g_abi.forward_alibi(&a, c.seqs(), c.window(), &*c.alibi); },
+     [](const Call& c) { return g_abi.backward_alibi_ws(&c.p, c.seqs(), c.window()); },
+     [](const fcsa_backward_args& a, const Call& c, const float*) { return g_abi.backward_alibi(&a, c.seqs(), c.window(), &*c.alibi); }},
+    /* kStateCall: a backward with d_lse */ {nullptr, "fcsa_backward_state", nullptr, nullptr,
+     [](const fcsa_backward_args& a, const Call& c, const float* d_lse) { return g_abi.backward_state(&a, c.seqs(), c.window(), d_lse); }},
+};
+TrainRoute train_route(const Call& c, bool d_lse) { return c.alibi ? kSlopesCall : d_lse ? kStateCall : c.win ? kWindowCall : c.packed() ? kPackedCall : kPlainCall; }
 
 // (o, inv_l, qn, kn, rq, rk): o shaped like q; inv_l float32 [rows_q]; qn [rows_q, D], kn [rows_k, D] in q's dtype; rq / rk float32
 // [rows_q, G] / [rows_k, G].  The saved-state tensors are empty (numel 0) where they are not produced.
 using Saved = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
 
-// alibi: the slopes of a linear position bias (alibi_train ops; fcsa_forward_alibi takes `win` as it is, NULL included), or nullptr
-Saved forward_body(const Call& c, bool need_backward, const fcsa_window* win, Lap& lap, const fcsa_alibi* alibi = nullptr) {
+Saved forward_body(const Call& c, bool need_backward, Lap& lap) {
   const bool l2norm_qk = c.p.l2norm_qk != 0;
   TORCH_CHECK_VALUE(!l2norm_qk || (c.groups >= 1 && c.D % c.groups == 0), "groups (", c.groups, ") must divide the head dimension (", c.D, ")");
   c10::DeviceGuard guard(c.q.device());
@@ -348,9 +386,9 @@ Saved forward_body(const Call& c, bool need_backward, const fcsa_window* win, La
   a.norm.rk = (l2norm_qk && need_backward) ? rk.data_ptr<float>() : nullptr;
   Tensor ws;
   a.workspace = nullptr; a.workspace_bytes = 0;
-  if (!c.packed() && alibi == nullptr) {      // packed sequences and calls with slopes never split the key range
+  if (!c.packed() && !c.alibi) {      // packed sequences and calls with slopes never split the key range
     size_t need = g_abi.forward_ws(&a.p);      // 0 unless the key range is split (grids that cannot fill the chip)
-    if (win != nullptr) {      // a window that IS the un-windowed or the causal call splits like that call: room for either
+    if (c.win) {      // a window that IS the un-windowed or the causal call splits like that call: room for either
       fcsa_problem other = a.p;
       other.causal = !other.causal;
       need = std::max(need, g_abi.forward_ws(&other));
@@ -362,18 +400,8 @@ Saved forward_body(const Call& c, bool need_backward, const fcsa_window* win, La
   }
   a.stream = stream_of(c.q);
   lap.mark(1);
-  if (alibi != nullptr) {
-    fcsa_varlen t;
-    if (c.packed()) t = varlen_table(c);
-    check(g_abi.forward_alibi(&a, c.packed() ? &t : nullptr, win, alibi), "fcsa_forward_alibi");
-  } else if (c.packed()) {
-    const fcsa_varlen t = varlen_table(c);
-    if (win != nullptr) check(g_abi.forward_window(&a, &t, win), "fcsa_forward_window");
-    else check(g_abi.forward_varlen(&a, &t), "fcsa_forward_varlen");
-  } else {
-    if (win != nullptr) check(g_abi.forward_window(&a, nullptr, win), "fcsa_forward_window");
-    else check(g_abi.forward(&a), "fcsa_forward");
-  }
+  const TrainEntry& e = kTrainEntries[train_route(c, false)];
+  check(e.forward(a, c), e.forward_symbol);
   lap.mark(2);
   lap.count(6);
   if (c.merged) o = o.squeeze(1);                                                                                  // cu:1740-1741
@@ -383,25 +411,26 @@ Saved forward_body(const Call& c, bool need_backward, const fcsa_window* win, La
 Saved forward(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& mask, const optional<Tensor>& attn_bias,
               bool attn_bias_batch_dim, double scale, bool causal, bool l2norm_qk, int64_t groups, bool need_backward) {
   Lap lap(true);
-  return forward_body(canonicalise(q, k, v, mask, attn_bias, attn_bias_batch_dim, scale, causal, l2norm_qk, groups), need_backward, nullptr, lap);
+  return forward_body(canonicalise(q, k, v, mask, attn_bias, attn_bias_batch_dim, scale, causal, l2norm_qk, groups), need_backward, lap);
 }
+// the window ops take their sides as they are ((-1, -1) is a window too) and check them before their tensors
 Saved window_forward(const Tensor& q, const Tensor& k, const Tensor& v, double scale, bool causal, bool l2norm_qk, int64_t groups,
                      bool need_backward, int64_t left, int64_t right) {
   const Win win(left, right);
   Lap lap(true);
-  return forward_body(canonicalise(q, k, v, c10::nullopt, c10::nullopt, false, scale, causal, l2norm_qk, groups), need_backward, &win.w, lap);
+  return forward_body(windowed(canonicalise(q, k, v, c10::nullopt, c10::nullopt, false, scale, causal, l2norm_qk, groups), win.w), need_backward, lap);
 }
 Saved varlen_forward(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q, const Tensor& cu_k, int64_t max_q, int64_t max_k,
                      double scale, bool causal, bool l2norm_qk, int64_t groups, bool need_backward) {
   Lap lap(false);
-  return forward_body(canonicalise_varlen(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups), need_backward, nullptr, lap);
+  return forward_body(canonicalise_varlen(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups), need_backward, lap);
 }
 Saved varlen_window_forward(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& cu_q, const Tensor& cu_k, int64_t max_q,
                             int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups, bool need_backward, int64_t left,
                             int64_t right) {
   Lap lap(false);
   const Win win(left, right);
-  return forward_body(canonicalise_varlen(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups), need_backward, &win.w, lap);
+  return forward_body(windowed(canonicalise_varlen(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups), win.w), need_backward, lap);
 }
 
 // (dq, dk, dv, d_bias) in the shapes / dtype of the canonical inputs; d_bias (dense only) is empty when not requested and undefined for a
@@ -409,8 +438,7 @@ Saved varlen_window_forward(const Tensor& q, const Tensor& k, const Tensor& v, c
 using Grads = std::tuple<Tensor, Tensor, Tensor, Tensor>;
 
 Grads backward_body(const Call& c, const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& qn, const Tensor& kn, const Tensor& rq,
-                    const Tensor& rk, bool need_bias_grad, const fcsa_window* win, Lap& lap, const Tensor* d_lse = nullptr,
-                    const fcsa_alibi* alibi = nullptr) {
+                    const Tensor& rk, bool need_bias_grad, Lap& lap) {
   const bool l2norm_qk = c.p.l2norm_qk != 0;
   const at::ScalarType dt = c.q.scalar_type();
   const auto dev = c.q.device();
@@ -452,9 +480,9 @@ Grads backward_body(const Call& c, const Tensor& d_out, const Tensor& o, const T
   // the gradient of the rows' log-sum-exp (attention_state_backward), brought into inv_l's layout whatever its strides: float32
   // contiguous [B, H, N], packed [H, total_q] from the public [total_q, H]
   Tensor gl;
-  if (d_lse != nullptr) {
+  if (c.d_lse != nullptr) {
     need_abi("attention_state_backward", "fcsa_backward_state", g_abi.backward_state);
-    gl = c.packed() ? d_lse->transpose(0, 1) : *d_lse;
+    gl = c.packed() ? c.d_lse->transpose(0, 1) : *c.d_lse;
     TORCH_CHECK_VALUE(gl.device() == dev && gl.sizes() == at::IntArrayRef(c.rows_q), "d_lse must have the shape of lse on q's device");
     gl = gl.to(at::kFloat).contiguous();
   }
@@ -467,12 +495,8 @@ Grads backward_body(const Call& c, const Tensor& d_out, const Tensor& o, const T
   if (!c.packed()) db = (c.bias.has_value() && need_bias_grad) ? at::empty(c.bias->sizes(), opt) : at::empty({0}, opt);
   fcsa_backward_args a;
   a.p = c.p;
-  fcsa_varlen t;
-  if (c.packed()) t = varlen_table(c);
-  const fcsa_varlen* seqs = c.packed() ? &t : nullptr;
-  size_t wsb = alibi != nullptr ? g_abi.backward_alibi_ws(&a.p, seqs, win)
-               : win != nullptr ? g_abi.backward_window_ws(&a.p, seqs, win)
-               : seqs != nullptr ? g_abi.backward_varlen_ws(&a.p, seqs) : g_abi.backward_ws(&a.p);
+  const TrainEntry& e = kTrainEntries[train_route(c, gl.defined())];
+  size_t wsb = (e.backward_ws != nullptr ? e : kTrainEntries[train_route(c, false)]).backward_ws(c);
   if (wsb < 256) wsb = 256;
   Tensor ws = at::empty({(int64_t)wsb}, opt.dtype(at::kByte));      // the caching allocator
   const Layout l = c.layout();
@@ -490,11 +514,7 @@ Grads backward_body(const Call& c, const Tensor& d_out, const Tensor& o, const T
   a.workspace = ws.data_ptr(); a.workspace_bytes = wsb;
   a.stream = stream_of(c.q);
   lap.mark(4);
-  if (alibi != nullptr) check(g_abi.backward_alibi(&a, seqs, win, alibi), "fcsa_backward_alibi");
-  else if (gl.defined()) check(g_abi.backward_state(&a, seqs, win, gl.data_ptr<float>()), "fcsa_backward_state");
-  else if (win != nullptr) check(g_abi.backward_window(&a, seqs, win), "fcsa_backward_window");
-  else if (seqs != nullptr) check(g_abi.backward_varlen(&a, seqs), "fcsa_backward_varlen");
-  else check(g_abi.backward(&a), "fcsa_backward");
+  check(e.backward(a, c, gl.defined() ? gl.data_ptr<float>() : nullptr), e.backward_symbol);
   lap.mark(5);
   lap.count(7);
   return std::make_tuple(dq, dk, dv, db);
@@ -504,17 +524,17 @@ Grads backward_body(const Call& c, const Tensor& d_out, const Tensor& o, const T
 Grads dense_backward(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k, const Tensor& v,
                      const optional<Tensor>& mask, const optional<Tensor>& attn_bias, const Tensor& qn, const Tensor& kn, const Tensor& rq,
                      const Tensor& rk, bool attn_bias_batch_dim, double scale, bool causal, bool l2norm_qk, int64_t groups, bool need_bias_grad,
-                     const fcsa_window* win) {
+                     const optional<fcsa_window>& win) {
   Lap lap(true);
-  auto [dq, dk, dv, db] = backward_body(canonicalise(q, k, v, mask, attn_bias, attn_bias_batch_dim, scale, causal, l2norm_qk, groups), d_out, o, inv_l,
-                                        qn, kn, rq, rk, need_bias_grad, win, lap);
+  auto [dq, dk, dv, db] = backward_body(windowed(canonicalise(q, k, v, mask, attn_bias, attn_bias_batch_dim, scale, causal, l2norm_qk, groups), win),
+                                        d_out, o, inv_l, qn, kn, rq, rk, need_bias_grad, lap);
   return std::make_tuple(dq.reshape(q.sizes()), dk.reshape(k.sizes()), dv.reshape(v.sizes()), db);
 }
 Grads backward(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k, const Tensor& v,
                const optional<Tensor>& mask, const optional<Tensor>& attn_bias, const Tensor& qn, const Tensor& kn, const Tensor& rq,
                const Tensor& rk, bool attn_bias_batch_dim, double scale, bool causal, bool l2norm_qk, int64_t groups, bool need_bias_grad) {
   return dense_backward(d_out, o, inv_l, q, k, v, mask, attn_bias, qn, kn, rq, rk, attn_bias_batch_dim, scale, causal, l2norm_qk, groups,
-                        need_bias_grad, nullptr);
+                        need_bias_grad, c10::nullopt);
 }
 
 // (dq, dk, dv) shaped like q, k, v
@@ -526,14 +546,14 @@ Grads3 window_backward(const Tensor& d_out, const Tensor& o, const Tensor& inv_l
                        int64_t groups, int64_t left, int64_t right) {
   const Win win(left, right);
   return first3(dense_backward(d_out, o, inv_l, q, k, v, c10::nullopt, c10::nullopt, qn, kn, rq, rk, false, scale, causal, l2norm_qk, groups, false,
-                               &win.w));
+                               win.w));
 }
 Grads3 varlen_backward(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k, const Tensor& v,
                        const Tensor& cu_q, const Tensor& cu_k, const Tensor& qn, const Tensor& kn, const Tensor& rq, const Tensor& rk,
                        int64_t max_q, int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups) {
   Lap lap(false);
   return first3(backward_body(canonicalise_varlen(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups), d_out, o, inv_l, qn, kn, rq,
-                              rk, false, nullptr, lap));
+                              rk, false, lap));
 }
 Grads3 varlen_window_backward(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k, const Tensor& v,
                               const Tensor& cu_q, const Tensor& cu_k, const Tensor& qn, const Tensor& kn, const Tensor& rq, const Tensor& rk,
@@ -541,8 +561,8 @@ Grads3 varlen_window_backward(const Tensor& d_out, const Tensor& o, const Tensor
                               int64_t right) {
   Lap lap(false);
   const Win win(left, right);
-  return first3(backward_body(canonicalise_varlen(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups), d_out, o, inv_l, qn, kn, rq,
-                              rk, false, &win.w, lap));
+  return first3(backward_body(windowed(canonicalise_varlen(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups), win.w), d_out, o,
+                              inv_l, qn, kn, rq, rk, false, lap));
 }
 
 // ---- autograd in C++ (reference: the Python autograd.Function FlashCosineSimAttention, flash_cosine_sim_attention.py:245-302).
@@ -762,14 +782,6 @@ struct CacheCall {
 };
 
 const Tensor* ptr(const optional<Tensor>& t) { return t.has_value() ? &*t : nullptr; }
-
-// window sides as the cache ops take them: (-1, -1) is the un-windowed call (ptr() null), anything else passes Win's checks
-struct OptWin {
-  fcsa_window w{};
-  const bool on;
-  OptWin(int64_t left, int64_t right) : on(!(left == -1 && right == -1)) { if (on) w = Win(left, right).w; }
-  const fcsa_window* ptr() const { return on ? &w : nullptr; }
-};
 
 void set_scales(CacheCall& c, const optional<Tensor>& k_scale, const optional<Tensor>& v_scale) {
   TORCH_CHECK_VALUE(k_scale.has_value() == v_scale.has_value(), "k_scale and v_scale must be given together");
@@ -1258,24 +1270,49 @@ std::tuple<Tensor, Tensor> merge_states(at::TensorList os, at::TensorList lses) 
 // (o, lse, inv_l, qn, kn, rq, rk): lse float32 [B, H, N], packed [total_q, H].  The saved state is always produced: the lse is read off inv_l.
 using StateSaved = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
 
-Call state_call(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& cu_q, const optional<Tensor>& cu_k, int64_t max_q,
-                int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups) {
+// The slopes of a linear position bias in training (alibi_train ops): float32 [H] or [B, H] (B: batch, packed: sequences) on q's device,
+// any strides, never read on the host.  There is no slope gradient.
+struct TrainSlopes {
+  fcsa_alibi a{};
+  TrainSlopes(const Call& c, const Tensor& slopes) {
+    need_abi("flash_cosine_sim_attention_alibi", "fcsa_forward_alibi / fcsa_backward_alibi", g_abi.forward_alibi, g_abi.backward_alibi, g_abi.backward_alibi_ws);
+    TORCH_CHECK_TYPE(slopes.scalar_type() == at::kFloat, "alibi_slopes must be float32, got ", slopes.scalar_type());
+    TORCH_CHECK_VALUE(slopes.device() == c.q.device(), "alibi_slopes is on ", slopes.device(), " but q is on ", c.q.device(),
+                      ": all tensors must live on q's GPU");
+    const int64_t H = c.p.heads, B = c.p.batch;
+    TORCH_CHECK_VALUE((slopes.dim() == 1 && slopes.size(0) == H) || (slopes.dim() == 2 && slopes.size(0) == B && slopes.size(1) == H),
+                      "alibi_slopes must be [heads] (", H, ") or [", c.packed() ? "sequences" : "batch", ", heads] (", B, ", ", H, "), got ", slopes.sizes());
+    TORCH_CHECK_VALUE(c.packed() || c.p.causal || c.p.q_len <= c.p.k_len, "alibi_slopes: a non-causal call needs q_len <= k_len, got ", c.p.q_len,
+                      " > ", c.p.k_len, " (rows with a negative position have no key at distance 0)");
+    a.slopes = slopes.numel() > 0 ? slopes.data_ptr<float>() : nullptr;
+    a.stride_b = slopes.dim() == 2 ? slopes.stride(0) : 0;
+    a.stride_h = slopes.stride(-1);
+    a.reserved = 0;
+  }
+};
+
+// The call of the ops that take dense or packed q, k, v with an optional window and optional slopes (attention_state, alibi_train): the
+// window's checks, then the tensors', then the slopes'.
+Call option_call(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& cu_q, const optional<Tensor>& cu_k, int64_t max_q,
+                 int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups, int64_t left, int64_t right, const Tensor* slopes) {
+  const OptWin win(left, right);
   TORCH_CHECK_VALUE(cu_q.has_value() == cu_k.has_value(), "cu_seqlens_q and cu_seqlens_k must be given together");
-  if (cu_q.has_value()) return canonicalise_varlen(q, k, v, *cu_q, *cu_k, max_q, max_k, scale, causal, l2norm_qk, groups);
-  TORCH_CHECK_VALUE(q.dim() == 4 && k.dim() == 4 && v.dim() == 4, "attention_state takes 4-D q, k, v, or packed 3-D ones with cu_seqlens");
-  return canonicalise(q, k, v, c10::nullopt, c10::nullopt, false, scale, causal, l2norm_qk, groups);
+  TORCH_CHECK_VALUE(cu_q.has_value() || (q.dim() == 4 && k.dim() == 4 && v.dim() == 4),
+                    "attention_state takes 4-D q, k, v, or packed 3-D ones with cu_seqlens");
+  Call c = cu_q.has_value() ? canonicalise_varlen(q, k, v, *cu_q, *cu_k, max_q, max_k, scale, causal, l2norm_qk, groups)
+                            : canonicalise(q, k, v, c10::nullopt, c10::nullopt, false, scale, causal, l2norm_qk, groups);
+  c.win = win.w;
+  if (slopes != nullptr) c.alibi = TrainSlopes(c, *slopes).a;
+  return c;
 }
 
 StateSaved attention_state_forward(const Tensor& q, const Tensor& k, const Tensor& v, const optional<Tensor>& cu_q, const optional<Tensor>& cu_k,
                                    int64_t max_q, int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups, int64_t left,
                                    int64_t right) {
   need_abi("attention_state", "fcsa_attention_lse", g_abi.attention_lse);
-  const bool windowed = !(left == -1 && right == -1);
-  fcsa_window w{-1, -1};
-  if (windowed) w = Win(left, right).w;
-  const Call c = state_call(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups);
+  const Call c = option_call(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, left, right, nullptr);
   Lap lap(false);
-  auto [o, inv_l, qn, kn, rq, rk] = forward_body(c, true, windowed ? &w : nullptr, lap);
+  auto [o, inv_l, qn, kn, rq, rk] = forward_body(c, true, lap);
   c10::DeviceGuard guard(c.q.device());
   const auto f32 = c.q.options().dtype(at::kFloat);
   Tensor lse = c.packed() ? at::empty({c.q.size(0), c.q.size(1)}, f32) : at::empty(c.rows_q, f32);
@@ -1289,17 +1326,14 @@ StateSaved attention_state_forward(const Tensor& q, const Tensor& k, const Tenso
     Call c32;
     Tensor inv_l32;
     if (exact) {
-      c32 = state_call(q.to(at::kFloat), k.to(at::kFloat), v.to(at::kFloat), cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups);
+      c32 = option_call(q.to(at::kFloat), k.to(at::kFloat), v.to(at::kFloat), cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, left, right,
+                        nullptr);
       Lap lap32(false);
-      inv_l32 = std::get<1>(forward_body(c32, true, windowed ? &w : nullptr, lap32));
+      inv_l32 = std::get<1>(forward_body(c32, true, lap32));
     }
     const Call& lc = exact ? c32 : c;
     const fcsa_lse_out lo = strided<fcsa_lse_out>(lse, c.layout());
-    fcsa_varlen t;
-    if (c.packed()) t = varlen_table(c);
-    check(g_abi.attention_lse(&lc.p, (exact ? inv_l32 : inv_l).data_ptr<float>(), c.packed() ? &t : nullptr, windowed ? &w : nullptr, &lo,
-                              stream_of(c.q)),
-          "fcsa_attention_lse");
+    check(g_abi.attention_lse(&lc.p, (exact ? inv_l32 : inv_l).data_ptr<float>(), c.seqs(), c.window(), &lo, stream_of(c.q)), "fcsa_attention_lse");
   }
   return std::make_tuple(o, lse, inv_l, qn, kn, rq, rk);
 }
@@ -1309,13 +1343,11 @@ Grads3 attention_state_backward(const optional<Tensor>& d_out, const optional<Te
                                 const Tensor& k, const Tensor& v, const optional<Tensor>& cu_q, const optional<Tensor>& cu_k, const Tensor& qn,
                                 const Tensor& kn, const Tensor& rq, const Tensor& rk, int64_t max_q, int64_t max_k, double scale, bool causal,
                                 bool l2norm_qk, int64_t groups, int64_t left, int64_t right) {
-  const bool windowed = !(left == -1 && right == -1);
-  fcsa_window w{-1, -1};
-  if (windowed) w = Win(left, right).w;
-  const Call c = state_call(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups);
+  Call c = option_call(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, left, right, nullptr);
+  c.d_lse = ptr(d_lse);
   Lap lap(false);
   const Tensor go = d_out.has_value() ? *d_out : at::zeros_like(o);
-  return first3(backward_body(c, go, o, inv_l, qn, kn, rq, rk, false, windowed ? &w : nullptr, lap, d_lse.has_value() ? &*d_lse : nullptr));
+  return first3(backward_body(c, go, o, inv_l, qn, kn, rq, rk, false, lap));
 }
 
 using StateScalars = std::tuple<int64_t, int64_t, double, bool, bool, int64_t, int64_t, int64_t>;   // max_q, max_k, scale, causal, l2norm_qk, groups, left, right
@@ -1361,67 +1393,33 @@ std::tuple<Tensor, Tensor> attention_state_autograd(const Tensor& q, const Tenso
 }
 
 // ---- a linear position bias in training (namespace fcsa_alibi_train): one op family for the dense, the local and the packed operator, as
-// attention_state is -- cu_seqlens given: packed q [total_q, H, D]; window sides of (-1, -1): no window -- through the same state_call /
-// forward_body / backward_body, with the slopes handed to fcsa_forward_alibi / fcsa_backward_alibi.  alibi_slopes: float32 [H] or [B, H]
-// (B: batch, packed: sequences) on q's device, any strides, never read on the host.  There is no slope gradient.
-struct TrainSlopes {
-  fcsa_alibi a{};
-  TrainSlopes(const Call& c, const Tensor& slopes) {
-    need_abi("flash_cosine_sim_attention_alibi", "fcsa_forward_alibi / fcsa_backward_alibi", g_abi.forward_alibi, g_abi.backward_alibi, g_abi.backward_alibi_ws);
-    TORCH_CHECK_TYPE(slopes.scalar_type() == at::kFloat, "alibi_slopes must be float32, got ", slopes.scalar_type());
-    TORCH_CHECK_VALUE(slopes.device() == c.q.device(), "alibi_slopes is on ", slopes.device(), " but q is on ", c.q.device(),
-                      ": all tensors must live on q's GPU");
-    const int64_t H = c.p.heads, B = c.p.batch;
-    TORCH_CHECK_VALUE((slopes.dim() == 1 && slopes.size(0) == H) || (slopes.dim() == 2 && slopes.size(0) == B && slopes.size(1) == H),
-                      "alibi_slopes must be [heads] (", H, ") or [", c.packed() ? "sequences" : "batch", ", heads] (", B, ", ", H, "), got ", slopes.sizes());
-    TORCH_CHECK_VALUE(c.packed() || c.p.causal || c.p.q_len <= c.p.k_len, "alibi_slopes: a non-causal call needs q_len <= k_len, got ", c.p.q_len,
-                      " > ", c.p.k_len, " (rows with a negative position have no key at distance 0)");
-    a.slopes = slopes.numel() > 0 ? slopes.data_ptr<float>() : nullptr;
-    a.stride_b = slopes.dim() == 2 ? slopes.stride(0) : 0;
-    a.stride_h = slopes.stride(-1);
-    a.reserved = 0;
-  }
-};
-
+// attention_state is -- cu_seqlens given: packed q [total_q, H, D]; window sides of (-1, -1): no window -- through the same option_call /
+// forward_body / backward_body, with the slopes (TrainSlopes) handed to fcsa_forward_alibi / fcsa_backward_alibi.
 Saved alibi_train_forward(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& alibi_slopes, const optional<Tensor>& cu_q,
                           const optional<Tensor>& cu_k, int64_t max_q, int64_t max_k, double scale, bool causal, bool l2norm_qk, int64_t groups,
                           int64_t left, int64_t right, bool need_backward) {
-  const OptWin win(left, right);
-  const Call c = state_call(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups);
-  const TrainSlopes sl(c, alibi_slopes);
   Lap lap(false);
-  return forward_body(c, need_backward, win.ptr(), lap, &sl.a);
+  return forward_body(option_call(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, left, right, &alibi_slopes), need_backward, lap);
 }
 Grads3 alibi_train_backward(const Tensor& d_out, const Tensor& o, const Tensor& inv_l, const Tensor& q, const Tensor& k, const Tensor& v,
                             const Tensor& alibi_slopes, const optional<Tensor>& cu_q, const optional<Tensor>& cu_k, const Tensor& qn,
                             const Tensor& kn, const Tensor& rq, const Tensor& rk, int64_t max_q, int64_t max_k, double scale, bool causal,
                             bool l2norm_qk, int64_t groups, int64_t left, int64_t right) {
-  const OptWin win(left, right);
-  const Call c = state_call(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups);
-  const TrainSlopes sl(c, alibi_slopes);
   Lap lap(false);
-  return first3(backward_body(c, d_out, o, inv_l, qn, kn, rq, rk, false, win.ptr(), lap, nullptr, &sl.a));
+  return first3(backward_body(option_call(q, k, v, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, left, right, &alibi_slopes), d_out, o,
+                              inv_l, qn, kn, rq, rk, false, lap));
 }
 
-struct AlibiTrainNode : public torch::autograd::Function<AlibiTrainNode> {
-  static Tensor forward(AutogradContext* ctx, const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& slopes, const optional<Tensor>& cu_q,
-                        const optional<Tensor>& cu_k, const StateScalars& s) {
-    at::AutoDispatchBelowADInplaceOrView guard;
-    static auto op = typed_op("fcsa_alibi_train::forward", &alibi_train_forward);
-    auto r = std::apply([&](const auto&... e) { return op.call(q, k, v, slopes, cu_q, cu_k, e..., true); }, s);
-    ctx->save_for_backward({std::get<0>(r), std::get<1>(r), q, k, v, std::get<2>(r), std::get<3>(r), std::get<4>(r), std::get<5>(r),
-                            saveable(cu_q), saveable(cu_k), slopes});
-    ctx->saved_data["scalars"] = c10::IValue(s);
-    return std::get<0>(r);
-  }
-  static variable_list backward(AutogradContext* ctx, variable_list grads) {
-    const auto t = ctx->get_saved_variables();      // o, inv_l, q, k, v, qn, kn, rq, rk, cu_q, cu_k, slopes
-    const StateScalars s = ctx->saved_data["scalars"].to<StateScalars>();
-    static auto op = typed_op("fcsa_alibi_train::backward", &alibi_train_backward);
-    const optional<Tensor> cu_q = restored<optional<Tensor>>(t[9]), cu_k = restored<optional<Tensor>>(t[10]);
-    auto g = std::apply([&](const auto&... e) { return op.call(grads[0], t[0], t[1], t[2], t[3], t[4], t[11], cu_q, cu_k, t[5], t[6], t[7], t[8], e...); }, s);
-    return {std::get<0>(g), std::get<1>(g), std::get<2>(g), Tensor(), Tensor(), Tensor(), Tensor()};
-  }
+// the family's node is AttentionNode: need_backward is true whenever it runs, and there is no bias gradient
+struct AlibiTrainOps {
+  static constexpr const char* forward_name = "fcsa_alibi_train::forward";
+  static constexpr const char* backward_name = "fcsa_alibi_train::backward";
+  static constexpr auto fwd = &alibi_train_forward;
+  static constexpr auto bwd = &alibi_train_backward;
+  using Extra = std::tuple<Tensor, optional<Tensor>, optional<Tensor>>;      // alibi_slopes, cu_seqlens_q, cu_seqlens_k
+  using Scalars = StateScalars;
+  using Window = std::tuple<>;
+  static constexpr bool bias_grad = false;
 };
 
 Tensor alibi_train_attention_plain(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& alibi_slopes, const optional<Tensor>& cu_q,
@@ -1438,7 +1436,8 @@ Tensor alibi_train_attention_autograd(const Tensor& q, const Tensor& k, const Te
     static auto op = typed_op("fcsa_alibi_train::attention", &alibi_train_attention_plain);
     return op.call(q, k, v, alibi_slopes, cu_q, cu_k, max_q, max_k, scale, causal, l2norm_qk, groups, left, right);
   }
-  return AlibiTrainNode::apply(q, k, v, alibi_slopes, cu_q, cu_k, StateScalars{max_q, max_k, scale, causal, l2norm_qk, groups, left, right});
+  return AttentionNode<AlibiTrainOps>::apply(q, k, v, optional<Tensor>(), AlibiTrainOps::Extra{alibi_slopes, cu_q, cu_k},
+                                             StateScalars{max_q, max_k, scale, causal, l2norm_qk, groups, left, right}, AlibiTrainOps::Window{});
 }
 
 // merge_state: merge_states (the same function: the forward kernel, bit for bit) with a backward.

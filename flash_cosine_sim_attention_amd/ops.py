@@ -234,6 +234,23 @@ def _packed_on_device(q, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
     return cu_seqlens_q.to(q.device, non_blocking=True), cu_seqlens_k.to(q.device, non_blocking=True), int(max_seqlen_q), int(max_seqlen_k)
 
 
+def _dense_or_packed(name, q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k):
+    """The opening of the functions that take 4-D q, k, v, or packed 3-D ones with both tables (`name`: the function, for its messages).
+    Returns (packed, max_seqlen_q, max_seqlen_k), the latter two as `_check_packed` leaves them."""
+    packed = cu_seqlens_q is not None or cu_seqlens_k is not None
+    if packed:
+        if cu_seqlens_q is None or cu_seqlens_k is None:
+            raise ValueError("cu_seqlens_q and cu_seqlens_k must be given together")
+        max_seqlen_q, max_seqlen_k = _check_packed(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
+    else:
+        if max_seqlen_q is not None or max_seqlen_k is not None:
+            raise ValueError("max_seqlen_q / max_seqlen_k belong to packed calls (cu_seqlens_q, cu_seqlens_k)")
+        if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+            raise ValueError(f"{name} takes 4-D q, k, v ([batch, heads, length, dim_head]), or packed 3-D ones "
+                             "with cu_seqlens_q and cu_seqlens_k")
+    return packed, max_seqlen_q, max_seqlen_k
+
+
 def flash_cosine_sim_attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q=None, max_seqlen_k=None, scale=8, groups=1,
                                       causal=False, l2norm_qk=True, window_size=(-1, -1)):
     """Fused cosine-similarity attention over packed variable-length sequences.
@@ -293,11 +310,9 @@ def flash_cosine_sim_attention_alibi(q, k, v, alibi_slopes, scale=8, groups=1, c
                         f"{getattr(alibi_slopes, 'dtype', type(alibi_slopes).__name__)}")
     if alibi_slopes.requires_grad:
         raise ValueError("alibi_slopes must not require grad: there is no slope gradient (fixed slopes only)")
-    packed = cu_seqlens_q is not None or cu_seqlens_k is not None
+    packed, max_seqlen_q, max_seqlen_k = _dense_or_packed("flash_cosine_sim_attention_alibi", q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q,
+                                                          max_seqlen_k)
     if packed:
-        if cu_seqlens_q is None or cu_seqlens_k is None:
-            raise ValueError("cu_seqlens_q and cu_seqlens_k must be given together")
-        max_seqlen_q, max_seqlen_k = _check_packed(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
         H, B = q.shape[1], cu_seqlens_q.numel() - 1
         if not causal and cu_seqlens_q.device.type == "cpu" and cu_seqlens_k.device.type == "cpu":
             nq, nk = cu_seqlens_q[1:] - cu_seqlens_q[:-1], cu_seqlens_k[1:] - cu_seqlens_k[:-1]
@@ -305,11 +320,6 @@ def flash_cosine_sim_attention_alibi(q, k, v, alibi_slopes, scale=8, groups=1, c
                 raise ValueError("alibi_slopes: a non-causal call needs N <= M for every sequence (rows with a negative position have no key "
                                  "at distance 0)")
     else:
-        if max_seqlen_q is not None or max_seqlen_k is not None:
-            raise ValueError("max_seqlen_q / max_seqlen_k belong to packed calls (cu_seqlens_q, cu_seqlens_k)")
-        if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
-            raise ValueError("flash_cosine_sim_attention_alibi takes 4-D q, k, v ([batch, heads, length, dim_head]), or packed 3-D ones "
-                             "with cu_seqlens_q and cu_seqlens_k")
         H, B = q.shape[1], q.shape[0]
         if not causal and q.shape[2] > k.shape[2]:
             raise ValueError(f"alibi_slopes: a non-causal call needs N <= M, got N = {q.shape[2]} > M = {k.shape[2]} (rows with a negative "
@@ -1004,17 +1014,8 @@ def flash_cosine_sim_attention_with_lse(q, k, v, scale=8, groups=1, causal=False
     per-batch emptiness rule: not supported with the lse).  Table checks and max_seqlen rules of `flash_cosine_sim_attention_varlen`.
     CPU tensors: forward only, like the other CPU paths."""
     window = _window(window_size)
-    packed = cu_seqlens_q is not None or cu_seqlens_k is not None
-    if packed:
-        if cu_seqlens_q is None or cu_seqlens_k is None:
-            raise ValueError("cu_seqlens_q and cu_seqlens_k must be given together")
-        max_seqlen_q, max_seqlen_k = _check_packed(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k)
-    else:
-        if max_seqlen_q is not None or max_seqlen_k is not None:
-            raise ValueError("max_seqlen_q / max_seqlen_k belong to packed calls (cu_seqlens_q, cu_seqlens_k)")
-        if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
-            raise ValueError("flash_cosine_sim_attention_with_lse takes 4-D q, k, v ([batch, heads, length, dim_head]), or packed 3-D ones "
-                             "with cu_seqlens_q and cu_seqlens_k")
+    packed, max_seqlen_q, max_seqlen_k = _dense_or_packed("flash_cosine_sim_attention_with_lse", q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q,
+                                                          max_seqlen_k)
     if q.device.type == "cpu":
         if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
             raise RuntimeError("flash_cosine_sim_attention_with_lse is forward-only on CPU tensors: run it under torch.no_grad()")

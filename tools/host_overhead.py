@@ -47,6 +47,22 @@ def sd():
 bench("SDPA forward + sum().backward()", sd)
 bench("SDPA forward only (grad)", lambda: torch.nn.functional.scaled_dot_product_attention(q, k, v, is_causal=True))
 bench("torch.empty x 6", lambda: [torch.empty(4, 8, N, 64, device="cuda", dtype=torch.bfloat16) for _ in range(6)])
+# The training operators that take an option -- a window, packed sequences, the lse, slopes -- forward + backward on the same problem (the
+# packed call: the same rows as 4 sequences of N), device tables and max_seqlen given: no call reads a device tensor on the host
+tq, tk, tv = (t.detach().transpose(1, 2).reshape(4 * N, 8, 64).contiguous().requires_grad_() for t in (q, k, v))
+tdo = do.transpose(1, 2).reshape(4 * N, 8, 64).contiguous()
+tcu = torch.arange(5, dtype=torch.int32, device="cuda") * N
+tslopes = torch.tensor([2.0 ** -(h + 1) for h in range(8)], device="cuda")
+def train(fn, leaves, g):
+    def run():
+        for t in leaves: t.grad = None
+        fn().backward(g)
+    return run
+bench("flash_cosine_sim_attention_local, forward + backward", train(lambda: F.flash_cosine_sim_attention_local(q, k, v, (N // 2, 0), causal=True), (q, k, v), do))
+bench("flash_cosine_sim_attention_varlen, forward + backward",
+      train(lambda: F.flash_cosine_sim_attention_varlen(tq, tk, tv, tcu, tcu, max_seqlen_q=N, max_seqlen_k=N, causal=True), (tq, tk, tv), tdo))
+bench("flash_cosine_sim_attention_with_lse, forward + backward", train(lambda: F.flash_cosine_sim_attention_with_lse(q, k, v, causal=True)[0], (q, k, v), do))
+bench("flash_cosine_sim_attention_alibi, forward + backward", train(lambda: F.flash_cosine_sim_attention_alibi(q, k, v, tslopes, causal=True), (q, k, v), do))
 # Decoding against a key/value cache is launch-bound (an append-free step is two launches of a few us), so the host time of its call path
 # is part of its speed: B4 H8 Hk2 N1 D64 bf16 against a full cache of 256 positions, device tables and max_seqlen_k given (no call
 # reads a device tensor on the host)
