@@ -92,6 +92,7 @@ KvCacheStep = _STRUCTS["fcsa_kvcache_step"]
 STEP_CHUNK_ROWS = _MACROS["FCSA_STEP_CHUNK_ROWS"]
 TreeMask = _STRUCTS["fcsa_tree_mask"]
 Alibi = _STRUCTS["fcsa_alibi"]
+Rotary = _STRUCTS["fcsa_rotary"]
 
 
 EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fcsa_forward_workspace_bytes", "fcsa_forward_needs_qn",
@@ -104,7 +105,8 @@ EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fc
            "fcsa_attention_lse", "fcsa_backward_state", "fcsa_merge_states_backward",
            "fcsa_forward_kvcache_step", "fcsa_forward_kvcache_step_workspace_bytes",
            "fcsa_forward_kvcache_tree", "fcsa_kvcache_compact", "fcsa_forward_kvcache_alibi",
-           "fcsa_forward_alibi", "fcsa_backward_alibi", "fcsa_forward_alibi_workspace_bytes", "fcsa_backward_alibi_workspace_bytes")
+           "fcsa_forward_alibi", "fcsa_backward_alibi", "fcsa_forward_alibi_workspace_bytes", "fcsa_backward_alibi_workspace_bytes",
+           "fcsa_forward_kvcache_rotary")
 
 _lib = None
 
@@ -225,6 +227,10 @@ def load():
         for fn in (lib.fcsa_forward_alibi_workspace_bytes, lib.fcsa_backward_alibi_workspace_bytes):
             fn.argtypes = [C.POINTER(Problem), C.POINTER(Varlen), C.POINTER(Window)]
             fn.restype = C.c_size_t
+    if hasattr(lib, "fcsa_forward_kvcache_rotary"):      # (likewise: an FCSA_LIB build from before the rotary embedding of the engine step)
+        lib.fcsa_forward_kvcache_rotary.argtypes = [C.POINTER(ForwardArgs), C.POINTER(KvCache), C.POINTER(Varlen), C.POINTER(KvCacheQuant),
+                                                    C.POINTER(Window), C.POINTER(KvCacheStep), C.POINTER(Rotary), C.POINTER(LseOut)]
+        lib.fcsa_forward_kvcache_rotary.restype = C.c_int
     if hasattr(lib, "fcsa_forward_kvcache_tree"):      # (likewise: an FCSA_LIB build from before tree attention)
         lib.fcsa_forward_kvcache_tree.argtypes = [C.POINTER(ForwardArgs), C.POINTER(KvCache), C.POINTER(Varlen), C.POINTER(KvCacheQuant),
                                                   C.POINTER(TreeMask), C.POINTER(LseOut)]

@@ -62,7 +62,7 @@ _LIKE_QKV = ("varlen_backward", "window_backward", "varlen_window_backward")
 # the cache ops that return (o, lse), by qualified name (the later ones live in namespaces of their own): o shaped like q, their first
 # argument; lse float32 [B, H, N], or [total_q, H] for a ragged step (q [total_q, H, D])
 _O_LSE = ("fcsa::kvcache_lse_forward", "fcsa_prefill::kvcache_prefill_forward", "fcsa_step::kvcache_step_forward",
-          "fcsa_tree::kvcache_tree_forward", "fcsa_alibi::kvcache_alibi_forward")
+          "fcsa_tree::kvcache_tree_forward", "fcsa_alibi::kvcache_alibi_forward", "fcsa_rotary::kvcache_rotary_forward")
 
 
 def _register_fakes():

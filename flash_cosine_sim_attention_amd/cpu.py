@@ -311,9 +311,24 @@ def tree_tail(words, length):
     return bits[:, n - min(n, length):]
 
 
+def rotate_rows_cpu(x, positions, cos, sin, interleaved):
+    """The rotary embedding of `flash_cosine_sim_attention_rotary_with_kvcache` on host tensors: x [..., n, D] (any dtype) -> float32, row i
+    rotated by table row clamp(positions[i], 0, rows - 1) of cos / sin (float32 [rows, rotary_dim / 2]); features at or beyond rotary_dim
+    pass through.  interleaved: pair f is (2 f, 2 f + 1), else (f, f + rotary_dim / 2); (x, y) -> (x cos - y sin, x sin + y cos)."""
+    out = x.float().clone()
+    half = cos.shape[1]
+    rows = torch.tensor(positions, dtype=torch.long).clamp(0, cos.shape[0] - 1)
+    c, s = cos[rows].float(), sin[rows].float()                       # [n, half], broadcast over the leading dims
+    a, b = (out[..., 0:2 * half:2], out[..., 1:2 * half:2]) if interleaved else (out[..., :half], out[..., half:2 * half])
+    ra, rb = a * c - b * s, a * s + b * c
+    a.copy_(ra)
+    b.copy_(rb)
+    return out
+
+
 def attention_forward_kvcache_varlen_cpu(q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, seqlens, block_table=None, scale=8.0, groups=1,
                                          causal=False, l2norm_qk=True, window_size=(-1, -1), k_scale=None, v_scale=None,
-                                         return_lse=False, tree_mask=None, alibi_slopes=None):
+                                         return_lse=False, tree_mask=None, alibi_slopes=None, rotary=None):
     """Forward-only path of `flash_cosine_sim_attention_varlen_with_kvcache` on host tensors: packed q [total_q, H, D] and k_new / v_new
     [total_q, Hk, D] with a validated host table; sequence b's N_b rows run through `attention_forward_kvcache_cpu` as a batch-1 call on
     its own cache (a view: the append lands in the caller's caches), so its rows and its cache slots are exactly what the equal-N path
@@ -322,7 +337,12 @@ def attention_forward_kvcache_varlen_cpu(q, k_cache, v_cache, cu_seqlens_q, k_ne
     P_b = L_b - N_b every query of sequence b sees the cache positions before P_b, and query i sees position P_b + t iff bit t of its word is set; a sequence with N_b > 64 ignores its words and is
     causal.
     alibi_slopes (`flash_cosine_sim_attention_alibi_with_kvcache`): float32 [H] or [B, H]: the logit of key j for query i of sequence b gains
-    -slope[b, h] * |L_b - N_b + i - j|.  It combines with causal and window_size, not with tree_mask."""
+    -slope[b, h] * |L_b - N_b + i - j|.  It combines with causal and window_size, not with tree_mask.
+    rotary (`flash_cosine_sim_attention_rotary_with_kvcache`): (cos, sin, interleaved), float32 host tables: q row i of sequence b is rotated at
+    position L_b - N_b + i and k_new row i at its slot seqlens[b] + i (`rotate_rows_cpu`), in float32 -- the rotated q stays float32, the
+    rotated key is rounded once by the append.  Not with tree_mask or alibi_slopes."""
+    if rotary is not None and (tree_mask is not None or alibi_slopes is not None):
+        raise ValueError("the rotary embedding is not taken with a tree_mask or alibi_slopes")
     if tree_mask is not None and (causal or tuple(window_index(window_size)) != (-1, -1)):
         raise ValueError("tree_mask states the visibility: no causal and no window_size with it")
     if tree_mask is not None and alibi_slopes is not None:
@@ -336,11 +356,18 @@ def attention_forward_kvcache_varlen_cpu(q, k_cache, v_cache, cu_seqlens_q, k_ne
             continue
         rows = lambda t: None if t is None else t[lo:hi].permute(1, 0, 2).unsqueeze(0)      # [1, heads, N_b, D]
         paged = block_table is not None
+        qb, kb = rows(q), rows(k_new)
+        if rotary is not None:
+            capacity = k_cache.shape[2] * (block_table.shape[1] if paged else 1)
+            length = min(min(max(seqlens[b], 0), capacity) + (hi - lo if k_new is not None else 0), capacity)
+            qb = rotate_rows_cpu(qb, [length - (hi - lo) + i for i in range(hi - lo)], *rotary)
+            if kb is not None:
+                kb = rotate_rows_cpu(kb, [seqlens[b] + i for i in range(hi - lo)], *rotary)
         kc, vc = (k_cache, v_cache) if paged else (k_cache[b:b + 1], v_cache[b:b + 1])
         quant = {} if k_scale is None else dict(k_scale=k_scale[b:b + 1], v_scale=v_scale[b:b + 1])
         words = tree_mask[lo:hi] if tree_mask is not None and hi - lo <= TREE_MAX_TOKENS else None
         slopes = None if alibi_slopes is None else (alibi_slopes if alibi_slopes.dim() == 1 else alibi_slopes[b])      # [H] of this sequence
-        o, l = attention_forward_kvcache_cpu(rows(q), kc, vc, rows(k_new), rows(v_new), [seqlens[b]], block_table[b:b + 1] if paged else None,
+        o, l = attention_forward_kvcache_cpu(qb, kc, vc, kb, rows(v_new), [seqlens[b]], block_table[b:b + 1] if paged else None,
                                              scale=scale, groups=groups, causal=causal or (tree_mask is not None and words is None),
                                              l2norm_qk=l2norm_qk, window_size=window_size, return_lse=True, tree_words=words,
                                              alibi_slopes=slopes, **quant)

@@ -822,6 +822,7 @@ struct DecodeCall {
   const fcsa_kvcache_step* step = nullptr;      // an engine step (fcsa_forward_kvcache_step): the routing of a ragged step, or NULL
   const fcsa_tree_mask* tree = nullptr;         // a tree step (fcsa_forward_kvcache_tree): the visibility words of a ragged step, or NULL
   const fcsa_alibi* alibi = nullptr;            // a linear position bias (fcsa_forward_kvcache_alibi) on a ragged or engine step, or NULL
+  const fcsa_rotary* rotary = nullptr;          // a rotary embedding (fcsa_forward_kvcache_rotary) of q and k_new on an engine step, or NULL
 };
 
 // The window of a decode call as the kernels take it.  A rectangular call is normalised (fcsa::win_normalise): a window that hides nothing
@@ -1039,9 +1040,21 @@ int check_workspace(const char* who, const fcsa_forward_args& a, const DecodePla
   return FCSA_OK;
 }
 
-// the append (before anything reads the cache: same stream), where the call brings rows and the cache has room for any
+// c.rotary (a rotary embedding): the tables as the kernels take them, and the names of the launches that rotate
+fcsa::DecodeRotary rotary_view(const fcsa_rotary& r) { return {r.cos, r.sin, r.stride_row, (int)r.rows, r.rotary_dim, r.interleaved}; }
+constexpr LaunchName kRotaryAppendName[2] = {{"kv_append_rotary", "kv append (rotary)"}, {"kv_append_rotary_fp8", "kv append (rotary, fp8)"}};
+constexpr LaunchName kRotaryDecodeName[2] = {{"rotary_decode", "decode (rotary)"}, {"rotary_decode_fp8", "decode (rotary, fp8)"}};
+constexpr LaunchName kRotaryPrefillName[2] = {{"rotary_prefill", "prefill (rotary)"}, {"rotary_prefill_fp8", "prefill (rotary, fp8)"}};
+
+// the append (before anything reads the cache: same stream), where the call brings rows and the cache has room for any; c.rotary: the
+// append that rotates K on its way into the cache
 int append_launch(const DecodeCall& c, fcsa::DecodeForm form, const fcsa::DecodeStepParams& dp, hipStream_t s) {
   if (c.kv->new_len <= 0 || c.kv->capacity <= 0) return FCSA_OK;
+  if (c.rotary != nullptr) {
+    const LaunchName& n = kRotaryAppendName[form.fp8];
+    const fcsa::DecodeRotary ro = rotary_view(*c.rotary);
+    return timed(n.name, n.what, s, [&] { return fcsa::launch_kv_append_rotary(c.a->p.dtype, c.a->p.dim_head, form, dp, ro, s); });
+  }
   const LaunchName& n = kAppendName[form.ragged][form.fp8];
   return timed(n.name, n.what, s, [&] { return fcsa::launch_kv_append(c.a->p.dtype, c.a->p.dim_head, form, dp, s); });
 }
@@ -1054,6 +1067,11 @@ constexpr LaunchName kAlibiPrefillName[2] = {{"alibi_prefill", "prefill (alibi)"
 // the decode launch of a ragged or engine step under the name `plain`; c.alibi: the entry points that take the slopes, under their own name
 int decode_launch(const LaunchName& plain, const DecodeCall& c, fcsa::DecodeForm form, const fcsa::DecodeStepParams& dp, hipStream_t s) {
   const fcsa_problem& p = c.a->p;
+  if (c.rotary != nullptr) {
+    const LaunchName& n = kRotaryDecodeName[form.fp8];
+    const fcsa::DecodeRotary ro = rotary_view(*c.rotary);
+    return timed(n.name, n.what, s, [&] { return fcsa::launch_decode_rotary(p.dtype, p.dim_head, form, dp, ro, s); });
+  }
   if (c.alibi == nullptr) return timed(plain.name, plain.what, s, [&] { return fcsa::launch_decode(p.dtype, p.dim_head, form, dp, s); });
   const LaunchName& n = kAlibiDecodeName[form.fp8];
   const fcsa::DecodeAlibi al = alibi_view(*c.alibi);
@@ -1068,6 +1086,11 @@ int chunk_launch(const LaunchName& plain, const DecodeCall& c, fcsa::DecodeForm 
   dp.ws_ml = nullptr;
   const fcsa::DecodeLseOut lo = c.lse != nullptr ? lse_view(*c.lse, true) : fcsa::DecodeLseOut{};
   const fcsa::DecodeLseOut* lse = c.lse != nullptr ? &lo : nullptr;
+  if (c.rotary != nullptr) {
+    const LaunchName& n = kRotaryPrefillName[form.fp8];
+    const fcsa::DecodeRotary ro = rotary_view(*c.rotary);
+    return timed(n.name, n.what, s, [&] { return fcsa::launch_prefill_rotary(c.a->p.dtype, c.a->p.dim_head, form, dp, ro, lse, s); });
+  }
   if (c.alibi == nullptr)
     return timed(plain.name, plain.what, s, [&] { return fcsa::launch_prefill(c.a->p.dtype, c.a->p.dim_head, form, dp, lse, s); });
   const LaunchName& n = kAlibiPrefillName[form.fp8];
@@ -1177,7 +1200,10 @@ int step_call(const DecodeCall& c) {
   const fcsa_kvcache_step& st = *c.step;
   const bool rows = p.batch > 0 && p.heads > 0 && c.seqs->total_q > 0;
   if (rows && c.lse != nullptr && c.lse->lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_step: lse: null pointer");
-  if (!has_chunk_kernel(p)) return decode_call({c.a, c.kv, c.seqs, c.qz, c.w, c.lse, nullptr, nullptr, c.alibi});
+  if (!has_chunk_kernel(p)) {
+    if (c.rotary != nullptr) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_rotary: no rotary kernels for this dtype / dim_head (f16 or bf16, 64 or 128)");
+    return decode_call({c.a, c.kv, c.seqs, c.qz, c.w, c.lse, nullptr, nullptr, c.alibi});
+  }
   const bool fp8 = c.qz != nullptr;
   const DecodeWindow win = decode_window(p, *kv, true, c.w);
   const DecodePlan d = step_plan(p, *kv, *c.seqs, st, win.reach());
@@ -1286,6 +1312,26 @@ int fcsa_forward_kvcache_alibi(const fcsa_forward_args* a, const fcsa_kvcache* k
   if ((reinterpret_cast<uintptr_t>(alibi->slopes) & 3) != 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_alibi: slopes not 4-byte aligned");
   if (alibi->reserved != 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_alibi: reserved (%lld) is 0", (long long)alibi->reserved);
   return step_call({a, kv, seqs, qz, w, lse, step, nullptr, alibi});
+}
+
+int fcsa_forward_kvcache_rotary(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_kvcache_quant* qz,
+                                const fcsa_window* w, const fcsa_kvcache_step* step, const fcsa_rotary* ro, const fcsa_lse_out* lse) {
+  if (a == nullptr || kv == nullptr || seqs == nullptr || step == nullptr || ro == nullptr)
+    return fail(FCSA_ERR_INVALID_ARG, "kvcache_rotary: null argument");
+  if (ro->cos == nullptr || ro->sin == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_rotary: cos / sin: null pointer");
+  if (((reinterpret_cast<uintptr_t>(ro->cos) | reinterpret_cast<uintptr_t>(ro->sin)) & 15) != 0 || ro->stride_row % 4 != 0)
+    return fail(FCSA_ERR_INVALID_ARG, "kvcache_rotary: cos / sin rows not 16-byte aligned (pointers, and stride_row %lld a multiple of 4)", (long long)ro->stride_row);
+  if (ro->reserved != 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_rotary: reserved (%lld) is 0", (long long)ro->reserved);
+  if (ro->rows <= 0 || ro->rows > INT32_MAX) return fail(FCSA_ERR_INVALID_ARG, "kvcache_rotary: rows (%lld) outside [1, 2^31)", (long long)ro->rows);
+  if (ro->interleaved != 0 && ro->interleaved != 1) return fail(FCSA_ERR_INVALID_ARG, "kvcache_rotary: interleaved (%d) is a flag (0 or 1)", ro->interleaved);
+  if (ro->rotary_dim != 64 && ro->rotary_dim != 128) return fail(FCSA_ERR_INVALID_ARG, "kvcache_rotary: rotary_dim %d is not supported (dim_head, or 64 at dim_head 128)", ro->rotary_dim);
+  if (a->p.dtype == FCSA_F32) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_rotary: float32 is not supported (f16 or bf16)");
+  if (a->p.dim_head != 64 && a->p.dim_head != 128) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_rotary: dim_head %d is not supported (64 or 128)", a->p.dim_head);
+  if (ro->rotary_dim > a->p.dim_head)
+    return fail(FCSA_ERR_INVALID_ARG, "kvcache_rotary: rotary_dim %d is not supported at dim_head %d (dim_head, or 64 at dim_head 128)", ro->rotary_dim, a->p.dim_head);
+  DecodeCall c{a, kv, seqs, qz, w, lse, step};
+  c.rotary = ro;
+  return step_call(c);
 }
 
 int fcsa_kvcache_compact(const fcsa_kvcache* kv, int32_t batch, int32_t kv_heads, int32_t dim_head, int32_t elem_bytes, const int32_t* accepted,

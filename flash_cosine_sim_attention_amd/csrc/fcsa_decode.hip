@@ -148,15 +148,20 @@ template <typename T, int D, bool FP8 = false> struct DecodeRegs {
 // ALIBI (alibi_decode_kernel, alibi_decode_fp8_kernel): a ragged or step form in the per-row-shift regime whose logits gain the linear
 // position bias -slope[b, h] * |last_key - key| (al.slopes; alibi_slope / alibi_logit of fcsa_decode_common.cuh): the slope is loaded once per
 // lane row, the float distance to the block once per block, and the bias joins the logit where the scale does, so the row max includes it.
-template <typename T, int D, bool DYN, bool GEN, bool WIN, bool FP8 = false, bool RAGGED = false, bool STEP = false, bool TREE = false, bool ALIBI = false>
+// ROTARY (rotary_decode_kernel, rotary_decode_fp8_kernel): the step form whose RAW query row is rotated by the table row of its position
+// last_key (ro; rotary_row of fcsa_decode_common.cuh) between the unpack and the l2norm, in float32 and in registers -- the rotated q is
+// rounded once, where qf is packed.  The tables are dead before the key loop, which is the step form's.
+template <typename T, int D, bool DYN, bool GEN, bool WIN, bool FP8 = false, bool RAGGED = false, bool STEP = false, bool TREE = false, bool ALIBI = false,
+          bool ROTARY = false>
 FCSA_DEV void decode_body(const std::conditional_t<STEP, DecodeStepParams, std::conditional_t<RAGGED, DecodeRaggedParams,
                                                    std::conditional_t<FP8, DecodeFp8Params, std::conditional_t<WIN, DecodeWinParams, DecodeParams>>>>& p,
-                          const DecodeTreeMask& tm = DecodeTreeMask{}, const DecodeAlibi& al = DecodeAlibi{}) {
+                          const DecodeTreeMask& tm = DecodeTreeMask{}, const DecodeAlibi& al = DecodeAlibi{}, const DecodeRotary& ro = DecodeRotary{}) {
   static_assert(!FP8 || Traits<T>::ES == 2, "an fp8 cache is read with 16-bit queries");
   static_assert(!RAGGED || WIN, "the ragged entry points carry the window fields");
   static_assert(!STEP || RAGGED, "a step is a ragged step");
   static_assert(!TREE || (RAGGED && !STEP), "a tree step is a ragged step");
   static_assert(!ALIBI || (RAGGED && DYN && !TREE), "a position bias comes with the ragged and step forms, in the per-row-shift regime");
+  static_assert(!ROTARY || (STEP && !ALIBI && Traits<T>::ES == 2 && (D == 64 || D == 128)), "the rotary embedding comes with the step form");
   typedef DecodeRegs<T, D, FP8> R;
   typedef DecodeLds<D, R::ES, GEN> LP;
   constexpr int ES = R::ES, UE = R::UE, NJ = R::NJ, CPR = R::CPR, VCH = R::VCH;
@@ -228,6 +233,7 @@ FCSA_DEV void decode_body(const std::conditional_t<STEP, DecodeStepParams, std::
       const u32x4 u = (row_ok && f < D) ? *reinterpret_cast<const u32x4*>(qrow + f * ES) : u32x4{0u, 0u, 0u, 0u};
       unpack<T>(u, xq[j]);
     }
+    if constexpr (ROTARY) rotary_row<NJ>(xq, ro, last_key, hi);
     if (p.l2norm) normalise(xq);
 #pragma unroll
     for (int j = 0; j < NJ; ++j) qf[j] = pack<T>(xq[j], p.l2norm ? p.c1 : 1.f);     // c1 * q^, one rounding (the dense kernels' qn)
@@ -405,6 +411,15 @@ __global__ __launch_bounds__(64) void alibi_decode_kernel(std::conditional_t<STE
 template <typename T, int D, bool GEN, bool STEP>
 __global__ __launch_bounds__(64) void alibi_decode_fp8_kernel(std::conditional_t<STEP, DecodeStepParams, DecodeRaggedParams> p, DecodeAlibi al) {
   decode_body<T, D, true, GEN, true, true, true, STEP, false, true>(p, DecodeTreeMask{}, al);
+}
+// an engine step with a rotary embedding (launch_decode_rotary): the step entry points' block, and the tables as a second argument
+template <typename T, int D, bool DYN>
+__global__ __launch_bounds__(64) FCSA_NO_PK_F32 void rotary_decode_kernel(DecodeStepParams p, DecodeRotary ro) {
+  decode_body<T, D, DYN, false, true, false, true, true, false, false, true>(p, DecodeTreeMask{}, DecodeAlibi{}, ro);
+}
+template <typename T, int D, bool DYN>
+__global__ __launch_bounds__(64) FCSA_NO_PK_F32 void rotary_decode_fp8_kernel(DecodeStepParams p, DecodeRotary ro) {
+  decode_body<T, D, DYN, false, true, true, true, true, false, false, true>(p, DecodeTreeMask{}, DecodeAlibi{}, ro);
 }
 // the decode side of an engine step (launch_decode with the step form): 16-bit types and D = 64 / 128, where every group width is reduced in registers
 template <typename T, int D, bool DYN>
@@ -622,6 +637,89 @@ __global__ __launch_bounds__(256) void kv_append_ragged_kernel(DecodeRaggedParam
   append_chunk<T, FP8>(p, b, kvh, pos, ch, p.kn.p + (int64_t)kvh * p.kn.sh + tok * p.kn.sn, p.vn.p + (int64_t)kvh * p.vn.sh + tok * p.vn.sn);
 }
 
+// kv_append_ragged_kernel with a rotary embedding (kv_append_rotary_kernel, kv_append_rotary_fp8_kernel; launch_kv_append_rotary): one launch
+// rotates K and appends K and V -- no rotated k_new exists in memory.  Where the row goes is append_pos, its address cache_base, unchanged;
+// the slot's position is the row's angle (rotary_at).  A written 16-byte chunk holds F features (8, or 16 codes of an fp8 cache); thread
+// `ch` of a (row, K/V head) copies (fp8: quantises) V chunk ch and owns K chunk ch TOGETHER with its rotary partner: a split pair's partner
+// is chunk ch + rotary_dim / (2 F) (the thread of the partner chunk leaves K alone), an interleaved chunk is self-contained, and a chunk at
+// or beyond rotary_dim is copied.  So every source byte is read once, every table value once per (row, chunk pair), and every cache byte
+// written once with a 16-byte store.  K is rotated in float32 and rounded once: to the type, or by quantise16's rule to the code.
+template <typename T, int F> FCSA_DEV void append_feats(const char* src, int f0, float (&x)[F]) {
+#pragma unroll
+  for (int q = 0; q < F / 8; ++q) {
+    float y[8];
+    unpack<T>(*reinterpret_cast<const u32x4*>(src + (f0 + 8 * q) * 2), y);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) x[8 * q + e] = y[e];
+  }
+}
+// F floats -> the 16 bytes of a cache chunk: 8 elements of T, or (FP8) 16 codes e4m3_rne(clamp(x / scale, -448, 448)), as quantise16
+template <typename T, bool FP8, int F> FCSA_DEV u32x4 append_bytes(const float (&x)[F], float scale) {
+  if constexpr (!FP8) {
+    return pack<T>(x, 1.f);
+  } else {
+    u32x4 out;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      float y[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float v = x[4 * w + e] / scale;
+        y[e] = v != v ? v : fminf(fmaxf(v, -448.f), 448.f);
+      }
+      int code = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false);
+      code = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], code, true);
+      out[w] = (uint32_t)code;
+    }
+    return out;
+  }
+}
+template <typename T, int D, bool FP8>
+__global__ __launch_bounds__(256) FCSA_NO_PK_F32 void kv_append_rotary_kernel(DecodeRaggedParams p, DecodeRotary ro) {
+  constexpr int F = FP8 ? 16 : 8;                 // features of a written chunk
+  constexpr int CPR = D / F;
+  const int64_t total = (int64_t)p.total_q * p.Hk * CPR;
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= total) return;
+  const int ch = (int)(t % CPR);
+  const int64_t rest = t / CPR;
+  const int kvh = (int)(rest % p.Hk);
+  const int64_t tok = rest / p.Hk;
+  const int b = ragged_seq_of(p.cu_q, p.B, p.total_q, tok);
+  const int64_t q0 = ragged_cu(p.cu_q[b], p.total_q), q1 = ragged_cu(p.cu_q[b + 1], p.total_q);
+  if (tok < q0 || tok >= q1) return;          // (a malformed table: the row belongs to no sequence)
+  int pos;
+  if (!append_pos(p, b, tok - q0, pos)) return;
+  const char* ksrc = p.kn.p + (int64_t)kvh * p.kn.sh + tok * p.kn.sn;
+  const char* vsrc = p.vn.p + (int64_t)kvh * p.vn.sh + tok * p.vn.sn;
+  char* kdst = cache_base(p, p.kc, b, kvh, pos);
+  char* vdst = cache_base(p, p.vc, b, kvh, pos);
+  float kscale = 1.f;
+  if constexpr (FP8) {
+    kscale = p.k_scale[(int64_t)b * p.ks_b + (int64_t)kvh * p.ks_h];
+    const u32x4* vs = reinterpret_cast<const u32x4*>(vsrc + ch * 32);
+    *reinterpret_cast<u32x4*>(vdst + ch * 16) = quantise16<T>(vs[0], vs[1], p.v_scale[(int64_t)b * p.vs_b + (int64_t)kvh * p.vs_h]);
+  } else {
+    *reinterpret_cast<u32x4*>(vdst + ch * 16) = *reinterpret_cast<const u32x4*>(vsrc + ch * 16);
+  }
+  const float* c = ro.cos + rotary_at(ro, pos);
+  const float* s = ro.sin + rotary_at(ro, pos);
+  const int f0 = ch * F, half = ro.rotary_dim / 2;
+  float x[F];
+  if (f0 >= ro.rotary_dim || ro.interleaved) {
+    append_feats<T, F>(ksrc, f0, x);
+    if (f0 < ro.rotary_dim) rotate_adjacent<F>(x, c + f0 / 2, s + f0 / 2);
+    *reinterpret_cast<u32x4*>(kdst + ch * 16) = append_bytes<T, FP8, F>(x, kscale);
+  } else if (f0 < half) {
+    float y[F];
+    append_feats<T, F>(ksrc, f0, x);
+    append_feats<T, F>(ksrc, f0 + half, y);
+    rotate_split<F>(x, y, c + f0, s + f0);
+    *reinterpret_cast<u32x4*>(kdst + ch * 16) = append_bytes<T, FP8, F>(x, kscale);
+    *reinterpret_cast<u32x4*>(kdst + (ch + half / F) * 16) = append_bytes<T, FP8, F>(y, kscale);
+  }
+}
+
 // ---- compaction of the accepted path of a tree step (fcsa_kvcache_compact) -----------------------------------------------------------
 // One workgroup owns ALL moves of a (sequence, K/V head) pair: move i takes the row at position start + accepted[b, i] to start + i, K and
 // V alike, start = clamp(cache_seqlens[b], 0, capacity).  Destination i of one move can be the source of another (accepted = [1, 2, 3, ...]
@@ -825,6 +923,53 @@ hipError_t launch_decode_alibi(int dtype, int D, DecodeForm f, const DecodeStepP
         else return hipErrorInvalidValue;
       }
       return go(std::false_type{});
+    }
+  });
+}
+
+// the rotary embedding's shapes: an engine step (the step kernels exist) whose rotary_dim is D, or 64 at D = 128
+static bool rotary_ok(DecodeForm f, int D, const DecodeRotary& r) {
+  return f.ragged && f.step && r.cos != nullptr && r.sin != nullptr && r.rows >= 1 && (r.rotary_dim == D || (r.rotary_dim == 64 && D == 128));
+}
+
+// launch_kv_append's ragged form on the entry points that rotate K by the tables: the same threads (one per 16 bytes written of a K row)
+hipError_t launch_kv_append_rotary(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeRotary& rotary, hipStream_t s) {
+  if (!rotary_ok(f, D, rotary)) return hipErrorInvalidValue;
+  return dispatch_decode(dtype, D, f, [&](auto td, auto fp8, auto ragged) -> hipError_t {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    constexpr bool FP8 = decltype(fp8)::value, RAGGED = decltype(ragged)::value;
+    if constexpr (!kStepKernels<T, DD, RAGGED>) {
+      return hipErrorInvalidValue;
+    } else {
+      const int64_t threads = (int64_t)p.total_q * p.Hk * (DD / (FP8 ? 16 : 8));
+      if (threads <= 0 || p.B <= 0) return hipSuccess;
+      return launch_part<kv_append_rotary_kernel<T, DD, FP8>, 0>(dim3((unsigned)blocks_of(threads)), dim3(256), s, p, rotary);
+    }
+  });
+}
+
+// launch_decode's step form on the entry points that take the tables: the same workgroups, block and LDS, in both exponent regimes
+hipError_t launch_decode_rotary(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeRotary& rotary, hipStream_t s) {
+  if (!rotary_ok(f, D, rotary)) return hipErrorInvalidValue;
+  return dispatch_decode(dtype, D, f, [&](auto td, auto fp8, auto ragged) -> hipError_t {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    constexpr bool FP8 = decltype(fp8)::value, RAGGED = decltype(ragged)::value;
+    if constexpr (!kStepKernels<T, DD, RAGGED>) {
+      return hipErrorInvalidValue;
+    } else {
+      if (p.l2norm && !decode_groups_fast(DD, p.groups, Unit<T>::UE)) return hipErrorInvalidValue;
+      const int64_t wgs = (int64_t)p.slots * p.Hk * p.splits;
+      if (wgs <= 0) return hipSuccess;
+      const dim3 grid((unsigned)wgs), block(64);
+      constexpr int LDS = DecodeLds<DD, 2, false>::BYTES;
+      auto go = [&](auto dyn) -> hipError_t {
+        constexpr bool DY = decltype(dyn)::value;
+        if constexpr (FP8) return launch_part<rotary_decode_fp8_kernel<T, DD, DY>, LDS>(grid, block, s, p, rotary);
+        else return launch_part<rotary_decode_kernel<T, DD, DY>, LDS>(grid, block, s, p, rotary);
+      };
+      return p.dyn ? go(std::true_type{}) : go(std::false_type{});
     }
   });
 }

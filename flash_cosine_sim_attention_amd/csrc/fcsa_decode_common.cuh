@@ -188,6 +188,87 @@ template <bool DYN, int FB> FCSA_DEV void softmax_step(const f32x4 (&s)[2], floa
 FCSA_DEV float alibi_slope(const DecodeAlibi& al, int b, int h) { return -(al.slopes[(int64_t)b * al.sb + (int64_t)h * al.sh] * 1.4426950408889634f); }
 FCSA_DEV float alibi_logit(float s, float smul, float nslope, float d0, int c) { return fmaf(nslope, fabsf(d0 - (float)c), s * smul); }
 
+// The rotary embedding of the ROTARY forms (fcsa_forward_kvcache_rotary), for both kernels and the rotating append.  The entry points that
+// rotate are compiled without packed float32 arithmetic (FCSA_NO_PK_F32): the rotation is plain v_mul_f32 / v_fma_f32.
+#if defined(FCSA_NO_PK_F32)
+#elif defined(__HIP_DEVICE_COMPILE__)
+#define FCSA_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define FCSA_NO_PK_F32
+#endif
+// rotary_at: the table row of cache position `pos`, clamped to [0, rows - 1] -- no position reads outside the tables.
+FCSA_DEV int64_t rotary_at(const DecodeRotary& ro, int pos) { return (int64_t)min(max(pos, 0), ro.rows - 1) * ro.stride; }
+// rotate_split: N pairs (a[e], b[e]) -> (a cos - b sin, a sin + b cos), angles c[e], s[e] (N a multiple of 4: 16-byte table loads).
+// rotate_adjacent: the N / 2 pairs (x[2 e], x[2 e + 1]) of N consecutive features, angles c[e], s[e].
+template <int N> FCSA_DEV void rotate_split(float (&a)[N], float (&b)[N], const float* c, const float* s) {
+#pragma unroll
+  for (int q = 0; q < N / 4; ++q) {
+    const f32x4 cv = *reinterpret_cast<const f32x4*>(c + 4 * q), sv = *reinterpret_cast<const f32x4*>(s + 4 * q);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float x = a[4 * q + e], y = b[4 * q + e];
+      a[4 * q + e] = x * cv[e] - y * sv[e];
+      b[4 * q + e] = x * sv[e] + y * cv[e];
+    }
+  }
+}
+template <int N> FCSA_DEV void rotate_adjacent(float (&x)[N], const float* c, const float* s) {
+#pragma unroll
+  for (int q = 0; q < N / 8; ++q) {
+    const f32x4 cv = *reinterpret_cast<const f32x4*>(c + 4 * q), sv = *reinterpret_cast<const f32x4*>(s + 4 * q);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float a = x[8 * q + 2 * e], b = x[8 * q + 2 * e + 1];
+      x[8 * q + 2 * e] = a * cv[e] - b * sv[e];
+      x[8 * q + 2 * e + 1] = a * sv[e] + b * cv[e];
+    }
+  }
+}
+// rotary_row: the lane's fragments of a RAW query row (unit j = features 32 j + 8 hi ... + 7) rotated by the table row of `pos`.  Both
+// partners of every pair are on the lane: interleaved pairs lie inside a unit (pairs 16 j + 4 hi ... + 3), and the partner of feature f of a
+// split pair, f + rotary_dim / 2, is the same element of unit j + rotary_dim / 64 (rotary_dim 64: units (0, 1); 128: (0, 2) and (1, 3)).  So
+// the rotation is register-only: no shuffle, no LDS.  Units at or beyond rotary_dim / 32 pass through.
+// One straight line of code for every layout -- the partner, the angle and the sign of each element are SELECTED by the (uniform) layout
+// flags, element e of unit j becoming x * cos + sign * partner * sin -- because a branch per layout that writes the row in place leaves the
+// row in scratch memory (the branches' stores are merged behind a pointer the register promotion cannot follow).  An interleaved unit loads
+// its four angles twice, a split one its eight: the second pointer never leaves the unit's own angles.
+template <int NJ, int J> FCSA_DEV void rotary_unit(const float (&x)[NJ][8], float (&r)[8], const DecodeRotary& ro, const float* c, const float* s, int hi) {
+  const bool il = ro.interleaved != 0, wide = ro.rotary_dim == 128;      // wide: split partners are two units apart
+  constexpr int JW = NJ == 4 ? (J ^ 2) : (J ^ 1);                        // the split partner unit when wide
+  const int lowj = wide ? (J & 1) : 0;                                   // the unit's place among the first halves of its pairs
+  const bool second = wide ? (J & 2) != 0 : (J & 1) != 0;                // split: the unit holds the second features of its pairs
+  const bool active = 32 * J < ro.rotary_dim;
+  const int at = !active ? 0 : il ? 16 * J + 4 * hi : 32 * lowj + 8 * hi;      // (a pass-through unit loads angles it does not use, in range)
+  const f32x4 c0 = *reinterpret_cast<const f32x4*>(c + at), s0 = *reinterpret_cast<const f32x4*>(s + at);
+  const f32x4 c1 = *reinterpret_cast<const f32x4*>(c + at + (il ? 0 : 4)), s1 = *reinterpret_cast<const f32x4*>(s + at + (il ? 0 : 4));
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float ce = il ? c0[e >> 1] : (e < 4 ? c0[e & 3] : c1[e & 3]);
+    const float se = il ? s0[e >> 1] : (e < 4 ? s0[e & 3] : s1[e & 3]);
+    const float partner = il ? x[J][e ^ 1] : wide ? x[JW][e] : x[J ^ 1][e];
+    const bool plus = il ? (e & 1) != 0 : second;                        // the pair's second feature: x sin + y cos
+    const float t = partner * se;
+    const float rot = x[J][e] * ce + (plus ? t : -t);
+    r[e] = active ? rot : x[J][e];
+  }
+}
+template <int NJ> FCSA_DEV void rotary_row(float (&x)[NJ][8], const DecodeRotary& ro, int pos, int hi) {
+  static_assert(NJ == 2 || NJ == 4, "dim_head 64 or 128");
+  const float* c = ro.cos + rotary_at(ro, pos);
+  const float* s = ro.sin + rotary_at(ro, pos);
+  float r[NJ][8];
+  rotary_unit<NJ, 0>(x, r[0], ro, c, s, hi);
+  rotary_unit<NJ, 1>(x, r[1], ro, c, s, hi);
+  if constexpr (NJ == 4) {
+    rotary_unit<NJ, 2>(x, r[2], ro, c, s, hi);
+    rotary_unit<NJ, 3>(x, r[3], ro, c, s, hi);
+  }
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) x[j][e] = r[j][e];
+}
+
 // O^T += V^T P~^T for the 32-key block of 16-bit V at rows row0 ... row0 + 31 of `v` in LDS (pitch kKvPitch<D, 2>): lane 4q + p of the
 // 16-lane group hi (x = lane & 15 = 4q + p) addresses key 4 hi + q, features 16 fb + 4p ... + 3; lane x receives feature 16 fb + x.  Every
 // transposed read feeds the NT row tiles pb[0 .. NT) -> acc[0 .. NT).

@@ -188,6 +188,16 @@ struct DecodeAlibi {
   const float* slopes;              // device
   int64_t sb, sh;
 };
+// The tables of a rotary position embedding (fcsa_forward_kvcache_rotary): a second kernel argument of the entry points that rotate
+// (kv_append_rotary[_fp8]_kernel, rotary_decode[_fp8]_kernel, rotary_prefill_kernel), as DecodeAlibi is of the ALiBi ones.  Row `pos` of cos /
+// sin holds the rotary_dim / 2 angles of cache position pos; the kernels clamp pos to [0, rows - 1].  Rows are 16-byte aligned (the
+// pointers, and `stride` -- ELEMENTS between rows -- a multiple of 4).  interleaved: pair f is (2 f, 2 f + 1), else (f, f + rotary_dim / 2).
+struct DecodeRotary {
+  const float* cos;                 // device [rows, rotary_dim / 2]
+  const float* sin;
+  int64_t stride;
+  int rows, rotary_dim, interleaved;
+};
 // An engine step (fcsa_forward_kvcache_step): the ragged step's block plus the routing threshold.  Sequence b takes the chunk kernel
 // (step_prefill_kernel) iff G * N_b >= chunk_rows and the decode kernels (step_decode[_fp8]_kernel, step_combine[_lse]_kernel) otherwise;
 // all of them evaluate that on the device from the clamped table (ragged_cu), so every row is written by exactly one of them.
@@ -230,6 +240,13 @@ hipError_t launch_prefill(int dtype, int D, DecodeForm f, const DecodeStepParams
 // where the step kernels exist (16-bit types, D = 64 / 128: one decode form per problem is compiled); hipErrorInvalidValue otherwise.  Append and combine are launch_kv_append / launch_decode_combine.
 hipError_t launch_decode_alibi(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeAlibi& alibi, hipStream_t s);
 hipError_t launch_prefill_alibi(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeAlibi& alibi, const DecodeLseOut* lse, hipStream_t s);
+// The three launches of an engine step with a rotary embedding (fcsa_forward_kvcache_rotary): the ragged append, launch_decode's step form
+// and launch_prefill's step form -- the same grids (the append: one thread per 16-byte chunk of a K row), LDS and blocks -- on the entry
+// points that take the tables.  f.ragged and f.step must be set, so they exist where the step kernels do (16-bit types, D = 64 / 128), and
+// rotary_dim is D, or 64 at D = 128; hipErrorInvalidValue otherwise.  The combine is launch_decode_combine.
+hipError_t launch_kv_append_rotary(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeRotary& rotary, hipStream_t s);
+hipError_t launch_decode_rotary(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeRotary& rotary, hipStream_t s);
+hipError_t launch_prefill_rotary(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeRotary& rotary, const DecodeLseOut* lse, hipStream_t s);
 
 // Merging attention states (fcsa_merge_states, csrc/fcsa_merge.hip): S states (o_s, lse_s) of the rows [n0, n1, n2] -> (o, lse).  o views
 // carry BYTE strides, lse views ELEMENT strides.

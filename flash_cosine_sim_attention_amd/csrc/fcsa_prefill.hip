@@ -112,11 +112,19 @@ template <typename T, int D, bool WIN, bool FP8> constexpr int kStepPrefillWaves
 // one wave per SIMD; the fp8 forms stay at 253, no scratch
 template <typename T, int D, bool FP8> constexpr int kAlibiPrefillWavesPerSimd = (!FP8 && D == 128) ? 1 : 2;
 
+// ... and of the forms with a rotary embedding (rotary_prefill_kernel; profiles/rotary_resources.txt): two everywhere.  Measured: 127 - 135
+// registers at D = 64 and 232 - 234 (fp8 cache) / 246 - 248 (16-bit cache) at D = 128, f16 and bf16 alike, with no spilled VGPR -- these
+// entry points are compiled without packed float32 arithmetic, which leaves the f16 D = 128 form below the 256 its step form exceeds
+template <typename T, int D, bool FP8> constexpr int kRotaryPrefillWavesPerSimd = 2;
+
 // ALIBI (alibi_prefill_kernel): the windowed step form in the per-row-shift regime whose logits gain the linear position bias of
 // decode_body<ALIBI> -- the same two functions (alibi_slope, alibi_logit), the slope once per lane row, the float distance once per block.
-template <typename T, int D, bool DYN, bool STEP = false, bool WIN = false, bool FP8 = false, bool ALIBI = false>
+// ROTARY (rotary_prefill_kernel): the windowed step form whose RAW query rows are rotated by the table row of their position (rotary_row, as
+// decode_body<ROTARY>) in the per-tile prologue, before the l2norm, for both row tiles of the wave.
+template <typename T, int D, bool DYN, bool STEP = false, bool WIN = false, bool FP8 = false, bool ALIBI = false, bool ROTARY = false>
 FCSA_DEV void prefill_body(const std::conditional_t<STEP, DecodeStepParams, DecodeRaggedParams>& p, const DecodeLseOut& lo,
-                           const DecodeAlibi& al = DecodeAlibi{}) {
+                           const DecodeAlibi& al = DecodeAlibi{}, const DecodeRotary& ro = DecodeRotary{}) {
+  static_assert(!ROTARY || (STEP && WIN && !ALIBI), "the rotary embedding comes with the windowed step form");
   static_assert(STEP || (!WIN && !FP8), "windows and fp8 caches come with the step entry points");
   static_assert(!ALIBI || (STEP && WIN && DYN), "a position bias comes with the windowed step form, in the per-row-shift regime");
   typedef PrefillLds<D> LP;
@@ -166,6 +174,7 @@ FCSA_DEV void prefill_body(const std::conditional_t<STEP, DecodeStepParams, Deco
       const u32x4 u = row_ok ? *reinterpret_cast<const u32x4*>(qrow + f * 2) : u32x4{0u, 0u, 0u, 0u};
       unpack<T>(u, xq[j]);
     }
+    if constexpr (ROTARY) rotary_row<NJ>(xq, ro, last_key[t], hi);
     if (p.l2norm) group_normalise<NJ, 8>(xq, gs, D);
 #pragma unroll
     for (int j = 0; j < NJ; ++j) qf[t][j] = pack<T>(xq[j], p.l2norm ? p.c1 : 1.f);     // c1 * q^, one rounding
@@ -304,6 +313,13 @@ __global__ __launch_bounds__(64 * kPrefillWaves, (kAlibiPrefillWavesPerSimd<T, D
   prefill_body<T, D, true, true, true, FP8, true>(p, lo, al);
 }
 
+// The chunk side of an engine step with a rotary embedding (launch_prefill_rotary): the windowed step form with the tables as a third argument.
+template <typename T, int D, bool DYN, bool FP8>
+__global__ __launch_bounds__(64 * kPrefillWaves, (kRotaryPrefillWavesPerSimd<T, D, FP8>)) FCSA_NO_PK_F32 void rotary_prefill_kernel(DecodeStepParams p, DecodeLseOut lo,
+                                                                                                                                  DecodeRotary ro) {
+  prefill_body<T, D, DYN, true, true, FP8, false, true>(p, lo, DecodeAlibi{}, ro);
+}
+
 }  // namespace
 
 // One 4-wave workgroup per (row-tile slot of 128 rows, K/V head): p.slots = fcsa::prefill_slots(total_q, B, G, kPrefillRows).  lse: nullptr,
@@ -346,6 +362,28 @@ hipError_t launch_prefill_alibi(int dtype, int D, DecodeForm f, const DecodeStep
     const DecodeLseOut lo = lse != nullptr ? *lse : DecodeLseOut{};
     if (f.fp8) return launch_part<alibi_prefill_kernel<T, DD, true>, LDS>(grid, block, s, p, lo, alibi);
     return launch_part<alibi_prefill_kernel<T, DD, false>, LDS>(grid, block, s, p, lo, alibi);
+  });
+}
+
+// launch_prefill's step form on the entry points that take the rotary tables: the same grid, block and LDS, in both exponent regimes; always
+// the windowed form, with the sides of the block (open ones where the call has no window)
+hipError_t launch_prefill_rotary(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeRotary& rotary, const DecodeLseOut* lse, hipStream_t s) {
+  if (!f.step || !f.ragged || rotary.cos == nullptr || rotary.sin == nullptr || rotary.rows < 1) return hipErrorInvalidValue;
+  if (rotary.rotary_dim != D && !(rotary.rotary_dim == 64 && D == 128)) return hipErrorInvalidValue;
+  return dispatch_chunk(dtype, D, [&](auto td) -> hipError_t {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    constexpr int LDS = PrefillLds<DD>::BYTES;
+    if (p.l2norm && !decode_groups_fast(DD, p.groups, 8)) return hipErrorInvalidValue;
+    if ((int64_t)p.slots * p.Hk <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((int64_t)p.slots * p.Hk)), block(64 * kPrefillWaves);
+    const DecodeLseOut lo = lse != nullptr ? *lse : DecodeLseOut{};
+    auto go = [&](auto dyn) -> hipError_t {
+      constexpr bool DY = decltype(dyn)::value;
+      if (f.fp8) return launch_part<rotary_prefill_kernel<T, DD, DY, true>, LDS>(grid, block, s, p, lo, rotary);
+      return launch_part<rotary_prefill_kernel<T, DD, DY, false>, LDS>(grid, block, s, p, lo, rotary);
+    };
+    return p.dyn ? go(std::true_type{}) : go(std::false_type{});
   });
 }
 

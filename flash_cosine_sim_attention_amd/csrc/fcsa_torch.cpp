@@ -78,7 +78,9 @@ namespace {
   /* the same bias in the training kernels, forward and backward */                       \
   X(forward_alibi, fcsa_forward_alibi, false)                                             \
   X(backward_alibi, fcsa_backward_alibi, false)                                           \
-  X(backward_alibi_ws, fcsa_backward_alibi_workspace_bytes, false)
+  X(backward_alibi_ws, fcsa_backward_alibi_workspace_bytes, false)                        \
+  /* a rotary position embedding inside the engine step */                                \
+  X(forward_kvcache_rotary, fcsa_forward_kvcache_rotary, false)
 
 struct Abi {
 #define X(member, symbol, required) decltype(&symbol) member = &symbol;
@@ -762,7 +764,7 @@ Tensor varlen_window_attention_autograd(const Tensor& q, const Tensor& k, const 
 //
 // One description of a call, CacheCall: every op function fills the members it has and hands it to kvcache_call, which runs the checks
 // (cache_checks), fills the library's structs (fill_lib_call) and dispatches through the one table of entry points (kEntries).
-enum class Route { Plain, Prefill, Step, Tree, Alibi };
+enum class Route { Plain, Prefill, Step, Tree, Alibi, Rotary };
 
 struct CacheCall {
   // what every op has
@@ -775,8 +777,9 @@ struct CacheCall {
   const Tensor* cu_q = nullptr; int64_t max_seqlen_q = 0; // a ragged step: packed q [total_q, H, D], with the bound on a sequence's rows
   bool lse = false;                                       // the rows' log-sum-exp as a second result
   Route route = Route::Plain;
-  fcsa_kvcache_step step{};                               // Step, Alibi: the routing fields
-  const Tensor* extra = nullptr;                          // Tree: tree_mask; Alibi: alibi_slopes
+  fcsa_kvcache_step step{};                               // Step, Alibi, Rotary: the routing fields
+  const Tensor* extra = nullptr;                          // Tree: tree_mask; Alibi: alibi_slopes; Rotary: rotary_cos
+  const Tensor* rotary_sin = nullptr; bool rotary_interleaved = false;      // Rotary
   bool ragged() const { return cu_q != nullptr; }
   bool fp8() const { return k_scale != nullptr; }
 };
@@ -830,7 +833,7 @@ Geometry cache_geometry(const Tensor& k_cache, const optional<Tensor>& block_tab
 
 // What the checks of a call return: the canonical tensors, kept alive until the call has been issued, and the sizes read off them.
 struct CacheKeep {
-  Tensor q, cu, words, slopes, kn, vn, sl;
+  Tensor q, cu, words, slopes, rcos, rsin, kn, vn, sl;
   Geometry g;
   int64_t B = 0, H = 0, N = 0, D = 0, Hk = 0, new_len = 0;      // ragged: N is the number of packed rows
 };
@@ -885,6 +888,24 @@ CacheKeep cache_checks(const CacheCall& c) {
     TORCH_CHECK_VALUE((alibi.dim() == 1 && alibi.size(0) == q.size(1)) || (alibi.dim() == 2 && alibi.size(0) == seqs_n && alibi.size(1) == q.size(1)),
                       "alibi_slopes must be [heads] (", q.size(1), ") or [sequences, heads] (", seqs_n, ", ", q.size(1), "), got ", alibi.sizes());
     k.slopes = alibi;      // any strides: the kernels take element strides, and a view keeps in-place updates visible to a captured graph
+  }
+  if (c.route == Route::Rotary) {
+    // float32 [rows, rotary_dim / 2] on q's device, the last dim contiguous and rows 16-byte aligned (made so otherwise); never read on the host
+    const Tensor &rc = *c.extra, &rs = *c.rotary_sin;
+    TORCH_CHECK_TYPE(rc.scalar_type() == at::kFloat && rs.scalar_type() == at::kFloat, "rotary_cos / rotary_sin must be float32, got ",
+                     rc.scalar_type(), " and ", rs.scalar_type());
+    same_dev("rotary_cos", rc);
+    same_dev("rotary_sin", rs);
+    TORCH_CHECK_VALUE(rc.dim() == 2 && rc.sizes() == rs.sizes() && rc.size(0) >= 1, "rotary_cos / rotary_sin must be [rows, rotary_dim / 2] with rows >= 1 and the same shape, got ",
+                      rc.sizes(), " and ", rs.sizes());
+    TORCH_CHECK_TYPE(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16, "the rotary embedding takes float16 or bfloat16 queries, got ",
+                     q.scalar_type());
+    const int64_t D = q.size(-1), rd = 2 * rc.size(1);
+    TORCH_CHECK_VALUE(D == 64 || D == 128, "the rotary embedding takes head dimensions 64 and 128, got ", D);
+    TORCH_CHECK_VALUE(rd == D || (rd == 64 && D == 128), "rotary_dim (", rd, ") must be dim_head (", D, "), or 64 at dim_head 128");
+    k.rcos = prep(rc);
+    k.rsin = prep(rs);
+    if (k.rcos.stride(0) != k.rsin.stride(0)) { k.rcos = k.rcos.contiguous(); k.rsin = k.rsin.contiguous(); }      // the library takes one row stride
   }
   const int64_t B = k.B = ragged ? k.cu.numel() - 1 : q.size(0), H = k.H = q.size(1), N = k.N = ragged ? q.size(0) : q.size(2);
   const int64_t D = k.D = q.size(-1), Hk = k.Hk = k_cache.size(1);
@@ -941,7 +962,7 @@ CacheKeep cache_checks(const CacheCall& c) {
 // What one call hands to the library: the structs of include/fcsa.h, filled from the call and its canonical tensors.
 struct LibCall {
   fcsa_forward_args a; fcsa_kvcache kv; fcsa_varlen seqs; fcsa_lse_out lo;
-  fcsa_kvcache_quant qz; fcsa_tree_mask tree; fcsa_alibi alibi;
+  fcsa_kvcache_quant qz; fcsa_tree_mask tree; fcsa_alibi alibi; fcsa_rotary rotary;
   const fcsa_window* win; const fcsa_kvcache_step* step;
   bool ragged, fp8;
   const fcsa_kvcache_quant* quant() const { return fp8 ? &qz : nullptr; }
@@ -952,7 +973,7 @@ void fill_lib_call(LibCall& l, const CacheCall& c, const CacheKeep& k, const Ten
   const Layout ql = c.ragged() ? kPacked : kDense;      // of q, o, k_new, v_new and the lse
   std::memset(&l, 0, sizeof(l));
   l.ragged = c.ragged(); l.fp8 = c.fp8(); l.win = c.win;
-  l.step = c.route == Route::Step || c.route == Route::Alibi ? &c.step : nullptr;
+  l.step = c.route == Route::Step || c.route == Route::Alibi || c.route == Route::Rotary ? &c.step : nullptr;
   fcsa_problem& p = l.a.p;
   p.dtype = dtype_code(c.q.scalar_type());
   p.batch = (int32_t)k.B; p.heads = (int32_t)k.H; p.kv_heads = (int32_t)k.Hk;
@@ -978,6 +999,10 @@ void fill_lib_call(LibCall& l, const CacheCall& c, const CacheKeep& k, const Ten
     l.alibi.stride_b = k.slopes.dim() == 2 ? k.slopes.stride(0) : 0;
     l.alibi.stride_h = k.slopes.stride(-1);
   }
+  if (k.rcos.defined()) {
+    l.rotary = {k.rcos.data_ptr<float>(), k.rsin.data_ptr<float>(), k.rcos.size(0), k.rcos.stride(0), (int32_t)(2 * k.rcos.size(1)),
+                c.rotary_interleaved ? 1 : 0, 0};
+  }
 }
 
 // The entry points of the family, one row each: the symbol (as errors name it), who asks for it when the loaded library lacks it, whether
@@ -988,7 +1013,7 @@ struct EntryPoint {
   size_t (*workspace)(const LibCall&);      // null: that of the call without the lse
   int (*run)(const LibCall&);
 };
-enum Entry { kKvcache, kWindow, kQuant, kVarlen, kLse, kPrefill, kStep, kTree, kAlibi };
+enum Entry { kKvcache, kWindow, kQuant, kVarlen, kLse, kPrefill, kStep, kTree, kAlibi, kRotary };
 const EntryPoint kEntries[] = {
     /* kKvcache */ {"fcsa_forward_kvcache", "flash_cosine_sim_attention_with_kvcache",
                     [] { return g_abi.forward_kvcache != nullptr && g_abi.forward_kvcache_ws != nullptr; },
@@ -1021,12 +1046,15 @@ const EntryPoint kEntries[] = {
     /* kAlibi: the step's workspace */ {"fcsa_forward_kvcache_alibi", "alibi_slopes", [] { return g_abi.forward_kvcache_alibi != nullptr; },
      [](const LibCall& l) { return g_abi.forward_kvcache_step_ws(&l.a.p, &l.kv, &l.seqs, l.quant(), l.win, l.step); },
      [](const LibCall& l) { return g_abi.forward_kvcache_alibi(&l.a, &l.kv, &l.seqs, l.quant(), l.win, l.step, &l.alibi, &l.lo); }},
+    /* kRotary: the step's workspace */ {"fcsa_forward_kvcache_rotary", "rotary_cos / rotary_sin", [] { return g_abi.forward_kvcache_rotary != nullptr; },
+     [](const LibCall& l) { return g_abi.forward_kvcache_step_ws(&l.a.p, &l.kv, &l.seqs, l.quant(), l.win, l.step); },
+     [](const LibCall& l) { return g_abi.forward_kvcache_rotary(&l.a, &l.kv, &l.seqs, l.quant(), l.win, l.step, &l.rotary, &l.lo); }},
 };
 
 // the entry point of a Plain call without the lse: by the ragged / fp8 / window facts
 Entry plain_entry(const CacheCall& c) { return c.ragged() ? kVarlen : c.fp8() ? kQuant : c.win != nullptr ? kWindow : kKvcache; }
-constexpr Entry kOfRoute[] = {kKvcache /* Plain: by the facts instead */, kPrefill, kStep, kTree, kAlibi};      // in Route's order
-static_assert(sizeof(kEntries) / sizeof(kEntries[0]) == kAlibi + 1 && sizeof(kOfRoute) / sizeof(kOfRoute[0]) == (int)Route::Alibi + 1,
+constexpr Entry kOfRoute[] = {kKvcache /* Plain: by the facts instead */, kPrefill, kStep, kTree, kAlibi, kRotary};      // in Route's order
+static_assert(sizeof(kEntries) / sizeof(kEntries[0]) == kRotary + 1 && sizeof(kOfRoute) / sizeof(kOfRoute[0]) == (int)Route::Rotary + 1,
               "kEntries has one row per Entry, in its order, and kOfRoute one entry per Route");
 Entry entry_of(const CacheCall& c) { return c.route != Route::Plain ? kOfRoute[(int)c.route] : c.lse ? kLse : plain_entry(c); }
 // a call needs its own entry point and those of the calls it is built on
@@ -1158,6 +1186,24 @@ std::tuple<Tensor, Tensor> kvcache_alibi_forward(const Tensor& q, const Tensor& 
                                                  int64_t right, int64_t chunk_rows, int64_t max_decode_tokens, bool no_decode, bool no_chunk) {
   return step_call({q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups}, &alibi_slopes,
                    cu_seqlens_q, k_scale, v_scale, max_seqlen_q, left, right, chunk_rows, max_decode_tokens, no_decode, no_chunk);
+}
+
+// An engine step with a rotary embedding of q and k_new (kvcache_rotary_forward): the step's front end with the two tables (float32
+// [rows, rotary_dim / 2] on q's device, never read on the host), through fcsa_forward_kvcache_rotary.
+std::tuple<Tensor, Tensor> kvcache_rotary_forward(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& cu_seqlens_q,
+                                                  const Tensor& rotary_cos, const Tensor& rotary_sin, bool rotary_interleaved,
+                                                  const optional<Tensor>& k_new, const optional<Tensor>& v_new,
+                                                  const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table,
+                                                  const optional<Tensor>& k_scale, const optional<Tensor>& v_scale, int64_t max_seqlen_q,
+                                                  int64_t max_seqlen_k, double scale, bool causal, bool l2norm_qk, int64_t groups, int64_t left,
+                                                  int64_t right, int64_t chunk_rows, int64_t max_decode_tokens, bool no_decode, bool no_chunk) {
+  CacheCall c{q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups};
+  set_scales(c, k_scale, v_scale);
+  c.step = step_fields(chunk_rows, max_decode_tokens, no_decode, no_chunk);
+  const OptWin win(left, right);
+  c.win = win.ptr(); c.cu_q = &cu_seqlens_q; c.max_seqlen_q = max_seqlen_q; c.lse = true;
+  c.route = Route::Rotary; c.extra = &rotary_cos; c.rotary_sin = &rotary_sin; c.rotary_interleaved = rotary_interleaved;
+  return kvcache_call(c);
 }
 
 // A tree step: kvcache_lse_forward's ragged step without a window and without `causal`, the visibility of the step's own tokens given per
@@ -1673,6 +1719,15 @@ TORCH_LIBRARY(fcsa_alibi, m) {
         "bool no_decode, bool no_chunk) -> (Tensor, Tensor)");
 }
 TORCH_LIBRARY_IMPL(fcsa_alibi, CUDA, m) { m.impl("kvcache_alibi_forward", &kvcache_alibi_forward); }
+
+// the engine step with a rotary embedding of q and k_new, likewise.  Forward only: no Autograd kernel.
+TORCH_LIBRARY(fcsa_rotary, m) {
+  m.def("kvcache_rotary_forward(Tensor q, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor cu_seqlens_q, Tensor rotary_cos, Tensor rotary_sin, "
+        "bool rotary_interleaved, Tensor? k_new, Tensor? v_new, Tensor? cache_seqlens, Tensor? block_table, Tensor? k_scale, Tensor? v_scale, "
+        "int max_seqlen_q, int max_seqlen_k, float scale, bool causal, bool l2norm_qk, int groups, int window_left, int window_right, "
+        "int chunk_rows, int max_decode_tokens, bool no_decode, bool no_chunk) -> (Tensor, Tensor)");
+}
+TORCH_LIBRARY_IMPL(fcsa_rotary, CUDA, m) { m.impl("kvcache_rotary_forward", &kvcache_rotary_forward); }
 
 // Attention states for training, in a namespace of their own (the op set of `fcsa` is pinned): the attention op with the rows'
 // log-sum-exp as a second differentiable result -- dense, local (window sides other than (-1, -1)) or packed (cu_seqlens given) -- and

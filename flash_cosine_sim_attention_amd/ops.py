@@ -821,6 +821,88 @@ def flash_cosine_sim_attention_alibi_with_kvcache(q, k_cache, v_cache, cu_seqlen
                         cpu_kw=dict(scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, alibi_slopes=alibi_slopes.detach()))
 
 
+def flash_cosine_sim_attention_rotary_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new=None, v_new=None, cache_seqlens=None,
+                                                   block_table=None, max_seqlen_q=None, max_seqlen_k=None, scale=8, groups=1, causal=False,
+                                                   l2norm_qk=True, k_scale=None, v_scale=None, return_lse=False, window_size=(-1, -1),
+                                                   chunk_rows=None, max_decode_tokens=None, rotary_cos=None, rotary_sin=None,
+                                                   rotary_interleaved=False):
+    """A rotary position embedding (RoPE) inside the engine step: `flash_cosine_sim_attention_step_with_kvcache` with three more, last
+    keywords, the rotary_cos / rotary_sin / rotary_interleaved of flash-attn's `flash_attn_with_kvcache`.  The arguments are that call's, in
+    its order; with both tables None this IS that call, bit for bit, launching exactly what it launches.  One table without the other is an
+    error.
+
+    The step call knows every token's position, so q and k_new are rotated where they are read, each sequence at its own cache position:
+    no gather of table rows for a ragged batch, no elementwise launches, no rounded copy of q and k_new.
+    rotary_cos, rotary_sin: float32 [rows, rotary_dim / 2], the same shape, the last dim contiguous, any row stride.  rotary_dim is
+    dim_head, or 64 at dim_head 128; features at or beyond it pass through unchanged.  With pos_i = L_b - N_b + i -- the position of query
+    i of sequence b, and the cache slot k_new row i is appended at -- q row i and k_new row i of every head are rotated by table row pos_i:
+    each pair (x, y) becomes (x cos - y sin, x sin + y cos).  rotary_interleaved=False (GPT-NeoX): pair f is the features
+    (f, f + rotary_dim / 2); True (GPT-J): (2 f, 2 f + 1).  v_new is appended as before; k_new rows dropped at the capacity are neither
+    rotated nor written; without an append (k_new=None) q is still rotated at pos_i.  Scaled or YaRN embeddings are other table contents.
+    One difference from flash-attn: every query takes its OWN position whether or not the call is causal (flash-attn puts all queries of a
+    non-causal, un-windowed call at cache_seqlens).
+    A host table is checked (finite, shapes) and moved to q's device without blocking; a device table is trusted and never read on the
+    host, so the call does not synchronise and can be captured in a graph.  A position at or beyond `rows` never reads outside the tables:
+    the kernels clamp it to [0, rows - 1]; host cache_seqlens that reach beyond the tables are refused.
+    Order and rounding: the raw q row is rotated in float32, then l2-normalised (rotation does not commute with the grouped l2norm of
+    groups > 1), scaled and rounded once -- the rotated q never exists in the 16-bit type.  k_new is rotated in float32 and rounded once to
+    the cache type (float8_e4m3fn caches: e4m3_rne(clamp(r / k_scale, -448, 448))); the cache holds rotated raw keys, normalised as they are
+    read.  The exponent regime is the step call's: a rotation preserves the norm of a row, so with l2norm_qk=True no bound of the static
+    regime changes.  With l2norm_qk=False the logits are scale * q . k of the rotated rows, bounded by scale * |q| |k| as before (a rotation
+    changes neither norm), so the step call's choice of regime holds as well; a rounded rotated key can exceed its source's largest element
+    by a factor of up to sqrt(2), which matters only to an fp8 k_scale chosen with no headroom.
+    Supported: float16 / bfloat16 q, dim_head 64 or 128, 16-bit and float8_e4m3fn caches, paged and strided caches, causal, window_size,
+    return_lse, groups, any Hk, chunk_rows / max_decode_tokens routing, N_b = 0.  float32, other head dims or rotary dims and tables that
+    are not float32 are refused.  Not taken by the tree, shared-prefix, prefill and ALiBi calls.  CPU tensors take the forward-only path
+    of `cpu.py` (host tables).  Forward only."""
+    fn = "flash_cosine_sim_attention_rotary_with_kvcache"
+    if rotary_cos is None and rotary_sin is None:
+        return flash_cosine_sim_attention_step_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q,
+                                                            max_seqlen_k, scale, groups, causal, l2norm_qk, k_scale, v_scale, return_lse, window_size,
+                                                            chunk_rows, max_decode_tokens)
+    if rotary_cos is None or rotary_sin is None:
+        raise ValueError("rotary_cos and rotary_sin must be given together")
+    window, chunk_rows, max_decode_tokens = _step_arguments(return_lse, window_size, chunk_rows, max_decode_tokens)
+    for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError(f"{name} must be a float32 tensor [rows, rotary_dim / 2], got {getattr(t, 'dtype', type(t).__name__)}")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError(f"{fn} takes float16 or bfloat16 q, got {q.dtype}")
+    if rotary_cos.dim() != 2 or rotary_cos.shape != rotary_sin.shape or rotary_cos.shape[0] < 1:
+        raise ValueError(f"rotary_cos / rotary_sin must be [rows, rotary_dim / 2] with the same shape and rows >= 1, got {tuple(rotary_cos.shape)} and "
+                         f"{tuple(rotary_sin.shape)}")
+    rows, rotary_dim = rotary_cos.shape[0], 2 * rotary_cos.shape[1]
+    if q.dim() == 3:
+        D = q.shape[-1]
+        if D not in (64, 128):
+            raise ValueError(f"{fn} takes head dimensions 64 and 128, got {D}")
+        if rotary_dim != D and not (rotary_dim == 64 and D == 128):
+            raise ValueError(f"rotary_dim ({rotary_dim}) must be dim_head ({D}), or 64 at dim_head 128")
+    tables = []
+    for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+        if t.device.type == "cpu":
+            if not bool(torch.isfinite(t).all()):
+                raise ValueError(f"{name} must be finite")
+        elif t.device != q.device:
+            raise ValueError(f"{name} is on {t.device} but q is on {q.device}")
+        tables.append(t.detach() if t.stride(-1) == 1 else t.detach().contiguous())
+    # host lengths against the tables' rows: the last position any sequence of the step touches
+    counts, lens, appended = _host_view(q, cu_seqlens_q, k_new, cache_seqlens)
+    if lens is not None and counts is not None:
+        for b, (n0, n, a) in enumerate(zip(lens, counts, appended)):
+            if n > 0 and n0 + a > rows:
+                raise ValueError(f"sequence {b}: position {n0 + a - 1} is beyond the {rows} rows of rotary_cos / rotary_sin")
+    op = lambda s: torch.ops.fcsa_rotary.kvcache_rotary_forward(q, s.k_cache, s.v_cache, s.cu_q, tables[0].to(q.device, non_blocking=True),
+                                                                tables[1].to(q.device, non_blocking=True), bool(rotary_interleaved), k_new, v_new,
+                                                                s.cache_seqlens, s.block_table, s.k_scale, s.v_scale, s.max_q, s.max_k,
+                                                                float(scale), bool(causal), bool(l2norm_qk), int(groups), window[0], window[1],
+                                                                *s.routing)
+    return _packed_call(fn, q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q, max_seqlen_k, k_scale,
+                        v_scale, return_lse=return_lse, window=window, op=op, routing=(chunk_rows, max_decode_tokens),
+                        cpu_kw=dict(scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk,
+                                    rotary=(tables[0], tables[1], bool(rotary_interleaved))))
+
+
 def flash_cosine_sim_attention_tree_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new=None, v_new=None, cache_seqlens=None,
                                                  block_table=None, max_seqlen_q=None, max_seqlen_k=None, scale=8, groups=1, causal=False,
                                                  l2norm_qk=True, k_scale=None, v_scale=None, return_lse=False, window_size=(-1, -1),

@@ -478,6 +478,42 @@ int    fcsa_forward_kvcache_alibi(const fcsa_forward_args* args, const fcsa_kvca
                                   const fcsa_kvcache_quant* quant, const fcsa_window* window, const fcsa_kvcache_step* step,
                                   const fcsa_alibi* alibi, const fcsa_lse_out* lse_out);
 
+/* A rotary position embedding (RoPE) inside the engine step: fcsa_forward_kvcache_step with one more argument, the cos / sin tables, as
+ * flash-attn's flash_attn_with_kvcache takes rotary_cos / rotary_sin / rotary_interleaved.  The step call already knows every token's
+ * position, so q and k_new are rotated where they are read: no gather of table rows, no elementwise launches, no rounded copy.
+ * args, cache, seqs, quant, window, step and lse_out are read exactly as fcsa_forward_kvcache_step reads them, and its checks, routing,
+ * split plan, exponent regime and workspace -- fcsa_forward_kvcache_step_workspace_bytes() on the same arguments -- apply (additive: no
+ * existing struct changes and FCSA_ABI_VERSION stays 4).
+ *   rotary->cos/sin : device float32 [rows, rotary_dim / 2], 16-byte aligned; row r starts at element r * stride_row (a multiple of 4).
+ *                     Device data, never read by the host: the call does not synchronise and can be captured in a graph.
+ *   rotary_dim      : dim_head, or 64 at dim_head 128; features at or beyond it pass through unchanged.
+ *   interleaved     : 0: pair f is the features (f, f + rotary_dim / 2) (GPT-NeoX); 1: (2 f, 2 f + 1) (GPT-J).
+ * Meaning: with pos_i = L_b - N_b + i (the position of query i of sequence b, and the slot k_new row i is appended at), q row i and k_new
+ * row i of every head are rotated by table row pos_i: (x, y) -> (x cos - y sin, x sin + y cos) per pair.  Every query takes its OWN
+ * position whether or not the call is causal (flash-attn puts all queries of a non-causal, un-windowed call at cache_seqlens).  A
+ * position outside [0, rows) uses row 0 or rows - 1: the kernels clamp, nothing is read outside the tables.  v_new is appended as in the
+ * step call; k_new rows dropped at the capacity are neither rotated nor written; without an append q is still rotated.
+ * Order and rounding: the RAW q row is rotated in float32, then l2-normalised (rotation does not commute with a grouped l2norm), scaled
+ * and rounded once to the type; k_new is rotated in float32 and rounded once to the cache type (fp8: e4m3_rne(clamp(r / k_scale, -448,
+ * 448))).  The cache holds rotated raw keys, normalised as they are read.
+ * FCSA_F32 and dim_head other than 64 and 128: FCSA_ERR_UNSUPPORTED.  rotary / cos / sin NULL, tables or stride_row misaligned,
+ * reserved != 0, rows <= 0 or above 2^31 - 1, rotary_dim other than the above, interleaved other than 0 / 1: FCSA_ERR_INVALID_ARG.  All
+ * before any launch.
+ * Launches: "kv_append_rotary[_fp8]" (when appending), "rotary_decode[_fp8]" (skipped under no_decode), the step call's combine
+ * ("step_combine[_lse][_fp8]"), "rotary_prefill[_fp8]" (skipped under no_chunk). */
+typedef struct fcsa_rotary {
+  const float* cos;                   /* device */
+  const float* sin;                   /* device */
+  int64_t      rows;
+  int64_t      stride_row;            /* elements */
+  int32_t      rotary_dim;
+  int32_t      interleaved;
+  int64_t      reserved;              /* 0 */
+} fcsa_rotary;
+int    fcsa_forward_kvcache_rotary(const fcsa_forward_args* args, const fcsa_kvcache* cache, const fcsa_varlen* seqs,
+                                   const fcsa_kvcache_quant* quant, const fcsa_window* window, const fcsa_kvcache_step* step,
+                                   const fcsa_rotary* rotary, const fcsa_lse_out* lse_out);
+
 /* The same linear position bias in the training kernels, forward and backward: fcsa_forward_window / fcsa_backward_window with one more
  * argument, the slopes (additive: no existing struct changes and FCSA_ABI_VERSION stays 4).  A model trained through these entries is
  * served unchanged by fcsa_forward_kvcache_alibi: the definition is the same.
