@@ -93,6 +93,8 @@ STEP_CHUNK_ROWS = _MACROS["FCSA_STEP_CHUNK_ROWS"]
 TreeMask = _STRUCTS["fcsa_tree_mask"]
 Alibi = _STRUCTS["fcsa_alibi"]
 Rotary = _STRUCTS["fcsa_rotary"]
+KvCacheMx = _STRUCTS["fcsa_kvcache_mx"]
+FCSA_CACHE_MXFP4 = _MACROS["FCSA_CACHE_MXFP4"]
 
 
 EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fcsa_forward_workspace_bytes", "fcsa_forward_needs_qn",
@@ -106,7 +108,7 @@ EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fc
            "fcsa_forward_kvcache_step", "fcsa_forward_kvcache_step_workspace_bytes",
            "fcsa_forward_kvcache_tree", "fcsa_kvcache_compact", "fcsa_forward_kvcache_alibi",
            "fcsa_forward_alibi", "fcsa_backward_alibi", "fcsa_forward_alibi_workspace_bytes", "fcsa_backward_alibi_workspace_bytes",
-           "fcsa_forward_kvcache_rotary")
+           "fcsa_forward_kvcache_rotary", "fcsa_forward_kvcache_mx", "fcsa_forward_kvcache_mx_workspace_bytes")
 
 _lib = None
 
@@ -231,6 +233,13 @@ def load():
         lib.fcsa_forward_kvcache_rotary.argtypes = [C.POINTER(ForwardArgs), C.POINTER(KvCache), C.POINTER(Varlen), C.POINTER(KvCacheQuant),
                                                     C.POINTER(Window), C.POINTER(KvCacheStep), C.POINTER(Rotary), C.POINTER(LseOut)]
         lib.fcsa_forward_kvcache_rotary.restype = C.c_int
+    if hasattr(lib, "fcsa_forward_kvcache_mx"):      # (likewise: an FCSA_LIB build from before the MXFP4 cache)
+        lib.fcsa_forward_kvcache_mx.argtypes = [C.POINTER(ForwardArgs), C.POINTER(KvCache), C.POINTER(KvCacheMx), C.POINTER(Varlen),
+                                                C.POINTER(Window), C.POINTER(LseOut)]
+        lib.fcsa_forward_kvcache_mx.restype = C.c_int
+        lib.fcsa_forward_kvcache_mx_workspace_bytes.argtypes = [C.POINTER(Problem), C.POINTER(KvCache),
+                                                                C.POINTER(KvCacheMx), C.POINTER(Varlen), C.POINTER(Window)]
+        lib.fcsa_forward_kvcache_mx_workspace_bytes.restype = C.c_size_t
     if hasattr(lib, "fcsa_forward_kvcache_tree"):      # (likewise: an FCSA_LIB build from before tree attention)
         lib.fcsa_forward_kvcache_tree.argtypes = [C.POINTER(ForwardArgs), C.POINTER(KvCache), C.POINTER(Varlen), C.POINTER(KvCacheQuant),
                                                   C.POINTER(TreeMask), C.POINTER(LseOut)]

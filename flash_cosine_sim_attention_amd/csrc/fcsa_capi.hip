@@ -823,6 +823,7 @@ struct DecodeCall {
   const fcsa_tree_mask* tree = nullptr;         // a tree step (fcsa_forward_kvcache_tree): the visibility words of a ragged step, or NULL
   const fcsa_alibi* alibi = nullptr;            // a linear position bias (fcsa_forward_kvcache_alibi) on a ragged or engine step, or NULL
   const fcsa_rotary* rotary = nullptr;          // a rotary embedding (fcsa_forward_kvcache_rotary) of q and k_new on an engine step, or NULL
+  const fcsa_kvcache_mx* mx = nullptr;          // an MXFP4 cache (fcsa_forward_kvcache_mx) on an equal-N call or a ragged step, or NULL
 };
 
 // The window of a decode call as the kernels take it.  A rectangular call is normalised (fcsa::win_normalise): a window that hides nothing
@@ -876,9 +877,9 @@ DecodePlan decode_plan(const fcsa_problem& p, const fcsa_kvcache& kv, const fcsa
   d.total = rows == 0 ? 0 : d.ws_ml + align_up(rows * d.splits * 8, 256);
   return d;
 }
-size_t decode_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_window* w) {
+size_t decode_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_window* w, bool mx = false) {
   if (p == nullptr || kv == nullptr) return 0;
-  return decode_plan(*p, *kv, seqs, decode_window(*p, *kv, seqs != nullptr, w).reach()).total;
+  return decode_plan(*p, *kv, seqs, decode_window(*p, *kv, seqs != nullptr || mx, w).reach()).total;
 }
 
 // the paged-table fields of a cache (capacity already known to be >= 0), for every call that takes one; who: the message prefix
@@ -935,6 +936,35 @@ int check_quant(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_k
   return check_kvcache(a, kv, 1);
 }
 
+// an MXFP4 cache: what the call refuses as unsupported before anything else (and answers a workspace query with 0 for) ...
+int mx_supported(const fcsa_problem& p, const fcsa_kvcache_mx& mx) {
+  if (mx.format != FCSA_CACHE_MXFP4)
+    return fail(FCSA_ERR_UNSUPPORTED, "kvcache_mx: format %d not supported (expected FCSA_CACHE_MXFP4 = %d)", mx.format, FCSA_CACHE_MXFP4);
+  if (p.dtype == FCSA_F32) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_mx: float32 queries with an MXFP4 cache are not supported (f16 or bf16)");
+  if (p.dim_head != 32 && p.dim_head != 64 && p.dim_head != 96 && p.dim_head != 128)
+    return fail(FCSA_ERR_UNSUPPORTED, "kvcache_mx: dim_head %d is not supported (32, 64, 96 or 128: whole blocks of 32 features)", p.dim_head);
+  if (p.l2norm_qk && p.groups >= 1 && p.dim_head % p.groups == 0 && !fcsa::mx_groups_ok(p.dim_head, p.groups))
+    return fail(FCSA_ERR_UNSUPPORTED, "kvcache_mx: groups %d (%d features each) is not supported: 1, or groups of a multiple of 8 features "
+                "(fcsa_forward_kvcache_quant takes every group count)", p.groups, p.dim_head / p.groups);
+  return FCSA_OK;
+}
+// ... then the cache checks with one-byte elements (rows of D / 2 codes) and the scales
+int check_mx(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_kvcache_mx* mx) {
+  if (a == nullptr || kv == nullptr || mx == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_mx: null argument");
+  const fcsa_problem& p = a->p;
+  if (int rc = mx_supported(p, *mx)) return rc;
+  if (int rc = check_kvcache(a, kv, 1)) return rc;
+  if (p.batch > 0 && kv->capacity > 0) {
+    for (const auto& [name, t] : {std::pair<const char*, const fcsa_tensor*>{"k_block_scale", &mx->k_block_scale}, {"v_block_scale", &mx->v_block_scale}}) {
+      if (t->ptr == nullptr) return fail(FCSA_ERR_INVALID_ARG, "%s: null pointer", name);
+      if (t->stride2 < p.dim_head / 32 || t->stride0 < 0 || t->stride1 < 0)
+        return fail(FCSA_ERR_INVALID_ARG, "%s: strides (%lld, %lld, %lld): rows of %d scale bytes must not overlap", name, (long long)t->stride0,
+                    (long long)t->stride1, (long long)t->stride2, p.dim_head / 32);
+    }
+  }
+  return FCSA_OK;
+}
+
 // a ragged step: its own arguments, then the equal-N checks on the problem of the packed rows
 int check_kvcache_varlen(const DecodeCall& c) {
   const fcsa_forward_args* a = c.a;
@@ -956,6 +986,7 @@ int check_kvcache_varlen(const DecodeCall& c) {
   pk.new_len = kv->new_len != 0 && seqs->total_q > 0 ? 1 : 0;
   if (a->p.q_len < 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_varlen: negative max_seqlen_q (%d)", a->p.q_len);
   if ((int64_t)std::max(a->p.heads, 0) * seqs->total_q > INT32_MAX) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_varlen: heads x packed rows above 2^31");
+  if (c.mx != nullptr) return check_mx(&pa, &pk, c.mx);
   return c.qz != nullptr ? check_quant(&pa, &pk, c.qz) : check_kvcache(&pa, &pk);
 }
 
@@ -979,7 +1010,7 @@ fcsa::DecodeStepParams decode_params(const DecodeCall& c, const DecodeWindow& wi
   const fcsa_forward_args* a = c.a;
   const fcsa_kvcache* kv = c.kv;
   const fcsa_problem& p = a->p;
-  const int es = elem_size(p.dtype), ces = fp8 ? 1 : es;
+  const int es = elem_size(p.dtype), ces = fp8 || c.mx != nullptr ? 1 : es;      // (an MXFP4 cache: rows of bytes, two codes each)
   auto rows_view = [&](const fcsa_tensor& t) { return view(ragged ? packed(t) : t, es); };
   fcsa::DecodeStepParams dp{};
   dp.q = rows_view(a->q);
@@ -1046,6 +1077,9 @@ constexpr LaunchName kRotaryAppendName[2] = {{"kv_append_rotary", "kv append (ro
 constexpr LaunchName kRotaryDecodeName[2] = {{"rotary_decode", "decode (rotary)"}, {"rotary_decode_fp8", "decode (rotary, fp8)"}};
 constexpr LaunchName kRotaryPrefillName[2] = {{"rotary_prefill", "prefill (rotary)"}, {"rotary_prefill_fp8", "prefill (rotary, fp8)"}};
 
+// c.mx (an MXFP4 cache): the scale bytes as the kernels take them (byte strides)
+fcsa::DecodeMx mx_view(const fcsa_kvcache_mx& m) { return {view(m.k_block_scale, 1), view(m.v_block_scale, 1)}; }
+
 // the append (before anything reads the cache: same stream), where the call brings rows and the cache has room for any; c.rotary: the
 // append that rotates K on its way into the cache
 int append_launch(const DecodeCall& c, fcsa::DecodeForm form, const fcsa::DecodeStepParams& dp, hipStream_t s) {
@@ -1054,6 +1088,10 @@ int append_launch(const DecodeCall& c, fcsa::DecodeForm form, const fcsa::Decode
     const LaunchName& n = kRotaryAppendName[form.fp8];
     const fcsa::DecodeRotary ro = rotary_view(*c.rotary);
     return timed(n.name, n.what, s, [&] { return fcsa::launch_kv_append_rotary(c.a->p.dtype, c.a->p.dim_head, form, dp, ro, s); });
+  }
+  if (c.mx != nullptr) {
+    const fcsa::DecodeMx mx = mx_view(*c.mx);
+    return timed("kv_append_mx", "kv append (mxfp4)", s, [&] { return fcsa::launch_kv_append_mx(c.a->p.dtype, c.a->p.dim_head, form, dp, mx, s); });
   }
   const LaunchName& n = kAppendName[form.ragged][form.fp8];
   return timed(n.name, n.what, s, [&] { return fcsa::launch_kv_append(c.a->p.dtype, c.a->p.dim_head, form, dp, s); });
@@ -1067,6 +1105,10 @@ constexpr LaunchName kAlibiPrefillName[2] = {{"alibi_prefill", "prefill (alibi)"
 // the decode launch of a ragged or engine step under the name `plain`; c.alibi: the entry points that take the slopes, under their own name
 int decode_launch(const LaunchName& plain, const DecodeCall& c, fcsa::DecodeForm form, const fcsa::DecodeStepParams& dp, hipStream_t s) {
   const fcsa_problem& p = c.a->p;
+  if (c.mx != nullptr) {
+    const fcsa::DecodeMx mx = mx_view(*c.mx);
+    return timed("decode_mx", "decode (mxfp4)", s, [&] { return fcsa::launch_decode_mx(p.dtype, p.dim_head, form, dp, mx, s); });
+  }
   if (c.rotary != nullptr) {
     const LaunchName& n = kRotaryDecodeName[form.fp8];
     const fcsa::DecodeRotary ro = rotary_view(*c.rotary);
@@ -1107,14 +1149,14 @@ int decode_call(const DecodeCall& c) {
   if (ragged) {
     if (int rc = check_kvcache_varlen(c)) return rc;
   } else {
-    if (int rc = fp8 ? check_quant(c.a, c.kv, c.qz) : check_kvcache(c.a, c.kv)) return rc;
+    if (int rc = c.mx != nullptr ? check_mx(c.a, c.kv, c.mx) : fp8 ? check_quant(c.a, c.kv, c.qz) : check_kvcache(c.a, c.kv)) return rc;
     if (c.w != nullptr)
       if (int rc = check_window(c.w, false, false)) return rc;
   }
   const fcsa_forward_args* a = c.a;
   const fcsa_kvcache* kv = c.kv;
   const fcsa_problem& p = a->p;
-  const DecodeWindow win = decode_window(p, *kv, ragged, c.w);
+  const DecodeWindow win = decode_window(p, *kv, ragged || c.mx != nullptr, c.w);      // (the MXFP4 kernel always takes sides)
   const DecodePlan d = decode_plan(p, *kv, c.seqs, win.reach());
   if (ragged && d.slots * std::max(p.kv_heads, 1) * d.splits > INT32_MAX) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_varlen: grid above 2^31 workgroups");
   if (p.batch == 0) return FCSA_OK;
@@ -1279,6 +1321,23 @@ int fcsa_forward_kvcache_varlen(const fcsa_forward_args* a, const fcsa_kvcache* 
 size_t fcsa_forward_kvcache_varlen_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv, const fcsa_varlen* seqs,
                                                    const fcsa_kvcache_quant*, const fcsa_window* w) {
   return seqs == nullptr ? 0 : decode_workspace_bytes(p, kv, seqs, w);
+}
+
+// An MXFP4 cache: the equal-N or ragged call's description with `mx` added -- its checks (one-byte cache elements), window, plan, workspace
+// and combine, with the append and decode launches on the entry points of fcsa_decode_mx.hip.
+int fcsa_forward_kvcache_mx(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_kvcache_mx* mx, const fcsa_varlen* seqs,
+                            const fcsa_window* w, const fcsa_lse_out* lse) {
+  if (a == nullptr || kv == nullptr || mx == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_mx: null argument");
+  const bool rows = a->p.batch > 0 && a->p.heads > 0 && (seqs != nullptr ? seqs->total_q > 0 : a->p.q_len > 0);
+  if (rows && lse != nullptr && lse->lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_mx: lse: null pointer");
+  DecodeCall c{a, kv, seqs, nullptr, w, lse};
+  c.mx = mx;
+  return decode_call(c);
+}
+size_t fcsa_forward_kvcache_mx_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv, const fcsa_kvcache_mx* mx, const fcsa_varlen* seqs,
+                                               const fcsa_window* w) {
+  if (p == nullptr || mx == nullptr || mx_supported(*p, *mx) != FCSA_OK) return 0;
+  return decode_workspace_bytes(p, kv, seqs, w, true);
 }
 
 // ---- the decode calls with the rows' log-sum-exp (fcsa_forward_kvcache_lse), and merging attention states (fcsa_merge_states) ----------

@@ -1,0 +1,402 @@
+// fcsa_decode_mx.hip -- decoding against an MXFP4 key/value cache (fcsa_forward_kvcache_mx, include/fcsa.h).
+//
+// The cache holds OCP MX v1.0 MXFP4: two e2m1 codes per byte (low nibble = the even feature) and one e8m0 scale byte per 32 consecutive
+// features of a position, read clamped to [113, 139] -- inside that range every value e2m1(code) * 2^(s - 127) is exact in f16 and in bf16,
+// so both MFMA products get the operands a 16-bit cache holding those values would feed, and the 16-bit combine kernels finish the call.
+//
+//   kv_append_mx_kernel   one thread per 32-feature block of a new row: amax, the scale byte, sixteen code bytes (v_cvt_scalef32_pk_fp4_f32
+//                         on the clamped, pre-scaled values), for K and for V -- one 16-byte store and one byte store each
+//   decode_mx_kernel      the decode frame -- one wave per (sequence, K/V head, 16-row tile, key split), 32-key blocks, S^T = K^ Q^T and
+//                         O^T = V^T P~^T on mfma_f32_16x16x32, softmax_step / pv_block / the partials of fcsa_decode_common.cuh -- around a
+//                         key loop of its own, "quarter row per lane": lane (c, g) of a 16-key half (c = lane % 16, g = lane / 16) loads
+//                         the CONTIGUOUS quarter [g D/4, (g + 1) D/4) of key c -- D/8 bytes, at D = 128 one 16-byte load that is exactly
+//                         one MX block -- and MFMA step t contracts the features g D/4 + 8 t + j.  That order is a permutation of the
+//                         features; the query fragments, loaded once, use the same one.  Every 8-feature step lies inside one MX block
+//                         (8 divides 32), so a step takes one scale, folded into the conversion (v_cvt_scalef32_pk_f32_fp4).
+//                         K: with l2norm the float32 values are normalised (the sum of squares crosses the key's four lanes, or stays
+//                         inside the l2norm group) and rounded once to the type, as 16-bit keys are; without it the codes go straight to
+//                         the type (v_cvt_scalef32_pk_{f16,bf16}_fp4).  V: a lane's 16-byte chunk is one MX block of one key; it is
+//                         converted straight to the type on the way into the LDS block that pv_block reads transposed.
+#include "fcsa_common.cuh"
+#include "fcsa_decode_common.cuh"
+
+#include <type_traits>
+
+namespace fcsa {
+namespace {
+
+// 2^(s - 127) for the scale byte s, read clamped to [113, 139]
+FCSA_DEV float mx_scale(uint32_t s) { return as_f32(min(max(s, 113u), 139u) << 23); }
+
+// the two codes of byte B of `w` times `s` -> a packed pair of T
+template <typename T, int B> FCSA_DEV uint32_t mx_pair(uint32_t w, float s) {
+  if constexpr (std::is_same_v<T, F16>) return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, s, B));
+  else return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, s, B));
+}
+// the eight codes of one word (eight consecutive features) times `s`: as eight elements of T (exact), or as float32
+template <typename T> FCSA_DEV u32x4 mx_word(uint32_t w, float s) {
+  return u32x4{mx_pair<T, 0>(w, s), mx_pair<T, 1>(w, s), mx_pair<T, 2>(w, s), mx_pair<T, 3>(w, s)};
+}
+FCSA_DEV void mx_word_f32(uint32_t w, float s, float (&x)[8]) {
+  const f32x2 a = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, s, 0), b = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, s, 1);
+  const f32x2 c = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, s, 2), d = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, s, 3);
+  x[0] = a[0]; x[1] = a[1]; x[2] = b[0]; x[3] = b[1]; x[4] = c[0]; x[5] = c[1]; x[6] = d[0]; x[7] = d[1];
+}
+
+// NT words from a 4 NT-byte aligned address: one load of that width (three words: a pair and one)
+template <int NT> FCSA_DEV void load_words(const char* src, uint32_t (&w)[NT]) {
+  if constexpr (NT == 4) {
+    const u32x4 v = *reinterpret_cast<const u32x4*>(src);
+    w[0] = v[0]; w[1] = v[1]; w[2] = v[2]; w[3] = v[3];
+  } else if constexpr (NT == 2) {
+    const u32x2 v = *reinterpret_cast<const u32x2*>(src);
+    w[0] = v[0]; w[1] = v[1];
+  } else {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) w[t] = *reinterpret_cast<const uint32_t*>(src + 4 * t);
+  }
+}
+
+// Grouped l2norm of a row in the quarter layout -- lane g = lane >> 4 of the row's four lanes holds the features [g Q, (g + 1) Q), Q = 8 NT,
+// as NT units of eight: x *= 1 / max(||group||, 1e-12), the l2norm kernel's formula.  gs = features per group: D, or a multiple of 8
+// (mx_groups_ok).  One group: the sum crosses the four lanes; whole quarters per group: it crosses one or no lane pair; whole groups per
+// quarter: it stays in the lane; anything else (D = 96 with 16 or 32 features per group, which straddle the quarters of 24): every lane
+// collects the row's 4 NT unit sums and adds those of its units' groups.  gs is uniform: every lane runs every shuffle.
+template <int NT> FCSA_DEV void mx_group_normalise(float (&x)[NT][8], int gs, int lane) {
+  constexpr int Q = 8 * NT;
+  const int g = lane >> 4;
+  float u[NT], ss[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    u[t] = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) u[t] += x[t][e] * x[t][e];
+  }
+  if (gs % Q == 0) {
+    float s = 0.f;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) s += u[t];
+    if (gs >= 2 * Q) s += __shfl_xor(s, 16, 64);
+    if (gs >= 4 * Q) s += __shfl_xor(s, 32, 64);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) ss[t] = s;
+  } else if (Q % gs == 0) {
+    const int m = gs / 8;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      ss[t] = 0.f;
+#pragma unroll
+      for (int t2 = 0; t2 < NT; ++t2) ss[t] += t2 / m == t / m ? u[t2] : 0.f;
+    }
+  } else {
+    const int m = gs / 8;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) ss[t] = 0.f;
+#pragma unroll
+    for (int h = 0; h < 4; ++h)
+#pragma unroll
+      for (int t2 = 0; t2 < NT; ++t2) {
+        const float v = __shfl(u[t2], (lane & 15) + 16 * h, 64);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) ss[t] += (h * NT + t2) / m == (g * NT + t) / m ? v : 0.f;
+      }
+  }
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const float r = 1.f / fmaxf(sqrtf(ss[t]), 1e-12f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) x[t][e] *= r;
+  }
+}
+
+// What a lane holds of a 32-key block.  K: per 16-key half its quarter of key c -- NT = D / 32 words of codes and the scale bytes of the
+// MX blocks they lie in (one; D = 96: a quarter of 24 features can touch two blocks, so one per word).  V: 16-byte chunk c = lane + 64 t of
+// the block's 32 D / 32 chunks is MX block c % (D / 32) of key c / (D / 32), with its scale byte.
+// Per block and lane at D = 128: two 16-byte K loads and two byte loads, two 16-byte V loads and two byte loads.
+template <int D> struct MxRegs {
+  static constexpr int NT = D / 32;                   // MFMA steps of a 16-key half = words of codes per lane and key
+  static constexpr int Q = D / 4;                     // features of a quarter
+  static constexpr int NS = D == 96 ? NT : 1;         // K scale bytes per lane and key
+  static constexpr int CPR = D / 32;                  // 16-byte chunks (= MX blocks) of a row of codes
+  static constexpr int VTOT = kDecodeBlock * CPR;
+  static constexpr int VCH = (VTOT + 63) / 64;
+  uint32_t k[2][NT];
+  uint32_t ks[2][NS];
+  u32x4 v[VCH];
+  uint32_t vs[VCH];
+
+  // the 32-key block from `kb`, each 16-key half under the load rule (clamped_first, clamped_off): every position read is below `end`
+  FCSA_DEV void load(const DecodeParams& p, const DecodeMx& mx, int b, int kvh, int kb, int end, int lane) {
+    const int c = lane & 15, g = lane >> 4;
+    int first[2];
+#pragma unroll
+    for (int sb = 0; sb < 2; ++sb) {
+      first[sb] = clamped_first(kb + 16 * sb, end);
+      const int off = clamped_off(kb + 16 * sb + c, first[sb], end);
+      load_words<NT>(cache_base(p, p.kc, b, kvh, first[sb]) + (int64_t)off * p.kc.sn + g * (Q / 2), k[sb]);
+      const uint8_t* srow = reinterpret_cast<const uint8_t*>(cache_base(p, mx.ks, b, kvh, first[sb]) + (int64_t)off * mx.ks.sn);
+#pragma unroll
+      for (int t = 0; t < NS; ++t) ks[sb][t] = srow[(g * Q + 8 * t) / 32];
+    }
+#pragma unroll
+    for (int t = 0; t < VCH; ++t) {
+      const int ci = lane + 64 * t, kk = ci / CPR, ch = ci % CPR, sb = kk >> 4;
+      v[t] = u32x4{0u, 0u, 0u, 0u};
+      vs[t] = 127u;
+      if (ci < VTOT && kb + kk < end) {
+        const int off = clamped_off(kb + kk, first[sb], end);
+        v[t] = *reinterpret_cast<const u32x4*>(cache_base(p, p.vc, b, kvh, first[sb]) + (int64_t)off * p.vc.sn + ch * 16);
+        vs[t] = *reinterpret_cast<const uint8_t*>(cache_base(p, mx.vs, b, kvh, first[sb]) + (int64_t)off * mx.vs.sn + ch);
+      }
+    }
+  }
+};
+
+// RAGGED: packed queries with per-sequence counts (ragged_tile: idle slots exit at once); otherwise N rows per sequence.  Both forms carry
+// the window sides, open ones (kWinOpen; causal: win_hi = 0) for a call without a window.
+template <typename T, int D, bool DYN, bool RAGGED>
+__global__ __launch_bounds__(64) void decode_mx_kernel(DecodeRaggedParams p, DecodeMx mx) {
+  typedef MxRegs<D> R;
+  constexpr int NT = R::NT, Q = R::Q, CPR = R::CPR, VCH = R::VCH;
+  constexpr int FB = D / 16;
+  constexpr int PITCH = kKvPitch<D, 2>;
+  extern __shared__ __attribute__((aligned(16))) char smem[];      // one 32-key V block in T, rows of D elements padded by 16 bytes
+
+  const int lane = threadIdx.x, x = lane & 15, hi = lane >> 4;
+  int id = blockIdx.x;
+  const int split = id % p.splits;
+  id /= p.splits;
+  int rt, kvh, b, N, q0 = 0, new_len;
+  if constexpr (RAGGED) {
+    kvh = id % p.Hk;
+    if (!ragged_tile(p.cu_q, p.B, p.total_q, p.G, id / p.Hk, b, rt, q0, N)) return;
+    new_len = p.append ? N : 0;
+  } else {
+    rt = id % p.row_tiles;
+    id /= p.row_tiles;
+    kvh = id % p.Hk, b = id / p.Hk;
+    N = p.N;
+    new_len = p.new_len;
+  }
+  const int L = decode_len(p.seqlens != nullptr, p.seqlens != nullptr ? p.seqlens[b] : 0, new_len, p.capacity);
+  int lo, n;
+  const int first = win_decode_first(L, N, p.win_lo);
+  decode_window(L - first, split, p.splits, lo, n);
+  lo += first;
+  const int end = lo + n;
+
+  // this lane's query row: the column of every MFMA result
+  const int r = rt * kDecodeRows + x;
+  const bool row_ok = r < p.G * N;
+  const int g = row_ok ? r / N : 0, qi = row_ok ? r % N : 0;
+  const int h = kvh * p.G + g;
+  const int last_key = L - N + qi;
+  const int gs = D / p.groups;
+
+  // the query in the keys' order: unit t of lane (x, hi) holds features hi Q + 8 t ... + 7
+  u32x4 qf[NT];
+  {
+    float xq[NT][8];
+    const char* qrow = p.q.p + (RAGGED ? 0 : (int64_t)b * p.q.sb) + (int64_t)h * p.q.sh + (int64_t)(q0 + qi) * p.q.sn + hi * Q * 2;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const u32x4 u = row_ok ? *reinterpret_cast<const u32x4*>(qrow + 16 * t) : u32x4{0u, 0u, 0u, 0u};
+      unpack<T>(u, xq[t]);
+    }
+    if (p.l2norm) mx_group_normalise<NT>(xq, gs, lane);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) qf[t] = pack<T>(xq[t], p.l2norm ? p.c1 : 1.f);
+  }
+  const float smul = p.l2norm ? 1.f : p.c1;
+
+  f32x4 acc[FB];
+#pragma unroll
+  for (int fb = 0; fb < FB; ++fb) acc[fb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m = DYN ? -INFINITY : p.c2, l = 0.f;
+
+  R cur, nxt;
+  if (n > 0) cur.load(p, mx, b, kvh, lo, end, lane);
+  for (int kb = lo; kb < end; kb += kDecodeBlock) {
+    if (kb + kDecodeBlock < end) nxt.load(p, mx, b, kvh, kb + kDecodeBlock, end, lane);
+    // S^T = K^ Q^T for the two 16-key halves: s[sb][rr] = logit of key kb + 16 sb + 4 hi + rr for row x (log2 units)
+    f32x4 s[2];
+#pragma unroll
+    for (int sb = 0; sb < 2; ++sb) {
+      u32x4 kf[NT];
+      if (p.l2norm) {
+        float xk[NT][8];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) mx_word_f32(cur.k[sb][t], mx_scale(cur.ks[sb][R::NS == 1 ? 0 : t]), xk[t]);
+        mx_group_normalise<NT>(xk, gs, lane);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) kf[t] = pack<T>(xk[t], 1.f);       // k^ rounded to the type, as the l2norm kernel writes it
+      } else {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) kf[t] = mx_word<T>(cur.k[sb][t], mx_scale(cur.ks[sb][R::NS == 1 ? 0 : t]));
+      }
+      s[sb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int t = 0; t < NT; ++t) s[sb] = Unit<T>::mfma(kf[t], qf[t], s[sb]);
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        const int key = kb + 16 * sb + 4 * hi + rr;
+        const bool vis = key < end && key <= last_key + p.win_hi && key >= last_key - p.win_lo;
+        s[sb][rr] = vis ? s[sb][rr] * smul : -INFINITY;
+      }
+    }
+    f32x4 pr[2];
+    softmax_step<DYN>(s, m, l, acc, p.c2, pr);
+
+    // V block -> LDS in T (row-major, padded rows): a chunk of 16 code bytes becomes 32 elements, then O^T += V^T P~^T
+#pragma unroll
+    for (int t = 0; t < VCH; ++t) {
+      const int ci = lane + 64 * t;
+      if (R::VTOT % 64 == 0 || ci < R::VTOT) {
+        const float vscale = mx_scale(cur.vs[t]);
+        u32x4* dst = reinterpret_cast<u32x4*>(smem + (ci / CPR) * PITCH + (ci % CPR) * 64);
+#pragma unroll
+        for (int w = 0; w < 4; ++w) dst[w] = mx_word<T>(cur.v[t][w], vscale);
+      }
+    }
+    __syncthreads();
+    u32x4 pb;
+    pb[0] = Traits<T>::pack2(pr[0][0], pr[0][1]);
+    pb[1] = Traits<T>::pack2(pr[0][2], pr[0][3]);
+    pb[2] = Traits<T>::pack2(pr[1][0], pr[1][1]);
+    pb[3] = Traits<T>::pack2(pr[1][2], pr[1][3]);
+    pv_block<T, D, 1>(smem, 0, x, hi, &pb, &acc);
+    __syncthreads();
+    cur = nxt;
+  }
+
+  // partials of row x, as the 16-bit decode kernel leaves them for the combine: [B, H, N] rows; RAGGED: [total_q, H]
+  l += __shfl_xor(l, 16, 64);
+  l += __shfl_xor(l, 32, 64);
+  if (row_ok) {
+    int64_t rows, row;
+    if constexpr (RAGGED) {
+      rows = (int64_t)p.total_q * p.H;
+      row = (int64_t)(q0 + qi) * p.H + h;
+    } else {
+      rows = (int64_t)p.B * p.H * N;
+      row = ((int64_t)b * p.H + h) * N + qi;
+    }
+    float* wo = p.ws_o + ((int64_t)split * rows + row) * D;
+#pragma unroll
+    for (int fb = 0; fb < FB; ++fb) *reinterpret_cast<f32x4*>(wo + 16 * fb + 4 * hi) = acc[fb];
+    if (hi == 0) *reinterpret_cast<f32x2*>(p.ws_ml + ((int64_t)split * rows + row) * 2) = f32x2{m, l};
+  }
+}
+
+// ---- the append -------------------------------------------------------------------------------------------------------------------------
+// One 32-feature block (64 source bytes of T) -> its scale byte and sixteen code bytes, in float32:
+//   e = clamp(floor(log2(amax)) - 2, -14, 12), floor(log2) being amax's exponent field (amax = 0 and float32 subnormals: -14);
+//   scale byte = e + 127;  code = e2m1_rne(clamp(x * 2^-e, -6, 6)).
+// The clamp is explicit and the multiply by the power of two exact, so the pack conversion (scale operand 1.0) only rounds a value inside
+// the e2m1 range to nearest, ties to the even code.
+template <typename T> FCSA_DEV void mx_quantise_block(const char* src, char* codes, uint8_t* scale) {
+  float x[4][8];
+  float amax = 0.f;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    unpack<T>(*reinterpret_cast<const u32x4*>(src + 16 * w), x[w]);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(x[w][e]));
+  }
+  const int e = min(max((int)((__builtin_bit_cast(uint32_t, amax) >> 23) & 0xffu) - 129, -14), 12);
+  const float inv = as_f32((uint32_t)(127 - e) << 23);
+  u32x4 out;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    float y[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) y[i] = fminf(fmaxf(x[w][i] * inv, -6.f), 6.f);
+    uint32_t c = 0u;
+    c = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(c, y[0], y[1], 1.f, 0);
+    c = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(c, y[2], y[3], 1.f, 1);
+    c = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(c, y[4], y[5], 1.f, 2);
+    c = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(c, y[6], y[7], 1.f, 3);
+    out[w] = c;
+  }
+  *reinterpret_cast<u32x4*>(codes) = out;
+  *scale = (uint8_t)(e + 127);
+}
+
+// One thread per MX block of a new row of a K/V head, K and V alike.  Where the row goes is the family's rule: position
+// clamp(cache_seqlens[b], 0, capacity) + i, dropped at or beyond the capacity (every row, when seqlens is null); its address is cache_base.
+// RAGGED: packed row `tok` of kn / vn [total_q, Hk, D], slot tok - cu_q[b] of its sequence; otherwise row tn of [B, Hk, new_len, D].
+template <typename T, int D, bool RAGGED>
+__global__ __launch_bounds__(256) void kv_append_mx_kernel(DecodeRaggedParams p, DecodeMx mx) {
+  constexpr int CPR = D / 32;
+  const int64_t total = (RAGGED ? (int64_t)p.total_q : (int64_t)p.B * p.new_len) * p.Hk * CPR;
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= total) return;
+  const int ch = (int)(t % CPR);
+  int64_t rest = t / CPR;
+  const int kvh = (int)(rest % p.Hk);
+  rest /= p.Hk;
+  int b;
+  int64_t i;
+  const char *ksrc, *vsrc;
+  if constexpr (RAGGED) {
+    const int64_t tok = rest;
+    b = ragged_seq_of(p.cu_q, p.B, p.total_q, tok);
+    const int64_t q0 = ragged_cu(p.cu_q[b], p.total_q), q1 = ragged_cu(p.cu_q[b + 1], p.total_q);
+    if (tok < q0 || tok >= q1) return;          // (a malformed table: the row belongs to no sequence)
+    i = tok - q0;
+    ksrc = p.kn.p + (int64_t)kvh * p.kn.sh + tok * p.kn.sn;
+    vsrc = p.vn.p + (int64_t)kvh * p.vn.sh + tok * p.vn.sn;
+  } else {
+    i = rest % p.new_len;
+    b = (int)(rest / p.new_len);
+    ksrc = p.kn.p + (int64_t)b * p.kn.sb + (int64_t)kvh * p.kn.sh + i * p.kn.sn;
+    vsrc = p.vn.p + (int64_t)b * p.vn.sb + (int64_t)kvh * p.vn.sh + i * p.vn.sn;
+  }
+  const int64_t start = p.seqlens != nullptr ? min(max((int64_t)p.seqlens[b], (int64_t)0), (int64_t)p.capacity) : (int64_t)p.capacity;
+  if (start + i >= p.capacity) return;
+  const int pos = (int)(start + i);
+  mx_quantise_block<T>(ksrc + ch * 64, cache_base(p, p.kc, b, kvh, pos) + ch * 16, reinterpret_cast<uint8_t*>(cache_base(p, mx.ks, b, kvh, pos)) + ch);
+  mx_quantise_block<T>(vsrc + ch * 64, cache_base(p, p.vc, b, kvh, pos) + ch * 16, reinterpret_cast<uint8_t*>(cache_base(p, mx.vs, b, kvh, pos)) + ch);
+}
+
+// the 16-bit types x D 32 / 64 / 96 / 128 x ragged or not: fn(TypeDim<T, D>, RAGGED); everything else hipErrorInvalidValue
+template <typename F> hipError_t dispatch_mx(int dtype, int D, DecodeForm f, F&& fn) {
+  if (f.fp8 || f.step) return hipErrorInvalidValue;
+  return dispatch_dtype_d(dtype, D, [&](auto td) -> hipError_t {
+    if constexpr (Traits<typename decltype(td)::T>::ES == 2 && decltype(td)::D % 32 == 0) {
+      return f.ragged ? fn(td, std::true_type{}) : fn(td, std::false_type{});
+    } else {
+      return hipErrorInvalidValue;
+    }
+  });
+}
+
+}  // namespace
+
+hipError_t launch_kv_append_mx(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeMx& mx, hipStream_t s) {
+  return dispatch_mx(dtype, D, f, [&](auto td, auto ragged) -> hipError_t {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    constexpr bool RAGGED = decltype(ragged)::value;
+    const int64_t threads = (RAGGED ? (int64_t)p.total_q : (int64_t)p.B * p.new_len) * p.Hk * (DD / 32);
+    if (threads <= 0 || (RAGGED && p.B <= 0)) return hipSuccess;
+    return launch_part<kv_append_mx_kernel<T, DD, RAGGED>, 0>(dim3((unsigned)((threads + 255) / 256)), dim3(256), s, p, mx);
+  });
+}
+
+hipError_t launch_decode_mx(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeMx& mx, hipStream_t s) {
+  if (p.l2norm && !mx_groups_ok(D, p.groups)) return hipErrorInvalidValue;
+  return dispatch_mx(dtype, D, f, [&](auto td, auto ragged) -> hipError_t {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    constexpr bool RAGGED = decltype(ragged)::value;
+    constexpr int LDS = kDecodeBlock * kKvPitch<DD, 2>;
+    const int64_t wgs = (RAGGED ? (int64_t)p.slots : (int64_t)p.B * p.row_tiles) * p.Hk * p.splits;
+    if (wgs <= 0) return hipSuccess;
+    const dim3 grid((unsigned)wgs), block(64);
+    return p.dyn ? launch_part<decode_mx_kernel<T, DD, true, RAGGED>, LDS>(grid, block, s, p, mx)
+                 : launch_part<decode_mx_kernel<T, DD, false, RAGGED>, LDS>(grid, block, s, p, mx);
+  });
+}
+
+}  // namespace fcsa

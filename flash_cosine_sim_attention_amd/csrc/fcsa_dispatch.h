@@ -234,6 +234,9 @@ constexpr bool decode_groups_fast(int D, int groups, int unit) {
   const int u = gs / unit;
   return (u & (u - 1)) == 0;
 }
+// l2norm groups the MXFP4 decode kernel (fcsa_decode_mx.hip) reduces: one group, or groups of a multiple of 8 features (an MFMA step of
+// its key loop never straddles two of them)
+constexpr bool mx_groups_ok(int D, int groups) { return groups >= 1 && D % groups == 0 && (groups == 1 || (D / groups) % 8 == 0); }
 
 // Sliding window (win_normalise: lo keys to the left): the N queries of a sequence of `len` keys are its last N positions, so its rows read
 // the keys from win_decode_first on (a whole 32-key block boundary), and the split count is sized by the keys a sequence can read

@@ -247,6 +247,18 @@ hipError_t launch_prefill_alibi(int dtype, int D, DecodeForm f, const DecodeStep
 hipError_t launch_kv_append_rotary(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeRotary& rotary, hipStream_t s);
 hipError_t launch_decode_rotary(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeRotary& rotary, hipStream_t s);
 hipError_t launch_prefill_rotary(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeRotary& rotary, const DecodeLseOut* lse, hipStream_t s);
+// An MXFP4 cache (fcsa_forward_kvcache_mx; csrc/fcsa_decode_mx.hip): kc / vc of the block hold two e2m1 codes per byte (views in bytes,
+// rows of D / 2), and the e8m0 scale bytes of their 32-feature blocks come as a second kernel argument of the entry points that read or
+// write them (kv_append_mx_kernel, decode_mx_kernel), as DecodeAlibi is of the ALiBi ones: ks / vs address like kc / vc (BYTE strides, the
+// same table), rows of D / 32 bytes.  The two launches of such a call: the append (one thread per MX block of a new row) and the decode
+// (launch_decode's grid, both exponent regimes; always with the window sides, open where the call has none).  16-bit types, D = 32 / 64 /
+// 96 / 128, l2norm groups of mx_groups_ok, no fp8 and no step form; hipErrorInvalidValue otherwise.  The combine is launch_decode_combine's
+// 16-bit one: the V scales are applied as the codes are read.
+struct DecodeMx {
+  View ks, vs;
+};
+hipError_t launch_kv_append_mx(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeMx& mx, hipStream_t s);
+hipError_t launch_decode_mx(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeMx& mx, hipStream_t s);
 
 // Merging attention states (fcsa_merge_states, csrc/fcsa_merge.hip): S states (o_s, lse_s) of the rows [n0, n1, n2] -> (o, lse).  o views
 // carry BYTE strides, lse views ELEMENT strides.

@@ -80,7 +80,10 @@ namespace {
   X(backward_alibi, fcsa_backward_alibi, false)                                           \
   X(backward_alibi_ws, fcsa_backward_alibi_workspace_bytes, false)                        \
   /* a rotary position embedding inside the engine step */                                \
-  X(forward_kvcache_rotary, fcsa_forward_kvcache_rotary, false)
+  X(forward_kvcache_rotary, fcsa_forward_kvcache_rotary, false)                           \
+  /* decoding against an MXFP4 cache */                                                   \
+  X(forward_kvcache_mx, fcsa_forward_kvcache_mx, false)                                   \
+  X(forward_kvcache_mx_ws, fcsa_forward_kvcache_mx_workspace_bytes, false)
 
 struct Abi {
 #define X(member, symbol, required) decltype(&symbol) member = &symbol;
@@ -764,7 +767,7 @@ Tensor varlen_window_attention_autograd(const Tensor& q, const Tensor& k, const 
 //
 // One description of a call, CacheCall: every op function fills the members it has and hands it to kvcache_call, which runs the checks
 // (cache_checks), fills the library's structs (fill_lib_call) and dispatches through the one table of entry points (kEntries).
-enum class Route { Plain, Prefill, Step, Tree, Alibi, Rotary };
+enum class Route { Plain, Prefill, Step, Tree, Alibi, Rotary, Mx };
 
 struct CacheCall {
   // what every op has
@@ -780,8 +783,10 @@ struct CacheCall {
   fcsa_kvcache_step step{};                               // Step, Alibi, Rotary: the routing fields
   const Tensor* extra = nullptr;                          // Tree: tree_mask; Alibi: alibi_slopes; Rotary: rotary_cos
   const Tensor* rotary_sin = nullptr; bool rotary_interleaved = false;      // Rotary
+  const Tensor *k_block_scale = nullptr, *v_block_scale = nullptr;          // Mx: the scale bytes of an MXFP4 cache (its codes as uint8 tensors)
   bool ragged() const { return cu_q != nullptr; }
   bool fp8() const { return k_scale != nullptr; }
+  bool mx() const { return route == Route::Mx; }
 };
 
 const Tensor* ptr(const optional<Tensor>& t) { return t.has_value() ? &*t : nullptr; }
@@ -856,6 +861,12 @@ CacheKeep cache_checks(const CacheCall& c) {
                      k_cache.scalar_type(), " and ", v_cache.scalar_type());
     TORCH_CHECK_TYPE(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16,
                      "fp8 caches take float16 or bfloat16 queries, got ", q.scalar_type());
+  } else if (c.mx()) {
+    TORCH_CHECK_TYPE(k_cache.scalar_type() == at::kByte && v_cache.scalar_type() == at::kByte,
+                     "kvcache_mxfp4_forward takes the e2m1 codes of both caches as uint8 tensors, two per byte, got ", k_cache.scalar_type(), " and ",
+                     v_cache.scalar_type());
+    TORCH_CHECK_TYPE(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16, "MXFP4 caches take float16 or bfloat16 queries, got ",
+                     q.scalar_type());
   } else {
     TORCH_CHECK_TYPE(q.scalar_type() == k_cache.scalar_type() && q.scalar_type() == v_cache.scalar_type(), "q, k_cache, v_cache must share a dtype");
   }
@@ -909,7 +920,21 @@ CacheKeep cache_checks(const CacheCall& c) {
   }
   const int64_t B = k.B = ragged ? k.cu.numel() - 1 : q.size(0), H = k.H = q.size(1), N = k.N = ragged ? q.size(0) : q.size(2);
   const int64_t D = k.D = q.size(-1), Hk = k.Hk = k_cache.size(1);
-  TORCH_CHECK_VALUE(k_cache.size(3) == D, "query, key, value dimensions must be the same");
+  if (c.mx()) {
+    // rows of D / 2 code bytes, and the scale bytes: the caches' leading dims (the same pool, the same table) with D / 32 bytes per position
+    TORCH_CHECK_VALUE(D == 32 || D == 64 || D == 96 || D == 128, "MXFP4 caches take head dimensions (32, 64, 96, 128): whole blocks of 32 features, got ", D);
+    TORCH_CHECK_VALUE(k_cache.size(3) == D / 2, "an MXFP4 cache holds dim_head / 2 (", D / 2, ") code bytes per position, got ", k_cache.size(3));
+    for (const auto& [name, t] : {std::pair<const char*, const Tensor*>{"k_block_scale", c.k_block_scale}, {"v_block_scale", c.v_block_scale}}) {
+      same_dev(name, *t);
+      TORCH_CHECK_TYPE(t->scalar_type() == at::kByte, name, " must be uint8 (e8m0 scale bytes), got ", t->scalar_type());
+      TORCH_CHECK_VALUE(t->dim() == 4 && t->sizes().slice(0, 3) == k_cache.sizes().slice(0, 3) && t->size(3) == D / 32, name,
+                        " must have the caches' leading dimensions and dim_head / 32 (", D / 32, ") bytes per position, got ", t->sizes());
+      TORCH_CHECK_VALUE(t->stride(3) == 1 || t->size(3) == 1, name, ": the last dim must be contiguous (the scales are updated in place, so they are not copied)");
+    }
+    // (which group counts the kernel reduces is the library's to say: fcsa::mx_groups_ok behind fcsa_forward_kvcache_mx)
+  } else {
+    TORCH_CHECK_VALUE(k_cache.size(3) == D, "query, key, value dimensions must be the same");
+  }
   TORCH_CHECK_VALUE(D == 16 || D == 32 || D == 64 || D == 96 || D == 128, "only dimensions (16, 32, 64, 96, 128) allowed for now, got ", D);
   TORCH_CHECK_VALUE(Hk >= 1 && H % Hk == 0, "k/v heads must divide q heads (", H, "), got ", Hk);
   TORCH_CHECK_VALUE(!c.l2norm_qk || (c.groups >= 1 && D % c.groups == 0), "groups (", c.groups, ") must divide the head dimension (", D, ")");
@@ -962,7 +987,7 @@ CacheKeep cache_checks(const CacheCall& c) {
 // What one call hands to the library: the structs of include/fcsa.h, filled from the call and its canonical tensors.
 struct LibCall {
   fcsa_forward_args a; fcsa_kvcache kv; fcsa_varlen seqs; fcsa_lse_out lo;
-  fcsa_kvcache_quant qz; fcsa_tree_mask tree; fcsa_alibi alibi; fcsa_rotary rotary;
+  fcsa_kvcache_quant qz; fcsa_tree_mask tree; fcsa_alibi alibi; fcsa_rotary rotary; fcsa_kvcache_mx mx;
   const fcsa_window* win; const fcsa_kvcache_step* step;
   bool ragged, fp8;
   const fcsa_kvcache_quant* quant() const { return fp8 ? &qz : nullptr; }
@@ -993,6 +1018,7 @@ void fill_lib_call(LibCall& l, const CacheCall& c, const CacheKeep& k, const Ten
     l.qz = {FCSA_CACHE_E4M3, ks.data_ptr<float>(), vs.data_ptr<float>(), ks.dim() == 2 ? ks.stride(0) : 0, ks.dim() >= 1 ? ks.stride(-1) : 0,
             vs.dim() == 2 ? vs.stride(0) : 0, vs.dim() >= 1 ? vs.stride(-1) : 0};
   }
+  if (c.mx()) l.mx = {FCSA_CACHE_MXFP4, strided(*c.k_block_scale), strided(*c.v_block_scale)};
   if (k.words.defined()) l.tree.mask = reinterpret_cast<const uint64_t*>(k.words.data_ptr<int64_t>());
   if (k.slopes.defined()) {
     l.alibi.slopes = k.slopes.data_ptr<float>();
@@ -1013,7 +1039,7 @@ struct EntryPoint {
   size_t (*workspace)(const LibCall&);      // null: that of the call without the lse
   int (*run)(const LibCall&);
 };
-enum Entry { kKvcache, kWindow, kQuant, kVarlen, kLse, kPrefill, kStep, kTree, kAlibi, kRotary };
+enum Entry { kKvcache, kWindow, kQuant, kVarlen, kLse, kPrefill, kStep, kTree, kAlibi, kRotary, kMx };
 const EntryPoint kEntries[] = {
     /* kKvcache */ {"fcsa_forward_kvcache", "flash_cosine_sim_attention_with_kvcache",
                     [] { return g_abi.forward_kvcache != nullptr && g_abi.forward_kvcache_ws != nullptr; },
@@ -1049,19 +1075,23 @@ const EntryPoint kEntries[] = {
     /* kRotary: the step's workspace */ {"fcsa_forward_kvcache_rotary", "rotary_cos / rotary_sin", [] { return g_abi.forward_kvcache_rotary != nullptr; },
      [](const LibCall& l) { return g_abi.forward_kvcache_step_ws(&l.a.p, &l.kv, &l.seqs, l.quant(), l.win, l.step); },
      [](const LibCall& l) { return g_abi.forward_kvcache_rotary(&l.a, &l.kv, &l.seqs, l.quant(), l.win, l.step, &l.rotary, &l.lo); }},
+    /* kMx: equal N or ragged, with or without the lse */ {"fcsa_forward_kvcache_mx", "flash_cosine_sim_attention_mxfp4_with_kvcache",
+     [] { return g_abi.forward_kvcache_mx != nullptr && g_abi.forward_kvcache_mx_ws != nullptr; },
+     [](const LibCall& l) { return g_abi.forward_kvcache_mx_ws(&l.a.p, &l.kv, &l.mx, l.ragged ? &l.seqs : nullptr, l.win); },
+     [](const LibCall& l) { return g_abi.forward_kvcache_mx(&l.a, &l.kv, &l.mx, l.ragged ? &l.seqs : nullptr, l.win, l.lo.lse != nullptr ? &l.lo : nullptr); }},
 };
 
 // the entry point of a Plain call without the lse: by the ragged / fp8 / window facts
 Entry plain_entry(const CacheCall& c) { return c.ragged() ? kVarlen : c.fp8() ? kQuant : c.win != nullptr ? kWindow : kKvcache; }
-constexpr Entry kOfRoute[] = {kKvcache /* Plain: by the facts instead */, kPrefill, kStep, kTree, kAlibi, kRotary};      // in Route's order
-static_assert(sizeof(kEntries) / sizeof(kEntries[0]) == kRotary + 1 && sizeof(kOfRoute) / sizeof(kOfRoute[0]) == (int)Route::Rotary + 1,
+constexpr Entry kOfRoute[] = {kKvcache /* Plain: by the facts instead */, kPrefill, kStep, kTree, kAlibi, kRotary, kMx};      // in Route's order
+static_assert(sizeof(kEntries) / sizeof(kEntries[0]) == kMx + 1 && sizeof(kOfRoute) / sizeof(kOfRoute[0]) == (int)Route::Mx + 1,
               "kEntries has one row per Entry, in its order, and kOfRoute one entry per Route");
 Entry entry_of(const CacheCall& c) { return c.route != Route::Plain ? kOfRoute[(int)c.route] : c.lse ? kLse : plain_entry(c); }
 // a call needs its own entry point and those of the calls it is built on
 void need_entries(const CacheCall& c, Entry own) {
   auto need = [](Entry e) { need_abi(kEntries[e].who, kEntries[e].symbol, kEntries[e].present()); };
   if (c.route != Route::Plain) need(own);
-  if (c.lse) need(kLse);
+  if (c.lse && !c.mx()) need(kLse);
   if (c.ragged()) need(kVarlen);
   need(kKvcache);
   if (c.fp8()) need(kQuant);
@@ -1204,6 +1234,22 @@ std::tuple<Tensor, Tensor> kvcache_rotary_forward(const Tensor& q, const Tensor&
   c.win = win.ptr(); c.cu_q = &cu_seqlens_q; c.max_seqlen_q = max_seqlen_q; c.lse = true;
   c.route = Route::Rotary; c.extra = &rotary_cos; c.rotary_sin = &rotary_sin; c.rotary_interleaved = rotary_interleaved;
   return kvcache_call(c);
+}
+
+// Decoding against an MXFP4 cache (kvcache_mxfp4_forward): the codes of both caches as uint8 tensors [..., D / 2] and their e8m0 scale bytes
+// [..., D / 32], all four updated in place by the append.  cu_seqlens_q given: a ragged step; window sides of (-1, -1): no window; return_lse:
+// whether the second result is the rows' log-sum-exp (an undefined tensor otherwise is no result an op can return: an empty one).
+std::tuple<Tensor, Tensor> kvcache_mxfp4_forward(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& k_block_scale,
+                                                 const Tensor& v_block_scale, const optional<Tensor>& cu_seqlens_q, const optional<Tensor>& k_new,
+                                                 const optional<Tensor>& v_new, const optional<Tensor>& cache_seqlens,
+                                                 const optional<Tensor>& block_table, int64_t max_seqlen_q, int64_t max_seqlen_k, double scale,
+                                                 bool causal, bool l2norm_qk, int64_t groups, int64_t left, int64_t right, bool return_lse) {
+  CacheCall c{q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups};
+  const OptWin win(left, right);
+  c.win = win.ptr(); c.cu_q = ptr(cu_seqlens_q); c.max_seqlen_q = max_seqlen_q; c.lse = return_lse;
+  c.route = Route::Mx; c.k_block_scale = &k_block_scale; c.v_block_scale = &v_block_scale;
+  auto [o, lse] = kvcache_call(c);
+  return {o, return_lse ? lse : at::empty({0}, q.options().dtype(at::kFloat))};
 }
 
 // A tree step: kvcache_lse_forward's ragged step without a window and without `causal`, the visibility of the step's own tokens given per
@@ -1728,6 +1774,14 @@ TORCH_LIBRARY(fcsa_rotary, m) {
         "int chunk_rows, int max_decode_tokens, bool no_decode, bool no_chunk) -> (Tensor, Tensor)");
 }
 TORCH_LIBRARY_IMPL(fcsa_rotary, CUDA, m) { m.impl("kvcache_rotary_forward", &kvcache_rotary_forward); }
+
+// decoding against an MXFP4 cache, likewise.  Forward only: no Autograd kernel.
+TORCH_LIBRARY(fcsa_mx, m) {
+  m.def("kvcache_mxfp4_forward(Tensor q, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor(c!) k_block_scale, Tensor(d!) v_block_scale, "
+        "Tensor? cu_seqlens_q, Tensor? k_new, Tensor? v_new, Tensor? cache_seqlens, Tensor? block_table, int max_seqlen_q, int max_seqlen_k, "
+        "float scale, bool causal, bool l2norm_qk, int groups, int window_left, int window_right, bool return_lse) -> (Tensor, Tensor)");
+}
+TORCH_LIBRARY_IMPL(fcsa_mx, CUDA, m) { m.impl("kvcache_mxfp4_forward", &kvcache_mxfp4_forward); }
 
 // Attention states for training, in a namespace of their own (the op set of `fcsa` is pinned): the attention op with the rows'
 // log-sum-exp as a second differentiable result -- dense, local (window sides other than (-1, -1)) or packed (cu_seqlens given) -- and

@@ -426,10 +426,17 @@ class _CacheCall:
     `_packed_call`, the packed ones (ragged, prefill, engine step, ALiBi, tree): the checks of the caches (here), of the tables, bounds and
     scales of a step of B sequences (`tables`), and the moves to q's device (`on_device`).  Nothing here reads a device tensor on the host."""
 
-    def __init__(self, fn, q, q_fault, k_cache, v_cache, k_new, v_new, k_scale, v_scale):
-        """q_fault: the caller's verdict on q's rank, None or the message to refuse it with (raised where the rank checks stand)."""
+    def __init__(self, fn, q, q_fault, k_cache, v_cache, k_new, v_new, k_scale, v_scale, block_scales=None):
+        """q_fault: the caller's verdict on q's rank, None or the message to refuse it with (raised where the rank checks stand).
+        block_scales: (k_block_scale, v_block_scale) of MXFP4 caches (`flash_cosine_sim_attention_mxfp4_with_kvcache`), whose rows hold
+        dim_head / 2 code bytes."""
         self.q, self.k_cache, self.v_cache, self.k_new, self.k_scale, self.v_scale = q, k_cache, v_cache, k_new, k_scale, v_scale
         self.fp8 = k_cache.dtype in _FP8_TYPES or v_cache.dtype in _FP8_TYPES
+        if block_scales is None and torch.uint8 in (k_cache.dtype, v_cache.dtype):
+            raise TypeError(f"{fn} does not take torch.uint8 caches: MXFP4 caches (codes and block scales as bytes) are read by "
+                            "flash_cosine_sim_attention_mxfp4_with_kvcache")
+        if block_scales is not None:
+            _check_mx(q, k_cache, v_cache, k_new, v_new, block_scales)
         if self.fp8:
             if k_cache.dtype != v_cache.dtype:
                 raise TypeError(f"one fp8 cache and one {min(k_cache.dtype, v_cache.dtype, key=lambda d: d in _FP8_TYPES)} cache: k_cache and "
@@ -456,7 +463,7 @@ class _CacheCall:
         if (k_new is None) != (v_new is None):
             raise ValueError("k_new and v_new must be given together")
         H, self.Hk, self.D = q.shape[1], k_cache.shape[1], q.shape[-1]
-        if k_cache.shape[3] != self.D:
+        if k_cache.shape[3] != (self.D if block_scales is None else self.D // 2):
             raise ValueError("query, key, value dimensions must be the same")
         if self.Hk < 1 or H % self.Hk:
             raise ValueError(f"k/v heads must divide q heads ({H}), got {self.Hk}")
@@ -577,6 +584,156 @@ def flash_cosine_sim_attention_with_kvcache(q, k_cache, v_cache, k_new=None, v_n
         return _torch_ops.load().kvcache_window_forward(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, c.max_k, *tail,
                                                         window[0], window[1])
     return _torch_ops.load().kvcache_forward(q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, c.max_k, *tail)
+
+
+# ---- MXFP4 caches (OCP Microscaling Formats v1.0): e2m1 codes, two per byte, and one e8m0 scale byte per 32 features ----
+
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+_MX_SCALE_MIN, _MX_SCALE_MAX = 113, 139      # scale bytes are read clamped to this range: exponents -14 ... 12
+
+
+def mxfp4_quantize(x):
+    """x [..., D] (D a multiple of 32) -> (codes uint8 [..., D / 2], scales uint8 [..., D / 32]): the rule by which the append of
+    `flash_cosine_sim_attention_mxfp4_with_kvcache` quantises, and the tool for converting an existing cache.  Per 32-feature block, in
+    float32: amax = max |x|; e = clamp(floor(log2(amax)) - 2, -14, 12) (amax = 0: -14); scale byte = e + 127; code = e2m1_rne(clamp(x *
+    2^-e, -6, 6)), round to nearest with ties to the even code.  The low nibble of a byte is the even feature.  Any device."""
+    if x.shape[-1] % 32:
+        raise ValueError(f"the last dimension must be a multiple of 32, got {x.shape[-1]}")
+    blocks = x.detach().float().unflatten(-1, (-1, 32))
+    amax = blocks.abs().amax(-1)
+    e = ((amax.contiguous().view(torch.int32) >> 23) - 129).clamp(-14, 12)      # floor(log2(amax)) - 2 from amax's exponent field (0: -14; inf: 12)
+    y = (blocks * torch.exp2(-e.float()).unsqueeze(-1)).clamp(-6, 6)
+    a = y.abs()      # the e2m1 grid steps by 0.5 below 2, by 1 below 4 and by 2 above; torch.round rounds halves to even, which is the even code
+    code = torch.where(a < 2, torch.round(a * 2), torch.where(a < 4, torch.round(a) + 2, torch.round(a / 2) + 4)).to(torch.uint8)
+    code = (code | (torch.signbit(y).to(torch.uint8) << 3)).flatten(-2)
+    return code[..., 0::2] | (code[..., 1::2] << 4), (e + 127).to(torch.uint8)
+
+
+def mxfp4_dequantize(codes, scales, dtype=torch.float32):
+    """(codes uint8 [..., D / 2], scales uint8 [..., D / 32]) -> the values [..., D] in `dtype`: e2m1(code) * 2^(s - 127), the scale byte s
+    read clamped to [113, 139] as the kernels read it (every value is then exact in float16 and bfloat16).  Any device."""
+    if codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or codes.shape[:-1] != scales.shape[:-1] or codes.shape[-1] != 16 * scales.shape[-1]:
+        raise TypeError(f"codes uint8 [..., D / 2] and scales uint8 [..., D / 32] expected, got {codes.dtype} {tuple(codes.shape)} and "
+                        f"{scales.dtype} {tuple(scales.shape)}")
+    nib = torch.stack((codes & 15, codes >> 4), -1).flatten(-2).long()
+    mag = torch.tensor(_E2M1, dtype=torch.float32, device=codes.device)[nib & 7]
+    val = torch.where((nib & 8) != 0, -mag, mag).unflatten(-1, (-1, 32))
+    s = scales.clamp(_MX_SCALE_MIN, _MX_SCALE_MAX).float() - 127
+    return (val * torch.exp2(s).unsqueeze(-1)).flatten(-2).to(dtype)
+
+
+def _check_mx(q, k_cache, v_cache, k_new, v_new, block_scales):
+    """dtypes and shapes of MXFP4 caches and their block scales, before the checks every cache call shares"""
+    D = q.shape[-1]
+    if k_cache.dtype != torch.uint8 or v_cache.dtype != torch.uint8:
+        raise TypeError(f"MXFP4 caches are torch.uint8 (two e2m1 codes per byte), got {k_cache.dtype} and {v_cache.dtype}")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError(f"MXFP4 caches take float16 or bfloat16 q, k_new and v_new, got a {q.dtype} q")
+    for name, t in (("k_new", k_new), ("v_new", v_new)):
+        if t is not None and t.dtype != q.dtype:
+            raise TypeError(f"{name} must have q's dtype ({q.dtype}), got {t.dtype}")
+    if D not in (32, 64, 96, 128):
+        raise ValueError(f"MXFP4 caches take dim_head 32, 64, 96 or 128 (whole blocks of 32 features), got {D}")
+    for name, t, cache in (("k_block_scale", block_scales[0], k_cache), ("v_block_scale", block_scales[1], v_cache)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+            raise TypeError(f"{name} must be a torch.uint8 tensor (e8m0 scale bytes)")
+        if cache.dim() == 4 and tuple(t.shape) != (*cache.shape[:3], D // 32):
+            raise ValueError(f"{name} must be {(*cache.shape[:3], D // 32)}: the cache's leading dimensions and dim_head / 32 scale bytes, got "
+                             f"{tuple(t.shape)}")
+        if t.device != cache.device:
+            raise ValueError(f"{name} is on {t.device} but its cache is on {cache.device}")
+
+
+def _mx_append_cpu(caches, news, starts, lens, capacity, block_table):
+    """the append of the CPU path: the rows news[i][starts[b]:starts[b + 1]] ([rows, Hk, ...] bytes) go to the positions from lens[b] on of
+    caches[i], through the block table when the cache is paged; positions at or beyond the capacity are dropped"""
+    page = caches[0].shape[2]
+    for b, n0 in enumerate(lens):
+        for i in range(starts[b + 1] - starts[b]):
+            pos = n0 + i
+            if pos >= capacity:
+                break
+            blk, off = (b, pos) if block_table is None else (int(block_table[b, pos // page]), pos % page)
+            for cache, new in zip(caches, news):
+                cache[blk, :, off] = new[starts[b] + i]
+
+
+def flash_cosine_sim_attention_mxfp4_with_kvcache(q, k_cache, v_cache, k_block_scale, v_block_scale, cu_seqlens_q=None, k_new=None, v_new=None,
+                                                  cache_seqlens=None, block_table=None, max_seqlen_q=None, max_seqlen_k=None, scale=8, groups=1,
+                                                  causal=False, l2norm_qk=True, return_lse=False, window_size=(-1, -1)):
+    """Decoding against MXFP4 caches (OCP Microscaling Formats v1.0), equal-N or ragged, with an append that quantises.  Forward only.
+
+    A position of a dim_head = 128 head takes 64 + 4 bytes instead of the 256 of a 16-bit cache (128 + a per-head scale for float8_e4m3fn).
+    k_cache, v_cache: torch.uint8 [B, Hk, capacity, D / 2] or, with a block_table, paged [num_blocks, Hk, page_size, D / 2]: two e2m1 codes
+    per byte (sign, two exponent bits, one mantissa bit: +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}), the low nibble the even feature.
+    k_block_scale, v_block_scale: torch.uint8 with the caches' leading dimensions (the same pool, the same block_table) and a last
+    dimension of D / 32: one e8m0 byte s per 32 consecutive features, meaning 2^(s - 127) and read CLAMPED to [113, 139].  Inside that range
+    every value code * 2^(s - 127) is exact in float16 and bfloat16, so the result is what `flash_cosine_sim_attention_with_kvcache` (q
+    [B, H, N, D]) or, with cu_seqlens_q, `flash_cosine_sim_attention_varlen_with_kvcache` (q packed [total_q, H, D]) computes on a 16-bit
+    cache holding those values, with those calls' strides, pages, tables, bounds, causal alignment, window_size and return_lse; rows
+    without a visible key give 0 (lse -inf).  Host tables are validated, device tables are trusted and clamped; with device tables the call
+    does not synchronise and can be captured in a graph.
+    q, k_new, v_new: float16 or bfloat16; D 32, 64, 96 or 128; groups: 1, or any count whose groups have a multiple of 8 features.
+    k_new, v_new ([B, Hk, N_new, D], or packed [total_q, Hk, D]) are quantised as `mxfp4_quantize` states and written -- codes and scale
+    bytes -- at [cache_seqlens[b], ...) before attention reads the caches.  With l2norm_qk a key only contributes its direction, and a
+    per-block power-of-two scale keeps every block of that direction at full e2m1 resolution.  `mxfp4_quantize` / `mxfp4_dequantize`
+    convert an existing cache.  CPU tensors take a forward-only path: dequantise, then `cpu.py` (host tables).
+    Not taken here: the prefill, step, tree, ALiBi, rotary and shared-prefix calls (those functions refuse uint8 caches), e5m2, MXFP6 /
+    MXFP8 caches, fp4 queries."""
+    fn = "flash_cosine_sim_attention_mxfp4_with_kvcache"
+    _check_return_lse(return_lse)
+    window = _window(window_size)
+    ragged = cu_seqlens_q is not None
+    want = 3 if ragged else 4
+    q_fault = None if q.dim() == want else (f"q must be a packed [total_q, heads, dim_head] tensor with cu_seqlens_q and [B, H, N, D] without, "
+                                            f"got {tuple(q.shape)}")
+    c = _CacheCall(fn, q, q_fault, k_cache, v_cache, k_new, v_new, None, None, block_scales=(k_block_scale, v_block_scale))
+    D = c.D
+    if l2norm_qk and groups != 1 and (groups < 1 or D % groups or (D // groups) % 8):
+        raise ValueError(f"MXFP4 caches take groups = 1 or groups of a multiple of 8 features, got groups = {groups} at dim_head {D} "
+                         "(flash_cosine_sim_attention_with_kvcache with float8_e4m3fn caches takes every group count)")
+    if ragged:
+        if not isinstance(cu_seqlens_q, torch.Tensor) or cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.dim() != 1 or cu_seqlens_q.numel() < 1:
+            raise TypeError("cu_seqlens_q must be a 1-D int32 tensor of sequences + 1 entries")
+        total_q, B, new_shape = q.shape[0], cu_seqlens_q.numel() - 1, (q.shape[0], c.Hk, D)
+        if cu_seqlens_q.device.type == "cpu":
+            _check_host_cu("cu_seqlens_q", cu_seqlens_q, total_q, None)
+    else:
+        B, new_shape = q.shape[0], None
+    if k_new is not None and (k_new.shape != v_new.shape or (tuple(k_new.shape) != new_shape if ragged else
+                                                             k_new.dim() != 4 or (k_new.shape[0], k_new.shape[1], k_new.shape[3]) != (B, c.Hk, D))):
+        raise ValueError(f"k_new / v_new must be {'packed like q, ' + str(list(new_shape)) if ragged else f'[{B}, {c.Hk}, N_new, {D}]'}, got "
+                         f"{tuple(k_new.shape)} and {tuple(v_new.shape)}")
+    if max_seqlen_q is not None and (int(max_seqlen_q) != max_seqlen_q or max_seqlen_q < 0):
+        raise ValueError(f"max_seqlen_q must be a non-negative integer, got {max_seqlen_q}")
+    appends = k_new is not None and (ragged or k_new.shape[2] > 0)
+    c.tables(B, cu_seqlens_q, appends, cache_seqlens, block_table, max_seqlen_k)
+    if q.device.type == "cpu":
+        if c.counts is None or (cache_seqlens is not None and c.lens is None):
+            raise ValueError("CPU tensors take host cu_seqlens_q and cache_seqlens tables")
+        new_q = None
+        lens = c.lens if c.lens is not None else [c.capacity - (0 if ragged else c.appended[0])] * B
+        if k_new is not None:      # quantise once: the bytes go into the caller's caches, their values into the dense path's append
+            (kc, ks), (vc, vs) = mxfp4_quantize(k_new), mxfp4_quantize(v_new)
+            new_q = (mxfp4_dequantize(kc, ks, q.dtype), mxfp4_dequantize(vc, vs, q.dtype))
+            rows = (kc, ks, vc, vs) if ragged else tuple(t.transpose(1, 2).flatten(0, 1) for t in (kc, ks, vc, vs))
+            starts = cu_seqlens_q.tolist() if ragged else [b * k_new.shape[2] for b in range(B + 1)]
+            _mx_append_cpu((k_cache, k_block_scale, v_cache, v_block_scale), rows, starts, lens, c.capacity, block_table)
+        dense = (mxfp4_dequantize(k_cache, k_block_scale, q.dtype), mxfp4_dequantize(v_cache, v_block_scale, q.dtype))
+        kw = dict(scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, window_size=window, return_lse=bool(return_lse))
+        if ragged:
+            return _cpu.attention_forward_kvcache_varlen_cpu(q.detach(), *dense, cu_seqlens_q, *(new_q or (None, None)), lens, block_table, **kw)
+        return _cpu.attention_forward_kvcache_cpu(q.detach(), *dense, *(new_q or (None, None)), lens, block_table, **kw)
+    if ragged and q.shape[0] == 0:
+        return _empty_result(q, return_lse)
+    max_q = 0 if not ragged else (q.shape[0] if max_seqlen_q is None else min(int(max_seqlen_q), q.shape[0]))
+    cu_q = cu_seqlens_q.to(q.device, non_blocking=True) if ragged else None
+    k_cache, v_cache, cache_seqlens, block_table = c.on_device()
+    _torch_ops.load()
+    o, lse = torch.ops.fcsa_mx.kvcache_mxfp4_forward(q, k_cache, v_cache, k_block_scale, v_block_scale, cu_q, k_new, v_new, cache_seqlens, block_table,
+                                                     max_q, c.max_k, float(scale), bool(causal), bool(l2norm_qk), int(groups), window[0], window[1],
+                                                     bool(return_lse))
+    return (o, lse) if return_lse else o
 
 
 def _step_count(name, value):

@@ -514,6 +514,46 @@ int    fcsa_forward_kvcache_rotary(const fcsa_forward_args* args, const fcsa_kvc
                                    const fcsa_kvcache_quant* quant, const fcsa_window* window, const fcsa_kvcache_step* step,
                                    const fcsa_rotary* rotary, const fcsa_lse_out* lse_out);
 
+/* Decoding against an MXFP4 cache (OCP Microscaling Formats v1.0): fcsa_forward_kvcache[_window] and fcsa_forward_kvcache_varlen / _lse
+ * against caches of 4-bit codes with a shared scale per 32 features, with an append that quantises (additive: no existing struct changes
+ * and FCSA_ABI_VERSION stays 4).  A position of a dim_head = 128 head takes 64 + 4 bytes instead of 256.
+ * The format.  A code is e2m1 -- sign, two exponent bits, one mantissa bit: +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}; two codes share a byte, the
+ * LOW nibble being the even feature.  One e8m0 byte s covers 32 consecutive features of one cache position and means 2^(s - 127); the
+ * library reads it CLAMPED to [113, 139] (exponents -14 ... 12).  In that range every cache value e2m1(code) * 2^(s - 127) -- 2^-15 at the
+ * smallest, 24576 at the largest -- is exact in float16 and in bfloat16, so the result is what the 16-bit call computes on those values:
+ * regimes, causal alignment, window rule, o = 0 and lse = -inf for a row without a visible key, and the clamping of lengths and block ids
+ * are unchanged.
+ *   cache->k_cache / v_cache : the codes, [B, Hk, capacity, D / 2] bytes, or paged [num_blocks, Hk, page_size, D / 2]; ELEMENT strides,
+ *                              an element being one byte: rows 16-byte aligned, last dim contiguous
+ *   mx->k_block_scale / v_block_scale : the scale bytes, the same leading dims and block_table with a last dim of D / 32; any byte strides
+ *                              with the last dim contiguous
+ *   p.dtype   : the type of q, o, k_new and v_new, FCSA_F16 or FCSA_BF16 (FCSA_F32: FCSA_ERR_UNSUPPORTED)
+ *   p.dim_head: 32, 64, 96 or 128 (16: FCSA_ERR_UNSUPPORTED)
+ *   p.groups  : with l2norm_qk, 1 or any count whose groups have a multiple of 8 features (others: FCSA_ERR_UNSUPPORTED;
+ *               fcsa_forward_kvcache_quant takes them)
+ *   seqs      : NULL: equal N, as fcsa_forward_kvcache; set: a ragged step, as fcsa_forward_kvcache_varlen (packed views, new_len a flag)
+ *   window    : NULL, or as in fcsa_forward_kvcache_window
+ *   lse_out   : NULL, or as in fcsa_forward_kvcache_lse
+ *   workspace : >= fcsa_forward_kvcache_mx_workspace_bytes() bytes, 256-byte aligned (the split rule counts keys: what the 16-bit call needs)
+ * The append quantises, per 32-feature block of a new row, in float32: amax = max |x|; e = clamp(floor(log2(amax)) - 2, -14, 12), where
+ * floor(log2) is amax's exponent field (amax = 0: -14); scale byte = e + 127; code = e2m1_rne(clamp(x * 2^-e, -6, 6)) -- round to nearest,
+ * ties to the even code, saturating.  NaN inputs are unspecified.  Slots at or beyond the capacity are dropped and cache_seqlens is not
+ * advanced, as in fcsa_forward_kvcache.
+ * Launches: "kv_append_mx" (when rows are appended), "decode_mx" and the 16-bit call's combine ("decode_combine[_lse][_ragged]"): the V
+ * scales are applied as the codes are read.
+ * Not offered with such a cache: the prefill, step, tree, ALiBi, rotary and shared-prefix calls; other element formats (e5m2 scales,
+ * MXFP6, MXFP8); fp4 queries and the scaled MFMA instructions. */
+#define FCSA_CACHE_MXFP4 2            /* fcsa_kvcache_mx.format */
+typedef struct fcsa_kvcache_mx {
+  int32_t      format;                /* FCSA_CACHE_MXFP4 (anything else: FCSA_ERR_UNSUPPORTED) */
+  fcsa_tensor  k_block_scale, v_block_scale;
+} fcsa_kvcache_mx;
+int    fcsa_forward_kvcache_mx(const fcsa_forward_args* args, const fcsa_kvcache* cache, const fcsa_kvcache_mx* mx, const fcsa_varlen* seqs,
+                               const fcsa_window* window, const fcsa_lse_out* lse_out);
+/* 0 for a call fcsa_forward_kvcache_mx refuses as unsupported (mx NULL, another format, FCSA_F32, an unsupported dim_head or group count) */
+size_t fcsa_forward_kvcache_mx_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* cache, const fcsa_kvcache_mx* mx,
+                                               const fcsa_varlen* seqs, const fcsa_window* window);
+
 /* The same linear position bias in the training kernels, forward and backward: fcsa_forward_window / fcsa_backward_window with one more
  * argument, the slopes (additive: no existing struct changes and FCSA_ABI_VERSION stays 4).  A model trained through these entries is
  * served unchanged by fcsa_forward_kvcache_alibi: the definition is the same.
