@@ -108,7 +108,8 @@ EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fc
            "fcsa_forward_kvcache_step", "fcsa_forward_kvcache_step_workspace_bytes",
            "fcsa_forward_kvcache_tree", "fcsa_kvcache_compact", "fcsa_forward_kvcache_alibi",
            "fcsa_forward_alibi", "fcsa_backward_alibi", "fcsa_forward_alibi_workspace_bytes", "fcsa_backward_alibi_workspace_bytes",
-           "fcsa_forward_kvcache_rotary", "fcsa_forward_kvcache_mx", "fcsa_forward_kvcache_mx_workspace_bytes")
+           "fcsa_forward_kvcache_rotary", "fcsa_forward_kvcache_mx", "fcsa_forward_kvcache_mx_workspace_bytes",
+           "fcsa_forward_kvcache_mx_prefill")
 
 _lib = None
 
@@ -240,6 +241,9 @@ def load():
         lib.fcsa_forward_kvcache_mx_workspace_bytes.argtypes = [C.POINTER(Problem), C.POINTER(KvCache),
                                                                 C.POINTER(KvCacheMx), C.POINTER(Varlen), C.POINTER(Window)]
         lib.fcsa_forward_kvcache_mx_workspace_bytes.restype = C.c_size_t
+    if hasattr(lib, "fcsa_forward_kvcache_mx_prefill"):      # (likewise: an FCSA_LIB build from before the MXFP4 chunk kernel)
+        lib.fcsa_forward_kvcache_mx_prefill.argtypes = lib.fcsa_forward_kvcache_mx.argtypes
+        lib.fcsa_forward_kvcache_mx_prefill.restype = C.c_int
     if hasattr(lib, "fcsa_forward_kvcache_tree"):      # (likewise: an FCSA_LIB build from before tree attention)
         lib.fcsa_forward_kvcache_tree.argtypes = [C.POINTER(ForwardArgs), C.POINTER(KvCache), C.POINTER(Varlen), C.POINTER(KvCacheQuant),
                                                   C.POINTER(TreeMask), C.POINTER(LseOut)]

@@ -101,10 +101,11 @@ def _register_fakes():
         def _(q, *args):
             return q.new_empty(q.shape), q.new_empty(q.shape[:-1], dtype=torch.float32)
 
-    # an MXFP4 cache (namespace fcsa_mx): the lse is empty unless asked for
-    @torch.library.register_fake("fcsa_mx::kvcache_mxfp4_forward")
-    def _(q, *args):
-        return q.new_empty(q.shape), q.new_empty(q.shape[:-1] if args[-1] else (0,), dtype=torch.float32)
+    # an MXFP4 cache (namespace fcsa_mx), decode and chunk ops alike: the lse is empty unless asked for
+    for op in ("fcsa_mx::kvcache_mxfp4_forward", "fcsa_mx::kvcache_mxfp4_prefill_forward"):
+        @torch.library.register_fake(op)
+        def _(q, *args):
+            return q.new_empty(q.shape), q.new_empty(q.shape[:-1] if args[-1] else (0,), dtype=torch.float32)
 
     @torch.library.register_fake("fcsa_tree::kvcache_compact")
     def _(k_cache, v_cache, cache_seqlens, accepted, num_accepted, block_table):

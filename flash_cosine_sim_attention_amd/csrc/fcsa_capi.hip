@@ -1128,6 +1128,10 @@ int chunk_launch(const LaunchName& plain, const DecodeCall& c, fcsa::DecodeForm 
   dp.ws_ml = nullptr;
   const fcsa::DecodeLseOut lo = c.lse != nullptr ? lse_view(*c.lse, true) : fcsa::DecodeLseOut{};
   const fcsa::DecodeLseOut* lse = c.lse != nullptr ? &lo : nullptr;
+  if (c.mx != nullptr) {
+    const fcsa::DecodeMx mx = mx_view(*c.mx);
+    return timed("prefill_mx", "prefill (mxfp4)", s, [&] { return fcsa::launch_prefill_mx(c.a->p.dtype, c.a->p.dim_head, form, dp, mx, lse, s); });
+  }
   if (c.rotary != nullptr) {
     const LaunchName& n = kRotaryPrefillName[form.fp8];
     const fcsa::DecodeRotary ro = rotary_view(*c.rotary);
@@ -1184,18 +1188,23 @@ int decode_call(const DecodeCall& c) {
 
 // A prompt chunk against the cache (fcsa_forward_kvcache_prefill): the ragged step's checks, its append with the parameter block the ragged
 // call fills, then one launch of the multi-wave kernel (fcsa_prefill.hip) with 128-row slots, one split and no workspace.
+// c.mx (fcsa_forward_kvcache_mx_prefill): the ragged MXFP4 call's checks (check_mx behind check_kvcache_varlen), its quantising append, and
+// the chunk kernel of fcsa_prefill_mx.hip; a window is part of that entry point's argument list and is refused where it hides a key.
 int prefill_call(const DecodeCall& c) {
+  const char* who = c.mx != nullptr ? "kvcache_mx_prefill" : "kvcache_prefill";
+  const char* other = c.mx != nullptr ? "fcsa_forward_kvcache_mx" : "fcsa_forward_kvcache_varlen";
   if (int rc = check_kvcache_varlen(c)) return rc;
   const fcsa_problem& p = c.a->p;
   if (!has_chunk_kernel(p))
-    return p.dtype == FCSA_F32
-               ? fail(FCSA_ERR_UNSUPPORTED, "kvcache_prefill: float32 is not supported (f16 or bf16; fcsa_forward_kvcache_varlen takes float32)")
-               : fail(FCSA_ERR_UNSUPPORTED, "kvcache_prefill: dim_head %d is not supported (64 or 128; fcsa_forward_kvcache_varlen takes the others)", p.dim_head);
+    return p.dtype == FCSA_F32 ? fail(FCSA_ERR_UNSUPPORTED, "%s: float32 is not supported (f16 or bf16; %s takes float32)", who, other)
+                               : fail(FCSA_ERR_UNSUPPORTED, "%s: dim_head %d is not supported (64 or 128; %s takes the others)", who, p.dim_head, other);
+  if (c.w != nullptr && (c.w->left >= 0 || (!p.causal && c.w->right >= 0)))
+    return fail(FCSA_ERR_UNSUPPORTED, "%s: a window (%d, %d) that hides keys is not supported (%s takes windows)", who, c.w->left, c.w->right, other);
   const int G = p.heads / p.kv_heads;
   const int64_t slots = fcsa::prefill_slots(c.seqs->total_q, std::max(p.batch, 0), G, fcsa::kPrefillRows);
-  if (slots * p.kv_heads > INT32_MAX) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_prefill: grid above 2^31 workgroups");
+  if (slots * p.kv_heads > INT32_MAX) return fail(FCSA_ERR_UNSUPPORTED, "%s: grid above 2^31 workgroups", who);
   if (p.batch == 0 || c.seqs->total_q == 0) return FCSA_OK;      // no packed row: nothing to append, nothing to write
-  if (p.heads > 0 && c.lse != nullptr && c.lse->lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_prefill: lse: null pointer");
+  if (p.heads > 0 && c.lse != nullptr && c.lse->lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "%s: lse: null pointer", who);
   const DecodeWindow win = decode_window(p, *c.kv, true, nullptr);
   const fcsa::DecodeStepParams dp = decode_params(c, win, decode_plan(p, *c.kv, c.seqs, win.reach()));
   const fcsa::DecodeForm form = {false, true};
@@ -1338,6 +1347,18 @@ size_t fcsa_forward_kvcache_mx_workspace_bytes(const fcsa_problem* p, const fcsa
                                                const fcsa_window* w) {
   if (p == nullptr || mx == nullptr || mx_supported(*p, *mx) != FCSA_OK) return 0;
   return decode_workspace_bytes(p, kv, seqs, w, true);
+}
+
+// Prompt chunks against an MXFP4 cache: the ragged MXFP4 call's description on prefill_call -- its checks and its quantising append, then the
+// multi-wave kernel of fcsa_prefill_mx.hip with 128-row slots, one split and no workspace.
+int fcsa_forward_kvcache_mx_prefill(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_kvcache_mx* mx, const fcsa_varlen* seqs,
+                                    const fcsa_window* w, const fcsa_lse_out* lse) {
+  if (a == nullptr || kv == nullptr || mx == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_mx_prefill: null argument");
+  if (seqs == nullptr)
+    return fail(FCSA_ERR_INVALID_ARG, "kvcache_mx_prefill: seqs is NULL: packed queries only (fcsa_forward_kvcache_mx takes equal-N calls)");
+  DecodeCall c{a, kv, seqs, nullptr, w, lse};
+  c.mx = mx;
+  return prefill_call(c);
 }
 
 // ---- the decode calls with the rows' log-sum-exp (fcsa_forward_kvcache_lse), and merging attention states (fcsa_merge_states) ----------

@@ -17,97 +17,15 @@
 //                         inside the l2norm group) and rounded once to the type, as 16-bit keys are; without it the codes go straight to
 //                         the type (v_cvt_scalef32_pk_{f16,bf16}_fp4).  V: a lane's 16-byte chunk is one MX block of one key; it is
 //                         converted straight to the type on the way into the LDS block that pv_block reads transposed.
+// The conversions, the word loads and mx_group_normalise are fcsa_mx_common.cuh's, shared with the chunk kernel (fcsa_prefill_mx.hip).
 #include "fcsa_common.cuh"
 #include "fcsa_decode_common.cuh"
+#include "fcsa_mx_common.cuh"
 
 #include <type_traits>
 
 namespace fcsa {
 namespace {
-
-// 2^(s - 127) for the scale byte s, read clamped to [113, 139]
-FCSA_DEV float mx_scale(uint32_t s) { return as_f32(min(max(s, 113u), 139u) << 23); }
-
-// the two codes of byte B of `w` times `s` -> a packed pair of T
-template <typename T, int B> FCSA_DEV uint32_t mx_pair(uint32_t w, float s) {
-  if constexpr (std::is_same_v<T, F16>) return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, s, B));
-  else return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, s, B));
-}
-// the eight codes of one word (eight consecutive features) times `s`: as eight elements of T (exact), or as float32
-template <typename T> FCSA_DEV u32x4 mx_word(uint32_t w, float s) {
-  return u32x4{mx_pair<T, 0>(w, s), mx_pair<T, 1>(w, s), mx_pair<T, 2>(w, s), mx_pair<T, 3>(w, s)};
-}
-FCSA_DEV void mx_word_f32(uint32_t w, float s, float (&x)[8]) {
-  const f32x2 a = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, s, 0), b = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, s, 1);
-  const f32x2 c = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, s, 2), d = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, s, 3);
-  x[0] = a[0]; x[1] = a[1]; x[2] = b[0]; x[3] = b[1]; x[4] = c[0]; x[5] = c[1]; x[6] = d[0]; x[7] = d[1];
-}
-
-// NT words from a 4 NT-byte aligned address: one load of that width (three words: a pair and one)
-template <int NT> FCSA_DEV void load_words(const char* src, uint32_t (&w)[NT]) {
-  if constexpr (NT == 4) {
-    const u32x4 v = *reinterpret_cast<const u32x4*>(src);
-    w[0] = v[0]; w[1] = v[1]; w[2] = v[2]; w[3] = v[3];
-  } else if constexpr (NT == 2) {
-    const u32x2 v = *reinterpret_cast<const u32x2*>(src);
-    w[0] = v[0]; w[1] = v[1];
-  } else {
-#pragma unroll
-    for (int t = 0; t < NT; ++t) w[t] = *reinterpret_cast<const uint32_t*>(src + 4 * t);
-  }
-}
-
-// Grouped l2norm of a row in the quarter layout -- lane g = lane >> 4 of the row's four lanes holds the features [g Q, (g + 1) Q), Q = 8 NT,
-// as NT units of eight: x *= 1 / max(||group||, 1e-12), the l2norm kernel's formula.  gs = features per group: D, or a multiple of 8
-// (mx_groups_ok).  One group: the sum crosses the four lanes; whole quarters per group: it crosses one or no lane pair; whole groups per
-// quarter: it stays in the lane; anything else (D = 96 with 16 or 32 features per group, which straddle the quarters of 24): every lane
-// collects the row's 4 NT unit sums and adds those of its units' groups.  gs is uniform: every lane runs every shuffle.
-template <int NT> FCSA_DEV void mx_group_normalise(float (&x)[NT][8], int gs, int lane) {
-  constexpr int Q = 8 * NT;
-  const int g = lane >> 4;
-  float u[NT], ss[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    u[t] = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) u[t] += x[t][e] * x[t][e];
-  }
-  if (gs % Q == 0) {
-    float s = 0.f;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) s += u[t];
-    if (gs >= 2 * Q) s += __shfl_xor(s, 16, 64);
-    if (gs >= 4 * Q) s += __shfl_xor(s, 32, 64);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) ss[t] = s;
-  } else if (Q % gs == 0) {
-    const int m = gs / 8;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      ss[t] = 0.f;
-#pragma unroll
-      for (int t2 = 0; t2 < NT; ++t2) ss[t] += t2 / m == t / m ? u[t2] : 0.f;
-    }
-  } else {
-    const int m = gs / 8;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) ss[t] = 0.f;
-#pragma unroll
-    for (int h = 0; h < 4; ++h)
-#pragma unroll
-      for (int t2 = 0; t2 < NT; ++t2) {
-        const float v = __shfl(u[t2], (lane & 15) + 16 * h, 64);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) ss[t] += (h * NT + t2) / m == (g * NT + t) / m ? v : 0.f;
-      }
-  }
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const float r = 1.f / fmaxf(sqrtf(ss[t]), 1e-12f);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) x[t][e] *= r;
-  }
-}
 
 // What a lane holds of a 32-key block.  K: per 16-key half its quarter of key c -- NT = D / 32 words of codes and the scale bytes of the
 // MX blocks they lie in (one; D = 96: a quarter of 24 features can touch two blocks, so one per word).  V: 16-byte chunk c = lane + 64 t of

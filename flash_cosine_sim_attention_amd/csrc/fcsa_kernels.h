@@ -259,6 +259,12 @@ struct DecodeMx {
 };
 hipError_t launch_kv_append_mx(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeMx& mx, hipStream_t s);
 hipError_t launch_decode_mx(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeMx& mx, hipStream_t s);
+// A prompt chunk against an MXFP4 cache (fcsa_forward_kvcache_mx_prefill; csrc/fcsa_prefill_mx.hip): launch_prefill's block -- slots =
+// fcsa::prefill_slots(total_q, B, G, kPrefillRows), one split, no workspace -- on the multi-wave kernel whose LDS stage is filled from codes
+// and scale bytes (DecodeMx, the second kernel argument).  f.ragged only (no fp8, no step form), f16 / bf16, D = 64 / 128, l2norm groups of
+// mx_groups_ok; hipErrorInvalidValue otherwise.  One kernel writes o and, where lse is not nullptr, the rows' log-sum-exp.  The append
+// before it is launch_kv_append_mx.
+hipError_t launch_prefill_mx(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeMx& mx, const DecodeLseOut* lse, hipStream_t s);
 
 // Merging attention states (fcsa_merge_states, csrc/fcsa_merge.hip): S states (o_s, lse_s) of the rows [n0, n1, n2] -> (o, lse).  o views
 // carry BYTE strides, lse views ELEMENT strides.

@@ -83,7 +83,9 @@ namespace {
   X(forward_kvcache_rotary, fcsa_forward_kvcache_rotary, false)                           \
   /* decoding against an MXFP4 cache */                                                   \
   X(forward_kvcache_mx, fcsa_forward_kvcache_mx, false)                                   \
-  X(forward_kvcache_mx_ws, fcsa_forward_kvcache_mx_workspace_bytes, false)
+  X(forward_kvcache_mx_ws, fcsa_forward_kvcache_mx_workspace_bytes, false)         \
+  /* prompt chunks against an MXFP4 cache */                                              \
+  X(forward_kvcache_mx_prefill, fcsa_forward_kvcache_mx_prefill, false)
 
 struct Abi {
 #define X(member, symbol, required) decltype(&symbol) member = &symbol;
@@ -767,7 +769,7 @@ Tensor varlen_window_attention_autograd(const Tensor& q, const Tensor& k, const 
 //
 // One description of a call, CacheCall: every op function fills the members it has and hands it to kvcache_call, which runs the checks
 // (cache_checks), fills the library's structs (fill_lib_call) and dispatches through the one table of entry points (kEntries).
-enum class Route { Plain, Prefill, Step, Tree, Alibi, Rotary, Mx };
+enum class Route { Plain, Prefill, Step, Tree, Alibi, Rotary, Mx, MxPrefill };
 
 struct CacheCall {
   // what every op has
@@ -786,7 +788,7 @@ struct CacheCall {
   const Tensor *k_block_scale = nullptr, *v_block_scale = nullptr;          // Mx: the scale bytes of an MXFP4 cache (its codes as uint8 tensors)
   bool ragged() const { return cu_q != nullptr; }
   bool fp8() const { return k_scale != nullptr; }
-  bool mx() const { return route == Route::Mx; }
+  bool mx() const { return route == Route::Mx || route == Route::MxPrefill; }      // MxPrefill: the ragged Mx call on the chunk kernel
 };
 
 const Tensor* ptr(const optional<Tensor>& t) { return t.has_value() ? &*t : nullptr; }
@@ -1039,7 +1041,7 @@ struct EntryPoint {
   size_t (*workspace)(const LibCall&);      // null: that of the call without the lse
   int (*run)(const LibCall&);
 };
-enum Entry { kKvcache, kWindow, kQuant, kVarlen, kLse, kPrefill, kStep, kTree, kAlibi, kRotary, kMx };
+enum Entry { kKvcache, kWindow, kQuant, kVarlen, kLse, kPrefill, kStep, kTree, kAlibi, kRotary, kMx, kMxPrefill };
 const EntryPoint kEntries[] = {
     /* kKvcache */ {"fcsa_forward_kvcache", "flash_cosine_sim_attention_with_kvcache",
                     [] { return g_abi.forward_kvcache != nullptr && g_abi.forward_kvcache_ws != nullptr; },
@@ -1079,12 +1081,15 @@ const EntryPoint kEntries[] = {
      [] { return g_abi.forward_kvcache_mx != nullptr && g_abi.forward_kvcache_mx_ws != nullptr; },
      [](const LibCall& l) { return g_abi.forward_kvcache_mx_ws(&l.a.p, &l.kv, &l.mx, l.ragged ? &l.seqs : nullptr, l.win); },
      [](const LibCall& l) { return g_abi.forward_kvcache_mx(&l.a, &l.kv, &l.mx, l.ragged ? &l.seqs : nullptr, l.win, l.lo.lse != nullptr ? &l.lo : nullptr); }},
+    /* kMxPrefill: ragged only, no workspace */ {"fcsa_forward_kvcache_mx_prefill", "flash_cosine_sim_attention_mxfp4_prefill_with_kvcache",
+     [] { return g_abi.forward_kvcache_mx_prefill != nullptr; }, [](const LibCall&) { return (size_t)0; },
+     [](const LibCall& l) { return g_abi.forward_kvcache_mx_prefill(&l.a, &l.kv, &l.mx, &l.seqs, l.win, l.lo.lse != nullptr ? &l.lo : nullptr); }},
 };
 
 // the entry point of a Plain call without the lse: by the ragged / fp8 / window facts
 Entry plain_entry(const CacheCall& c) { return c.ragged() ? kVarlen : c.fp8() ? kQuant : c.win != nullptr ? kWindow : kKvcache; }
-constexpr Entry kOfRoute[] = {kKvcache /* Plain: by the facts instead */, kPrefill, kStep, kTree, kAlibi, kRotary, kMx};      // in Route's order
-static_assert(sizeof(kEntries) / sizeof(kEntries[0]) == kMx + 1 && sizeof(kOfRoute) / sizeof(kOfRoute[0]) == (int)Route::Mx + 1,
+constexpr Entry kOfRoute[] = {kKvcache /* Plain: by the facts instead */, kPrefill, kStep, kTree, kAlibi, kRotary, kMx, kMxPrefill};      // in Route's order
+static_assert(sizeof(kEntries) / sizeof(kEntries[0]) == kMxPrefill + 1 && sizeof(kOfRoute) / sizeof(kOfRoute[0]) == (int)Route::MxPrefill + 1,
               "kEntries has one row per Entry, in its order, and kOfRoute one entry per Route");
 Entry entry_of(const CacheCall& c) { return c.route != Route::Plain ? kOfRoute[(int)c.route] : c.lse ? kLse : plain_entry(c); }
 // a call needs its own entry point and those of the calls it is built on
@@ -1248,6 +1253,24 @@ std::tuple<Tensor, Tensor> kvcache_mxfp4_forward(const Tensor& q, const Tensor& 
   const OptWin win(left, right);
   c.win = win.ptr(); c.cu_q = ptr(cu_seqlens_q); c.max_seqlen_q = max_seqlen_q; c.lse = return_lse;
   c.route = Route::Mx; c.k_block_scale = &k_block_scale; c.v_block_scale = &v_block_scale;
+  auto [o, lse] = kvcache_call(c);
+  return {o, return_lse ? lse : at::empty({0}, q.options().dtype(at::kFloat))};
+}
+
+// Prompt chunks against an MXFP4 cache (kvcache_mxfp4_prefill_forward): kvcache_mxfp4_forward's ragged step -- the same arguments, checks
+// and results -- through fcsa_forward_kvcache_mx_prefill, the multi-wave chunk kernel.  cu_seqlens_q is required (the schema is that op's).
+std::tuple<Tensor, Tensor> kvcache_mxfp4_prefill_forward(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& k_block_scale,
+                                                         const Tensor& v_block_scale, const optional<Tensor>& cu_seqlens_q,
+                                                         const optional<Tensor>& k_new, const optional<Tensor>& v_new,
+                                                         const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table,
+                                                         int64_t max_seqlen_q, int64_t max_seqlen_k, double scale, bool causal, bool l2norm_qk,
+                                                         int64_t groups, int64_t left, int64_t right, bool return_lse) {
+  TORCH_CHECK_VALUE(cu_seqlens_q.has_value(), "kvcache_mxfp4_prefill_forward takes packed queries with cu_seqlens_q (kvcache_mxfp4_forward takes "
+                    "equal-N calls)");
+  CacheCall c{q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups};
+  const OptWin win(left, right);
+  c.win = win.ptr(); c.cu_q = ptr(cu_seqlens_q); c.max_seqlen_q = max_seqlen_q; c.lse = return_lse;
+  c.route = Route::MxPrefill; c.k_block_scale = &k_block_scale; c.v_block_scale = &v_block_scale;
   auto [o, lse] = kvcache_call(c);
   return {o, return_lse ? lse : at::empty({0}, q.options().dtype(at::kFloat))};
 }
@@ -1780,8 +1803,15 @@ TORCH_LIBRARY(fcsa_mx, m) {
   m.def("kvcache_mxfp4_forward(Tensor q, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor(c!) k_block_scale, Tensor(d!) v_block_scale, "
         "Tensor? cu_seqlens_q, Tensor? k_new, Tensor? v_new, Tensor? cache_seqlens, Tensor? block_table, int max_seqlen_q, int max_seqlen_k, "
         "float scale, bool causal, bool l2norm_qk, int groups, int window_left, int window_right, bool return_lse) -> (Tensor, Tensor)");
+  // the same call on the multi-wave chunk kernel: packed queries only
+  m.def("kvcache_mxfp4_prefill_forward(Tensor q, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor(c!) k_block_scale, Tensor(d!) v_block_scale, "
+        "Tensor? cu_seqlens_q, Tensor? k_new, Tensor? v_new, Tensor? cache_seqlens, Tensor? block_table, int max_seqlen_q, int max_seqlen_k, "
+        "float scale, bool causal, bool l2norm_qk, int groups, int window_left, int window_right, bool return_lse) -> (Tensor, Tensor)");
 }
-TORCH_LIBRARY_IMPL(fcsa_mx, CUDA, m) { m.impl("kvcache_mxfp4_forward", &kvcache_mxfp4_forward); }
+TORCH_LIBRARY_IMPL(fcsa_mx, CUDA, m) {
+  m.impl("kvcache_mxfp4_forward", &kvcache_mxfp4_forward);
+  m.impl("kvcache_mxfp4_prefill_forward", &kvcache_mxfp4_prefill_forward);
+}
 
 // Attention states for training, in a namespace of their own (the op set of `fcsa` is pinned): the attention op with the rows'
 // log-sum-exp as a second differentiable result -- dense, local (window sides other than (-1, -1)) or packed (cu_seqlens given) -- and

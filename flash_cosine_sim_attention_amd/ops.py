@@ -678,9 +678,55 @@ def flash_cosine_sim_attention_mxfp4_with_kvcache(q, k_cache, v_cache, k_block_s
     bytes -- at [cache_seqlens[b], ...) before attention reads the caches.  With l2norm_qk a key only contributes its direction, and a
     per-block power-of-two scale keeps every block of that direction at full e2m1 resolution.  `mxfp4_quantize` / `mxfp4_dequantize`
     convert an existing cache.  CPU tensors take a forward-only path: dequantise, then `cpu.py` (host tables).
-    Not taken here: the prefill, step, tree, ALiBi, rotary and shared-prefix calls (those functions refuse uint8 caches), e5m2, MXFP6 /
-    MXFP8 caches, fp4 queries."""
-    fn = "flash_cosine_sim_attention_mxfp4_with_kvcache"
+    Prompt chunks of such a cache belong to `flash_cosine_sim_attention_mxfp4_prefill_with_kvcache` (the same arguments).
+    Not taken here: the step, tree, ALiBi, rotary and shared-prefix calls (those functions refuse uint8 caches), e5m2, MXFP6 / MXFP8
+    caches, fp4 queries."""
+    return _mxfp4_call("flash_cosine_sim_attention_mxfp4_with_kvcache", False, q, k_cache, v_cache, k_block_scale, v_block_scale, cu_seqlens_q,
+                       k_new, v_new, cache_seqlens, block_table, max_seqlen_q, max_seqlen_k, scale, groups, causal, l2norm_qk, return_lse,
+                       window_size)
+
+
+def flash_cosine_sim_attention_mxfp4_prefill_with_kvcache(q, k_cache, v_cache, k_block_scale, v_block_scale, cu_seqlens_q=None, k_new=None,
+                                                          v_new=None, cache_seqlens=None, block_table=None, max_seqlen_q=None,
+                                                          max_seqlen_k=None, scale=8, groups=1, causal=False, l2norm_qk=True, return_lse=False,
+                                                          window_size=(-1, -1)):
+    """Prompt chunks against MXFP4 caches: `flash_cosine_sim_attention_mxfp4_with_kvcache` with packed queries on a kernel built for many
+    rows per sequence -- what `flash_cosine_sim_attention_prefill_with_kvcache` is to the ragged 16-bit call.
+
+    The parameters and defaults are that function's, so a call site switches by name; the result -- o, or (o, lse) -- and the bytes of
+    k_cache, v_cache, k_block_scale and v_block_scale after the quantising append are that function's, bit for bit wherever it runs one key
+    split.  N_b = 0, rows without a visible key (0 and -inf), host tables validated and device tables trusted and clamped, no
+    synchronisation with device tables (the call captures in a HIP graph): as there.
+    The kernel: four waves own 128 token-major rows of one sequence's K/V head; each 64-key stage of the cache is loaded as codes (a lane:
+    one quarter row and its scale byte), converted, normalised and rounded ONCE per workgroup (the decode kernel: once per 16 rows) and
+    shared through LDS; under causal a workgroup stops at its last visible key.  There are NO key splits: the grid is about G * total_q /
+    128 + B workgroups per K/V head (max_seqlen_q and max_seqlen_k are accepted and size nothing), so short chunks on long caches belong
+    to `flash_cosine_sim_attention_mxfp4_with_kvcache`.
+    Supported: q packed [total_q, H, D] with cu_seqlens_q; float16 / bfloat16; dim_head 64 or 128; any Hk dividing H; the group counts
+    of that function; l2norm_qk=False; both exponent regimes; paged and strided caches.  Refused, because
+    `flash_cosine_sim_attention_mxfp4_with_kvcache` is the call that takes them: a 4-D q or cu_seqlens_q=None, dim_head 32 / 96, a
+    window_size that hides a key, float32 q.  CPU tensors take that function's forward-only path.  Forward only."""
+    fn, other = "flash_cosine_sim_attention_mxfp4_prefill_with_kvcache", "flash_cosine_sim_attention_mxfp4_with_kvcache"
+    _check_return_lse(return_lse)
+    window = _window(window_size)
+    # what this kernel does not take, before anything else (and before the device branch: CPU tensors are refused the same things)
+    if cu_seqlens_q is None or q.dim() != 3:
+        raise ValueError(f"{fn} takes packed queries [total_q, heads, dim_head] with cu_seqlens_q, got q {tuple(q.shape)}"
+                         f"{'' if cu_seqlens_q is not None else ' and cu_seqlens_q=None'}: {other} takes equal-N calls")
+    if q.dtype == torch.float32:
+        raise TypeError(f"{fn} takes float16 or bfloat16 q, got {q.dtype}: {other} is the call that says what MXFP4 caches take")
+    if q.shape[-1] in (32, 96):
+        raise ValueError(f"{fn} takes dim_head 64 or 128, got {q.shape[-1]}: {other} takes 32 and 96")
+    if window[0] != -1 or (window[1] != -1 and not causal):
+        raise ValueError(f"{fn} does not take a window_size that hides keys, got {window}: {other} takes windows")
+    return _mxfp4_call(fn, True, q, k_cache, v_cache, k_block_scale, v_block_scale, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table,
+                       max_seqlen_q, max_seqlen_k, scale, groups, causal, l2norm_qk, return_lse, window_size)
+
+
+def _mxfp4_call(fn, chunk, q, k_cache, v_cache, k_block_scale, v_block_scale, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q,
+                max_seqlen_k, scale, groups, causal, l2norm_qk, return_lse, window_size):
+    """The one front end of the MXFP4 cache functions: the checks, the CPU path and the op call -- chunk: the op of the multi-wave chunk
+    kernel (packed queries, checked by the caller) in place of the decode kernel's"""
     _check_return_lse(return_lse)
     window = _window(window_size)
     ragged = cu_seqlens_q is not None
@@ -730,9 +776,9 @@ def flash_cosine_sim_attention_mxfp4_with_kvcache(q, k_cache, v_cache, k_block_s
     cu_q = cu_seqlens_q.to(q.device, non_blocking=True) if ragged else None
     k_cache, v_cache, cache_seqlens, block_table = c.on_device()
     _torch_ops.load()
-    o, lse = torch.ops.fcsa_mx.kvcache_mxfp4_forward(q, k_cache, v_cache, k_block_scale, v_block_scale, cu_q, k_new, v_new, cache_seqlens, block_table,
-                                                     max_q, c.max_k, float(scale), bool(causal), bool(l2norm_qk), int(groups), window[0], window[1],
-                                                     bool(return_lse))
+    op = torch.ops.fcsa_mx.kvcache_mxfp4_prefill_forward if chunk else torch.ops.fcsa_mx.kvcache_mxfp4_forward
+    o, lse = op(q, k_cache, v_cache, k_block_scale, v_block_scale, cu_q, k_new, v_new, cache_seqlens, block_table, max_q, c.max_k, float(scale),
+                bool(causal), bool(l2norm_qk), int(groups), window[0], window[1], bool(return_lse))
     return (o, lse) if return_lse else o
 
 

@@ -541,7 +541,8 @@ int    fcsa_forward_kvcache_rotary(const fcsa_forward_args* args, const fcsa_kvc
  * advanced, as in fcsa_forward_kvcache.
  * Launches: "kv_append_mx" (when rows are appended), "decode_mx" and the 16-bit call's combine ("decode_combine[_lse][_ragged]"): the V
  * scales are applied as the codes are read.
- * Not offered with such a cache: the prefill, step, tree, ALiBi, rotary and shared-prefix calls; other element formats (e5m2 scales,
+ * Prompt chunks: fcsa_forward_kvcache_mx_prefill, below.
+ * Not offered with such a cache: the step, tree, ALiBi, rotary and shared-prefix calls; other element formats (e5m2 scales,
  * MXFP6, MXFP8); fp4 queries and the scaled MFMA instructions. */
 #define FCSA_CACHE_MXFP4 2            /* fcsa_kvcache_mx.format */
 typedef struct fcsa_kvcache_mx {
@@ -553,6 +554,20 @@ int    fcsa_forward_kvcache_mx(const fcsa_forward_args* args, const fcsa_kvcache
 /* 0 for a call fcsa_forward_kvcache_mx refuses as unsupported (mx NULL, another format, FCSA_F32, an unsupported dim_head or group count) */
 size_t fcsa_forward_kvcache_mx_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* cache, const fcsa_kvcache_mx* mx,
                                                const fcsa_varlen* seqs, const fcsa_window* window);
+
+/* Prompt chunks against an MXFP4 cache: fcsa_forward_kvcache_mx's ragged step on a multi-wave kernel, as fcsa_forward_kvcache_prefill is
+ * fcsa_forward_kvcache_varlen's (additive: no existing struct changes and FCSA_ABI_VERSION stays 4).  The arguments, checks, quantising
+ * append, clamping and results are those of fcsa_forward_kvcache_mx with seqs set: o, lse_out and the four cache tensors afterwards are
+ * that call's, BIT FOR BIT wherever it runs one key split.  Four waves own 128 token-major rows of one sequence's K/V head, convert and
+ * normalise every 64-key stage of the cache once per workgroup and share it through LDS; under `causal` a workgroup stops at its last
+ * visible key.  There are no key splits: the grid is fcsa::prefill_slots x kv_heads workgroups.
+ * NO WORKSPACE: one split, so args->workspace is not read and there is no workspace query for this entry.
+ *   seqs      : required (NULL: FCSA_ERR_INVALID_ARG; fcsa_forward_kvcache_mx takes equal-N calls)
+ *   p.dim_head: 64 or 128 (32, 96: FCSA_ERR_UNSUPPORTED; fcsa_forward_kvcache_mx takes them)
+ *   window    : NULL, or sides that hide nothing (left < 0, and right < 0 or p.causal); a window that hides keys: FCSA_ERR_UNSUPPORTED
+ * Every refusal happens before any launch.  Launches: "kv_append_mx" (when rows are appended) and "prefill_mx". */
+int    fcsa_forward_kvcache_mx_prefill(const fcsa_forward_args* args, const fcsa_kvcache* cache, const fcsa_kvcache_mx* mx,
+                                       const fcsa_varlen* seqs, const fcsa_window* window, const fcsa_lse_out* lse_out);
 
 /* The same linear position bias in the training kernels, forward and backward: fcsa_forward_window / fcsa_backward_window with one more
  * argument, the slopes (additive: no existing struct changes and FCSA_ABI_VERSION stays 4).  A model trained through these entries is
