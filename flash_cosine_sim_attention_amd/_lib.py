@@ -109,7 +109,7 @@ EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fc
            "fcsa_forward_kvcache_tree", "fcsa_kvcache_compact", "fcsa_forward_kvcache_alibi",
            "fcsa_forward_alibi", "fcsa_backward_alibi", "fcsa_forward_alibi_workspace_bytes", "fcsa_backward_alibi_workspace_bytes",
            "fcsa_forward_kvcache_rotary", "fcsa_forward_kvcache_mx", "fcsa_forward_kvcache_mx_workspace_bytes",
-           "fcsa_forward_kvcache_mx_prefill")
+           "fcsa_forward_kvcache_mx_prefill", "fcsa_forward_kvcache_mx_step", "fcsa_forward_kvcache_mx_step_workspace_bytes")
 
 _lib = None
 
@@ -244,6 +244,13 @@ def load():
     if hasattr(lib, "fcsa_forward_kvcache_mx_prefill"):      # (likewise: an FCSA_LIB build from before the MXFP4 chunk kernel)
         lib.fcsa_forward_kvcache_mx_prefill.argtypes = lib.fcsa_forward_kvcache_mx.argtypes
         lib.fcsa_forward_kvcache_mx_prefill.restype = C.c_int
+    if hasattr(lib, "fcsa_forward_kvcache_mx_step"):      # (likewise: an FCSA_LIB build from before the engine step on MXFP4 caches)
+        lib.fcsa_forward_kvcache_mx_step.argtypes = [C.POINTER(ForwardArgs), C.POINTER(KvCache), C.POINTER(KvCacheMx), C.POINTER(Varlen),
+                                                     C.POINTER(Window), C.POINTER(KvCacheStep), C.POINTER(Rotary), C.POINTER(LseOut)]
+        lib.fcsa_forward_kvcache_mx_step.restype = C.c_int
+        lib.fcsa_forward_kvcache_mx_step_workspace_bytes.argtypes = [C.POINTER(Problem), C.POINTER(KvCache), C.POINTER(KvCacheMx),
+                                                                     C.POINTER(Varlen), C.POINTER(Window), C.POINTER(KvCacheStep)]
+        lib.fcsa_forward_kvcache_mx_step_workspace_bytes.restype = C.c_size_t
     if hasattr(lib, "fcsa_forward_kvcache_tree"):      # (likewise: an FCSA_LIB build from before tree attention)
         lib.fcsa_forward_kvcache_tree.argtypes = [C.POINTER(ForwardArgs), C.POINTER(KvCache), C.POINTER(Varlen), C.POINTER(KvCacheQuant),
                                                   C.POINTER(TreeMask), C.POINTER(LseOut)]

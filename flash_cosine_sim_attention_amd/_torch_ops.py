@@ -101,8 +101,8 @@ def _register_fakes():
         def _(q, *args):
             return q.new_empty(q.shape), q.new_empty(q.shape[:-1], dtype=torch.float32)
 
-    # an MXFP4 cache (namespace fcsa_mx), decode and chunk ops alike: the lse is empty unless asked for
-    for op in ("fcsa_mx::kvcache_mxfp4_forward", "fcsa_mx::kvcache_mxfp4_prefill_forward"):
+    # an MXFP4 cache (namespace fcsa_mx; the engine step: fcsa_mx_step), decode, chunk and step ops alike: the lse is empty unless asked for
+    for op in ("fcsa_mx::kvcache_mxfp4_forward", "fcsa_mx::kvcache_mxfp4_prefill_forward", "fcsa_mx_step::kvcache_mxfp4_step_forward"):
         @torch.library.register_fake(op)
         def _(q, *args):
             return q.new_empty(q.shape), q.new_empty(q.shape[:-1] if args[-1] else (0,), dtype=torch.float32)

@@ -1084,6 +1084,12 @@ fcsa::DecodeMx mx_view(const fcsa_kvcache_mx& m) { return {view(m.k_block_scale,
 // append that rotates K on its way into the cache
 int append_launch(const DecodeCall& c, fcsa::DecodeForm form, const fcsa::DecodeStepParams& dp, hipStream_t s) {
   if (c.kv->new_len <= 0 || c.kv->capacity <= 0) return FCSA_OK;
+  if (c.rotary != nullptr && c.mx != nullptr) {      // an MXFP4 step with tables: K is rotated, then quantised
+    const fcsa::DecodeRotary ro = rotary_view(*c.rotary);
+    const fcsa::DecodeMx mx = mx_view(*c.mx);
+    return timed("kv_append_mx_rotary", "kv append (mxfp4, rotary)", s,
+                 [&] { return fcsa::launch_kv_append_mx_rotary(c.a->p.dtype, c.a->p.dim_head, form, dp, mx, ro, s); });
+  }
   if (c.rotary != nullptr) {
     const LaunchName& n = kRotaryAppendName[form.fp8];
     const fcsa::DecodeRotary ro = rotary_view(*c.rotary);
@@ -1091,7 +1097,8 @@ int append_launch(const DecodeCall& c, fcsa::DecodeForm form, const fcsa::Decode
   }
   if (c.mx != nullptr) {
     const fcsa::DecodeMx mx = mx_view(*c.mx);
-    return timed("kv_append_mx", "kv append (mxfp4)", s, [&] { return fcsa::launch_kv_append_mx(c.a->p.dtype, c.a->p.dim_head, form, dp, mx, s); });
+    const fcsa::DecodeForm plain = {form.fp8, form.ragged, false};      // (an engine step without tables: the ragged call's append, unchanged)
+    return timed("kv_append_mx", "kv append (mxfp4)", s, [&] { return fcsa::launch_kv_append_mx(c.a->p.dtype, c.a->p.dim_head, plain, dp, mx, s); });
   }
   const LaunchName& n = kAppendName[form.ragged][form.fp8];
   return timed(n.name, n.what, s, [&] { return fcsa::launch_kv_append(c.a->p.dtype, c.a->p.dim_head, form, dp, s); });
@@ -1105,6 +1112,12 @@ constexpr LaunchName kAlibiPrefillName[2] = {{"alibi_prefill", "prefill (alibi)"
 // the decode launch of a ragged or engine step under the name `plain`; c.alibi: the entry points that take the slopes, under their own name
 int decode_launch(const LaunchName& plain, const DecodeCall& c, fcsa::DecodeForm form, const fcsa::DecodeStepParams& dp, hipStream_t s) {
   const fcsa_problem& p = c.a->p;
+  if (c.mx != nullptr && form.step) {      // an MXFP4 engine step: the step form, with the tables where the call has them
+    const fcsa::DecodeMx mx = mx_view(*c.mx);
+    const fcsa::DecodeRotary ro = c.rotary != nullptr ? rotary_view(*c.rotary) : fcsa::DecodeRotary{};
+    const LaunchName n = c.rotary != nullptr ? LaunchName{"rotary_decode_mx", "decode (mxfp4, rotary)"} : LaunchName{"step_decode_mx", "step decode (mxfp4)"};
+    return timed(n.name, n.what, s, [&] { return fcsa::launch_decode_mx_step(p.dtype, p.dim_head, form, dp, mx, c.rotary != nullptr ? &ro : nullptr, s); });
+  }
   if (c.mx != nullptr) {
     const fcsa::DecodeMx mx = mx_view(*c.mx);
     return timed("decode_mx", "decode (mxfp4)", s, [&] { return fcsa::launch_decode_mx(p.dtype, p.dim_head, form, dp, mx, s); });
@@ -1128,6 +1141,14 @@ int chunk_launch(const LaunchName& plain, const DecodeCall& c, fcsa::DecodeForm 
   dp.ws_ml = nullptr;
   const fcsa::DecodeLseOut lo = c.lse != nullptr ? lse_view(*c.lse, true) : fcsa::DecodeLseOut{};
   const fcsa::DecodeLseOut* lse = c.lse != nullptr ? &lo : nullptr;
+  if (c.mx != nullptr && form.step) {
+    const fcsa::DecodeMx mx = mx_view(*c.mx);
+    const fcsa::DecodeRotary ro = c.rotary != nullptr ? rotary_view(*c.rotary) : fcsa::DecodeRotary{};
+    const LaunchName n = c.rotary != nullptr ? LaunchName{"rotary_prefill_mx", "prefill (mxfp4, rotary)"} : LaunchName{"step_prefill_mx", "step prefill (mxfp4)"};
+    return timed(n.name, n.what, s, [&] {
+      return fcsa::launch_prefill_mx_step(c.a->p.dtype, c.a->p.dim_head, form, dp, mx, c.rotary != nullptr ? &ro : nullptr, lse, s);
+    });
+  }
   if (c.mx != nullptr) {
     const fcsa::DecodeMx mx = mx_view(*c.mx);
     return timed("prefill_mx", "prefill (mxfp4)", s, [&] { return fcsa::launch_prefill_mx(c.a->p.dtype, c.a->p.dim_head, form, dp, mx, lse, s); });
@@ -1219,6 +1240,21 @@ int prefill_call(const DecodeCall& c) {
 // launch over 128-row slots, each skipped where the caller promises it has no work.  Where the chunk kernel is not compiled for the problem
 // the call is decode_call.
 static_assert(fcsa::kStepChunkRows == FCSA_STEP_CHUNK_ROWS, "the default threshold of include/fcsa.h");
+// the tables of a rotary embedding, for the two entry points that take them (the messages name the 16-bit one, whose they were)
+int check_rotary(const fcsa_forward_args* a, const fcsa_rotary* ro) {
+  if (ro->cos == nullptr || ro->sin == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_rotary: cos / sin: null pointer");
+  if (((reinterpret_cast<uintptr_t>(ro->cos) | reinterpret_cast<uintptr_t>(ro->sin)) & 15) != 0 || ro->stride_row % 4 != 0)
+    return fail(FCSA_ERR_INVALID_ARG, "kvcache_rotary: cos / sin rows not 16-byte aligned (pointers, and stride_row %lld a multiple of 4)", (long long)ro->stride_row);
+  if (ro->reserved != 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_rotary: reserved (%lld) is 0", (long long)ro->reserved);
+  if (ro->rows <= 0 || ro->rows > INT32_MAX) return fail(FCSA_ERR_INVALID_ARG, "kvcache_rotary: rows (%lld) outside [1, 2^31)", (long long)ro->rows);
+  if (ro->interleaved != 0 && ro->interleaved != 1) return fail(FCSA_ERR_INVALID_ARG, "kvcache_rotary: interleaved (%d) is a flag (0 or 1)", ro->interleaved);
+  if (ro->rotary_dim != 64 && ro->rotary_dim != 128) return fail(FCSA_ERR_INVALID_ARG, "kvcache_rotary: rotary_dim %d is not supported (dim_head, or 64 at dim_head 128)", ro->rotary_dim);
+  if (a->p.dtype == FCSA_F32) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_rotary: float32 is not supported (f16 or bf16)");
+  if (a->p.dim_head != 64 && a->p.dim_head != 128) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_rotary: dim_head %d is not supported (64 or 128)", a->p.dim_head);
+  if (ro->rotary_dim > a->p.dim_head)
+    return fail(FCSA_ERR_INVALID_ARG, "kvcache_rotary: rotary_dim %d is not supported at dim_head %d (dim_head, or 64 at dim_head 128)", ro->rotary_dim, a->p.dim_head);
+  return FCSA_OK;
+}
 int check_step(const fcsa_kvcache_step* st) {
   if (st == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_step: null argument");
   if ((st->no_decode != 0 && st->no_decode != 1) || (st->no_chunk != 0 && st->no_chunk != 1) || st->reserved != 0)
@@ -1238,6 +1274,18 @@ DecodePlan step_plan(const fcsa_problem& p, const fcsa_kvcache& kv, const fcsa_v
   if (st.no_decode) { d.splits = 1; d.ws_ml = 0; d.total = 0; }      // no decode launch: no partials
   return d;
 }
+// c.mx (fcsa_forward_kvcache_mx_step): the MXFP4 chunk kernel has no windowed form, so a window that hides a key sends every sequence to the
+// decode kernel -- a threshold no G * N_b reaches (heads x packed rows stay below 2^31), the chunk launch skipped, the split count sized by
+// all rows -- decided from the arguments alone, as the 16-bit step call decides for float32.
+fcsa_kvcache_step mx_step_fields(const fcsa_problem& p, const fcsa_window* w, fcsa_kvcache_step st) {
+  if (w != nullptr && (w->left >= 0 || (!p.causal && w->right >= 0))) {
+    st.chunk_rows = INT32_MAX;
+    st.no_chunk = 1;
+    st.no_decode = 0;
+    st.max_decode_tokens = -1;
+  }
+  return st;
+}
 constexpr LaunchName kStepDecodeName[2] = {{"step_decode", "step decode"}, {"step_decode_fp8", "step decode (fp8)"}};
 constexpr LaunchName kStepCombineName[2][2] = {{{"step_combine", "step combine"}, {"step_combine_lse", "step combine (lse)"}},
                                                {{"step_combine_fp8", "step combine (fp8)"}, {"step_combine_lse_fp8", "step combine (lse, fp8)"}}};
@@ -1248,12 +1296,14 @@ int step_call(const DecodeCall& c) {
   const fcsa_forward_args* a = c.a;
   const fcsa_kvcache* kv = c.kv;
   const fcsa_problem& p = a->p;
-  const fcsa_kvcache_step& st = *c.step;
+  const fcsa_kvcache_step st = c.mx != nullptr ? mx_step_fields(p, c.w, *c.step) : *c.step;
   const bool rows = p.batch > 0 && p.heads > 0 && c.seqs->total_q > 0;
   if (rows && c.lse != nullptr && c.lse->lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_step: lse: null pointer");
   if (!has_chunk_kernel(p)) {
     if (c.rotary != nullptr) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_rotary: no rotary kernels for this dtype / dim_head (f16 or bf16, 64 or 128)");
-    return decode_call({c.a, c.kv, c.seqs, c.qz, c.w, c.lse, nullptr, nullptr, c.alibi});
+    DecodeCall d{c.a, c.kv, c.seqs, c.qz, c.w, c.lse, nullptr, nullptr, c.alibi};
+    d.mx = c.mx;      // (an MXFP4 cache at dim_head 32 / 96: the ragged MXFP4 call)
+    return decode_call(d);
   }
   const bool fp8 = c.qz != nullptr;
   const DecodeWindow win = decode_window(p, *kv, true, c.w);
@@ -1398,20 +1448,31 @@ int fcsa_forward_kvcache_rotary(const fcsa_forward_args* a, const fcsa_kvcache* 
                                 const fcsa_window* w, const fcsa_kvcache_step* step, const fcsa_rotary* ro, const fcsa_lse_out* lse) {
   if (a == nullptr || kv == nullptr || seqs == nullptr || step == nullptr || ro == nullptr)
     return fail(FCSA_ERR_INVALID_ARG, "kvcache_rotary: null argument");
-  if (ro->cos == nullptr || ro->sin == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_rotary: cos / sin: null pointer");
-  if (((reinterpret_cast<uintptr_t>(ro->cos) | reinterpret_cast<uintptr_t>(ro->sin)) & 15) != 0 || ro->stride_row % 4 != 0)
-    return fail(FCSA_ERR_INVALID_ARG, "kvcache_rotary: cos / sin rows not 16-byte aligned (pointers, and stride_row %lld a multiple of 4)", (long long)ro->stride_row);
-  if (ro->reserved != 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_rotary: reserved (%lld) is 0", (long long)ro->reserved);
-  if (ro->rows <= 0 || ro->rows > INT32_MAX) return fail(FCSA_ERR_INVALID_ARG, "kvcache_rotary: rows (%lld) outside [1, 2^31)", (long long)ro->rows);
-  if (ro->interleaved != 0 && ro->interleaved != 1) return fail(FCSA_ERR_INVALID_ARG, "kvcache_rotary: interleaved (%d) is a flag (0 or 1)", ro->interleaved);
-  if (ro->rotary_dim != 64 && ro->rotary_dim != 128) return fail(FCSA_ERR_INVALID_ARG, "kvcache_rotary: rotary_dim %d is not supported (dim_head, or 64 at dim_head 128)", ro->rotary_dim);
-  if (a->p.dtype == FCSA_F32) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_rotary: float32 is not supported (f16 or bf16)");
-  if (a->p.dim_head != 64 && a->p.dim_head != 128) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_rotary: dim_head %d is not supported (64 or 128)", a->p.dim_head);
-  if (ro->rotary_dim > a->p.dim_head)
-    return fail(FCSA_ERR_INVALID_ARG, "kvcache_rotary: rotary_dim %d is not supported at dim_head %d (dim_head, or 64 at dim_head 128)", ro->rotary_dim, a->p.dim_head);
+  if (int rc = check_rotary(a, ro)) return rc;
   DecodeCall c{a, kv, seqs, qz, w, lse, step};
   c.rotary = ro;
   return step_call(c);
+}
+
+// An engine step on an MXFP4 cache: the step call's description with `mx` (and, where given, `rotary`) added -- the ragged MXFP4 call's
+// checks, the step's window, plan and workspace, then append, step decode + 16-bit step combine and step chunk launches back to back.
+int fcsa_forward_kvcache_mx_step(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_kvcache_mx* mx, const fcsa_varlen* seqs,
+                                 const fcsa_window* w, const fcsa_kvcache_step* step, const fcsa_rotary* ro, const fcsa_lse_out* lse) {
+  if (a == nullptr || kv == nullptr || mx == nullptr || seqs == nullptr || step == nullptr)
+    return fail(FCSA_ERR_INVALID_ARG, "kvcache_mx_step: null argument");
+  if (int rc = mx_supported(a->p, *mx)) return rc;
+  if (ro != nullptr)
+    if (int rc = check_rotary(a, ro)) return rc;
+  DecodeCall c{a, kv, seqs, nullptr, w, lse, step};
+  c.mx = mx;
+  c.rotary = ro;
+  return step_call(c);
+}
+size_t fcsa_forward_kvcache_mx_step_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv, const fcsa_kvcache_mx* mx, const fcsa_varlen* seqs,
+                                                    const fcsa_window* w, const fcsa_kvcache_step* step) {
+  if (p == nullptr || kv == nullptr || mx == nullptr || seqs == nullptr || step == nullptr || mx_supported(*p, *mx) != FCSA_OK) return 0;
+  if (!has_chunk_kernel(*p)) return decode_workspace_bytes(p, kv, seqs, w, true);
+  return step_plan(*p, *kv, *seqs, mx_step_fields(*p, w, *step), decode_window(*p, *kv, true, w).reach()).total;
 }
 
 int fcsa_kvcache_compact(const fcsa_kvcache* kv, int32_t batch, int32_t kv_heads, int32_t dim_head, int32_t elem_bytes, const int32_t* accepted,

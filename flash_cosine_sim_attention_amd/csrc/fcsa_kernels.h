@@ -265,6 +265,17 @@ hipError_t launch_decode_mx(int dtype, int D, DecodeForm f, const DecodeStepPara
 // mx_groups_ok; hipErrorInvalidValue otherwise.  One kernel writes o and, where lse is not nullptr, the rows' log-sum-exp.  The append
 // before it is launch_kv_append_mx.
 hipError_t launch_prefill_mx(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeMx& mx, const DecodeLseOut* lse, hipStream_t s);
+// An engine step on an MXFP4 cache (fcsa_forward_kvcache_mx_step): the step forms of the two kernels above -- the same grids, LDS and blocks
+// on entry points that take DecodeStepParams and leave the other route's sequences alone (step_is_chunk on the device) -- and, with tables,
+// the append that rotates K before it quantises and the forms that rotate the raw q row in their prologue.  f.ragged and f.step must be
+// set; f16 / bf16, D = 64 / 128; rotary: nullptr, or tables with rotary_dim D, or 64 at D = 128; hipErrorInvalidValue otherwise.  The append
+// without tables is launch_kv_append_mx and the combine launch_decode_combine's 16-bit step form.
+hipError_t launch_kv_append_mx_rotary(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeMx& mx, const DecodeRotary& rotary,
+                                      hipStream_t s);
+hipError_t launch_decode_mx_step(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeMx& mx, const DecodeRotary* rotary,
+                                 hipStream_t s);
+hipError_t launch_prefill_mx_step(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeMx& mx, const DecodeRotary* rotary,
+                                  const DecodeLseOut* lse, hipStream_t s);
 
 // Merging attention states (fcsa_merge_states, csrc/fcsa_merge.hip): S states (o_s, lse_s) of the rows [n0, n1, n2] -> (o, lse).  o views
 // carry BYTE strides, lse views ELEMENT strides.

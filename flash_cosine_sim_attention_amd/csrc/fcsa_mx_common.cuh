@@ -95,5 +95,56 @@ template <int NT> FCSA_DEV void mx_group_normalise(float (&x)[NT][8], int gs, in
   }
 }
 
+// the rotary embedding's shapes for the three launchers of an MXFP4 engine step: no tables, or rotary_dim D, or 64 at D = 128
+inline bool mx_rotary_ok(int D, const DecodeRotary* r) {
+  return r == nullptr || (r->cos != nullptr && r->sin != nullptr && r->rows >= 1 && (r->rotary_dim == D || (r->rotary_dim == 64 && D == 128)));
+}
+
+// The rotary embedding of a RAW query row in the quarter layout (the ROTARY forms of both kernels): raw[t] = the
+// eight 16-bit features g Q + 8 t ... + 7 of lane g = lane >> 4 as loaded, x[t] = their float32 values, rotated in place by the table row of
+// `pos` (rotary_at: clamped).  Interleaved pairs (2 f, 2 f + 1) lie inside a unit.  A split pair (f, f + rotary_dim / 2) does NOT stay on the
+// lane as it does in the 16-bit kernels' layout: the partner of feature g Q + 8 t + e is the same element of the same unit of the lane
+// (rotary_dim / 2) / Q quarters away -- two (lane ^ 32) where rotary_dim is dim_head at 128 and at 64, one (lane ^ 16) for rotary_dim 64 at
+// dim_head 128, whose quarters 2 and 3 pass through.  So a unit's partners arrive with ONE exchange of its four raw words (ds_bpermute: no
+// LDS traffic, no second global read), before the unpack.  Every lane runs every exchange: the mask is uniform, and rows the tile does not
+// have hold zeros.  As in rotary_unit, partner, angle and sign are SELECTED by the uniform layout flags, element e becoming
+// fma(x, cos, +-fl(partner * sin)), so the row stays in registers.
+template <typename T, int NT> FCSA_DEV void mx_rotary_row(const u32x4 (&raw)[NT], float (&x)[NT][8], const DecodeRotary& ro, int pos, int lane) {
+  constexpr int Q = 8 * NT;
+  const bool il = ro.interleaved != 0;
+  const int half = ro.rotary_dim / 2, g = lane >> 4;
+  const int away = (half / Q) * 16;                 // lanes between split partners
+  const float* c = ro.cos + rotary_at(ro, pos);
+  const float* s = ro.sin + rotary_at(ro, pos);
+  float r[NT][8];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int f0 = g * Q + 8 * t;                   // the unit's first feature
+    const bool active = f0 < ro.rotary_dim, second = f0 >= half;
+    u32x4 pw;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) pw[w] = (uint32_t)__shfl_xor((int)raw[t][w], away, 64);
+    float y[8];
+    unpack<T>(pw, y);
+    const int at = !active ? 0 : il ? f0 / 2 : f0 - (second ? half : 0);      // (a pass-through unit loads angles it does not use, in range)
+    const f32x4 c0 = *reinterpret_cast<const f32x4*>(c + at), s0 = *reinterpret_cast<const f32x4*>(s + at);
+    const f32x4 c1 = *reinterpret_cast<const f32x4*>(c + at + (il ? 0 : 4)), s1 = *reinterpret_cast<const f32x4*>(s + at + (il ? 0 : 4));
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float ce = il ? c0[e >> 1] : (e < 4 ? c0[e & 3] : c1[e & 3]);
+      const float se = il ? s0[e >> 1] : (e < 4 ? s0[e & 3] : s1[e & 3]);
+      const float partner = il ? x[t][e ^ 1] : y[e];
+      const bool plus = il ? (e & 1) != 0 : second;      // the pair's second feature: x sin + y cos
+      const float ps = partner * se;
+      const float rot = fmaf(x[t][e], ce, plus ? ps : -ps);
+      r[t][e] = active ? rot : x[t][e];
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) x[t][e] = r[t][e];
+}
+
 }  // namespace
 }  // namespace fcsa

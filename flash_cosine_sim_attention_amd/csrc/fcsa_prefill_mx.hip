@@ -94,6 +94,8 @@ template <typename T, int D> struct PrefillMxRegs {
 // scratch (profiles/mxfp4_prefill_resources.txt): the stage in flight is codes, a quarter of the registers of the 16-bit kernel's.
 template <typename T, int D> constexpr int kPrefillMxWavesPerSimd = 2;
 
+// EDITORS: this kernel exists a SECOND time below, as step_prefill_mx_body (the chunk side of an engine step), and the two must stay bit for
+// bit alike: a change to the stage loop, the math or the epilogue here is made there as well.
 template <typename T, int D, bool DYN>
 __global__ __launch_bounds__(64 * kMxWaves, (kPrefillMxWavesPerSimd<T, D>)) void prefill_mx_kernel(DecodeRaggedParams p, DecodeMx mx, DecodeLseOut lo) {
   typedef PrefillMxLds<D> LP;
@@ -244,6 +246,182 @@ __global__ __launch_bounds__(64 * kMxWaves, (kPrefillMxWavesPerSimd<T, D>)) void
   }
 }
 
+// ... and of the chunk side of an engine step (step_prefill_mx_kernel, rotary_prefill_mx_kernel; profiles/mxfp4_step_resources.txt): two
+// everywhere -- the routing test adds nothing to the key loop, and the rotation's registers (a unit's exchanged words, eight angles) are dead
+// before it starts.
+template <typename T, int D, bool ROTARY> constexpr int kStepPrefillMxWavesPerSimd = 2;
+
+// The chunk side of an engine step (step_prefill_mx_kernel, rotary_prefill_mx_kernel; fcsa_forward_kvcache_mx_step):
+// prefill_mx_kernel written a SECOND time, because that kernel keeps its text -- the same statements in the same order, so a chunk-routed
+// row is that kernel's bit for bit -- with two additions.  A workgroup whose sequence is no chunk (step_is_chunk) exits: those rows are the
+// step decode kernel's.  ROTARY: the RAW query rows are rotated by the table row of their position (mx_rotary_row, as
+// step_decode_mx_body<ROTARY>) in the per-tile prologue, before the l2norm, for both row tiles of the wave.
+template <typename T, int D, bool DYN, bool ROTARY>
+FCSA_DEV void step_prefill_mx_body(const DecodeStepParams& p, const DecodeMx& mx, const DecodeLseOut& lo, const DecodeRotary& ro) {
+  typedef PrefillMxLds<D> LP;
+  typedef PrefillMxRegs<T, D> R;
+  constexpr int NS = R::NS, Q = R::Q, FB = D / 16, NR = kMxTiles;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+
+  const int lane = threadIdx.x & 63, x = lane & 15, hi = lane >> 4;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int kvh = blockIdx.x % p.Hk;
+  int b, rt, q0, N;
+  if (!prefill_tile(p.cu_q, p.B, p.total_q, p.G, kPrefillRows, blockIdx.x / p.Hk, b, rt, q0, N)) return;
+  if (!step_is_chunk(p.G, N, p.chunk_rows)) return;
+  const int L = decode_len(p.seqlens != nullptr, p.seqlens != nullptr ? p.seqlens[b] : 0, p.append ? N : 0, p.capacity);
+  const int64_t row0 = (int64_t)rt * kPrefillRows;
+  // the tile's keys [0, kend); a wave stops at the last key its own 32 rows see, but loads its share of every stage and joins every barrier
+  const int kend = prefill_kend(L, N, p.G, row0, kPrefillRows, p.causal != 0);
+  const int wave_kend = prefill_kend(L, N, p.G, row0 + wave * (NR * kDecodeRows), NR * kDecodeRows, p.causal != 0);
+  const int gs = D / p.groups;
+
+  // this lane's query rows, one per row tile, in the keys' order: unit t of lane (x, hi) holds features hi Q + 8 t ... + 7
+  int last_key[NR];
+  u32x4 qf[NR][NS];
+#pragma unroll
+  for (int r2 = 0; r2 < NR; ++r2) {
+    const int64_t r = row0 + (wave * NR + r2) * kDecodeRows + x;
+    const bool row_ok = r < (int64_t)p.G * N;
+    const int g = row_ok ? (int)(r % p.G) : 0, qi = row_ok ? (int)(r / p.G) : 0;
+    last_key[r2] = L - N + qi;                 // causal: key j is visible iff j <= last_key
+    float xq[NS][8];
+    [[maybe_unused]] u32x4 raw[NS];
+    const char* qrow = p.q.p + (int64_t)(kvh * p.G + g) * p.q.sh + (int64_t)(q0 + qi) * p.q.sn + hi * Q * 2;
+#pragma unroll
+    for (int t = 0; t < NS; ++t) {
+      const u32x4 u = row_ok ? *reinterpret_cast<const u32x4*>(qrow + 16 * t) : u32x4{0u, 0u, 0u, 0u};
+      if constexpr (ROTARY) raw[t] = u;
+      unpack<T>(u, xq[t]);
+    }
+    if constexpr (ROTARY) mx_rotary_row<T, NS>(raw, xq, ro, last_key[r2], lane);
+    if (p.l2norm) mx_group_normalise<NS>(xq, gs, lane);
+#pragma unroll
+    for (int t = 0; t < NS; ++t) qf[r2][t] = pack<T>(xq[t], p.l2norm ? p.c1 : 1.f);      // c1 * q^, one rounding
+  }
+  const float smul = p.l2norm ? 1.f : p.c1;
+
+  f32x4 acc[NR][FB];
+  float m[NR], l[NR];
+#pragma unroll
+  for (int r2 = 0; r2 < NR; ++r2) {
+#pragma unroll
+    for (int fb = 0; fb < FB; ++fb) acc[r2][fb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    m[r2] = DYN ? -INFINITY : p.c2;
+    l[r2] = 0.f;
+  }
+
+  const int stages = (kend + kPrefillStage - 1) / kPrefillStage;
+  const int my_row = wave * 16 + x;              // the stage row this lane loads
+  const bool l2norm = p.l2norm != 0;
+
+  // the math of stage st (in buffer st & 1): decode_mx_kernel's block step for both row tiles
+  auto math = [&](int st) {
+    const char* kst = smem + (st & 1) * LP::BUF;
+    const char* vst = kst + LP::TILE;
+#pragma unroll
+    for (int blk = 0; blk < kPrefillStage / kDecodeBlock; ++blk) {
+      const int kb = st * kPrefillStage + blk * kDecodeBlock;
+      if (kb >= wave_kend) break;
+      // S^T = K^ Q^T for the two 16-key halves: s[r2][sb][rr] = logit of key kb + 16 sb + 4 hi + rr for row x of tile r2 (log2 units)
+      f32x4 s[NR][2];
+#pragma unroll
+      for (int sb = 0; sb < 2; ++sb) {
+#pragma unroll
+        for (int r2 = 0; r2 < NR; ++r2) s[r2][sb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int t = 0; t < NS; ++t) {
+          const u32x4 kf = *reinterpret_cast<const u32x4*>(kst + (blk * kDecodeBlock + 16 * sb + x) * LP::PITCH + hi * (Q * 2) + 16 * t);
+#pragma unroll
+          for (int r2 = 0; r2 < NR; ++r2) s[r2][sb] = Unit<T>::mfma(kf, qf[r2][t], s[r2][sb]);
+        }
+      }
+      u32x4 pb[NR];
+#pragma unroll
+      for (int r2 = 0; r2 < NR; ++r2) {
+#pragma unroll
+        for (int sb = 0; sb < 2; ++sb)
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) {
+            const int key = kb + 16 * sb + 4 * hi + rr;
+            const bool vis = key < L && (!p.causal || key <= last_key[r2]);
+            s[r2][sb][rr] = vis ? s[r2][sb][rr] * smul : -INFINITY;
+          }
+        f32x4 pr[2];
+        softmax_step<DYN>(s[r2], m[r2], l[r2], acc[r2], p.c2, pr);
+        // k-slot (hi, e) of the P~V product is key 16 (e >> 2) + 4 hi + (e & 3): P~ is used where the first product left it
+        pb[r2][0] = Traits<T>::pack2(pr[0][0], pr[0][1]);
+        pb[r2][1] = Traits<T>::pack2(pr[0][2], pr[0][3]);
+        pb[r2][2] = Traits<T>::pack2(pr[1][0], pr[1][1]);
+        pb[r2][3] = Traits<T>::pack2(pr[1][2], pr[1][3]);
+      }
+      pv_block<T, D, NR>(vst, blk * kDecodeBlock, x, hi, pb, acc);
+    }
+  };
+  // One stage of the loop.  On entry buffer st & 1 holds stage st, `have` the codes of stage st + 1 (requested one or two steps ago) and
+  // `fetch` is free: request stage st + 2, do the math of stage st, convert stage st + 1 into the other buffer (last read before the
+  // barrier that ended the previous step).
+  auto step = [&](int st, R& have, R& fetch) {
+    fetch.load(p, mx, b, kvh, min(st + 2, stages - 1) * kPrefillStage + wave * 16, L, lane);      // (past the end: the last stage again)
+    math(st);
+    if (st + 1 < stages) have.store(smem + ((st + 1) & 1) * LP::BUF, my_row, lane, (st + 1) * kPrefillStage + my_row < L, l2norm, gs);
+    __syncthreads();
+  };
+  if (stages > 0) {      // (so L >= 1: what the load rule needs)
+    R ra, rb;
+    ra.load(p, mx, b, kvh, wave * 16, L, lane);
+    rb.load(p, mx, b, kvh, min(1, stages - 1) * kPrefillStage + wave * 16, L, lane);
+    ra.store(smem, my_row, lane, my_row < L, l2norm, gs);
+    __syncthreads();
+    for (int st = 0; st < stages; st += 2) {
+      step(st, rb, ra);
+      if (st + 1 >= stages) break;
+      step(st + 1, ra, rb);
+    }
+  }
+
+  // Row x of tile r2: O^T[16 fb + 4 hi + rr][x] in acc[r2][fb][rr].  The combine of its one split (decode_combine_body's functions), in
+  // registers.  The row's head and token are worked out again here (from an opaque lane id), so that no address lives through the key loop.
+  const int xe = opaque(lane) & 15, hie = opaque(lane) >> 4;
+#pragma unroll
+  for (int r2 = 0; r2 < NR; ++r2) {
+    float ls = l[r2];
+    ls += __shfl_xor(ls, 16, 64);
+    ls += __shfl_xor(ls, 32, 64);
+    const int64_t r = row0 + (wave * NR + r2) * kDecodeRows + xe;
+    if (r >= (int64_t)p.G * N) continue;
+    const int h = kvh * p.G + (int)(r % p.G);
+    const int64_t tok = q0 + r / p.G;
+    const float M = m[r2];
+    const bool any = M != -INFINITY;
+    const float w = combine_weight(M, M);      // the one split's weight: 1
+    float lsum = 0.f;
+    if (any) lsum += w * ls;
+    const float inv = combine_inv(p.dyn != 0, lsum, p.l_eps);
+    char* dst = p.o.p + (int64_t)h * p.o.sh + tok * p.o.sn + 4 * hie * 2;
+#pragma unroll
+    for (int fb = 0; fb < FB; ++fb) {
+      f32x4 a = {0.f, 0.f, 0.f, 0.f};
+      if (any) a += w * acc[r2][fb];
+      a *= inv;
+      *reinterpret_cast<u32x2*>(dst + 16 * fb * 2) = u32x2{Traits<T>::pack2(a[0], a[1]), Traits<T>::pack2(a[2], a[3])};
+    }
+    if (lo.lse != nullptr && hie == 0) lo.lse[(int64_t)h * lo.sh + tok * lo.sn] = decode_row_lse(M, lsum);
+  }
+}
+
+// The two entry points of launch_prefill_mx_step.
+template <typename T, int D, bool DYN>
+__global__ __launch_bounds__(64 * kMxWaves, (kStepPrefillMxWavesPerSimd<T, D, false>)) void step_prefill_mx_kernel(DecodeStepParams p, DecodeMx mx,
+                                                                                                                 DecodeLseOut lo) {
+  step_prefill_mx_body<T, D, DYN, false>(p, mx, lo, DecodeRotary{});
+}
+template <typename T, int D, bool DYN>
+__global__ __launch_bounds__(64 * kMxWaves, (kStepPrefillMxWavesPerSimd<T, D, true>)) FCSA_NO_PK_F32 void rotary_prefill_mx_kernel(
+    DecodeStepParams p, DecodeMx mx, DecodeLseOut lo, DecodeRotary ro) {
+  step_prefill_mx_body<T, D, DYN, true>(p, mx, lo, ro);
+}
+
 }  // namespace
 
 // One 4-wave workgroup per (row-tile slot of 128 rows, K/V head): p.slots = fcsa::prefill_slots(total_q, B, G, kPrefillRows), one split, no
@@ -260,6 +438,28 @@ hipError_t launch_prefill_mx(int dtype, int D, DecodeForm f, const DecodeStepPar
     const DecodeLseOut lo = lse != nullptr ? *lse : DecodeLseOut{};
     return p.dyn ? launch_part<prefill_mx_kernel<T, DD, true>, LDS>(grid, block, s, p, mx, lo)
                  : launch_part<prefill_mx_kernel<T, DD, false>, LDS>(grid, block, s, p, mx, lo);
+  });
+}
+
+// launch_prefill_mx's grid, block and LDS on the step entry points (fcsa_forward_kvcache_mx_step): the workgroups of decode-routed sequences
+// exit at once.  rotary: nullptr, or the tables the prologue rotates q by (rotary_dim D, or 64 at D = 128).
+hipError_t launch_prefill_mx_step(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeMx& mx, const DecodeRotary* rotary,
+                                  const DecodeLseOut* lse, hipStream_t s) {
+  if (f.fp8 || !f.step || !f.ragged || !mx_rotary_ok(D, rotary)) return hipErrorInvalidValue;
+  if (p.l2norm && !mx_groups_ok(D, p.groups)) return hipErrorInvalidValue;
+  return dispatch_chunk(dtype, D, [&](auto td) -> hipError_t {
+    using T = typename decltype(td)::T;
+    constexpr int DD = decltype(td)::D;
+    constexpr int LDS = PrefillMxLds<DD>::BYTES;
+    if ((int64_t)p.slots * p.Hk <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((int64_t)p.slots * p.Hk)), block(64 * kMxWaves);
+    const DecodeLseOut lo = lse != nullptr ? *lse : DecodeLseOut{};
+    auto go = [&](auto dyn) -> hipError_t {
+      constexpr bool DY = decltype(dyn)::value;
+      if (rotary != nullptr) return launch_part<rotary_prefill_mx_kernel<T, DD, DY>, LDS>(grid, block, s, p, mx, lo, *rotary);
+      return launch_part<step_prefill_mx_kernel<T, DD, DY>, LDS>(grid, block, s, p, mx, lo);
+    };
+    return p.dyn ? go(std::true_type{}) : go(std::false_type{});
   });
 }
 

@@ -85,7 +85,10 @@ namespace {
   X(forward_kvcache_mx, fcsa_forward_kvcache_mx, false)                                   \
   X(forward_kvcache_mx_ws, fcsa_forward_kvcache_mx_workspace_bytes, false)         \
   /* prompt chunks against an MXFP4 cache */                                              \
-  X(forward_kvcache_mx_prefill, fcsa_forward_kvcache_mx_prefill, false)
+  X(forward_kvcache_mx_prefill, fcsa_forward_kvcache_mx_prefill, false)                   \
+  /* the engine step against an MXFP4 cache, with or without a rotary embedding */        \
+  X(forward_kvcache_mx_step, fcsa_forward_kvcache_mx_step, false)                         \
+  X(forward_kvcache_mx_step_ws, fcsa_forward_kvcache_mx_step_workspace_bytes, false)
 
 struct Abi {
 #define X(member, symbol, required) decltype(&symbol) member = &symbol;
@@ -769,7 +772,7 @@ Tensor varlen_window_attention_autograd(const Tensor& q, const Tensor& k, const 
 //
 // One description of a call, CacheCall: every op function fills the members it has and hands it to kvcache_call, which runs the checks
 // (cache_checks), fills the library's structs (fill_lib_call) and dispatches through the one table of entry points (kEntries).
-enum class Route { Plain, Prefill, Step, Tree, Alibi, Rotary, Mx, MxPrefill };
+enum class Route { Plain, Prefill, Step, Tree, Alibi, Rotary, Mx, MxPrefill, MxStep };
 
 struct CacheCall {
   // what every op has
@@ -788,7 +791,9 @@ struct CacheCall {
   const Tensor *k_block_scale = nullptr, *v_block_scale = nullptr;          // Mx: the scale bytes of an MXFP4 cache (its codes as uint8 tensors)
   bool ragged() const { return cu_q != nullptr; }
   bool fp8() const { return k_scale != nullptr; }
-  bool mx() const { return route == Route::Mx || route == Route::MxPrefill; }      // MxPrefill: the ragged Mx call on the chunk kernel
+  // MxPrefill: the ragged Mx call on the chunk kernel; MxStep: routed over both, with the tables (extra, rotary_sin) where the call has them
+  bool mx() const { return route == Route::Mx || route == Route::MxPrefill || route == Route::MxStep; }
+  bool rotary() const { return route == Route::Rotary || (route == Route::MxStep && extra != nullptr); }
 };
 
 const Tensor* ptr(const optional<Tensor>& t) { return t.has_value() ? &*t : nullptr; }
@@ -902,7 +907,7 @@ CacheKeep cache_checks(const CacheCall& c) {
                       "alibi_slopes must be [heads] (", q.size(1), ") or [sequences, heads] (", seqs_n, ", ", q.size(1), "), got ", alibi.sizes());
     k.slopes = alibi;      // any strides: the kernels take element strides, and a view keeps in-place updates visible to a captured graph
   }
-  if (c.route == Route::Rotary) {
+  if (c.rotary()) {
     // float32 [rows, rotary_dim / 2] on q's device, the last dim contiguous and rows 16-byte aligned (made so otherwise); never read on the host
     const Tensor &rc = *c.extra, &rs = *c.rotary_sin;
     TORCH_CHECK_TYPE(rc.scalar_type() == at::kFloat && rs.scalar_type() == at::kFloat, "rotary_cos / rotary_sin must be float32, got ",
@@ -1000,7 +1005,7 @@ void fill_lib_call(LibCall& l, const CacheCall& c, const CacheKeep& k, const Ten
   const Layout ql = c.ragged() ? kPacked : kDense;      // of q, o, k_new, v_new and the lse
   std::memset(&l, 0, sizeof(l));
   l.ragged = c.ragged(); l.fp8 = c.fp8(); l.win = c.win;
-  l.step = c.route == Route::Step || c.route == Route::Alibi || c.route == Route::Rotary ? &c.step : nullptr;
+  l.step = c.route == Route::Step || c.route == Route::Alibi || c.route == Route::Rotary || c.route == Route::MxStep ? &c.step : nullptr;
   fcsa_problem& p = l.a.p;
   p.dtype = dtype_code(c.q.scalar_type());
   p.batch = (int32_t)k.B; p.heads = (int32_t)k.H; p.kv_heads = (int32_t)k.Hk;
@@ -1041,7 +1046,7 @@ struct EntryPoint {
   size_t (*workspace)(const LibCall&);      // null: that of the call without the lse
   int (*run)(const LibCall&);
 };
-enum Entry { kKvcache, kWindow, kQuant, kVarlen, kLse, kPrefill, kStep, kTree, kAlibi, kRotary, kMx, kMxPrefill };
+enum Entry { kKvcache, kWindow, kQuant, kVarlen, kLse, kPrefill, kStep, kTree, kAlibi, kRotary, kMx, kMxPrefill, kMxStep };
 const EntryPoint kEntries[] = {
     /* kKvcache */ {"fcsa_forward_kvcache", "flash_cosine_sim_attention_with_kvcache",
                     [] { return g_abi.forward_kvcache != nullptr && g_abi.forward_kvcache_ws != nullptr; },
@@ -1084,12 +1089,19 @@ const EntryPoint kEntries[] = {
     /* kMxPrefill: ragged only, no workspace */ {"fcsa_forward_kvcache_mx_prefill", "flash_cosine_sim_attention_mxfp4_prefill_with_kvcache",
      [] { return g_abi.forward_kvcache_mx_prefill != nullptr; }, [](const LibCall&) { return (size_t)0; },
      [](const LibCall& l) { return g_abi.forward_kvcache_mx_prefill(&l.a, &l.kv, &l.mx, &l.seqs, l.win, l.lo.lse != nullptr ? &l.lo : nullptr); }},
+    /* kMxStep: ragged only; the tables where the call has them */ {"fcsa_forward_kvcache_mx_step", "flash_cosine_sim_attention_mxfp4_step_with_kvcache",
+     [] { return g_abi.forward_kvcache_mx_step != nullptr && g_abi.forward_kvcache_mx_step_ws != nullptr; },
+     [](const LibCall& l) { return g_abi.forward_kvcache_mx_step_ws(&l.a.p, &l.kv, &l.mx, &l.seqs, l.win, l.step); },
+     [](const LibCall& l) {
+       return g_abi.forward_kvcache_mx_step(&l.a, &l.kv, &l.mx, &l.seqs, l.win, l.step, l.rotary.cos != nullptr ? &l.rotary : nullptr,
+                                            l.lo.lse != nullptr ? &l.lo : nullptr);
+     }},
 };
 
 // the entry point of a Plain call without the lse: by the ragged / fp8 / window facts
 Entry plain_entry(const CacheCall& c) { return c.ragged() ? kVarlen : c.fp8() ? kQuant : c.win != nullptr ? kWindow : kKvcache; }
-constexpr Entry kOfRoute[] = {kKvcache /* Plain: by the facts instead */, kPrefill, kStep, kTree, kAlibi, kRotary, kMx, kMxPrefill};      // in Route's order
-static_assert(sizeof(kEntries) / sizeof(kEntries[0]) == kMxPrefill + 1 && sizeof(kOfRoute) / sizeof(kOfRoute[0]) == (int)Route::MxPrefill + 1,
+constexpr Entry kOfRoute[] = {kKvcache /* Plain: by the facts instead */, kPrefill, kStep, kTree, kAlibi, kRotary, kMx, kMxPrefill, kMxStep};      // in Route's order
+static_assert(sizeof(kEntries) / sizeof(kEntries[0]) == kMxStep + 1 && sizeof(kOfRoute) / sizeof(kOfRoute[0]) == (int)Route::MxStep + 1,
               "kEntries has one row per Entry, in its order, and kOfRoute one entry per Route");
 Entry entry_of(const CacheCall& c) { return c.route != Route::Plain ? kOfRoute[(int)c.route] : c.lse ? kLse : plain_entry(c); }
 // a call needs its own entry point and those of the calls it is built on
@@ -1271,6 +1283,27 @@ std::tuple<Tensor, Tensor> kvcache_mxfp4_prefill_forward(const Tensor& q, const 
   const OptWin win(left, right);
   c.win = win.ptr(); c.cu_q = ptr(cu_seqlens_q); c.max_seqlen_q = max_seqlen_q; c.lse = return_lse;
   c.route = Route::MxPrefill; c.k_block_scale = &k_block_scale; c.v_block_scale = &v_block_scale;
+  auto [o, lse] = kvcache_call(c);
+  return {o, return_lse ? lse : at::empty({0}, q.options().dtype(at::kFloat))};
+}
+
+// An engine step against an MXFP4 cache (kvcache_mxfp4_step_forward): kvcache_mxfp4_forward's ragged step with the routing fields of
+// kvcache_step_forward and, where given, the two tables of kvcache_rotary_forward (float32 [rows, rotary_dim / 2] on q's device, never read on
+// the host), through fcsa_forward_kvcache_mx_step.  One table without the other is refused.
+std::tuple<Tensor, Tensor> kvcache_mxfp4_step_forward(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& k_block_scale,
+                                                      const Tensor& v_block_scale, const Tensor& cu_seqlens_q, const optional<Tensor>& rotary_cos,
+                                                      const optional<Tensor>& rotary_sin, bool rotary_interleaved, const optional<Tensor>& k_new,
+                                                      const optional<Tensor>& v_new, const optional<Tensor>& cache_seqlens,
+                                                      const optional<Tensor>& block_table, int64_t max_seqlen_q, int64_t max_seqlen_k, double scale,
+                                                      bool causal, bool l2norm_qk, int64_t groups, int64_t left, int64_t right, int64_t chunk_rows,
+                                                      int64_t max_decode_tokens, bool no_decode, bool no_chunk, bool return_lse) {
+  TORCH_CHECK_VALUE(rotary_cos.has_value() == rotary_sin.has_value(), "rotary_cos and rotary_sin must be given together");
+  CacheCall c{q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups};
+  c.step = step_fields(chunk_rows, max_decode_tokens, no_decode, no_chunk);
+  const OptWin win(left, right);
+  c.win = win.ptr(); c.cu_q = &cu_seqlens_q; c.max_seqlen_q = max_seqlen_q; c.lse = return_lse;
+  c.route = Route::MxStep; c.k_block_scale = &k_block_scale; c.v_block_scale = &v_block_scale;
+  c.extra = ptr(rotary_cos); c.rotary_sin = ptr(rotary_sin); c.rotary_interleaved = rotary_interleaved;
   auto [o, lse] = kvcache_call(c);
   return {o, return_lse ? lse : at::empty({0}, q.options().dtype(at::kFloat))};
 }
@@ -1812,6 +1845,16 @@ TORCH_LIBRARY_IMPL(fcsa_mx, CUDA, m) {
   m.impl("kvcache_mxfp4_forward", &kvcache_mxfp4_forward);
   m.impl("kvcache_mxfp4_prefill_forward", &kvcache_mxfp4_prefill_forward);
 }
+
+// the engine step against an MXFP4 cache, in a namespace of its own (the op set of fcsa_mx is pinned).  Forward only: no Autograd kernel.
+TORCH_LIBRARY(fcsa_mx_step, m) {
+  m.def("kvcache_mxfp4_step_forward(Tensor q, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor(c!) k_block_scale, Tensor(d!) v_block_scale, "
+        "Tensor cu_seqlens_q, Tensor? rotary_cos, Tensor? rotary_sin, bool rotary_interleaved, Tensor? k_new, Tensor? v_new, "
+        "Tensor? cache_seqlens, Tensor? block_table, int max_seqlen_q, int max_seqlen_k, float scale, bool causal, bool l2norm_qk, int groups, "
+        "int window_left, int window_right, int chunk_rows, int max_decode_tokens, bool no_decode, bool no_chunk, bool return_lse) "
+        "-> (Tensor, Tensor)");
+}
+TORCH_LIBRARY_IMPL(fcsa_mx_step, CUDA, m) { m.impl("kvcache_mxfp4_step_forward", &kvcache_mxfp4_step_forward); }
 
 // Attention states for training, in a namespace of their own (the op set of `fcsa` is pinned): the attention op with the rows'
 // log-sum-exp as a second differentiable result -- dense, local (window sides other than (-1, -1)) or packed (cu_seqlens given) -- and

@@ -678,8 +678,9 @@ def flash_cosine_sim_attention_mxfp4_with_kvcache(q, k_cache, v_cache, k_block_s
     bytes -- at [cache_seqlens[b], ...) before attention reads the caches.  With l2norm_qk a key only contributes its direction, and a
     per-block power-of-two scale keeps every block of that direction at full e2m1 resolution.  `mxfp4_quantize` / `mxfp4_dequantize`
     convert an existing cache.  CPU tensors take a forward-only path: dequantise, then `cpu.py` (host tables).
-    Prompt chunks of such a cache belong to `flash_cosine_sim_attention_mxfp4_prefill_with_kvcache` (the same arguments).
-    Not taken here: the step, tree, ALiBi, rotary and shared-prefix calls (those functions refuse uint8 caches), e5m2, MXFP6 / MXFP8
+    Prompt chunks of such a cache belong to `flash_cosine_sim_attention_mxfp4_prefill_with_kvcache` (the same arguments), an engine step
+    -- chunks and decodes routed in one call, with or without a rotary embedding -- to `flash_cosine_sim_attention_mxfp4_step_with_kvcache`.
+    Not taken with such a cache: the tree, ALiBi and shared-prefix calls (those functions refuse uint8 caches), e5m2, MXFP6 / MXFP8
     caches, fp4 queries."""
     return _mxfp4_call("flash_cosine_sim_attention_mxfp4_with_kvcache", False, q, k_cache, v_cache, k_block_scale, v_block_scale, cu_seqlens_q,
                        k_new, v_new, cache_seqlens, block_table, max_seqlen_q, max_seqlen_k, scale, groups, causal, l2norm_qk, return_lse,
@@ -724,9 +725,10 @@ def flash_cosine_sim_attention_mxfp4_prefill_with_kvcache(q, k_cache, v_cache, k
 
 
 def _mxfp4_call(fn, chunk, q, k_cache, v_cache, k_block_scale, v_block_scale, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q,
-                max_seqlen_k, scale, groups, causal, l2norm_qk, return_lse, window_size):
+                max_seqlen_k, scale, groups, causal, l2norm_qk, return_lse, window_size, step=None):
     """The one front end of the MXFP4 cache functions: the checks, the CPU path and the op call -- chunk: the op of the multi-wave chunk
-    kernel (packed queries, checked by the caller) in place of the decode kernel's"""
+    kernel (packed queries, checked by the caller) in place of the decode kernel's; step (the engine step; packed queries, checked by the
+    caller): (chunk_rows, max_decode_tokens, rotary) with rotary None or (cos, sin, interleaved), on the op that routes over both kernels"""
     _check_return_lse(return_lse)
     window = _window(window_size)
     ragged = cu_seqlens_q is not None
@@ -759,8 +761,19 @@ def _mxfp4_call(fn, chunk, q, k_cache, v_cache, k_block_scale, v_block_scale, cu
             raise ValueError("CPU tensors take host cu_seqlens_q and cache_seqlens tables")
         new_q = None
         lens = c.lens if c.lens is not None else [c.capacity - (0 if ragged else c.appended[0])] * B
+        q_in, k_in = q.detach(), k_new
+        if step is not None and step[2] is not None:      # rotate in float32 before anything is rounded: k_new at its slot, q at L_b - N_b + i
+            cq, q_in = cu_seqlens_q.tolist(), q.detach().float().clone()
+            k_in = None if k_new is None else k_new.detach().float().clone()
+            for b in range(B):
+                lo, hi = cq[b], cq[b + 1]
+                n0 = min(max(lens[b], 0), c.capacity)
+                first = min(n0 + (hi - lo if k_new is not None else 0), c.capacity) - (hi - lo)
+                q_in[lo:hi] = _cpu.rotate_rows_cpu(q_in[lo:hi].transpose(0, 1), [first + i for i in range(hi - lo)], *step[2]).transpose(0, 1)
+                if k_in is not None:
+                    k_in[lo:hi] = _cpu.rotate_rows_cpu(k_in[lo:hi].transpose(0, 1), [n0 + i for i in range(hi - lo)], *step[2]).transpose(0, 1)
         if k_new is not None:      # quantise once: the bytes go into the caller's caches, their values into the dense path's append
-            (kc, ks), (vc, vs) = mxfp4_quantize(k_new), mxfp4_quantize(v_new)
+            (kc, ks), (vc, vs) = mxfp4_quantize(k_in), mxfp4_quantize(v_new)
             new_q = (mxfp4_dequantize(kc, ks, q.dtype), mxfp4_dequantize(vc, vs, q.dtype))
             rows = (kc, ks, vc, vs) if ragged else tuple(t.transpose(1, 2).flatten(0, 1) for t in (kc, ks, vc, vs))
             starts = cu_seqlens_q.tolist() if ragged else [b * k_new.shape[2] for b in range(B + 1)]
@@ -768,14 +781,26 @@ def _mxfp4_call(fn, chunk, q, k_cache, v_cache, k_block_scale, v_block_scale, cu
         dense = (mxfp4_dequantize(k_cache, k_block_scale, q.dtype), mxfp4_dequantize(v_cache, v_block_scale, q.dtype))
         kw = dict(scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, window_size=window, return_lse=bool(return_lse))
         if ragged:
-            return _cpu.attention_forward_kvcache_varlen_cpu(q.detach(), *dense, cu_seqlens_q, *(new_q or (None, None)), lens, block_table, **kw)
+            res = _cpu.attention_forward_kvcache_varlen_cpu(q_in, *dense, cu_seqlens_q, *(new_q or (None, None)), lens, block_table, **kw)
+            if q_in.dtype == q.dtype:
+                return res
+            return (res[0].to(q.dtype), res[1]) if return_lse else res.to(q.dtype)      # (a rotated q is float32: o in q's type, as on the device)
         return _cpu.attention_forward_kvcache_cpu(q.detach(), *dense, *(new_q or (None, None)), lens, block_table, **kw)
     if ragged and q.shape[0] == 0:
         return _empty_result(q, return_lse)
     max_q = 0 if not ragged else (q.shape[0] if max_seqlen_q is None else min(int(max_seqlen_q), q.shape[0]))
     cu_q = cu_seqlens_q.to(q.device, non_blocking=True) if ragged else None
+    routing = None if step is None else _step_routing(c, q.shape[0], q.shape[1], step[0], step[1])
     k_cache, v_cache, cache_seqlens, block_table = c.on_device()
     _torch_ops.load()
+    if step is not None:
+        cos, sin, interleaved = step[2] if step[2] is not None else (None, None, False)
+        move = lambda t: None if t is None else t.to(q.device, non_blocking=True)
+        o, lse = torch.ops.fcsa_mx_step.kvcache_mxfp4_step_forward(q, k_cache, v_cache, k_block_scale, v_block_scale, cu_q, move(cos), move(sin),
+                                                                   bool(interleaved), k_new, v_new, cache_seqlens, block_table, max_q, c.max_k,
+                                                                   float(scale), bool(causal), bool(l2norm_qk), int(groups), window[0], window[1],
+                                                                   *routing, bool(return_lse))
+        return (o, lse) if return_lse else o
     op = torch.ops.fcsa_mx.kvcache_mxfp4_prefill_forward if chunk else torch.ops.fcsa_mx.kvcache_mxfp4_forward
     o, lse = op(q, k_cache, v_cache, k_block_scale, v_block_scale, cu_q, k_new, v_new, cache_seqlens, block_table, max_q, c.max_k, float(scale),
                 bool(causal), bool(l2norm_qk), int(groups), window[0], window[1], bool(return_lse))
@@ -1024,6 +1049,42 @@ def flash_cosine_sim_attention_alibi_with_kvcache(q, k_cache, v_cache, cu_seqlen
                         cpu_kw=dict(scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, alibi_slopes=alibi_slopes.detach()))
 
 
+def _rotary_tables(fn, q, cu_seqlens_q, k_new, cache_seqlens, rotary_cos, rotary_sin):
+    """The checks of a pair of rotary tables, for the two step functions that take them (fn: the one named in the messages): float32
+    [rows, rotary_dim / 2] of one shape, a 16-bit q, dim_head 64 / 128 with rotary_dim dim_head or 64 at 128, host tables finite and device
+    tables on q's device, host lengths inside the rows.  Returns the two tables with a contiguous last dim."""
+    for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError(f"{name} must be a float32 tensor [rows, rotary_dim / 2], got {getattr(t, 'dtype', type(t).__name__)}")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError(f"{fn} takes float16 or bfloat16 q, got {q.dtype}")
+    if rotary_cos.dim() != 2 or rotary_cos.shape != rotary_sin.shape or rotary_cos.shape[0] < 1:
+        raise ValueError(f"rotary_cos / rotary_sin must be [rows, rotary_dim / 2] with the same shape and rows >= 1, got {tuple(rotary_cos.shape)} and "
+                         f"{tuple(rotary_sin.shape)}")
+    rows, rotary_dim = rotary_cos.shape[0], 2 * rotary_cos.shape[1]
+    if q.dim() == 3:
+        D = q.shape[-1]
+        if D not in (64, 128):
+            raise ValueError(f"{fn} takes head dimensions 64 and 128, got {D}")
+        if rotary_dim != D and not (rotary_dim == 64 and D == 128):
+            raise ValueError(f"rotary_dim ({rotary_dim}) must be dim_head ({D}), or 64 at dim_head 128")
+    tables = []
+    for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+        if t.device.type == "cpu":
+            if not bool(torch.isfinite(t).all()):
+                raise ValueError(f"{name} must be finite")
+        elif t.device != q.device:
+            raise ValueError(f"{name} is on {t.device} but q is on {q.device}")
+        tables.append(t.detach() if t.stride(-1) == 1 else t.detach().contiguous())
+    # host lengths against the tables' rows: the last position any sequence of the step touches
+    counts, lens, appended = _host_view(q, cu_seqlens_q, k_new, cache_seqlens)
+    if lens is not None and counts is not None:
+        for b, (n0, n, a) in enumerate(zip(lens, counts, appended)):
+            if n > 0 and n0 + a > rows:
+                raise ValueError(f"sequence {b}: position {n0 + a - 1} is beyond the {rows} rows of rotary_cos / rotary_sin")
+    return tables
+
+
 def flash_cosine_sim_attention_rotary_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new=None, v_new=None, cache_seqlens=None,
                                                    block_table=None, max_seqlen_q=None, max_seqlen_k=None, scale=8, groups=1, causal=False,
                                                    l2norm_qk=True, k_scale=None, v_scale=None, return_lse=False, window_size=(-1, -1),
@@ -1066,35 +1127,7 @@ def flash_cosine_sim_attention_rotary_with_kvcache(q, k_cache, v_cache, cu_seqle
     if rotary_cos is None or rotary_sin is None:
         raise ValueError("rotary_cos and rotary_sin must be given together")
     window, chunk_rows, max_decode_tokens = _step_arguments(return_lse, window_size, chunk_rows, max_decode_tokens)
-    for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-            raise TypeError(f"{name} must be a float32 tensor [rows, rotary_dim / 2], got {getattr(t, 'dtype', type(t).__name__)}")
-    if q.dtype not in (torch.float16, torch.bfloat16):
-        raise TypeError(f"{fn} takes float16 or bfloat16 q, got {q.dtype}")
-    if rotary_cos.dim() != 2 or rotary_cos.shape != rotary_sin.shape or rotary_cos.shape[0] < 1:
-        raise ValueError(f"rotary_cos / rotary_sin must be [rows, rotary_dim / 2] with the same shape and rows >= 1, got {tuple(rotary_cos.shape)} and "
-                         f"{tuple(rotary_sin.shape)}")
-    rows, rotary_dim = rotary_cos.shape[0], 2 * rotary_cos.shape[1]
-    if q.dim() == 3:
-        D = q.shape[-1]
-        if D not in (64, 128):
-            raise ValueError(f"{fn} takes head dimensions 64 and 128, got {D}")
-        if rotary_dim != D and not (rotary_dim == 64 and D == 128):
-            raise ValueError(f"rotary_dim ({rotary_dim}) must be dim_head ({D}), or 64 at dim_head 128")
-    tables = []
-    for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
-        if t.device.type == "cpu":
-            if not bool(torch.isfinite(t).all()):
-                raise ValueError(f"{name} must be finite")
-        elif t.device != q.device:
-            raise ValueError(f"{name} is on {t.device} but q is on {q.device}")
-        tables.append(t.detach() if t.stride(-1) == 1 else t.detach().contiguous())
-    # host lengths against the tables' rows: the last position any sequence of the step touches
-    counts, lens, appended = _host_view(q, cu_seqlens_q, k_new, cache_seqlens)
-    if lens is not None and counts is not None:
-        for b, (n0, n, a) in enumerate(zip(lens, counts, appended)):
-            if n > 0 and n0 + a > rows:
-                raise ValueError(f"sequence {b}: position {n0 + a - 1} is beyond the {rows} rows of rotary_cos / rotary_sin")
+    tables = _rotary_tables(fn, q, cu_seqlens_q, k_new, cache_seqlens, rotary_cos, rotary_sin)
     op = lambda s: torch.ops.fcsa_rotary.kvcache_rotary_forward(q, s.k_cache, s.v_cache, s.cu_q, tables[0].to(q.device, non_blocking=True),
                                                                 tables[1].to(q.device, non_blocking=True), bool(rotary_interleaved), k_new, v_new,
                                                                 s.cache_seqlens, s.block_table, s.k_scale, s.v_scale, s.max_q, s.max_k,
@@ -1104,6 +1137,52 @@ def flash_cosine_sim_attention_rotary_with_kvcache(q, k_cache, v_cache, cu_seqle
                         v_scale, return_lse=return_lse, window=window, op=op, routing=(chunk_rows, max_decode_tokens),
                         cpu_kw=dict(scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk,
                                     rotary=(tables[0], tables[1], bool(rotary_interleaved))))
+
+
+def flash_cosine_sim_attention_mxfp4_step_with_kvcache(q, k_cache, v_cache, k_block_scale, v_block_scale, cu_seqlens_q=None, k_new=None, v_new=None,
+                                                       cache_seqlens=None, block_table=None, max_seqlen_q=None, max_seqlen_k=None, scale=8,
+                                                       groups=1, causal=False, l2norm_qk=True, return_lse=False, window_size=(-1, -1),
+                                                       chunk_rows=None, max_decode_tokens=None, rotary_cos=None, rotary_sin=None,
+                                                       rotary_interleaved=False):
+    """The step of a continuous-batching engine against MXFP4 caches, in one call: `flash_cosine_sim_attention_step_with_kvcache`'s routing
+    and `flash_cosine_sim_attention_rotary_with_kvcache`'s embedding on the caches of `flash_cosine_sim_attention_mxfp4_with_kvcache`.
+
+    The first eighteen parameters are that last function's, with its defaults; q must be packed [total_q, H, D] with cu_seqlens_q.  One
+    quantising append, then sequence b (N_b rows, G = H / Hk) takes the MXFP4 chunk kernel iff G * N_b >= chunk_rows and the MXFP4 decode
+    kernel with key splits otherwise; both decide it on the device from the clamped table, so every row is written exactly once.
+    chunk_rows (default 1024) means what it means on the 16-bit step call.
+    max_decode_tokens: PASS IT whenever cu_seqlens_q is a device tensor -- the packed rows of the decode-routed sequences, which your
+    scheduler knows.  Without it the decode side's key splits are sized as if every packed row decoded, and a batch of decodes plus a
+    long chunk measured 1.1 - 2.7x slower than with it.  A host cu_seqlens_q is counted for you.  As on the 16-bit step call it is an
+    upper bound that only sizes the split count: a wrong bound changes speed, never the result.
+    Without tables a chunk-routed sequence's rows of o and lse are bit for bit those of
+    `flash_cosine_sim_attention_mxfp4_prefill_with_kvcache`, a decode-routed sequence's bit for bit those of
+    `flash_cosine_sim_attention_mxfp4_with_kvcache` at this call's split count, and the four cache tensors are the bytes either leaves.
+    rotary_cos, rotary_sin, rotary_interleaved: as on `flash_cosine_sim_attention_rotary_with_kvcache` -- float32 [rows, rotary_dim / 2],
+    rotary_dim dim_head or 64 at dim_head 128, NeoX pairs (f, f + rotary_dim / 2) or interleaved (2 f, 2 f + 1), every query at its own
+    position pos_i = L_b - N_b + i whether or not the call is causal, positions clamped to the tables on the device, host cache_seqlens
+    beyond the tables refused.  k_new is unpacked to float32, rotated (t = fl(partner * sin), then one fused multiply-add) and quantised as
+    `mxfp4_quantize` states, the per-block amax taken over the ROTATED values; v_new is quantised unrotated; the raw q row is rotated in
+    float32 in the prologue of both kernels, then normalised, scaled and rounded once.  No rotated 16-bit copy of q or k_new exists.
+    Tables need dim_head 64 or 128.
+    Where the MXFP4 chunk kernel has no form -- dim_head 32 / 96, a window_size that hides a key -- every sequence takes the decode kernel,
+    decided from the arguments alone.  With device tables the call does not synchronise and captures in a graph.  CPU tensors take a
+    forward-only path: rotate in float32, quantise and append, dequantise, then `cpu.py` (host tables).
+    Not taken with MXFP4 caches: the tree, ALiBi and shared-prefix calls, and windows on the chunk kernel.  Forward only."""
+    fn, other = "flash_cosine_sim_attention_mxfp4_step_with_kvcache", "flash_cosine_sim_attention_mxfp4_with_kvcache"
+    _, chunk_rows, max_decode_tokens = _step_arguments(return_lse, window_size, chunk_rows, max_decode_tokens)
+    if cu_seqlens_q is None or q.dim() != 3:
+        raise ValueError(f"{fn} takes packed queries [total_q, heads, dim_head] with cu_seqlens_q, got q {tuple(q.shape)}"
+                         f"{'' if cu_seqlens_q is not None else ' and cu_seqlens_q=None'}: {other} takes equal-N calls")
+    rotary = None
+    if rotary_cos is not None or rotary_sin is not None:
+        if rotary_cos is None or rotary_sin is None:
+            raise ValueError("rotary_cos and rotary_sin must be given together")
+        tables = _rotary_tables(fn, q, cu_seqlens_q, k_new, cache_seqlens, rotary_cos, rotary_sin)      # (with tables: dim_head 64 / 128 only)
+        rotary = (tables[0], tables[1], bool(rotary_interleaved))
+    return _mxfp4_call(fn, False, q, k_cache, v_cache, k_block_scale, v_block_scale, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table,
+                       max_seqlen_q, max_seqlen_k, scale, groups, causal, l2norm_qk, return_lse, window_size,
+                       step=(chunk_rows, max_decode_tokens, rotary))
 
 
 def flash_cosine_sim_attention_tree_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new=None, v_new=None, cache_seqlens=None,

@@ -541,8 +541,8 @@ int    fcsa_forward_kvcache_rotary(const fcsa_forward_args* args, const fcsa_kvc
  * advanced, as in fcsa_forward_kvcache.
  * Launches: "kv_append_mx" (when rows are appended), "decode_mx" and the 16-bit call's combine ("decode_combine[_lse][_ragged]"): the V
  * scales are applied as the codes are read.
- * Prompt chunks: fcsa_forward_kvcache_mx_prefill, below.
- * Not offered with such a cache: the step, tree, ALiBi, rotary and shared-prefix calls; other element formats (e5m2 scales,
+ * Prompt chunks: fcsa_forward_kvcache_mx_prefill, below; the engine step with routing and a rotary embedding: fcsa_forward_kvcache_mx_step.
+ * Not offered with such a cache: the tree, ALiBi and shared-prefix calls; other element formats (e5m2 scales,
  * MXFP6, MXFP8); fp4 queries and the scaled MFMA instructions. */
 #define FCSA_CACHE_MXFP4 2            /* fcsa_kvcache_mx.format */
 typedef struct fcsa_kvcache_mx {
@@ -568,6 +568,32 @@ size_t fcsa_forward_kvcache_mx_workspace_bytes(const fcsa_problem* p, const fcsa
  * Every refusal happens before any launch.  Launches: "kv_append_mx" (when rows are appended) and "prefill_mx". */
 int    fcsa_forward_kvcache_mx_prefill(const fcsa_forward_args* args, const fcsa_kvcache* cache, const fcsa_kvcache_mx* mx,
                                        const fcsa_varlen* seqs, const fcsa_window* window, const fcsa_lse_out* lse_out);
+
+/* An engine step against an MXFP4 cache: fcsa_forward_kvcache_step's routing and fcsa_forward_kvcache_rotary's embedding on the caches of
+ * fcsa_forward_kvcache_mx (additive: no existing struct changes and FCSA_ABI_VERSION stays 4).  One quantising append, then every sequence
+ * of the packed batch on the MXFP4 kernel built for its row count: the chunk kernel of fcsa_forward_kvcache_mx_prefill iff
+ * G * N_b >= chunk_rows, the decode kernel of fcsa_forward_kvcache_mx with key splits otherwise -- both decide it on the device from the
+ * clamped table, so every row is written exactly once.
+ * args, cache, mx, seqs, window and lse_out are read as fcsa_forward_kvcache_mx reads them with seqs set (seqs NULL: FCSA_ERR_INVALID_ARG),
+ * step as fcsa_forward_kvcache_step reads it, rotary as fcsa_forward_kvcache_rotary reads it -- or NULL: no embedding.
+ * Result without tables: a chunk-routed sequence's rows of o and lse are bit for bit fcsa_forward_kvcache_mx_prefill's, a decode-routed
+ * sequence's bit for bit fcsa_forward_kvcache_mx's at this call's split count, and the four cache tensors are the bytes either leaves.
+ * With tables: pos_i = L_b - N_b + i as in fcsa_forward_kvcache_rotary; k_new row i is unpacked to float32, rotated by table row pos_i
+ * (t = fl(partner * sin), then one fused multiply-add) and quantised by the rule above, the per-block amax taken over the ROTATED values;
+ * v_new is quantised unrotated; the raw q row is rotated in float32 in the prologue of both kernels, then normalised, scaled and rounded
+ * once.  No rotated 16-bit copy of q or k_new exists.  Positions are clamped to the tables on the device.
+ * Where the MXFP4 chunk kernel has no form every sequence takes the decode kernel, decided from the arguments alone: dim_head 32 / 96
+ * (the call is fcsa_forward_kvcache_mx's ragged step; tables: FCSA_ERR_UNSUPPORTED) and a window that hides a key (left >= 0, or
+ * right >= 0 without p.causal).
+ * workspace: >= fcsa_forward_kvcache_mx_step_workspace_bytes() bytes for the same arguments, 256-byte aligned (0 for a call refused as
+ * unsupported).  Device tables are never read by the host: the call does not synchronise and can be captured in a graph.
+ * Launches, back to back on args->stream: "kv_append_mx" or "kv_append_mx_rotary" (when appending), "step_decode_mx" or "rotary_decode_mx"
+ * and the 16-bit "step_combine[_lse]" (skipped under no_decode), "step_prefill_mx" or "rotary_prefill_mx" (skipped under no_chunk). */
+int    fcsa_forward_kvcache_mx_step(const fcsa_forward_args* args, const fcsa_kvcache* cache, const fcsa_kvcache_mx* mx,
+                                    const fcsa_varlen* seqs, const fcsa_window* window, const fcsa_kvcache_step* step,
+                                    const fcsa_rotary* rotary, const fcsa_lse_out* lse_out);
+size_t fcsa_forward_kvcache_mx_step_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* cache, const fcsa_kvcache_mx* mx,
+                                                    const fcsa_varlen* seqs, const fcsa_window* window, const fcsa_kvcache_step* step);
 
 /* The same linear position bias in the training kernels, forward and backward: fcsa_forward_window / fcsa_backward_window with one more
  * argument, the slopes (additive: no existing struct changes and FCSA_ABI_VERSION stays 4).  A model trained through these entries is
