@@ -8,9 +8,9 @@ from .ops import (flash_cosine_sim_attention, flash_cosine_sim_attention_local, 
                   flash_cosine_sim_attention_alibi_with_kvcache, flash_cosine_sim_attention_alibi,
                   flash_cosine_sim_attention_rotary_with_kvcache,
                   flash_cosine_sim_attention_mxfp4_with_kvcache, flash_cosine_sim_attention_mxfp4_prefill_with_kvcache,
-                  flash_cosine_sim_attention_mxfp4_step_with_kvcache,
+                  flash_cosine_sim_attention_mxfp4_step_with_kvcache, flash_cosine_sim_attention_mxfp4_tree_with_kvcache,
                   mxfp4_quantize, mxfp4_dequantize,
-                  kvcache_keep_accepted,
+                  kvcache_keep_accepted, mxfp4_kvcache_keep_accepted,
                   flash_cosine_sim_attention_with_shared_prefix, merge_attention_states,
                   flash_cosine_sim_attention_with_lse, merge_attention_states_with_grad,
                   plain_cosine_sim_attention, l2norm_tensors, FlashCosineSimAttention)
@@ -24,9 +24,9 @@ __all__ = ['flash_cosine_sim_attention', 'flash_cosine_sim_attention_local', 'fl
            'flash_cosine_sim_attention_alibi_with_kvcache', 'flash_cosine_sim_attention_alibi',
            'flash_cosine_sim_attention_rotary_with_kvcache',
            'flash_cosine_sim_attention_mxfp4_with_kvcache', 'flash_cosine_sim_attention_mxfp4_prefill_with_kvcache',
-           'flash_cosine_sim_attention_mxfp4_step_with_kvcache',
+           'flash_cosine_sim_attention_mxfp4_step_with_kvcache', 'flash_cosine_sim_attention_mxfp4_tree_with_kvcache',
            'mxfp4_quantize', 'mxfp4_dequantize',
-           'kvcache_keep_accepted',
+           'kvcache_keep_accepted', 'mxfp4_kvcache_keep_accepted',
            'flash_cosine_sim_attention_with_shared_prefix', 'merge_attention_states',
            'flash_cosine_sim_attention_with_lse', 'merge_attention_states_with_grad',
            'plain_cosine_sim_attention', 'l2norm_tensors', 'debug', 'FlashCosineSimAttention']

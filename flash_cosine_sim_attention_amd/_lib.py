@@ -109,7 +109,8 @@ EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fc
            "fcsa_forward_kvcache_tree", "fcsa_kvcache_compact", "fcsa_forward_kvcache_alibi",
            "fcsa_forward_alibi", "fcsa_backward_alibi", "fcsa_forward_alibi_workspace_bytes", "fcsa_backward_alibi_workspace_bytes",
            "fcsa_forward_kvcache_rotary", "fcsa_forward_kvcache_mx", "fcsa_forward_kvcache_mx_workspace_bytes",
-           "fcsa_forward_kvcache_mx_prefill", "fcsa_forward_kvcache_mx_step", "fcsa_forward_kvcache_mx_step_workspace_bytes")
+           "fcsa_forward_kvcache_mx_prefill", "fcsa_forward_kvcache_mx_step", "fcsa_forward_kvcache_mx_step_workspace_bytes",
+           "fcsa_forward_kvcache_mx_tree", "fcsa_forward_kvcache_mx_tree_workspace_bytes", "fcsa_kvcache_mx_compact")
 
 _lib = None
 
@@ -258,6 +259,16 @@ def load():
         lib.fcsa_kvcache_compact.argtypes = [C.POINTER(KvCache), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32,
                                              C.c_void_p, C.c_void_p]
         lib.fcsa_kvcache_compact.restype = C.c_int
+    if hasattr(lib, "fcsa_forward_kvcache_mx_tree"):      # (likewise: an FCSA_LIB build from before tree attention on MXFP4 caches)
+        lib.fcsa_forward_kvcache_mx_tree.argtypes = [C.POINTER(ForwardArgs), C.POINTER(KvCache), C.POINTER(KvCacheMx), C.POINTER(Varlen),
+                                                     C.POINTER(Window), C.POINTER(TreeMask), C.POINTER(LseOut)]
+        lib.fcsa_forward_kvcache_mx_tree.restype = C.c_int
+        lib.fcsa_forward_kvcache_mx_tree_workspace_bytes.argtypes = [C.POINTER(Problem), C.POINTER(KvCache), C.POINTER(KvCacheMx),
+                                                                     C.POINTER(Varlen)]
+        lib.fcsa_forward_kvcache_mx_tree_workspace_bytes.restype = C.c_size_t
+        lib.fcsa_kvcache_mx_compact.argtypes = [C.POINTER(KvCache), C.POINTER(KvCacheMx), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                                                C.c_int32, C.c_void_p, C.c_void_p]
+        lib.fcsa_kvcache_mx_compact.restype = C.c_int
     lib.fcsa_last_error.argtypes = []
     lib.fcsa_last_error.restype = C.c_char_p
     ver = lib.fcsa_debug(None, 0)

@@ -102,10 +102,15 @@ def _register_fakes():
             return q.new_empty(q.shape), q.new_empty(q.shape[:-1], dtype=torch.float32)
 
     # an MXFP4 cache (namespace fcsa_mx; the engine step: fcsa_mx_step), decode, chunk and step ops alike: the lse is empty unless asked for
-    for op in ("fcsa_mx::kvcache_mxfp4_forward", "fcsa_mx::kvcache_mxfp4_prefill_forward", "fcsa_mx_step::kvcache_mxfp4_step_forward"):
+    for op in ("fcsa_mx::kvcache_mxfp4_forward", "fcsa_mx::kvcache_mxfp4_prefill_forward", "fcsa_mx_step::kvcache_mxfp4_step_forward",
+               "fcsa_mx_tree::kvcache_mxfp4_tree_forward"):
         @torch.library.register_fake(op)
         def _(q, *args):
             return q.new_empty(q.shape), q.new_empty(q.shape[:-1] if args[-1] else (0,), dtype=torch.float32)
+
+    @torch.library.register_fake("fcsa_mx_tree::kvcache_mxfp4_compact")
+    def _(k_cache, v_cache, k_block_scale, v_block_scale, cache_seqlens, accepted, num_accepted, block_table):
+        return None
 
     @torch.library.register_fake("fcsa_tree::kvcache_compact")
     def _(k_cache, v_cache, cache_seqlens, accepted, num_accepted, block_table):

@@ -425,3 +425,10 @@ def kvcache_keep_accepted_cpu(k_cache, v_cache, seqlens, accepted, num_accepted,
         for (_, dst), (kr, vr) in zip(moves, held):
             row(k_cache, b, dst).copy_(kr)
             row(v_cache, b, dst).copy_(vr)
+
+
+def mxfp4_kvcache_keep_accepted_cpu(k_cache, v_cache, k_block_scale, v_block_scale, seqlens, accepted, num_accepted, block_table=None):
+    """`mxfp4_kvcache_keep_accepted` on host tensors, in place: `kvcache_keep_accepted_cpu`'s moves on the codes and on the scale bytes (the
+    same positions of the same pool, through the same block table)."""
+    kvcache_keep_accepted_cpu(k_cache, v_cache, seqlens, accepted, num_accepted, block_table)
+    kvcache_keep_accepted_cpu(k_block_scale, v_block_scale, seqlens, accepted, num_accepted, block_table)

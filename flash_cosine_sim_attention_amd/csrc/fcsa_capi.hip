@@ -1207,6 +1207,54 @@ int decode_call(const DecodeCall& c) {
   return timed(m.name, m.what, s, [&] { return fcsa::launch_decode_combine(p.dtype, p.dim_head, form, dp, c.lse != nullptr ? &lo : nullptr, s); });
 }
 
+// A tree step on an MXFP4 cache (fcsa_forward_kvcache_mx_tree): the ragged MXFP4 call's checks, window-less sides, quantising append and 16-bit
+// combine around the 4-wave verify kernel (fcsa_verify_mx.hip).  Its plan is decode_plan's with 64-row slots: fcsa::prefill_slots flat slots of
+// kVerifyRows token-major rows per K/V head, the decode split rule (fcsa::decode_splits) fed that slot count, and the decode workspace --
+// f32 partial P~V, then (row max, row sum), of every split of every packed row.
+DecodePlan verify_plan(const fcsa_problem& p, const fcsa_kvcache& kv, const fcsa_varlen& seqs) {
+  DecodePlan d;
+  const int G = p.kv_heads > 0 ? p.heads / p.kv_heads : 0;
+  const int max_k = std::min(std::max(p.k_len, 0), std::max(kv.capacity, 0));
+  const int64_t total_q = std::max<int64_t>(seqs.total_q, 0);
+  d.row_tiles = 0;
+  d.slots = fcsa::prefill_slots(total_q, std::max(p.batch, 0), G, fcsa::kVerifyRows);
+  d.splits = fcsa::decode_splits(1, p.kv_heads, (int)std::min<int64_t>(d.slots, INT32_MAX), max_k, p.dim_head, fcsa::cu_count());
+  const size_t rows = (size_t)total_q * std::max(p.heads, 0);
+  d.ws_ml = align_up(rows * d.splits * std::max(p.dim_head, 0) * 4, 256);
+  d.total = rows == 0 ? 0 : d.ws_ml + align_up(rows * d.splits * 8, 256);
+  return d;
+}
+// what the tree call refuses beyond mx_supported: the kernel exists for the 16-bit types at dim_head 64 / 128
+int mx_tree_supported(const fcsa_problem& p, const fcsa_kvcache_mx& mx) {
+  if (int rc = mx_supported(p, mx)) return rc;
+  if (!has_chunk_kernel(p))
+    return fail(FCSA_ERR_UNSUPPORTED, "kvcache_mx_tree: dim_head %d is not supported (64 or 128, f16 or bf16: the tree kernel of an MXFP4 cache)", p.dim_head);
+  return FCSA_OK;
+}
+int verify_call(const DecodeCall& c) {
+  if (int rc = check_kvcache_varlen(c)) return rc;
+  const fcsa_forward_args* a = c.a;
+  const fcsa_problem& p = a->p;
+  const DecodeWindow win = decode_window(p, *c.kv, true, nullptr);      // open sides: the words state the visibility
+  const DecodePlan d = verify_plan(p, *c.kv, *c.seqs);
+  if (d.slots * std::max(p.kv_heads, 1) * d.splits > INT32_MAX) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_mx_tree: grid above 2^31 workgroups");
+  if (p.batch == 0 || c.seqs->total_q == 0) return FCSA_OK;      // no packed row: nothing to append, nothing to write
+  const bool rows = p.heads > 0;
+  if (rows)
+    if (int rc = check_workspace("kvcache_mx_tree", *a, d)) return rc;
+  const fcsa::DecodeStepParams dp = decode_params(c, win, d);
+  const fcsa::DecodeLseOut lo = c.lse != nullptr ? lse_view(*c.lse, true) : fcsa::DecodeLseOut{};
+  const fcsa::DecodeForm form = {false, true};
+  hipStream_t s = static_cast<hipStream_t>(a->stream);
+  if (int rc = append_launch(c, form, dp, s)) return rc;
+  if (!rows) return FCSA_OK;
+  const fcsa::DecodeMx mx = mx_view(*c.mx);
+  const fcsa::DecodeTreeMask tm = {c.tree->mask};
+  if (int rc = timed("verify_mx", "verify (mxfp4, tree)", s, [&] { return fcsa::launch_verify_mx(p.dtype, p.dim_head, form, dp, mx, tm, s); })) return rc;
+  const LaunchName& m = kCombineName[1][0][c.lse != nullptr];
+  return timed(m.name, m.what, s, [&] { return fcsa::launch_decode_combine(p.dtype, p.dim_head, form, dp, c.lse != nullptr ? &lo : nullptr, s); });
+}
+
 // A prompt chunk against the cache (fcsa_forward_kvcache_prefill): the ragged step's checks, its append with the parameter block the ragged
 // call fills, then one launch of the multi-wave kernel (fcsa_prefill.hip) with 128-row slots, one split and no workspace.
 // c.mx (fcsa_forward_kvcache_mx_prefill): the ragged MXFP4 call's checks (check_mx behind check_kvcache_varlen), its quantising append, and
@@ -1473,6 +1521,68 @@ size_t fcsa_forward_kvcache_mx_step_workspace_bytes(const fcsa_problem* p, const
   if (p == nullptr || kv == nullptr || mx == nullptr || seqs == nullptr || step == nullptr || mx_supported(*p, *mx) != FCSA_OK) return 0;
   if (!has_chunk_kernel(*p)) return decode_workspace_bytes(p, kv, seqs, w, true);
   return step_plan(*p, *kv, *seqs, mx_step_fields(*p, w, *step), decode_window(*p, *kv, true, w).reach()).total;
+}
+
+// A tree step on an MXFP4 cache: the ragged MXFP4 call's description with the visibility words added, on verify_call.
+int fcsa_forward_kvcache_mx_tree(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_kvcache_mx* mx, const fcsa_varlen* seqs,
+                                 const fcsa_window* w, const fcsa_tree_mask* tree, const fcsa_lse_out* lse) {
+  if (a == nullptr || kv == nullptr || mx == nullptr || seqs == nullptr || tree == nullptr)
+    return fail(FCSA_ERR_INVALID_ARG, "kvcache_mx_tree: null argument");
+  if (int rc = mx_tree_supported(a->p, *mx)) return rc;
+  if (a->p.causal != 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_mx_tree: causal must be 0 (the mask states the visibility)");
+  if (w != nullptr && (w->left >= 0 || w->right >= 0))
+    return fail(FCSA_ERR_INVALID_ARG, "kvcache_mx_tree: a tree step takes no window (%d, %d)", w->left, w->right);
+  if (tree->reserved != 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_mx_tree: reserved (%lld) is 0", (long long)tree->reserved);
+  const bool rows = a->p.batch > 0 && a->p.heads > 0 && seqs->total_q > 0;
+  if (rows && tree->mask == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_mx_tree: mask: null pointer");
+  if ((reinterpret_cast<uintptr_t>(tree->mask) & 7) != 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_mx_tree: mask not 8-byte aligned");
+  if (rows && lse != nullptr && lse->lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_mx_tree: lse: null pointer");
+  DecodeCall c{a, kv, seqs, nullptr, nullptr, lse};
+  c.tree = tree;
+  c.mx = mx;
+  return verify_call(c);
+}
+size_t fcsa_forward_kvcache_mx_tree_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv, const fcsa_kvcache_mx* mx, const fcsa_varlen* seqs) {
+  if (p == nullptr || kv == nullptr || mx == nullptr || seqs == nullptr || mx_tree_supported(*p, *mx) != FCSA_OK) return 0;
+  return verify_plan(*p, *kv, *seqs).total;
+}
+
+// fcsa_kvcache_compact on the four tensors of an MXFP4 cache: the same checks with one-byte elements and rows of dim_head / 2 codes.
+int fcsa_kvcache_mx_compact(const fcsa_kvcache* kv, const fcsa_kvcache_mx* mx, int32_t batch, int32_t kv_heads, int32_t dim_head,
+                            const int32_t* accepted, int64_t accepted_stride, int32_t max_accepted, const int32_t* num_accepted, void* stream) {
+  if (kv == nullptr || mx == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_mx_compact: null argument");
+  if (mx->format != FCSA_CACHE_MXFP4)
+    return fail(FCSA_ERR_UNSUPPORTED, "kvcache_mx_compact: format %d not supported (expected FCSA_CACHE_MXFP4 = %d)", mx->format, FCSA_CACHE_MXFP4);
+  if (batch < 0 || kv_heads < 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_mx_compact: negative size (B=%d Hk=%d)", batch, kv_heads);
+  if (dim_head != 32 && dim_head != 64 && dim_head != 96 && dim_head != 128)
+    return fail(FCSA_ERR_UNSUPPORTED, "kvcache_mx_compact: dim_head %d not in {32, 64, 96, 128}", dim_head);
+  if (max_accepted < 1 || max_accepted > fcsa::kCompactSlots)
+    return fail(FCSA_ERR_INVALID_ARG, "kvcache_mx_compact: max_accepted (%d) outside [1, %d]", max_accepted, fcsa::kCompactSlots);
+  if (accepted_stride < max_accepted)
+    return fail(FCSA_ERR_INVALID_ARG, "kvcache_mx_compact: accepted row stride %lld below %d entries", (long long)accepted_stride, max_accepted);
+  if (kv->capacity < 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_mx_compact: negative capacity (%d)", kv->capacity);
+  if (int rc = check_cache_table("kvcache_mx_compact", *kv)) return rc;
+  if (batch == 0 || kv_heads == 0 || kv->capacity == 0) return FCSA_OK;      // no row to move
+  if (accepted == nullptr || num_accepted == nullptr || kv->cache_seqlens == nullptr)
+    return fail(FCSA_ERR_INVALID_ARG, "kvcache_mx_compact: null accepted, num_accepted or cache_seqlens");
+  if (int rc = check_tensor("k_cache", kv->k_cache, 1, true)) return rc;
+  if (int rc = check_tensor("v_cache", kv->v_cache, 1, true)) return rc;
+  if (mx->k_block_scale.ptr == nullptr || mx->v_block_scale.ptr == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_mx_compact: null block scales");
+  if ((int64_t)batch * kv_heads > INT32_MAX) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_mx_compact: grid above 2^31 workgroups");
+  fcsa::DecodeParams dp{};
+  dp.kc = view(kv->k_cache, 1);
+  dp.vc = view(kv->v_cache, 1);
+  dp.seqlens = kv->cache_seqlens;
+  dp.table = kv->block_table;
+  dp.table_stride = kv->block_table_stride;
+  dp.capacity = kv->capacity;
+  dp.page = kv->block_table != nullptr ? kv->page_size : 0;
+  dp.num_blocks = kv->num_blocks;
+  dp.B = batch; dp.Hk = kv_heads;
+  const fcsa::DecodeMx dmx = mx_view(*mx);
+  const fcsa::CompactParams cp = {accepted, num_accepted, accepted_stride, max_accepted, dim_head / 2};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return timed("kv_compact_mx", "kv compact (mxfp4)", s, [&] { return fcsa::launch_kv_compact_mx(dp, dmx, cp, s); });
 }
 
 int fcsa_kvcache_compact(const fcsa_kvcache* kv, int32_t batch, int32_t kv_heads, int32_t dim_head, int32_t elem_bytes, const int32_t* accepted,

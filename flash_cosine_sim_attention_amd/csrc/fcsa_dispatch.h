@@ -329,6 +329,10 @@ constexpr int prefill_win_kend(int L, int N, int G, int64_t first, int count, in
   if (last < first || L <= 0) return 0;
   return (int)std::min<int64_t>(std::max<int64_t>((int64_t)L - N + last / G + hi + 1, 0), L);
 }
+// The verify step of a speculative decoder on an MXFP4 cache (fcsa_forward_kvcache_mx_tree, csrc/fcsa_verify_mx.hip): the same flat slots
+// (prefill_slots, prefill_tile) at 64 token-major rows per workgroup, four waves x one MFMA tile of 16, with the decode kernels' key splits
+// (decode_splits fed the 64-row slot count, decode_window).
+constexpr int kVerifyRows = 64;
 // An engine step (fcsa_forward_kvcache_step): a sequence of N rows takes the chunk kernel iff G * N >= chunk_rows, the decode kernels
 // otherwise.  Both sides evaluate this one function on the N their tile maps give them (ragged_tile, prefill_tile: the same clamped entries).
 constexpr bool step_is_chunk(int G, int64_t N, int chunk_rows) { return (int64_t)G * N >= chunk_rows; }

@@ -276,6 +276,15 @@ hipError_t launch_decode_mx_step(int dtype, int D, DecodeForm f, const DecodeSte
                                  hipStream_t s);
 hipError_t launch_prefill_mx_step(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeMx& mx, const DecodeRotary* rotary,
                                   const DecodeLseOut* lse, hipStream_t s);
+// A tree step on an MXFP4 cache (fcsa_forward_kvcache_mx_tree; csrc/fcsa_verify_mx.hip): the ragged MXFP4 call's block with slots =
+// fcsa::prefill_slots(total_q, B, G, kVerifyRows) and the split count of fcsa::decode_splits on those slots, on the 4-wave kernel that takes
+// the scale bytes and the visibility words (DecodeTreeMask) and leaves launch_decode_mx's partials.  f.ragged only (no fp8, no step form),
+// f16 / bf16, D = 64 / 128, l2norm groups of mx_groups_ok; hipErrorInvalidValue otherwise.  The append before it is launch_kv_append_mx and
+// the combine after it launch_decode_combine's 16-bit ragged one.
+hipError_t launch_verify_mx(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeMx& mx, const DecodeTreeMask& tree, hipStream_t s);
+// launch_kv_compact on an MXFP4 cache (fcsa_kvcache_mx_compact): the codes (c.row_bytes = D / 2, a multiple of 16, at most 64) and the
+// scale bytes (one per 16 code bytes) of K and V move together.
+hipError_t launch_kv_compact_mx(const DecodeParams& cache, const DecodeMx& mx, const CompactParams& c, hipStream_t s);
 
 // Merging attention states (fcsa_merge_states, csrc/fcsa_merge.hip): S states (o_s, lse_s) of the rows [n0, n1, n2] -> (o, lse).  o views
 // carry BYTE strides, lse views ELEMENT strides.

@@ -88,7 +88,11 @@ namespace {
   X(forward_kvcache_mx_prefill, fcsa_forward_kvcache_mx_prefill, false)                   \
   /* the engine step against an MXFP4 cache, with or without a rotary embedding */        \
   X(forward_kvcache_mx_step, fcsa_forward_kvcache_mx_step, false)                         \
-  X(forward_kvcache_mx_step_ws, fcsa_forward_kvcache_mx_step_workspace_bytes, false)
+  X(forward_kvcache_mx_step_ws, fcsa_forward_kvcache_mx_step_workspace_bytes, false)     \
+  /* tree attention against an MXFP4 cache, and the compaction of its accepted path */    \
+  X(forward_kvcache_mx_tree, fcsa_forward_kvcache_mx_tree, false)                         \
+  X(forward_kvcache_mx_tree_ws, fcsa_forward_kvcache_mx_tree_workspace_bytes, false)      \
+  X(kvcache_mx_compact, fcsa_kvcache_mx_compact, false)
 
 struct Abi {
 #define X(member, symbol, required) decltype(&symbol) member = &symbol;
@@ -772,7 +776,7 @@ Tensor varlen_window_attention_autograd(const Tensor& q, const Tensor& k, const 
 //
 // One description of a call, CacheCall: every op function fills the members it has and hands it to kvcache_call, which runs the checks
 // (cache_checks), fills the library's structs (fill_lib_call) and dispatches through the one table of entry points (kEntries).
-enum class Route { Plain, Prefill, Step, Tree, Alibi, Rotary, Mx, MxPrefill, MxStep };
+enum class Route { Plain, Prefill, Step, Tree, Alibi, Rotary, Mx, MxPrefill, MxStep, MxTree };
 
 struct CacheCall {
   // what every op has
@@ -786,13 +790,14 @@ struct CacheCall {
   bool lse = false;                                       // the rows' log-sum-exp as a second result
   Route route = Route::Plain;
   fcsa_kvcache_step step{};                               // Step, Alibi, Rotary: the routing fields
-  const Tensor* extra = nullptr;                          // Tree: tree_mask; Alibi: alibi_slopes; Rotary: rotary_cos
+  const Tensor* extra = nullptr;                          // Tree, MxTree: tree_mask; Alibi: alibi_slopes; Rotary: rotary_cos
   const Tensor* rotary_sin = nullptr; bool rotary_interleaved = false;      // Rotary
   const Tensor *k_block_scale = nullptr, *v_block_scale = nullptr;          // Mx: the scale bytes of an MXFP4 cache (its codes as uint8 tensors)
   bool ragged() const { return cu_q != nullptr; }
   bool fp8() const { return k_scale != nullptr; }
-  // MxPrefill: the ragged Mx call on the chunk kernel; MxStep: routed over both, with the tables (extra, rotary_sin) where the call has them
-  bool mx() const { return route == Route::Mx || route == Route::MxPrefill || route == Route::MxStep; }
+  // MxPrefill: the ragged Mx call on the chunk kernel; MxStep: routed over both, with the tables (extra, rotary_sin) where the call has them;
+  // MxTree: the ragged Mx call on the verify kernel, with the visibility words (extra)
+  bool mx() const { return route == Route::Mx || route == Route::MxPrefill || route == Route::MxStep || route == Route::MxTree; }
   bool rotary() const { return route == Route::Rotary || (route == Route::MxStep && extra != nullptr); }
 };
 
@@ -891,7 +896,7 @@ CacheKeep cache_checks(const CacheCall& c) {
     TORCH_CHECK_VALUE(q.size(0) * std::max<int64_t>(q.size(1), 1) <= INT32_MAX, "heads x packed rows must stay below 2^31");
     k.cu = cu_q.contiguous();
   }
-  if (c.route == Route::Tree) {
+  if (c.route == Route::Tree || c.route == Route::MxTree) {
     const Tensor& tree = *c.extra;
     TORCH_CHECK_TYPE(tree.scalar_type() == at::kLong, "tree_mask must be int64, got ", tree.scalar_type());
     same_dev("tree_mask", tree);
@@ -1046,7 +1051,7 @@ struct EntryPoint {
   size_t (*workspace)(const LibCall&);      // null: that of the call without the lse
   int (*run)(const LibCall&);
 };
-enum Entry { kKvcache, kWindow, kQuant, kVarlen, kLse, kPrefill, kStep, kTree, kAlibi, kRotary, kMx, kMxPrefill, kMxStep };
+enum Entry { kKvcache, kWindow, kQuant, kVarlen, kLse, kPrefill, kStep, kTree, kAlibi, kRotary, kMx, kMxPrefill, kMxStep, kMxTree };
 const EntryPoint kEntries[] = {
     /* kKvcache */ {"fcsa_forward_kvcache", "flash_cosine_sim_attention_with_kvcache",
                     [] { return g_abi.forward_kvcache != nullptr && g_abi.forward_kvcache_ws != nullptr; },
@@ -1096,12 +1101,16 @@ const EntryPoint kEntries[] = {
        return g_abi.forward_kvcache_mx_step(&l.a, &l.kv, &l.mx, &l.seqs, l.win, l.step, l.rotary.cos != nullptr ? &l.rotary : nullptr,
                                             l.lo.lse != nullptr ? &l.lo : nullptr);
      }},
+    /* kMxTree: ragged only, a plan of its own */ {"fcsa_forward_kvcache_mx_tree", "flash_cosine_sim_attention_mxfp4_tree_with_kvcache",
+     [] { return g_abi.forward_kvcache_mx_tree != nullptr && g_abi.forward_kvcache_mx_tree_ws != nullptr; },
+     [](const LibCall& l) { return g_abi.forward_kvcache_mx_tree_ws(&l.a.p, &l.kv, &l.mx, &l.seqs); },
+     [](const LibCall& l) { return g_abi.forward_kvcache_mx_tree(&l.a, &l.kv, &l.mx, &l.seqs, l.win, &l.tree, l.lo.lse != nullptr ? &l.lo : nullptr); }},
 };
 
 // the entry point of a Plain call without the lse: by the ragged / fp8 / window facts
 Entry plain_entry(const CacheCall& c) { return c.ragged() ? kVarlen : c.fp8() ? kQuant : c.win != nullptr ? kWindow : kKvcache; }
-constexpr Entry kOfRoute[] = {kKvcache /* Plain: by the facts instead */, kPrefill, kStep, kTree, kAlibi, kRotary, kMx, kMxPrefill, kMxStep};      // in Route's order
-static_assert(sizeof(kEntries) / sizeof(kEntries[0]) == kMxStep + 1 && sizeof(kOfRoute) / sizeof(kOfRoute[0]) == (int)Route::MxStep + 1,
+constexpr Entry kOfRoute[] = {kKvcache /* Plain: by the facts instead */, kPrefill, kStep, kTree, kAlibi, kRotary, kMx, kMxPrefill, kMxStep, kMxTree};      // in Route's order
+static_assert(sizeof(kEntries) / sizeof(kEntries[0]) == kMxTree + 1 && sizeof(kOfRoute) / sizeof(kOfRoute[0]) == (int)Route::MxTree + 1,
               "kEntries has one row per Entry, in its order, and kOfRoute one entry per Route");
 Entry entry_of(const CacheCall& c) { return c.route != Route::Plain ? kOfRoute[(int)c.route] : c.lse ? kLse : plain_entry(c); }
 // a call needs its own entry point and those of the calls it is built on
@@ -1306,6 +1315,75 @@ std::tuple<Tensor, Tensor> kvcache_mxfp4_step_forward(const Tensor& q, const Ten
   c.extra = ptr(rotary_cos); c.rotary_sin = ptr(rotary_sin); c.rotary_interleaved = rotary_interleaved;
   auto [o, lse] = kvcache_call(c);
   return {o, return_lse ? lse : at::empty({0}, q.options().dtype(at::kFloat))};
+}
+
+// A tree step against an MXFP4 cache (kvcache_mxfp4_tree_forward): kvcache_mxfp4_forward's ragged step without a window and without `causal`,
+// the visibility of the step's own tokens given per packed row by tree_mask (int64 [total_q], read as unsigned 64-bit words), through
+// fcsa_forward_kvcache_mx_tree, the 64-row verify kernel with key splits.
+std::tuple<Tensor, Tensor> kvcache_mxfp4_tree_forward(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& k_block_scale,
+                                                      const Tensor& v_block_scale, const Tensor& cu_seqlens_q, const Tensor& tree_mask,
+                                                      const optional<Tensor>& k_new, const optional<Tensor>& v_new,
+                                                      const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table,
+                                                      int64_t max_seqlen_q, int64_t max_seqlen_k, double scale, bool l2norm_qk, int64_t groups,
+                                                      bool return_lse) {
+  CacheCall c{q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, false, l2norm_qk, groups};
+  c.cu_q = &cu_seqlens_q; c.max_seqlen_q = max_seqlen_q; c.lse = return_lse;
+  c.route = Route::MxTree; c.k_block_scale = &k_block_scale; c.v_block_scale = &v_block_scale; c.extra = &tree_mask;
+  TORCH_CHECK_VALUE(q.dim() != 3 || q.size(-1) == 64 || q.size(-1) == 128, "tree attention against MXFP4 caches takes head dimensions 64 and 128, got ",
+                    q.size(-1));
+  auto [o, lse] = kvcache_call(c);
+  return {o, return_lse ? lse : at::empty({0}, q.options().dtype(at::kFloat))};
+}
+
+// mxfp4_kvcache_keep_accepted: kvcache_compact on the four tensors of an MXFP4 cache -- the rows cache_seqlens[b] + accepted[b, i] of the codes
+// and of the scale bytes, of K and of V, move to cache_seqlens[b] + i (i < num_accepted[b]), in place.  Tables int32 on the caches' device.
+void kvcache_mxfp4_compact(const Tensor& k_cache, const Tensor& v_cache, const Tensor& k_block_scale, const Tensor& v_block_scale,
+                           const Tensor& cache_seqlens, const Tensor& accepted, const Tensor& num_accepted, const optional<Tensor>& block_table) {
+  need_abi("mxfp4_kvcache_keep_accepted", "fcsa_kvcache_mx_compact", g_abi.kvcache_mx_compact);
+  TORCH_CHECK(k_cache.is_cuda(), "mxfp4_kvcache_keep_accepted: the caches must be GPU tensors (HIP kernels only)");
+  auto same_dev = [&](const char* name, const Tensor& t) {
+    TORCH_CHECK_VALUE(t.device() == k_cache.device(), name, " is on ", t.device(), " but k_cache is on ", k_cache.device());
+  };
+  same_dev("v_cache", v_cache);
+  TORCH_CHECK_TYPE(k_cache.scalar_type() == at::kByte && v_cache.scalar_type() == at::kByte, "MXFP4 caches are uint8 (two e2m1 codes per byte)");
+  TORCH_CHECK_VALUE(k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes(), "k_cache and v_cache must have 4 dimensions and the same shape");
+  const int64_t D = 2 * k_cache.size(3), Hk = k_cache.size(1);
+  TORCH_CHECK_VALUE(D == 32 || D == 64 || D == 96 || D == 128, "MXFP4 caches hold dim_head / 2 code bytes per position, dim_head in (32, 64, 96, 128), got ",
+                    k_cache.size(3), " bytes");
+  TORCH_CHECK_VALUE(rows_ok(k_cache) && rows_ok(v_cache), "k_cache / v_cache: the feature dim must be contiguous and rows 16-byte aligned "
+                    "(the caches are updated in place, so they are not copied)");
+  for (const auto& [name, t] : {std::pair<const char*, const Tensor*>{"k_block_scale", &k_block_scale}, {"v_block_scale", &v_block_scale}}) {
+    same_dev(name, *t);
+    TORCH_CHECK_TYPE(t->scalar_type() == at::kByte, name, " must be uint8 (e8m0 scale bytes), got ", t->scalar_type());
+    TORCH_CHECK_VALUE(t->dim() == 4 && t->sizes().slice(0, 3) == k_cache.sizes().slice(0, 3) && t->size(3) == D / 32, name,
+                      " must have the caches' leading dimensions and dim_head / 32 (", D / 32, ") bytes per position, got ", t->sizes());
+    TORCH_CHECK_VALUE(t->stride(3) == 1 || t->size(3) == 1, name, ": the last dim must be contiguous (the scales are updated in place, so they are not copied)");
+  }
+  same_dev("cache_seqlens", cache_seqlens);
+  same_dev("accepted", accepted);
+  same_dev("num_accepted", num_accepted);
+  TORCH_CHECK_TYPE(cache_seqlens.scalar_type() == at::kInt && accepted.scalar_type() == at::kInt && num_accepted.scalar_type() == at::kInt,
+                   "cache_seqlens, accepted and num_accepted must be int32");
+  TORCH_CHECK_VALUE(accepted.dim() == 2 && accepted.size(1) >= 1 && accepted.size(1) <= 64, "accepted must be [sequences, A] with 1 <= A <= 64, got ",
+                    accepted.sizes());
+  const int64_t B = accepted.size(0);
+  TORCH_CHECK_VALUE(cache_seqlens.dim() == 1 && cache_seqlens.size(0) == B && num_accepted.dim() == 1 && num_accepted.size(0) == B,
+                    "cache_seqlens and num_accepted must be [", B, "]");
+  const Geometry g = cache_geometry(k_cache, block_table, B, same_dev, "sequences", "accepted");
+  TORCH_CHECK_VALUE(g.capacity <= INT32_MAX, "cache capacity must stay below 2^31");
+  if (B == 0 || Hk == 0 || g.capacity == 0) return;
+  c10::DeviceGuard guard(k_cache.device());
+  const Tensor sl = cache_seqlens.contiguous(), acc = accepted.stride(1) == 1 ? accepted : accepted.contiguous(), na = num_accepted.contiguous();
+  fcsa_kvcache kv;
+  std::memset(&kv, 0, sizeof(kv));
+  kv.k_cache = strided(k_cache);
+  kv.v_cache = strided(v_cache);
+  g.fill(kv);
+  kv.cache_seqlens = sl.data_ptr<int32_t>();
+  const fcsa_kvcache_mx mx = {FCSA_CACHE_MXFP4, strided(k_block_scale), strided(v_block_scale)};
+  check(g_abi.kvcache_mx_compact(&kv, &mx, (int32_t)B, (int32_t)Hk, (int32_t)D, acc.data_ptr<int32_t>(), acc.stride(0), (int32_t)acc.size(1),
+                                 na.data_ptr<int32_t>(), stream_of(k_cache)),
+        "fcsa_kvcache_mx_compact");
 }
 
 // A tree step: kvcache_lse_forward's ragged step without a window and without `causal`, the visibility of the step's own tokens given per
@@ -1844,6 +1922,20 @@ TORCH_LIBRARY(fcsa_mx, m) {
 TORCH_LIBRARY_IMPL(fcsa_mx, CUDA, m) {
   m.impl("kvcache_mxfp4_forward", &kvcache_mxfp4_forward);
   m.impl("kvcache_mxfp4_prefill_forward", &kvcache_mxfp4_prefill_forward);
+}
+
+// tree attention against an MXFP4 cache and the compaction of its accepted path, in a namespace of their own (the op sets of fcsa_mx and
+// fcsa_tree are pinned).  Forward only: no Autograd kernel.
+TORCH_LIBRARY(fcsa_mx_tree, m) {
+  m.def("kvcache_mxfp4_tree_forward(Tensor q, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor(c!) k_block_scale, Tensor(d!) v_block_scale, "
+        "Tensor cu_seqlens_q, Tensor tree_mask, Tensor? k_new, Tensor? v_new, Tensor? cache_seqlens, Tensor? block_table, int max_seqlen_q, "
+        "int max_seqlen_k, float scale, bool l2norm_qk, int groups, bool return_lse) -> (Tensor, Tensor)");
+  m.def("kvcache_mxfp4_compact(Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor(c!) k_block_scale, Tensor(d!) v_block_scale, Tensor cache_seqlens, "
+        "Tensor accepted, Tensor num_accepted, Tensor? block_table) -> ()");
+}
+TORCH_LIBRARY_IMPL(fcsa_mx_tree, CUDA, m) {
+  m.impl("kvcache_mxfp4_tree_forward", &kvcache_mxfp4_tree_forward);
+  m.impl("kvcache_mxfp4_compact", &kvcache_mxfp4_compact);
 }
 
 // the engine step against an MXFP4 cache, in a namespace of its own (the op set of fcsa_mx is pinned).  Forward only: no Autograd kernel.

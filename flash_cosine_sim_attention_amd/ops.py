@@ -680,7 +680,8 @@ def flash_cosine_sim_attention_mxfp4_with_kvcache(q, k_cache, v_cache, k_block_s
     convert an existing cache.  CPU tensors take a forward-only path: dequantise, then `cpu.py` (host tables).
     Prompt chunks of such a cache belong to `flash_cosine_sim_attention_mxfp4_prefill_with_kvcache` (the same arguments), an engine step
     -- chunks and decodes routed in one call, with or without a rotary embedding -- to `flash_cosine_sim_attention_mxfp4_step_with_kvcache`.
-    Not taken with such a cache: the tree, ALiBi and shared-prefix calls (those functions refuse uint8 caches), e5m2, MXFP6 / MXFP8
+    A tree step of a speculative decoder: `flash_cosine_sim_attention_mxfp4_tree_with_kvcache` (this call with a tree_mask).
+    Not taken with such a cache: the ALiBi and shared-prefix calls (those functions refuse uint8 caches), e5m2, MXFP6 / MXFP8
     caches, fp4 queries."""
     return _mxfp4_call("flash_cosine_sim_attention_mxfp4_with_kvcache", False, q, k_cache, v_cache, k_block_scale, v_block_scale, cu_seqlens_q,
                        k_new, v_new, cache_seqlens, block_table, max_seqlen_q, max_seqlen_k, scale, groups, causal, l2norm_qk, return_lse,
@@ -725,10 +726,11 @@ def flash_cosine_sim_attention_mxfp4_prefill_with_kvcache(q, k_cache, v_cache, k
 
 
 def _mxfp4_call(fn, chunk, q, k_cache, v_cache, k_block_scale, v_block_scale, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q,
-                max_seqlen_k, scale, groups, causal, l2norm_qk, return_lse, window_size, step=None):
+                max_seqlen_k, scale, groups, causal, l2norm_qk, return_lse, window_size, step=None, tree_mask=None):
     """The one front end of the MXFP4 cache functions: the checks, the CPU path and the op call -- chunk: the op of the multi-wave chunk
     kernel (packed queries, checked by the caller) in place of the decode kernel's; step (the engine step; packed queries, checked by the
-    caller): (chunk_rows, max_decode_tokens, rotary) with rotary None or (cos, sin, interleaved), on the op that routes over both kernels"""
+    caller): (chunk_rows, max_decode_tokens, rotary) with rotary None or (cos, sin, interleaved), on the op that routes over both kernels;
+    tree_mask (a tree step; packed queries, no causal and no window, checked by the caller): the visibility words, on the op of the verify kernel"""
     _check_return_lse(return_lse)
     window = _window(window_size)
     ragged = cu_seqlens_q is not None
@@ -780,6 +782,8 @@ def _mxfp4_call(fn, chunk, q, k_cache, v_cache, k_block_scale, v_block_scale, cu
             _mx_append_cpu((k_cache, k_block_scale, v_cache, v_block_scale), rows, starts, lens, c.capacity, block_table)
         dense = (mxfp4_dequantize(k_cache, k_block_scale, q.dtype), mxfp4_dequantize(v_cache, v_block_scale, q.dtype))
         kw = dict(scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, window_size=window, return_lse=bool(return_lse))
+        if tree_mask is not None:
+            kw["tree_mask"] = tree_mask
         if ragged:
             res = _cpu.attention_forward_kvcache_varlen_cpu(q_in, *dense, cu_seqlens_q, *(new_q or (None, None)), lens, block_table, **kw)
             if q_in.dtype == q.dtype:
@@ -793,6 +797,11 @@ def _mxfp4_call(fn, chunk, q, k_cache, v_cache, k_block_scale, v_block_scale, cu
     routing = None if step is None else _step_routing(c, q.shape[0], q.shape[1], step[0], step[1])
     k_cache, v_cache, cache_seqlens, block_table = c.on_device()
     _torch_ops.load()
+    if tree_mask is not None:
+        o, lse = torch.ops.fcsa_mx_tree.kvcache_mxfp4_tree_forward(q, k_cache, v_cache, k_block_scale, v_block_scale, cu_q, tree_mask, k_new, v_new,
+                                                                   cache_seqlens, block_table, max_q, c.max_k, float(scale), bool(l2norm_qk),
+                                                                   int(groups), bool(return_lse))
+        return (o, lse) if return_lse else o
     if step is not None:
         cos, sin, interleaved = step[2] if step[2] is not None else (None, None, False)
         move = lambda t: None if t is None else t.to(q.device, non_blocking=True)
@@ -1185,6 +1194,56 @@ def flash_cosine_sim_attention_mxfp4_step_with_kvcache(q, k_cache, v_cache, k_bl
                        step=(chunk_rows, max_decode_tokens, rotary))
 
 
+def flash_cosine_sim_attention_mxfp4_tree_with_kvcache(q, k_cache, v_cache, k_block_scale, v_block_scale, cu_seqlens_q=None, k_new=None, v_new=None,
+                                                       cache_seqlens=None, block_table=None, max_seqlen_q=None, max_seqlen_k=None, scale=8,
+                                                       groups=1, causal=False, l2norm_qk=True, return_lse=False, window_size=(-1, -1),
+                                                       tree_mask=None):
+    """Tree attention for speculative decoding against MXFP4 caches: `flash_cosine_sim_attention_mxfp4_with_kvcache` with one more, last
+    keyword.  The first eighteen parameters are that call's, with its defaults; tree_mask=None IS that call.
+
+    tree_mask: an int64 tensor [total_q] on q's device, packed by cu_seqlens_q like q, with the meaning it has on
+    `flash_cosine_sim_attention_tree_with_kvcache`, word for word: with L_b as the ragged call defines it and P_b = L_b - N_b, every query of
+    sequence b sees the cache positions j < P_b; query i sees position P_b + t, 0 <= t < N_b (the step's token t), iff bit t of its word is
+    set (bit 0 the least significant, the word read as unsigned; bits t >= N_b are never looked at).  A sequence with N_b > 64 ignores its
+    words and is causal, bottom-right (decided on the device from the clamped table).  A row without a visible key gives o = 0 and
+    lse = -inf.  With a mask q must be packed [total_q, H, D] with cu_seqlens_q; causal=True and a window_size other than (-1, -1) are
+    refused; q, k_new, v_new are float16 or bfloat16 and dim_head is 64 or 128.  return_lse, paged and strided caches, k_new=None, device
+    tables without synchronisation and graph capture work as on the MXFP4 call; the append quantises as `mxfp4_quantize` states.
+    The kernel is built for the verify step's shape, G * N_b = 32 ... 256 rows per K/V head against a long cache: four waves own 64
+    token-major rows, every 64-key stage of the cache is converted, normalised and rounded once per workgroup and shared through LDS, and
+    the key range is split over workgroups as the decode kernel splits it.  Per wave and 32-key block the arithmetic is the MXFP4 decode
+    kernel's, so the chain mask (word i = bits 0 .. i) gives causal=True of `flash_cosine_sim_attention_mxfp4_with_kvcache` and all bits set
+    give causal=False -- o, lse and the four cache tensors bit for bit where both calls run one key split, to rounding otherwise.  After
+    verification `mxfp4_kvcache_keep_accepted` moves the accepted path to the front of the step's slots.
+    CPU tensors: quantise and append, dequantise, then the tree path of `cpu.py` (host tables).  Forward only."""
+    fn = "flash_cosine_sim_attention_mxfp4_tree_with_kvcache"
+    if tree_mask is None:
+        return flash_cosine_sim_attention_mxfp4_with_kvcache(q, k_cache, v_cache, k_block_scale, v_block_scale, cu_seqlens_q, k_new, v_new,
+                                                             cache_seqlens, block_table, max_seqlen_q, max_seqlen_k, scale, groups, causal,
+                                                             l2norm_qk, return_lse, window_size)
+    _check_return_lse(return_lse)
+    window = _window(window_size)
+    if cu_seqlens_q is None or q.dim() != 3:
+        raise ValueError(f"{fn} with a tree_mask takes packed queries [total_q, heads, dim_head] with cu_seqlens_q, got q {tuple(q.shape)}"
+                         f"{'' if cu_seqlens_q is not None else ' and cu_seqlens_q=None'} (equal N: cu_seqlens_q = arange(B + 1) * N)")
+    if causal:
+        raise ValueError("tree_mask states the visibility of the step's tokens: causal=True cannot be given with it")
+    if tuple(window) != (-1, -1):
+        raise ValueError(f"tree_mask takes no sliding window (window_size {tuple(window_size)})")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError(f"{fn} with a tree_mask takes float16 or bfloat16 q at dim_head 64 or 128, got {q.dtype}")
+    if q.shape[-1] not in (64, 128):
+        raise ValueError(f"{fn} with a tree_mask takes dim_head 64 or 128 (float16 or bfloat16), got {q.shape[-1]}")
+    if not isinstance(tree_mask, torch.Tensor) or tree_mask.dtype != torch.int64:
+        raise TypeError(f"tree_mask must be an int64 tensor of shape [total_q], got {getattr(tree_mask, 'dtype', type(tree_mask).__name__)}")
+    if tuple(tree_mask.shape) != (q.shape[0],):
+        raise ValueError(f"tree_mask must have shape [{q.shape[0]}] (one word per packed query row), got {tuple(tree_mask.shape)}")
+    if tree_mask.device != q.device:
+        raise ValueError(f"tree_mask is on {tree_mask.device} but q is on {q.device}")
+    return _mxfp4_call(fn, False, q, k_cache, v_cache, k_block_scale, v_block_scale, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table,
+                       max_seqlen_q, max_seqlen_k, scale, groups, False, l2norm_qk, return_lse, window_size, tree_mask=tree_mask)
+
+
 def flash_cosine_sim_attention_tree_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new=None, v_new=None, cache_seqlens=None,
                                                  block_table=None, max_seqlen_q=None, max_seqlen_k=None, scale=8, groups=1, causal=False,
                                                  l2norm_qk=True, k_scale=None, v_scale=None, return_lse=False, window_size=(-1, -1),
@@ -1252,6 +1311,24 @@ def kvcache_keep_accepted(k_cache, v_cache, cache_seqlens, accepted, num_accepte
     not synchronise and can be captured in a HIP graph.  One workgroup owns all moves of a (sequence, K/V head) pair and reads every
     source row before it writes the first, so a destination that is another move's source (accepted = [1, 2, 3, ...]) is safe.
     CPU tensors take the path of `cpu.py` (host tables)."""
+    _check_accepted(k_cache, v_cache, cache_seqlens, accepted, num_accepted, block_table)
+    dev = k_cache.device
+    host = lambda t: t.device.type == "cpu"
+    if dev.type == "cpu":
+        if not (host(accepted) and host(num_accepted) and host(cache_seqlens)) or (block_table is not None and not host(block_table)):
+            raise ValueError("CPU caches take host tables")
+        _cpu.kvcache_keep_accepted_cpu(k_cache, v_cache, cache_seqlens.tolist(), accepted.tolist(), num_accepted.tolist(), block_table)
+        return None
+    if k_cache.dtype in _FP8_TYPES:      # the codes travel as bytes (same storage)
+        k_cache, v_cache = k_cache.view(torch.uint8), v_cache.view(torch.uint8)
+    move = lambda t: None if t is None else t.to(dev, non_blocking=True)
+    _torch_ops.load()
+    torch.ops.fcsa_tree.kvcache_compact(k_cache, v_cache, move(cache_seqlens), move(accepted), move(num_accepted), move(block_table))
+    return None
+
+
+def _check_accepted(k_cache, v_cache, cache_seqlens, accepted, num_accepted, block_table):
+    """the checks of `kvcache_keep_accepted` and `mxfp4_kvcache_keep_accepted` on the caches and the tables; host tables are validated"""
     for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
         if not isinstance(t, torch.Tensor) or t.dim() != 4:
             raise ValueError(f"{name} must be a tensor of 4 dimensions")
@@ -1278,17 +1355,42 @@ def kvcache_keep_accepted(k_cache, v_cache, cache_seqlens, accepted, num_accepte
                     raise ValueError(f"sequence {b}: accepted must be strictly increasing step-token indices in [0, 64), got {path}")
     if host(cache_seqlens) and any(n < 0 or n > capacity for n in cache_seqlens.tolist()):
         raise ValueError(f"cache_seqlens must lie in [0, capacity {capacity}], got {cache_seqlens.tolist()}")
+
+
+def mxfp4_kvcache_keep_accepted(k_cache, v_cache, k_block_scale, v_block_scale, cache_seqlens, accepted, num_accepted, block_table=None):
+    """`kvcache_keep_accepted` for MXFP4 caches: moves the accepted path of a tree step
+    (`flash_cosine_sim_attention_mxfp4_tree_with_kvcache`) to the front of the slots the step appended, in place, in all four tensors.
+
+    k_cache, v_cache (torch.uint8 codes, [..., D / 2]) and k_block_scale, v_block_scale (torch.uint8 scale bytes, [..., D / 32]) as that
+    call takes them; cache_seqlens, accepted, num_accepted and block_table with the rules of `kvcache_keep_accepted`: for
+    i < num_accepted[b] the position cache_seqlens[b] + accepted[b, i] moves to cache_seqlens[b] + i -- its codes and its scale bytes, in
+    K and in V, for every K/V head; cache_seqlens is not advanced; host tables are validated, device tables trusted and clamped, and a
+    move at or beyond the capacity is skipped.  One workgroup owns all moves of a (sequence, K/V head) pair and reads every source row
+    before it writes the first.  With device tables the call does not synchronise and can be captured in a HIP graph.  CPU tensors take
+    the path of `cpu.py` (host tables).  Returns None."""
+    _check_accepted(k_cache, v_cache, cache_seqlens, accepted, num_accepted, block_table)
+    if k_cache.dtype != torch.uint8:
+        raise TypeError(f"MXFP4 caches are torch.uint8 (two e2m1 codes per byte), got {k_cache.dtype}: kvcache_keep_accepted moves other caches")
+    D = 2 * k_cache.shape[3]
+    if D not in (32, 64, 96, 128):
+        raise ValueError(f"MXFP4 caches hold dim_head / 2 code bytes per position with dim_head 32, 64, 96 or 128, got {k_cache.shape[3]} bytes")
+    for name, t in (("k_block_scale", k_block_scale), ("v_block_scale", v_block_scale)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+            raise TypeError(f"{name} must be a torch.uint8 tensor (e8m0 scale bytes)")
+        if tuple(t.shape) != (*k_cache.shape[:3], D // 32) or t.device != k_cache.device:
+            raise ValueError(f"{name} must be {(*k_cache.shape[:3], D // 32)} on {k_cache.device}, got {tuple(t.shape)} on {t.device}")
     dev = k_cache.device
+    host = lambda t: t.device.type == "cpu"
     if dev.type == "cpu":
         if not (host(accepted) and host(num_accepted) and host(cache_seqlens)) or (block_table is not None and not host(block_table)):
             raise ValueError("CPU caches take host tables")
-        _cpu.kvcache_keep_accepted_cpu(k_cache, v_cache, cache_seqlens.tolist(), accepted.tolist(), num_accepted.tolist(), block_table)
+        _cpu.mxfp4_kvcache_keep_accepted_cpu(k_cache, v_cache, k_block_scale, v_block_scale, cache_seqlens.tolist(), accepted.tolist(),
+                                             num_accepted.tolist(), block_table)
         return None
-    if k_cache.dtype in _FP8_TYPES:      # the codes travel as bytes (same storage)
-        k_cache, v_cache = k_cache.view(torch.uint8), v_cache.view(torch.uint8)
     move = lambda t: None if t is None else t.to(dev, non_blocking=True)
     _torch_ops.load()
-    torch.ops.fcsa_tree.kvcache_compact(k_cache, v_cache, move(cache_seqlens), move(accepted), move(num_accepted), move(block_table))
+    torch.ops.fcsa_mx_tree.kvcache_mxfp4_compact(k_cache, v_cache, k_block_scale, v_block_scale, move(cache_seqlens), move(accepted),
+                                                 move(num_accepted), move(block_table))
     return None
 
 

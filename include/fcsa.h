@@ -542,7 +542,8 @@ int    fcsa_forward_kvcache_rotary(const fcsa_forward_args* args, const fcsa_kvc
  * Launches: "kv_append_mx" (when rows are appended), "decode_mx" and the 16-bit call's combine ("decode_combine[_lse][_ragged]"): the V
  * scales are applied as the codes are read.
  * Prompt chunks: fcsa_forward_kvcache_mx_prefill, below; the engine step with routing and a rotary embedding: fcsa_forward_kvcache_mx_step.
- * Not offered with such a cache: the tree, ALiBi and shared-prefix calls; other element formats (e5m2 scales,
+ * Tree attention for speculative decoding: fcsa_forward_kvcache_mx_tree and fcsa_kvcache_mx_compact.
+ * Not offered with such a cache: the ALiBi and shared-prefix calls; other element formats (e5m2 scales,
  * MXFP6, MXFP8); fp4 queries and the scaled MFMA instructions. */
 #define FCSA_CACHE_MXFP4 2            /* fcsa_kvcache_mx.format */
 typedef struct fcsa_kvcache_mx {
@@ -594,6 +595,40 @@ int    fcsa_forward_kvcache_mx_step(const fcsa_forward_args* args, const fcsa_kv
                                     const fcsa_rotary* rotary, const fcsa_lse_out* lse_out);
 size_t fcsa_forward_kvcache_mx_step_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* cache, const fcsa_kvcache_mx* mx,
                                                     const fcsa_varlen* seqs, const fcsa_window* window, const fcsa_kvcache_step* step);
+
+/* Tree attention against an MXFP4 cache: the verify step of a speculative decoder (fcsa_forward_kvcache_tree's semantics) on the caches of
+ * fcsa_forward_kvcache_mx (additive: no existing struct changes and FCSA_ABI_VERSION stays 4).
+ * args, cache, mx, seqs and lse_out are read as fcsa_forward_kvcache_mx reads them with seqs set (seqs NULL: FCSA_ERR_INVALID_ARG), with its
+ * checks, quantising append, clamping of lengths, table entries and block ids, and both exponent regimes; tree as
+ * fcsa_forward_kvcache_tree reads it, with that call's visibility rule word for word: with L_b the cached positions after the append,
+ * N_b the sequence's packed rows and P_b = L_b - N_b, query i sees every position j < P_b, and position P_b + t iff bit t of its word is
+ * set; a sequence with N_b > 64 ignores its words and is causal, bottom-right aligned (decided on the device from the clamped table); a
+ * row without a visible key gives o = 0 and lse = -inf.
+ *   p.dtype   : FCSA_F16 or FCSA_BF16;  p.dim_head: 64 or 128 (32, 96: FCSA_ERR_UNSUPPORTED);  p.groups: as fcsa_forward_kvcache_mx
+ *   p.causal  : 0 (the mask states the visibility; anything else: FCSA_ERR_INVALID_ARG)
+ *   window    : NULL or (-1, -1); a side >= 0: FCSA_ERR_INVALID_ARG
+ *   tree      : required; tree->mask NULL (with rows to compute) or not 8-byte aligned, reserved != 0: FCSA_ERR_INVALID_ARG
+ *   workspace : >= fcsa_forward_kvcache_mx_tree_workspace_bytes() bytes for the same arguments, 256-byte aligned (0 for a call refused as
+ *               unsupported)
+ * The kernel: one 4-wave workgroup per (64-row tile slot, K/V head, key split), rows token-major; a 64-key stage of the split's key range is
+ * converted, normalised and rounded once per workgroup and shared through LDS, and per wave and 32-key block the arithmetic is the MXFP4
+ * decode kernel's in its order.  The split count is the decode split rule on the 64-row slot count.  So with the chain mask (word i = bits
+ * 0 .. i) o, lse and the four cache tensors are those of fcsa_forward_kvcache_mx with seqs and p.causal = 1, and with all bits set those
+ * of p.causal = 0 -- bit for bit where both calls run one key split, to rounding otherwise.
+ * Device tables and the words are never read by the host: the call does not synchronise and can be captured in a graph.  Every refusal
+ * happens before any launch.  Launches: "kv_append_mx" (when appending), "verify_mx", "decode_combine[_lse]_ragged". */
+int    fcsa_forward_kvcache_mx_tree(const fcsa_forward_args* args, const fcsa_kvcache* cache, const fcsa_kvcache_mx* mx,
+                                    const fcsa_varlen* seqs, const fcsa_window* window, const fcsa_tree_mask* tree,
+                                    const fcsa_lse_out* lse_out);
+size_t fcsa_forward_kvcache_mx_tree_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* cache, const fcsa_kvcache_mx* mx,
+                                                    const fcsa_varlen* seqs);
+/* fcsa_kvcache_compact for an MXFP4 cache: for i < num_accepted[b] the row at cache position cache_seqlens[b] + accepted[b, i] moves to
+ * cache_seqlens[b] + i in all four tensors -- dim_head / 2 code bytes and dim_head / 32 scale bytes, of K and of V -- for every K/V head.
+ * cache and the tables as in fcsa_kvcache_compact (elements of one byte), mx as in fcsa_forward_kvcache_mx; dim_head 32, 64, 96 or 128.
+ * The same clamping, the same skipped moves at or beyond the capacity, the same read-all-then-write order.  Launch: "kv_compact_mx". */
+int    fcsa_kvcache_mx_compact(const fcsa_kvcache* cache, const fcsa_kvcache_mx* mx, int32_t batch, int32_t kv_heads, int32_t dim_head,
+                               const int32_t* accepted, int64_t accepted_stride, int32_t max_accepted, const int32_t* num_accepted,
+                               void* stream);
 
 /* The same linear position bias in the training kernels, forward and backward: fcsa_forward_window / fcsa_backward_window with one more
  * argument, the slopes (additive: no existing struct changes and FCSA_ABI_VERSION stays 4).  A model trained through these entries is
