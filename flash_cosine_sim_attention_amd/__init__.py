@@ -9,6 +9,7 @@ from .ops import (flash_cosine_sim_attention, flash_cosine_sim_attention_local, 
                   flash_cosine_sim_attention_rotary_with_kvcache,
                   flash_cosine_sim_attention_mxfp4_with_kvcache, flash_cosine_sim_attention_mxfp4_prefill_with_kvcache,
                   flash_cosine_sim_attention_mxfp4_step_with_kvcache, flash_cosine_sim_attention_mxfp4_tree_with_kvcache,
+                  flash_cosine_sim_attention_verify_with_kvcache,
                   mxfp4_quantize, mxfp4_dequantize,
                   kvcache_keep_accepted, mxfp4_kvcache_keep_accepted,
                   flash_cosine_sim_attention_with_shared_prefix, merge_attention_states,
@@ -25,6 +26,7 @@ __all__ = ['flash_cosine_sim_attention', 'flash_cosine_sim_attention_local', 'fl
            'flash_cosine_sim_attention_rotary_with_kvcache',
            'flash_cosine_sim_attention_mxfp4_with_kvcache', 'flash_cosine_sim_attention_mxfp4_prefill_with_kvcache',
            'flash_cosine_sim_attention_mxfp4_step_with_kvcache', 'flash_cosine_sim_attention_mxfp4_tree_with_kvcache',
+           'flash_cosine_sim_attention_verify_with_kvcache',
            'mxfp4_quantize', 'mxfp4_dequantize',
            'kvcache_keep_accepted', 'mxfp4_kvcache_keep_accepted',
            'flash_cosine_sim_attention_with_shared_prefix', 'merge_attention_states',

@@ -110,7 +110,8 @@ EXPORTS = ("fcsa_forward", "fcsa_backward", "fcsa_backward_workspace_bytes", "fc
            "fcsa_forward_alibi", "fcsa_backward_alibi", "fcsa_forward_alibi_workspace_bytes", "fcsa_backward_alibi_workspace_bytes",
            "fcsa_forward_kvcache_rotary", "fcsa_forward_kvcache_mx", "fcsa_forward_kvcache_mx_workspace_bytes",
            "fcsa_forward_kvcache_mx_prefill", "fcsa_forward_kvcache_mx_step", "fcsa_forward_kvcache_mx_step_workspace_bytes",
-           "fcsa_forward_kvcache_mx_tree", "fcsa_forward_kvcache_mx_tree_workspace_bytes", "fcsa_kvcache_mx_compact")
+           "fcsa_forward_kvcache_mx_tree", "fcsa_forward_kvcache_mx_tree_workspace_bytes", "fcsa_kvcache_mx_compact",
+           "fcsa_forward_kvcache_verify", "fcsa_forward_kvcache_verify_workspace_bytes")
 
 _lib = None
 
@@ -269,6 +270,12 @@ def load():
         lib.fcsa_kvcache_mx_compact.argtypes = [C.POINTER(KvCache), C.POINTER(KvCacheMx), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                                                 C.c_int32, C.c_void_p, C.c_void_p]
         lib.fcsa_kvcache_mx_compact.restype = C.c_int
+    if hasattr(lib, "fcsa_forward_kvcache_verify"):      # (likewise: an FCSA_LIB build from before the 64-row verify kernel of 16-bit and fp8 caches)
+        lib.fcsa_forward_kvcache_verify.argtypes = [C.POINTER(ForwardArgs), C.POINTER(KvCache), C.POINTER(Varlen), C.POINTER(KvCacheQuant),
+                                                    C.POINTER(TreeMask), C.POINTER(LseOut)]
+        lib.fcsa_forward_kvcache_verify.restype = C.c_int
+        lib.fcsa_forward_kvcache_verify_workspace_bytes.argtypes = [C.POINTER(Problem), C.POINTER(KvCache), C.POINTER(Varlen), C.POINTER(KvCacheQuant)]
+        lib.fcsa_forward_kvcache_verify_workspace_bytes.restype = C.c_size_t
     lib.fcsa_last_error.argtypes = []
     lib.fcsa_last_error.restype = C.c_char_p
     ver = lib.fcsa_debug(None, 0)

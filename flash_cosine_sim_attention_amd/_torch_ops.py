@@ -102,8 +102,9 @@ def _register_fakes():
             return q.new_empty(q.shape), q.new_empty(q.shape[:-1], dtype=torch.float32)
 
     # an MXFP4 cache (namespace fcsa_mx; the engine step: fcsa_mx_step), decode, chunk and step ops alike: the lse is empty unless asked for
+    # (and the 64-row verify op of 16-bit and fp8 caches, namespace fcsa_verify: return_lse is its last argument too)
     for op in ("fcsa_mx::kvcache_mxfp4_forward", "fcsa_mx::kvcache_mxfp4_prefill_forward", "fcsa_mx_step::kvcache_mxfp4_step_forward",
-               "fcsa_mx_tree::kvcache_mxfp4_tree_forward"):
+               "fcsa_mx_tree::kvcache_mxfp4_tree_forward", "fcsa_verify::kvcache_verify_forward"):
         @torch.library.register_fake(op)
         def _(q, *args):
             return q.new_empty(q.shape), q.new_empty(q.shape[:-1] if args[-1] else (0,), dtype=torch.float32)

@@ -1231,27 +1231,45 @@ int mx_tree_supported(const fcsa_problem& p, const fcsa_kvcache_mx& mx) {
     return fail(FCSA_ERR_UNSUPPORTED, "kvcache_mx_tree: dim_head %d is not supported (64 or 128, f16 or bf16: the tree kernel of an MXFP4 cache)", p.dim_head);
   return FCSA_OK;
 }
+// ... and what fcsa_forward_kvcache_verify refuses: the 64-row kernel of a 16-bit or fp8 cache exists for the same problems
+int verify_supported(const fcsa_problem& p) {
+  if (p.dtype == FCSA_F32)
+    return fail(FCSA_ERR_UNSUPPORTED, "kvcache_verify: float32 is not supported (f16 or bf16; fcsa_forward_kvcache_tree takes float32)");
+  if (!has_chunk_kernel(p))
+    return fail(FCSA_ERR_UNSUPPORTED, "kvcache_verify: dim_head %d is not supported (64 or 128; fcsa_forward_kvcache_tree takes the others)", p.dim_head);
+  return FCSA_OK;
+}
+// Without c.mx (fcsa_forward_kvcache_verify): the ragged call's checks, append and combine of a 16-bit or fp8 cache (c.qz) around the 4-wave
+// kernel of fcsa_verify.hip, on the same plan.  c.tree may be absent there: the problem's `causal` then states the visibility.
+constexpr LaunchName kVerifyName[2] = {{"verify", "verify"}, {"verify_fp8", "verify (fp8)"}};
 int verify_call(const DecodeCall& c) {
+  const char* who = c.mx != nullptr ? "kvcache_mx_tree" : "kvcache_verify";
   if (int rc = check_kvcache_varlen(c)) return rc;
   const fcsa_forward_args* a = c.a;
   const fcsa_problem& p = a->p;
-  const DecodeWindow win = decode_window(p, *c.kv, true, nullptr);      // open sides: the words state the visibility
+  const bool fp8 = c.qz != nullptr;
+  const DecodeWindow win = decode_window(p, *c.kv, true, nullptr);      // open sides: the words, or `causal`, state the visibility
   const DecodePlan d = verify_plan(p, *c.kv, *c.seqs);
-  if (d.slots * std::max(p.kv_heads, 1) * d.splits > INT32_MAX) return fail(FCSA_ERR_UNSUPPORTED, "kvcache_mx_tree: grid above 2^31 workgroups");
+  if (d.slots * std::max(p.kv_heads, 1) * d.splits > INT32_MAX) return fail(FCSA_ERR_UNSUPPORTED, "%s: grid above 2^31 workgroups", who);
   if (p.batch == 0 || c.seqs->total_q == 0) return FCSA_OK;      // no packed row: nothing to append, nothing to write
   const bool rows = p.heads > 0;
   if (rows)
-    if (int rc = check_workspace("kvcache_mx_tree", *a, d)) return rc;
+    if (int rc = check_workspace(who, *a, d)) return rc;
   const fcsa::DecodeStepParams dp = decode_params(c, win, d);
   const fcsa::DecodeLseOut lo = c.lse != nullptr ? lse_view(*c.lse, true) : fcsa::DecodeLseOut{};
-  const fcsa::DecodeForm form = {false, true};
+  const fcsa::DecodeForm form = {fp8, true};
   hipStream_t s = static_cast<hipStream_t>(a->stream);
   if (int rc = append_launch(c, form, dp, s)) return rc;
   if (!rows) return FCSA_OK;
-  const fcsa::DecodeMx mx = mx_view(*c.mx);
-  const fcsa::DecodeTreeMask tm = {c.tree->mask};
-  if (int rc = timed("verify_mx", "verify (mxfp4, tree)", s, [&] { return fcsa::launch_verify_mx(p.dtype, p.dim_head, form, dp, mx, tm, s); })) return rc;
-  const LaunchName& m = kCombineName[1][0][c.lse != nullptr];
+  const fcsa::DecodeTreeMask tm = {c.tree != nullptr ? c.tree->mask : nullptr};
+  if (c.mx != nullptr) {
+    const fcsa::DecodeMx mx = mx_view(*c.mx);
+    if (int rc = timed("verify_mx", "verify (mxfp4, tree)", s, [&] { return fcsa::launch_verify_mx(p.dtype, p.dim_head, form, dp, mx, tm, s); })) return rc;
+  } else {
+    const LaunchName& n = kVerifyName[fp8];
+    if (int rc = timed(n.name, n.what, s, [&] { return fcsa::launch_verify(p.dtype, p.dim_head, form, dp, tm, s); })) return rc;
+  }
+  const LaunchName& m = kCombineName[1][fp8][c.lse != nullptr];
   return timed(m.name, m.what, s, [&] { return fcsa::launch_decode_combine(p.dtype, p.dim_head, form, dp, c.lse != nullptr ? &lo : nullptr, s); });
 }
 
@@ -1544,6 +1562,31 @@ int fcsa_forward_kvcache_mx_tree(const fcsa_forward_args* a, const fcsa_kvcache*
 }
 size_t fcsa_forward_kvcache_mx_tree_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv, const fcsa_kvcache_mx* mx, const fcsa_varlen* seqs) {
   if (p == nullptr || kv == nullptr || mx == nullptr || seqs == nullptr || mx_tree_supported(*p, *mx) != FCSA_OK) return 0;
+  return verify_plan(*p, *kv, *seqs).total;
+}
+
+// A verify step, or a short prompt chunk, on a 16-bit or fp8 cache: the ragged call's description with the visibility words where the call
+// has them, on verify_call.  What the 64-row kernel is not compiled for is refused first, and answers a workspace query with 0.
+int fcsa_forward_kvcache_verify(const fcsa_forward_args* a, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_kvcache_quant* qz,
+                                const fcsa_tree_mask* tree, const fcsa_lse_out* lse) {
+  if (a == nullptr || kv == nullptr || seqs == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_verify: null argument");
+  if (int rc = verify_supported(a->p)) return rc;
+  const bool rows = a->p.batch > 0 && a->p.heads > 0 && seqs->total_q > 0;
+  if (tree != nullptr) {
+    if (a->p.causal != 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_verify: causal must be 0 with a mask (the mask states the visibility)");
+    if (tree->reserved != 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_verify: reserved (%lld) is 0", (long long)tree->reserved);
+    if (rows && tree->mask == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_verify: mask: null pointer");
+    if ((reinterpret_cast<uintptr_t>(tree->mask) & 7) != 0) return fail(FCSA_ERR_INVALID_ARG, "kvcache_verify: mask not 8-byte aligned");
+  }
+  if (rows && lse != nullptr && lse->lse == nullptr) return fail(FCSA_ERR_INVALID_ARG, "kvcache_verify: lse: null pointer");
+  // (a mask without rows may be a null pointer: the kernel is not launched then, so it cannot be taken for "no mask")
+  DecodeCall c{a, kv, seqs, qz, nullptr, lse};
+  c.tree = tree;
+  return verify_call(c);
+}
+size_t fcsa_forward_kvcache_verify_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* kv, const fcsa_varlen* seqs, const fcsa_kvcache_quant* qz) {
+  (void)qz;      // (an fp8 cache has the plan of a 16-bit one)
+  if (p == nullptr || kv == nullptr || seqs == nullptr || verify_supported(*p) != FCSA_OK) return 0;
   return verify_plan(*p, *kv, *seqs).total;
 }
 

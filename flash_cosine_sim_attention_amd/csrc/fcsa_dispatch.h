@@ -331,7 +331,8 @@ constexpr int prefill_win_kend(int L, int N, int G, int64_t first, int count, in
 }
 // The verify step of a speculative decoder on an MXFP4 cache (fcsa_forward_kvcache_mx_tree, csrc/fcsa_verify_mx.hip): the same flat slots
 // (prefill_slots, prefill_tile) at 64 token-major rows per workgroup, four waves x one MFMA tile of 16, with the decode kernels' key splits
-// (decode_splits fed the 64-row slot count, decode_window).
+// (decode_splits fed the 64-row slot count, decode_window).  The same plan serves 16-bit and fp8 caches (fcsa_forward_kvcache_verify,
+// csrc/fcsa_verify.hip): no cost model of its own.
 constexpr int kVerifyRows = 64;
 // An engine step (fcsa_forward_kvcache_step): a sequence of N rows takes the chunk kernel iff G * N >= chunk_rows, the decode kernels
 // otherwise.  Both sides evaluate this one function on the N their tile maps give them (ragged_tile, prefill_tile: the same clamped entries).

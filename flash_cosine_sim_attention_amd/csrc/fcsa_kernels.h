@@ -282,6 +282,11 @@ hipError_t launch_prefill_mx_step(int dtype, int D, DecodeForm f, const DecodeSt
 // f16 / bf16, D = 64 / 128, l2norm groups of mx_groups_ok; hipErrorInvalidValue otherwise.  The append before it is launch_kv_append_mx and
 // the combine after it launch_decode_combine's 16-bit ragged one.
 hipError_t launch_verify_mx(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeMx& mx, const DecodeTreeMask& tree, hipStream_t s);
+// The same step on a 16-bit or fp8 cache (fcsa_forward_kvcache_verify; csrc/fcsa_verify.hip): the ragged call's block with the slots and
+// split count above, on the 4-wave kernel that leaves launch_decode's partials.  tree.words may be nullptr: p.causal then states the
+// visibility (with words it must be 0).  f.ragged only (no step form), f.fp8 for an e4m3fn cache, f16 / bf16, D = 64 / 128;
+// hipErrorInvalidValue otherwise.  The append before it is launch_kv_append and the combine after it launch_decode_combine, both unchanged.
+hipError_t launch_verify(int dtype, int D, DecodeForm f, const DecodeStepParams& p, const DecodeTreeMask& tree, hipStream_t s);
 // launch_kv_compact on an MXFP4 cache (fcsa_kvcache_mx_compact): the codes (c.row_bytes = D / 2, a multiple of 16, at most 64) and the
 // scale bytes (one per 16 code bytes) of K and V move together.
 hipError_t launch_kv_compact_mx(const DecodeParams& cache, const DecodeMx& mx, const CompactParams& c, hipStream_t s);

@@ -92,7 +92,10 @@ namespace {
   /* tree attention against an MXFP4 cache, and the compaction of its accepted path */    \
   X(forward_kvcache_mx_tree, fcsa_forward_kvcache_mx_tree, false)                         \
   X(forward_kvcache_mx_tree_ws, fcsa_forward_kvcache_mx_tree_workspace_bytes, false)      \
-  X(kvcache_mx_compact, fcsa_kvcache_mx_compact, false)
+  X(kvcache_mx_compact, fcsa_kvcache_mx_compact, false)                                   \
+  /* the verify step on 16-bit and fp8 caches: 64-row tiles with key splits */            \
+  X(forward_kvcache_verify, fcsa_forward_kvcache_verify, false)                           \
+  X(forward_kvcache_verify_ws, fcsa_forward_kvcache_verify_workspace_bytes, false)
 
 struct Abi {
 #define X(member, symbol, required) decltype(&symbol) member = &symbol;
@@ -776,7 +779,7 @@ Tensor varlen_window_attention_autograd(const Tensor& q, const Tensor& k, const 
 //
 // One description of a call, CacheCall: every op function fills the members it has and hands it to kvcache_call, which runs the checks
 // (cache_checks), fills the library's structs (fill_lib_call) and dispatches through the one table of entry points (kEntries).
-enum class Route { Plain, Prefill, Step, Tree, Alibi, Rotary, Mx, MxPrefill, MxStep, MxTree };
+enum class Route { Plain, Prefill, Step, Tree, Alibi, Rotary, Mx, MxPrefill, MxStep, MxTree, Verify };
 
 struct CacheCall {
   // what every op has
@@ -790,7 +793,7 @@ struct CacheCall {
   bool lse = false;                                       // the rows' log-sum-exp as a second result
   Route route = Route::Plain;
   fcsa_kvcache_step step{};                               // Step, Alibi, Rotary: the routing fields
-  const Tensor* extra = nullptr;                          // Tree, MxTree: tree_mask; Alibi: alibi_slopes; Rotary: rotary_cos
+  const Tensor* extra = nullptr;                          // Tree, MxTree: tree_mask (Verify: or none); Alibi: alibi_slopes; Rotary: rotary_cos
   const Tensor* rotary_sin = nullptr; bool rotary_interleaved = false;      // Rotary
   const Tensor *k_block_scale = nullptr, *v_block_scale = nullptr;          // Mx: the scale bytes of an MXFP4 cache (its codes as uint8 tensors)
   bool ragged() const { return cu_q != nullptr; }
@@ -896,7 +899,7 @@ CacheKeep cache_checks(const CacheCall& c) {
     TORCH_CHECK_VALUE(q.size(0) * std::max<int64_t>(q.size(1), 1) <= INT32_MAX, "heads x packed rows must stay below 2^31");
     k.cu = cu_q.contiguous();
   }
-  if (c.route == Route::Tree || c.route == Route::MxTree) {
+  if (c.route == Route::Tree || c.route == Route::MxTree || (c.route == Route::Verify && c.extra != nullptr)) {
     const Tensor& tree = *c.extra;
     TORCH_CHECK_TYPE(tree.scalar_type() == at::kLong, "tree_mask must be int64, got ", tree.scalar_type());
     same_dev("tree_mask", tree);
@@ -1001,7 +1004,7 @@ struct LibCall {
   fcsa_forward_args a; fcsa_kvcache kv; fcsa_varlen seqs; fcsa_lse_out lo;
   fcsa_kvcache_quant qz; fcsa_tree_mask tree; fcsa_alibi alibi; fcsa_rotary rotary; fcsa_kvcache_mx mx;
   const fcsa_window* win; const fcsa_kvcache_step* step;
-  bool ragged, fp8;
+  bool ragged, fp8, masked;      // masked: the call brings visibility words (they may be no bytes at all: a call without rows)
   const fcsa_kvcache_quant* quant() const { return fp8 ? &qz : nullptr; }
 };
 
@@ -1031,7 +1034,7 @@ void fill_lib_call(LibCall& l, const CacheCall& c, const CacheKeep& k, const Ten
             vs.dim() == 2 ? vs.stride(0) : 0, vs.dim() >= 1 ? vs.stride(-1) : 0};
   }
   if (c.mx()) l.mx = {FCSA_CACHE_MXFP4, strided(*c.k_block_scale), strided(*c.v_block_scale)};
-  if (k.words.defined()) l.tree.mask = reinterpret_cast<const uint64_t*>(k.words.data_ptr<int64_t>());
+  if (k.words.defined()) { l.masked = true; l.tree.mask = reinterpret_cast<const uint64_t*>(k.words.data_ptr<int64_t>()); }
   if (k.slopes.defined()) {
     l.alibi.slopes = k.slopes.data_ptr<float>();
     l.alibi.stride_b = k.slopes.dim() == 2 ? k.slopes.stride(0) : 0;
@@ -1051,7 +1054,7 @@ struct EntryPoint {
   size_t (*workspace)(const LibCall&);      // null: that of the call without the lse
   int (*run)(const LibCall&);
 };
-enum Entry { kKvcache, kWindow, kQuant, kVarlen, kLse, kPrefill, kStep, kTree, kAlibi, kRotary, kMx, kMxPrefill, kMxStep, kMxTree };
+enum Entry { kKvcache, kWindow, kQuant, kVarlen, kLse, kPrefill, kStep, kTree, kAlibi, kRotary, kMx, kMxPrefill, kMxStep, kMxTree, kVerify };
 const EntryPoint kEntries[] = {
     /* kKvcache */ {"fcsa_forward_kvcache", "flash_cosine_sim_attention_with_kvcache",
                     [] { return g_abi.forward_kvcache != nullptr && g_abi.forward_kvcache_ws != nullptr; },
@@ -1105,19 +1108,25 @@ const EntryPoint kEntries[] = {
      [] { return g_abi.forward_kvcache_mx_tree != nullptr && g_abi.forward_kvcache_mx_tree_ws != nullptr; },
      [](const LibCall& l) { return g_abi.forward_kvcache_mx_tree_ws(&l.a.p, &l.kv, &l.mx, &l.seqs); },
      [](const LibCall& l) { return g_abi.forward_kvcache_mx_tree(&l.a, &l.kv, &l.mx, &l.seqs, l.win, &l.tree, l.lo.lse != nullptr ? &l.lo : nullptr); }},
+    /* kVerify: ragged only, the same plan; the words where the call has them */ {"fcsa_forward_kvcache_verify", "flash_cosine_sim_attention_verify_with_kvcache",
+     [] { return g_abi.forward_kvcache_verify != nullptr && g_abi.forward_kvcache_verify_ws != nullptr; },
+     [](const LibCall& l) { return g_abi.forward_kvcache_verify_ws(&l.a.p, &l.kv, &l.seqs, l.quant()); },
+     [](const LibCall& l) {
+       return g_abi.forward_kvcache_verify(&l.a, &l.kv, &l.seqs, l.quant(), l.masked ? &l.tree : nullptr, l.lo.lse != nullptr ? &l.lo : nullptr);
+     }},
 };
 
 // the entry point of a Plain call without the lse: by the ragged / fp8 / window facts
 Entry plain_entry(const CacheCall& c) { return c.ragged() ? kVarlen : c.fp8() ? kQuant : c.win != nullptr ? kWindow : kKvcache; }
-constexpr Entry kOfRoute[] = {kKvcache /* Plain: by the facts instead */, kPrefill, kStep, kTree, kAlibi, kRotary, kMx, kMxPrefill, kMxStep, kMxTree};      // in Route's order
-static_assert(sizeof(kEntries) / sizeof(kEntries[0]) == kMxTree + 1 && sizeof(kOfRoute) / sizeof(kOfRoute[0]) == (int)Route::MxTree + 1,
+constexpr Entry kOfRoute[] = {kKvcache /* Plain: by the facts instead */, kPrefill, kStep, kTree, kAlibi, kRotary, kMx, kMxPrefill, kMxStep, kMxTree, kVerify};      // in Route's order
+static_assert(sizeof(kEntries) / sizeof(kEntries[0]) == kVerify + 1 && sizeof(kOfRoute) / sizeof(kOfRoute[0]) == (int)Route::Verify + 1,
               "kEntries has one row per Entry, in its order, and kOfRoute one entry per Route");
 Entry entry_of(const CacheCall& c) { return c.route != Route::Plain ? kOfRoute[(int)c.route] : c.lse ? kLse : plain_entry(c); }
 // a call needs its own entry point and those of the calls it is built on
 void need_entries(const CacheCall& c, Entry own) {
   auto need = [](Entry e) { need_abi(kEntries[e].who, kEntries[e].symbol, kEntries[e].present()); };
   if (c.route != Route::Plain) need(own);
-  if (c.lse && !c.mx()) need(kLse);
+  if (c.lse && !c.mx() && c.route != Route::Verify) need(kLse);
   if (c.ragged()) need(kVarlen);
   need(kKvcache);
   if (c.fp8()) need(kQuant);
@@ -1397,6 +1406,25 @@ std::tuple<Tensor, Tensor> kvcache_tree_forward(const Tensor& q, const Tensor& k
   set_scales(c, k_scale, v_scale);
   c.cu_q = &cu_seqlens_q; c.max_seqlen_q = max_seqlen_q; c.lse = true; c.route = Route::Tree; c.extra = &tree_mask;
   return kvcache_call(c);
+}
+
+// A verify step, or a short prompt chunk, on the 64-row kernel with key splits (kvcache_verify_forward): kvcache_tree_forward's call through
+// fcsa_forward_kvcache_verify.  tree_mask may be absent -- `causal` then states the visibility, as on kvcache_varlen_forward without a window.
+std::tuple<Tensor, Tensor> kvcache_verify_forward(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& cu_seqlens_q,
+                                                  const optional<Tensor>& tree_mask, const optional<Tensor>& k_new, const optional<Tensor>& v_new,
+                                                  const optional<Tensor>& cache_seqlens, const optional<Tensor>& block_table,
+                                                  const optional<Tensor>& k_scale, const optional<Tensor>& v_scale, int64_t max_seqlen_q,
+                                                  int64_t max_seqlen_k, double scale, bool causal, bool l2norm_qk, int64_t groups, bool return_lse) {
+  CacheCall c{q, k_cache, v_cache, k_new, v_new, cache_seqlens, block_table, max_seqlen_k, scale, causal, l2norm_qk, groups};
+  set_scales(c, k_scale, v_scale);
+  c.cu_q = &cu_seqlens_q; c.max_seqlen_q = max_seqlen_q; c.lse = return_lse; c.route = Route::Verify; c.extra = ptr(tree_mask);
+  TORCH_CHECK_VALUE(!(causal && tree_mask.has_value()), "causal=True with a tree_mask: the mask states the visibility");
+  TORCH_CHECK_TYPE(q.scalar_type() == at::kHalf || q.scalar_type() == at::kBFloat16, "the 64-row verify kernel takes float16 or bfloat16, got ",
+                   q.scalar_type(), " (flash_cosine_sim_attention_tree_with_kvcache takes float32)");
+  TORCH_CHECK_VALUE(q.dim() != 3 || q.size(-1) == 64 || q.size(-1) == 128, "the 64-row verify kernel takes head dimensions 64 and 128, got ", q.size(-1),
+                    " (flash_cosine_sim_attention_tree_with_kvcache takes the others)");
+  auto [o, lse] = kvcache_call(c);
+  return {o, return_lse ? lse : at::empty({0}, q.options().dtype(at::kFloat))};
 }
 
 // kvcache_keep_accepted: the rows cache_seqlens[b] + accepted[b, i] of both caches move to cache_seqlens[b] + i (i < num_accepted[b]), in
@@ -1937,6 +1965,15 @@ TORCH_LIBRARY_IMPL(fcsa_mx_tree, CUDA, m) {
   m.impl("kvcache_mxfp4_tree_forward", &kvcache_mxfp4_tree_forward);
   m.impl("kvcache_mxfp4_compact", &kvcache_mxfp4_compact);
 }
+
+// the verify step on 16-bit and fp8 caches (64-row tiles with key splits), in a namespace of its own (the op set of fcsa_tree is pinned).
+// Forward only: no Autograd kernel.
+TORCH_LIBRARY(fcsa_verify, m) {
+  m.def("kvcache_verify_forward(Tensor q, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor cu_seqlens_q, Tensor? tree_mask, Tensor? k_new, "
+        "Tensor? v_new, Tensor? cache_seqlens, Tensor? block_table, Tensor? k_scale, Tensor? v_scale, int max_seqlen_q, int max_seqlen_k, "
+        "float scale, bool causal, bool l2norm_qk, int groups, bool return_lse) -> (Tensor, Tensor)");
+}
+TORCH_LIBRARY_IMPL(fcsa_verify, CUDA, m) { m.impl("kvcache_verify_forward", &kvcache_verify_forward); }
 
 // the engine step against an MXFP4 cache, in a namespace of its own (the op set of fcsa_mx is pinned).  Forward only: no Autograd kernel.
 TORCH_LIBRARY(fcsa_mx_step, m) {

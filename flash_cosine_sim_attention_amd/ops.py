@@ -1293,6 +1293,58 @@ def flash_cosine_sim_attention_tree_with_kvcache(q, k_cache, v_cache, cu_seqlens
                         cpu_kw=dict(scale=scale, groups=groups, l2norm_qk=l2norm_qk, tree_mask=tree_mask))
 
 
+def flash_cosine_sim_attention_verify_with_kvcache(q, k_cache, v_cache, cu_seqlens_q, k_new=None, v_new=None, cache_seqlens=None,
+                                                   block_table=None, max_seqlen_q=None, max_seqlen_k=None, scale=8, groups=1, causal=False,
+                                                   l2norm_qk=True, k_scale=None, v_scale=None, return_lse=False, window_size=(-1, -1),
+                                                   tree_mask=None):
+    """The verify step of a speculative decoder, or a short prompt chunk, on a kernel built for its shape: the arguments, semantics and
+    results of `flash_cosine_sim_attention_tree_with_kvcache`, for float16 / bfloat16 q at dim_head 64 or 128 against float16, bfloat16 or
+    float8_e4m3fn caches.
+
+    A verify step brings N_b = 8 ... 64 tokens per sequence, G * N_b = 32 ... 256 rows per K/V head, against a long cache.  The tree and
+    ragged calls give every 16 of those rows a one-wave workgroup that re-reads and re-normalises every key; this call gives every 64 rows
+    (token-major, so the heads of a token share its word) a four-wave workgroup per key split, which normalises each 64-key stage once
+    and shares it through LDS.  Per wave and 32-key block the arithmetic is the decode kernel's in its order, and the append before and
+    the combine after are the ragged call's.
+    tree_mask: as on the tree call -- with it the result is that call's.  tree_mask=None still runs this kernel (unlike the tree call) and
+    the result is `flash_cosine_sim_attention_varlen_with_kvcache`'s, causal (bottom-right) or not: the call for 64 ... 256 prompt tokens
+    per sequence on a long cache, where the 128-row prefill kernel has too few workgroups because it cannot split the keys.  The caches
+    after the append are those calls' bit for bit, o and lse bit for bit where both plan one key split and to rounding otherwise.
+    Refused: causal=True with a mask, a window_size other than (-1, -1) (ValueError); float32 q and dim_head other than 64 / 128 (the tree
+    call takes them); torch.uint8 caches (`flash_cosine_sim_attention_mxfp4_tree_with_kvcache` reads MXFP4 caches); a 4-D q.  Everything
+    else combines as on the tree call: paged and strided caches, fp8 caches with k_scale / v_scale, return_lse, k_new=None, device tables
+    without synchronisation, graph capture, sequences without rows.  CPU tensors take the tree call's CPU path."""
+    fn = "flash_cosine_sim_attention_verify_with_kvcache"
+    window, _, _ = _step_arguments(return_lse, window_size)
+    if q.dim() != 3:
+        raise ValueError(f"{fn} takes packed queries [total_q, heads, dim_head] with cu_seqlens_q, got q {tuple(q.shape)} "
+                         "(equal N: cu_seqlens_q = arange(B + 1) * N)")
+    if causal and tree_mask is not None:
+        raise ValueError("tree_mask states the visibility of the step's tokens: causal=True cannot be given with it")
+    if window != (-1, -1):
+        raise ValueError(f"{fn} takes no sliding window (window_size {tuple(window_size)})")
+    if torch.uint8 in (k_cache.dtype, v_cache.dtype):
+        raise TypeError(f"{fn} does not take torch.uint8 caches: MXFP4 caches are read by flash_cosine_sim_attention_mxfp4_tree_with_kvcache")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError(f"{fn} takes float16 or bfloat16 q at dim_head 64 or 128, got {q.dtype} (flash_cosine_sim_attention_tree_with_kvcache "
+                        "takes float32)")
+    if q.shape[-1] not in (64, 128):
+        raise ValueError(f"{fn} takes dim_head 64 or 128, got {q.shape[-1]} (flash_cosine_sim_attention_tree_with_kvcache takes the others)")
+    if tree_mask is not None:
+        if not isinstance(tree_mask, torch.Tensor) or tree_mask.dtype != torch.int64:
+            raise TypeError(f"tree_mask must be an int64 tensor of shape [total_q], got {getattr(tree_mask, 'dtype', type(tree_mask).__name__)}")
+        if tuple(tree_mask.shape) != (q.shape[0],):
+            raise ValueError(f"tree_mask must have shape [{q.shape[0]}] (one word per packed query row), got {tuple(tree_mask.shape)}")
+        if tree_mask.device != q.device:
+            raise ValueError(f"tree_mask is on {tree_mask.device} but q is on {q.device}")
+    op = lambda s: torch.ops.fcsa_verify.kvcache_verify_forward(q, s.k_cache, s.v_cache, s.cu_q, tree_mask, k_new, v_new, s.cache_seqlens,
+                                                                s.block_table, s.k_scale, s.v_scale, s.max_q, s.max_k, float(scale), bool(causal),
+                                                                bool(l2norm_qk), int(groups), bool(return_lse))
+    return _packed_call(fn, q, k_cache, v_cache, cu_seqlens_q, k_new, v_new, cache_seqlens, block_table, max_seqlen_q, max_seqlen_k, k_scale,
+                        v_scale, return_lse=return_lse, window=window, op=op,
+                        cpu_kw=dict(scale=scale, groups=groups, causal=causal, l2norm_qk=l2norm_qk, tree_mask=tree_mask))
+
+
 def kvcache_keep_accepted(k_cache, v_cache, cache_seqlens, accepted, num_accepted, block_table=None):
     """Moves the accepted path of a tree step to the front of the slots the step appended, in place.  Returns None.
 

@@ -630,6 +630,32 @@ int    fcsa_kvcache_mx_compact(const fcsa_kvcache* cache, const fcsa_kvcache_mx*
                                const int32_t* accepted, int64_t accepted_stride, int32_t max_accepted, const int32_t* num_accepted,
                                void* stream);
 
+/* The verify step of a speculative decoder, or a short prompt chunk, against a float16 / bfloat16 / fp8 cache on 64-row tiles with key splits:
+ * fcsa_forward_kvcache_tree's arguments on a kernel built for G * N_b = 32 ... 256 rows per K/V head (additive: no existing struct changes
+ * and FCSA_ABI_VERSION stays 4).
+ * args, cache, seqs, quant, tree and lse_out are read as fcsa_forward_kvcache_tree reads them (seqs NULL: FCSA_ERR_INVALID_ARG), with its
+ * checks, append (quantising with quant), clamping of lengths, table entries and block ids, both exponent regimes and its visibility rule
+ * -- except that tree may be NULL: the call is then fcsa_forward_kvcache_varlen's without a window, p.causal bottom-right aligned or none.
+ *   p.dtype   : FCSA_F16 or FCSA_BF16 (FCSA_F32: FCSA_ERR_UNSUPPORTED; fcsa_forward_kvcache_tree takes it)
+ *   p.dim_head: 64 or 128 (anything else: FCSA_ERR_UNSUPPORTED; fcsa_forward_kvcache_tree takes the others)
+ *   p.causal  : with tree, 0 (the mask states the visibility; anything else: FCSA_ERR_INVALID_ARG); without, 0 or 1
+ *   tree      : NULL, or as on fcsa_forward_kvcache_tree: tree->mask NULL (with rows to compute) or not 8-byte aligned, reserved != 0:
+ *               FCSA_ERR_INVALID_ARG
+ *   workspace : >= fcsa_forward_kvcache_verify_workspace_bytes() bytes for the same arguments, 256-byte aligned (0 for a call refused as
+ *               unsupported)
+ * The kernel: one 4-wave workgroup per (64-row tile slot, K/V head, key split), rows token-major; a 64-key stage of the split's key range is
+ * normalised and rounded once per workgroup and shared through LDS, and per wave and 32-key block the arithmetic is the decode kernel's in
+ * its order.  The split count is the decode split rule on the 64-row slot count.  So o, lse and the caches are those of
+ * fcsa_forward_kvcache_tree (with tree) or fcsa_forward_kvcache_varlen / _lse (without) -- the caches always bit for bit, o and lse bit for
+ * bit where both calls run one key split, to rounding otherwise.
+ * Device tables and the words are never read by the host: the call does not synchronise and can be captured in a graph.  Every refusal
+ * happens before any launch.  Launches: "kv_append_ragged[_fp8]" (when appending), "verify" or "verify_fp8",
+ * "decode_combine[_lse]_ragged[_fp8]". */
+int    fcsa_forward_kvcache_verify(const fcsa_forward_args* args, const fcsa_kvcache* cache, const fcsa_varlen* seqs,
+                                   const fcsa_kvcache_quant* quant, const fcsa_tree_mask* tree, const fcsa_lse_out* lse_out);
+size_t fcsa_forward_kvcache_verify_workspace_bytes(const fcsa_problem* p, const fcsa_kvcache* cache, const fcsa_varlen* seqs,
+                                                   const fcsa_kvcache_quant* quant);
+
 /* The same linear position bias in the training kernels, forward and backward: fcsa_forward_window / fcsa_backward_window with one more
  * argument, the slopes (additive: no existing struct changes and FCSA_ABI_VERSION stays 4).  A model trained through these entries is
  * served unchanged by fcsa_forward_kvcache_alibi: the definition is the same.
